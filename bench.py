@@ -37,8 +37,19 @@ Both are measured in every multi-GPU run; the one not selected is reported under
 Inputs are resident in HBM when the timed region starts; data is synthetic (seeded PRNG).
 
 The timed region is EXACTLY K steps between two fences (barrier + device synchronisation); it is repeated --repeats
-times (default 5) inside the one command and `value` is the MEDIAN block (`value_min` / `value_max` beside it): one
-block of 20 steps is 11 ms, and box-to-box noise is larger than any round's gain.
+times inside the one command and `value` is the MEDIAN block (`value_min` / `value_max` beside it): one block of 20
+steps is 11 ms, and box-to-box noise is larger than any round's gain.
+
+A plain run does only what the headline needs: set up, W warm-up steps, ONE timed block of exactly K steps (--repeats
+defaults to 1), the outputs of --dump-outputs, the JSON line (metric, value, unit, ms_per_step, ...).  --full adds
+everything else, as before: --repeats 5 by default, the second leg without the per-step read (`value_async`) with the
+rollout kernel's time and the roofline / VALU views, the final reward of complete plans, the extra sizes, the CPU
+baseline with `parity` / `parity_jax`, and with G > 1 ranks the other scaling, the other collective and the phases.
+
+--dump-outputs DIR writes what the timed path computed in its LAST timed step, as a caller of that step receives it
+(rank 0; float32 .npy): ybar.npy (Ybar_{i-1}, [H, Nu]), rew_mean.npy (the step's mean reward as the host read it, [1]),
+rewards.npy (the step's per-candidate rewards of this rank's shard, [N/G]; with enable_demo also demo_logp.npy).
+sweep8: ybar.npy [P, H, Nu] and rew_mean.npy [P] of every plan's last step.  Same arguments, same inputs (seeded).
 """
 import argparse
 import contextlib
@@ -441,6 +452,58 @@ def whole_run_parity(traj, gpu_details, gpu_rew_final):
     return out
 
 
+def build_or_load(entry):
+    """build(): serialised across ranks by a lock file in the library's directory, a no-op when the library is fresh.  A
+    tree built by another user cannot be written here, not even that lock file: its library is then loaded as that build
+    left it (load() raises when there is none — the tree's own native code or nothing)."""
+    import errno
+    try:
+        entry.build()
+    except OSError as e:
+        if e.errno not in (errno.EACCES, errno.EPERM, errno.EROFS):
+            raise
+        from mbd_hip import _capi
+        print(f"[bench] {e.filename}: {e.strerror}: the tree is not writable, running its library as built", file=sys.stderr)
+        _capi.load()
+
+
+# the canary's entry with this rank's device as the process group's dry run maps it (LOCAL_RANK modulo the visible devices)
+_CANARY = ("import sys, torch\n"
+           "from mbd_hip.planners import exchange_canary\n"
+           "sys.argv[3] = str(int(sys.argv[3]) % max(torch.cuda.device_count(), 1))\n"
+           "exchange_canary.main()\n")
+
+
+def early_canary(dist, rank, world, local_rank):
+    """A canary for the in-library exchange: one short-lived process per rank maps the peers' windows and runs a few
+    exchanges with known values (mbd_hip.planners.exchange_canary).  Peer stores into mapped memory are what ends in an
+    uncatchable GPU fault when a node's peer access is not what the code assumes — that must cost a canary, not this
+    process and its RCCL measurement.  It runs BEFORE this process opens the GPU, so that a rank and its canary never hold
+    the device at the same time (G ranks dry-running on one device open it G times, not 2 G).  The rendezvous is the
+    process group's own store, which the caller hands to init_process_group.  Every rank learns the worst exit status.
+    Returns (store, (worst status, this rank's status, the tail of its stderr))."""
+    import shutil
+    import subprocess
+    import tempfile
+    store = next(dist.rendezvous("env://"))[0]
+    # a FRESH rendezvous directory per run (rank 0 makes it, everybody learns its name): files of a crashed earlier
+    # run — stale IPC handles, stale barrier files — can never be read
+    if rank == 0:
+        store.set("mbd_canary_rdv", tempfile.mkdtemp(prefix="mbd_canary_"))
+    rdv = store.get("mbd_canary_rdv").decode()
+    try:
+        cp = subprocess.run([sys.executable, "-c", _CANARY, str(rank), str(world), str(local_rank), rdv],
+                            cwd=os.path.join(ROOT, "model-based-diffusion_amd"), capture_output=True, text=True, timeout=240)
+        rc, err = cp.returncode, cp.stderr[-300:]
+    except Exception as e:  # noqa: BLE001
+        rc, err = 99, f"{type(e).__name__}: {e}"
+    store.set(f"mbd_canary_rc{rank}", str(abs(rc)))
+    worst = max(int(store.get(f"mbd_canary_rc{r}")) for r in range(world))
+    if rank == 0:  # (every canary has exited: every rank has posted its status)
+        shutil.rmtree(rdv, ignore_errors=True)
+    return store, (worst, rc, err)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -448,8 +511,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="metric")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed blocks of exactly --steps steps each (fenced on both sides); `value` is the median block")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of exactly --steps steps each (fenced on both sides); `value` is the median block "
+                         "(default 1; 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline (see the module docstring); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-final-reward", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
@@ -459,6 +527,8 @@ def main():
                     help="N > 1: the step's exchange — torch (all_gather_into_tensor: RCCL over xGMI), p2p (the in-library "
                          "windows, mbd_exchange_*), both (torch is `value`, p2p is measured after it and reported beside)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     cfg = dict(CONFIGS[args.config], name=args.config)
     ENV, N_CFG, H, ND, TEMP, DEMO = cfg["env"], cfg["N"], cfg["H"], cfg["Nd"], cfg["temp"], cfg["demo"]
     if os.environ.get("MBD_BENCH_N"):  # experiments only
@@ -474,20 +544,26 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    __graft_entry__.build()  # serialised across ranks by a file lock; a no-op when the library is fresh
+    build_or_load(__graft_entry__)
     # MBD_FORCE_DIST=1: take the multi-rank code path (RCCL init, all-gather, barrier, max-reduce) with ONE rank —
     # what the single-GPU test box can exercise of it (tests/test_gpu_parity.py)
     distributed = world > 1 or os.environ.get("MBD_FORCE_DIST") == "1"
     backend = os.environ.get("MBD_DIST_BACKEND", "nccl")  # "gloo": 2-rank dry runs on a single-GPU box
+    is_sweep = "plans" in cfg
+    # --full with G > 1 ranks measures the other collective too: its canary runs first, before this process opens the GPU
+    pg_kw, canary = {}, None
+    if args.full and distributed and world > 1 and args.collective == "both" and not is_sweep:
+        store, canary = early_canary(dist, rank, world, local_rank)
+        pg_kw = dict(store=store, rank=rank, world_size=world)
     n_dev = torch.cuda.device_count()
     if distributed:
         if backend == "nccl":
             assert n_dev >= world, f"{world} ranks need {world} GPUs, found {n_dev}"
             torch.cuda.set_device(local_rank)
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank), **pg_kw)
         else:
             local_rank = local_rank % max(n_dev, 1)
-            dist.init_process_group(backend)
+            dist.init_process_group(backend, **pg_kw)
         dist.barrier()
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}: launch through torch.distributed.run"
     # the ranks the COLLECTIVE LIBRARY actually joined: a sum of ones through the process group itself (RCCL over xGMI with
@@ -547,7 +623,9 @@ def main():
             keys.append(_capi.prng_split(rng, 2)[0])  # rng_exp (:150)
         return np.array(keys, np.uint32), states
 
-    def measure_sweep(seeds, steps=None, warmup=None, repeats=None, local=False):
+    outputs = {}  # --dump-outputs: what the last timed step computed
+
+    def measure_sweep(seeds, steps=None, warmup=None, repeats=None, local=False, capture=False):
         """config sweep8: blocks of K lockstep diffusion steps of the plans with these seeds (mbd_sweep_run with
         Ndiffuse = K + 1, no host outputs: the timed region is the K steps and nothing else).  No per-step host read: the
         reference's sweep prints nothing per step either (not_render runs of run_diffusion keep their progress bar, but
@@ -588,10 +666,15 @@ def main():
                     continue
                 fence()
                 blocks.append(max_over_ranks(time.perf_counter() - t0))
-            sw.kernel_time(enable=True)
-            sw.run(keys, outputs=False)
-            torch.cuda.synchronize(dev)
-            kern_ms, kern_n = sw.kernel_time(enable=False)
+            kern_ms, kern_n = 0.0, 0
+            if args.full:
+                sw.kernel_time(enable=True)
+                sw.run(keys, outputs=False)
+                torch.cuda.synchronize(dev)
+                kern_ms, kern_n = sw.kernel_time(enable=False)
+            if capture:  # every run is the same K steps from the same keys and states: one more, with its outputs
+                mu, rm, _, _ = sw.run(keys, outputs=True)
+                outputs.update(ybar=mu[:, -1], rew_mean=rm[:, -1])
         finally:
             sw.close()
         return blocks, kern_ms, kern_n, own
@@ -600,8 +683,9 @@ def main():
         return [Args(seed=int(sd), env_name=ENV, Nsample=N_CFG, Hsample=H, Ndiffuse=ND, temp_sample=TEMP,
                      disable_recommended_params=True, not_render=True) for sd in seeds]
 
-    def measure(N_total, N_local, collective="torch"):
-        """K synced + K async steps of a plan with N_total candidates of which this rank owns N_local."""
+    def measure(N_total, N_local, collective="torch", capture=False):
+        """K synced (+ with --full K async) steps of a plan with N_total candidates of which this rank owns N_local.
+        capture: keep the outputs of the last synced step in `outputs`."""
         pargs = Args(seed=0, env_name=ENV, Nsample=N_total, Hsample=H, Ndiffuse=ND, temp_sample=TEMP,
                      enable_demo=DEMO, disable_recommended_params=True, not_render=True)
         key = _capi.prng_key(pargs.seed)
@@ -620,7 +704,7 @@ def main():
         # the per-step host read (mbd_planner.py:147) without a stream synchronisation: the score kernel stores the
         # step's mean reward into a pinned host slot and the host spins on it (mbd_hip HostProgress)
         host = HostProgress(1, dev)
-        st = {"rng": np.asarray(rng_exp, np.uint32), "i": ND - 1, "Ybar": Ybar, "Ynext": Ynext}
+        st = {"rng": np.asarray(rng_exp, np.uint32), "i": ND - 1, "Ybar": Ybar, "Ynext": Ynext, "capture": False}
         p2p = None
         if distributed and collective == "p2p":
             from mbd_hip.planners.mbd_planner import P2PExchange
@@ -671,6 +755,8 @@ def main():
                                                   host.ptr(0) if read_back else p_rewmean, stream))
             st["Ybar"], st["Ynext"] = st["Ynext"], st["Ybar"]
             st["i"] = i - 1
+            if st["capture"]:  # --dump-outputs, last timed step: copies on the step's stream, before prepare() may zero Ybar
+                st["out"] = (st["Ybar"].clone(), local.clone())
             prepare()
             if read_back:  # pbar.set_postfix({"rew": f"{rew:.2e}"}) (mbd_planner.py:147): the host has the step's
                 return host.wait(0)  # mean reward in hand before it dispatches the next step
@@ -689,20 +775,29 @@ def main():
             # moves them (experiments).
             ev_mode = os.environ.get("MBD_BENCH_EVENTS", "async")
             plan.enable_timing(ev_mode == "all" or (ev_mode == "async" and not read_back))
-            blocks = []
-            for _ in range(args.repeats):  # R blocks of exactly K steps, each fenced on both sides
+            blocks, rm = [], None
+            cap_block = args.repeats - 1 if (capture and read_back) else -1
+            for b in range(args.repeats):  # R blocks of exactly K steps, each fenced on both sides
                 fence()
                 t0 = time.perf_counter()
-                for _ in range(args.steps):
-                    step(read_back)
+                for k in range(args.steps):
+                    st["capture"] = b == cap_block and k == args.steps - 1
+                    rm = step(read_back)
                 fence()
                 blocks.append(max_over_ranks(time.perf_counter() - t0))
+            st["capture"] = False
             plan.enable_timing(False)
             kern_ms, kern_n = plan.kernel_time()
+            if "out" in st:
+                y, loc = st.pop("out")
+                outputs.update(ybar=y.view(H, Nu).cpu().numpy(), rew_mean=np.array([rm], np.float32),
+                               rewards=loc[0].cpu().numpy())
+                if DEMO:
+                    outputs["demo_logp"] = loc[1].cpu().numpy()
             return blocks, kern_ms, kern_n
 
         sync = timed(True)
-        asyn = timed(False)
+        asyn = timed(False) if args.full else None
         if p2p is not None:
             p2p.status()
             p2p.close()
@@ -716,8 +811,8 @@ def main():
     runs = {"strong": (strong_local * world, strong_local)}
     if world > 1:
         runs["weak"] = (N_CFG * world, N_CFG)
-    is_sweep = "plans" in cfg
     sweep_plans = {}
+    dump = bool(args.dump_outputs)
     if is_sweep:
         # the reference's only timing protocol (scripts/run_mbd.py:17-39): independent plans -> REPLICAS over the ranks,
         # no communication inside a run.  strong: the sweep's P plans over the G GPUs (seeds r*P/G ...: at G = P one plan
@@ -730,52 +825,36 @@ def main():
             sweep_plans["weak"] = list(range(rank * P, (rank + 1) * P))
         res = {}
         for k, seeds in sweep_plans.items():
-            blocks, kms, kn, own = measure_sweep(seeds)
-            res[k] = (blocks, blocks, kms, kn, own)
+            if k == args.scaling or args.full:
+                blocks, kms, kn, own = measure_sweep(seeds, capture=dump and k == args.scaling)
+                res[k] = (blocks, blocks, kms, kn, own)
     else:
         main_coll = "p2p" if args.collective == "p2p" else "torch"
         res = {}
         for k, v in runs.items():
-            if k == args.scaling or world > 1:
-                (bs, _, _), (ba, kms, kn) = sy, asy = measure(*v, collective=main_coll)
+            if k == args.scaling or (world > 1 and args.full):
+                sy, asy = measure(*v, collective=main_coll, capture=dump and k == args.scaling)
+                if asy is None:  # (a plain run: the headline leg only)
+                    res[k] = (sy[0], None, 0.0, 0, None)
+                    continue
+                (bs, _, _), (ba, kms, kn) = sy, asy
                 if kn == 0:  # MBD_BENCH_EVENTS=all / none
                     kms, kn = sy[1], sy[2]
                 res[k] = (bs, ba, kms, kn, None)
     if args.scaling not in res:  # one GPU, --scaling weak: the same measurement
         res[args.scaling] = res["strong"]
+    if dump and rank == 0:  # (before anything else runs on the GPU: what the timed path computed, nothing after it)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in outputs.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.ascontiguousarray(arr, np.float32))
     # the other collective, after the headline measurement and guarded: a failure here (a peer that cannot map a
-    # window, a wait that runs into its limit) is reported, it never costs the line its `value`
+    # window, a wait that runs into its limit) is reported, it never costs the line its `value`.  Its canary ran before
+    # this process opened the GPU (early_canary)
     other_coll = None
-    if distributed and world > 1 and args.collective == "both" and not is_sweep:
-        # a canary first: one short-lived process per rank maps the peers' windows and runs a few exchanges with known
-        # values (mbd_hip.planners.exchange_canary).  Peer stores into mapped memory are what ends in an uncatchable GPU
-        # fault when a node's peer access is not what the code assumes — that must cost a canary, not this process and
-        # its RCCL measurement.  Every rank learns the worst exit status before anybody goes on.
-        import shutil
-        import subprocess
-        import tempfile
-        # a FRESH rendezvous directory per run (rank 0 makes it, everybody learns its name): files of a crashed earlier
-        # run — stale IPC handles, stale barrier files — can never be read
-        box = [tempfile.mkdtemp(prefix="mbd_canary_") if rank == 0 else None]
-        dist.broadcast_object_list(box, src=0)
-        rdv = box[0]
-        try:
-            try:
-                cp = subprocess.run([sys.executable, "-m", "mbd_hip.planners.exchange_canary", str(rank), str(world),
-                                     str(local_rank), rdv], cwd=os.path.join(ROOT, "model-based-diffusion_amd"),
-                                    capture_output=True, text=True, timeout=240)
-                canary_rc, canary_err = cp.returncode, cp.stderr[-300:]
-            except Exception as e:  # noqa: BLE001
-                canary_rc, canary_err = 99, f"{type(e).__name__}: {e}"
-            worst = torch.tensor([abs(canary_rc)], dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
-            dist.all_reduce(worst, op=dist.ReduceOp.MAX)
-        finally:
-            if rank == 0:
-                shutil.rmtree(rdv, ignore_errors=True)
-        if int(worst.item()) != 0:
-            other_coll = {"collective": "p2p", "error": f"canary failed (worst exit status {int(worst.item())}; rank {rank}: "
-                                                            f"{canary_rc} {canary_err.strip()[-200:]})"}
-    if distributed and world > 1 and args.collective == "both" and not is_sweep and other_coll is None:
+    if canary is not None and canary[0] != 0:
+        other_coll = {"collective": "p2p", "error": f"canary failed (worst exit status {canary[0]}; rank {rank}: "
+                                                    f"{canary[1]} {canary[2].strip()[-200:]})"}
+    if canary is not None and other_coll is None:
         try:
             (ocs, _, _), (oca, okms, _) = measure(*runs[args.scaling], collective="p2p")
             other_coll = {"collective": "p2p (mbd_exchange_*: hipIpc-mapped windows, peer stores + epoch flags)",
@@ -790,7 +869,7 @@ def main():
     # where a sharded step's time goes: HIP events around phase 1 (sample + rollout), the exchange and phase 2 (score +
     # weighted mean) of a whole plan, each phase fenced (measurement only; run_diffusion(measure_phases=True))
     phase_ms = None
-    if distributed and not is_sweep:
+    if args.full and distributed and not is_sweep:
         a = Args(seed=0, env_name=ENV, Nsample=runs[args.scaling][0], Hsample=H, Ndiffuse=min(ND, 30), temp_sample=TEMP,
                  enable_demo=DEMO, disable_recommended_params=True, not_render=True)
         with contextlib.redirect_stdout(sys.stderr):
@@ -799,7 +878,7 @@ def main():
         phase_ms = det["phase_ms"]
 
     final = None
-    if not args.no_final_reward and is_sweep:
+    if args.full and not args.no_final_reward and is_sweep:
         # the sweep's second half: rew_final of the COMPLETE plans (Ndiffuse of the config), every rank its own seeds in one
         # sweep, gathered once at the end; rank 0 then runs all of them as ONE sweep on its GPU — plans are independent,
         # the two must agree bit for bit
@@ -814,7 +893,7 @@ def main():
             final["replicated_over"] = world
             final["equals_one_gpu_bitwise"] = bool(np.array_equal(np.float32(rews), np.float32(single)))
             final["rew_final_one_gpu"] = single
-    elif not args.no_final_reward and (rank == 0 or distributed):
+    elif args.full and not args.no_final_reward and (rank == 0 or distributed):
         # the metric's second half: final reward of complete plans, seeds 0..7 as mbd/scripts/run_mbd.py:20.  With
         # G > 1 ranks every plan runs SHARDED over the ranks (the product's multi-GPU path: run_diffusion ->
         # reverse_distributed) and, on rank 0, once more on one GPU: the two must agree bit for bit (variant B: every
@@ -840,7 +919,7 @@ def main():
     # (scripts/run_mbd.py:17-39) — so that the driver's record of this command holds them too.  ~3 s.  Each extra is
     # guarded on its own: a failure is reported as {"error": ...} under its name and never costs the line its value.
     extras = None
-    if rank == 0 and not distributed and args.config == "metric" and not args.no_extras and not os.environ.get("MBD_BENCH_N"):
+    if args.full and rank == 0 and not distributed and args.config == "metric" and not args.no_extras and not os.environ.get("MBD_BENCH_N"):
         extras = {}
 
         def extra_big():
@@ -879,7 +958,7 @@ def main():
     # long as N).  The workload of the reference that DOES scale — its 8-seed sweep, plans as replicas — rides in the
     # same line: every rank runs 8 plans of N = 1024 (its own seeds) as one sweep on its GPU, no collective inside and no
     # fence between the ranks; ONE gather of the per-rank rates at the end, reached by every rank whatever happened.
-    if distributed and world > 1 and args.config == "metric" and not args.no_extras and not os.environ.get("MBD_BENCH_N"):
+    if args.full and distributed and world > 1 and args.config == "metric" and not args.no_extras and not os.environ.get("MBD_BENCH_N"):
         try:
             P_x = CONFIGS["sweep8"]["plans"]
             _, x_kms, _, x_own = measure_sweep(list(range(rank * P_x, (rank + 1) * P_x)), steps=40, warmup=5, repeats=3,
@@ -898,7 +977,7 @@ def main():
                 "plan_steps_per_sec": sum(b["plan_steps_per_sec"] for b in good), "ranks_ok": len(good), "per_rank": box}}
 
     per_rank = None
-    if is_sweep and distributed:  # every rank's own rate (its plans, its clock), for the line
+    if args.full and is_sweep and distributed:  # every rank's own rate (its plans, its clock), for the line
         own = res[args.scaling][4]
         mine = len(sweep_plans[args.scaling]) * args.steps / med(own)
         box = [None] * world
@@ -921,10 +1000,6 @@ def main():
         kern_ms, kern_n = res[mode][2], res[mode][3]
         N_total, N_local = runs.get(mode, runs["strong"])
         value, vmin, vmax, ms_sync = rate(mode, "sync")
-        value_async, amin, amax, ms_async = rate(mode, "async")
-        balg = b_alg_bytes(N_local, H, Nu, DEMO)
-        achieved = (balg / 1e9) / (kern_ms / 1e3) if kern_ms > 0 else 0.0
-        traffic, traffic_src = pmc_traffic(args.config)
         out = {
             "metric": "diffusion-steps/sec (N=1024, H=50) + final reward, humanoidrun, 1/2/4/8 GPU",
             "value": value, "unit": "diffusion-steps/sec (whole job, per-step host read of the mean reward included)",
@@ -934,7 +1009,6 @@ def main():
             "repeats": args.repeats, "value_min": vmin, "value_max": vmax,
             "value_note": f"median of {args.repeats} timed blocks of exactly {args.steps} steps, each fenced (barrier + "
                           "device synchronisation) on both sides, max over ranks per block",
-            "value_async": value_async, "value_async_min": amin, "value_async_max": amax, "ms_per_step_async": ms_async,
             "config": {"workload": f"{args.config}: {ENV} N_total={N_total} ({N_local}/GPU) H={H} Ndiffuse={ND} "
                                    f"temp={TEMP}{' enable_demo' if DEMO else ''} seed=0 disable_recommended_params",
                        "name": args.config, "N_total": N_total, "N_per_gpu": N_local, "H": H, "Nu": Nu,
@@ -944,16 +1018,24 @@ def main():
                                         "the in-library windows (mbd_exchange_*)") +
                                        " (variant B: every rank re-derives the softmax and the weighted mean over all N "
                                        "from identical inputs)") if distributed else "none")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": cfg["kernel"], "kernel_avg_ms": kern_ms,
-                         "kernel_launches": kern_n, "kernel_timing": "HIP events around every rollout launch of the "
-                         "value_async leg (same R x K steps; the value leg runs without them: two event records cost a "
-                         "step ~7.5 us)", "algorithmic_bytes_per_launch": balg,
-                         "note": "state stays in VGPRs for all H*n_frames substeps: the kernel is bound by "
-                                 "dependent FP32 VALU issue, not HBM (DESIGN.md §Roofline)"},
-            "final_reward": final,
         }
+        if args.full:  # the second leg, the kernel's time and the views built on it, the final reward
+            value_async, amin, amax, ms_async = rate(mode, "async")
+            balg = b_alg_bytes(N_local, H, Nu, DEMO)
+            achieved = (balg / 1e9) / (kern_ms / 1e3) if kern_ms > 0 else 0.0
+            traffic, traffic_src = pmc_traffic(args.config)
+            out.update({
+                "value_async": value_async, "value_async_min": amin, "value_async_max": amax, "ms_per_step_async": ms_async,
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                             "kernel": cfg["kernel"], "kernel_avg_ms": kern_ms,
+                             "kernel_launches": kern_n, "kernel_timing": "HIP events around every rollout launch of the "
+                             "value_async leg (same R x K steps; the value leg runs without them: two event records cost a "
+                             "step ~7.5 us)", "algorithmic_bytes_per_launch": balg,
+                             "note": "state stays in VGPRs for all H*n_frames substeps: the kernel is bound by "
+                                     "dependent FP32 VALU issue, not HBM (DESIGN.md §Roofline)"},
+                "final_reward": final,
+            })
         n_valu = N_local
         if is_sweep:  # plan-steps: K lockstep steps of the plans
             P = cfg["plans"]
@@ -966,93 +1048,95 @@ def main():
             out["config"].update(plans=p_local * world, plans_per_gpu=p_local, N_total=p_local * world * N_CFG,
                                  N_per_gpu=p_local * N_CFG,
                                  collective="none inside a run (independent plans); rew_final gathered once at the end")
-            if p_local * N_CFG <= 4096:  # (the launch selection of csrc: two candidates per lane above 4096 candidates)
+            if args.full and p_local * N_CFG <= 4096:  # (the launch selection of csrc: two candidates per lane above 4096)
                 out["roofline"]["kernel"] = CONFIGS["metric"]["kernel"] + f" over {p_local} plan(s) x {N_CFG} candidates"
-            bal = p_local * b_alg_bytes(N_CFG, H, Nu, DEMO)
-            out["roofline"].update(achieved=(bal / 1e9) / (kern_ms / 1e3) if kern_ms > 0 else 0.0,
-                                   algorithmic_bytes_per_launch=bal)
-            out["roofline"]["frac"] = out["roofline"]["achieved"] / HBM_PEAK_GBS
-            out["roofline"]["traffic"] = None
-            out["roofline"]["kernel_timing"] = ("HIP events around every rollout launch of one MORE run of the same K "
-                                                "lockstep steps (the value runs carry no events)")
+            if args.full:
+                bal = p_local * b_alg_bytes(N_CFG, H, Nu, DEMO)
+                out["roofline"].update(achieved=(bal / 1e9) / (kern_ms / 1e3) if kern_ms > 0 else 0.0,
+                                       algorithmic_bytes_per_launch=bal)
+                out["roofline"]["frac"] = out["roofline"]["achieved"] / HBM_PEAK_GBS
+                out["roofline"]["traffic"] = None
+                out["roofline"]["kernel_timing"] = ("HIP events around every rollout launch of one MORE run of the same K "
+                                                    "lockstep steps (the value runs carry no events)")
             if per_rank is not None:
                 out["per_rank_plan_steps_per_sec"] = per_rank
             n_valu = p_local * N_CFG
         if distributed:
             out["rccl_world"] = rccl_world
             out["dist_backend"] = backend + (" (RCCL over xGMI)" if backend == "nccl" else " (dry run: ranks may share a device)")
-        # what a reader of the N = 1, 2, 4, 8 lines should expect BEFORE computing an efficiency from them (the driver does
-        # that itself from `value`): the literal metric shards ONE plan's N candidates, and a rollout is latency-bound —
-        # N / G candidates take as long as N while a launch leaves SIMDs idle (N <= 4096 on this chip)
-        out["scaling_expectation"] = {
-            "strong": "FLAT by design: phase 1 (sample + rollout) of N/G candidates costs what N do (one wavefront per SIMD "
-                      "either way: ~0.55 ms at any N/G <= 1024 for humanoidrun), plus one all-gather of N/G rewards per rank and "
-                      "step (~10-30 us): value(G) ~ value(1) x 0.93-0.97, efficiency ~ 1/G",
-            "weak": "N per GPU, G x N in total: ~0.95 of linear in candidates per second (the same phase 1 per rank, the score over "
-                    "G x N candidates recomputed on every rank: +8 us per 1024 candidates)",
-            "sweep8_replicas": "LINEAR: independent plans as replicas over the ranks (the reference's own sweep protocol, "
-                               "scripts/run_mbd.py:17-39), no collective inside a run — the workload of the reference that fills "
-                               "more than one GPU; `--config sweep8 --gpus G` is its fenced form, extras.sweep8_replicas the "
-                               "rider of the metric line",
-            "measured_on_hardware": "no run on more than one DEVICE exists yet (rounds 1-5: the driver's SCALE was skipped, no "
-                                    "8-GPU node); ranks > 1 have only run as processes sharing one GPU",
-        }
-        if phase_ms is not None:
-            out["phase_ms"] = phase_ms
-        if other_coll is not None:
-            if "elapsed" in other_coll:
-                nt = runs[mode][0]
-                fac = (nt / N_CFG if mode == "weak" else 1.0)
-                other_coll["value"] = args.steps / other_coll.pop("elapsed") * fac
-                other_coll["value_async"] = args.steps / other_coll.pop("elapsed_async") * fac
-            out["other_collective"] = other_coll
-        if world > 1:
-            other = "weak" if mode == "strong" else "strong"
-            ov, _, _, oms = rate(other, "sync")
-            oa, _, _, _ = rate(other, "async")
-            out["other_scaling"] = {"scaling": other, "value": ov, "ms_per_step": oms, "value_async": oa}
-            if is_sweep:
-                out["other_scaling"].update(plans=len(sweep_plans[other]) * world, plans_per_gpu=len(sweep_plans[other]))
-            else:
-                out["other_scaling"].update(N_total=runs[other][0], N_per_gpu=runs[other][1])
-        fsub, fsub_src = op_counts(ENV)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"], live = cpu_baseline(cfg)
-            if live:
-                fsub, fsub_src = live, "oracle/count_ops.cc (this run)"
-            pj = out["cpu_baseline"].pop("parity_jax", None) if isinstance(out["cpu_baseline"], dict) else None
-            if pj is not None:
-                if "rew_final_ndiffuse" in pj and not is_sweep:  # this library's rew_final of the reference's last timed arguments
-                    try:
-                        a = Args(seed=0, env_name=ENV, Nsample=N_CFG, Hsample=H, Ndiffuse=pj["rew_final_ndiffuse"], temp_sample=TEMP,
-                                 enable_demo=DEMO, disable_recommended_params=True, not_render=True)
+        if args.full:  # everything else the line has carried: the other legs, the CPU baseline, the views
+            # what a reader of the N = 1, 2, 4, 8 lines should expect BEFORE computing an efficiency from them (the driver does
+            # that itself from `value`): the literal metric shards ONE plan's N candidates, and a rollout is latency-bound —
+            # N / G candidates take as long as N while a launch leaves SIMDs idle (N <= 4096 on this chip)
+            out["scaling_expectation"] = {
+                "strong": "FLAT by design: phase 1 (sample + rollout) of N/G candidates costs what N do (one wavefront per SIMD "
+                          "either way: ~0.55 ms at any N/G <= 1024 for humanoidrun), plus one all-gather of N/G rewards per rank and "
+                          "step (~10-30 us): value(G) ~ value(1) x 0.93-0.97, efficiency ~ 1/G",
+                "weak": "N per GPU, G x N in total: ~0.95 of linear in candidates per second (the same phase 1 per rank, the score over "
+                        "G x N candidates recomputed on every rank: +8 us per 1024 candidates)",
+                "sweep8_replicas": "LINEAR: independent plans as replicas over the ranks (the reference's own sweep protocol, "
+                                   "scripts/run_mbd.py:17-39), no collective inside a run — the workload of the reference that fills "
+                                   "more than one GPU; `--config sweep8 --gpus G` is its fenced form, extras.sweep8_replicas the "
+                                   "rider of the metric line",
+                "measured_on_hardware": "no run on more than one DEVICE exists yet (rounds 1-5: the driver's SCALE was skipped, no "
+                                        "8-GPU node); ranks > 1 have only run as processes sharing one GPU",
+            }
+            if phase_ms is not None:
+                out["phase_ms"] = phase_ms
+            if other_coll is not None:
+                if "elapsed" in other_coll:
+                    nt = runs[mode][0]
+                    fac = (nt / N_CFG if mode == "weak" else 1.0)
+                    other_coll["value"] = args.steps / other_coll.pop("elapsed") * fac
+                    other_coll["value_async"] = args.steps / other_coll.pop("elapsed_async") * fac
+                out["other_collective"] = other_coll
+            if world > 1:
+                other = "weak" if mode == "strong" else "strong"
+                ov, _, _, oms = rate(other, "sync")
+                oa, _, _, _ = rate(other, "async")
+                out["other_scaling"] = {"scaling": other, "value": ov, "ms_per_step": oms, "value_async": oa}
+                if is_sweep:
+                    out["other_scaling"].update(plans=len(sweep_plans[other]) * world, plans_per_gpu=len(sweep_plans[other]))
+                else:
+                    out["other_scaling"].update(N_total=runs[other][0], N_per_gpu=runs[other][1])
+            fsub, fsub_src = op_counts(ENV)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"], live = cpu_baseline(cfg)
+                if live:
+                    fsub, fsub_src = live, "oracle/count_ops.cc (this run)"
+                pj = out["cpu_baseline"].pop("parity_jax", None) if isinstance(out["cpu_baseline"], dict) else None
+                if pj is not None:
+                    if "rew_final_ndiffuse" in pj and not is_sweep:  # this library's rew_final of the reference's last timed arguments
+                        try:
+                            a = Args(seed=0, env_name=ENV, Nsample=N_CFG, Hsample=H, Ndiffuse=pj["rew_final_ndiffuse"], temp_sample=TEMP,
+                                     enable_demo=DEMO, disable_recommended_params=True, not_render=True)
+                            with contextlib.redirect_stdout(sys.stderr):
+                                pj["rew_final_ours"] = float(run_diffusion(a, device=local_rank, force_single=True))
+                        except Exception as e:  # noqa: BLE001
+                            pj["rew_final_ours_error"] = f"{type(e).__name__}: {e}"
+                    out["parity_jax"] = pj
+                traj = out["cpu_baseline"].pop("_trajectory", None)
+                if traj is not None and not is_sweep and not os.environ.get("MBD_BENCH_N"):
+                    try:  # (guarded like the extras: a failure here is reported, it never costs the line its value)
+                        a = Args(seed=0, env_name=ENV, Nsample=N_CFG, Hsample=H, Ndiffuse=ND, temp_sample=TEMP, enable_demo=DEMO,
+                                 disable_recommended_params=True, not_render=True)
                         with contextlib.redirect_stdout(sys.stderr):
-                            pj["rew_final_ours"] = float(run_diffusion(a, device=local_rank, force_single=True))
+                            g_rf, g_det = run_diffusion(a, device=local_rank, return_details=True, force_single=True)
+                        out["parity"] = whole_run_parity(traj, g_det, g_rf)
                     except Exception as e:  # noqa: BLE001
-                        pj["rew_final_ours_error"] = f"{type(e).__name__}: {e}"
-                out["parity_jax"] = pj
-            traj = out["cpu_baseline"].pop("_trajectory", None)
-            if traj is not None and not is_sweep and not os.environ.get("MBD_BENCH_N"):
-                try:  # (guarded like the extras: a failure here is reported, it never costs the line its value)
-                    a = Args(seed=0, env_name=ENV, Nsample=N_CFG, Hsample=H, Ndiffuse=ND, temp_sample=TEMP, enable_demo=DEMO,
-                             disable_recommended_params=True, not_render=True)
-                    with contextlib.redirect_stdout(sys.stderr):
-                        g_rf, g_det = run_diffusion(a, device=local_rank, return_details=True, force_single=True)
-                    out["parity"] = whole_run_parity(traj, g_det, g_rf)
-                except Exception as e:  # noqa: BLE001
-                    out["parity"] = {"error": f"{type(e).__name__}: {e}"}
-        if is_sweep and n_valu <= 4096:  # (the one-candidate kernel's geometry and static counts)
-            cfg = dict(cfg, cpw=4, static="humanoidrun")
-        out["valu"] = valu_view(cfg, n_valu, kern_ms, n_frames, fsub, fsub_src)
-        if extras is not None:
-            for e in extras.values():  # (the VALU view of the extra workloads needs the op count of this line)
-                if not isinstance(e, dict):
-                    continue
-                cands = e.pop("_candidates", None)
-                if fsub and cands and e.get("kernel_avg_ms"):
-                    e["valu_algorithmic_frac"] = (float(fsub["flops"]) * cands * H * n_frames /
-                                                  (e["kernel_avg_ms"] * 1e-3) / 1e12 / VALU_PEAK_TF)
-            out["extras"] = extras
+                        out["parity"] = {"error": f"{type(e).__name__}: {e}"}
+            if is_sweep and n_valu <= 4096:  # (the one-candidate kernel's geometry and static counts)
+                cfg = dict(cfg, cpw=4, static="humanoidrun")
+            out["valu"] = valu_view(cfg, n_valu, kern_ms, n_frames, fsub, fsub_src)
+            if extras is not None:
+                for e in extras.values():  # (the VALU view of the extra workloads needs the op count of this line)
+                    if not isinstance(e, dict):
+                        continue
+                    cands = e.pop("_candidates", None)
+                    if fsub and cands and e.get("kernel_avg_ms"):
+                        e["valu_algorithmic_frac"] = (float(fsub["flops"]) * cands * H * n_frames /
+                                                      (e["kernel_avg_ms"] * 1e-3) / 1e12 / VALU_PEAK_TF)
+                out["extras"] = extras
         print(json.dumps(out))
     if distributed:
         dist.barrier()

@@ -782,6 +782,50 @@ def test_bench_multirank_code_path_on_rccl_with_one_rank(gpu):
     assert d["n_gpus"] == 1 and d["config"]["collective"].startswith("all-gather of N/G rewards") and d["value"] > 300.0
 
 
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """A plain bench.py run: ONE timed block of exactly --steps steps, a line with the headline fields only, and
+    --dump-outputs writing what the last timed step computed — the new mean [H, Nu], the step's mean reward as the host read
+    it and the per-candidate rewards it is the mean of."""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 7 and d["repeats"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 300.0 and abs(d["ms_per_step"] - 1e3 / d["value"]) < 1e-6 * d["ms_per_step"]
+    assert not {"value_async", "roofline", "final_reward", "cpu_baseline", "extras", "valu"} & set(d), sorted(d)
+    y, rm, rw = (np.load(tmp_path / f"{n}.npy") for n in ("ybar", "rew_mean", "rewards"))
+    assert y.dtype == rm.dtype == rw.dtype == np.float32
+    assert y.shape == (50, 17) and rm.shape == (1,) and rw.shape == (1024,)
+    assert np.isfinite(y).all() and np.isfinite(rw).all() and np.abs(y).max() > 0
+    assert abs(float(rm[0]) - float(rw.astype(np.float64).mean())) < 1e-4 * max(1.0, abs(float(rm[0])))
+
+
+def test_bench_runs_a_tree_it_cannot_write(gpu, tmp_path):
+    """bench.py on a tree another user built: the library's directory and its build lock are not writable (build() cannot
+    even take the lock).  The run must load the library as built and print its line, the plain and the --full one."""
+    import json, os, stat, subprocess, sys
+    from conftest import ROOT
+    libdir = os.path.join(ROOT, "model-based-diffusion_amd", "lib")
+    lock = os.path.join(libdir, ".build.lock")
+    modes = {p_: stat.S_IMODE(os.stat(p_).st_mode) for p_ in (libdir, lock)}
+    try:
+        os.chmod(lock, 0o444)
+        os.chmod(libdir, 0o555)
+        for extra in ([], ["--full", "--no-cpu-baseline", "--no-final-reward", "--no-extras"]):
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup",
+                                  "1", *extra], capture_output=True, text=True, timeout=600)
+            assert out.returncode == 0, out.stderr[-2000:]
+            lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+            assert len(lines) == 1 and json.loads(lines[0])["value"] > 300.0, out.stdout[-2000:]
+    finally:
+        for p_, m in modes.items():
+            os.chmod(p_, m)
+
+
 def test_bench_two_ranks_line_is_complete(gpu):
     """bench.py --gpus 2 the way the driver launches it, as a dry run on this box's ONE GPU (MBD_DIST_BACKEND=gloo, both
     ranks on device 0): the line must carry the final reward of the SHARDED plans and say that it equals the one-GPU
@@ -795,7 +839,7 @@ def test_bench_two_ranks_line_is_complete(gpu):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10",
-           "--warmup", "2", "--no-cpu-baseline"]
+           "--warmup", "2", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -957,7 +1001,7 @@ def test_bench_eight_ranks_lines_are_complete(gpu, config, n_strong):
     device 0), for the metric and for BASELINE configs 4 and 5 (both DEFINED on 8 GPUs): the line carries the final
     rewards of the plans SHARDED over the eight ranks, equal to one GPU's bit for bit, the phases of a sharded step, and
     the second collective (eight windows) beside the process group's."""
-    d = _bench_ranks(8, ["--steps", "4", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline", "--config", config])
+    d = _bench_ranks(8, ["--steps", "4", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline", "--full", "--config", config])
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["N_per_gpu"] == n_strong and d["repeats"] == 2
     assert d["value_min"] <= d["value"] <= d["value_max"]
     fr = d["final_reward"]
@@ -975,7 +1019,8 @@ def test_bench_sweep_replicas_over_ranks(gpu, world):
     """bench.py --config sweep8 --gpus G (round-3 verdict item 2): the reference's eight independent plans
     (mbd/scripts/run_mbd.py:17-39) as REPLICAS over the ranks — 8/G plans per rank through mbd_sweep_*, no communication
     inside a run — with the final rewards gathered once and equal, bit for bit, to the one-GPU sweep of all eight."""
-    d = _bench_ranks(world, ["--steps", "6", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--config", "sweep8"])
+    d = _bench_ranks(world, ["--steps", "6", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--full", "--config",
+                             "sweep8"])
     assert d["n_gpus"] == world and d["config"]["plans"] == 8 and d["config"]["plans_per_gpu"] == 8 // world
     assert d["unit"].startswith("plan-steps/sec") and d["value"] > 100.0
     fr = d["final_reward"]

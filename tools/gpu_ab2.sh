@@ -8,7 +8,7 @@ if [ "$1" != notests ]; then
   tail -3 gpurun_out/ab2_tests.log
 else shift; fi
 V=$GRAFT_REPO_ROOT/model-based-diffusion_amd/lib/variants
-run() { MBD_HIP_LIB=$3 python bench.py --config $1 --steps 198 --warmup 20 --no-cpu-baseline --no-final-reward 2>/dev/null | tail -1 | python -c "
+run() { MBD_HIP_LIB=$3 python bench.py --full --config $1 --steps 198 --warmup 20 --no-cpu-baseline --no-final-reward 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('%-22s %-8s' % ('$1', '$2'), 'steps/s %.1f  async %.1f  ms/step %.4f  rollout_kernel_ms %.4f' % (d['value'], d['value_async'], d['ms_per_step'], d['roofline']['kernel_avg_ms']))"; }
 {
 for c in ${@:-metric}; do

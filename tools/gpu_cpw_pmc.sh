@@ -8,7 +8,7 @@ CFGS=${@:-hopper512:1000 halfcheetah1024:800}
 for cs in $CFGS; do
   c=${cs%%:*}; sub=${cs##*:}
   for cpw in 0 -1; do
-    B="python $R/bench.py --config $c --no-cpu-baseline --no-final-reward --no-extras --repeats 2 --steps 20 --warmup 2"
+    B="python $R/bench.py --full --config $c --no-cpu-baseline --no-final-reward --no-extras --repeats 2 --steps 20 --warmup 2"
     rm -rf $W/a $W/b
     MBD_CPW=$cpw rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_SMEM --kernel-trace -d $W/a -o x -- $B > $W/a.log 2>&1
     MBD_CPW=$cpw rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace -d $W/b -o x -- $B > $W/b.log 2>&1

@@ -7,7 +7,7 @@ export MBD_DIST_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0
 G=${G:-8}
 for c in ${CONFIGS:-metric humanoidrun4096 humanoidtrack2048demo sweep8}; do
   echo "== bench.py --config $c --gpus $G (one GPU, gloo) =="
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node $G --master-addr 127.0.0.1 --master-port 29631 bench.py --gpus $G --config $c --steps ${STEPS:-20} --warmup 5 --repeats ${REPEATS:-3} --no-cpu-baseline 2>gpurun_out/ranks_${c}_err.log | grep "^{" | python -c "
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node $G --master-addr 127.0.0.1 --master-port 29631 bench.py --gpus $G --full --config $c --steps ${STEPS:-20} --warmup 5 --repeats ${REPEATS:-3} --no-cpu-baseline 2>${LOGS:-/tmp}/ranks_${c}_err.log | grep "^{" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=lambda v: round(v,3) if isinstance(v,float) else v
@@ -21,5 +21,5 @@ print('per_rank', [r(x) for x in d.get('per_rank_plan_steps_per_sec',[])])
 x=(d.get('extras') or {}).get('sweep8_replicas'); print('extras.sweep8_replicas', None if x is None else {k:r(v) for k,v in x.items() if k in ('plan_steps_per_sec','ranks_ok')})
 fr=d['final_reward']; print('final_reward equals_one_gpu_bitwise', fr.get('equals_one_gpu_bitwise'), 'over', fr.get('sharded_over', fr.get('replicated_over')), 'mean', r(fr.get('mean')))
 "
-  tail -3 gpurun_out/ranks_${c}_err.log | cut -c1-300
+  tail -3 ${LOGS:-/tmp}/ranks_${c}_err.log | cut -c1-300
 done

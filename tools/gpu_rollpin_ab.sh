@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 R=$GRAFT_REPO_ROOT; W=/tmp/rollpin; mkdir -p $W; cd /tmp; export TMPDIR=/tmp
 for c in hopper512 halfcheetah1024 metric; do
   for pin in 0 1; do
-    B="python $R/bench.py --config $c --no-cpu-baseline --no-final-reward --no-extras"
+    B="python $R/bench.py --full --config $c --no-cpu-baseline --no-final-reward --no-extras"
     MBD_ROLL_PIN=$pin $B 2>/dev/null | tail -1 > $W/line.json
     rm -rf $W/f $W/w
     MBD_ROLL_PIN=$pin rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $W/f -o x -- $B --repeats 2 --steps 30 --warmup 5 > $W/f.log 2>&1

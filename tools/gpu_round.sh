@@ -10,16 +10,16 @@ if [[ " $what " == *" tests "* ]]; then
   timeout 1200 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $OUT/pytest_${TAG}.log
 fi
 if [[ " $what " == *" bench "* ]]; then
-  python bench.py --steps 60 --warmup 10 2>$OUT/bench_err.log | tail -1 > $OUT/bench_${TAG}_metric.json; cat $OUT/bench_${TAG}_metric.json
+  python bench.py --full --steps 60 --warmup 10 2>$OUT/bench_err.log | tail -1 > $OUT/bench_${TAG}_metric.json; cat $OUT/bench_${TAG}_metric.json
   for c in hopper512 halfcheetah1024 humanoidrun4096 humanoidtrack2048demo car2d humanoidrun8192 sweep8; do
-    python bench.py --config $c --steps 100 --warmup 10 2>>$OUT/bench_err.log | tail -1 > $OUT/bench_${TAG}_$c.json; cat $OUT/bench_${TAG}_$c.json
+    python bench.py --full --config $c --steps 100 --warmup 10 2>>$OUT/bench_err.log | tail -1 > $OUT/bench_${TAG}_$c.json; cat $OUT/bench_${TAG}_$c.json
   done
 fi
 if [[ " $what " == *" prof "* ]]; then
   cd /tmp && export TMPDIR=/tmp
   for c in metric hopper512 halfcheetah1024 humanoidrun4096 humanoidtrack2048demo humanoidrun8192 sweep8; do
     [[ " $what " == *" $c "* ]] || continue
-    B="python $R/bench.py --config $c --no-cpu-baseline --no-final-reward --no-extras --repeats 2"
+    B="python $R/bench.py --full --config $c --no-cpu-baseline --no-final-reward --no-extras --repeats 2"
     rocprofv3 --kernel-trace --stats -d $OUT/prof_${c}_stats -o ${TAG} -- $B --steps 60 --warmup 10 > $OUT/prof_${c}_stats.log 2>&1
     rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY --kernel-trace -d $OUT/prof_${c}_sq -o ${TAG} -- $B --steps 20 --warmup 2 > $OUT/prof_${c}_sq.log 2>&1
     rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/prof_${c}_fetch -o ${TAG} -- $B --steps 20 --warmup 2 > $OUT/prof_${c}_fetch.log 2>&1

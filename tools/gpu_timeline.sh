@@ -8,7 +8,7 @@ for m in ${MODES:-lazy nolazy}; do
   [[ $m == *-noev ]] && E="$E MBD_BENCH_EVENTS=none"; [[ $m == *-ev ]] && E="$E MBD_BENCH_EVENTS=all"
   [[ $m == nopf* ]] && E="$E MBD_NO_PREFETCH=1"
   [[ $m == nolds* ]] && E="$E MBD_LDS_RESERVE=0"
-  env $E rocprofv3 --kernel-trace -d $OUT/tl_$m -o t -- python $R/bench.py --config ${CFG:-metric} --no-cpu-baseline --no-final-reward --steps 30 --warmup 5 > $OUT/tl_$m.log 2>&1
+  env $E rocprofv3 --kernel-trace -d $OUT/tl_$m -o t -- python $R/bench.py --full --config ${CFG:-metric} --no-cpu-baseline --no-final-reward --steps 30 --warmup 5 > $OUT/tl_$m.log 2>&1
   python - <<P
 import sqlite3,glob
 db=glob.glob("$OUT/tl_$m/*.db")[0]

@@ -30,7 +30,7 @@ def main():
     con = sqlite3.connect(stats_db)
     rows = list(con.execute("select name, total_calls, total_duration, average, percentage from top_kernels"))
     lines = [f"# rocprofv3 --kernel-trace --stats ({tag})", "",
-             f"command: `rocprofv3 --kernel-trace --stats -- python bench.py --config {config} --steps 60 --warmup 10 "
+             f"command: `rocprofv3 --kernel-trace --stats -- python bench.py --full --config {config} --steps 60 --warmup 10 "
              "--no-cpu-baseline --no-final-reward --no-extras --repeats 2` (durations in microseconds)", "",
              "| kernel | calls | total_us | avg_us | % |", "|---|---:|---:|---:|---:|"]
     for name, calls, tot, avg, pct in rows:
