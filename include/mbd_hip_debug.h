@@ -16,6 +16,13 @@ int mbd_debug_set(const char* name, int value);
 int mbd_debug_get(const char* name, int* value_out);
 /* the DPP layout family (0..3, -1: none) a model's link tree fits, with its lane <-> link table and shifts */
 int mbd_debug_dpp_layout(const mbd_model_t* model, signed char tab[32], int shifts_out[4]);
+/* the rollout launch the library picks for a model (no device needed): n_cus compute units, B candidates, horizon H,
+ * sweep_plan_N > 0: a sweep of plans of that many candidates, has_xref: the env has a demo.  out = grid (workgroups of
+ * the rollout itself), block, dynamic LDS bytes, candidates per wavefront (0: filled), wavefronts per SIMD asked of a
+ * two-candidates-per-lane kernel, XCD-pinned, takes a noise job into spare workgroups, accumulates the demo log-density;
+ * name: the instantiation's demangled symbol.  Reads the levers like a launch. */
+int mbd_debug_rollout_choice(const mbd_model_t* model, int n_cus, int B, int H, int sweep_plan_N, int has_xref,
+                             char* name, int cap, int out[8]);
 /* per-wavefront clock records of the 3-D rollout kernels (tools/probes/rollout_timeline.py); d_buf: device, caller-owned */
 int mbd_debug_set_clock_buffer(mbd_env* env, void* d_buf);
 #ifdef __cplusplus

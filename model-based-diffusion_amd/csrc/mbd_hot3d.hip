@@ -10,31 +10,27 @@
 
 namespace mbd {
 
-// which: 0 humanoid-shaped, one collider per link; 1 humanoid-shaped, up to five with helper lanes; 2 the same without
-// helper lanes; 3 ant.  rk: the model's reward kind, or -1 (lever MBD_NO_REWARD_CONST); nfr: n_frames, or 0 (run-time).
-hipError_t launch_rollout_hot3d(int which, int rk, int nfr, int device, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
-                                const RolloutParams& P) {
-#define HOT(...) return launch_rollout_kernel(rollout_kernel<__VA_ARGS__>, device, grid, block, lds, stream, P)
+RolloutKernel hot3d_kernel(const EnvShape& s, bool helpers, int rk, int nfr) {
   constexpr int D0 = 1, D1 = -4, D2 = -6;
-  if (which == 0) {
-    if (rk == MBD_REW_HUMANOIDRUN && nfr == 7) HOT(16, true, false, 3, 1, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDRUN, 7);
-    if (rk == MBD_REW_HUMANOIDTRACK && nfr == 5) HOT(16, true, false, 3, 1, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDTRACK, 5);
-    HOT(16, true, false, 3, 1, D0, D1, D2, 0, false, true);
+  if (s.humanoid_shape && s.dpp_family == 0 && s.max_col <= 1) {
+    if (rk == MBD_REW_HUMANOIDRUN && nfr == 7) return rollout_kernel<16, true, false, 3, 1, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDRUN, 7>;
+    if (rk == MBD_REW_HUMANOIDTRACK && nfr == 5) return rollout_kernel<16, true, false, 3, 1, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDTRACK, 5>;
+    return rollout_kernel<16, true, false, 3, 1, D0, D1, D2, 0, false, true>;
   }
-  if (which == 1) {  // humanoidstandup: the torso's colliders 2..4 run stage (4) on two of the candidate's idle lanes (HELP)
-    if (rk == MBD_REW_HUMANOIDSTANDUP && nfr == 7) HOT(16, true, false, 3, 5, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDSTANDUP, 7, true, true);
-    HOT(16, true, false, 3, 5, D0, D1, D2, 0, false, true, 3, false, false, -1, 0, true);
+  if (s.humanoid_shape && s.dpp_family == 0 && s.max_col <= 5) {
+    if (helpers) {  // humanoidstandup: the torso's colliders 2..4 run stage (4) on two of the candidate's idle lanes (HELP)
+      if (rk == MBD_REW_HUMANOIDSTANDUP && nfr == 7) return rollout_kernel<16, true, false, 3, 5, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDSTANDUP, 7, true, true>;
+      return rollout_kernel<16, true, false, 3, 5, D0, D1, D2, 0, false, true, 3, false, false, -1, 0, true>;
+    }
+    if (rk == MBD_REW_HUMANOIDSTANDUP && nfr == 7) return rollout_kernel<16, true, false, 3, 5, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDSTANDUP, 7>;
+    return rollout_kernel<16, true, false, 3, 5, D0, D1, D2, 0, false, true>;
   }
-  if (which == 2) {
-    if (rk == MBD_REW_HUMANOIDSTANDUP && nfr == 7) HOT(16, true, false, 3, 5, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDSTANDUP, 7);
-    HOT(16, true, false, 3, 5, D0, D1, D2, 0, false, true);
+  if (s.lps == 16 && s.iso && !s.slides && s.max_col <= 2 && s.dpp_family == 3 && s.max_rot <= 1) {
+    // ant (the reference's default env_name): reward kind and n_frames compiled in, like the humanoids
+    if (rk == MBD_REW_ANT && nfr == 10) return rollout_kernel<16, true, false, 4, 2, 1, -2, -4, -6, false, false, 3, false, false, MBD_REW_ANT, 10, false, true>;
+    return rollout_kernel<16, true, false, 4, 2, 1, -2, -4, -6, false, false>;
   }
-  if (which == 3) {  // ant (the reference's default env_name): reward kind and n_frames compiled in, like the humanoids
-    if (rk == MBD_REW_ANT && nfr == 10) HOT(16, true, false, 4, 2, 1, -2, -4, -6, false, false, 3, false, false, MBD_REW_ANT, 10, false, true);
-    HOT(16, true, false, 4, 2, 1, -2, -4, -6, false, false);
-  }
-#undef HOT
-  return hipErrorInvalidValue;
+  return nullptr;
 }
 
 }  // namespace mbd

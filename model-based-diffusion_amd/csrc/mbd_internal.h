@@ -22,6 +22,7 @@
 
 #include "../../include/mbd_hip.h"
 #include "mbd_kernels.h"
+#include "mbd_launch.h"
 #include "mbd_step_kernels.h"
 
 using namespace mbd;
@@ -60,7 +61,7 @@ enum EnvKind { ENV_CAR2D = 0, ENV_MODEL = 1 };
 constexpr int kLdsN = 36 * 1024;  // candidates whose logp0 fits the score kernel's LDS (144 KB of the CU's 160)
 
 
-struct mbd_env {
+struct mbd_env : EnvShape {  // (the shape: derive_shape, at creation; car2d keeps the defaults)
   int kind = ENV_MODEL;
   int device = 0;
   std::string name;
@@ -69,25 +70,10 @@ struct mbd_env {
   float* d_xref = nullptr;
   bool has_xref = false;
   float rew_xref = 0.0f;
-  int lps = 16, max_children = 0, max_col = 0, max_rot = 0;
   int n_cus = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount; four SIMDs each)
-  bool diag_inertia = true;  // every body-frame inverse-inertia tensor is exactly diagonal
-  bool axisym = true;        // ... with two equal entries: axisymmetric about a link axis (AXI instantiations)
-  bool slides = false;
-  bool slide_limits = false;  // any slide dof with a finite range
-  int max_slide = 0;          // largest slide-dof count of a joint
-  bool slides_world_only = true;  // every joint with a slide dof hangs off the world
-  bool has_weld = false;          // some joint has no hinge dof
-  bool planar = false;            // MBD_FLAG_PLANAR: the planar restatement (mbd_planar.h)
-  bool any_stiff = false;         // some hinge has a joint spring
-  // DPP layout (kernels.h "lane exchange without the LDS"): lane <-> link tables when the tree fits the shifts
-  int dpp_family = -1;  // index into kDppFamilies, -1: shuffles
-  signed char lane_tab[32];
   signed char* d_lane_tab = nullptr;
   LaneRec3* d_lane_rec = nullptr;  // [3][16]: per-lane constants of the 3-D kernels (lane = link; the DPP layout; the
                                    // DPP layout with helper lanes)
-  bool helpers = false;  // one link with 3..5 colliders and two idle lanes to lend them to (HELP instantiations)
-  bool spec = false;     // the model carries specification switches (MBD_SPEC_FLAGS): the general SPEC instantiations, 16 lanes
   unsigned long long* dbg_clock = nullptr;  // per env, caller-owned device buffer (mbd_debug_set_clock_buffer; probes only)
   // scratch for the single-env step path
   float *d_s_in = nullptr, *d_act = nullptr, *d_s_out = nullptr, *d_rew = nullptr;
@@ -200,18 +186,33 @@ constexpr int kInStepWaitMs = 20;
 // test / A-B levers (one process-wide table, include/mbd_hip_debug.h): -1 = not set
 int lever(const char* name);
 bool env_flag(const char* name);
-// launch of the env's rollout instantiation; sweep = {plan_N, plan_state_stride, plan_ybar_stride} (RolloutParams), or nullptr
-// d_lp: the demo log-densities [B] accumulated inside the rollout (RolloutParams::lp) — only where rollout_fuses_logpd says so
+// the device-free facts of a model the launch paths need (env creation; mbd_debug_rollout_choice): MBD_OK, or the error
+// of a model no instantiation is built for
+int derive_shape(const mbd_model_t& m, EnvShape& s);
+// Everything about a rollout launch of B candidates, decided in one place (mbd_env.hip::choose_rollout).
+struct RolloutChoice {
+  RolloutKernel kernel = nullptr;  // host stub of the instantiation; nullptr: none serves the model
+  dim3 grid, block;                // the rollout's own workgroups (launch_rollout adds the noise job's and the XCD pin's)
+  size_t lds = 0;                  // dynamic LDS each workgroup reserves
+  int cpw = 0;                     // RolloutParams::cpw: candidates per wavefront of an early-out launch, 0: filled
+  int wpe = 1;                     // two-candidates-per-lane launches: wavefronts per SIMD the instantiation is asked for
+  bool xcd_pin = false;            // the launch goes to one XCD (RolloutParams::xcd_pin)
+  bool fuses_noise = false;        // a launch with a noise job takes it into spare workgroups
+  bool fuses_logpd = false;        // the instantiation accumulates the demo log-density itself (RolloutParams::lp)
+  std::string name() const;        // the instantiation's symbol, demangled (what profilers show)
+};
+// sweep = {plan_N, plan_state_stride, plan_ybar_stride} (RolloutParams), or nullptr: one plan; has_xref: the env has a demo
+RolloutChoice choose_rollout(const EnvShape& s, const mbd_model_t& m, int n_cus, int B, int H, const int* sweep, bool has_xref);
+// choose_rollout for an env (car2d: no choice — its rollout is not a RolloutParams instantiation)
+RolloutChoice rollout_choice(const mbd_env* env, int B, int H, const int* sweep = nullptr);
+// launch of the env's rollout instantiation; sweep as above.  d_lp: the demo log-densities [B] accumulated inside the
+// rollout (RolloutParams::lp) — only where the choice's fuses_logpd says so (the caller then passes d_lp instead of d_xpos
+// and skips launch_logpd)
 int launch_rollout(mbd_env* env, const float* d_state0, const float* d_us, int B, int H, float* d_rewss, float* d_rews,
                    float* d_xpos, float* d_state_final, hipStream_t stream, LazyArgs* lz = nullptr, const int* sweep = nullptr,
                    float* d_lp = nullptr);
-// whether the instantiation such a launch runs accumulates HumanoidTrack.eval_xref_logpd itself (the tracking reward compiled
-// in, one candidate per lane): the caller then passes d_lp instead of d_xpos and skips launch_logpd.  MBD_NO_FUSED_LOGPD = 1: never.
-bool rollout_fuses_logpd(const mbd_env* env, int B, int H, const int* sweep = nullptr);
 // whether the device is a whole 8-XCD part (the premise of the XCD-pinned launch forms)
 bool device_has_eight_xcds(const mbd_env* env);
-// whether a rollout launch of B candidates takes the next step's normals into spare workgroups
-bool rollout_fuses_noise(const mbd_env* env, int B, bool allow_pk2 = true);  // (allow_pk2: false for sweeps whose plans hold an odd candidate count — launch_rollout)
 int launch_logpd(const mbd_env* e, const float* d_xpos, int B, int H, float* d_out, hipStream_t s);
 // ---- defined in mbd_plan.hip -----------------------------------------------------------------------------------------
 // noise schedule (mbd_planner.py:84-87)

@@ -41,6 +41,10 @@ namespace mbd {
 
 constexpr int kMaxChildren = 4;
 
+// rows of a demonstration trajectory (the reference's demos are 50 control steps long: humanoidtrack.py:36-43, car2d.py:71):
+// xref is [n_track][kXrefRows][3] (car2d: [kXrefRows][2]); plans with a demo run that horizon
+constexpr int kXrefRows = 50;
+
 struct RolloutParams {
   const mbd_model_t* model;  // device copy of the compiled model
   const float* state0;       // [L][13]
@@ -946,16 +950,9 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
   // a workgroup is 1 or 4 INDEPENDENT wavefronts (nothing shared, no barrier): four-wave workgroups are how a launch
   // of >= 1024 wavefronts gets one wavefront on every SIMD of a CU (dispatch)
   const int wave_id = rblock * (blockDim.x >> 6) + (threadIdx.x >> 6);
-#ifdef MBD_PROBE_3D_CPW1
-  // (TIMING PROBE, variant builds only — docs/experiments.md §15: ONE candidate per wavefront, the other groups repeat it)
-  const int b_raw = wave_id;
-  const bool b_ok = b_raw < P.B && lane / LPS == 0;
-  const int b = b_raw < P.B ? b_raw : P.B - 1;
-#else
   const int b_raw = wave_id * SPW + lane / LPS;
   const bool b_ok = b_raw < P.B;
   const int b = b_ok ? b_raw : P.B - 1;
-#endif
   const int H = P.H, Nu = Mg->n_act, nfr = NFR > 0 ? NFR : Mg->n_frames, K = Mg->n_track;
 
   const int nr = R.nr;
@@ -1117,6 +1114,8 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
   q4 Pr_next = shfl4(r, plane);
   float rew_sum = 0.0f;
   float lp_acc = 0.0f;  // (fused demo log-density: this lane's S_k)
+  // (no demo: a dummy address the loads below stay inside — the model)
+  static_assert(sizeof(mbd_model_t) >= MBD_MAX_TRACK * kXrefRows * 3 * sizeof(float), "the dummy xref must hold [K][kXrefRows][3]");
   const float* __restrict__ xref_base = P.xref ? P.xref : (const float*)P.model;
 
   for (int t = 0; t < H; ++t) {
@@ -1156,10 +1155,10 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
     // (fused demo log-density) this control step's reference position of the lane's tracked link, in flight across the
     // substeps.  UNCONDITIONAL loads (under `if (P.lp)` the merge of the loaded value with the other side's zero put the full
     // wait for the loads at the top of every control step: +14 us per rollout): the address is valid whatever the launch
-    // wants — xref is [K][50][3]; launches without one read the model's bytes — and a launch without lp ignores the sum.
+    // wants — xref is [K][kXrefRows][3]; launches without one read the model's bytes — and a launch without lp ignores the sum.
     v3 xr = mk3(0, 0, 0);
     if constexpr (RK == MBD_REW_HUMANOIDTRACK) {
-      const float* c = xref_base + ((size_t)(track_k >= 0 ? track_k : 0) * 50 + (t < 50 ? t : 49)) * 3;
+      const float* c = xref_base + ((size_t)(track_k >= 0 ? track_k : 0) * kXrefRows + (t < kXrefRows ? t : kXrefRows - 1)) * 3;
       xr = mk3(c[0], c[1], c[2]);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1174,14 +1173,9 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
     // kernels +4 ... 6.5 % (mbd_planar.h).  Here it LOSES 2.3 % (metric 1790 -> 1748 steps/s, humanoidtrack2048 2331 -> 2293,
     // same box, profiles/r06_spec3d_ab.txt): without the two branches this compiler emits 867 instead of 846 instructions per
     // humanoid substep (+10 v_mov, +10 unpacked v_fma, two more s_waitcnt; scheduling barriers where the branches were do not
-    // bring them back), and the compare-to-branch latency it removes was evidently hidden already.  Off; -DMBD_3D_SPECULATE
-    // builds it (instantiations with n_frames compiled in: the run-time loop of the others crashes this compiler's register
-    // allocator under the iterative scheduler), bit-identical (148 GPU tests).
-#ifdef MBD_3D_SPECULATE
-    constexpr int QM_FAST = NFR > 0 ? 1 : 0;
-#else
+    // bring them back), and the compare-to-branch latency it removes was evidently hidden already.  Off (the switch that built
+    // it, bit-identical over 148 GPU tests, is gone: docs/experiments.md keeps the numbers).
     constexpr int QM_FAST = 0;
-#endif
     float q_worst = 0.0f;
     const v3 s_p = p, s_v = v, s_w = w;  // the control step's start
     const q4 s_r = r;
@@ -1493,17 +1487,6 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
       {
         const WInert<ISO> Wc = world_inertia<ISO, DIAG, AXI>(ic, r);  // (r not yet renormalised, like the contact points)
         v3 cd_p = mk3(0, 0, 0), cd_th = mk3(0, 0, 0);
-#ifdef MBD_PROBE_NO_CONTACT
-        // (TIMING PROBE, variant builds only: the substep of a candidate that never touches — WRONG physics, the upper bound of
-        // what a contact early-out could save)
-        constexpr bool kContactCode = false;
-#else
-        constexpr bool kContactCode = true;
-#endif
-        if constexpr (!kContactCode) {
-#pragma unroll
-          for (int j = 0; j < MAXCOL; ++j) { con_pos[j] = mk3(0, 0, 0); con_dlam[j] = 0.0f; con_act[j] = false; }
-        } else
         if constexpr (MAXCOL == 2 || HELP) {
           // both colliders of the link as one packed pair (the solve is Jacobi: each sees the pose of the stage's
           // start); their corrections are then added in collider order, exactly like the loop below
@@ -1688,7 +1671,6 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
           v = sel3(con_act[j], nv, v);
           w = sel3(con_act[j], nw, w);
       };
-#ifndef MBD_PROBE_NO_CONTACT
 #pragma unroll
       for (int j = 0; j < MAXCOL; ++j) {
         // (one test PER slot: with one test for all of them humanoidstandup's default plan ran 1161 instead of 1284 steps/s —
@@ -1696,7 +1678,6 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
         if (SKIP6 && j > 0 && __builtin_expect(__builtin_amdgcn_ballot_w64(con_act[j]) == 0ull, 1)) continue;
         slot6(j);
       }
-#endif
       if constexpr (SPEC_AVG && MAXCOL > 1) {
         if (!sp_gs && sp_avg) {  // the average of the link's velocity changes: v6 + (v - v6) / n
           int n_act = 0;

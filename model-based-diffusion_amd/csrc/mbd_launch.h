@@ -1,60 +1,51 @@
-// mbd_launch.h — the one launch site of every rollout instantiation (host side; shared by the translation units that
-// hold rollout kernels: mbd_env.hip, mbd_hot3d.hip, mbd_pk2.hip, mbd_planar.hip).
+// mbd_launch.h — what the translation units that hold rollout kernels share on the host side (mbd_env.hip, mbd_hot3d.hip,
+// mbd_pk2.hip, mbd_planar.hip): the device-free facts of an env's model (EnvShape) and one lookup per unit that names the
+// instantiation serving a model.  mbd_env.hip::choose_rollout asks them; launch_rollout launches what it chose.
 #pragma once
 
 #include <hip/hip_runtime.h>
-
-#include <mutex>
-#include <set>
-#include <utility>
 
 #include "mbd_kernels.h"
 
 namespace mbd {
 
-// One launch site for every instantiation.  lds > 0 reserves dynamic LDS the kernel never touches: more than half
-// of a CU's 160 KB keeps a second workgroup — of this or of a concurrent plan's launch — off the CU, so concurrent
-// plans spread over the chip instead of piling onto the CUs the dispatcher fills first (tools/gpu_concurrent.sh).
-template <typename K>
-inline hipError_t launch_rollout_kernel(K kernel, int device, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
-                                 const RolloutParams& P) {
-  if (lds > 0) {
-    // > 64 KB of dynamic LDS needs the attribute on EVERY instantiation that is launched that way; all of them share
-    // this function's signature, so the bookkeeping is keyed on (kernel address, device)
-    static std::mutex mu;
-    static std::set<std::pair<const void*, int>> raised;
-    std::lock_guard<std::mutex> g(mu);
-    const auto key = std::make_pair((const void*)kernel, device);
-    if (!raised.count(key)) {
-      hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-      if (e != hipSuccess) return e;
-      raised.insert(key);
-    }
-  }
-  hipLaunchKernelGGL(kernel, grid, block, lds, stream, P);
-  return hipGetLastError();
-}
+// every rollout instantiation takes one RolloutParams: its host stub, or nullptr (no such instantiation)
+using RolloutKernel = void (*)(RolloutParams);
 
+// What the launch paths need to know of an env's model, derived once at env creation without a device (derive_shape).
+struct EnvShape {
+  int lps = 16, max_children = 0, max_col = 0, max_rot = 0;
+  bool iso = false;          // mbd_model_t::iso_inertia
+  bool diag_inertia = true;  // every body-frame inverse-inertia tensor is exactly diagonal
+  bool axisym = true;        // ... with two equal entries: axisymmetric about a link axis (AXI instantiations)
+  bool axi = false;          // diag_inertia && axisym && !iso
+  bool slides = false;
+  bool slide_limits = false;  // any slide dof with a finite range
+  int max_slide = 0;          // largest slide-dof count of a joint
+  bool slides_world_only = true;  // every joint with a slide dof hangs off the world
+  bool has_weld = false;          // some joint has no hinge dof
+  bool planar = false;            // MBD_FLAG_PLANAR: the planar restatement (mbd_planar.h)
+  bool any_stiff = false;         // some hinge has a joint spring
+  int fl = 0;  // the planar kernels' model switches: 1 joint springs | 2 slide limits | 4 elasticity
+  // free root, isotropic inertia, no slide / weld joints, up to three children per link, multi-dof joints: the humanoids
+  bool humanoid_shape = false;
+  // DPP layout (kernels.h "lane exchange without the LDS"): lane <-> link tables when the tree fits the shifts
+  int dpp_family = -1;  // index into kDppFamilies, -1: shuffles
+  signed char lane_tab[32];
+  bool helpers = false;  // one link with 3..5 colliders and two idle lanes to lend them to (HELP instantiations)
+  bool spec = false;     // the model carries specification switches (MBD_SPEC_FLAGS): the general SPEC instantiations, 16 lanes
+};
 
-// the two-candidates-per-lane rollouts of the humanoid family (mbd_pk2.h; their own translation unit, mbd_pk2.hip, built
-// with the scheduler strategy that keeps dependent packed instructions apart).  hipErrorInvalidValue: no such instantiation.
-// wpe: 2 asks for the instantiation whose registers leave room for two wavefronts per SIMD (where there is one).
-// the 3-D instantiations the built-in humanoids and ant run (their own translation unit, mbd_hot3d.hip): which = 0 humanoid
-// with one collider per link, 1 / 2 up to five with / without helper lanes, 3 ant; rk = -1, nfr = 0: the run-time forms
-hipError_t launch_rollout_hot3d(int which, int rk, int nfr, int device, dim3 grid, dim3 block, size_t lds, hipStream_t stream,
-                                const RolloutParams& P);
-// the planar rollouts (mbd_planar.h; their own translation unit, mbd_planar.hip): lps lanes per candidate, the env's DPP
-// family, colliders per link, fl = the model's switches (1 springs | 2 slide limits | 4 elasticity), reward kind, n_frames
-// (0: run-time), no_fl: the general instantiation (lever MBD_NO_PLANAR_FLAGS), spec: the model carries specification
-// switches (MBD_SPEC_FLAGS): the SPEC instantiation (16 lanes, shuffle exchange) reads them at run time
-hipError_t launch_rollout_planar(int lps, int dpp_family, int max_col, int fl, int rk, int nfr, bool no_fl, bool spec, int device,
-                                 dim3 grid, dim3 block, size_t lds, hipStream_t stream, const RolloutParams& P);
-// whether an early-out instantiation (RolloutParams::cpw) exists for such a model with its switches as compile-time constants
-bool planar_has_early_out(int lps, int dpp_family, int max_col, int fl, int rk, int nfr);
-// fam: 0 the humanoid family, 1 ant (mbd_pk2.h)
-hipError_t launch_rollout_pk2(int fam, int maxcol, int rk, int nfr, int wpe, int device, dim3 grid, dim3 block, size_t lds,
-                              hipStream_t stream, const RolloutParams& P);
-// (maxcol, rk, nfr) the launcher would run for a model with `max_col` colliders per link, reward kind `rk`, `nfr` frames
-bool pk2_instantiation(int fam, int max_col, int rk, int nfr, int out[3]);
+// The lookups.  rk: the model's reward kind, or -1 (lever MBD_NO_REWARD_CONST); nfr: n_frames, or 0 (run-time).
+// mbd_hot3d.hip: the DPP instantiations the built-in humanoids and ant run (nullptr: the model is not one of those shapes);
+// helpers: the humanoid form that lends colliders to idle lanes (EnvShape::helpers, unless lever MBD_NO_HELPERS)
+RolloutKernel hot3d_kernel(const EnvShape& s, bool helpers, int rk, int nfr);
+// mbd_pk2.h, two candidates per lane: fam 0 the humanoid family, 1 ant; rk: the model's reward kind, no_rk: the run-time
+// form whatever it is; wpe 2 asks for the form whose registers leave room for two wavefronts per SIMD (where there is
+// one).  nullptr: no instantiation serves such a model.
+RolloutKernel pk2_kernel(int fam, int max_col, int rk, int nfr, bool no_rk, int wpe);
+// mbd_planar.h: no_fl: the general instantiation (lever MBD_NO_PLANAR_FLAGS); early_out: the form that takes
+// RolloutParams::cpw candidates per wavefront (nullptr where there is none)
+RolloutKernel planar_kernel(const EnvShape& s, int rk, int nfr, bool no_fl, bool early_out);
 
 }  // namespace mbd

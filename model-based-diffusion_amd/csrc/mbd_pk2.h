@@ -24,7 +24,7 @@
 namespace mbd {
 
 // (of the specification switches a tuned build may compile in, MBD_TUNED_SPEC, this kernel knows contact_avg; a build with any
-// other keeps its launches on the one-candidate kernels: rollout_uses_pk2, mbd_env.hip)
+// other keeps its launches on the one-candidate kernels: choose_rollout, mbd_env.hip)
 
 struct b2 {
   bool x, y;
@@ -384,13 +384,9 @@ __global__ __launch_bounds__(256, WPE) void rollout_pk2_kernel(RolloutParams P) 
       v0 = sub2(v, cross2(w, rc0));
     }
 
-    // (the renormalisations' rare exact side speculated like the planar kernels': -DMBD_PK2_SPECULATE; measured in round 6 —
-    // see below at the substep loop)
-#ifdef MBD_PK2_SPECULATE
-    constexpr int QM_FAST = NFR > 1 ? 1 : 0;
-#else
+    // (the renormalisations' rare exact side speculated like the planar kernels' was measured in round 6 and left off — see
+    // below at the substep loop)
     constexpr int QM_FAST = 0;
-#endif
     float q_worst = 0.0f;
     const v3x2 s_p = p, s_v = v, s_w = w;
     const q4x2 s_r = r;

@@ -29,7 +29,7 @@ extern "C" int mbd_plan_create(mbd_env* env, const mbd_plan_config* cfg, mbd_pla
   if (cfg->update_method > 0 && cfg->enable_demo) return fail(MBD_ERR_INVALID, "path-integral plans do not use demos");
   if (cfg->enable_demo) {
     if (!env->has_xref) return fail(MBD_ERR_INVALID, "enable_demo needs an env created with xref");
-    if (cfg->Hsample != 50) return fail(MBD_ERR_INVALID, "demos require Hsample == 50 (xref has 50 rows)");
+    if (cfg->Hsample != kXrefRows) return fail(MBD_ERR_INVALID, "demos require Hsample == %d (xref has %d rows)", kXrefRows, kXrefRows);
   }
   // logp0 [N] of the score kernel (and the cem selection's copy of the weights) live in LDS up to kLdsN candidates:
   // beyond the default 48 KB window the kernels' dynamic-LDS limit is raised; beyond kLdsN they use a plan-owned
@@ -231,7 +231,7 @@ extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sa
       lz.nz_impl = c.prng_impl; lz.nz_N = N; lz.nz_HNu = HNu;
       // (launches that take the job into spare workgroups need no second stream and none of its events: a record
       // behind every weighted mean idles the queue ~5.5 us, 1 % of a step — profiles/r02_timeline.txt)
-      noise_on_aux = !rollout_fuses_noise(e, c.shard_count);
+      noise_on_aux = !rollout_choice(e, c.shard_count, H).fuses_noise;
     }
   } else {
     // A1, materialised (car2d, path-integral updates): every rank samples ALL N candidate sequences.  A sharded plan
@@ -312,7 +312,7 @@ extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sa
   }
   // A5: the demo log-densities of the local shard come out of the rollout itself where its instantiation accumulates them
   // (round 6: no [shard][H][K][3] round trip, no second launch); otherwise from the tracked positions, below
-  const bool fused_lp = c.enable_demo && rollout_fuses_logpd(e, c.shard_count, H);
+  const bool fused_lp = c.enable_demo && rollout_choice(e, c.shard_count, H).fuses_logpd;
   int rc = launch_rollout(e, p->d_state0, d_cand + (size_t)c.shard_begin * HNu, c.shard_count, H, p->d_rewss,
                           d_rews_local, (c.enable_demo && !fused_lp) ? p->d_xpos : nullptr, nullptr, s, p->lazy ? &lz : nullptr,
                           nullptr, fused_lp ? d_logpd_local : nullptr);
@@ -454,7 +454,7 @@ extern "C" int mbd_plan_get_sigma(mbd_plan* p, float* sigma_out) {
 // it needs it and the step's stream carries no event (mbd_plan: the ring of three buffers).
 static int plan_keep_in_step(mbd_plan* p) {
   if (!p->lazy || !p->h_progress || p->seq == 0 || p->cfg.shares_device != 0) return MBD_OK;
-  if (rollout_fuses_noise(p->env, p->cfg.shard_count)) return MBD_OK;
+  if (rollout_choice(p->env, p->cfg.shard_count, p->cfg.Hsample).fuses_noise) return MBD_OK;
   p->kept_in_step = true;
   const auto w0 = std::chrono::steady_clock::now();
   while (progress_read(p->h_progress) < p->seq) {

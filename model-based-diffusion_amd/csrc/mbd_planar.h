@@ -113,12 +113,8 @@ __global__ __launch_bounds__(256) void rollout_planar_kernel(RolloutParams P) {
   static_assert(!EO || (MBD_TUNED_SPEC & MBD_FLAG_CONTACT6_GAUSS_SEIDEL) == 0, "EO: stage (6) as a packed pair (Jacobi)");
   constexpr bool DPP = D0 != 0;
   // the renormalisations' rare exact side is SPECULATED away (pl_qupdate QM = 1: no compare-to-branch latency in the substep;
-  // a control step in which it would have been taken is re-run).  MBD_PLANAR_NO_SPECULATE: the branches of rounds 1-5 (A/B).
-#ifdef MBD_PLANAR_NO_SPECULATE
-  constexpr bool SPECULATE = EO;
-#else
+  // a control step in which it would have been taken is re-run; against the branches of rounds 1-5: docs/experiments.md).
   constexpr bool SPECULATE = true;
-#endif
   constexpr int NSLOT = DPP ? (D1 != 0 ? 2 : 1) : kMaxChildren;
   rollout_progress(P);
   const int rblock = rollout_block(P);  // (noise workgroups and the idle ones of a pinned launch are done here: mbd_kernels.h)

@@ -79,7 +79,7 @@ extern "C" int mbd_sweep_create(mbd_env* env, const mbd_plan_config* cfg, int n_
   if (cfg->shard_begin != 0 || cfg->shard_count != cfg->Nsample) return fail(MBD_ERR_INVALID, "sweeps are not sharded");
   if ((size_t)cfg->Nsample * sizeof(float) > 48 * 1024)
     return fail(MBD_ERR_UNSUPPORTED, "plans of more than 12288 candidates fill the chip on their own: run them as plans");
-  if (cfg->enable_demo && (!env->has_xref || cfg->Hsample != 50)) return fail(MBD_ERR_INVALID, "enable_demo: the env has no demo / H != 50");
+  if (cfg->enable_demo && (!env->has_xref || cfg->Hsample != kXrefRows)) return fail(MBD_ERR_INVALID, "enable_demo: the env has no demo / H != %d", kXrefRows);
   HIP_TRY(hipSetDevice(env->device));
   std::unique_ptr<mbd_sweep> guard(new mbd_sweep());
   mbd_sweep* w = guard.get();
@@ -352,7 +352,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
       w->events_used++;
       HIP_TRY(hipEventRecord(ev0, s));
     }
-    const bool fused_lp = c.enable_demo && rollout_fuses_logpd(e, P * N, H, sw);  // (mbd_plan.hip: the log-densities out of the rollout)
+    const bool fused_lp = c.enable_demo && rollout_choice(e, P * N, H, sw).fuses_logpd;  // (mbd_plan.hip: the log-densities out of the rollout)
     int rc = launch_rollout(e, w->d_state0, w->d_eps[cur], P * N, H, w->d_rewss, w->d_rews,
                             (c.enable_demo && !fused_lp) ? w->d_xpos : nullptr, nullptr, s, &lz, sw, fused_lp ? w->d_lp : nullptr);
     if (rc != MBD_OK) return rc;

@@ -146,6 +146,17 @@ def debug_get(name: str) -> int:
     return v.value
 
 
+def debug_rollout_choice(model, n_cus: int, B: int, H: int, sweep_plan_N: int = 0, has_xref: bool = False) -> dict:
+    """include/mbd_hip_debug.h: the rollout launch the library picks for `model` (an MbdModel) — no device needed."""
+    lib = load()
+    lib.mbd_debug_rollout_choice.argtypes = [C.POINTER(MbdModel), _i, _i, _i, _i, _i, C.c_char_p, _i, C.POINTER(_i)]
+    name = C.create_string_buffer(512)
+    out = (_i * 8)()
+    check(lib.mbd_debug_rollout_choice(C.byref(model), n_cus, B, H, sweep_plan_N, int(has_xref), name, 512, out))
+    keys = ("grid", "block", "lds", "cpw", "wpe", "xcd_pin", "fuses_noise", "fuses_logpd")
+    return dict(zip(keys, list(out)), name=name.value.decode())
+
+
 def check(rc: int) -> None:
     if rc != MBD_OK:
         raise MbdError(rc, load().mbd_last_error().decode())

@@ -139,6 +139,67 @@ def test_product_does_not_import_the_oracle():
                 assert "oracle" not in text.lower().replace("checker", ""), f"{f} mentions the oracle"
 
 
+
+def _choice_models():
+    from mbd_hip import mjcf
+    from mbd_hip.envs import specs
+    from mbd_hip.model import MbdModel
+    from mbd_hip import _capi
+
+    def builtin(name):
+        st = MbdModel()
+        _capi.check(_capi.load().mbd_builtin_model(name.encode(), C.byref(st)))
+        return st
+
+    def collide_all(name):
+        s = specs.SPECS[name]
+        return mjcf.load(os.path.join(ROOT, "model-based-diffusion_amd", "assets", s["xml"]), env_name=name,
+                         n_frames=s["n_frames"], reset_noise=s["reset_noise"], reward_params=s.get("reward_params", ()),
+                         gear_override=s.get("gear_override", ()), collide_all_capsules=True, warn_unstable=False).to_struct()
+    models = {n: builtin(n) for n in ("cartpole", "hopper", "walker2d", "halfcheetah", "ant", "humanoidrun", "humanoidtrack",
+                                      "humanoidstandup")}
+    models["halfcheetah_collide_all"] = collide_all("halfcheetah")
+    models["ant_spec"] = load_model("ant").with_spec(8 | 128).to_struct()
+    models["hopper_spec"] = load_model("hopper").with_spec(4 | 8 | 16 | 32).to_struct()
+    return models
+
+
+def test_rollout_choice_table(lib, levers):
+    """csrc/mbd_env.hip::choose_rollout, without a device, against the launches recorded on an MI355X
+    (tests/golden/rollout_choices.json): for every built-in model, the collide-all halfcheetah and two models with a
+    specification word of their own, at B = 1 ... 16384 as one rollout, in plans and in sweeps of an even and an odd
+    plan size, under each lever that changes the choice — the same instantiation, workgroups (with the XCD pin's) and
+    block, and the same noise / demo log-density jobs (the LDS reservation shows in the trace only through the pin and
+    the noise job, which both require it).  Every instantiation computes the same bits: this table is what notices a
+    launch sent to another (slower) kernel."""
+    import json
+    from mbd_hip import _capi
+    from mbd_hip.model import SPEC_MASK
+    with open(os.path.join(ROOT, "tests", "golden", "rollout_choices.json")) as f:
+        table = json.load(f)
+    models = _choice_models()
+    for name in ("ant_spec", "hopper_spec"):
+        assert int(models[name].flags) & SPEC_MASK != lib.mbd_tuned_spec(), name
+    by_cfg = {}
+    for row in table["rows"]:
+        by_cfg.setdefault(row[0], []).append(row)
+    assert len(table["levers"]) == 18 and len(table["rows"]) == 18 * len(models) * 13
+    for ci, cfg in enumerate(table["levers"]):
+        for k in set(name for c in table["levers"] for name in c):
+            levers(**{k: cfg.get(k, -1)})
+        for _, model, B, plan_N, kernel, grid, block, noise, logpd in by_cfg[ci]:
+            c = _capi.debug_rollout_choice(models[model], 256, B, 50, plan_N, model == "humanoidtrack")
+            where = (cfg, model, B, plan_N)
+            assert c["name"] == table["kernels"][kernel], where
+            assert c["block"] == block, where
+            if grid is not None:
+                assert c["grid"] * (8 if c["xcd_pin"] else 1) == grid, where
+            if noise is not None:
+                assert bool(c["fuses_noise"]) == noise, where
+            if logpd is not None:
+                assert bool(c["fuses_logpd"]) == logpd, where
+
+
 def test_dpp_lane_layouts_of_the_builtin_models(lib):
     """Host logic of the DPP exchange (csrc/mbd_env.hip::find_dpp_layout): every built-in tree gets a layout in
     which each link sits on its own lane of the LPS-lane group and every s-th child (in link order) sits exactly
