@@ -25,6 +25,14 @@ int mbd_debug_rollout_choice(const mbd_model_t* model, int n_cus, int B, int H, 
                              char* name, int cap, int out[8]);
 /* per-wavefront clock records of the 3-D rollout kernels (tools/probes/rollout_timeline.py); d_buf: device, caller-owned */
 int mbd_debug_set_clock_buffer(mbd_env* env, void* d_buf);
+/* the arithmetic primitives of csrc/mbd_math.h over host arrays, one GPU thread per element (op: the primitive's name
+ * there, e.g. "div_", "angle_unit2", "qnormalize_qm<1>"; mbd_debug_math_name(k) lists them, NULL past the last).
+ * in: [n][k_in] row-major, out: [n][k_out], both fixed per op (mbd_debug_math_arity; no device needed).  Packed ops take
+ * elements (2j, 2j+1) as the two halves of their pairs.  Argument errors first (unknown op, n outside [0, 2^26], NULL
+ * arrays), then MBD_ERR_NO_DEVICE. */
+const char* mbd_debug_math_name(int k);
+int mbd_debug_math_arity(const char* op, int* k_in, int* k_out);
+int mbd_debug_eval_math(const char* op, long long n, const float* in, float* out);
 #ifdef __cplusplus
 }
 #endif

@@ -201,25 +201,6 @@ __device__ __forceinline__ axes3x2 qaxes2(q4x2 q) {
   return a;
 }
 
-// atan2 with a = min/max in [0,1], atan(a) = a P(a^2) (A&S 4.4.49), octant fix-ups; branch-free
-MBD_HD float atan2_(float y, float x) {
-  float ax = fabs_(x), ay = fabs_(y);
-  float mx = fmax_(ax, ay), mn = fmin_(ax, ay);
-  float a = mx == 0.0f ? 0.0f : mn / mx;
-  float s = a * a;
-  float p = 0.0028662257f;
-  p = ffma(p, s, -0.0161657367f);
-  p = ffma(p, s, 0.0429096138f);
-  p = ffma(p, s, -0.0752896400f);
-  p = ffma(p, s, 0.1065626393f);
-  p = ffma(p, s, -0.1420889944f);
-  p = ffma(p, s, 0.1999355085f);
-  p = ffma(p, s, -0.3333314528f);
-  float r = ffma(p * s, a, a);
-  r = ay > ax ? 1.57079632679489661923f - r : r;
-  r = x < 0.0f ? 3.14159265358979323846f - r : r;
-  return y < 0.0f ? -r : r;
-}
 // ---- the solver's division -------------------------------------------------------------------------------
 // numerators below 1e-28 are flushed to zero (or clamped there when non-negative by construction); with that, and
 // denominators in [1e-20, 1e10], the sequence below rounds exactly like IEEE division:

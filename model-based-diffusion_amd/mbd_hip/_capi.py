@@ -157,6 +157,39 @@ def debug_rollout_choice(model, n_cus: int, B: int, H: int, sweep_plan_N: int = 
     return dict(zip(keys, list(out)), name=name.value.decode())
 
 
+def debug_math_ops() -> list:
+    """include/mbd_hip_debug.h: the names of the primitives mbd_debug_eval_math evaluates."""
+    lib = load()
+    lib.mbd_debug_math_name.argtypes = [_i]
+    lib.mbd_debug_math_name.restype = C.c_char_p
+    names, k = [], 0
+    while (n := lib.mbd_debug_math_name(k)) is not None:
+        names.append(n.decode())
+        k += 1
+    return names
+
+
+def debug_math_arity(op: str) -> tuple:
+    """(inputs, outputs) per element of primitive `op` — no device needed."""
+    lib = load()
+    lib.mbd_debug_math_arity.argtypes = [C.c_char_p, C.POINTER(_i), C.POINTER(_i)]
+    k_in, k_out = _i(0), _i(0)
+    check(lib.mbd_debug_math_arity(op.encode(), C.byref(k_in), C.byref(k_out)))
+    return k_in.value, k_out.value
+
+
+def debug_eval_math(op: str, x) -> np.ndarray:
+    """include/mbd_hip_debug.h: primitive `op` of csrc/mbd_math.h on the GPU, one thread per row of x ([n][k_in] float32,
+    or [n] when k_in = 1); returns [n][k_out] ([n] when k_out = 1)."""
+    lib = load()
+    k_in, k_out = debug_math_arity(op)
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, k_in)
+    out = np.empty((x.shape[0], k_out), np.float32)
+    lib.mbd_debug_eval_math.argtypes = [C.c_char_p, C.c_longlong, _vp, _vp]
+    check(lib.mbd_debug_eval_math(op.encode(), x.shape[0], x.ctypes.data, out.ctypes.data))
+    return out[:, 0] if k_out == 1 else out
+
+
 def check(rc: int) -> None:
     if rc != MBD_OK:
         raise MbdError(rc, load().mbd_last_error().decode())

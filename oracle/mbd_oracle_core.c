@@ -468,6 +468,105 @@ ORC_API void orc_sp_rot(const float v[3], const float q[4], float o[3]) { sp_rot
 ORC_API void orc_sp_qmul(const float a[4], const float b[4], float o[4]) { sp_qmul(a, b, o); }
 ORC_API float orc_sp_sum(const float* x, int n) { return sum_f32(x, n); }
 
+/* The primitives by the names of the kernels' copy (csrc/mbd_math.h; the GPU side is mbd_debug_eval_math), over arrays:
+ * in [n][k_in], out [n][k_out] row-major.  The checker has no packed forms: a packed name maps to its scalar sp_*
+ * function — the kernels' claim that the pairs round component-wise like the scalars is what tests/test_gpu_math.py
+ * holds them to.  Element j of a packed op is the low half of its pair when j is even (div2_sp_, div2x2_sp_: the signed
+ * numerator sits in the low half).  qnormalize_qm<1> (the kernels' speculative series side) has the values of
+ * sp_qnormalize wherever its `worst` output |n2 - 1| is within 0.05 — the kernels re-run a control step in which it is
+ * not — and `worst` itself. */
+enum {
+  SP_RCP, SP_DIV, SP_DIV_POS, SP_DIV_SP, SP_DIV2X2, SP_DIV2X2_SP, SP_SQRT_FLOOR, SP_ANGLE_UNIT, SP_SINCOS, SP_EXP, SP_LOG,
+  SP_LOG1P, SP_ERFINV, SP_UNIFORM, SP_NORMAL, SP_QNORMALIZE, SP_QNORMALIZE_WORST, SP_QROTVEC_RAW, SP_QROTVEC, SP_ROT,
+  SP_IROT, SP_IROT_Z, SP_QMUL, SP_QAXES, SP_DOT, SP_CROSS, SP_MIN, SP_MAX, SP_CLIP
+};
+static const struct {
+  const char* name;
+  int k_in, k_out, sp;
+} orc_ops[] = {
+    {"rcp_exact", 1, 1, SP_RCP},           {"div_", 2, 1, SP_DIV},
+    {"div_pos_", 2, 1, SP_DIV_POS},        {"div2_", 2, 1, SP_DIV},
+    {"div2_pos_", 2, 1, SP_DIV_POS},       {"div2_sp_", 2, 1, SP_DIV_SP},
+    {"div2x2_", 4, 2, SP_DIV2X2},          {"div2x2_sp_", 4, 2, SP_DIV2X2_SP},
+    {"sqrt_floor", 1, 1, SP_SQRT_FLOOR},   {"angle_unit", 2, 1, SP_ANGLE_UNIT},
+    {"angle_unit_cpos", 2, 1, SP_ANGLE_UNIT}, {"angle_unit2", 2, 1, SP_ANGLE_UNIT},
+    {"sincos_", 1, 2, SP_SINCOS},          {"exp_", 1, 1, SP_EXP},
+    {"log_", 1, 1, SP_LOG},                {"log1p_", 1, 1, SP_LOG1P},
+    {"erfinv_", 1, 1, SP_ERFINV},          {"bits_to_uniform", 3, 1, SP_UNIFORM},
+    {"bits_to_normal", 1, 1, SP_NORMAL},   {"qnormalize", 4, 4, SP_QNORMALIZE},
+    {"qnormalize_qm<1>", 4, 5, SP_QNORMALIZE_WORST}, {"qnormalize_qm<2>", 4, 4, SP_QNORMALIZE},
+    {"qrotvec_raw", 7, 4, SP_QROTVEC_RAW}, {"qrotvec", 7, 4, SP_QROTVEC},
+    {"rot", 7, 3, SP_ROT},                 {"irot", 7, 3, SP_IROT},
+    {"irot_z", 5, 3, SP_IROT_Z},           {"qmul", 8, 4, SP_QMUL},
+    {"qaxes", 4, 9, SP_QAXES},             {"dot", 6, 1, SP_DOT},
+    {"cross", 6, 3, SP_CROSS},             {"rot2", 7, 3, SP_ROT},
+    {"qmul2", 8, 4, SP_QMUL},              {"qaxes2", 4, 9, SP_QAXES},
+    {"dot2", 6, 1, SP_DOT},                {"cross2", 6, 3, SP_CROSS},
+    {"fmin_", 2, 1, SP_MIN},               {"fmax_", 2, 1, SP_MAX},
+    {"fclip", 3, 1, SP_CLIP},
+};
+#define ORC_NUM_OPS ((int)(sizeof(orc_ops) / sizeof(orc_ops[0])))
+static int orc_find_op(const char* op) {
+  for (int k = 0; op && k < ORC_NUM_OPS; ++k)
+    if (strcmp(orc_ops[k].name, op) == 0) return k;
+  return -1;
+}
+ORC_API const char* orc_sp_eval_name(int k) { return k >= 0 && k < ORC_NUM_OPS ? orc_ops[k].name : NULL; }
+ORC_API int orc_sp_eval_arity(const char* op, int* k_in, int* k_out) {
+  int id = orc_find_op(op);
+  if (id < 0 || !k_in || !k_out) return -1;
+  *k_in = orc_ops[id].k_in;
+  *k_out = orc_ops[id].k_out;
+  return 0;
+}
+ORC_API int orc_sp_eval(const char* op, long long n, const float* in, float* out) {
+  int id = orc_find_op(op);
+  if (id < 0 || n < 0 || !in || !out) return -1;
+  const int ki = orc_ops[id].k_in, ko = orc_ops[id].k_out, sp = orc_ops[id].sp;
+  for (long long j = 0; j < n; ++j) {
+    const float* a = in + j * ki;
+    float* o = out + j * ko;
+    float q[4];
+    uint32_t bits;
+    switch (sp) {
+      case SP_RCP: o[0] = sp_div(1.0f, a[0]); break;
+      case SP_DIV: o[0] = sp_div(a[0], a[1]); break;
+      case SP_DIV_POS: o[0] = sp_div_pos(a[0], a[1]); break;
+      case SP_DIV_SP: o[0] = (j & 1) == 0 ? sp_div(a[0], a[1]) : sp_div_pos(a[0], a[1]); break;
+      case SP_DIV2X2: o[0] = sp_div_pos(a[0], a[1]); o[1] = sp_div_pos(a[2], a[3]); break;
+      case SP_DIV2X2_SP: o[0] = sp_div(a[0], a[1]); o[1] = sp_div_pos(a[2], a[3]); break;
+      case SP_SQRT_FLOOR: o[0] = sp_sqrt_floor(a[0]); break;
+      case SP_ANGLE_UNIT: o[0] = sp_angle_unit(a[0], a[1]); break;
+      case SP_SINCOS: sp_sincos(a[0], &o[0], &o[1]); break;
+      case SP_EXP: o[0] = sp_exp_f32(a[0]); break;
+      case SP_LOG: o[0] = sp_log_f32(a[0]); break;
+      case SP_LOG1P: o[0] = sp_log1p_f32(a[0]); break;
+      case SP_ERFINV: o[0] = orc_erfinv_f32(a[0]); break;
+      case SP_UNIFORM: memcpy(&bits, a, 4); o[0] = bits_to_uniform(bits, a[1], a[2]); break;
+      case SP_NORMAL:
+        memcpy(&bits, a, 4);
+        o[0] = (float)1.4142135623730951 * orc_erfinv_f32(bits_to_uniform(bits, nextafterf(-1.0f, 0.0f), 1.0f));
+        break;
+      case SP_QNORMALIZE_WORST: o[4] = sp_abs(sp_fma(a[0], a[0], sp_fma(a[1], a[1], sp_fma(a[2], a[2], a[3] * a[3]))) - 1.0f);
+        /* fall through */
+      case SP_QNORMALIZE: memcpy(q, a, sizeof(q)); sp_qnormalize(q); memcpy(o, q, sizeof(q)); break;
+      case SP_QROTVEC_RAW: memcpy(q, a, sizeof(q)); sp_qrotvec_raw(q, a + 4); memcpy(o, q, sizeof(q)); break;
+      case SP_QROTVEC: memcpy(q, a, sizeof(q)); sp_qrotvec(q, a + 4); memcpy(o, q, sizeof(q)); break;
+      case SP_ROT: sp_rot(a, a + 3, o); break;
+      case SP_IROT: sp_irot(a, a + 3, o); break;
+      case SP_IROT_Z: sp_irot_z(a[0], a + 1, o); break;
+      case SP_QMUL: sp_qmul(a, a + 4, o); break;
+      case SP_QAXES: sp_qaxes(a, o, o + 3, o + 6); break;
+      case SP_DOT: o[0] = sp_dot3(a, a + 3); break;
+      case SP_CROSS: sp_cross3(a, a + 3, o); break;
+      case SP_MIN: o[0] = sp_min(a[0], a[1]); break;
+      case SP_MAX: o[0] = sp_max(a[0], a[1]); break;
+      case SP_CLIP: o[0] = sp_clip(a[0], a[1], a[2]); break;
+    }
+  }
+  return 0;
+}
+
 /* ------------------------------------------------------------------------------------------------ */
 /* path-integral baselines  (mbd/planners/path_integral.py:33-52,111-127)                            */
 /*   logp0 = (rews - mean)/std/temp WITHOUT the zero-std guard (:123); weights = softmax (:124);     */

@@ -111,11 +111,39 @@ class Oracle:
         lib.orc_sp_qmul.argtypes = [_f32p, _f32p, _f32p]
         lib.orc_sp_sum.argtypes = [_f32p, C.c_int]
         lib.orc_sp_sum.restype = C.c_float
+        lib.orc_sp_eval.argtypes = [C.c_char_p, C.c_longlong, _f32p, _f32p]
+        lib.orc_sp_eval_arity.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.orc_sp_eval_name.argtypes = [C.c_int]
+        lib.orc_sp_eval_name.restype = C.c_char_p
         lib.orc_pi_update.argtypes = [C.c_int, C.c_int, C.c_int, _f32p, C.c_float, _f32p, _f32p, _f32p, _f32p, _f32p]
         lib.orc_pi_update.restype = C.c_float
         lib.orc_mean_h.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         lib.orc_real_bytes.restype = C.c_int
         lib.orc_model_bytes.restype = C.c_int
+
+    # ---- the numerical-contract primitives by the kernels' names (csrc/mbd_math.h) -----------------------------
+    def sp_ops(self) -> list:
+        names, k = [], 0
+        while (n := self.lib.orc_sp_eval_name(k)) is not None:
+            names.append(n.decode())
+            k += 1
+        return names
+
+    def sp_arity(self, op: str) -> tuple:
+        k_in, k_out = C.c_int(), C.c_int()
+        if self.lib.orc_sp_eval_arity(op.encode(), C.byref(k_in), C.byref(k_out)) != 0:
+            raise ValueError(f"no primitive named {op}")
+        return k_in.value, k_out.value
+
+    def sp_eval(self, op: str, x) -> np.ndarray:
+        """orc_sp_eval: primitive `op` on the rows of x ([n][k_in] float32, or [n] when k_in = 1); [n][k_out] out
+        ([n] when k_out = 1) — the same shapes as mbd_hip._capi.debug_eval_math."""
+        k_in, k_out = self.sp_arity(op)
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, k_in)
+        out = np.empty((x.shape[0], k_out), np.float32)
+        if self.lib.orc_sp_eval(op.encode(), x.shape[0], x.reshape(-1), out.reshape(-1)) != 0:
+            raise ValueError(f"orc_sp_eval({op})")
+        return out[:, 0] if k_out == 1 else out
 
     # ---- PRNG -------------------------------------------------------------------------------------
     def threefry2x32(self, k0, k1, c0, c1):

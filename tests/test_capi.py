@@ -247,6 +247,34 @@ def test_c_abi_argument_errors_without_a_device(lib):
     n = C.c_int(-1)
     assert lib.mbd_device_count(C.byref(n)) == 0 and n.value >= 0
     assert lib.mbd_version() >= 1
+    # the primitive evaluator of include/mbd_hip_debug.h: unknown op, n < 0 and NULL arrays first, then the device
+    lib.mbd_debug_eval_math.argtypes = [C.c_char_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    buf = np.zeros(8, np.float32)
+    p = buf.ctypes.data
+    assert lib.mbd_debug_eval_math(b"no_such_op", 1, p, p) == INVALID and b"no_such_op" in lib.mbd_last_error()
+    assert lib.mbd_debug_eval_math(None, 1, p, p) == INVALID
+    assert lib.mbd_debug_eval_math(b"div_", -1, p, p) == INVALID
+    assert lib.mbd_debug_eval_math(b"div_", 1, None, p) == INVALID
+    assert lib.mbd_debug_eval_math(b"div_", 1, p, None) == INVALID
+    if _capi.device_count() == 0:
+        assert lib.mbd_debug_eval_math(b"div_", 1, p, p) == _capi.MBD_ERR_NO_DEVICE
+        assert lib.mbd_debug_eval_math(b"div_", 0, p, p) == _capi.MBD_ERR_NO_DEVICE
+        with pytest.raises(_capi.MbdError) as e:
+            _capi.debug_eval_math("angle_unit2", np.zeros((4, 2), np.float32))
+        assert e.value.code == _capi.MBD_ERR_NO_DEVICE
+
+
+def test_math_primitive_tables_agree_between_library_and_checker(lib, orc):
+    """mbd_debug_eval_math (csrc/mbd_math.h) and orc_sp_eval (oracle/spec_math.h) know the same primitives by the same
+    names with the same inputs and outputs per element — the interface tests/test_gpu_math.py compares them through.
+    No device needed."""
+    from mbd_hip import _capi
+    ops = _capi.debug_math_ops()
+    assert ops == orc.sp_ops() and len(ops) == 39
+    for op in ops:
+        assert _capi.debug_math_arity(op) == orc.sp_arity(op), op
+    with pytest.raises(_capi.MbdError):
+        _capi.debug_math_arity("atan2_")
 
 
 def test_round3_entry_points_fail_loudly_without_a_device_and_levers_work_on_the_host(lib):

@@ -1,7 +1,11 @@
-"""The numerical-contract primitives (oracle/spec_math.h) against numpy in float64."""
+"""The numerical-contract primitives (oracle/spec_math.h) against numpy in float64; the kernels' copy of the same
+primitives is held to the checker and to the same bounds in tests/test_gpu_math.py."""
 import ctypes as C
 
 import numpy as np
+import pytest
+
+import math_inputs as mi
 
 
 def test_atan2_and_asin_accuracy(orc):
@@ -91,3 +95,49 @@ def test_car2d_collision_threshold_is_the_sqrt_comparison():
     assert float(T) == 0.09000000357627869
     assert np.array_equal(s < c, xs < T)
     assert np.all(np.diff(s) >= 0)
+
+
+# ---- every primitive of the contract, by the kernels' names, against float64 (tests/math_inputs.py) ------------------
+SP_OPS = ["rcp_exact", "div_", "div_pos_", "div2_", "div2_pos_", "div2_sp_", "div2x2_", "div2x2_sp_", "sqrt_floor",
+          "angle_unit", "angle_unit_cpos", "angle_unit2", "sincos_", "exp_", "log_", "log1p_", "erfinv_",
+          "bits_to_uniform", "bits_to_normal", "qnormalize", "qnormalize_qm<1>", "qnormalize_qm<2>", "qrotvec_raw",
+          "qrotvec", "rot", "irot", "irot_z", "qmul", "qaxes", "dot", "cross", "rot2", "qmul2", "qaxes2", "dot2", "cross2",
+          "fmin_", "fmax_", "fclip"]
+
+
+def test_checker_names_every_primitive(orc):
+    assert orc.sp_ops() == SP_OPS
+
+
+@pytest.mark.parametrize("op", SP_OPS)
+def test_checker_primitive_against_float64(orc, op):
+    """The checker's copy (oracle/spec_math.h) on the op's whole input set: exact where the contract is IEEE (division,
+    square root, the uniform bit trick), within a bound just above its measured worst case elsewhere — so that a shared
+    mistake of both copies (a mistyped coefficient, a wrong octant) fails here, where bit-equality cannot see it."""
+    x = mi.inputs(op)
+    mi.check_contract(op, x, orc.sp_eval(op, x))
+
+
+@pytest.mark.parametrize("defect", [1e-7, -1e-6, 1e-6, 1e-5, -3e-5])
+def test_angle_unit_error_grows_with_the_norm_defect(orc, defect):
+    """3.4e-7 at a defect of 1e-7, 1.2e-6 at 1e-6, 1.0e-5 at 1e-5: bounded by 3e-7 + 1.05 |defect|."""
+    x = mi.angle_inputs(defect, n=1 << 20)
+    mi.check_angle(x, orc.sp_eval("angle_unit", x), rounded=False)
+
+
+def test_angle_unit_signed_zeros_follow_arctan2(orc):
+    s = np.float32([0.0, -0.0, 0.0, -0.0])
+    c = np.float32([-1.0, -1.0, 1.0, 1.0])
+    got = orc.sp_eval("angle_unit", mi.pairs(s, c))
+    want = np.arctan2(s, c)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (got, want)  # +-pi and +-0
+
+
+def test_sampler_uniforms_are_jax_bit_trick(orc):
+    """All 2^23 sampler uniforms of mi.sampler_uniforms (numpy's restatement of the bit trick) are what the checker's
+    bits_to_uniform makes of the same bits, and they lie in [nextafter(-1, 0), 1)."""
+    u, b = mi.sampler_uniforms()
+    lo = np.float32(-0.99999994)
+    got = orc.sp_eval("bits_to_uniform", mi.pairs(b.view(np.float32), np.full(b.size, lo), np.ones(b.size)))
+    assert np.array_equal(got.view(np.uint32), u.view(np.uint32))
+    assert u.min() == lo and u.max() < 1.0 and np.unique(u).size > (1 << 22)
