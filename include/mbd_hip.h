@@ -368,6 +368,31 @@ int mbd_plan_run(mbd_plan* plan, const uint32_t key[2], float* mu_0ts_out, float
 /* rew_final = rollout_us(state_init, Y).mean() for one plan Y [H][Nu] HOST (mbd_planner.py:179-180) */
 int mbd_plan_eval(mbd_plan* plan, const float* Y, float* rew_final_out);
 
+/* ---- receding horizon (no counterpart in the reference, which plans open loop) ---- */
+typedef struct mbd_mpc_config {
+  int32_t n_ticks;     /* T >= 1 */
+  int32_t warm_steps;  /* K: diffusion steps i = K..1 of every tick after the first, 1 <= K <= Ndiffuse-1 */
+  int32_t exec_steps;  /* E: control steps executed per tick, 1 <= E < Hsample; the mean then shifts by E */
+  int32_t reserved[5]; /* must be 0 */
+} mbd_mpc_config;
+/* Closed-loop episode from the plan's state0 s_0: every tick t replans from the state s_t the system reached and executes the
+ * first E rows of that plan through the env's rollout path, on the device, with no host synchronisation between ticks.
+ *   rng = key; Ybar = zeros; i_start = Ndiffuse-1                  (tick 0: a cold plan, exactly mbd_plan_run's loop)
+ *   per tick t:  rng, k_t = split(rng)
+ *                Ybar = reverse_once(i, ., Ybar) from s_t for i = i_start .. 1, key chain from k_t  -> M_t [H][Nu]
+ *                rewards[tE .. tE+E), s_{t+1} = rollout(s_t, M_t[0:E])   (rows fed unclipped; the env clips)
+ *                Ybar = M_t shifted E rows forward, the last E rows 0 (the cold prior); i_start = K
+ * so tick 0 equals mbd_plan_run(plan, k_0) bit for bit, and an episode of T ticks is a prefix of one of T+1.  K sets both
+ * the cost of a tick and the noise level sigma_K it restarts from.
+ * HOST outputs, each may be NULL: actions_out [T*E][Nu] (the rows executed), rewards_out [T*E], states_out
+ * [T+1][state_size] (s_0 .. s_T), means_out [T][H][Nu] (M_t); loop_seconds_out: wall time of the tick loop.
+ * Synchronous; ONE device->host copy per output at the end.  The plan's state0 is unchanged afterwards.
+ * MBD plans only (update_method 0, unsharded, no demos): NULL plan / config / key and out-of-range fields ->
+ * MBD_ERR_INVALID (the NULL checks before any device access), enable_demo or a path-integral update -> MBD_ERR_UNSUPPORTED
+ * (demos are time-indexed: their clock would have to follow the episode), a sharded plan -> MBD_ERR_STATE. */
+int mbd_plan_run_mpc(mbd_plan* plan, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
+                     float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out);
+
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
  * candidates Y0s [Nsample][H][Nu] (plans that keep normals instead form them here, from the normals, sigma_i and the
  * Ybar_i of the last step — between phase 1 and phase 2 the caller's d_Ybar_i must still be unchanged), the shard's

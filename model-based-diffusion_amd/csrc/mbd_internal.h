@@ -119,6 +119,8 @@ struct mbd_plan {
   // STARTED — every rollout launch of the plan stores its sequence number into h_progress (pinned host memory) as it
   // starts, and the host looks there.  A caller that runs ahead of the device (mbd_plan_run's loop, the async leg of the
   // bench) gets the event-ordered form: a mark on the step's stream in front of the rollout, a wait on the aux stream.
+  // (Other launches between two steps on the step's stream — a receding-horizon episode's two per tick — change neither
+  // argument: they are stream-ordered behind the weighted mean and in front of the next rollout.)
   bool lazy = false;
   float* d_eps[3] = {nullptr, nullptr, nullptr};
   int eps_cur = 0;                 // buffer of the step in flight (set by sample_rollout, read by score_update / peek)
@@ -139,6 +141,11 @@ struct mbd_plan {
   hipEvent_t ev_noise[3] = {nullptr, nullptr, nullptr}, ev_wm = nullptr;
   float *d_sigma = nullptr, *d_spread = nullptr;  // path-integral plans
   int* d_idx = nullptr;
+  // receding-horizon episodes (mbd_plan_run_mpc): the two states its ticks ping-pong between [2][state_size], and the
+  // episode's logs — states [T+1][state_size], means [T][HNu], rewards [T][H-1] (E < H rows per tick) — for up to
+  // mpc_ticks ticks, grown on demand.  Plan-owned, so that nothing an episode leaves behind points at freed memory.
+  float *d_mpc_state = nullptr, *d_mpc_states = nullptr, *d_mpc_means = nullptr, *d_mpc_rewards = nullptr;
+  size_t mpc_ticks = 0;
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
@@ -154,6 +161,7 @@ struct mbd_plan {
     (void)hipFree(d_mu); (void)hipFree(d_rewmeans); (void)hipFree(d_scratch);
     (void)hipFree(d_sigma); (void)hipFree(d_spread); (void)hipFree(d_idx); (void)hipFree(d_wm_partial); (void)hipFree(d_lg);
     (void)hipFree(d_eps[0]); (void)hipFree(d_eps[1]); (void)hipFree(d_eps[2]); (void)hipFree(d_ybar_keep);
+    (void)hipFree(d_mpc_state); (void)hipFree(d_mpc_states); (void)hipFree(d_mpc_means); (void)hipFree(d_mpc_rewards);
     if (h_progress) (void)hipHostFree(h_progress);
     for (int b = 0; b < 3; ++b)
       if (ev_noise[b]) (void)hipEventDestroy(ev_noise[b]);

@@ -1,6 +1,7 @@
 // mbd_plan.hip — the planner fast path (include/mbd_hip.h): one reverse-diffusion step split at its exchange point
 // (mbd_plan_sample_rollout / mbd_plan_score_update), the noise ring of lazy plans, and the loops over steps
-// (mbd_plan_reverse_once, mbd_plan_run, mbd_plan_eval, mbd_plan_peek).  mbd_planner.py:84-148,179-180.
+// (mbd_plan_reverse_once, mbd_plan_run, mbd_plan_eval, mbd_plan_peek; the receding-horizon loop mbd_plan_run_mpc).
+// mbd_planner.py:84-148,179-180.
 #include "mbd_internal.h"
 
 // ==================================================================================================
@@ -470,8 +471,10 @@ static int plan_keep_in_step(mbd_plan* p) {
   return MBD_OK;
 }
 
+// key_after: the Y0s_rng of the step that follows the LAST step (i == 1) of this loop in another one (a receding-horizon
+// episode's next tick), or nullptr
 static int reverse_once_impl(mbd_plan* p, int i, uint32_t key_inout[2], const float* d_Ybar_in, float* d_Ybar_out,
-                             float* d_rew_mean, hipStream_t s) {
+                             float* d_rew_mean, hipStream_t s, const uint32_t* key_after = nullptr) {
   if (p->cfg.shard_count != p->cfg.Nsample)
     return fail(MBD_ERR_STATE, "reverse_once on a sharded plan: use sample_rollout + all-gather + score_update");
   uint32_t keys[4];
@@ -484,6 +487,9 @@ static int reverse_once_impl(mbd_plan* p, int i, uint32_t key_inout[2], const fl
     host_split(adv, 2, p->cfg.prng_impl, nk);
     const uint32_t next_ks[2] = {nk[2], nk[3]};
     rc = mbd_plan_prefetch_noise(p, next_ks, s);
+    if (rc != MBD_OK) return rc;
+  } else if (key_after) {
+    rc = mbd_plan_prefetch_noise(p, key_after, s);
     if (rc != MBD_OK) return rc;
   }
   rc = mbd_plan_sample_rollout(p, i, ks, d_Ybar_in, p->d_rews, p->cfg.enable_demo ? p->d_lp : nullptr, s);
@@ -539,6 +545,97 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
     if (rc != MBD_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipMemcpy(rew_final_out, p->d_scratch, sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return MBD_OK;
+}
+
+// Receding horizon (include/mbd_hip.h): the host only enqueues — the key chain is host arithmetic, the executed state never
+// comes back — and keeps at most one step ahead of the device through plan_keep_in_step, as mbd_plan_run does.  A tick
+// boundary adds two launches on the plan's stream: the rollout of M_t's first E rows (the env's rollout path, one candidate:
+// what mbd_env_step runs) and mpc_boundary_kernel.  Both are stream-ordered between the tick's last weighted mean and the
+// next tick's first rollout, so the ring of noise buffers keeps its argument (mbd_plan), aux-stream form included.
+extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
+                                float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (!mc) return fail(MBD_ERR_INVALID, "mpc config is NULL");
+  if (!key) return fail(MBD_ERR_INVALID, "key is NULL");
+  const mbd_plan_config& c = p->cfg;
+  const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
+  if (T < 1) return fail(MBD_ERR_INVALID, "n_ticks=%d: must be >= 1", T);
+  if (K < 1 || K > Nd - 1) return fail(MBD_ERR_INVALID, "warm_steps=%d outside [1, Ndiffuse-1=%d]", K, Nd - 1);
+  if (E < 1 || E >= H) return fail(MBD_ERR_INVALID, "exec_steps=%d outside [1, Hsample=%d)", E, H);
+  for (int r = 0; r < 5; ++r)
+    if (mc->reserved[r] != 0) return fail(MBD_ERR_INVALID, "reserved[%d]=%d: must be 0", r, mc->reserved[r]);
+  if (c.enable_demo) return fail(MBD_ERR_UNSUPPORTED, "enable_demo: demos are time-indexed, an episode has no clock for them");
+  if (c.update_method != 0) return fail(MBD_ERR_UNSUPPORTED, "update_method=%d: receding horizon runs MBD plans only", c.update_method);
+  if (c.shard_count != c.Nsample)
+    return fail(MBD_ERR_STATE, "shard_count=%d of Nsample=%d: receding horizon runs unsharded plans", c.shard_count, c.Nsample);
+  mbd_env* e = p->env;
+  HIP_TRY(hipSetDevice(e->device));
+  const int HNu = p->HNu, Nu = e->action_size(), S = e->state_size();
+  if ((size_t)T > p->mpc_ticks) {
+    HIP_TRY(hipFree(p->d_mpc_states)); HIP_TRY(hipFree(p->d_mpc_means)); HIP_TRY(hipFree(p->d_mpc_rewards));
+    p->d_mpc_states = p->d_mpc_means = p->d_mpc_rewards = nullptr;
+    p->mpc_ticks = 0;
+    if (!p->d_mpc_state) HIP_TRY(hipMalloc(&p->d_mpc_state, sizeof(float) * 2 * (size_t)S));
+    HIP_TRY(hipMalloc(&p->d_mpc_states, sizeof(float) * ((size_t)T + 1) * S));
+    HIP_TRY(hipMalloc(&p->d_mpc_means, sizeof(float) * (size_t)T * HNu));
+    HIP_TRY(hipMalloc(&p->d_mpc_rewards, sizeof(float) * (size_t)T * (H - 1)));
+    p->mpc_ticks = (size_t)T;
+  }
+  // the ticks' rollouts read p->d_state0: s_0 there, then the ping-pong buffers; the plan's own buffer comes back on every exit
+  struct RestoreState0 {
+    mbd_plan* p;
+    float* s0;
+    ~RestoreState0() { p->d_state0 = s0; }
+  } restore{p, p->d_state0};
+  hipStream_t s = p->stream;
+  float* const ybar0 = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros at tick 0, shift_E(M_{t-1}) after
+  HIP_TRY(hipMemsetAsync(ybar0, 0, sizeof(float) * HNu, s));
+  HIP_TRY(hipMemcpyAsync(p->d_mpc_states, p->d_state0, sizeof(float) * S, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const auto t0 = std::chrono::steady_clock::now();
+  uint32_t rng[2] = {key[0], key[1]}, kk[4];
+  host_split(rng, 2, c.prng_impl, kk);  // rng, k_0 = split(rng)
+  for (int t = 0; t < T; ++t) {
+    uint32_t r[2] = {kk[2], kk[3]};  // k_t: the tick's key chain is mbd_plan_run's from it
+    rng[0] = kk[0]; rng[1] = kk[1];
+    // the Y0s_rng of tick t+1's first step, split(split(rng)[1])[1]: its normals are prepared beside tick t's last rollout
+    uint32_t after[4];
+    if (t + 1 < T) {
+      host_split(rng, 2, c.prng_impl, kk);
+      const uint32_t k_next[2] = {kk[2], kk[3]};
+      host_split(k_next, 2, c.prng_impl, after);
+    }
+    const float* cur = ybar0;
+    for (int i = t == 0 ? Nd - 1 : K; i >= 1; --i) {
+      float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
+      int rc = plan_keep_in_step(p);
+      if (rc != MBD_OK) return rc;
+      rc = reverse_once_impl(p, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, t + 1 < T ? after + 2 : nullptr);
+      if (rc != MBD_OK) return rc;
+      cur = nxt;
+    }
+    // execute M_t's first E rows from s_t, then the boundary: Ybar of tick t+1, the logs of M_t and s_{t+1}
+    float* s_next = p->d_mpc_state + (size_t)(t & 1) * S;
+    int rc = launch_rollout(e, p->d_state0, cur, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr, nullptr, s_next, s);
+    if (rc != MBD_OK) return rc;
+    hipLaunchKernelGGL(mpc_boundary_kernel, dim3(1), dim3(256), 0, s, cur, HNu, E * Nu, (const float*)s_next, S, ybar0,
+                       p->d_mpc_means + (size_t)t * HNu, p->d_mpc_states + (size_t)(t + 1) * S);
+    HIP_TRY(hipGetLastError());
+    p->d_state0 = s_next;
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  const auto t1 = std::chrono::steady_clock::now();
+  if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
+  if (rewards_out) HIP_TRY(hipMemcpy(rewards_out, p->d_mpc_rewards, sizeof(float) * (size_t)T * E, hipMemcpyDeviceToHost));
+  if (states_out) HIP_TRY(hipMemcpy(states_out, p->d_mpc_states, sizeof(float) * ((size_t)T + 1) * S, hipMemcpyDeviceToHost));
+  if (means_out || actions_out) {  // (the executed rows are M_t[0:E]: taken from the one copy of the means)
+    std::vector<float> tmp(means_out ? 0 : (size_t)T * HNu);
+    float* m = means_out ? means_out : tmp.data();
+    HIP_TRY(hipMemcpy(m, p->d_mpc_means, sizeof(float) * (size_t)T * HNu, hipMemcpyDeviceToHost));
+    if (actions_out)
+      for (int t = 0; t < T; ++t) memcpy(actions_out + (size_t)t * E * Nu, m + (size_t)t * HNu, sizeof(float) * (size_t)E * Nu);
   }
   return MBD_OK;
 }

@@ -149,6 +149,21 @@ static __global__ __launch_bounds__(256) void shift_kernel(const float* __restri
   Y0s[e] = fclip(y, -1.0f, 1.0f);
 }
 
+// The boundary between two ticks of a receding-horizon episode (mbd_plan_run_mpc), one workgroup, behind the rollout that
+// executed the tick's first E rows: the next tick's starting mean Ybar_K = shift_E(M) — M [H][Nu] moved E rows forward,
+// the vacated last E rows zero (the cold plan's prior) — and the episode's logs of M and of s_next, the state the executed
+// rows reached (it stays where it is: the host hands that buffer to the next tick's rollouts).  shift = E * Nu floats.
+static __global__ __launch_bounds__(256) void mpc_boundary_kernel(const float* __restrict__ M, int HNu, int shift,
+                                                            const float* __restrict__ s_next, int S,
+                                                            float* __restrict__ ybar_next, float* __restrict__ means_log,
+                                                            float* __restrict__ states_log) {
+  for (int e = threadIdx.x; e < HNu; e += blockDim.x) {
+    means_log[e] = M[e];
+    ybar_next[e] = e < HNu - shift ? M[e + shift] : 0.0f;
+  }
+  for (int e = threadIdx.x; e < S; e += blockDim.x) states_log[e] = s_next[e];
+}
+
 // ---- A5: demo log-densities ------------------------------------------------------------------------------
 // HumanoidTrack.eval_xref_logpd (humanoidtrack.py:98-106): xpos [B][H][K][3], xref [K][H][3].  One workgroup per
 // candidate: its K*H terms ((clip(|x - xref|, 0, .5) / .5)^2, the candidate's 3 K H floats are contiguous) are formed in

@@ -177,6 +177,24 @@ class Plan:
                                           C.byref(rf), C.byref(secs)))
         return mu, rm, rf.value, secs.value
 
+    def run_mpc(self, key, n_ticks: int, warm_steps: int, exec_steps: int = 1) -> dict:
+        """Closed-loop episode from the plan's state0 (include/mbd_hip.h mbd_plan_run_mpc): every tick replans from the
+        state reached, warm-started from the previous tick's mean shifted by ``exec_steps`` and diffused over steps
+        ``warm_steps``..1 (tick 0: a cold plan from ``key``'s first split), then executes its first ``exec_steps`` rows.
+        Returns dict(actions [T*E, Nu], rewards [T*E], states [T+1, state_size], means [T, H, Nu], seconds)."""
+        mc = _capi.MpcConfig()
+        mc.n_ticks, mc.warm_steps, mc.exec_steps = int(n_ticks), int(warm_steps), int(exec_steps)
+        T, E = max(mc.n_ticks, 0), max(mc.exec_steps, 0)
+        S = self.env._state_size
+        out = dict(actions=np.zeros((T * E, self.Nu), np.float32), rewards=np.zeros(T * E, np.float32),
+                   states=np.zeros((T + 1, S), np.float32), means=np.zeros((T, self.H, self.Nu), np.float32))
+        secs = C.c_double()
+        _capi.check(self.lib.mbd_plan_run_mpc(self.h, C.byref(mc), _capi.key_array(key), _capi.np_ptr(out["actions"]),
+                                              _capi.np_ptr(out["rewards"]), _capi.np_ptr(out["states"]),
+                                              _capi.np_ptr(out["means"]), C.byref(secs)))
+        out["seconds"] = secs.value
+        return out
+
     def get_sigma(self) -> float:
         v = C.c_float()
         _capi.check(self.lib.mbd_plan_get_sigma(self.h, C.byref(v)))
