@@ -62,10 +62,12 @@ def depth_substeps(model_struct, state, action, n_sub: int = 8):
 
 
 class Oracle:
-    def __init__(self, variant: str = "f32"):
-        path = os.path.join(_BUILD, f"liboracle_{variant}.so")
-        if not os.path.exists(path):
-            build()
+    def __init__(self, variant: str = "f32", path: str = None):
+        """path: a checker library built elsewhere (oracle/Makefile's `cov` target) instead of oracle/_build's `variant`."""
+        if path is None:
+            path = os.path.join(_BUILD, f"liboracle_{variant}.so")
+            if not os.path.exists(path):
+                build()
         self.lib = lib = C.CDLL(path)
         lib.orc_threefry2x32.argtypes = [C.c_uint32] * 4 + [C.POINTER(C.c_uint32)] * 2
         lib.orc_prng_key.argtypes = [C.c_uint64, _u32p]

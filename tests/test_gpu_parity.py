@@ -262,6 +262,9 @@ def test_custom_planar_model_sixteen_lane_groups(gpu, orc, planar):
 
 
 def _rollout_bitexact(gpu, orc, name, B, H, sigma):
+    """Rewards (and tracked positions where the env has a demo) of a rollout from a reset state, by BIT PATTERN
+    (state_inputs.same_bits: -0.0 is not +0.0) against the checker's."""
+    from state_inputs import same_bits
     from mbd_hip.envs import get_env
     env = get_env(name)
     st = env.reset(gpu.prng_key(3))
@@ -272,12 +275,12 @@ def _rollout_bitexact(gpu, orc, name, B, H, sigma):
     oe = _oenv(orc, env)
     ref = oe.rollout(np.asarray(st.pipeline_state, np.float32), us, want_xpos=want)
     if want:
-        assert np.array_equal(out[0].cpu().numpy(), ref[0]), f"{name}: rewards differ"
-        assert np.array_equal(out[1].cpu().numpy(), ref[1]), f"{name}: tracked positions differ"
+        same_bits(out[0].cpu().numpy(), ref[0], f"{name}: rewards")
+        same_bits(out[1].cpu().numpy(), ref[1], f"{name}: tracked positions")
     else:
         got = out.cpu().numpy()
         assert np.isfinite(got).all()
-        assert np.array_equal(got, ref), f"{name}: max |d| = {np.abs(got - ref).max()}"
+        same_bits(got, ref, f"{name}: rewards (max |d| = {np.abs(got - ref).max()})")
 
 
 @pytest.mark.parametrize("name", ["humanoidrun", "hopper", "halfcheetah", "cartpole", "car2d"])
@@ -299,7 +302,10 @@ def test_env_step_matches_oracle(gpu, orc, name):
         assert np.float32(st.reward) == np.float32(r_ref)
 
 
-def _one_step(gpu, orc, name, N, H, Nd, temp, impl, demo, i=None, env=None):
+def _one_step(gpu, orc, name, N, H, Nd, temp, impl, demo, i=None, env=None, state0=None):
+    """One diffusion step of a plan against the checker's, by bit pattern.  state0: a pipeline state to plan from instead of
+    the reset state (Plan.set_state0 only reads state.pipeline_state)."""
+    from state_inputs import same_bits
     from mbd_hip.envs import get_env
     from mbd_hip.planners.mbd_planner import Args, Plan
     from oracle import planner as op
@@ -310,6 +316,8 @@ def _one_step(gpu, orc, name, N, H, Nd, temp, impl, demo, i=None, env=None):
     key = gpu.prng_key(1)
     rng, rng_reset = gpu.prng_split(key, 2, impl)
     st = env.reset(rng_reset)
+    if state0 is not None:
+        st = st.replace(pipeline_state=np.asarray(state0, np.float32).reshape(np.asarray(st.pipeline_state).shape))
     plan = Plan(env, args)
     plan.set_state0(st)
     i = Nd - 1 if i is None else i
@@ -326,11 +334,11 @@ def _one_step(gpu, orc, name, N, H, Nd, temp, impl, demo, i=None, env=None):
     r2, Y_ref, rm_ref, det = op.reverse_once(orc, oe, np.asarray(st.pipeline_state, np.float32), i, rng, Ybar, sched,
                                              N, H, temp, impl, enable_demo=demo)
     assert np.array_equal(np.array([k[0], k[1]], np.uint32), r2)
-    assert np.array_equal(Y0s, det["Y0s"]), "sampled candidates differ"
-    assert np.array_equal(rewss, det["rewss"]), "rollout rewards differ"
-    assert np.array_equal(w, det["weights"]), "softmax weights differ"
-    assert np.float32(d_rm.item()) == np.float32(rm_ref)
-    assert np.array_equal(d_Y.cpu().numpy().reshape(H, -1), Y_ref), "Ybar_{i-1} differs"
+    same_bits(Y0s, det["Y0s"], "sampled candidates")
+    same_bits(rewss, det["rewss"], "rollout rewards")
+    same_bits(w, det["weights"], "softmax weights")
+    same_bits(np.float32(d_rm.item()), np.float32(rm_ref), "mean reward")
+    same_bits(d_Y.cpu().numpy().reshape(H, -1), Y_ref, "Ybar_{i-1}")
     assert abs(float(w.sum()) - 1.0) < 1e-5
     plan.close()
 
@@ -2150,17 +2158,10 @@ def _spec_env(name, bits, planar=None):
     return RigidBodyEnv(env_name, model=m.with_spec(bits))
 
 
-@pytest.mark.parametrize("name,planar,bits", [
-    ("humanoidstandup", None, 4), ("humanoidstandup", None, 8), ("humanoidstandup", None, 12), ("humanoidstandup", None, 16),
-    ("humanoidstandup", None, 64), ("humanoidstandup", None, 252),
-    ("humanoidrun", None, 64), ("humanoidrun", None, 16 | 8), ("humanoidtrack", None, 64 | 16),
-    ("ant", None, 4 | 8 | 16),
-    ("hopper", None, 4), ("hopper", None, 8), ("hopper", None, 16), ("hopper", None, 4 | 8 | 16 | 32),
-    ("walker2d", None, 12), ("halfcheetah", None, 4 | 8 | 16), ("cartpole", None, 16),
-    ("tripod", None, 32), ("tripod", None, 4 | 8 | 16 | 32), ("tripod", False, 4 | 8 | 16 | 32 | 128),
-    ("hopper", False, 4 | 8 | 16 | 128), ("walker2d", False, 128 | 8),
-    ("crab", None, 4), ("crab", None, 8), ("crab", None, 16), ("crab", None, 32), ("crab", None, 64), ("crab", None, 128),
-    ("crab", None, 252)])
+from state_inputs import SPEC_WORDS  # noqa: E402 — shared with the census (tests/state_census_worker.py)
+
+
+@pytest.mark.parametrize("name,planar,bits", SPEC_WORDS)
 def test_specification_switches_bitexact(gpu, orc, name, planar, bits):
     """Every specification switch (include/mbd_hip.h mbd_model_flags: contact_avg 4, contact6_gauss_seidel 8, friction_vel_bound
     16, restitution_min 32, euler_extrinsic 64, gyroscopic 128), alone and combined, on every inertia class of the 3-D SPEC
