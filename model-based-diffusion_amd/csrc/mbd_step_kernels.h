@@ -800,16 +800,23 @@ static __global__ __launch_bounds__(64) void cma_sigma_kernel(const float* __res
   float part = 0.0f;
   for (int i = threadIdx.x; i < HNu; i += 64) part = part + s[i];
   float sig = (wave_sum(part) / (float)HNu) * (*sigma);
-  if (threadIdx.x == 0) *sigma = sig > 1e-3f ? sig : 1e-3f;
+  if (threadIdx.x == 0) *sigma = sig < 1e-3f ? 1e-3f : sig;  // jnp.maximum (path_integral.py:44): a NaN sigma stays NaN
 }
-// cem: indices of the K (<= 10) largest weights, ties towards the higher index (argsort()[::-1][:10])
+// cem: indices of the K (<= 10, <= N) largest weights, ties towards the higher index: argsort(weights)[::-1][:10]
+// (path_integral.py:50) of a stable sort that places NaN last — the selection ranks by the key isnan(w) ? +inf : w, so NaN
+// weights (zero-spread rewards, a plan of one candidate: :123 has no guard) rank first, among themselves by descending index.
+// Keys are in [0, 1] or +inf: above the -1 start value and the -2 "taken" mark, so every pass takes one untaken candidate
+// and every index written to idx_out is in [0, N), for every input.
 static __global__ __launch_bounds__(64) void cem_select_kernel(const float* __restrict__ weights, int N, int K,
                                                         int* __restrict__ idx_out, float* __restrict__ wl_global, PiBatch pb) {
   weights += (long long)blockIdx.y * pb.weights; idx_out += (long long)blockIdx.y * pb.idx;
   extern __shared__ __attribute__((aligned(16))) float wl_lds[];
   float* __restrict__ wl = wl_global ? wl_global : wl_lds;  // (a lane only ever touches the indices = lane mod 64)
   const int lane = threadIdx.x;
-  for (int i = lane; i < N; i += 64) wl[i] = weights[i];
+  for (int i = lane; i < N; i += 64) {
+    const float w = weights[i];
+    wl[i] = w != w ? __builtin_inff() : w;
+  }
   for (int k = 0; k < K; ++k) {
     float bv = -1.0f;
     int bi = -1;

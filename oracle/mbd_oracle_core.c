@@ -585,14 +585,17 @@ ORC_API float orc_pi_update(int method, int N, int HNu, const float* rews, float
   for (int n = 0; n < N; ++n) weights[n] = sp_exp_f32(logp0[n] - mx);
   float den = sumB(weights, N);
   for (int n = 0; n < N; ++n) weights[n] = weights[n] / den;
-  if (method == 3) { /* argsort(weights)[::-1][:10]: ties resolved towards the HIGHER index */
+  if (method == 3) { /* argsort(weights)[::-1][:10] of a stable, NaN-last sort: the key is isnan(w) ? +inf : w, ties
+                        resolved towards the HIGHER index (NaN weights rank first, by descending index) */
     int K = N < 10 ? N : 10;
     char* used = (char*)calloc((size_t)N, 1);
+    float* key = (float*)malloc(sizeof(float) * (size_t)N);
+    for (int n = 0; n < N; ++n) key[n] = weights[n] != weights[n] ? __builtin_inff() : weights[n];
     int idx[10];
     for (int k = 0; k < K; ++k) {
       int best = -1;
       for (int n = 0; n < N; ++n)
-        if (!used[n] && (best < 0 || weights[n] >= weights[best])) best = n;
+        if (!used[n] && (best < 0 || key[n] >= key[best])) best = n;
       used[best] = 1;
       idx[k] = best;
     }
@@ -601,6 +604,7 @@ ORC_API float orc_pi_update(int method, int N, int HNu, const float* rews, float
       for (int k = 0; k < K; ++k) acc = acc + Y0s[(size_t)idx[k] * HNu + e];
       mu_tm1[e] = acc / (float)K;
     }
+    free(key);
     free(used);
   } else {
     for (int e = 0; e < HNu; ++e) mu_tm1[e] = wsum64(weights, Y0s + e, N, HNu);
@@ -615,7 +619,7 @@ ORC_API float orc_pi_update(int method, int N, int HNu, const float* rews, float
         s[e] = __builtin_sqrtf(acc);
       }
       float sig = (sum_f32(s, HNu) / (float)HNu) * (*sigma_inout);
-      *sigma_inout = sig > 1e-3f ? sig : 1e-3f;
+      *sigma_inout = sig < 1e-3f ? 1e-3f : sig; /* jnp.maximum (:44) propagates NaN */
       free(s);
     }
   }
