@@ -427,6 +427,21 @@ int mbd_sweep_set_state0(mbd_sweep* sweep, int k, const float* state0);
  * [n_plans][Ndiffuse-1], rew_final_out [n_plans]; loop_seconds_out: wall time of the lockstep loop.  Synchronous. */
 int mbd_sweep_run(mbd_sweep* sweep, const uint32_t* keys, float* mu_0ts_out, float* rew_means_out,
                   float* rew_final_out, double* loop_seconds_out);
+/* ---- batched receding horizon (no counterpart in the reference, which plans open loop; DESIGN.md section 1 "N5 batched") ---- */
+/* P closed-loop episodes in lockstep: episode k is EXACTLY mbd_plan_run_mpc's episode (above) on a plan of the sweep's config
+ * with state0 = the state mbd_sweep_set_state0(k) set, key = keys[k] and temp_sample = the sweep's temps[k] — bit for bit —
+ * and all episodes share mc (T, K, E).  Diffusion step i of tick t is ONE rollout launch over the P * Nsample candidates and
+ * ONE score + weighted-mean launch, as in mbd_sweep_run; a tick boundary is one small kernel (blockIdx.y = episode) and one
+ * rollout launch of the executed rows, one candidate per episode, which writes every episode's next state where the next
+ * tick's rollouts read it.  No host synchronisation between ticks; the host waits as mbd_sweep_run does (see above).
+ * keys: [n_plans][2].  HOST outputs, each may be NULL: actions_out [n_plans][T*E][Nu], rewards_out [n_plans][T*E], states_out
+ * [n_plans][T+1][state_size], means_out [n_plans][T][H][Nu]; loop_seconds_out: wall time of the tick loop.  Synchronous; one
+ * device->host copy per output at the end.  The sweep's start states are unchanged afterwards, whatever the outcome: a following
+ * mbd_sweep_run equals a fresh sweep's.
+ * MBD sweeps only (update_method 0, no demos): NULL sweep / config / keys and out-of-range fields -> MBD_ERR_INVALID (the NULL
+ * checks before any device access), enable_demo or a path-integral update -> MBD_ERR_UNSUPPORTED. */
+int mbd_sweep_run_mpc(mbd_sweep* sweep, const mbd_mpc_config* mc, const uint32_t* keys, float* actions_out,
+                      float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out);
 /* path-integral sweeps: the carried sampling sigma of every plan after the last run (path_integral.py:113,131); HOST [n_plans] */
 int mbd_sweep_get_sigmas(mbd_sweep* sweep, float* sigmas_out);
 /* average milliseconds of the sweep's rollout launches since the last reset (hipEvents on the launch stream) */

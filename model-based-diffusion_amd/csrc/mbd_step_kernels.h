@@ -164,6 +164,24 @@ static __global__ __launch_bounds__(256) void mpc_boundary_kernel(const float* _
   for (int e = threadIdx.x; e < S; e += blockDim.x) states_log[e] = s_next[e];
 }
 
+// The same boundary for the P lockstep episodes of a sweep (mbd_sweep_run_mpc), blockIdx.y = episode, one workgroup each, in
+// FRONT of the rollout that executes the tick's first E rows: episode k's M (M_stride floats apart: the last slot of its
+// means) goes into the tick's slice of the means log [P][HNu], its first `shift` = E * Nu floats into the compact rows
+// [P][shift] that rollout reads as one candidate per episode, and shift_E(M) into the next tick's first Ybar [P][HNu].  (The
+// states need no copy: that rollout writes s_next of every episode into the state log itself.)
+static __global__ __launch_bounds__(256) void mpc_boundary_batch_kernel(const float* __restrict__ M, long long M_stride, int HNu,
+                                                                  int shift, float* __restrict__ ybar_next,
+                                                                  float* __restrict__ means_log, float* __restrict__ rows) {
+  const long long k = blockIdx.y;
+  M += k * M_stride; ybar_next += k * HNu; means_log += k * HNu; rows += k * shift;
+  for (int e = threadIdx.x; e < HNu; e += blockDim.x) {
+    const float m = M[e];
+    means_log[e] = m;
+    if (e < shift) rows[e] = m;
+    ybar_next[e] = e < HNu - shift ? M[e + shift] : 0.0f;
+  }
+}
+
 // ---- A5: demo log-densities ------------------------------------------------------------------------------
 // HumanoidTrack.eval_xref_logpd (humanoidtrack.py:98-106): xpos [B][H][K][3], xref [K][H][3].  One workgroup per
 // candidate: its K*H terms ((clip(|x - xref|, 0, .5) / .5)^2, the candidate's 3 K H floats are contiguous) are formed in

@@ -45,6 +45,12 @@ struct mbd_sweep {
   // every plan, cma-es' spread, cem's selection
   float *d_Y0s = nullptr, *d_sigma = nullptr, *d_spread = nullptr;
   int* d_idx = nullptr;
+  // batched receding-horizon episodes (mbd_sweep_run_mpc): the episodes' logs, TICK-major — states [T+1][P][state_size],
+  // means [T][P][HNu], rewards [T][P][H-1] (E < H rows per tick) — for up to mpc_ticks ticks, grown on demand; the executed
+  // rows of a tick [P][(H-1) Nu] (compact: what the one-candidate-per-episode rollout reads) and the next tick's first
+  // Ybar [P][HNu].  Sweep-owned, like a plan's.
+  float *d_mpc_states = nullptr, *d_mpc_means = nullptr, *d_mpc_rewards = nullptr, *d_mpc_rows = nullptr, *d_mpc_ybar = nullptr;
+  size_t mpc_ticks = 0;
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
@@ -60,6 +66,8 @@ struct mbd_sweep {
     (void)hipFree(d_lp); (void)hipFree(d_xpos); (void)hipFree(d_weights); (void)hipFree(d_zero); (void)hipFree(d_mu);
     (void)hipFree(d_rewmeans); (void)hipFree(d_temps); (void)hipFree(d_final); (void)hipFree(d_final_rew);
     (void)hipFree(d_Y0s); (void)hipFree(d_sigma); (void)hipFree(d_spread); (void)hipFree(d_idx);
+    (void)hipFree(d_mpc_states); (void)hipFree(d_mpc_means); (void)hipFree(d_mpc_rewards); (void)hipFree(d_mpc_rows);
+    (void)hipFree(d_mpc_ybar);
     for (int b = 0; b < 3; ++b)
       if (ev_ready[b]) (void)hipEventDestroy(ev_ready[b]);
     if (ev_order) (void)hipEventDestroy(ev_order);
@@ -262,111 +270,140 @@ extern "C" int mbd_sweep_get_sigmas(mbd_sweep* w, float* sigmas_out) {
   return MBD_OK;
 }
 
+// ---- the lockstep diffusion step of MBD sweeps (update_method 0), shared by mbd_sweep_run and mbd_sweep_run_mpc ----------
+namespace {
+struct SweepStep {
+  int q;                       // position of the step in its loop: the ring buffer q % 3, the progress word q + 1
+  int i;                       // diffusion step Nd-1 .. 1
+  int slot;                    // slot of every plan's d_mu / d_rewmeans the step writes
+  const float* state0;         // [P][S] start states of the rollouts
+  const float* ybar_in;        // Ybar_i of plan 0; plan k's is ybar_in_stride floats further
+  long long ybar_in_stride;
+  const SweepKeys* next_keys;  // Y0s_rng of the loop's following step (its normals go beside this rollout), or nullptr: none follows
+};
+
+// the normals of a step depend on its keys only: they are generated on the second stream while the previous step's
+// rollout runs (a ring of three buffers, see mbd_sweep), like a single large plan's
+void sweep_noise(mbd_sweep* w, const SweepKeys& sk, int buf, hipStream_t st) {
+  const mbd_plan_config& c = w->cfg;
+  const uint64_t per_plan = (uint64_t)c.Nsample * w->HNu;
+  const uint64_t items = c.prng_impl == MBD_PRNG_PARTITIONABLE ? per_plan : (per_plan + 1) / 2;
+  uint64_t nblocks = (items + 255) / 256;
+  if (nblocks > 4096) nblocks = 4096;  // (grid-stride)
+  hipLaunchKernelGGL(noise_batch_kernel, dim3((unsigned)nblocks, (unsigned)w->P), dim3(256), 0, st, sk, c.prng_impl, c.Nsample, w->HNu,
+                     w->d_eps[buf]);
+}
+
+// rng, Y0s_rng = split(rng) of every plan (mbd_planner.py:103) — the whole key chain is host arithmetic
+void sweep_split_keys(const mbd_sweep* w, std::vector<uint32_t>& rng, SweepKeys& out) {
+  for (int k = 0; k < w->P; ++k) {
+    uint32_t ks[4];
+    host_split(&rng[2 * k], 2, w->cfg.prng_impl, ks);
+    rng[2 * k] = ks[0]; rng[2 * k + 1] = ks[1];
+    out.k[k][0] = ks[2]; out.k[k][1] = ks[3];
+  }
+}
+
+int sweep_step(mbd_sweep* w, const SweepStep& st) {
+  mbd_env* e = w->env;
+  const mbd_plan_config& c = w->cfg;
+  const int P = w->P, N = c.Nsample, H = c.Hsample, Nd = c.Ndiffuse, HNu = w->HNu, S = e->state_size();
+  const int step = st.q, i = st.i;
+  hipStream_t s = w->stream;
+  const int cur = step % 3, nxt = (step + 1) % 3;
+  if (step > 0 && hipEventQuery(w->ev_ready[cur]) != hipSuccess) {  // (generated a whole step ago: ready in practice)
+    (void)hipGetLastError();
+    HIP_TRY(hipStreamWaitEvent(s, w->ev_ready[cur], 0));
+  }
+  if (st.next_keys) {  // the next step's normals beside this rollout
+    // eps[nxt] was last read by the weighted mean of step - 2, finished once the rollout of step - 1 (which stores
+    // `step` into the progress word) has started: the loop waits for that — one step behind the device, whose queue
+    // still holds that rollout and its score — instead of ordering the two streams with events
+    if (step >= 2) {
+      const auto w0 = std::chrono::steady_clock::now();
+      while (progress_read(w->h_progress) < step) {
+        if (std::chrono::steady_clock::now() - w0 > std::chrono::milliseconds(kInStepWaitMs)) {
+          // a legitimately slow stream (shared / time-sliced GPU, profiler, system pause): order the streams with an
+          // event instead — everything enqueued on s so far, the reader of eps[nxt] included, precedes the generation
+          if (!w->ev_order) HIP_TRY(hipEventCreateWithFlags(&w->ev_order, hipEventDisableTiming));
+          HIP_TRY(hipEventRecord(w->ev_order, s));
+          HIP_TRY(hipStreamWaitEvent(w->aux, w->ev_order, 0));
+          w->event_fallbacks++;
+          break;
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+      }
+    }
+    sweep_noise(w, *st.next_keys, nxt, w->aux);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(w->ev_ready[nxt], w->aux));
+  }
+  LazyArgs lz;
+  lz.ybar = st.ybar_in;
+  lz.sigma = w->sigmas[i];
+  lz.progress = w->h_progress;
+  lz.progress_val = step + 1;
+  const int sw[3] = {N, S, (int)st.ybar_in_stride};
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (w->timing) {
+    if (w->events_used == w->events.size()) {
+      hipEvent_t a, b;
+      HIP_TRY(hipEventCreate(&a));
+      HIP_TRY(hipEventCreate(&b));
+      w->events.emplace_back(a, b);
+    }
+    ev0 = w->events[w->events_used].first; ev1 = w->events[w->events_used].second;
+    w->events_used++;
+    HIP_TRY(hipEventRecord(ev0, s));
+  }
+  const bool fused_lp = c.enable_demo && rollout_choice(e, P * N, H, sw).fuses_logpd;  // (mbd_plan.hip: the log-densities out of the rollout)
+  int rc = launch_rollout(e, st.state0, w->d_eps[cur], P * N, H, w->d_rewss, w->d_rews,
+                          (c.enable_demo && !fused_lp) ? w->d_xpos : nullptr, nullptr, s, &lz, sw, fused_lp ? w->d_lp : nullptr);
+  if (rc != MBD_OK) return rc;
+  if (w->timing) HIP_TRY(hipEventRecord(ev1, s));
+  if (c.enable_demo && !fused_lp) {
+    rc = launch_logpd(e, w->d_xpos, P * N, H, w->d_lp, s);
+    if (rc != MBD_OK) return rc;
+  }
+  ScoreBatch sb;
+  sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)N * HNu;
+  sb.ybar_in = st.ybar_in_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
+  launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews, c.enable_demo ? w->d_lp : nullptr, N,
+                           e->rew_xref, c.temp_sample, 1, w->d_weights, w->d_rewmeans + st.slot, w->d_eps[cur], HNu, st.ybar_in,
+                           w->alphas[i], w->alphas_bar[i], w->alphas_bar[i - 1], c.literal_score,
+                           w->d_mu + (size_t)st.slot * HNu, 1, w->sigmas[i], (float*)nullptr, sb);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+}  // namespace
+
 extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_out, float* rew_means_out,
                              float* rew_final_out, double* loop_seconds_out) {
   if (!w || !keys) return fail(MBD_ERR_INVALID, "NULL argument");
   mbd_env* e = w->env;
   HIP_TRY(hipSetDevice(e->device));
   const mbd_plan_config& c = w->cfg;
-  const int P = w->P, N = c.Nsample, H = c.Hsample, Nd = c.Ndiffuse, HNu = w->HNu, S = e->state_size();
+  const int P = w->P, H = c.Hsample, Nd = c.Ndiffuse, HNu = w->HNu, S = e->state_size();
   hipStream_t s = w->stream;
-  // per plan: rng, Y0s_rng = split(rng) per step (mbd_planner.py:103) — the whole key chain is host arithmetic
-  std::vector<uint32_t> rng(keys, keys + 2 * (size_t)P);
-  auto step_keys = [&](SweepKeys& out) {
-    for (int k = 0; k < P; ++k) {
-      uint32_t ks[4];
-      host_split(&rng[2 * k], 2, c.prng_impl, ks);
-      rng[2 * k] = ks[0]; rng[2 * k + 1] = ks[1];
-      out.k[k][0] = ks[2]; out.k[k][1] = ks[3];
-    }
-  };
-  // the normals of a step depend on its keys only: they are generated on the second stream while the previous step's
-  // rollout runs (a ring of three buffers, see mbd_sweep), like a single large plan's
-  const uint64_t per_plan = (uint64_t)N * HNu;
-  const uint64_t items = c.prng_impl == MBD_PRNG_PARTITIONABLE ? per_plan : (per_plan + 1) / 2;
-  uint64_t nblocks = (items + 255) / 256;
-  if (nblocks > 4096) nblocks = 4096;  // (grid-stride)
-  auto launch_noise_step = [&](int buf, hipStream_t st) {
-    SweepKeys sk;
-    step_keys(sk);
-    hipLaunchKernelGGL(noise_batch_kernel, dim3((unsigned)nblocks, (unsigned)P), dim3(256), 0, st, sk, c.prng_impl, N, HNu,
-                       w->d_eps[buf]);
-  };
   if (c.update_method != 0) return sweep_run_path_integral(w, keys, mu_0ts_out, rew_means_out, rew_final_out, loop_seconds_out);
-  const int sweep_args[3] = {N, S, HNu};
-  ScoreBatch sb;
-  sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)per_plan;
-  sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
+  std::vector<uint32_t> rng(keys, keys + 2 * (size_t)P);
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(w->aux));
   __atomic_store_n(w->h_progress, 0, __ATOMIC_RELEASE);
   auto t0 = std::chrono::steady_clock::now();
-  launch_noise_step(0, s);  // step Nd-1
+  SweepKeys sk;
+  sweep_split_keys(w, rng, sk);
+  sweep_noise(w, sk, 0, s);  // step Nd-1
   HIP_TRY(hipGetLastError());
   for (int i = Nd - 1, step = 0; i >= 1; --i, ++step) {
-    const int cur = step % 3, nxt = (step + 1) % 3;
-    if (step > 0 && hipEventQuery(w->ev_ready[cur]) != hipSuccess) {  // (generated a whole step ago: ready in practice)
-      (void)hipGetLastError();
-      HIP_TRY(hipStreamWaitEvent(s, w->ev_ready[cur], 0));
-    }
-    if (i > 1) {  // the next step's normals beside this rollout
-      // eps[nxt] was last read by the weighted mean of step - 2, finished once the rollout of step - 1 (which stores
-      // `step` into the progress word) has started: the loop waits for that — one step behind the device, whose queue
-      // still holds that rollout and its score — instead of ordering the two streams with events
-      if (step >= 2) {
-        const auto w0 = std::chrono::steady_clock::now();
-        while (progress_read(w->h_progress) < step) {
-          if (std::chrono::steady_clock::now() - w0 > std::chrono::milliseconds(kInStepWaitMs)) {
-            // a legitimately slow stream (shared / time-sliced GPU, profiler, system pause): order the streams with an
-            // event instead — everything enqueued on s so far, the reader of eps[nxt] included, precedes the generation
-            if (!w->ev_order) HIP_TRY(hipEventCreateWithFlags(&w->ev_order, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(w->ev_order, s));
-            HIP_TRY(hipStreamWaitEvent(w->aux, w->ev_order, 0));
-            w->event_fallbacks++;
-            break;
-          }
-          std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-      }
-      launch_noise_step(nxt, w->aux);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(w->ev_ready[nxt], w->aux));
-    }
-    const float* ybar_in = step == 0 ? w->d_zero : w->d_mu + (size_t)(step - 1) * HNu;
-    const long long ybar_in_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
-    LazyArgs lz;
-    lz.ybar = ybar_in;
-    lz.sigma = w->sigmas[i];
-    lz.progress = w->h_progress;
-    lz.progress_val = step + 1;
-    const int sw[3] = {sweep_args[0], sweep_args[1], (int)ybar_in_stride};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (w->timing) {
-      if (w->events_used == w->events.size()) {
-        hipEvent_t a, b;
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        w->events.emplace_back(a, b);
-      }
-      ev0 = w->events[w->events_used].first; ev1 = w->events[w->events_used].second;
-      w->events_used++;
-      HIP_TRY(hipEventRecord(ev0, s));
-    }
-    const bool fused_lp = c.enable_demo && rollout_choice(e, P * N, H, sw).fuses_logpd;  // (mbd_plan.hip: the log-densities out of the rollout)
-    int rc = launch_rollout(e, w->d_state0, w->d_eps[cur], P * N, H, w->d_rewss, w->d_rews,
-                            (c.enable_demo && !fused_lp) ? w->d_xpos : nullptr, nullptr, s, &lz, sw, fused_lp ? w->d_lp : nullptr);
+    if (i > 1) sweep_split_keys(w, rng, sk);
+    SweepStep st;
+    st.q = step; st.i = i; st.slot = step; st.state0 = w->d_state0;
+    st.ybar_in = step == 0 ? w->d_zero : w->d_mu + (size_t)(step - 1) * HNu;
+    st.ybar_in_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
+    st.next_keys = i > 1 ? &sk : nullptr;
+    int rc = sweep_step(w, st);
     if (rc != MBD_OK) return rc;
-    if (w->timing) HIP_TRY(hipEventRecord(ev1, s));
-    if (c.enable_demo && !fused_lp) {
-      rc = launch_logpd(e, w->d_xpos, P * N, H, w->d_lp, s);
-      if (rc != MBD_OK) return rc;
-    }
-    sb.ybar_in = ybar_in_stride;
-    launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews, c.enable_demo ? w->d_lp : nullptr, N,
-                             e->rew_xref, c.temp_sample, 1, w->d_weights, w->d_rewmeans + step, w->d_eps[cur], HNu, ybar_in,
-                             w->alphas[i], w->alphas_bar[i], w->alphas_bar[i - 1], c.literal_score,
-                             w->d_mu + (size_t)step * HNu, 1, w->sigmas[i], (float*)nullptr, sb);
-    HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipStreamSynchronize(s));
   auto t1 = std::chrono::steady_clock::now();
@@ -382,6 +419,120 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
     if (rc != MBD_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipMemcpy(rew_final_out, w->d_final_rew, sizeof(float) * P, hipMemcpyDeviceToHost));
+  }
+  return MBD_OK;
+}
+
+// Batched receding horizon (include/mbd_hip.h): P episodes in lockstep, the host only enqueues.  The episodes' logs are
+// tick-major on the device, so that the rollout of the executed rows writes s_{.,t+1} of all P episodes straight into slice
+// t+1 of the state log (state_final is [B][S]) and the next tick's rollouts read their start states from that same slice:
+// the sweep's own start states are never touched.  A tick boundary adds two launches on the sweep's stream —
+// mpc_boundary_batch_kernel and the rollout of the executed rows, one candidate per episode — stream-ordered between the
+// tick's last weighted mean and the next tick's first rollout, so the ring of noise buffers and the progress word carry
+// across ticks with their argument unchanged (mbd_sweep): the steps of all ticks count through as one loop.
+extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const uint32_t* keys, float* actions_out,
+                                 float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (!mc) return fail(MBD_ERR_INVALID, "mpc config is NULL");
+  if (!keys) return fail(MBD_ERR_INVALID, "keys is NULL");
+  const mbd_plan_config& c = w->cfg;
+  const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
+  if (T < 1) return fail(MBD_ERR_INVALID, "n_ticks=%d: must be >= 1", T);
+  if (K < 1 || K > Nd - 1) return fail(MBD_ERR_INVALID, "warm_steps=%d outside [1, Ndiffuse-1=%d]", K, Nd - 1);
+  if (E < 1 || E >= H) return fail(MBD_ERR_INVALID, "exec_steps=%d outside [1, Hsample=%d)", E, H);
+  for (int r = 0; r < 5; ++r)
+    if (mc->reserved[r] != 0) return fail(MBD_ERR_INVALID, "reserved[%d]=%d: must be 0", r, mc->reserved[r]);
+  if (c.enable_demo) return fail(MBD_ERR_UNSUPPORTED, "enable_demo: demos are time-indexed, an episode has no clock for them");
+  if (c.update_method != 0) return fail(MBD_ERR_UNSUPPORTED, "update_method=%d: receding horizon runs MBD plans only", c.update_method);
+  mbd_env* e = w->env;
+  HIP_TRY(hipSetDevice(e->device));
+  const int P = w->P, HNu = w->HNu, Nu = e->action_size(), S = e->state_size();
+  if ((size_t)T > w->mpc_ticks) {
+    HIP_TRY(hipFree(w->d_mpc_states)); HIP_TRY(hipFree(w->d_mpc_means)); HIP_TRY(hipFree(w->d_mpc_rewards));
+    w->d_mpc_states = w->d_mpc_means = w->d_mpc_rewards = nullptr;
+    w->mpc_ticks = 0;
+    if (!w->d_mpc_rows) HIP_TRY(hipMalloc(&w->d_mpc_rows, sizeof(float) * (size_t)P * (H - 1) * Nu));
+    if (!w->d_mpc_ybar) HIP_TRY(hipMalloc(&w->d_mpc_ybar, sizeof(float) * (size_t)P * HNu));
+    HIP_TRY(hipMalloc(&w->d_mpc_states, sizeof(float) * ((size_t)T + 1) * P * S));
+    HIP_TRY(hipMalloc(&w->d_mpc_means, sizeof(float) * (size_t)T * P * HNu));
+    HIP_TRY(hipMalloc(&w->d_mpc_rewards, sizeof(float) * (size_t)T * P * (H - 1)));
+    w->mpc_ticks = (size_t)T;
+  }
+  hipStream_t s = w->stream;
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipStreamSynchronize(w->aux));
+  HIP_TRY(hipMemcpyAsync(w->d_mpc_states, w->d_state0, sizeof(float) * (size_t)P * S, hipMemcpyDeviceToDevice, s));  // s_{.,0}
+  HIP_TRY(hipStreamSynchronize(s));
+  __atomic_store_n(w->h_progress, 0, __ATOMIC_RELEASE);
+  const auto t0 = std::chrono::steady_clock::now();
+  // per episode: rng, k_t = split(rng) per tick, the tick's chain r, Y0s_rng = split(r) per step from r = k_t.  The keys
+  // are drawn in the order the steps run, one step ahead of the rollouts (the normals of a tick's first step are prepared
+  // beside the previous tick's last rollout, like any other step's)
+  std::vector<uint32_t> rng(keys, keys + 2 * (size_t)P), r(2 * (size_t)P);
+  SweepKeys tick, sk;
+  auto first_keys_of_tick = [&]() {
+    sweep_split_keys(w, rng, tick);
+    for (int k = 0; k < P; ++k) { r[2 * k] = tick.k[k][0]; r[2 * k + 1] = tick.k[k][1]; }
+    sweep_split_keys(w, r, sk);
+  };
+  first_keys_of_tick();
+  sweep_noise(w, sk, 0, s);  // tick 0, step Nd-1
+  HIP_TRY(hipGetLastError());
+  const long long mu_stride = (long long)(Nd - 1) * HNu;
+  const int exec_sw[3] = {1, S, 0};
+  for (int t = 0, q = 0; t < T; ++t) {
+    const float* states_t = w->d_mpc_states + (size_t)t * P * S;
+    const int i_start = t == 0 ? Nd - 1 : K;
+    for (int i = i_start; i >= 1; --i, ++q) {
+      const bool follows = i > 1 || t + 1 < T;
+      if (i > 1) sweep_split_keys(w, r, sk);
+      else if (follows) first_keys_of_tick();
+      SweepStep st;
+      st.q = q; st.i = i; st.slot = Nd - 1 - i;  // (K <= Nd-1: a warm tick's steps use the last K slots)
+      st.state0 = states_t;
+      st.ybar_in = i == i_start ? (t == 0 ? w->d_zero : w->d_mpc_ybar) : w->d_mu + (size_t)(st.slot - 1) * HNu;
+      st.ybar_in_stride = i == i_start ? HNu : mu_stride;
+      st.next_keys = follows ? &sk : nullptr;
+      int rc = sweep_step(w, st);
+      if (rc != MBD_OK) return rc;
+    }
+    // the boundary: the logs of M_{.,t}, its first E rows and Ybar of tick t+1; then the rows executed from s_{.,t}
+    hipLaunchKernelGGL(mpc_boundary_batch_kernel, dim3(1, (unsigned)P), dim3(256), 0, s,
+                       (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, HNu, E * Nu, w->d_mpc_ybar,
+                       w->d_mpc_means + (size_t)t * P * HNu, w->d_mpc_rows);
+    HIP_TRY(hipGetLastError());
+    int rc = launch_rollout(e, states_t, w->d_mpc_rows, P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr, nullptr,
+                            w->d_mpc_states + (size_t)(t + 1) * P * S, s, nullptr, exec_sw);
+    if (rc != MBD_OK) return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  const auto t1 = std::chrono::steady_clock::now();
+  if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
+  // the logs are tick-major, the outputs episode-major: ONE device->host copy per log, transposed on the host
+  std::vector<float> tmp;
+  if (rewards_out) {
+    tmp.resize((size_t)T * P * E);
+    HIP_TRY(hipMemcpy(tmp.data(), w->d_mpc_rewards, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
+    for (int t = 0; t < T; ++t)
+      for (int k = 0; k < P; ++k)
+        memcpy(rewards_out + ((size_t)k * T + t) * E, tmp.data() + ((size_t)t * P + k) * E, sizeof(float) * (size_t)E);
+  }
+  if (states_out) {
+    tmp.resize(((size_t)T + 1) * P * S);
+    HIP_TRY(hipMemcpy(tmp.data(), w->d_mpc_states, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
+    for (int t = 0; t <= T; ++t)
+      for (int k = 0; k < P; ++k)
+        memcpy(states_out + ((size_t)k * (T + 1) + t) * S, tmp.data() + ((size_t)t * P + k) * S, sizeof(float) * (size_t)S);
+  }
+  if (means_out || actions_out) {  // (the executed rows are M_t[0:E]: taken from the one copy of the means)
+    tmp.resize((size_t)T * P * HNu);
+    HIP_TRY(hipMemcpy(tmp.data(), w->d_mpc_means, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
+    for (int t = 0; t < T; ++t)
+      for (int k = 0; k < P; ++k) {
+        const float* m = tmp.data() + ((size_t)t * P + k) * HNu;
+        if (means_out) memcpy(means_out + ((size_t)k * T + t) * HNu, m, sizeof(float) * (size_t)HNu);
+        if (actions_out) memcpy(actions_out + ((size_t)k * T + t) * E * Nu, m, sizeof(float) * (size_t)E * Nu);
+      }
   }
   return MBD_OK;
 }

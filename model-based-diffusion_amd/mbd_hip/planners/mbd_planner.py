@@ -103,6 +103,25 @@ class Sweep:
                                            C.byref(secs)))
         return mu, rm, rf, secs.value
 
+    def run_mpc(self, keys, n_ticks: int, warm_steps: int, exec_steps: int = 1) -> dict:
+        """P closed-loop episodes in lockstep (include/mbd_hip.h mbd_sweep_run_mpc): episode k is ``Plan.run_mpc`` from plan
+        k's state0 with ``keys[k]`` and plan k's temperature, bit for bit; a diffusion step of a tick is one rollout launch
+        over all the episodes' candidates.  Returns dict(actions [P, T*E, Nu], rewards [P, T*E], states [P, T+1, state_size],
+        means [P, T, H, Nu], seconds)."""
+        mc = _capi.MpcConfig()
+        mc.n_ticks, mc.warm_steps, mc.exec_steps = int(n_ticks), int(warm_steps), int(exec_steps)
+        T, E, P = max(mc.n_ticks, 0), max(mc.exec_steps, 0), self.P
+        S = self.env._state_size
+        k = np.ascontiguousarray(keys, np.uint32).reshape(P, 2)
+        out = dict(actions=np.zeros((P, T * E, self.Nu), np.float32), rewards=np.zeros((P, T * E), np.float32),
+                   states=np.zeros((P, T + 1, S), np.float32), means=np.zeros((P, T, self.H, self.Nu), np.float32))
+        secs = C.c_double()
+        _capi.check(self.lib.mbd_sweep_run_mpc(self.h, C.byref(mc), _capi.np_ptr(k), _capi.np_ptr(out["actions"]),
+                                               _capi.np_ptr(out["rewards"]), _capi.np_ptr(out["states"]),
+                                               _capi.np_ptr(out["means"]), C.byref(secs)))
+        out["seconds"] = secs.value
+        return out
+
     def get_sigmas(self):
         """path-integral sweeps: every plan's carried sigma after the last run (path_integral.py:113,131)."""
         out = np.zeros(self.P, np.float32)
