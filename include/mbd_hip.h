@@ -173,6 +173,7 @@ typedef struct mbd_model {
  * positional State.x_i / State.xd_i — the only quantities integrated from step to step. Layout of a
  * state buffer: float[n_links][13].  car2d's state is float[3] = (x, y, theta) (car2d.py:35-40). */
 #define MBD_LINK_STATE 13
+#define MBD_LINK_VEL 7 /* offset of a link's linear velocity v[3] inside its 13 floats (what a plant record's kick moves) */
 
 /* ------------------------------------------------------------------------------------------------ */
 /* library                                                                                           */
@@ -393,6 +394,43 @@ typedef struct mbd_mpc_config {
 int mbd_plan_run_mpc(mbd_plan* plan, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
                      float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out);
 
+/* ---- the plant of an episode: a system that is NOT the planner's model (DESIGN.md section 1 "N5 plant") ---- */
+/* A plant record names the env that executes a closed-loop episode's rows, and the episode's disturbances.  It is a setting
+ * of the plan (of an episode of a sweep) that mbd_plan_run_mpc (mbd_sweep_run_mpc) reads; mbd_plan_run / mbd_sweep_run ignore
+ * it.  Without a record the two run calls are unchanged: same launches, same bits. */
+typedef struct mbd_mpc_plant {
+  mbd_env* plant;      /* the env that executes the rows; NULL = the plan's own env.  Not owned: the caller keeps it alive */
+  uint32_t key[2];     /* the disturbance key; its chain is separate from the episode's key chain */
+  float act_std;       /* >= 0: std of the normal noise added to every executed action (before the env's clip) */
+  float kick_std;      /* >= 0: std per component (m/s) of the velocity kick on link 0 */
+  int32_t kick_every;  /* >= 1: a kick at the end of every tick t with (t+1) % kick_every == 0 */
+  int32_t reserved[3]; /* must be 0 */
+} mbd_mpc_plant;
+/* With a plant record, the episode of mbd_plan_run_mpc (above) becomes — everything not shown is unchanged; the planner
+ * always plans with the PLAN's env, from the state the PLANT reached:
+ *   dk = rec.key
+ *   per tick t:  M_t as above (from s_t, the plan's env, the episode's key chain)
+ *                dk, d_t = split(dk)                                  (the plan's prng_impl)
+ *                eps = normal(d_t, (E*Nu + 3,))                       (always this many, whatever is switched on)
+ *                rows = M_t[0:E]                         if act_std == 0  (copied, not computed: -0.0 stays -0.0)
+ *                     = M_t[0:E] + act_std * eps[0:E*Nu]  otherwise       (f32 product, then f32 sum: two roundings, no fma)
+ *                rewards[tE .. tE+E), s' = rollout_PLANT(s_t, rows)   (the plant env's rollout path and its reward)
+ *                if kick_std > 0 and (t+1) % kick_every == 0:
+ *                  s'.v[link 0] += kick_std * eps[E*Nu .. E*Nu+3)     (f32 product then sum; planar models,
+ *                                                                      MBD_FLAG_PLANAR: the y component is not applied)
+ *                s_{t+1} = s';  Ybar = shift_E(M_t)                   (the shift takes the UNDISTURBED mean)
+ * actions_out then holds `rows` (what the plant was fed), means_out the undisturbed M_t, rewards_out the plant's rewards,
+ * states_out the states after the kick.  A record with plant NULL (or a second env of the same model) and both stds 0 gives
+ * the episode without a record bit for bit; the prefix property and "tick 0's mean is mbd_plan_run(k_0)'s" hold with any
+ * record.  Still no host synchronisation between ticks: the disturbances are drawn and applied on the device.
+ * The record is copied and stays until cleared (rec == NULL) or the handle is destroyed.  Refused at the set call, before
+ * any launch: NULL plan -> MBD_ERR_INVALID; a plant on another device, or whose n_links (hence state_size) / action_size / planar
+ * flag differ from the plan's env -> MBD_ERR_INVALID naming the field; a negative or non-finite std, kick_every < 1, non-zero
+ * reserved -> MBD_ERR_INVALID; kick_std > 0 on an env whose link 0 cannot translate freely in its plane ->
+ * MBD_ERR_UNSUPPORTED (allowed iff the model's n_rot[0] == -1, a free joint, or it is planar with n_slide[0] >= 2; refused for
+ * cartpole's cart on a rail and for car2d, which has no links).  act_std works for every env. */
+int mbd_plan_set_mpc_plant(mbd_plan* plan, const mbd_mpc_plant* rec);
+
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
  * candidates Y0s [Nsample][H][Nu] (plans that keep normals instead form them here, from the normals, sigma_i and the
  * Ybar_i of the last step — between phase 1 and phase 2 the caller's d_Ybar_i must still be unchanged), the shard's
@@ -442,6 +480,14 @@ int mbd_sweep_run(mbd_sweep* sweep, const uint32_t* keys, float* mu_0ts_out, flo
  * checks before any device access), enable_demo or a path-integral update -> MBD_ERR_UNSUPPORTED. */
 int mbd_sweep_run_mpc(mbd_sweep* sweep, const mbd_mpc_config* mc, const uint32_t* keys, float* actions_out,
                       float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out);
+/* The plant record of episode k (mbd_mpc_plant, above; rec == NULL clears).  With records: episode k of mbd_sweep_run_mpc is
+ * EXACTLY mbd_plan_run_mpc on a plan of its own carrying record k, bit for bit; the episodes may carry different plants, keys
+ * and stds, or none.  The diffusion steps are unchanged; a tick boundary draws every episode's disturbances in one small
+ * launch (blockIdx.y = episode), executes the rows in one rollout launch per maximal run of consecutive episodes that share
+ * a plant handle (one shared plant: ONE launch), and applies the kicks in one launch, in the ticks that have any.  A sweep
+ * without records runs exactly the launches described above.  Refusals as mbd_plan_set_mpc_plant's, against the sweep's env;
+ * NULL sweep or k outside [0, n_plans) -> MBD_ERR_INVALID before any device access. */
+int mbd_sweep_set_mpc_plant(mbd_sweep* sweep, int k, const mbd_mpc_plant* rec);
 /* path-integral sweeps: the carried sampling sigma of every plan after the last run (path_integral.py:113,131); HOST [n_plans] */
 int mbd_sweep_get_sigmas(mbd_sweep* sweep, float* sigmas_out);
 /* average milliseconds of the sweep's rollout launches since the last reset (hipEvents on the launch stream) */

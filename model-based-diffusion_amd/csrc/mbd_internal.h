@@ -146,6 +146,13 @@ struct mbd_plan {
   // mpc_ticks ticks, grown on demand.  Plan-owned, so that nothing an episode leaves behind points at freed memory.
   float *d_mpc_state = nullptr, *d_mpc_states = nullptr, *d_mpc_means = nullptr, *d_mpc_rewards = nullptr;
   size_t mpc_ticks = 0;
+  // the plant record of the plan's episodes (mbd_plan_set_mpc_plant; a copy, the plant env is the caller's), and what an
+  // episode with a record needs beyond the above: the log of the executed rows [T][E Nu] — the tick's rollout reads its
+  // slice, so the rows exist once —, the tick's normals [E Nu + 3] and its three kick values
+  mbd_mpc_plant plant_rec{};
+  bool has_plant = false;
+  float *d_mpc_actions = nullptr, *d_plant_eps = nullptr, *d_plant_kick = nullptr;
+  size_t mpc_actions_cap = 0, plant_eps_cap = 0;
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
@@ -162,6 +169,7 @@ struct mbd_plan {
     (void)hipFree(d_sigma); (void)hipFree(d_spread); (void)hipFree(d_idx); (void)hipFree(d_wm_partial); (void)hipFree(d_lg);
     (void)hipFree(d_eps[0]); (void)hipFree(d_eps[1]); (void)hipFree(d_eps[2]); (void)hipFree(d_ybar_keep);
     (void)hipFree(d_mpc_state); (void)hipFree(d_mpc_states); (void)hipFree(d_mpc_means); (void)hipFree(d_mpc_rewards);
+    (void)hipFree(d_mpc_actions); (void)hipFree(d_plant_eps); (void)hipFree(d_plant_kick);
     if (h_progress) (void)hipHostFree(h_progress);
     for (int b = 0; b < 3; ++b)
       if (ev_noise[b]) (void)hipEventDestroy(ev_noise[b]);
@@ -226,3 +234,5 @@ int launch_logpd(const mbd_env* e, const float* d_xpos, int B, int H, float* d_o
 // noise schedule (mbd_planner.py:84-87)
 void host_schedule(float beta0, float betaT, int Nd, std::vector<float>& alphas, std::vector<float>& alphas_bar,
                    std::vector<float>& sigmas);
+// the refusals of a plant record (include/mbd_hip.h mbd_mpc_plant) against the env that plans — host arithmetic, no launch
+int check_mpc_plant(const mbd_env* env, const mbd_mpc_plant* rec);

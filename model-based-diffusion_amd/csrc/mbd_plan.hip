@@ -549,11 +549,63 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
   return MBD_OK;
 }
 
+// ---- the plant record (include/mbd_hip.h mbd_mpc_plant) ----------------------------------------------------------------
+int check_mpc_plant(const mbd_env* env, const mbd_mpc_plant* rec) {
+  for (int r = 0; r < 3; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "plant record: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (!std::isfinite(rec->act_std) || rec->act_std < 0.0f)
+    return fail(MBD_ERR_INVALID, "plant record: act_std=%g: must be finite and >= 0", (double)rec->act_std);
+  if (!std::isfinite(rec->kick_std) || rec->kick_std < 0.0f)
+    return fail(MBD_ERR_INVALID, "plant record: kick_std=%g: must be finite and >= 0", (double)rec->kick_std);
+  if (rec->kick_every < 1) return fail(MBD_ERR_INVALID, "plant record: kick_every=%d: must be >= 1", rec->kick_every);
+  auto links = [](const mbd_env* e) { return e->kind == ENV_MODEL ? e->model.n_links : 0; };
+  auto planar = [](const mbd_env* e) { return e->kind == ENV_MODEL && (e->model.flags & MBD_FLAG_PLANAR) ? 1 : 0; };
+  const mbd_env* pe = rec->plant ? rec->plant : env;
+  if (pe != env) {  // the plant executes rows planned for env and hands its states back: one topology, one device
+    if (pe->device != env->device)
+      return fail(MBD_ERR_INVALID, "plant record: the plant's device=%d, the planning env's is %d", pe->device, env->device);
+    // (state_size is 13 n_links for a rigid-body env and 3 for car2d, which has no links: n_links covers it)
+    if (links(pe) != links(env))
+      return fail(MBD_ERR_INVALID, "plant record: the plant's n_links=%d (state_size=%d), the planning env's is %d (state_size=%d)",
+                  links(pe), pe->state_size(), links(env), env->state_size());
+    if (pe->action_size() != env->action_size())
+      return fail(MBD_ERR_INVALID, "plant record: the plant's action_size=%d, the planning env's is %d", pe->action_size(),
+                  env->action_size());
+    if (planar(pe) != planar(env))
+      return fail(MBD_ERR_INVALID, "plant record: the plant's planar flag=%d, the planning env's is %d", planar(pe), planar(env));
+  }
+  if (rec->kick_std > 0.0f) {  // a kick moves link 0's linear velocity: the link has to be free to translate in the model's plane
+    const bool free_root = links(pe) > 0 && (pe->model.n_rot[0] == -1 || (planar(pe) && pe->model.n_slide[0] >= 2));
+    if (!free_root)
+      return fail(MBD_ERR_UNSUPPORTED, "plant record: kick_std=%g on env '%s', whose link 0 cannot translate freely in its plane",
+                  (double)rec->kick_std, pe->name.c_str());
+  }
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_mpc_plant(mbd_plan* p, const mbd_mpc_plant* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (!rec) {
+    p->has_plant = false;
+    p->plant_rec = mbd_mpc_plant{};
+    return MBD_OK;
+  }
+  int rc = check_mpc_plant(p->env, rec);
+  if (rc != MBD_OK) return rc;
+  p->plant_rec = *rec;
+  p->has_plant = true;
+  return MBD_OK;
+}
+
 // Receding horizon (include/mbd_hip.h): the host only enqueues — the key chain is host arithmetic, the executed state never
 // comes back — and keeps at most one step ahead of the device through plan_keep_in_step, as mbd_plan_run does.  A tick
 // boundary adds two launches on the plan's stream: the rollout of M_t's first E rows (the env's rollout path, one candidate:
 // what mbd_env_step runs) and mpc_boundary_kernel.  Both are stream-ordered between the tick's last weighted mean and the
 // next tick's first rollout, so the ring of noise buffers keeps its argument (mbd_plan), aux-stream form included.
+// With a plant record (mbd_plan_set_mpc_plant) the boundary is three launches in the same place on the same stream —
+// mpc_plant_rows_kernel (the tick's normals, the executed rows, the kick values), the PLANT env's rollout of those rows, and
+// the boundary kernel, in the ticks that end with a kick its kick variant — so that argument is unchanged again; the
+// disturbance key chain is host arithmetic like the episode's.  Without a record: the two launches above, nothing else.
 extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
                                 float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
@@ -583,6 +635,27 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     HIP_TRY(hipMalloc(&p->d_mpc_rewards, sizeof(float) * (size_t)T * (H - 1)));
     p->mpc_ticks = (size_t)T;
   }
+  const bool has_plant = p->has_plant;
+  const mbd_mpc_plant& pr = p->plant_rec;
+  mbd_env* const pe = has_plant && pr.plant ? pr.plant : e;  // the env that executes the rows
+  const int EN = E * Nu;
+  if (has_plant) {
+    if ((size_t)T * EN > p->mpc_actions_cap) {
+      HIP_TRY(hipFree(p->d_mpc_actions));
+      p->d_mpc_actions = nullptr; p->mpc_actions_cap = 0;
+      HIP_TRY(hipMalloc(&p->d_mpc_actions, sizeof(float) * (size_t)T * EN));
+      p->mpc_actions_cap = (size_t)T * EN;
+    }
+    if ((size_t)EN + 3 > p->plant_eps_cap) {
+      HIP_TRY(hipFree(p->d_plant_eps));
+      p->d_plant_eps = nullptr; p->plant_eps_cap = 0;
+      HIP_TRY(hipMalloc(&p->d_plant_eps, sizeof(float) * ((size_t)EN + 3)));
+      p->plant_eps_cap = (size_t)EN + 3;
+    }
+    if (!p->d_plant_kick) HIP_TRY(hipMalloc(&p->d_plant_kick, sizeof(float) * 3));
+  }
+  const int planar = e->kind == ENV_MODEL && (e->model.flags & MBD_FLAG_PLANAR) ? 1 : 0;
+  uint32_t dk[2] = {pr.key[0], pr.key[1]};  // the disturbance key chain: dk, d_t = split(dk) per tick
   // the ticks' rollouts read p->d_state0: s_0 there, then the ping-pong buffers; the plan's own buffer comes back on every exit
   struct RestoreState0 {
     mbd_plan* p;
@@ -618,10 +691,31 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     }
     // execute M_t's first E rows from s_t, then the boundary: Ybar of tick t+1, the logs of M_t and s_{t+1}
     float* s_next = p->d_mpc_state + (size_t)(t & 1) * S;
-    int rc = launch_rollout(e, p->d_state0, cur, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr, nullptr, s_next, s);
+    const float* rows = cur;
+    bool kick_now = false;
+    if (has_plant) {  // the rows the plant is fed: M_t[0:E] plus the tick's action noise, into the tick's slice of their log
+      uint32_t dkk[4];
+      host_split(dk, 2, c.prng_impl, dkk);
+      dk[0] = dkk[0]; dk[1] = dkk[1];
+      kick_now = pr.kick_std > 0.0f && (t + 1) % pr.kick_every == 0;
+      SweepPlant sp{};
+      sp.k[0][0] = dkk[2]; sp.k[0][1] = dkk[3];
+      sp.act_std[0] = pr.act_std; sp.kick_std[0] = kick_now ? pr.kick_std : 0.0f; sp.has[0] = 1;
+      float* exec_rows = p->d_mpc_actions + (size_t)t * EN;
+      hipLaunchKernelGGL(mpc_plant_rows_kernel, dim3(1, 1), dim3(256), 0, s, sp, c.prng_impl, cur, 0ll, EN, p->d_plant_eps,
+                         exec_rows, p->d_plant_kick);
+      HIP_TRY(hipGetLastError());
+      rows = exec_rows;
+    }
+    int rc = launch_rollout(pe, p->d_state0, rows, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr, nullptr, s_next, s);
     if (rc != MBD_OK) return rc;
-    hipLaunchKernelGGL(mpc_boundary_kernel, dim3(1), dim3(256), 0, s, cur, HNu, E * Nu, (const float*)s_next, S, ybar0,
-                       p->d_mpc_means + (size_t)t * HNu, p->d_mpc_states + (size_t)(t + 1) * S);
+    if (kick_now)
+      hipLaunchKernelGGL(mpc_boundary_kick_kernel, dim3(1), dim3(256), 0, s, cur, HNu, EN, s_next, S,
+                         (const float*)p->d_plant_kick, planar, ybar0, p->d_mpc_means + (size_t)t * HNu,
+                         p->d_mpc_states + (size_t)(t + 1) * S);
+    else
+      hipLaunchKernelGGL(mpc_boundary_kernel, dim3(1), dim3(256), 0, s, cur, HNu, E * Nu, (const float*)s_next, S, ybar0,
+                         p->d_mpc_means + (size_t)t * HNu, p->d_mpc_states + (size_t)(t + 1) * S);
     HIP_TRY(hipGetLastError());
     p->d_state0 = s_next;
   }
@@ -630,7 +724,10 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
   if (rewards_out) HIP_TRY(hipMemcpy(rewards_out, p->d_mpc_rewards, sizeof(float) * (size_t)T * E, hipMemcpyDeviceToHost));
   if (states_out) HIP_TRY(hipMemcpy(states_out, p->d_mpc_states, sizeof(float) * ((size_t)T + 1) * S, hipMemcpyDeviceToHost));
-  if (means_out || actions_out) {  // (the executed rows are M_t[0:E]: taken from the one copy of the means)
+  if (has_plant) {  // (the executed rows carry the action noise: their own log)
+    if (actions_out) HIP_TRY(hipMemcpy(actions_out, p->d_mpc_actions, sizeof(float) * (size_t)T * EN, hipMemcpyDeviceToHost));
+    if (means_out) HIP_TRY(hipMemcpy(means_out, p->d_mpc_means, sizeof(float) * (size_t)T * HNu, hipMemcpyDeviceToHost));
+  } else if (means_out || actions_out) {  // (the executed rows are M_t[0:E]: taken from the one copy of the means)
     std::vector<float> tmp(means_out ? 0 : (size_t)T * HNu);
     float* m = means_out ? means_out : tmp.data();
     HIP_TRY(hipMemcpy(m, p->d_mpc_means, sizeof(float) * (size_t)T * HNu, hipMemcpyDeviceToHost));

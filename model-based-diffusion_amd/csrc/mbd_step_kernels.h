@@ -153,15 +153,38 @@ static __global__ __launch_bounds__(256) void shift_kernel(const float* __restri
 // executed the tick's first E rows: the next tick's starting mean Ybar_K = shift_E(M) — M [H][Nu] moved E rows forward,
 // the vacated last E rows zero (the cold plan's prior) — and the episode's logs of M and of s_next, the state the executed
 // rows reached (it stays where it is: the host hands that buffer to the next tick's rollouts).  shift = E * Nu floats.
-static __global__ __launch_bounds__(256) void mpc_boundary_kernel(const float* __restrict__ M, int HNu, int shift,
-                                                            const float* __restrict__ s_next, int S,
-                                                            float* __restrict__ ybar_next, float* __restrict__ means_log,
-                                                            float* __restrict__ states_log) {
+constexpr int kLinkVel = MBD_LINK_VEL;  // link 0's linear velocity inside a state (include/mbd_hip.h)
+// (kick: the three values a tick's kick adds to link 0's linear velocity — floats kLinkVel .. kLinkVel + 2 of the state —
+// before s_next is logged and before the next tick reads it, planar models leaving the y component alone; nullptr: no kick.)
+__device__ __forceinline__ void mpc_boundary_body(const float* __restrict__ M, int HNu, int shift, float* s_next, int S,
+                                                  const float* __restrict__ kick, int planar, float* __restrict__ ybar_next,
+                                                  float* __restrict__ means_log, float* __restrict__ states_log) {
   for (int e = threadIdx.x; e < HNu; e += blockDim.x) {
     means_log[e] = M[e];
     ybar_next[e] = e < HNu - shift ? M[e + shift] : 0.0f;
   }
-  for (int e = threadIdx.x; e < S; e += blockDim.x) states_log[e] = s_next[e];
+  for (int e = threadIdx.x; e < S; e += blockDim.x) {
+    float v = s_next[e];
+    const int j = e - kLinkVel;
+    if (kick && j >= 0 && j < 3 && !(planar && j == 1)) {
+      v = v + kick[j];
+      s_next[e] = v;
+    }
+    states_log[e] = v;
+  }
+}
+static __global__ __launch_bounds__(256) void mpc_boundary_kernel(const float* __restrict__ M, int HNu, int shift,
+                                                            const float* __restrict__ s_next, int S,
+                                                            float* __restrict__ ybar_next, float* __restrict__ means_log,
+                                                            float* __restrict__ states_log) {
+  mpc_boundary_body(M, HNu, shift, const_cast<float*>(s_next), S, nullptr, 0, ybar_next, means_log, states_log);
+}
+// mpc_boundary_kernel of a tick that ends with a kick (mbd_mpc_plant; single plan)
+static __global__ __launch_bounds__(256) void mpc_boundary_kick_kernel(const float* __restrict__ M, int HNu, int shift, float* s_next,
+                                                                 int S, const float* __restrict__ kick, int planar,
+                                                                 float* __restrict__ ybar_next, float* __restrict__ means_log,
+                                                                 float* __restrict__ states_log) {
+  mpc_boundary_body(M, HNu, shift, s_next, S, kick, planar, ybar_next, means_log, states_log);
 }
 
 // The same boundary for the P lockstep episodes of a sweep (mbd_sweep_run_mpc), blockIdx.y = episode, one workgroup each, in
@@ -705,6 +728,45 @@ static __global__ __launch_bounds__(256) void noise_batch_kernel(SweepKeys keys,
   const uint64_t size = (uint64_t)N * (uint64_t)HNu;
   noise_fill(keys.k[blockIdx.y][0], keys.k[blockIdx.y][1], impl, size, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x,
              (uint64_t)gridDim.x * blockDim.x, eps + (uint64_t)blockIdx.y * size);
+}
+
+// ---- the plant of a receding-horizon episode (include/mbd_hip.h mbd_mpc_plant): disturbances drawn and applied on the device ----
+// What a tick's disturbance launches need of every episode (blockIdx.y = episode; a single plan is episode 0), passed like
+// SweepKeys: d_t of the disturbance key chain, the action-noise std, and the kick std — which the host sets to 0 in the
+// ticks that carry no kick, so that it doubles as the kick kernels' mask.  has[k] == 0: the episode has no record.
+struct SweepPlant {
+  uint32_t k[32][2];
+  float act_std[32], kick_std[32];
+  unsigned char has[32];
+};
+// One workgroup per episode, behind the tick's last weighted mean: eps = normal(d_t, (EN + 3,)) by noise_fill (the counters
+// and layouts of every other normal of the library: bit-exact to the checker's), then the executed rows
+// rows[e] = M[e] + act_std * eps[e] — product and sum rounded separately, like every float32 expression of the library: the build
+// compiles with -ffp-contract=off (the checker is numpy float32; the ISA shows v_mul_f32, then v_add_f32) — or M[e] itself where
+// act_std == 0 (a copy: -0.0 stays -0.0), and the three kick values kick_std * eps[EN ..].  EN = E * Nu; M of episode k is M_stride floats further; eps [P][EN + 3] is scratch.
+static __global__ __launch_bounds__(256) void mpc_plant_rows_kernel(SweepPlant pl, int impl, const float* __restrict__ M,
+                                                              long long M_stride, int EN, float* eps, float* __restrict__ rows,
+                                                              float* __restrict__ kick) {
+  const long long k = blockIdx.y;
+  M += k * M_stride; eps += k * (EN + 3); rows += k * EN; kick += k * 3;
+  const bool has = pl.has[k] != 0;  // (uniform over the workgroup)
+  if (has) {
+    noise_fill(pl.k[k][0], pl.k[k][1], impl, (uint64_t)(EN + 3), (uint64_t)threadIdx.x, (uint64_t)blockDim.x, eps);
+    __syncthreads();  // (the normals are read back by other threads of this workgroup)
+  }
+  const float a = has ? pl.act_std[k] : 0.0f;
+  for (int e = threadIdx.x; e < EN; e += blockDim.x) rows[e] = a == 0.0f ? M[e] : M[e] + a * eps[e];
+  if (threadIdx.x < 3) kick[threadIdx.x] = has ? pl.kick_std[k] * eps[EN + threadIdx.x] : 0.0f;
+}
+// the kicks of a sweep's episodes, one workgroup per episode, behind the rollout(s) that wrote the tick's states [P][S] into
+// the state log: episodes whose kick_std is 0 (no record, no kick, not in this tick) are left alone
+static __global__ __launch_bounds__(64) void mpc_kick_batch_kernel(SweepPlant pl, float* __restrict__ states, int S,
+                                                             const float* __restrict__ kick, int planar) {
+  const long long k = blockIdx.y;
+  const int j = threadIdx.x;
+  if (!pl.has[k] || !(pl.kick_std[k] > 0.0f) || j >= 3 || (planar && j == 1)) return;
+  float* v = states + k * S + kLinkVel + j;
+  *v = *v + kick[k * 3 + j];
 }
 
 // the materialised candidates of P path-integral plans in one launch (blockIdx.y = plan; grid-stride over the thread-items

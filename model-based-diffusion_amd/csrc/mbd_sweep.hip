@@ -51,6 +51,13 @@ struct mbd_sweep {
   // Ybar [P][HNu].  Sweep-owned, like a plan's.
   float *d_mpc_states = nullptr, *d_mpc_means = nullptr, *d_mpc_rewards = nullptr, *d_mpc_rows = nullptr, *d_mpc_ybar = nullptr;
   size_t mpc_ticks = 0;
+  // the episodes' plant records (mbd_sweep_set_mpc_plant; copies, the plant envs are the caller's), and what a batch with
+  // records needs beyond the above: the log of the executed rows, tick-major [T][P][E Nu] — the tick's rollouts read their
+  // slices of it —, the tick's normals [P][(H-1) Nu + 3] and kick values [P][3]
+  mbd_mpc_plant plant_rec[MBD_SWEEP_MAX_PLANS] = {};
+  bool has_plant[MBD_SWEEP_MAX_PLANS] = {};
+  float *d_mpc_actions = nullptr, *d_plant_eps = nullptr, *d_plant_kick = nullptr;
+  size_t mpc_actions_cap = 0;
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
@@ -68,6 +75,7 @@ struct mbd_sweep {
     (void)hipFree(d_Y0s); (void)hipFree(d_sigma); (void)hipFree(d_spread); (void)hipFree(d_idx);
     (void)hipFree(d_mpc_states); (void)hipFree(d_mpc_means); (void)hipFree(d_mpc_rewards); (void)hipFree(d_mpc_rows);
     (void)hipFree(d_mpc_ybar);
+    (void)hipFree(d_mpc_actions); (void)hipFree(d_plant_eps); (void)hipFree(d_plant_kick);
     for (int b = 0; b < 3; ++b)
       if (ev_ready[b]) (void)hipEventDestroy(ev_ready[b]);
     if (ev_order) (void)hipEventDestroy(ev_order);
@@ -423,6 +431,21 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
   return MBD_OK;
 }
 
+extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "episode k=%d outside [0,%d)", k, w->P);
+  if (!rec) {
+    w->has_plant[k] = false;
+    w->plant_rec[k] = mbd_mpc_plant{};
+    return MBD_OK;
+  }
+  int rc = check_mpc_plant(w->env, rec);
+  if (rc != MBD_OK) return rc;
+  w->plant_rec[k] = *rec;
+  w->has_plant[k] = true;
+  return MBD_OK;
+}
+
 // Batched receding horizon (include/mbd_hip.h): P episodes in lockstep, the host only enqueues.  The episodes' logs are
 // tick-major on the device, so that the rollout of the executed rows writes s_{.,t+1} of all P episodes straight into slice
 // t+1 of the state log (state_final is [B][S]) and the next tick's rollouts read their start states from that same slice:
@@ -430,6 +453,11 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
 // mpc_boundary_batch_kernel and the rollout of the executed rows, one candidate per episode — stream-ordered between the
 // tick's last weighted mean and the next tick's first rollout, so the ring of noise buffers and the progress word carry
 // across ticks with their argument unchanged (mbd_sweep): the steps of all ticks count through as one loop.
+// With plant records (mbd_sweep_set_mpc_plant) the boundary grows in the same place on the same stream — behind
+// mpc_boundary_batch_kernel come mpc_plant_rows_kernel (every episode's normals, executed rows and kick values), one rollout
+// launch per maximal run of consecutive episodes that share a plant handle, each over its slice of the tick's rows, rewards
+// and states, and, in the ticks where an episode is kicked, mpc_kick_batch_kernel on slice t+1 of the state log — so that
+// argument is unchanged once more; the disturbance key chains are host arithmetic.  Without records: the two launches above.
 extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const uint32_t* keys, float* actions_out,
                                  float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
@@ -458,6 +486,24 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     HIP_TRY(hipMalloc(&w->d_mpc_rewards, sizeof(float) * (size_t)T * P * (H - 1)));
     w->mpc_ticks = (size_t)T;
   }
+  const int EN = E * Nu;
+  bool any_plant = false;
+  for (int k = 0; k < P; ++k) any_plant = any_plant || w->has_plant[k];
+  if (any_plant) {
+    if ((size_t)T * P * EN > w->mpc_actions_cap) {
+      HIP_TRY(hipFree(w->d_mpc_actions));
+      w->d_mpc_actions = nullptr; w->mpc_actions_cap = 0;
+      HIP_TRY(hipMalloc(&w->d_mpc_actions, sizeof(float) * (size_t)T * P * EN));
+      w->mpc_actions_cap = (size_t)T * P * EN;
+    }
+    if (!w->d_plant_eps) HIP_TRY(hipMalloc(&w->d_plant_eps, sizeof(float) * (size_t)P * ((size_t)(H - 1) * Nu + 3)));
+    if (!w->d_plant_kick) HIP_TRY(hipMalloc(&w->d_plant_kick, sizeof(float) * (size_t)P * 3));
+  }
+  const int planar = (e->model.flags & MBD_FLAG_PLANAR) ? 1 : 0;
+  // the disturbance key chains: dk, d_t = split(dk) per tick and episode
+  std::vector<uint32_t> dk(2 * (size_t)P, 0u);
+  for (int k = 0; k < P; ++k)
+    if (w->has_plant[k]) { dk[2 * k] = w->plant_rec[k].key[0]; dk[2 * k + 1] = w->plant_rec[k].key[1]; }
   hipStream_t s = w->stream;
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(w->aux));
@@ -501,9 +547,45 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
                        (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, HNu, E * Nu, w->d_mpc_ybar,
                        w->d_mpc_means + (size_t)t * P * HNu, w->d_mpc_rows);
     HIP_TRY(hipGetLastError());
-    int rc = launch_rollout(e, states_t, w->d_mpc_rows, P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr, nullptr,
-                            w->d_mpc_states + (size_t)(t + 1) * P * S, s, nullptr, exec_sw);
-    if (rc != MBD_OK) return rc;
+    if (!any_plant) {
+      int rc = launch_rollout(e, states_t, w->d_mpc_rows, P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr, nullptr,
+                              w->d_mpc_states + (size_t)(t + 1) * P * S, s, nullptr, exec_sw);
+      if (rc != MBD_OK) return rc;
+      continue;
+    }
+    SweepPlant sp{};
+    bool any_kick = false;
+    for (int k = 0; k < P; ++k) {
+      if (!w->has_plant[k]) continue;
+      const mbd_mpc_plant& pr = w->plant_rec[k];
+      uint32_t dkk[4];
+      host_split(&dk[2 * k], 2, c.prng_impl, dkk);
+      dk[2 * k] = dkk[0]; dk[2 * k + 1] = dkk[1];
+      const bool kick_now = pr.kick_std > 0.0f && (t + 1) % pr.kick_every == 0;
+      any_kick = any_kick || kick_now;
+      sp.k[k][0] = dkk[2]; sp.k[k][1] = dkk[3];
+      sp.act_std[k] = pr.act_std; sp.kick_std[k] = kick_now ? pr.kick_std : 0.0f; sp.has[k] = 1;
+    }
+    float* rows_t = w->d_mpc_actions + (size_t)t * P * EN;
+    float* rewards_t = w->d_mpc_rewards + (size_t)t * P * E;
+    float* states_t1 = w->d_mpc_states + (size_t)(t + 1) * P * S;
+    hipLaunchKernelGGL(mpc_plant_rows_kernel, dim3(1, (unsigned)P), dim3(256), 0, s, sp, c.prng_impl,
+                       (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, EN, w->d_plant_eps, rows_t, w->d_plant_kick);
+    HIP_TRY(hipGetLastError());
+    auto plant_of = [&](int k) { return w->has_plant[k] && w->plant_rec[k].plant ? w->plant_rec[k].plant : e; };
+    for (int k0 = 0; k0 < P;) {  // one launch per run of episodes that share a plant handle
+      int k1 = k0 + 1;
+      while (k1 < P && plant_of(k1) == plant_of(k0)) ++k1;
+      int rc = launch_rollout(plant_of(k0), states_t + (size_t)k0 * S, rows_t + (size_t)k0 * EN, k1 - k0, E,
+                              rewards_t + (size_t)k0 * E, nullptr, nullptr, states_t1 + (size_t)k0 * S, s, nullptr, exec_sw);
+      if (rc != MBD_OK) return rc;
+      k0 = k1;
+    }
+    if (any_kick) {
+      hipLaunchKernelGGL(mpc_kick_batch_kernel, dim3(1, (unsigned)P), dim3(64), 0, s, sp, states_t1, S,
+                         (const float*)w->d_plant_kick, planar);
+      HIP_TRY(hipGetLastError());
+    }
   }
   HIP_TRY(hipStreamSynchronize(s));
   const auto t1 = std::chrono::steady_clock::now();
@@ -523,6 +605,14 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     for (int t = 0; t <= T; ++t)
       for (int k = 0; k < P; ++k)
         memcpy(states_out + ((size_t)k * (T + 1) + t) * S, tmp.data() + ((size_t)t * P + k) * S, sizeof(float) * (size_t)S);
+  }
+  if (any_plant && actions_out) {  // (the executed rows carry the action noise: their own log)
+    tmp.resize((size_t)T * P * EN);
+    HIP_TRY(hipMemcpy(tmp.data(), w->d_mpc_actions, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
+    for (int t = 0; t < T; ++t)
+      for (int k = 0; k < P; ++k)
+        memcpy(actions_out + ((size_t)k * T + t) * EN, tmp.data() + ((size_t)t * P + k) * EN, sizeof(float) * (size_t)EN);
+    actions_out = nullptr;
   }
   if (means_out || actions_out) {  // (the executed rows are M_t[0:E]: taken from the one copy of the means)
     tmp.resize((size_t)T * P * HNu);

@@ -39,15 +39,21 @@ class MpcConfig(C.Structure):
                 ("reserved", C.c_int32 * 5)]
 
 
+class MpcPlant(C.Structure):
+    """mbd_mpc_plant (include/mbd_hip.h): the env that executes an episode's rows, and the episode's disturbances."""
+    _fields_ = [("plant", C.c_void_p), ("key", C.c_uint32 * 2), ("act_std", C.c_float), ("kick_std", C.c_float),
+                ("kick_every", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 EXPORTS = [
     "mbd_last_error", "mbd_version", "mbd_tuned_spec", "mbd_device_count", "mbd_prng_key", "mbd_prng_split",
     "mbd_env_create", "mbd_env_name", "mbd_builtin_model", "mbd_env_get_model", "mbd_env_xref", "mbd_env_xref_logpd",
     "mbd_env_observe", "mbd_model_observe", "mbd_model_forward", "mbd_env_create_car2d", "mbd_env_create_model", "mbd_env_destroy", "mbd_env_info", "mbd_env_reset", "mbd_env_pipeline_init",
     "mbd_env_step", "mbd_env_rew_xref", "mbd_env_rollout", "mbd_plan_create", "mbd_plan_destroy",
     "mbd_plan_schedule", "mbd_plan_set_state0", "mbd_plan_sample_rollout", "mbd_plan_prefetch_noise", "mbd_plan_score_update",
-    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
+    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
-    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
+    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
     "mbd_exchange_create", "mbd_exchange_destroy", "mbd_exchange_local_handle", "mbd_exchange_connect",
     "mbd_exchange_all_gather", "mbd_exchange_status", "mbd_exchange_fine_grained",
 ]
@@ -110,6 +116,7 @@ def load() -> C.CDLL:
     lib.mbd_plan_reverse_once.argtypes = [_vp, _i, _u32p, _vp, _vp, _vp]
     lib.mbd_plan_run.argtypes = [_vp, _u32p, _vp, _vp, _fp, C.POINTER(C.c_double)]
     lib.mbd_plan_run_mpc.argtypes = [_vp, C.POINTER(MpcConfig), _u32p, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]
+    lib.mbd_plan_set_mpc_plant.argtypes = [_vp, C.POINTER(MpcPlant)]
     lib.mbd_plan_eval.argtypes = [_vp, _vp, _fp]
     lib.mbd_plan_peek.argtypes = [_vp, _vp, _vp, _vp]
     lib.mbd_plan_kernel_time.argtypes = [_vp, _fp, C.POINTER(_i), _i]
@@ -119,6 +126,7 @@ def load() -> C.CDLL:
     lib.mbd_sweep_set_state0.argtypes = [_vp, _i, _vp]
     lib.mbd_sweep_run.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]
     lib.mbd_sweep_run_mpc.argtypes = [_vp, C.POINTER(MpcConfig), _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]
+    lib.mbd_sweep_set_mpc_plant.argtypes = [_vp, _i, C.POINTER(MpcPlant)]
     lib.mbd_sweep_kernel_time.argtypes = [_vp, _i, _fp, C.POINTER(_i)]
     lib.mbd_sweep_get_sigmas.argtypes = [_vp, _vp]
     lib.mbd_exchange_create.argtypes = [_i, _i, _i, _i, _i, C.POINTER(_vp)]

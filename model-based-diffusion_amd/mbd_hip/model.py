@@ -118,6 +118,25 @@ class Model:
                 setattr(m, extra, getattr(self, extra))
         return m
 
+    def scaled(self, mass: float = 1.0, friction: float = 1.0, gear: float = 1.0) -> "Model":
+        """A copy of the model with every link ``mass`` times as heavy (``inv_mass`` and ``inv_inertia`` divided by it), the
+        contact ``friction`` and the actuators' ``act_gear`` multiplied — float32 arithmetic; everything else is shared with
+        this model.  The mismatched plants a robustness study starts with (planners.mpc, ``Plan.set_mpc_plant``).  The
+        ``masses`` / ``inertias`` diagnostics of a model from ``mjcf.load`` are scaled along."""
+        f = dict(self.fields)
+        m_, fr, g = np.float32(mass), np.float32(friction), np.float32(gear)
+        if not (np.isfinite(m_) and m_ > 0 and np.isfinite(fr) and fr >= 0 and np.isfinite(g)):
+            raise ValueError(f"scaled(mass={mass}, friction={friction}, gear={gear}): mass > 0, friction >= 0, all finite")
+        f["inv_mass"] = (np.asarray(f["inv_mass"], np.float32) / m_).astype(np.float32)
+        f["inv_inertia"] = (np.asarray(f["inv_inertia"], np.float32) / m_).astype(np.float32)
+        f["friction"] = float(np.float32(f["friction"]) * fr)
+        f["act_gear"] = (np.asarray(f["act_gear"], np.float32) * g).astype(np.float32)
+        m = Model(f, self.link_names, self.actuator_names, self.env_name)
+        for extra in ("masses", "inertias"):
+            if hasattr(self, extra):
+                setattr(m, extra, np.asarray(getattr(self, extra)) * float(mass))
+        return m
+
     def to_struct(self) -> MbdModel:
         s = MbdModel()
         for name in _SCALARS:

@@ -82,6 +82,7 @@ class Sweep:
                                               C.byref(h)))
         self.h = h
         self.Nd, self.H, self.Nu = cfg.Ndiffuse, args.Hsample, env.action_size
+        self._plant_envs = {}  # episode -> the plant env of its record (kept alive: a record does not own its plant)
 
     def set_state0(self, k: int, state):
         st = np.ascontiguousarray(state.pipeline_state, np.float32).reshape(-1)
@@ -122,6 +123,18 @@ class Sweep:
         out["seconds"] = secs.value
         return out
 
+    def set_mpc_plant(self, k: int, env=None, key=None, act_std: float = 0.0, kick_std: float = 0.0, kick_every: int = 1):
+        """The plant of episode ``k`` (``Plan.set_mpc_plant``): episode k of ``run_mpc`` is then ``Plan.run_mpc`` with that
+        record, bit for bit.  Episodes may carry different plants, keys and stds, or none; consecutive episodes that share
+        a plant env are executed in one launch.  The sweep keeps a reference to ``env``."""
+        rec = _plant_record(env, key, act_std, kick_std, kick_every)
+        _capi.check(self.lib.mbd_sweep_set_mpc_plant(self.h, int(k), C.byref(rec)))
+        self._plant_envs[int(k)] = env
+
+    def clear_mpc_plant(self, k: int):
+        _capi.check(self.lib.mbd_sweep_set_mpc_plant(self.h, int(k), None))
+        self._plant_envs.pop(int(k), None)
+
     def get_sigmas(self):
         """path-integral sweeps: every plan's carried sigma after the last run (path_integral.py:113,131)."""
         out = np.zeros(self.P, np.float32)
@@ -143,6 +156,16 @@ class Sweep:
             self.close()
         except Exception:
             pass
+
+
+def _plant_record(env, key, act_std, kick_std, kick_every):
+    """The mbd_mpc_plant of ``set_mpc_plant``'s arguments (``key`` None: the key of seed 0)."""
+    rec = _capi.MpcPlant()
+    rec.plant = None if env is None else env.handle
+    k = np.ascontiguousarray(_capi.prng_key(0) if key is None else key, np.uint32).reshape(2)
+    rec.key[0], rec.key[1] = int(k[0]), int(k[1])
+    rec.act_std, rec.kick_std, rec.kick_every = float(act_std), float(kick_std), int(kick_every)
+    return rec
 
 
 class Plan:
@@ -169,6 +192,7 @@ class Plan:
         _capi.check(self.lib.mbd_plan_create(env.handle, C.byref(cfg), C.byref(h)))
         self.h = h
         self.Nd, self.H, self.Nu = cfg.Ndiffuse, args.Hsample, env.action_size
+        self._plant_env = None  # the plant env of the plan's record (kept alive: a record does not own its plant)
 
     def schedule(self):
         a, ab, s = (np.zeros(self.Nd, np.float32) for _ in range(3))
@@ -213,6 +237,20 @@ class Plan:
                                               _capi.np_ptr(out["means"]), C.byref(secs)))
         out["seconds"] = secs.value
         return out
+
+    def set_mpc_plant(self, env=None, key=None, act_std: float = 0.0, kick_std: float = 0.0, kick_every: int = 1):
+        """The plant of the plan's episodes (include/mbd_hip.h mbd_mpc_plant): ``run_mpc`` then executes the rows on ``env``
+        (None: the plan's own env; any env of the same topology, e.g. ``RigidBodyEnv(name, model=env.sys.scaled(mass=1.3))``)
+        with normal noise of std ``act_std`` on every executed action and a velocity kick of std ``kick_std`` on link 0
+        after every ``kick_every``-th tick, drawn on the device from ``key``'s own chain.  ``run`` ignores it.  The plan keeps
+        a reference to ``env``."""
+        rec = _plant_record(env, key, act_std, kick_std, kick_every)
+        _capi.check(self.lib.mbd_plan_set_mpc_plant(self.h, C.byref(rec)))
+        self._plant_env = env
+
+    def clear_mpc_plant(self):
+        _capi.check(self.lib.mbd_plan_set_mpc_plant(self.h, None))
+        self._plant_env = None
 
     def get_sigma(self) -> float:
         v = C.c_float()

@@ -8,6 +8,17 @@ first ``exec_steps`` rows of the new one — the whole episode on the device.  T
 prints one JSON line (timings of a second episode, after a warm-up one in the same process).  ``--n_episodes P`` runs the
 seeds ``seed .. seed+P-1`` as ONE batch of lockstep episodes (mbd_sweep_run_mpc; ``run_mpc_batch``): a diffusion step of a tick
 is one rollout launch over all the episodes' candidates, and every episode is the single one bit for bit.
+
+The system need not be the model (include/mbd_hip.h mbd_mpc_plant; DESIGN.md section 1 "N5 plant"): ``--plant_mass``,
+``--plant_friction``, ``--plant_gear`` execute the rows on a copy of the env whose links are that many times as heavy, whose
+contact friction and actuator gears are multiplied (``Model.scaled``); ``--act_noise_std`` adds normal noise to every executed
+action, ``--kick_std`` / ``--kick_every`` shove link 0 after every kick_every-th tick.  The disturbances are drawn on the device
+from ``prng_key(disturb_seed)`` — that key as it is, folded with nothing else: episodes of different ``seed`` share their
+disturbance chain unless ``disturb_seed`` differs too (the episodes of ``--n_episodes P`` all do: one noise realisation).  The planner keeps planning with the unperturbed model.  With every one
+of these at its default no plant record is set at all and the JSON line is what it always was; with a record it also carries
+the plant settings and ``nominal_episode_reward``: the same episode without the record, run in the same process.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --n_ticks 100 --plant_mass 1.3 --act_noise_std 0.2 --n_episodes 8
 """
 from __future__ import annotations
 
@@ -29,6 +40,48 @@ class MpcArgs(Args):
     n_ticks: int = 50  # control ticks T of the episode
     warm_steps: int = 20  # diffusion steps K..1 of every tick after the first (the noise level it restarts from: sigma_K)
     exec_steps: int = 1  # control steps E executed per tick; the plan then shifts by E rows
+    plant_mass: float = 1.0  # the plant's links are this many times as heavy as the model's
+    plant_friction: float = 1.0  # the plant's contact friction, as a multiple of the model's
+    plant_gear: float = 1.0  # the plant's actuator gears, as a multiple of the model's
+    act_noise_std: float = 0.0  # std of the normal noise added to every executed action (before the env's clip)
+    kick_std: float = 0.0  # std per component (m/s) of the velocity kick on link 0 ...
+    kick_every: int = 1  # ... at the end of every kick_every-th tick
+    disturb_seed: int = 0  # the disturbance key is prng_key(disturb_seed), folded with nothing else
+
+
+_PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
+
+
+def _plant_settings(args: MpcArgs) -> dict:
+    return {f: getattr(args, f) for f in _PLANT_FIELDS}
+
+
+def _has_plant(args: MpcArgs) -> bool:
+    """Whether the arguments ask for a plant record at all (every default: none is set)."""
+    return any(getattr(args, f) != MpcArgs.__dataclass_fields__[f].default for f in _PLANT_FIELDS)
+
+
+def _plant_env(env, args: MpcArgs, device: int, cache: dict = None):
+    """The env that executes the rows: None (the planner's own) unless mass / friction / gear differ from 1; one env per
+    distinct triple in ``cache``."""
+    triple = (float(args.plant_mass), float(args.plant_friction), float(args.plant_gear))
+    if triple == (1.0, 1.0, 1.0):
+        return None
+    if not hasattr(env, "sys"):
+        raise ValueError(f"env_name={args.env_name!r} has no rigid-body model to scale: plant_mass / plant_friction / "
+                         "plant_gear need one")
+    if cache is not None and triple in cache:
+        return cache[triple]
+    from ..envs.base import RigidBodyEnv
+    plant = RigidBodyEnv(args.env_name, device=device, model=env.sys.scaled(*triple))
+    if cache is not None:
+        cache[triple] = plant
+    return plant
+
+
+def _record_kwargs(env, args: MpcArgs, device: int, cache: dict = None) -> dict:
+    return dict(env=_plant_env(env, args, device, cache), key=_capi.prng_key(args.disturb_seed), act_std=args.act_noise_std,
+                kick_std=args.kick_std, kick_every=args.kick_every)
 
 
 def _reset_and_key(env, seed: int):
@@ -46,12 +99,15 @@ def _setup(args: MpcArgs, device: int):
     state_init, rng_exp = _reset_and_key(env, args.seed)
     plan = Plan(env, args)
     plan.set_state0(state_init)
+    if _has_plant(args):
+        plan.set_mpc_plant(**_record_kwargs(env, args, device))
     return env, plan, state_init, rng_exp
 
 
 def _check_batch(arg_list) -> None:
     """What a batch of lockstep episodes takes (the rule of scripts.run_mbd._batchable): up to 32 episodes of one rigid-body
-    env with one set of sizes, schedule and (T, K, E); seeds and temperatures may differ.  Decided from the arguments alone."""
+    env with one set of sizes, schedule and (T, K, E); seeds, temperatures and the plant settings may differ.  Decided from the
+    arguments alone."""
     from dataclasses import asdict
 
     from ..scripts.run_mbd import _resolved
@@ -60,9 +116,9 @@ def _check_batch(arg_list) -> None:
     ds = [asdict(_resolved(a)) for a in arg_list]
     for k, d in enumerate(ds):
         for f, v in d.items():
-            if f not in ("seed", "temp_sample", "not_render") and v != ds[0][f]:
+            if f not in ("seed", "temp_sample", "not_render") + _PLANT_FIELDS and v != ds[0][f]:
                 raise ValueError(f"{f} differs between episodes 0 and {k} ({ds[0][f]!r}, {v!r}): the episodes of a batch "
-                                 "may differ in seed and temp_sample only")
+                                 "may differ in seed, temp_sample and the plant settings only")
     if ds[0]["env_name"] in ("car2d", "pushT"):
         raise ValueError(f"env_name={ds[0]['env_name']!r}: batches run rigid-body envs; run its episodes one by one")
     if ds[0]["Nsample"] * 4 > 48 * 1024:
@@ -78,10 +134,12 @@ def _setup_batch(arg_list, device: int):
     a0 = arg_list[0]
     env = get_env(a0.env_name, device=device)
     sweep = Sweep(env, a0, len(arg_list), temps=[a.temp_sample for a in arg_list])
-    states, keys = [], []
+    states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
         sweep.set_state0(k, state_init)
+        if _has_plant(a):  # (one plant env per distinct (mass, friction, gear): episodes in a row that share it share a launch)
+            sweep.set_mpc_plant(k, **_record_kwargs(env, a, device, plants))
         states.append(state_init)
         keys.append(rng_exp)
     return env, sweep, states, np.array(keys, np.uint32)
@@ -91,7 +149,8 @@ _LOGS = ("actions", "rewards", "states", "means")
 
 
 def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
-    """The episodes of ``arg_list`` (MpcArgs that differ in ``seed`` and ``temp_sample`` only, else ValueError naming the field)
+    """The episodes of ``arg_list`` (MpcArgs that differ in ``seed``, ``temp_sample`` and the plant settings only, else ValueError
+    naming the field)
     as ONE batch in lockstep.  Episode k is ``run_mpc(arg_list[k])`` bit for bit.  Returns the list of the episodes' mean
     rewards; ``return_details`` adds the list of their detail dicts (as ``run_mpc``'s; ``seconds`` is the whole batch's).
     Unless the first episode says ``not_render``: results/<env>/mpc_episode.npz, its arrays with a leading episode axis when
@@ -107,8 +166,8 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
     if not arg_list[0].not_render:
         _save(arg_list[0], ep if len(arg_list) > 1 else {k: ep[k][0] for k in _LOGS})
     if return_details:
-        return rewards, [dict({f: ep[f][k] for f in _LOGS}, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt)
-                         for k in range(len(arg_list))]
+        return rewards, [dict({f: ep[f][k] for f in _LOGS}, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
+                              **_plant_settings(arg_list[k])) for k in range(len(arg_list))]
     return rewards
 
 
@@ -133,7 +192,7 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
     if not args.not_render:
         _save(args, ep)
     if return_details:
-        return reward, dict(ep, state_init=state_init, key=key, dt=env.dt)
+        return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args))
     return reward
 
 
@@ -163,6 +222,10 @@ def _main(argv=None) -> dict:
         plan.run_mpc(key, T, K, E)  # warm-up
         _, _, _, open_secs = plan.run(key)
         ep = plan.run_mpc(key, T, K, E)
+        nominal = None
+        if _has_plant(args):  # what the perturbation cost: the same episode without the record
+            plan.clear_mpc_plant()
+            nominal = float(plan.run_mpc(key, T, K, E)["rewards"].mean())
         plan.close()
     steps = (Nd - 1) + (T - 1) * K  # diffusion steps the episode ran
     secs = ep["seconds"]
@@ -170,9 +233,11 @@ def _main(argv=None) -> dict:
     res = dict(env=args.env_name, Nsample=args.Nsample, Hsample=args.Hsample, Ndiffuse=Nd, n_ticks=T, warm_steps=K,
                exec_steps=E, ms_per_tick=1e3 * secs / T, ticks_per_s=T / secs, ms_per_diffusion_step=1e3 * secs / steps,
                open_loop_ms_per_diffusion_step=open_ms,
-               # what a tick costs beyond its diffusion steps at the open-loop rate: the two boundary launches
+               # what a tick costs beyond its diffusion steps at the open-loop rate: the boundary launches (two; three with a plant record)
                boundary_ms_per_tick=(1e3 * secs - steps * open_ms) / T,
                real_time_factor=T * E * env.dt / secs, episode_reward=float(ep["rewards"].mean()))
+    if nominal is not None:  # (without a record the line is what it always was)
+        res.update(_plant_settings(args), nominal_episode_reward=nominal)
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -196,9 +261,16 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
         sweep.run_mpc(keys, T, K, E)  # warm-up
         _, _, _, open_secs = sweep.run(keys, outputs=False)
         ep = sweep.run_mpc(keys, T, K, E)
+        nominal = None
+        if _has_plant(a0):  # what the perturbation cost: the same batch without the records
+            for k in range(P):
+                sweep.clear_mpc_plant(k)
+            nominal = [float(r.mean()) for r in sweep.run_mpc(keys, T, K, E)["rewards"]]
         sweep.close()
         plan = Plan(env, a0)
         plan.set_state0(states[0])
+        if _has_plant(a0):
+            plan.set_mpc_plant(**_record_kwargs(env, a0, 0))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -210,13 +282,15 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
     res = dict(env=a0.env_name, Nsample=a0.Nsample, Hsample=a0.Hsample, Ndiffuse=Nd, n_ticks=T, warm_steps=K, exec_steps=E,
                n_episodes=P, ms_per_tick=1e3 * secs / T, ticks_per_s=T / secs, episode_ticks_per_s=P * T / secs,
                ms_per_diffusion_step=1e3 * secs / steps, open_loop_ms_per_diffusion_step=open_ms,
-               # what a tick of the batch costs beyond its diffusion steps at the sweep's open-loop rate: the two boundary launches
+               # what a tick of the batch costs beyond its diffusion steps at the sweep's open-loop rate: the boundary launches
                boundary_ms_per_tick=(1e3 * secs - steps * open_ms) / T,
                real_time_factor=T * E * env.dt / secs, episode_reward=float(np.mean(rews)), episode_rewards=rews,
                episode_reward_mean=float(np.mean(rews)), episode_reward_std=float(np.std(rews)),
                # one episode of the first seed on a plan of its own, and what P of them one after another cost against the batch
                sequential_episode_seconds=seq["seconds"], single_open_loop_ms_per_diffusion_step=open_ms_1,
                speedup=P * seq["seconds"] / secs, open_loop_ratio=P * open_ms_1 / open_ms)
+    if nominal is not None:  # (without records the line is what it always was)
+        res.update(_plant_settings(a0), nominal_episode_reward=float(np.mean(nominal)))
     if not a0.not_render:
         _save(a0, ep)
     print(json.dumps(res), flush=True)
