@@ -221,6 +221,11 @@ struct RolloutChoice {
 RolloutChoice choose_rollout(const EnvShape& s, const mbd_model_t& m, int n_cus, int B, int H, const int* sweep, bool has_xref);
 // choose_rollout for an env (car2d: no choice — its rollout is not a RolloutParams instantiation)
 RolloutChoice rollout_choice(const mbd_env* env, int B, int H, const int* sweep = nullptr);
+// Whether a launch of that choice takes a noise job of nz_N x nz_HNu normals into its own workgroups (launch_rollout's
+// decision, for the plans that ask in advance): fuses_noise, and for a launch pinned to one XCD enough noise workgroups —
+// a sharded plan generates the normals of ALL N candidates beside a rollout of its shard only.  false: the job runs on the
+// plan's second stream, which then has to be ordered behind the buffer's last reader.
+bool rollout_takes_noise(const RolloutChoice& c, int nz_impl, int nz_N, int nz_HNu);
 // launch of the env's rollout instantiation; sweep as above.  d_lp: the demo log-densities [B] accumulated inside the
 // rollout (RolloutParams::lp) — only where the choice's fuses_logpd says so (the caller then passes d_lp instead of d_xpos
 // and skips launch_logpd)

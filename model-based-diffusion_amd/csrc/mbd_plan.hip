@@ -232,7 +232,9 @@ extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sa
       lz.nz_impl = c.prng_impl; lz.nz_N = N; lz.nz_HNu = HNu;
       // (launches that take the job into spare workgroups need no second stream and none of its events: a record
       // behind every weighted mean idles the queue ~5.5 us, 1 % of a step — profiles/r02_timeline.txt)
-      noise_on_aux = !rollout_choice(e, c.shard_count, H).fuses_noise;
+      // (asked of the launch's own decision: a one-workgroup shard of a large plan pins its rollout and still cannot take
+      // the job — its normals then need the second stream's ordering like a full-chip launch's)
+      noise_on_aux = !rollout_takes_noise(rollout_choice(e, c.shard_count, H), c.prng_impl, N, HNu);
     }
   } else {
     // A1, materialised (car2d, path-integral updates): every rank samples ALL N candidate sequences.  A sharded plan
@@ -455,7 +457,8 @@ extern "C" int mbd_plan_get_sigma(mbd_plan* p, float* sigma_out) {
 // it needs it and the step's stream carries no event (mbd_plan: the ring of three buffers).
 static int plan_keep_in_step(mbd_plan* p) {
   if (!p->lazy || !p->h_progress || p->seq == 0 || p->cfg.shares_device != 0) return MBD_OK;
-  if (rollout_choice(p->env, p->cfg.shard_count, p->cfg.Hsample).fuses_noise) return MBD_OK;
+  if (rollout_takes_noise(rollout_choice(p->env, p->cfg.shard_count, p->cfg.Hsample), p->cfg.prng_impl, p->cfg.Nsample, p->HNu))
+    return MBD_OK;
   p->kept_in_step = true;
   const auto w0 = std::chrono::steady_clock::now();
   while (progress_read(p->h_progress) < p->seq) {

@@ -535,8 +535,9 @@ def test_two_shards_on_one_gpu_match_unsharded(gpu, impl, monkeypatch):
     g = np.random.default_rng(1)
     Ybar = torch.tensor((g.normal(size=H * 17) * 0.2).astype(np.float32), device="cuda")
     outs = []
-    # (8 shards: the other ranks' rows are then sampled on the plan's second stream, behind the rollout; with the
-    # legacy threefry layout a sub-range is sampled element by element instead of block by block)
+    # (humanoidrun MBD plans are lazy: every shard generates the normals of ALL N rows with noise_kernel, whatever the shard
+    # layout — the materialised plans' three-range launch, where the other ranks' rows are sampled on the second stream and
+    # the legacy layout goes element by element, is not on this path: tests/test_gpu_sampler.py reaches it)
     for shards in ([(0, N)], [(0, N // 2), (N // 2, N // 2)], [(0, 64), (64, 64), (128, 64), (192, 64)],
                    [(k * 32, 32) for k in range(8)]):
         plans = [Plan(env, args, shard_begin=b, shard_count=c) for b, c in shards]
