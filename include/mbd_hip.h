@@ -431,6 +431,53 @@ typedef struct mbd_mpc_plant {
  * cartpole's cart on a rail and for car2d, which has no links).  act_std works for every env. */
 int mbd_plan_set_mpc_plant(mbd_plan* plan, const mbd_mpc_plant* rec);
 
+/* ---- ensembles: planning over perturbed copies of the model (domain randomisation; no counterpart in the reference, which
+ * scores every candidate on one nominal model; DESIGN.md section 1 "N6 ensemble") ---- */
+#define MBD_MAX_ENSEMBLE 8
+enum mbd_risk_mode {
+  MBD_RISK_MEAN = 0, /* a candidate's reward is its mean over the members */
+  MBD_RISK_MIN = 1   /* ... its worst over the members */
+};
+/* An ensemble record is a setting of a plan, like the plant record: the M member envs every candidate is rolled out on, and how
+ * the M returns become the candidate's reward. */
+typedef struct mbd_ensemble {
+  mbd_env* members[MBD_MAX_ENSEMBLE]; /* entries [0, n_members); NULL = the plan's own env.  Not owned: the caller keeps them alive */
+  int32_t n_members;                  /* M, 1 <= M <= MBD_MAX_ENSEMBLE */
+  int32_t risk;                       /* mbd_risk_mode */
+  int32_t reserved[6];                /* must be 0 */
+} mbd_ensemble;
+/* With a record, diffusion step i becomes — everything not shown is unchanged:
+ *   eps, Y0s = as without a record (ONE set of normals and candidates, from the step's key; mbd_planner.py:103-106)
+ *   for m in 0..M-1:  r_m[n] = mean_H( rollout_{member m}(state0, Y0s[n]) )   (each exactly what that env's rollout path gives)
+ *   rews[n] = ((r_0[n] + r_1[n]) + ... + r_{M-1}[n]) / float(M)               MBD_RISK_MEAN: f32, left to right, ONE division
+ *           = min(min(r_0[n], r_1[n]), ...)                                   MBD_RISK_MIN: left to right
+ *             (min(a, b) = b if b < a or b is NaN, else a: a member whose rollout diverged to NaN makes the candidate's
+ *             reward NaN under MIN as it does under MEAN — a diverged member is the worst case, never hidden)
+ *   standardise, softmax, weighted mean, score update on rews as without a record; rew_mean out = rews.mean()
+ * Hence: a plan without a record is unchanged (same launches, same bits); a record of M = 1 whose member is NULL, or a second
+ * env of the same model, gives the plan without a record under either risk mode; MIN does not depend on the members' order;
+ * r_m equals mbd_env_rollout on member m's env for the same Y0s.  mbd_plan_eval and the final reward of mbd_plan_run keep
+ * using the plan's own env.  One rollout launch over the M * Nsample candidates per step (a wavefront picks its member's model
+ * in its prologue) and one small launch that combines the M rows in front of the score; when Nsample is not a multiple of the
+ * candidates a wavefront of the chosen instantiation holds, M rollout launches on the plan's stream instead (same bits).
+ * The record is read by mbd_plan_sample_rollout (whose d_rews_local receives the COMBINED rewards; mbd_plan_score_update is
+ * unchanged), mbd_plan_reverse_once, mbd_plan_run and mbd_plan_run_mpc — there the planner plans with the ensemble from the
+ * state the plant reached, and the executed rows still go through the plant's env (the plan's env without a plant record).
+ * The record is copied and stays until cleared (rec == NULL) or the handle is destroyed.  Refused at the set call, before any
+ * launch, each message naming the field.  MBD_ERR_INVALID: NULL plan; n_members outside [1, MBD_MAX_ENSEMBLE]; an unknown risk;
+ * non-zero reserved; a member on another device; a member that differs from the plan's env in anything that decides a launch
+ * or a template parameter — n_links (hence state_size), action_size (n_act), the planar flag, the spec-flag word (flags),
+ * reward_kind, n_frames, colliders per link, the tree and lane tables, the demo reference table xref (a tracking reward reads it), iso_inertia / the inertia shape, and the wave-uniform
+ * switches slide_limits, max_children, max_rot, any_stiff, has_weld.  Members may differ in data only — masses, inertias,
+ * friction, gears, damping and the like: everything mbd_hip.model.Model.scaled produces is accepted.  MBD_ERR_UNSUPPORTED:
+ * enable_demo (which member's log-density would count?), a path-integral update_method, car2d (it has no model).
+ * MBD_ERR_STATE: a sharded plan.  Sweeps (mbd_sweep_*) take no ensemble: at M = 4 a single plan already fills the chip. */
+int mbd_plan_set_ensemble(mbd_plan* plan, const mbd_ensemble* rec);
+/* the last step's per-member rewards r_m, rews_members_out [M][Nsample], and the combined rewards, rews_out [Nsample] (HOST;
+ * either may be NULL; synchronises the device).  MBD_ERR_STATE without a record or before the first step with one.  With a
+ * record, mbd_plan_peek's rewss_out is member 0's. */
+int mbd_plan_peek_ensemble(mbd_plan* plan, float* rews_members_out, float* rews_out);
+
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
  * candidates Y0s [Nsample][H][Nu] (plans that keep normals instead form them here, from the normals, sigma_i and the
  * Ybar_i of the last step — between phase 1 and phase 2 the caller's d_Ybar_i must still be unchanged), the shard's

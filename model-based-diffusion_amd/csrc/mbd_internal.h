@@ -153,6 +153,12 @@ struct mbd_plan {
   bool has_plant = false;
   float *d_mpc_actions = nullptr, *d_plant_eps = nullptr, *d_plant_kick = nullptr;
   size_t mpc_actions_cap = 0, plant_eps_cap = 0;
+  // the ensemble record (mbd_plan_set_ensemble; a copy, NULL members resolved to the plan's env — the envs are the caller's)
+  // and its buffers: the members' rewards r_m [M][N] and per-step rewards [M][N][H] of the rollout launch over M N
+  // candidates, and the library's own copy of the combined rewards [N] (mbd_plan_peek_ensemble)
+  mbd_ensemble ens_rec{};
+  bool has_ens = false, ens_stepped = false;
+  float *d_ens_rews = nullptr, *d_ens_rewss = nullptr, *d_ens_comb = nullptr;
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
@@ -170,6 +176,7 @@ struct mbd_plan {
     (void)hipFree(d_eps[0]); (void)hipFree(d_eps[1]); (void)hipFree(d_eps[2]); (void)hipFree(d_ybar_keep);
     (void)hipFree(d_mpc_state); (void)hipFree(d_mpc_states); (void)hipFree(d_mpc_means); (void)hipFree(d_mpc_rewards);
     (void)hipFree(d_mpc_actions); (void)hipFree(d_plant_eps); (void)hipFree(d_plant_kick);
+    (void)hipFree(d_ens_rews); (void)hipFree(d_ens_rewss); (void)hipFree(d_ens_comb);
     if (h_progress) (void)hipHostFree(h_progress);
     for (int b = 0; b < 3; ++b)
       if (ev_noise[b]) (void)hipEventDestroy(ev_noise[b]);
@@ -211,6 +218,7 @@ struct RolloutChoice {
   dim3 grid, block;                // the rollout's own workgroups (launch_rollout adds the noise job's and the XCD pin's)
   size_t lds = 0;                  // dynamic LDS each workgroup reserves
   int cpw = 0;                     // RolloutParams::cpw: candidates per wavefront of an early-out launch, 0: filled
+  int spw = 1;                     // candidates a wavefront of the launch holds (cpw, or the layout's, twice that two per lane)
   int wpe = 1;                     // two-candidates-per-lane launches: wavefronts per SIMD the instantiation is asked for
   bool xcd_pin = false;            // the launch goes to one XCD (RolloutParams::xcd_pin)
   bool fuses_noise = false;        // a launch with a noise job takes it into spare workgroups
@@ -226,12 +234,21 @@ RolloutChoice rollout_choice(const mbd_env* env, int B, int H, const int* sweep 
 // a sharded plan generates the normals of ALL N candidates beside a rollout of its shard only.  false: the job runs on the
 // plan's second stream, which then has to be ordered behind the buffer's last reader.
 bool rollout_takes_noise(const RolloutChoice& c, int nz_impl, int nz_N, int nz_HNu);
-// launch of the env's rollout instantiation; sweep as above.  d_lp: the demo log-densities [B] accumulated inside the
+// An ensemble launch (RolloutParams::ens_M): the candidates d_us [N] on each of the M member envs, outputs [M][N]...; the
+// launch's switches, tables and choice are env's (mbd_plan_set_ensemble has checked that the members share them).
+struct EnsArgs {
+  int M = 0;
+  mbd_env* const* members = nullptr;  // [M], none NULL
+};
+// the choice of an ensemble's rollout over M N candidates, and whether ONE launch serves it (N a multiple of the candidates
+// per wavefront of that choice); otherwise launch_rollout runs M launches of N candidates, one per member
+RolloutChoice ensemble_choice(const mbd_env* env, int M, int N, int H, bool* one_launch);
+// launch of the env's rollout instantiation; sweep as above.  ens: B is the plan's N, the outputs hold M rows of it.  d_lp: the demo log-densities [B] accumulated inside the
 // rollout (RolloutParams::lp) — only where the choice's fuses_logpd says so (the caller then passes d_lp instead of d_xpos
 // and skips launch_logpd)
 int launch_rollout(mbd_env* env, const float* d_state0, const float* d_us, int B, int H, float* d_rewss, float* d_rews,
                    float* d_xpos, float* d_state_final, hipStream_t stream, LazyArgs* lz = nullptr, const int* sweep = nullptr,
-                   float* d_lp = nullptr);
+                   float* d_lp = nullptr, const EnsArgs* ens = nullptr);
 // whether the device is a whole 8-XCD part (the premise of the XCD-pinned launch forms)
 bool device_has_eight_xcds(const mbd_env* env);
 int launch_logpd(const mbd_env* e, const float* d_xpos, int B, int H, float* d_out, hipStream_t s);

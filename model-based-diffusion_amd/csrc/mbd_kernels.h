@@ -109,7 +109,21 @@ struct RolloutParams {
   // trip through HBM and its launch.  xref: [K][H][3] (device).  The launcher tells its caller whether it happened.
   float* lp;
   const float* xref;
+  // ENSEMBLES (mbd_plan_set_ensemble: one set of candidates rolled out on ens_M perturbed copies of the model in ONE launch).
+  // ens_M > 0: the launch holds ens_M * plan_N candidates, candidate b runs on member b / plan_N's model — ens_model[m] and
+  // its per-lane records ens_lane_rec[m] ([3][16] LaneRec3, laid out like lane_rec) instead of model / lane_rec — and fetches
+  // row b % plan_N of `us`; both plan strides are 0 (one start state, one Ybar).  A wavefront never straddles two members
+  // (the host launches this form only when plan_N is a multiple of the candidates per wavefront), so the choice is scalar,
+  // made once in the prologue.  The members share everything that decides a launch or a template parameter; the switches
+  // and tables above are the plan's env's.  ens_M = 0: every other launch, which reads none of this.
+  int ens_M;
+  const mbd_model_t* ens_model[MBD_MAX_ENSEMBLE];
+  const void* ens_lane_rec[MBD_MAX_ENSEMBLE];
 };
+// the member a wavefront of an ensemble launch works for, from the wavefront's first candidate (wave-uniform, made scalar)
+__device__ __forceinline__ int ens_member(const RolloutParams& P, int b_first) {
+  return __builtin_amdgcn_readfirstlane((b_first < P.B ? b_first : P.B - 1) / P.plan_N);
+}
 __device__ __forceinline__ void rollout_progress(const RolloutParams& P) {
   if (P.progress && blockIdx.x == 0 && threadIdx.x == 0)
     __hip_atomic_store(P.progress, P.progress_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -936,20 +950,30 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
   if (rblock < 0) return;
   const unsigned long long dbg_t0 = P.dbg_clock ? __builtin_amdgcn_s_memtime() : 0ull;
   unsigned long long dbg_t1 = 0ull, dbg_t2 = 0ull, dbg_t3 = 0ull;  // (probes: prologue / first / second control step done)
-  const mbd_model_t* __restrict__ Mg = P.model;  // the wave-uniform scalars of the model
-  const int lane = threadIdx.x & 63;
-  const int base = lane & ~(LPS - 1);
-  const int l_lane = lane & (LPS - 1);
-  // ---- per-lane model constants: the record lane_setup3_kernel gathered at env creation, one batch of reads --------
-  const LaneRec3& R = reinterpret_cast<const LaneRec3*>(P.lane_rec[HELP ? 2 : (DPP ? 1 : 0)])[l_lane];
-  const int L = Mg->n_links;
-  const bool link_ok = R.link_ok != 0;
-  const int l = R.l;
-  const bool root_lane = R.root_lane != 0;  // the lane that owns link 0 (rewards, control cost)
   constexpr int SPW = 64 / LPS;
   // a workgroup is 1 or 4 INDEPENDENT wavefronts (nothing shared, no barrier): four-wave workgroups are how a launch
   // of >= 1024 wavefronts gets one wavefront on every SIMD of a CU (dispatch)
   const int wave_id = rblock * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  // ensembles (RolloutParams::ens_M): this wavefront's member — its model, its lane records, its first candidate
+  const mbd_model_t* model_sel = P.model;
+  const LaneRec3* rec_sel = reinterpret_cast<const LaneRec3*>(P.lane_rec[HELP ? 2 : (DPP ? 1 : 0)]);
+  int ens_b0 = 0;
+  if (P.ens_M > 0) {
+    const int m = ens_member(P, wave_id * SPW);
+    model_sel = P.ens_model[m];
+    rec_sel = reinterpret_cast<const LaneRec3*>(P.ens_lane_rec[m]) + 16 * (HELP ? 2 : (DPP ? 1 : 0));
+    ens_b0 = m * P.plan_N;
+  }
+  const mbd_model_t* __restrict__ Mg = model_sel;  // the wave-uniform scalars of the model
+  const int lane = threadIdx.x & 63;
+  const int base = lane & ~(LPS - 1);
+  const int l_lane = lane & (LPS - 1);
+  // ---- per-lane model constants: the record lane_setup3_kernel gathered at env creation, one batch of reads --------
+  const LaneRec3& R = rec_sel[l_lane];
+  const int L = Mg->n_links;
+  const bool link_ok = R.link_ok != 0;
+  const int l = R.l;
+  const bool root_lane = R.root_lane != 0;  // the lane that owns link 0 (rewards, control cost)
   const int b_raw = wave_id * SPW + lane / LPS;
   const bool b_ok = b_raw < P.B;
   const int b = b_ok ? b_raw : P.B - 1;
@@ -1061,7 +1085,7 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
   v3 w = mk3(s0[10], s0[11], s0[12]);
   if (!link_ok) { p = mk3(0, 0, 0); r = q4{1, 0, 0, 0}; v = mk3(0, 0, 0); w = mk3(0, 0, 0); }
 
-  const float* u_row = P.us + (size_t)b * H * Nu;
+  const float* u_row = P.us + (size_t)(b - ens_b0) * H * Nu;  // (ensembles: row b % plan_N)
   // lazy candidates (wave-uniform): u_row holds normals, the action is clip(eps * sigma + Ybar_i[t][a], -1, 1)
   // (branch-free: the Ybar loads are unconditional — from P.us itself, ignored, when the launch is not lazy — and the
   // choice is a select; branches around loads make the compiler wait for every load in flight at the joins)

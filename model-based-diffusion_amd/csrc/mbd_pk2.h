@@ -244,17 +244,27 @@ __global__ __launch_bounds__(256, WPE) void rollout_pk2_kernel(RolloutParams P) 
     return;
   }
   constexpr int LPS = 16;
-  const mbd_model_t* __restrict__ Mg = P.model;
+  constexpr int PPW = 64 / LPS;  // candidate PAIRS per wavefront
+  const int wave_id = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  // ensembles (RolloutParams::ens_M): this wavefront's member — its model, its lane records, its first candidate
+  const mbd_model_t* model_sel = P.model;
+  const LaneRec3* rec_sel = reinterpret_cast<const LaneRec3*>(P.lane_rec[1]);
+  int ens_b0 = 0;
+  if (P.ens_M > 0) {
+    const int m = ens_member(P, wave_id * PPW * 2);
+    model_sel = P.ens_model[m];
+    rec_sel = reinterpret_cast<const LaneRec3*>(P.ens_lane_rec[m]) + 16;
+    ens_b0 = m * P.plan_N;
+  }
+  const mbd_model_t* __restrict__ Mg = model_sel;
   const int lane = threadIdx.x & 63;
   const int base = lane & ~(LPS - 1);
   const int l_lane = lane & (LPS - 1);
-  const LaneRec3& R = reinterpret_cast<const LaneRec3*>(P.lane_rec[1])[l_lane];
+  const LaneRec3& R = rec_sel[l_lane];
   const int L = Mg->n_links;
   const bool link_ok = R.link_ok != 0;
   const int l = R.l;
   const bool root_lane = R.root_lane != 0;
-  constexpr int PPW = 64 / LPS;  // candidate PAIRS per wavefront
-  const int wave_id = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const int bA_raw = (wave_id * PPW + lane / LPS) * 2, bB_raw = bA_raw + 1;
   const bool okA = bA_raw < P.B, okB = bB_raw < P.B;
   const int bA = okA ? bA_raw : P.B - 1, bB = okB ? bB_raw : P.B - 1;
@@ -314,8 +324,8 @@ __global__ __launch_bounds__(256, WPE) void rollout_pk2_kernel(RolloutParams P) 
   v3x2 p = bcast3(p1), v = bcast3(v1), w = bcast3(w1);
   q4x2 r = bcast4(r1);
 
-  const float* uA = P.us + (size_t)bA * H * Nu;
-  const float* uB = P.us + (size_t)bB * H * Nu;
+  const float* uA = P.us + (size_t)(bA - ens_b0) * H * Nu;  // (ensembles: row b % plan_N)
+  const float* uB = P.us + (size_t)(bB - ens_b0) * H * Nu;
   const bool lazy = P.ybar != nullptr;
   const float* __restrict__ yb_row = lazy ? P.ybar + (size_t)pl * P.plan_ybar_stride : P.us;
   const float sigma = P.sigma;

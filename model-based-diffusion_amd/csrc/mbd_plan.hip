@@ -107,6 +107,17 @@ extern "C" int mbd_plan_set_state0(mbd_plan* p, const float* state0) {
   return MBD_OK;
 }
 
+// the choice of the plan's rollout launch — the one that carries the progress word and may take the noise job: the launch
+// over M N candidates of a plan with an ensemble record (its first member launch when the members are launched one by one)
+static RolloutChoice plan_rollout_choice(const mbd_plan* p) {
+  if (p->has_ens) {
+    bool one = false;
+    const RolloutChoice c = ensemble_choice(p->env, p->ens_rec.n_members, p->cfg.Nsample, p->cfg.Hsample, &one);
+    if (one) return c;
+  }
+  return rollout_choice(p->env, p->cfg.shard_count, p->cfg.Hsample);
+}
+
 static int ensure_aux(mbd_plan* p) {
   if (p->aux) return MBD_OK;
   HIP_TRY(hipStreamCreateWithFlags(&p->aux, hipStreamNonBlocking));
@@ -234,7 +245,7 @@ extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sa
       // behind every weighted mean idles the queue ~5.5 us, 1 % of a step — profiles/r02_timeline.txt)
       // (asked of the launch's own decision: a one-workgroup shard of a large plan pins its rollout and still cannot take
       // the job — its normals then need the second stream's ordering like a full-chip launch's)
-      noise_on_aux = !rollout_takes_noise(rollout_choice(e, c.shard_count, H), c.prng_impl, N, HNu);
+      noise_on_aux = !rollout_takes_noise(plan_rollout_choice(p), c.prng_impl, N, HNu);
     }
   } else {
     // A1, materialised (car2d, path-integral updates): every rank samples ALL N candidate sequences.  A sharded plan
@@ -316,10 +327,24 @@ extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sa
   // A5: the demo log-densities of the local shard come out of the rollout itself where its instantiation accumulates them
   // (round 6: no [shard][H][K][3] round trip, no second launch); otherwise from the tracked positions, below
   const bool fused_lp = c.enable_demo && rollout_choice(e, c.shard_count, H).fuses_logpd;
-  int rc = launch_rollout(e, p->d_state0, d_cand + (size_t)c.shard_begin * HNu, c.shard_count, H, p->d_rewss,
-                          d_rews_local, (c.enable_demo && !fused_lp) ? p->d_xpos : nullptr, nullptr, s, p->lazy ? &lz : nullptr,
-                          nullptr, fused_lp ? d_logpd_local : nullptr);
-  if (rc != MBD_OK) return rc;
+  int rc;
+  if (p->has_ens) {
+    // the ensemble (include/mbd_hip.h mbd_ensemble): the N candidates on every member, then the members' rewards combined
+    // into the caller's buffer — phase 2 is handed those and is unchanged.  (unsharded, no demo: the set call's refusals)
+    const EnsArgs ea{p->ens_rec.n_members, p->ens_rec.members};
+    rc = launch_rollout(e, p->d_state0, d_cand, N, H, p->d_ens_rewss, p->d_ens_rews, nullptr, nullptr, s,
+                        p->lazy ? &lz : nullptr, nullptr, nullptr, &ea);
+    if (rc != MBD_OK) return rc;
+    hipLaunchKernelGGL(ensemble_reduce_kernel, dim3((N + 255) / 256), dim3(256), 0, s, (const float*)p->d_ens_rews,
+                       p->ens_rec.n_members, N, p->ens_rec.risk, d_rews_local, p->d_ens_comb);
+    HIP_TRY(hipGetLastError());
+    p->ens_stepped = true;
+  } else {
+    rc = launch_rollout(e, p->d_state0, d_cand + (size_t)c.shard_begin * HNu, c.shard_count, H, p->d_rewss,
+                        d_rews_local, (c.enable_demo && !fused_lp) ? p->d_xpos : nullptr, nullptr, s, p->lazy ? &lz : nullptr,
+                        nullptr, fused_lp ? d_logpd_local : nullptr);
+    if (rc != MBD_OK) return rc;
+  }
   if (p->timing) HIP_TRY(hipEventRecord(ev1, s));
   if (lz.nz_out) {
     if (!lz.nz_fused) {  // the rollout fills the chip: the next step's normals on the second stream, beside it
@@ -457,8 +482,7 @@ extern "C" int mbd_plan_get_sigma(mbd_plan* p, float* sigma_out) {
 // it needs it and the step's stream carries no event (mbd_plan: the ring of three buffers).
 static int plan_keep_in_step(mbd_plan* p) {
   if (!p->lazy || !p->h_progress || p->seq == 0 || p->cfg.shares_device != 0) return MBD_OK;
-  if (rollout_takes_noise(rollout_choice(p->env, p->cfg.shard_count, p->cfg.Hsample), p->cfg.prng_impl, p->cfg.Nsample, p->HNu))
-    return MBD_OK;
+  if (rollout_takes_noise(plan_rollout_choice(p), p->cfg.prng_impl, p->cfg.Nsample, p->HNu)) return MBD_OK;
   p->kept_in_step = true;
   const auto w0 = std::chrono::steady_clock::now();
   while (progress_read(p->h_progress) < p->seq) {
@@ -597,6 +621,135 @@ extern "C" int mbd_plan_set_mpc_plant(mbd_plan* p, const mbd_mpc_plant* rec) {
   if (rc != MBD_OK) return rc;
   p->plant_rec = *rec;
   p->has_plant = true;
+  return MBD_OK;
+}
+
+// ---- the ensemble record (include/mbd_hip.h mbd_ensemble) ---------------------------------------------------------------
+// the refusals of a record against the plan — host arithmetic, no launch
+static int check_ensemble(const mbd_plan* p, const mbd_ensemble* rec) {
+  const mbd_env* env = p->env;
+  const mbd_plan_config& c = p->cfg;
+  if (rec->n_members < 1 || rec->n_members > MBD_MAX_ENSEMBLE)
+    return fail(MBD_ERR_INVALID, "ensemble record: n_members=%d outside [1, %d]", rec->n_members, MBD_MAX_ENSEMBLE);
+  if (rec->risk != MBD_RISK_MEAN && rec->risk != MBD_RISK_MIN)
+    return fail(MBD_ERR_INVALID, "ensemble record: risk=%d: MBD_RISK_MEAN (0) or MBD_RISK_MIN (1)", rec->risk);
+  for (int r = 0; r < 6; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "ensemble record: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (env->kind != ENV_MODEL) return fail(MBD_ERR_UNSUPPORTED, "ensemble record: env '%s' has no model to perturb", env->name.c_str());
+  if (c.enable_demo) return fail(MBD_ERR_UNSUPPORTED, "ensemble record: enable_demo=1: which member's log-density would count?");
+  if (c.update_method != 0)
+    return fail(MBD_ERR_UNSUPPORTED, "ensemble record: update_method=%d: ensembles score MBD plans only", c.update_method);
+  if (c.shard_count != c.Nsample)
+    return fail(MBD_ERR_STATE, "ensemble record: shard_count=%d of Nsample=%d: ensembles run unsharded plans", c.shard_count, c.Nsample);
+  const mbd_model_t& a = env->model;
+  for (int m = 0; m < rec->n_members; ++m) {
+    const mbd_env* me = rec->members[m];
+    if (!me || me == env) continue;
+#define ENS_SAME(what, x, y)                                                                                              \
+  if ((x) != (y))                                                                                                         \
+    return fail(MBD_ERR_INVALID, "ensemble record: member %d: %s=%d, the plan's env has %d", m, what, (int)(x), (int)(y))
+    ENS_SAME("device", me->device, env->device);
+    if (me->kind != ENV_MODEL) return fail(MBD_ERR_INVALID, "ensemble record: member %d: env '%s' has no model", m, me->name.c_str());
+    const mbd_model_t& b = me->model;
+    ENS_SAME("n_links", b.n_links, a.n_links);
+    ENS_SAME("action_size", b.n_act, a.n_act);
+    ENS_SAME("planar flag", (b.flags & MBD_FLAG_PLANAR) != 0, (a.flags & MBD_FLAG_PLANAR) != 0);
+    ENS_SAME("flags (the spec-flag word)", b.flags & MBD_SPEC_FLAGS, a.flags & MBD_SPEC_FLAGS);
+    ENS_SAME("reward_kind", b.reward_kind, a.reward_kind);
+    ENS_SAME("n_frames", b.n_frames, a.n_frames);
+    ENS_SAME("n_col", b.n_col, a.n_col);
+    ENS_SAME("n_track", b.n_track, a.n_track);
+    ENS_SAME("n_q", b.n_q, a.n_q);
+    ENS_SAME("n_qd", b.n_qd, a.n_qd);
+    for (int k = 0; k < a.n_col; ++k) ENS_SAME("col_link (colliders per link)", b.col_link[k], a.col_link[k]);
+    for (int l = 0; l < a.n_links; ++l) {
+      ENS_SAME("parent (the tree)", b.parent[l], a.parent[l]);
+      ENS_SAME("n_rot (the tree)", b.n_rot[l], a.n_rot[l]);
+      ENS_SAME("n_slide (the tree)", b.n_slide[l], a.n_slide[l]);
+    }
+    for (int k = 0; k < a.n_act; ++k) {
+      ENS_SAME("act_link", b.act_link[k], a.act_link[k]);
+      ENS_SAME("act_slot", b.act_slot[k], a.act_slot[k]);
+    }
+    for (int k = 0; k < a.n_track; ++k) ENS_SAME("track_link", b.track_link[k], a.track_link[k]);
+    // the wave-uniform switches of RolloutParams, then the shape the launch decision and the template parameters are
+    // derived from (EnvShape)
+    ENS_SAME("slide_limits", me->slide_limits, env->slide_limits);
+    ENS_SAME("max_children", me->max_children, env->max_children);
+    ENS_SAME("max_rot", me->max_rot, env->max_rot);
+    ENS_SAME("any_stiff", me->any_stiff, env->any_stiff);
+    ENS_SAME("has_weld", me->has_weld, env->has_weld);
+    ENS_SAME("lps (lane table)", me->lps, env->lps);
+    ENS_SAME("dpp_family (lane table)", me->dpp_family, env->dpp_family);
+    ENS_SAME("lane_tab", memcmp(me->lane_tab, env->lane_tab, sizeof(env->lane_tab)) != 0, 0);
+    ENS_SAME("helpers (lane table)", me->helpers, env->helpers);
+    ENS_SAME("spec", me->spec, env->spec);
+    ENS_SAME("iso_inertia", me->iso, env->iso);
+    ENS_SAME("diag_inertia (inertia shape)", me->diag_inertia, env->diag_inertia);
+    ENS_SAME("axisym (inertia shape)", me->axisym, env->axisym);
+    ENS_SAME("axi (inertia shape)", me->axi, env->axi);
+    ENS_SAME("max_col", me->max_col, env->max_col);
+    ENS_SAME("slides", me->slides, env->slides);
+    ENS_SAME("max_slide", me->max_slide, env->max_slide);
+    ENS_SAME("slides_world_only", me->slides_world_only, env->slides_world_only);
+    ENS_SAME("humanoid_shape", me->humanoid_shape, env->humanoid_shape);
+    ENS_SAME("fl (planar switches)", me->fl, env->fl);
+#undef ENS_SAME
+    // the reference table a tracking reward reads (RolloutParams::xref): the one launch reads the plan's env's for every
+    // member, a member's own launch its own — they have to be the same table
+    if ((me->d_xref != nullptr) != (env->d_xref != nullptr))
+      return fail(MBD_ERR_INVALID, "ensemble record: member %d: xref %s, the plan's env's is %s", m, me->d_xref ? "present" : "absent",
+                  env->d_xref ? "present" : "absent");
+    if (env->d_xref && a.n_track > 0) {
+      const size_t nx = (size_t)a.n_track * kXrefRows * 3;
+      std::vector<float> xa(nx), xb(nx);
+      HIP_TRY(hipSetDevice(env->device));
+      HIP_TRY(hipMemcpy(xa.data(), env->d_xref, sizeof(float) * nx, hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(xb.data(), me->d_xref, sizeof(float) * nx, hipMemcpyDeviceToHost));
+      if (memcmp(xa.data(), xb.data(), sizeof(float) * nx) != 0)
+        return fail(MBD_ERR_INVALID, "ensemble record: member %d: xref differs from the plan's env's", m);
+    }
+  }
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_ensemble(mbd_plan* p, const mbd_ensemble* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (!rec) {
+    p->has_ens = false;
+    p->ens_stepped = false;
+    p->ens_rec = mbd_ensemble{};
+    return MBD_OK;
+  }
+  int rc = check_ensemble(p, rec);
+  if (rc != MBD_OK) return rc;
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the previous record's buffers)
+  const size_t N = (size_t)p->cfg.Nsample, H = (size_t)p->cfg.Hsample, M = (size_t)rec->n_members;
+  HIP_TRY(hipFree(p->d_ens_rews)); HIP_TRY(hipFree(p->d_ens_rewss));
+  p->d_ens_rews = p->d_ens_rewss = nullptr;
+  p->has_ens = false;
+  HIP_TRY(hipMalloc(&p->d_ens_rews, sizeof(float) * M * N));
+  HIP_TRY(hipMalloc(&p->d_ens_rewss, sizeof(float) * M * N * H));
+  if (!p->d_ens_comb) HIP_TRY(hipMalloc(&p->d_ens_comb, sizeof(float) * N));
+  p->ens_rec = *rec;
+  for (int m = 0; m < rec->n_members; ++m)
+    if (!p->ens_rec.members[m]) p->ens_rec.members[m] = p->env;
+  for (int m = rec->n_members; m < MBD_MAX_ENSEMBLE; ++m) p->ens_rec.members[m] = nullptr;
+  p->has_ens = true;
+  p->ens_stepped = false;
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_peek_ensemble(mbd_plan* p, float* rews_members_out, float* rews_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (!p->has_ens) return fail(MBD_ERR_STATE, "peek_ensemble: the plan has no ensemble record");
+  if (!p->ens_stepped) return fail(MBD_ERR_STATE, "peek_ensemble: no diffusion step with the record to show yet");
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t N = (size_t)p->cfg.Nsample, M = (size_t)p->ens_rec.n_members;
+  if (rews_members_out) HIP_TRY(hipMemcpy(rews_members_out, p->d_ens_rews, sizeof(float) * M * N, hipMemcpyDeviceToHost));
+  if (rews_out) HIP_TRY(hipMemcpy(rews_out, p->d_ens_comb, sizeof(float) * N, hipMemcpyDeviceToHost));
   return MBD_OK;
 }
 
@@ -767,7 +920,9 @@ extern "C" int mbd_plan_peek(mbd_plan* p, float* Y0s_out, float* rewss_out, floa
     HIP_TRY(hipStreamSynchronize(p->stream));
   }
   if (Y0s_out) HIP_TRY(hipMemcpy(Y0s_out, p->d_Y0s, sizeof(float) * (size_t)c.Nsample * p->HNu, hipMemcpyDeviceToHost));
-  if (rewss_out) HIP_TRY(hipMemcpy(rewss_out, p->d_rewss, sizeof(float) * (size_t)c.shard_count * c.Hsample, hipMemcpyDeviceToHost));
+  // (with an ensemble record that has stepped: member 0's rows of the launch over all members)
+  const float* rewss = p->has_ens && p->ens_stepped ? p->d_ens_rewss : p->d_rewss;
+  if (rewss_out) HIP_TRY(hipMemcpy(rewss_out, rewss, sizeof(float) * (size_t)c.shard_count * c.Hsample, hipMemcpyDeviceToHost));
   if (weights_out) HIP_TRY(hipMemcpy(weights_out, p->d_weights, sizeof(float) * (size_t)c.Nsample, hipMemcpyDeviceToHost));
   return MBD_OK;
 }

@@ -119,7 +119,21 @@ __global__ __launch_bounds__(256) void rollout_planar_kernel(RolloutParams P) {
   rollout_progress(P);
   const int rblock = rollout_block(P);  // (noise workgroups and the idle ones of a pinned launch are done here: mbd_kernels.h)
   if (rblock < 0) return;
-  const mbd_model_t* __restrict__ M = P.model;
+  constexpr int SPW = 64 / LPS;
+  const int wave_id = rblock * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  // candidates per wavefront: SPW, or (EO) the launch's choice P.cpw, a power of two below it
+  const int cpw = EO ? P.cpw : SPW;
+  const int b_first = wave_id * cpw;
+  // ensembles (RolloutParams::ens_M): this wavefront's member — its model and its first candidate (the planar kernels read
+  // the model itself, no lane records; the tree tables are the plan's env's)
+  const mbd_model_t* model_sel = P.model;
+  int ens_b0 = 0;
+  if (P.ens_M > 0) {
+    const int m = ens_member(P, b_first);
+    model_sel = P.ens_model[m];
+    ens_b0 = m * P.plan_N;
+  }
+  const mbd_model_t* __restrict__ M = model_sel;
   const int lane = threadIdx.x & 63;
   const int base = lane & ~(LPS - 1);
   const int l_lane = lane & (LPS - 1);
@@ -129,12 +143,7 @@ __global__ __launch_bounds__(256) void rollout_planar_kernel(RolloutParams P) {
   const int l = link_ok ? l_link : 0;
   auto lane_of = [&](int link) { return base + (DPP ? (int)P.lane_tab[16 + link] : link); };
   const bool root_lane = link_ok && l == 0;
-  constexpr int SPW = 64 / LPS;
-  const int wave_id = rblock * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  // candidates per wavefront: SPW, or (EO) the launch's choice P.cpw, a power of two below it
-  const int cpw = EO ? P.cpw : SPW;
   const int grp = lane / LPS;
-  const int b_first = wave_id * cpw;
   const int b_raw = b_first + (EO ? (grp & (cpw - 1)) : grp);
   const bool b_ok = b_raw < P.B && grp < cpw;
   // (lanes without a candidate of their own repeat one of the wavefront's: the tail of the launch, the groups beyond cpw)
@@ -273,7 +282,7 @@ __global__ __launch_bounds__(256) void rollout_planar_kernel(RolloutParams P) {
   float px = s0[0], pz = s0[2], qw = s0[3], qy = s0[5], vx = s0[7], vz = s0[9], om = s0[11];
   if (!link_ok) { px = pz = 0.0f; qw = 1.0f; qy = 0.0f; vx = vz = om = 0.0f; }
 
-  const float* u_row = P.us + (size_t)b * H * Nu;
+  const float* u_row = P.us + (size_t)(b - ens_b0) * H * Nu;  // (ensembles: row b % plan_N)
   // lazy candidates (wave-uniform; RolloutParams): u_row holds normals, the action is clip(eps * sigma + Ybar_i, -1, 1)
   // (branch-free, like rollout_kernel: unconditional Ybar loads — from P.us itself, ignored, when not lazy — and selects)
   const bool lazy = P.ybar != nullptr;

@@ -411,6 +411,27 @@ __device__ __forceinline__ float score_block(const float* __restrict__ rews, con
   return block_sum(part, red);
 }
 
+// ---- ensembles (mbd_plan_set_ensemble): the members' rewards r [M][N] -> the candidates' rewards, in front of the score ----
+// MEAN: ((r_0 + r_1) + ... + r_{M-1}) / float(M) — f32, left to right, one division; MIN: min(min(r_0, r_1), ...), left to
+// right, NaN-propagating (min(a, b) = b if b < a or b is NaN, else a).  Two copies: the caller's buffer (what mbd_plan_score_update is handed) and the plan's own (mbd_plan_peek_ensemble).
+static __global__ __launch_bounds__(256) void ensemble_reduce_kernel(const float* __restrict__ r, int M, int N, int risk,
+                                                               float* __restrict__ out, float* __restrict__ keep) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  float a = r[n];
+  if (risk == MBD_RISK_MIN) {
+    for (int m = 1; m < M; ++m) {  // (a NaN return wins: a member that diverged IS the worst case, and MEAN spreads it too)
+      const float b = r[(size_t)m * N + n];
+      a = (b < a || b != b) ? b : a;
+    }
+  } else {
+    for (int m = 1; m < M; ++m) a = a + r[(size_t)m * N + n];
+    a = a / (float)M;
+  }
+  out[n] = a;
+  keep[n] = a;
+}
+
 // Sweeps of path-integral plans (mbd_sweep_*, update_method != 0): the small kernels of the update rules take blockIdx.y
 // = plan and these strides (in elements) from plan 0's data; a single plan launches them with one row and zero strides.
 struct PiBatch {

@@ -45,13 +45,24 @@ class MpcPlant(C.Structure):
                 ("kick_every", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+MAX_ENSEMBLE = 8
+RISK_MEAN, RISK_MIN = 0, 1
+RISKS = {"mean": RISK_MEAN, "min": RISK_MIN}
+
+
+class Ensemble(C.Structure):
+    """mbd_ensemble (include/mbd_hip.h): the member envs every candidate of a plan is rolled out on, and the risk mode."""
+    _fields_ = [("members", C.c_void_p * MAX_ENSEMBLE), ("n_members", C.c_int32), ("risk", C.c_int32),
+                ("reserved", C.c_int32 * 6)]
+
+
 EXPORTS = [
     "mbd_last_error", "mbd_version", "mbd_tuned_spec", "mbd_device_count", "mbd_prng_key", "mbd_prng_split",
     "mbd_env_create", "mbd_env_name", "mbd_builtin_model", "mbd_env_get_model", "mbd_env_xref", "mbd_env_xref_logpd",
     "mbd_env_observe", "mbd_model_observe", "mbd_model_forward", "mbd_env_create_car2d", "mbd_env_create_model", "mbd_env_destroy", "mbd_env_info", "mbd_env_reset", "mbd_env_pipeline_init",
     "mbd_env_step", "mbd_env_rew_xref", "mbd_env_rollout", "mbd_plan_create", "mbd_plan_destroy",
     "mbd_plan_schedule", "mbd_plan_set_state0", "mbd_plan_sample_rollout", "mbd_plan_prefetch_noise", "mbd_plan_score_update",
-    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
+    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
     "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
     "mbd_exchange_create", "mbd_exchange_destroy", "mbd_exchange_local_handle", "mbd_exchange_connect",
@@ -117,6 +128,8 @@ def load() -> C.CDLL:
     lib.mbd_plan_run.argtypes = [_vp, _u32p, _vp, _vp, _fp, C.POINTER(C.c_double)]
     lib.mbd_plan_run_mpc.argtypes = [_vp, C.POINTER(MpcConfig), _u32p, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]
     lib.mbd_plan_set_mpc_plant.argtypes = [_vp, C.POINTER(MpcPlant)]
+    lib.mbd_plan_set_ensemble.argtypes = [_vp, C.POINTER(Ensemble)]
+    lib.mbd_plan_peek_ensemble.argtypes = [_vp, _vp, _vp]
     lib.mbd_plan_eval.argtypes = [_vp, _vp, _fp]
     lib.mbd_plan_peek.argtypes = [_vp, _vp, _vp, _vp]
     lib.mbd_plan_kernel_time.argtypes = [_vp, _fp, C.POINTER(_i), _i]
@@ -142,7 +155,7 @@ def load() -> C.CDLL:
 
 LEVERS = ("MBD_NO_DPP", "MBD_NO_NFR_CONST", "MBD_NO_REWARD_CONST", "MBD_NO_PLANAR_FLAGS", "MBD_NO_FAST_SLIDES",
           "MBD_NO_FUSED_NOISE", "MBD_NO_LAZY", "MBD_NO_PREFETCH", "MBD_NO_AUX", "MBD_WMEAN_SPLIT", "MBD_NO_FUSED_SCORE",
-          "MBD_PK2", "MBD_WPB", "MBD_LDS_RESERVE", "MBD_NO_HELPERS")
+          "MBD_PK2", "MBD_WPB", "MBD_LDS_RESERVE", "MBD_NO_HELPERS", "MBD_ENS_SPLIT")
 
 
 def debug_set(name: str, value: int) -> None:

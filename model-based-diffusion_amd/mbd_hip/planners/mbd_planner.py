@@ -168,6 +168,20 @@ def _plant_record(env, key, act_std, kick_std, kick_every):
     return rec
 
 
+def _ensemble_record(envs, risk):
+    """The mbd_ensemble of ``set_ensemble``'s arguments (an entry None: the plan's own env)."""
+    envs = list(envs)
+    if risk not in _capi.RISKS:
+        raise ValueError(f"risk={risk!r}: one of {sorted(_capi.RISKS)}")
+    if not 1 <= len(envs) <= _capi.MAX_ENSEMBLE:
+        raise ValueError(f"an ensemble has 1..{_capi.MAX_ENSEMBLE} members, not {len(envs)}")
+    rec = _capi.Ensemble()
+    for m, e in enumerate(envs):
+        rec.members[m] = None if e is None else e.handle
+    rec.n_members, rec.risk = len(envs), _capi.RISKS[risk]
+    return rec
+
+
 class Plan:
     """Thin owner of an ``mbd_plan`` handle."""
 
@@ -193,6 +207,7 @@ class Plan:
         self.h = h
         self.Nd, self.H, self.Nu = cfg.Ndiffuse, args.Hsample, env.action_size
         self._plant_env = None  # the plant env of the plan's record (kept alive: a record does not own its plant)
+        self._ens_envs = None   # the member envs of the plan's ensemble record (kept alive likewise)
 
     def schedule(self):
         a, ab, s = (np.zeros(self.Nd, np.float32) for _ in range(3))
@@ -251,6 +266,28 @@ class Plan:
     def clear_mpc_plant(self):
         _capi.check(self.lib.mbd_plan_set_mpc_plant(self.h, None))
         self._plant_env = None
+
+    def set_ensemble(self, envs, risk: str = "mean"):
+        """Plan over an ensemble of perturbed models (include/mbd_hip.h mbd_ensemble): every candidate of every diffusion
+        step is rolled out on each env of ``envs`` (1..8 of them, None: the plan's own env; any env of the same topology,
+        e.g. ``RigidBodyEnv(name, model=env.sys.scaled(mass=1.2))``) and scored by its ``risk`` over them — "mean" or
+        "min" (the worst member).  ``run``, ``run_mpc`` and the step calls read it; ``eval`` and the final reward keep
+        the plan's own env.  The plan keeps references to the envs."""
+        rec = _ensemble_record(envs, risk)
+        _capi.check(self.lib.mbd_plan_set_ensemble(self.h, C.byref(rec)))
+        self._ens_envs = list(envs)
+
+    def clear_ensemble(self):
+        _capi.check(self.lib.mbd_plan_set_ensemble(self.h, None))
+        self._ens_envs = None
+
+    def peek_ensemble(self):
+        """The last step's per-member rewards [M, N] and combined rewards [N] (a plan with an ensemble record)."""
+        M = len(self._ens_envs or ())
+        rm = np.zeros((M, self.cfg.Nsample), np.float32)
+        r = np.zeros(self.cfg.Nsample, np.float32)
+        _capi.check(self.lib.mbd_plan_peek_ensemble(self.h, _capi.np_ptr(rm), _capi.np_ptr(r)))
+        return rm, r
 
     def get_sigma(self) -> float:
         v = C.c_float()
@@ -520,12 +557,14 @@ def reverse_distributed(plan: Plan, key, device, group=None, sync_every_step: bo
 
 
 def run_diffusion(args: Args, device: int = None, return_details: bool = False, progress=None,
-                  force_single: bool = False, measure_phases: bool = False, collective: str = None):
+                  force_single: bool = False, measure_phases: bool = False, collective: str = None, ensemble=None):
     """mbd_planner.py:38-182. Returns rew_final (float); ``return_details`` adds a dict with mu_0ts,
     per-step mean rewards and the reverse-loop wall time.  ``progress(i, rew)`` is called after every diffusion
     step with the step's mean reward, like the reference's progress bar (:147) — one device->host read per step;
     without it the loop runs asynchronously and the means are read once at the end.  ``force_single`` ignores an
-    initialised process group (every rank then runs the whole plan)."""
+    initialised process group (every rank then runs the whole plan).  ``ensemble``: plan over perturbed models
+    (``Plan.set_ensemble``) — a list of member envs (None: the env itself), or a dict(envs=[...], risk="mean" | "min");
+    unsharded plans only."""
     import torch
     import torch.distributed as dist
 
@@ -546,6 +585,9 @@ def run_diffusion(args: Args, device: int = None, return_details: bool = False, 
     else:
         plan = Plan(env, args)
     plan.set_state0(state_init)
+    if ensemble is not None:
+        ens = ensemble if isinstance(ensemble, dict) else dict(envs=ensemble)
+        plan.set_ensemble(ens["envs"], ens.get("risk", "mean"))
     _, _, sigmas = plan.schedule()
     print(f"init sigma = {sigmas[-1]:.2e}")  # :93
 

@@ -19,6 +19,15 @@ of these at its default no plant record is set at all and the JSON line is what 
 the plant settings and ``nominal_episode_reward``: the same episode without the record, run in the same process.
 
     python -m mbd_hip.planners.mpc --env_name hopper --n_ticks 100 --plant_mass 1.3 --act_noise_std 0.2 --n_episodes 8
+
+The planner can answer a wrong model with an ensemble (include/mbd_hip.h mbd_ensemble; DESIGN.md section 1 "N6 ensemble"):
+``--ens_mass``, ``--ens_friction``, ``--ens_gear`` take comma lists, zipped into members (a single value broadcasts, an absent
+list is all 1); member m is the env's model scaled by the m-th triple (``Model.scaled``), and every candidate is scored by its
+mean — ``--ens_risk min``: its worst — return over the members.  Single episodes only.  With plant flags as well,
+``nominal_episode_reward`` is the episode of the SAME planner — ensemble included — without the plant record: what the plant's
+mismatch and disturbances cost that planner, not what the ensemble buys.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --plant_mass 1.25 --ens_mass 0.8,1,1.25,1.5 --ens_risk min
 """
 from __future__ import annotations
 
@@ -47,6 +56,10 @@ class MpcArgs(Args):
     kick_std: float = 0.0  # std per component (m/s) of the velocity kick on link 0 ...
     kick_every: int = 1  # ... at the end of every kick_every-th tick
     disturb_seed: int = 0  # the disturbance key is prng_key(disturb_seed), folded with nothing else
+    ens_mass: str = ""  # comma list: the ensemble members' link masses, as multiples of the model's
+    ens_friction: str = ""  # ... their contact friction
+    ens_gear: str = ""  # ... their actuator gears (the three lists are zipped; a single value broadcasts)
+    ens_risk: str = "mean"  # a candidate's reward over the members: "mean" or "min"
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -59,6 +72,42 @@ def _plant_settings(args: MpcArgs) -> dict:
 def _has_plant(args: MpcArgs) -> bool:
     """Whether the arguments ask for a plant record at all (every default: none is set)."""
     return any(getattr(args, f) != MpcArgs.__dataclass_fields__[f].default for f in _PLANT_FIELDS)
+
+
+_ENS_FIELDS = ("ens_mass", "ens_friction", "ens_gear", "ens_risk")
+
+
+def _has_ensemble(args: MpcArgs) -> bool:
+    return any(getattr(args, f) != MpcArgs.__dataclass_fields__[f].default for f in _ENS_FIELDS)
+
+
+def ensemble_triples(args: MpcArgs) -> list:
+    """The members' (mass, friction, gear) triples: the three comma lists zipped, a single value broadcast, an absent list
+    all 1.  [] without ensemble flags."""
+    if not _has_ensemble(args):
+        return []
+    if args.ens_risk not in _capi.RISKS:
+        raise ValueError(f"ens_risk={args.ens_risk!r}: one of {sorted(_capi.RISKS)}")
+    lists = {f: [float(v) for v in str(getattr(args, f)).split(",") if v.strip()] or [1.0]
+             for f in ("ens_mass", "ens_friction", "ens_gear")}
+    M = max(len(v) for v in lists.values())
+    for f, v in lists.items():
+        if len(v) not in (1, M):
+            raise ValueError(f"{f} lists {len(v)} values, another ensemble list {M}: equal lengths, or a single value")
+    if not 1 <= M <= _capi.MAX_ENSEMBLE:
+        raise ValueError(f"{M} ensemble members: 1 to {_capi.MAX_ENSEMBLE}")
+    return [tuple(v[m] if len(v) > 1 else v[0] for v in lists.values()) for m in range(M)]
+
+
+def _ensemble_envs(env, args: MpcArgs, device: int, cache: dict = None) -> list:
+    """The member envs (None: the env itself, for the triple (1, 1, 1)), built with the plant's cache."""
+    from dataclasses import replace
+    return [_plant_env(env, replace(args, plant_mass=t[0], plant_friction=t[1], plant_gear=t[2]), device, cache)
+            for t in ensemble_triples(args)]
+
+
+def _ensemble_settings(args: MpcArgs) -> dict:
+    return dict(ensemble=[dict(mass=t[0], friction=t[1], gear=t[2]) for t in ensemble_triples(args)], ens_risk=args.ens_risk)
 
 
 def _plant_env(env, args: MpcArgs, device: int, cache: dict = None):
@@ -99,8 +148,11 @@ def _setup(args: MpcArgs, device: int):
     state_init, rng_exp = _reset_and_key(env, args.seed)
     plan = Plan(env, args)
     plan.set_state0(state_init)
+    cache = {}
     if _has_plant(args):
-        plan.set_mpc_plant(**_record_kwargs(env, args, device))
+        plan.set_mpc_plant(**_record_kwargs(env, args, device, cache))
+    if _has_ensemble(args):
+        plan.set_ensemble(_ensemble_envs(env, args, device, cache), args.ens_risk)
     return env, plan, state_init, rng_exp
 
 
@@ -113,6 +165,10 @@ def _check_batch(arg_list) -> None:
     from ..scripts.run_mbd import _resolved
     if not 1 <= len(arg_list) <= MAX_EPISODES:
         raise ValueError(f"{len(arg_list)} episodes: a batch holds 1 to {MAX_EPISODES}")
+    for k, a in enumerate(arg_list):
+        if _has_ensemble(a):
+            raise ValueError(f"episode {k} carries ensemble flags ({', '.join(f for f in _ENS_FIELDS if getattr(a, f) != MpcArgs.__dataclass_fields__[f].default)}): "
+                             "batches of lockstep episodes take no ensemble; run the episodes one by one (run_mpc)")
     ds = [asdict(_resolved(a)) for a in arg_list]
     for k, d in enumerate(ds):
         for f, v in d.items():
@@ -192,7 +248,8 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
     if not args.not_render:
         _save(args, ep)
     if return_details:
-        return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args))
+        ens = _ensemble_settings(args) if _has_ensemble(args) else {}
+        return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens)
     return reward
 
 
@@ -238,6 +295,8 @@ def _main(argv=None) -> dict:
                real_time_factor=T * E * env.dt / secs, episode_reward=float(ep["rewards"].mean()))
     if nominal is not None:  # (without a record the line is what it always was)
         res.update(_plant_settings(args), nominal_episode_reward=nominal)
+    if _has_ensemble(args):
+        res.update(_ensemble_settings(args))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
