@@ -53,23 +53,20 @@ __global__ __launch_bounds__(256) void exchange_wait_kernel(const float* win, in
 struct mbd_exchange {
   int device = 0, rank = 0, world = 1, rows = 1, shard = 0, N = 0;
   unsigned epoch = 0;
-  float* d_win = nullptr;               // own window
+  DevBuf<float> d_win;                  // own window (float words; the flag words behind the values are as wide)
   float* peer[MBD_EXCHANGE_MAX_RANKS];  // every rank's window as seen from here (own: d_win)
   bool opened[MBD_EXCHANGE_MAX_RANKS];
   bool connected = false;
   bool fine_grained = false;            // the window is fine-grained device memory (hipDeviceMallocFinegrained)
-  float* d_all = nullptr;               // [rows][N]: what mbd_exchange_all_gather hands out
-  int* d_err = nullptr;
+  DevBuf<float> d_all;                  // [rows][N]: what mbd_exchange_all_gather hands out
+  DevBuf<int> d_err;
   size_t win_bytes = 0;
   mbd_exchange() { for (int r = 0; r < MBD_EXCHANGE_MAX_RANKS; ++r) { peer[r] = nullptr; opened[r] = false; } }
-  mbd_exchange(const mbd_exchange&) = delete;
-  mbd_exchange& operator=(const mbd_exchange&) = delete;
-  ~mbd_exchange() {
+  ~mbd_exchange() {  // (no kernel may still store into a peer's window; the own buffers release themselves behind this)
     (void)hipSetDevice(device);
     (void)hipDeviceSynchronize();
     for (int r = 0; r < MBD_EXCHANGE_MAX_RANKS; ++r)
       if (opened[r]) (void)hipIpcCloseMemHandle(peer[r]);
-    (void)hipFree(d_win); (void)hipFree(d_all); (void)hipFree(d_err);
   }
 };
 
@@ -90,20 +87,19 @@ extern "C" int mbd_exchange_create(int device, int rank, int world, int rows, in
   // can then sit behind a stale line of the owner's L2 whatever the scope of the owner's loads — a flag seen while the
   // rewards beside it are old.  That is refused (the caller keeps the process group's all-gather) unless the lever
   // MBD_EXCHANGE_COARSE_OK=1 asks for it (single-device dry runs on a runtime without the pool).
+  const size_t win_words = x->win_bytes / sizeof(float);
   x->fine_grained = true;
-  if (env_flag("MBD_EXCHANGE_NO_FINEGRAINED") ||
-      hipExtMallocWithFlags((void**)&x->d_win, x->win_bytes, hipDeviceMallocFinegrained) != hipSuccess) {
+  if (env_flag("MBD_EXCHANGE_NO_FINEGRAINED") || x->d_win.alloc(win_words, true) != hipSuccess) {
     (void)hipGetLastError();
-    x->d_win = nullptr;
     x->fine_grained = false;
     if (!env_flag("MBD_EXCHANGE_COARSE_OK"))
       return fail(MBD_ERR_UNSUPPORTED, "exchange: no fine-grained device memory on device %d (hipExtMallocWithFlags): "
                   "use the process group's all-gather", device);
-    HIP_TRY(hipMalloc(&x->d_win, x->win_bytes));
+    HIP_TRY(x->d_win.alloc(win_words));
   }
   HIP_TRY(hipMemset(x->d_win, 0, x->win_bytes));
-  HIP_TRY(hipMalloc(&x->d_all, sizeof(float) * (size_t)rows * x->N));
-  HIP_TRY(hipMalloc(&x->d_err, sizeof(int)));
+  HIP_TRY(x->d_all.alloc((size_t)rows * x->N));
+  HIP_TRY(x->d_err.alloc(1));
   HIP_TRY(hipMemset(x->d_err, 0, sizeof(int)));
   HIP_TRY(hipDeviceSynchronize());
   x->peer[rank] = x->d_win;

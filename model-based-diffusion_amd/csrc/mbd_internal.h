@@ -1,7 +1,8 @@
 // mbd_internal.h — what the translation units of libmbd_hip.so's host side share (NOT part of the boundary: the C ABI is
-// include/mbd_hip.h): the handle structs, error reporting, the test levers, and the launch functions one unit defines for
-// the others.  Units: mbd_env.hip (library, levers, envs, the rollout launch), mbd_plan.hip (plans: one reverse-diffusion
-// step and the loops over it), mbd_sweep.hip (sweeps: several plans per launch), mbd_exchange.hip (the in-library exchange).
+// include/mbd_hip.h): the owners of runtime resources, the env handle, error reporting, the test levers, what plans and
+// sweeps do alike, and the functions one unit defines for the others.  (A handle only its own unit uses is defined there.)
+// Units: mbd_env.hip (library, levers, envs, the rollout launch), mbd_plan.hip (plans: one reverse-diffusion step and the
+// loops over it), mbd_sweep.hip (sweeps: several plans per launch), mbd_exchange.hip (the in-library exchange).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@
 #include <set>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/mbd_hip.h"
@@ -35,6 +37,12 @@ int fail(int code, const char* fmt, ...);
     hipError_t _e = (expr);                                                                   \
     if (_e != hipSuccess)                                                                     \
       return fail(MBD_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+  } while (0)
+// the same for a function of this library that has already set the message
+#define MBD_TRY(expr)                \
+  do {                               \
+    int _rc = (expr);                \
+    if (_rc != MBD_OK) return _rc;   \
   } while (0)
 
 
@@ -61,131 +69,101 @@ enum EnvKind { ENV_CAR2D = 0, ENV_MODEL = 1 };
 constexpr int kLdsN = 36 * 1024;  // candidates whose logp0 fits the score kernel's LDS (144 KB of the CU's 160)
 
 
+// ---- owners of runtime resources ---------------------------------------------------------------------------------------
+// What a handle struct holds of the device, by type: each owner releases in its destructor, so a handle's destructor lists
+// nothing, and an exit of a create function, early or not, leaks nothing.  Move-only.  Allocation and creation are calls
+// that return hipError_t (HIP_TRY at the call site), not constructors: what is created on first use stays that way.
+// Members are destroyed in reverse order of declaration: a handle declares its streams in front of its buffers.
+template <typename T>
+class DevBuf {  // n elements of device memory; converts to T*, so kernel argument lists read as with a raw pointer
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); return *this; }
+  ~DevBuf() { (void)hipFree(p_); }
+  // n elements, whatever it held before.  The one spelling of free, null, allocate, record: a failed allocation leaves an
+  // empty buffer.  fine_grained: hipDeviceMallocFinegrained memory (the exchange's window)
+  hipError_t alloc(size_t n, bool fine_grained = false) {
+    hipError_t e = hipFree(p_);
+    p_ = nullptr; n_ = 0;
+    if (e != hipSuccess) return e;
+    e = fine_grained ? hipExtMallocWithFlags((void**)&p_, sizeof(T) * n, hipDeviceMallocFinegrained) : hipMalloc(&p_, sizeof(T) * n);
+    if (e != hipSuccess) p_ = nullptr;
+    else n_ = n;
+    return e;
+  }
+  hipError_t grow(size_t n) { return n <= n_ ? hipSuccess : alloc(n); }  // at least n elements; the contents do not survive
+  operator T*() const { return p_; }
+  T* get() const { return p_; }  // (where no conversion happens by itself: a deduced parameter, an operand of ?:)
+
+ private:
+  T* p_ = nullptr;
+  size_t n_ = 0;
+};
+
+class Stream {  // a non-blocking stream
+ public:
+  Stream() = default;
+  Stream(Stream&& o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+  Stream& operator=(Stream&& o) noexcept { std::swap(s_, o.s_); return *this; }
+  ~Stream() { if (s_) (void)hipStreamDestroy(s_); }
+  hipError_t create() { return hipStreamCreateWithFlags(&s_, hipStreamNonBlocking); }
+  operator hipStream_t() const { return s_; }
+
+ private:
+  hipStream_t s_ = nullptr;
+};
+
+class Event {
+ public:
+  Event() = default;
+  Event(Event&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+  Event& operator=(Event&& o) noexcept { std::swap(e_, o.e_); return *this; }
+  ~Event() { if (e_) (void)hipEventDestroy(e_); }
+  hipError_t create(unsigned flags = hipEventDisableTiming) { return hipEventCreateWithFlags(&e_, flags); }
+  operator hipEvent_t() const { return e_; }
+
+ private:
+  hipEvent_t e_ = nullptr;
+};
+
+class PinnedWord {  // one int of pinned host memory the device stores into (a progress word), zero at creation
+ public:
+  PinnedWord() = default;
+  PinnedWord(PinnedWord&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  PinnedWord& operator=(PinnedWord&& o) noexcept { std::swap(h_, o.h_); return *this; }
+  ~PinnedWord() { if (h_) (void)hipHostFree(h_); }
+  hipError_t create() {
+    const hipError_t e = hipHostMalloc((void**)&h_, sizeof(int), hipHostMallocDefault);
+    if (e == hipSuccess) *h_ = 0;
+    return e;
+  }
+  operator int*() const { return h_; }
+
+ private:
+  int* h_ = nullptr;
+};
+
 struct mbd_env : EnvShape {  // (the shape: derive_shape, at creation; car2d keeps the defaults)
   int kind = ENV_MODEL;
   int device = 0;
   std::string name;
   mbd_model_t model;
-  mbd_model_t* d_model = nullptr;
-  float* d_xref = nullptr;
+  DevBuf<mbd_model_t> d_model;
+  DevBuf<float> d_xref;
   bool has_xref = false;
   float rew_xref = 0.0f;
   int n_cus = 256;  // compute units of the device (hipDeviceProp_t::multiProcessorCount; four SIMDs each)
-  signed char* d_lane_tab = nullptr;
-  LaneRec3* d_lane_rec = nullptr;  // [3][16]: per-lane constants of the 3-D kernels (lane = link; the DPP layout; the
-                                   // DPP layout with helper lanes)
+  DevBuf<signed char> d_lane_tab;
+  DevBuf<LaneRec3> d_lane_rec;  // [3][16]: per-lane constants of the 3-D kernels (lane = link; the DPP layout; the
+                                // DPP layout with helper lanes)
   unsigned long long* dbg_clock = nullptr;  // per env, caller-owned device buffer (mbd_debug_set_clock_buffer; probes only)
   // scratch for the single-env step path
-  float *d_s_in = nullptr, *d_act = nullptr, *d_s_out = nullptr, *d_rew = nullptr;
-  mbd_env() = default;
-  mbd_env(const mbd_env&) = delete;
-  mbd_env& operator=(const mbd_env&) = delete;
-  ~mbd_env() {  // owns its device buffers: every exit of the create functions, early or not, releases them
-    (void)hipSetDevice(device);
-    (void)hipFree(d_model); (void)hipFree(d_xref); (void)hipFree(d_lane_tab); (void)hipFree(d_lane_rec);
-    (void)hipFree(d_s_in); (void)hipFree(d_s_out); (void)hipFree(d_act); (void)hipFree(d_rew);
-  }
+  DevBuf<float> d_s_in, d_act, d_s_out, d_rew;
+  ~mbd_env() { (void)hipSetDevice(device); }  // (the buffers release themselves, on the env's device)
   int state_size() const { return kind == ENV_CAR2D ? 3 : model.n_links * MBD_LINK_STATE; }
   int action_size() const { return kind == ENV_CAR2D ? 2 : model.n_act; }
   int observation_size() const;
-};
-
-struct mbd_plan {
-  mbd_env* env = nullptr;
-  hipStream_t last_stream = nullptr;  // stream of the plan's previous phase call (plan_enter orders a change of stream)
-  bool last_stream_set = false;
-  hipEvent_t ev_xs = nullptr;
-  mbd_plan_config cfg;
-  int HNu = 0;
-  std::vector<float> alphas, alphas_bar, sigmas;
-  hipStream_t stream = nullptr;
-  // second stream: the non-lazy sharded sampler's other-rank rows, and the next step's normals of lazy plans whose
-  // rollout fills the chip (smaller rollouts generate them in spare workgroups of their own launch)
-  hipStream_t aux = nullptr;
-  hipEvent_t ev_in = nullptr, ev_aux = nullptr;
-  bool aux_pending = false;
-  float *d_state0 = nullptr, *d_Y0s = nullptr, *d_rewss = nullptr, *d_rews = nullptr, *d_lp = nullptr;
-  float *d_xpos = nullptr, *d_weights = nullptr, *d_Ybar = nullptr, *d_mu = nullptr, *d_rewmeans = nullptr;
-  float *d_scratch = nullptr;
-  float* d_wm_partial = nullptr;  // [64][HNu] partials of the split weighted mean (plans of >= 4096 candidates)
-  float* d_lg = nullptr;          // [N] logp0 scratch of the score kernel for plans beyond kLdsN candidates
-  // LAZY plans (the MBD update on a rigid-body env): the candidates are never materialised.  d_eps[b] holds the normals
-  // eps [N][HNu] of a diffusion step; the rollout's action fetch and the weighted mean form clip(eps sigma_i + Ybar_i)
-  // on the fly (RolloutParams).  A ring of buffers: while step k reads one, the normals of step k+1 (they depend on that
-  // step's key only) are generated into the next — by spare workgroups of step k's rollout launch, or on the aux
-  // stream when that launch fills the chip (mbd_plan_prefetch_noise declares the key).  THREE buffers, so that the aux
-  // stream needs no event from the step's stream while the caller keeps in step with the device: the buffer step k+1's
-  // normals go into was last read by step k-2's weighted mean, which has finished once the rollout of step k-1 has
-  // STARTED — every rollout launch of the plan stores its sequence number into h_progress (pinned host memory) as it
-  // starts, and the host looks there.  A caller that runs ahead of the device (mbd_plan_run's loop, the async leg of the
-  // bench) gets the event-ordered form: a mark on the step's stream in front of the rollout, a wait on the aux stream.
-  // (Other launches between two steps on the step's stream — a receding-horizon episode's two per tick — change neither
-  // argument: they are stream-ordered behind the weighted mean and in front of the next rollout.)
-  bool lazy = false;
-  float* d_eps[3] = {nullptr, nullptr, nullptr};
-  int eps_cur = 0;                 // buffer of the step in flight (set by sample_rollout, read by score_update / peek)
-  uint32_t eps_key[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-  bool eps_valid[3] = {false, false, false};   // d_eps[b] holds normal(eps_key[b])
-  bool eps_on_aux[3] = {false, false, false};  // ... generated on the aux stream: the reader checks ev_noise[b] first
-  int eps_read_seq[3] = {0, 0, 0};             // sequence number of the last rollout launch that read d_eps[b]
-  int* h_progress = nullptr;
-  int seq = 0;
-  bool in_step = false;        // the last sample_rollout found the host in step with the device (a per-step host read)
-  bool wm_mark_valid = false;  // ev_wm was recorded behind the latest weighted mean
-  bool kept_in_step = false;   // plan_keep_in_step held the host back for the coming sample_rollout (the queue is NOT draining)
-  uint32_t hint_key[2] = {0, 0};        // mbd_plan_prefetch_noise: key of the step after the next sample_rollout
-  bool hint_valid = false;
-  float* d_ybar_keep = nullptr;    // [HNu] Ybar_i of the last finished step (mbd_plan_peek materialises Y0s from it)
-  const float* peek_ybar = nullptr;  // the caller's d_Ybar_i between phase 1 and phase 2 of a step, d_ybar_keep after
-  float sigma_last = 0.0f;
-  hipEvent_t ev_noise[3] = {nullptr, nullptr, nullptr}, ev_wm = nullptr;
-  float *d_sigma = nullptr, *d_spread = nullptr;  // path-integral plans
-  int* d_idx = nullptr;
-  // receding-horizon episodes (mbd_plan_run_mpc): the two states its ticks ping-pong between [2][state_size], and the
-  // episode's logs — states [T+1][state_size], means [T][HNu], rewards [T][H-1] (E < H rows per tick) — for up to
-  // mpc_ticks ticks, grown on demand.  Plan-owned, so that nothing an episode leaves behind points at freed memory.
-  float *d_mpc_state = nullptr, *d_mpc_states = nullptr, *d_mpc_means = nullptr, *d_mpc_rewards = nullptr;
-  size_t mpc_ticks = 0;
-  // the plant record of the plan's episodes (mbd_plan_set_mpc_plant; a copy, the plant env is the caller's), and what an
-  // episode with a record needs beyond the above: the log of the executed rows [T][E Nu] — the tick's rollout reads its
-  // slice, so the rows exist once —, the tick's normals [E Nu + 3] and its three kick values
-  mbd_mpc_plant plant_rec{};
-  bool has_plant = false;
-  float *d_mpc_actions = nullptr, *d_plant_eps = nullptr, *d_plant_kick = nullptr;
-  size_t mpc_actions_cap = 0, plant_eps_cap = 0;
-  // the ensemble record (mbd_plan_set_ensemble; a copy, NULL members resolved to the plan's env — the envs are the caller's)
-  // and its buffers: the members' rewards r_m [M][N] and per-step rewards [M][N][H] of the rollout launch over M N
-  // candidates, and the library's own copy of the combined rewards [N] (mbd_plan_peek_ensemble)
-  mbd_ensemble ens_rec{};
-  bool has_ens = false, ens_stepped = false;
-  float *d_ens_rews = nullptr, *d_ens_rewss = nullptr, *d_ens_comb = nullptr;
-  bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  size_t events_used = 0;
-  mbd_plan() = default;
-  mbd_plan(const mbd_plan&) = delete;
-  mbd_plan& operator=(const mbd_plan&) = delete;
-  ~mbd_plan() {  // owns its device buffers, streams and events
-    if (env) (void)hipSetDevice(env->device);
-    if (ev_xs) (void)hipEventDestroy(ev_xs);
-    for (auto& ev : events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    (void)hipFree(d_state0); (void)hipFree(d_Y0s); (void)hipFree(d_rewss); (void)hipFree(d_rews);
-    (void)hipFree(d_lp); (void)hipFree(d_xpos); (void)hipFree(d_weights); (void)hipFree(d_Ybar);
-    (void)hipFree(d_mu); (void)hipFree(d_rewmeans); (void)hipFree(d_scratch);
-    (void)hipFree(d_sigma); (void)hipFree(d_spread); (void)hipFree(d_idx); (void)hipFree(d_wm_partial); (void)hipFree(d_lg);
-    (void)hipFree(d_eps[0]); (void)hipFree(d_eps[1]); (void)hipFree(d_eps[2]); (void)hipFree(d_ybar_keep);
-    (void)hipFree(d_mpc_state); (void)hipFree(d_mpc_states); (void)hipFree(d_mpc_means); (void)hipFree(d_mpc_rewards);
-    (void)hipFree(d_mpc_actions); (void)hipFree(d_plant_eps); (void)hipFree(d_plant_kick);
-    (void)hipFree(d_ens_rews); (void)hipFree(d_ens_rewss); (void)hipFree(d_ens_comb);
-    if (h_progress) (void)hipHostFree(h_progress);
-    for (int b = 0; b < 3; ++b)
-      if (ev_noise[b]) (void)hipEventDestroy(ev_noise[b]);
-    if (ev_wm) (void)hipEventDestroy(ev_wm);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (aux) (void)hipStreamDestroy(aux);
-    if (ev_in) (void)hipEventDestroy(ev_in);
-    if (ev_aux) (void)hipEventDestroy(ev_aux);
-  }
 };
 
 // Lazy candidates of a plan's rollout (RolloutParams): d_us holds normals, actions are formed at the fetch; and the
@@ -202,9 +180,62 @@ struct LazyArgs {
 };
 // the host's view of a progress word (pinned host memory the device stores into)
 static inline int progress_read(const int* h) { return __atomic_load_n(h, __ATOMIC_ACQUIRE); }
+static inline void progress_reset(int* h) { __atomic_store_n(h, 0, __ATOMIC_RELEASE); }  // (between loops, the streams idle)
 // how long a host loop that keeps step with the device through the progress word waits before it falls back to ordering
-// the streams with an event (a slow stream is not an error; steady_clock also counts system pauses)
+// the streams with an event (steady_clock also counts system pauses)
 constexpr int kInStepWaitMs = 20;
+// Waits until the progress word has reached `target`, looking every sleep_us, for limit_ms at the most; whether it has (the
+// last look comes after the limit).  A stream that is legitimately slow (a shared or time-sliced GPU, a profiler, a system
+// pause) is not an error: the caller then orders its streams with an event instead.
+inline bool progress_wait(const int* h, int target, int limit_ms, int sleep_us) {
+  const auto w0 = std::chrono::steady_clock::now();
+  while (progress_read(h) < target && std::chrono::steady_clock::now() - w0 < std::chrono::milliseconds(limit_ms))
+    std::this_thread::sleep_for(std::chrono::microseconds(sleep_us));
+  return progress_read(h) >= target;
+}
+// workgroups (of 256) of a launch that generates `normals` normals grid-stride: a thread makes one, or two of an unpartitioned
+// stream; cap: 65536 for a plan, 4096 per plan of a sweep
+inline unsigned noise_blocks(int prng_impl, uint64_t normals, uint64_t cap) {
+  const uint64_t items = prng_impl == MBD_PRNG_PARTITIONABLE ? normals : (normals + 1) / 2;
+  const uint64_t blocks = (items + 255) / 256;
+  return (unsigned)(blocks < cap ? blocks : cap);
+}
+// The pool of event pairs that time the rollout launches of a plan or a sweep (mbd_*_kernel_time): begin in front of the
+// launch, end behind it, both nothing while the pool is off; pairs are created as they are needed and reused after a reset.
+struct TimingPool {
+  bool on = false;
+  std::vector<std::pair<Event, Event>> pairs;
+  size_t used = 0;
+  int begin(hipStream_t s) {
+    if (!on) return MBD_OK;
+    if (used == pairs.size()) {
+      Event a, b;
+      HIP_TRY(a.create(hipEventDefault));
+      HIP_TRY(b.create(hipEventDefault));
+      pairs.emplace_back(std::move(a), std::move(b));
+    }
+    HIP_TRY(hipEventRecord(pairs[used++].first, s));
+    return MBD_OK;
+  }
+  int end(hipStream_t s) {
+    if (on) HIP_TRY(hipEventRecord(pairs[used - 1].second, s));
+    return MBD_OK;
+  }
+  // the mean over the pairs used since the last reset, once the device is idle
+  int average(float* avg_ms_out, int* count_out, bool reset) {
+    HIP_TRY(hipDeviceSynchronize());
+    double tot = 0.0;
+    for (size_t k = 0; k < used; ++k) {
+      float ms = 0.0f;
+      HIP_TRY(hipEventElapsedTime(&ms, pairs[k].first, pairs[k].second));
+      tot += ms;
+    }
+    if (avg_ms_out) *avg_ms_out = used ? (float)(tot / (double)used) : 0.0f;
+    if (count_out) *count_out = (int)used;
+    if (reset) used = 0;
+    return MBD_OK;
+  }
+};
 // ---- defined in mbd_env.hip ------------------------------------------------------------------------------------------
 // test / A-B levers (one process-wide table, include/mbd_hip_debug.h): -1 = not set
 int lever(const char* name);
@@ -258,3 +289,8 @@ void host_schedule(float beta0, float betaT, int Nd, std::vector<float>& alphas,
                    std::vector<float>& sigmas);
 // the refusals of a plant record (include/mbd_hip.h mbd_mpc_plant) against the env that plans — host arithmetic, no launch
 int check_mpc_plant(const mbd_env* env, const mbd_mpc_plant* rec);
+// the refusals of an episode's configuration that plans and sweeps share (include/mbd_hip.h mbd_mpc_config), in their order
+int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc);
+// One tick of a plant's disturbance chain, dk, d_t = split(dk): advances dk, fills slot k of sp with d_t and the record's
+// deviations — the kick's only in the ticks that end with one — and says whether tick t does
+bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k);

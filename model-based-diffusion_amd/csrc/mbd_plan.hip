@@ -1,8 +1,146 @@
-// mbd_plan.hip — the planner fast path (include/mbd_hip.h): one reverse-diffusion step split at its exchange point
-// (mbd_plan_sample_rollout / mbd_plan_score_update), the noise ring of lazy plans, and the loops over steps
-// (mbd_plan_reverse_once, mbd_plan_run, mbd_plan_eval, mbd_plan_peek; the receding-horizon loop mbd_plan_run_mpc).
-// mbd_planner.py:84-148,179-180.
+// mbd_plan.hip — the planner fast path (include/mbd_hip.h): the plan handle and the noise ring of lazy plans, one
+// reverse-diffusion step split at its exchange point (mbd_plan_sample_rollout / mbd_plan_score_update; the step functions
+// behind them take the rollouts' start state as a parameter), and the loops over steps (mbd_plan_reverse_once, mbd_plan_run,
+// mbd_plan_eval, mbd_plan_peek; the receding-horizon loop mbd_plan_run_mpc).  mbd_planner.py:84-148,179-180.
 #include "mbd_internal.h"
+
+// LAZY plans (the MBD update on a rigid-body env): the candidates are never materialised.  eps[b] holds the normals
+// [N][HNu] of a diffusion step; the rollout's action fetch and the weighted mean form clip(eps sigma_i + Ybar_i)
+// on the fly (RolloutParams).  A ring of buffers: while step k reads one, the normals of step k+1 (they depend on that
+// step's key only) are generated into the next — by spare workgroups of step k's rollout launch, or on the aux
+// stream when that launch fills the chip (mbd_plan_prefetch_noise declares the key).  THREE buffers, so that the aux
+// stream needs no event from the step's stream while the caller keeps in step with the device: the buffer step k+1's
+// normals go into was last read by step k-2's weighted mean, which has finished once the rollout of step k-1 has
+// STARTED — every rollout launch of the plan stores its sequence number into the progress word (pinned host memory) as it
+// starts, and the host looks there.  A caller that runs ahead of the device (mbd_plan_run's loop, the async leg of the
+// bench) gets the event-ordered form: a mark on the step's stream in front of the rollout, a wait on the aux stream.
+// (Other launches between two steps on the step's stream — a receding-horizon episode's two per tick — change neither
+// argument: they are stream-ordered behind the weighted mean and in front of the next rollout.)
+struct NoiseRing {
+  Event ev_noise[3], ev_wm;  // created with the plan's second stream (ensure_aux): a plan without one carries no event
+  DevBuf<float> eps[3];
+  int cur = 0;                             // buffer of the step in flight (set by sample_rollout, read by score_update / peek)
+  uint32_t key[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+  bool valid[3] = {false, false, false};   // eps[b] holds normal(key[b])
+  bool on_aux[3] = {false, false, false};  // ... generated on the aux stream: the reader checks ev_noise[b] first
+  int read_seq[3] = {0, 0, 0};             // sequence number of the last rollout launch that read eps[b]
+  PinnedWord progress;
+  int seq = 0;
+  bool in_step = false;        // the last sample_rollout found the host in step with the device (a per-step host read)
+  bool wm_mark_valid = false;  // ev_wm was recorded behind the latest weighted mean
+  bool kept_in_step = false;   // plan_keep_in_step held the host back for the coming sample_rollout (the queue is NOT draining)
+  uint32_t hint_key[2] = {0, 0};  // mbd_plan_prefetch_noise: key of the step after the next sample_rollout
+  bool hint_valid = false;
+
+  // the buffer that holds normal(k), or -1
+  int find(const uint32_t k[2]) const {
+    int at = -1;
+    for (int b = 0; b < 3; ++b)
+      if (valid[b] && key[b][0] == k[0] && key[b][1] == k[1]) at = b;
+    return at;
+  }
+  void holds(int b, const uint32_t k[2]) {
+    key[b][0] = k[0]; key[b][1] = k[1];
+    valid[b] = true;
+  }
+  // the reader (or the next writer) of a buffer the aux stream filled: no wait on the step's stream when the job has
+  // already finished
+  int join(int b, hipStream_t s) {
+    if (!on_aux[b]) return MBD_OK;
+    on_aux[b] = false;
+    if (hipEventQuery(ev_noise[b]) == hipSuccess) return MBD_OK;
+    (void)hipGetLastError();  // (hipErrorNotReady is not an error here)
+    HIP_TRY(hipStreamWaitEvent(s, ev_noise[b], 0));
+    return MBD_OK;
+  }
+  // takes the declared key: whether there is one that is not this step's own
+  bool take_hint(const uint32_t step_key[2], uint32_t out[2]) {
+    const bool have = hint_valid && !(hint_key[0] == step_key[0] && hint_key[1] == step_key[1]);
+    hint_valid = false;
+    out[0] = hint_key[0]; out[1] = hint_key[1];
+    return have;
+  }
+  // Aux-stream generation into eps[b] must start after the last reader of eps[b] — the weighted mean behind rollout launch
+  // number read_seq[b] — and should not wait for the rollout about to be launched on s.  That reader has finished once the
+  // NEXT rollout launch of the plan has started (the progress word); a host that has not seen that yet puts a mark onto s,
+  // in front of the coming launch, for the aux stream to wait on (*marked)
+  int mark_last_reader(int b, hipStream_t s, bool* marked) {
+    const int r = read_seq[b];
+    in_step = (r == 0 || progress_read(progress) >= r + 1) && !kept_in_step;
+    kept_in_step = false;
+    *marked = false;
+    // the caller runs ahead of the device (an asynchronous loop): it is held here until the rollout before this one has
+    // started — the queue still holds that rollout and its score, so the device does not wait for the host — rather
+    // than paying a record on s and a wait on the aux stream per step (~20 us at N = 8192).  Bounded: a stream that is
+    // itself waiting for something the caller has yet to do gets the mark after 5 ms.
+    if (r != 0 && progress_read(progress) < r + 1) *marked = !progress_wait(progress, r + 1, 5, 10);
+    if (*marked) HIP_TRY(hipEventRecord(ev_wm, s));
+    return MBD_OK;
+  }
+  // ... and the aux stream's side of it, in front of the job.  (A caller in step with the device — it reads every step's
+  // mean reward before it dispatches the next — launches the job while the previous step's weighted mean is still running:
+  // the job waits for the mark behind that kernel, which cost nothing there (the queue was about to drain), instead of
+  // competing with it for the memory system)
+  int aux_waits_for_mark(hipStream_t aux, bool marked) {
+    if (marked || (in_step && wm_mark_valid)) HIP_TRY(hipStreamWaitEvent(aux, ev_wm, 0));
+    return MBD_OK;
+  }
+  // behind a weighted mean on s: the mark, only where the record is free (see aux_waits_for_mark)
+  int mark_wmean(hipStream_t s, bool has_aux) {
+    wm_mark_valid = false;
+    if (has_aux && in_step && ev_wm) {
+      HIP_TRY(hipEventRecord(ev_wm, s));
+      wm_mark_valid = true;
+    }
+    return MBD_OK;
+  }
+};
+
+struct mbd_plan {
+  mbd_env* env = nullptr;
+  hipStream_t last_stream = nullptr;  // stream of the plan's previous phase call (plan_enter orders a change of stream)
+  bool last_stream_set = false;
+  mbd_plan_config cfg;
+  int HNu = 0;
+  std::vector<float> alphas, alphas_bar, sigmas;
+  Stream stream;
+  // second stream: the non-lazy sharded sampler's other-rank rows, and the next step's normals of lazy plans whose
+  // rollout fills the chip (smaller rollouts generate them in spare workgroups of their own launch).  Created on first use
+  // (ensure_aux), with its events: a second stream per plan costs hardware queues beside other plans
+  Stream aux;
+  Event ev_xs, ev_in, ev_aux;
+  bool aux_pending = false;
+  DevBuf<float> d_state0, d_Y0s, d_rewss, d_rews, d_lp, d_xpos, d_weights, d_Ybar, d_mu, d_rewmeans, d_scratch;
+  DevBuf<float> d_wm_partial;  // [64][HNu] partials of the split weighted mean (plans of >= 4096 candidates)
+  DevBuf<float> d_lg;          // [N] logp0 scratch of the score kernel for plans beyond kLdsN candidates
+  bool lazy = false;
+  NoiseRing ring;
+  DevBuf<float> d_ybar_keep;         // [HNu] Ybar_i of the last finished step (mbd_plan_peek materialises Y0s from it)
+  const float* peek_ybar = nullptr;  // the caller's d_Ybar_i between phase 1 and phase 2 of a step, d_ybar_keep after
+  float sigma_last = 0.0f;
+  DevBuf<float> d_sigma, d_spread;  // path-integral plans
+  DevBuf<int> d_idx;
+  // receding-horizon episodes (mbd_plan_run_mpc): the two states its ticks ping-pong between [2][state_size], and the
+  // episode's logs — states [T+1][state_size], means [T][HNu], rewards [T][H-1] (E < H rows per tick) — grown on demand.
+  // Plan-owned, so that nothing an episode leaves behind points at freed memory.
+  DevBuf<float> d_mpc_state, d_mpc_states, d_mpc_means, d_mpc_rewards;
+  // the plant record of the plan's episodes (mbd_plan_set_mpc_plant; a copy, the plant env is the caller's), and what an
+  // episode with a record needs beyond the above: the log of the executed rows [T][E Nu] — the tick's rollout reads its
+  // slice, so the rows exist once —, the tick's normals [E Nu + 3] and its three kick values
+  mbd_mpc_plant plant_rec{};
+  bool has_plant = false;
+  DevBuf<float> d_mpc_actions, d_plant_eps, d_plant_kick;
+  // the ensemble record (mbd_plan_set_ensemble; a copy, NULL members resolved to the plan's env — the envs are the caller's)
+  // and its buffers: the members' rewards r_m [M][N] and per-step rewards [M][N][H] of the rollout launch over M N
+  // candidates, and the library's own copy of the combined rewards [N] (mbd_plan_peek_ensemble)
+  mbd_ensemble ens_rec{};
+  bool has_ens = false, ens_stepped = false;
+  DevBuf<float> d_ens_rews, d_ens_rewss, d_ens_comb;
+  TimingPool timing;
+  ~mbd_plan() {  // (streams, events and buffers release themselves, on the env's device)
+    if (env) (void)hipSetDevice(env->device);
+  }
+};
 
 // ==================================================================================================
 // planner
@@ -48,37 +186,34 @@ extern "C" int mbd_plan_create(mbd_env* env, const mbd_plan_config* cfg, mbd_pla
   const int N = cfg->Nsample, H = cfg->Hsample, Nu = env->action_size(), Nd = cfg->Ndiffuse, sh = cfg->shard_count;
   p->HNu = H * Nu;
   host_schedule(cfg->beta0, cfg->betaT, Nd, p->alphas, p->alphas_bar, p->sigmas);
-  HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  HIP_TRY(p->stream.create());
   const int K = env->kind == ENV_CAR2D ? 1 : (env->model.n_track > 0 ? env->model.n_track : 1);
-  HIP_TRY(hipMalloc(&p->d_state0, sizeof(float) * env->state_size()));
-  HIP_TRY(hipMalloc(&p->d_Y0s, sizeof(float) * (size_t)N * p->HNu));
-  HIP_TRY(hipMalloc(&p->d_rewss, sizeof(float) * (size_t)sh * H));
-  HIP_TRY(hipMalloc(&p->d_rews, sizeof(float) * (size_t)N));
-  HIP_TRY(hipMalloc(&p->d_lp, sizeof(float) * (size_t)N));
-  if (cfg->enable_demo) HIP_TRY(hipMalloc(&p->d_xpos, sizeof(float) * (size_t)sh * H * K * 3));
-  HIP_TRY(hipMalloc(&p->d_weights, sizeof(float) * (size_t)N));
-  HIP_TRY(hipMalloc(&p->d_Ybar, sizeof(float) * (size_t)p->HNu * 2));
-  HIP_TRY(hipMalloc(&p->d_mu, sizeof(float) * (size_t)(Nd - 1) * p->HNu));
-  HIP_TRY(hipMalloc(&p->d_rewmeans, sizeof(float) * (size_t)Nd));
-  HIP_TRY(hipMalloc(&p->d_scratch, sizeof(float) * (size_t)(H + 8)));
-  HIP_TRY(hipMalloc(&p->d_wm_partial, sizeof(float) * (size_t)kWmG * p->HNu));
-  if (N > kLdsN) HIP_TRY(hipMalloc(&p->d_lg, sizeof(float) * (size_t)N));
+  HIP_TRY(p->d_state0.alloc(env->state_size()));
+  HIP_TRY(p->d_Y0s.alloc((size_t)N * p->HNu));
+  HIP_TRY(p->d_rewss.alloc((size_t)sh * H));
+  HIP_TRY(p->d_rews.alloc(N));
+  HIP_TRY(p->d_lp.alloc(N));
+  if (cfg->enable_demo) HIP_TRY(p->d_xpos.alloc((size_t)sh * H * K * 3));
+  HIP_TRY(p->d_weights.alloc(N));
+  HIP_TRY(p->d_Ybar.alloc((size_t)p->HNu * 2));
+  HIP_TRY(p->d_mu.alloc((size_t)(Nd - 1) * p->HNu));
+  HIP_TRY(p->d_rewmeans.alloc(Nd));
+  HIP_TRY(p->d_scratch.alloc((size_t)H + 8));
+  HIP_TRY(p->d_wm_partial.alloc((size_t)kWmG * p->HNu));
+  if (N > kLdsN) HIP_TRY(p->d_lg.alloc(N));
   // lazy candidates: the MBD update on a rigid-body env (the path-integral updates and car2d keep the materialised
   // Y0s: their kernels read it, and car2d's sampler is a few microseconds).  MBD_NO_LAZY=1: the materialised path (A/B)
   const bool no_lazy = env_flag("MBD_NO_LAZY");
   p->lazy = cfg->update_method == 0 && env->kind == ENV_MODEL && !no_lazy;
   if (p->lazy) {
-    HIP_TRY(hipMalloc(&p->d_eps[0], sizeof(float) * (size_t)N * p->HNu));
-    HIP_TRY(hipMalloc(&p->d_eps[1], sizeof(float) * (size_t)N * p->HNu));
-    HIP_TRY(hipMalloc(&p->d_eps[2], sizeof(float) * (size_t)N * p->HNu));
-    HIP_TRY(hipHostMalloc((void**)&p->h_progress, sizeof(int), hipHostMallocDefault));
-    *p->h_progress = 0;
-    HIP_TRY(hipMalloc(&p->d_ybar_keep, sizeof(float) * (size_t)p->HNu));
+    for (int b = 0; b < 3; ++b) HIP_TRY(p->ring.eps[b].alloc((size_t)N * p->HNu));
+    HIP_TRY(p->ring.progress.create());
+    HIP_TRY(p->d_ybar_keep.alloc(p->HNu));
   }
   if (cfg->update_method > 0) {
-    HIP_TRY(hipMalloc(&p->d_sigma, sizeof(float)));
-    HIP_TRY(hipMalloc(&p->d_spread, sizeof(float) * (size_t)p->HNu));
-    HIP_TRY(hipMalloc(&p->d_idx, sizeof(int) * 16));
+    HIP_TRY(p->d_sigma.alloc(1));
+    HIP_TRY(p->d_spread.alloc(p->HNu));
+    HIP_TRY(p->d_idx.alloc(16));
     const float one = 1.0f;  // path_integral.py:131
     HIP_TRY(hipMemcpy(p->d_sigma, &one, sizeof(float), hipMemcpyHostToDevice));
   }
@@ -120,22 +255,18 @@ static RolloutChoice plan_rollout_choice(const mbd_plan* p) {
 
 static int ensure_aux(mbd_plan* p) {
   if (p->aux) return MBD_OK;
-  HIP_TRY(hipStreamCreateWithFlags(&p->aux, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&p->ev_in, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&p->ev_aux, hipEventDisableTiming));
-  for (int b = 0; b < 3; ++b) HIP_TRY(hipEventCreateWithFlags(&p->ev_noise[b], hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&p->ev_wm, hipEventDisableTiming));
+  HIP_TRY(p->aux.create());
+  HIP_TRY(p->ev_in.create());
+  HIP_TRY(p->ev_aux.create());
+  for (int b = 0; b < 3; ++b) HIP_TRY(p->ring.ev_noise[b].create());
+  HIP_TRY(p->ring.ev_wm.create());
   return MBD_OK;
 }
 
 static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], float* out) {
   const mbd_plan_config& c = p->cfg;
-  const uint64_t total = (uint64_t)c.Nsample * p->HNu;
-  const uint64_t items = c.prng_impl == MBD_PRNG_PARTITIONABLE ? total : (total + 1) / 2;
-  uint64_t blocks = (items + 255) / 256;
-  if (blocks > 65536) blocks = 65536;  // (grid-stride)
-  hipLaunchKernelGGL(noise_kernel, dim3((unsigned)blocks), dim3(256), 0, st, key[0], key[1], c.prng_impl, c.Nsample,
-                     p->HNu, out);
+  const unsigned blocks = noise_blocks(c.prng_impl, (uint64_t)c.Nsample * p->HNu, 65536);
+  hipLaunchKernelGGL(noise_kernel, dim3(blocks), dim3(256), 0, st, key[0], key[1], c.prng_impl, c.Nsample, p->HNu, out);
 }
 
 // The normals of a diffusion step depend on its key only, not on the previous step's result.  This call DECLARES the
@@ -149,9 +280,9 @@ extern "C" int mbd_plan_prefetch_noise(mbd_plan* p, const uint32_t key_next[2], 
   if (!p || !key_next) return fail(MBD_ERR_INVALID, "NULL argument");
   const bool off = env_flag("MBD_NO_PREFETCH");
   if (off || !p->lazy) return MBD_OK;
-  p->hint_key[0] = key_next[0];
-  p->hint_key[1] = key_next[1];
-  p->hint_valid = true;
+  p->ring.hint_key[0] = key_next[0];
+  p->ring.hint_key[1] = key_next[1];
+  p->ring.hint_valid = true;
   return MBD_OK;
 }
 
@@ -160,7 +291,7 @@ extern "C" int mbd_plan_prefetch_noise(mbd_plan* p, const uint32_t key_next[2], 
 // arrives on another stream it is ordered behind the previous call with an event.
 static int plan_enter(mbd_plan* p, hipStream_t s) {
   if (p->last_stream_set && p->last_stream != s) {
-    if (!p->ev_xs) HIP_TRY(hipEventCreateWithFlags(&p->ev_xs, hipEventDisableTiming));
+    if (!p->ev_xs) HIP_TRY(p->ev_xs.create());
     HIP_TRY(hipEventRecord(p->ev_xs, p->last_stream));
     HIP_TRY(hipStreamWaitEvent(s, p->ev_xs, 0));
   }
@@ -169,205 +300,171 @@ static int plan_enter(mbd_plan* p, hipStream_t s) {
   return MBD_OK;
 }
 
-extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
-                                       float* d_rews_local, float* d_logpd_local, void* stream_) {
+// Step 1 of phase 1, lazy: every rank holds the normals of ALL N candidates (counter-based noise), so that phase 2 needs no
+// second collective and is bit-identical for every shard layout; the candidates themselves are formed at the rollout's
+// action fetch and inside the weighted mean.  The step's normals: ring.cur afterwards.
+static int obtain_normals(mbd_plan* p, const uint32_t key_sample[2], hipStream_t s) {
+  NoiseRing& ring = p->ring;
+  int cur = ring.find(key_sample);
+  if (cur >= 0) {  // prepared behind the previous rollout
+    MBD_TRY(ring.join(cur, s));
+  } else {  // not prepared: generate now, into the buffer behind the previous step's (stream order protects it)
+    cur = (ring.cur + 1) % 3;
+    MBD_TRY(ring.join(cur, s));  // (a stale prefetch may still be writing it)
+    launch_noise(p, s, key_sample, ring.eps[cur]);
+    HIP_TRY(hipGetLastError());
+    ring.holds(cur, key_sample);
+  }
+  ring.cur = cur;
+  return MBD_OK;
+}
+
+// Step 1, materialised (car2d, path-integral updates): every rank samples ALL N candidate sequences.  A sharded plan
+// samples its own rows first and the others' on a second stream, behind the rollout; mbd_plan_score_update joins
+// that stream before it reads them.
+static int sample_candidates(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i, hipStream_t s) {
+  const mbd_plan_config& c = p->cfg;
+  const int N = c.Nsample, HNu = p->HNu;
+  const uint64_t total = (uint64_t)N * HNu;
+  auto sample = [&](hipStream_t st, uint64_t e0, uint64_t cnt) {
+    if (cnt == 0) return;
+    const bool pair_blocks = c.prng_impl != MBD_PRNG_PARTITIONABLE && e0 == 0 && cnt == total;
+    const uint64_t threads = pair_blocks ? (total + 1) / 2 : cnt;
+    hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, key_sample[0],
+                       key_sample[1], c.prng_impl, N, HNu, (unsigned long long)e0, (unsigned long long)cnt,
+                       p->sigmas[i], c.update_method > 0 ? (const float*)p->d_sigma : (const float*)nullptr,
+                       d_Ybar_i, p->d_Y0s);
+  };
+  const uint64_t own0 = (uint64_t)c.shard_begin * HNu, own1 = own0 + (uint64_t)c.shard_count * HNu;
+  const bool no_aux = env_flag("MBD_NO_AUX");
+  if (c.shard_count == N || no_aux || (long long)N < 5LL * c.shard_count) {
+    // worth the two events only when the other ranks' rows dominate (tools/gpu_rank_emu.sh: 8 shards 0.774 ->
+    // 0.762 ms per step, 2 shards 0.736 -> 0.742); MBD_NO_AUX=1 keeps everything on the caller's stream (A/B)
+    sample(s, 0, total);
+  } else {
+    MBD_TRY(ensure_aux(p));
+    HIP_TRY(hipEventRecord(p->ev_in, s));  // Ybar_i is final and the previous step is done with Y0s
+    HIP_TRY(hipStreamWaitEvent(p->aux, p->ev_in, 0));
+    sample(s, own0, own1 - own0);
+    sample(p->aux, 0, own0);
+    sample(p->aux, own1, total - own1);
+    HIP_TRY(hipEventRecord(p->ev_aux, p->aux));
+    p->aux_pending = true;
+  }
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+
+// Step 2, lazy: whether the coming rollout launch carries a noise job for the NEXT step — lz.nz_*, nz_out null: none — and
+// the job's buffer, the one behind ring.cur, made ready for it; *marked: see NoiseRing::mark_last_reader.
+static int prepare_noise_job(mbd_plan* p, const uint32_t key_sample[2], hipStream_t s, LazyArgs& lz, bool* marked) {
+  const mbd_plan_config& c = p->cfg;
+  NoiseRing& ring = p->ring;
+  const int nxt = (ring.cur + 1) % 3;
+  // Preparing the next step's normals ahead only pays for a plan that has the device to itself (the caller says so:
+  // mbd_plan_config.shares_device): beside other plans
+  // (seed / temperature sweeps as concurrent plans, scripts/run_mbd.py) the noise workgroups would hold — through
+  // the launch's LDS reservation — the CUs the other plans' rollouts need, and a second stream per plan runs the
+  // process out of hardware queues (four N=1024 plans: 3100 plan-steps/s either way against 6200 with the normals
+  // generated in front of each rollout, where the other plans' rollouts hide them anyway).
+  const bool alone = c.shares_device == 0;
+  uint32_t declared[2];
+  const bool want = ring.take_hint(key_sample, declared) && alone;
+  if (!want) return MBD_OK;
+  // eps[nxt] was last read two steps ago
+  MBD_TRY(ring.join(nxt, s));  // (a stale prefetch of another key: let it finish before it is overwritten)
+  ring.valid[nxt] = false;
+  lz.nz_out = ring.eps[nxt];
+  lz.nz_key[0] = declared[0]; lz.nz_key[1] = declared[1];
+  lz.nz_impl = c.prng_impl; lz.nz_N = c.Nsample; lz.nz_HNu = p->HNu;
+  // (launches that take the job into spare workgroups need no second stream and none of its events: a record
+  // behind every weighted mean idles the queue ~5.5 us, 1 % of a step — profiles/r02_timeline.txt)
+  // (asked of the launch's own decision: a one-workgroup shard of a large plan pins its rollout and still cannot take
+  // the job — its normals then need the second stream's ordering like a full-chip launch's)
+  if (rollout_takes_noise(plan_rollout_choice(p), c.prng_impl, c.Nsample, p->HNu)) return MBD_OK;
+  MBD_TRY(ensure_aux(p));
+  return ring.mark_last_reader(nxt, s, marked);
+}
+
+// Step 4, lazy: the job behind the launch.  One the launch did not take (the rollout fills the chip) runs on the second
+// stream, beside the rollout; either way eps[nxt] holds the declared step's normals from here on.
+static int finish_noise_job(mbd_plan* p, const LazyArgs& lz, bool marked) {
+  if (!lz.nz_out) return MBD_OK;
+  NoiseRing& ring = p->ring;
+  const int nxt = (ring.cur + 1) % 3;
+  if (!lz.nz_fused) {
+    MBD_TRY(ensure_aux(p));
+    MBD_TRY(ring.aux_waits_for_mark(p->aux, marked));
+    launch_noise(p, p->aux, lz.nz_key, lz.nz_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ring.ev_noise[nxt], p->aux));
+    ring.on_aux[nxt] = true;
+  }
+  ring.holds(nxt, lz.nz_key);
+  return MBD_OK;
+}
+
+// phase 1 of a step, from d_state0: the plan's own start state (mbd_plan_sample_rollout), or an episode's executed state
+static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i, float* d_rews_local,
+                               float* d_logpd_local, hipStream_t s, const float* d_state0) {
   if (!p || !key_sample || !d_Ybar_i || !d_rews_local) return fail(MBD_ERR_INVALID, "NULL argument");
   const mbd_plan_config& c = p->cfg;
   if (i < 1 || i >= c.Ndiffuse) return fail(MBD_ERR_INVALID, "diffusion index %d outside [1,%d)", i, c.Ndiffuse);
   if (c.enable_demo && !d_logpd_local) return fail(MBD_ERR_INVALID, "enable_demo needs d_logpd_local");
   mbd_env* e = p->env;
   HIP_TRY(hipSetDevice(e->device));
-  hipStream_t s = (hipStream_t)stream_;
-  {
-    int rc = plan_enter(p, s);
-    if (rc != MBD_OK) return rc;
-  }
+  MBD_TRY(plan_enter(p, s));
   const int N = c.Nsample, H = c.Hsample, HNu = p->HNu;
+  NoiseRing& ring = p->ring;
   LazyArgs lz;
-  bool noise_on_aux = false;
-  int nxt = 0;
+  bool marked = false;
+  // A1: this step's normals, then the next step's noise job; or this step's candidates
   if (p->lazy) {
-    // A1, lazy: every rank holds the normals of ALL N candidates (counter-based noise), so that phase 2 needs no
-    // second collective and is bit-identical for every shard layout; the candidates themselves are formed at the
-    // rollout's action fetch and inside the weighted mean.
-    // the reader of a buffer the aux stream filled: no wait on the step's stream when the job has already finished
-    auto join_aux = [&](int b) -> int {
-      if (!p->eps_on_aux[b]) return MBD_OK;
-      p->eps_on_aux[b] = false;
-      if (hipEventQuery(p->ev_noise[b]) == hipSuccess) return MBD_OK;
-      (void)hipGetLastError();  // (hipErrorNotReady is not an error here)
-      HIP_TRY(hipStreamWaitEvent(s, p->ev_noise[b], 0));
-      return MBD_OK;
-    };
-    int cur = -1;
-    for (int b = 0; b < 3; ++b)
-      if (p->eps_valid[b] && p->eps_key[b][0] == key_sample[0] && p->eps_key[b][1] == key_sample[1]) cur = b;
-    if (cur >= 0) {  // prepared behind the previous rollout
-      int rc = join_aux(cur);
-      if (rc != MBD_OK) return rc;
-    } else {  // not prepared: generate now, into the buffer behind the previous step's (stream order protects it)
-      cur = (p->eps_cur + 1) % 3;
-      int rc = join_aux(cur);  // (a stale prefetch may still be writing it)
-      if (rc != MBD_OK) return rc;
-      launch_noise(p, s, key_sample, p->d_eps[cur]);
-      HIP_TRY(hipGetLastError());
-      p->eps_key[cur][0] = key_sample[0];
-      p->eps_key[cur][1] = key_sample[1];
-      p->eps_valid[cur] = true;
-    }
-    p->eps_cur = cur;
+    MBD_TRY(obtain_normals(p, key_sample, s));
     p->peek_ybar = d_Ybar_i;  // (the caller keeps it unchanged until phase 2 has run)
     p->sigma_last = p->sigmas[i];
     lz.ybar = d_Ybar_i;
     lz.sigma = p->sigmas[i];
-    nxt = (cur + 1) % 3;
-    // Preparing the next step's normals ahead only pays for a plan that has the device to itself (the caller says so:
-    // mbd_plan_config.shares_device): beside other plans
-    // (seed / temperature sweeps as concurrent plans, scripts/run_mbd.py) the noise workgroups would hold — through
-    // the launch's LDS reservation — the CUs the other plans' rollouts need, and a second stream per plan runs the
-    // process out of hardware queues (four N=1024 plans: 3100 plan-steps/s either way against 6200 with the normals
-    // generated in front of each rollout, where the other plans' rollouts hide them anyway).
-    const bool alone = c.shares_device == 0;
-    const bool want = alone && p->hint_valid &&
-                      !(p->hint_key[0] == key_sample[0] && p->hint_key[1] == key_sample[1]);
-    p->hint_valid = false;
-    if (want) {
-      // d_eps[nxt] was last read two steps ago
-      {
-        int rc = join_aux(nxt);  // (a stale prefetch of another key: let it finish before it is overwritten)
-        if (rc != MBD_OK) return rc;
-      }
-      p->eps_valid[nxt] = false;
-      lz.nz_out = p->d_eps[nxt];
-      lz.nz_key[0] = p->hint_key[0]; lz.nz_key[1] = p->hint_key[1];
-      lz.nz_impl = c.prng_impl; lz.nz_N = N; lz.nz_HNu = HNu;
-      // (launches that take the job into spare workgroups need no second stream and none of its events: a record
-      // behind every weighted mean idles the queue ~5.5 us, 1 % of a step — profiles/r02_timeline.txt)
-      // (asked of the launch's own decision: a one-workgroup shard of a large plan pins its rollout and still cannot take
-      // the job — its normals then need the second stream's ordering like a full-chip launch's)
-      noise_on_aux = !rollout_takes_noise(plan_rollout_choice(p), c.prng_impl, N, HNu);
-    }
+    MBD_TRY(prepare_noise_job(p, key_sample, s, lz, &marked));
   } else {
-    // A1, materialised (car2d, path-integral updates): every rank samples ALL N candidate sequences.  A sharded plan
-    // samples its own rows first and the others' on a second stream, behind the rollout; mbd_plan_score_update joins
-    // that stream before it reads them.
-    auto sample = [&](hipStream_t st, uint64_t e0, uint64_t cnt) {
-      if (cnt == 0) return;
-      const uint64_t size = (uint64_t)N * HNu;
-      const bool pair_blocks = c.prng_impl != MBD_PRNG_PARTITIONABLE && e0 == 0 && cnt == size;
-      const uint64_t threads = pair_blocks ? (size + 1) / 2 : cnt;
-      hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, key_sample[0],
-                         key_sample[1], c.prng_impl, N, HNu, (unsigned long long)e0, (unsigned long long)cnt,
-                         p->sigmas[i], c.update_method > 0 ? (const float*)p->d_sigma : (const float*)nullptr,
-                         d_Ybar_i, p->d_Y0s);
-    };
-    const uint64_t own0 = (uint64_t)c.shard_begin * HNu, own1 = own0 + (uint64_t)c.shard_count * HNu;
-    const bool no_aux = env_flag("MBD_NO_AUX");
-    const uint64_t total = (uint64_t)N * HNu;
-    if (c.shard_count == N || no_aux || (long long)N < 5LL * c.shard_count) {
-      // worth the two events only when the other ranks' rows dominate (tools/gpu_rank_emu.sh: 8 shards 0.774 ->
-      // 0.762 ms per step, 2 shards 0.736 -> 0.742); MBD_NO_AUX=1 keeps everything on the caller's stream (A/B)
-      sample(s, 0, total);
-    } else {
-      int rc = ensure_aux(p);
-      if (rc != MBD_OK) return rc;
-      HIP_TRY(hipEventRecord(p->ev_in, s));  // Ybar_i is final and the previous step is done with Y0s
-      HIP_TRY(hipStreamWaitEvent(p->aux, p->ev_in, 0));
-      sample(s, own0, own1 - own0);
-      sample(p->aux, 0, own0);
-      sample(p->aux, own1, total - own1);
-      HIP_TRY(hipEventRecord(p->ev_aux, p->aux));
-      p->aux_pending = true;
-    }
-    HIP_TRY(hipGetLastError());
-  }
-  bool aux_needs_mark = false;
-  if (noise_on_aux) {
-    // aux-stream generation must start after the last reader of d_eps[nxt] — the weighted mean behind rollout launch
-    // number eps_read_seq[nxt] — and should not wait for THIS rollout.  That reader has finished once the NEXT rollout
-    // launch of the plan has started (the progress word); a host that has not seen that yet puts a mark onto s in front
-    // of this launch for the aux stream to wait on
-    int rc = ensure_aux(p);
-    if (rc != MBD_OK) return rc;
-    const int r = p->eps_read_seq[nxt];
-    p->in_step = (r == 0 || progress_read(p->h_progress) >= r + 1) && !p->kept_in_step;
-    p->kept_in_step = false;
-    if (r != 0 && progress_read(p->h_progress) < r + 1) {
-      // the caller runs ahead of the device (an asynchronous loop): it is held here until the rollout before this one has
-      // started — the queue still holds that rollout and its score, so the device does not wait for the host — rather
-      // than paying a record on s and a wait on the aux stream per step (~20 us at N = 8192).  Bounded: a stream that is
-      // itself waiting for something the caller has yet to do gets the mark after 5 ms.
-      const auto w0 = std::chrono::steady_clock::now();
-      while (progress_read(p->h_progress) < r + 1 && std::chrono::steady_clock::now() - w0 < std::chrono::milliseconds(5))
-        std::this_thread::sleep_for(std::chrono::microseconds(10));
-      aux_needs_mark = progress_read(p->h_progress) < r + 1;
-    }
-    if (aux_needs_mark) HIP_TRY(hipEventRecord(p->ev_wm, s));
+    MBD_TRY(sample_candidates(p, i, key_sample, d_Ybar_i, s));
   }
   // A2/A3: rollout of the local shard
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (p->timing) {
-    if (p->events_used == p->events.size()) {
-      hipEvent_t a, b;
-      HIP_TRY(hipEventCreate(&a));
-      HIP_TRY(hipEventCreate(&b));
-      p->events.emplace_back(a, b);
-    }
-    ev0 = p->events[p->events_used].first;
-    ev1 = p->events[p->events_used].second;
-    p->events_used++;
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
-  const float* d_cand = p->lazy ? p->d_eps[p->eps_cur] : p->d_Y0s;
+  MBD_TRY(p->timing.begin(s));
+  const float* d_cand = p->lazy ? ring.eps[ring.cur] : p->d_Y0s;
   if (p->lazy) {
-    lz.progress = p->h_progress;
-    lz.progress_val = ++p->seq;
-    p->eps_read_seq[p->eps_cur] = p->seq;
+    lz.progress = ring.progress;
+    lz.progress_val = ++ring.seq;
+    ring.read_seq[ring.cur] = ring.seq;
   }
   // A5: the demo log-densities of the local shard come out of the rollout itself where its instantiation accumulates them
   // (round 6: no [shard][H][K][3] round trip, no second launch); otherwise from the tracked positions, below
   const bool fused_lp = c.enable_demo && rollout_choice(e, c.shard_count, H).fuses_logpd;
-  int rc;
   if (p->has_ens) {
     // the ensemble (include/mbd_hip.h mbd_ensemble): the N candidates on every member, then the members' rewards combined
     // into the caller's buffer — phase 2 is handed those and is unchanged.  (unsharded, no demo: the set call's refusals)
     const EnsArgs ea{p->ens_rec.n_members, p->ens_rec.members};
-    rc = launch_rollout(e, p->d_state0, d_cand, N, H, p->d_ens_rewss, p->d_ens_rews, nullptr, nullptr, s,
-                        p->lazy ? &lz : nullptr, nullptr, nullptr, &ea);
-    if (rc != MBD_OK) return rc;
+    MBD_TRY(launch_rollout(e, d_state0, d_cand, N, H, p->d_ens_rewss, p->d_ens_rews, nullptr, nullptr, s,
+                           p->lazy ? &lz : nullptr, nullptr, nullptr, &ea));
     hipLaunchKernelGGL(ensemble_reduce_kernel, dim3((N + 255) / 256), dim3(256), 0, s, (const float*)p->d_ens_rews,
                        p->ens_rec.n_members, N, p->ens_rec.risk, d_rews_local, p->d_ens_comb);
     HIP_TRY(hipGetLastError());
     p->ens_stepped = true;
   } else {
-    rc = launch_rollout(e, p->d_state0, d_cand + (size_t)c.shard_begin * HNu, c.shard_count, H, p->d_rewss,
-                        d_rews_local, (c.enable_demo && !fused_lp) ? p->d_xpos : nullptr, nullptr, s, p->lazy ? &lz : nullptr,
-                        nullptr, fused_lp ? d_logpd_local : nullptr);
-    if (rc != MBD_OK) return rc;
+    MBD_TRY(launch_rollout(e, d_state0, d_cand + (size_t)c.shard_begin * HNu, c.shard_count, H, p->d_rewss, d_rews_local,
+                           (c.enable_demo && !fused_lp) ? p->d_xpos.get() : nullptr, nullptr, s, p->lazy ? &lz : nullptr,
+                           nullptr, fused_lp ? d_logpd_local : nullptr));
   }
-  if (p->timing) HIP_TRY(hipEventRecord(ev1, s));
-  if (lz.nz_out) {
-    if (!lz.nz_fused) {  // the rollout fills the chip: the next step's normals on the second stream, beside it
-      rc = ensure_aux(p);
-      if (rc != MBD_OK) return rc;
-      // (a caller in step with the device — it reads every step's mean reward before it dispatches the next — launches
-      // this while the previous step's weighted mean is still running: the job waits for the mark behind that kernel,
-      // which cost nothing there (the queue was about to drain), instead of competing with it for the memory system)
-      if (aux_needs_mark || (p->in_step && p->wm_mark_valid)) HIP_TRY(hipStreamWaitEvent(p->aux, p->ev_wm, 0));
-      launch_noise(p, p->aux, lz.nz_key, lz.nz_out);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(p->ev_noise[nxt], p->aux));
-      p->eps_on_aux[nxt] = true;
-    }
-    p->eps_key[nxt][0] = lz.nz_key[0];
-    p->eps_key[nxt][1] = lz.nz_key[1];
-    p->eps_valid[nxt] = true;
-  }
-  if (c.enable_demo && !fused_lp) {
-    rc = launch_logpd(e, p->d_xpos, c.shard_count, H, d_logpd_local, s);
-    if (rc != MBD_OK) return rc;
-  }
+  MBD_TRY(p->timing.end(s));
+  MBD_TRY(finish_noise_job(p, lz, marked));
+  if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, p->d_xpos, c.shard_count, H, d_logpd_local, s));
   return MBD_OK;
+}
+
+extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
+                                       float* d_rews_local, float* d_logpd_local, void* stream_) {
+  return plan_sample_rollout(p, i, key_sample, d_Ybar_i, d_rews_local, d_logpd_local, (hipStream_t)stream_,
+                             p ? p->d_state0.get() : nullptr);
 }
 
 extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
@@ -380,10 +477,7 @@ extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_samp
   if (c.enable_demo && !d_logpd_all) return fail(MBD_ERR_INVALID, "enable_demo needs d_logpd_all");
   HIP_TRY(hipSetDevice(p->env->device));
   hipStream_t s = (hipStream_t)stream_;
-  {
-    int rc = plan_enter(p, s);
-    if (rc != MBD_OK) return rc;
-  }
+  MBD_TRY(plan_enter(p, s));
   const int N = c.Nsample, HNu = p->HNu;
   if (p->aux_pending) {  // the other ranks' rows of Y0s (sampled behind the rollout)
     HIP_TRY(hipStreamWaitEvent(s, p->ev_aux, 0));
@@ -406,7 +500,7 @@ extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_samp
     HIP_TRY(hipGetLastError());
   }
   const dim3 ge((HNu + 63) / 64), b64(64);
-  const float* d_cand = p->lazy ? p->d_eps[p->eps_cur] : p->d_Y0s;
+  const float* d_cand = p->lazy ? p->ring.eps[p->ring.cur] : p->d_Y0s;
   const int lazy = p->lazy ? 1 : 0;
   const float sigma_i = p->sigmas[i];
   if (c.update_method == 3) {  // cem_update (path_integral.py:48-52)
@@ -450,11 +544,7 @@ extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_samp
   HIP_TRY(hipGetLastError());
   if (p->lazy) {
     p->peek_ybar = p->d_ybar_keep;
-    p->wm_mark_valid = false;
-    if (p->aux && p->in_step && p->ev_wm) {  // (see sample_rollout: only where the record is free)
-      HIP_TRY(hipEventRecord(p->ev_wm, s));
-      p->wm_mark_valid = true;
-    }
+    MBD_TRY(p->ring.mark_wmean(s, p->aux != nullptr));
   }
   return MBD_OK;
 }
@@ -479,50 +569,37 @@ extern "C" int mbd_plan_get_sigma(mbd_plan* p, float* sigma_out) {
 // Loops that enqueue step after step (mbd_plan_run): a plan whose next step's normals are generated on the second stream
 // stays ONE step behind the device — it enqueues step q once the rollout of step q-1 has started (the queue still holds
 // that rollout and its score: the device never waits for the host) — so that sample_rollout finds the progress word where
-// it needs it and the step's stream carries no event (mbd_plan: the ring of three buffers).
+// it needs it and the step's stream carries no event (NoiseRing: the ring of three buffers).
 static int plan_keep_in_step(mbd_plan* p) {
-  if (!p->lazy || !p->h_progress || p->seq == 0 || p->cfg.shares_device != 0) return MBD_OK;
+  NoiseRing& ring = p->ring;
+  if (!p->lazy || !ring.progress || ring.seq == 0 || p->cfg.shares_device != 0) return MBD_OK;
   if (rollout_takes_noise(plan_rollout_choice(p), p->cfg.prng_impl, p->cfg.Nsample, p->HNu)) return MBD_OK;
-  p->kept_in_step = true;
-  const auto w0 = std::chrono::steady_clock::now();
-  while (progress_read(p->h_progress) < p->seq) {
-    // a stream that is legitimately slow (a shared or time-sliced GPU, a profiler, a system pause) is not an error: the
-    // loop stops keeping step and mbd_plan_sample_rollout orders the two streams with an event instead (its own bounded
-    // wait, then a mark on the step's stream for the aux stream)
-    if (std::chrono::steady_clock::now() - w0 > std::chrono::milliseconds(kInStepWaitMs)) {
-      p->kept_in_step = false;
-      break;
-    }
-    std::this_thread::sleep_for(std::chrono::microseconds(20));
-  }
+  // (a stream slower than the limit: the loop stops keeping step and the step orders the two streams with an event instead —
+  // NoiseRing::mark_last_reader's own bounded wait, then a mark on the step's stream for the aux stream)
+  ring.kept_in_step = progress_wait(ring.progress, ring.seq, kInStepWaitMs, 20);
   return MBD_OK;
 }
 
-// key_after: the Y0s_rng of the step that follows the LAST step (i == 1) of this loop in another one (a receding-horizon
-// episode's next tick), or nullptr
-static int reverse_once_impl(mbd_plan* p, int i, uint32_t key_inout[2], const float* d_Ybar_in, float* d_Ybar_out,
-                             float* d_rew_mean, hipStream_t s, const uint32_t* key_after = nullptr) {
+// d_state0: where the step's rollouts start.  key_after: the Y0s_rng of the step that follows the LAST step (i == 1) of
+// this loop in another one (a receding-horizon episode's next tick), or nullptr
+static int reverse_once_impl(mbd_plan* p, const float* d_state0, int i, uint32_t key_inout[2], const float* d_Ybar_in,
+                             float* d_Ybar_out, float* d_rew_mean, hipStream_t s, const uint32_t* key_after = nullptr) {
   if (p->cfg.shard_count != p->cfg.Nsample)
     return fail(MBD_ERR_STATE, "reverse_once on a sharded plan: use sample_rollout + all-gather + score_update");
   uint32_t keys[4];
   host_split(key_inout, 2, p->cfg.prng_impl, keys);  // rng, Y0s_rng = split(rng)  (mbd_planner.py:103)
   const uint32_t ks[2] = {keys[2], keys[3]};
-  int rc;
   if (i > 1) {  // the next step's normals beside this rollout: its key is the next split of the advanced rng
     uint32_t nk[4];
     const uint32_t adv[2] = {keys[0], keys[1]};
     host_split(adv, 2, p->cfg.prng_impl, nk);
     const uint32_t next_ks[2] = {nk[2], nk[3]};
-    rc = mbd_plan_prefetch_noise(p, next_ks, s);
-    if (rc != MBD_OK) return rc;
+    MBD_TRY(mbd_plan_prefetch_noise(p, next_ks, s));
   } else if (key_after) {
-    rc = mbd_plan_prefetch_noise(p, key_after, s);
-    if (rc != MBD_OK) return rc;
+    MBD_TRY(mbd_plan_prefetch_noise(p, key_after, s));
   }
-  rc = mbd_plan_sample_rollout(p, i, ks, d_Ybar_in, p->d_rews, p->cfg.enable_demo ? p->d_lp : nullptr, s);
-  if (rc != MBD_OK) return rc;
-  rc = mbd_plan_score_update(p, i, ks, d_Ybar_in, p->d_rews, p->d_lp, d_Ybar_out, d_rew_mean, s);
-  if (rc != MBD_OK) return rc;
+  MBD_TRY(plan_sample_rollout(p, i, ks, d_Ybar_in, p->d_rews, p->cfg.enable_demo ? p->d_lp.get() : nullptr, s, d_state0));
+  MBD_TRY(mbd_plan_score_update(p, i, ks, d_Ybar_in, p->d_rews, p->d_lp, d_Ybar_out, d_rew_mean, s));
   key_inout[0] = keys[0];
   key_inout[1] = keys[1];
   return MBD_OK;
@@ -533,8 +610,7 @@ extern "C" int mbd_plan_reverse_once(mbd_plan* p, int i, uint32_t key_inout[2], 
   if (!p || !key_inout || !d_Ybar || !d_rew_mean) return fail(MBD_ERR_INVALID, "NULL argument");
   hipStream_t s = (hipStream_t)stream_;
   // the update is not in place on the device (wmean reads Ybar_i while writing Ybar_{i-1})
-  int rc = reverse_once_impl(p, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s);
-  if (rc != MBD_OK) return rc;
+  MBD_TRY(reverse_once_impl(p, p->d_state0, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s));
   HIP_TRY(hipMemcpyAsync(d_Ybar, p->d_Ybar, sizeof(float) * p->HNu, hipMemcpyDeviceToDevice, s));
   return MBD_OK;
 }
@@ -556,10 +632,8 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
   auto t0 = std::chrono::steady_clock::now();
   for (int i = Nd - 1; i >= 1; --i) {  // reverse() (mbd_planner.py:138-148)
     float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // Ybars.append(Yi)
-    int rc = plan_keep_in_step(p);
-    if (rc != MBD_OK) return rc;
-    rc = reverse_once_impl(p, i, rng, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s);
-    if (rc != MBD_OK) return rc;
+    MBD_TRY(plan_keep_in_step(p));
+    MBD_TRY(reverse_once_impl(p, p->d_state0, i, rng, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s));
     cur = nxt;
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -568,8 +642,7 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
   if (mu_0ts_out) HIP_TRY(hipMemcpy(mu_0ts_out, p->d_mu, sizeof(float) * (size_t)(Nd - 1) * HNu, hipMemcpyDeviceToHost));
   if (rew_means_out) HIP_TRY(hipMemcpy(rew_means_out, p->d_rewmeans, sizeof(float) * (size_t)(Nd - 1), hipMemcpyDeviceToHost));
   if (rew_final_out) {  // rollout_us(state_init, Yi[-1]).mean()  (mbd_planner.py:179-180)
-    int rc = launch_rollout(p->env, p->d_state0, cur, 1, p->cfg.Hsample, nullptr, p->d_scratch, nullptr, nullptr, s);
-    if (rc != MBD_OK) return rc;
+    MBD_TRY(launch_rollout(p->env, p->d_state0, cur, 1, p->cfg.Hsample, nullptr, p->d_scratch, nullptr, nullptr, s));
     HIP_TRY(hipStreamSynchronize(s));
     HIP_TRY(hipMemcpy(rew_final_out, p->d_scratch, sizeof(float), hipMemcpyDeviceToHost));
   }
@@ -610,6 +683,29 @@ int check_mpc_plant(const mbd_env* env, const mbd_mpc_plant* rec) {
   return MBD_OK;
 }
 
+// (mbd_internal.h: what the plans' and the sweeps' episodes do alike)
+bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k) {
+  uint32_t dkk[4];
+  host_split(dk, 2, prng_impl, dkk);
+  dk[0] = dkk[0]; dk[1] = dkk[1];
+  const bool kick_now = pr.kick_std > 0.0f && (t + 1) % pr.kick_every == 0;
+  sp.k[k][0] = dkk[2]; sp.k[k][1] = dkk[3];
+  sp.act_std[k] = pr.act_std; sp.kick_std[k] = kick_now ? pr.kick_std : 0.0f; sp.has[k] = 1;
+  return kick_now;
+}
+
+int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc) {
+  const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
+  if (T < 1) return fail(MBD_ERR_INVALID, "n_ticks=%d: must be >= 1", T);
+  if (K < 1 || K > Nd - 1) return fail(MBD_ERR_INVALID, "warm_steps=%d outside [1, Ndiffuse-1=%d]", K, Nd - 1);
+  if (E < 1 || E >= H) return fail(MBD_ERR_INVALID, "exec_steps=%d outside [1, Hsample=%d)", E, H);
+  for (int r = 0; r < 5; ++r)
+    if (mc->reserved[r] != 0) return fail(MBD_ERR_INVALID, "reserved[%d]=%d: must be 0", r, mc->reserved[r]);
+  if (c.enable_demo) return fail(MBD_ERR_UNSUPPORTED, "enable_demo: demos are time-indexed, an episode has no clock for them");
+  if (c.update_method != 0) return fail(MBD_ERR_UNSUPPORTED, "update_method=%d: receding horizon runs MBD plans only", c.update_method);
+  return MBD_OK;
+}
+
 extern "C" int mbd_plan_set_mpc_plant(mbd_plan* p, const mbd_mpc_plant* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
   if (!rec) {
@@ -617,8 +713,7 @@ extern "C" int mbd_plan_set_mpc_plant(mbd_plan* p, const mbd_mpc_plant* rec) {
     p->plant_rec = mbd_mpc_plant{};
     return MBD_OK;
   }
-  int rc = check_mpc_plant(p->env, rec);
-  if (rc != MBD_OK) return rc;
+  MBD_TRY(check_mpc_plant(p->env, rec));
   p->plant_rec = *rec;
   p->has_plant = true;
   return MBD_OK;
@@ -721,17 +816,14 @@ extern "C" int mbd_plan_set_ensemble(mbd_plan* p, const mbd_ensemble* rec) {
     p->ens_rec = mbd_ensemble{};
     return MBD_OK;
   }
-  int rc = check_ensemble(p, rec);
-  if (rc != MBD_OK) return rc;
+  MBD_TRY(check_ensemble(p, rec));
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the previous record's buffers)
   const size_t N = (size_t)p->cfg.Nsample, H = (size_t)p->cfg.Hsample, M = (size_t)rec->n_members;
-  HIP_TRY(hipFree(p->d_ens_rews)); HIP_TRY(hipFree(p->d_ens_rewss));
-  p->d_ens_rews = p->d_ens_rewss = nullptr;
   p->has_ens = false;
-  HIP_TRY(hipMalloc(&p->d_ens_rews, sizeof(float) * M * N));
-  HIP_TRY(hipMalloc(&p->d_ens_rewss, sizeof(float) * M * N * H));
-  if (!p->d_ens_comb) HIP_TRY(hipMalloc(&p->d_ens_comb, sizeof(float) * N));
+  HIP_TRY(p->d_ens_rews.grow(M * N));
+  HIP_TRY(p->d_ens_rewss.grow(M * N * H));
+  HIP_TRY(p->d_ens_comb.grow(N));
   p->ens_rec = *rec;
   for (int m = 0; m < rec->n_members; ++m)
     if (!p->ens_rec.members[m]) p->ens_rec.members[m] = p->env;
@@ -769,55 +861,28 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   if (!key) return fail(MBD_ERR_INVALID, "key is NULL");
   const mbd_plan_config& c = p->cfg;
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
-  if (T < 1) return fail(MBD_ERR_INVALID, "n_ticks=%d: must be >= 1", T);
-  if (K < 1 || K > Nd - 1) return fail(MBD_ERR_INVALID, "warm_steps=%d outside [1, Ndiffuse-1=%d]", K, Nd - 1);
-  if (E < 1 || E >= H) return fail(MBD_ERR_INVALID, "exec_steps=%d outside [1, Hsample=%d)", E, H);
-  for (int r = 0; r < 5; ++r)
-    if (mc->reserved[r] != 0) return fail(MBD_ERR_INVALID, "reserved[%d]=%d: must be 0", r, mc->reserved[r]);
-  if (c.enable_demo) return fail(MBD_ERR_UNSUPPORTED, "enable_demo: demos are time-indexed, an episode has no clock for them");
-  if (c.update_method != 0) return fail(MBD_ERR_UNSUPPORTED, "update_method=%d: receding horizon runs MBD plans only", c.update_method);
+  MBD_TRY(check_mpc_config(c, mc));
   if (c.shard_count != c.Nsample)
     return fail(MBD_ERR_STATE, "shard_count=%d of Nsample=%d: receding horizon runs unsharded plans", c.shard_count, c.Nsample);
   mbd_env* e = p->env;
   HIP_TRY(hipSetDevice(e->device));
   const int HNu = p->HNu, Nu = e->action_size(), S = e->state_size();
-  if ((size_t)T > p->mpc_ticks) {
-    HIP_TRY(hipFree(p->d_mpc_states)); HIP_TRY(hipFree(p->d_mpc_means)); HIP_TRY(hipFree(p->d_mpc_rewards));
-    p->d_mpc_states = p->d_mpc_means = p->d_mpc_rewards = nullptr;
-    p->mpc_ticks = 0;
-    if (!p->d_mpc_state) HIP_TRY(hipMalloc(&p->d_mpc_state, sizeof(float) * 2 * (size_t)S));
-    HIP_TRY(hipMalloc(&p->d_mpc_states, sizeof(float) * ((size_t)T + 1) * S));
-    HIP_TRY(hipMalloc(&p->d_mpc_means, sizeof(float) * (size_t)T * HNu));
-    HIP_TRY(hipMalloc(&p->d_mpc_rewards, sizeof(float) * (size_t)T * (H - 1)));
-    p->mpc_ticks = (size_t)T;
-  }
+  HIP_TRY(p->d_mpc_state.grow(2 * (size_t)S));
+  HIP_TRY(p->d_mpc_states.grow(((size_t)T + 1) * S));
+  HIP_TRY(p->d_mpc_means.grow((size_t)T * HNu));
+  HIP_TRY(p->d_mpc_rewards.grow((size_t)T * (H - 1)));
   const bool has_plant = p->has_plant;
   const mbd_mpc_plant& pr = p->plant_rec;
   mbd_env* const pe = has_plant && pr.plant ? pr.plant : e;  // the env that executes the rows
   const int EN = E * Nu;
   if (has_plant) {
-    if ((size_t)T * EN > p->mpc_actions_cap) {
-      HIP_TRY(hipFree(p->d_mpc_actions));
-      p->d_mpc_actions = nullptr; p->mpc_actions_cap = 0;
-      HIP_TRY(hipMalloc(&p->d_mpc_actions, sizeof(float) * (size_t)T * EN));
-      p->mpc_actions_cap = (size_t)T * EN;
-    }
-    if ((size_t)EN + 3 > p->plant_eps_cap) {
-      HIP_TRY(hipFree(p->d_plant_eps));
-      p->d_plant_eps = nullptr; p->plant_eps_cap = 0;
-      HIP_TRY(hipMalloc(&p->d_plant_eps, sizeof(float) * ((size_t)EN + 3)));
-      p->plant_eps_cap = (size_t)EN + 3;
-    }
-    if (!p->d_plant_kick) HIP_TRY(hipMalloc(&p->d_plant_kick, sizeof(float) * 3));
+    HIP_TRY(p->d_mpc_actions.grow((size_t)T * EN));
+    HIP_TRY(p->d_plant_eps.grow((size_t)EN + 3));
+    HIP_TRY(p->d_plant_kick.grow(3));
   }
   const int planar = e->kind == ENV_MODEL && (e->model.flags & MBD_FLAG_PLANAR) ? 1 : 0;
   uint32_t dk[2] = {pr.key[0], pr.key[1]};  // the disturbance key chain: dk, d_t = split(dk) per tick
-  // the ticks' rollouts read p->d_state0: s_0 there, then the ping-pong buffers; the plan's own buffer comes back on every exit
-  struct RestoreState0 {
-    mbd_plan* p;
-    float* s0;
-    ~RestoreState0() { p->d_state0 = s0; }
-  } restore{p, p->d_state0};
+  const float* s_t = p->d_state0;  // where tick t's rollouts start: s_0 in the plan's own buffer, then the ping-pong buffers
   hipStream_t s = p->stream;
   float* const ybar0 = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros at tick 0, shift_E(M_{t-1}) after
   HIP_TRY(hipMemsetAsync(ybar0, 0, sizeof(float) * HNu, s));
@@ -839,10 +904,8 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     const float* cur = ybar0;
     for (int i = t == 0 ? Nd - 1 : K; i >= 1; --i) {
       float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
-      int rc = plan_keep_in_step(p);
-      if (rc != MBD_OK) return rc;
-      rc = reverse_once_impl(p, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, t + 1 < T ? after + 2 : nullptr);
-      if (rc != MBD_OK) return rc;
+      MBD_TRY(plan_keep_in_step(p));
+      MBD_TRY(reverse_once_impl(p, s_t, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, t + 1 < T ? after + 2 : nullptr));
       cur = nxt;
     }
     // execute M_t's first E rows from s_t, then the boundary: Ybar of tick t+1, the logs of M_t and s_{t+1}
@@ -850,21 +913,15 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     const float* rows = cur;
     bool kick_now = false;
     if (has_plant) {  // the rows the plant is fed: M_t[0:E] plus the tick's action noise, into the tick's slice of their log
-      uint32_t dkk[4];
-      host_split(dk, 2, c.prng_impl, dkk);
-      dk[0] = dkk[0]; dk[1] = dkk[1];
-      kick_now = pr.kick_std > 0.0f && (t + 1) % pr.kick_every == 0;
       SweepPlant sp{};
-      sp.k[0][0] = dkk[2]; sp.k[0][1] = dkk[3];
-      sp.act_std[0] = pr.act_std; sp.kick_std[0] = kick_now ? pr.kick_std : 0.0f; sp.has[0] = 1;
+      kick_now = plant_tick_draw(pr, c.prng_impl, t, dk, sp, 0);
       float* exec_rows = p->d_mpc_actions + (size_t)t * EN;
       hipLaunchKernelGGL(mpc_plant_rows_kernel, dim3(1, 1), dim3(256), 0, s, sp, c.prng_impl, cur, 0ll, EN, p->d_plant_eps,
                          exec_rows, p->d_plant_kick);
       HIP_TRY(hipGetLastError());
       rows = exec_rows;
     }
-    int rc = launch_rollout(pe, p->d_state0, rows, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr, nullptr, s_next, s);
-    if (rc != MBD_OK) return rc;
+    MBD_TRY(launch_rollout(pe, s_t, rows, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr, nullptr, s_next, s));
     if (kick_now)
       hipLaunchKernelGGL(mpc_boundary_kick_kernel, dim3(1), dim3(256), 0, s, cur, HNu, EN, s_next, S,
                          (const float*)p->d_plant_kick, planar, ybar0, p->d_mpc_means + (size_t)t * HNu,
@@ -873,7 +930,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
       hipLaunchKernelGGL(mpc_boundary_kernel, dim3(1), dim3(256), 0, s, cur, HNu, E * Nu, (const float*)s_next, S, ybar0,
                          p->d_mpc_means + (size_t)t * HNu, p->d_mpc_states + (size_t)(t + 1) * S);
     HIP_TRY(hipGetLastError());
-    p->d_state0 = s_next;
+    s_t = s_next;
   }
   HIP_TRY(hipStreamSynchronize(s));
   const auto t1 = std::chrono::steady_clock::now();
@@ -897,9 +954,8 @@ extern "C" int mbd_plan_eval(mbd_plan* p, const float* Y, float* rew_final_out) 
   if (!p || !Y || !rew_final_out) return fail(MBD_ERR_INVALID, "NULL argument");
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipMemcpy(p->d_Ybar + p->HNu, Y, sizeof(float) * p->HNu, hipMemcpyHostToDevice));
-  int rc = launch_rollout(p->env, p->d_state0, p->d_Ybar + p->HNu, 1, p->cfg.Hsample, nullptr, p->d_scratch, nullptr,
-                          nullptr, p->stream);
-  if (rc != MBD_OK) return rc;
+  MBD_TRY(launch_rollout(p->env, p->d_state0, p->d_Ybar + p->HNu, 1, p->cfg.Hsample, nullptr, p->d_scratch, nullptr, nullptr,
+                         p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   HIP_TRY(hipMemcpy(rew_final_out, p->d_scratch, sizeof(float), hipMemcpyDeviceToHost));
   return MBD_OK;
@@ -914,7 +970,7 @@ extern "C" int mbd_plan_peek(mbd_plan* p, float* Y0s_out, float* rewss_out, floa
     if (!p->peek_ybar) return fail(MBD_ERR_STATE, "peek: no diffusion step to show yet");
     const uint64_t total = (uint64_t)c.Nsample * p->HNu;
     hipLaunchKernelGGL(shift_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, p->stream,
-                       p->d_eps[p->eps_cur], p->HNu, 0ull, (unsigned long long)total, p->sigma_last,
+                       p->ring.eps[p->ring.cur], p->HNu, 0ull, (unsigned long long)total, p->sigma_last,
                        (const float*)nullptr, p->peek_ybar, p->d_Y0s);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(p->stream));
@@ -929,22 +985,12 @@ extern "C" int mbd_plan_peek(mbd_plan* p, float* Y0s_out, float* rewss_out, floa
 
 extern "C" int mbd_plan_enable_timing(mbd_plan* p, int enable) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
-  p->timing = enable != 0;
+  p->timing.on = enable != 0;
   return MBD_OK;
 }
 
 extern "C" int mbd_plan_kernel_time(mbd_plan* p, float* avg_ms_out, int* count_out, int reset) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
   HIP_TRY(hipSetDevice(p->env->device));
-  HIP_TRY(hipDeviceSynchronize());
-  double tot = 0.0;
-  for (size_t k = 0; k < p->events_used; ++k) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, p->events[k].first, p->events[k].second));
-    tot += ms;
-  }
-  if (avg_ms_out) *avg_ms_out = p->events_used ? (float)(tot / (double)p->events_used) : 0.0f;
-  if (count_out) *count_out = (int)p->events_used;
-  if (reset) p->events_used = 0;
-  return MBD_OK;
+  return p->timing.average(avg_ms_out, count_out, reset != 0);
 }

@@ -1,5 +1,6 @@
 // mbd_sweep.hip — sweeps (include/mbd_hip.h): several plans of one env advanced in lockstep, one rollout launch over all
-// their candidates per step (mbd/scripts/run_mbd.py:17-64); MBD plans and the path-integral baselines.
+// their candidates per step (mbd/scripts/run_mbd.py:17-64); MBD plans and the path-integral baselines.  The sweep handle, its
+// ring of noise buffers (sweep_step: another protocol than a plan's NoiseRing) and the batched receding-horizon loop.
 #include "mbd_internal.h"
 
 namespace {
@@ -28,59 +29,34 @@ struct mbd_sweep {
   mbd_plan_config cfg;
   int P = 0, HNu = 0;
   std::vector<float> temps, alphas, alphas_bar, sigmas;
-  hipStream_t stream = nullptr, aux = nullptr;
+  Stream stream, aux;
   // The normals of a step live in a ring of THREE buffers, so that the stream of the steps carries no event at all: the
   // buffer step k+1's normals go into was last read by step k-2's weighted mean, which has finished once the rollout of
   // step k-1 has STARTED — the host learns that from the progress word the rollout launches store into (pinned memory),
   // and the loop stays that close behind the device.  (Two buffers + events: a record behind every weighted mean and a
   // wait in front of every rollout idled the queue 17 us per step, profiles/r03_ring_ab.txt.)
-  hipEvent_t ev_ready[3] = {nullptr, nullptr, nullptr};  // eps[b] holds the normals of its step (recorded on aux)
-  hipEvent_t ev_order = nullptr;  // the event-ordered fallback of a loop whose stream is slower than kInStepWaitMs
-  int event_fallbacks = 0;
-  int* h_progress = nullptr;
-  float *d_state0 = nullptr, *d_eps[3] = {nullptr, nullptr, nullptr}, *d_rews = nullptr, *d_rewss = nullptr, *d_lp = nullptr;
-  float *d_xpos = nullptr, *d_weights = nullptr, *d_zero = nullptr, *d_mu = nullptr, *d_rewmeans = nullptr;
-  float *d_temps = nullptr, *d_final = nullptr, *d_final_rew = nullptr;
+  Event ev_ready[3];  // eps[b] holds the normals of its step (recorded on aux)
+  Event ev_order;     // the event-ordered fallback of a loop whose stream is slower than kInStepWaitMs (created on first use)
+  PinnedWord h_progress;
+  DevBuf<float> d_state0, d_eps[3], d_rews, d_rewss, d_lp, d_xpos, d_weights, d_zero, d_mu, d_rewmeans, d_temps, d_final, d_final_rew;
   // path-integral sweeps (update_method != 0; path_integral.py:111-127): materialised candidates, the carried sigma of
   // every plan, cma-es' spread, cem's selection
-  float *d_Y0s = nullptr, *d_sigma = nullptr, *d_spread = nullptr;
-  int* d_idx = nullptr;
+  DevBuf<float> d_Y0s, d_sigma, d_spread;
+  DevBuf<int> d_idx;
   // batched receding-horizon episodes (mbd_sweep_run_mpc): the episodes' logs, TICK-major — states [T+1][P][state_size],
-  // means [T][P][HNu], rewards [T][P][H-1] (E < H rows per tick) — for up to mpc_ticks ticks, grown on demand; the executed
-  // rows of a tick [P][(H-1) Nu] (compact: what the one-candidate-per-episode rollout reads) and the next tick's first
-  // Ybar [P][HNu].  Sweep-owned, like a plan's.
-  float *d_mpc_states = nullptr, *d_mpc_means = nullptr, *d_mpc_rewards = nullptr, *d_mpc_rows = nullptr, *d_mpc_ybar = nullptr;
-  size_t mpc_ticks = 0;
+  // means [T][P][HNu], rewards [T][P][H-1] (E < H rows per tick) — grown on demand; the executed rows of a tick
+  // [P][(H-1) Nu] (compact: what the one-candidate-per-episode rollout reads) and the next tick's first Ybar [P][HNu].
+  // Sweep-owned, like a plan's.
+  DevBuf<float> d_mpc_states, d_mpc_means, d_mpc_rewards, d_mpc_rows, d_mpc_ybar;
   // the episodes' plant records (mbd_sweep_set_mpc_plant; copies, the plant envs are the caller's), and what a batch with
   // records needs beyond the above: the log of the executed rows, tick-major [T][P][E Nu] — the tick's rollouts read their
   // slices of it —, the tick's normals [P][(H-1) Nu + 3] and kick values [P][3]
   mbd_mpc_plant plant_rec[MBD_SWEEP_MAX_PLANS] = {};
   bool has_plant[MBD_SWEEP_MAX_PLANS] = {};
-  float *d_mpc_actions = nullptr, *d_plant_eps = nullptr, *d_plant_kick = nullptr;
-  size_t mpc_actions_cap = 0;
-  bool timing = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  size_t events_used = 0;
-  mbd_sweep() = default;
-  mbd_sweep(const mbd_sweep&) = delete;
-  mbd_sweep& operator=(const mbd_sweep&) = delete;
-  ~mbd_sweep() {
+  DevBuf<float> d_mpc_actions, d_plant_eps, d_plant_kick;
+  TimingPool timing;
+  ~mbd_sweep() {  // (streams, events and buffers release themselves, on the env's device)
     if (env) (void)hipSetDevice(env->device);
-    for (auto& ev : events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-    (void)hipFree(d_state0); (void)hipFree(d_eps[0]); (void)hipFree(d_eps[1]); (void)hipFree(d_eps[2]); (void)hipFree(d_rews);
-    (void)hipFree(d_rewss);
-    if (h_progress) (void)hipHostFree(h_progress);
-    (void)hipFree(d_lp); (void)hipFree(d_xpos); (void)hipFree(d_weights); (void)hipFree(d_zero); (void)hipFree(d_mu);
-    (void)hipFree(d_rewmeans); (void)hipFree(d_temps); (void)hipFree(d_final); (void)hipFree(d_final_rew);
-    (void)hipFree(d_Y0s); (void)hipFree(d_sigma); (void)hipFree(d_spread); (void)hipFree(d_idx);
-    (void)hipFree(d_mpc_states); (void)hipFree(d_mpc_means); (void)hipFree(d_mpc_rewards); (void)hipFree(d_mpc_rows);
-    (void)hipFree(d_mpc_ybar);
-    (void)hipFree(d_mpc_actions); (void)hipFree(d_plant_eps); (void)hipFree(d_plant_kick);
-    for (int b = 0; b < 3; ++b)
-      if (ev_ready[b]) (void)hipEventDestroy(ev_ready[b]);
-    if (ev_order) (void)hipEventDestroy(ev_order);
-    if (stream) (void)hipStreamDestroy(stream);
-    if (aux) (void)hipStreamDestroy(aux);
   }
 };
 
@@ -105,37 +81,34 @@ extern "C" int mbd_sweep_create(mbd_env* env, const mbd_plan_config* cfg, int n_
   w->temps.assign(P, cfg->temp_sample);
   if (temps) for (int k = 0; k < P; ++k) w->temps[k] = temps[k];
   host_schedule(cfg->beta0, cfg->betaT, Nd, w->alphas, w->alphas_bar, w->sigmas);
-  HIP_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-  HIP_TRY(hipStreamCreateWithFlags(&w->aux, hipStreamNonBlocking));
-  for (int b = 0; b < 3; ++b) HIP_TRY(hipEventCreateWithFlags(&w->ev_ready[b], hipEventDisableTiming));
-  HIP_TRY(hipHostMalloc((void**)&w->h_progress, sizeof(int), hipHostMallocDefault));
-  *w->h_progress = 0;
+  HIP_TRY(w->stream.create());
+  HIP_TRY(w->aux.create());
+  for (int b = 0; b < 3; ++b) HIP_TRY(w->ev_ready[b].create());
+  HIP_TRY(w->h_progress.create());
   const int K = env->model.n_track > 0 ? env->model.n_track : 1;
   const size_t PN = (size_t)P * N;
-  HIP_TRY(hipMalloc(&w->d_state0, sizeof(float) * (size_t)P * env->state_size()));
+  HIP_TRY(w->d_state0.alloc((size_t)P * env->state_size()));
   if (cfg->update_method == 0) {  // MBD plans: lazy candidates, the normals in a ring of three buffers
-    HIP_TRY(hipMalloc(&w->d_eps[0], sizeof(float) * PN * w->HNu));
-    HIP_TRY(hipMalloc(&w->d_eps[1], sizeof(float) * PN * w->HNu));
-    HIP_TRY(hipMalloc(&w->d_eps[2], sizeof(float) * PN * w->HNu));
+    for (int b = 0; b < 3; ++b) HIP_TRY(w->d_eps[b].alloc(PN * w->HNu));
   } else {  // path-integral plans: the candidates themselves (their kernels read them), sigma per plan on the device
-    HIP_TRY(hipMalloc(&w->d_Y0s, sizeof(float) * PN * w->HNu));
-    HIP_TRY(hipMalloc(&w->d_sigma, sizeof(float) * P));
-    HIP_TRY(hipMalloc(&w->d_spread, sizeof(float) * (size_t)P * w->HNu));
-    HIP_TRY(hipMalloc(&w->d_idx, sizeof(int) * (size_t)P * 16));
+    HIP_TRY(w->d_Y0s.alloc(PN * w->HNu));
+    HIP_TRY(w->d_sigma.alloc(P));
+    HIP_TRY(w->d_spread.alloc((size_t)P * w->HNu));
+    HIP_TRY(w->d_idx.alloc((size_t)P * 16));
   }
-  HIP_TRY(hipMalloc(&w->d_rews, sizeof(float) * PN));
-  HIP_TRY(hipMalloc(&w->d_rewss, sizeof(float) * PN * H));
-  HIP_TRY(hipMalloc(&w->d_lp, sizeof(float) * PN));
-  if (cfg->enable_demo) HIP_TRY(hipMalloc(&w->d_xpos, sizeof(float) * PN * H * K * 3));
-  HIP_TRY(hipMalloc(&w->d_weights, sizeof(float) * PN));
-  HIP_TRY(hipMalloc(&w->d_zero, sizeof(float) * (size_t)P * w->HNu));
+  HIP_TRY(w->d_rews.alloc(PN));
+  HIP_TRY(w->d_rewss.alloc(PN * H));
+  HIP_TRY(w->d_lp.alloc(PN));
+  if (cfg->enable_demo) HIP_TRY(w->d_xpos.alloc(PN * H * K * 3));
+  HIP_TRY(w->d_weights.alloc(PN));
+  HIP_TRY(w->d_zero.alloc((size_t)P * w->HNu));
   HIP_TRY(hipMemset(w->d_zero, 0, sizeof(float) * (size_t)P * w->HNu));
-  HIP_TRY(hipMalloc(&w->d_mu, sizeof(float) * (size_t)P * (Nd - 1) * w->HNu));
-  HIP_TRY(hipMalloc(&w->d_rewmeans, sizeof(float) * (size_t)P * (Nd - 1)));
-  HIP_TRY(hipMalloc(&w->d_temps, sizeof(float) * P));
+  HIP_TRY(w->d_mu.alloc((size_t)P * (Nd - 1) * w->HNu));
+  HIP_TRY(w->d_rewmeans.alloc((size_t)P * (Nd - 1)));
+  HIP_TRY(w->d_temps.alloc(P));
   HIP_TRY(hipMemcpy(w->d_temps, w->temps.data(), sizeof(float) * P, hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&w->d_final, sizeof(float) * (size_t)P * w->HNu));
-  HIP_TRY(hipMalloc(&w->d_final_rew, sizeof(float) * (size_t)P));
+  HIP_TRY(w->d_final.alloc((size_t)P * w->HNu));
+  HIP_TRY(w->d_final_rew.alloc(P));
   *out = guard.release();
   return MBD_OK;
 }
@@ -157,17 +130,27 @@ extern "C" int mbd_sweep_set_state0(mbd_sweep* w, int k, const float* state0) {
 extern "C" int mbd_sweep_kernel_time(mbd_sweep* w, int enable, float* avg_ms_out, int* count_out) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   HIP_TRY(hipSetDevice(w->env->device));
-  HIP_TRY(hipDeviceSynchronize());
-  double tot = 0.0;
-  for (size_t k = 0; k < w->events_used; ++k) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, w->events[k].first, w->events[k].second));
-    tot += ms;
-  }
-  if (avg_ms_out) *avg_ms_out = w->events_used ? (float)(tot / (double)w->events_used) : 0.0f;
-  if (count_out) *count_out = (int)w->events_used;
-  w->events_used = 0;
-  w->timing = enable != 0;
+  MBD_TRY(w->timing.average(avg_ms_out, count_out, true));
+  w->timing.on = enable != 0;
+  return MBD_OK;
+}
+
+// what a finished run hands back, once its stream is idle: every plan's means and mean rewards, and the reward of its final
+// mean — rollout_us(state_init, Yi[-1]).mean() (mbd_planner.py:179-180), eval_us(state_init, mu_0).mean()
+// (path_integral.py:146) — from one launch of P candidates
+static int sweep_results(mbd_sweep* w, float* mu_0ts_out, float* rew_means_out, float* rew_final_out) {
+  const int P = w->P, Nd = w->cfg.Ndiffuse, HNu = w->HNu;
+  hipStream_t s = w->stream;
+  const size_t mu_n = (size_t)P * (Nd - 1) * HNu;
+  if (mu_0ts_out) HIP_TRY(hipMemcpy(mu_0ts_out, w->d_mu, sizeof(float) * mu_n, hipMemcpyDeviceToHost));
+  if (rew_means_out) HIP_TRY(hipMemcpy(rew_means_out, w->d_rewmeans, sizeof(float) * (size_t)P * (Nd - 1), hipMemcpyDeviceToHost));
+  if (!rew_final_out) return MBD_OK;
+  HIP_TRY(hipMemcpy2DAsync(w->d_final, sizeof(float) * HNu, w->d_mu + (size_t)(Nd - 2) * HNu,
+                           sizeof(float) * (size_t)(Nd - 1) * HNu, sizeof(float) * HNu, P, hipMemcpyDeviceToDevice, s));
+  const int sw[3] = {1, w->env->state_size(), 0};
+  MBD_TRY(launch_rollout(w->env, w->d_state0, w->d_final, P, w->cfg.Hsample, nullptr, w->d_final_rew, nullptr, nullptr, s, nullptr, sw));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipMemcpy(rew_final_out, w->d_final_rew, sizeof(float) * P, hipMemcpyDeviceToHost));
   return MBD_OK;
 }
 
@@ -183,9 +166,7 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
   hipStream_t s = w->stream;
   std::vector<uint32_t> rng(keys, keys + 2 * (size_t)P);
   const uint64_t per_plan = (uint64_t)N * HNu;
-  const uint64_t items = c.prng_impl == MBD_PRNG_PARTITIONABLE ? per_plan : (per_plan + 1) / 2;
-  uint64_t nblocks = (items + 255) / 256;
-  if (nblocks > 4096) nblocks = 4096;  // (grid-stride)
+  const unsigned nblocks = noise_blocks(c.prng_impl, per_plan, 4096);
   {
     std::vector<float> ones((size_t)P, 1.0f);  // sigma = 1.0 (path_integral.py:131)
     HIP_TRY(hipMemcpy(w->d_sigma, ones.data(), sizeof(float) * P, hipMemcpyHostToDevice));
@@ -207,25 +188,13 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
     const float* mu_in = step == 0 ? w->d_zero : w->d_mu + (size_t)(step - 1) * HNu;
     const long long mu_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
     float* mu_out = w->d_mu + (size_t)step * HNu;
-    hipLaunchKernelGGL(sample_batch_kernel, dim3((unsigned)nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
+    hipLaunchKernelGGL(sample_batch_kernel, dim3(nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
                        (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s);
     HIP_TRY(hipGetLastError());
-    hipEvent_t ev1 = nullptr;
-    if (w->timing) {
-      if (w->events_used == w->events.size()) {
-        hipEvent_t a, b;
-        HIP_TRY(hipEventCreate(&a));
-        HIP_TRY(hipEventCreate(&b));
-        w->events.emplace_back(a, b);
-      }
-      ev1 = w->events[w->events_used].second;
-      HIP_TRY(hipEventRecord(w->events[w->events_used].first, s));
-      w->events_used++;
-    }
+    MBD_TRY(w->timing.begin(s));
     const int sw[3] = {N, S, 0};
-    int rc = launch_rollout(e, w->d_state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, nullptr, s, nullptr, sw);
-    if (rc != MBD_OK) return rc;
-    if (ev1) HIP_TRY(hipEventRecord(ev1, s));
+    MBD_TRY(launch_rollout(e, w->d_state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, nullptr, s, nullptr, sw));
+    MBD_TRY(w->timing.end(s));
     pb.mu = mu_stride;
     if (c.update_method == 3) {  // cem_update (path_integral.py:48-52)
       const int K = N < 10 ? N : 10;
@@ -240,8 +209,8 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
       ScoreBatch sb;
       sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)per_plan;
       sb.ybar_in = mu_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
-      launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews, (const float*)nullptr, N, e->rew_xref,
-                               c.temp_sample, 0, w->d_weights, w->d_rewmeans + step, (const float*)w->d_Y0s, HNu, mu_in, 1.0f, 1.0f,
+      launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
+                               c.temp_sample, 0, w->d_weights.get(), w->d_rewmeans + step, (const float*)w->d_Y0s, HNu, mu_in, 1.0f, 1.0f,
                                1.0f, 0, mu_out, 0, 0.0f, (float*)nullptr, sb);
       if (c.update_method == 2) {
         hipLaunchKernelGGL(cma_spread_kernel, dim3((HNu + 63) / 64, (unsigned)P), b64, 0, s, (const float*)w->d_weights,
@@ -254,19 +223,7 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
   HIP_TRY(hipStreamSynchronize(s));
   auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
-  const size_t mu_n = (size_t)P * (Nd - 1) * HNu;
-  if (mu_0ts_out) HIP_TRY(hipMemcpy(mu_0ts_out, w->d_mu, sizeof(float) * mu_n, hipMemcpyDeviceToHost));
-  if (rew_means_out) HIP_TRY(hipMemcpy(rew_means_out, w->d_rewmeans, sizeof(float) * (size_t)P * (Nd - 1), hipMemcpyDeviceToHost));
-  if (rew_final_out) {  // eval_us(state_init, mu_0).mean() of every plan (path_integral.py:146): one launch of P candidates
-    HIP_TRY(hipMemcpy2DAsync(w->d_final, sizeof(float) * HNu, w->d_mu + (size_t)(Nd - 2) * HNu,
-                             sizeof(float) * (size_t)(Nd - 1) * HNu, sizeof(float) * HNu, P, hipMemcpyDeviceToDevice, s));
-    const int sw[3] = {1, S, 0};
-    int rc = launch_rollout(e, w->d_state0, w->d_final, P, H, nullptr, w->d_final_rew, nullptr, nullptr, s, nullptr, sw);
-    if (rc != MBD_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(rew_final_out, w->d_final_rew, sizeof(float) * P, hipMemcpyDeviceToHost));
-  }
-  return MBD_OK;
+  return sweep_results(w, mu_0ts_out, rew_means_out, rew_final_out);
 }
 
 extern "C" int mbd_sweep_get_sigmas(mbd_sweep* w, float* sigmas_out) {
@@ -294,11 +251,8 @@ struct SweepStep {
 // rollout runs (a ring of three buffers, see mbd_sweep), like a single large plan's
 void sweep_noise(mbd_sweep* w, const SweepKeys& sk, int buf, hipStream_t st) {
   const mbd_plan_config& c = w->cfg;
-  const uint64_t per_plan = (uint64_t)c.Nsample * w->HNu;
-  const uint64_t items = c.prng_impl == MBD_PRNG_PARTITIONABLE ? per_plan : (per_plan + 1) / 2;
-  uint64_t nblocks = (items + 255) / 256;
-  if (nblocks > 4096) nblocks = 4096;  // (grid-stride)
-  hipLaunchKernelGGL(noise_batch_kernel, dim3((unsigned)nblocks, (unsigned)w->P), dim3(256), 0, st, sk, c.prng_impl, c.Nsample, w->HNu,
+  const unsigned nblocks = noise_blocks(c.prng_impl, (uint64_t)c.Nsample * w->HNu, 4096);
+  hipLaunchKernelGGL(noise_batch_kernel, dim3(nblocks, (unsigned)w->P), dim3(256), 0, st, sk, c.prng_impl, c.Nsample, w->HNu,
                      w->d_eps[buf]);
 }
 
@@ -327,20 +281,12 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
     // eps[nxt] was last read by the weighted mean of step - 2, finished once the rollout of step - 1 (which stores
     // `step` into the progress word) has started: the loop waits for that — one step behind the device, whose queue
     // still holds that rollout and its score — instead of ordering the two streams with events
-    if (step >= 2) {
-      const auto w0 = std::chrono::steady_clock::now();
-      while (progress_read(w->h_progress) < step) {
-        if (std::chrono::steady_clock::now() - w0 > std::chrono::milliseconds(kInStepWaitMs)) {
-          // a legitimately slow stream (shared / time-sliced GPU, profiler, system pause): order the streams with an
-          // event instead — everything enqueued on s so far, the reader of eps[nxt] included, precedes the generation
-          if (!w->ev_order) HIP_TRY(hipEventCreateWithFlags(&w->ev_order, hipEventDisableTiming));
-          HIP_TRY(hipEventRecord(w->ev_order, s));
-          HIP_TRY(hipStreamWaitEvent(w->aux, w->ev_order, 0));
-          w->event_fallbacks++;
-          break;
-        }
-        std::this_thread::sleep_for(std::chrono::microseconds(20));
-      }
+    if (step >= 2 && !progress_wait(w->h_progress, step, kInStepWaitMs, 20)) {
+      // a legitimately slow stream (shared / time-sliced GPU, profiler, system pause): order the streams with an
+      // event instead — everything enqueued on s so far, the reader of eps[nxt] included, precedes the generation
+      if (!w->ev_order) HIP_TRY(w->ev_order.create());
+      HIP_TRY(hipEventRecord(w->ev_order, s));
+      HIP_TRY(hipStreamWaitEvent(w->aux, w->ev_order, 0));
     }
     sweep_noise(w, *st.next_keys, nxt, w->aux);
     HIP_TRY(hipGetLastError());
@@ -352,32 +298,18 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
   lz.progress = w->h_progress;
   lz.progress_val = step + 1;
   const int sw[3] = {N, S, (int)st.ybar_in_stride};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (w->timing) {
-    if (w->events_used == w->events.size()) {
-      hipEvent_t a, b;
-      HIP_TRY(hipEventCreate(&a));
-      HIP_TRY(hipEventCreate(&b));
-      w->events.emplace_back(a, b);
-    }
-    ev0 = w->events[w->events_used].first; ev1 = w->events[w->events_used].second;
-    w->events_used++;
-    HIP_TRY(hipEventRecord(ev0, s));
-  }
+  MBD_TRY(w->timing.begin(s));
   const bool fused_lp = c.enable_demo && rollout_choice(e, P * N, H, sw).fuses_logpd;  // (mbd_plan.hip: the log-densities out of the rollout)
-  int rc = launch_rollout(e, st.state0, w->d_eps[cur], P * N, H, w->d_rewss, w->d_rews,
-                          (c.enable_demo && !fused_lp) ? w->d_xpos : nullptr, nullptr, s, &lz, sw, fused_lp ? w->d_lp : nullptr);
-  if (rc != MBD_OK) return rc;
-  if (w->timing) HIP_TRY(hipEventRecord(ev1, s));
-  if (c.enable_demo && !fused_lp) {
-    rc = launch_logpd(e, w->d_xpos, P * N, H, w->d_lp, s);
-    if (rc != MBD_OK) return rc;
-  }
+  MBD_TRY(launch_rollout(e, st.state0, w->d_eps[cur], P * N, H, w->d_rewss, w->d_rews,
+                         (c.enable_demo && !fused_lp) ? w->d_xpos.get() : nullptr, nullptr, s, &lz, sw,
+                         fused_lp ? w->d_lp.get() : nullptr));
+  MBD_TRY(w->timing.end(s));
+  if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, w->d_xpos, P * N, H, w->d_lp, s));
   ScoreBatch sb;
   sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)N * HNu;
   sb.ybar_in = st.ybar_in_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
-  launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews, c.enable_demo ? w->d_lp : nullptr, N,
-                           e->rew_xref, c.temp_sample, 1, w->d_weights, w->d_rewmeans + st.slot, w->d_eps[cur], HNu, st.ybar_in,
+  launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), c.enable_demo ? w->d_lp.get() : nullptr, N,
+                           e->rew_xref, c.temp_sample, 1, w->d_weights.get(), w->d_rewmeans + st.slot, w->d_eps[cur].get(), HNu, st.ybar_in,
                            w->alphas[i], w->alphas_bar[i], w->alphas_bar[i - 1], c.literal_score,
                            w->d_mu + (size_t)st.slot * HNu, 1, w->sigmas[i], (float*)nullptr, sb);
   HIP_TRY(hipGetLastError());
@@ -391,13 +323,13 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
   mbd_env* e = w->env;
   HIP_TRY(hipSetDevice(e->device));
   const mbd_plan_config& c = w->cfg;
-  const int P = w->P, H = c.Hsample, Nd = c.Ndiffuse, HNu = w->HNu, S = e->state_size();
+  const int P = w->P, Nd = c.Ndiffuse, HNu = w->HNu;
   hipStream_t s = w->stream;
   if (c.update_method != 0) return sweep_run_path_integral(w, keys, mu_0ts_out, rew_means_out, rew_final_out, loop_seconds_out);
   std::vector<uint32_t> rng(keys, keys + 2 * (size_t)P);
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(w->aux));
-  __atomic_store_n(w->h_progress, 0, __ATOMIC_RELEASE);
+  progress_reset(w->h_progress);
   auto t0 = std::chrono::steady_clock::now();
   SweepKeys sk;
   sweep_split_keys(w, rng, sk);
@@ -410,25 +342,12 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
     st.ybar_in = step == 0 ? w->d_zero : w->d_mu + (size_t)(step - 1) * HNu;
     st.ybar_in_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
     st.next_keys = i > 1 ? &sk : nullptr;
-    int rc = sweep_step(w, st);
-    if (rc != MBD_OK) return rc;
+    MBD_TRY(sweep_step(w, st));
   }
   HIP_TRY(hipStreamSynchronize(s));
   auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
-  const size_t mu_n = (size_t)P * (Nd - 1) * HNu;
-  if (mu_0ts_out) HIP_TRY(hipMemcpy(mu_0ts_out, w->d_mu, sizeof(float) * mu_n, hipMemcpyDeviceToHost));
-  if (rew_means_out) HIP_TRY(hipMemcpy(rew_means_out, w->d_rewmeans, sizeof(float) * (size_t)P * (Nd - 1), hipMemcpyDeviceToHost));
-  if (rew_final_out) {  // rollout_us(state_init, Yi[-1]).mean() of every plan (mbd_planner.py:179-180): one launch of P candidates
-    HIP_TRY(hipMemcpy2DAsync(w->d_final, sizeof(float) * HNu, w->d_mu + (size_t)(Nd - 2) * HNu,
-                             sizeof(float) * (size_t)(Nd - 1) * HNu, sizeof(float) * HNu, P, hipMemcpyDeviceToDevice, s));
-    const int sw[3] = {1, S, 0};
-    int rc = launch_rollout(e, w->d_state0, w->d_final, P, H, nullptr, w->d_final_rew, nullptr, nullptr, s, nullptr, sw);
-    if (rc != MBD_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(rew_final_out, w->d_final_rew, sizeof(float) * P, hipMemcpyDeviceToHost));
-  }
-  return MBD_OK;
+  return sweep_results(w, mu_0ts_out, rew_means_out, rew_final_out);
 }
 
 extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant* rec) {
@@ -439,8 +358,7 @@ extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant*
     w->plant_rec[k] = mbd_mpc_plant{};
     return MBD_OK;
   }
-  int rc = check_mpc_plant(w->env, rec);
-  if (rc != MBD_OK) return rc;
+  MBD_TRY(check_mpc_plant(w->env, rec));
   w->plant_rec[k] = *rec;
   w->has_plant[k] = true;
   return MBD_OK;
@@ -465,39 +383,22 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   if (!keys) return fail(MBD_ERR_INVALID, "keys is NULL");
   const mbd_plan_config& c = w->cfg;
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
-  if (T < 1) return fail(MBD_ERR_INVALID, "n_ticks=%d: must be >= 1", T);
-  if (K < 1 || K > Nd - 1) return fail(MBD_ERR_INVALID, "warm_steps=%d outside [1, Ndiffuse-1=%d]", K, Nd - 1);
-  if (E < 1 || E >= H) return fail(MBD_ERR_INVALID, "exec_steps=%d outside [1, Hsample=%d)", E, H);
-  for (int r = 0; r < 5; ++r)
-    if (mc->reserved[r] != 0) return fail(MBD_ERR_INVALID, "reserved[%d]=%d: must be 0", r, mc->reserved[r]);
-  if (c.enable_demo) return fail(MBD_ERR_UNSUPPORTED, "enable_demo: demos are time-indexed, an episode has no clock for them");
-  if (c.update_method != 0) return fail(MBD_ERR_UNSUPPORTED, "update_method=%d: receding horizon runs MBD plans only", c.update_method);
+  MBD_TRY(check_mpc_config(c, mc));
   mbd_env* e = w->env;
   HIP_TRY(hipSetDevice(e->device));
   const int P = w->P, HNu = w->HNu, Nu = e->action_size(), S = e->state_size();
-  if ((size_t)T > w->mpc_ticks) {
-    HIP_TRY(hipFree(w->d_mpc_states)); HIP_TRY(hipFree(w->d_mpc_means)); HIP_TRY(hipFree(w->d_mpc_rewards));
-    w->d_mpc_states = w->d_mpc_means = w->d_mpc_rewards = nullptr;
-    w->mpc_ticks = 0;
-    if (!w->d_mpc_rows) HIP_TRY(hipMalloc(&w->d_mpc_rows, sizeof(float) * (size_t)P * (H - 1) * Nu));
-    if (!w->d_mpc_ybar) HIP_TRY(hipMalloc(&w->d_mpc_ybar, sizeof(float) * (size_t)P * HNu));
-    HIP_TRY(hipMalloc(&w->d_mpc_states, sizeof(float) * ((size_t)T + 1) * P * S));
-    HIP_TRY(hipMalloc(&w->d_mpc_means, sizeof(float) * (size_t)T * P * HNu));
-    HIP_TRY(hipMalloc(&w->d_mpc_rewards, sizeof(float) * (size_t)T * P * (H - 1)));
-    w->mpc_ticks = (size_t)T;
-  }
+  HIP_TRY(w->d_mpc_rows.grow((size_t)P * (H - 1) * Nu));
+  HIP_TRY(w->d_mpc_ybar.grow((size_t)P * HNu));
+  HIP_TRY(w->d_mpc_states.grow(((size_t)T + 1) * P * S));
+  HIP_TRY(w->d_mpc_means.grow((size_t)T * P * HNu));
+  HIP_TRY(w->d_mpc_rewards.grow((size_t)T * P * (H - 1)));
   const int EN = E * Nu;
   bool any_plant = false;
   for (int k = 0; k < P; ++k) any_plant = any_plant || w->has_plant[k];
   if (any_plant) {
-    if ((size_t)T * P * EN > w->mpc_actions_cap) {
-      HIP_TRY(hipFree(w->d_mpc_actions));
-      w->d_mpc_actions = nullptr; w->mpc_actions_cap = 0;
-      HIP_TRY(hipMalloc(&w->d_mpc_actions, sizeof(float) * (size_t)T * P * EN));
-      w->mpc_actions_cap = (size_t)T * P * EN;
-    }
-    if (!w->d_plant_eps) HIP_TRY(hipMalloc(&w->d_plant_eps, sizeof(float) * (size_t)P * ((size_t)(H - 1) * Nu + 3)));
-    if (!w->d_plant_kick) HIP_TRY(hipMalloc(&w->d_plant_kick, sizeof(float) * (size_t)P * 3));
+    HIP_TRY(w->d_mpc_actions.grow((size_t)T * P * EN));
+    HIP_TRY(w->d_plant_eps.grow((size_t)P * ((size_t)(H - 1) * Nu + 3)));
+    HIP_TRY(w->d_plant_kick.grow((size_t)P * 3));
   }
   const int planar = (e->model.flags & MBD_FLAG_PLANAR) ? 1 : 0;
   // the disturbance key chains: dk, d_t = split(dk) per tick and episode
@@ -509,7 +410,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   HIP_TRY(hipStreamSynchronize(w->aux));
   HIP_TRY(hipMemcpyAsync(w->d_mpc_states, w->d_state0, sizeof(float) * (size_t)P * S, hipMemcpyDeviceToDevice, s));  // s_{.,0}
   HIP_TRY(hipStreamSynchronize(s));
-  __atomic_store_n(w->h_progress, 0, __ATOMIC_RELEASE);
+  progress_reset(w->h_progress);
   const auto t0 = std::chrono::steady_clock::now();
   // per episode: rng, k_t = split(rng) per tick, the tick's chain r, Y0s_rng = split(r) per step from r = k_t.  The keys
   // are drawn in the order the steps run, one step ahead of the rollouts (the normals of a tick's first step are prepared
@@ -539,8 +440,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       st.ybar_in = i == i_start ? (t == 0 ? w->d_zero : w->d_mpc_ybar) : w->d_mu + (size_t)(st.slot - 1) * HNu;
       st.ybar_in_stride = i == i_start ? HNu : mu_stride;
       st.next_keys = follows ? &sk : nullptr;
-      int rc = sweep_step(w, st);
-      if (rc != MBD_OK) return rc;
+      MBD_TRY(sweep_step(w, st));
     }
     // the boundary: the logs of M_{.,t}, its first E rows and Ybar of tick t+1; then the rows executed from s_{.,t}
     hipLaunchKernelGGL(mpc_boundary_batch_kernel, dim3(1, (unsigned)P), dim3(256), 0, s,
@@ -548,24 +448,14 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
                        w->d_mpc_means + (size_t)t * P * HNu, w->d_mpc_rows);
     HIP_TRY(hipGetLastError());
     if (!any_plant) {
-      int rc = launch_rollout(e, states_t, w->d_mpc_rows, P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr, nullptr,
-                              w->d_mpc_states + (size_t)(t + 1) * P * S, s, nullptr, exec_sw);
-      if (rc != MBD_OK) return rc;
+      MBD_TRY(launch_rollout(e, states_t, w->d_mpc_rows, P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr, nullptr,
+                             w->d_mpc_states + (size_t)(t + 1) * P * S, s, nullptr, exec_sw));
       continue;
     }
     SweepPlant sp{};
     bool any_kick = false;
-    for (int k = 0; k < P; ++k) {
-      if (!w->has_plant[k]) continue;
-      const mbd_mpc_plant& pr = w->plant_rec[k];
-      uint32_t dkk[4];
-      host_split(&dk[2 * k], 2, c.prng_impl, dkk);
-      dk[2 * k] = dkk[0]; dk[2 * k + 1] = dkk[1];
-      const bool kick_now = pr.kick_std > 0.0f && (t + 1) % pr.kick_every == 0;
-      any_kick = any_kick || kick_now;
-      sp.k[k][0] = dkk[2]; sp.k[k][1] = dkk[3];
-      sp.act_std[k] = pr.act_std; sp.kick_std[k] = kick_now ? pr.kick_std : 0.0f; sp.has[k] = 1;
-    }
+    for (int k = 0; k < P; ++k)
+      if (w->has_plant[k] && plant_tick_draw(w->plant_rec[k], c.prng_impl, t, &dk[2 * k], sp, k)) any_kick = true;
     float* rows_t = w->d_mpc_actions + (size_t)t * P * EN;
     float* rewards_t = w->d_mpc_rewards + (size_t)t * P * E;
     float* states_t1 = w->d_mpc_states + (size_t)(t + 1) * P * S;
@@ -576,9 +466,8 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     for (int k0 = 0; k0 < P;) {  // one launch per run of episodes that share a plant handle
       int k1 = k0 + 1;
       while (k1 < P && plant_of(k1) == plant_of(k0)) ++k1;
-      int rc = launch_rollout(plant_of(k0), states_t + (size_t)k0 * S, rows_t + (size_t)k0 * EN, k1 - k0, E,
-                              rewards_t + (size_t)k0 * E, nullptr, nullptr, states_t1 + (size_t)k0 * S, s, nullptr, exec_sw);
-      if (rc != MBD_OK) return rc;
+      MBD_TRY(launch_rollout(plant_of(k0), states_t + (size_t)k0 * S, rows_t + (size_t)k0 * EN, k1 - k0, E,
+                             rewards_t + (size_t)k0 * E, nullptr, nullptr, states_t1 + (size_t)k0 * S, s, nullptr, exec_sw));
       k0 = k1;
     }
     if (any_kick) {
@@ -592,37 +481,33 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
   // the logs are tick-major, the outputs episode-major: ONE device->host copy per log, transposed on the host
   std::vector<float> tmp;
-  if (rewards_out) {
-    tmp.resize((size_t)T * P * E);
-    HIP_TRY(hipMemcpy(tmp.data(), w->d_mpc_rewards, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
-    for (int t = 0; t < T; ++t)
+  auto fetch = [&](const float* d_log, size_t n) {
+    tmp.resize(n);
+    return hipMemcpy(tmp.data(), d_log, sizeof(float) * n, hipMemcpyDeviceToHost);
+  };
+  // out [P][rows][n] from the first n floats of every row of tmp [rows][P][row]
+  auto episode_major = [&](float* out, int rows, size_t row, size_t n) {
+    for (int t = 0; t < rows; ++t)
       for (int k = 0; k < P; ++k)
-        memcpy(rewards_out + ((size_t)k * T + t) * E, tmp.data() + ((size_t)t * P + k) * E, sizeof(float) * (size_t)E);
+        memcpy(out + ((size_t)k * rows + t) * n, tmp.data() + ((size_t)t * P + k) * row, sizeof(float) * n);
+  };
+  if (rewards_out) {
+    HIP_TRY(fetch(w->d_mpc_rewards, (size_t)T * P * E));
+    episode_major(rewards_out, T, E, E);
   }
   if (states_out) {
-    tmp.resize(((size_t)T + 1) * P * S);
-    HIP_TRY(hipMemcpy(tmp.data(), w->d_mpc_states, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
-    for (int t = 0; t <= T; ++t)
-      for (int k = 0; k < P; ++k)
-        memcpy(states_out + ((size_t)k * (T + 1) + t) * S, tmp.data() + ((size_t)t * P + k) * S, sizeof(float) * (size_t)S);
+    HIP_TRY(fetch(w->d_mpc_states, ((size_t)T + 1) * P * S));
+    episode_major(states_out, T + 1, S, S);
   }
   if (any_plant && actions_out) {  // (the executed rows carry the action noise: their own log)
-    tmp.resize((size_t)T * P * EN);
-    HIP_TRY(hipMemcpy(tmp.data(), w->d_mpc_actions, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
-    for (int t = 0; t < T; ++t)
-      for (int k = 0; k < P; ++k)
-        memcpy(actions_out + ((size_t)k * T + t) * EN, tmp.data() + ((size_t)t * P + k) * EN, sizeof(float) * (size_t)EN);
+    HIP_TRY(fetch(w->d_mpc_actions, (size_t)T * P * EN));
+    episode_major(actions_out, T, EN, EN);
     actions_out = nullptr;
   }
   if (means_out || actions_out) {  // (the executed rows are M_t[0:E]: taken from the one copy of the means)
-    tmp.resize((size_t)T * P * HNu);
-    HIP_TRY(hipMemcpy(tmp.data(), w->d_mpc_means, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
-    for (int t = 0; t < T; ++t)
-      for (int k = 0; k < P; ++k) {
-        const float* m = tmp.data() + ((size_t)t * P + k) * HNu;
-        if (means_out) memcpy(means_out + ((size_t)k * T + t) * HNu, m, sizeof(float) * (size_t)HNu);
-        if (actions_out) memcpy(actions_out + ((size_t)k * T + t) * E * Nu, m, sizeof(float) * (size_t)E * Nu);
-      }
+    HIP_TRY(fetch(w->d_mpc_means, (size_t)T * P * HNu));
+    if (means_out) episode_major(means_out, T, HNu, HNu);
+    if (actions_out) episode_major(actions_out, T, HNu, EN);
   }
   return MBD_OK;
 }

@@ -143,7 +143,8 @@ def test_episode_matches_the_checker_at_full_size(gpu, orc_omp, N, Nd, K, T):
 @pytest.mark.parametrize("N", [256, 4096])
 def test_episode_against_the_open_loop_runs(gpu, N):
     """Self-comparisons of the library: tick 0 is mbd_plan_run(k_0)'s last mean; an episode of 3 ticks is a prefix of one of 6;
-    after an episode the plan's mbd_plan_run equals a fresh plan's (its state0 came back)."""
+    after an episode the plan's mbd_plan_run equals a fresh plan's (its state0 is untouched).  N = 256: the episode of 6 ticks
+    is a prefix of one of 9 run after both on the same plan — the plan's logs grow after their first use."""
     from mbd_hip.envs import get_env
     from mbd_hip.planners.mbd_planner import Plan
     a = _args("humanoidrun", N, Nd=12, K=3)
@@ -157,6 +158,10 @@ def test_episode_against_the_open_loop_runs(gpu, N):
     for k in ("actions", "rewards", "states", "means"):
         assert np.array_equal(short[k], long[k][: len(short[k])]), k
     assert np.array_equal(long["states"][0], np.asarray(st.pipeline_state, np.float32).reshape(-1))
+    if N == 256:
+        longer = plan.run_mpc(key, 9, 3, 2)
+        for k in ("actions", "rewards", "states", "means"):
+            assert len(longer[k]) > len(long[k]) and np.array_equal(long[k], longer[k][: len(long[k])]), k
     mu_after, rm_after, rf_after, _ = plan.run(key)
     fresh = Plan(env, a)
     fresh.set_state0(st)

@@ -182,6 +182,36 @@ def test_batch_on_the_general_instantiations_equals_the_single_episodes(gpu, nam
 
 
 @pytest.mark.gpu
+def test_batch_logs_grow_after_their_first_use(gpu):
+    """P = 2: a batch of T = 3 and then one of T = 7 on the same sweep — the sweep's logs grow behind their first use.  The
+    short batch is a prefix of the long one per episode, and the long one equals the same 7 ticks on a fresh sweep."""
+    from mbd_hip.envs import get_env
+    from mbd_hip.planners.mbd_planner import Sweep
+    P, K, E = 2, 3, 2
+    a = _args("humanoidrun", 256, Nd=12)
+    env = get_env("humanoidrun")
+    keys = np.array([gpu.prng_key(30 + k) for k in range(P)], np.uint32)
+    states = [env.reset(gpu.prng_key(5 + k)) for k in range(P)]
+
+    def sweep():
+        sw = Sweep(env, a, P)
+        for k in range(P):
+            sw.set_state0(k, states[k])
+        return sw
+    sw = sweep()
+    short = sw.run_mpc(keys, 3, K, E)
+    long = sw.run_mpc(keys, 7, K, E)
+    sw.close()
+    fresh = sweep()
+    ref = fresh.run_mpc(keys, 7, K, E)
+    fresh.close()
+    for f in _LOGS:
+        assert short[f].shape[1] < long[f].shape[1] and np.array_equal(short[f], long[f][:, : short[f].shape[1]]), f
+        assert np.array_equal(long[f], ref[f]), f
+    assert not np.array_equal(long["means"][0], long["means"][1])
+
+
+@pytest.mark.gpu
 def test_batch_structure(gpu):
     """A batch of T = 3 is a prefix of the same batch with T = 6; means[k][0] is the last mean of Sweep.run from
     split(keys[k])[1]; after a batch Sweep.run equals a fresh sweep's (the start states came back); reordering the episodes

@@ -311,6 +311,35 @@ def test_record_without_disturbances_is_no_record(gpu, name, N):
     fresh.close()
 
 
+@pytest.mark.gpu
+def test_the_disturbed_episodes_buffers_grow_after_their_first_use(gpu):
+    """hopper with action noise and a kick every second tick: 3 ticks of one executed row, then 7 ticks of two on the same
+    plan — the log of the executed rows and the tick's normals both grow behind their first use.  Each episode equals the
+    one a fresh plan runs."""
+    from mbd_hip.envs import get_env
+    from mbd_hip.planners.mbd_planner import Plan
+    a = _args("hopper", 256, Nd=12, K=3)
+    env = get_env("hopper")
+    st = env.reset(gpu.prng_key(7))
+    key = gpu.prng_key(8)
+    rec = dict(act_std=0.3, kick_std=0.5, kick_every=2, key=gpu.prng_key(5))
+
+    def plan():
+        p = Plan(env, a)
+        p.set_state0(st)
+        p.set_mpc_plant(**rec)
+        return p
+    grown = plan()
+    episodes = [grown.run_mpc(key, 3, 3, 1), grown.run_mpc(key, 7, 3, 2)]
+    grown.close()
+    for got, (T, E) in zip(episodes, ((3, 1), (7, 2))):
+        fresh = plan()
+        _equal(got, fresh.run_mpc(key, T, 3, E), f"T={T} E={E}")
+        fresh.close()
+        assert got["states"].shape[0] == T + 1 and not np.array_equal(got["actions"][:E], got["means"][0][:E])
+    assert episodes[1]["actions"].size > episodes[0]["actions"].size
+
+
 def _records(gpu, env, P):
     """Three distinct plants in the order A, A, B, none, C, C, A, B: runs of equal handles, a gap, different keys and stds."""
     from mbd_hip.envs.base import RigidBodyEnv
