@@ -3,7 +3,10 @@
  * by NAME from the models embedded in libmbd_hip.so.
  *
  *   gcc -O2 -I include examples/mbd_run.c -o mbd_run -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
- *   ./mbd_run humanoidrun 1024 50 100 0.1 [n_seeds]
+ *   ./mbd_run humanoidrun 1024 50 100 0.1 [n_seeds [tail_peak]]
+ *
+ * tail_peak > 0: every plan samples under a noise shape (mbd_noise_shape) that ramps the noise of the last five horizon rows
+ * up to tail_peak times sigma_i.
  *
  * Prints one line per seed: "seed S rew_final R steps_per_sec X", then (n_seeds > 1) the same seeds as ONE sweep. */
 #include <math.h>
@@ -39,6 +42,7 @@ int main(int argc, char** argv) {
   const int N = argc > 2 ? atoi(argv[2]) : 1024, H = argc > 3 ? atoi(argv[3]) : 50, Nd = argc > 4 ? atoi(argv[4]) : 100;
   const float temp = argc > 5 ? (float)atof(argv[5]) : 0.1f;
   const int n_seeds = argc > 6 ? atoi(argv[6]) : 1;
+  const float tail_peak = argc > 7 ? (float)atof(argv[7]) : 0.0f;
   const int impl = MBD_PRNG_PARTITIONABLE;
   mbd_env* env = NULL;
   CHECK(mbd_env_create(env_name, 0, &env));
@@ -49,6 +53,18 @@ int main(int argc, char** argv) {
   cfg.Nsample = N; cfg.Hsample = H; cfg.Ndiffuse = Nd; cfg.temp_sample = temp;
   cfg.beta0 = 1e-4f; cfg.betaT = 1e-2f; cfg.prng_impl = impl; cfg.shard_begin = 0; cfg.shard_count = N;
   cfg.literal_score = 1;
+  /* the noise shape g [H][Nu]: 1, then a linear ramp over the last R rows up to tail_peak, the same for every actuator */
+  mbd_noise_shape shape;
+  memset(&shape, 0, sizeof(shape));
+  float* g = NULL;
+  if (tail_peak > 0.0f) {
+    const int R = H < 5 ? H : 5;
+    g = (float*)malloc(sizeof(float) * (size_t)H * (size_t)Nu);
+    for (int h = 0; h < H; ++h)
+      for (int a = 0; a < Nu; ++a)
+        g[h * Nu + a] = h < H - R ? 1.0f : (float)(1.0 + ((double)tail_peak - 1.0) * (double)(h - (H - R) + 1) / (double)R);
+    shape.scale = g; shape.rows = H; shape.cols = Nu; shape.when = MBD_NOISE_ALWAYS;
+  }
   float* state = (float*)malloc(sizeof(float) * (size_t)S * (size_t)(n_seeds > 0 ? n_seeds : 1));
   uint32_t* keys = (uint32_t*)malloc(sizeof(uint32_t) * 2 * (size_t)(n_seeds > 0 ? n_seeds : 1));
   for (int seed = 0; seed < n_seeds; ++seed) {
@@ -59,6 +75,7 @@ int main(int argc, char** argv) {
     mbd_plan* plan = NULL;
     CHECK(mbd_plan_create(env, &cfg, &plan));
     CHECK(mbd_plan_set_state0(plan, state + (size_t)seed * S));
+    if (g) CHECK(mbd_plan_set_noise_shape(plan, &shape));
     float rew_final = 0.0f;
     double secs = 0.0;
     CHECK(mbd_plan_run(plan, rng_exp, NULL, NULL, &rew_final, &secs));
@@ -69,6 +86,7 @@ int main(int argc, char** argv) {
     mbd_sweep* sweep = NULL;
     CHECK(mbd_sweep_create(env, &cfg, n_seeds, NULL, &sweep));
     for (int seed = 0; seed < n_seeds; ++seed) CHECK(mbd_sweep_set_state0(sweep, seed, state + (size_t)seed * S));
+    if (g) CHECK(mbd_sweep_set_noise_shape(sweep, &shape));
     float* rews = (float*)malloc(sizeof(float) * (size_t)n_seeds);
     double secs = 0.0;
     CHECK(mbd_sweep_run(sweep, keys, NULL, NULL, rews, &secs));
@@ -79,6 +97,7 @@ int main(int argc, char** argv) {
   }
   free(keys);
   free(state);
+  free(g);
   CHECK(mbd_env_destroy(env));
   return 0;
 }

@@ -478,6 +478,39 @@ int mbd_plan_set_ensemble(mbd_plan* plan, const mbd_ensemble* rec);
  * record, mbd_plan_peek's rewss_out is member 0's. */
 int mbd_plan_peek_ensemble(mbd_plan* plan, float* rews_members_out, float* rews_out);
 
+/* ---- noise shapes: the sampling noise per horizon row and actuator (no counterpart in the reference, whose sigma_i is one
+ * scalar per diffusion step; DESIGN.md section 1 "N7 noise shape") ---- */
+#define MBD_NOISE_ALWAYS     0  /* every diffusion step of every call that samples */
+#define MBD_NOISE_WARM_TICKS 1  /* only the steps of ticks t >= 1 of mbd_plan_run_mpc / mbd_sweep_run_mpc */
+/* A noise shape is a table g [Hsample][action_size] of finite floats >= 0, a setting of a plan (of a sweep) beside the plant
+ * and ensemble records.  With a shape in force, a candidate element of diffusion step i is
+ *   z   = eps[n][h][a] * g[h][a]                   (eps: the normals the plan draws anyway: same key, counters, layout)
+ *   Y0s = clip((z * sigma_i) + Ybar_i[h][a], -1, 1)
+ * three float32 operations, each rounded, no fma; sigma_i is the schedule's, or a path-integral plan's carried sigma.
+ * Everything else of the step is unchanged — the rollout, mean_H, standardisation, softmax, the weighted mean over these same
+ * candidates, the score update, the path-integral updates.  Hence, bit for bit: a table of all ones is no shape at all
+ * (x * 1 = x, -0.0 and NaN included), and a row or column of zeros freezes those elements at clip(Ybar_i).  The table is
+ * applied where the normals are produced, so mbd_plan_peek's Y0s are the shaped candidates; the disturbance normals of a
+ * plant record (mbd_mpc_plant) are never shaped.
+ * MBD_NOISE_WARM_TICKS exists for receding-horizon episodes, whose warm ticks restart at sigma_K: the rows a shift has just
+ * appended get a larger g (a horizon-row schedule), while mbd_plan_run, mbd_sweep_run, the phase calls and tick 0 of an
+ * episode stay flat — tick 0 is still mbd_plan_run(k_0), and an episode of T ticks still a prefix of one of T + 1.  Under
+ * MBD_NOISE_ALWAYS both hold as well, with the shape in both.
+ * Every plan that samples takes a shape: MBD and path-integral updates, rigid-body envs and car2d, sharded plans (every rank
+ * sets the same record: the table is indexed by the global element), plans with a plant or an ensemble record, sweeps.
+ * The set call copies the table, is synchronous (it waits for the device) and discards normals prepared ahead for a key_next
+ * (mbd_plan_prefetch_noise), so no step consumes normals scaled under the previous setting; call it between diffusion steps,
+ * not between the two phases of one.  rec == NULL clears.  Refused with MBD_ERR_INVALID before any device access, the message
+ * naming the field: a NULL handle, non-zero reserved, an unknown when, a NULL scale, rows / cols below 1, a negative or
+ * non-finite scale value, rows != Hsample, cols != action_size. */
+typedef struct mbd_noise_shape {
+  const float* scale;   /* HOST [rows][cols], copied by the set call */
+  int32_t rows, cols;   /* must equal Hsample, action_size */
+  int32_t when;         /* MBD_NOISE_ALWAYS or MBD_NOISE_WARM_TICKS */
+  int32_t reserved[5];  /* must be 0 */
+} mbd_noise_shape;
+int mbd_plan_set_noise_shape(mbd_plan* plan, const mbd_noise_shape* rec);
+
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
  * candidates Y0s [Nsample][H][Nu] (plans that keep normals instead form them here, from the normals, sigma_i and the
  * Ybar_i of the last step — between phase 1 and phase 2 the caller's d_Ybar_i must still be unchanged), the shard's
@@ -535,6 +568,9 @@ int mbd_sweep_run_mpc(mbd_sweep* sweep, const mbd_mpc_config* mc, const uint32_t
  * without records runs exactly the launches described above.  Refusals as mbd_plan_set_mpc_plant's, against the sweep's env;
  * NULL sweep or k outside [0, n_plans) -> MBD_ERR_INVALID before any device access. */
 int mbd_sweep_set_mpc_plant(mbd_sweep* sweep, int k, const mbd_mpc_plant* rec);
+/* one noise shape (mbd_noise_shape, above) for all plans of the sweep: plan k of mbd_sweep_run, episode k of mbd_sweep_run_mpc,
+ * is then the single plan's with the same record, bit for bit.  Refusals as mbd_plan_set_noise_shape's. */
+int mbd_sweep_set_noise_shape(mbd_sweep* sweep, const mbd_noise_shape* rec);
 /* path-integral sweeps: the carried sampling sigma of every plan after the last run (path_integral.py:113,131); HOST [n_plans] */
 int mbd_sweep_get_sigmas(mbd_sweep* sweep, float* sigmas_out);
 /* average milliseconds of the sweep's rollout launches since the last reset (hipEvents on the launch stream) */

@@ -33,6 +33,12 @@ int mbd_debug_set_clock_buffer(mbd_env* env, void* d_buf);
 const char* mbd_debug_math_name(int k);
 int mbd_debug_math_arity(const char* op, int* k_in, int* k_out);
 int mbd_debug_eval_math(const char* op, long long n, const float* in, float* out);
+/* The shaped normals of a diffusion step on their own (include/mbd_hip.h mbd_noise_shape): z_out HOST [N][HNu] =
+ * normal(key, (N, HNu)) * g[e mod HNu] by the loops the noise kernels run with a shape, on `blocks` workgroups of 256 threads,
+ * with 32-bit indices (wide = 0: what the library takes below 2^32 elements) or 64-bit ones (wide = 1: beyond) — so that the
+ * wide form is held to the checker at a size a test can afford.  g HOST [HNu]; N * HNu <= 2^26.  Argument errors first, then
+ * MBD_ERR_NO_DEVICE. */
+int mbd_debug_noise_shaped(const uint32_t key[2], int impl, int N, int HNu, const float* g, int wide, int blocks, float* z_out);
 #ifdef __cplusplus
 }
 #endif

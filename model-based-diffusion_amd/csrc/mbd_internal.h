@@ -172,6 +172,7 @@ struct LazyArgs {
   const float* ybar = nullptr;  // Ybar_i [H][Nu]
   float sigma = 0.0f;
   float* nz_out = nullptr;      // [nz_N][nz_HNu] normals of the next step, or nullptr: no job
+  const float* nz_g = nullptr;  // the noise shape [nz_HNu] that step samples under (device), or nullptr: none
   uint32_t nz_key[2] = {0, 0};
   int nz_impl = 0, nz_N = 0, nz_HNu = 0;
   bool nz_fused = false;        // out: the job went into this launch (false: the caller runs it elsewhere)
@@ -291,6 +292,9 @@ void host_schedule(float beta0, float betaT, int Nd, std::vector<float>& alphas,
 int check_mpc_plant(const mbd_env* env, const mbd_mpc_plant* rec);
 // the refusals of an episode's configuration that plans and sweeps share (include/mbd_hip.h mbd_mpc_config), in their order
 int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc);
+// the refusals of a noise-shape record (include/mbd_hip.h mbd_noise_shape) against a handle's Hsample x action_size, in the
+// header's order, each naming the field — host arithmetic on the record's own table, before any device access
+int check_noise_shape(const mbd_noise_shape* rec, int Hsample, int action_size);
 // One tick of a plant's disturbance chain, dk, d_t = split(dk): advances dk, fills slot k of sp with d_t and the record's
 // deviations — the kick's only in the ticks that end with one — and says whether tick t does
 bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k);

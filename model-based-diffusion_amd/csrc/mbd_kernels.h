@@ -75,6 +75,7 @@ struct RolloutParams {
   // blockIdx.x >= roll_blocks of THIS launch: a rollout of up to ~3000 humanoid candidates leaves most CUs without a
   // workgroup, so the sampler costs no launch, no event and no time on the step's critical path
   float* nz_out;      // [nz_N][nz_HNu] or nullptr
+  const float* nz_g;  // noise shape [nz_HNu] the noise workgroups scale those normals by (mbd_noise_shape), or nullptr: none
   uint32_t nz_k0, nz_k1;
   int nz_impl, nz_N, nz_HNu;
   int roll_blocks;    // workgroups of the rollout proper (the grid may be larger by the noise workgroups)
@@ -310,8 +311,52 @@ __device__ __forceinline__ void dpp_fetch7<1, 0, 0>(v3 p, q4 r, float m0, float,
 // jax.random.normal(key, (N, HNu)) in flat element order, by the threads tid0, tid0 + stride, ...: legacy layout —
 // one threefry block per thread-item, pairing element j with j + half (both outputs used); partitionable layout —
 // one block per element.  Used by noise_kernel and by the noise workgroups of a rollout launch.
+// With a noise shape g [HNu] (include/mbd_hip.h mbd_noise_shape) element e is stored as z = eps * g[e mod HNu], one
+// rounding: every consumer of the buffer then forms clip(z * sigma + Ybar) unchanged.  No division per element: a thread's
+// index advances by the same stride every time, so its residue advances by stride mod HNu with one conditional
+// subtraction (noise_fill_shaped); the divisions left are one per thread (tid0) and two on wave-uniform values.  I is
+// uint32_t when every index the loops form fits 32 bits — every tensor of the library's usual sizes — and uint64_t beyond.
+template <typename I>
+__device__ __forceinline__ void noise_fill_shaped(uint32_t k0, uint32_t k1, int impl, I size, I tid0, I stride,
+                                                  float* __restrict__ eps, const float* __restrict__ g, uint32_t HNu) {
+  const uint32_t step = (uint32_t)(stride % HNu);  // (wave-uniform)
+  auto advance = [&](uint32_t r, uint32_t by) {    // (r + by) mod HNu for r, by < HNu — no overflow: HNu < 2^31
+    r += by;
+    return r >= HNu ? r - HNu : r;
+  };
+  if (impl == 1) {
+    uint32_t r = (uint32_t)(tid0 % HNu);
+    for (I e = tid0; e < size; e += stride) {
+      uint32_t o0, o1;
+      threefry2x32(k0, k1, (uint32_t)((uint64_t)e >> 32), (uint32_t)e, o0, o1);
+      eps[e] = bits_to_normal(o0 ^ o1) * g[r];
+      r = advance(r, step);
+    }
+    return;
+  }
+  const I half = (I)(((uint64_t)size + 1) / 2);
+  uint32_t r0 = (uint32_t)(tid0 % HNu), r1 = advance(r0, (uint32_t)(half % HNu));
+  for (I j0 = tid0; j0 < half; j0 += stride) {
+    const I j1 = j0 + half;
+    uint32_t o0, o1;
+    threefry2x32(k0, k1, (uint32_t)j0, j1 < size ? (uint32_t)j1 : 0u, o0, o1);
+    eps[j0] = bits_to_normal(o0) * g[r0];
+    if (j1 < size) eps[j1] = bits_to_normal(o1) * g[r1];
+    r0 = advance(r0, step);
+    r1 = advance(r1, step);
+  }
+}
 __device__ __forceinline__ void noise_fill(uint32_t k0, uint32_t k1, int impl, uint64_t size, uint64_t tid0,
-                                           uint64_t stride, float* __restrict__ eps) {
+                                           uint64_t stride, float* __restrict__ eps, const float* __restrict__ g = nullptr,
+                                           int HNu = 0) {
+  if (g) {  // (wave-uniform; the loops below, without a shape, are untouched)
+    // 32-bit indices while the largest value a loop forms, below size + stride, fits
+    if (size + stride <= 0xffffffffull)
+      noise_fill_shaped<uint32_t>(k0, k1, impl, (uint32_t)size, (uint32_t)tid0, (uint32_t)stride, eps, g, (uint32_t)HNu);
+    else
+      noise_fill_shaped<uint64_t>(k0, k1, impl, size, tid0, stride, eps, g, (uint32_t)HNu);
+    return;
+  }
   if (impl == 1) {
     for (uint64_t e = tid0; e < size; e += stride) {
       uint32_t o0, o1;
@@ -333,7 +378,7 @@ __device__ __forceinline__ void noise_fill(uint32_t k0, uint32_t k1, int impl, u
 __device__ __forceinline__ void noise_blocks(const RolloutParams& P) {
   const uint64_t nb = gridDim.x - P.roll_blocks;
   noise_fill(P.nz_k0, P.nz_k1, P.nz_impl, (uint64_t)P.nz_N * (uint64_t)P.nz_HNu,
-             (uint64_t)(blockIdx.x - P.roll_blocks) * blockDim.x + threadIdx.x, nb * blockDim.x, P.nz_out);
+             (uint64_t)(blockIdx.x - P.roll_blocks) * blockDim.x + threadIdx.x, nb * blockDim.x, P.nz_out, P.nz_g, P.nz_HNu);
 }
 // Which workgroup of the rollout this one is — or -1: it was a noise workgroup (done) or has nothing to do.  Wave-uniform.
 __device__ __forceinline__ int rollout_block(const RolloutParams& P) {
@@ -342,7 +387,8 @@ __device__ __forceinline__ int rollout_block(const RolloutParams& P) {
     if (r == 0) return q;
     if (P.nz_out)
       noise_fill(P.nz_k0, P.nz_k1, P.nz_impl, (uint64_t)P.nz_N * (uint64_t)P.nz_HNu,
-                 (uint64_t)(q * 7 + r - 1) * blockDim.x + threadIdx.x, (uint64_t)(7 * P.roll_blocks) * blockDim.x, P.nz_out);
+                 (uint64_t)(q * 7 + r - 1) * blockDim.x + threadIdx.x, (uint64_t)(7 * P.roll_blocks) * blockDim.x, P.nz_out,
+                 P.nz_g, P.nz_HNu);
     return -1;
   }
   if ((int)blockIdx.x >= P.roll_blocks) {  // the next step's normals, on CUs the rollout leaves idle

@@ -3,6 +3,7 @@
 // behind them take the rollouts' start state as a parameter), and the loops over steps (mbd_plan_reverse_once, mbd_plan_run,
 // mbd_plan_eval, mbd_plan_peek; the receding-horizon loop mbd_plan_run_mpc).  mbd_planner.py:84-148,179-180.
 #include "mbd_internal.h"
+#include "../../include/mbd_hip_debug.h"
 
 // LAZY plans (the MBD update on a rigid-body env): the candidates are never materialised.  eps[b] holds the normals
 // [N][HNu] of a diffusion step; the rollout's action fetch and the weighted mean form clip(eps sigma_i + Ybar_i)
@@ -21,7 +22,8 @@ struct NoiseRing {
   DevBuf<float> eps[3];
   int cur = 0;                             // buffer of the step in flight (set by sample_rollout, read by score_update / peek)
   uint32_t key[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-  bool valid[3] = {false, false, false};   // eps[b] holds normal(key[b])
+  bool valid[3] = {false, false, false};   // eps[b] holds normal(key[b]) ...
+  const float* shape[3] = {nullptr, nullptr, nullptr};  // ... scaled by this noise shape (the plan's d_shape; nullptr: none)
   bool on_aux[3] = {false, false, false};  // ... generated on the aux stream: the reader checks ev_noise[b] first
   int read_seq[3] = {0, 0, 0};             // sequence number of the last rollout launch that read eps[b]
   PinnedWord progress;
@@ -30,18 +32,25 @@ struct NoiseRing {
   bool wm_mark_valid = false;  // ev_wm was recorded behind the latest weighted mean
   bool kept_in_step = false;   // plan_keep_in_step held the host back for the coming sample_rollout (the queue is NOT draining)
   uint32_t hint_key[2] = {0, 0};  // mbd_plan_prefetch_noise: key of the step after the next sample_rollout
+  const float* hint_g = nullptr;  // ... and the noise shape that step samples under
   bool hint_valid = false;
 
-  // the buffer that holds normal(k), or -1
-  int find(const uint32_t k[2]) const {
+  // the buffer that holds normal(k) under the shape g, or -1
+  int find(const uint32_t k[2], const float* g) const {
     int at = -1;
     for (int b = 0; b < 3; ++b)
-      if (valid[b] && key[b][0] == k[0] && key[b][1] == k[1]) at = b;
+      if (valid[b] && key[b][0] == k[0] && key[b][1] == k[1] && shape[b] == g) at = b;
     return at;
   }
-  void holds(int b, const uint32_t k[2]) {
+  void holds(int b, const uint32_t k[2], const float* g) {
     key[b][0] = k[0]; key[b][1] = k[1];
+    shape[b] = g;
     valid[b] = true;
+  }
+  // nothing prepared ahead survives (mbd_plan_set_noise_shape: the table behind a shape pointer has changed)
+  void forget() {
+    for (int b = 0; b < 3; ++b) valid[b] = false;
+    hint_valid = false;
   }
   // the reader (or the next writer) of a buffer the aux stream filled: no wait on the step's stream when the job has
   // already finished
@@ -54,10 +63,11 @@ struct NoiseRing {
     return MBD_OK;
   }
   // takes the declared key: whether there is one that is not this step's own
-  bool take_hint(const uint32_t step_key[2], uint32_t out[2]) {
+  bool take_hint(const uint32_t step_key[2], uint32_t out[2], const float** g_out) {
     const bool have = hint_valid && !(hint_key[0] == step_key[0] && hint_key[1] == step_key[1]);
     hint_valid = false;
     out[0] = hint_key[0]; out[1] = hint_key[1];
+    *g_out = hint_g;
     return have;
   }
   // Aux-stream generation into eps[b] must start after the last reader of eps[b] — the weighted mean behind rollout launch
@@ -101,7 +111,7 @@ struct mbd_plan {
   hipStream_t last_stream = nullptr;  // stream of the plan's previous phase call (plan_enter orders a change of stream)
   bool last_stream_set = false;
   mbd_plan_config cfg;
-  int HNu = 0;
+  int HNu = 0, Nu = 0;
   std::vector<float> alphas, alphas_bar, sigmas;
   Stream stream;
   // second stream: the non-lazy sharded sampler's other-rank rows, and the next step's normals of lazy plans whose
@@ -136,6 +146,11 @@ struct mbd_plan {
   mbd_ensemble ens_rec{};
   bool has_ens = false, ens_stepped = false;
   DevBuf<float> d_ens_rews, d_ens_rewss, d_ens_comb;
+  // the noise shape (mbd_plan_set_noise_shape): the table g [HNu] on the device and when it is in force.  The samplers take
+  // it as a pointer, nullptr for a flat step (shape_always / shape_warm below decide per loop)
+  DevBuf<float> d_shape;
+  bool has_shape = false;
+  int shape_when = MBD_NOISE_ALWAYS;
   TimingPool timing;
   ~mbd_plan() {  // (streams, events and buffers release themselves, on the env's device)
     if (env) (void)hipSetDevice(env->device);
@@ -185,6 +200,7 @@ extern "C" int mbd_plan_create(mbd_env* env, const mbd_plan_config* cfg, mbd_pla
   p->cfg = *cfg;
   const int N = cfg->Nsample, H = cfg->Hsample, Nu = env->action_size(), Nd = cfg->Ndiffuse, sh = cfg->shard_count;
   p->HNu = H * Nu;
+  p->Nu = Nu;
   host_schedule(cfg->beta0, cfg->betaT, Nd, p->alphas, p->alphas_bar, p->sigmas);
   HIP_TRY(p->stream.create());
   const int K = env->kind == ENV_CAR2D ? 1 : (env->model.n_track > 0 ? env->model.n_track : 1);
@@ -263,10 +279,18 @@ static int ensure_aux(mbd_plan* p) {
   return MBD_OK;
 }
 
-static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], float* out) {
+// The noise shape of the plan's steps (include/mbd_hip.h mbd_noise_shape), as the pointer the samplers take — nullptr: flat.
+// shape_always: every step outside the warm ticks of an episode (the phase calls, mbd_plan_run, tick 0); shape_warm: the
+// steps of the ticks t >= 1 of mbd_plan_run_mpc, where either mode is in force.
+static const float* shape_always(const mbd_plan* p) {
+  return p->has_shape && p->shape_when == MBD_NOISE_ALWAYS ? p->d_shape.get() : nullptr;
+}
+static const float* shape_warm(const mbd_plan* p) { return p->has_shape ? p->d_shape.get() : nullptr; }
+
+static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], float* out, const float* g) {
   const mbd_plan_config& c = p->cfg;
   const unsigned blocks = noise_blocks(c.prng_impl, (uint64_t)c.Nsample * p->HNu, 65536);
-  hipLaunchKernelGGL(noise_kernel, dim3(blocks), dim3(256), 0, st, key[0], key[1], c.prng_impl, c.Nsample, p->HNu, out);
+  hipLaunchKernelGGL(noise_kernel, dim3(blocks), dim3(256), 0, st, key[0], key[1], c.prng_impl, c.Nsample, p->HNu, out, g);
 }
 
 // The normals of a diffusion step depend on its key only, not on the previous step's result.  This call DECLARES the
@@ -275,15 +299,20 @@ static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], flo
 // ~3000 humanoid candidates; no extra launch, no event), on the plan's second stream otherwise — so that the declared
 // step starts without a sampler on its critical path.  A hint: a step whose normals were not prepared (no declaration,
 // another key, a non-lazy plan) generates them on the spot; results are bit-identical either way.
-extern "C" int mbd_plan_prefetch_noise(mbd_plan* p, const uint32_t key_next[2], void* stream_) {
-  (void)stream_;
-  if (!p || !key_next) return fail(MBD_ERR_INVALID, "NULL argument");
+// (g: the noise shape the declared step samples under — a warm tick's first step is declared beside tick 0's last rollout)
+static int declare_next_key(mbd_plan* p, const uint32_t key_next[2], const float* g) {
   const bool off = env_flag("MBD_NO_PREFETCH");
   if (off || !p->lazy) return MBD_OK;
   p->ring.hint_key[0] = key_next[0];
   p->ring.hint_key[1] = key_next[1];
+  p->ring.hint_g = g;
   p->ring.hint_valid = true;
   return MBD_OK;
+}
+extern "C" int mbd_plan_prefetch_noise(mbd_plan* p, const uint32_t key_next[2], void* stream_) {
+  (void)stream_;
+  if (!p || !key_next) return fail(MBD_ERR_INVALID, "NULL argument");
+  return declare_next_key(p, key_next, shape_always(p));
 }
 
 // A plan's phases depend on each other through its buffers (the normals one step's launch prepares are read by the
@@ -303,17 +332,17 @@ static int plan_enter(mbd_plan* p, hipStream_t s) {
 // Step 1 of phase 1, lazy: every rank holds the normals of ALL N candidates (counter-based noise), so that phase 2 needs no
 // second collective and is bit-identical for every shard layout; the candidates themselves are formed at the rollout's
 // action fetch and inside the weighted mean.  The step's normals: ring.cur afterwards.
-static int obtain_normals(mbd_plan* p, const uint32_t key_sample[2], hipStream_t s) {
+static int obtain_normals(mbd_plan* p, const uint32_t key_sample[2], const float* g, hipStream_t s) {
   NoiseRing& ring = p->ring;
-  int cur = ring.find(key_sample);
+  int cur = ring.find(key_sample, g);
   if (cur >= 0) {  // prepared behind the previous rollout
     MBD_TRY(ring.join(cur, s));
   } else {  // not prepared: generate now, into the buffer behind the previous step's (stream order protects it)
     cur = (ring.cur + 1) % 3;
     MBD_TRY(ring.join(cur, s));  // (a stale prefetch may still be writing it)
-    launch_noise(p, s, key_sample, ring.eps[cur]);
+    launch_noise(p, s, key_sample, ring.eps[cur], g);
     HIP_TRY(hipGetLastError());
-    ring.holds(cur, key_sample);
+    ring.holds(cur, key_sample, g);
   }
   ring.cur = cur;
   return MBD_OK;
@@ -322,7 +351,8 @@ static int obtain_normals(mbd_plan* p, const uint32_t key_sample[2], hipStream_t
 // Step 1, materialised (car2d, path-integral updates): every rank samples ALL N candidate sequences.  A sharded plan
 // samples its own rows first and the others' on a second stream, behind the rollout; mbd_plan_score_update joins
 // that stream before it reads them.
-static int sample_candidates(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i, hipStream_t s) {
+static int sample_candidates(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i, const float* g,
+                             hipStream_t s) {
   const mbd_plan_config& c = p->cfg;
   const int N = c.Nsample, HNu = p->HNu;
   const uint64_t total = (uint64_t)N * HNu;
@@ -333,7 +363,7 @@ static int sample_candidates(mbd_plan* p, int i, const uint32_t key_sample[2], c
     hipLaunchKernelGGL(sample_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, key_sample[0],
                        key_sample[1], c.prng_impl, N, HNu, (unsigned long long)e0, (unsigned long long)cnt,
                        p->sigmas[i], c.update_method > 0 ? (const float*)p->d_sigma : (const float*)nullptr,
-                       d_Ybar_i, p->d_Y0s);
+                       d_Ybar_i, p->d_Y0s, g);
   };
   const uint64_t own0 = (uint64_t)c.shard_begin * HNu, own1 = own0 + (uint64_t)c.shard_count * HNu;
   const bool no_aux = env_flag("MBD_NO_AUX");
@@ -369,12 +399,14 @@ static int prepare_noise_job(mbd_plan* p, const uint32_t key_sample[2], hipStrea
   // generated in front of each rollout, where the other plans' rollouts hide them anyway).
   const bool alone = c.shares_device == 0;
   uint32_t declared[2];
-  const bool want = ring.take_hint(key_sample, declared) && alone;
+  const float* declared_g = nullptr;
+  const bool want = ring.take_hint(key_sample, declared, &declared_g) && alone;
   if (!want) return MBD_OK;
   // eps[nxt] was last read two steps ago
   MBD_TRY(ring.join(nxt, s));  // (a stale prefetch of another key: let it finish before it is overwritten)
   ring.valid[nxt] = false;
   lz.nz_out = ring.eps[nxt];
+  lz.nz_g = declared_g;
   lz.nz_key[0] = declared[0]; lz.nz_key[1] = declared[1];
   lz.nz_impl = c.prng_impl; lz.nz_N = c.Nsample; lz.nz_HNu = p->HNu;
   // (launches that take the job into spare workgroups need no second stream and none of its events: a record
@@ -395,18 +427,19 @@ static int finish_noise_job(mbd_plan* p, const LazyArgs& lz, bool marked) {
   if (!lz.nz_fused) {
     MBD_TRY(ensure_aux(p));
     MBD_TRY(ring.aux_waits_for_mark(p->aux, marked));
-    launch_noise(p, p->aux, lz.nz_key, lz.nz_out);
+    launch_noise(p, p->aux, lz.nz_key, lz.nz_out, lz.nz_g);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ring.ev_noise[nxt], p->aux));
     ring.on_aux[nxt] = true;
   }
-  ring.holds(nxt, lz.nz_key);
+  ring.holds(nxt, lz.nz_key, lz.nz_g);
   return MBD_OK;
 }
 
-// phase 1 of a step, from d_state0: the plan's own start state (mbd_plan_sample_rollout), or an episode's executed state
+// phase 1 of a step, from d_state0: the plan's own start state (mbd_plan_sample_rollout), or an episode's executed state;
+// g: the noise shape the step samples under, or nullptr
 static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i, float* d_rews_local,
-                               float* d_logpd_local, hipStream_t s, const float* d_state0) {
+                               float* d_logpd_local, hipStream_t s, const float* d_state0, const float* g) {
   if (!p || !key_sample || !d_Ybar_i || !d_rews_local) return fail(MBD_ERR_INVALID, "NULL argument");
   const mbd_plan_config& c = p->cfg;
   if (i < 1 || i >= c.Ndiffuse) return fail(MBD_ERR_INVALID, "diffusion index %d outside [1,%d)", i, c.Ndiffuse);
@@ -420,14 +453,14 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
   bool marked = false;
   // A1: this step's normals, then the next step's noise job; or this step's candidates
   if (p->lazy) {
-    MBD_TRY(obtain_normals(p, key_sample, s));
+    MBD_TRY(obtain_normals(p, key_sample, g, s));
     p->peek_ybar = d_Ybar_i;  // (the caller keeps it unchanged until phase 2 has run)
     p->sigma_last = p->sigmas[i];
     lz.ybar = d_Ybar_i;
     lz.sigma = p->sigmas[i];
     MBD_TRY(prepare_noise_job(p, key_sample, s, lz, &marked));
   } else {
-    MBD_TRY(sample_candidates(p, i, key_sample, d_Ybar_i, s));
+    MBD_TRY(sample_candidates(p, i, key_sample, d_Ybar_i, g, s));
   }
   // A2/A3: rollout of the local shard
   MBD_TRY(p->timing.begin(s));
@@ -464,7 +497,7 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
 extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
                                        float* d_rews_local, float* d_logpd_local, void* stream_) {
   return plan_sample_rollout(p, i, key_sample, d_Ybar_i, d_rews_local, d_logpd_local, (hipStream_t)stream_,
-                             p ? p->d_state0.get() : nullptr);
+                             p ? p->d_state0.get() : nullptr, p ? shape_always(p) : nullptr);
 }
 
 extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
@@ -566,6 +599,64 @@ extern "C" int mbd_plan_get_sigma(mbd_plan* p, float* sigma_out) {
   return MBD_OK;
 }
 
+// ---- the noise shape (include/mbd_hip.h mbd_noise_shape) ----------------------------------------------------------------
+int check_noise_shape(const mbd_noise_shape* rec, int Hsample, int action_size) {
+  for (int r = 0; r < 5; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "noise shape: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (rec->when != MBD_NOISE_ALWAYS && rec->when != MBD_NOISE_WARM_TICKS)
+    return fail(MBD_ERR_INVALID, "noise shape: when=%d: MBD_NOISE_ALWAYS (0) or MBD_NOISE_WARM_TICKS (1)", rec->when);
+  if (!rec->scale) return fail(MBD_ERR_INVALID, "noise shape: scale is NULL");
+  if (rec->rows < 1) return fail(MBD_ERR_INVALID, "noise shape: rows=%d: must be >= 1", rec->rows);
+  if (rec->cols < 1) return fail(MBD_ERR_INVALID, "noise shape: cols=%d: must be >= 1", rec->cols);
+  const size_t n = (size_t)rec->rows * (size_t)rec->cols;
+  for (size_t e = 0; e < n; ++e)
+    if (!std::isfinite(rec->scale[e]) || rec->scale[e] < 0.0f)
+      return fail(MBD_ERR_INVALID, "noise shape: scale[%d][%d]=%g: must be finite and >= 0", (int)(e / rec->cols), (int)(e % rec->cols),
+                  (double)rec->scale[e]);
+  if (rec->rows != Hsample) return fail(MBD_ERR_INVALID, "noise shape: rows=%d, the handle's Hsample is %d", rec->rows, Hsample);
+  if (rec->cols != action_size) return fail(MBD_ERR_INVALID, "noise shape: cols=%d, the env's action_size is %d", rec->cols, action_size);
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_noise_shape(mbd_plan* p, const mbd_noise_shape* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (rec) MBD_TRY(check_noise_shape(rec, p->cfg.Hsample, p->Nu));
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight, or normals being prepared ahead, may still read the previous table)
+  // Normals prepared ahead were scaled under the previous setting, and the table behind the pointer that tags them is about to
+  // change: the ring forgets them and the declared key, so the next step generates its own under the new setting.
+  p->ring.forget();
+  p->has_shape = false;
+  if (!rec) return MBD_OK;
+  HIP_TRY(p->d_shape.grow(p->HNu));
+  HIP_TRY(hipMemcpy(p->d_shape, rec->scale, sizeof(float) * p->HNu, hipMemcpyHostToDevice));
+  p->shape_when = rec->when;
+  p->has_shape = true;
+  return MBD_OK;
+}
+
+// include/mbd_hip_debug.h: the shaped normals z = normal(key, (N, HNu)) * g of noise_fill's two index widths, on `blocks`
+// workgroups of 256 threads (fewer than the thread-items: the loops stride)
+extern "C" int mbd_debug_noise_shaped(const uint32_t key[2], int impl, int N, int HNu, const float* g, int wide, int blocks,
+                                      float* z_out) {
+  if (!key || !g || !z_out) return fail(MBD_ERR_INVALID, "NULL argument");
+  if (N < 1 || HNu < 1 || blocks < 1 || blocks > 65536 || (uint64_t)N * (uint64_t)HNu > (1ull << 26))
+    return fail(MBD_ERR_INVALID, "noise_shaped: N=%d HNu=%d blocks=%d", N, HNu, blocks);
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  const size_t n = (size_t)N * HNu;
+  DevBuf<float> d_g, d_z;
+  HIP_TRY(d_g.alloc(HNu));
+  HIP_TRY(d_z.alloc(n));
+  HIP_TRY(hipMemcpy(d_g, g, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_z, 0xff, sizeof(float) * n));  // (an element left unwritten reads back as NaN)
+  hipLaunchKernelGGL(noise_shaped_probe_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, key[0], key[1], impl, N, HNu, d_z.get(),
+                     (const float*)d_g, wide);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(z_out, d_z, sizeof(float) * n, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
 // Loops that enqueue step after step (mbd_plan_run): a plan whose next step's normals are generated on the second stream
 // stays ONE step behind the device — it enqueues step q once the rollout of step q-1 has started (the queue still holds
 // that rollout and its score: the device never waits for the host) — so that sample_rollout finds the progress word where
@@ -581,9 +672,11 @@ static int plan_keep_in_step(mbd_plan* p) {
 }
 
 // d_state0: where the step's rollouts start.  key_after: the Y0s_rng of the step that follows the LAST step (i == 1) of
-// this loop in another one (a receding-horizon episode's next tick), or nullptr
+// this loop in another one (a receding-horizon episode's next tick), or nullptr.  g: the noise shape this loop's steps
+// sample under, g_after: the one key_after's step does (nullptr: flat)
 static int reverse_once_impl(mbd_plan* p, const float* d_state0, int i, uint32_t key_inout[2], const float* d_Ybar_in,
-                             float* d_Ybar_out, float* d_rew_mean, hipStream_t s, const uint32_t* key_after = nullptr) {
+                             float* d_Ybar_out, float* d_rew_mean, hipStream_t s, const float* g,
+                             const uint32_t* key_after = nullptr, const float* g_after = nullptr) {
   if (p->cfg.shard_count != p->cfg.Nsample)
     return fail(MBD_ERR_STATE, "reverse_once on a sharded plan: use sample_rollout + all-gather + score_update");
   uint32_t keys[4];
@@ -594,11 +687,11 @@ static int reverse_once_impl(mbd_plan* p, const float* d_state0, int i, uint32_t
     const uint32_t adv[2] = {keys[0], keys[1]};
     host_split(adv, 2, p->cfg.prng_impl, nk);
     const uint32_t next_ks[2] = {nk[2], nk[3]};
-    MBD_TRY(mbd_plan_prefetch_noise(p, next_ks, s));
+    MBD_TRY(declare_next_key(p, next_ks, g));
   } else if (key_after) {
-    MBD_TRY(mbd_plan_prefetch_noise(p, key_after, s));
+    MBD_TRY(declare_next_key(p, key_after, g_after));
   }
-  MBD_TRY(plan_sample_rollout(p, i, ks, d_Ybar_in, p->d_rews, p->cfg.enable_demo ? p->d_lp.get() : nullptr, s, d_state0));
+  MBD_TRY(plan_sample_rollout(p, i, ks, d_Ybar_in, p->d_rews, p->cfg.enable_demo ? p->d_lp.get() : nullptr, s, d_state0, g));
   MBD_TRY(mbd_plan_score_update(p, i, ks, d_Ybar_in, p->d_rews, p->d_lp, d_Ybar_out, d_rew_mean, s));
   key_inout[0] = keys[0];
   key_inout[1] = keys[1];
@@ -610,7 +703,7 @@ extern "C" int mbd_plan_reverse_once(mbd_plan* p, int i, uint32_t key_inout[2], 
   if (!p || !key_inout || !d_Ybar || !d_rew_mean) return fail(MBD_ERR_INVALID, "NULL argument");
   hipStream_t s = (hipStream_t)stream_;
   // the update is not in place on the device (wmean reads Ybar_i while writing Ybar_{i-1})
-  MBD_TRY(reverse_once_impl(p, p->d_state0, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s));
+  MBD_TRY(reverse_once_impl(p, p->d_state0, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s, shape_always(p)));
   HIP_TRY(hipMemcpyAsync(d_Ybar, p->d_Ybar, sizeof(float) * p->HNu, hipMemcpyDeviceToDevice, s));
   return MBD_OK;
 }
@@ -633,7 +726,7 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
   for (int i = Nd - 1; i >= 1; --i) {  // reverse() (mbd_planner.py:138-148)
     float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // Ybars.append(Yi)
     MBD_TRY(plan_keep_in_step(p));
-    MBD_TRY(reverse_once_impl(p, p->d_state0, i, rng, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s));
+    MBD_TRY(reverse_once_impl(p, p->d_state0, i, rng, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, shape_always(p)));
     cur = nxt;
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -902,10 +995,14 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
       host_split(k_next, 2, c.prng_impl, after);
     }
     const float* cur = ybar0;
+    // the noise shape: tick 0 is mbd_plan_run's loop (MBD_NOISE_WARM_TICKS: flat), every later tick samples under the shape
+    // in either mode — the first normals of tick t + 1, prepared beside this tick's last rollout, included
+    const float* g = t == 0 ? shape_always(p) : shape_warm(p);
     for (int i = t == 0 ? Nd - 1 : K; i >= 1; --i) {
       float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
       MBD_TRY(plan_keep_in_step(p));
-      MBD_TRY(reverse_once_impl(p, s_t, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, t + 1 < T ? after + 2 : nullptr));
+      MBD_TRY(reverse_once_impl(p, s_t, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, g, t + 1 < T ? after + 2 : nullptr,
+                                shape_warm(p)));
       cur = nxt;
     }
     // execute M_t's first E rows from s_t, then the boundary: Ybar of tick t+1, the logs of M_t and s_{t+1}

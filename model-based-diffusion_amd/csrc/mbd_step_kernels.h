@@ -82,10 +82,14 @@ static __global__ __launch_bounds__(64) void car2d_rollout_kernel(Car2dParams P)
 // first, the other ranks' rows on a second stream while the rollout runs).  Whole tensor, legacy layout: one
 // thread per threefry block, which pairs element j with j+half (both outputs used).  Otherwise one thread per
 // element (partitionable layout: its own block; legacy layout on a sub-range: the block it belongs to).
+// g: the noise shape [HNu] (include/mbd_hip.h mbd_noise_shape) or nullptr — the normal of element e becomes
+// z = eps * g[e mod HNu], rounded, before the two roundings above (shaped; g is wave-uniform, the index is Ybar's).
+__device__ __forceinline__ float shaped(float eps, const float* __restrict__ g, uint64_t r) { return g ? eps * g[r] : eps; }
 static __global__ __launch_bounds__(256) void sample_kernel(uint32_t k0, uint32_t k1, int impl, int N, int HNu,
                                                       unsigned long long e_begin, unsigned long long e_count,
                                                       float sigma_host, const float* __restrict__ sigma_dev,
-                                                      const float* __restrict__ Ybar, float* __restrict__ Y0s) {
+                                                      const float* __restrict__ Ybar, float* __restrict__ Y0s,
+                                                      const float* __restrict__ g) {
   const float sigma = sigma_dev ? *sigma_dev : sigma_host;  // path-integral plans carry sigma on the device
   const uint64_t size = (uint64_t)N * (uint64_t)HNu;
   const uint64_t half = (size + 1) / 2;
@@ -95,8 +99,9 @@ static __global__ __launch_bounds__(256) void sample_kernel(uint32_t k0, uint32_
     const uint64_t e = e_begin + tid;
     uint32_t o0, o1;
     threefry2x32(k0, k1, (uint32_t)(e >> 32), (uint32_t)e, o0, o1);
-    float eps = bits_to_normal(o0 ^ o1);
-    float y = eps * sigma + Ybar[e % (uint64_t)HNu];
+    const uint64_t r = e % (uint64_t)HNu;
+    float eps = shaped(bits_to_normal(o0 ^ o1), g, r);
+    float y = eps * sigma + Ybar[r];
     Y0s[e] = fclip(y, -1.0f, 1.0f);
     return;
   }
@@ -106,11 +111,13 @@ static __global__ __launch_bounds__(256) void sample_kernel(uint32_t k0, uint32_
     uint32_t o0, o1;
     threefry2x32(k0, k1, (uint32_t)tid, j1 < size ? (uint32_t)j1 : 0u, o0, o1);
     {
-      float y = bits_to_normal(o0) * sigma + Ybar[tid % (uint64_t)HNu];
+      const uint64_t r = tid % (uint64_t)HNu;
+      float y = shaped(bits_to_normal(o0), g, r) * sigma + Ybar[r];
       Y0s[tid] = fclip(y, -1.0f, 1.0f);
     }
     if (j1 < size) {
-      float y = bits_to_normal(o1) * sigma + Ybar[j1 % (uint64_t)HNu];
+      const uint64_t r = j1 % (uint64_t)HNu;
+      float y = shaped(bits_to_normal(o1), g, r) * sigma + Ybar[r];
       Y0s[j1] = fclip(y, -1.0f, 1.0f);
     }
     return;
@@ -120,7 +127,8 @@ static __global__ __launch_bounds__(256) void sample_kernel(uint32_t k0, uint32_
   const uint64_t j0 = e < half ? e : e - half, j1 = j0 + half;
   uint32_t o0, o1;
   threefry2x32(k0, k1, (uint32_t)j0, j1 < size ? (uint32_t)j1 : 0u, o0, o1);
-  float y = bits_to_normal(e < half ? o0 : o1) * sigma + Ybar[e % (uint64_t)HNu];
+  const uint64_t r = e % (uint64_t)HNu;
+  float y = shaped(bits_to_normal(e < half ? o0 : o1), g, r) * sigma + Ybar[r];
   Y0s[e] = fclip(y, -1.0f, 1.0f);
 }
 
@@ -132,10 +140,20 @@ static __global__ __launch_bounds__(256) void sample_kernel(uint32_t k0, uint32_
 //   shift_kernel  Y0s[e] = clip(eps[e] * sigma + Ybar[e mod HNu], -1, 1) — the same two roundings as sample_kernel;
 //                 lazy plans form these values at the rollout's action fetch and inside the weighted mean instead, and
 //                 run this kernel only when somebody asks for Y0s (mbd_plan_peek)
+// (g: the noise shape or nullptr — noise_fill then stores z = eps * g[e mod HNu] and everything downstream is unchanged)
 static __global__ __launch_bounds__(256) void noise_kernel(uint32_t k0, uint32_t k1, int impl, int N, int HNu,
-                                                     float* __restrict__ eps) {
+                                                     float* __restrict__ eps, const float* __restrict__ g) {
   noise_fill(k0, k1, impl, (uint64_t)N * (uint64_t)HNu, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x,
-             (uint64_t)gridDim.x * blockDim.x, eps);
+             (uint64_t)gridDim.x * blockDim.x, eps, g, HNu);
+}
+// noise_fill's shaped loops with the index type chosen by the caller (mbd_debug_noise_shaped: the 64-bit instantiation, which
+// the library itself takes only beyond 2^32 elements, held to the checker at a size a test can afford)
+static __global__ __launch_bounds__(256) void noise_shaped_probe_kernel(uint32_t k0, uint32_t k1, int impl, int N, int HNu,
+                                                                  float* __restrict__ eps, const float* __restrict__ g, int wide) {
+  const uint64_t size = (uint64_t)N * (uint64_t)HNu, tid0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  if (wide) noise_fill_shaped<uint64_t>(k0, k1, impl, size, tid0, stride, eps, g, (uint32_t)HNu);
+  else noise_fill_shaped<uint32_t>(k0, k1, impl, (uint32_t)size, (uint32_t)tid0, (uint32_t)stride, eps, g, (uint32_t)HNu);
 }
 static __global__ __launch_bounds__(256) void shift_kernel(const float* __restrict__ eps, int HNu, unsigned long long e_begin,
                                                      unsigned long long e_count, float sigma_host,
@@ -745,10 +763,12 @@ static __global__ __launch_bounds__(kWmE * kWmG, V == 1 ? 8 : 4) void score_wmea
 struct SweepKeys {
   uint32_t k[32][2];
 };
-static __global__ __launch_bounds__(256) void noise_batch_kernel(SweepKeys keys, int impl, int N, int HNu, float* __restrict__ eps) {
+// (g: the sweep's noise shape [HNu], one for all plans, or nullptr)
+static __global__ __launch_bounds__(256) void noise_batch_kernel(SweepKeys keys, int impl, int N, int HNu, float* __restrict__ eps,
+                                                           const float* __restrict__ g) {
   const uint64_t size = (uint64_t)N * (uint64_t)HNu;
   noise_fill(keys.k[blockIdx.y][0], keys.k[blockIdx.y][1], impl, size, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x,
-             (uint64_t)gridDim.x * blockDim.x, eps + (uint64_t)blockIdx.y * size);
+             (uint64_t)gridDim.x * blockDim.x, eps + (uint64_t)blockIdx.y * size, g, HNu);
 }
 
 // ---- the plant of a receding-horizon episode (include/mbd_hip.h mbd_mpc_plant): disturbances drawn and applied on the device ----
@@ -761,7 +781,8 @@ struct SweepPlant {
   unsigned char has[32];
 };
 // One workgroup per episode, behind the tick's last weighted mean: eps = normal(d_t, (EN + 3,)) by noise_fill (the counters
-// and layouts of every other normal of the library: bit-exact to the checker's), then the executed rows
+// and layouts of every other normal of the library: bit-exact to the checker's; never shaped — a noise shape is the
+// planner's exploration, the disturbances are the world's), then the executed rows
 // rows[e] = M[e] + act_std * eps[e] — product and sum rounded separately, like every float32 expression of the library: the build
 // compiles with -ffp-contract=off (the checker is numpy float32; the ISA shows v_mul_f32, then v_add_f32) — or M[e] itself where
 // act_std == 0 (a copy: -0.0 stays -0.0), and the three kick values kick_std * eps[EN ..].  EN = E * Nu; M of episode k is M_stride floats further; eps [P][EN + 3] is scratch.
@@ -791,11 +812,12 @@ static __global__ __launch_bounds__(64) void mpc_kick_batch_kernel(SweepPlant pl
 }
 
 // the materialised candidates of P path-integral plans in one launch (blockIdx.y = plan; grid-stride over the thread-items
-// of sample_kernel's whole-tensor forms — same counters, same two roundings): Y0s[k] = clip(eps_k * sigma[k] + mu[k], -1, 1)
+// of sample_kernel's whole-tensor forms — same counters, same two roundings): Y0s[k] = clip(eps_k * sigma[k] + mu[k], -1, 1);
+// g: the sweep's noise shape or nullptr (sample_kernel's `shaped`)
 static __global__ __launch_bounds__(256) void sample_batch_kernel(SweepKeys keys, int impl, int N, int HNu,
                                                             const float* __restrict__ sigma_dev /* [P] */,
                                                             const float* __restrict__ mu, long long mu_stride,
-                                                            float* __restrict__ Y0s) {
+                                                            float* __restrict__ Y0s, const float* __restrict__ g) {
   const long long plan = blockIdx.y;
   const uint32_t k0 = keys.k[plan][0], k1 = keys.k[plan][1];
   const float sigma = sigma_dev[plan];
@@ -808,15 +830,18 @@ static __global__ __launch_bounds__(256) void sample_batch_kernel(SweepKeys keys
     uint32_t o0, o1;
     if (impl == 1) {
       threefry2x32(k0, k1, (uint32_t)(tid >> 32), (uint32_t)tid, o0, o1);
-      const float y = bits_to_normal(o0 ^ o1) * sigma + Ybar[tid % (uint64_t)HNu];
+      const uint64_t r = tid % (uint64_t)HNu;
+      const float y = shaped(bits_to_normal(o0 ^ o1), g, r) * sigma + Ybar[r];
       out[tid] = fclip(y, -1.0f, 1.0f);
     } else {
       const uint64_t j1 = tid + half;
       threefry2x32(k0, k1, (uint32_t)tid, j1 < size ? (uint32_t)j1 : 0u, o0, o1);
-      const float y0 = bits_to_normal(o0) * sigma + Ybar[tid % (uint64_t)HNu];
+      const uint64_t r0 = tid % (uint64_t)HNu;
+      const float y0 = shaped(bits_to_normal(o0), g, r0) * sigma + Ybar[r0];
       out[tid] = fclip(y0, -1.0f, 1.0f);
       if (j1 < size) {
-        const float y1 = bits_to_normal(o1) * sigma + Ybar[j1 % (uint64_t)HNu];
+        const uint64_t r1 = j1 % (uint64_t)HNu;
+        const float y1 = shaped(bits_to_normal(o1), g, r1) * sigma + Ybar[r1];
         out[j1] = fclip(y1, -1.0f, 1.0f);
       }
     }

@@ -27,7 +27,7 @@ void launch_score_wmean_batch(int V, int HNu, int P, size_t lds, hipStream_t s, 
 struct mbd_sweep {
   mbd_env* env = nullptr;
   mbd_plan_config cfg;
-  int P = 0, HNu = 0;
+  int P = 0, HNu = 0, Nu = 0;
   std::vector<float> temps, alphas, alphas_bar, sigmas;
   Stream stream, aux;
   // The normals of a step live in a ring of THREE buffers, so that the stream of the steps carries no event at all: the
@@ -54,6 +54,12 @@ struct mbd_sweep {
   mbd_mpc_plant plant_rec[MBD_SWEEP_MAX_PLANS] = {};
   bool has_plant[MBD_SWEEP_MAX_PLANS] = {};
   DevBuf<float> d_mpc_actions, d_plant_eps, d_plant_kick;
+  // the noise shape of all the sweep's plans (mbd_sweep_set_noise_shape): a plan's, with the same two accessors
+  DevBuf<float> d_shape;
+  bool has_shape = false;
+  int shape_when = MBD_NOISE_ALWAYS;
+  const float* shape_always() const { return has_shape && shape_when == MBD_NOISE_ALWAYS ? d_shape.get() : nullptr; }
+  const float* shape_warm() const { return has_shape ? d_shape.get() : nullptr; }
   TimingPool timing;
   ~mbd_sweep() {  // (streams, events and buffers release themselves, on the env's device)
     if (env) (void)hipSetDevice(env->device);
@@ -78,6 +84,7 @@ extern "C" int mbd_sweep_create(mbd_env* env, const mbd_plan_config* cfg, int n_
   w->env = env; w->cfg = *cfg; w->P = n_plans;
   const int N = cfg->Nsample, H = cfg->Hsample, Nu = env->action_size(), Nd = cfg->Ndiffuse, P = n_plans;
   w->HNu = H * Nu;
+  w->Nu = Nu;
   w->temps.assign(P, cfg->temp_sample);
   if (temps) for (int k = 0; k < P; ++k) w->temps[k] = temps[k];
   host_schedule(cfg->beta0, cfg->betaT, Nd, w->alphas, w->alphas_bar, w->sigmas);
@@ -189,7 +196,7 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
     const long long mu_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
     float* mu_out = w->d_mu + (size_t)step * HNu;
     hipLaunchKernelGGL(sample_batch_kernel, dim3(nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
-                       (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s);
+                       (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s, w->shape_always());
     HIP_TRY(hipGetLastError());
     MBD_TRY(w->timing.begin(s));
     const int sw[3] = {N, S, 0};
@@ -245,15 +252,16 @@ struct SweepStep {
   const float* ybar_in;        // Ybar_i of plan 0; plan k's is ybar_in_stride floats further
   long long ybar_in_stride;
   const SweepKeys* next_keys;  // Y0s_rng of the loop's following step (its normals go beside this rollout), or nullptr: none follows
+  const float* next_g;         // the noise shape that following step samples under, or nullptr: flat
 };
 
 // the normals of a step depend on its keys only: they are generated on the second stream while the previous step's
 // rollout runs (a ring of three buffers, see mbd_sweep), like a single large plan's
-void sweep_noise(mbd_sweep* w, const SweepKeys& sk, int buf, hipStream_t st) {
+void sweep_noise(mbd_sweep* w, const SweepKeys& sk, int buf, hipStream_t st, const float* g) {
   const mbd_plan_config& c = w->cfg;
   const unsigned nblocks = noise_blocks(c.prng_impl, (uint64_t)c.Nsample * w->HNu, 4096);
   hipLaunchKernelGGL(noise_batch_kernel, dim3(nblocks, (unsigned)w->P), dim3(256), 0, st, sk, c.prng_impl, c.Nsample, w->HNu,
-                     w->d_eps[buf]);
+                     w->d_eps[buf], g);
 }
 
 // rng, Y0s_rng = split(rng) of every plan (mbd_planner.py:103) — the whole key chain is host arithmetic
@@ -288,7 +296,7 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
       HIP_TRY(hipEventRecord(w->ev_order, s));
       HIP_TRY(hipStreamWaitEvent(w->aux, w->ev_order, 0));
     }
-    sweep_noise(w, *st.next_keys, nxt, w->aux);
+    sweep_noise(w, *st.next_keys, nxt, w->aux, st.next_g);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(w->ev_ready[nxt], w->aux));
   }
@@ -333,7 +341,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
   auto t0 = std::chrono::steady_clock::now();
   SweepKeys sk;
   sweep_split_keys(w, rng, sk);
-  sweep_noise(w, sk, 0, s);  // step Nd-1
+  sweep_noise(w, sk, 0, s, w->shape_always());  // step Nd-1
   HIP_TRY(hipGetLastError());
   for (int i = Nd - 1, step = 0; i >= 1; --i, ++step) {
     if (i > 1) sweep_split_keys(w, rng, sk);
@@ -342,12 +350,29 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
     st.ybar_in = step == 0 ? w->d_zero : w->d_mu + (size_t)(step - 1) * HNu;
     st.ybar_in_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
     st.next_keys = i > 1 ? &sk : nullptr;
+    st.next_g = w->shape_always();
     MBD_TRY(sweep_step(w, st));
   }
   HIP_TRY(hipStreamSynchronize(s));
   auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
   return sweep_results(w, mu_0ts_out, rew_means_out, rew_final_out);
+}
+
+// one noise shape for all plans of the sweep (include/mbd_hip.h mbd_noise_shape).  A sweep prepares nothing across run calls:
+// every run generates its first normals itself, so there is nothing to discard beyond waiting for the device.
+extern "C" int mbd_sweep_set_noise_shape(mbd_sweep* w, const mbd_noise_shape* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (rec) MBD_TRY(check_noise_shape(rec, w->cfg.Hsample, w->Nu));
+  HIP_TRY(hipSetDevice(w->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  w->has_shape = false;
+  if (!rec) return MBD_OK;
+  HIP_TRY(w->d_shape.grow(w->HNu));
+  HIP_TRY(hipMemcpy(w->d_shape, rec->scale, sizeof(float) * w->HNu, hipMemcpyHostToDevice));
+  w->shape_when = rec->when;
+  w->has_shape = true;
+  return MBD_OK;
 }
 
 extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant* rec) {
@@ -423,7 +448,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     sweep_split_keys(w, r, sk);
   };
   first_keys_of_tick();
-  sweep_noise(w, sk, 0, s);  // tick 0, step Nd-1
+  sweep_noise(w, sk, 0, s, w->shape_always());  // tick 0, step Nd-1
   HIP_TRY(hipGetLastError());
   const long long mu_stride = (long long)(Nd - 1) * HNu;
   const int exec_sw[3] = {1, S, 0};
@@ -440,6 +465,8 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       st.ybar_in = i == i_start ? (t == 0 ? w->d_zero : w->d_mpc_ybar) : w->d_mu + (size_t)(st.slot - 1) * HNu;
       st.ybar_in_stride = i == i_start ? HNu : mu_stride;
       st.next_keys = follows ? &sk : nullptr;
+      // (the noise shape of the following step: this tick's, or — behind a tick's last step — a warm tick's, mbd_plan_run_mpc)
+      st.next_g = (t == 0 && i > 1) ? w->shape_always() : w->shape_warm();
       MBD_TRY(sweep_step(w, st));
     }
     // the boundary: the logs of M_{.,t}, its first E rows and Ybar of tick t+1; then the rows executed from s_{.,t}

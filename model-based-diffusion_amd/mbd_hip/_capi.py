@@ -56,15 +56,25 @@ class Ensemble(C.Structure):
                 ("reserved", C.c_int32 * 6)]
 
 
+NOISE_ALWAYS, NOISE_WARM_TICKS = 0, 1
+NOISE_WHEN = {"always": NOISE_ALWAYS, "warm": NOISE_WARM_TICKS}
+
+
+class NoiseShape(C.Structure):
+    """mbd_noise_shape (include/mbd_hip.h): the table g [Hsample][action_size] the sampling noise is scaled by, and when."""
+    _fields_ = [("scale", C.POINTER(C.c_float)), ("rows", C.c_int32), ("cols", C.c_int32), ("when", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
 EXPORTS = [
     "mbd_last_error", "mbd_version", "mbd_tuned_spec", "mbd_device_count", "mbd_prng_key", "mbd_prng_split",
     "mbd_env_create", "mbd_env_name", "mbd_builtin_model", "mbd_env_get_model", "mbd_env_xref", "mbd_env_xref_logpd",
     "mbd_env_observe", "mbd_model_observe", "mbd_model_forward", "mbd_env_create_car2d", "mbd_env_create_model", "mbd_env_destroy", "mbd_env_info", "mbd_env_reset", "mbd_env_pipeline_init",
     "mbd_env_step", "mbd_env_rew_xref", "mbd_env_rollout", "mbd_plan_create", "mbd_plan_destroy",
     "mbd_plan_schedule", "mbd_plan_set_state0", "mbd_plan_sample_rollout", "mbd_plan_prefetch_noise", "mbd_plan_score_update",
-    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
+    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
-    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
+    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_set_noise_shape", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
     "mbd_exchange_create", "mbd_exchange_destroy", "mbd_exchange_local_handle", "mbd_exchange_connect",
     "mbd_exchange_all_gather", "mbd_exchange_status", "mbd_exchange_fine_grained",
 ]
@@ -130,6 +140,7 @@ def load() -> C.CDLL:
     lib.mbd_plan_set_mpc_plant.argtypes = [_vp, C.POINTER(MpcPlant)]
     lib.mbd_plan_set_ensemble.argtypes = [_vp, C.POINTER(Ensemble)]
     lib.mbd_plan_peek_ensemble.argtypes = [_vp, _vp, _vp]
+    lib.mbd_plan_set_noise_shape.argtypes = [_vp, C.POINTER(NoiseShape)]
     lib.mbd_plan_eval.argtypes = [_vp, _vp, _fp]
     lib.mbd_plan_peek.argtypes = [_vp, _vp, _vp, _vp]
     lib.mbd_plan_kernel_time.argtypes = [_vp, _fp, C.POINTER(_i), _i]
@@ -140,6 +151,7 @@ def load() -> C.CDLL:
     lib.mbd_sweep_run.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]
     lib.mbd_sweep_run_mpc.argtypes = [_vp, C.POINTER(MpcConfig), _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]
     lib.mbd_sweep_set_mpc_plant.argtypes = [_vp, _i, C.POINTER(MpcPlant)]
+    lib.mbd_sweep_set_noise_shape.argtypes = [_vp, C.POINTER(NoiseShape)]
     lib.mbd_sweep_kernel_time.argtypes = [_vp, _i, _fp, C.POINTER(_i)]
     lib.mbd_sweep_get_sigmas.argtypes = [_vp, _vp]
     lib.mbd_exchange_create.argtypes = [_i, _i, _i, _i, _i, C.POINTER(_vp)]
@@ -183,6 +195,17 @@ def debug_rollout_choice(model, n_cus: int, B: int, H: int, sweep_plan_N: int = 
     check(lib.mbd_debug_rollout_choice(C.byref(model), n_cus, B, H, sweep_plan_N, int(has_xref), name, 512, out))
     keys = ("grid", "block", "lds", "cpw", "wpe", "xcd_pin", "fuses_noise", "fuses_logpd")
     return dict(zip(keys, list(out)), name=name.value.decode())
+
+
+def debug_noise_shaped(key, impl: int, N: int, HNu: int, g, wide: bool, blocks: int) -> np.ndarray:
+    """include/mbd_hip_debug.h: z [N, HNu] = normal(key, (N, HNu)) * g by the noise kernels' shaped loops, with 32-bit
+    (``wide`` False) or 64-bit indices, on ``blocks`` workgroups."""
+    lib = load()
+    lib.mbd_debug_noise_shaped.argtypes = [_u32p, _i, _i, _i, _vp, _i, _i, _vp]
+    g = np.ascontiguousarray(g, np.float32).reshape(HNu)
+    out = np.empty((N, HNu), np.float32)
+    check(lib.mbd_debug_noise_shaped(key_array(key), impl, N, HNu, np_ptr(g), int(wide), blocks, np_ptr(out)))
+    return out
 
 
 def debug_math_ops() -> list:

@@ -135,6 +135,16 @@ class Sweep:
         _capi.check(self.lib.mbd_sweep_set_mpc_plant(self.h, int(k), None))
         self._plant_envs.pop(int(k), None)
 
+    def set_noise_shape(self, scale, when: str = "always"):
+        """One noise shape for all plans of the sweep (``Plan.set_noise_shape``): plan k of ``run``, episode k of ``run_mpc``,
+        is then the single plan's with the same shape, bit for bit."""
+        rec, keep = _noise_record(scale, when, self.H, self.Nu)
+        _capi.check(self.lib.mbd_sweep_set_noise_shape(self.h, C.byref(rec)))
+        del keep  # (the set call has copied the table)
+
+    def clear_noise_shape(self):
+        _capi.check(self.lib.mbd_sweep_set_noise_shape(self.h, None))
+
     def get_sigmas(self):
         """path-integral sweeps: every plan's carried sigma after the last run (path_integral.py:113,131)."""
         out = np.zeros(self.P, np.float32)
@@ -166,6 +176,21 @@ def _plant_record(env, key, act_std, kick_std, kick_every):
     rec.key[0], rec.key[1] = int(k[0]), int(k[1])
     rec.act_std, rec.kick_std, rec.kick_every = float(act_std), float(kick_std), int(kick_every)
     return rec
+
+
+def _noise_record(scale, when, H, Nu):
+    """The mbd_noise_shape of ``set_noise_shape``'s arguments, and the float32 array its pointer reads (``scale`` [H, Nu], or
+    anything that broadcasts to it: a column [H, 1] is a horizon-row schedule, a row [Nu] a per-actuator one)."""
+    if when not in _capi.NOISE_WHEN:
+        raise ValueError(f"when={when!r}: one of {sorted(_capi.NOISE_WHEN)}")
+    g = np.asarray(scale, np.float32)
+    if g.ndim < 2 or g.shape[-2:] != (H, Nu):  # (a full table of another size goes to the library, which names the field)
+        g = np.broadcast_to(g, (H, Nu))
+    g = np.ascontiguousarray(g, np.float32)
+    rec = _capi.NoiseShape()
+    rec.scale = g.ctypes.data_as(C.POINTER(C.c_float))
+    rec.rows, rec.cols, rec.when = g.shape[0], g.shape[1], _capi.NOISE_WHEN[when]
+    return rec, g
 
 
 def _ensemble_record(envs, risk):
@@ -280,6 +305,19 @@ class Plan:
     def clear_ensemble(self):
         _capi.check(self.lib.mbd_plan_set_ensemble(self.h, None))
         self._ens_envs = None
+
+    def set_noise_shape(self, scale, when: str = "always"):
+        """Shape the sampling noise per horizon row and actuator (include/mbd_hip.h mbd_noise_shape): ``scale`` [H, Nu] (or
+        anything that broadcasts to it) of finite values >= 0; a candidate is clip((eps * scale) * sigma_i + Ybar_i).
+        ``when``: "always" — every diffusion step of every call that samples — or "warm": only the ticks t >= 1 of
+        ``run_mpc`` (``mpc.tail_shape`` gives the rows a warm tick has just appended the noise a cold plan starts with).  All
+        ones is no shape, bit for bit; zeros freeze their elements at clip(Ybar_i)."""
+        rec, keep = _noise_record(scale, when, self.H, self.Nu)
+        _capi.check(self.lib.mbd_plan_set_noise_shape(self.h, C.byref(rec)))
+        del keep  # (the set call has copied the table)
+
+    def clear_noise_shape(self):
+        _capi.check(self.lib.mbd_plan_set_noise_shape(self.h, None))
 
     def peek_ensemble(self):
         """The last step's per-member rewards [M, N] and combined rewards [N] (a plan with an ensemble record)."""

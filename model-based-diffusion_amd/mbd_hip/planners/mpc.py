@@ -28,6 +28,15 @@ mean — ``--ens_risk min``: its worst — return over the members.  Single epis
 mismatch and disturbances cost that planner, not what the ensemble buys.
 
     python -m mbd_hip.planners.mpc --env_name hopper --plant_mass 1.25 --ens_mass 0.8,1,1.25,1.5 --ens_risk min
+
+A warm tick restarts every row of the shifted mean at one sigma_K — the rows the shift has just appended, never optimised,
+as much as the head rows refined over many ticks.  A noise shape (include/mbd_hip.h mbd_noise_shape; DESIGN.md section 1 "N7
+noise shape") scales the sampling noise per horizon row and actuator: ``--tail_rows R --tail_sigma S`` ramp the last R rows
+up to S times sigma_K (``tail_shape``) in the ticks t >= 1 only, so tick 0 stays ``run_diffusion``'s plan;
+``--noise_shape FILE.npy`` loads a table [Hsample, Nu] (or anything that broadcasts to it, e.g. one value per actuator) that
+is in force in every step, tick 0 included.  One or the other; a batch of episodes shares it.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --tail_rows 5 --tail_sigma 4
 """
 from __future__ import annotations
 
@@ -60,6 +69,9 @@ class MpcArgs(Args):
     ens_friction: str = ""  # ... their contact friction
     ens_gear: str = ""  # ... their actuator gears (the three lists are zipped; a single value broadcasts)
     ens_risk: str = "mean"  # a candidate's reward over the members: "mean" or "min"
+    tail_rows: int = 0  # the last tail_rows horizon rows of every warm tick (t >= 1) sample with more noise ...
+    tail_sigma: float = 1.0  # ... ramping up to tail_sigma times sigma_K at the last row (tail_shape)
+    noise_shape: str = ""  # FILE.npy: a noise shape [Hsample, Nu] (or what broadcasts to it) in force in every step
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -110,6 +122,43 @@ def _ensemble_settings(args: MpcArgs) -> dict:
     return dict(ensemble=[dict(mass=t[0], friction=t[1], gear=t[2]) for t in ensemble_triples(args)], ens_risk=args.ens_risk)
 
 
+_SHAPE_FIELDS = ("tail_rows", "tail_sigma", "noise_shape")
+
+
+def tail_shape(H: int, Nu: int, rows: int, peak: float) -> np.ndarray:
+    """The noise shape [H, Nu] of a warm replan: 1 for the rows h < H - rows, then the linear ramp
+    1 + (peak - 1) (h - (H - rows) + 1) / rows up to ``peak`` at the last row — computed in float64, cast once to float32,
+    the same for every actuator.  (With the default betas, Ndiffuse = 100 and warm_steps = 20, sigma_99 / sigma_20 = 4.2: a
+    peak near 4 gives the last row the noise a cold plan starts with.)"""
+    H, Nu, rows = int(H), int(Nu), int(rows)
+    if not 0 <= rows <= H:
+        raise ValueError(f"tail_rows={rows} outside [0, Hsample={H}]")
+    if not (np.isfinite(peak) and peak >= 0):
+        raise ValueError(f"tail_sigma={peak!r}: must be finite and >= 0")
+    g = np.ones(H, np.float64)
+    h = np.arange(H - rows, H, dtype=np.float64)
+    g[H - rows:] = 1.0 + (float(peak) - 1.0) * (h - (H - rows) + 1.0) / max(rows, 1)
+    return np.ascontiguousarray(np.broadcast_to(g.astype(np.float32)[:, None], (H, Nu)))
+
+
+def _has_shape(args: MpcArgs) -> bool:
+    """Whether the arguments ask for a noise shape at all (every default: none is set)."""
+    return args.tail_rows != 0 or bool(args.noise_shape)
+
+
+def _shape_of(args: MpcArgs, Nu: int):
+    """(scale, when) of the arguments' noise shape: the tail ramp in the warm ticks, or the file's table in every step."""
+    if args.tail_rows != 0 and args.noise_shape:
+        raise ValueError("tail_rows and noise_shape both given: a plan has one noise shape")
+    if args.noise_shape:
+        return np.load(args.noise_shape), "always"
+    return tail_shape(args.Hsample, Nu, args.tail_rows, args.tail_sigma), "warm"
+
+
+def _shape_settings(args: MpcArgs) -> dict:
+    return {f: getattr(args, f) for f in _SHAPE_FIELDS}
+
+
 def _plant_env(env, args: MpcArgs, device: int, cache: dict = None):
     """The env that executes the rows: None (the planner's own) unless mass / friction / gear differ from 1; one env per
     distinct triple in ``cache``."""
@@ -153,6 +202,8 @@ def _setup(args: MpcArgs, device: int):
         plan.set_mpc_plant(**_record_kwargs(env, args, device, cache))
     if _has_ensemble(args):
         plan.set_ensemble(_ensemble_envs(env, args, device, cache), args.ens_risk)
+    if _has_shape(args):
+        plan.set_noise_shape(*_shape_of(args, env.action_size))
     return env, plan, state_init, rng_exp
 
 
@@ -175,6 +226,8 @@ def _check_batch(arg_list) -> None:
             if f not in ("seed", "temp_sample", "not_render") + _PLANT_FIELDS and v != ds[0][f]:
                 raise ValueError(f"{f} differs between episodes 0 and {k} ({ds[0][f]!r}, {v!r}): the episodes of a batch "
                                  "may differ in seed, temp_sample and the plant settings only")
+    if _has_shape(arg_list[0]) and arg_list[0].tail_rows != 0 and arg_list[0].noise_shape:
+        raise ValueError("tail_rows and noise_shape both given: a sweep has one noise shape")
     if ds[0]["env_name"] in ("car2d", "pushT"):
         raise ValueError(f"env_name={ds[0]['env_name']!r}: batches run rigid-body envs; run its episodes one by one")
     if ds[0]["Nsample"] * 4 > 48 * 1024:
@@ -190,6 +243,8 @@ def _setup_batch(arg_list, device: int):
     a0 = arg_list[0]
     env = get_env(a0.env_name, device=device)
     sweep = Sweep(env, a0, len(arg_list), temps=[a.temp_sample for a in arg_list])
+    if _has_shape(a0):  # (one shape for all episodes: _check_batch has held the three fields equal)
+        sweep.set_noise_shape(*_shape_of(a0, env.action_size))
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -222,8 +277,9 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
     if not arg_list[0].not_render:
         _save(arg_list[0], ep if len(arg_list) > 1 else {k: ep[k][0] for k in _LOGS})
     if return_details:
+        shape = _shape_settings(arg_list[0]) if _has_shape(arg_list[0]) else {}
         return rewards, [dict({f: ep[f][k] for f in _LOGS}, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
-                              **_plant_settings(arg_list[k])) for k in range(len(arg_list))]
+                              **_plant_settings(arg_list[k]), **shape) for k in range(len(arg_list))]
     return rewards
 
 
@@ -249,7 +305,8 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         _save(args, ep)
     if return_details:
         ens = _ensemble_settings(args) if _has_ensemble(args) else {}
-        return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens)
+        shape = _shape_settings(args) if _has_shape(args) else {}
+        return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
 
@@ -297,6 +354,8 @@ def _main(argv=None) -> dict:
         res.update(_plant_settings(args), nominal_episode_reward=nominal)
     if _has_ensemble(args):
         res.update(_ensemble_settings(args))
+    if _has_shape(args):
+        res.update(_shape_settings(args))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -330,6 +389,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
         plan.set_state0(states[0])
         if _has_plant(a0):
             plan.set_mpc_plant(**_record_kwargs(env, a0, 0))
+        if _has_shape(a0):
+            plan.set_noise_shape(*_shape_of(a0, env.action_size))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -350,6 +411,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
                speedup=P * seq["seconds"] / secs, open_loop_ratio=P * open_ms_1 / open_ms)
     if nominal is not None:  # (without records the line is what it always was)
         res.update(_plant_settings(a0), nominal_episode_reward=float(np.mean(nominal)))
+    if _has_shape(a0):
+        res.update(_shape_settings(a0))
     if not a0.not_render:
         _save(a0, ep)
     print(json.dumps(res), flush=True)
