@@ -3,10 +3,12 @@
  * by NAME from the models embedded in libmbd_hip.so.
  *
  *   gcc -O2 -I include examples/mbd_run.c -o mbd_run -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
- *   ./mbd_run humanoidrun 1024 50 100 0.1 [n_seeds [tail_peak]]
+ *   ./mbd_run humanoidrun 1024 50 100 0.1 [n_seeds [tail_peak [hold_knots]]]
  *
  * tail_peak > 0: every plan samples under a noise shape (mbd_noise_shape) that ramps the noise of the last five horizon rows
  * up to tail_peak times sigma_i.
+ * hold_knots in [1, 16]: every plan samples under a noise basis (mbd_noise_basis) that draws hold_knots normals per candidate and
+ * actuator and holds each for H / hold_knots horizon rows.
  *
  * Prints one line per seed: "seed S rew_final R steps_per_sec X", then (n_seeds > 1) the same seeds as ONE sweep. */
 #include <math.h>
@@ -43,6 +45,7 @@ int main(int argc, char** argv) {
   const float temp = argc > 5 ? (float)atof(argv[5]) : 0.1f;
   const int n_seeds = argc > 6 ? atoi(argv[6]) : 1;
   const float tail_peak = argc > 7 ? (float)atof(argv[7]) : 0.0f;
+  const int hold_knots = argc > 8 ? atoi(argv[8]) : 0;
   const int impl = MBD_PRNG_PARTITIONABLE;
   mbd_env* env = NULL;
   CHECK(mbd_env_create(env_name, 0, &env));
@@ -65,6 +68,15 @@ int main(int argc, char** argv) {
         g[h * Nu + a] = h < H - R ? 1.0f : (float)(1.0 + ((double)tail_peak - 1.0) * (double)(h - (H - R) + 1) / (double)R);
     shape.scale = g; shape.rows = H; shape.cols = Nu; shape.when = MBD_NOISE_ALWAYS;
   }
+  /* the noise basis W [H][hold_knots]: row h reads knot floor(h hold_knots / H) alone */
+  mbd_noise_basis basis;
+  memset(&basis, 0, sizeof(basis));
+  float* W = NULL;
+  if (hold_knots > 0) {
+    W = (float*)calloc((size_t)H * (size_t)hold_knots, sizeof(float));
+    for (int h = 0; h < H; ++h) W[h * hold_knots + (int)((long long)h * hold_knots / H)] = 1.0f;
+    basis.basis = W; basis.n_knots = hold_knots; basis.when = MBD_NOISE_ALWAYS;
+  }
   float* state = (float*)malloc(sizeof(float) * (size_t)S * (size_t)(n_seeds > 0 ? n_seeds : 1));
   uint32_t* keys = (uint32_t*)malloc(sizeof(uint32_t) * 2 * (size_t)(n_seeds > 0 ? n_seeds : 1));
   for (int seed = 0; seed < n_seeds; ++seed) {
@@ -76,6 +88,7 @@ int main(int argc, char** argv) {
     CHECK(mbd_plan_create(env, &cfg, &plan));
     CHECK(mbd_plan_set_state0(plan, state + (size_t)seed * S));
     if (g) CHECK(mbd_plan_set_noise_shape(plan, &shape));
+    if (W) CHECK(mbd_plan_set_noise_basis(plan, &basis));
     float rew_final = 0.0f;
     double secs = 0.0;
     CHECK(mbd_plan_run(plan, rng_exp, NULL, NULL, &rew_final, &secs));
@@ -87,6 +100,7 @@ int main(int argc, char** argv) {
     CHECK(mbd_sweep_create(env, &cfg, n_seeds, NULL, &sweep));
     for (int seed = 0; seed < n_seeds; ++seed) CHECK(mbd_sweep_set_state0(sweep, seed, state + (size_t)seed * S));
     if (g) CHECK(mbd_sweep_set_noise_shape(sweep, &shape));
+    if (W) CHECK(mbd_sweep_set_noise_basis(sweep, &basis));
     float* rews = (float*)malloc(sizeof(float) * (size_t)n_seeds);
     double secs = 0.0;
     CHECK(mbd_sweep_run(sweep, keys, NULL, NULL, rews, &secs));
@@ -98,6 +112,7 @@ int main(int argc, char** argv) {
   free(keys);
   free(state);
   free(g);
+  free(W);
   CHECK(mbd_env_destroy(env));
   return 0;
 }

@@ -511,6 +511,38 @@ typedef struct mbd_noise_shape {
 } mbd_noise_shape;
 int mbd_plan_set_noise_shape(mbd_plan* plan, const mbd_noise_shape* rec);
 
+/* ---- noise bases: the sampling noise correlated along the horizon through a few knots per actuator (no counterpart in the
+ * reference, whose normals are white along the horizon; DESIGN.md section 1 "N8 noise basis") ---- */
+#define MBD_MAX_KNOTS 16
+/* A noise basis is a table W [Hsample][n_knots] of finite floats of any sign, 1 <= n_knots <= MBD_MAX_KNOTS, a setting of a
+ * plan (of a sweep) beside the noise shape.  With a basis in force a diffusion step draws
+ *   eps = normal(key, (Nsample, n_knots, action_size))
+ * INSTEAD of the (Nsample, Hsample, action_size) tensor — the step's own sampling key, the plan's prng_impl, and the counters
+ * and pairing those give a tensor of Nsample n_knots action_size elements (the legacy layout pairs element j with j + half,
+ * the padded last block as for every other normal of the library) — and a candidate element of step i is
+ *   c = +0.0f;  for k = 0 .. n_knots-1, ascending:  if (W[h][k] != 0) c = c + (W[h][k] * eps[n][k][a])   (two roundings a term)
+ *   z = c                        without a noise shape
+ *   z = c * g[h][a]              with one: the basis first, then the shape
+ *   Y0s = clip((z * sigma_i) + Ybar_i[h][a], -1, 1)
+ * float32 operations, each rounded, no fma.  Terms whose weight is exactly zero (of either sign) are left out, so a sparse
+ * basis — interpolation, hold — may be evaluated per element or per column with the same bits.  Everything else of the step is
+ * unchanged: the rollout, mean_H, standardisation, softmax, the weighted mean over these same candidates in the full [H][Nu]
+ * space, the score update, the path-integral updates.  Hence: a row of zeros in W freezes that horizon row at clip(Ybar_i),
+ * z = +0; and with n_knots = Hsample <= 16 and W the identity the plan equals the plan without a basis in value (only the sign
+ * of a zero normal may differ).  The disturbance normals of a plant record are the world's and pass no basis.
+ * `when` takes mbd_noise_shape's two values with their meaning; a plan may carry a shape and a basis with different `when`.
+ * Every plan that samples takes a basis, as it takes a shape.  The set call copies the table, is synchronous (it waits for
+ * the device) and discards normals prepared ahead for a key_next, so no step consumes normals made under the previous setting;
+ * call it between diffusion steps.  rec == NULL clears.  Refused with MBD_ERR_INVALID before any device access, the message
+ * naming the field: a NULL handle, a NULL basis, n_knots outside [1, MBD_MAX_KNOTS], a non-finite basis value, an unknown
+ * when. */
+typedef struct mbd_noise_basis {
+  const float* basis;  /* HOST [Hsample][n_knots], copied by the set call */
+  int32_t n_knots;     /* 1 .. MBD_MAX_KNOTS */
+  int32_t when;        /* MBD_NOISE_ALWAYS or MBD_NOISE_WARM_TICKS */
+} mbd_noise_basis;
+int mbd_plan_set_noise_basis(mbd_plan* plan, const mbd_noise_basis* rec);
+
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
  * candidates Y0s [Nsample][H][Nu] (plans that keep normals instead form them here, from the normals, sigma_i and the
  * Ybar_i of the last step — between phase 1 and phase 2 the caller's d_Ybar_i must still be unchanged), the shard's
@@ -571,6 +603,9 @@ int mbd_sweep_set_mpc_plant(mbd_sweep* sweep, int k, const mbd_mpc_plant* rec);
 /* one noise shape (mbd_noise_shape, above) for all plans of the sweep: plan k of mbd_sweep_run, episode k of mbd_sweep_run_mpc,
  * is then the single plan's with the same record, bit for bit.  Refusals as mbd_plan_set_noise_shape's. */
 int mbd_sweep_set_noise_shape(mbd_sweep* sweep, const mbd_noise_shape* rec);
+/* one noise basis (mbd_noise_basis, above) for all plans of the sweep, with the same guarantee.  Refusals as
+ * mbd_plan_set_noise_basis's. */
+int mbd_sweep_set_noise_basis(mbd_sweep* sweep, const mbd_noise_basis* rec);
 /* path-integral sweeps: the carried sampling sigma of every plan after the last run (path_integral.py:113,131); HOST [n_plans] */
 int mbd_sweep_get_sigmas(mbd_sweep* sweep, float* sigmas_out);
 /* average milliseconds of the sweep's rollout launches since the last reset (hipEvents on the launch stream) */

@@ -39,6 +39,15 @@ int mbd_debug_eval_math(const char* op, long long n, const float* in, float* out
  * wide form is held to the checker at a size a test can afford.  g HOST [HNu]; N * HNu <= 2^26.  Argument errors first, then
  * MBD_ERR_NO_DEVICE. */
 int mbd_debug_noise_shaped(const uint32_t key[2], int impl, int N, int HNu, const float* g, int wide, int blocks, float* z_out);
+/* The normals of a diffusion step under a noise basis on their own (include/mbd_hip.h mbd_noise_basis): z_out HOST [N][H Nu] by
+ * knot_noise_kernel on `blocks` workgroups (fewer than the columns need: the column loop strides).  W HOST [H][n_knots]; g HOST
+ * [H Nu] or NULL: no shape; N * H * Nu <= 2^26.  Argument errors first, then MBD_ERR_NO_DEVICE. */
+int mbd_debug_knot_noise(const uint32_t key[2], int impl, int N, int H, int Nu, int n_knots, const float* W, const float* g,
+                         int blocks, float* z_out);
+/* The same on the HOST: the kernel's per-column code (one text for host and device) over all N Nu columns in a loop, no device
+ * touched — a test without a GPU holds the kernel's indexing and arithmetic to the checker.  z_out HOST [N][H Nu]. */
+int mbd_debug_knot_noise_host(const uint32_t key[2], int impl, int N, int H, int Nu, int n_knots, const float* W, const float* g,
+                              float* z_out);
 #ifdef __cplusplus
 }
 #endif

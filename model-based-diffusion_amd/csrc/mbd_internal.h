@@ -173,11 +173,23 @@ struct LazyArgs {
   float sigma = 0.0f;
   float* nz_out = nullptr;      // [nz_N][nz_HNu] normals of the next step, or nullptr: no job
   const float* nz_g = nullptr;  // the noise shape [nz_HNu] that step samples under (device), or nullptr: none
+  // the noise basis [H][nz_knots] that step samples under (device), or nullptr: none.  A job under a basis is knot_noise_kernel's,
+  // never the launch's: launch_rollout leaves it alone (nz_fused stays false) and the caller runs it on its second stream
+  const float* nz_W = nullptr;
+  int nz_knots = 0;
   uint32_t nz_key[2] = {0, 0};
   int nz_impl = 0, nz_N = 0, nz_HNu = 0;
   bool nz_fused = false;        // out: the job went into this launch (false: the caller runs it elsewhere)
   int* progress = nullptr;      // RolloutParams.progress / progress_val
   int progress_val = 0;
+};
+// What the normals of a diffusion step are made under: the noise shape g [HNu] (mbd_noise_shape) and the noise basis
+// W [H][knots] (mbd_noise_basis), both device tables of the plan or sweep, nullptr: none.  The tag of a prepared buffer.
+struct NoiseSpec {
+  const float* g = nullptr;
+  const float* W = nullptr;
+  int knots = 0;
+  bool operator==(const NoiseSpec& o) const { return g == o.g && W == o.W && knots == o.knots; }
 };
 // the host's view of a progress word (pinned host memory the device stores into)
 static inline int progress_read(const int* h) { return __atomic_load_n(h, __ATOMIC_ACQUIRE); }
@@ -295,6 +307,8 @@ int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc);
 // the refusals of a noise-shape record (include/mbd_hip.h mbd_noise_shape) against a handle's Hsample x action_size, in the
 // header's order, each naming the field — host arithmetic on the record's own table, before any device access
 int check_noise_shape(const mbd_noise_shape* rec, int Hsample, int action_size);
+// the refusals of a noise-basis record (include/mbd_hip.h mbd_noise_basis) of a handle with Hsample rows, likewise
+int check_noise_basis(const mbd_noise_basis* rec, int Hsample);
 // One tick of a plant's disturbance chain, dk, d_t = split(dk): advances dk, fills slot k of sp with d_t and the record's
 // deviations — the kick's only in the ticks that end with one — and says whether tick t does
 bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k);

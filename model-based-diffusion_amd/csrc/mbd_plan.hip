@@ -23,7 +23,7 @@ struct NoiseRing {
   int cur = 0;                             // buffer of the step in flight (set by sample_rollout, read by score_update / peek)
   uint32_t key[3][2] = {{0, 0}, {0, 0}, {0, 0}};
   bool valid[3] = {false, false, false};   // eps[b] holds normal(key[b]) ...
-  const float* shape[3] = {nullptr, nullptr, nullptr};  // ... scaled by this noise shape (the plan's d_shape; nullptr: none)
+  NoiseSpec spec[3];                       // ... made under this noise shape and basis (the plan's d_shape, d_basis)
   bool on_aux[3] = {false, false, false};  // ... generated on the aux stream: the reader checks ev_noise[b] first
   int read_seq[3] = {0, 0, 0};             // sequence number of the last rollout launch that read eps[b]
   PinnedWord progress;
@@ -32,22 +32,22 @@ struct NoiseRing {
   bool wm_mark_valid = false;  // ev_wm was recorded behind the latest weighted mean
   bool kept_in_step = false;   // plan_keep_in_step held the host back for the coming sample_rollout (the queue is NOT draining)
   uint32_t hint_key[2] = {0, 0};  // mbd_plan_prefetch_noise: key of the step after the next sample_rollout
-  const float* hint_g = nullptr;  // ... and the noise shape that step samples under
+  NoiseSpec hint_ns;              // ... and the noise shape and basis that step samples under
   bool hint_valid = false;
 
-  // the buffer that holds normal(k) under the shape g, or -1
-  int find(const uint32_t k[2], const float* g) const {
+  // the buffer that holds the normals of key k made under ns, or -1
+  int find(const uint32_t k[2], const NoiseSpec& ns) const {
     int at = -1;
     for (int b = 0; b < 3; ++b)
-      if (valid[b] && key[b][0] == k[0] && key[b][1] == k[1] && shape[b] == g) at = b;
+      if (valid[b] && key[b][0] == k[0] && key[b][1] == k[1] && spec[b] == ns) at = b;
     return at;
   }
-  void holds(int b, const uint32_t k[2], const float* g) {
+  void holds(int b, const uint32_t k[2], const NoiseSpec& ns) {
     key[b][0] = k[0]; key[b][1] = k[1];
-    shape[b] = g;
+    spec[b] = ns;
     valid[b] = true;
   }
-  // nothing prepared ahead survives (mbd_plan_set_noise_shape: the table behind a shape pointer has changed)
+  // nothing prepared ahead survives (mbd_plan_set_noise_shape, mbd_plan_set_noise_basis: the table behind a pointer has changed)
   void forget() {
     for (int b = 0; b < 3; ++b) valid[b] = false;
     hint_valid = false;
@@ -63,11 +63,11 @@ struct NoiseRing {
     return MBD_OK;
   }
   // takes the declared key: whether there is one that is not this step's own
-  bool take_hint(const uint32_t step_key[2], uint32_t out[2], const float** g_out) {
+  bool take_hint(const uint32_t step_key[2], uint32_t out[2], NoiseSpec* ns_out) {
     const bool have = hint_valid && !(hint_key[0] == step_key[0] && hint_key[1] == step_key[1]);
     hint_valid = false;
     out[0] = hint_key[0]; out[1] = hint_key[1];
-    *g_out = hint_g;
+    *ns_out = hint_ns;
     return have;
   }
   // Aux-stream generation into eps[b] must start after the last reader of eps[b] — the weighted mean behind rollout launch
@@ -151,6 +151,11 @@ struct mbd_plan {
   DevBuf<float> d_shape;
   bool has_shape = false;
   int shape_when = MBD_NOISE_ALWAYS;
+  // the noise basis (mbd_plan_set_noise_basis): the table W [Hsample][basis_knots] on the device and when it is in force; and,
+  // for materialised plans, the scratch z [N][HNu] knot_noise_kernel fills in front of shift_kernel
+  DevBuf<float> d_basis, d_knot_z;
+  bool has_basis = false;
+  int basis_knots = 0, basis_when = MBD_NOISE_ALWAYS;
   TimingPool timing;
   ~mbd_plan() {  // (streams, events and buffers release themselves, on the env's device)
     if (env) (void)hipSetDevice(env->device);
@@ -286,11 +291,29 @@ static const float* shape_always(const mbd_plan* p) {
   return p->has_shape && p->shape_when == MBD_NOISE_ALWAYS ? p->d_shape.get() : nullptr;
 }
 static const float* shape_warm(const mbd_plan* p) { return p->has_shape ? p->d_shape.get() : nullptr; }
+// ... and with the noise basis (mbd_noise_basis) beside it, each under its own `when`: what a step's normals are made under
+static NoiseSpec noise_spec(const mbd_plan* p, bool warm_tick) {
+  NoiseSpec ns;
+  ns.g = warm_tick ? shape_warm(p) : shape_always(p);
+  if (p->has_basis && (warm_tick || p->basis_when == MBD_NOISE_ALWAYS)) {
+    ns.W = p->d_basis.get();
+    ns.knots = p->basis_knots;
+  }
+  return ns;
+}
+static NoiseSpec noise_always(const mbd_plan* p) { return noise_spec(p, false); }
+static NoiseSpec noise_warm(const mbd_plan* p) { return noise_spec(p, true); }
 
-static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], float* out, const float* g) {
+// z [N][HNu] of a step into `out`: noise_kernel, or under a basis knot_noise_kernel
+static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], float* out, const NoiseSpec& ns) {
   const mbd_plan_config& c = p->cfg;
+  if (ns.W) {
+    hipLaunchKernelGGL(knot_noise_kernel, dim3(knot_blocks(c.Nsample, p->Nu, 65536)), dim3(kKnotThreads), 0, st, key[0], key[1],
+                       c.prng_impl, c.Nsample, c.Hsample, p->Nu, ns.knots, ns.W, ns.g, out);
+    return;
+  }
   const unsigned blocks = noise_blocks(c.prng_impl, (uint64_t)c.Nsample * p->HNu, 65536);
-  hipLaunchKernelGGL(noise_kernel, dim3(blocks), dim3(256), 0, st, key[0], key[1], c.prng_impl, c.Nsample, p->HNu, out, g);
+  hipLaunchKernelGGL(noise_kernel, dim3(blocks), dim3(256), 0, st, key[0], key[1], c.prng_impl, c.Nsample, p->HNu, out, ns.g);
 }
 
 // The normals of a diffusion step depend on its key only, not on the previous step's result.  This call DECLARES the
@@ -299,20 +322,21 @@ static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], flo
 // ~3000 humanoid candidates; no extra launch, no event), on the plan's second stream otherwise — so that the declared
 // step starts without a sampler on its critical path.  A hint: a step whose normals were not prepared (no declaration,
 // another key, a non-lazy plan) generates them on the spot; results are bit-identical either way.
-// (g: the noise shape the declared step samples under — a warm tick's first step is declared beside tick 0's last rollout)
-static int declare_next_key(mbd_plan* p, const uint32_t key_next[2], const float* g) {
+// (ns: the noise shape and basis the declared step samples under — a warm tick's first step is declared beside tick 0's last
+// rollout.  Under a basis the job is knot_noise_kernel's and always goes to the second stream: prepare_noise_job)
+static int declare_next_key(mbd_plan* p, const uint32_t key_next[2], const NoiseSpec& ns) {
   const bool off = env_flag("MBD_NO_PREFETCH");
   if (off || !p->lazy) return MBD_OK;
   p->ring.hint_key[0] = key_next[0];
   p->ring.hint_key[1] = key_next[1];
-  p->ring.hint_g = g;
+  p->ring.hint_ns = ns;
   p->ring.hint_valid = true;
   return MBD_OK;
 }
 extern "C" int mbd_plan_prefetch_noise(mbd_plan* p, const uint32_t key_next[2], void* stream_) {
   (void)stream_;
   if (!p || !key_next) return fail(MBD_ERR_INVALID, "NULL argument");
-  return declare_next_key(p, key_next, shape_always(p));
+  return declare_next_key(p, key_next, noise_always(p));
 }
 
 // A plan's phases depend on each other through its buffers (the normals one step's launch prepares are read by the
@@ -332,17 +356,17 @@ static int plan_enter(mbd_plan* p, hipStream_t s) {
 // Step 1 of phase 1, lazy: every rank holds the normals of ALL N candidates (counter-based noise), so that phase 2 needs no
 // second collective and is bit-identical for every shard layout; the candidates themselves are formed at the rollout's
 // action fetch and inside the weighted mean.  The step's normals: ring.cur afterwards.
-static int obtain_normals(mbd_plan* p, const uint32_t key_sample[2], const float* g, hipStream_t s) {
+static int obtain_normals(mbd_plan* p, const uint32_t key_sample[2], const NoiseSpec& ns, hipStream_t s) {
   NoiseRing& ring = p->ring;
-  int cur = ring.find(key_sample, g);
+  int cur = ring.find(key_sample, ns);
   if (cur >= 0) {  // prepared behind the previous rollout
     MBD_TRY(ring.join(cur, s));
   } else {  // not prepared: generate now, into the buffer behind the previous step's (stream order protects it)
     cur = (ring.cur + 1) % 3;
     MBD_TRY(ring.join(cur, s));  // (a stale prefetch may still be writing it)
-    launch_noise(p, s, key_sample, ring.eps[cur], g);
+    launch_noise(p, s, key_sample, ring.eps[cur], ns);
     HIP_TRY(hipGetLastError());
-    ring.holds(cur, key_sample, g);
+    ring.holds(cur, key_sample, ns);
   }
   ring.cur = cur;
   return MBD_OK;
@@ -350,12 +374,22 @@ static int obtain_normals(mbd_plan* p, const uint32_t key_sample[2], const float
 
 // Step 1, materialised (car2d, path-integral updates): every rank samples ALL N candidate sequences.  A sharded plan
 // samples its own rows first and the others' on a second stream, behind the rollout; mbd_plan_score_update joins
-// that stream before it reads them.
-static int sample_candidates(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i, const float* g,
+// that stream before it reads them.  Under a noise basis: knot_noise_kernel into the plan's scratch z, then shift_kernel —
+// sample_kernel's two roundings — over the whole tensor on the caller's stream, sharded or not.
+static int sample_candidates(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i, const NoiseSpec& ns,
                              hipStream_t s) {
   const mbd_plan_config& c = p->cfg;
   const int N = c.Nsample, HNu = p->HNu;
   const uint64_t total = (uint64_t)N * HNu;
+  const float* g = ns.g;
+  if (ns.W) {
+    launch_noise(p, s, key_sample, p->d_knot_z, ns);
+    hipLaunchKernelGGL(shift_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)p->d_knot_z, HNu, 0ull,
+                       (unsigned long long)total, p->sigmas[i],
+                       c.update_method > 0 ? (const float*)p->d_sigma : (const float*)nullptr, d_Ybar_i, p->d_Y0s.get());
+    HIP_TRY(hipGetLastError());
+    return MBD_OK;
+  }
   auto sample = [&](hipStream_t st, uint64_t e0, uint64_t cnt) {
     if (cnt == 0) return;
     const bool pair_blocks = c.prng_impl != MBD_PRNG_PARTITIONABLE && e0 == 0 && cnt == total;
@@ -399,21 +433,22 @@ static int prepare_noise_job(mbd_plan* p, const uint32_t key_sample[2], hipStrea
   // generated in front of each rollout, where the other plans' rollouts hide them anyway).
   const bool alone = c.shares_device == 0;
   uint32_t declared[2];
-  const float* declared_g = nullptr;
-  const bool want = ring.take_hint(key_sample, declared, &declared_g) && alone;
+  NoiseSpec declared_ns;
+  const bool want = ring.take_hint(key_sample, declared, &declared_ns) && alone;
   if (!want) return MBD_OK;
   // eps[nxt] was last read two steps ago
   MBD_TRY(ring.join(nxt, s));  // (a stale prefetch of another key: let it finish before it is overwritten)
   ring.valid[nxt] = false;
   lz.nz_out = ring.eps[nxt];
-  lz.nz_g = declared_g;
+  lz.nz_g = declared_ns.g; lz.nz_W = declared_ns.W; lz.nz_knots = declared_ns.knots;
   lz.nz_key[0] = declared[0]; lz.nz_key[1] = declared[1];
   lz.nz_impl = c.prng_impl; lz.nz_N = c.Nsample; lz.nz_HNu = p->HNu;
   // (launches that take the job into spare workgroups need no second stream and none of its events: a record
   // behind every weighted mean idles the queue ~5.5 us, 1 % of a step — profiles/r02_timeline.txt)
   // (asked of the launch's own decision: a one-workgroup shard of a large plan pins its rollout and still cannot take
-  // the job — its normals then need the second stream's ordering like a full-chip launch's)
-  if (rollout_takes_noise(plan_rollout_choice(p), c.prng_impl, c.Nsample, p->HNu)) return MBD_OK;
+  // the job — its normals then need the second stream's ordering like a full-chip launch's; and so does every job under a
+  // noise basis, which no rollout launch takes)
+  if (!declared_ns.W && rollout_takes_noise(plan_rollout_choice(p), c.prng_impl, c.Nsample, p->HNu)) return MBD_OK;
   MBD_TRY(ensure_aux(p));
   return ring.mark_last_reader(nxt, s, marked);
 }
@@ -424,22 +459,24 @@ static int finish_noise_job(mbd_plan* p, const LazyArgs& lz, bool marked) {
   if (!lz.nz_out) return MBD_OK;
   NoiseRing& ring = p->ring;
   const int nxt = (ring.cur + 1) % 3;
+  NoiseSpec ns;
+  ns.g = lz.nz_g; ns.W = lz.nz_W; ns.knots = lz.nz_knots;
   if (!lz.nz_fused) {
     MBD_TRY(ensure_aux(p));
     MBD_TRY(ring.aux_waits_for_mark(p->aux, marked));
-    launch_noise(p, p->aux, lz.nz_key, lz.nz_out, lz.nz_g);
+    launch_noise(p, p->aux, lz.nz_key, lz.nz_out, ns);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ring.ev_noise[nxt], p->aux));
     ring.on_aux[nxt] = true;
   }
-  ring.holds(nxt, lz.nz_key, lz.nz_g);
+  ring.holds(nxt, lz.nz_key, ns);
   return MBD_OK;
 }
 
 // phase 1 of a step, from d_state0: the plan's own start state (mbd_plan_sample_rollout), or an episode's executed state;
-// g: the noise shape the step samples under, or nullptr
+// ns: the noise shape and basis the step samples under
 static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i, float* d_rews_local,
-                               float* d_logpd_local, hipStream_t s, const float* d_state0, const float* g) {
+                               float* d_logpd_local, hipStream_t s, const float* d_state0, const NoiseSpec& ns) {
   if (!p || !key_sample || !d_Ybar_i || !d_rews_local) return fail(MBD_ERR_INVALID, "NULL argument");
   const mbd_plan_config& c = p->cfg;
   if (i < 1 || i >= c.Ndiffuse) return fail(MBD_ERR_INVALID, "diffusion index %d outside [1,%d)", i, c.Ndiffuse);
@@ -453,14 +490,14 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
   bool marked = false;
   // A1: this step's normals, then the next step's noise job; or this step's candidates
   if (p->lazy) {
-    MBD_TRY(obtain_normals(p, key_sample, g, s));
+    MBD_TRY(obtain_normals(p, key_sample, ns, s));
     p->peek_ybar = d_Ybar_i;  // (the caller keeps it unchanged until phase 2 has run)
     p->sigma_last = p->sigmas[i];
     lz.ybar = d_Ybar_i;
     lz.sigma = p->sigmas[i];
     MBD_TRY(prepare_noise_job(p, key_sample, s, lz, &marked));
   } else {
-    MBD_TRY(sample_candidates(p, i, key_sample, d_Ybar_i, g, s));
+    MBD_TRY(sample_candidates(p, i, key_sample, d_Ybar_i, ns, s));
   }
   // A2/A3: rollout of the local shard
   MBD_TRY(p->timing.begin(s));
@@ -497,7 +534,7 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
 extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
                                        float* d_rews_local, float* d_logpd_local, void* stream_) {
   return plan_sample_rollout(p, i, key_sample, d_Ybar_i, d_rews_local, d_logpd_local, (hipStream_t)stream_,
-                             p ? p->d_state0.get() : nullptr, p ? shape_always(p) : nullptr);
+                             p ? p->d_state0.get() : nullptr, p ? noise_always(p) : NoiseSpec{});
 }
 
 extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
@@ -657,6 +694,79 @@ extern "C" int mbd_debug_noise_shaped(const uint32_t key[2], int impl, int N, in
   return MBD_OK;
 }
 
+// ---- the noise basis (include/mbd_hip.h mbd_noise_basis) ----------------------------------------------------------------
+int check_noise_basis(const mbd_noise_basis* rec, int Hsample) {
+  if (!rec->basis) return fail(MBD_ERR_INVALID, "noise basis: basis is NULL");
+  if (rec->n_knots < 1 || rec->n_knots > MBD_MAX_KNOTS)
+    return fail(MBD_ERR_INVALID, "noise basis: n_knots=%d outside [1, %d]", rec->n_knots, MBD_MAX_KNOTS);
+  const size_t n = (size_t)Hsample * (size_t)rec->n_knots;
+  for (size_t e = 0; e < n; ++e)
+    if (!std::isfinite(rec->basis[e]))
+      return fail(MBD_ERR_INVALID, "noise basis: basis[%d][%d]=%g: must be finite", (int)(e / rec->n_knots), (int)(e % rec->n_knots),
+                  (double)rec->basis[e]);
+  if (rec->when != MBD_NOISE_ALWAYS && rec->when != MBD_NOISE_WARM_TICKS)
+    return fail(MBD_ERR_INVALID, "noise basis: when=%d: MBD_NOISE_ALWAYS (0) or MBD_NOISE_WARM_TICKS (1)", rec->when);
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_noise_basis(mbd_plan* p, const mbd_noise_basis* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (rec) MBD_TRY(check_noise_basis(rec, p->cfg.Hsample));
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight, or normals being prepared ahead, may still read the previous table)
+  // as mbd_plan_set_noise_shape: nothing prepared under the previous setting survives
+  p->ring.forget();
+  p->has_basis = false;
+  if (!rec) return MBD_OK;
+  const size_t n = (size_t)p->cfg.Hsample * (size_t)rec->n_knots;
+  HIP_TRY(p->d_basis.grow((size_t)p->cfg.Hsample * MBD_MAX_KNOTS));
+  if (!p->lazy) HIP_TRY(p->d_knot_z.grow((size_t)p->cfg.Nsample * p->HNu));
+  HIP_TRY(hipMemcpy(p->d_basis, rec->basis, sizeof(float) * n, hipMemcpyHostToDevice));
+  p->basis_knots = rec->n_knots;
+  p->basis_when = rec->when;
+  p->has_basis = true;
+  return MBD_OK;
+}
+
+// include/mbd_hip_debug.h: knot_noise_kernel alone, on `blocks` workgroups of kKnotThreads threads
+extern "C" int mbd_debug_knot_noise(const uint32_t key[2], int impl, int N, int H, int Nu, int n_knots, const float* W,
+                                    const float* g, int blocks, float* z_out) {
+  if (!key || !W || !z_out) return fail(MBD_ERR_INVALID, "NULL argument");
+  if (N < 1 || H < 1 || Nu < 1 || n_knots < 1 || n_knots > MBD_MAX_KNOTS || blocks < 1 || blocks > 65536 ||
+      (uint64_t)N * (uint64_t)H * (uint64_t)Nu > (1ull << 26))
+    return fail(MBD_ERR_INVALID, "knot_noise: N=%d H=%d Nu=%d n_knots=%d blocks=%d", N, H, Nu, n_knots, blocks);
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  const size_t HNu = (size_t)H * Nu, n = (size_t)N * HNu;
+  DevBuf<float> d_W, d_g, d_z;
+  HIP_TRY(d_W.alloc((size_t)H * n_knots));
+  HIP_TRY(d_z.alloc(n));
+  HIP_TRY(hipMemcpy(d_W, W, sizeof(float) * (size_t)H * n_knots, hipMemcpyHostToDevice));
+  if (g) {
+    HIP_TRY(d_g.alloc(HNu));
+    HIP_TRY(hipMemcpy(d_g, g, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemset(d_z, 0xff, sizeof(float) * n));  // (an element left unwritten reads back as NaN)
+  hipLaunchKernelGGL(knot_noise_kernel, dim3((unsigned)blocks), dim3(kKnotThreads), 0, nullptr, key[0], key[1], impl, N, H, Nu, n_knots,
+                     (const float*)d_W, g ? (const float*)d_g : (const float*)nullptr, d_z.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(z_out, d_z, sizeof(float) * n, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
+// include/mbd_hip_debug.h: the same columns on the host (knot_column is host and device text) — no device is touched
+extern "C" int mbd_debug_knot_noise_host(const uint32_t key[2], int impl, int N, int H, int Nu, int n_knots, const float* W,
+                                         const float* g, float* z_out) {
+  if (!key || !W || !z_out) return fail(MBD_ERR_INVALID, "NULL argument");
+  if (N < 1 || H < 1 || Nu < 1 || n_knots < 1 || n_knots > MBD_MAX_KNOTS || (uint64_t)N * (uint64_t)H * (uint64_t)Nu > (1ull << 26))
+    return fail(MBD_ERR_INVALID, "knot_noise_host: N=%d H=%d Nu=%d n_knots=%d", N, H, Nu, n_knots);
+  const uint64_t cols = (uint64_t)N * (uint64_t)Nu;
+  float slots[MBD_MAX_KNOTS];
+  for (uint64_t col = 0; col < cols; ++col)
+    knot_column(key[0], key[1], impl, cols * (uint64_t)n_knots, H, Nu, n_knots, W, g, z_out, col, slots, 1);
+  return MBD_OK;
+}
+
 // Loops that enqueue step after step (mbd_plan_run): a plan whose next step's normals are generated on the second stream
 // stays ONE step behind the device — it enqueues step q once the rollout of step q-1 has started (the queue still holds
 // that rollout and its score: the device never waits for the host) — so that sample_rollout finds the progress word where
@@ -664,7 +774,8 @@ extern "C" int mbd_debug_noise_shaped(const uint32_t key[2], int impl, int N, in
 static int plan_keep_in_step(mbd_plan* p) {
   NoiseRing& ring = p->ring;
   if (!p->lazy || !ring.progress || ring.seq == 0 || p->cfg.shares_device != 0) return MBD_OK;
-  if (rollout_takes_noise(plan_rollout_choice(p), p->cfg.prng_impl, p->cfg.Nsample, p->HNu)) return MBD_OK;
+  // (a plan with a noise basis prepares its normals on the second stream whatever the launch could take)
+  if (!p->has_basis && rollout_takes_noise(plan_rollout_choice(p), p->cfg.prng_impl, p->cfg.Nsample, p->HNu)) return MBD_OK;
   // (a stream slower than the limit: the loop stops keeping step and the step orders the two streams with an event instead —
   // NoiseRing::mark_last_reader's own bounded wait, then a mark on the step's stream for the aux stream)
   ring.kept_in_step = progress_wait(ring.progress, ring.seq, kInStepWaitMs, 20);
@@ -672,11 +783,11 @@ static int plan_keep_in_step(mbd_plan* p) {
 }
 
 // d_state0: where the step's rollouts start.  key_after: the Y0s_rng of the step that follows the LAST step (i == 1) of
-// this loop in another one (a receding-horizon episode's next tick), or nullptr.  g: the noise shape this loop's steps
-// sample under, g_after: the one key_after's step does (nullptr: flat)
+// this loop in another one (a receding-horizon episode's next tick), or nullptr.  ns: the noise shape and basis this loop's
+// steps sample under, ns_after: what key_after's step does
 static int reverse_once_impl(mbd_plan* p, const float* d_state0, int i, uint32_t key_inout[2], const float* d_Ybar_in,
-                             float* d_Ybar_out, float* d_rew_mean, hipStream_t s, const float* g,
-                             const uint32_t* key_after = nullptr, const float* g_after = nullptr) {
+                             float* d_Ybar_out, float* d_rew_mean, hipStream_t s, const NoiseSpec& ns,
+                             const uint32_t* key_after = nullptr, const NoiseSpec& ns_after = NoiseSpec{}) {
   if (p->cfg.shard_count != p->cfg.Nsample)
     return fail(MBD_ERR_STATE, "reverse_once on a sharded plan: use sample_rollout + all-gather + score_update");
   uint32_t keys[4];
@@ -687,11 +798,11 @@ static int reverse_once_impl(mbd_plan* p, const float* d_state0, int i, uint32_t
     const uint32_t adv[2] = {keys[0], keys[1]};
     host_split(adv, 2, p->cfg.prng_impl, nk);
     const uint32_t next_ks[2] = {nk[2], nk[3]};
-    MBD_TRY(declare_next_key(p, next_ks, g));
+    MBD_TRY(declare_next_key(p, next_ks, ns));
   } else if (key_after) {
-    MBD_TRY(declare_next_key(p, key_after, g_after));
+    MBD_TRY(declare_next_key(p, key_after, ns_after));
   }
-  MBD_TRY(plan_sample_rollout(p, i, ks, d_Ybar_in, p->d_rews, p->cfg.enable_demo ? p->d_lp.get() : nullptr, s, d_state0, g));
+  MBD_TRY(plan_sample_rollout(p, i, ks, d_Ybar_in, p->d_rews, p->cfg.enable_demo ? p->d_lp.get() : nullptr, s, d_state0, ns));
   MBD_TRY(mbd_plan_score_update(p, i, ks, d_Ybar_in, p->d_rews, p->d_lp, d_Ybar_out, d_rew_mean, s));
   key_inout[0] = keys[0];
   key_inout[1] = keys[1];
@@ -703,7 +814,7 @@ extern "C" int mbd_plan_reverse_once(mbd_plan* p, int i, uint32_t key_inout[2], 
   if (!p || !key_inout || !d_Ybar || !d_rew_mean) return fail(MBD_ERR_INVALID, "NULL argument");
   hipStream_t s = (hipStream_t)stream_;
   // the update is not in place on the device (wmean reads Ybar_i while writing Ybar_{i-1})
-  MBD_TRY(reverse_once_impl(p, p->d_state0, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s, shape_always(p)));
+  MBD_TRY(reverse_once_impl(p, p->d_state0, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s, noise_always(p)));
   HIP_TRY(hipMemcpyAsync(d_Ybar, p->d_Ybar, sizeof(float) * p->HNu, hipMemcpyDeviceToDevice, s));
   return MBD_OK;
 }
@@ -726,7 +837,7 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
   for (int i = Nd - 1; i >= 1; --i) {  // reverse() (mbd_planner.py:138-148)
     float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // Ybars.append(Yi)
     MBD_TRY(plan_keep_in_step(p));
-    MBD_TRY(reverse_once_impl(p, p->d_state0, i, rng, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, shape_always(p)));
+    MBD_TRY(reverse_once_impl(p, p->d_state0, i, rng, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, noise_always(p)));
     cur = nxt;
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -995,14 +1106,14 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
       host_split(k_next, 2, c.prng_impl, after);
     }
     const float* cur = ybar0;
-    // the noise shape: tick 0 is mbd_plan_run's loop (MBD_NOISE_WARM_TICKS: flat), every later tick samples under the shape
-    // in either mode — the first normals of tick t + 1, prepared beside this tick's last rollout, included
-    const float* g = t == 0 ? shape_always(p) : shape_warm(p);
+    // the noise shape and basis: tick 0 is mbd_plan_run's loop (MBD_NOISE_WARM_TICKS: without), every later tick samples under
+    // them in either mode — the first normals of tick t + 1, prepared beside this tick's last rollout, included
+    const NoiseSpec ns = t == 0 ? noise_always(p) : noise_warm(p);
     for (int i = t == 0 ? Nd - 1 : K; i >= 1; --i) {
       float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
       MBD_TRY(plan_keep_in_step(p));
-      MBD_TRY(reverse_once_impl(p, s_t, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, g, t + 1 < T ? after + 2 : nullptr,
-                                shape_warm(p)));
+      MBD_TRY(reverse_once_impl(p, s_t, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, ns, t + 1 < T ? after + 2 : nullptr,
+                                noise_warm(p)));
       cur = nxt;
     }
     // execute M_t's first E rows from s_t, then the boundary: Ybar of tick t+1, the logs of M_t and s_{t+1}

@@ -155,6 +155,81 @@ static __global__ __launch_bounds__(256) void noise_shaped_probe_kernel(uint32_t
   if (wide) noise_fill_shaped<uint64_t>(k0, k1, impl, size, tid0, stride, eps, g, (uint32_t)HNu);
   else noise_fill_shaped<uint32_t>(k0, k1, impl, (uint32_t)size, (uint32_t)tid0, (uint32_t)stride, eps, g, (uint32_t)HNu);
 }
+// ---- the noise basis (include/mbd_hip.h mbd_noise_basis; DESIGN.md section 1 "N8 noise basis") -----------------------------
+// z [N][H Nu], the layout of the buffers noise_fill writes, from eps = normal(key, (N, knots, Nu)):
+//   z[n][h][a] = (sum over k ascending of W[h][k] * eps[n][k][a], from +0, product and sum rounded, zero weights left out)
+//                * g[h][a] where there is a shape
+// so that every consumer forms clip(z * sigma + Ybar) unchanged.  One thread per column (n, a), grid-stride over the N Nu
+// columns from col0 by stride (any grid gives the same bits): it draws its `knots` normals — one threefry block each
+// (random_bits32: the legacy layout pairs element j of the knot tensor with j + half, the thread keeps its half) — through a slot
+// of LDS into registers (the draw is a loop, not sixteen copies of threefry and the ErfInv polynomial; the walk over the rows
+// reads registers), then walks the H rows with W[h][k] wave-uniform: a scalar load, and a zero weight is a scalar branch around
+// the term.  knots / H of the flat sampler's threefry + ErfInv work; a wavefront's stores of one row are runs of Nu floats
+// (one per candidate it holds), which the H rows of the walk complete into whole lines in L2.
+constexpr int kKnotThreads = 64;
+// One column (n, a) = col of the N Nu: its `knots` normals through the slots drawn[0], drawn[slot_stride], ... and the walk over
+// the H rows.  Host and device: mbd_debug_knot_noise_host runs this same text on the CPU, where a test without a device holds
+// the indexing to the checker.
+MBD_HD void knot_column(uint32_t k0, uint32_t k1, int impl, uint64_t size, int H, int Nu, int knots,
+                        const float* __restrict__ W, const float* __restrict__ g, float* __restrict__ z, uint64_t col,
+                        float* drawn, int slot_stride) {
+  const uint64_t n = col / (uint64_t)Nu;
+  const uint32_t a = (uint32_t)(col - n * (uint64_t)Nu);
+  for (int k = 0; k < knots; ++k) {
+    const uint64_t j = (n * (uint64_t)knots + (uint64_t)k) * (uint64_t)Nu + a;  // flat element of the knot tensor
+    drawn[k * slot_stride] = bits_to_normal(random_bits32(k0, k1, impl, j, size));
+  }
+  float eps[MBD_MAX_KNOTS];
+#pragma unroll
+  for (int k = 0; k < MBD_MAX_KNOTS; ++k) eps[k] = k < knots ? drawn[k * slot_stride] : 0.0f;
+  float* __restrict__ out = z + n * (uint64_t)H * (uint64_t)Nu;  // candidate n's [H][Nu]; the column's element of row h is h Nu + a
+  for (int h = 0; h < H; ++h) {
+    const float* __restrict__ Wh = W + (size_t)h * knots;
+    float c = 0.0f;
+#pragma unroll
+    for (int k = 0; k < MBD_MAX_KNOTS; ++k) {
+      if (k < knots) {  // (wave-uniform, like the weight)
+        const float w = Wh[k];
+        if (w != 0.0f) c = c + w * eps[k];
+      }
+    }
+    const uint32_t r = (uint32_t)h * (uint32_t)Nu + a;
+    out[r] = g ? c * g[r] : c;
+  }
+}
+__device__ __forceinline__ void knot_fill(uint32_t k0, uint32_t k1, int impl, int N, int H, int Nu, int knots,
+                                          const float* __restrict__ W, const float* __restrict__ g, float* __restrict__ z,
+                                          uint64_t col0, uint64_t stride) {
+  __shared__ float drawn[MBD_MAX_KNOTS * kKnotThreads];
+  const uint64_t cols = (uint64_t)N * (uint64_t)Nu, size = cols * (uint64_t)knots;
+  for (uint64_t col = col0; col < cols; col += stride)
+    knot_column(k0, k1, impl, size, H, Nu, knots, W, g, z, col, drawn + threadIdx.x, kKnotThreads);
+}
+static __global__ __launch_bounds__(kKnotThreads) void knot_noise_kernel(uint32_t k0, uint32_t k1, int impl, int N, int H, int Nu,
+                                                                   int knots, const float* __restrict__ W,
+                                                                   const float* __restrict__ g, float* __restrict__ z) {
+  knot_fill(k0, k1, impl, N, H, Nu, knots, W, g, z, (uint64_t)blockIdx.x * kKnotThreads + threadIdx.x,
+            (uint64_t)gridDim.x * kKnotThreads);
+}
+// workgroups (of kKnotThreads) of a knot launch over N Nu columns; cap: 65536 for a plan, 1024 per plan of a sweep
+inline unsigned knot_blocks(int N, int Nu, uint64_t cap) {
+  const uint64_t blocks = ((uint64_t)N * (uint64_t)Nu + kKnotThreads - 1) / kKnotThreads;
+  return (unsigned)(blocks < cap ? blocks : cap);
+}
+// the second half of a materialised step under a basis for the P plans of a sweep (blockIdx.y = plan): shift_kernel's two
+// roundings with each plan's carried sigma and mean
+static __global__ __launch_bounds__(256) void shift_batch_kernel(const float* __restrict__ z, int N, int HNu,
+                                                           const float* __restrict__ sigma_dev /* [P] */,
+                                                           const float* __restrict__ mu, long long mu_stride,
+                                                           float* __restrict__ Y0s) {
+  const uint64_t size = (uint64_t)N * (uint64_t)HNu, base = (uint64_t)blockIdx.y * size;
+  const float sigma = sigma_dev[blockIdx.y];
+  const float* __restrict__ Ybar = mu + (long long)blockIdx.y * mu_stride;
+  for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < size; e += (uint64_t)gridDim.x * blockDim.x) {
+    const float y = z[base + e] * sigma + Ybar[e % (uint64_t)HNu];
+    Y0s[base + e] = fclip(y, -1.0f, 1.0f);
+  }
+}
 static __global__ __launch_bounds__(256) void shift_kernel(const float* __restrict__ eps, int HNu, unsigned long long e_begin,
                                                      unsigned long long e_count, float sigma_host,
                                                      const float* __restrict__ sigma_dev,
@@ -769,6 +844,14 @@ static __global__ __launch_bounds__(256) void noise_batch_kernel(SweepKeys keys,
   const uint64_t size = (uint64_t)N * (uint64_t)HNu;
   noise_fill(keys.k[blockIdx.y][0], keys.k[blockIdx.y][1], impl, size, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x,
              (uint64_t)gridDim.x * blockDim.x, eps + (uint64_t)blockIdx.y * size, g, HNu);
+}
+// knot_noise_kernel for the P plans of a sweep (blockIdx.y = plan): one basis and one shape for all, each plan its key
+static __global__ __launch_bounds__(kKnotThreads) void knot_noise_batch_kernel(SweepKeys keys, int impl, int N, int H, int Nu,
+                                                                         int knots, const float* __restrict__ W,
+                                                                         const float* __restrict__ g, float* __restrict__ z) {
+  knot_fill(keys.k[blockIdx.y][0], keys.k[blockIdx.y][1], impl, N, H, Nu, knots, W, g,
+            z + (uint64_t)blockIdx.y * (uint64_t)N * (uint64_t)H * (uint64_t)Nu,
+            (uint64_t)blockIdx.x * kKnotThreads + threadIdx.x, (uint64_t)gridDim.x * kKnotThreads);
 }
 
 // ---- the plant of a receding-horizon episode (include/mbd_hip.h mbd_mpc_plant): disturbances drawn and applied on the device ----

@@ -60,6 +60,22 @@ struct mbd_sweep {
   int shape_when = MBD_NOISE_ALWAYS;
   const float* shape_always() const { return has_shape && shape_when == MBD_NOISE_ALWAYS ? d_shape.get() : nullptr; }
   const float* shape_warm() const { return has_shape ? d_shape.get() : nullptr; }
+  // the noise basis of all the sweep's plans (mbd_sweep_set_noise_basis), likewise; d_knot_z [P][N][HNu]: the scratch of a
+  // path-integral sweep's knot_noise_batch_kernel in front of shift_batch_kernel
+  DevBuf<float> d_basis, d_knot_z;
+  bool has_basis = false;
+  int basis_knots = 0, basis_when = MBD_NOISE_ALWAYS;
+  NoiseSpec noise_spec(bool warm_tick) const {
+    NoiseSpec ns;
+    ns.g = warm_tick ? shape_warm() : shape_always();
+    if (has_basis && (warm_tick || basis_when == MBD_NOISE_ALWAYS)) {
+      ns.W = d_basis.get();
+      ns.knots = basis_knots;
+    }
+    return ns;
+  }
+  NoiseSpec noise_always() const { return noise_spec(false); }
+  NoiseSpec noise_warm() const { return noise_spec(true); }
   TimingPool timing;
   ~mbd_sweep() {  // (streams, events and buffers release themselves, on the env's device)
     if (env) (void)hipSetDevice(env->device);
@@ -195,8 +211,16 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
     const float* mu_in = step == 0 ? w->d_zero : w->d_mu + (size_t)(step - 1) * HNu;
     const long long mu_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
     float* mu_out = w->d_mu + (size_t)step * HNu;
-    hipLaunchKernelGGL(sample_batch_kernel, dim3(nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
-                       (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s, w->shape_always());
+    const NoiseSpec ns = w->noise_always();
+    if (ns.W) {  // under a noise basis: the knot kernel into the scratch z, then sample_batch_kernel's two roundings
+      hipLaunchKernelGGL(knot_noise_batch_kernel, dim3(knot_blocks(N, w->Nu, 1024), (unsigned)P), dim3(kKnotThreads), 0, s, sk,
+                         c.prng_impl, N, H, w->Nu, ns.knots, ns.W, ns.g, w->d_knot_z.get());
+      hipLaunchKernelGGL(shift_batch_kernel, dim3(noise_blocks(MBD_PRNG_PARTITIONABLE, per_plan, 4096), (unsigned)P), dim3(256), 0, s,
+                         (const float*)w->d_knot_z, N, HNu, (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s.get());
+    } else {
+      hipLaunchKernelGGL(sample_batch_kernel, dim3(nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
+                         (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s, ns.g);
+    }
     HIP_TRY(hipGetLastError());
     MBD_TRY(w->timing.begin(s));
     const int sw[3] = {N, S, 0};
@@ -252,16 +276,22 @@ struct SweepStep {
   const float* ybar_in;        // Ybar_i of plan 0; plan k's is ybar_in_stride floats further
   long long ybar_in_stride;
   const SweepKeys* next_keys;  // Y0s_rng of the loop's following step (its normals go beside this rollout), or nullptr: none follows
-  const float* next_g;         // the noise shape that following step samples under, or nullptr: flat
+  NoiseSpec next_ns;           // the noise shape and basis that following step samples under
 };
 
 // the normals of a step depend on its keys only: they are generated on the second stream while the previous step's
 // rollout runs (a ring of three buffers, see mbd_sweep), like a single large plan's
-void sweep_noise(mbd_sweep* w, const SweepKeys& sk, int buf, hipStream_t st, const float* g) {
+// (under a noise basis: knot_noise_batch_kernel, into the same buffers)
+void sweep_noise(mbd_sweep* w, const SweepKeys& sk, int buf, hipStream_t st, const NoiseSpec& ns) {
   const mbd_plan_config& c = w->cfg;
+  if (ns.W) {
+    hipLaunchKernelGGL(knot_noise_batch_kernel, dim3(knot_blocks(c.Nsample, w->Nu, 1024), (unsigned)w->P), dim3(kKnotThreads), 0, st,
+                       sk, c.prng_impl, c.Nsample, c.Hsample, w->Nu, ns.knots, ns.W, ns.g, w->d_eps[buf].get());
+    return;
+  }
   const unsigned nblocks = noise_blocks(c.prng_impl, (uint64_t)c.Nsample * w->HNu, 4096);
   hipLaunchKernelGGL(noise_batch_kernel, dim3(nblocks, (unsigned)w->P), dim3(256), 0, st, sk, c.prng_impl, c.Nsample, w->HNu,
-                     w->d_eps[buf], g);
+                     w->d_eps[buf], ns.g);
 }
 
 // rng, Y0s_rng = split(rng) of every plan (mbd_planner.py:103) — the whole key chain is host arithmetic
@@ -296,7 +326,7 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
       HIP_TRY(hipEventRecord(w->ev_order, s));
       HIP_TRY(hipStreamWaitEvent(w->aux, w->ev_order, 0));
     }
-    sweep_noise(w, *st.next_keys, nxt, w->aux, st.next_g);
+    sweep_noise(w, *st.next_keys, nxt, w->aux, st.next_ns);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(w->ev_ready[nxt], w->aux));
   }
@@ -341,7 +371,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
   auto t0 = std::chrono::steady_clock::now();
   SweepKeys sk;
   sweep_split_keys(w, rng, sk);
-  sweep_noise(w, sk, 0, s, w->shape_always());  // step Nd-1
+  sweep_noise(w, sk, 0, s, w->noise_always());  // step Nd-1
   HIP_TRY(hipGetLastError());
   for (int i = Nd - 1, step = 0; i >= 1; --i, ++step) {
     if (i > 1) sweep_split_keys(w, rng, sk);
@@ -350,7 +380,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
     st.ybar_in = step == 0 ? w->d_zero : w->d_mu + (size_t)(step - 1) * HNu;
     st.ybar_in_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
     st.next_keys = i > 1 ? &sk : nullptr;
-    st.next_g = w->shape_always();
+    st.next_ns = w->noise_always();
     MBD_TRY(sweep_step(w, st));
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -372,6 +402,23 @@ extern "C" int mbd_sweep_set_noise_shape(mbd_sweep* w, const mbd_noise_shape* re
   HIP_TRY(hipMemcpy(w->d_shape, rec->scale, sizeof(float) * w->HNu, hipMemcpyHostToDevice));
   w->shape_when = rec->when;
   w->has_shape = true;
+  return MBD_OK;
+}
+
+// one noise basis for all plans of the sweep (include/mbd_hip.h mbd_noise_basis), as mbd_sweep_set_noise_shape
+extern "C" int mbd_sweep_set_noise_basis(mbd_sweep* w, const mbd_noise_basis* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (rec) MBD_TRY(check_noise_basis(rec, w->cfg.Hsample));
+  HIP_TRY(hipSetDevice(w->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  w->has_basis = false;
+  if (!rec) return MBD_OK;
+  HIP_TRY(w->d_basis.grow((size_t)w->cfg.Hsample * MBD_MAX_KNOTS));
+  if (w->cfg.update_method != 0) HIP_TRY(w->d_knot_z.grow((size_t)w->P * w->cfg.Nsample * w->HNu));
+  HIP_TRY(hipMemcpy(w->d_basis, rec->basis, sizeof(float) * (size_t)w->cfg.Hsample * rec->n_knots, hipMemcpyHostToDevice));
+  w->basis_knots = rec->n_knots;
+  w->basis_when = rec->when;
+  w->has_basis = true;
   return MBD_OK;
 }
 
@@ -448,7 +495,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     sweep_split_keys(w, r, sk);
   };
   first_keys_of_tick();
-  sweep_noise(w, sk, 0, s, w->shape_always());  // tick 0, step Nd-1
+  sweep_noise(w, sk, 0, s, w->noise_always());  // tick 0, step Nd-1
   HIP_TRY(hipGetLastError());
   const long long mu_stride = (long long)(Nd - 1) * HNu;
   const int exec_sw[3] = {1, S, 0};
@@ -465,8 +512,9 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       st.ybar_in = i == i_start ? (t == 0 ? w->d_zero : w->d_mpc_ybar) : w->d_mu + (size_t)(st.slot - 1) * HNu;
       st.ybar_in_stride = i == i_start ? HNu : mu_stride;
       st.next_keys = follows ? &sk : nullptr;
-      // (the noise shape of the following step: this tick's, or — behind a tick's last step — a warm tick's, mbd_plan_run_mpc)
-      st.next_g = (t == 0 && i > 1) ? w->shape_always() : w->shape_warm();
+      // (the noise shape and basis of the following step: this tick's, or — behind a tick's last step — a warm tick's,
+      // mbd_plan_run_mpc)
+      st.next_ns = (t == 0 && i > 1) ? w->noise_always() : w->noise_warm();
       MBD_TRY(sweep_step(w, st));
     }
     // the boundary: the logs of M_{.,t}, its first E rows and Ybar of tick t+1; then the rows executed from s_{.,t}

@@ -66,15 +66,24 @@ class NoiseShape(C.Structure):
                 ("reserved", C.c_int32 * 5)]
 
 
+MAX_KNOTS = 16
+
+
+class NoiseBasis(C.Structure):
+    """mbd_noise_basis (include/mbd_hip.h): the table W [Hsample][n_knots] the sampling noise is correlated along the horizon
+    through, and when."""
+    _fields_ = [("basis", C.POINTER(C.c_float)), ("n_knots", C.c_int32), ("when", C.c_int32)]
+
+
 EXPORTS = [
     "mbd_last_error", "mbd_version", "mbd_tuned_spec", "mbd_device_count", "mbd_prng_key", "mbd_prng_split",
     "mbd_env_create", "mbd_env_name", "mbd_builtin_model", "mbd_env_get_model", "mbd_env_xref", "mbd_env_xref_logpd",
     "mbd_env_observe", "mbd_model_observe", "mbd_model_forward", "mbd_env_create_car2d", "mbd_env_create_model", "mbd_env_destroy", "mbd_env_info", "mbd_env_reset", "mbd_env_pipeline_init",
     "mbd_env_step", "mbd_env_rew_xref", "mbd_env_rollout", "mbd_plan_create", "mbd_plan_destroy",
     "mbd_plan_schedule", "mbd_plan_set_state0", "mbd_plan_sample_rollout", "mbd_plan_prefetch_noise", "mbd_plan_score_update",
-    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
+    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
-    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_set_noise_shape", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
+    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_set_noise_shape", "mbd_sweep_set_noise_basis", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
     "mbd_exchange_create", "mbd_exchange_destroy", "mbd_exchange_local_handle", "mbd_exchange_connect",
     "mbd_exchange_all_gather", "mbd_exchange_status", "mbd_exchange_fine_grained",
 ]
@@ -141,6 +150,7 @@ def load() -> C.CDLL:
     lib.mbd_plan_set_ensemble.argtypes = [_vp, C.POINTER(Ensemble)]
     lib.mbd_plan_peek_ensemble.argtypes = [_vp, _vp, _vp]
     lib.mbd_plan_set_noise_shape.argtypes = [_vp, C.POINTER(NoiseShape)]
+    lib.mbd_plan_set_noise_basis.argtypes = [_vp, C.POINTER(NoiseBasis)]
     lib.mbd_plan_eval.argtypes = [_vp, _vp, _fp]
     lib.mbd_plan_peek.argtypes = [_vp, _vp, _vp, _vp]
     lib.mbd_plan_kernel_time.argtypes = [_vp, _fp, C.POINTER(_i), _i]
@@ -152,6 +162,7 @@ def load() -> C.CDLL:
     lib.mbd_sweep_run_mpc.argtypes = [_vp, C.POINTER(MpcConfig), _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]
     lib.mbd_sweep_set_mpc_plant.argtypes = [_vp, _i, C.POINTER(MpcPlant)]
     lib.mbd_sweep_set_noise_shape.argtypes = [_vp, C.POINTER(NoiseShape)]
+    lib.mbd_sweep_set_noise_basis.argtypes = [_vp, C.POINTER(NoiseBasis)]
     lib.mbd_sweep_kernel_time.argtypes = [_vp, _i, _fp, C.POINTER(_i)]
     lib.mbd_sweep_get_sigmas.argtypes = [_vp, _vp]
     lib.mbd_exchange_create.argtypes = [_i, _i, _i, _i, _i, C.POINTER(_vp)]
@@ -205,6 +216,31 @@ def debug_noise_shaped(key, impl: int, N: int, HNu: int, g, wide: bool, blocks: 
     g = np.ascontiguousarray(g, np.float32).reshape(HNu)
     out = np.empty((N, HNu), np.float32)
     check(lib.mbd_debug_noise_shaped(key_array(key), impl, N, HNu, np_ptr(g), int(wide), blocks, np_ptr(out)))
+    return out
+
+
+def debug_knot_noise(key, impl: int, N: int, H: int, Nu: int, W, g, blocks: int) -> np.ndarray:
+    """include/mbd_hip_debug.h: z [N, H, Nu] of a step under the noise basis ``W`` [H, n_knots] (and the shape ``g`` [H, Nu], or
+    None) by knot_noise_kernel alone, on ``blocks`` workgroups."""
+    lib = load()
+    lib.mbd_debug_knot_noise.argtypes = [_u32p, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]
+    W = np.ascontiguousarray(W, np.float32).reshape(H, -1)
+    g = None if g is None else np.ascontiguousarray(g, np.float32).reshape(H * Nu)
+    out = np.empty((N, H, Nu), np.float32)
+    check(lib.mbd_debug_knot_noise(key_array(key), impl, N, H, Nu, W.shape[1], np_ptr(W), None if g is None else np_ptr(g), blocks,
+                                   np_ptr(out)))
+    return out
+
+
+def debug_knot_noise_host(key, impl: int, N: int, H: int, Nu: int, W, g) -> np.ndarray:
+    """include/mbd_hip_debug.h: ``debug_knot_noise``'s z by the kernel's per-column code run on the host (no device)."""
+    lib = load()
+    lib.mbd_debug_knot_noise_host.argtypes = [_u32p, _i, _i, _i, _i, _i, _vp, _vp, _vp]
+    W = np.ascontiguousarray(W, np.float32).reshape(H, -1)
+    g = None if g is None else np.ascontiguousarray(g, np.float32).reshape(H * Nu)
+    out = np.full((N, H, Nu), np.nan, np.float32)
+    check(lib.mbd_debug_knot_noise_host(key_array(key), impl, N, H, Nu, W.shape[1], np_ptr(W), None if g is None else np_ptr(g),
+                                        np_ptr(out)))
     return out
 
 

@@ -145,6 +145,15 @@ class Sweep:
     def clear_noise_shape(self):
         _capi.check(self.lib.mbd_sweep_set_noise_shape(self.h, None))
 
+    def set_noise_basis(self, W, when: str = "always"):
+        """One noise basis for all plans of the sweep (``Plan.set_noise_basis``), with the same guarantee; None clears."""
+        if W is None:
+            _capi.check(self.lib.mbd_sweep_set_noise_basis(self.h, None))
+            return
+        rec, keep = _basis_record(W, when, self.H)
+        _capi.check(self.lib.mbd_sweep_set_noise_basis(self.h, C.byref(rec)))
+        del keep  # (the set call has copied the table)
+
     def get_sigmas(self):
         """path-integral sweeps: every plan's carried sigma after the last run (path_integral.py:113,131)."""
         out = np.zeros(self.P, np.float32)
@@ -191,6 +200,20 @@ def _noise_record(scale, when, H, Nu):
     rec.scale = g.ctypes.data_as(C.POINTER(C.c_float))
     rec.rows, rec.cols, rec.when = g.shape[0], g.shape[1], _capi.NOISE_WHEN[when]
     return rec, g
+
+
+def _basis_record(W, when, H):
+    """The mbd_noise_basis of ``set_noise_basis``'s arguments, and the float32 array its pointer reads (``W`` [H, n_knots]; a
+    table of another size or with non-finite values goes to the library, which names the field)."""
+    if when not in _capi.NOISE_WHEN:
+        raise ValueError(f"when={when!r}: one of {sorted(_capi.NOISE_WHEN)}")
+    W = np.ascontiguousarray(W, np.float32)
+    if W.ndim != 2 or W.shape[0] != H:
+        raise ValueError(f"noise basis of shape {W.shape}: must be [Hsample={H}, n_knots]")
+    rec = _capi.NoiseBasis()
+    rec.basis = W.ctypes.data_as(C.POINTER(C.c_float))
+    rec.n_knots, rec.when = W.shape[1], _capi.NOISE_WHEN[when]
+    return rec, W
 
 
 def _ensemble_record(envs, risk):
@@ -318,6 +341,18 @@ class Plan:
 
     def clear_noise_shape(self):
         _capi.check(self.lib.mbd_plan_set_noise_shape(self.h, None))
+
+    def set_noise_basis(self, W, when: str = "always"):
+        """Correlate the sampling noise along the horizon (include/mbd_hip.h mbd_noise_basis): ``W`` [H, n_knots] of finite
+        values, n_knots <= 16; a step then draws normal(key, (N, n_knots, Nu)) and a candidate is
+        clip(((sum_k W[h, k] eps[n, k, a]) * shape) * sigma_i + Ybar_i) (``mpc.knot_basis`` builds interpolation and hold
+        tables).  ``when`` as ``set_noise_shape``'s, independently of the shape's.  None clears."""
+        if W is None:
+            _capi.check(self.lib.mbd_plan_set_noise_basis(self.h, None))
+            return
+        rec, keep = _basis_record(W, when, self.H)
+        _capi.check(self.lib.mbd_plan_set_noise_basis(self.h, C.byref(rec)))
+        del keep  # (the set call has copied the table)
 
     def peek_ensemble(self):
         """The last step's per-member rewards [M, N] and combined rewards [N] (a plan with an ensemble record)."""

@@ -37,6 +37,14 @@ up to S times sigma_K (``tail_shape``) in the ticks t >= 1 only, so tick 0 stays
 is in force in every step, tick 0 included.  One or the other; a batch of episodes shares it.
 
     python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --tail_rows 5 --tail_sigma 4
+
+The sampling noise is white along the horizon: Hsample independent normals per actuator, which the body low-pass filters.  A
+noise basis (include/mbd_hip.h mbd_noise_basis; DESIGN.md section 1 "N8 noise basis") draws ``--noise_knots K`` normals per
+actuator instead and spreads them over the rows (``knot_basis``): ``--noise_interp linear`` interpolates between K knots,
+``hold`` keeps each for Hsample / K rows; every row keeps the variance sigma_i^2.  In force in every step, tick 0 included,
+and composable with the tail ramp, which then scales the correlated noise.
+
+    python -m mbd_hip.planners.mpc --env_name humanoidrun --warm_steps 20 --noise_knots 10 --noise_interp linear
 """
 from __future__ import annotations
 
@@ -72,6 +80,8 @@ class MpcArgs(Args):
     tail_rows: int = 0  # the last tail_rows horizon rows of every warm tick (t >= 1) sample with more noise ...
     tail_sigma: float = 1.0  # ... ramping up to tail_sigma times sigma_K at the last row (tail_shape)
     noise_shape: str = ""  # FILE.npy: a noise shape [Hsample, Nu] (or what broadcasts to it) in force in every step
+    noise_knots: int = 0  # 0: white noise along the horizon; K: K knot normals per actuator in every step (knot_basis) ...
+    noise_interp: str = "linear"  # ... interpolated between the knots ("linear") or held ("hold")
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -159,6 +169,50 @@ def _shape_settings(args: MpcArgs) -> dict:
     return {f: getattr(args, f) for f in _SHAPE_FIELDS}
 
 
+_BASIS_FIELDS = ("noise_knots", "noise_interp")
+_BASIS_KINDS = ("linear", "hold")
+
+
+def knot_basis(H: int, n_knots: int, kind: str = "linear", normalise: bool = True) -> np.ndarray:
+    """The noise basis W [H, n_knots] of ``Plan.set_noise_basis``: "linear" — hat functions at the knots
+    t_k = k (H - 1) / (n_knots - 1), so row h interpolates between the two knots around it and its weights sum to 1 (one
+    knot: a constant column); "hold" — row h takes knot floor(h n_knots / H).  ``normalise`` divides every row by its
+    Euclidean norm, so that every row keeps the variance sigma^2.  Computed in float64, cast once to float32."""
+    H, K = int(H), int(n_knots)
+    if H < 1:
+        raise ValueError(f"Hsample={H}: must be >= 1")
+    if not 1 <= K <= _capi.MAX_KNOTS:
+        raise ValueError(f"noise_knots={K} outside [1, {_capi.MAX_KNOTS}]")
+    if kind not in _BASIS_KINDS:
+        raise ValueError(f"noise_interp={kind!r}: one of {list(_BASIS_KINDS)}")
+    W = np.zeros((H, K), np.float64)
+    h = np.arange(H, dtype=np.float64)
+    if kind == "hold":
+        W[np.arange(H), (np.arange(H) * K) // H] = 1.0
+    elif K == 1 or H == 1:
+        W[:, 0] = 1.0
+    else:
+        t = np.arange(K, dtype=np.float64) * (H - 1) / (K - 1)
+        W = np.maximum(0.0, 1.0 - np.abs(h[:, None] - t[None, :]) * (K - 1) / (H - 1))
+    if normalise:
+        W = W / np.sqrt((W * W).sum(axis=1, keepdims=True))
+    return np.ascontiguousarray(W.astype(np.float32))
+
+
+def _has_basis(args: MpcArgs) -> bool:
+    """Whether the arguments ask for a noise basis at all (the default: none)."""
+    return args.noise_knots != 0
+
+
+def _basis_of(args: MpcArgs):
+    """(W, when) of the arguments' noise basis: in force in every step."""
+    return knot_basis(args.Hsample, args.noise_knots, args.noise_interp), "always"
+
+
+def _basis_settings(args: MpcArgs) -> dict:
+    return {f: getattr(args, f) for f in _BASIS_FIELDS}
+
+
 def _plant_env(env, args: MpcArgs, device: int, cache: dict = None):
     """The env that executes the rows: None (the planner's own) unless mass / friction / gear differ from 1; one env per
     distinct triple in ``cache``."""
@@ -204,6 +258,8 @@ def _setup(args: MpcArgs, device: int):
         plan.set_ensemble(_ensemble_envs(env, args, device, cache), args.ens_risk)
     if _has_shape(args):
         plan.set_noise_shape(*_shape_of(args, env.action_size))
+    if _has_basis(args):
+        plan.set_noise_basis(*_basis_of(args))
     return env, plan, state_init, rng_exp
 
 
@@ -245,6 +301,8 @@ def _setup_batch(arg_list, device: int):
     sweep = Sweep(env, a0, len(arg_list), temps=[a.temp_sample for a in arg_list])
     if _has_shape(a0):  # (one shape for all episodes: _check_batch has held the three fields equal)
         sweep.set_noise_shape(*_shape_of(a0, env.action_size))
+    if _has_basis(a0):  # (and one basis)
+        sweep.set_noise_basis(*_basis_of(a0))
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -278,6 +336,8 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
         _save(arg_list[0], ep if len(arg_list) > 1 else {k: ep[k][0] for k in _LOGS})
     if return_details:
         shape = _shape_settings(arg_list[0]) if _has_shape(arg_list[0]) else {}
+        if _has_basis(arg_list[0]):
+            shape = dict(shape, **_basis_settings(arg_list[0]))
         return rewards, [dict({f: ep[f][k] for f in _LOGS}, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
                               **_plant_settings(arg_list[k]), **shape) for k in range(len(arg_list))]
     return rewards
@@ -306,6 +366,8 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
     if return_details:
         ens = _ensemble_settings(args) if _has_ensemble(args) else {}
         shape = _shape_settings(args) if _has_shape(args) else {}
+        if _has_basis(args):
+            shape = dict(shape, **_basis_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -356,6 +418,8 @@ def _main(argv=None) -> dict:
         res.update(_ensemble_settings(args))
     if _has_shape(args):
         res.update(_shape_settings(args))
+    if _has_basis(args):
+        res.update(_basis_settings(args))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -391,6 +455,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
             plan.set_mpc_plant(**_record_kwargs(env, a0, 0))
         if _has_shape(a0):
             plan.set_noise_shape(*_shape_of(a0, env.action_size))
+        if _has_basis(a0):
+            plan.set_noise_basis(*_basis_of(a0))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -413,6 +479,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
         res.update(_plant_settings(a0), nominal_episode_reward=float(np.mean(nominal)))
     if _has_shape(a0):
         res.update(_shape_settings(a0))
+    if _has_basis(a0):
+        res.update(_basis_settings(a0))
     if not a0.not_render:
         _save(a0, ep)
     print(json.dumps(res), flush=True)
