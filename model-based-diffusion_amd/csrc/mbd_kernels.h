@@ -1640,6 +1640,47 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
             }
             con_act[0] = act0 && !helper; con_act[1] = act1 && !helper;  // (a helper has no velocities of its own to correct)
           }
+        } else if constexpr (MAXCOL == 1 && ISO && !SPEC && !HELP) {
+          // the loop below for its one collider, on (x, y) pairs with z alone (v3p): the same operations in the same
+          // order, component by component; the cross products stay scalar on the halves of the pairs
+          const f2 ib2 = mk2(ic.ib[0], ic.ib[0]), im2 = mk2(ic.inv_mass, ic.inv_mass);
+          const v3p cpos = to_p(col_pos[0]);
+          const v3p off = rot_p(cpos, r);
+          const v3p ctr = v3p{mk2(p.x, p.y) + off.xy, p.z + off.z};
+          const float pen = col_rad[0] - ctr.z;
+          const bool active = col_has[0] && pen > 0.0f;
+          const float h = ffma(-0.5f, pen, col_rad[0]);
+          const f2 zz = mk2(ctr.z, off.z) - mk2(h, h);  // the z of the contact point and of its lever arm
+          const v3p pos = v3p{ctr.xy, zz.x};
+          const v3p rc = v3p{off.xy, zz.y};
+          // crossz(rc) = (rc.y, -rc.x, 0) and its I^-1 image, from icx = rc.xy * ib = (-icn.y, icn.x): no swizzled copy
+          const f2 icx = rc.xy * ib2;
+          const float wn = opq_(ic.inv_mass + ffma(rc.xy.y, icx.y, (-rc.xy.x) * (-icx.x)));
+          const v3p ir = irot_z_p(-h, r);
+          const v3p rl = v3p{cpos.xy + ir.xy, cpos.z + ir.z};
+          const v3p rr = rot_p(rl, r_prev);
+          const f2 pprev = mk2(p_prev.x, p_prev.y) + rr.xy;  // (dx.z is set to zero: the z of pprev is never read)
+          const f2 dx = pos.xy - pprev;
+          const float ct2 = ffma(dx.x, dx.x, dx.y * dx.y);
+          // cross_bz0(rc, dx) = (-cm.y, cm.x, cnt_z) with cm = rc.z dx, and its I^-1 image (-icm.y, icm.x, icnt_z)
+          const f2 cm = mk2(rc.z, rc.z) * dx;
+          const float cnt_z = opq_(ffma(rc.xy.x, dx.y, -(rc.xy.y * dx.x)));
+          const f2 icm = cm * ib2;
+          const float icnt_z = cnt_z * ic.ib[0];
+          const float dent = opq_(ffma(ic.inv_mass, ct2, ffma(-cm.y, -icm.y, ffma(cm.x, icm.x, cnt_z * icnt_z))));
+          const f2 q_ng = div2_pos_(mk2(pen, ct2), mk2(wn, dent + 1e-20f));
+          const float dlam = q_ng.x * coll_scale;
+          const float gt = q_ng.y;
+          const float lim = mu * dlam;
+          const bool stick = opq_(opq_(ct2 * gt) * gt) < lim * lim;
+          const f2 pt = mk2(-gt, -gt) * dx;
+          const v3p Pimp = v3p{mk2(stick ? pt.x : 0.0f, stick ? pt.y : 0.0f), dlam};
+          const v3p cr = cross_p(rc, Pimp);
+          const f2 dth_xy = cr.xy * ib2, ncd_xy = Pimp.xy * im2;
+          const f2 dn_z = mk2(cr.z, Pimp.z) * mk2(ic.ib[0], ic.inv_mass);  // (dth.z, ncd.z)
+          cd_p = sel3(active, mk3(ncd_xy.x, ncd_xy.y, dn_z.y), cd_p);
+          cd_th = sel3(active, mk3(dth_xy.x, dth_xy.y, dn_z.x), cd_th);
+          con_pos[0] = mk3(pos.xy.x, pos.xy.y, pos.z); con_dlam[0] = dlam; con_act[0] = active;
         } else {
 #pragma unroll
         for (int j = 0; j < MAXCOL; ++j) {

@@ -185,6 +185,39 @@ __device__ __forceinline__ v3x2 bcast3(v3 a) { return v3x2{mk2(a.x, a.x), mk2(a.
 __device__ __forceinline__ v3x2 scale2(v3x2 a, f2 s) { return v3x2{a.x * s, a.y * s, a.z * s}; }
 __device__ __forceinline__ f2 dot2(v3x2 a, v3x2 b) { return fma2(a.x, b.x, fma2(a.y, b.y, a.z * b.z)); }
 __device__ __forceinline__ v3x2 axpy2(f2 s, v3x2 a, v3x2 o) { return v3x2{fma2(s, a.x, o.x), fma2(s, a.y, o.y), fma2(s, a.z, o.z)}; }
+// ---- one 3-vector as an (x, y) pair and a lone z (stage (4) of the one-collider links): the component-wise operations
+// run packed on the pair; a cross product mixes all three axes in every component, so it stays scalar — it reads the
+// halves of its operands' pairs and writes the halves of its result's (a scalar instruction addresses either half of a
+// register pair for free; what costs is a packed operand whose halves live in two pairs).  The fence keeps the SLP
+// vectoriser from re-pairing the cross products' scalars across those pairs (it pays for that in v_mov).
+struct v3p {
+  f2 xy;
+  float z;
+};
+__device__ __forceinline__ float opq_(float x) { asm("" : "+v"(x)); return x; }
+__device__ __forceinline__ v3p to_p(v3 a) { return v3p{mk2(a.x, a.y), a.z}; }
+__device__ __forceinline__ v3p cross_p(v3p a, v3p b) {
+  return v3p{mk2(opq_(ffma(a.xy.y, b.z, -(a.z * b.xy.y))), opq_(ffma(a.z, b.xy.x, -(a.xy.x * b.z)))),
+             opq_(ffma(a.xy.x, b.xy.y, -(a.xy.y * b.xy.x)))};
+}
+__device__ __forceinline__ v3p rot_p(v3p v, q4 q) {
+  const v3p u{mk2(q.x, q.y), q.z};
+  v3p t = cross_p(u, v);
+  t = v3p{t.xy + t.xy, opq_(t.z + t.z)};
+  const v3p c = cross_p(u, t);
+  return v3p{fma2(mk2(q.w, q.w), t.xy, v.xy) + c.xy, opq_(opq_(ffma(q.w, t.z, v.z)) + c.z)};
+}
+// irot_z on the pair form: T = (tx, ty) comes out of one packed product and one packed sum — -(a + a) = (q.y (-d)) +
+// (q.y (-d)) exactly — and (cx, cy) = (q.z ty, -(q.z tx)) out of one more: the swaps are operand selects and the
+// negations operand modifiers of broadcast scalars — the values of irot_z
+__device__ __forceinline__ v3p irot_z_p(float d, q4 q) {
+  const f2 t0 = mk2(q.y, q.x) * mk2(-d, d);
+  const f2 t = t0 + t0;
+  const float qz = opq_(q.z);  // (a lone scalar: its broadcast with one half negated is an operand modifier)
+  const f2 cxy = mk2(qz, -qz) * mk2(t.y, t.x);
+  const float cz = opq_(ffma(-q.x, t.y, q.y * t.x));
+  return v3p{fma2(mk2(q.w, q.w), t, cxy), d + cz};
+}
 struct axes3x2 {
   v3x2 X, Y, Z;
 };
