@@ -10,9 +10,15 @@
 
 namespace mbd {
 
-RolloutKernel hot3d_kernel(const EnvShape& s, bool helpers, int rk, int nfr) {
+RolloutKernel hot3d_kernel(const EnvShape& s, bool helpers, int rk, int nfr, bool unit) {
   constexpr int D0 = 1, D1 = -4, D2 = -6;
   if (s.humanoid_shape && s.dpp_family == 0 && s.max_col <= 1) {
+    // (these two compile in the built-in humanoids' unit inverse inertia as well — mbd_kernels.h unit_inertia_form: -20 of
+    // 823 instructions per substep; a model with another inertia runs the same instantiation with the inertia at run time)
+    if (!unit) {
+      if (rk == MBD_REW_HUMANOIDRUN && nfr == 7) return rollout_kernel_rtib<16, true, false, 3, 1, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDRUN, 7>;
+      if (rk == MBD_REW_HUMANOIDTRACK && nfr == 5) return rollout_kernel_rtib<16, true, false, 3, 1, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDTRACK, 5>;
+    }
     if (rk == MBD_REW_HUMANOIDRUN && nfr == 7) return rollout_kernel<16, true, false, 3, 1, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDRUN, 7>;
     if (rk == MBD_REW_HUMANOIDTRACK && nfr == 5) return rollout_kernel<16, true, false, 3, 1, D0, D1, D2, 0, false, true, 3, false, false, MBD_REW_HUMANOIDTRACK, 5>;
     return rollout_kernel<16, true, false, 3, 1, D0, D1, D2, 0, false, true>;

@@ -285,8 +285,9 @@ struct EnsArgs {
   mbd_env* const* members = nullptr;  // [M], none NULL
 };
 // the choice of an ensemble's rollout over M N candidates, and whether ONE launch serves it (N a multiple of the candidates
-// per wavefront of that choice); otherwise launch_rollout runs M launches of N candidates, one per member
-RolloutChoice ensemble_choice(const mbd_env* env, int M, int N, int H, bool* one_launch);
+// per wavefront of that choice); otherwise launch_rollout runs M launches of N candidates, one per member.  members [M],
+// none NULL: the choice compiles in only what holds for every one of them (EnvShape::unit_ib)
+RolloutChoice ensemble_choice(const mbd_env* env, int M, mbd_env* const* members, int N, int H, bool* one_launch);
 // launch of the env's rollout instantiation; sweep as above.  ens: B is the plan's N, the outputs hold M rows of it.  d_lp: the demo log-densities [B] accumulated inside the
 // rollout (RolloutParams::lp) — only where the choice's fuses_logpd says so (the caller then passes d_lp instead of d_xpos
 // and skips launch_logpd)

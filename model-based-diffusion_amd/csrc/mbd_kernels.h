@@ -400,7 +400,7 @@ __device__ __forceinline__ int rollout_block(const RolloutParams& P) {
 
 // ---- code placement (tools/tune_phase.py) -----------------------------------------------------------------------------
 #if defined(MBD_PHASE_TUNING) || !__has_include("mbd_phase_gen.inc")
-constexpr int mbd_pad_3d(int, int) { return 0; }
+constexpr int mbd_pad_3d(int, int, int) { return 0; }
 constexpr int mbd_pad_planar(int, int, int, int, int, int, int) { return 0; }
 #else
 #include "mbd_phase_gen.inc"
@@ -982,9 +982,10 @@ __device__ __forceinline__ v3 gyro_accel(const float ib[6], const Inertia6& I, q
 
 template <int LPS, bool ISO, bool SLIDES, int MAXCH, int MAXCOL, int D0 = 0, int D1 = 0, int D2 = 0, int D3 = 0,
           bool DIAG = false, bool MULTI = true, int NS = 3, bool SLIDEW = false, bool AXI = false, int RK = -1, int NFR = 0,
-          bool HELP = false, bool SKIP6 = false, bool SPEC = false>
-__global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
+          bool HELP = false, bool SKIP6 = false, bool SPEC = false, bool UC = false>
+__device__ __forceinline__ void rollout_body(RolloutParams P) {
   constexpr bool DPP = D0 != 0;
+  static_assert(!UC || (ISO && DPP && !SPEC && !HELP && RK >= 0 && NFR > 0), "UC: the built-in humanoids' instantiations");
   static_assert(!SPEC || (!DPP && !HELP && !SKIP6 && MULTI), "SPEC: the general shuffle-exchange instantiations");
   // HELP: the link with more than two colliders runs stage (4) on slots 0, 1 and gets the corrections of its other
   // colliders from two helper lanes (LaneRec3); stage (6) stays MAXCOL slots in a row, every one from the velocities stage (5) left (Jacobi per link)
@@ -1033,6 +1034,20 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
   ip.inv_mass = R.ip_inv_mass;
 #pragma unroll
   for (int k = 0; k < (ISO ? 1 : 6); ++k) { ic.ib[k] = R.ic_ib[k]; ip.ib[k] = R.ip_ib[k]; }  // (AXI: stored remapped)
+  // UC: every link's inverse inertia is the literal 1 (x * 1.0f is x for every float: the products fold away, same bits).
+  // ic.ib is 1 on every lane that holds a link, and a padding lane holds link 0's record.  ip.ib is 0, not 1, in the
+  // record of a lane whose parent is the world (the free root, padding lanes); such a lane is no joint (is_joint = 0), and
+  // use by use nothing it computes from ip.ib differs in a value that is kept:
+  //   (1) fp_w = -(ip.ib * tot): nr_eff = -1, ang_damp = vel_damp = 0 make T, F and tot exact zeros (everything they
+  //       multiply is finite), and 0 * z and 1 * z are the same zero, sign included;
+  //   (3) wq.x = cr_p . (ip.ib cr_p) does differ (0 against |cr_p|^2) and with it den — which stays finite and >= 1e-20
+  //       either way, so the quotient c2 / den is finite and >= 0 and g = quotient * js_pos (js_pos = +0 here) is +0 both
+  //       ways; P2 = d * 0 is then the same signed zero, and dp_th = -(ip.ib * (rp x P2)) scales an exact zero again;
+  //       lin's parent half goes through ip.inv_mass = 0 and the alignment term through kang2 = (-0, 0), both from the
+  //       record, untouched;
+  //   and no lane pulls the parent-side shares fp_* / dp_* of such a lane: a link's rm mask is set only for the lanes of
+  //   its children, and the root and the padding lanes are nobody's child.
+  if constexpr (UC) { ic.ib[0] = 1.0f; ip.ib[0] = 1.0f; }
   JointConst jc;
   jc.ap_pos = mk3(R.ap_pos[0], R.ap_pos[1], R.ap_pos[2]);
   jc.ac_pos = mk3(R.ac_pos[0], R.ac_pos[1], R.ac_pos[2]);
@@ -1806,7 +1821,7 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
     {
       // code placement: the loop starts where the fewest of its 8-byte instructions straddle a 32-byte fetch boundary
       // (tools/tune_phase.py; the built-in humanoid instantiations)
-      phase_pad<(LPS == 16 && ISO && !SLIDES && MULTI && D0 == 1 && D1 == -4 && D2 == -6 && D3 == 0) ? mbd_pad_3d(MAXCOL, RK) : 0>();
+      phase_pad<(LPS == 16 && ISO && !SLIDES && MULTI && D0 == 1 && D1 == -4 && D2 == -6 && D3 == 0) ? mbd_pad_3d(MAXCOL, RK, UC ? 1 : 0) : 0>();
       // (all 7 substeps of the humanoid in line: -1.9 % on the metric config — 39 KB of loop body)
       if constexpr (NFR > 1) {
         for (int it = 0; it < 2; ++it) repeat_n<NFR / 2>(substep);
@@ -1914,5 +1929,31 @@ __global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
   }
 }
 
+// The kernels of rollout_body.  UC — every link's inverse inertia is the literal 1 — is not a parameter of theirs: the
+// instantiations that compile in a built-in one-collider humanoid's reward kind and n_frames (humanoidrun: 0, 7;
+// humanoidtrack: 3, 5; the DPP layout (+1, -4, -6)) compile in that model's unit inverse inertia as well, and serve models
+// that have it.  A humanoid of those rewards with any other inertia (Model.scaled, a custom model), and every model under
+// the lever MBD_NO_UNIT_CONST, runs the same instantiation of rollout_kernel_rtib: the inverse inertia read from the lane
+// record at run time, as everywhere else.  (mbd_hot3d.hip::hot3d_kernel is the one place that hands either out.)
+constexpr bool unit_inertia_form(int lps, bool iso, bool slides, int maxch, int maxcol, int d0, int d1, int d2, int d3, int rk,
+                                 int nfr, bool help, bool spec) {
+  return lps == 16 && iso && !slides && maxch == 3 && maxcol == 1 && d0 == 1 && d1 == -4 && d2 == -6 && d3 == 0 && !help &&
+         !spec && ((rk == MBD_REW_HUMANOIDRUN && nfr == 7) || (rk == MBD_REW_HUMANOIDTRACK && nfr == 5));
+}
+template <int LPS, bool ISO, bool SLIDES, int MAXCH, int MAXCOL, int D0 = 0, int D1 = 0, int D2 = 0, int D3 = 0,
+          bool DIAG = false, bool MULTI = true, int NS = 3, bool SLIDEW = false, bool AXI = false, int RK = -1, int NFR = 0,
+          bool HELP = false, bool SKIP6 = false, bool SPEC = false>
+__global__ __launch_bounds__(256) void rollout_kernel(RolloutParams P) {
+  rollout_body<LPS, ISO, SLIDES, MAXCH, MAXCOL, D0, D1, D2, D3, DIAG, MULTI, NS, SLIDEW, AXI, RK, NFR, HELP, SKIP6, SPEC,
+               unit_inertia_form(LPS, ISO, SLIDES, MAXCH, MAXCOL, D0, D1, D2, D3, RK, NFR, HELP, SPEC)>(P);
+}
+template <int LPS, bool ISO, bool SLIDES, int MAXCH, int MAXCOL, int D0 = 0, int D1 = 0, int D2 = 0, int D3 = 0,
+          bool DIAG = false, bool MULTI = true, int NS = 3, bool SLIDEW = false, bool AXI = false, int RK = -1, int NFR = 0,
+          bool HELP = false, bool SKIP6 = false, bool SPEC = false>
+__global__ __launch_bounds__(256) void rollout_kernel_rtib(RolloutParams P) {
+  static_assert(unit_inertia_form(LPS, ISO, SLIDES, MAXCH, MAXCOL, D0, D1, D2, D3, RK, NFR, HELP, SPEC),
+                "only where rollout_kernel compiles the unit inverse inertia in");
+  rollout_body<LPS, ISO, SLIDES, MAXCH, MAXCOL, D0, D1, D2, D3, DIAG, MULTI, NS, SLIDEW, AXI, RK, NFR, HELP, SKIP6, SPEC, false>(P);
+}
 
 }  // namespace mbd

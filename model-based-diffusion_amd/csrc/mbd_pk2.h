@@ -235,9 +235,11 @@ __device__ __forceinline__ void dpp_fetch_p(v3x2 p, q4x2 r, const float (&m)[4],
 //      (N = 32768: 3.60 -> 3.39 ms; N = 8192, one wavefront per SIMD either way: 0.97 -> 1.09 ms)
 // FAM: 0 the humanoid family (three child slots, multi-dof joints), 1 ant (four child slots, single hinges, the
 //      control-cost reward: the action row of the next control step travels with the other prefetched actions)
-template <int MAXCOL, int RK = -1, int NFR = 0, int WPE = 1, int FAM = 0>
-__global__ __launch_bounds__(256, WPE) void rollout_pk2_kernel(RolloutParams P) {
+// UC: every link's inverse inertia is the literal 1 (rollout_kernel's UC, same bits)
+template <int MAXCOL, int RK = -1, int NFR = 0, int WPE = 1, int FAM = 0, bool UC = false>
+__device__ __forceinline__ void rollout_pk2_body(RolloutParams P) {
   constexpr bool MULTI = FAM == 0;
+  static_assert(!UC || (FAM == 0 && RK >= 0 && NFR > 0), "UC: the built-in humanoids' instantiations");
   rollout_progress(P);
   if ((int)blockIdx.x >= P.roll_blocks) {  // the next step's normals, on CUs the rollout leaves idle
     noise_blocks(P);
@@ -272,7 +274,11 @@ __global__ __launch_bounds__(256, WPE) void rollout_pk2_kernel(RolloutParams P) 
 
   const int nr = R.nr;
   const int plane = base + R.plane_rel;
-  const float ic_inv_mass = R.ic_inv_mass, ip_inv_mass = R.ip_inv_mass, ic_ib = R.ic_ib[0], ip_ib = R.ip_ib[0];
+  // (UC: ip_ib is 0 in the record of the root's and the padding lanes; what that changes never reaches a kept value —
+  // the argument is rollout_kernel's, at its fold: fp_w and dp_th scale exact zeros, den stays finite and positive and its
+  // quotient meets js_pos = 0, and no rm mask points at such a lane)
+  const float ic_inv_mass = R.ic_inv_mass, ip_inv_mass = R.ip_inv_mass;
+  const float ic_ib = UC ? 1.0f : R.ic_ib[0], ip_ib = UC ? 1.0f : R.ip_ib[0];
   JointConst jc;
   jc.ap_pos = mk3(R.ap_pos[0], R.ap_pos[1], R.ap_pos[2]);
   jc.ac_pos = mk3(R.ac_pos[0], R.ac_pos[1], R.ac_pos[2]);
@@ -660,6 +666,22 @@ __global__ __launch_bounds__(256, WPE) void rollout_pk2_kernel(RolloutParams P) 
       o[7] = v.x.y; o[8] = v.y.y; o[9] = v.z.y; o[10] = w.x.y; o[11] = w.y.y; o[12] = w.z.y;
     }
   }
+}
+
+// The kernels of rollout_pk2_body, as in mbd_kernels.h: the instantiations with a one-collider humanoid's reward kind and
+// n_frames compiled in compile in its unit inverse inertia too (UC); rollout_pk2_kernel_rtib is the same instantiation with
+// the inverse inertia read at run time (other inertias, lever MBD_NO_UNIT_CONST).
+constexpr bool unit_inertia_form_pk2(int maxcol, int rk, int nfr, int fam) {
+  return fam == 0 && maxcol == 1 && ((rk == MBD_REW_HUMANOIDRUN && nfr == 7) || (rk == MBD_REW_HUMANOIDTRACK && nfr == 5));
+}
+template <int MAXCOL, int RK = -1, int NFR = 0, int WPE = 1, int FAM = 0>
+__global__ __launch_bounds__(256, WPE) void rollout_pk2_kernel(RolloutParams P) {
+  rollout_pk2_body<MAXCOL, RK, NFR, WPE, FAM, unit_inertia_form_pk2(MAXCOL, RK, NFR, FAM)>(P);
+}
+template <int MAXCOL, int RK = -1, int NFR = 0, int WPE = 1, int FAM = 0>
+__global__ __launch_bounds__(256, WPE) void rollout_pk2_kernel_rtib(RolloutParams P) {
+  static_assert(unit_inertia_form_pk2(MAXCOL, RK, NFR, FAM), "only where rollout_pk2_kernel compiles the unit inverse inertia in");
+  rollout_pk2_body<MAXCOL, RK, NFR, WPE, FAM, false>(P);
 }
 
 }  // namespace mbd

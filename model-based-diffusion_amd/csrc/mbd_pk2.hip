@@ -9,7 +9,7 @@
 
 namespace mbd {
 
-RolloutKernel pk2_kernel(int fam, int max_col, int rk, int nfr, bool no_rk, int wpe) {
+RolloutKernel pk2_kernel(int fam, int max_col, int rk, int nfr, bool no_rk, int wpe, bool unit) {
   if (no_rk) nfr = 0;  // (the run-time forms read both)
   if (fam == 1) {  // ant (the reference's default env_name: mbd_planner.py:28, run_mbd.py:14)
     if (max_col > 2 || rk != MBD_REW_ANT) return nullptr;
@@ -24,6 +24,12 @@ RolloutKernel pk2_kernel(int fam, int max_col, int rk, int nfr, bool no_rk, int 
                                                                     : rollout_pk2_kernel<5, -1, 0>;
   // (two wavefronts per SIMD: the reference's own humanoids with one collider per link; humanoidstandup's five
   // colliders do not fit 256 registers without spilling inside the substep loop — N = 16384: 4.36 -> 4.57 ms)
+  // (the forms below with a reward kind and n_frames compiled in compile in the built-in humanoids' unit inverse inertia as
+  // well — mbd_pk2.h unit_inertia_form_pk2; any other inertia: the same instantiation with the inertia at run time)
+  if (!unit && rk == MBD_REW_HUMANOIDRUN && nfr == 7)
+    return wpe == 2 ? rollout_pk2_kernel_rtib<1, MBD_REW_HUMANOIDRUN, 7, 2> : rollout_pk2_kernel_rtib<1, MBD_REW_HUMANOIDRUN, 7>;
+  if (!unit && rk == MBD_REW_HUMANOIDTRACK && nfr == 5)
+    return wpe == 2 ? rollout_pk2_kernel_rtib<1, MBD_REW_HUMANOIDTRACK, 5, 2> : rollout_pk2_kernel_rtib<1, MBD_REW_HUMANOIDTRACK, 5>;
   if (rk == MBD_REW_HUMANOIDRUN && nfr == 7)
     return wpe == 2 ? rollout_pk2_kernel<1, MBD_REW_HUMANOIDRUN, 7, 2> : rollout_pk2_kernel<1, MBD_REW_HUMANOIDRUN, 7>;
   if (rk == MBD_REW_HUMANOIDTRACK && nfr == 5)

@@ -268,7 +268,7 @@ extern "C" int mbd_plan_set_state0(mbd_plan* p, const float* state0) {
 static RolloutChoice plan_rollout_choice(const mbd_plan* p) {
   if (p->has_ens) {
     bool one = false;
-    const RolloutChoice c = ensemble_choice(p->env, p->ens_rec.n_members, p->cfg.Nsample, p->cfg.Hsample, &one);
+    const RolloutChoice c = ensemble_choice(p->env, p->ens_rec.n_members, p->ens_rec.members, p->cfg.Nsample, p->cfg.Hsample, &one);
     if (one) return c;
   }
   return rollout_choice(p->env, p->cfg.shard_count, p->cfg.Hsample);

@@ -16,8 +16,12 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # env -> template arguments of the instantiation launch_rollout() picks for it (csrc/mbd_env.hip)
 INSTANCES = {
+    # (these two compile in the built-in humanoids' unit inverse inertia: mbd_kernels.h unit_inertia_form; *_general: their
+    # rollout_kernel_rtib twins, which read it from the lane record and serve every other humanoid of those rewards)
     "humanoidrun": "16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,0,7",
     "humanoidtrack": "16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,3,5",
+    "humanoidrun_general": "rtib:16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,0,7",
+    "humanoidtrack_general": "rtib:16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,3,5",
     "humanoidstandup": "16,true,false,3,5,1,-4,-6,0,false,true,3,false,false,4,7",
     "humanoidstandup_help": "16,true,false,3,5,1,-4,-6,0,false,true,3,false,false,4,7,true,true",
     "ant": "16,true,false,4,2,1,-2,-4,-6,false,false,3,false,false,6,10,false,true",
@@ -40,6 +44,8 @@ INSTANCES = {
     # two candidates per lane (mbd_pk2.h: rollout_pk2_kernel<MAXCOL, RK, NFR>): the counts are per candidate PAIR
     "humanoidrun_pk2": "pk2:1,0,7",
     "humanoidtrack_pk2": "pk2:1,3,5",
+    "humanoidrun_pk2_general": "rtib:pk2:1,0,7",
+    "humanoidtrack_pk2_general": "rtib:pk2:1,3,5",
     "humanoidstandup_pk2": "pk2:5,4,7",
     "ant_pk2": "pk2:2,6,10,1,1",
 }
@@ -50,6 +56,8 @@ def count(targs):
     with tempfile.TemporaryDirectory() as td:
         src = os.path.join(td, "k.hip")
         kern, hdr = "rollout_kernel", "mbd_kernels.h"
+        rtib = targs.startswith("rtib:")  # (the twin with the inverse inertia at run time: rollout_kernel_rtib)
+        targs = targs[len("rtib:"):] if rtib else targs
         # (the flags of the translation unit an instantiation is built in, __graft_entry__.TUS: the DPP instantiations of
         # the humanoids and ant are mbd_hot3d.hip's)
         hot = targs.startswith(("16,true,false,3,1,1,-4,-6", "16,true,false,3,5,1,-4,-6", "16,true,false,4,2,1,-2,-4,-6,false,false"))
@@ -61,7 +69,7 @@ def count(targs):
             kern, hdr, targs = "rollout_pk2_kernel", "mbd_pk2.h", targs[len("pk2:"):]
             extra = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]  # (the flags of its translation unit: build())
         with open(src, "w") as f:
-            f.write(f'#include "{csrc}/{hdr}"\ntemplate __global__ void mbd::{kern}<{targs}>(mbd::RolloutParams);\n')
+            f.write(f'#include "{csrc}/{hdr}"\ntemplate __global__ void mbd::{kern}{"_rtib" if rtib else ""}<{targs}>(mbd::RolloutParams);\n')
         out = os.path.join(td, "k.s")
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                         "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", *extra, *os.environ.get("MBD_COUNT_DEFS", "").split(),

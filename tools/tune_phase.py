@@ -23,10 +23,14 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fn
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-DMBD_PHASE_TUNING", "-S", "--cuda-device-only"]
 # (kind, template arguments, key of the generated table)
 TARGETS = [
-    ("3d", "16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,0,7", (1, 0)),  # humanoidrun
-    ("3d", "16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,3,5", (1, 3)),  # humanoidtrack
-    ("3d", "16,true,false,3,5,1,-4,-6,0,false,true,3,false,false,4,7", (5, 4)),  # humanoidstandup
-    ("3d", "16,true,false,3,1,1,-4,-6,0,false,true", (1, -1)),                    # humanoid-shaped, other rewards
+    # (3-D keys: MAXCOL, RK, UC — the forms with the unit inverse inertia compiled in are different code from their
+    # rollout_kernel_rtib twins, "3d_rtib", and get pads of their own)
+    ("3d", "16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,0,7", (1, 0, 1)),  # humanoidrun
+    ("3d", "16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,3,5", (1, 3, 1)),  # humanoidtrack
+    ("3d_rtib", "16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,0,7", (1, 0, 0)),  # ... with another inertia
+    ("3d_rtib", "16,true,false,3,1,1,-4,-6,0,false,true,3,false,false,3,5", (1, 3, 0)),
+    ("3d", "16,true,false,3,5,1,-4,-6,0,false,true,3,false,false,4,7", (5, 4, 0)),  # humanoidstandup
+    ("3d", "16,true,false,3,1,1,-4,-6,0,false,true", (1, -1, 0)),                    # humanoid-shaped, other rewards
     ("planar", "4,2,1,0,0,1,20", (4, 2, 1, 0, 0, 1, 20)),      # hopper
     ("planar", "8,2,1,-3,0,1,20", (8, 2, 1, -3, 0, 1, 20)),    # walker2d
     ("planar", "8,2,1,-3,1,2,16", (8, 2, 1, -3, 1, 2, 16)),    # halfcheetah
@@ -63,6 +67,8 @@ def substep_loop(asm_lines):
 def analyse(kind, targs, tuned=False):
     """tuned=True: compile WITH the generated pads (what the library gets): `now` is then the count to expect."""
     hdr, kern = ("mbd_planar.h", "rollout_planar_kernel") if kind == "planar" else ("mbd_kernels.h", "rollout_kernel")
+    if kind == "3d_rtib":
+        kern = "rollout_kernel_rtib"
     with tempfile.TemporaryDirectory() as td:
         src, asm, obj = (os.path.join(td, n) for n in ("k.hip", "k.s", "k.o"))
         with open(src, "w") as f:
@@ -121,14 +127,14 @@ def _write(path, res, verbose):
         if verbose:
             print(f"{kind:6s} <{targs}>: loop of {r['instructions']} instructions, straddles by shift {r['straddles']} "
                   f"-> {r['pad']} s_nop ({r['now']} -> {r['straddles'][r['shift']]})", file=sys.stderr)
-        (rows3 if kind == "3d" else rowsp).append((key, r))
+        (rows3 if kind.startswith("3d") else rowsp).append((key, r))
     with open(path + ".tmp", "w") as f:
         f.write("// generated by tools/tune_phase.py — do not edit.  s_nop 0 (4 bytes each) in front of the unrolled substep loop\n"
                 "// of the instantiations the built-in models run: the shift that leaves the fewest 8-byte instructions\n"
                 "// straddling a 32-byte fetch boundary (straddles per loop iteration before -> after in the comments).\n")
-        f.write("constexpr int mbd_pad_3d(int maxcol, int rk) {\n  return ")
-        for (mc, rk), r in rows3:
-            f.write(f"(maxcol == {mc} && rk == {rk}) ? {r['pad']} /* {r['now']} -> {r['straddles'][r['shift']]} */\n       : ")
+        f.write("constexpr int mbd_pad_3d(int maxcol, int rk, int uc) {\n  return ")
+        for (mc, rk, uc), r in rows3:
+            f.write(f"(maxcol == {mc} && rk == {rk} && uc == {uc}) ? {r['pad']} /* {r['now']} -> {r['straddles'][r['shift']]} */\n       : ")
         f.write("0;\n}\n")
         f.write("constexpr int mbd_pad_planar(int lps, int maxcol, int d0, int d1, int fl, int rk, int nfr) {\n  return ")
         for (lps, mc, d0, d1, fl, rk, nfr), r in rowsp:
