@@ -282,7 +282,11 @@ int mbd_model_forward(const mbd_model_t* model, const float* q, const float* qd,
  *                                  (car2d: [B][H][3] = q).  Only what eval_xref_logpd consumes of the
  *                                  reference's `pipline_states` output.
  *   d_state_final : [B][state_size] or NULL
- * asynchronous on `stream`. */
+ * asynchronous on `stream`.
+ * Candidates are independent, also where one of them leaves the finite numbers (a rollout that diverges from finite inputs:
+ * summed contacts, a huge gear): every other candidate's rewards, positions and final state are bit for bit what they are
+ * without it, in every launch form, and the diverged candidate's outputs are non-finite wherever the specification's are —
+ * never a finite number that hides it.  (NaN payloads and which non-finite value appears are not part of the contract.) */
 int mbd_env_rollout(mbd_env* env, const float* d_state0, const float* d_us, int B, int H,
                     float* d_rewss, float* d_xpos, float* d_state_final, void* stream);
 
@@ -574,7 +578,9 @@ int mbd_sweep_destroy(mbd_sweep* sweep);
 int mbd_sweep_set_state0(mbd_sweep* sweep, int k, const float* state0);
 /* the P reverse loops + final evaluations (mbd_planner.py:138-148,179-180).  keys: [n_plans][2] = rng_exp of each
  * plan (:150).  HOST outputs, any may be NULL: mu_0ts_out [n_plans][Ndiffuse-1][H][Nu], rew_means_out
- * [n_plans][Ndiffuse-1], rew_final_out [n_plans]; loop_seconds_out: wall time of the lockstep loop.  Synchronous. */
+ * [n_plans][Ndiffuse-1], rew_final_out [n_plans]; loop_seconds_out: wall time of the lockstep loop.  Synchronous.
+ * Every plan's outputs are bit-identical to mbd_plan_run on its own WHATEVER the other plans do: a plan whose rollouts diverge
+ * (non-finite rewards, a NaN mean) leaves the others' bits alone, whichever lanes their candidates share in the one launch. */
 int mbd_sweep_run(mbd_sweep* sweep, const uint32_t* keys, float* mu_0ts_out, float* rew_means_out,
                   float* rew_final_out, double* loop_seconds_out);
 /* ---- batched receding horizon (no counterpart in the reference, which plans open loop; DESIGN.md section 1 "N5 batched") ---- */
@@ -588,6 +594,9 @@ int mbd_sweep_run(mbd_sweep* sweep, const uint32_t* keys, float* mu_0ts_out, flo
  * [n_plans][T+1][state_size], means_out [n_plans][T][H][Nu]; loop_seconds_out: wall time of the tick loop.  Synchronous; one
  * device->host copy per output at the end.  The sweep's start states are unchanged afterwards, whatever the outcome: a following
  * mbd_sweep_run equals a fresh sweep's.
+ * The "bit for bit" above holds whatever the other episodes do: an episode that diverges — from its start state, or on its
+ * plant — carries non-finite states and rewards from there on and leaves the other episodes' bits alone, in the planning
+ * launches and in the launch that executes every episode's rows side by side.
  * MBD sweeps only (update_method 0, no demos): NULL sweep / config / keys and out-of-range fields -> MBD_ERR_INVALID (the NULL
  * checks before any device access), enable_demo or a path-integral update -> MBD_ERR_UNSUPPORTED. */
 int mbd_sweep_run_mpc(mbd_sweep* sweep, const mbd_mpc_config* mc, const uint32_t* keys, float* actions_out,

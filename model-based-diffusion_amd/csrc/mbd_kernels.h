@@ -160,33 +160,36 @@ __device__ __forceinline__ float dpp_from(float x) {
   constexpr int ctrl = K > 0 ? 0x100 + K /* row_shl:K */ : 0x110 - K /* row_shr:-K */;
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, 0xf, 0xf, true));
 }
+// CONFINED forms, for the layouts that put several candidates into one row (LPS < 16): there lane i+K of a read that the
+// lane's 0/1 mask discards belongs to the NEIGHBOURING candidate (or to a padding lane that read it), and a product with
+// 0.0f passes that candidate's NaN / Inf on.  These discard by bits instead: dpp_from_and<K>(x, bits) is the value of x in
+// lane i+K under bits = ~0 and +0.0f under bits = 0 (one v_and_b32_dpp, the count of the v_mul_f32_dpp it replaces, where
+// the compiler cannot see that bits is all or none; a select after a v_mov_b32_dpp where it can);
+// dpp_add_if<K>(on, acc, x) is acc + x(lane i+K) where `on` and acc ITSELF elsewhere (the checker's "add the children that
+// exist", which keeps an acc of -0.0f).  tests/test_gpu_containment.py holds every layout to it.
+template <int K>
+__device__ __forceinline__ float dpp_from_and(float x, int bits) {
+  return __builtin_bit_cast(float, __builtin_bit_cast(int, dpp_from<K>(x)) & bits);
+}
+template <int K>
+__device__ __forceinline__ float dpp_add_if(bool on, float acc, float x) {
+  const float s = acc + dpp_from<K>(x);
+  return on ? s : acc;
+}
 // v_fmac_f32 with a DPP source is not something the compiler forms (it keeps v_mov_b32_dpp + v_fmac_f32), so the
 // accumulating forms are written out.  acc += x(lane i+K) * m is bit-identical to an add when m is 1.0f and a
-// no-op when m is 0.0f.  The leading "s_nop 1" covers the hazard of a DPP read within two wait states of a VALU
+// no-op when m is 0.0f AND x IS FINITE: the forms below serve the layouts of one candidate per row (LPS = 16), where lane
+// i+K is a lane of the same candidate.  The leading "s_nop 1" covers the hazard of a DPP read within two wait states of a VALU
 // write of the same register, which the compiler cannot see inside an asm block; the accumulators are only ever
 // consumed by ordinary VALU instructions.
-// (the modifier text must be a literal inside the asm string: one specialisation per shift in use)
+// (the modifier text must be a literal inside the asm string: one block per layout in use)
+// One child slot of the layouts with SEVERAL candidates per row (LPS 4 and 8: shifts -1 and +3), confined: see above.
 template <int K>
-__device__ __forceinline__ void dpp_acc6(v3& a, v3& b, v3 x, v3 y, float m);
-#define MBD_DPP_ACC6(K, MOD)                                                                                  \
-  template <>                                                                                                 \
-  __device__ __forceinline__ void dpp_acc6<K>(v3 & a, v3 & b, v3 x, v3 y, float m) {                          \
-    asm("s_nop 1\n\t"                                                                                         \
-        "v_fmac_f32_dpp %0, %6, %12 " MOD " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                      \
-        "v_fmac_f32_dpp %1, %7, %12 " MOD " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                      \
-        "v_fmac_f32_dpp %2, %8, %12 " MOD " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                      \
-        "v_fmac_f32_dpp %3, %9, %12 " MOD " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                      \
-        "v_fmac_f32_dpp %4, %10, %12 " MOD " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                     \
-        "v_fmac_f32_dpp %5, %11, %12 " MOD " row_mask:0xf bank_mask:0xf bound_ctrl:1"                          \
-        : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(b.x), "+v"(b.y), "+v"(b.z)                                    \
-        : "v"(x.x), "v"(x.y), "v"(x.z), "v"(y.x), "v"(y.y), "v"(y.z), "v"(m));                                \
-  }
-MBD_DPP_ACC6(-1, "row_shr:1")
-MBD_DPP_ACC6(4, "row_shl:4")
-MBD_DPP_ACC6(6, "row_shl:6")
-MBD_DPP_ACC6(3, "row_shl:3")
-MBD_DPP_ACC6(2, "row_shl:2")
-#undef MBD_DPP_ACC6
+__device__ __forceinline__ void dpp_acc6(v3& a, v3& b, v3 x, v3 y, float m) {
+  const bool on = m != 0.0f;
+  a = v3{dpp_add_if<K>(on, a.x, x.x), dpp_add_if<K>(on, a.y, x.y), dpp_add_if<K>(on, a.z, x.z)};
+  b = v3{dpp_add_if<K>(on, b.x, y.x), dpp_add_if<K>(on, b.y, y.y), dpp_add_if<K>(on, b.z, y.z)};
+}
 // The three child slots of the humanoid layout (shifts -1, +4, +6) in ONE block: one hazard s_nop for 18 accumulations
 // (an "s_nop 1" costs a lone wavefront two whole issue slots, tools/probes/probe_issue.hip).
 #define MBD_F6(MOD, M)                                                                                        \
@@ -288,24 +291,22 @@ __device__ __forceinline__ void dpp_fetch7x4_ant(v3 p, q4 r, float m0, float m1,
   Pp = v3{o0, o1, o2};
   Pr = q4{o3, o4, o5, o6};
 }
-// trees with at most two children per link (walker2d, halfcheetah: D = (+1, -3)) and chains (hopper, cartpole)
+// trees with at most two children per link (walker2d, halfcheetah: D = (+1, -3)) and chains (hopper, cartpole): several
+// candidates per row, so the discarded reads are confined (dpp_from_and: the parent's bits, or +0 without a parent)
 template <>
 __device__ __forceinline__ void dpp_fetch7<1, -3, 0>(v3 p, q4 r, float m0, float m1, float, v3& Pp, q4& Pr) {
-  float o0 = dpp_from<1>(p.x) * m0, o1 = dpp_from<1>(p.y) * m0, o2 = dpp_from<1>(p.z) * m0;
-  float o3 = dpp_from<1>(r.w) * m0, o4 = dpp_from<1>(r.x) * m0, o5 = dpp_from<1>(r.y) * m0;
-  float o6 = dpp_from<1>(r.z) * m0;
-  asm("s_nop 1\n\t" MBD_DPP_F(0, 7, 14, "row_shr:3") MBD_DPP_F(1, 8, 14, "row_shr:3") MBD_DPP_F(2, 9, 14, "row_shr:3")
-          MBD_DPP_F(3, 10, 14, "row_shr:3") MBD_DPP_F(4, 11, 14, "row_shr:3") MBD_DPP_F(5, 12, 14, "row_shr:3")
-              MBD_DPP_F(6, 13, 14, "row_shr:3")
-      : "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3), "+v"(o4), "+v"(o5), "+v"(o6)
-      : "v"(p.x), "v"(p.y), "v"(p.z), "v"(r.w), "v"(r.x), "v"(r.y), "v"(r.z), "v"(m1));
-  Pp = v3{o0, o1, o2};
-  Pr = q4{o3, o4, o5, o6};
+  const int b0 = m0 != 0.0f ? -1 : 0, b1 = m1 != 0.0f ? -1 : 0;
+  auto f = [&](float x) {
+    return __builtin_bit_cast(float, __builtin_bit_cast(int, dpp_from_and<1>(x, b0)) | __builtin_bit_cast(int, dpp_from_and<-3>(x, b1)));
+  };
+  Pp = v3{f(p.x), f(p.y), f(p.z)};
+  Pr = q4{f(r.w), f(r.x), f(r.y), f(r.z)};
 }
 template <>
 __device__ __forceinline__ void dpp_fetch7<1, 0, 0>(v3 p, q4 r, float m0, float, float, v3& Pp, q4& Pr) {
-  Pp = v3{dpp_from<1>(p.x) * m0, dpp_from<1>(p.y) * m0, dpp_from<1>(p.z) * m0};
-  Pr = q4{dpp_from<1>(r.w) * m0, dpp_from<1>(r.x) * m0, dpp_from<1>(r.y) * m0, dpp_from<1>(r.z) * m0};
+  const int b0 = m0 != 0.0f ? -1 : 0;
+  Pp = v3{dpp_from_and<1>(p.x, b0), dpp_from_and<1>(p.y, b0), dpp_from_and<1>(p.z, b0)};
+  Pr = q4{dpp_from_and<1>(r.w, b0), dpp_from_and<1>(r.x, b0), dpp_from_and<1>(r.y, b0), dpp_from_and<1>(r.z, b0)};
 }
 
 // jax.random.normal(key, (N, HNu)) in flat element order, by the threads tid0, tid0 + stride, ...: legacy layout —

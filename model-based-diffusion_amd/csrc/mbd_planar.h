@@ -193,9 +193,9 @@ __global__ __launch_bounds__(256) void rollout_planar_kernel(RolloutParams P) {
     for (int j = 0; j < 2; ++j)
       if (s == 3 + j) { act_sl[j] = a; gear_sl[j] = M->act_gear[a]; alo_sl[j] = M->act_lo[a]; ahi_sl[j] = M->act_hi[a]; }
   }
-  // children: DPP masks (rm[s]: this link has an s-th child at lane - Ds; pm[s]: this link is the s-th child of its
-  // parent at lane + Ds) or source lanes of the shuffle exchange (a missing child: own lane, masked)
-  float rm[2] = {0.0f, 0.0f}, pm[2] = {0.0f, 0.0f};
+  // children: DPP masks, all bits or none (rb[s]: this link has an s-th child at lane - Ds; pb[s]: this link is the s-th
+  // child of its parent at lane + Ds) or source lanes of the shuffle exchange (a missing child: own lane, masked)
+  int rb[2] = {0, 0}, pb[2] = {0, 0};
   int child_src[NSLOT];
   float child_m[NSLOT];
   {
@@ -216,7 +216,10 @@ __global__ __launch_bounds__(256) void rollout_planar_kernel(RolloutParams P) {
         for (int c = 0; c < l; ++c) myslot += M->parent[c] == parent ? 1 : 0;
       }
 #pragma unroll
-      for (int k = 0; k < 2; ++k) { rm[k] = (k < NSLOT && child_m[k < NSLOT ? k : 0] != 0.0f) ? 1.0f : 0.0f; pm[k] = myslot == k ? 1.0f : 0.0f; }
+      for (int k = 0; k < 2; ++k) { rb[k] = (k < NSLOT && child_m[k < NSLOT ? k : 0] != 0.0f) ? -1 : 0; pb[k] = myslot == k ? -1 : 0; }
+      // (opaque: where the compiler knows them to be all bits or none it turns each v_and_b32_dpp into v_mov_b32_dpp +
+      // v_cndmask_b32, 23 instructions per substep more for the halfcheetah)
+      asm volatile("" : "+v"(pb[0]), "+v"(pb[1]), "+v"(rb[0]), "+v"(rb[1]));
     }
   }
   float colx[MAXCOL > 0 ? MAXCOL : 1], colz[MAXCOL > 0 ? MAXCOL : 1], col_rad[MAXCOL > 0 ? MAXCOL : 1];
@@ -253,8 +256,9 @@ __global__ __launch_bounds__(256) void rollout_planar_kernel(RolloutParams P) {
   // ---- exchange -----------------------------------------------------------------------------------------
   auto from_parent = [&](float v) -> float {  // the value of v in the parent's lane (0 for a world parent)
     if constexpr (DPP) {
-      float o = dpp_from<D0>(v) * pm[0];
-      if constexpr (D1 != 0) o = ffma(dpp_from<D1>(v), pm[1], o);
+      // (by bits, not by a product with the 0/1 mask: with LPS < 16 the discarded lane is the neighbouring candidate's)
+      float o = dpp_from_and<D0>(v, pb[0]);
+      if constexpr (D1 != 0) o = __builtin_bit_cast(float, __builtin_bit_cast(int, o) | __builtin_bit_cast(int, dpp_from_and<D1>(v, pb[1])));
       return o;
     } else {
       const float o = shfl(v, plane);
@@ -263,8 +267,11 @@ __global__ __launch_bounds__(256) void rollout_planar_kernel(RolloutParams P) {
   };
   auto add_children = [&](float own, float contrib) -> float {  // own + child 0 + child 1 + ..., in child order
     if constexpr (DPP) {
-      float o = ffma(dpp_from<-D0>(contrib), rm[0], own);
-      if constexpr (D1 != 0) o = ffma(dpp_from<-D1>(contrib), rm[1], o);
+      // (a slot without a child adds +0.0f — what the product form added whenever the discarded lane held a number >= +0, and
+      // always at the row's edge; adding only where there is a child, dpp_add_if, is 5 instructions per substep more for the
+      // halfcheetah: docs/experiments.md §18)
+      float o = own + dpp_from_and<-D0>(contrib, rb[0]);
+      if constexpr (D1 != 0) o = o + dpp_from_and<-D1>(contrib, rb[1]);
       return o;
     } else {
       float o = own;
