@@ -547,6 +547,52 @@ typedef struct mbd_noise_basis {
 } mbd_noise_basis;
 int mbd_plan_set_noise_basis(mbd_plan* plan, const mbd_noise_basis* rec);
 
+/* ---- planning ahead of the plant: an episode whose plans take D ticks to arrive (the real-time iteration scheme; no
+ * counterpart in the reference; DESIGN.md section 1 "N9 delay") ---- */
+/* The episode of mbd_plan_run_mpc plans from s_t and executes that plan's first rows from the same s_t: planning takes no time.
+ * A delay record gives it time.  While the system executes rows it is already committed to, the controller predicts — with the
+ * PLAN's env — where those rows will leave the system, plans from that predicted state, and commits the new rows for D ticks
+ * later.  A setting of a plan (of a sweep) beside the plant, ensemble and noise records, read by mbd_plan_run_mpc
+ * (mbd_sweep_run_mpc) only: mbd_plan_run, mbd_sweep_run and the phase calls ignore it. */
+#define MBD_MAX_MPC_DELAY 8
+typedef struct mbd_mpc_delay {
+  const float* rows0;   /* HOST [n_rows][action_size]: the rows the system is already committed to when the episode
+                           starts; NULL = zeros (n_rows must then be 0).  Copied by the set call. */
+  int32_t delay_ticks;  /* D, 1 .. MBD_MAX_MPC_DELAY: a plan made in tick t is first executed in tick t + D */
+  int32_t n_rows;       /* 0, or D * exec_steps of the run that reads the record */
+  int32_t reserved[4];  /* must be 0 */
+} mbd_mpc_delay;
+/* With a delay record, the episode of mbd_plan_run_mpc (above) becomes — everything not shown is unchanged, including the key
+ * chains, the plant record's draws and the noise `when` modes (E = exec_steps, Nu = action_size):
+ *   C = rows0 as D blocks of E rows (zeros if NULL)            the committed queue, [D][E][Nu]
+ *   per tick t:  rng, k_t = split(rng)
+ *                shat_t = final state of ONE rollout of the PLAN's env from s_t over the D*E rows of C, in queue order
+ *                         (one candidate, horizon D*E; undisturbed rows; with an ensemble record still the plan's own env)
+ *                M_t    = the plan from shat_t (i = i_start .. 1 from Ybar, key chain from k_t; ensemble, shape, basis as above)
+ *                rows   = C[0]                    (plant record with act_std > 0: C[0] + act_std * eps[0:E*Nu], as above)
+ *                rewards[tE .. tE+E), s' = rollout_PLANT(s_t, rows);  kick as above;  s_{t+1} = s'
+ *                C = C[1:] ++ M_t[0:E]            (copied: -0.0 stays -0.0)
+ *                Ybar = shift_E(M_t);  i_start = K
+ * actions_out then holds the rows the plant was fed, means_out holds M_t — whose row 0 belongs to control step (t + D) E —,
+ * states_out holds s_0 .. s_T, and mbd_plan_peek_mpc_predicted returns shat_0 .. shat_{T-1}.  Bit for bit:
+ *  - no record, or a cleared record, leaves the episode as it is without one: same launches, same bits;
+ *  - an episode of T ticks is a prefix of one of T + 1;
+ *  - tick 0's mean is mbd_plan_run(k_0) of a plan whose state0 is shat_0;
+ *  - with D = 1 and no disturbance (no plant record, or a record with plant NULL and both stds 0) the prediction launch and
+ *    the execution launch have the same inputs, so shat_t == s_{t+1}, and the delayed episode of T + 1 ticks from s_0 equals the
+ *    undelayed episode of T ticks that starts from s_1 with the same key, shifted by one tick: means_d[t] == means_u[t],
+ *    states_d[t+1] == states_u[t], actions_d[(t+1)E ..] == actions_u[tE ..] and likewise the rewards, and
+ *    actions_d[0:E] == rows0[0:E].
+ * Still no host synchronisation between ticks: the queue lives on the device, and the tick boundary's kernel advances it.
+ * The record is copied and stays until cleared (rec == NULL) or the handle is destroyed.  Refused with MBD_ERR_INVALID at the
+ * set call, before any device access, the message naming the field: a NULL handle; delay_ticks outside
+ * [1, MBD_MAX_MPC_DELAY]; non-zero reserved; rows0 NULL with n_rows != 0; rows0 non-NULL with n_rows < 1; a non-finite row
+ * value.  Refused with MBD_ERR_INVALID at the run call, before any launch: n_rows != 0 && n_rows != D * exec_steps. */
+int mbd_plan_set_mpc_delay(mbd_plan* plan, const mbd_mpc_delay* rec);
+/* the predicted states of the last episode run with a record: HOST [T][state_size] (synchronises the device).  MBD_ERR_STATE
+ * without a record, or before an episode has run with one. */
+int mbd_plan_peek_mpc_predicted(mbd_plan* plan, float* predicted_out);
+
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
  * candidates Y0s [Nsample][H][Nu] (plans that keep normals instead form them here, from the normals, sigma_i and the
  * Ybar_i of the last step — between phase 1 and phase 2 the caller's d_Ybar_i must still be unchanged), the shard's
@@ -615,6 +661,13 @@ int mbd_sweep_set_noise_shape(mbd_sweep* sweep, const mbd_noise_shape* rec);
 /* one noise basis (mbd_noise_basis, above) for all plans of the sweep, with the same guarantee.  Refusals as
  * mbd_plan_set_noise_basis's. */
 int mbd_sweep_set_noise_basis(mbd_sweep* sweep, const mbd_noise_basis* rec);
+/* one delay record (mbd_mpc_delay, above) for all episodes of the sweep: episode k of mbd_sweep_run_mpc is then
+ * mbd_plan_run_mpc on a plan of its own with the same record, bit for bit, whatever the other episodes do.  The prediction is
+ * ONE rollout launch over the n_plans episodes, one candidate each, and the n_plans * Nsample planning candidates start from
+ * the states it wrote.  Refusals as mbd_plan_set_mpc_delay's. */
+int mbd_sweep_set_mpc_delay(mbd_sweep* sweep, const mbd_mpc_delay* rec);
+/* the predicted states of the last batch run with a record: HOST [n_plans][T][state_size]; as mbd_plan_peek_mpc_predicted */
+int mbd_sweep_peek_mpc_predicted(mbd_sweep* sweep, float* predicted_out);
 /* path-integral sweeps: the carried sampling sigma of every plan after the last run (path_integral.py:113,131); HOST [n_plans] */
 int mbd_sweep_get_sigmas(mbd_sweep* sweep, float* sigmas_out);
 /* average milliseconds of the sweep's rollout launches since the last reset (hipEvents on the launch stream) */

@@ -48,6 +48,10 @@ int mbd_debug_knot_noise(const uint32_t key[2], int impl, int N, int H, int Nu, 
  * touched — a test without a GPU holds the kernel's indexing and arithmetic to the checker.  z_out HOST [N][H Nu]. */
 int mbd_debug_knot_noise_host(const uint32_t key[2], int impl, int N, int H, int Nu, int n_knots, const float* W, const float* g,
                               float* z_out);
+/* The refusals a delay record alone decides (include/mbd_hip.h mbd_mpc_delay) for a handle of that action_size: the function
+ * both set calls run on their record, host arithmetic, no device — so that a test without a GPU, which has no handle whose
+ * action_size is not 0, reaches the refusal of a non-finite row value too. */
+int mbd_debug_check_mpc_delay(const mbd_mpc_delay* rec, int action_size);
 #ifdef __cplusplus
 }
 #endif

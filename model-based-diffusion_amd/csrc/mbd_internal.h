@@ -310,6 +310,21 @@ int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc);
 int check_noise_shape(const mbd_noise_shape* rec, int Hsample, int action_size);
 // the refusals of a noise-basis record (include/mbd_hip.h mbd_noise_basis) of a handle with Hsample rows, likewise
 int check_noise_basis(const mbd_noise_basis* rec, int Hsample);
+// The delay record of a plan or a sweep (include/mbd_hip.h mbd_mpc_delay) as the handle keeps it — rows0 copied to the host, it
+// goes to the device when an episode starts — with what the two handles do alike: the refusals the record alone decides, in the
+// header's order, each naming the field (check_mpc_delay: host arithmetic, before any device access), the set call behind
+// its NULL-handle check (nullptr clears), and the run call's refusal against its exec_steps.  pred_ticks: T of the last episode
+// run with the record, 0: none yet (mbd_*_peek_mpc_predicted).
+struct DelayRec {
+  bool has = false;
+  int D = 0, n_rows = 0, pred_ticks = 0;
+  std::vector<float> rows0;  // [n_rows][action_size]
+  int set(const mbd_mpc_delay* rec, int action_size);
+  int check_run(int exec_steps) const;
+  // the committed queue of `copies` episodes at the start of an episode, [copies][D E Nu] on the device (rows0, or zeros)
+  int upload(float* d_queue, int copies, int E, int Nu, hipStream_t s) const;
+};
+int check_mpc_delay(const mbd_mpc_delay* rec, int action_size);
 // One tick of a plant's disturbance chain, dk, d_t = split(dk): advances dk, fills slot k of sp with d_t and the record's
 // deviations — the kick's only in the ticks that end with one — and says whether tick t does
 bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k);

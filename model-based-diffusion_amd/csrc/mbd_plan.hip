@@ -140,6 +140,12 @@ struct mbd_plan {
   mbd_mpc_plant plant_rec{};
   bool has_plant = false;
   DevBuf<float> d_mpc_actions, d_plant_eps, d_plant_kick;
+  // the delay record (mbd_plan_set_mpc_delay), and what an episode with one needs beyond the above: the committed queue
+  // [2][D E Nu] — a tick reads one buffer, its boundary kernel writes the advanced queue into the other — and the predicted
+  // states [T][state_size]: the prediction rollout of tick t writes slot t and the tick's planning launches start from that
+  // slot, so the states exist once.  (The executed rows are the queue's head, not the mean's: d_mpc_actions logs them.)
+  DelayRec delay;
+  DevBuf<float> d_mpc_queue, d_mpc_pred;
   // the ensemble record (mbd_plan_set_ensemble; a copy, NULL members resolved to the plan's env — the envs are the caller's)
   // and its buffers: the members' rewards r_m [M][N] and per-step rewards [M][N][H] of the rollout launch over M N
   // candidates, and the library's own copy of the combined rewards [N] (mbd_plan_peek_ensemble)
@@ -923,6 +929,79 @@ extern "C" int mbd_plan_set_mpc_plant(mbd_plan* p, const mbd_mpc_plant* rec) {
   return MBD_OK;
 }
 
+// ---- the delay record (include/mbd_hip.h mbd_mpc_delay) -----------------------------------------------------------------
+int check_mpc_delay(const mbd_mpc_delay* rec, int action_size) {
+  if (rec->delay_ticks < 1 || rec->delay_ticks > MBD_MAX_MPC_DELAY)
+    return fail(MBD_ERR_INVALID, "delay record: delay_ticks=%d outside [1, %d]", rec->delay_ticks, MBD_MAX_MPC_DELAY);
+  for (int r = 0; r < 4; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "delay record: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (!rec->rows0 && rec->n_rows != 0)
+    return fail(MBD_ERR_INVALID, "delay record: rows0 is NULL and n_rows=%d: must then be 0", rec->n_rows);
+  if (rec->rows0 && rec->n_rows < 1)
+    return fail(MBD_ERR_INVALID, "delay record: n_rows=%d with rows0 given: must be >= 1", rec->n_rows);
+  if (rec->rows0 && action_size > 0) {
+    const size_t n = (size_t)rec->n_rows * (size_t)action_size;
+    for (size_t e = 0; e < n; ++e)
+      if (!std::isfinite(rec->rows0[e]))
+        return fail(MBD_ERR_INVALID, "delay record: rows0[%d][%d]=%g: must be finite", (int)(e / action_size), (int)(e % action_size),
+                    (double)rec->rows0[e]);
+  }
+  return MBD_OK;
+}
+extern "C" int mbd_debug_check_mpc_delay(const mbd_mpc_delay* rec, int action_size) {
+  if (!rec) return fail(MBD_ERR_INVALID, "delay record is NULL");
+  if (action_size < 0) return fail(MBD_ERR_INVALID, "action_size=%d", action_size);
+  return check_mpc_delay(rec, action_size);
+}
+
+int DelayRec::set(const mbd_mpc_delay* rec, int action_size) {
+  if (!rec) {
+    *this = DelayRec{};
+    return MBD_OK;
+  }
+  MBD_TRY(check_mpc_delay(rec, action_size));
+  has = true;
+  D = rec->delay_ticks;
+  n_rows = rec->n_rows;
+  pred_ticks = 0;
+  rows0.clear();
+  if (rec->rows0) rows0.assign(rec->rows0, rec->rows0 + (size_t)rec->n_rows * (size_t)action_size);
+  return MBD_OK;
+}
+int DelayRec::check_run(int exec_steps) const {
+  if (has && n_rows != 0 && n_rows != D * exec_steps)
+    return fail(MBD_ERR_INVALID, "delay record: n_rows=%d, this run needs 0 or delay_ticks * exec_steps = %d * %d", n_rows, D,
+                exec_steps);
+  return MBD_OK;
+}
+int DelayRec::upload(float* d_queue, int copies, int E, int Nu, hipStream_t s) const {
+  const size_t Q = (size_t)D * E * Nu;
+  if (n_rows == 0) {
+    HIP_TRY(hipMemsetAsync(d_queue, 0, sizeof(float) * Q * copies, s));
+    return MBD_OK;
+  }
+  for (int k = 0; k < copies; ++k)
+    HIP_TRY(hipMemcpyAsync(d_queue + (size_t)k * Q, rows0.data(), sizeof(float) * Q, hipMemcpyHostToDevice, s));
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_mpc_delay(mbd_plan* p, const mbd_mpc_delay* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->delay.set(rec, p->Nu);
+}
+
+extern "C" int mbd_plan_peek_mpc_predicted(mbd_plan* p, float* predicted_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (!p->delay.has) return fail(MBD_ERR_STATE, "peek_mpc_predicted: the plan has no delay record");
+  if (p->delay.pred_ticks < 1) return fail(MBD_ERR_STATE, "peek_mpc_predicted: no episode has run with the record yet");
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (predicted_out)
+    HIP_TRY(hipMemcpy(predicted_out, p->d_mpc_pred, sizeof(float) * (size_t)p->delay.pred_ticks * p->env->state_size(),
+                      hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
 // ---- the ensemble record (include/mbd_hip.h mbd_ensemble) ---------------------------------------------------------------
 // the refusals of a record against the plan — host arithmetic, no launch
 static int check_ensemble(const mbd_plan* p, const mbd_ensemble* rec) {
@@ -1058,6 +1137,16 @@ extern "C" int mbd_plan_peek_ensemble(mbd_plan* p, float* rews_members_out, floa
 // mpc_plant_rows_kernel (the tick's normals, the executed rows, the kick values), the PLANT env's rollout of those rows, and
 // the boundary kernel, in the ticks that end with a kick its kick variant — so that argument is unchanged again; the
 // disturbance key chain is host arithmetic like the episode's.  Without a record: the two launches above, nothing else.
+// With a delay record (mbd_plan_set_mpc_delay) a tick gains ONE launch, in FRONT of its first diffusion step on the same stream:
+// the plan's env's rollout of the committed queue from s_t, one candidate over D E rows, whose final state is shat_t — written
+// into slot t of the predicted states, which the tick's planning launches read as their start state.  The ring's argument,
+// re-stated for it: the prediction is stream-ordered behind the previous tick's boundary (which wrote the queue it reads and
+// s_t) and in front of the tick's first rollout (which reads shat_t); it carries no progress word and no noise job, so the
+// sequence numbers the host looks for count the planning rollouts alone, as before.  The normals of the tick's first step were
+// prepared beside the PREVIOUS tick's last rollout: they depend on their key only, not on shat_t, so the extra launch is not on
+// their path — it sits between that rollout's weighted mean, which was the last reader of the buffer two steps back, and the
+// rollout that reads them, like the boundary's launches.  The boundary itself stays where it was, in its delay variant: the
+// rows executed are the queue's head, and the same launch that shifts the mean advances the queue into its other buffer.
 extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
                                 float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
@@ -1068,6 +1157,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   MBD_TRY(check_mpc_config(c, mc));
   if (c.shard_count != c.Nsample)
     return fail(MBD_ERR_STATE, "shard_count=%d of Nsample=%d: receding horizon runs unsharded plans", c.shard_count, c.Nsample);
+  MBD_TRY(p->delay.check_run(E));
   mbd_env* e = p->env;
   HIP_TRY(hipSetDevice(e->device));
   const int HNu = p->HNu, Nu = e->action_size(), S = e->state_size();
@@ -1079,8 +1169,14 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   const mbd_mpc_plant& pr = p->plant_rec;
   mbd_env* const pe = has_plant && pr.plant ? pr.plant : e;  // the env that executes the rows
   const int EN = E * Nu;
+  const bool has_delay = p->delay.has;
+  const int D = p->delay.D, Q = D * EN;  // (the committed queue: D blocks of E rows)
+  if (has_delay) {
+    HIP_TRY(p->d_mpc_queue.grow(2 * (size_t)Q));
+    HIP_TRY(p->d_mpc_pred.grow((size_t)T * S));
+  }
+  if (has_plant || has_delay) HIP_TRY(p->d_mpc_actions.grow((size_t)T * EN));
   if (has_plant) {
-    HIP_TRY(p->d_mpc_actions.grow((size_t)T * EN));
     HIP_TRY(p->d_plant_eps.grow((size_t)EN + 3));
     HIP_TRY(p->d_plant_kick.grow(3));
   }
@@ -1091,6 +1187,10 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   float* const ybar0 = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros at tick 0, shift_E(M_{t-1}) after
   HIP_TRY(hipMemsetAsync(ybar0, 0, sizeof(float) * HNu, s));
   HIP_TRY(hipMemcpyAsync(p->d_mpc_states, p->d_state0, sizeof(float) * S, hipMemcpyDeviceToDevice, s));
+  if (has_delay) {
+    MBD_TRY(p->delay.upload(p->d_mpc_queue, 1, E, Nu, s));
+    p->delay.pred_ticks = 0;
+  }
   HIP_TRY(hipStreamSynchronize(s));
   const auto t0 = std::chrono::steady_clock::now();
   uint32_t rng[2] = {key[0], key[1]}, kk[4];
@@ -1106,31 +1206,49 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
       host_split(k_next, 2, c.prng_impl, after);
     }
     const float* cur = ybar0;
+    // with a delay record: the rows the system is committed to, the prediction of where they leave it, and the plan from there
+    const float* q_in = has_delay ? p->d_mpc_queue + (size_t)(t & 1) * Q : nullptr;
+    float* q_out = has_delay ? p->d_mpc_queue + (size_t)((t + 1) & 1) * Q : nullptr;
+    const float* plan_from = s_t;
+    if (has_delay) {
+      float* shat = p->d_mpc_pred + (size_t)t * S;
+      MBD_TRY(launch_rollout(e, s_t, q_in, 1, D * E, nullptr, nullptr, nullptr, shat, s));
+      plan_from = shat;
+    }
     // the noise shape and basis: tick 0 is mbd_plan_run's loop (MBD_NOISE_WARM_TICKS: without), every later tick samples under
     // them in either mode — the first normals of tick t + 1, prepared beside this tick's last rollout, included
     const NoiseSpec ns = t == 0 ? noise_always(p) : noise_warm(p);
     for (int i = t == 0 ? Nd - 1 : K; i >= 1; --i) {
       float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
       MBD_TRY(plan_keep_in_step(p));
-      MBD_TRY(reverse_once_impl(p, s_t, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, ns, t + 1 < T ? after + 2 : nullptr,
+      MBD_TRY(reverse_once_impl(p, plan_from, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, ns, t + 1 < T ? after + 2 : nullptr,
                                 noise_warm(p)));
       cur = nxt;
     }
-    // execute M_t's first E rows from s_t, then the boundary: Ybar of tick t+1, the logs of M_t and s_{t+1}
+    // execute M_t's first E rows from s_t — with a delay record the queue's head —, then the boundary: Ybar of tick t+1, the
+    // logs of M_t and s_{t+1}
     float* s_next = p->d_mpc_state + (size_t)(t & 1) * S;
-    const float* rows = cur;
+    const float* rows = has_delay ? q_in : cur;
     bool kick_now = false;
     if (has_plant) {  // the rows the plant is fed: M_t[0:E] plus the tick's action noise, into the tick's slice of their log
       SweepPlant sp{};
       kick_now = plant_tick_draw(pr, c.prng_impl, t, dk, sp, 0);
       float* exec_rows = p->d_mpc_actions + (size_t)t * EN;
-      hipLaunchKernelGGL(mpc_plant_rows_kernel, dim3(1, 1), dim3(256), 0, s, sp, c.prng_impl, cur, 0ll, EN, p->d_plant_eps,
+      hipLaunchKernelGGL(mpc_plant_rows_kernel, dim3(1, 1), dim3(256), 0, s, sp, c.prng_impl, rows, 0ll, EN, p->d_plant_eps,
                          exec_rows, p->d_plant_kick);
       HIP_TRY(hipGetLastError());
       rows = exec_rows;
     }
     MBD_TRY(launch_rollout(pe, s_t, rows, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr, nullptr, s_next, s));
-    if (kick_now)
+    float* const exec_log = has_plant ? nullptr : p->d_mpc_actions + (size_t)t * EN;  // (a plant's rows kernel has logged them)
+    if (has_delay && kick_now)
+      hipLaunchKernelGGL(mpc_boundary_delay_kick_kernel, dim3(1), dim3(256), 0, s, cur, HNu, EN, s_next, S,
+                         (const float*)p->d_plant_kick, planar, ybar0, p->d_mpc_means + (size_t)t * HNu,
+                         p->d_mpc_states + (size_t)(t + 1) * S, q_in, q_out, Q, exec_log);
+    else if (has_delay)
+      hipLaunchKernelGGL(mpc_boundary_delay_kernel, dim3(1), dim3(256), 0, s, cur, HNu, EN, (const float*)s_next, S, ybar0,
+                         p->d_mpc_means + (size_t)t * HNu, p->d_mpc_states + (size_t)(t + 1) * S, q_in, q_out, Q, exec_log);
+    else if (kick_now)
       hipLaunchKernelGGL(mpc_boundary_kick_kernel, dim3(1), dim3(256), 0, s, cur, HNu, EN, s_next, S,
                          (const float*)p->d_plant_kick, planar, ybar0, p->d_mpc_means + (size_t)t * HNu,
                          p->d_mpc_states + (size_t)(t + 1) * S);
@@ -1145,7 +1263,8 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
   if (rewards_out) HIP_TRY(hipMemcpy(rewards_out, p->d_mpc_rewards, sizeof(float) * (size_t)T * E, hipMemcpyDeviceToHost));
   if (states_out) HIP_TRY(hipMemcpy(states_out, p->d_mpc_states, sizeof(float) * ((size_t)T + 1) * S, hipMemcpyDeviceToHost));
-  if (has_plant) {  // (the executed rows carry the action noise: their own log)
+  if (has_delay) p->delay.pred_ticks = T;
+  if (has_plant || has_delay) {  // (the executed rows carry the action noise, or are the committed queue's: their own log)
     if (actions_out) HIP_TRY(hipMemcpy(actions_out, p->d_mpc_actions, sizeof(float) * (size_t)T * EN, hipMemcpyDeviceToHost));
     if (means_out) HIP_TRY(hipMemcpy(means_out, p->d_mpc_means, sizeof(float) * (size_t)T * HNu, hipMemcpyDeviceToHost));
   } else if (means_out || actions_out) {  // (the executed rows are M_t[0:E]: taken from the one copy of the means)

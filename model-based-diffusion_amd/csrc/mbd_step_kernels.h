@@ -298,6 +298,57 @@ static __global__ __launch_bounds__(256) void mpc_boundary_batch_kernel(const fl
   }
 }
 
+// The boundaries of an episode with a delay record (include/mbd_hip.h mbd_mpc_delay): the executed rows were the head C[0] of
+// the committed queue C [D][shift] (Q = D * shift floats), not M's.  In the same launch the queue advances into its other
+// buffer — q_out = C[1:] ++ M[0:shift]; two buffers, so that no thread overwrites what another has yet to read and the
+// launches around this one may still read q_in — and the executed block C[0] goes into the tick's slice of the log of
+// executed rows (exec_log; nullptr where mpc_plant_rows_kernel has already written the disturbed rows there).  Copies
+// throughout: -0.0 stays -0.0.
+__device__ __forceinline__ void mpc_queue_advance(const float* __restrict__ M, int shift, const float* __restrict__ q_in,
+                                                  float* __restrict__ q_out, int Q, float* __restrict__ exec_log) {
+  const int keep = Q - shift;
+  for (int e = threadIdx.x; e < Q; e += blockDim.x) q_out[e] = e < keep ? q_in[e + shift] : M[e - keep];
+  if (exec_log)
+    for (int e = threadIdx.x; e < shift; e += blockDim.x) exec_log[e] = q_in[e];
+}
+static __global__ __launch_bounds__(256) void mpc_boundary_delay_kernel(const float* __restrict__ M, int HNu, int shift,
+                                                                  const float* __restrict__ s_next, int S,
+                                                                  float* __restrict__ ybar_next, float* __restrict__ means_log,
+                                                                  float* __restrict__ states_log,
+                                                                  const float* __restrict__ q_in, float* __restrict__ q_out,
+                                                                  int Q, float* __restrict__ exec_log) {
+  mpc_boundary_body(M, HNu, shift, const_cast<float*>(s_next), S, nullptr, 0, ybar_next, means_log, states_log);
+  mpc_queue_advance(M, shift, q_in, q_out, Q, exec_log);
+}
+static __global__ __launch_bounds__(256) void mpc_boundary_delay_kick_kernel(const float* __restrict__ M, int HNu, int shift,
+                                                                       float* s_next, int S, const float* __restrict__ kick,
+                                                                       int planar, float* __restrict__ ybar_next,
+                                                                       float* __restrict__ means_log,
+                                                                       float* __restrict__ states_log,
+                                                                       const float* __restrict__ q_in,
+                                                                       float* __restrict__ q_out, int Q,
+                                                                       float* __restrict__ exec_log) {
+  mpc_boundary_body(M, HNu, shift, s_next, S, kick, planar, ybar_next, means_log, states_log);
+  mpc_queue_advance(M, shift, q_in, q_out, Q, exec_log);
+}
+// ... and mpc_boundary_batch_kernel's form (blockIdx.y = episode): the queues [P][Q]; rows [P][shift] — the compact rows the
+// rollout of the executed rows reads, here the tick's slice of their log — takes C[0] (nullptr: mpc_plant_rows_kernel forms them
+// from the queue heads)
+static __global__ __launch_bounds__(256) void mpc_boundary_delay_batch_kernel(const float* __restrict__ M, long long M_stride,
+                                                                        int HNu, int shift, float* __restrict__ ybar_next,
+                                                                        float* __restrict__ means_log,
+                                                                        const float* __restrict__ q_in,
+                                                                        float* __restrict__ q_out, int Q,
+                                                                        float* __restrict__ rows) {
+  const long long k = blockIdx.y;
+  M += k * M_stride; ybar_next += k * HNu; means_log += k * HNu;
+  for (int e = threadIdx.x; e < HNu; e += blockDim.x) {
+    means_log[e] = M[e];
+    ybar_next[e] = e < HNu - shift ? M[e + shift] : 0.0f;
+  }
+  mpc_queue_advance(M, shift, q_in + k * Q, q_out + k * Q, Q, rows ? rows + k * shift : nullptr);
+}
+
 // ---- A5: demo log-densities ------------------------------------------------------------------------------
 // HumanoidTrack.eval_xref_logpd (humanoidtrack.py:98-106): xpos [B][H][K][3], xref [K][H][3].  One workgroup per
 // candidate: its K*H terms ((clip(|x - xref|, 0, .5) / .5)^2, the candidate's 3 K H floats are contiguous) are formed in
@@ -869,6 +920,8 @@ struct SweepPlant {
 // rows[e] = M[e] + act_std * eps[e] — product and sum rounded separately, like every float32 expression of the library: the build
 // compiles with -ffp-contract=off (the checker is numpy float32; the ISA shows v_mul_f32, then v_add_f32) — or M[e] itself where
 // act_std == 0 (a copy: -0.0 stays -0.0), and the three kick values kick_std * eps[EN ..].  EN = E * Nu; M of episode k is M_stride floats further; eps [P][EN + 3] is scratch.
+// M is wherever the undisturbed rows of the tick are: the tick's mean, or with a delay record (mbd_mpc_delay) the head of the
+// committed queue, M_stride = D * EN floats apart.
 static __global__ __launch_bounds__(256) void mpc_plant_rows_kernel(SweepPlant pl, int impl, const float* __restrict__ M,
                                                               long long M_stride, int EN, float* eps, float* __restrict__ rows,
                                                               float* __restrict__ kick) {

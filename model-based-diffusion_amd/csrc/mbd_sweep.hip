@@ -54,6 +54,12 @@ struct mbd_sweep {
   mbd_mpc_plant plant_rec[MBD_SWEEP_MAX_PLANS] = {};
   bool has_plant[MBD_SWEEP_MAX_PLANS] = {};
   DevBuf<float> d_mpc_actions, d_plant_eps, d_plant_kick;
+  // the delay record of all episodes (mbd_sweep_set_mpc_delay), and what a batch with one needs beyond the above: the
+  // episodes' committed queues [2][P][D E Nu] (two buffers, as a plan's) and the predicted states, tick-major [T][P][state_size]
+  // — slice t is what the tick's prediction launch writes and what its P N planning candidates start from.  (The executed rows
+  // are the queues' heads: d_mpc_actions logs them, and the rollout of the executed rows reads its slice.)
+  DelayRec delay;
+  DevBuf<float> d_mpc_queue, d_mpc_pred;
   // the noise shape of all the sweep's plans (mbd_sweep_set_noise_shape): a plan's, with the same two accessors
   DevBuf<float> d_shape;
   bool has_shape = false;
@@ -436,6 +442,27 @@ extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant*
   return MBD_OK;
 }
 
+// one delay record for all episodes of the sweep (include/mbd_hip.h mbd_mpc_delay): host state until an episode starts
+extern "C" int mbd_sweep_set_mpc_delay(mbd_sweep* w, const mbd_mpc_delay* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  return w->delay.set(rec, w->Nu);
+}
+
+extern "C" int mbd_sweep_peek_mpc_predicted(mbd_sweep* w, float* predicted_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (!w->delay.has) return fail(MBD_ERR_STATE, "peek_mpc_predicted: the sweep has no delay record");
+  if (w->delay.pred_ticks < 1) return fail(MBD_ERR_STATE, "peek_mpc_predicted: no batch has run with the record yet");
+  HIP_TRY(hipSetDevice(w->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (!predicted_out) return MBD_OK;
+  const size_t T = (size_t)w->delay.pred_ticks, P = (size_t)w->P, S = (size_t)w->env->state_size();
+  std::vector<float> tmp(T * P * S);  // (tick-major on the device, episode-major for the caller)
+  HIP_TRY(hipMemcpy(tmp.data(), w->d_mpc_pred, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
+  for (size_t t = 0; t < T; ++t)
+    for (size_t k = 0; k < P; ++k) memcpy(predicted_out + (k * T + t) * S, tmp.data() + (t * P + k) * S, sizeof(float) * S);
+  return MBD_OK;
+}
+
 // Batched receding horizon (include/mbd_hip.h): P episodes in lockstep, the host only enqueues.  The episodes' logs are
 // tick-major on the device, so that the rollout of the executed rows writes s_{.,t+1} of all P episodes straight into slice
 // t+1 of the state log (state_final is [B][S]) and the next tick's rollouts read their start states from that same slice:
@@ -448,6 +475,14 @@ extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant*
 // launch per maximal run of consecutive episodes that share a plant handle, each over its slice of the tick's rows, rewards
 // and states, and, in the ticks where an episode is kicked, mpc_kick_batch_kernel on slice t+1 of the state log — so that
 // argument is unchanged once more; the disturbance key chains are host arithmetic.  Without records: the two launches above.
+// With a delay record (mbd_sweep_set_mpc_delay) a tick gains ONE launch in front of its first diffusion step on the sweep's
+// stream: the sweep's env's rollout of every episode's committed queue from s_{.,t}, one candidate per episode over D E rows
+// (the per-episode start states through the state stride of a sweep of one-candidate plans), writing shat_{.,t} into slice t
+// of the predicted states, where the tick's P N planning candidates start.  It is stream-ordered behind the previous tick's
+// boundary and in front of the tick's first rollout, stores nothing into the progress word and generates no normals, so the
+// steps of all ticks still count through as one loop; the normals of the tick's first step, generated on the second stream
+// beside the previous tick's last rollout, depend on their keys only and not on it.  The boundary's first kernel is the delay
+// variant: it advances the queues into their other buffer and hands the queues' heads to the rollout of the executed rows.
 extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const uint32_t* keys, float* actions_out,
                                  float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
@@ -456,6 +491,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   const mbd_plan_config& c = w->cfg;
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
   MBD_TRY(check_mpc_config(c, mc));
+  MBD_TRY(w->delay.check_run(E));
   mbd_env* e = w->env;
   HIP_TRY(hipSetDevice(e->device));
   const int P = w->P, HNu = w->HNu, Nu = e->action_size(), S = e->state_size();
@@ -467,8 +503,14 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   const int EN = E * Nu;
   bool any_plant = false;
   for (int k = 0; k < P; ++k) any_plant = any_plant || w->has_plant[k];
+  const bool has_delay = w->delay.has;
+  const int D = w->delay.D, Q = D * EN;  // (an episode's committed queue: D blocks of E rows)
+  if (has_delay) {
+    HIP_TRY(w->d_mpc_queue.grow(2 * (size_t)P * Q));
+    HIP_TRY(w->d_mpc_pred.grow((size_t)T * P * S));
+  }
+  if (any_plant || has_delay) HIP_TRY(w->d_mpc_actions.grow((size_t)T * P * EN));
   if (any_plant) {
-    HIP_TRY(w->d_mpc_actions.grow((size_t)T * P * EN));
     HIP_TRY(w->d_plant_eps.grow((size_t)P * ((size_t)(H - 1) * Nu + 3)));
     HIP_TRY(w->d_plant_kick.grow((size_t)P * 3));
   }
@@ -481,6 +523,10 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(w->aux));
   HIP_TRY(hipMemcpyAsync(w->d_mpc_states, w->d_state0, sizeof(float) * (size_t)P * S, hipMemcpyDeviceToDevice, s));  // s_{.,0}
+  if (has_delay) {
+    MBD_TRY(w->delay.upload(w->d_mpc_queue, P, E, Nu, s));
+    w->delay.pred_ticks = 0;
+  }
   HIP_TRY(hipStreamSynchronize(s));
   progress_reset(w->h_progress);
   const auto t0 = std::chrono::steady_clock::now();
@@ -502,13 +548,22 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   for (int t = 0, q = 0; t < T; ++t) {
     const float* states_t = w->d_mpc_states + (size_t)t * P * S;
     const int i_start = t == 0 ? Nd - 1 : K;
+    // with a delay record: every episode's committed rows, the prediction of where they leave it, and the plans from there
+    const float* q_in = has_delay ? w->d_mpc_queue + (size_t)(t & 1) * P * Q : nullptr;
+    float* q_out = has_delay ? w->d_mpc_queue + (size_t)((t + 1) & 1) * P * Q : nullptr;
+    const float* plan_from = states_t;
+    if (has_delay) {
+      float* shat = w->d_mpc_pred + (size_t)t * P * S;
+      MBD_TRY(launch_rollout(e, states_t, q_in, P, D * E, nullptr, nullptr, nullptr, shat, s, nullptr, exec_sw));
+      plan_from = shat;
+    }
     for (int i = i_start; i >= 1; --i, ++q) {
       const bool follows = i > 1 || t + 1 < T;
       if (i > 1) sweep_split_keys(w, r, sk);
       else if (follows) first_keys_of_tick();
       SweepStep st;
       st.q = q; st.i = i; st.slot = Nd - 1 - i;  // (K <= Nd-1: a warm tick's steps use the last K slots)
-      st.state0 = states_t;
+      st.state0 = plan_from;
       st.ybar_in = i == i_start ? (t == 0 ? w->d_zero : w->d_mpc_ybar) : w->d_mu + (size_t)(st.slot - 1) * HNu;
       st.ybar_in_stride = i == i_start ? HNu : mu_stride;
       st.next_keys = follows ? &sk : nullptr;
@@ -518,12 +573,20 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       MBD_TRY(sweep_step(w, st));
     }
     // the boundary: the logs of M_{.,t}, its first E rows and Ybar of tick t+1; then the rows executed from s_{.,t}
-    hipLaunchKernelGGL(mpc_boundary_batch_kernel, dim3(1, (unsigned)P), dim3(256), 0, s,
-                       (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, HNu, E * Nu, w->d_mpc_ybar,
-                       w->d_mpc_means + (size_t)t * P * HNu, w->d_mpc_rows);
+    // (with a delay record the rows executed are the queues' heads: into the tick's slice of their log, which the rollout
+    // reads — unless plant records form the disturbed rows there themselves)
+    float* rows_t = any_plant || has_delay ? w->d_mpc_actions + (size_t)t * P * EN : nullptr;
+    if (has_delay)
+      hipLaunchKernelGGL(mpc_boundary_delay_batch_kernel, dim3(1, (unsigned)P), dim3(256), 0, s,
+                         (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, HNu, EN, w->d_mpc_ybar,
+                         w->d_mpc_means + (size_t)t * P * HNu, q_in, q_out, Q, any_plant ? (float*)nullptr : rows_t);
+    else
+      hipLaunchKernelGGL(mpc_boundary_batch_kernel, dim3(1, (unsigned)P), dim3(256), 0, s,
+                         (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, HNu, E * Nu, w->d_mpc_ybar,
+                         w->d_mpc_means + (size_t)t * P * HNu, w->d_mpc_rows);
     HIP_TRY(hipGetLastError());
     if (!any_plant) {
-      MBD_TRY(launch_rollout(e, states_t, w->d_mpc_rows, P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr, nullptr,
+      MBD_TRY(launch_rollout(e, states_t, has_delay ? rows_t : w->d_mpc_rows.get(), P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr, nullptr,
                              w->d_mpc_states + (size_t)(t + 1) * P * S, s, nullptr, exec_sw));
       continue;
     }
@@ -531,11 +594,12 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     bool any_kick = false;
     for (int k = 0; k < P; ++k)
       if (w->has_plant[k] && plant_tick_draw(w->plant_rec[k], c.prng_impl, t, &dk[2 * k], sp, k)) any_kick = true;
-    float* rows_t = w->d_mpc_actions + (size_t)t * P * EN;
     float* rewards_t = w->d_mpc_rewards + (size_t)t * P * E;
     float* states_t1 = w->d_mpc_states + (size_t)(t + 1) * P * S;
-    hipLaunchKernelGGL(mpc_plant_rows_kernel, dim3(1, (unsigned)P), dim3(256), 0, s, sp, c.prng_impl,
-                       (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, EN, w->d_plant_eps, rows_t, w->d_plant_kick);
+    // (the undisturbed rows: the means' first E, or the queues' heads)
+    const float* rows_from = has_delay ? q_in : w->d_mu + (size_t)(Nd - 2) * HNu;
+    hipLaunchKernelGGL(mpc_plant_rows_kernel, dim3(1, (unsigned)P), dim3(256), 0, s, sp, c.prng_impl, rows_from,
+                       has_delay ? (long long)Q : mu_stride, EN, w->d_plant_eps, rows_t, w->d_plant_kick);
     HIP_TRY(hipGetLastError());
     auto plant_of = [&](int k) { return w->has_plant[k] && w->plant_rec[k].plant ? w->plant_rec[k].plant : e; };
     for (int k0 = 0; k0 < P;) {  // one launch per run of episodes that share a plant handle
@@ -574,7 +638,8 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     HIP_TRY(fetch(w->d_mpc_states, ((size_t)T + 1) * P * S));
     episode_major(states_out, T + 1, S, S);
   }
-  if (any_plant && actions_out) {  // (the executed rows carry the action noise: their own log)
+  if (has_delay) w->delay.pred_ticks = T;
+  if ((any_plant || has_delay) && actions_out) {  // (the executed rows carry the action noise, or are the queues': their own log)
     HIP_TRY(fetch(w->d_mpc_actions, (size_t)T * P * EN));
     episode_major(actions_out, T, EN, EN);
     actions_out = nullptr;

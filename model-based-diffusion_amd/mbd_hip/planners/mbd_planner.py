@@ -83,6 +83,7 @@ class Sweep:
         self.h = h
         self.Nd, self.H, self.Nu = cfg.Ndiffuse, args.Hsample, env.action_size
         self._plant_envs = {}  # episode -> the plant env of its record (kept alive: a record does not own its plant)
+        self._has_delay = False
 
     def set_state0(self, k: int, state):
         st = np.ascontiguousarray(state.pipeline_state, np.float32).reshape(-1)
@@ -121,6 +122,9 @@ class Sweep:
                                                _capi.np_ptr(out["rewards"]), _capi.np_ptr(out["states"]),
                                                _capi.np_ptr(out["means"]), C.byref(secs)))
         out["seconds"] = secs.value
+        if self._has_delay:  # (the states the ticks planned from: shat_{k,0} .. shat_{k,T-1})
+            out["predicted"] = np.zeros((P, T, S), np.float32)
+            _capi.check(self.lib.mbd_sweep_peek_mpc_predicted(self.h, _capi.np_ptr(out["predicted"])))
         return out
 
     def set_mpc_plant(self, k: int, env=None, key=None, act_std: float = 0.0, kick_std: float = 0.0, kick_every: int = 1):
@@ -154,6 +158,18 @@ class Sweep:
         _capi.check(self.lib.mbd_sweep_set_noise_basis(self.h, C.byref(rec)))
         del keep  # (the set call has copied the table)
 
+    def set_mpc_delay(self, ticks: int, rows0=None):
+        """One delay record for all episodes of the sweep (``Plan.set_mpc_delay``): episode k of ``run_mpc`` is then
+        ``Plan.run_mpc`` with the same record, bit for bit; ``run_mpc`` also returns ``predicted`` [P, T, state_size]."""
+        rec, keep = _delay_record(ticks, rows0, self.Nu)
+        _capi.check(self.lib.mbd_sweep_set_mpc_delay(self.h, C.byref(rec)))
+        self._has_delay = True
+        del keep  # (the set call has copied the rows)
+
+    def clear_mpc_delay(self):
+        _capi.check(self.lib.mbd_sweep_set_mpc_delay(self.h, None))
+        self._has_delay = False
+
     def get_sigmas(self):
         """path-integral sweeps: every plan's carried sigma after the last run (path_integral.py:113,131)."""
         out = np.zeros(self.P, np.float32)
@@ -185,6 +201,19 @@ def _plant_record(env, key, act_std, kick_std, kick_every):
     rec.key[0], rec.key[1] = int(k[0]), int(k[1])
     rec.act_std, rec.kick_std, rec.kick_every = float(act_std), float(kick_std), int(kick_every)
     return rec
+
+
+def _delay_record(ticks, rows0, Nu):
+    """The mbd_mpc_delay of ``set_mpc_delay``'s arguments, and the float32 array its pointer reads (``rows0`` [n_rows, Nu], or
+    None: zeros; rows of another count or with non-finite values go to the library, which names the field)."""
+    rec = _capi.MpcDelay()
+    rec.delay_ticks = int(ticks)
+    r = None
+    if rows0 is not None:
+        r = np.ascontiguousarray(rows0, np.float32).reshape(-1, Nu)
+        rec.rows0 = r.ctypes.data_as(C.POINTER(C.c_float))
+        rec.n_rows = r.shape[0]
+    return rec, r
 
 
 def _noise_record(scale, when, H, Nu):
@@ -256,6 +285,7 @@ class Plan:
         self.Nd, self.H, self.Nu = cfg.Ndiffuse, args.Hsample, env.action_size
         self._plant_env = None  # the plant env of the plan's record (kept alive: a record does not own its plant)
         self._ens_envs = None   # the member envs of the plan's ensemble record (kept alive likewise)
+        self._has_delay = False
 
     def schedule(self):
         a, ab, s = (np.zeros(self.Nd, np.float32) for _ in range(3))
@@ -299,7 +329,25 @@ class Plan:
                                               _capi.np_ptr(out["rewards"]), _capi.np_ptr(out["states"]),
                                               _capi.np_ptr(out["means"]), C.byref(secs)))
         out["seconds"] = secs.value
+        if self._has_delay:  # (the states the ticks planned from: shat_0 .. shat_{T-1})
+            out["predicted"] = np.zeros((T, S), np.float32)
+            _capi.check(self.lib.mbd_plan_peek_mpc_predicted(self.h, _capi.np_ptr(out["predicted"])))
         return out
+
+    def set_mpc_delay(self, ticks: int, rows0=None):
+        """Plan ahead of the plant (include/mbd_hip.h mbd_mpc_delay): a plan made in tick t of ``run_mpc`` is first executed in
+        tick t + ``ticks`` (1..8).  Meanwhile the system executes the rows it is already committed to — ``rows0``
+        [ticks * exec_steps, Nu] when the episode starts, None: zeros — and every tick plans from the state the plan's env
+        predicts those rows will reach.  ``run_mpc`` then also returns ``predicted`` [T, state_size], and ``means[t]``'s row 0
+        belongs to control step (t + ticks) * exec_steps.  ``run`` ignores it."""
+        rec, keep = _delay_record(ticks, rows0, self.Nu)
+        _capi.check(self.lib.mbd_plan_set_mpc_delay(self.h, C.byref(rec)))
+        self._has_delay = True
+        del keep  # (the set call has copied the rows)
+
+    def clear_mpc_delay(self):
+        _capi.check(self.lib.mbd_plan_set_mpc_delay(self.h, None))
+        self._has_delay = False
 
     def set_mpc_plant(self, env=None, key=None, act_std: float = 0.0, kick_std: float = 0.0, kick_every: int = 1):
         """The plant of the plan's episodes (include/mbd_hip.h mbd_mpc_plant): ``run_mpc`` then executes the rows on ``env``

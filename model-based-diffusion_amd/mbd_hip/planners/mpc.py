@@ -45,6 +45,14 @@ actuator instead and spreads them over the rows (``knot_basis``): ``--noise_inte
 and composable with the tail ramp, which then scales the correlated noise.
 
     python -m mbd_hip.planners.mpc --env_name humanoidrun --warm_steps 20 --noise_knots 10 --noise_interp linear
+
+Planning takes time.  ``--delay_ticks D`` (include/mbd_hip.h mbd_mpc_delay; DESIGN.md section 1 "N9 delay") runs the episode the
+way a real-time controller has to: the plan made in tick t is first executed in tick t + D; meanwhile the system executes the
+rows it is already committed to (zeros when the episode starts) and every tick plans from the state the planner's own model
+predicts those rows will reach.  0, the default, sets no record.  It composes with ``--n_episodes`` (one D for the batch) and
+with every plant, ensemble and noise flag; the saved episode then carries the predicted states.
+
+    python -m mbd_hip.planners.mpc --env_name humanoidrun --warm_steps 20 --delay_ticks 1 --plant_mass 1.3
 """
 from __future__ import annotations
 
@@ -82,6 +90,7 @@ class MpcArgs(Args):
     noise_shape: str = ""  # FILE.npy: a noise shape [Hsample, Nu] (or what broadcasts to it) in force in every step
     noise_knots: int = 0  # 0: white noise along the horizon; K: K knot normals per actuator in every step (knot_basis) ...
     noise_interp: str = "linear"  # ... interpolated between the knots ("linear") or held ("hold")
+    delay_ticks: int = 0  # 0: plans are executed in the tick that made them; D: D ticks later, planned from a predicted state
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -213,6 +222,15 @@ def _basis_settings(args: MpcArgs) -> dict:
     return {f: getattr(args, f) for f in _BASIS_FIELDS}
 
 
+def _has_delay(args: MpcArgs) -> bool:
+    """Whether the arguments ask for a delay record at all (the default: none)."""
+    return args.delay_ticks != 0
+
+
+def _delay_settings(args: MpcArgs) -> dict:
+    return dict(delay_ticks=args.delay_ticks) if _has_delay(args) else {}
+
+
 def _plant_env(env, args: MpcArgs, device: int, cache: dict = None):
     """The env that executes the rows: None (the planner's own) unless mass / friction / gear differ from 1; one env per
     distinct triple in ``cache``."""
@@ -260,13 +278,15 @@ def _setup(args: MpcArgs, device: int):
         plan.set_noise_shape(*_shape_of(args, env.action_size))
     if _has_basis(args):
         plan.set_noise_basis(*_basis_of(args))
+    if _has_delay(args):
+        plan.set_mpc_delay(args.delay_ticks)
     return env, plan, state_init, rng_exp
 
 
 def _check_batch(arg_list) -> None:
     """What a batch of lockstep episodes takes (the rule of scripts.run_mbd._batchable): up to 32 episodes of one rigid-body
-    env with one set of sizes, schedule and (T, K, E); seeds, temperatures and the plant settings may differ.  Decided from the
-    arguments alone."""
+    env with one set of sizes, schedule, (T, K, E) and delay_ticks; seeds, temperatures and the plant settings may differ.
+    Decided from the arguments alone."""
     from dataclasses import asdict
 
     from ..scripts.run_mbd import _resolved
@@ -303,6 +323,8 @@ def _setup_batch(arg_list, device: int):
         sweep.set_noise_shape(*_shape_of(a0, env.action_size))
     if _has_basis(a0):  # (and one basis)
         sweep.set_noise_basis(*_basis_of(a0))
+    if _has_delay(a0):  # (and one delay)
+        sweep.set_mpc_delay(a0.delay_ticks)
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -333,21 +355,26 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
         sweep.close()
     rewards = [float(r.mean()) for r in ep["rewards"]]
     if not arg_list[0].not_render:
-        _save(arg_list[0], ep if len(arg_list) > 1 else {k: ep[k][0] for k in _LOGS})
+        _save(arg_list[0], ep if len(arg_list) > 1 else {k: ep[k][0] for k in _logs(ep)})
     if return_details:
         shape = _shape_settings(arg_list[0]) if _has_shape(arg_list[0]) else {}
         if _has_basis(arg_list[0]):
             shape = dict(shape, **_basis_settings(arg_list[0]))
-        return rewards, [dict({f: ep[f][k] for f in _LOGS}, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
+        shape = dict(shape, **_delay_settings(arg_list[0]))
+        return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
                               **_plant_settings(arg_list[k]), **shape) for k in range(len(arg_list))]
     return rewards
+
+
+def _logs(ep: dict) -> tuple:
+    """The episode's logs: the four every episode has, and the predicted states of one with a delay record."""
+    return _LOGS + (("predicted",) if "predicted" in ep else ())
 
 
 def _save(args: MpcArgs, ep: dict) -> None:
     path = os.path.join(os.getcwd(), "results", args.env_name)
     os.makedirs(path, exist_ok=True)
-    np.savez_compressed(os.path.join(path, "mpc_episode.npz"), actions=ep["actions"], rewards=ep["rewards"],
-                        states=ep["states"], means=ep["means"])
+    np.savez_compressed(os.path.join(path, "mpc_episode.npz"), **{k: ep[k] for k in _logs(ep)})
 
 
 def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
@@ -368,6 +395,7 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         shape = _shape_settings(args) if _has_shape(args) else {}
         if _has_basis(args):
             shape = dict(shape, **_basis_settings(args))
+        shape = dict(shape, **_delay_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -420,6 +448,7 @@ def _main(argv=None) -> dict:
         res.update(_shape_settings(args))
     if _has_basis(args):
         res.update(_basis_settings(args))
+    res.update(_delay_settings(args))  # (without a record the line is what it always was)
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -457,6 +486,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
             plan.set_noise_shape(*_shape_of(a0, env.action_size))
         if _has_basis(a0):
             plan.set_noise_basis(*_basis_of(a0))
+        if _has_delay(a0):
+            plan.set_mpc_delay(a0.delay_ticks)
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -481,6 +512,7 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
         res.update(_shape_settings(a0))
     if _has_basis(a0):
         res.update(_basis_settings(a0))
+    res.update(_delay_settings(a0))
     if not a0.not_render:
         _save(a0, ep)
     print(json.dumps(res), flush=True)
