@@ -392,9 +392,10 @@ typedef struct mbd_mpc_config {
  * HOST outputs, each may be NULL: actions_out [T*E][Nu] (the rows executed), rewards_out [T*E], states_out
  * [T+1][state_size] (s_0 .. s_T), means_out [T][H][Nu] (M_t); loop_seconds_out: wall time of the tick loop.
  * Synchronous; ONE device->host copy per output at the end.  The plan's state0 is unchanged afterwards.
- * MBD plans only (update_method 0, unsharded, no demos): NULL plan / config / key and out-of-range fields ->
- * MBD_ERR_INVALID (the NULL checks before any device access), enable_demo or a path-integral update -> MBD_ERR_UNSUPPORTED
- * (demos are time-indexed: their clock would have to follow the episode), a sharded plan -> MBD_ERR_STATE. */
+ * MBD plans only (update_method 0, unsharded; demo plans need a demo record, mbd_plan_set_mpc_demo below): NULL plan / config /
+ * key and out-of-range fields -> MBD_ERR_INVALID (the NULL checks before any device access), enable_demo without a demo record
+ * or a path-integral update -> MBD_ERR_UNSUPPORTED (demos are time-indexed: the record is the clock that follows the episode),
+ * a sharded plan -> MBD_ERR_STATE. */
 int mbd_plan_run_mpc(mbd_plan* plan, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
                      float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out);
 
@@ -593,6 +594,43 @@ int mbd_plan_set_mpc_delay(mbd_plan* plan, const mbd_mpc_delay* rec);
  * without a record, or before an episode has run with one. */
 int mbd_plan_peek_mpc_predicted(mbd_plan* plan, float* predicted_out);
 
+/* ---- the demo clock: an episode that follows a demonstration on the episode's own clock (mbd_planner.py:116-125 is the open-
+ * loop demo step; the reference has no episode; DESIGN.md section 1 "N10 demo clock") ---- */
+/* A demo plan (enable_demo) compares its kXrefRows = 50 planned steps with the env's 50 demo rows.  In an episode the demo has to
+ * move with the system: a demo record carries a clip of any length and the row the episode starts at, and tick t plans under the
+ * window of the clip that lies ahead of the system at that tick.  A setting of a plan (of a sweep) beside the plant, delay and
+ * noise records, read by mbd_plan_run_mpc (mbd_sweep_run_mpc) only: mbd_plan_run, mbd_sweep_run and the phase calls ignore it. */
+typedef struct mbd_mpc_demo {
+  const float* clip;    /* HOST [n_track][n_rows][3] (car2d: [n_rows][2]); copied by the set call */
+  int32_t n_rows;       /* L >= 1 */
+  int32_t start_row;    /* c0 >= 0: the clip row the episode's first executed control step is compared with */
+  float   rew_xref;     /* the demo's reward level in the blend (mbd_planner.py:121), constant over the episode */
+  int32_t reserved[4];  /* must be 0 */
+} mbd_mpc_demo;
+/* With a demo record, tick t of the episode of mbd_plan_run_mpc (above) plans under (K = n_track, car2d 1; E = exec_steps; D =
+ * the delay record's delay_ticks, 0 without one)
+ *   window_t[k][h] = clip[k][min(c0 + (t + D) E + h, L - 1)]        h = 0 .. 49
+ * — rows past the clip's end hold its last row (humanoidtrack.py:38-39); with a delay record the tick plans from the state
+ * predicted for tick t + D, so its window starts there.  Every diffusion step of tick t is the demo step of mbd_plan_run with
+ * window_t in place of the env's xref and rec.rew_xref in place of the env's rew_xref; everything else of the episode — the key
+ * chains, the warm start, the shift, the executed rows, the plant, the delay queue, the noise shape and basis — is unchanged.
+ * All T windows are built by ONE launch in front of the tick loop; a tick launches nothing new.  The rollouts of the executed
+ * rows also write the tracked links' positions (car2d: x, y) of the E executed steps — the plant's, with a plant record — and
+ * ONE launch behind the tick loop compares control step n = t E + j of the episode with the clip:
+ *   err[n][k] = | x_k(n) - clip[k][min(c0 + n, L - 1)] |          (unclipped, f32: sqrtf(dx dx + dy dy + dz dz) in this order)
+ * Bit for bit: with clip = the env's own xref, c0 = 0 and rew_xref = the env's, tick 0's mean is mbd_plan_run(k_0) of the demo
+ * plan; an episode of T ticks is a prefix of one of T + 1, logs included; a plan without enable_demo is untouched.
+ * The record is copied and stays until cleared (rec == NULL) or the handle is destroyed.  Refused with MBD_ERR_INVALID before any
+ * launch, the message naming the field: a NULL handle; a NULL clip; n_rows < 1; start_row < 0; a non-finite rew_xref; non-zero
+ * reserved; an env without xref; a plan whose config has enable_demo == 0 ("the plan does not use demos"); a non-finite clip
+ * value.  A demo plan WITHOUT a record stays refused by the run call (MBD_ERR_UNSUPPORTED, enable_demo), and so does a demo plan
+ * with an ensemble record.  At the run call, MBD_ERR_INVALID: a plant env whose n_track or tracked links differ from the plan's
+ * env's. */
+int mbd_plan_set_mpc_demo(mbd_plan* plan, const mbd_mpc_demo* rec);
+/* the last episode run with a record (synchronises the device): HOST err_out [T*E][K] and windows_out [T][K][50][C] (C = 3,
+ * car2d 2); either may be NULL.  MBD_ERR_STATE without a record, or before an episode has run with one. */
+int mbd_plan_peek_mpc_track(mbd_plan* plan, float* err_out, float* windows_out);
+
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
  * candidates Y0s [Nsample][H][Nu] (plans that keep normals instead form them here, from the normals, sigma_i and the
  * Ybar_i of the last step — between phase 1 and phase 2 the caller's d_Ybar_i must still be unchanged), the shard's
@@ -643,8 +681,9 @@ int mbd_sweep_run(mbd_sweep* sweep, const uint32_t* keys, float* mu_0ts_out, flo
  * The "bit for bit" above holds whatever the other episodes do: an episode that diverges — from its start state, or on its
  * plant — carries non-finite states and rewards from there on and leaves the other episodes' bits alone, in the planning
  * launches and in the launch that executes every episode's rows side by side.
- * MBD sweeps only (update_method 0, no demos): NULL sweep / config / keys and out-of-range fields -> MBD_ERR_INVALID (the NULL
- * checks before any device access), enable_demo or a path-integral update -> MBD_ERR_UNSUPPORTED. */
+ * MBD sweeps only (update_method 0; demo sweeps need a demo record): NULL sweep / config / keys and out-of-range fields ->
+ * MBD_ERR_INVALID (the NULL checks before any device access), enable_demo without a demo record or a path-integral update ->
+ * MBD_ERR_UNSUPPORTED. */
 int mbd_sweep_run_mpc(mbd_sweep* sweep, const mbd_mpc_config* mc, const uint32_t* keys, float* actions_out,
                       float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out);
 /* The plant record of episode k (mbd_mpc_plant, above; rec == NULL clears).  With records: episode k of mbd_sweep_run_mpc is
@@ -668,6 +707,14 @@ int mbd_sweep_set_noise_basis(mbd_sweep* sweep, const mbd_noise_basis* rec);
 int mbd_sweep_set_mpc_delay(mbd_sweep* sweep, const mbd_mpc_delay* rec);
 /* the predicted states of the last batch run with a record: HOST [n_plans][T][state_size]; as mbd_plan_peek_mpc_predicted */
 int mbd_sweep_peek_mpc_predicted(mbd_sweep* sweep, float* predicted_out);
+/* one demo record (mbd_mpc_demo, above) for all episodes of the sweep — one clip and one clock: a rollout launch reads ONE demo
+ * table for all its candidates, so per-episode clips or start rows would mean other rollout kernels.  Episode k of
+ * mbd_sweep_run_mpc is then mbd_plan_run_mpc on a plan of its own with the same record, bit for bit.  Refusals as
+ * mbd_plan_set_mpc_demo's. */
+int mbd_sweep_set_mpc_demo(mbd_sweep* sweep, const mbd_mpc_demo* rec);
+/* episode k's err_out [T*E][K] and the batch's windows_out [T][K][50][3] of the last batch run with a record; as
+ * mbd_plan_peek_mpc_track; k outside [0, n_plans) -> MBD_ERR_INVALID */
+int mbd_sweep_peek_mpc_track(mbd_sweep* sweep, int k, float* err_out, float* windows_out);
 /* path-integral sweeps: the carried sampling sigma of every plan after the last run (path_integral.py:113,131); HOST [n_plans] */
 int mbd_sweep_get_sigmas(mbd_sweep* sweep, float* sigmas_out);
 /* average milliseconds of the sweep's rollout launches since the last reset (hipEvents on the launch stream) */

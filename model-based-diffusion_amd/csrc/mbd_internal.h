@@ -290,13 +290,14 @@ struct EnsArgs {
 RolloutChoice ensemble_choice(const mbd_env* env, int M, mbd_env* const* members, int N, int H, bool* one_launch);
 // launch of the env's rollout instantiation; sweep as above.  ens: B is the plan's N, the outputs hold M rows of it.  d_lp: the demo log-densities [B] accumulated inside the
 // rollout (RolloutParams::lp) — only where the choice's fuses_logpd says so (the caller then passes d_lp instead of d_xpos
-// and skips launch_logpd)
+// and skips launch_logpd).  d_xref: the demo table the launch reads in place of the env's (RolloutParams::xref; a tick's window
+// of an episode with a demo record, [n_track][kXrefRows][3]), nullptr: the env's own
 int launch_rollout(mbd_env* env, const float* d_state0, const float* d_us, int B, int H, float* d_rewss, float* d_rews,
                    float* d_xpos, float* d_state_final, hipStream_t stream, LazyArgs* lz = nullptr, const int* sweep = nullptr,
-                   float* d_lp = nullptr, const EnsArgs* ens = nullptr);
+                   float* d_lp = nullptr, const EnsArgs* ens = nullptr, const float* d_xref = nullptr);
 // whether the device is a whole 8-XCD part (the premise of the XCD-pinned launch forms)
 bool device_has_eight_xcds(const mbd_env* env);
-int launch_logpd(const mbd_env* e, const float* d_xpos, int B, int H, float* d_out, hipStream_t s);
+int launch_logpd(const mbd_env* e, const float* d_xpos, int B, int H, float* d_out, hipStream_t s, const float* d_xref = nullptr);
 // ---- defined in mbd_plan.hip -----------------------------------------------------------------------------------------
 // noise schedule (mbd_planner.py:84-87)
 void host_schedule(float beta0, float betaT, int Nd, std::vector<float>& alphas, std::vector<float>& alphas_bar,
@@ -304,7 +305,8 @@ void host_schedule(float beta0, float betaT, int Nd, std::vector<float>& alphas,
 // the refusals of a plant record (include/mbd_hip.h mbd_mpc_plant) against the env that plans — host arithmetic, no launch
 int check_mpc_plant(const mbd_env* env, const mbd_mpc_plant* rec);
 // the refusals of an episode's configuration that plans and sweeps share (include/mbd_hip.h mbd_mpc_config), in their order
-int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc);
+// (has_demo_rec: the handle carries a demo record — a demo plan without one has no clock for its demo and stays refused)
+int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc, bool has_demo_rec);
 // the refusals of a noise-shape record (include/mbd_hip.h mbd_noise_shape) against a handle's Hsample x action_size, in the
 // header's order, each naming the field — host arithmetic on the record's own table, before any device access
 int check_noise_shape(const mbd_noise_shape* rec, int Hsample, int action_size);
@@ -325,6 +327,28 @@ struct DelayRec {
   int upload(float* d_queue, int copies, int E, int Nu, hipStream_t s) const;
 };
 int check_mpc_delay(const mbd_mpc_delay* rec, int action_size);
+// The demo record of a plan or a sweep (include/mbd_hip.h mbd_mpc_demo) as the handle keeps it, with what the two handles do
+// alike.  set: the refusals in the header's order, each naming the field — host arithmetic, before any device access — then the
+// clip's copy onto the env's device (nullptr clears).  K, C: the clip's tracks and floats per row (n_track and 3; car2d 1 and 2).
+// An episode grows the buffers (start), fills the window table in one launch (start), hands tick t its window (window) and the
+// executed rows' rollout its slice of the position log, and ends with the error launch (finish).  ticks / exec / episodes: T, E
+// and P of the last episode run with the record, 0: none yet (mbd_*_peek_mpc_track).
+struct DemoRec {
+  bool has = false;
+  int L = 0, c0 = 0, K = 1, C = 3;
+  float rew_xref = 0.0f;
+  int ticks = 0, exec = 0, episodes = 0;
+  DevBuf<float> d_clip, d_windows, d_xlog, d_err;
+  int set(const mbd_env* env, const mbd_plan_config& cfg, const mbd_mpc_demo* rec);
+  // the plant env of an episode with the record: the positions it writes must be the tracked links' of the plan's env
+  int check_plant(const mbd_env* env, const mbd_env* plant) const;
+  int start(int T, int P, int E, int D, hipStream_t s);
+  const float* window(int t) const { return d_windows + (size_t)t * K * kXrefRows * C; }
+  float* xlog(int t, int P, int E, int k = 0) const { return d_xlog + ((size_t)t * P + k) * E * K * 3; }
+  int finish(int T, int P, int E, hipStream_t s);
+  // HOST err_out [T E][K] and windows_out [T][K][kXrefRows][C] of episode k of the last run; either may be NULL
+  int peek(int device, int k, float* err_out, float* windows_out, const char* what) const;
+};
 // One tick of a plant's disturbance chain, dk, d_t = split(dk): advances dk, fills slot k of sp with d_t and the record's
 // deviations — the kick's only in the ticks that end with one — and says whether tick t does
 bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k);

@@ -146,6 +146,9 @@ struct mbd_plan {
   // slot, so the states exist once.  (The executed rows are the queue's head, not the mean's: d_mpc_actions logs them.)
   DelayRec delay;
   DevBuf<float> d_mpc_queue, d_mpc_pred;
+  // the demo record (mbd_plan_set_mpc_demo) with its buffers: the clip, the table of every tick's window, the log of the
+  // executed steps' tracked positions and their distances from the clip
+  DemoRec demo;
   // the ensemble record (mbd_plan_set_ensemble; a copy, NULL members resolved to the plan's env — the envs are the caller's)
   // and its buffers: the members' rewards r_m [M][N] and per-step rewards [M][N][H] of the rollout launch over M N
   // candidates, and the library's own copy of the combined rewards [N] (mbd_plan_peek_ensemble)
@@ -481,8 +484,10 @@ static int finish_noise_job(mbd_plan* p, const LazyArgs& lz, bool marked) {
 
 // phase 1 of a step, from d_state0: the plan's own start state (mbd_plan_sample_rollout), or an episode's executed state;
 // ns: the noise shape and basis the step samples under
+// d_xref: the demo table the step's log-densities are taken against, nullptr: the env's own (a tick's window: DemoRec)
 static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i, float* d_rews_local,
-                               float* d_logpd_local, hipStream_t s, const float* d_state0, const NoiseSpec& ns) {
+                               float* d_logpd_local, hipStream_t s, const float* d_state0, const NoiseSpec& ns,
+                               const float* d_xref = nullptr) {
   if (!p || !key_sample || !d_Ybar_i || !d_rews_local) return fail(MBD_ERR_INVALID, "NULL argument");
   const mbd_plan_config& c = p->cfg;
   if (i < 1 || i >= c.Ndiffuse) return fail(MBD_ERR_INVALID, "diffusion index %d outside [1,%d)", i, c.Ndiffuse);
@@ -529,11 +534,11 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
   } else {
     MBD_TRY(launch_rollout(e, d_state0, d_cand + (size_t)c.shard_begin * HNu, c.shard_count, H, p->d_rewss, d_rews_local,
                            (c.enable_demo && !fused_lp) ? p->d_xpos.get() : nullptr, nullptr, s, p->lazy ? &lz : nullptr,
-                           nullptr, fused_lp ? d_logpd_local : nullptr));
+                           nullptr, fused_lp ? d_logpd_local : nullptr, nullptr, d_xref));
   }
   MBD_TRY(p->timing.end(s));
   MBD_TRY(finish_noise_job(p, lz, marked));
-  if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, p->d_xpos, c.shard_count, H, d_logpd_local, s));
+  if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, p->d_xpos, c.shard_count, H, d_logpd_local, s, d_xref));
   return MBD_OK;
 }
 
@@ -543,10 +548,10 @@ extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sa
                              p ? p->d_state0.get() : nullptr, p ? noise_always(p) : NoiseSpec{});
 }
 
-extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
-                                     const float* d_rews_all, const float* d_logpd_all, float* d_Ybar_im1,
-                                     float* d_rew_mean, void* stream_) {
-  (void)key_sample;  // the candidates (or their normals) of all N are already resident from phase 1 of this step
+// phase 2 of a step; rew_xref: the demo's reward level in the blend — the env's (mbd_plan_score_update), or an episode's
+// demo record's
+static int plan_score_update(mbd_plan* p, int i, const float* d_Ybar_i, const float* d_rews_all, const float* d_logpd_all,
+                             float* d_Ybar_im1, float* d_rew_mean, void* stream_, float rew_xref) {
   if (!p || !d_Ybar_i || !d_rews_all || !d_Ybar_im1 || !d_rew_mean) return fail(MBD_ERR_INVALID, "NULL argument");
   const mbd_plan_config& c = p->cfg;
   if (i < 1 || i >= c.Ndiffuse) return fail(MBD_ERR_INVALID, "diffusion index %d outside [1,%d)", i, c.Ndiffuse);
@@ -571,7 +576,7 @@ extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_samp
   const bool fused_score = !split && c.update_method != 3 && (size_t)N * sizeof(float) <= 48 * 1024 && !no_fused_score;
   if (!fused_score) {
     hipLaunchKernelGGL(score_kernel, dim3(1), dim3(kScoreThreads), lds_n, s, d_rews_all,
-                       c.enable_demo ? d_logpd_all : nullptr, N, p->env->rew_xref, c.temp_sample,
+                       c.enable_demo ? d_logpd_all : nullptr, N, rew_xref, c.temp_sample,
                        c.update_method == 0 ? 1 : 0, p->d_weights, d_rew_mean, p->d_lg, PiBatch{});
     HIP_TRY(hipGetLastError());
   }
@@ -599,7 +604,7 @@ extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_samp
       if (x_env == 1 || x_env == 2 || x_env == 4 || x_env == 8) X = x_env;
       auto kern = V == 2 ? score_wmean_kernel<2> : score_wmean_kernel<1>;
       hipLaunchKernelGGL(kern, dim3(8 * ((T + X - 1) / X)), dim3(kWmE * kWmG), sizeof(float) * (size_t)N,
-                         s, d_rews_all, c.enable_demo ? d_logpd_all : nullptr, N, p->env->rew_xref, c.temp_sample,
+                         s, d_rews_all, c.enable_demo ? d_logpd_all : nullptr, N, rew_xref, c.temp_sample,
                          c.update_method == 0 ? 1 : 0, p->d_weights, d_rew_mean, d_cand, HNu, d_Ybar_i, p->alphas[i],
                          p->alphas_bar[i], p->alphas_bar[i - 1], lit, d_Ybar_im1, lazy, sigma_i, p->d_ybar_keep, T, X);
     } else if (split) {
@@ -623,6 +628,13 @@ extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_samp
     MBD_TRY(p->ring.mark_wmean(s, p->aux != nullptr));
   }
   return MBD_OK;
+}
+
+extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
+                                     const float* d_rews_all, const float* d_logpd_all, float* d_Ybar_im1,
+                                     float* d_rew_mean, void* stream_) {
+  (void)key_sample;  // the candidates (or their normals) of all N are already resident from phase 1 of this step
+  return plan_score_update(p, i, d_Ybar_i, d_rews_all, d_logpd_all, d_Ybar_im1, d_rew_mean, stream_, p ? p->env->rew_xref : 0.0f);
 }
 
 extern "C" int mbd_plan_set_sigma(mbd_plan* p, float sigma) {
@@ -790,10 +802,12 @@ static int plan_keep_in_step(mbd_plan* p) {
 
 // d_state0: where the step's rollouts start.  key_after: the Y0s_rng of the step that follows the LAST step (i == 1) of
 // this loop in another one (a receding-horizon episode's next tick), or nullptr.  ns: the noise shape and basis this loop's
-// steps sample under, ns_after: what key_after's step does
+// steps sample under, ns_after: what key_after's step does.  d_xref: the demo table of the step, nullptr: the env's with the
+// env's rew_xref (a tick of an episode with a demo record: its window and the record's rew_xref)
 static int reverse_once_impl(mbd_plan* p, const float* d_state0, int i, uint32_t key_inout[2], const float* d_Ybar_in,
                              float* d_Ybar_out, float* d_rew_mean, hipStream_t s, const NoiseSpec& ns,
-                             const uint32_t* key_after = nullptr, const NoiseSpec& ns_after = NoiseSpec{}) {
+                             const uint32_t* key_after = nullptr, const NoiseSpec& ns_after = NoiseSpec{},
+                             const float* d_xref = nullptr) {
   if (p->cfg.shard_count != p->cfg.Nsample)
     return fail(MBD_ERR_STATE, "reverse_once on a sharded plan: use sample_rollout + all-gather + score_update");
   uint32_t keys[4];
@@ -808,8 +822,9 @@ static int reverse_once_impl(mbd_plan* p, const float* d_state0, int i, uint32_t
   } else if (key_after) {
     MBD_TRY(declare_next_key(p, key_after, ns_after));
   }
-  MBD_TRY(plan_sample_rollout(p, i, ks, d_Ybar_in, p->d_rews, p->cfg.enable_demo ? p->d_lp.get() : nullptr, s, d_state0, ns));
-  MBD_TRY(mbd_plan_score_update(p, i, ks, d_Ybar_in, p->d_rews, p->d_lp, d_Ybar_out, d_rew_mean, s));
+  MBD_TRY(plan_sample_rollout(p, i, ks, d_Ybar_in, p->d_rews, p->cfg.enable_demo ? p->d_lp.get() : nullptr, s, d_state0, ns, d_xref));
+  MBD_TRY(plan_score_update(p, i, d_Ybar_in, p->d_rews, p->d_lp, d_Ybar_out, d_rew_mean, s,
+                            d_xref ? p->demo.rew_xref : p->env->rew_xref));
   key_inout[0] = keys[0];
   key_inout[1] = keys[1];
   return MBD_OK;
@@ -904,14 +919,15 @@ bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[
   return kick_now;
 }
 
-int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc) {
+int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc, bool has_demo_rec) {
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
   if (T < 1) return fail(MBD_ERR_INVALID, "n_ticks=%d: must be >= 1", T);
   if (K < 1 || K > Nd - 1) return fail(MBD_ERR_INVALID, "warm_steps=%d outside [1, Ndiffuse-1=%d]", K, Nd - 1);
   if (E < 1 || E >= H) return fail(MBD_ERR_INVALID, "exec_steps=%d outside [1, Hsample=%d)", E, H);
   for (int r = 0; r < 5; ++r)
     if (mc->reserved[r] != 0) return fail(MBD_ERR_INVALID, "reserved[%d]=%d: must be 0", r, mc->reserved[r]);
-  if (c.enable_demo) return fail(MBD_ERR_UNSUPPORTED, "enable_demo: demos are time-indexed, an episode has no clock for them");
+  if (c.enable_demo && !has_demo_rec)
+    return fail(MBD_ERR_UNSUPPORTED, "enable_demo: demos are time-indexed, an episode has no clock for them: set a demo record");
   if (c.update_method != 0) return fail(MBD_ERR_UNSUPPORTED, "update_method=%d: receding horizon runs MBD plans only", c.update_method);
   return MBD_OK;
 }
@@ -1000,6 +1016,97 @@ extern "C" int mbd_plan_peek_mpc_predicted(mbd_plan* p, float* predicted_out) {
     HIP_TRY(hipMemcpy(predicted_out, p->d_mpc_pred, sizeof(float) * (size_t)p->delay.pred_ticks * p->env->state_size(),
                       hipMemcpyDeviceToHost));
   return MBD_OK;
+}
+
+// ---- the demo record (include/mbd_hip.h mbd_mpc_demo) -------------------------------------------------------------------
+int DemoRec::set(const mbd_env* env, const mbd_plan_config& cfg, const mbd_mpc_demo* rec) {
+  if (!rec) {
+    has = false;
+    ticks = exec = episodes = 0;
+    return MBD_OK;
+  }
+  if (!rec->clip) return fail(MBD_ERR_INVALID, "demo record: clip is NULL");
+  if (rec->n_rows < 1) return fail(MBD_ERR_INVALID, "demo record: n_rows=%d: must be >= 1", rec->n_rows);
+  if (rec->start_row < 0) return fail(MBD_ERR_INVALID, "demo record: start_row=%d: must be >= 0", rec->start_row);
+  if (!std::isfinite(rec->rew_xref)) return fail(MBD_ERR_INVALID, "demo record: rew_xref=%g: must be finite", (double)rec->rew_xref);
+  for (int r = 0; r < 4; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "demo record: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (!env->has_xref) return fail(MBD_ERR_INVALID, "demo record: env '%s' has no xref: nothing of it follows a demonstration", env->name.c_str());
+  if (!cfg.enable_demo) return fail(MBD_ERR_INVALID, "demo record: enable_demo=0: the plan does not use demos");
+  const int k_ = env->kind == ENV_CAR2D ? 1 : env->model.n_track, c_ = env->kind == ENV_CAR2D ? 2 : 3;
+  const size_t n = (size_t)k_ * (size_t)rec->n_rows * (size_t)c_;
+  for (size_t e = 0; e < n; ++e)
+    if (!std::isfinite(rec->clip[e]))
+      return fail(MBD_ERR_INVALID, "demo record: clip[%d][%d][%d]=%g: must be finite", (int)(e / ((size_t)rec->n_rows * c_)),
+                  (int)(e / c_ % rec->n_rows), (int)(e % c_), (double)rec->clip[e]);
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (an episode's last launch may still read the previous clip)
+  has = false;
+  ticks = exec = episodes = 0;
+  HIP_TRY(d_clip.grow(n));
+  HIP_TRY(hipMemcpy(d_clip, rec->clip, sizeof(float) * n, hipMemcpyHostToDevice));
+  L = rec->n_rows; c0 = rec->start_row; K = k_; C = c_;
+  rew_xref = rec->rew_xref;
+  has = true;
+  return MBD_OK;
+}
+
+int DemoRec::check_plant(const mbd_env* env, const mbd_env* plant) const {
+  if (!has || plant == env || env->kind != ENV_MODEL) return MBD_OK;
+  if (plant->model.n_track != env->model.n_track)
+    return fail(MBD_ERR_INVALID, "demo record: the plant's n_track=%d, the planning env's is %d", plant->model.n_track, env->model.n_track);
+  for (int k = 0; k < env->model.n_track; ++k)
+    if (plant->model.track_link[k] != env->model.track_link[k])
+      return fail(MBD_ERR_INVALID, "demo record: the plant's track_link[%d]=%d, the planning env's is %d", k,
+                  plant->model.track_link[k], env->model.track_link[k]);
+  return MBD_OK;
+}
+
+int DemoRec::start(int T, int P, int E, int D, hipStream_t s) {
+  ticks = exec = episodes = 0;
+  const size_t steps = (size_t)T * P * E;
+  HIP_TRY(d_windows.grow((size_t)T * K * kXrefRows * C));
+  HIP_TRY(d_xlog.grow(steps * K * 3));
+  HIP_TRY(d_err.grow(steps * K));
+  hipLaunchKernelGGL(demo_windows_kernel, dim3(demo_blocks((long long)T * K * kXrefRows)), dim3(256), 0, s, (const float*)d_clip, L, c0,
+                     T, K, C, E, D, d_windows.get());
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+
+int DemoRec::finish(int T, int P, int E, hipStream_t s) {
+  hipLaunchKernelGGL(mpc_track_err_kernel, dim3(demo_blocks((long long)T * P * E * K)), dim3(256), 0, s, (const float*)d_xlog,
+                     (const float*)d_clip, L, c0, T, P, E, K, C, d_err.get());
+  HIP_TRY(hipGetLastError());
+  ticks = T; exec = E; episodes = P;
+  return MBD_OK;
+}
+
+int DemoRec::peek(int device, int k, float* err_out, float* windows_out, const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_mpc_track: the %s has no demo record", what);
+  if (ticks < 1) return fail(MBD_ERR_STATE, "peek_mpc_track: no episode has run with the record yet");
+  if (k < 0 || k >= episodes) return fail(MBD_ERR_INVALID, "peek_mpc_track: episode k=%d outside [0,%d)", k, episodes);
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t T = (size_t)ticks, P = (size_t)episodes, EK = (size_t)exec * K;
+  if (err_out) {  // (tick-major on the device: [T][P][E][K])
+    std::vector<float> tmp(T * P * EK);
+    HIP_TRY(hipMemcpy(tmp.data(), d_err, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
+    for (size_t t = 0; t < T; ++t) memcpy(err_out + t * EK, tmp.data() + (t * P + (size_t)k) * EK, sizeof(float) * EK);
+  }
+  if (windows_out)
+    HIP_TRY(hipMemcpy(windows_out, d_windows, sizeof(float) * T * K * kXrefRows * C, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_mpc_demo(mbd_plan* p, const mbd_mpc_demo* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->demo.set(p->env, p->cfg, rec);
+}
+
+extern "C" int mbd_plan_peek_mpc_track(mbd_plan* p, float* err_out, float* windows_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->demo.peek(p->env->device, 0, err_out, windows_out, "plan");
 }
 
 // ---- the ensemble record (include/mbd_hip.h mbd_ensemble) ---------------------------------------------------------------
@@ -1147,6 +1254,11 @@ extern "C" int mbd_plan_peek_ensemble(mbd_plan* p, float* rews_members_out, floa
 // their path — it sits between that rollout's weighted mean, which was the last reader of the buffer two steps back, and the
 // rollout that reads them, like the boundary's launches.  The boundary itself stays where it was, in its delay variant: the
 // rows executed are the queue's head, and the same launch that shifts the mean advances the queue into its other buffer.
+// With a demo record (mbd_plan_set_mpc_demo; demo plans only) the tick loop launches nothing new: demo_windows_kernel fills the
+// table of all T windows in ONE launch in front of the loop, on the same stream, and a tick's planning launches are handed a
+// pointer into it where they read the env's demo (launch_rollout's and launch_logpd's d_xref) and the record's rew_xref where they
+// read the env's; the rollout of the executed rows is handed its slice of the position log as d_xpos; mpc_track_err_kernel, ONE
+// launch behind the loop, reads that log.  The ring's argument does not see any of it.
 extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
                                 float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
@@ -1154,7 +1266,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   if (!key) return fail(MBD_ERR_INVALID, "key is NULL");
   const mbd_plan_config& c = p->cfg;
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
-  MBD_TRY(check_mpc_config(c, mc));
+  MBD_TRY(check_mpc_config(c, mc, p->demo.has));
   if (c.shard_count != c.Nsample)
     return fail(MBD_ERR_STATE, "shard_count=%d of Nsample=%d: receding horizon runs unsharded plans", c.shard_count, c.Nsample);
   MBD_TRY(p->delay.check_run(E));
@@ -1180,6 +1292,9 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     HIP_TRY(p->d_plant_eps.grow((size_t)EN + 3));
     HIP_TRY(p->d_plant_kick.grow(3));
   }
+  // with a demo record (only a demo plan carries one): the table of the ticks' windows, one launch, and the position log
+  const bool has_demo = p->demo.has;
+  MBD_TRY(p->demo.check_plant(e, pe));
   const int planar = e->kind == ENV_MODEL && (e->model.flags & MBD_FLAG_PLANAR) ? 1 : 0;
   uint32_t dk[2] = {pr.key[0], pr.key[1]};  // the disturbance key chain: dk, d_t = split(dk) per tick
   const float* s_t = p->d_state0;  // where tick t's rollouts start: s_0 in the plan's own buffer, then the ping-pong buffers
@@ -1193,6 +1308,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   }
   HIP_TRY(hipStreamSynchronize(s));
   const auto t0 = std::chrono::steady_clock::now();
+  if (has_demo) MBD_TRY(p->demo.start(T, 1, E, has_delay ? D : 0, s));
   uint32_t rng[2] = {key[0], key[1]}, kk[4];
   host_split(rng, 2, c.prng_impl, kk);  // rng, k_0 = split(rng)
   for (int t = 0; t < T; ++t) {
@@ -1222,7 +1338,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
       float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
       MBD_TRY(plan_keep_in_step(p));
       MBD_TRY(reverse_once_impl(p, plan_from, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, ns, t + 1 < T ? after + 2 : nullptr,
-                                noise_warm(p)));
+                                noise_warm(p), has_demo ? p->demo.window(t) : nullptr));
       cur = nxt;
     }
     // execute M_t's first E rows from s_t — with a delay record the queue's head —, then the boundary: Ybar of tick t+1, the
@@ -1239,7 +1355,9 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
       HIP_TRY(hipGetLastError());
       rows = exec_rows;
     }
-    MBD_TRY(launch_rollout(pe, s_t, rows, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr, nullptr, s_next, s));
+    // (with a demo record the launch also writes the tracked positions of its E steps into their log: same rewards, same state)
+    MBD_TRY(launch_rollout(pe, s_t, rows, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr, has_demo ? p->demo.xlog(t, 1, E) : nullptr,
+                           s_next, s));
     float* const exec_log = has_plant ? nullptr : p->d_mpc_actions + (size_t)t * EN;  // (a plant's rows kernel has logged them)
     if (has_delay && kick_now)
       hipLaunchKernelGGL(mpc_boundary_delay_kick_kernel, dim3(1), dim3(256), 0, s, cur, HNu, EN, s_next, S,
@@ -1258,6 +1376,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     HIP_TRY(hipGetLastError());
     s_t = s_next;
   }
+  if (has_demo) MBD_TRY(p->demo.finish(T, 1, E, s));
   HIP_TRY(hipStreamSynchronize(s));
   const auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();

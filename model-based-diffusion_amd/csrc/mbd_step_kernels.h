@@ -349,6 +349,54 @@ static __global__ __launch_bounds__(256) void mpc_boundary_delay_batch_kernel(co
   mpc_queue_advance(M, shift, q_in + k * Q, q_out + k * Q, Q, rows ? rows + k * shift : nullptr);
 }
 
+// The demo clock of an episode with a demo record (include/mbd_hip.h mbd_mpc_demo).  ONE launch in front of the tick loop
+// builds the table of every tick's window from the clip [K][L][C] (C = 3, car2d 2):
+//   windows[t][k][h] = clip[k][min(c0 + (t + D) E + h, L - 1)]        h = 0 .. kXrefRows - 1
+// so a tick hands its launches a pointer into the table and nothing else.  Grid-stride over the T K kXrefRows rows, every
+// element written, the row arithmetic in 64 bits (c0 alone may be close to 2^31).
+static __global__ __launch_bounds__(256) void demo_windows_kernel(const float* __restrict__ clip, int L, int c0, int T, int K,
+                                                            int C, int E, int D, float* __restrict__ windows) {
+  const long long rows = (long long)T * K * kXrefRows;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride) {
+    const long long tk = r / kXrefRows;
+    const long long h = r - tk * kXrefRows, t = tk / K, k = tk - t * K;
+    long long src = (long long)c0 + (t + D) * E + h;
+    if (src > (long long)L - 1) src = (long long)L - 1;
+    const float* a = clip + (k * L + src) * C;
+    float* o = windows + r * C;
+    for (int c = 0; c < C; ++c) o[c] = a[c];
+  }
+}
+// ... and ONE launch behind it: how far the executed motion was from the clip.  xlog [T][P][E][K][3] holds the positions the
+// rollouts of the executed rows wrote (P = 1: a plan's [T E][K][3]; car2d: K = 1, its qs — x, y, theta); control step t E + j
+// of every episode is compared with clip row min(c0 + t E + j, L - 1), whatever the delay: err, in xlog's order [T][P][E][K],
+// is the unclipped Euclidean distance (C = 2: over x and y), products and sums in this order.
+static __global__ __launch_bounds__(256) void mpc_track_err_kernel(const float* __restrict__ xlog, const float* __restrict__ clip,
+                                                             int L, int c0, int T, int P, int E, int K, int C,
+                                                             float* __restrict__ err) {
+  const long long n = (long long)T * P * E * K;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const long long k = i % K, j = (i / K) % E, t = i / ((long long)K * E * P);
+    long long row = (long long)c0 + t * E + j;
+    if (row > (long long)L - 1) row = (long long)L - 1;
+    const float* x = xlog + i * 3;
+    const float* c = clip + (k * L + row) * C;
+    const float dx = x[0] - c[0], dy = x[1] - c[1];
+    float s = dx * dx + dy * dy;
+    if (C == 3) {
+      const float dz = x[2] - c[2];
+      s = s + dz * dz;
+    }
+    err[i] = sqrtf(s);
+  }
+}
+inline unsigned demo_blocks(long long items) {
+  const long long b = (items + 255) / 256;
+  return (unsigned)(b < 1 ? 1 : (b < 1024 ? b : 1024));
+}
+
 // ---- A5: demo log-densities ------------------------------------------------------------------------------
 // HumanoidTrack.eval_xref_logpd (humanoidtrack.py:98-106): xpos [B][H][K][3], xref [K][H][3].  One workgroup per
 // candidate: its K*H terms ((clip(|x - xref|, 0, .5) / .5)^2, the candidate's 3 K H floats are contiguous) are formed in

@@ -60,6 +60,9 @@ struct mbd_sweep {
   // are the queues' heads: d_mpc_actions logs them, and the rollout of the executed rows reads its slice.)
   DelayRec delay;
   DevBuf<float> d_mpc_queue, d_mpc_pred;
+  // the demo record of all episodes (mbd_sweep_set_mpc_demo): one clip and one clock, so ONE table of windows — a rollout
+  // launch reads one demo table for all its candidates —; the position log and the distances are tick-major [T][P][E][K]...
+  DemoRec demo;
   // the noise shape of all the sweep's plans (mbd_sweep_set_noise_shape): a plan's, with the same two accessors
   DevBuf<float> d_shape;
   bool has_shape = false;
@@ -283,6 +286,8 @@ struct SweepStep {
   long long ybar_in_stride;
   const SweepKeys* next_keys;  // Y0s_rng of the loop's following step (its normals go beside this rollout), or nullptr: none follows
   NoiseSpec next_ns;           // the noise shape and basis that following step samples under
+  const float* xref = nullptr; // the demo table of the step: a tick's window of a batch with a demo record, nullptr: the env's ...
+  float rew_xref = 0.0f;       // ... and the demo's reward level in the blend: the record's, or the env's
 };
 
 // the normals of a step depend on its keys only: they are generated on the second stream while the previous step's
@@ -346,14 +351,14 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
   const bool fused_lp = c.enable_demo && rollout_choice(e, P * N, H, sw).fuses_logpd;  // (mbd_plan.hip: the log-densities out of the rollout)
   MBD_TRY(launch_rollout(e, st.state0, w->d_eps[cur], P * N, H, w->d_rewss, w->d_rews,
                          (c.enable_demo && !fused_lp) ? w->d_xpos.get() : nullptr, nullptr, s, &lz, sw,
-                         fused_lp ? w->d_lp.get() : nullptr));
+                         fused_lp ? w->d_lp.get() : nullptr, nullptr, st.xref));
   MBD_TRY(w->timing.end(s));
-  if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, w->d_xpos, P * N, H, w->d_lp, s));
+  if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, w->d_xpos, P * N, H, w->d_lp, s, st.xref));
   ScoreBatch sb;
   sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)N * HNu;
   sb.ybar_in = st.ybar_in_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
   launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), c.enable_demo ? w->d_lp.get() : nullptr, N,
-                           e->rew_xref, c.temp_sample, 1, w->d_weights.get(), w->d_rewmeans + st.slot, w->d_eps[cur].get(), HNu, st.ybar_in,
+                           st.rew_xref, c.temp_sample, 1, w->d_weights.get(), w->d_rewmeans + st.slot, w->d_eps[cur].get(), HNu, st.ybar_in,
                            w->alphas[i], w->alphas_bar[i], w->alphas_bar[i - 1], c.literal_score,
                            w->d_mu + (size_t)st.slot * HNu, 1, w->sigmas[i], (float*)nullptr, sb);
   HIP_TRY(hipGetLastError());
@@ -387,6 +392,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
     st.ybar_in_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
     st.next_keys = i > 1 ? &sk : nullptr;
     st.next_ns = w->noise_always();
+    st.rew_xref = e->rew_xref;
     MBD_TRY(sweep_step(w, st));
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -448,6 +454,18 @@ extern "C" int mbd_sweep_set_mpc_delay(mbd_sweep* w, const mbd_mpc_delay* rec) {
   return w->delay.set(rec, w->Nu);
 }
 
+// one demo record for all episodes of the sweep (include/mbd_hip.h mbd_mpc_demo)
+extern "C" int mbd_sweep_set_mpc_demo(mbd_sweep* w, const mbd_mpc_demo* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  return w->demo.set(w->env, w->cfg, rec);
+}
+
+extern "C" int mbd_sweep_peek_mpc_track(mbd_sweep* w, int k, float* err_out, float* windows_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "episode k=%d outside [0,%d)", k, w->P);
+  return w->demo.peek(w->env->device, k, err_out, windows_out, "sweep");
+}
+
 extern "C" int mbd_sweep_peek_mpc_predicted(mbd_sweep* w, float* predicted_out) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   if (!w->delay.has) return fail(MBD_ERR_STATE, "peek_mpc_predicted: the sweep has no delay record");
@@ -490,7 +508,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   if (!keys) return fail(MBD_ERR_INVALID, "keys is NULL");
   const mbd_plan_config& c = w->cfg;
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
-  MBD_TRY(check_mpc_config(c, mc));
+  MBD_TRY(check_mpc_config(c, mc, w->demo.has));
   MBD_TRY(w->delay.check_run(E));
   mbd_env* e = w->env;
   HIP_TRY(hipSetDevice(e->device));
@@ -514,6 +532,10 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     HIP_TRY(w->d_plant_eps.grow((size_t)P * ((size_t)(H - 1) * Nu + 3)));
     HIP_TRY(w->d_plant_kick.grow((size_t)P * 3));
   }
+  // with a demo record: every plant must write the positions of the sweep's env's tracked links
+  const bool has_demo = w->demo.has;
+  for (int k = 0; k < P; ++k)
+    if (w->has_plant[k] && w->plant_rec[k].plant) MBD_TRY(w->demo.check_plant(e, w->plant_rec[k].plant));
   const int planar = (e->model.flags & MBD_FLAG_PLANAR) ? 1 : 0;
   // the disturbance key chains: dk, d_t = split(dk) per tick and episode
   std::vector<uint32_t> dk(2 * (size_t)P, 0u);
@@ -530,6 +552,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   HIP_TRY(hipStreamSynchronize(s));
   progress_reset(w->h_progress);
   const auto t0 = std::chrono::steady_clock::now();
+  if (has_demo) MBD_TRY(w->demo.start(T, P, E, has_delay ? D : 0, s));  // (the table of the ticks' windows: one launch)
   // per episode: rng, k_t = split(rng) per tick, the tick's chain r, Y0s_rng = split(r) per step from r = k_t.  The keys
   // are drawn in the order the steps run, one step ahead of the rollouts (the normals of a tick's first step are prepared
   // beside the previous tick's last rollout, like any other step's)
@@ -570,6 +593,8 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       // (the noise shape and basis of the following step: this tick's, or — behind a tick's last step — a warm tick's,
       // mbd_plan_run_mpc)
       st.next_ns = (t == 0 && i > 1) ? w->noise_always() : w->noise_warm();
+      st.xref = has_demo ? w->demo.window(t) : nullptr;
+      st.rew_xref = has_demo ? w->demo.rew_xref : e->rew_xref;
       MBD_TRY(sweep_step(w, st));
     }
     // the boundary: the logs of M_{.,t}, its first E rows and Ybar of tick t+1; then the rows executed from s_{.,t}
@@ -586,8 +611,9 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
                          w->d_mpc_means + (size_t)t * P * HNu, w->d_mpc_rows);
     HIP_TRY(hipGetLastError());
     if (!any_plant) {
-      MBD_TRY(launch_rollout(e, states_t, has_delay ? rows_t : w->d_mpc_rows.get(), P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr, nullptr,
-                             w->d_mpc_states + (size_t)(t + 1) * P * S, s, nullptr, exec_sw));
+      // (with a demo record the launch also writes the tracked positions of every episode's E steps into their log)
+      MBD_TRY(launch_rollout(e, states_t, has_delay ? rows_t : w->d_mpc_rows.get(), P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr,
+                             has_demo ? w->demo.xlog(t, P, E) : nullptr, w->d_mpc_states + (size_t)(t + 1) * P * S, s, nullptr, exec_sw));
       continue;
     }
     SweepPlant sp{};
@@ -606,7 +632,8 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       int k1 = k0 + 1;
       while (k1 < P && plant_of(k1) == plant_of(k0)) ++k1;
       MBD_TRY(launch_rollout(plant_of(k0), states_t + (size_t)k0 * S, rows_t + (size_t)k0 * EN, k1 - k0, E,
-                             rewards_t + (size_t)k0 * E, nullptr, nullptr, states_t1 + (size_t)k0 * S, s, nullptr, exec_sw));
+                             rewards_t + (size_t)k0 * E, nullptr, has_demo ? w->demo.xlog(t, P, E, k0) : nullptr,
+                             states_t1 + (size_t)k0 * S, s, nullptr, exec_sw));
       k0 = k1;
     }
     if (any_kick) {
@@ -615,6 +642,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       HIP_TRY(hipGetLastError());
     }
   }
+  if (has_demo) MBD_TRY(w->demo.finish(T, P, E, s));
   HIP_TRY(hipStreamSynchronize(s));
   const auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();

@@ -84,15 +84,24 @@ class MpcDelay(C.Structure):
     _fields_ = [("rows0", C.POINTER(C.c_float)), ("delay_ticks", C.c_int32), ("n_rows", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+XREF_ROWS = 50  # csrc/mbd_kernels.h kXrefRows: the rows of a demo window
+
+
+class MpcDemo(C.Structure):
+    """mbd_mpc_demo (include/mbd_hip.h): the clip an episode follows, the row it starts at and the demo's reward level."""
+    _fields_ = [("clip", C.POINTER(C.c_float)), ("n_rows", C.c_int32), ("start_row", C.c_int32), ("rew_xref", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
 EXPORTS = [
     "mbd_last_error", "mbd_version", "mbd_tuned_spec", "mbd_device_count", "mbd_prng_key", "mbd_prng_split",
     "mbd_env_create", "mbd_env_name", "mbd_builtin_model", "mbd_env_get_model", "mbd_env_xref", "mbd_env_xref_logpd",
     "mbd_env_observe", "mbd_model_observe", "mbd_model_forward", "mbd_env_create_car2d", "mbd_env_create_model", "mbd_env_destroy", "mbd_env_info", "mbd_env_reset", "mbd_env_pipeline_init",
     "mbd_env_step", "mbd_env_rew_xref", "mbd_env_rollout", "mbd_plan_create", "mbd_plan_destroy",
     "mbd_plan_schedule", "mbd_plan_set_state0", "mbd_plan_sample_rollout", "mbd_plan_prefetch_noise", "mbd_plan_score_update",
-    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_set_mpc_delay", "mbd_plan_peek_mpc_predicted", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
+    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_set_mpc_delay", "mbd_plan_peek_mpc_predicted", "mbd_plan_set_mpc_demo", "mbd_plan_peek_mpc_track", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
-    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_set_noise_shape", "mbd_sweep_set_noise_basis", "mbd_sweep_set_mpc_delay", "mbd_sweep_peek_mpc_predicted", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
+    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_set_noise_shape", "mbd_sweep_set_noise_basis", "mbd_sweep_set_mpc_delay", "mbd_sweep_peek_mpc_predicted", "mbd_sweep_set_mpc_demo", "mbd_sweep_peek_mpc_track", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
     "mbd_exchange_create", "mbd_exchange_destroy", "mbd_exchange_local_handle", "mbd_exchange_connect",
     "mbd_exchange_all_gather", "mbd_exchange_status", "mbd_exchange_fine_grained",
 ]
@@ -162,6 +171,8 @@ def load() -> C.CDLL:
     lib.mbd_plan_set_noise_basis.argtypes = [_vp, C.POINTER(NoiseBasis)]
     lib.mbd_plan_set_mpc_delay.argtypes = [_vp, C.POINTER(MpcDelay)]
     lib.mbd_plan_peek_mpc_predicted.argtypes = [_vp, _vp]
+    lib.mbd_plan_set_mpc_demo.argtypes = [_vp, C.POINTER(MpcDemo)]
+    lib.mbd_plan_peek_mpc_track.argtypes = [_vp, _vp, _vp]
     lib.mbd_plan_eval.argtypes = [_vp, _vp, _fp]
     lib.mbd_plan_peek.argtypes = [_vp, _vp, _vp, _vp]
     lib.mbd_plan_kernel_time.argtypes = [_vp, _fp, C.POINTER(_i), _i]
@@ -176,6 +187,8 @@ def load() -> C.CDLL:
     lib.mbd_sweep_set_noise_basis.argtypes = [_vp, C.POINTER(NoiseBasis)]
     lib.mbd_sweep_set_mpc_delay.argtypes = [_vp, C.POINTER(MpcDelay)]
     lib.mbd_sweep_peek_mpc_predicted.argtypes = [_vp, _vp]
+    lib.mbd_sweep_set_mpc_demo.argtypes = [_vp, C.POINTER(MpcDemo)]
+    lib.mbd_sweep_peek_mpc_track.argtypes = [_vp, _i, _vp, _vp]
     lib.mbd_sweep_kernel_time.argtypes = [_vp, _i, _fp, C.POINTER(_i)]
     lib.mbd_sweep_get_sigmas.argtypes = [_vp, _vp]
     lib.mbd_exchange_create.argtypes = [_i, _i, _i, _i, _i, C.POINTER(_vp)]

@@ -84,6 +84,7 @@ class Sweep:
         self.Nd, self.H, self.Nu = cfg.Ndiffuse, args.Hsample, env.action_size
         self._plant_envs = {}  # episode -> the plant env of its record (kept alive: a record does not own its plant)
         self._has_delay = False
+        self._demo_shape = None  # (K, C) of the clip of the sweep's demo record
 
     def set_state0(self, k: int, state):
         st = np.ascontiguousarray(state.pipeline_state, np.float32).reshape(-1)
@@ -125,7 +126,27 @@ class Sweep:
         if self._has_delay:  # (the states the ticks planned from: shat_{k,0} .. shat_{k,T-1})
             out["predicted"] = np.zeros((P, T, S), np.float32)
             _capi.check(self.lib.mbd_sweep_peek_mpc_predicted(self.h, _capi.np_ptr(out["predicted"])))
+        if self._demo_shape is not None:  # (every episode's distances from the clip, and the one table of windows)
+            Kt, Cc = self._demo_shape
+            out["track_err"] = np.zeros((P, T * E, Kt), np.float32)
+            out["demo_windows"] = np.zeros((T, Kt, _capi.XREF_ROWS, Cc), np.float32)
+            for e in range(P):
+                _capi.check(self.lib.mbd_sweep_peek_mpc_track(self.h, e, _capi.np_ptr(out["track_err"][e]),
+                                                              _capi.np_ptr(out["demo_windows"]) if e == 0 else None))
         return out
+
+    def set_mpc_demo(self, clip, start_row: int = 0, rew_xref: float = None):
+        """One demo record for all episodes of the sweep (``Plan.set_mpc_demo``) — one clip and one clock: episode k of
+        ``run_mpc`` is then ``Plan.run_mpc`` with the same record, bit for bit; ``run_mpc`` also returns ``track_err``
+        [P, T*E, K] and ``demo_windows`` [T, K, 50, 3]."""
+        rec, keep = _demo_record(self.env, clip, start_row, rew_xref)
+        _capi.check(self.lib.mbd_sweep_set_mpc_demo(self.h, C.byref(rec)))
+        self._demo_shape = (keep.shape[0], keep.shape[2])
+        del keep  # (the set call has copied the clip)
+
+    def clear_mpc_demo(self):
+        _capi.check(self.lib.mbd_sweep_set_mpc_demo(self.h, None))
+        self._demo_shape = None
 
     def set_mpc_plant(self, k: int, env=None, key=None, act_std: float = 0.0, kick_std: float = 0.0, kick_every: int = 1):
         """The plant of episode ``k`` (``Plan.set_mpc_plant``): episode k of ``run_mpc`` is then ``Plan.run_mpc`` with that
@@ -201,6 +222,24 @@ def _plant_record(env, key, act_std, kick_std, kick_every):
     rec.key[0], rec.key[1] = int(k[0]), int(k[1])
     rec.act_std, rec.kick_std, rec.kick_every = float(act_std), float(kick_std), int(kick_every)
     return rec
+
+
+def _demo_record(env, clip, start_row, rew_xref):
+    """The mbd_mpc_demo of ``set_mpc_demo``'s arguments, and the float32 array [K, L, C] its pointer reads (``clip``
+    [n_track, L, 3]; car2d: [L, 2]; ``rew_xref`` None: the env's; everything else goes to the library, which names the field)."""
+    c = np.ascontiguousarray(clip, np.float32)
+    if c.ndim == 2:  # (car2d: one track)
+        c = c[None]
+    # (an env without tracked links has no demo at all: the library refuses the record before it reads the clip)
+    want = (1, 2) if getattr(env, "sys", None) is None else (max(int(env.sys.fields["n_track"]), 1), 3)
+    if c.ndim != 3 or (c.shape[0], c.shape[2]) != want:
+        raise ValueError(f"demo clip of shape {np.shape(clip)}: must be [n_track={want[0]}, n_rows, {want[1]}]"
+                         + (" or [n_rows, 2]" if want[1] == 2 else ""))
+    rec = _capi.MpcDemo()
+    rec.clip = c.ctypes.data_as(C.POINTER(C.c_float))
+    rec.n_rows, rec.start_row = c.shape[1], int(start_row)
+    rec.rew_xref = float(env.rew_xref if rew_xref is None else rew_xref)
+    return rec, c
 
 
 def _delay_record(ticks, rows0, Nu):
@@ -286,6 +325,7 @@ class Plan:
         self._plant_env = None  # the plant env of the plan's record (kept alive: a record does not own its plant)
         self._ens_envs = None   # the member envs of the plan's ensemble record (kept alive likewise)
         self._has_delay = False
+        self._demo_shape = None  # (K, C) of the clip of the plan's demo record
 
     def schedule(self):
         a, ab, s = (np.zeros(self.Nd, np.float32) for _ in range(3))
@@ -332,7 +372,28 @@ class Plan:
         if self._has_delay:  # (the states the ticks planned from: shat_0 .. shat_{T-1})
             out["predicted"] = np.zeros((T, S), np.float32)
             _capi.check(self.lib.mbd_plan_peek_mpc_predicted(self.h, _capi.np_ptr(out["predicted"])))
+        if self._demo_shape is not None:  # (how far the executed steps were from the clip, and the windows the ticks planned under)
+            Kt, Cc = self._demo_shape
+            out["track_err"] = np.zeros((T * E, Kt), np.float32)
+            out["demo_windows"] = np.zeros((T, Kt, _capi.XREF_ROWS, Cc), np.float32)
+            _capi.check(self.lib.mbd_plan_peek_mpc_track(self.h, _capi.np_ptr(out["track_err"]), _capi.np_ptr(out["demo_windows"])))
         return out
+
+    def set_mpc_demo(self, clip, start_row: int = 0, rew_xref: float = None):
+        """Follow a demonstration on the episode's clock (include/mbd_hip.h mbd_mpc_demo; demo plans only): tick t of
+        ``run_mpc`` plans under the 50 rows of ``clip`` [n_track, L, 3] (car2d: [L, 2]) from row
+        ``start_row + (t + delay_ticks) * exec_steps`` on, rows past the clip's end holding its last row, with ``rew_xref``
+        (None: the env's) as the demo's reward level.  ``run_mpc`` then also returns ``track_err`` [T*E, K] — the distance of
+        every executed control step's tracked positions from its clip row — and ``demo_windows`` [T, K, 50, 3] (car2d: 2).
+        ``run`` ignores it."""
+        rec, keep = _demo_record(self.env, clip, start_row, rew_xref)
+        _capi.check(self.lib.mbd_plan_set_mpc_demo(self.h, C.byref(rec)))
+        self._demo_shape = (keep.shape[0], keep.shape[2])
+        del keep  # (the set call has copied the clip)
+
+    def clear_mpc_demo(self):
+        _capi.check(self.lib.mbd_plan_set_mpc_demo(self.h, None))
+        self._demo_shape = None
 
     def set_mpc_delay(self, ticks: int, rows0=None):
         """Plan ahead of the plant (include/mbd_hip.h mbd_mpc_delay): a plan made in tick t of ``run_mpc`` is first executed in

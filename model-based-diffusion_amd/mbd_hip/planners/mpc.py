@@ -53,6 +53,18 @@ predicts those rows will reach.  0, the default, sets no record.  It composes wi
 with every plant, ensemble and noise flag; the saved episode then carries the predicted states.
 
     python -m mbd_hip.planners.mpc --env_name humanoidrun --warm_steps 20 --delay_ticks 1 --plant_mass 1.3
+
+A demo plan (``--enable_demo``) compares its 50 planned steps with the env's 50 demo rows; in an episode the demo has to move
+with the system.  ``--demo_clip env|FILE.npy`` (include/mbd_hip.h mbd_mpc_demo; DESIGN.md section 1 "N10 demo clock") sets the
+clip the episode follows — the env's own demo, or an array [n_track, L, 3] (car2d: [L, 2]) — and ``--demo_start c0`` the clip
+row of the episode's first control step: tick t plans under the 50 rows from c0 + (t + delay_ticks) exec_steps on, rows past
+the clip's end holding its last row.  ``--demo_period p`` first extends the clip periodically (``cycle_clip``) to the rows the
+episode reaches, so that a long episode follows a gait that keeps moving instead of a pose frozen in world x.  The JSON line
+then carries ``track_err_mean``, the mean distance of the executed steps' tracked positions from their clip rows; the saved
+episode carries ``track_err`` and ``demo_windows``.  ``--enable_demo`` without a clip stays refused: an episode has no clock for
+the env's 50 rows.  A batch of episodes shares one clip and one clock.
+
+    python -m mbd_hip.planners.mpc --env_name humanoidtrack --enable_demo --demo_clip env --demo_period 20 --n_ticks 200
 """
 from __future__ import annotations
 
@@ -91,6 +103,9 @@ class MpcArgs(Args):
     noise_knots: int = 0  # 0: white noise along the horizon; K: K knot normals per actuator in every step (knot_basis) ...
     noise_interp: str = "linear"  # ... interpolated between the knots ("linear") or held ("hold")
     delay_ticks: int = 0  # 0: plans are executed in the tick that made them; D: D ticks later, planned from a predicted state
+    demo_clip: str = ""  # "": no demo record; "env": the env's own demo; FILE.npy: a clip [n_track, L, 3] (car2d [L, 2])
+    demo_start: int = 0  # c0: the clip row the episode's first executed control step is compared with
+    demo_period: int = 0  # p > 0: the clip is first extended periodically (cycle_clip) to the rows the episode reaches
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -231,6 +246,62 @@ def _delay_settings(args: MpcArgs) -> dict:
     return dict(delay_ticks=args.delay_ticks) if _has_delay(args) else {}
 
 
+def cycle_clip(xref, n_rows: int, period: int) -> np.ndarray:
+    """``xref`` [K, L0, 3] (or [L0, C]) extended periodically to ``n_rows`` rows: the rows < L0 are xref's own; row L0 + i
+    repeats row L0 - period + (i mod period) of the last ``period`` rows, advanced by 1 + i // period times the displacement
+    over one period, xref[:, L0-1] - xref[:, L0-1-period] — a gait cycle that keeps travelling.  Computed in float64, cast once
+    to float32.  1 <= period <= L0 - 1."""
+    x = np.asarray(xref, np.float64)
+    flat = x.ndim == 2
+    if flat:
+        x = x[None]
+    if x.ndim != 3:
+        raise ValueError(f"clip of shape {np.shape(xref)}: must be [K, L0, C] or [L0, C]")
+    L0, n_rows, period = x.shape[1], int(n_rows), int(period)
+    if n_rows < 1:
+        raise ValueError(f"n_rows={n_rows}: must be >= 1")
+    if period < 1:
+        raise ValueError(f"period={period}: must be >= 1")
+    if period >= L0:
+        raise ValueError(f"period={period}: must be < the clip's {L0} rows (the displacement over one period is taken inside it)")
+    out = np.empty((x.shape[0], n_rows, x.shape[2]), np.float64)
+    out[:, : min(L0, n_rows)] = x[:, :n_rows]
+    if n_rows > L0:
+        i = np.arange(n_rows - L0)
+        disp = x[:, L0 - 1] - x[:, L0 - 1 - period]
+        out[:, L0:] = x[:, L0 - period + i % period] + (1 + i // period)[None, :, None] * disp[:, None, :]
+    out = np.ascontiguousarray(out.astype(np.float32))
+    return out[0] if flat else out
+
+
+_DEMO_FIELDS = ("demo_clip", "demo_start", "demo_period")
+
+
+def _has_demo(args: MpcArgs) -> bool:
+    """Whether the arguments ask for a demo record at all (the default: none)."""
+    return bool(args.demo_clip)
+
+
+def _demo_of(env, args: MpcArgs):
+    """(clip, start_row) of the arguments' demo record: the env's demo or the file's array, extended by ``cycle_clip`` to the
+    last row a window of the episode reads when ``demo_period`` > 0."""
+    if args.demo_clip == "env":
+        if getattr(env, "xref", None) is None:
+            raise ValueError(f"demo_clip=env: env_name={args.env_name!r} has no demo")
+        clip = np.asarray(env.xref, np.float32)
+    else:
+        clip = np.asarray(np.load(args.demo_clip), np.float32)
+    if args.demo_period < 0:
+        raise ValueError(f"demo_period={args.demo_period}: must be >= 0")
+    if args.demo_period > 0:
+        clip = cycle_clip(clip, args.demo_start + (args.n_ticks + args.delay_ticks) * args.exec_steps + args.Hsample, args.demo_period)
+    return clip, args.demo_start
+
+
+def _demo_settings(args: MpcArgs) -> dict:
+    return {f: getattr(args, f) for f in _DEMO_FIELDS} if _has_demo(args) else {}
+
+
 def _plant_env(env, args: MpcArgs, device: int, cache: dict = None):
     """The env that executes the rows: None (the planner's own) unless mass / friction / gear differ from 1; one env per
     distinct triple in ``cache``."""
@@ -280,6 +351,8 @@ def _setup(args: MpcArgs, device: int):
         plan.set_noise_basis(*_basis_of(args))
     if _has_delay(args):
         plan.set_mpc_delay(args.delay_ticks)
+    if _has_demo(args):
+        plan.set_mpc_demo(*_demo_of(env, args))
     return env, plan, state_init, rng_exp
 
 
@@ -309,8 +382,10 @@ def _check_batch(arg_list) -> None:
     if ds[0]["Nsample"] * 4 > 48 * 1024:
         raise ValueError(f"Nsample={ds[0]['Nsample']}: plans of more than 12288 candidates fill the chip on their own; "
                          "run their episodes one by one")
-    if ds[0]["enable_demo"]:
-        raise ValueError("enable_demo: demos are time-indexed, an episode has no clock for them")
+    if ds[0]["enable_demo"] and not _has_demo(arg_list[0]):
+        raise ValueError("enable_demo: demos are time-indexed, an episode has no clock for them: give it one with demo_clip")
+    if _has_demo(arg_list[0]) and not ds[0]["enable_demo"]:
+        raise ValueError(f"demo_clip={arg_list[0].demo_clip!r} without enable_demo: the plans do not use demos")
 
 
 def _setup_batch(arg_list, device: int):
@@ -325,6 +400,8 @@ def _setup_batch(arg_list, device: int):
         sweep.set_noise_basis(*_basis_of(a0))
     if _has_delay(a0):  # (and one delay)
         sweep.set_mpc_delay(a0.delay_ticks)
+    if _has_demo(a0):  # (one clip and one clock)
+        sweep.set_mpc_demo(*_demo_of(env, a0))
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -360,21 +437,24 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
         shape = _shape_settings(arg_list[0]) if _has_shape(arg_list[0]) else {}
         if _has_basis(arg_list[0]):
             shape = dict(shape, **_basis_settings(arg_list[0]))
-        shape = dict(shape, **_delay_settings(arg_list[0]))
-        return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
+        shape = dict(shape, **_delay_settings(arg_list[0]), **_demo_settings(arg_list[0]))
+        windows = {"demo_windows": ep["demo_windows"]} if "demo_windows" in ep else {}  # (one table: every episode's)
+        return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, **windows, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
                               **_plant_settings(arg_list[k]), **shape) for k in range(len(arg_list))]
     return rewards
 
 
 def _logs(ep: dict) -> tuple:
-    """The episode's logs: the four every episode has, and the predicted states of one with a delay record."""
-    return _LOGS + (("predicted",) if "predicted" in ep else ())
+    """The episode's logs: the four every episode has, the predicted states of one with a delay record, the distances from
+    the clip of one with a demo record."""
+    return _LOGS + tuple(k for k in ("predicted", "track_err") if k in ep)
 
 
 def _save(args: MpcArgs, ep: dict) -> None:
     path = os.path.join(os.getcwd(), "results", args.env_name)
     os.makedirs(path, exist_ok=True)
-    np.savez_compressed(os.path.join(path, "mpc_episode.npz"), **{k: ep[k] for k in _logs(ep)})
+    extra = {"demo_windows": ep["demo_windows"]} if "demo_windows" in ep else {}  # (one table, whatever the episodes)
+    np.savez_compressed(os.path.join(path, "mpc_episode.npz"), **{k: ep[k] for k in _logs(ep)}, **extra)
 
 
 def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
@@ -395,7 +475,7 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         shape = _shape_settings(args) if _has_shape(args) else {}
         if _has_basis(args):
             shape = dict(shape, **_basis_settings(args))
-        shape = dict(shape, **_delay_settings(args))
+        shape = dict(shape, **_delay_settings(args), **_demo_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -449,6 +529,8 @@ def _main(argv=None) -> dict:
     if _has_basis(args):
         res.update(_basis_settings(args))
     res.update(_delay_settings(args))  # (without a record the line is what it always was)
+    if _has_demo(args):
+        res.update(_demo_settings(args), track_err_mean=float(ep["track_err"].mean()))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -488,6 +570,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
             plan.set_noise_basis(*_basis_of(a0))
         if _has_delay(a0):
             plan.set_mpc_delay(a0.delay_ticks)
+        if _has_demo(a0):
+            plan.set_mpc_demo(*_demo_of(env, a0))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -513,6 +597,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
     if _has_basis(a0):
         res.update(_basis_settings(a0))
     res.update(_delay_settings(a0))
+    if _has_demo(a0):
+        res.update(_demo_settings(a0), track_err_mean=float(ep["track_err"].mean()))
     if not a0.not_render:
         _save(a0, ep)
     print(json.dumps(res), flush=True)
