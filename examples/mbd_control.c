@@ -1,0 +1,101 @@
+/* mbd_control.c — the planner in the loop of a system the library does not own, from plain C through include/mbd_hip.h: a
+ * session (mbd_plan_mpc_open) is opened once and advanced one tick per call from the state the caller's system is in.
+ *
+ *   gcc -O2 -I include examples/mbd_control.c -o mbd_control -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
+ *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks]
+ *                 env    N   H  Nd K ticks
+ *
+ * The "system" here is a second env the example owns, stepped with mbd_env_step — the env's rollout kernel at B = 1, H = 1 through
+ * HOST pointers (mbd_env_rollout takes device pointers, which a program without the HIP runtime cannot make): replace plant_step by
+ * your robot's or your simulator's step and plant state by what you measure (mbd_env_pipeline_init turns generalized coordinates
+ * (q, qd) into a state).
+ * With delay_ticks D > 0 the rows to execute NOW are head (what the system was already committed to); the rows the tick planned are
+ * due D ticks later, and the tick planned from the state it predicted for then.
+ *
+ * Prints one line per tick: "tick T reward R ms M flags F", then "mean_reward R ms_per_tick M". */
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "mbd_hip.h"
+
+#define CHECK(call)                                                                    \
+  do {                                                                                 \
+    int rc_ = (call);                                                                  \
+    if (rc_ != MBD_OK) {                                                               \
+      fprintf(stderr, "%s failed (%d): %s\n", #call, rc_, mbd_last_error());           \
+      return 1;                                                                        \
+    }                                                                                  \
+  } while (0)
+
+/* the caller's system: one control step from `state` under `action`, in place */
+static int plant_step(mbd_env* plant, float* state, const float* action, float* scratch, int S, float* reward) {
+  int rc = mbd_env_step(plant, state, action, scratch, reward, NULL);
+  if (rc == MBD_OK) memcpy(state, scratch, sizeof(float) * (size_t)S);
+  return rc;
+}
+
+int main(int argc, char** argv) {
+  const char* env_name = argc > 1 ? argv[1] : "hopper";
+  const int N = argc > 2 ? atoi(argv[2]) : 256, H = argc > 3 ? atoi(argv[3]) : 20, Nd = argc > 4 ? atoi(argv[4]) : 10;
+  const int K = argc > 5 ? atoi(argv[5]) : 3, T = argc > 6 ? atoi(argv[6]) : 20, D = argc > 7 ? atoi(argv[7]) : 0;
+  const int impl = MBD_PRNG_PARTITIONABLE, E = 1;
+  mbd_env *env = NULL, *plant = NULL;
+  CHECK(mbd_env_create(env_name, 0, &env));   /* the planner's model */
+  CHECK(mbd_env_create(env_name, 0, &plant)); /* the system: here a second env, owned by this program */
+  int Nu = 0, Nx = 0, S = 0;
+  CHECK(mbd_env_info(env, &Nu, &Nx, &S, NULL, NULL, NULL));
+  mbd_plan_config cfg;
+  memset(&cfg, 0, sizeof(cfg));
+  cfg.Nsample = N; cfg.Hsample = H; cfg.Ndiffuse = Nd; cfg.temp_sample = 0.1f;
+  cfg.beta0 = 1e-4f; cfg.betaT = 1e-2f; cfg.prng_impl = impl; cfg.shard_begin = 0; cfg.shard_count = N;
+  cfg.literal_score = 1;
+  mbd_plan* plan = NULL;
+  CHECK(mbd_plan_create(env, &cfg, &plan));
+  if (D > 0) { /* plans arrive D ticks late; the system starts committed to zeros */
+    mbd_mpc_delay delay;
+    memset(&delay, 0, sizeof(delay));
+    delay.delay_ticks = D;
+    CHECK(mbd_plan_set_mpc_delay(plan, &delay));
+  }
+  uint32_t key[2], k4[4];
+  CHECK(mbd_prng_key(0, key));
+  CHECK(mbd_prng_split(key, 2, impl, k4));
+  const uint32_t rng_reset[2] = {k4[2], k4[3]}, rng_episode[2] = {k4[0], k4[1]};
+  float* state = (float*)malloc(sizeof(float) * (size_t)S);
+  float* scratch = (float*)malloc(sizeof(float) * (size_t)S);
+  float* rows = (float*)malloc(sizeof(float) * (size_t)E * (size_t)Nu);
+  float* head = (float*)malloc(sizeof(float) * (size_t)E * (size_t)Nu);
+  CHECK(mbd_env_reset(plant, rng_reset, impl, state));
+  mbd_mpc_config mc;
+  memset(&mc, 0, sizeof(mc));
+  mc.n_ticks = T; mc.warm_steps = K; mc.exec_steps = E;
+  CHECK(mbd_plan_mpc_open(plan, &mc, rng_episode));
+  double reward_sum = 0.0, seconds = 0.0;
+  for (int t = 0; t < T; ++t) {
+    mbd_mpc_tick_info info;
+    CHECK(mbd_plan_mpc_tick(plan, state, rows, NULL, head, NULL, &info));
+    /* never forward non-finite rows.  The flag speaks of `rows`, the NEW plan: plan afresh from the next state.  What goes to the
+     * actuators is `head` — without a delay record the same rows; with one, the queue's head, which rows flagged D ticks ago have
+     * reached by now (reset_mean leaves the queue as it is) — so `head` itself is what is checked before it is executed. */
+    if (info.flags & MBD_TICK_ROWS_NONFINITE) CHECK(mbd_plan_mpc_reset_mean(plan));
+    for (int k = 0; k < E * Nu; ++k)
+      if (!isfinite(head[k])) head[k] = 0.0f; /* hold */
+    float reward = 0.0f;
+    for (int j = 0; j < E; ++j) CHECK(plant_step(plant, state, head + (size_t)j * Nu, scratch, S, &reward));
+    printf("tick %d reward %.9g ms %.3f flags %d\n", info.tick, reward, 1e3 * info.seconds, info.flags);
+    reward_sum += reward;
+    seconds += info.seconds;
+  }
+  printf("mean_reward %.9g ms_per_tick %.3f\n", reward_sum / T, 1e3 * seconds / T);
+  CHECK(mbd_plan_mpc_close(plan));
+  free(head);
+  free(rows);
+  free(scratch);
+  free(state);
+  CHECK(mbd_plan_destroy(plan));
+  CHECK(mbd_env_destroy(plant));
+  CHECK(mbd_env_destroy(env));
+  return 0;
+}

@@ -631,6 +631,66 @@ int mbd_plan_set_mpc_demo(mbd_plan* plan, const mbd_mpc_demo* rec);
  * car2d 2); either may be NULL.  MBD_ERR_STATE without a record, or before an episode has run with one. */
 int mbd_plan_peek_mpc_track(mbd_plan* plan, float* err_out, float* windows_out);
 
+/* ---- sessions: an episode the CALLER drives, one tick per call, from the state of a system the library does not own (no
+ * counterpart in the reference; DESIGN.md section 1 "N11 session") ---- */
+/* mbd_plan_run_mpc runs a whole episode and owns the plant.  A session is the same episode opened once and advanced one tick per
+ * call from a state the caller hands in — a robot's, another simulator's: the caller is the plant.
+ *   open:    rng = key; Ybar = zeros; i_start = Ndiffuse-1; t = 0; with a delay record C = rows0 or zeros   [D][E][Nu]
+ *   tick(x): rng, k_t = split(rng)
+ *            from = x                                   without a delay record
+ *                 = final state of ONE rollout of the plan's env from x over the D*E rows of C      with one (predicted_out)
+ *            Ybar = reverse_once(i, ., Ybar) from `from` for i = i_start .. 1, key chain from k_t  -> M_t   (mean_out)
+ *            rows_out = M_t[0:E]                        (copied: -0.0 stays -0.0; unclipped, like actions_out)
+ *            head_out = C[0];  C = C[1:] ++ M_t[0:E]    with a delay record (without one head_out = rows_out)
+ *            Ybar = shift_E(M_t); i_start = K; t += 1
+ * Without a delay record the caller executes rows_out now; with one it executes head_out now and rows_out in tick t + D.
+ * Nothing is executed on the device: no rollout of the executed rows, no reward or state log, and mbd_plan_peek_mpc_track /
+ * mbd_plan_peek_mpc_predicted do not serve sessions.  The noise shape, noise basis, ensemble, delay and demo records are read at
+ * open, exactly as mbd_plan_run_mpc reads them; with a demo record tick t's window — the one mbd_plan_run_mpc's table holds for
+ * that tick — is built by one small launch per tick.  mc->n_ticks is the most ticks the session serves; a session allocates
+ * nothing per tick, so any value up to INT32_MAX costs nothing.
+ * Bit for bit, because the batch episode and the session run ONE tick function:
+ *  - a session fed states[t] of mbd_plan_run_mpc(key, T, K, E) returns mean_t == means[t] and rows_t == actions[tE .. tE+E); with
+ *    a delay record head_t == actions[tE .. tE+E), predicted_t == predicted[t] and rows_t == means[t][0:E];
+ *  - a session that executes rows_t on an env of its own equals the episode under a plant record naming that env, stds 0;
+ *  - a handle that never opens a session behaves exactly as before: same launches, same bits. */
+enum { MBD_TICK_ROWS_NONFINITE = 1, MBD_TICK_STATE_NONFINITE = 2, MBD_TICK_COLD = 4 };
+typedef struct mbd_mpc_tick_info {
+  int32_t tick;         /* t of the tick that produced the rows */
+  int32_t flags;        /* the bits above: ROWS_NONFINITE — some element of rows_out is not finite (decided on the device, by
+                           bits): a controller must never forward such rows; STATE_NONFINITE — the state handed in held a
+                           non-finite value (checked on the host; the tick still runs); COLD — the tick ran Ndiffuse-1 steps */
+  float   rew_mean;     /* rews.mean() of the tick's last diffusion step (what mbd_plan_run logs per step) */
+  float   seconds;      /* host wall time submit -> rows on the host */
+  int32_t reserved[4];  /* written 0 */
+} mbd_mpc_tick_info;
+/* open: everything mbd_plan_run_mpc refuses, with the same codes and messages (NULL plan / config / key -> MBD_ERR_INVALID
+ * before any device access; the config's ranges; enable_demo without a demo record, a path-integral update ->
+ * MBD_ERR_UNSUPPORTED; a sharded plan -> MBD_ERR_STATE; the delay record's n_rows against exec_steps -> MBD_ERR_INVALID); a
+ * plant record set -> MBD_ERR_STATE (in a session the caller is the plant); a session already open -> MBD_ERR_STATE. */
+int mbd_plan_mpc_open(mbd_plan* plan, const mbd_mpc_config* mc, const uint32_t key[2]);
+/* submit: state HOST [state_size]; enqueues tick t and returns.  NULL plan / state -> MBD_ERR_INVALID; no session open, a tick
+ * already in flight, or n_ticks ticks served -> MBD_ERR_STATE. */
+int mbd_plan_mpc_submit(mbd_plan* plan, const float* state);
+/* collect: waits for the tick in flight (an event behind its last kernel, which has written the outputs into pinned host
+ * memory: a tick ends with no copy launch).  HOST outputs, each may be NULL: rows_out [E][Nu], mean_out [H][Nu], head_out
+ * [E][Nu], predicted_out [state_size] (without a delay record: the state handed in), info_out.  NULL plan -> MBD_ERR_INVALID;
+ * no session open or nothing in flight -> MBD_ERR_STATE. */
+int mbd_plan_mpc_collect(mbd_plan* plan, float* rows_out, float* mean_out, float* head_out, float* predicted_out,
+                         mbd_mpc_tick_info* info_out);
+/* == submit then collect */
+int mbd_plan_mpc_tick(mbd_plan* plan, const float* state, float* rows_out, float* mean_out, float* head_out,
+                      float* predicted_out, mbd_mpc_tick_info* info_out);
+/* the next tick is a cold one — Ybar = zeros, Ndiffuse-1 steps, sampled as tick 0 is, flagged COLD — and equals tick 0 of a
+ * fresh session whose key is this session's rng at that tick; the delay queue is left as it is.  NULL plan -> MBD_ERR_INVALID;
+ * no session open, or a tick in flight (collect it first) -> MBD_ERR_STATE. */
+int mbd_plan_mpc_reset_mean(mbd_plan* plan);
+/* close: waits for a tick in flight and drops it.  NULL plan -> MBD_ERR_INVALID; no session open -> MBD_ERR_STATE.
+ * mbd_plan_destroy closes an open session.  While a session is open, these calls on the same handle return MBD_ERR_STATE, the
+ * message naming the session: mbd_plan_run, _run_mpc, _eval, _set_state0, _reverse_once, _sample_rollout, _score_update and
+ * every mbd_plan_set_* record call (plant, ensemble, noise shape, noise basis, delay, demo). */
+int mbd_plan_mpc_close(mbd_plan* plan);
+
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
  * candidates Y0s [Nsample][H][Nu] (plans that keep normals instead form them here, from the normals, sigma_i and the
  * Ybar_i of the last step — between phase 1 and phase 2 the caller's d_Ybar_i must still be unchanged), the shard's
@@ -715,6 +775,34 @@ int mbd_sweep_set_mpc_demo(mbd_sweep* sweep, const mbd_mpc_demo* rec);
 /* episode k's err_out [T*E][K] and the batch's windows_out [T][K][50][3] of the last batch run with a record; as
  * mbd_plan_peek_mpc_track; k outside [0, n_plans) -> MBD_ERR_INVALID */
 int mbd_sweep_peek_mpc_track(mbd_sweep* sweep, int k, float* err_out, float* windows_out);
+/* ---- sessions of sweeps: P sessions in lockstep (mbd_plan_mpc_open, above; DESIGN.md section 1 "N11 session") ---- */
+/* Episode k of a sweep's session is EXACTLY mbd_plan_mpc_open's session on a plan of the sweep's config with key = keys[k] and
+ * temp_sample = the sweep's temps[k], fed states[k] — bit for bit, whatever the other episodes do or are fed (a non-finite state
+ * included) — and all episodes share mc.  A diffusion step of a tick is ONE rollout launch over the n_plans * Nsample candidates,
+ * the prediction of a delay record ONE launch over the episodes, and the tick ends with ONE boundary launch (blockIdx.y =
+ * episode) that writes every episode's results into the mailbox.  The sweep's noise shape, noise basis, delay and demo records
+ * are read at open; the sweep's start states are not used.
+ * keys [n_plans][2]; states HOST [n_plans][state_size]; HOST outputs, each may be NULL: rows_out [n_plans][E][Nu], means_out
+ * [n_plans][H][Nu], heads_out [n_plans][E][Nu], predicted_out [n_plans][state_size], infos_out [n_plans] (seconds: the tick's,
+ * the same for every episode).
+ * mbd_sweep_mpc_reset_mean(sweep, k): episode k's next tick is a cold one; the others' are not.  The lockstep loop then runs
+ * Ndiffuse-1 steps, and an episode that is not cold idles through the steps above K — what they compute for it is discarded, its
+ * key chain waits — and joins at step K from its shifted mean: its bits are a single session's.  One launch samples under one
+ * noise shape and basis: such a mixed tick under a record in force in the warm ticks only -> MBD_ERR_UNSUPPORTED at submit.
+ * Refusals as the plan calls', in their order: NULL sweep / config / keys / states -> MBD_ERR_INVALID before any device access;
+ * open: mbd_sweep_run_mpc's refusals with its codes, an episode with a plant record -> MBD_ERR_STATE, a session already open ->
+ * MBD_ERR_STATE; submit with no session, a tick in flight or n_ticks served, collect with nothing in flight, reset_mean / close
+ * with no session -> MBD_ERR_STATE; reset_mean's k outside [0, n_plans) -> MBD_ERR_INVALID.  While a session is open
+ * mbd_sweep_run, _run_mpc, _set_state0 and every mbd_sweep_set_* record call return MBD_ERR_STATE naming the session;
+ * mbd_sweep_destroy closes an open session. */
+int mbd_sweep_mpc_open(mbd_sweep* sweep, const mbd_mpc_config* mc, const uint32_t* keys);
+int mbd_sweep_mpc_submit(mbd_sweep* sweep, const float* states);
+int mbd_sweep_mpc_collect(mbd_sweep* sweep, float* rows_out, float* means_out, float* heads_out, float* predicted_out,
+                          mbd_mpc_tick_info* infos_out);
+int mbd_sweep_mpc_tick(mbd_sweep* sweep, const float* states, float* rows_out, float* means_out, float* heads_out,
+                       float* predicted_out, mbd_mpc_tick_info* infos_out);
+int mbd_sweep_mpc_reset_mean(mbd_sweep* sweep, int k);
+int mbd_sweep_mpc_close(mbd_sweep* sweep);
 /* path-integral sweeps: the carried sampling sigma of every plan after the last run (path_integral.py:113,131); HOST [n_plans] */
 int mbd_sweep_get_sigmas(mbd_sweep* sweep, float* sigmas_out);
 /* average milliseconds of the sweep's rollout launches since the last reset (hipEvents on the launch stream) */

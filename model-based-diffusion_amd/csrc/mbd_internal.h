@@ -144,6 +144,33 @@ class PinnedWord {  // one int of pinned host memory the device stores into (a p
   int* h_ = nullptr;
 };
 
+class PinnedBuf {  // n floats of pinned host memory mapped into the device's address space (a session's staging and mailbox)
+ public:
+  PinnedBuf() = default;
+  PinnedBuf(PinnedBuf&& o) noexcept : h_(o.h_), d_(o.d_) { o.h_ = nullptr; o.d_ = nullptr; }
+  PinnedBuf& operator=(PinnedBuf&& o) noexcept { std::swap(h_, o.h_); std::swap(d_, o.d_); return *this; }
+  ~PinnedBuf() { release(); }
+  void release() {
+    if (h_) (void)hipHostFree(h_);
+    h_ = nullptr; d_ = nullptr;
+  }
+  hipError_t alloc(size_t n) {  // zeroed; whatever it held before is gone
+    release();
+    hipError_t e = hipHostMalloc((void**)&h_, sizeof(float) * n, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e != hipSuccess) { h_ = nullptr; return e; }
+    memset(h_, 0, sizeof(float) * n);
+    e = hipHostGetDevicePointer((void**)&d_, h_, 0);
+    if (e != hipSuccess) release();
+    return e;
+  }
+  float* host() const { return h_; }
+  float* dev() const { return d_; }  // the same bytes as the device addresses them
+
+ private:
+  float* h_ = nullptr;
+  float* d_ = nullptr;
+};
+
 struct mbd_env : EnvShape {  // (the shape: derive_shape, at creation; car2d keeps the defaults)
   int kind = ENV_MODEL;
   int device = 0;
@@ -346,6 +373,10 @@ struct DemoRec {
   const float* window(int t) const { return d_windows + (size_t)t * K * kXrefRows * C; }
   float* xlog(int t, int P, int E, int k = 0) const { return d_xlog + ((size_t)t * P + k) * E * K * 3; }
   int finish(int T, int P, int E, hipStream_t s);
+  // a session (mbd_plan_mpc_open) has no table: session_start forgets the last episode's logs and makes room for ONE window,
+  // session_window fills it with tick t's — the window start()'s table holds at slot t — by one launch of the same kernel
+  int session_start();
+  int session_window(long long t, int E, int D, hipStream_t s);
   // HOST err_out [T E][K] and windows_out [T][K][kXrefRows][C] of episode k of the last run; either may be NULL
   int peek(int device, int k, float* err_out, float* windows_out, const char* what) const;
 };

@@ -106,6 +106,21 @@ struct NoiseRing {
   }
 };
 
+// A session (include/mbd_hip.h mbd_plan_mpc_open): the episode state mbd_plan_run_mpc keeps in locals, kept across calls, and
+// the two pinned buffers a tick talks to the host through.  All zero: no session (a zeroed stand-in handle has none).
+struct MpcSession {
+  bool open = false, in_flight = false;
+  bool cold = true;             // the next tick runs Ndiffuse-1 steps from Ybar = zeros (tick 0; after mbd_plan_mpc_reset_mean)
+  mbd_mpc_config mc{};
+  uint32_t rng[2] = {0, 0};     // the episode's key chain: rng, k_t = split(rng) per tick
+  int t = 0;                    // ticks served
+  int qbuf = 0;                 // the buffer of d_mpc_queue the next tick reads
+  int flags = 0;                // of the tick in flight: what the host decided (COLD, STATE_NONFINITE)
+  PinnedBuf stage, mailbox;     // the state on its way up [S]; rows | mean | head | predicted | rew_mean | flag on their way down
+  Event done;                   // recorded behind the tick's boundary kernel
+  std::chrono::steady_clock::time_point t_submit{};
+};
+
 struct mbd_plan {
   mbd_env* env = nullptr;
   hipStream_t last_stream = nullptr;  // stream of the plan's previous phase call (plan_enter orders a change of stream)
@@ -166,10 +181,17 @@ struct mbd_plan {
   bool has_basis = false;
   int basis_knots = 0, basis_when = MBD_NOISE_ALWAYS;
   TimingPool timing;
+  // the session a caller drives tick by tick (mbd_plan_mpc_open); it uses the episodes' buffers above — d_mpc_state for the
+  // state handed in, d_mpc_pred for the one predicted state, d_mpc_queue — so a handle runs episodes or a session, not both
+  MpcSession session;
   ~mbd_plan() {  // (streams, events and buffers release themselves, on the env's device)
     if (env) (void)hipSetDevice(env->device);
   }
 };
+
+// the refusal of a call that would disturb an open session (include/mbd_hip.h mbd_plan_mpc_close)
+#define NO_SESSION(p, what) \
+  if ((p)->session.open) return fail(MBD_ERR_STATE, what ": a session is open on this plan (mbd_plan_mpc_close first)")
 
 // ==================================================================================================
 // planner
@@ -252,6 +274,10 @@ extern "C" int mbd_plan_create(mbd_env* env, const mbd_plan_config* cfg, mbd_pla
 }
 
 extern "C" int mbd_plan_destroy(mbd_plan* p) {
+  if (p && p->session.in_flight) {  // (an open session ends here: its last kernel still writes the mailbox)
+    (void)hipSetDevice(p->env->device);
+    (void)hipStreamSynchronize(p->stream);
+  }
   delete p;  // (nullptr is fine)
   return MBD_OK;
 }
@@ -267,6 +293,7 @@ extern "C" int mbd_plan_schedule(const mbd_plan* p, float* alphas, float* alphas
 
 extern "C" int mbd_plan_set_state0(mbd_plan* p, const float* state0) {
   if (!p || !state0) return fail(MBD_ERR_INVALID, "NULL argument");
+  NO_SESSION(p, "set_state0");
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipMemcpy(p->d_state0, state0, sizeof(float) * p->env->state_size(), hipMemcpyHostToDevice));
   return MBD_OK;
@@ -544,6 +571,7 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
 
 extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2], const float* d_Ybar_i,
                                        float* d_rews_local, float* d_logpd_local, void* stream_) {
+  if (p) NO_SESSION(p, "sample_rollout");
   return plan_sample_rollout(p, i, key_sample, d_Ybar_i, d_rews_local, d_logpd_local, (hipStream_t)stream_,
                              p ? p->d_state0.get() : nullptr, p ? noise_always(p) : NoiseSpec{});
 }
@@ -634,6 +662,7 @@ extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_samp
                                      const float* d_rews_all, const float* d_logpd_all, float* d_Ybar_im1,
                                      float* d_rew_mean, void* stream_) {
   (void)key_sample;  // the candidates (or their normals) of all N are already resident from phase 1 of this step
+  if (p) NO_SESSION(p, "score_update");
   return plan_score_update(p, i, d_Ybar_i, d_rews_all, d_logpd_all, d_Ybar_im1, d_rew_mean, stream_, p ? p->env->rew_xref : 0.0f);
 }
 
@@ -675,6 +704,7 @@ int check_noise_shape(const mbd_noise_shape* rec, int Hsample, int action_size) 
 
 extern "C" int mbd_plan_set_noise_shape(mbd_plan* p, const mbd_noise_shape* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_noise_shape");
   if (rec) MBD_TRY(check_noise_shape(rec, p->cfg.Hsample, p->Nu));
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipDeviceSynchronize());  // (a step in flight, or normals being prepared ahead, may still read the previous table)
@@ -729,6 +759,7 @@ int check_noise_basis(const mbd_noise_basis* rec, int Hsample) {
 
 extern "C" int mbd_plan_set_noise_basis(mbd_plan* p, const mbd_noise_basis* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_noise_basis");
   if (rec) MBD_TRY(check_noise_basis(rec, p->cfg.Hsample));
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipDeviceSynchronize());  // (a step in flight, or normals being prepared ahead, may still read the previous table)
@@ -833,6 +864,7 @@ static int reverse_once_impl(mbd_plan* p, const float* d_state0, int i, uint32_t
 extern "C" int mbd_plan_reverse_once(mbd_plan* p, int i, uint32_t key_inout[2], float* d_Ybar, float* d_rew_mean,
                                      void* stream_) {
   if (!p || !key_inout || !d_Ybar || !d_rew_mean) return fail(MBD_ERR_INVALID, "NULL argument");
+  NO_SESSION(p, "reverse_once");
   hipStream_t s = (hipStream_t)stream_;
   // the update is not in place on the device (wmean reads Ybar_i while writing Ybar_{i-1})
   MBD_TRY(reverse_once_impl(p, p->d_state0, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s, noise_always(p)));
@@ -843,6 +875,7 @@ extern "C" int mbd_plan_reverse_once(mbd_plan* p, int i, uint32_t key_inout[2], 
 extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_out, float* rew_means_out,
                             float* rew_final_out, double* loop_seconds_out) {
   if (!p || !key) return fail(MBD_ERR_INVALID, "NULL argument");
+  NO_SESSION(p, "run");
   HIP_TRY(hipSetDevice(p->env->device));
   const int Nd = p->cfg.Ndiffuse, HNu = p->HNu;
   hipStream_t s = p->stream;
@@ -934,6 +967,7 @@ int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc, bool ha
 
 extern "C" int mbd_plan_set_mpc_plant(mbd_plan* p, const mbd_mpc_plant* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_mpc_plant");
   if (!rec) {
     p->has_plant = false;
     p->plant_rec = mbd_mpc_plant{};
@@ -1003,6 +1037,7 @@ int DelayRec::upload(float* d_queue, int copies, int E, int Nu, hipStream_t s) c
 
 extern "C" int mbd_plan_set_mpc_delay(mbd_plan* p, const mbd_mpc_delay* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_mpc_delay");
   return p->delay.set(rec, p->Nu);
 }
 
@@ -1074,6 +1109,23 @@ int DemoRec::start(int T, int P, int E, int D, hipStream_t s) {
   return MBD_OK;
 }
 
+int DemoRec::session_start() {
+  HIP_TRY(d_windows.grow((size_t)K * kXrefRows * C));
+  ticks = exec = episodes = 0;  // (behind what can fail)
+  return MBD_OK;
+}
+
+int DemoRec::session_window(long long t, int E, int D, hipStream_t s) {
+  // windows[t][k][h] = clip[k][min(c0 + (t + D) E + h, L - 1)]: a table of one tick whose start row is the tick's own — a start
+  // at or past the clip's last row reads that row for every h, so the start is clamped there and stays an int
+  long long start = (long long)c0 + (t + D) * (long long)E;
+  if (start > (long long)L - 1) start = (long long)L - 1;
+  hipLaunchKernelGGL(demo_windows_kernel, dim3(demo_blocks((long long)K * kXrefRows)), dim3(256), 0, s, (const float*)d_clip, L,
+                     (int)start, 1, K, C, E, 0, d_windows.get());
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+
 int DemoRec::finish(int T, int P, int E, hipStream_t s) {
   hipLaunchKernelGGL(mpc_track_err_kernel, dim3(demo_blocks((long long)T * P * E * K)), dim3(256), 0, s, (const float*)d_xlog,
                      (const float*)d_clip, L, c0, T, P, E, K, C, d_err.get());
@@ -1101,6 +1153,7 @@ int DemoRec::peek(int device, int k, float* err_out, float* windows_out, const c
 
 extern "C" int mbd_plan_set_mpc_demo(mbd_plan* p, const mbd_mpc_demo* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_mpc_demo");
   return p->demo.set(p->env, p->cfg, rec);
 }
 
@@ -1200,6 +1253,7 @@ static int check_ensemble(const mbd_plan* p, const mbd_ensemble* rec) {
 
 extern "C" int mbd_plan_set_ensemble(mbd_plan* p, const mbd_ensemble* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_ensemble");
   if (!rec) {
     p->has_ens = false;
     p->ens_stepped = false;
@@ -1235,6 +1289,58 @@ extern "C" int mbd_plan_peek_ensemble(mbd_plan* p, float* rews_members_out, floa
   return MBD_OK;
 }
 
+// ---- one tick's planning, shared by the batch episode (mbd_plan_run_mpc) and the session (mbd_plan_mpc_submit) ------------------
+// The tick's keys, host arithmetic: rng, k_t = split(rng) advances the episode's chain; r = k_t is where the tick's own chain
+// starts (mbd_plan_run's from it); after = split(split(rng')[1])[1] is the Y0s_rng of tick t+1's first step, whose normals are
+// prepared beside this tick's last rollout (rng' = the advanced rng: looked at, not advanced).
+static void mpc_tick_keys(int prng_impl, uint32_t rng[2], uint32_t r[2], uint32_t after[2]) {
+  uint32_t kk[4], nk[4];
+  host_split(rng, 2, prng_impl, kk);
+  rng[0] = kk[0]; rng[1] = kk[1];
+  r[0] = kk[2]; r[1] = kk[3];
+  host_split(rng, 2, prng_impl, kk);
+  const uint32_t k_next[2] = {kk[2], kk[3]};
+  host_split(k_next, 2, prng_impl, nk);
+  after[0] = nk[2]; after[1] = nk[3];
+}
+// What a tick plans from and under.  s_t: the state the system is in.  q_in: the committed queue [DE][Nu] of an episode with a
+// delay record — the tick then first predicts, with the plan's env, where those rows leave the system (ONE rollout, one
+// candidate, into shat) and plans from there — or nullptr.  cold: Ybar = zeros was set by the caller and the tick runs steps
+// Ndiffuse-1 .. 1 under the noise in force ALWAYS (tick 0; a session's tick after mbd_plan_mpc_reset_mean); otherwise steps K .. 1
+// from the shifted mean in d_Ybar under the warm ticks' noise.  r: k_t, advanced along the tick's chain.  key_after: see
+// mpc_tick_keys, nullptr: no tick follows.  d_xref: the tick's demo window, or nullptr.  *mean: where M_t lies afterwards.
+struct MpcTick {
+  const float* s_t = nullptr;
+  const float* q_in = nullptr;
+  float* shat = nullptr;
+  int DE = 0;
+  bool cold = false;
+  int K = 1;
+  const uint32_t* key_after = nullptr;
+  const float* d_xref = nullptr;
+};
+static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStream_t s, const float** mean) {
+  const int Nd = p->cfg.Ndiffuse, HNu = p->HNu;
+  // with a delay record: the rows the system is committed to, the prediction of where they leave it, and the plan from there
+  const float* plan_from = tk.s_t;
+  if (tk.q_in) {
+    MBD_TRY(launch_rollout(p->env, tk.s_t, tk.q_in, 1, tk.DE, nullptr, nullptr, nullptr, tk.shat, s));
+    plan_from = tk.shat;
+  }
+  // the noise shape and basis: a cold tick is mbd_plan_run's loop (MBD_NOISE_WARM_TICKS: without), every other tick samples under
+  // them in either mode — the first normals of the next tick, prepared beside this tick's last rollout, included
+  const NoiseSpec ns = tk.cold ? noise_always(p) : noise_warm(p);
+  const float* cur = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros of a cold tick, shift_E(M_{t-1}) otherwise
+  for (int i = tk.cold ? Nd - 1 : tk.K; i >= 1; --i) {
+    float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
+    MBD_TRY(plan_keep_in_step(p));
+    MBD_TRY(reverse_once_impl(p, plan_from, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, ns, tk.key_after, noise_warm(p), tk.d_xref));
+    cur = nxt;
+  }
+  *mean = cur;
+  return MBD_OK;
+}
+
 // Receding horizon (include/mbd_hip.h): the host only enqueues — the key chain is host arithmetic, the executed state never
 // comes back — and keeps at most one step ahead of the device through plan_keep_in_step, as mbd_plan_run does.  A tick
 // boundary adds two launches on the plan's stream: the rollout of M_t's first E rows (the env's rollout path, one candidate:
@@ -1259,13 +1365,16 @@ extern "C" int mbd_plan_peek_ensemble(mbd_plan* p, float* rews_members_out, floa
 // pointer into it where they read the env's demo (launch_rollout's and launch_logpd's d_xref) and the record's rew_xref where they
 // read the env's; the rollout of the executed rows is handed its slice of the position log as d_xpos; mpc_track_err_kernel, ONE
 // launch behind the loop, reads that log.  The ring's argument does not see any of it.
+// The planning of a tick — the prediction, the diffusion steps, the key chain — is mpc_plan_tick above, which a session
+// (mbd_plan_mpc_submit) runs as well: what is said here about those launches holds for both, and the session restates the rest.
 extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
                                 float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
   if (!mc) return fail(MBD_ERR_INVALID, "mpc config is NULL");
   if (!key) return fail(MBD_ERR_INVALID, "key is NULL");
+  NO_SESSION(p, "run_mpc");
   const mbd_plan_config& c = p->cfg;
-  const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
+  const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, H = c.Hsample;
   MBD_TRY(check_mpc_config(c, mc, p->demo.has));
   if (c.shard_count != c.Nsample)
     return fail(MBD_ERR_STATE, "shard_count=%d of Nsample=%d: receding horizon runs unsharded plans", c.shard_count, c.Nsample);
@@ -1309,38 +1418,19 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   HIP_TRY(hipStreamSynchronize(s));
   const auto t0 = std::chrono::steady_clock::now();
   if (has_demo) MBD_TRY(p->demo.start(T, 1, E, has_delay ? D : 0, s));
-  uint32_t rng[2] = {key[0], key[1]}, kk[4];
-  host_split(rng, 2, c.prng_impl, kk);  // rng, k_0 = split(rng)
+  uint32_t rng[2] = {key[0], key[1]};
   for (int t = 0; t < T; ++t) {
-    uint32_t r[2] = {kk[2], kk[3]};  // k_t: the tick's key chain is mbd_plan_run's from it
-    rng[0] = kk[0]; rng[1] = kk[1];
-    // the Y0s_rng of tick t+1's first step, split(split(rng)[1])[1]: its normals are prepared beside tick t's last rollout
-    uint32_t after[4];
-    if (t + 1 < T) {
-      host_split(rng, 2, c.prng_impl, kk);
-      const uint32_t k_next[2] = {kk[2], kk[3]};
-      host_split(k_next, 2, c.prng_impl, after);
-    }
-    const float* cur = ybar0;
-    // with a delay record: the rows the system is committed to, the prediction of where they leave it, and the plan from there
+    uint32_t r[2], after[2];  // k_t: the tick's key chain is mbd_plan_run's from it; the first Y0s_rng of tick t+1
+    mpc_tick_keys(c.prng_impl, rng, r, after);
+    // with a delay record: the queue the tick reads, and the one its boundary kernel advances it into
     const float* q_in = has_delay ? p->d_mpc_queue + (size_t)(t & 1) * Q : nullptr;
     float* q_out = has_delay ? p->d_mpc_queue + (size_t)((t + 1) & 1) * Q : nullptr;
-    const float* plan_from = s_t;
-    if (has_delay) {
-      float* shat = p->d_mpc_pred + (size_t)t * S;
-      MBD_TRY(launch_rollout(e, s_t, q_in, 1, D * E, nullptr, nullptr, nullptr, shat, s));
-      plan_from = shat;
-    }
-    // the noise shape and basis: tick 0 is mbd_plan_run's loop (MBD_NOISE_WARM_TICKS: without), every later tick samples under
-    // them in either mode — the first normals of tick t + 1, prepared beside this tick's last rollout, included
-    const NoiseSpec ns = t == 0 ? noise_always(p) : noise_warm(p);
-    for (int i = t == 0 ? Nd - 1 : K; i >= 1; --i) {
-      float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
-      MBD_TRY(plan_keep_in_step(p));
-      MBD_TRY(reverse_once_impl(p, plan_from, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, ns, t + 1 < T ? after + 2 : nullptr,
-                                noise_warm(p), has_demo ? p->demo.window(t) : nullptr));
-      cur = nxt;
-    }
+    MpcTick tk;
+    tk.s_t = s_t; tk.q_in = q_in; tk.shat = has_delay ? p->d_mpc_pred + (size_t)t * S : nullptr; tk.DE = D * E;
+    tk.cold = t == 0; tk.K = K; tk.key_after = t + 1 < T ? after : nullptr;
+    tk.d_xref = has_demo ? p->demo.window(t) : nullptr;
+    const float* cur = nullptr;
+    MBD_TRY(mpc_plan_tick(p, tk, r, s, &cur));
     // execute M_t's first E rows from s_t — with a delay record the queue's head —, then the boundary: Ybar of tick t+1, the
     // logs of M_t and s_{t+1}
     float* s_next = p->d_mpc_state + (size_t)(t & 1) * S;
@@ -1396,8 +1486,181 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   return MBD_OK;
 }
 
+// ---- sessions (include/mbd_hip.h mbd_plan_mpc_open) --------------------------------------------------------------------------
+// A session is mbd_plan_run_mpc's loop with the body of one tick per call and the caller in the plant's place.  A tick enqueues,
+// on the plan's stream: the upload of the state from its pinned staging buffer (one hipMemcpyAsync), with a demo record the launch
+// that builds the tick's window, mpc_plan_tick — the function the batch episode runs — and mpc_session_boundary_kernel, which
+// shifts the mean, advances the queue and writes the results into the mailbox; then an event.  No rollout of executed rows, no log.
+// The ring of noise buffers (mbd_plan) keeps its argument, restated: the launches a tick adds are stream-ordered behind the previous
+// tick's boundary and in front of the tick's first rollout, carry no progress word and no noise job, so the sequence numbers the
+// host looks for count the planning rollouts alone; the host waits at every tick's end (collect, on the event), and nothing is
+// enqueued between collect and the next submit, so when a tick's first step looks for the last reader of a buffer the stream is
+// idle and the progress word holds the last rollout's number — the in-step form, always.  A session always declares the next
+// tick's first key (it is known: the chain is host arithmetic), unless mc.n_ticks says no tick follows; the normals prepared
+// beside the tick's last rollout — on the second stream for a rollout that fills the chip or a plan with a basis — are joined by
+// the next tick's first step as any prepared buffer is, or regenerated when that tick turns out cold under a warm-only shape
+// (the tag differs).  The bits depend on none of this.
+// What close leaves behind: a session opened without a limit (n_ticks = INT32_MAX) declares a next key at EVERY tick, its last one
+// included, so after close one ring buffer holds normals nobody asked for — prepared on the second stream, possibly still being
+// written.  That is a stale prepared buffer like any other: its tag (key, shape, basis) matches no later step unless it IS that
+// step's, the next writer of the buffer first joins the job through ring.join (obtain_normals, prepare_noise_job), and
+// mbd_plan_destroy frees the buffers with hipFree, which waits for the device.  run and run_mpc after a session give a fresh
+// handle's bits (tests/test_gpu_mpc_online.py).
+static size_t session_mailbox_floats(const mbd_plan* p, int EN) {
+  return 2 * (size_t)EN + (size_t)p->HNu + (size_t)p->env->state_size() + 2;
+}
+static SessionMailbox session_mailbox(const mbd_plan* p, float* base, int EN) {
+  SessionMailbox mb;
+  mb.rows = base;
+  mb.mean = mb.rows + EN;
+  mb.head = mb.mean + p->HNu;
+  mb.pred = mb.head + EN;
+  mb.rew_mean = mb.pred + p->env->state_size();
+  mb.flag = (int*)(mb.rew_mean + 1);
+  return mb;
+}
+
+extern "C" int mbd_plan_mpc_open(mbd_plan* p, const mbd_mpc_config* mc, const uint32_t key[2]) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (!mc) return fail(MBD_ERR_INVALID, "mpc config is NULL");
+  if (!key) return fail(MBD_ERR_INVALID, "key is NULL");
+  const mbd_plan_config& c = p->cfg;
+  MBD_TRY(check_mpc_config(c, mc, p->demo.has));
+  if (c.shard_count != c.Nsample)
+    return fail(MBD_ERR_STATE, "shard_count=%d of Nsample=%d: receding horizon runs unsharded plans", c.shard_count, c.Nsample);
+  MBD_TRY(p->delay.check_run(mc->exec_steps));
+  if (p->has_plant) return fail(MBD_ERR_STATE, "mpc_open: the plan carries a plant record: in a session the caller is the plant");
+  NO_SESSION(p, "mpc_open");
+  mbd_env* e = p->env;
+  HIP_TRY(hipSetDevice(e->device));
+  MpcSession& ss = p->session;
+  const int S = e->state_size(), EN = mc->exec_steps * p->Nu, Q = p->delay.D * EN;
+  HIP_TRY(p->d_mpc_state.grow(2 * (size_t)S));
+  if (p->delay.has) {
+    HIP_TRY(p->d_mpc_queue.grow(2 * (size_t)Q));
+    HIP_TRY(p->d_mpc_pred.grow(S));
+  }
+  HIP_TRY(ss.stage.alloc(S));
+  HIP_TRY(ss.mailbox.alloc(session_mailbox_floats(p, EN)));
+  if (!ss.done) HIP_TRY(ss.done.create());
+  hipStream_t s = p->stream;
+  if (p->delay.has) MBD_TRY(p->delay.upload(p->d_mpc_queue, 1, mc->exec_steps, p->Nu, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (p->demo.has) MBD_TRY(p->demo.session_start());
+  // (nothing fails from here on: a refused or failed open leaves the last episode's logs readable)
+  if (p->delay.has) p->delay.pred_ticks = 0;  // (mbd_plan_peek_mpc_predicted does not serve sessions)
+  ss.mc = *mc;
+  ss.rng[0] = key[0]; ss.rng[1] = key[1];
+  ss.t = 0; ss.qbuf = 0; ss.flags = 0;
+  ss.cold = true;
+  ss.in_flight = false;
+  ss.open = true;
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_mpc_submit(mbd_plan* p, const float* state) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (!state) return fail(MBD_ERR_INVALID, "state is NULL");
+  MpcSession& ss = p->session;
+  if (!ss.open) return fail(MBD_ERR_STATE, "mpc_submit: no session is open on this plan");
+  if (ss.in_flight) return fail(MBD_ERR_STATE, "mpc_submit: a tick is in flight (mbd_plan_mpc_collect first)");
+  if (ss.t >= ss.mc.n_ticks) return fail(MBD_ERR_STATE, "mpc_submit: the session has served its n_ticks=%d ticks", ss.mc.n_ticks);
+  mbd_env* e = p->env;
+  HIP_TRY(hipSetDevice(e->device));
+  const mbd_plan_config& c = p->cfg;
+  const int S = e->state_size(), E = ss.mc.exec_steps, EN = E * p->Nu, HNu = p->HNu, Nd = c.Ndiffuse;
+  const bool has_delay = p->delay.has;
+  const int D = p->delay.D, Q = D * EN;
+  hipStream_t s = p->stream;
+  ss.t_submit = std::chrono::steady_clock::now();
+  int flags = ss.cold ? MBD_TICK_COLD : 0;
+  for (int k = 0; k < S; ++k)
+    if (!std::isfinite(state[k])) flags |= MBD_TICK_STATE_NONFINITE;
+  memcpy(ss.stage.host(), state, sizeof(float) * S);
+  float* s_t = p->d_mpc_state;
+  HIP_TRY(hipMemcpyAsync(s_t, ss.stage.host(), sizeof(float) * S, hipMemcpyHostToDevice, s));
+  if (ss.cold) HIP_TRY(hipMemsetAsync(p->d_Ybar, 0, sizeof(float) * HNu, s));
+  uint32_t rng[2] = {ss.rng[0], ss.rng[1]}, r[2], after[2];  // (a copy of the chain: committed with the tick, below)
+  mpc_tick_keys(c.prng_impl, rng, r, after);
+  if (p->demo.has) MBD_TRY(p->demo.session_window(ss.t, E, has_delay ? D : 0, s));
+  const float* q_in = has_delay ? p->d_mpc_queue + (size_t)ss.qbuf * Q : nullptr;
+  float* q_out = has_delay ? p->d_mpc_queue + (size_t)(ss.qbuf ^ 1) * Q : nullptr;
+  MpcTick tk;
+  tk.s_t = s_t; tk.q_in = q_in; tk.shat = has_delay ? p->d_mpc_pred.get() : nullptr; tk.DE = D * E;
+  tk.cold = ss.cold; tk.K = ss.mc.warm_steps; tk.key_after = ss.t + 1 < ss.mc.n_ticks ? after : nullptr;
+  tk.d_xref = p->demo.has ? p->demo.window(0) : nullptr;
+  const float* M = nullptr;
+  MBD_TRY(mpc_plan_tick(p, tk, r, s, &M));
+  hipLaunchKernelGGL(mpc_session_boundary_kernel, dim3(1), dim3(256), 0, s, M, HNu, EN, p->d_Ybar.get(), q_in, q_out, Q,
+                     has_delay ? (const float*)p->d_mpc_pred : (const float*)nullptr, S, (const float*)(p->d_rewmeans + (Nd - 2)),
+                     session_mailbox(p, ss.mailbox.dev(), EN));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ss.done, s));
+  ss.rng[0] = rng[0]; ss.rng[1] = rng[1];  // (a submit that failed above has not moved the chain: a retry plans tick t with k_t)
+  ss.flags = flags;
+  ss.in_flight = true;
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_mpc_collect(mbd_plan* p, float* rows_out, float* mean_out, float* head_out, float* predicted_out,
+                                    mbd_mpc_tick_info* info_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  MpcSession& ss = p->session;
+  if (!ss.open) return fail(MBD_ERR_STATE, "mpc_collect: no session is open on this plan");
+  if (!ss.in_flight) return fail(MBD_ERR_STATE, "mpc_collect: no tick is in flight (mbd_plan_mpc_submit first)");
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipEventSynchronize(ss.done));
+  const int S = p->env->state_size(), EN = ss.mc.exec_steps * p->Nu;
+  const SessionMailbox mb = session_mailbox(p, ss.mailbox.host(), EN);
+  if (rows_out) memcpy(rows_out, mb.rows, sizeof(float) * EN);
+  if (mean_out) memcpy(mean_out, mb.mean, sizeof(float) * p->HNu);
+  if (head_out) memcpy(head_out, mb.head, sizeof(float) * EN);
+  if (predicted_out) memcpy(predicted_out, p->delay.has ? mb.pred : ss.stage.host(), sizeof(float) * S);
+  const auto t1 = std::chrono::steady_clock::now();
+  if (info_out) {
+    *info_out = mbd_mpc_tick_info{};
+    info_out->tick = ss.t;
+    info_out->flags = ss.flags | (*mb.flag ? MBD_TICK_ROWS_NONFINITE : 0);
+    info_out->rew_mean = *mb.rew_mean;
+    info_out->seconds = std::chrono::duration<float>(t1 - ss.t_submit).count();
+  }
+  ss.in_flight = false;
+  ss.cold = false;
+  ss.qbuf ^= 1;
+  ss.t += 1;
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_mpc_tick(mbd_plan* p, const float* state, float* rows_out, float* mean_out, float* head_out,
+                                 float* predicted_out, mbd_mpc_tick_info* info_out) {
+  MBD_TRY(mbd_plan_mpc_submit(p, state));
+  return mbd_plan_mpc_collect(p, rows_out, mean_out, head_out, predicted_out, info_out);
+}
+
+extern "C" int mbd_plan_mpc_reset_mean(mbd_plan* p) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (!p->session.open) return fail(MBD_ERR_STATE, "mpc_reset_mean: no session is open on this plan");
+  if (p->session.in_flight) return fail(MBD_ERR_STATE, "mpc_reset_mean: a tick is in flight (mbd_plan_mpc_collect first)");
+  p->session.cold = true;  // (the next submit zeroes Ybar; the queue stays)
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_mpc_close(mbd_plan* p) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  MpcSession& ss = p->session;
+  if (!ss.open) return fail(MBD_ERR_STATE, "mpc_close: no session is open on this plan");
+  HIP_TRY(hipSetDevice(p->env->device));
+  if (ss.in_flight) HIP_TRY(hipStreamSynchronize(p->stream));  // (its last kernel writes the mailbox)
+  ss.in_flight = false;
+  ss.open = false;
+  ss.stage.release();
+  ss.mailbox.release();
+  return MBD_OK;
+}
+
 extern "C" int mbd_plan_eval(mbd_plan* p, const float* Y, float* rew_final_out) {
   if (!p || !Y || !rew_final_out) return fail(MBD_ERR_INVALID, "NULL argument");
+  NO_SESSION(p, "eval");
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipMemcpy(p->d_Ybar + p->HNu, Y, sizeof(float) * p->HNu, hipMemcpyHostToDevice));
   MBD_TRY(launch_rollout(p->env, p->d_state0, p->d_Ybar + p->HNu, 1, p->cfg.Hsample, nullptr, p->d_scratch, nullptr, nullptr,

@@ -349,6 +349,71 @@ static __global__ __launch_bounds__(256) void mpc_boundary_delay_batch_kernel(co
   mpc_queue_advance(M, shift, q_in + k * Q, q_out + k * Q, Q, rows ? rows + k * shift : nullptr);
 }
 
+// The boundary of a SESSION's tick (include/mbd_hip.h mbd_plan_mpc_submit), one workgroup behind the tick's last weighted mean:
+// nothing was executed on the device, so there is no state to log — the launch shifts M into the next tick's Ybar, advances the
+// committed queue into its other buffer (q_in nullptr: no delay record) and hands the tick's results to the host by writing
+// them straight into the mailbox `mb`, pinned host memory mapped into the device's address space, so a tick ends with no copy
+// launch: rows = M[0:shift] | mean = M | head = C[0] (without a queue: M[0:shift]) | predicted [S] (pred nullptr: left alone) |
+// rew_mean | the flag word.  The flag word is 1 iff some element of rows is not finite, decided on the bits (exponent all
+// ones), not by a compare a fast-math flag could fold; an OR over the workgroup.  Copies throughout: -0.0 stays -0.0.  Plain
+// vector stores and a system-scope fence; the host waits on an event recorded behind the launch, it does not spin on the memory.
+struct SessionMailbox {
+  float* rows;   // [shift]
+  float* mean;   // [HNu]
+  float* head;   // [shift]
+  float* pred;   // [S]
+  float* rew_mean;
+  int* flag;
+};
+__device__ __forceinline__ void mpc_session_boundary_body(const float* __restrict__ M, int HNu, int shift,
+                                                          float* __restrict__ ybar_next, const float* __restrict__ q_in,
+                                                          float* __restrict__ q_out, int Q, const float* __restrict__ pred, int S,
+                                                          const float* __restrict__ rew_mean, const SessionMailbox& mb) {
+  int bad = 0;
+  for (int e = threadIdx.x; e < HNu; e += blockDim.x) {
+    const float m = M[e];
+    mb.mean[e] = m;
+    if (e < shift) {
+      mb.rows[e] = m;
+      mb.head[e] = q_in ? q_in[e] : m;
+      bad |= (__float_as_uint(m) & 0x7f800000u) == 0x7f800000u;
+    }
+    ybar_next[e] = e < HNu - shift ? M[e + shift] : 0.0f;
+  }
+  if (q_in) mpc_queue_advance(M, shift, q_in, q_out, Q, nullptr);
+  if (pred)
+    for (int e = threadIdx.x; e < S; e += blockDim.x) mb.pred[e] = pred[e];
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) {
+    *mb.rew_mean = *rew_mean;
+    *mb.flag = bad ? 1 : 0;
+  }
+  __threadfence_system();
+}
+static __global__ __launch_bounds__(256) void mpc_session_boundary_kernel(const float* __restrict__ M, int HNu, int shift,
+                                                                    float* __restrict__ ybar_next, const float* __restrict__ q_in,
+                                                                    float* __restrict__ q_out, int Q, const float* __restrict__ pred,
+                                                                    int S, const float* __restrict__ rew_mean, SessionMailbox mb) {
+  mpc_session_boundary_body(M, HNu, shift, ybar_next, q_in, q_out, Q, pred, S, rew_mean, mb);
+}
+
+// ... and the boundary of a tick of a SWEEP's session (mbd_sweep_mpc_submit), blockIdx.y = episode: episode k's M lies M_stride
+// floats from episode 0's, its queue at q + k Q, its predicted state at pred + k S, its mean reward rew_stride floats from episode
+// 0's; the mailbox holds rows [P][shift] | means [P][HNu] | heads [P][shift] | predicted [P][S] | rew_mean [P] | flags [P].
+static __global__ __launch_bounds__(256) void mpc_session_boundary_batch_kernel(const float* __restrict__ M, long long M_stride, int HNu,
+                                                                          int shift, float* __restrict__ ybar_next,
+                                                                          const float* __restrict__ q_in, float* __restrict__ q_out,
+                                                                          int Q, const float* __restrict__ pred, int S,
+                                                                          const float* __restrict__ rew_mean, int rew_stride,
+                                                                          SessionMailbox mb) {
+  const long long k = blockIdx.y;
+  SessionMailbox m;
+  m.rows = mb.rows + k * shift; m.mean = mb.mean + k * HNu; m.head = mb.head + k * shift; m.pred = mb.pred + k * S;
+  m.rew_mean = mb.rew_mean + k; m.flag = mb.flag + k;
+  mpc_session_boundary_body(M + k * M_stride, HNu, shift, ybar_next + k * HNu, q_in ? q_in + k * Q : nullptr,
+                            q_in ? q_out + k * Q : nullptr, Q, pred ? pred + k * S : nullptr, S, rew_mean + k * rew_stride, m);
+}
+
 // The demo clock of an episode with a demo record (include/mbd_hip.h mbd_mpc_demo).  ONE launch in front of the tick loop
 // builds the table of every tick's window from the clip [K][L][C] (C = 3, car2d 2):
 //   windows[t][k][h] = clip[k][min(c0 + (t + D) E + h, L - 1)]        h = 0 .. kXrefRows - 1

@@ -23,6 +23,20 @@ void launch_score_wmean_batch(int V, int HNu, int P, size_t lds, hipStream_t s, 
 }
 }  // namespace
 
+// A sweep's session (include/mbd_hip.h mbd_sweep_mpc_open): P episodes the caller drives in lockstep, one tick per call.  All
+// zero: no session.
+struct SweepSession {
+  bool open = false, in_flight = false;
+  mbd_mpc_config mc{};
+  std::vector<uint32_t> rng;            // [P][2] the episodes' key chains: rng, k_t = split(rng) per tick
+  bool cold[MBD_SWEEP_MAX_PLANS] = {};  // episode k's next tick runs Ndiffuse-1 steps from Ybar = zeros
+  int flags[MBD_SWEEP_MAX_PLANS] = {};  // of the tick in flight: what the host decided (COLD, STATE_NONFINITE)
+  int t = 0, qbuf = 0;
+  PinnedBuf stage, mailbox;             // the states on their way up [P][S]; the results on their way down
+  Event done;
+  std::chrono::steady_clock::time_point t_submit{};
+};
+
 // ---- sweeps: P plans of one env in lockstep (mbd/scripts/run_mbd.py:17-64) ---------------------------------------
 struct mbd_sweep {
   mbd_env* env = nullptr;
@@ -86,10 +100,17 @@ struct mbd_sweep {
   NoiseSpec noise_always() const { return noise_spec(false); }
   NoiseSpec noise_warm() const { return noise_spec(true); }
   TimingPool timing;
+  // the session a caller drives tick by tick (mbd_sweep_mpc_open): it uses the batch's buffers above — slice 0 of d_mpc_states for
+  // the states handed in, slice 0 of d_mpc_pred, d_mpc_queue, d_mpc_ybar — so a handle runs batches or a session, not both
+  SweepSession session;
   ~mbd_sweep() {  // (streams, events and buffers release themselves, on the env's device)
     if (env) (void)hipSetDevice(env->device);
   }
 };
+
+// the refusal of a call that would disturb an open session (include/mbd_hip.h mbd_sweep_mpc_close)
+#define NO_SWEEP_SESSION(w, what) \
+  if ((w)->session.open) return fail(MBD_ERR_STATE, what ": a session is open on this sweep (mbd_sweep_mpc_close first)")
 
 extern "C" int mbd_sweep_create(mbd_env* env, const mbd_plan_config* cfg, int n_plans, const float* temps, mbd_sweep** out) {
   if (!env || !cfg || !out) return fail(MBD_ERR_INVALID, "NULL argument");
@@ -146,6 +167,10 @@ extern "C" int mbd_sweep_create(mbd_env* env, const mbd_plan_config* cfg, int n_
 }
 
 extern "C" int mbd_sweep_destroy(mbd_sweep* w) {
+  if (w && w->session.in_flight) {  // (an open session ends here: its last kernel still writes the mailbox)
+    (void)hipSetDevice(w->env->device);
+    (void)hipStreamSynchronize(w->stream);
+  }
   delete w;
   return MBD_OK;
 }
@@ -153,6 +178,7 @@ extern "C" int mbd_sweep_destroy(mbd_sweep* w) {
 extern "C" int mbd_sweep_set_state0(mbd_sweep* w, int k, const float* state0) {
   if (!w || !state0) return fail(MBD_ERR_INVALID, "NULL argument");
   if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "plan %d outside [0,%d)", k, w->P);
+  NO_SWEEP_SESSION(w, "set_state0");
   HIP_TRY(hipSetDevice(w->env->device));
   const size_t S = w->env->state_size();
   HIP_TRY(hipMemcpy(w->d_state0 + (size_t)k * S, state0, sizeof(float) * S, hipMemcpyHostToDevice));
@@ -369,6 +395,7 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
 extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_out, float* rew_means_out,
                              float* rew_final_out, double* loop_seconds_out) {
   if (!w || !keys) return fail(MBD_ERR_INVALID, "NULL argument");
+  NO_SWEEP_SESSION(w, "run");
   mbd_env* e = w->env;
   HIP_TRY(hipSetDevice(e->device));
   const mbd_plan_config& c = w->cfg;
@@ -405,6 +432,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
 // every run generates its first normals itself, so there is nothing to discard beyond waiting for the device.
 extern "C" int mbd_sweep_set_noise_shape(mbd_sweep* w, const mbd_noise_shape* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  NO_SWEEP_SESSION(w, "set_noise_shape");
   if (rec) MBD_TRY(check_noise_shape(rec, w->cfg.Hsample, w->Nu));
   HIP_TRY(hipSetDevice(w->env->device));
   HIP_TRY(hipDeviceSynchronize());
@@ -420,6 +448,7 @@ extern "C" int mbd_sweep_set_noise_shape(mbd_sweep* w, const mbd_noise_shape* re
 // one noise basis for all plans of the sweep (include/mbd_hip.h mbd_noise_basis), as mbd_sweep_set_noise_shape
 extern "C" int mbd_sweep_set_noise_basis(mbd_sweep* w, const mbd_noise_basis* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  NO_SWEEP_SESSION(w, "set_noise_basis");
   if (rec) MBD_TRY(check_noise_basis(rec, w->cfg.Hsample));
   HIP_TRY(hipSetDevice(w->env->device));
   HIP_TRY(hipDeviceSynchronize());
@@ -437,6 +466,7 @@ extern "C" int mbd_sweep_set_noise_basis(mbd_sweep* w, const mbd_noise_basis* re
 extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "episode k=%d outside [0,%d)", k, w->P);
+  NO_SWEEP_SESSION(w, "set_mpc_plant");
   if (!rec) {
     w->has_plant[k] = false;
     w->plant_rec[k] = mbd_mpc_plant{};
@@ -451,12 +481,14 @@ extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant*
 // one delay record for all episodes of the sweep (include/mbd_hip.h mbd_mpc_delay): host state until an episode starts
 extern "C" int mbd_sweep_set_mpc_delay(mbd_sweep* w, const mbd_mpc_delay* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  NO_SWEEP_SESSION(w, "set_mpc_delay");
   return w->delay.set(rec, w->Nu);
 }
 
 // one demo record for all episodes of the sweep (include/mbd_hip.h mbd_mpc_demo)
 extern "C" int mbd_sweep_set_mpc_demo(mbd_sweep* w, const mbd_mpc_demo* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  NO_SWEEP_SESSION(w, "set_mpc_demo");
   return w->demo.set(w->env, w->cfg, rec);
 }
 
@@ -506,6 +538,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   if (!mc) return fail(MBD_ERR_INVALID, "mpc config is NULL");
   if (!keys) return fail(MBD_ERR_INVALID, "keys is NULL");
+  NO_SWEEP_SESSION(w, "run_mpc");
   const mbd_plan_config& c = w->cfg;
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
   MBD_TRY(check_mpc_config(c, mc, w->demo.has));
@@ -677,5 +710,234 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     if (means_out) episode_major(means_out, T, HNu, HNu);
     if (actions_out) episode_major(actions_out, T, HNu, EN);
   }
+  return MBD_OK;
+}
+
+// ---- sessions of sweeps (include/mbd_hip.h mbd_sweep_mpc_open) ---------------------------------------------------------------
+// P sessions in lockstep: episode k is mbd_plan_mpc_open's session on a plan of the sweep's config with temps[k], bit for bit.  A
+// tick is a loop of its own over sweep_step — the lockstep step mbd_sweep_run and mbd_sweep_run_mpc run — with the ring of noise
+// buffers and the progress word starting afresh: the host has waited for the previous tick's event, the tick's last step leaves no
+// job on the second stream, so both streams are idle when a tick begins, the progress word is reset as between two runs, and the
+// tick's first normals are generated on the sweep's stream in front of its first rollout, as a run's are.  (A plan's session has
+// them prepared beside the previous tick's last rollout; here whether episode k's next tick is cold is not known then, and the
+// launch that would read them differs with it.  The bits depend on keys alone.)
+// Ticks of different lengths: after mbd_sweep_mpc_reset_mean(k) episode k's tick runs steps Ndiffuse-1 .. 1 and the others' K .. 1.
+// The lockstep loop then runs Ndiffuse-1 .. 1 for all: an episode that is not cold IDLES through the steps above K — its
+// candidates are rolled out from keys (0, 0) and its warm mean, its key chain does not advance, and what those steps wrote for it
+// is overwritten, in front of step K, by its shifted mean (one device-to-device copy per such episode), from which steps K .. 1
+// then run with its own keys: the same K launches' worth of arithmetic on the same inputs as in a tick of its own, and episodes
+// share no arithmetic (mbd_sweep_run's guarantee).  One launch samples under ONE noise shape and basis, so a tick in which some
+// episodes are cold and some are not is refused (MBD_ERR_UNSUPPORTED) when a record in force in the warm ticks only makes the two
+// differ.
+namespace {
+size_t sweep_mailbox_floats(const mbd_sweep* w, int EN) {
+  return (size_t)w->P * (2 * (size_t)EN + (size_t)w->HNu + (size_t)w->env->state_size() + 2);
+}
+SessionMailbox sweep_mailbox(const mbd_sweep* w, float* base, int EN) {
+  const size_t P = (size_t)w->P;
+  SessionMailbox mb;
+  mb.rows = base;
+  mb.mean = mb.rows + P * EN;
+  mb.head = mb.mean + P * w->HNu;
+  mb.pred = mb.head + P * EN;
+  mb.rew_mean = mb.pred + P * w->env->state_size();
+  mb.flag = (int*)(mb.rew_mean + P);
+  return mb;
+}
+// rng, Y0s_rng = split(rng) of the episodes that take part in a step; the others' chains stay and their keys are (0, 0)
+void session_split_keys(const mbd_sweep* w, std::vector<uint32_t>& r, const bool* active, SweepKeys& out) {
+  for (int k = 0; k < w->P; ++k) {
+    out.k[k][0] = 0; out.k[k][1] = 0;
+    if (!active[k]) continue;
+    uint32_t ks[4];
+    host_split(&r[2 * k], 2, w->cfg.prng_impl, ks);
+    r[2 * k] = ks[0]; r[2 * k + 1] = ks[1];
+    out.k[k][0] = ks[2]; out.k[k][1] = ks[3];
+  }
+}
+}  // namespace
+
+extern "C" int mbd_sweep_mpc_open(mbd_sweep* w, const mbd_mpc_config* mc, const uint32_t* keys) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (!mc) return fail(MBD_ERR_INVALID, "mpc config is NULL");
+  if (!keys) return fail(MBD_ERR_INVALID, "keys is NULL");
+  MBD_TRY(check_mpc_config(w->cfg, mc, w->demo.has));
+  MBD_TRY(w->delay.check_run(mc->exec_steps));
+  for (int k = 0; k < w->P; ++k)
+    if (w->has_plant[k])
+      return fail(MBD_ERR_STATE, "mpc_open: episode %d carries a plant record: in a session the caller is the plant", k);
+  NO_SWEEP_SESSION(w, "mpc_open");
+  mbd_env* e = w->env;
+  HIP_TRY(hipSetDevice(e->device));
+  SweepSession& ss = w->session;
+  const int P = w->P, S = e->state_size(), EN = mc->exec_steps * w->Nu, Q = w->delay.D * EN;
+  HIP_TRY(w->d_mpc_states.grow((size_t)P * S));
+  HIP_TRY(w->d_mpc_ybar.grow((size_t)P * w->HNu));
+  if (w->delay.has) {
+    HIP_TRY(w->d_mpc_queue.grow(2 * (size_t)P * Q));
+    HIP_TRY(w->d_mpc_pred.grow((size_t)P * S));
+  }
+  HIP_TRY(ss.stage.alloc((size_t)P * S));
+  HIP_TRY(ss.mailbox.alloc(sweep_mailbox_floats(w, EN)));
+  if (!ss.done) HIP_TRY(ss.done.create());
+  hipStream_t s = w->stream;
+  if (w->delay.has) MBD_TRY(w->delay.upload(w->d_mpc_queue, P, mc->exec_steps, w->Nu, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipStreamSynchronize(w->aux));
+  if (w->demo.has) MBD_TRY(w->demo.session_start());
+  // (nothing fails from here on: the bookkeeping of the previous batch's logs goes last)
+  if (w->delay.has) w->delay.pred_ticks = 0;  // (mbd_sweep_peek_mpc_predicted does not serve sessions)
+  ss.mc = *mc;
+  ss.rng.assign(keys, keys + 2 * (size_t)P);
+  for (int k = 0; k < MBD_SWEEP_MAX_PLANS; ++k) { ss.cold[k] = true; ss.flags[k] = 0; }
+  ss.t = 0; ss.qbuf = 0;
+  ss.in_flight = false;
+  ss.open = true;
+  return MBD_OK;
+}
+
+extern "C" int mbd_sweep_mpc_submit(mbd_sweep* w, const float* states) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (!states) return fail(MBD_ERR_INVALID, "states is NULL");
+  SweepSession& ss = w->session;
+  if (!ss.open) return fail(MBD_ERR_STATE, "mpc_submit: no session is open on this sweep");
+  if (ss.in_flight) return fail(MBD_ERR_STATE, "mpc_submit: a tick is in flight (mbd_sweep_mpc_collect first)");
+  if (ss.t >= ss.mc.n_ticks) return fail(MBD_ERR_STATE, "mpc_submit: the session has served its n_ticks=%d ticks", ss.mc.n_ticks);
+  mbd_env* e = w->env;
+  const mbd_plan_config& c = w->cfg;
+  const int P = w->P, S = e->state_size(), E = ss.mc.exec_steps, K = ss.mc.warm_steps, EN = E * w->Nu, HNu = w->HNu, Nd = c.Ndiffuse;
+  const bool has_delay = w->delay.has;
+  const int D = w->delay.D, Q = D * EN;
+  bool any_cold = false, all_cold = true;
+  for (int k = 0; k < P; ++k) { any_cold = any_cold || ss.cold[k]; all_cold = all_cold && ss.cold[k]; }
+  const NoiseSpec ns = all_cold ? w->noise_always() : w->noise_warm();
+  if (any_cold && !all_cold && !(w->noise_always() == w->noise_warm()))
+    return fail(MBD_ERR_UNSUPPORTED, "mpc_submit: some episodes' ticks are cold and some are not, under a noise shape or basis in force "
+                                     "in the warm ticks only: one launch samples under one; reset every episode's mean, or none's");
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t s = w->stream;
+  ss.t_submit = std::chrono::steady_clock::now();
+  int flags[MBD_SWEEP_MAX_PLANS];
+  for (int k = 0; k < P; ++k) {
+    flags[k] = ss.cold[k] ? MBD_TICK_COLD : 0;
+    for (int j = 0; j < S; ++j)
+      if (!std::isfinite(states[(size_t)k * S + j])) flags[k] |= MBD_TICK_STATE_NONFINITE;
+  }
+  memcpy(ss.stage.host(), states, sizeof(float) * (size_t)P * S);
+  float* states_t = w->d_mpc_states;
+  HIP_TRY(hipMemcpyAsync(states_t, ss.stage.host(), sizeof(float) * (size_t)P * S, hipMemcpyHostToDevice, s));
+  for (int k = 0; k < P; ++k)
+    if (ss.cold[k]) HIP_TRY(hipMemsetAsync(w->d_mpc_ybar + (size_t)k * HNu, 0, sizeof(float) * HNu, s));
+  // the keys: a copy of the chains is advanced and committed with the tick
+  std::vector<uint32_t> rng(ss.rng), r(2 * (size_t)P);
+  SweepKeys tick, sk, sk_next;
+  sweep_split_keys(w, rng, tick);
+  for (int k = 0; k < P; ++k) { r[2 * k] = tick.k[k][0]; r[2 * k + 1] = tick.k[k][1]; }
+  if (w->demo.has) MBD_TRY(w->demo.session_window(ss.t, E, has_delay ? D : 0, s));
+  const float* q_in = has_delay ? w->d_mpc_queue + (size_t)ss.qbuf * P * Q : nullptr;
+  float* q_out = has_delay ? w->d_mpc_queue + (size_t)(ss.qbuf ^ 1) * P * Q : nullptr;
+  const float* plan_from = states_t;
+  if (has_delay) {
+    const int exec_sw[3] = {1, S, 0};
+    MBD_TRY(launch_rollout(e, states_t, q_in, P, D * E, nullptr, nullptr, nullptr, w->d_mpc_pred, s, nullptr, exec_sw));
+    plan_from = w->d_mpc_pred;
+  }
+  progress_reset(w->h_progress);  // (both streams are idle: see above)
+  const int i_start = any_cold ? Nd - 1 : K;
+  const long long mu_stride = (long long)(Nd - 1) * HNu;
+  bool active[MBD_SWEEP_MAX_PLANS], active_next[MBD_SWEEP_MAX_PLANS];
+  for (int k = 0; k < P; ++k) active[k] = ss.cold[k] || i_start <= K;
+  session_split_keys(w, r, active, sk);
+  sweep_noise(w, sk, 0, s, ns);
+  HIP_TRY(hipGetLastError());
+  for (int i = i_start, q = 0; i >= 1; --i, ++q) {
+    if (i > 1) {
+      for (int k = 0; k < P; ++k) active_next[k] = ss.cold[k] || i - 1 <= K;
+      session_split_keys(w, r, active_next, sk_next);
+    }
+    SweepStep st;
+    st.q = q; st.i = i; st.slot = Nd - 1 - i;
+    st.state0 = plan_from;
+    if (i == K && i != i_start)  // the episodes that idled so far start here, from their shifted means
+      for (int k = 0; k < P; ++k)
+        if (!ss.cold[k])
+          HIP_TRY(hipMemcpyAsync(w->d_mu + (size_t)k * mu_stride + (size_t)(st.slot - 1) * HNu, w->d_mpc_ybar + (size_t)k * HNu,
+                                 sizeof(float) * HNu, hipMemcpyDeviceToDevice, s));
+    st.ybar_in = i == i_start ? w->d_mpc_ybar.get() : w->d_mu + (size_t)(st.slot - 1) * HNu;
+    st.ybar_in_stride = i == i_start ? HNu : mu_stride;
+    st.next_keys = i > 1 ? &sk_next : nullptr;
+    st.next_ns = ns;
+    st.xref = w->demo.has ? w->demo.window(0) : nullptr;
+    st.rew_xref = w->demo.has ? w->demo.rew_xref : e->rew_xref;
+    MBD_TRY(sweep_step(w, st));
+  }
+  hipLaunchKernelGGL(mpc_session_boundary_batch_kernel, dim3(1, (unsigned)P), dim3(256), 0, s,
+                     (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, HNu, EN, w->d_mpc_ybar.get(), q_in, q_out, Q,
+                     has_delay ? (const float*)w->d_mpc_pred : (const float*)nullptr, S, (const float*)(w->d_rewmeans + (Nd - 2)), Nd - 1,
+                     sweep_mailbox(w, ss.mailbox.dev(), EN));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ss.done, s));
+  ss.rng = rng;
+  for (int k = 0; k < P; ++k) ss.flags[k] = flags[k];
+  ss.in_flight = true;
+  return MBD_OK;
+}
+
+extern "C" int mbd_sweep_mpc_collect(mbd_sweep* w, float* rows_out, float* means_out, float* heads_out, float* predicted_out,
+                                     mbd_mpc_tick_info* infos_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  SweepSession& ss = w->session;
+  if (!ss.open) return fail(MBD_ERR_STATE, "mpc_collect: no session is open on this sweep");
+  if (!ss.in_flight) return fail(MBD_ERR_STATE, "mpc_collect: no tick is in flight (mbd_sweep_mpc_submit first)");
+  HIP_TRY(hipSetDevice(w->env->device));
+  HIP_TRY(hipEventSynchronize(ss.done));
+  const size_t P = (size_t)w->P, S = (size_t)w->env->state_size(), EN = (size_t)ss.mc.exec_steps * w->Nu;
+  const SessionMailbox mb = sweep_mailbox(w, ss.mailbox.host(), (int)EN);
+  if (rows_out) memcpy(rows_out, mb.rows, sizeof(float) * P * EN);
+  if (means_out) memcpy(means_out, mb.mean, sizeof(float) * P * w->HNu);
+  if (heads_out) memcpy(heads_out, mb.head, sizeof(float) * P * EN);
+  if (predicted_out) memcpy(predicted_out, w->delay.has ? mb.pred : ss.stage.host(), sizeof(float) * P * S);
+  const auto t1 = std::chrono::steady_clock::now();
+  for (size_t k = 0; k < P; ++k) {
+    if (infos_out) {
+      infos_out[k] = mbd_mpc_tick_info{};
+      infos_out[k].tick = ss.t;
+      infos_out[k].flags = ss.flags[k] | (mb.flag[k] ? MBD_TICK_ROWS_NONFINITE : 0);
+      infos_out[k].rew_mean = mb.rew_mean[k];
+      infos_out[k].seconds = std::chrono::duration<float>(t1 - ss.t_submit).count();
+    }
+    ss.cold[k] = false;
+  }
+  ss.in_flight = false;
+  ss.qbuf ^= 1;
+  ss.t += 1;
+  return MBD_OK;
+}
+
+extern "C" int mbd_sweep_mpc_tick(mbd_sweep* w, const float* states, float* rows_out, float* means_out, float* heads_out,
+                                  float* predicted_out, mbd_mpc_tick_info* infos_out) {
+  MBD_TRY(mbd_sweep_mpc_submit(w, states));
+  return mbd_sweep_mpc_collect(w, rows_out, means_out, heads_out, predicted_out, infos_out);
+}
+
+extern "C" int mbd_sweep_mpc_reset_mean(mbd_sweep* w, int k) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (!w->session.open) return fail(MBD_ERR_STATE, "mpc_reset_mean: no session is open on this sweep");
+  if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "mpc_reset_mean: episode k=%d outside [0,%d)", k, w->P);
+  if (w->session.in_flight) return fail(MBD_ERR_STATE, "mpc_reset_mean: a tick is in flight (mbd_sweep_mpc_collect first)");
+  w->session.cold[k] = true;  // (the next submit zeroes its Ybar; its queue stays)
+  return MBD_OK;
+}
+
+extern "C" int mbd_sweep_mpc_close(mbd_sweep* w) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  SweepSession& ss = w->session;
+  if (!ss.open) return fail(MBD_ERR_STATE, "mpc_close: no session is open on this sweep");
+  HIP_TRY(hipSetDevice(w->env->device));
+  if (ss.in_flight) HIP_TRY(hipStreamSynchronize(w->stream));  // (its last kernel writes the mailbox)
+  ss.in_flight = false;
+  ss.open = false;
+  ss.stage.release();
+  ss.mailbox.release();
   return MBD_OK;
 }

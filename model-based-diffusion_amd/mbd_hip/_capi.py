@@ -93,15 +93,27 @@ class MpcDemo(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+TICK_ROWS_NONFINITE, TICK_STATE_NONFINITE, TICK_COLD = 1, 2, 4
+
+
+class MpcTickInfo(C.Structure):
+    """mbd_mpc_tick_info (include/mbd_hip.h): what a session's tick reports beside its rows."""
+    _fields_ = [("tick", C.c_int32), ("flags", C.c_int32), ("rew_mean", C.c_float), ("seconds", C.c_float),
+                ("reserved", C.c_int32 * 4)]
+
+
 EXPORTS = [
     "mbd_last_error", "mbd_version", "mbd_tuned_spec", "mbd_device_count", "mbd_prng_key", "mbd_prng_split",
     "mbd_env_create", "mbd_env_name", "mbd_builtin_model", "mbd_env_get_model", "mbd_env_xref", "mbd_env_xref_logpd",
     "mbd_env_observe", "mbd_model_observe", "mbd_model_forward", "mbd_env_create_car2d", "mbd_env_create_model", "mbd_env_destroy", "mbd_env_info", "mbd_env_reset", "mbd_env_pipeline_init",
     "mbd_env_step", "mbd_env_rew_xref", "mbd_env_rollout", "mbd_plan_create", "mbd_plan_destroy",
     "mbd_plan_schedule", "mbd_plan_set_state0", "mbd_plan_sample_rollout", "mbd_plan_prefetch_noise", "mbd_plan_score_update",
-    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_set_mpc_delay", "mbd_plan_peek_mpc_predicted", "mbd_plan_set_mpc_demo", "mbd_plan_peek_mpc_track", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
+    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_set_mpc_delay", "mbd_plan_peek_mpc_predicted", "mbd_plan_set_mpc_demo", "mbd_plan_peek_mpc_track",
+    "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
+    "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
-    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_set_noise_shape", "mbd_sweep_set_noise_basis", "mbd_sweep_set_mpc_delay", "mbd_sweep_peek_mpc_predicted", "mbd_sweep_set_mpc_demo", "mbd_sweep_peek_mpc_track", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
+    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_set_noise_shape", "mbd_sweep_set_noise_basis", "mbd_sweep_set_mpc_delay", "mbd_sweep_peek_mpc_predicted", "mbd_sweep_set_mpc_demo", "mbd_sweep_peek_mpc_track", "mbd_sweep_mpc_open", "mbd_sweep_mpc_submit", "mbd_sweep_mpc_collect", "mbd_sweep_mpc_tick", "mbd_sweep_mpc_reset_mean",
+    "mbd_sweep_mpc_close", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
     "mbd_exchange_create", "mbd_exchange_destroy", "mbd_exchange_local_handle", "mbd_exchange_connect",
     "mbd_exchange_all_gather", "mbd_exchange_status", "mbd_exchange_fine_grained",
 ]
@@ -173,6 +185,12 @@ def load() -> C.CDLL:
     lib.mbd_plan_peek_mpc_predicted.argtypes = [_vp, _vp]
     lib.mbd_plan_set_mpc_demo.argtypes = [_vp, C.POINTER(MpcDemo)]
     lib.mbd_plan_peek_mpc_track.argtypes = [_vp, _vp, _vp]
+    lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
+    lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
+    lib.mbd_plan_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(MpcTickInfo)]
+    lib.mbd_plan_mpc_tick.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(MpcTickInfo)]
+    lib.mbd_plan_mpc_reset_mean.argtypes = [_vp]
+    lib.mbd_plan_mpc_close.argtypes = [_vp]
     lib.mbd_plan_eval.argtypes = [_vp, _vp, _fp]
     lib.mbd_plan_peek.argtypes = [_vp, _vp, _vp, _vp]
     lib.mbd_plan_kernel_time.argtypes = [_vp, _fp, C.POINTER(_i), _i]
@@ -189,6 +207,12 @@ def load() -> C.CDLL:
     lib.mbd_sweep_peek_mpc_predicted.argtypes = [_vp, _vp]
     lib.mbd_sweep_set_mpc_demo.argtypes = [_vp, C.POINTER(MpcDemo)]
     lib.mbd_sweep_peek_mpc_track.argtypes = [_vp, _i, _vp, _vp]
+    lib.mbd_sweep_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _vp]
+    lib.mbd_sweep_mpc_submit.argtypes = [_vp, _vp]
+    lib.mbd_sweep_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
+    lib.mbd_sweep_mpc_tick.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    lib.mbd_sweep_mpc_reset_mean.argtypes = [_vp, _i]
+    lib.mbd_sweep_mpc_close.argtypes = [_vp]
     lib.mbd_sweep_kernel_time.argtypes = [_vp, _i, _fp, C.POINTER(_i)]
     lib.mbd_sweep_get_sigmas.argtypes = [_vp, _vp]
     lib.mbd_exchange_create.argtypes = [_i, _i, _i, _i, _i, C.POINTER(_vp)]

@@ -135,6 +135,12 @@ class Sweep:
                                                               _capi.np_ptr(out["demo_windows"]) if e == 0 else None))
         return out
 
+    def mpc_open(self, keys, warm_steps: int, exec_steps: int = 1, max_ticks: int = None):
+        """Open P sessions in lockstep (include/mbd_hip.h mbd_sweep_mpc_open; ``MpcSession``): episode k is ``Plan.mpc_open``'s
+        session with ``keys[k]`` and plan k's temperature, bit for bit, whatever the other episodes are fed.  A tick takes the
+        episodes' states [P, state_size]; ``reset_mean(k)`` makes episode k's next tick a cold one."""
+        return MpcSession(self, keys, warm_steps, exec_steps, max_ticks)
+
     def set_mpc_demo(self, clip, start_row: int = 0, rew_xref: float = None):
         """One demo record for all episodes of the sweep (``Plan.set_mpc_demo``) — one clip and one clock: episode k of
         ``run_mpc`` is then ``Plan.run_mpc`` with the same record, bit for bit; ``run_mpc`` also returns ``track_err``
@@ -298,6 +304,115 @@ def _ensemble_record(envs, risk):
     return rec
 
 
+class MpcSession:
+    """An episode the caller drives (include/mbd_hip.h mbd_plan_mpc_open): opened once by ``Plan.mpc_open``, advanced one tick
+    per ``tick`` from the state of a system the library does not own — the caller is the plant.  A context manager; ``close``
+    (or leaving the block) gives the plan back to its other calls.  Fed the states of ``Plan.run_mpc`` it returns that
+    episode's means and rows bit for bit.  Opened by ``Sweep.mpc_open`` it is P such sessions in lockstep
+    (mbd_sweep_mpc_open): ``key`` is then ``keys`` [P, 2], a tick takes states [P, state_size] (or q [P, n_q], qd [P, n_qd]), every
+    array it returns has a leading episode axis, ``flags`` and ``rew_mean`` are arrays [P], and ``reset_mean`` takes the episode."""
+
+    def __init__(self, plan, key, warm_steps: int, exec_steps: int = 1, max_ticks: int = None):
+        for name, v in (("warm_steps", warm_steps), ("exec_steps", exec_steps)) + ((("max_ticks", max_ticks),) if max_ticks is not None else ()):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name}={v!r}: an int")
+        if not 1 <= warm_steps <= plan.Nd - 1:
+            raise ValueError(f"warm_steps={warm_steps} outside [1, Ndiffuse-1={plan.Nd - 1}]")
+        if not 1 <= exec_steps < plan.H:
+            raise ValueError(f"exec_steps={exec_steps} outside [1, Hsample={plan.H})")
+        if max_ticks is not None and not 1 <= max_ticks <= 2 ** 31 - 1:
+            raise ValueError(f"max_ticks={max_ticks} outside [1, 2^31-1]")
+        self.P = getattr(plan, "P", None)  # (a sweep's episodes; None: a plan)
+        k = np.ascontiguousarray(key, np.uint32)
+        if k.size != 2 * (self.P or 1):
+            raise ValueError(f"key of shape {k.shape}: " + ("two uint32 words" if self.P is None else f"[{self.P}, 2] uint32 words"))
+        self.plan, self.lib = plan, plan.lib
+        self.E, self.S = int(exec_steps), plan.env._state_size
+        self._call = "mbd_plan_mpc_" if self.P is None else "mbd_sweep_mpc_"
+        mc = _capi.MpcConfig()
+        mc.n_ticks = 2 ** 31 - 1 if max_ticks is None else int(max_ticks)
+        mc.warm_steps, mc.exec_steps = int(warm_steps), int(exec_steps)
+        self._open = False
+        _capi.check(self._fn("open")(plan.h, C.byref(mc), _capi.key_array(key) if self.P is None else _capi.np_ptr(k)))
+        self._open = True
+
+    def _fn(self, what):
+        return getattr(self.lib, self._call + what)
+
+    def _state(self, state, q, qd):
+        if (state is None) == (q is None):
+            raise ValueError("a tick takes a state, or generalized coordinates q (and qd): one of the two")
+        if state is not None and qd is not None:
+            raise ValueError("qd goes with q, not with a state")
+        n = self.P or 1
+        if state is None:
+            init = self.plan.env.pipeline_init
+            if self.P is None:
+                state = init(q, qd)
+            else:
+                state = np.stack([np.asarray(init(q[k], None if qd is None else qd[k]), np.float32).reshape(-1) for k in range(n)])
+        elif self.P is not None and not isinstance(state, np.ndarray):
+            state = np.stack([np.asarray(getattr(x, "pipeline_state", x), np.float32).reshape(-1) for x in state])
+        st = np.ascontiguousarray(getattr(state, "pipeline_state", state), np.float32).reshape(-1)
+        if st.size != n * self.S:
+            raise ValueError(f"a state of {st.size} floats: the env's state_size is {self.S}" + ("" if self.P is None else f", times {n} episodes"))
+        return st
+
+    def submit(self, state=None, q=None, qd=None) -> None:
+        """Enqueue the next tick from ``state`` (a State, or its pipeline state as an array [state_size]) or from generalized
+        coordinates ``q`` (and ``qd``; through ``env.pipeline_init``) and return; ``collect`` waits for it."""
+        st = self._state(state, q, qd)
+        _capi.check(self._fn("submit")(self.plan.h, _capi.np_ptr(st)))
+
+    def collect(self) -> dict:
+        """The tick in flight: dict(rows [E, Nu] — the plan's first rows, unclipped —, mean [H, Nu], head [E, Nu] — with a delay
+        record the rows to execute NOW, rows being due in ``delay_ticks`` ticks; otherwise rows again —, predicted [state_size]
+        — the state the tick planned from under a delay record, else None —, flags, rew_mean, seconds, tick)."""
+        p = self.plan
+        lead = () if self.P is None else (self.P,)
+        rows, head = (np.zeros(lead + (self.E, p.Nu), np.float32) for _ in range(2))
+        mean, pred = np.zeros(lead + (p.H, p.Nu), np.float32), np.zeros(lead + (self.S,), np.float32)
+        info = (_capi.MpcTickInfo * (self.P or 1))()
+        _capi.check(self._fn("collect")(p.h, _capi.np_ptr(rows), _capi.np_ptr(mean), _capi.np_ptr(head), _capi.np_ptr(pred), info))
+        flags, rew = np.array([i.flags for i in info], np.int32), np.array([i.rew_mean for i in info], np.float32)
+        return dict(rows=rows, mean=mean, head=head, predicted=pred if p._has_delay else None,
+                    flags=int(flags[0]) if self.P is None else flags, rew_mean=float(rew[0]) if self.P is None else rew,
+                    seconds=info[0].seconds, tick=info[0].tick)
+
+    def tick(self, state=None, q=None, qd=None) -> dict:
+        """``submit`` then ``collect``."""
+        self.submit(state, q, qd)
+        return self.collect()
+
+    def reset_mean(self, k: int = None) -> None:
+        """The next tick is a cold one (Ybar = 0, Ndiffuse-1 steps, flagged TICK_COLD): what a controller does after rows it
+        could not use.  The delay queue stays.  A sweep's session: episode ``k``'s (None: every episode's)."""
+        if self.P is None:
+            _capi.check(self._fn("reset_mean")(self.plan.h))
+            return
+        for e in range(self.P) if k is None else (int(k),):
+            _capi.check(self._fn("reset_mean")(self.plan.h, e))
+
+    def close(self) -> None:
+        if self._open and self.plan.h is not None:
+            self._open = False
+            _capi.check(self._fn("close")(self.plan.h))
+        self._open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Plan:
     """Thin owner of an ``mbd_plan`` handle."""
 
@@ -378,6 +493,13 @@ class Plan:
             out["demo_windows"] = np.zeros((T, Kt, _capi.XREF_ROWS, Cc), np.float32)
             _capi.check(self.lib.mbd_plan_peek_mpc_track(self.h, _capi.np_ptr(out["track_err"]), _capi.np_ptr(out["demo_windows"])))
         return out
+
+    def mpc_open(self, key, warm_steps: int, exec_steps: int = 1, max_ticks: int = None) -> MpcSession:
+        """Open a session (include/mbd_hip.h mbd_plan_mpc_open): ``run_mpc``'s episode advanced one tick per call from a state
+        the caller supplies — ``with plan.mpc_open(key, K) as s: rows = s.tick(state)["rows"]``.  The plan's noise, ensemble,
+        delay and demo records are read now; a plant record is refused (the caller is the plant).  ``max_ticks`` None: no limit.
+        Until the session is closed the plan's other calls are refused."""
+        return MpcSession(self, key, warm_steps, exec_steps, max_ticks)
 
     def set_mpc_demo(self, clip, start_row: int = 0, rew_xref: float = None):
         """Follow a demonstration on the episode's clock (include/mbd_hip.h mbd_mpc_demo; demo plans only): tick t of

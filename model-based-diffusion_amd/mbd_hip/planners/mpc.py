@@ -65,6 +65,17 @@ episode carries ``track_err`` and ``demo_windows``.  ``--enable_demo`` without a
 the env's 50 rows.  A batch of episodes shares one clip and one clock.
 
     python -m mbd_hip.planners.mpc --env_name humanoidtrack --enable_demo --demo_clip env --demo_period 20 --n_ticks 200
+
+All of the above runs the whole episode in one call, on a plant the library owns.  ``--online`` (include/mbd_hip.h
+mbd_plan_mpc_open; DESIGN.md section 1 "N11 session") runs it the way a user with a system of their own would: a session, one
+``tick`` per control tick, with this script as the plant — ``env.rollout`` of the rows to execute, on the ``--plant_mass`` /
+``--plant_friction`` / ``--plant_gear`` env if one is given — handing the state reached back to the next tick.  It saves the
+episode (results/<env>/mpc_episode.npz) with the fields of the batch run and equal contents; its JSON line is its own — the ms per
+tick the session itself took (the plant excluded), tick 0 and the warm ticks' min / median / max.
+``--act_noise_std`` and ``--kick_std`` are refused with it: those are drawn by the plant record, and a session has none.  With a
+demo clip the distances from the clip are not logged (a session executes nothing on the device).  Single episodes only.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --n_ticks 100 --warm_steps 20 --online --plant_mass 1.3
 """
 from __future__ import annotations
 
@@ -106,6 +117,7 @@ class MpcArgs(Args):
     demo_clip: str = ""  # "": no demo record; "env": the env's own demo; FILE.npy: a clip [n_track, L, 3] (car2d [L, 2])
     demo_start: int = 0  # c0: the clip row the episode's first executed control step is compared with
     demo_period: int = 0  # p > 0: the clip is first extended periodically (cycle_clip) to the rows the episode reaches
+    online: bool = False  # run the episode through a session (Plan.mpc_open), one tick per call, this script being the plant
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -334,14 +346,15 @@ def _reset_and_key(env, seed: int):
     return state_init, rng_exp
 
 
-def _setup(args: MpcArgs, device: int):
+def _setup(args: MpcArgs, device: int, online: bool = False):
+    """``online``: no plant record is set — the caller executes the rows (``run_mpc_online``)."""
     apply_recommended(args)
     env = get_env(args.env_name, device=device)
     state_init, rng_exp = _reset_and_key(env, args.seed)
     plan = Plan(env, args)
     plan.set_state0(state_init)
     cache = {}
-    if _has_plant(args):
+    if _has_plant(args) and not online:
         plan.set_mpc_plant(**_record_kwargs(env, args, device, cache))
     if _has_ensemble(args):
         plan.set_ensemble(_ensemble_envs(env, args, device, cache), args.ens_risk)
@@ -354,6 +367,58 @@ def _setup(args: MpcArgs, device: int):
     if _has_demo(args):
         plan.set_mpc_demo(*_demo_of(env, args))
     return env, plan, state_init, rng_exp
+
+
+def _check_online(args: MpcArgs) -> None:
+    """What ``--online`` refuses, decided from the arguments alone."""
+    for f in ("act_noise_std", "kick_std"):
+        if getattr(args, f) != MpcArgs.__dataclass_fields__[f].default:
+            raise ValueError(f"{f}={getattr(args, f)!r} with online: the action noise and the kicks are drawn by the plant record, "
+                             "and a session has none — the caller is the plant; disturb the plant you drive instead")
+
+
+def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
+    """One episode through a session: tick, execute the rows on ``plant`` (None: ``env``) with ``env.rollout``, hand the state
+    reached to the next tick.  Returns ``Plan.run_mpc``'s dict (``seconds``: the sum of the ticks' own) and ``tick_seconds`` [T]."""
+    from ..envs.base import State
+    pe = env if plant is None else plant
+    T, E = args.n_ticks, args.exec_steps
+    s = np.ascontiguousarray(state_init.pipeline_state, np.float32).reshape(-1)
+    actions, rewards, states, means, predicted, secs = [], [], [s], [], [], []
+    with plan.mpc_open(key, args.warm_steps, E, T) as session:
+        for _ in range(T):
+            out = session.tick(s)
+            rows = out["head"]  # (the rows to execute now: the plan's own first rows, or under a delay record the queue's head)
+            rewss, fin = pe.rollout(State(s, None, np.float32(0), np.float32(0), {}), rows[None], want_final=True)
+            s = fin[0].cpu().numpy().reshape(-1)
+            actions.append(rows)
+            rewards.append(rewss[0].cpu().numpy())
+            states.append(s)
+            means.append(out["mean"])
+            predicted.append(out["predicted"])
+            secs.append(out["seconds"])
+    ep = dict(actions=np.concatenate(actions), rewards=np.concatenate(rewards), states=np.stack(states), means=np.stack(means),
+              seconds=float(np.sum(secs)), tick_seconds=np.asarray(secs, np.float64))
+    if plan._has_delay:
+        ep["predicted"] = np.stack(predicted)
+    return ep
+
+
+def run_mpc_online(args: MpcArgs, device: int = None, return_details: bool = False):
+    """``run_mpc``'s episode through a session, the Python side being the plant (``--online``)."""
+    _check_online(args)
+    device = 0 if device is None else device
+    env, plan, state_init, key = _setup(args, device, online=True)
+    try:
+        ep = _online_episode(env, _plant_env(env, args, device), plan, state_init, key, args)
+    finally:
+        plan.close()
+    reward = float(ep["rewards"].mean())
+    if not args.not_render:
+        _save(args, ep)
+    if return_details:
+        return reward, dict(ep, state_init=state_init, key=key, dt=env.dt)
+    return reward
 
 
 def _check_batch(arg_list) -> None:
@@ -498,6 +563,10 @@ def _main(argv=None) -> dict:
     ns = vars(p.parse_args(argv))
     n_episodes = ns.pop("n_episodes")
     args = MpcArgs(**ns)
+    if args.online:
+        if n_episodes != 1:
+            raise ValueError(f"n_episodes={n_episodes} with online: a session drives one episode")
+        return _main_online(args)
     if n_episodes != 1:
         return _main_batch(args, n_episodes)
     with contextlib.redirect_stdout(sys.stderr):  # (stdout carries the JSON line only)
@@ -531,6 +600,35 @@ def _main(argv=None) -> dict:
     res.update(_delay_settings(args))  # (without a record the line is what it always was)
     if _has_demo(args):
         res.update(_demo_settings(args), track_err_mean=float(ep["track_err"].mean()))
+    if not args.not_render:
+        _save(args, ep)
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def _main_online(args: MpcArgs) -> dict:
+    """``--online``: the episode through a session after a warm-up one, in one process; the times are the session's own."""
+    import contextlib
+    import json
+    import sys
+
+    _check_online(args)
+    with contextlib.redirect_stdout(sys.stderr):  # (stdout carries the JSON line only)
+        env, plan, state_init, key = _setup(args, 0, online=True)
+        plant = _plant_env(env, args, 0)
+        _online_episode(env, plant, plan, state_init, key, args)  # warm-up
+        ep = _online_episode(env, plant, plan, state_init, key, args)
+        plan.close()
+    T, E = args.n_ticks, args.exec_steps
+    ms = 1e3 * ep["tick_seconds"]
+    warm = ms[1:] if T > 1 else ms  # (tick 0 is the cold plan: Ndiffuse-1 steps)
+    res = dict(env=args.env_name, Nsample=args.Nsample, Hsample=args.Hsample, Ndiffuse=args.Ndiffuse, n_ticks=T,
+               warm_steps=args.warm_steps, exec_steps=E, online=True, ms_per_tick=float(ms.mean()), tick0_ms=float(ms[0]),
+               warm_tick_ms_min=float(warm.min()), warm_tick_ms_median=float(np.median(warm)), warm_tick_ms_max=float(warm.max()),
+               real_time_factor=T * E * env.dt / ep["seconds"], episode_reward=float(ep["rewards"].mean()))
+    if _has_plant(args):
+        res.update(_plant_settings(args))
+    res.update(_delay_settings(args))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
