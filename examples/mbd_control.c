@@ -2,7 +2,7 @@
  * session (mbd_plan_mpc_open) is opened once and advanced one tick per call from the state the caller's system is in.
  *
  *   gcc -O2 -I include examples/mbd_control.c -o mbd_control -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
- *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks]
+ *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--mppi]
  *                 env    N   H  Nd K ticks
  *
  * The "system" here is a second env the example owns, stepped with mbd_env_step — the env's rollout kernel at B = 1, H = 1 through
@@ -11,6 +11,8 @@
  * (q, qd) into a state).
  * With delay_ticks D > 0 the rows to execute NOW are head (what the system was already committed to); the rows the tick planned are
  * due D ticks later, and the tick planned from the state it predicted for then.
+ * --mppi (last argument): the same loop with MPPI (path_integral.py) in the planner's place — a path-integral plan and the sigma
+ * record that lets a session accept it: sigma 1.0 in the cold tick, 0.25 in every later one.
  *
  * Prints one line per tick: "tick T reward R ms M flags F", then "mean_reward R ms_per_tick M". */
 #include <math.h>
@@ -37,6 +39,8 @@ static int plant_step(mbd_env* plant, float* state, const float* action, float* 
 }
 
 int main(int argc, char** argv) {
+  const int mppi = argc > 1 && strcmp(argv[argc - 1], "--mppi") == 0;
+  if (mppi) argc -= 1;
   const char* env_name = argc > 1 ? argv[1] : "hopper";
   const int N = argc > 2 ? atoi(argv[2]) : 256, H = argc > 3 ? atoi(argv[3]) : 20, Nd = argc > 4 ? atoi(argv[4]) : 10;
   const int K = argc > 5 ? atoi(argv[5]) : 3, T = argc > 6 ? atoi(argv[6]) : 20, D = argc > 7 ? atoi(argv[7]) : 0;
@@ -52,7 +56,14 @@ int main(int argc, char** argv) {
   cfg.beta0 = 1e-4f; cfg.betaT = 1e-2f; cfg.prng_impl = impl; cfg.shard_begin = 0; cfg.shard_count = N;
   cfg.literal_score = 1;
   mbd_plan* plan = NULL;
+  if (mppi) cfg.update_method = 1; /* 1 mppi, 2 cma-es, 3 cem: Ndiffuse plays Nrefine */
   CHECK(mbd_plan_create(env, &cfg, &plan));
+  if (mppi) { /* without the record a path-integral plan is refused by mbd_plan_mpc_open */
+    mbd_mpc_sigma sigma;
+    memset(&sigma, 0, sizeof(sigma));
+    sigma.sigma_cold = 1.0f; sigma.sigma_warm = 0.25f; sigma.gain = 0.0f;
+    CHECK(mbd_plan_set_mpc_sigma(plan, &sigma));
+  }
   if (D > 0) { /* plans arrive D ticks late; the system starts committed to zeros */
     mbd_mpc_delay delay;
     memset(&delay, 0, sizeof(delay));

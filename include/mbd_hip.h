@@ -351,7 +351,9 @@ int mbd_plan_score_update(mbd_plan* plan, int i, const uint32_t key_sample[2], c
                           const float* d_rews_all, const float* d_logpd_all, float* d_Ybar_im1,
                           float* d_rew_mean, void* stream);
 /* path-integral plans: the carried sampling sigma (path_integral.py:113,131). set before the first
- * step (mbd_plan_run does it itself); synchronous. */
+ * step (mbd_plan_run does it itself); synchronous.  After an episode with a sigma record (mbd_mpc_sigma, below), and between
+ * the ticks of a session, mbd_plan_get_sigma returns the sigma the NEXT tick starts from (after mbd_plan_mpc_reset_mean:
+ * sigma_cold). */
 int mbd_plan_set_sigma(mbd_plan* plan, float sigma);
 int mbd_plan_get_sigma(mbd_plan* plan, float* sigma_out);
 /* single-GPU convenience = reverse_once (mbd_planner.py:97-135): phase 1 + phase 2 on `stream`;
@@ -392,12 +394,60 @@ typedef struct mbd_mpc_config {
  * HOST outputs, each may be NULL: actions_out [T*E][Nu] (the rows executed), rewards_out [T*E], states_out
  * [T+1][state_size] (s_0 .. s_T), means_out [T][H][Nu] (M_t); loop_seconds_out: wall time of the tick loop.
  * Synchronous; ONE device->host copy per output at the end.  The plan's state0 is unchanged afterwards.
- * MBD plans only (update_method 0, unsharded; demo plans need a demo record, mbd_plan_set_mpc_demo below): NULL plan / config /
- * key and out-of-range fields -> MBD_ERR_INVALID (the NULL checks before any device access), enable_demo without a demo record
- * or a path-integral update -> MBD_ERR_UNSUPPORTED (demos are time-indexed: the record is the clock that follows the episode),
- * a sharded plan -> MBD_ERR_STATE. */
+ * Unsharded plans; demo plans need a demo record (mbd_plan_set_mpc_demo below) and path-integral plans a sigma record
+ * (mbd_plan_set_mpc_sigma below, which also says what their episode is): NULL plan / config / key and out-of-range fields ->
+ * MBD_ERR_INVALID (the NULL checks before any device access), enable_demo without a demo record or a path-integral update
+ * (update_method != 0) without a sigma record -> MBD_ERR_UNSUPPORTED (demos are time-indexed: the record is the clock that
+ * follows the episode; a path-integral plan carries a sigma an episode has to be told how to restart), a sharded plan ->
+ * MBD_ERR_STATE. */
 int mbd_plan_run_mpc(mbd_plan* plan, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
                      float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out);
+
+/* ---- path-integral episodes: mppi, cma-es and cem as receding-horizon controllers (path_integral.py:111-127 is the open-loop
+ * refinement loop; the reference has no episode; DESIGN.md section 1 "N12 path-integral episodes") ---- */
+/* A sigma record turns a path-integral plan (update_method 1 / 2 / 3) into one that episodes accept, and says what sigma a tick
+ * starts from.  A setting of a plan (of a sweep) beside the plant, delay and noise records, read by mbd_plan_run_mpc,
+ * mbd_plan_mpc_open and mbd_sweep_run_mpc only: mbd_plan_run, mbd_sweep_run and the phase calls ignore it, and mbd_plan_run's
+ * own reset of sigma to 1 is untouched.  The record is the switch: without one a path-integral handle stays refused. */
+typedef struct mbd_mpc_sigma {
+  float sigma_cold;    /* > 0, finite: sigma at the first step of a cold tick (tick 0; a session's tick after
+                          mbd_plan_mpc_reset_mean).  1.0 is path_integral.py:131 */
+  float sigma_warm;    /* > 0, finite: sigma at the first step of every other tick */
+  float gain;          /* >= 0, finite.  0: a warm tick starts at sigma_warm.  > 0 (cma-es only, needs sigma_warm <= sigma_cold):
+                          it starts at clamp(gain * sigma_end of the previous tick, sigma_warm, sigma_cold) */
+  int32_t reserved[5]; /* must be 0 */
+} mbd_mpc_sigma;
+/* With a record the episode of mbd_plan_run_mpc (above) is — everything not shown is unchanged:
+ *   rng = key; mu = zeros; n_it = Ndiffuse-1; sigma = sigma_cold
+ *   per tick t:  rng, k_t = split(rng);  r = k_t;  sigmas[t][0] = sigma
+ *                n_it times:  r, ks = split(r)
+ *                             Y0s  = clip(normal(ks, (N,H,Nu)) * sigma + mu)     (path_integral.py:116-119; under a noise shape
+ *                                                                                 or basis what mbd_plan_run forms for this plan)
+ *                             rews = mean_H(rollout(s_t, Y0s))                   (from the predicted state under a delay record)
+ *                             mu, sigma = update_fn(softmax(standardise(rews)/temp), Y0s, sigma, mu)   (:122-125, no zero-std guard)
+ *                M_t = mu;  sigmas[t][1] = sigma
+ *                execute M_t[0:E] as above / as the plant and delay records say;  mu = shift_E(M_t);  n_it = K
+ *                sigma = sigma_warm                        if gain == 0
+ *                      = x, three separately rounded f32 steps, no fma:
+ *                          x = fl32(gain * sigma);  x = x < sigma_warm ? sigma_warm : x;  x = x > sigma_cold ? sigma_cold : x
+ *                        (so that a NaN sigma stays NaN)
+ * For mppi and cem sigma never changes within a tick, so gain > 0 is refused there rather than silently meaningless; cma-es'
+ * sigma collapses as it converges, and gain lets a warm tick's regrowth follow how converged the last tick was.
+ * Bit for bit: with sigma_cold = 1, tick 0's mean and sigma are mbd_plan_run(k_0)'s; an episode of T ticks is a prefix of one of
+ * T + 1; the record {1, 1, 0} makes every tick the reference's update() from the shifted mean, with K refinements.
+ * On the device the carried sigma never leaves it: one launch of one small kernel per tick boundary (and one in front of tick 0)
+ * logs it and forms the next — no host write of sigma inside the tick loop, no synchronisation.
+ * The plant record, the delay record (the prediction is unchanged: one candidate on the plan's env) and the noise shape and basis,
+ * in both `when` modes, compose as for MBD episodes; the first normals of a tick are sampled in the tick.  An ensemble record
+ * stays refused for path-integral plans, and a path-integral handle with demos cannot be created.
+ * The set call copies the record; rec == NULL clears it and brings the run call's refusal back.  Refused before any device access,
+ * the message naming the field: a NULL handle -> MBD_ERR_INVALID; update_method == 0 -> MBD_ERR_STATE ("not a path-integral
+ * plan"); a session open on the handle -> MBD_ERR_STATE; a non-finite or non-positive sigma_cold / sigma_warm, a negative or
+ * non-finite gain, gain > 0 with update_method != 2, gain > 0 with sigma_warm > sigma_cold, non-zero reserved -> MBD_ERR_INVALID. */
+int mbd_plan_set_mpc_sigma(mbd_plan* plan, const mbd_mpc_sigma* rec);
+/* the sigmas of the last episode run with a record (synchronises the device): HOST sigmas_out [T][2] — what tick t started from
+ * and ended with; may be NULL.  MBD_ERR_STATE without a record, or before an episode has run with one (sessions keep no log). */
+int mbd_plan_peek_mpc_sigma(mbd_plan* plan, float* sigmas_out);
 
 /* ---- the plant of an episode: a system that is NOT the planner's model (DESIGN.md section 1 "N5 plant") ---- */
 /* A plant record names the env that executes a closed-loop episode's rows, and the episode's disturbances.  It is a setting
@@ -664,8 +714,11 @@ typedef struct mbd_mpc_tick_info {
   float   seconds;      /* host wall time submit -> rows on the host */
   int32_t reserved[4];  /* written 0 */
 } mbd_mpc_tick_info;
-/* open: everything mbd_plan_run_mpc refuses, with the same codes and messages (NULL plan / config / key -> MBD_ERR_INVALID
- * before any device access; the config's ranges; enable_demo without a demo record, a path-integral update ->
+/* A path-integral plan with a sigma record (mbd_mpc_sigma, above) opens a session like any other: tick(x) is then the record's
+ * tick — n_it refinements from sigma, M_t = mu, the boundary formula for the next sigma — and mbd_plan_mpc_reset_mean makes the
+ * next tick cold, sigma = sigma_cold included.  Between two ticks mbd_plan_get_sigma returns the sigma the next tick starts from.
+ * open: everything mbd_plan_run_mpc refuses, with the same codes and messages (NULL plan / config / key -> MBD_ERR_INVALID
+ * before any device access; the config's ranges; enable_demo without a demo record, a path-integral update without a sigma record ->
  * MBD_ERR_UNSUPPORTED; a sharded plan -> MBD_ERR_STATE; the delay record's n_rows against exec_steps -> MBD_ERR_INVALID); a
  * plant record set -> MBD_ERR_STATE (in a session the caller is the plant); a session already open -> MBD_ERR_STATE. */
 int mbd_plan_mpc_open(mbd_plan* plan, const mbd_mpc_config* mc, const uint32_t key[2]);
@@ -688,7 +741,7 @@ int mbd_plan_mpc_reset_mean(mbd_plan* plan);
 /* close: waits for a tick in flight and drops it.  NULL plan -> MBD_ERR_INVALID; no session open -> MBD_ERR_STATE.
  * mbd_plan_destroy closes an open session.  While a session is open, these calls on the same handle return MBD_ERR_STATE, the
  * message naming the session: mbd_plan_run, _run_mpc, _eval, _set_state0, _reverse_once, _sample_rollout, _score_update and
- * every mbd_plan_set_* record call (plant, ensemble, noise shape, noise basis, delay, demo). */
+ * every mbd_plan_set_* record call (plant, ensemble, noise shape, noise basis, delay, demo, sigma). */
 int mbd_plan_mpc_close(mbd_plan* plan);
 
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
@@ -741,9 +794,9 @@ int mbd_sweep_run(mbd_sweep* sweep, const uint32_t* keys, float* mu_0ts_out, flo
  * The "bit for bit" above holds whatever the other episodes do: an episode that diverges — from its start state, or on its
  * plant — carries non-finite states and rewards from there on and leaves the other episodes' bits alone, in the planning
  * launches and in the launch that executes every episode's rows side by side.
- * MBD sweeps only (update_method 0; demo sweeps need a demo record): NULL sweep / config / keys and out-of-range fields ->
- * MBD_ERR_INVALID (the NULL checks before any device access), enable_demo without a demo record or a path-integral update ->
- * MBD_ERR_UNSUPPORTED. */
+ * Demo sweeps need a demo record, path-integral sweeps a sigma record (mbd_sweep_set_mpc_sigma below): NULL sweep / config /
+ * keys and out-of-range fields -> MBD_ERR_INVALID (the NULL checks before any device access), enable_demo without a demo record
+ * or a path-integral update without a sigma record -> MBD_ERR_UNSUPPORTED. */
 int mbd_sweep_run_mpc(mbd_sweep* sweep, const mbd_mpc_config* mc, const uint32_t* keys, float* actions_out,
                       float* rewards_out, float* states_out, float* means_out, double* loop_seconds_out);
 /* The plant record of episode k (mbd_mpc_plant, above; rec == NULL clears).  With records: episode k of mbd_sweep_run_mpc is
@@ -775,6 +828,19 @@ int mbd_sweep_set_mpc_demo(mbd_sweep* sweep, const mbd_mpc_demo* rec);
 /* episode k's err_out [T*E][K] and the batch's windows_out [T][K][50][3] of the last batch run with a record; as
  * mbd_plan_peek_mpc_track; k outside [0, n_plans) -> MBD_ERR_INVALID */
 int mbd_sweep_peek_mpc_track(mbd_sweep* sweep, int k, float* err_out, float* windows_out);
+/* one sigma record (mbd_mpc_sigma, above) for all episodes of a path-integral sweep: episode k of mbd_sweep_run_mpc is then
+ * mbd_plan_run_mpc on a path-integral plan of its own with the same record, keys[k] and temps[k], bit for bit.  A refinement of
+ * a tick is mbd_sweep_run's lockstep step — one sampling launch, one rollout launch over the n_plans * Nsample candidates, the
+ * update rule's kernels with blockIdx.y = episode — from the tick's slice of the state log (of the predicted states under a
+ * delay record); the carried sigmas [n_plans] are logged and re-formed by ONE launch per tick boundary.  Plant records per
+ * episode and the sweep's delay record compose through the boundary the MBD batches run.  Refusals as
+ * mbd_plan_set_mpc_sigma's.  SESSIONS of path-integral sweeps stay refused by mbd_sweep_mpc_open (MBD_ERR_UNSUPPORTED,
+ * update_method), record or not: a lockstep tick in which some episodes are cold and some are not would have to idle a carried
+ * sigma. */
+int mbd_sweep_set_mpc_sigma(mbd_sweep* sweep, const mbd_mpc_sigma* rec);
+/* episode k's sigmas_out [T][2] of the last batch run with a record; as mbd_plan_peek_mpc_sigma; k outside [0, n_plans) ->
+ * MBD_ERR_INVALID */
+int mbd_sweep_peek_mpc_sigma(mbd_sweep* sweep, int k, float* sigmas_out);
 /* ---- sessions of sweeps: P sessions in lockstep (mbd_plan_mpc_open, above; DESIGN.md section 1 "N11 session") ---- */
 /* Episode k of a sweep's session is EXACTLY mbd_plan_mpc_open's session on a plan of the sweep's config with key = keys[k] and
  * temp_sample = the sweep's temps[k], fed states[k] — bit for bit, whatever the other episodes do or are fed (a non-finite state

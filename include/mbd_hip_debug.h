@@ -52,6 +52,13 @@ int mbd_debug_knot_noise_host(const uint32_t key[2], int impl, int N, int H, int
  * both set calls run on their record, host arithmetic, no device — so that a test without a GPU, which has no handle whose
  * action_size is not 0, reaches the refusal of a non-finite row value too. */
 int mbd_debug_check_mpc_delay(const mbd_mpc_delay* rec, int action_size);
+/* The sigma a warm tick of a path-integral episode starts from (include/mbd_hip.h mbd_mpc_sigma), on the HOST: the function
+ * mpc_pi_sigma_kernel calls (one text for host and device) over n values of sigma_end, no device touched.  HOST sigma_end [n],
+ * next_out [n]. */
+int mbd_debug_mpc_sigma_next(const float* sigma_end, int n, float sigma_cold, float sigma_warm, float gain, float* next_out);
+/* The refusals a sigma record alone decides for a handle of that update_method: the function both set calls run on their record,
+ * host arithmetic, no device. */
+int mbd_debug_check_mpc_sigma(const mbd_mpc_sigma* rec, int update_method);
 #ifdef __cplusplus
 }
 #endif

@@ -332,8 +332,34 @@ void host_schedule(float beta0, float betaT, int Nd, std::vector<float>& alphas,
 // the refusals of a plant record (include/mbd_hip.h mbd_mpc_plant) against the env that plans — host arithmetic, no launch
 int check_mpc_plant(const mbd_env* env, const mbd_mpc_plant* rec);
 // the refusals of an episode's configuration that plans and sweeps share (include/mbd_hip.h mbd_mpc_config), in their order
-// (has_demo_rec: the handle carries a demo record — a demo plan without one has no clock for its demo and stays refused)
-int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc, bool has_demo_rec);
+// (has_demo_rec: the handle carries a demo record — a demo plan without one has no clock for its demo and stays refused;
+// has_sigma_rec: it carries a sigma record — a path-integral handle without one stays refused; pi_sessions: the call opens a
+// sweep's session, which path-integral sweeps do not have, record or not)
+int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc, bool has_demo_rec, bool has_sigma_rec,
+                     bool pi_sessions = false);
+// The sigma record of a path-integral plan or sweep (include/mbd_hip.h mbd_mpc_sigma) as the handle keeps it, with what the two
+// handles do alike: the refusals the record alone decides against the handle's update_method, in the header's order, each naming
+// the field (check_mpc_sigma: host arithmetic, before any device access), and the set call behind its NULL-handle, update_method
+// and session checks (nullptr clears).  d_log: the sigmas of the last episode, episode-major [P][T + 1][2] — what tick t started
+// from and ended with; the boundary behind the last tick writes slot T's first float —, ticks / episodes: its T and P, 0: none
+// yet (mbd_*_peek_mpc_sigma).
+struct SigmaRec {
+  bool has = false;
+  float cold = 1.0f, warm = 1.0f, gain = 0.0f;
+  int ticks = 0, episodes = 0;
+  int log_ticks = 0;  // the T the log was laid out for (start)
+  DevBuf<float> d_log;
+  int set(const mbd_mpc_sigma* rec, int update_method);
+  // in front of an episode of T ticks and P episodes: room for the log (a session: T = 1)
+  int start(int T, int P);
+  long long stride() const { return 2ll * (log_ticks + 1); }
+  // the launch in front of a cold tick (cold: the carried sigmas [P] and slot t's first float take sigma_cold) or at the
+  // boundary behind tick t (slot t's second float takes the carried sigma, which becomes the next tick's; slot t + 1's first)
+  void launch(float* d_sigma, int P, int t, bool cold_tick, hipStream_t s) const;
+  // HOST sigmas_out [T][2] of episode k of the last run
+  int peek(int device, int k, float* sigmas_out, const char* what) const;
+};
+int check_mpc_sigma(const mbd_mpc_sigma* rec, int update_method);
 // the refusals of a noise-shape record (include/mbd_hip.h mbd_noise_shape) against a handle's Hsample x action_size, in the
 // header's order, each naming the field — host arithmetic on the record's own table, before any device access
 int check_noise_shape(const mbd_noise_shape* rec, int Hsample, int action_size);

@@ -164,6 +164,8 @@ struct mbd_plan {
   // the demo record (mbd_plan_set_mpc_demo) with its buffers: the clip, the table of every tick's window, the log of the
   // executed steps' tracked positions and their distances from the clip
   DemoRec demo;
+  // the sigma record of a path-integral plan (mbd_plan_set_mpc_sigma) with the log of the last episode's sigmas
+  SigmaRec sigma_rec;
   // the ensemble record (mbd_plan_set_ensemble; a copy, NULL members resolved to the plan's env — the envs are the caller's)
   // and its buffers: the members' rewards r_m [M][N] and per-step rewards [M][N][H] of the rollout launch over M N
   // candidates, and the library's own copy of the combined rewards [N] (mbd_plan_peek_ensemble)
@@ -952,7 +954,7 @@ bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[
   return kick_now;
 }
 
-int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc, bool has_demo_rec) {
+int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc, bool has_demo_rec, bool has_sigma_rec, bool pi_sessions) {
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
   if (T < 1) return fail(MBD_ERR_INVALID, "n_ticks=%d: must be >= 1", T);
   if (K < 1 || K > Nd - 1) return fail(MBD_ERR_INVALID, "warm_steps=%d outside [1, Ndiffuse-1=%d]", K, Nd - 1);
@@ -961,8 +963,88 @@ int check_mpc_config(const mbd_plan_config& c, const mbd_mpc_config* mc, bool ha
     if (mc->reserved[r] != 0) return fail(MBD_ERR_INVALID, "reserved[%d]=%d: must be 0", r, mc->reserved[r]);
   if (c.enable_demo && !has_demo_rec)
     return fail(MBD_ERR_UNSUPPORTED, "enable_demo: demos are time-indexed, an episode has no clock for them: set a demo record");
-  if (c.update_method != 0) return fail(MBD_ERR_UNSUPPORTED, "update_method=%d: receding horizon runs MBD plans only", c.update_method);
+  if (c.update_method != 0 && pi_sessions)
+    return fail(MBD_ERR_UNSUPPORTED, "update_method=%d: sessions of sweeps run MBD plans only (a path-integral sweep runs whole "
+                                     "episodes: mbd_sweep_run_mpc with a sigma record)", c.update_method);
+  if (c.update_method != 0 && !has_sigma_rec)
+    return fail(MBD_ERR_UNSUPPORTED, "update_method=%d: receding horizon runs a path-integral plan only with a sigma record "
+                                     "(mbd_plan_set_mpc_sigma / mbd_sweep_set_mpc_sigma)", c.update_method);
   return MBD_OK;
+}
+
+// ---- the sigma record (include/mbd_hip.h mbd_mpc_sigma) ------------------------------------------------------------------
+int check_mpc_sigma(const mbd_mpc_sigma* rec, int update_method) {
+  if (!std::isfinite(rec->sigma_cold) || !(rec->sigma_cold > 0.0f))
+    return fail(MBD_ERR_INVALID, "sigma record: sigma_cold=%g: must be finite and > 0", (double)rec->sigma_cold);
+  if (!std::isfinite(rec->sigma_warm) || !(rec->sigma_warm > 0.0f))
+    return fail(MBD_ERR_INVALID, "sigma record: sigma_warm=%g: must be finite and > 0", (double)rec->sigma_warm);
+  if (!std::isfinite(rec->gain) || rec->gain < 0.0f)
+    return fail(MBD_ERR_INVALID, "sigma record: gain=%g: must be finite and >= 0", (double)rec->gain);
+  if (rec->gain > 0.0f && update_method != 2)
+    return fail(MBD_ERR_INVALID, "sigma record: gain=%g with update_method=%d: only cma-es (2) changes sigma within a tick", (double)rec->gain,
+                update_method);
+  if (rec->gain > 0.0f && rec->sigma_warm > rec->sigma_cold)
+    return fail(MBD_ERR_INVALID, "sigma record: gain=%g with sigma_warm=%g > sigma_cold=%g: the clamp needs sigma_warm <= sigma_cold",
+                (double)rec->gain, (double)rec->sigma_warm, (double)rec->sigma_cold);
+  for (int r = 0; r < 5; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "sigma record: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  return MBD_OK;
+}
+extern "C" int mbd_debug_check_mpc_sigma(const mbd_mpc_sigma* rec, int update_method) {
+  if (!rec) return fail(MBD_ERR_INVALID, "sigma record is NULL");
+  return check_mpc_sigma(rec, update_method);
+}
+// include/mbd_hip_debug.h: the boundary function on the host (mpc_pi_next_sigma is host and device text) — no device is touched
+extern "C" int mbd_debug_mpc_sigma_next(const float* sigma_end, int n, float sigma_cold, float sigma_warm, float gain, float* next_out) {
+  if (!sigma_end || !next_out) return fail(MBD_ERR_INVALID, "NULL argument");
+  if (n < 0) return fail(MBD_ERR_INVALID, "n=%d", n);
+  for (int j = 0; j < n; ++j) next_out[j] = mpc_pi_next_sigma(sigma_end[j], sigma_cold, sigma_warm, gain);
+  return MBD_OK;
+}
+
+int SigmaRec::set(const mbd_mpc_sigma* rec, int update_method) {
+  if (!rec) {
+    has = false;
+    ticks = episodes = 0;
+    return MBD_OK;
+  }
+  MBD_TRY(check_mpc_sigma(rec, update_method));
+  cold = rec->sigma_cold; warm = rec->sigma_warm; gain = rec->gain;
+  ticks = episodes = 0;
+  has = true;
+  return MBD_OK;
+}
+int SigmaRec::start(int T, int P) {
+  ticks = episodes = 0;
+  HIP_TRY(d_log.grow((size_t)P * 2 * ((size_t)T + 1)));
+  log_ticks = T;
+  return MBD_OK;
+}
+void SigmaRec::launch(float* d_sigma, int P, int t, bool cold_tick, hipStream_t s) const {
+  hipLaunchKernelGGL(mpc_pi_sigma_kernel, dim3((P + 63) / 64), dim3(64), 0, s, d_sigma, P, d_log.get() + 2 * (size_t)t, stride(),
+                     cold_tick ? 1 : 0, cold, warm, gain);
+}
+int SigmaRec::peek(int device, int k, float* sigmas_out, const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_mpc_sigma: the %s has no sigma record", what);
+  if (ticks < 1) return fail(MBD_ERR_STATE, "peek_mpc_sigma: no episode has run with the record yet");
+  if (k < 0 || k >= episodes) return fail(MBD_ERR_INVALID, "peek_mpc_sigma: episode k=%d outside [0,%d)", k, episodes);
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (sigmas_out)
+    HIP_TRY(hipMemcpy(sigmas_out, d_log.get() + (size_t)k * stride(), sizeof(float) * 2 * (size_t)ticks, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_mpc_sigma(mbd_plan* p, const mbd_mpc_sigma* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (p->cfg.update_method == 0) return fail(MBD_ERR_STATE, "set_mpc_sigma: not a path-integral plan (update_method == 0)");
+  NO_SESSION(p, "set_mpc_sigma");
+  return p->sigma_rec.set(rec, p->cfg.update_method);
+}
+
+extern "C" int mbd_plan_peek_mpc_sigma(mbd_plan* p, float* sigmas_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->sigma_rec.peek(p->env->device, 0, sigmas_out, "plan");
 }
 
 extern "C" int mbd_plan_set_mpc_plant(mbd_plan* p, const mbd_mpc_plant* rec) {
@@ -1365,6 +1447,15 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
 // pointer into it where they read the env's demo (launch_rollout's and launch_logpd's d_xref) and the record's rew_xref where they
 // read the env's; the rollout of the executed rows is handed its slice of the position log as d_xpos; mpc_track_err_kernel, ONE
 // launch behind the loop, reads that log.  The ring's argument does not see any of it.
+// A path-integral plan with a sigma record (mbd_plan_set_mpc_sigma) runs the same loop: mpc_plan_tick as it is — reverse_once_impl
+// serves both families, a materialised plan ignores the declared keys, and the slots of d_mu and d_rewmeans are the same — so a
+// tick's first normals are sampled in the tick.  Around it: ONE launch of mpc_pi_sigma_kernel in front of tick 0 (sigma = sigma_cold,
+// the log's first entry) and one behind every tick's last update kernel, in front of the execution of its rows, which logs the
+// sigma the tick ended with and leaves the next tick's in the carried slot.  Stream order is the whole argument: the kernel reads
+// what cma_sigma_kernel wrote and writes what the next tick's sampler reads, all on the plan's stream; no host value, no
+// synchronisation.  Launches per tick of K refinements: mppi 3 K (sampler, rollout, score + weighted mean), cma-es 5 K (plus
+// spread and sigma), cem 5 K (sampler, rollout, score, selection, mean), under a noise basis one more per refinement; plus the
+// sigma kernel and the boundary's two (three with a plant record, one more with a delay record).
 // The planning of a tick — the prediction, the diffusion steps, the key chain — is mpc_plan_tick above, which a session
 // (mbd_plan_mpc_submit) runs as well: what is said here about those launches holds for both, and the session restates the rest.
 extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uint32_t key[2], float* actions_out,
@@ -1375,11 +1466,12 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   NO_SESSION(p, "run_mpc");
   const mbd_plan_config& c = p->cfg;
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, H = c.Hsample;
-  MBD_TRY(check_mpc_config(c, mc, p->demo.has));
+  MBD_TRY(check_mpc_config(c, mc, p->demo.has, p->sigma_rec.has));
   if (c.shard_count != c.Nsample)
     return fail(MBD_ERR_STATE, "shard_count=%d of Nsample=%d: receding horizon runs unsharded plans", c.shard_count, c.Nsample);
   MBD_TRY(p->delay.check_run(E));
   mbd_env* e = p->env;
+  const bool pi = c.update_method != 0;  // a path-integral plan (with a sigma record: check_mpc_config)
   HIP_TRY(hipSetDevice(e->device));
   const int HNu = p->HNu, Nu = e->action_size(), S = e->state_size();
   HIP_TRY(p->d_mpc_state.grow(2 * (size_t)S));
@@ -1415,6 +1507,11 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     MBD_TRY(p->delay.upload(p->d_mpc_queue, 1, E, Nu, s));
     p->delay.pred_ticks = 0;
   }
+  if (pi) {  // sigma = sigma_cold and the log's first entry, by the kernel that carries sigma across the boundaries
+    MBD_TRY(p->sigma_rec.start(T, 1));
+    p->sigma_rec.launch(p->d_sigma, 1, 0, true, s);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipStreamSynchronize(s));
   const auto t0 = std::chrono::steady_clock::now();
   if (has_demo) MBD_TRY(p->demo.start(T, 1, E, has_delay ? D : 0, s));
@@ -1431,6 +1528,10 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     tk.d_xref = has_demo ? p->demo.window(t) : nullptr;
     const float* cur = nullptr;
     MBD_TRY(mpc_plan_tick(p, tk, r, s, &cur));
+    if (pi) {  // the sigma the tick ended with into the log, the next tick's into the carried slot: one launch, no host value
+      p->sigma_rec.launch(p->d_sigma, 1, t, false, s);
+      HIP_TRY(hipGetLastError());
+    }
     // execute M_t's first E rows from s_t — with a delay record the queue's head —, then the boundary: Ybar of tick t+1, the
     // logs of M_t and s_{t+1}
     float* s_next = p->d_mpc_state + (size_t)(t & 1) * S;
@@ -1473,6 +1574,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   if (rewards_out) HIP_TRY(hipMemcpy(rewards_out, p->d_mpc_rewards, sizeof(float) * (size_t)T * E, hipMemcpyDeviceToHost));
   if (states_out) HIP_TRY(hipMemcpy(states_out, p->d_mpc_states, sizeof(float) * ((size_t)T + 1) * S, hipMemcpyDeviceToHost));
   if (has_delay) p->delay.pred_ticks = T;
+  if (pi) { p->sigma_rec.ticks = T; p->sigma_rec.episodes = 1; }
   if (has_plant || has_delay) {  // (the executed rows carry the action noise, or are the committed queue's: their own log)
     if (actions_out) HIP_TRY(hipMemcpy(actions_out, p->d_mpc_actions, sizeof(float) * (size_t)T * EN, hipMemcpyDeviceToHost));
     if (means_out) HIP_TRY(hipMemcpy(means_out, p->d_mpc_means, sizeof(float) * (size_t)T * HNu, hipMemcpyDeviceToHost));
@@ -1506,6 +1608,14 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
 // step's, the next writer of the buffer first joins the job through ring.join (obtain_normals, prepare_noise_job), and
 // mbd_plan_destroy frees the buffers with hipFree, which waits for the device.  run and run_mpc after a session give a fresh
 // handle's bits (tests/test_gpu_mpc_online.py).
+// The materialised case (car2d; a path-integral plan with a sigma record): there is no ring.  sample_candidates writes d_Y0s on
+// the plan's stream in front of the rollout that reads it, the update kernels read it behind that rollout, and the next step's
+// sampler overwrites it behind them: stream order alone.  No key is declared (declare_next_key returns at once), the second
+// stream is never created, the progress word is never written.  A path-integral tick adds mpc_pi_sigma_kernel in FRONT of
+// mpc_session_boundary_kernel — behind the tick's last cma_sigma_kernel, whose value it reads — so the boundary stays the tick's
+// last kernel and the event behind it covers the mailbox as before; the sigma kernel touches device memory only (the carried
+// sigma, a two-slot log nobody reads back).  A cold tick's launch of the same kernel (sigma = sigma_cold) stands in front of the
+// tick's first sampler; mbd_plan_mpc_reset_mean launches it too, between two ticks, so that mbd_plan_get_sigma already says so.
 static size_t session_mailbox_floats(const mbd_plan* p, int EN) {
   return 2 * (size_t)EN + (size_t)p->HNu + (size_t)p->env->state_size() + 2;
 }
@@ -1525,7 +1635,7 @@ extern "C" int mbd_plan_mpc_open(mbd_plan* p, const mbd_mpc_config* mc, const ui
   if (!mc) return fail(MBD_ERR_INVALID, "mpc config is NULL");
   if (!key) return fail(MBD_ERR_INVALID, "key is NULL");
   const mbd_plan_config& c = p->cfg;
-  MBD_TRY(check_mpc_config(c, mc, p->demo.has));
+  MBD_TRY(check_mpc_config(c, mc, p->demo.has, p->sigma_rec.has));
   if (c.shard_count != c.Nsample)
     return fail(MBD_ERR_STATE, "shard_count=%d of Nsample=%d: receding horizon runs unsharded plans", c.shard_count, c.Nsample);
   MBD_TRY(p->delay.check_run(mc->exec_steps));
@@ -1545,6 +1655,11 @@ extern "C" int mbd_plan_mpc_open(mbd_plan* p, const mbd_mpc_config* mc, const ui
   if (!ss.done) HIP_TRY(ss.done.create());
   hipStream_t s = p->stream;
   if (p->delay.has) MBD_TRY(p->delay.upload(p->d_mpc_queue, 1, mc->exec_steps, p->Nu, s));
+  if (c.update_method != 0) {  // (a session keeps no sigma log: one slot and its successor; mbd_plan_get_sigma: sigma_cold from here on)
+    MBD_TRY(p->sigma_rec.start(1, 1));
+    p->sigma_rec.launch(p->d_sigma, 1, 0, true, s);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipStreamSynchronize(s));
   if (p->demo.has) MBD_TRY(p->demo.session_start());
   // (nothing fails from here on: a refused or failed open leaves the last episode's logs readable)
@@ -1580,6 +1695,11 @@ extern "C" int mbd_plan_mpc_submit(mbd_plan* p, const float* state) {
   float* s_t = p->d_mpc_state;
   HIP_TRY(hipMemcpyAsync(s_t, ss.stage.host(), sizeof(float) * S, hipMemcpyHostToDevice, s));
   if (ss.cold) HIP_TRY(hipMemsetAsync(p->d_Ybar, 0, sizeof(float) * HNu, s));
+  const bool pi = c.update_method != 0;
+  if (pi && ss.cold) {  // a cold tick starts from sigma_cold
+    p->sigma_rec.launch(p->d_sigma, 1, 0, true, s);
+    HIP_TRY(hipGetLastError());
+  }
   uint32_t rng[2] = {ss.rng[0], ss.rng[1]}, r[2], after[2];  // (a copy of the chain: committed with the tick, below)
   mpc_tick_keys(c.prng_impl, rng, r, after);
   if (p->demo.has) MBD_TRY(p->demo.session_window(ss.t, E, has_delay ? D : 0, s));
@@ -1591,6 +1711,10 @@ extern "C" int mbd_plan_mpc_submit(mbd_plan* p, const float* state) {
   tk.d_xref = p->demo.has ? p->demo.window(0) : nullptr;
   const float* M = nullptr;
   MBD_TRY(mpc_plan_tick(p, tk, r, s, &M));
+  if (pi) {  // the next tick's sigma, in FRONT of the boundary: that stays the tick's last kernel, the one the event stands behind
+    p->sigma_rec.launch(p->d_sigma, 1, 0, false, s);
+    HIP_TRY(hipGetLastError());
+  }
   hipLaunchKernelGGL(mpc_session_boundary_kernel, dim3(1), dim3(256), 0, s, M, HNu, EN, p->d_Ybar.get(), q_in, q_out, Q,
                      has_delay ? (const float*)p->d_mpc_pred : (const float*)nullptr, S, (const float*)(p->d_rewmeans + (Nd - 2)),
                      session_mailbox(p, ss.mailbox.dev(), EN));
@@ -1642,6 +1766,11 @@ extern "C" int mbd_plan_mpc_reset_mean(mbd_plan* p) {
   if (!p->session.open) return fail(MBD_ERR_STATE, "mpc_reset_mean: no session is open on this plan");
   if (p->session.in_flight) return fail(MBD_ERR_STATE, "mpc_reset_mean: a tick is in flight (mbd_plan_mpc_collect first)");
   p->session.cold = true;  // (the next submit zeroes Ybar; the queue stays)
+  if (p->cfg.update_method != 0) {  // (and starts from sigma_cold: written now as well, so that mbd_plan_get_sigma says so)
+    HIP_TRY(hipSetDevice(p->env->device));
+    p->sigma_rec.launch(p->d_sigma, 1, 0, true, p->stream);
+    HIP_TRY(hipGetLastError());
+  }
   return MBD_OK;
 }
 

@@ -414,6 +414,41 @@ static __global__ __launch_bounds__(256) void mpc_session_boundary_batch_kernel(
                             q_in ? q_out + k * Q : nullptr, Q, pred ? pred + k * S : nullptr, S, rew_mean + k * rew_stride, m);
 }
 
+// The carried sigma of a path-integral episode at a tick boundary (include/mbd_hip.h mbd_mpc_sigma).  The sigma the next tick
+// starts from, from the one the last tick ended with: sigma_warm, or with a gain clamp(gain * sigma_end, sigma_warm, sigma_cold)
+// — a product and two selects, three separately rounded f32 steps (the build's -ffp-contract=off), written so that a NaN sigma
+// stays NaN (both compares are false).  Host and device: mbd_debug_mpc_sigma_next runs this same text on the CPU.
+MBD_HD float mpc_pi_next_sigma(float sigma_end, float sigma_cold, float sigma_warm, float gain) {
+  if (gain == 0.0f) return sigma_warm;
+  float x = gain * sigma_end;
+  x = x < sigma_warm ? sigma_warm : x;
+  x = x > sigma_cold ? sigma_cold : x;
+  return x;
+}
+// One launch per tick boundary, one thread per episode k < P (P = 1: a plan), behind the tick's last cma_sigma_kernel and in
+// front of the next tick's sampler on the same stream.  sigma [P]: the carried sigmas (what cma_sigma_kernel left; mppi and cem
+// leave them alone).  log: episode 0's slot t of the sigma log, episode k's log_stride floats further; a slot is (start, end).
+// cold != 0: the launch in front of a cold tick — sigma and the slot's start take sigma_cold.  Otherwise: the slot's end takes
+// the carried sigma, and the next sigma goes into the carried slot and into the following slot's start (the log has T + 1
+// slots).  Plain loads and stores; the arguments are uniform.
+static __global__ __launch_bounds__(64) void mpc_pi_sigma_kernel(float* __restrict__ sigma, int P, float* __restrict__ log,
+                                                           long long log_stride, int cold, float sigma_cold, float sigma_warm,
+                                                           float gain) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= P) return;
+  float* __restrict__ slot = log + (long long)k * log_stride;
+  if (cold) {
+    sigma[k] = sigma_cold;
+    slot[0] = sigma_cold;
+    return;
+  }
+  const float end = sigma[k];
+  slot[1] = end;
+  const float next = mpc_pi_next_sigma(end, sigma_cold, sigma_warm, gain);
+  sigma[k] = next;
+  slot[2] = next;
+}
+
 // The demo clock of an episode with a demo record (include/mbd_hip.h mbd_mpc_demo).  ONE launch in front of the tick loop
 // builds the table of every tick's window from the clip [K][L][C] (C = 3, car2d 2):
 //   windows[t][k][h] = clip[k][min(c0 + (t + D) E + h, L - 1)]        h = 0 .. kXrefRows - 1

@@ -77,6 +77,8 @@ struct mbd_sweep {
   // the demo record of all episodes (mbd_sweep_set_mpc_demo): one clip and one clock, so ONE table of windows — a rollout
   // launch reads one demo table for all its candidates —; the position log and the distances are tick-major [T][P][E][K]...
   DemoRec demo;
+  // the sigma record of all episodes of a path-integral sweep (mbd_sweep_set_mpc_sigma) with the log of the last batch's sigmas
+  SigmaRec sigma_rec;
   // the noise shape of all the sweep's plans (mbd_sweep_set_noise_shape): a plan's, with the same two accessors
   DevBuf<float> d_shape;
   bool has_shape = false;
@@ -216,25 +218,85 @@ static int sweep_results(mbd_sweep* w, float* mu_0ts_out, float* rew_means_out, 
 // ONE sampling launch (every plan's key, carried sigma and mean), ONE rollout launch over the P * N materialised
 // candidates, and the update rule's kernels with blockIdx.y = plan — mppi: the fused score + weighted mean; cma-es: plus
 // spread and sigma; cem: score, selection, mean of the K best.  Same kernels, same order, same bits as mbd_plan_run.
-static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_out, float* rew_means_out,
-                                   float* rew_final_out, double* loop_seconds_out) {
+// sweep_pi_step is that lockstep step, shared by mbd_sweep_run and the path-integral episodes of mbd_sweep_run_mpc.
+namespace {
+struct PiStep {
+  int slot;              // slot of every plan's d_mu / d_rewmeans the step writes
+  const float* state0;   // [P][S] start states of the rollouts
+  const float* mu_in;    // the mean of plan 0 the step samples around; plan k's is mu_stride floats further
+  long long mu_stride;
+  NoiseSpec ns;          // the noise shape and basis the step samples under
+};
+int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
   mbd_env* e = w->env;
   const mbd_plan_config& c = w->cfg;
   const int P = w->P, N = c.Nsample, H = c.Hsample, Nd = c.Ndiffuse, HNu = w->HNu, S = e->state_size();
   hipStream_t s = w->stream;
-  std::vector<uint32_t> rng(keys, keys + 2 * (size_t)P);
   const uint64_t per_plan = (uint64_t)N * HNu;
   const unsigned nblocks = noise_blocks(c.prng_impl, per_plan, 4096);
+  const dim3 b64(64);
+  PiBatch pb;
+  pb.rews = N; pb.weights = N; pb.mean = Nd - 1; pb.cand = (long long)per_plan; pb.spread = HNu; pb.sigma = 1; pb.idx = 16;
+  pb.out = (long long)(Nd - 1) * HNu; pb.temps = w->d_temps;
+  const int step = st.slot;
+  const float* mu_in = st.mu_in;
+  const long long mu_stride = st.mu_stride;
+  float* mu_out = w->d_mu + (size_t)step * HNu;
+  const NoiseSpec& ns = st.ns;
+  if (ns.W) {  // under a noise basis: the knot kernel into the scratch z, then sample_batch_kernel's two roundings
+    hipLaunchKernelGGL(knot_noise_batch_kernel, dim3(knot_blocks(N, w->Nu, 1024), (unsigned)P), dim3(kKnotThreads), 0, s, sk,
+                       c.prng_impl, N, H, w->Nu, ns.knots, ns.W, ns.g, w->d_knot_z.get());
+    hipLaunchKernelGGL(shift_batch_kernel, dim3(noise_blocks(MBD_PRNG_PARTITIONABLE, per_plan, 4096), (unsigned)P), dim3(256), 0, s,
+                       (const float*)w->d_knot_z, N, HNu, (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s.get());
+  } else {
+    hipLaunchKernelGGL(sample_batch_kernel, dim3(nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
+                       (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s, ns.g);
+  }
+  HIP_TRY(hipGetLastError());
+  MBD_TRY(w->timing.begin(s));
+  const int sw[3] = {N, S, 0};
+  MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, nullptr, s, nullptr, sw));
+  MBD_TRY(w->timing.end(s));
+  pb.mu = mu_stride;
+  if (c.update_method == 3) {  // cem_update (path_integral.py:48-52)
+    const int K = N < 10 ? N : 10;
+    hipLaunchKernelGGL(score_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), sizeof(float) * (size_t)N, s, (const float*)w->d_rews,
+                       (const float*)nullptr, N, e->rew_xref, c.temp_sample, 0, w->d_weights, w->d_rewmeans + step,
+                       (float*)nullptr, pb);
+    hipLaunchKernelGGL(cem_select_kernel, dim3(1, (unsigned)P), b64, sizeof(float) * (size_t)N, s, (const float*)w->d_weights, N, K,
+                       w->d_idx, (float*)nullptr, pb);
+    hipLaunchKernelGGL(cem_mean_kernel, dim3((HNu + 63) / 64, (unsigned)P), b64, 0, s, (const int*)w->d_idx, K,
+                       (const float*)w->d_Y0s, HNu, mu_out, pb);
+  } else {  // mppi (:33-36), cma-es (:39-45): softmax weights and the weighted mean in one launch
+    ScoreBatch sb;
+    sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)per_plan;
+    sb.ybar_in = mu_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
+    launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
+                             c.temp_sample, 0, w->d_weights.get(), w->d_rewmeans + step, (const float*)w->d_Y0s, HNu, mu_in, 1.0f, 1.0f,
+                             1.0f, 0, mu_out, 0, 0.0f, (float*)nullptr, sb);
+    if (c.update_method == 2) {
+      hipLaunchKernelGGL(cma_spread_kernel, dim3((HNu + 63) / 64, (unsigned)P), b64, 0, s, (const float*)w->d_weights,
+                         (const float*)w->d_Y0s, N, HNu, mu_in, w->d_spread, pb);
+      hipLaunchKernelGGL(cma_sigma_kernel, dim3(1, (unsigned)P), b64, 0, s, (const float*)w->d_spread, HNu, w->d_sigma, pb);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+}  // namespace
+
+static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_out, float* rew_means_out,
+                                   float* rew_final_out, double* loop_seconds_out) {
+  const mbd_plan_config& c = w->cfg;
+  const int P = w->P, Nd = c.Ndiffuse, HNu = w->HNu;
+  hipStream_t s = w->stream;
+  std::vector<uint32_t> rng(keys, keys + 2 * (size_t)P);
   {
     std::vector<float> ones((size_t)P, 1.0f);  // sigma = 1.0 (path_integral.py:131)
     HIP_TRY(hipMemcpy(w->d_sigma, ones.data(), sizeof(float) * P, hipMemcpyHostToDevice));
   }
   HIP_TRY(hipStreamSynchronize(s));
   auto t0 = std::chrono::steady_clock::now();
-  const dim3 b64(64);
-  PiBatch pb;
-  pb.rews = N; pb.weights = N; pb.mean = Nd - 1; pb.cand = (long long)per_plan; pb.spread = HNu; pb.sigma = 1; pb.idx = 16;
-  pb.out = (long long)(Nd - 1) * HNu; pb.temps = w->d_temps;
   for (int i = Nd - 1, step = 0; i >= 1; --i, ++step) {
     SweepKeys sk;
     for (int k = 0; k < P; ++k) {  // rng, Y0s_rng = split(rng) (path_integral.py:114)
@@ -243,48 +305,12 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
       rng[2 * k] = ks[0]; rng[2 * k + 1] = ks[1];
       sk.k[k][0] = ks[2]; sk.k[k][1] = ks[3];
     }
-    const float* mu_in = step == 0 ? w->d_zero : w->d_mu + (size_t)(step - 1) * HNu;
-    const long long mu_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
-    float* mu_out = w->d_mu + (size_t)step * HNu;
-    const NoiseSpec ns = w->noise_always();
-    if (ns.W) {  // under a noise basis: the knot kernel into the scratch z, then sample_batch_kernel's two roundings
-      hipLaunchKernelGGL(knot_noise_batch_kernel, dim3(knot_blocks(N, w->Nu, 1024), (unsigned)P), dim3(kKnotThreads), 0, s, sk,
-                         c.prng_impl, N, H, w->Nu, ns.knots, ns.W, ns.g, w->d_knot_z.get());
-      hipLaunchKernelGGL(shift_batch_kernel, dim3(noise_blocks(MBD_PRNG_PARTITIONABLE, per_plan, 4096), (unsigned)P), dim3(256), 0, s,
-                         (const float*)w->d_knot_z, N, HNu, (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s.get());
-    } else {
-      hipLaunchKernelGGL(sample_batch_kernel, dim3(nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
-                         (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s, ns.g);
-    }
-    HIP_TRY(hipGetLastError());
-    MBD_TRY(w->timing.begin(s));
-    const int sw[3] = {N, S, 0};
-    MBD_TRY(launch_rollout(e, w->d_state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, nullptr, s, nullptr, sw));
-    MBD_TRY(w->timing.end(s));
-    pb.mu = mu_stride;
-    if (c.update_method == 3) {  // cem_update (path_integral.py:48-52)
-      const int K = N < 10 ? N : 10;
-      hipLaunchKernelGGL(score_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), sizeof(float) * (size_t)N, s, (const float*)w->d_rews,
-                         (const float*)nullptr, N, e->rew_xref, c.temp_sample, 0, w->d_weights, w->d_rewmeans + step,
-                         (float*)nullptr, pb);
-      hipLaunchKernelGGL(cem_select_kernel, dim3(1, (unsigned)P), b64, sizeof(float) * (size_t)N, s, (const float*)w->d_weights, N, K,
-                         w->d_idx, (float*)nullptr, pb);
-      hipLaunchKernelGGL(cem_mean_kernel, dim3((HNu + 63) / 64, (unsigned)P), b64, 0, s, (const int*)w->d_idx, K,
-                         (const float*)w->d_Y0s, HNu, mu_out, pb);
-    } else {  // mppi (:33-36), cma-es (:39-45): softmax weights and the weighted mean in one launch
-      ScoreBatch sb;
-      sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)per_plan;
-      sb.ybar_in = mu_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
-      launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
-                               c.temp_sample, 0, w->d_weights.get(), w->d_rewmeans + step, (const float*)w->d_Y0s, HNu, mu_in, 1.0f, 1.0f,
-                               1.0f, 0, mu_out, 0, 0.0f, (float*)nullptr, sb);
-      if (c.update_method == 2) {
-        hipLaunchKernelGGL(cma_spread_kernel, dim3((HNu + 63) / 64, (unsigned)P), b64, 0, s, (const float*)w->d_weights,
-                           (const float*)w->d_Y0s, N, HNu, mu_in, w->d_spread, pb);
-        hipLaunchKernelGGL(cma_sigma_kernel, dim3(1, (unsigned)P), b64, 0, s, (const float*)w->d_spread, HNu, w->d_sigma, pb);
-      }
-    }
-    HIP_TRY(hipGetLastError());
+    PiStep st;
+    st.slot = step; st.state0 = w->d_state0;
+    st.mu_in = step == 0 ? w->d_zero.get() : w->d_mu + (size_t)(step - 1) * HNu;
+    st.mu_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
+    st.ns = w->noise_always();
+    MBD_TRY(sweep_pi_step(w, st, sk));
   }
   HIP_TRY(hipStreamSynchronize(s));
   auto t1 = std::chrono::steady_clock::now();
@@ -498,6 +524,20 @@ extern "C" int mbd_sweep_peek_mpc_track(mbd_sweep* w, int k, float* err_out, flo
   return w->demo.peek(w->env->device, k, err_out, windows_out, "sweep");
 }
 
+// one sigma record for all episodes of a path-integral sweep (include/mbd_hip.h mbd_mpc_sigma): host state
+extern "C" int mbd_sweep_set_mpc_sigma(mbd_sweep* w, const mbd_mpc_sigma* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (w->cfg.update_method == 0) return fail(MBD_ERR_STATE, "set_mpc_sigma: not a path-integral sweep (update_method == 0)");
+  NO_SWEEP_SESSION(w, "set_mpc_sigma");
+  return w->sigma_rec.set(rec, w->cfg.update_method);
+}
+
+extern "C" int mbd_sweep_peek_mpc_sigma(mbd_sweep* w, int k, float* sigmas_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "episode k=%d outside [0,%d)", k, w->P);
+  return w->sigma_rec.peek(w->env->device, k, sigmas_out, "sweep");
+}
+
 extern "C" int mbd_sweep_peek_mpc_predicted(mbd_sweep* w, float* predicted_out) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   if (!w->delay.has) return fail(MBD_ERR_STATE, "peek_mpc_predicted: the sweep has no delay record");
@@ -541,11 +581,12 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   NO_SWEEP_SESSION(w, "run_mpc");
   const mbd_plan_config& c = w->cfg;
   const int T = mc->n_ticks, K = mc->warm_steps, E = mc->exec_steps, Nd = c.Ndiffuse, H = c.Hsample;
-  MBD_TRY(check_mpc_config(c, mc, w->demo.has));
+  MBD_TRY(check_mpc_config(c, mc, w->demo.has, w->sigma_rec.has));
   MBD_TRY(w->delay.check_run(E));
   mbd_env* e = w->env;
   HIP_TRY(hipSetDevice(e->device));
   const int P = w->P, HNu = w->HNu, Nu = e->action_size(), S = e->state_size();
+  const bool pi = c.update_method != 0;  // a path-integral sweep (with a sigma record: check_mpc_config)
   HIP_TRY(w->d_mpc_rows.grow((size_t)P * (H - 1) * Nu));
   HIP_TRY(w->d_mpc_ybar.grow((size_t)P * HNu));
   HIP_TRY(w->d_mpc_states.grow(((size_t)T + 1) * P * S));
@@ -596,8 +637,13 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     for (int k = 0; k < P; ++k) { r[2 * k] = tick.k[k][0]; r[2 * k + 1] = tick.k[k][1]; }
     sweep_split_keys(w, r, sk);
   };
-  first_keys_of_tick();
-  sweep_noise(w, sk, 0, s, w->noise_always());  // tick 0, step Nd-1
+  if (pi) {  // nothing is prepared ahead: sigma = sigma_cold of every episode and the logs' first entries, one launch
+    MBD_TRY(w->sigma_rec.start(T, P));
+    w->sigma_rec.launch(w->d_sigma, P, 0, true, s);
+  } else {
+    first_keys_of_tick();
+    sweep_noise(w, sk, 0, s, w->noise_always());  // tick 0, step Nd-1
+  }
   HIP_TRY(hipGetLastError());
   const long long mu_stride = (long long)(Nd - 1) * HNu;
   const int exec_sw[3] = {1, S, 0};
@@ -613,7 +659,26 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       MBD_TRY(launch_rollout(e, states_t, q_in, P, D * E, nullptr, nullptr, nullptr, shat, s, nullptr, exec_sw));
       plan_from = shat;
     }
-    for (int i = i_start; i >= 1; --i, ++q) {
+    if (pi) {
+      // a path-integral tick (include/mbd_hip.h mbd_mpc_sigma): rng, k_t = split(rng); r = k_t; per refinement r, Y0s_rng =
+      // split(r) and mbd_sweep_run's lockstep step from the tick's states — every episode's keys, carried sigma and mean in the
+      // one sampling launch — then the carried sigmas [P] across the boundary in one launch
+      sweep_split_keys(w, rng, tick);
+      for (int k = 0; k < P; ++k) { r[2 * k] = tick.k[k][0]; r[2 * k + 1] = tick.k[k][1]; }
+      for (int i = i_start; i >= 1; --i) {
+        sweep_split_keys(w, r, sk);
+        PiStep st;
+        st.slot = Nd - 1 - i;  // (K <= Nd-1: a warm tick's steps use the last K slots)
+        st.state0 = plan_from;
+        st.mu_in = i == i_start ? (t == 0 ? w->d_zero.get() : w->d_mpc_ybar.get()) : w->d_mu + (size_t)(st.slot - 1) * HNu;
+        st.mu_stride = i == i_start ? HNu : mu_stride;
+        st.ns = t == 0 ? w->noise_always() : w->noise_warm();
+        MBD_TRY(sweep_pi_step(w, st, sk));
+      }
+      w->sigma_rec.launch(w->d_sigma, P, t, false, s);
+      HIP_TRY(hipGetLastError());
+    }
+    for (int i = pi ? 0 : i_start; i >= 1; --i, ++q) {
       const bool follows = i > 1 || t + 1 < T;
       if (i > 1) sweep_split_keys(w, r, sk);
       else if (follows) first_keys_of_tick();
@@ -700,6 +765,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     episode_major(states_out, T + 1, S, S);
   }
   if (has_delay) w->delay.pred_ticks = T;
+  if (pi) { w->sigma_rec.ticks = T; w->sigma_rec.episodes = P; }
   if ((any_plant || has_delay) && actions_out) {  // (the executed rows carry the action noise, or are the queues': their own log)
     HIP_TRY(fetch(w->d_mpc_actions, (size_t)T * P * EN));
     episode_major(actions_out, T, EN, EN);
@@ -761,7 +827,7 @@ extern "C" int mbd_sweep_mpc_open(mbd_sweep* w, const mbd_mpc_config* mc, const 
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   if (!mc) return fail(MBD_ERR_INVALID, "mpc config is NULL");
   if (!keys) return fail(MBD_ERR_INVALID, "keys is NULL");
-  MBD_TRY(check_mpc_config(w->cfg, mc, w->demo.has));
+  MBD_TRY(check_mpc_config(w->cfg, mc, w->demo.has, w->sigma_rec.has, true));
   MBD_TRY(w->delay.check_run(mc->exec_steps));
   for (int k = 0; k < w->P; ++k)
     if (w->has_plant[k])

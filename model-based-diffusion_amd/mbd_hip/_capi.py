@@ -93,6 +93,12 @@ class MpcDemo(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class MpcSigma(C.Structure):
+    """mbd_mpc_sigma (include/mbd_hip.h): the sigma a path-integral episode's cold and warm ticks start from, and the gain by
+    which a warm tick's follows the sigma the last tick ended with."""
+    _fields_ = [("sigma_cold", C.c_float), ("sigma_warm", C.c_float), ("gain", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
 TICK_ROWS_NONFINITE, TICK_STATE_NONFINITE, TICK_COLD = 1, 2, 4
 
 
@@ -108,11 +114,11 @@ EXPORTS = [
     "mbd_env_observe", "mbd_model_observe", "mbd_model_forward", "mbd_env_create_car2d", "mbd_env_create_model", "mbd_env_destroy", "mbd_env_info", "mbd_env_reset", "mbd_env_pipeline_init",
     "mbd_env_step", "mbd_env_rew_xref", "mbd_env_rollout", "mbd_plan_create", "mbd_plan_destroy",
     "mbd_plan_schedule", "mbd_plan_set_state0", "mbd_plan_sample_rollout", "mbd_plan_prefetch_noise", "mbd_plan_score_update",
-    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_set_mpc_delay", "mbd_plan_peek_mpc_predicted", "mbd_plan_set_mpc_demo", "mbd_plan_peek_mpc_track",
+    "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_set_mpc_delay", "mbd_plan_peek_mpc_predicted", "mbd_plan_set_mpc_demo", "mbd_plan_peek_mpc_track", "mbd_plan_set_mpc_sigma", "mbd_plan_peek_mpc_sigma",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
-    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_set_noise_shape", "mbd_sweep_set_noise_basis", "mbd_sweep_set_mpc_delay", "mbd_sweep_peek_mpc_predicted", "mbd_sweep_set_mpc_demo", "mbd_sweep_peek_mpc_track", "mbd_sweep_mpc_open", "mbd_sweep_mpc_submit", "mbd_sweep_mpc_collect", "mbd_sweep_mpc_tick", "mbd_sweep_mpc_reset_mean",
+    "mbd_sweep_create", "mbd_sweep_destroy", "mbd_sweep_set_state0", "mbd_sweep_run", "mbd_sweep_run_mpc", "mbd_sweep_set_mpc_plant", "mbd_sweep_set_noise_shape", "mbd_sweep_set_noise_basis", "mbd_sweep_set_mpc_delay", "mbd_sweep_peek_mpc_predicted", "mbd_sweep_set_mpc_demo", "mbd_sweep_peek_mpc_track", "mbd_sweep_set_mpc_sigma", "mbd_sweep_peek_mpc_sigma", "mbd_sweep_mpc_open", "mbd_sweep_mpc_submit", "mbd_sweep_mpc_collect", "mbd_sweep_mpc_tick", "mbd_sweep_mpc_reset_mean",
     "mbd_sweep_mpc_close", "mbd_sweep_kernel_time", "mbd_sweep_get_sigmas",
     "mbd_exchange_create", "mbd_exchange_destroy", "mbd_exchange_local_handle", "mbd_exchange_connect",
     "mbd_exchange_all_gather", "mbd_exchange_status", "mbd_exchange_fine_grained",
@@ -185,6 +191,8 @@ def load() -> C.CDLL:
     lib.mbd_plan_peek_mpc_predicted.argtypes = [_vp, _vp]
     lib.mbd_plan_set_mpc_demo.argtypes = [_vp, C.POINTER(MpcDemo)]
     lib.mbd_plan_peek_mpc_track.argtypes = [_vp, _vp, _vp]
+    lib.mbd_plan_set_mpc_sigma.argtypes = [_vp, C.POINTER(MpcSigma)]
+    lib.mbd_plan_peek_mpc_sigma.argtypes = [_vp, _vp]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
     lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
     lib.mbd_plan_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(MpcTickInfo)]
@@ -207,6 +215,8 @@ def load() -> C.CDLL:
     lib.mbd_sweep_peek_mpc_predicted.argtypes = [_vp, _vp]
     lib.mbd_sweep_set_mpc_demo.argtypes = [_vp, C.POINTER(MpcDemo)]
     lib.mbd_sweep_peek_mpc_track.argtypes = [_vp, _i, _vp, _vp]
+    lib.mbd_sweep_set_mpc_sigma.argtypes = [_vp, C.POINTER(MpcSigma)]
+    lib.mbd_sweep_peek_mpc_sigma.argtypes = [_vp, _i, _vp]
     lib.mbd_sweep_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _vp]
     lib.mbd_sweep_mpc_submit.argtypes = [_vp, _vp]
     lib.mbd_sweep_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
@@ -300,6 +310,25 @@ def debug_check_mpc_delay(rec: "MpcDelay", action_size: int) -> int:
     lib = load()
     lib.mbd_debug_check_mpc_delay.argtypes = [C.POINTER(MpcDelay), _i]
     return lib.mbd_debug_check_mpc_delay(C.byref(rec), int(action_size))
+
+
+def debug_mpc_sigma_next(sigma_end, cold: float, warm: float, gain: float) -> np.ndarray:
+    """include/mbd_hip_debug.h: the sigma a warm tick of a path-integral episode starts from, for every value of ``sigma_end``,
+    by the boundary kernel's own function run on the host (no device)."""
+    lib = load()
+    lib.mbd_debug_mpc_sigma_next.argtypes = [_vp, _i, _f, _f, _f, _vp]
+    x = np.ascontiguousarray(sigma_end, np.float32).reshape(-1)
+    out = np.empty_like(x)
+    check(lib.mbd_debug_mpc_sigma_next(np_ptr(x), x.size, cold, warm, gain, np_ptr(out)))
+    return out
+
+
+def debug_check_mpc_sigma(rec: "MpcSigma", update_method: int) -> int:
+    """include/mbd_hip_debug.h: the refusals a sigma record alone decides for a handle of that update_method — no device
+    needed.  Returns the code (the message: ``load().mbd_last_error()``)."""
+    lib = load()
+    lib.mbd_debug_check_mpc_sigma.argtypes = [C.POINTER(MpcSigma), _i]
+    return lib.mbd_debug_check_mpc_sigma(C.byref(rec), int(update_method))
 
 
 def debug_math_ops() -> list:

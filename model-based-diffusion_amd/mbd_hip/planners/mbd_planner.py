@@ -84,6 +84,7 @@ class Sweep:
         self.Nd, self.H, self.Nu = cfg.Ndiffuse, args.Hsample, env.action_size
         self._plant_envs = {}  # episode -> the plant env of its record (kept alive: a record does not own its plant)
         self._has_delay = False
+        self._has_sigma = False
         self._demo_shape = None  # (K, C) of the clip of the sweep's demo record
 
     def set_state0(self, k: int, state):
@@ -126,6 +127,10 @@ class Sweep:
         if self._has_delay:  # (the states the ticks planned from: shat_{k,0} .. shat_{k,T-1})
             out["predicted"] = np.zeros((P, T, S), np.float32)
             _capi.check(self.lib.mbd_sweep_peek_mpc_predicted(self.h, _capi.np_ptr(out["predicted"])))
+        if self._has_sigma:  # (the sigma every tick of every episode started from and ended with)
+            out["sigmas"] = np.zeros((P, T, 2), np.float32)
+            for e in range(P):
+                _capi.check(self.lib.mbd_sweep_peek_mpc_sigma(self.h, e, _capi.np_ptr(out["sigmas"][e])))
         if self._demo_shape is not None:  # (every episode's distances from the clip, and the one table of windows)
             Kt, Cc = self._demo_shape
             out["track_err"] = np.zeros((P, T * E, Kt), np.float32)
@@ -153,6 +158,18 @@ class Sweep:
     def clear_mpc_demo(self):
         _capi.check(self.lib.mbd_sweep_set_mpc_demo(self.h, None))
         self._demo_shape = None
+
+    def set_mpc_sigma(self, cold: float = 1.0, warm: float = 1.0, gain: float = 0.0):
+        """One sigma record for all episodes of a path-integral sweep (``Plan.set_mpc_sigma``): episode k of ``run_mpc`` is then
+        ``Plan.run_mpc`` on a path-integral plan with the same record, bit for bit; ``run_mpc`` also returns ``sigmas``
+        [P, T, 2].  Sessions of path-integral sweeps stay refused."""
+        rec = _sigma_record(cold, warm, gain)
+        _capi.check(self.lib.mbd_sweep_set_mpc_sigma(self.h, C.byref(rec)))
+        self._has_sigma = True
+
+    def clear_mpc_sigma(self):
+        _capi.check(self.lib.mbd_sweep_set_mpc_sigma(self.h, None))
+        self._has_sigma = False
 
     def set_mpc_plant(self, k: int, env=None, key=None, act_std: float = 0.0, kick_std: float = 0.0, kick_every: int = 1):
         """The plant of episode ``k`` (``Plan.set_mpc_plant``): episode k of ``run_mpc`` is then ``Plan.run_mpc`` with that
@@ -218,6 +235,13 @@ class Sweep:
             self.close()
         except Exception:
             pass
+
+
+def _sigma_record(cold, warm, gain):
+    """The mbd_mpc_sigma of ``set_mpc_sigma``'s arguments."""
+    rec = _capi.MpcSigma()
+    rec.sigma_cold, rec.sigma_warm, rec.gain = float(cold), float(warm), float(gain)
+    return rec
 
 
 def _plant_record(env, key, act_std, kick_std, kick_every):
@@ -440,6 +464,7 @@ class Plan:
         self._plant_env = None  # the plant env of the plan's record (kept alive: a record does not own its plant)
         self._ens_envs = None   # the member envs of the plan's ensemble record (kept alive likewise)
         self._has_delay = False
+        self._has_sigma = False
         self._demo_shape = None  # (K, C) of the clip of the plan's demo record
 
     def schedule(self):
@@ -487,6 +512,9 @@ class Plan:
         if self._has_delay:  # (the states the ticks planned from: shat_0 .. shat_{T-1})
             out["predicted"] = np.zeros((T, S), np.float32)
             _capi.check(self.lib.mbd_plan_peek_mpc_predicted(self.h, _capi.np_ptr(out["predicted"])))
+        if self._has_sigma:  # (the sigma every tick started from and ended with)
+            out["sigmas"] = np.zeros((T, 2), np.float32)
+            _capi.check(self.lib.mbd_plan_peek_mpc_sigma(self.h, _capi.np_ptr(out["sigmas"])))
         if self._demo_shape is not None:  # (how far the executed steps were from the clip, and the windows the ticks planned under)
             Kt, Cc = self._demo_shape
             out["track_err"] = np.zeros((T * E, Kt), np.float32)
@@ -531,6 +559,20 @@ class Plan:
     def clear_mpc_delay(self):
         _capi.check(self.lib.mbd_plan_set_mpc_delay(self.h, None))
         self._has_delay = False
+
+    def set_mpc_sigma(self, cold: float = 1.0, warm: float = 1.0, gain: float = 0.0):
+        """Run a path-integral plan (``update_method`` 1 / 2 / 3: mppi, cma-es, cem) as a receding-horizon controller
+        (include/mbd_hip.h mbd_mpc_sigma): ``run_mpc`` and ``mpc_open`` then accept the plan; a cold tick (tick 0; a session's
+        tick after ``reset_mean``) starts from sigma ``cold``, every other tick from ``warm`` — or, with ``gain`` > 0 (cma-es
+        only, ``warm`` <= ``cold``), from clamp(gain * the sigma the last tick ended with, warm, cold).  ``run_mpc`` then also
+        returns ``sigmas`` [T, 2]: what every tick started from and ended with.  ``run`` ignores it."""
+        rec = _sigma_record(cold, warm, gain)
+        _capi.check(self.lib.mbd_plan_set_mpc_sigma(self.h, C.byref(rec)))
+        self._has_sigma = True
+
+    def clear_mpc_sigma(self):
+        _capi.check(self.lib.mbd_plan_set_mpc_sigma(self.h, None))
+        self._has_sigma = False
 
     def set_mpc_plant(self, env=None, key=None, act_std: float = 0.0, kick_std: float = 0.0, kick_every: int = 1):
         """The plant of the plan's episodes (include/mbd_hip.h mbd_mpc_plant): ``run_mpc`` then executes the rows on ``env``

@@ -76,6 +76,17 @@ tick the session itself took (the plant excluded), tick 0 and the warm ticks' mi
 demo clip the distances from the clip are not logged (a session executes nothing on the device).  Single episodes only.
 
     python -m mbd_hip.planners.mpc --env_name hopper --n_ticks 100 --warm_steps 20 --online --plant_mass 1.3
+
+The controller need not be MBD.  ``--update_method mppi|cma-es|cem`` (include/mbd_hip.h mbd_mpc_sigma; DESIGN.md section 1 "N12
+path-integral episodes") runs the reference's path-integral baselines (path_integral.py) as the planning loop of the same
+episode — same plant, seeds, delay, mismatch and noise flags: a tick is ``warm_steps`` refinements (tick 0: Ndiffuse - 1) from the
+shifted mean.  ``--sigma_cold`` is the sampling sigma tick 0 starts from (1.0: the reference's), ``--sigma_warm`` what every later
+tick starts from; ``--sigma_gain G`` > 0 (cma-es only, whose sigma shrinks as it converges) starts a warm tick from
+clamp(G * the sigma the last tick ended with, sigma_warm, sigma_cold) instead.  ``--n_episodes`` and ``--online`` work as for MBD;
+ensembles and demos do not apply, and ``--online`` with ``--n_episodes`` > 1 ends with the library's refusal (sessions of
+path-integral sweeps are not supported).  The JSON line and the saved episode then carry the settings and the ticks' ``sigmas``.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --n_ticks 100 --warm_steps 20 --update_method mppi --sigma_warm 0.25
 """
 from __future__ import annotations
 
@@ -88,6 +99,9 @@ from .. import _capi
 from ..envs import get_env
 from ..envs.base import prng_impl
 from .mbd_planner import Args, Plan, Sweep, apply_recommended
+from .path_integral import UPDATE_METHODS as _PI_METHODS
+
+UPDATE_METHODS = dict(mbd=0, **_PI_METHODS)  # mbd_plan_config.update_method
 
 MAX_EPISODES = 32  # include/mbd_hip.h MBD_SWEEP_MAX_PLANS
 
@@ -118,6 +132,10 @@ class MpcArgs(Args):
     demo_start: int = 0  # c0: the clip row the episode's first executed control step is compared with
     demo_period: int = 0  # p > 0: the clip is first extended periodically (cycle_clip) to the rows the episode reaches
     online: bool = False  # run the episode through a session (Plan.mpc_open), one tick per call, this script being the plant
+    update_method: str = "mbd"  # the planning loop of a tick: "mbd", or the path-integral baselines "mppi", "cma-es", "cem"
+    sigma_cold: float = 1.0  # path-integral methods: the sampling sigma tick 0 starts from (1.0: path_integral.py:131) ...
+    sigma_warm: float = 1.0  # ... and every later tick,
+    sigma_gain: float = 0.0  # or with G > 0 (cma-es only) clamp(G * the sigma the last tick ended with, sigma_warm, sigma_cold)
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -314,6 +332,29 @@ def _demo_settings(args: MpcArgs) -> dict:
     return {f: getattr(args, f) for f in _DEMO_FIELDS} if _has_demo(args) else {}
 
 
+_SIGMA_FIELDS = ("update_method", "sigma_cold", "sigma_warm", "sigma_gain")
+
+
+def _method(args: MpcArgs) -> int:
+    """The update_method of the arguments' plans (ValueError on an unknown name)."""
+    if args.update_method not in UPDATE_METHODS:
+        raise ValueError(f"update_method={args.update_method!r}: one of {list(UPDATE_METHODS)}")
+    return UPDATE_METHODS[args.update_method]
+
+
+def _has_sigma(args: MpcArgs) -> bool:
+    """Whether the arguments ask for a sigma record: whenever the method is not MBD."""
+    return _method(args) != 0
+
+
+def _sigma_of(args: MpcArgs) -> tuple:
+    return args.sigma_cold, args.sigma_warm, args.sigma_gain
+
+
+def _sigma_settings(args: MpcArgs) -> dict:
+    return {f: getattr(args, f) for f in _SIGMA_FIELDS} if _has_sigma(args) else {}
+
+
 def _plant_env(env, args: MpcArgs, device: int, cache: dict = None):
     """The env that executes the rows: None (the planner's own) unless mass / friction / gear differ from 1; one env per
     distinct triple in ``cache``."""
@@ -351,8 +392,10 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
     apply_recommended(args)
     env = get_env(args.env_name, device=device)
     state_init, rng_exp = _reset_and_key(env, args.seed)
-    plan = Plan(env, args)
+    plan = Plan(env, args, update_method=_method(args))
     plan.set_state0(state_init)
+    if _has_sigma(args):
+        plan.set_mpc_sigma(*_sigma_of(args))
     cache = {}
     if _has_plant(args) and not online:
         plan.set_mpc_plant(**_record_kwargs(env, args, device, cache))
@@ -458,7 +501,9 @@ def _setup_batch(arg_list, device: int):
         apply_recommended(a)
     a0 = arg_list[0]
     env = get_env(a0.env_name, device=device)
-    sweep = Sweep(env, a0, len(arg_list), temps=[a.temp_sample for a in arg_list])
+    sweep = Sweep(env, a0, len(arg_list), temps=[a.temp_sample for a in arg_list], update_method=_method(a0))
+    if _has_sigma(a0):  # (one record for all episodes: _check_batch has held the four fields equal)
+        sweep.set_mpc_sigma(*_sigma_of(a0))
     if _has_shape(a0):  # (one shape for all episodes: _check_batch has held the three fields equal)
         sweep.set_noise_shape(*_shape_of(a0, env.action_size))
     if _has_basis(a0):  # (and one basis)
@@ -502,7 +547,7 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
         shape = _shape_settings(arg_list[0]) if _has_shape(arg_list[0]) else {}
         if _has_basis(arg_list[0]):
             shape = dict(shape, **_basis_settings(arg_list[0]))
-        shape = dict(shape, **_delay_settings(arg_list[0]), **_demo_settings(arg_list[0]))
+        shape = dict(shape, **_delay_settings(arg_list[0]), **_demo_settings(arg_list[0]), **_sigma_settings(arg_list[0]))
         windows = {"demo_windows": ep["demo_windows"]} if "demo_windows" in ep else {}  # (one table: every episode's)
         return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, **windows, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
                               **_plant_settings(arg_list[k]), **shape) for k in range(len(arg_list))]
@@ -511,8 +556,8 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
 
 def _logs(ep: dict) -> tuple:
     """The episode's logs: the four every episode has, the predicted states of one with a delay record, the distances from
-    the clip of one with a demo record."""
-    return _LOGS + tuple(k for k in ("predicted", "track_err") if k in ep)
+    the clip of one with a demo record, the ticks' sigmas of a path-integral one."""
+    return _LOGS + tuple(k for k in ("predicted", "track_err", "sigmas") if k in ep)
 
 
 def _save(args: MpcArgs, ep: dict) -> None:
@@ -540,7 +585,7 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         shape = _shape_settings(args) if _has_shape(args) else {}
         if _has_basis(args):
             shape = dict(shape, **_basis_settings(args))
-        shape = dict(shape, **_delay_settings(args), **_demo_settings(args))
+        shape = dict(shape, **_delay_settings(args), **_demo_settings(args), **_sigma_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -564,6 +609,15 @@ def _main(argv=None) -> dict:
     n_episodes = ns.pop("n_episodes")
     args = MpcArgs(**ns)
     if args.online:
+        if n_episodes != 1 and _has_sigma(args):  # (the library's own refusal: sessions of path-integral sweeps)
+            from dataclasses import replace
+            arg_list = [replace(args, seed=args.seed + k) for k in range(n_episodes)]
+            _check_batch(arg_list)
+            _, sweep, _, keys = _setup_batch(arg_list, 0)
+            try:
+                sweep.mpc_open(keys, args.warm_steps, args.exec_steps, args.n_ticks).close()
+            finally:
+                sweep.close()
         if n_episodes != 1:
             raise ValueError(f"n_episodes={n_episodes} with online: a session drives one episode")
         return _main_online(args)
@@ -598,6 +652,7 @@ def _main(argv=None) -> dict:
     if _has_basis(args):
         res.update(_basis_settings(args))
     res.update(_delay_settings(args))  # (without a record the line is what it always was)
+    res.update(_sigma_settings(args))
     if _has_demo(args):
         res.update(_demo_settings(args), track_err_mean=float(ep["track_err"].mean()))
     if not args.not_render:
@@ -629,6 +684,7 @@ def _main_online(args: MpcArgs) -> dict:
     if _has_plant(args):
         res.update(_plant_settings(args))
     res.update(_delay_settings(args))
+    res.update(_sigma_settings(args))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -658,8 +714,10 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
                 sweep.clear_mpc_plant(k)
             nominal = [float(r.mean()) for r in sweep.run_mpc(keys, T, K, E)["rewards"]]
         sweep.close()
-        plan = Plan(env, a0)
+        plan = Plan(env, a0, update_method=_method(a0))
         plan.set_state0(states[0])
+        if _has_sigma(a0):
+            plan.set_mpc_sigma(*_sigma_of(a0))
         if _has_plant(a0):
             plan.set_mpc_plant(**_record_kwargs(env, a0, 0))
         if _has_shape(a0):
@@ -695,6 +753,7 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
     if _has_basis(a0):
         res.update(_basis_settings(a0))
     res.update(_delay_settings(a0))
+    res.update(_sigma_settings(a0))
     if _has_demo(a0):
         res.update(_demo_settings(a0), track_err_mean=float(ep["track_err"].mean()))
     if not a0.not_render:
