@@ -2,7 +2,7 @@
  * session (mbd_plan_mpc_open) is opened once and advanced one tick per call from the state the caller's system is in.
  *
  *   gcc -O2 -I include examples/mbd_control.c -o mbd_control -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
- *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--mppi]
+ *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi]
  *                 env    N   H  Nd K ticks
  *
  * The "system" here is a second env the example owns, stepped with mbd_env_step — the env's rollout kernel at B = 1, H = 1 through
@@ -13,6 +13,10 @@
  * due D ticks later, and the tick planned from the state it predicted for then.
  * --mppi (last argument): the same loop with MPPI (path_integral.py) in the planner's place — a path-integral plan and the sigma
  * record that lets a session accept it: sigma 1.0 in the cold tick, 0.25 in every later one.
+ *
+ * --rate_cost L (in front of --mppi): an objective record (mbd_objective) whose rate cost L * sum_h |u_h - u_{h-1}|^2 keeps the
+ * replanned rows from chattering; the command the system is executing when the session opens goes in as prev0 — here zeros, the
+ * actuators at rest; on a robot, its current command — and from then on the library carries the last committed row itself.
  *
  * Prints one line per tick: "tick T reward R ms M flags F", then "mean_reward R ms_per_tick M". */
 #include <math.h>
@@ -41,6 +45,11 @@ static int plant_step(mbd_env* plant, float* state, const float* action, float* 
 int main(int argc, char** argv) {
   const int mppi = argc > 1 && strcmp(argv[argc - 1], "--mppi") == 0;
   if (mppi) argc -= 1;
+  float rate_cost = 0.0f;
+  if (argc > 2 && strcmp(argv[argc - 2], "--rate_cost") == 0) {
+    rate_cost = (float)atof(argv[argc - 1]);
+    argc -= 2;
+  }
   const char* env_name = argc > 1 ? argv[1] : "hopper";
   const int N = argc > 2 ? atoi(argv[2]) : 256, H = argc > 3 ? atoi(argv[3]) : 20, Nd = argc > 4 ? atoi(argv[4]) : 10;
   const int K = argc > 5 ? atoi(argv[5]) : 3, T = argc > 6 ? atoi(argv[6]) : 20, D = argc > 7 ? atoi(argv[7]) : 0;
@@ -63,6 +72,19 @@ int main(int argc, char** argv) {
     memset(&sigma, 0, sizeof(sigma));
     sigma.sigma_cold = 1.0f; sigma.sigma_warm = 0.25f; sigma.gain = 0.0f;
     CHECK(mbd_plan_set_mpc_sigma(plan, &sigma));
+  }
+  float* command = (float*)calloc((size_t)Nu, sizeof(float)); /* what the system is executing now: at rest */
+  if (!command) { /* (a NULL prev0 would silently mean "no previous action") */
+    fprintf(stderr, "out of memory\n");
+    return 1;
+  }
+  if (rate_cost > 0.0f) { /* the controller's own rate cost; the first difference of the first plan is taken against `command` */
+    mbd_objective obj;
+    memset(&obj, 0, sizeof(obj));
+    obj.rate = rate_cost;
+    obj.prev0 = command;
+    obj.rows = H; obj.cols = Nu;
+    CHECK(mbd_plan_set_objective(plan, &obj));
   }
   if (D > 0) { /* plans arrive D ticks late; the system starts committed to zeros */
     mbd_mpc_delay delay;
@@ -102,6 +124,7 @@ int main(int argc, char** argv) {
   printf("mean_reward %.9g ms_per_tick %.3f\n", reward_sum / T, 1e3 * seconds / T);
   CHECK(mbd_plan_mpc_close(plan));
   free(head);
+  free(command);
   free(rows);
   free(scratch);
   free(state);

@@ -598,6 +598,66 @@ typedef struct mbd_noise_basis {
 } mbd_noise_basis;
 int mbd_plan_set_noise_basis(mbd_plan* plan, const mbd_noise_basis* rec);
 
+/* ---- the objective: what a plan maximises (no counterpart in the reference, whose plans maximise the unweighted mean of the
+ * env's per-step rewards, mbd_planner.py:110; DESIGN.md section 1 "N13 objective") ---- */
+/* An objective record is a setting of a plan (of a sweep) beside the ensemble and noise records: weights over the horizon's rows —
+ * a discount, a terminal weight —, an effort cost and a rate cost that are the controller's, not the env's, and the action the
+ * system executed just before the plan begins, which the rate cost's first term is taken against. */
+typedef struct mbd_objective {
+  const float* row_weight;  /* HOST [Hsample] or NULL: w[h], finite, >= 0, f32 left-to-right sum > 0 and finite */
+  const float* act_weight;  /* HOST [action_size] or NULL (= ones): q[a], finite, >= 0 */
+  const float* prev0;       /* HOST [action_size] or NULL: the action executed before row 0 of the first plan */
+  float effort;             /* lambda_u  >= 0, finite */
+  float rate;               /* lambda_du >= 0, finite */
+  int32_t rows, cols;       /* must equal Hsample, action_size */
+  int32_t reserved[5];      /* must be 0 */
+} mbd_objective;
+/* With a record in force, phase 1 of a diffusion step leaves in the rewards buffer, in place of mean_H(rewss) — f32 throughout,
+ * every operation rounded, no fma (H = Hsample, N = Nsample; row b of the launch is candidate b of the shard, under an ensemble
+ * record row b of the M N rows is candidate b % N on member b / N):
+ *   ret[b]  = rews[b] as the rollout stored it                          row_weight == NULL (copied, not recomputed)
+ *           = acc / wsum,  acc = +0; for h ascending: acc = acc + (w[h] * rewss[b][h])
+ *             wsum = f32 left-to-right sum of w, formed once on the host by the set call
+ *   u[n][h][a] = the candidate value the rollout fetched: Y0s, or clip((z*sigma) + Ybar_i[h][a], -1, 1) from the normals z the
+ *                plan keeps, with the sampler's two roundings (z is already shaped or basis-spread where those records are in force)
+ *   per actuator a:  eff_a = +0; rat_a = +0
+ *                    for h ascending:
+ *                        eff_a = eff_a + (u*u)
+ *                        d = u - u_prev;  rat_a = rat_a + (d*d)
+ *                            u_prev = u[n][h-1][a] for h >= 1
+ *                            u_prev = prev[a] for h = 0; without a previous action the h = 0 term is left out
+ *   cost[n] = (c / float(H)),  c = +0; for a ascending: c = c + (q[a] * ((effort * eff_a) + (rate * rat_a)))
+ *   rews[b] = ret[b] - cost[b % N]              effort == 0 and rate == 0: the cost pass is skipped, rews[b] = ret[b]
+ * The order — per actuator over h, then over the actuators — is part of the contract.  Everything downstream is unchanged and sees
+ * these rews: the ensemble's combination of its members' (shaped) returns, standardisation, the demo blend (the log-densities
+ * are untouched), softmax, the weighted mean, the score update, the path-integral updates, rew_mean out.  mbd_plan_eval, the final
+ * reward of mbd_plan_run, an episode's rewards log and mbd_env_rollout keep the env's own rewards.
+ * Bit for bit: no record, or a cleared one, leaves every call as it is — same launches, same bits; a record of NULL weights and zero
+ * costs gives the same bits; so does row_weight all ones with zero costs (the rollout kernels accumulate rew_sum = 0; rew_sum =
+ * rew_sum + rew in step order and divide by float(H): the sum above with w = 1 and wsum = float(H)); a one-hot w gives ret[b] ==
+ * rewss[b][h0] in value; a candidate whose rewss holds a non-finite value has a non-finite ret (nothing is skipped: 0 * NaN stays
+ * NaN) and no other candidate's bits move.
+ * The previous action.  mbd_plan_run, mbd_sweep_run and the phase calls use clip(prev0, -1, 1), or none when prev0 is NULL.  In an
+ * episode or a session, every tick after the first uses clip(M_{t-1}[E-1], -1, 1), the last row committed before the new plan's
+ * row 0 — the same row with a delay record and without, because C = C[1:] ++ M_t[0:E]; with a plant record it is the commanded row,
+ * not the disturbed one.  The first tick uses the clipped last row of the delay record's queue C (rows0, or zeros), and without a
+ * delay record clip(prev0), or none.  prev lives on the device: one small launch per tick, in front of the boundary kernel, forms
+ * the next tick's — no host write, no synchronisation inside a tick loop — and mbd_*_mpc_reset_mean leaves it alone, as it leaves
+ * the delay queue alone.
+ * Every call that samples takes the record: MBD and path-integral plans, rigid-body envs and car2d, sharded plans (every rank sets
+ * the same record), plans with a plant, delay, demo, sigma, ensemble, noise-shape or noise-basis record, sweeps (one record for
+ * all plans) and both kinds of session (read at open).  Under a record a step gains exactly one launch, between the rollout and
+ * the score (under an ensemble: in front of the launch that combines the members).
+ * The set call copies its tables, is synchronous (it waits for the device) and is to be called between diffusion steps; rec ==
+ * NULL clears.  Refused with MBD_ERR_INVALID before any device access, the message naming the field: a NULL handle, non-zero
+ * reserved, rows != Hsample, cols != action_size, a negative or non-finite row_weight / act_weight / effort / rate, a non-finite
+ * prev0, a sum of row_weight that is not finite and positive.  MBD_ERR_STATE while a session is open on the handle. */
+int mbd_plan_set_objective(mbd_plan* plan, const mbd_objective* rec);
+/* the last step's ret and cost (HOST; either may be NULL; synchronises the device): ret_out [shard_count], under an ensemble
+ * record [n_members * Nsample]; cost_out [shard_count], all +0 when the cost pass is skipped.  MBD_ERR_STATE without a record, or
+ * before a step has run with one. */
+int mbd_plan_peek_objective(mbd_plan* plan, float* ret_out, float* cost_out);
+
 /* ---- planning ahead of the plant: an episode whose plans take D ticks to arrive (the real-time iteration scheme; no
  * counterpart in the reference; DESIGN.md section 1 "N9 delay") ---- */
 /* The episode of mbd_plan_run_mpc plans from s_t and executes that plan's first rows from the same s_t: planning takes no time.
@@ -741,7 +801,7 @@ int mbd_plan_mpc_reset_mean(mbd_plan* plan);
 /* close: waits for a tick in flight and drops it.  NULL plan -> MBD_ERR_INVALID; no session open -> MBD_ERR_STATE.
  * mbd_plan_destroy closes an open session.  While a session is open, these calls on the same handle return MBD_ERR_STATE, the
  * message naming the session: mbd_plan_run, _run_mpc, _eval, _set_state0, _reverse_once, _sample_rollout, _score_update and
- * every mbd_plan_set_* record call (plant, ensemble, noise shape, noise basis, delay, demo, sigma). */
+ * every mbd_plan_set_* record call (plant, ensemble, noise shape, noise basis, delay, demo, sigma, objective). */
 int mbd_plan_mpc_close(mbd_plan* plan);
 
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
@@ -813,6 +873,14 @@ int mbd_sweep_set_noise_shape(mbd_sweep* sweep, const mbd_noise_shape* rec);
 /* one noise basis (mbd_noise_basis, above) for all plans of the sweep, with the same guarantee.  Refusals as
  * mbd_plan_set_noise_basis's. */
 int mbd_sweep_set_noise_basis(mbd_sweep* sweep, const mbd_noise_basis* rec);
+/* one objective record (mbd_objective, above) for all plans of the sweep — prev0 is every plan's —: plan k of mbd_sweep_run, episode
+ * k of mbd_sweep_run_mpc and of a sweep's session is then the single plan's with the same record, bit for bit, whatever the other
+ * plans do.  One launch over the n_plans * Nsample rows per step (blockIdx.y = plan), one launch per tick for every episode's
+ * previous action.  Refusals as mbd_plan_set_objective's. */
+int mbd_sweep_set_objective(mbd_sweep* sweep, const mbd_objective* rec);
+/* plan k's ret_out [Nsample] and cost_out [Nsample] of the last step; as mbd_plan_peek_objective; k outside [0, n_plans) ->
+ * MBD_ERR_INVALID */
+int mbd_sweep_peek_objective(mbd_sweep* sweep, int k, float* ret_out, float* cost_out);
 /* one delay record (mbd_mpc_delay, above) for all episodes of the sweep: episode k of mbd_sweep_run_mpc is then
  * mbd_plan_run_mpc on a plan of its own with the same record, bit for bit, whatever the other episodes do.  The prediction is
  * ONE rollout launch over the n_plans episodes, one candidate each, and the n_plans * Nsample planning candidates start from

@@ -59,6 +59,18 @@ int mbd_debug_mpc_sigma_next(const float* sigma_end, int n, float sigma_cold, fl
 /* The refusals a sigma record alone decides for a handle of that update_method: the function both set calls run on their record,
  * host arithmetic, no device. */
 int mbd_debug_check_mpc_sigma(const mbd_mpc_sigma* rec, int update_method);
+/* The refusals an objective record alone decides (include/mbd_hip.h mbd_objective) for a handle of that Hsample and action_size:
+ * the function both set calls run on their record, host arithmetic, no device — so that a test without a GPU, whose stand-in handle
+ * has Hsample = action_size = 0, reaches the refusals of the tables' values too. */
+int mbd_debug_check_objective(const mbd_objective* rec, int Hsample, int action_size);
+/* objective_kernel's arithmetic on the HOST: the per-candidate functions the kernel calls (one text for host and device) over B rows
+ * in a loop, the actuators' terms summed in ascending order as the kernel's lanes are, no device touched.  HOST rewss [B][H], rews
+ * [B] (mean_H as a rollout stores it), cand [N][H][Nu] — values, or with lazy != 0 normals formed as clip((z * sigma) + ybar[h][a],
+ * -1, 1) —, row b is candidate b % N; w [H] or NULL with its f32 left-to-right sum wsum, q [Nu], prev [Nu] (already clipped) or
+ * NULL; rews_out [B], ret_out [B], cost_out [min(B, N)]. */
+int mbd_debug_objective_host(const float* rewss, const float* rews, int B, int N, int H, int Nu, const float* cand, int lazy,
+                             float sigma, const float* ybar, const float* w, float wsum, const float* q, float effort, float rate,
+                             const float* prev, float* rews_out, float* ret_out, float* cost_out);
 #ifdef __cplusplus
 }
 #endif

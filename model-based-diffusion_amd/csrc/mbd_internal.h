@@ -406,6 +406,38 @@ struct DemoRec {
   // HOST err_out [T E][K] and windows_out [T][K][kXrefRows][C] of episode k of the last run; either may be NULL
   int peek(int device, int k, float* err_out, float* windows_out, const char* what) const;
 };
+// The objective record of a plan or a sweep (include/mbd_hip.h mbd_objective) as the handle keeps it, with what the two handles do
+// alike.  check_objective: the refusals the record alone decides against the handle's Hsample x action_size, in the header's
+// order, each naming the field — host arithmetic on the record's own tables, before any device access —, and the f32
+// left-to-right sum of row_weight (*wsum_out; untouched when row_weight is NULL).  set: behind the handle's NULL and session checks
+// and check_objective, whose sum it is handed (nullptr clears); copies the tables onto the device for P plans of N candidates (a plan: P = 1; max_rows: the most rows a step's
+// launch scores — M N under an ensemble record).  prev: the previous action every plan's steps take their rate cost against,
+// [P][Nu] on the device or nullptr: none — d_prev0 (clip(prev0), or nullptr) outside episodes; an episode or a session points it
+// at d_prev, which episode_start fills where the first tick has a previous action and tick_advance re-forms per tick, and
+// episode_end puts it back.
+struct ObjectiveRec {
+  bool has = false, has_w = false, has_prev0 = false, stepped = false;
+  float effort = 0.0f, rate = 0.0f, wsum = 0.0f;
+  int P = 1, N = 0, H = 0, Nu = 0, rows = 0;  // rows: of the last step's launch, per plan
+  DevBuf<float> d_w, d_q, d_prev0, d_prev, d_ret, d_cost;
+  const float* prev = nullptr;
+  int set(const mbd_objective* rec, float wsum_, int device, int P_, int N_, int H_, int Nu_, size_t max_rows);
+  bool costs() const { return effort != 0.0f || rate != 0.0f; }
+  // the launch between a rollout and its score: a plan's (ybar_stride < 0: objective_kernel) or a sweep's P plans.  d_rewss
+  // [B][H] and d_rews [B] are the rollout's outputs, d_rews is rewritten in place; B, row0: ObjectiveArgs
+  int launch(const float* d_rewss, float* d_rews, int B, int row0, const float* d_cand, bool lazy, float sigma,
+             const float* d_ybar, long long ybar_stride, hipStream_t s);
+  // in front of an episode's or a session's first tick: d_queue_last — row D E - 1 of episode 0's committed queue [P][Q] on the
+  // device, or nullptr: no delay record
+  int episode_start(const float* d_queue_last, long long Q, hipStream_t s);
+  // behind a tick's last update kernel, in front of its boundary kernel: d_row — row E-1 of episode 0's M_t, episode k's
+  // stride floats further
+  int tick_advance(const float* d_row, long long stride, hipStream_t s);
+  void episode_end() { prev = has_prev0 ? d_prev0.get() : nullptr; }
+  // HOST ret_out [rows], cost_out [min(rows, N)] of plan k's last step (env: the handle's, looked at behind the state checks)
+  int peek(const mbd_env* env, int k, float* ret_out, float* cost_out, const char* what) const;
+};
+int check_objective(const mbd_objective* rec, int Hsample, int action_size, float* wsum_out);
 // One tick of a plant's disturbance chain, dk, d_t = split(dk): advances dk, fills slot k of sp with d_t and the record's
 // deviations — the kick's only in the ticks that end with one — and says whether tick t does
 bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k);

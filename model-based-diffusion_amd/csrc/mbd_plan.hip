@@ -182,6 +182,8 @@ struct mbd_plan {
   DevBuf<float> d_basis, d_knot_z;
   bool has_basis = false;
   int basis_knots = 0, basis_when = MBD_NOISE_ALWAYS;
+  // the objective record (mbd_plan_set_objective) with its tables, the previous action and the last step's ret and cost
+  ObjectiveRec obj;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_plan_mpc_open); it uses the episodes' buffers above — d_mpc_state for the
   // state handed in, d_mpc_pred for the one predicted state, d_mpc_queue — so a handle runs episodes or a session, not both
@@ -556,6 +558,9 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
     const EnsArgs ea{p->ens_rec.n_members, p->ens_rec.members};
     MBD_TRY(launch_rollout(e, d_state0, d_cand, N, H, p->d_ens_rewss, p->d_ens_rews, nullptr, nullptr, s,
                            p->lazy ? &lz : nullptr, nullptr, nullptr, &ea));
+    // the objective over the M N rows, candidate b % N: each member's return is the shaped one, the combination is unchanged
+    if (p->obj.has)
+      MBD_TRY(p->obj.launch(p->d_ens_rewss, p->d_ens_rews, p->ens_rec.n_members * N, 0, d_cand, p->lazy, p->sigmas[i], d_Ybar_i, -1, s));
     hipLaunchKernelGGL(ensemble_reduce_kernel, dim3((N + 255) / 256), dim3(256), 0, s, (const float*)p->d_ens_rews,
                        p->ens_rec.n_members, N, p->ens_rec.risk, d_rews_local, p->d_ens_comb);
     HIP_TRY(hipGetLastError());
@@ -566,6 +571,12 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
                            nullptr, fused_lp ? d_logpd_local : nullptr, nullptr, d_xref));
   }
   MBD_TRY(p->timing.end(s));
+  // The objective record: ONE launch between the rollout and the score rewrites the shard's rewards in place (a path-integral plan
+  // samples under its carried sigma, but its candidates are materialised: d_Y0s holds the values).  The noise ring's bookkeeping
+  // needs no change: the launch reads eps[cur] on the step's stream between the rollout and the weighted mean, and the weighted
+  // mean is already marked as the buffer's last reader.
+  if (p->obj.has && !p->has_ens)
+    MBD_TRY(p->obj.launch(p->d_rewss, d_rews_local, c.shard_count, c.shard_begin, d_cand, p->lazy, p->sigmas[i], d_Ybar_i, -1, s));
   MBD_TRY(finish_noise_job(p, lz, marked));
   if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, p->d_xpos, c.shard_count, H, d_logpd_local, s, d_xref));
   return MBD_OK;
@@ -1371,6 +1382,164 @@ extern "C" int mbd_plan_peek_ensemble(mbd_plan* p, float* rews_members_out, floa
   return MBD_OK;
 }
 
+// ---- the objective record (include/mbd_hip.h mbd_objective) -------------------------------------------------------------
+int check_objective(const mbd_objective* rec, int Hsample, int action_size, float* wsum_out) {
+  for (int r = 0; r < 5; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "objective: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (rec->rows != Hsample) return fail(MBD_ERR_INVALID, "objective: rows=%d, the handle's Hsample is %d", rec->rows, Hsample);
+  if (rec->cols != action_size) return fail(MBD_ERR_INVALID, "objective: cols=%d, the env's action_size is %d", rec->cols, action_size);
+  if (rec->row_weight)
+    for (int h = 0; h < Hsample; ++h)
+      if (!std::isfinite(rec->row_weight[h]) || rec->row_weight[h] < 0.0f)
+        return fail(MBD_ERR_INVALID, "objective: row_weight[%d]=%g: must be finite and >= 0", h, (double)rec->row_weight[h]);
+  if (rec->act_weight)
+    for (int a = 0; a < action_size; ++a)
+      if (!std::isfinite(rec->act_weight[a]) || rec->act_weight[a] < 0.0f)
+        return fail(MBD_ERR_INVALID, "objective: act_weight[%d]=%g: must be finite and >= 0", a, (double)rec->act_weight[a]);
+  if (!std::isfinite(rec->effort) || rec->effort < 0.0f)
+    return fail(MBD_ERR_INVALID, "objective: effort=%g: must be finite and >= 0", (double)rec->effort);
+  if (!std::isfinite(rec->rate) || rec->rate < 0.0f)
+    return fail(MBD_ERR_INVALID, "objective: rate=%g: must be finite and >= 0", (double)rec->rate);
+  if (rec->prev0)
+    for (int a = 0; a < action_size; ++a)
+      if (!std::isfinite(rec->prev0[a])) return fail(MBD_ERR_INVALID, "objective: prev0[%d]=%g: must be finite", a, (double)rec->prev0[a]);
+  if (rec->row_weight) {
+    float wsum = 0.0f;
+    for (int h = 0; h < Hsample; ++h) wsum = wsum + rec->row_weight[h];
+    if (!std::isfinite(wsum) || !(wsum > 0.0f))
+      return fail(MBD_ERR_INVALID, "objective: the sum of row_weight is %g: must be finite and > 0", (double)wsum);
+    if (wsum_out) *wsum_out = wsum;
+  }
+  return MBD_OK;
+}
+extern "C" int mbd_debug_check_objective(const mbd_objective* rec, int Hsample, int action_size) {
+  if (!rec) return fail(MBD_ERR_INVALID, "objective record is NULL");
+  if (Hsample < 0 || action_size < 0) return fail(MBD_ERR_INVALID, "Hsample=%d action_size=%d", Hsample, action_size);
+  return check_objective(rec, Hsample, action_size, nullptr);
+}
+// include/mbd_hip_debug.h: the per-candidate functions of objective_kernel on the host (one text for host and device) over B rows
+// in a loop, the actuators' terms summed in ascending order as the kernel's lanes are — no device is touched
+extern "C" int mbd_debug_objective_host(const float* rewss, const float* rews, int B, int N, int H, int Nu, const float* cand, int lazy,
+                                        float sigma, const float* ybar, const float* w, float wsum, const float* q, float effort,
+                                        float rate, const float* prev, float* rews_out, float* ret_out, float* cost_out) {
+  if (!rewss || !rews || !cand || !q || !rews_out || !ret_out || !cost_out || (lazy && !ybar))
+    return fail(MBD_ERR_INVALID, "NULL argument");
+  if (B < 1 || N < 1 || H < 1 || Nu < 1 || Nu > MBD_MAX_ACT) return fail(MBD_ERR_INVALID, "objective_host: B=%d N=%d H=%d Nu=%d", B, N, H, Nu);
+  const bool costs = effort != 0.0f || rate != 0.0f;
+  for (int b = 0; b < B; ++b) {
+    const float ret = w ? objective_ret(rewss + (size_t)b * H, w, wsum, H) : rews[b];
+    float c = 0.0f;
+    if (costs) {
+      for (int a = 0; a < Nu; ++a) {
+        float eff, rat;
+        objective_column(cand + (size_t)(b % N) * H * Nu, H, Nu, a, lazy, sigma, ybar, prev, eff, rat);
+        c = c + objective_term(q[a], effort, eff, rate, rat);
+      }
+      c = c / (float)H;
+    }
+    rews_out[b] = costs ? ret - c : ret;
+    ret_out[b] = ret;
+    if (b < N) cost_out[b] = c;
+  }
+  return MBD_OK;
+}
+
+int ObjectiveRec::set(const mbd_objective* rec, float ws, int device, int P_, int N_, int H_, int Nu_, size_t max_rows) {
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the previous record's tables)
+  has = false;
+  stepped = false;
+  prev = nullptr;
+  if (!rec) return MBD_OK;
+  P = P_; N = N_; H = H_; Nu = Nu_;
+  HIP_TRY(d_w.grow(H));
+  HIP_TRY(d_q.grow(Nu));
+  HIP_TRY(d_prev0.grow((size_t)P * Nu));
+  HIP_TRY(d_prev.grow((size_t)P * Nu));
+  HIP_TRY(d_ret.grow((size_t)P * max_rows));
+  HIP_TRY(d_cost.grow((size_t)P * N));
+  has_w = rec->row_weight != nullptr;
+  if (has_w) HIP_TRY(hipMemcpy(d_w, rec->row_weight, sizeof(float) * H, hipMemcpyHostToDevice));
+  std::vector<float> q((size_t)Nu, 1.0f);  // (NULL: ones — x * 1 = x)
+  if (rec->act_weight) q.assign(rec->act_weight, rec->act_weight + Nu);
+  HIP_TRY(hipMemcpy(d_q, q.data(), sizeof(float) * Nu, hipMemcpyHostToDevice));
+  has_prev0 = rec->prev0 != nullptr;
+  if (has_prev0) {  // clip(prev0), one copy per plan
+    std::vector<float> pv((size_t)P * Nu);
+    for (size_t e = 0; e < pv.size(); ++e) pv[e] = fclip(rec->prev0[e % Nu], -1.0f, 1.0f);
+    HIP_TRY(hipMemcpy(d_prev0, pv.data(), sizeof(float) * pv.size(), hipMemcpyHostToDevice));
+  }
+  effort = rec->effort; rate = rec->rate; wsum = ws;
+  has = true;
+  episode_end();
+  return MBD_OK;
+}
+
+int ObjectiveRec::launch(const float* d_rewss, float* d_rews, int B, int row0, const float* d_cand, bool lazy, float sigma,
+                         const float* d_ybar, long long ybar_stride, hipStream_t s) {
+  ObjectiveArgs A;
+  A.rewss = d_rewss; A.rews = d_rews;
+  // (rows cycle through the plan's N candidates under an ensemble, B = M N; a shard's B <= N rows are its own candidates, from row0)
+  A.B = B; A.N = B < N ? B : N; A.row0 = row0; A.H = H; A.Nu = Nu;
+  A.cand = d_cand; A.lazy = lazy ? 1 : 0; A.sigma = sigma; A.ybar = d_ybar;
+  A.w = has_w ? d_w.get() : nullptr; A.wsum = wsum;
+  A.q = d_q; A.effort = effort; A.rate = rate; A.costs = costs() ? 1 : 0;
+  A.prev = prev;
+  A.ret_keep = d_ret; A.cost_keep = d_cost;
+  if (ybar_stride < 0)
+    hipLaunchKernelGGL(objective_kernel, dim3(objective_blocks(B)), dim3(kObjThreads), 0, s, A);
+  else
+    hipLaunchKernelGGL(objective_batch_kernel, dim3(objective_blocks(B), (unsigned)P), dim3(kObjThreads), 0, s, A, ybar_stride);
+  HIP_TRY(hipGetLastError());
+  rows = B;
+  stepped = true;
+  return MBD_OK;
+}
+
+int ObjectiveRec::episode_start(const float* d_queue_last, long long Q, hipStream_t s) {
+  if (!has) return MBD_OK;
+  episode_end();  // the first tick without a delay record: clip(prev0), or none
+  if (d_queue_last) {
+    hipLaunchKernelGGL(objective_prev_kernel, dim3(1, (unsigned)P), dim3(64), 0, s, d_queue_last, Q, Nu, d_prev.get());
+    HIP_TRY(hipGetLastError());
+    prev = d_prev;
+  }
+  return MBD_OK;
+}
+
+int ObjectiveRec::tick_advance(const float* d_row, long long stride, hipStream_t s) {
+  if (!has) return MBD_OK;
+  hipLaunchKernelGGL(objective_prev_kernel, dim3(1, (unsigned)P), dim3(64), 0, s, d_row, stride, Nu, d_prev.get());
+  HIP_TRY(hipGetLastError());
+  prev = d_prev;
+  return MBD_OK;
+}
+
+int ObjectiveRec::peek(const mbd_env* env, int k, float* ret_out, float* cost_out, const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_objective: the %s has no objective record", what);
+  if (!stepped) return fail(MBD_ERR_STATE, "peek_objective: no diffusion step with the record to show yet");
+  if (k < 0 || k >= P) return fail(MBD_ERR_INVALID, "peek_objective: plan k=%d outside [0,%d)", k, P);
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const int nc = rows < N ? rows : N;
+  if (ret_out) HIP_TRY(hipMemcpy(ret_out, d_ret.get() + (size_t)k * rows, sizeof(float) * rows, hipMemcpyDeviceToHost));
+  if (cost_out) HIP_TRY(hipMemcpy(cost_out, d_cost.get() + (size_t)k * nc, sizeof(float) * nc, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_objective(mbd_plan* p, const mbd_objective* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_objective");
+  float wsum = 0.0f;
+  if (rec) MBD_TRY(check_objective(rec, p->cfg.Hsample, p->Nu, &wsum));  // (before any device access)
+  return p->obj.set(rec, wsum, p->env->device, 1, p->cfg.Nsample, p->cfg.Hsample, p->Nu, (size_t)MBD_MAX_ENSEMBLE * p->cfg.Nsample);
+}
+
+extern "C" int mbd_plan_peek_objective(mbd_plan* p, float* ret_out, float* cost_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->obj.peek(p->env, 0, ret_out, cost_out, "plan");
+}
+
 // ---- one tick's planning, shared by the batch episode (mbd_plan_run_mpc) and the session (mbd_plan_mpc_submit) ------------------
 // The tick's keys, host arithmetic: rng, k_t = split(rng) advances the episode's chain; r = k_t is where the tick's own chain
 // starts (mbd_plan_run's from it); after = split(split(rng')[1])[1] is the Y0s_rng of tick t+1's first step, whose normals are
@@ -1398,6 +1567,7 @@ struct MpcTick {
   int DE = 0;
   bool cold = false;
   int K = 1;
+  int E = 1;  // exec_steps: row E-1 of M_t is the last row committed before the next plan's row 0 (an objective record's prev)
   const uint32_t* key_after = nullptr;
   const float* d_xref = nullptr;
 };
@@ -1420,6 +1590,10 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
     cur = nxt;
   }
   *mean = cur;
+  // with an objective record, the next tick's previous action: clip(M_t[E-1]) — the commanded row, whatever a plant record adds to
+  // it — by one launch behind the tick's last update kernel, hence in front of whatever boundary the caller runs: a session's
+  // boundary kernel stays its tick's last kernel.  Here, so that the batch episode and the session cannot differ in it.
+  MBD_TRY(p->obj.tick_advance(cur + (size_t)(tk.E - 1) * p->Nu, 0, s));
   return MBD_OK;
 }
 
@@ -1507,6 +1681,13 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     MBD_TRY(p->delay.upload(p->d_mpc_queue, 1, E, Nu, s));
     p->delay.pred_ticks = 0;
   }
+  // with an objective record: the previous action of tick 0 — the clipped last row of the committed queue, else clip(prev0) or
+  // none — and from here to the end of the call the episode's slot, which one launch per tick re-forms
+  MBD_TRY(p->obj.episode_start(has_delay ? p->d_mpc_queue + (Q - Nu) : nullptr, Q, s));
+  struct ObjEpisode {
+    ObjectiveRec& o;
+    ~ObjEpisode() { o.episode_end(); }
+  } obj_episode{p->obj};
   if (pi) {  // sigma = sigma_cold and the log's first entry, by the kernel that carries sigma across the boundaries
     MBD_TRY(p->sigma_rec.start(T, 1));
     p->sigma_rec.launch(p->d_sigma, 1, 0, true, s);
@@ -1524,7 +1705,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     float* q_out = has_delay ? p->d_mpc_queue + (size_t)((t + 1) & 1) * Q : nullptr;
     MpcTick tk;
     tk.s_t = s_t; tk.q_in = q_in; tk.shat = has_delay ? p->d_mpc_pred + (size_t)t * S : nullptr; tk.DE = D * E;
-    tk.cold = t == 0; tk.K = K; tk.key_after = t + 1 < T ? after : nullptr;
+    tk.cold = t == 0; tk.K = K; tk.E = E; tk.key_after = t + 1 < T ? after : nullptr;
     tk.d_xref = has_demo ? p->demo.window(t) : nullptr;
     const float* cur = nullptr;
     MBD_TRY(mpc_plan_tick(p, tk, r, s, &cur));
@@ -1662,6 +1843,9 @@ extern "C" int mbd_plan_mpc_open(mbd_plan* p, const mbd_mpc_config* mc, const ui
   }
   HIP_TRY(hipStreamSynchronize(s));
   if (p->demo.has) MBD_TRY(p->demo.session_start());
+  // the objective record's previous action of the first tick, as mbd_plan_run_mpc forms it, and the session's slot until close —
+  // behind everything else that can fail, and itself leaving the slot alone when it fails: a failed open leaves prev as it was
+  MBD_TRY(p->obj.episode_start(p->delay.has ? p->d_mpc_queue + (Q - p->Nu) : nullptr, Q, s));
   // (nothing fails from here on: a refused or failed open leaves the last episode's logs readable)
   if (p->delay.has) p->delay.pred_ticks = 0;  // (mbd_plan_peek_mpc_predicted does not serve sessions)
   ss.mc = *mc;
@@ -1707,7 +1891,7 @@ extern "C" int mbd_plan_mpc_submit(mbd_plan* p, const float* state) {
   float* q_out = has_delay ? p->d_mpc_queue + (size_t)(ss.qbuf ^ 1) * Q : nullptr;
   MpcTick tk;
   tk.s_t = s_t; tk.q_in = q_in; tk.shat = has_delay ? p->d_mpc_pred.get() : nullptr; tk.DE = D * E;
-  tk.cold = ss.cold; tk.K = ss.mc.warm_steps; tk.key_after = ss.t + 1 < ss.mc.n_ticks ? after : nullptr;
+  tk.cold = ss.cold; tk.K = ss.mc.warm_steps; tk.E = E; tk.key_after = ss.t + 1 < ss.mc.n_ticks ? after : nullptr;
   tk.d_xref = p->demo.has ? p->demo.window(0) : nullptr;
   const float* M = nullptr;
   MBD_TRY(mpc_plan_tick(p, tk, r, s, &M));
@@ -1782,6 +1966,7 @@ extern "C" int mbd_plan_mpc_close(mbd_plan* p) {
   if (ss.in_flight) HIP_TRY(hipStreamSynchronize(p->stream));  // (its last kernel writes the mailbox)
   ss.in_flight = false;
   ss.open = false;
+  p->obj.episode_end();
   ss.stage.release();
   ss.mailbox.release();
   return MBD_OK;

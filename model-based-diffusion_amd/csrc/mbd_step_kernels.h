@@ -724,6 +724,136 @@ static __global__ __launch_bounds__(256) void ensemble_reduce_kernel(const float
   keep[n] = a;
 }
 
+// ---- the objective (mbd_plan_set_objective, include/mbd_hip.h mbd_objective): between the rollout and the score, the rollout's
+// per-step rewards and the candidates it fetched -> the rewards the score sees, rews[b] = ret[b] - cost[b % N] ----
+// The arithmetic of one candidate is the functions below, host and device text: the per-row steps are what the kernel's lanes run,
+// the loops over them what mbd_debug_objective_host runs on the CPU, where a test without a device holds them to the checker.
+// f32, every operation rounded (the build's -ffp-contract=off).
+// ret of one row: its per-step rewards r [H] under the row weights w [H] — acc = +0, acc = acc + (w[h] * r[h]) for h ascending,
+// then ONE division by wsum, the f32 left-to-right sum of w the set call formed.  Nothing is skipped: 0 * NaN stays NaN.
+MBD_HD float objective_ret_step(float acc, float w, float r) { return acc + w * r; }
+MBD_HD float objective_ret(const float* __restrict__ r, const float* __restrict__ w, float wsum, int H) {
+  float acc = 0.0f;
+  for (int h = 0; h < H; ++h) acc = objective_ret_step(acc, w[h], r[h]);
+  return acc / wsum;
+}
+// Column a of one candidate c [H][Nu] — values, or (lazy) the normals z of a plan that keeps them, formed as the rollout's fetch
+// forms them: clip((z * sigma) + ybar[h][a], -1, 1), shift_kernel's two roundings —: eff = sum over h of u u, rat = sum over h of
+// (u - u_prev)^2, both from +0 in ascending h.  u_prev stays in a register from the row before; at h = 0 it is prev[a], and
+// without a previous action (have == false) the h = 0 term is left out.
+MBD_HD float objective_value(float x, int lazy, float sigma, float yb) { return lazy ? fclip(x * sigma + yb, -1.0f, 1.0f) : x; }
+MBD_HD void objective_column_step(float u, float& up, bool& have, float& eff, float& rat) {
+  eff = eff + u * u;
+  const float d = u - up;
+  rat = have ? rat + d * d : rat;
+  up = u;
+  have = true;
+}
+MBD_HD void objective_column(const float* __restrict__ c, int H, int Nu, int a, int lazy, float sigma,
+                             const float* __restrict__ ybar, const float* __restrict__ prev, float& eff, float& rat) {
+  eff = 0.0f; rat = 0.0f;
+  bool have = prev != nullptr;
+  float up = have ? prev[a] : 0.0f;
+  for (int h = 0; h < H; ++h)
+    objective_column_step(objective_value(c[h * Nu + a], lazy, sigma, lazy ? ybar[h * Nu + a] : 0.0f), up, have, eff, rat);
+}
+// actuator a's term of the cost: q[a] * ((effort * eff_a) + (rate * rat_a)); the cost is their sum from +0 in ascending a, / float(H)
+MBD_HD float objective_term(float q, float effort, float eff, float rate, float rat) { return q * (effort * eff + rate * rat); }
+
+// One launch over the B rows of a rollout launch.  A candidate's row is served by a 32-lane half of a wavefront: lane a < Nu is
+// actuator a (Nu <= MBD_MAX_ACT = 24) — row h of the candidate is ONE contiguous read of Nu floats across the half —, and the
+// half's last lane, never an actuator, reads the row's H per-step rewards, forms ret and stores the results.  ONE loop over h
+// serves both: every lane loads one float per row through its own pointer and stride (an actuator's column, the last lane's
+// rewards; the other lanes a constant) and runs both per-row steps on it — each lane keeps the one that is its own, so the
+// wavefront never diverges and the rewards' chain runs beside the columns' instead of behind them; the loads do not depend on the
+// chains, and the loop is unrolled so that several rows are in flight.  The sum over the actuators is serial in ascending lane
+// order, as the contract says (every lane of the half runs it, the last one keeps it): a butterfly would change the bits.  A
+// half reads only its own lanes (__shfl of width 32), lanes >= Nu hold a term nobody reads and the halves of rows >= B read
+// nothing of any candidate and store nothing, so no value crosses from one candidate to another: a diverged candidate's NaN stays in its own row.  No
+// lane leaves early (the shuffles see whole halves).  Plain vector loads and stores.
+constexpr int kObjLanes = 32;     // lanes per candidate
+constexpr int kObjThreads = 256;  // 8 candidates per workgroup
+static_assert(MBD_MAX_ACT < kObjLanes, "a candidate's half needs a lane beyond the actuators");
+struct ObjectiveArgs {
+  const float* rewss;  // [B][H] the per-step rewards of the launch's rows
+  float* rews;         // [B] in: mean_H as the rollout stored it; out: ret - cost
+  int B, N, row0;      // rows; row b is candidate row0 + b % N of cand (a shard: row0 = shard_begin, N = B; an ensemble: B = M N)
+  int H, Nu;
+  const float* cand;   // [.][H][Nu] the candidates' values, or their normals (lazy)
+  int lazy;
+  float sigma;
+  const float* ybar;   // [H][Nu] Ybar_i (lazy)
+  const float* w;      // [H] row weights, or nullptr: ret = rews as stored
+  float wsum;
+  const float* q;      // [Nu] actuator weights
+  float effort, rate;
+  int costs;           // 0: the cost pass is skipped (effort == 0 and rate == 0)
+  const float* prev;   // [Nu] the action executed before row 0, clipped, or nullptr: none
+  float* ret_keep;     // [B]  what mbd_*_peek_objective returns
+  float* cost_keep;    // [N]
+};
+__device__ __forceinline__ void objective_body(const ObjectiveArgs& A) {
+  const int lane = threadIdx.x & (kObjLanes - 1);
+  const int b = blockIdx.x * (kObjThreads / kObjLanes) + threadIdx.x / kObjLanes;
+  const bool live = b < A.B;
+  const bool last = live && lane == kObjLanes - 1;
+  const bool act = live && A.costs && lane < A.Nu;  // this lane walks a column
+  const bool weighs = last && A.w;                  // this lane walks the row's rewards
+  const int lazy = act ? A.lazy : 0;
+  // what the lane reads in row h: x[h * stride] and, forming a lazy candidate, yb[h * ystride].  A lane with nothing of its own to
+  // read — a lane between the actuators and the last one, every lane of a half beyond the rows — reads element 0 of the
+  // actuator weights with stride 0 instead, a table every launch has: the loads need no branch, and what such a lane computes
+  // is never looked at
+  const float* __restrict__ x = A.q;
+  int stride = 0;
+  if (act) { x = A.cand + (size_t)(A.row0 + b % A.N) * (size_t)(A.H * A.Nu) + lane; stride = A.Nu; }
+  if (weighs) { x = A.rewss + (size_t)b * A.H; stride = 1; }
+  const float* __restrict__ yb = lazy ? A.ybar + lane : A.q;
+  const int ystride = lazy ? A.Nu : 0;
+  const float* __restrict__ w = A.w ? A.w : A.q;  // (uniform; without row weights acc is not looked at)
+  const int wstride = A.w ? 1 : 0;
+  bool have = act && A.prev;
+  float up = have ? A.prev[lane] : 0.0f, eff = 0.0f, rat = 0.0f, acc = 0.0f;
+#pragma unroll 4
+  for (int h = 0; h < A.H; ++h) {
+    const float v = x[h * stride];
+    objective_column_step(objective_value(v, lazy, A.sigma, yb[h * ystride]), up, have, eff, rat);
+    acc = objective_ret_step(acc, w[h * wstride], v);
+  }
+  const float term = act ? objective_term(A.q[lane], A.effort, eff, A.rate, rat) : 0.0f;
+  float c = 0.0f;
+  if (A.costs) {  // (uniform)
+    for (int a = 0; a < A.Nu; ++a) c = c + __shfl(term, a, kObjLanes);
+    c = c / (float)A.H;
+  }
+  if (last) {
+    const float ret = A.w ? acc / A.wsum : A.rews[b];
+    A.rews[b] = A.costs ? ret - c : ret;
+    A.ret_keep[b] = ret;
+    if (b < A.N) A.cost_keep[b] = c;
+  }
+}
+static __global__ __launch_bounds__(kObjThreads) void objective_kernel(ObjectiveArgs A) { objective_body(A); }
+// ... and for the P plans of a sweep, blockIdx.y = plan: plan k's N rows, candidates, results and previous action lie N rows,
+// N candidates and Nu floats from plan 0's, its Ybar_i ybar_stride floats from plan 0's; B = N
+static __global__ __launch_bounds__(kObjThreads) void objective_batch_kernel(ObjectiveArgs A, long long ybar_stride) {
+  const long long k = blockIdx.y;
+  A.rewss += k * A.N * A.H; A.rews += k * A.N; A.cand += k * A.N * (long long)(A.H * A.Nu);
+  if (A.ybar) A.ybar += k * ybar_stride;
+  if (A.prev) A.prev += k * A.Nu;
+  A.ret_keep += k * A.N; A.cost_keep += k * A.N;
+  objective_body(A);
+}
+inline unsigned objective_blocks(int B) { return (unsigned)((B + kObjThreads / kObjLanes - 1) / (kObjThreads / kObjLanes)); }
+// The previous action of the NEXT tick of an episode or a session, one launch per tick in front of the boundary kernel:
+// prev[k][a] = clip(src[k][a], -1, 1), src = row E-1 of episode k's mean M_t (src_stride floats from episode 0's) — or, in front
+// of the first tick of an episode with a delay record, the last row of its committed queue.  blockIdx.y = episode.
+static __global__ __launch_bounds__(64) void objective_prev_kernel(const float* __restrict__ src, long long src_stride, int Nu,
+                                                             float* __restrict__ prev) {
+  const int a = threadIdx.x;
+  if (a < Nu) prev[(long long)blockIdx.y * Nu + a] = fclip(src[(long long)blockIdx.y * src_stride + a], -1.0f, 1.0f);
+}
+
 // Sweeps of path-integral plans (mbd_sweep_*, update_method != 0): the small kernels of the update rules take blockIdx.y
 // = plan and these strides (in elements) from plan 0's data; a single plan launches them with one row and zero strides.
 struct PiBatch {

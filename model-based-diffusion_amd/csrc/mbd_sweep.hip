@@ -101,6 +101,8 @@ struct mbd_sweep {
   }
   NoiseSpec noise_always() const { return noise_spec(false); }
   NoiseSpec noise_warm() const { return noise_spec(true); }
+  // the objective record of all the sweep's plans (mbd_sweep_set_objective): a plan's, with every plan's previous action [P][Nu]
+  ObjectiveRec obj;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_sweep_mpc_open): it uses the batch's buffers above — slice 0 of d_mpc_states for
   // the states handed in, slice 0 of d_mpc_pred, d_mpc_queue, d_mpc_ybar — so a handle runs batches or a session, not both
@@ -257,6 +259,8 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
   const int sw[3] = {N, S, 0};
   MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, nullptr, s, nullptr, sw));
   MBD_TRY(w->timing.end(s));
+  // the objective record: one launch over the P N rows (blockIdx.y = plan) on the materialised candidates
+  if (w->obj.has) MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_Y0s, false, 0.0f, nullptr, 0, s));
   pb.mu = mu_stride;
   if (c.update_method == 3) {  // cem_update (path_integral.py:48-52)
     const int K = N < 10 ? N : 10;
@@ -406,6 +410,10 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
                          fused_lp ? w->d_lp.get() : nullptr, nullptr, st.xref));
   MBD_TRY(w->timing.end(s));
   if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, w->d_xpos, P * N, H, w->d_lp, s, st.xref));
+  // the objective record: one launch over the P N rows (blockIdx.y = plan) between the rollout and the score.  The ring needs no
+  // change: the launch reads eps[cur] on the steps' stream in front of the weighted mean, which is the buffer's last reader.
+  if (w->obj.has)
+    MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_eps[cur], true, w->sigmas[i], st.ybar_in, st.ybar_in_stride, s));
   ScoreBatch sb;
   sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)N * HNu;
   sb.ybar_in = st.ybar_in_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
@@ -487,6 +495,20 @@ extern "C" int mbd_sweep_set_noise_basis(mbd_sweep* w, const mbd_noise_basis* re
   w->basis_when = rec->when;
   w->has_basis = true;
   return MBD_OK;
+}
+
+// one objective record for all plans of the sweep (include/mbd_hip.h mbd_objective), as mbd_plan_set_objective
+extern "C" int mbd_sweep_set_objective(mbd_sweep* w, const mbd_objective* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  NO_SWEEP_SESSION(w, "set_objective");
+  float wsum = 0.0f;
+  if (rec) MBD_TRY(check_objective(rec, w->cfg.Hsample, w->Nu, &wsum));  // (before any device access)
+  return w->obj.set(rec, wsum, w->env->device, w->P, w->cfg.Nsample, w->cfg.Hsample, w->Nu, (size_t)w->cfg.Nsample);
+}
+
+extern "C" int mbd_sweep_peek_objective(mbd_sweep* w, int k, float* ret_out, float* cost_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  return w->obj.peek(w->env, k, ret_out, cost_out, "sweep");
 }
 
 extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant* rec) {
@@ -623,6 +645,12 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     MBD_TRY(w->delay.upload(w->d_mpc_queue, P, E, Nu, s));
     w->delay.pred_ticks = 0;
   }
+  // with an objective record: every episode's previous action of tick 0 (mbd_plan_run_mpc), and the episodes' slot to the call's end
+  MBD_TRY(w->obj.episode_start(has_delay ? w->d_mpc_queue + (Q - Nu) : nullptr, Q, s));
+  struct ObjEpisode {
+    ObjectiveRec& o;
+    ~ObjEpisode() { o.episode_end(); }
+  } obj_episode{w->obj};
   HIP_TRY(hipStreamSynchronize(s));
   progress_reset(w->h_progress);
   const auto t0 = std::chrono::steady_clock::now();
@@ -699,6 +727,8 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     // (with a delay record the rows executed are the queues' heads: into the tick's slice of their log, which the rollout
     // reads — unless plant records form the disturbed rows there themselves)
     float* rows_t = any_plant || has_delay ? w->d_mpc_actions + (size_t)t * P * EN : nullptr;
+    // (in front of it, with an objective record: the next tick's previous actions, clip(M_{.,t}[E-1]), one launch)
+    MBD_TRY(w->obj.tick_advance(w->d_mu + (size_t)(Nd - 2) * HNu + (size_t)(E - 1) * Nu, mu_stride, s));
     if (has_delay)
       hipLaunchKernelGGL(mpc_boundary_delay_batch_kernel, dim3(1, (unsigned)P), dim3(256), 0, s,
                          (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, HNu, EN, w->d_mpc_ybar,
@@ -851,6 +881,9 @@ extern "C" int mbd_sweep_mpc_open(mbd_sweep* w, const mbd_mpc_config* mc, const 
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(w->aux));
   if (w->demo.has) MBD_TRY(w->demo.session_start());
+  // an objective record's previous actions of the first tick and the session's slot until close: behind everything else that can
+  // fail (a failed open leaves prev as it was); the launch is stream-ordered in front of the first tick
+  MBD_TRY(w->obj.episode_start(w->delay.has ? w->d_mpc_queue + (Q - w->Nu) : nullptr, Q, s));
   // (nothing fails from here on: the bookkeeping of the previous batch's logs goes last)
   if (w->delay.has) w->delay.pred_ticks = 0;  // (mbd_sweep_peek_mpc_predicted does not serve sessions)
   ss.mc = *mc;
@@ -937,6 +970,8 @@ extern "C" int mbd_sweep_mpc_submit(mbd_sweep* w, const float* states) {
     st.rew_xref = w->demo.has ? w->demo.rew_xref : e->rew_xref;
     MBD_TRY(sweep_step(w, st));
   }
+  // the next tick's previous actions (an objective record) in FRONT of the boundary, which stays the tick's last kernel
+  MBD_TRY(w->obj.tick_advance(w->d_mu + (size_t)(Nd - 2) * HNu + (size_t)(E - 1) * w->Nu, mu_stride, s));
   hipLaunchKernelGGL(mpc_session_boundary_batch_kernel, dim3(1, (unsigned)P), dim3(256), 0, s,
                      (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, HNu, EN, w->d_mpc_ybar.get(), q_in, q_out, Q,
                      has_delay ? (const float*)w->d_mpc_pred : (const float*)nullptr, S, (const float*)(w->d_rewmeans + (Nd - 2)), Nd - 1,
@@ -1003,6 +1038,7 @@ extern "C" int mbd_sweep_mpc_close(mbd_sweep* w) {
   if (ss.in_flight) HIP_TRY(hipStreamSynchronize(w->stream));  // (its last kernel writes the mailbox)
   ss.in_flight = false;
   ss.open = false;
+  w->obj.episode_end();
   ss.stage.release();
   ss.mailbox.release();
   return MBD_OK;

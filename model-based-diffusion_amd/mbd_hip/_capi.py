@@ -99,6 +99,13 @@ class MpcSigma(C.Structure):
     _fields_ = [("sigma_cold", C.c_float), ("sigma_warm", C.c_float), ("gain", C.c_float), ("reserved", C.c_int32 * 5)]
 
 
+class Objective(C.Structure):
+    """mbd_objective (include/mbd_hip.h): the row weights, the actuator weights, the effort and rate costs a plan's rewards are
+    shaped by, and the action executed before the first plan's row 0."""
+    _fields_ = [("row_weight", C.POINTER(C.c_float)), ("act_weight", C.POINTER(C.c_float)), ("prev0", C.POINTER(C.c_float)),
+                ("effort", C.c_float), ("rate", C.c_float), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 TICK_ROWS_NONFINITE, TICK_STATE_NONFINITE, TICK_COLD = 1, 2, 4
 
 
@@ -115,6 +122,7 @@ EXPORTS = [
     "mbd_env_step", "mbd_env_rew_xref", "mbd_env_rollout", "mbd_plan_create", "mbd_plan_destroy",
     "mbd_plan_schedule", "mbd_plan_set_state0", "mbd_plan_sample_rollout", "mbd_plan_prefetch_noise", "mbd_plan_score_update",
     "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_set_mpc_delay", "mbd_plan_peek_mpc_predicted", "mbd_plan_set_mpc_demo", "mbd_plan_peek_mpc_track", "mbd_plan_set_mpc_sigma", "mbd_plan_peek_mpc_sigma",
+    "mbd_plan_set_objective", "mbd_plan_peek_objective", "mbd_sweep_set_objective", "mbd_sweep_peek_objective",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
@@ -193,6 +201,10 @@ def load() -> C.CDLL:
     lib.mbd_plan_peek_mpc_track.argtypes = [_vp, _vp, _vp]
     lib.mbd_plan_set_mpc_sigma.argtypes = [_vp, C.POINTER(MpcSigma)]
     lib.mbd_plan_peek_mpc_sigma.argtypes = [_vp, _vp]
+    lib.mbd_plan_set_objective.argtypes = [_vp, C.POINTER(Objective)]
+    lib.mbd_plan_peek_objective.argtypes = [_vp, _vp, _vp]
+    lib.mbd_sweep_set_objective.argtypes = [_vp, C.POINTER(Objective)]
+    lib.mbd_sweep_peek_objective.argtypes = [_vp, _i, _vp, _vp]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
     lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
     lib.mbd_plan_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(MpcTickInfo)]
@@ -329,6 +341,40 @@ def debug_check_mpc_sigma(rec: "MpcSigma", update_method: int) -> int:
     lib = load()
     lib.mbd_debug_check_mpc_sigma.argtypes = [C.POINTER(MpcSigma), _i]
     return lib.mbd_debug_check_mpc_sigma(C.byref(rec), int(update_method))
+
+
+def debug_check_objective(rec: "Objective", Hsample: int, action_size: int) -> int:
+    """include/mbd_hip_debug.h: the refusals an objective record alone decides, for a handle of that Hsample and action_size — no
+    device needed.  Returns the code (the message: ``load().mbd_last_error()``)."""
+    lib = load()
+    lib.mbd_debug_check_objective.argtypes = [C.POINTER(Objective), _i, _i]
+    return lib.mbd_debug_check_objective(C.byref(rec), int(Hsample), int(action_size))
+
+
+def debug_objective_host(rewss, rews, cand, w=None, q=None, effort: float = 0.0, rate: float = 0.0, prev=None, lazy=None):
+    """include/mbd_hip_debug.h: objective_kernel's arithmetic run on the host (no device).  ``rewss`` [B, H], ``rews`` [B],
+    ``cand`` [N, H, Nu] (row b is candidate b % N), ``w`` [H] or None, ``q`` [Nu] or None (ones), ``prev`` [Nu] (clipped) or None;
+    ``lazy`` None: cand holds values, else (sigma, ybar [H, Nu]): it holds normals.  Returns (rews_out [B], ret [B], cost [min(B, N)])."""
+    lib = load()
+    lib.mbd_debug_objective_host.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp, _i, _f, _vp, _vp, _f, _vp, _f, _f, _vp, _vp, _vp, _vp]
+    f32 = lambda x: np.ascontiguousarray(x, np.float32)
+    rewss, rews, cand = f32(rewss), f32(rews), f32(cand)
+    B, H = rewss.shape
+    N, _, Nu = cand.shape
+    wsum = np.float32(0)
+    if w is not None:
+        w = f32(w)
+        for x in w:  # the f32 left-to-right sum the set call forms
+            wsum = np.float32(wsum + x)
+    q = np.ones(Nu, np.float32) if q is None else f32(q)
+    prev = None if prev is None else f32(prev)
+    sigma, ybar = (0.0, None) if lazy is None else (float(lazy[0]), f32(lazy[1]))
+    out, ret, cost = np.full(B, np.nan, np.float32), np.full(B, np.nan, np.float32), np.full(min(B, N), np.nan, np.float32)
+    opt = lambda a: None if a is None else np_ptr(a)
+    check(lib.mbd_debug_objective_host(np_ptr(rewss), np_ptr(rews), B, N, H, Nu, np_ptr(cand), int(lazy is not None), sigma, opt(ybar),
+                                       opt(w), float(wsum), np_ptr(q), float(effort), float(rate), opt(prev), np_ptr(out), np_ptr(ret),
+                                       np_ptr(cost)))
+    return out, ret, cost
 
 
 def debug_math_ops() -> list:

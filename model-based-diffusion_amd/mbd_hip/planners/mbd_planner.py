@@ -202,6 +202,23 @@ class Sweep:
         _capi.check(self.lib.mbd_sweep_set_noise_basis(self.h, C.byref(rec)))
         del keep  # (the set call has copied the table)
 
+    def set_objective(self, row_weight=None, effort: float = 0.0, rate: float = 0.0, act_weight=None, prev0=None):
+        """One objective record for all plans of the sweep (``Plan.set_objective``; ``prev0`` is every plan's): plan k of ``run``,
+        episode k of ``run_mpc`` and of a session is then the single plan's with the same record, bit for bit."""
+        rec, keep = _objective_record(row_weight, effort, rate, act_weight, prev0, self.H, self.Nu)
+        _capi.check(self.lib.mbd_sweep_set_objective(self.h, C.byref(rec)))
+        del keep  # (the set call has copied the tables)
+
+    def clear_objective(self):
+        _capi.check(self.lib.mbd_sweep_set_objective(self.h, None))
+
+    def peek_objective(self, k: int):
+        """Plan k's ``ret`` [N] and ``cost`` [N] of the last step (a sweep with an objective record)."""
+        N = self.cfg.Nsample
+        ret, cost = np.zeros(N, np.float32), np.zeros(N, np.float32)
+        _capi.check(self.lib.mbd_sweep_peek_objective(self.h, int(k), _capi.np_ptr(ret), _capi.np_ptr(cost)))
+        return ret, cost
+
     def set_mpc_delay(self, ticks: int, rows0=None):
         """One delay record for all episodes of the sweep (``Plan.set_mpc_delay``): episode k of ``run_mpc`` is then
         ``Plan.run_mpc`` with the same record, bit for bit; ``run_mpc`` also returns ``predicted`` [P, T, state_size]."""
@@ -312,6 +329,25 @@ def _basis_record(W, when, H):
     rec.basis = W.ctypes.data_as(C.POINTER(C.c_float))
     rec.n_knots, rec.when = W.shape[1], _capi.NOISE_WHEN[when]
     return rec, W
+
+
+def _objective_record(row_weight, effort, rate, act_weight, prev0, H, Nu):
+    """The mbd_objective of ``set_objective``'s arguments, and the float32 arrays its pointers read (tables of another length
+    or with refused values go to the library, which names the field)."""
+    rec = _capi.Objective()
+    keep = []
+    for field, x in (("row_weight", row_weight), ("act_weight", act_weight), ("prev0", prev0)):
+        if x is not None:
+            a = np.ascontiguousarray(x, np.float32).reshape(-1)
+            setattr(rec, field, a.ctypes.data_as(C.POINTER(C.c_float)))
+            keep.append(a)
+    rec.effort, rec.rate = float(effort), float(rate)
+    rec.rows = H if row_weight is None else keep[0].size
+    rec.cols = Nu
+    for x in (act_weight, prev0):
+        if x is not None:
+            rec.cols = int(np.size(x))
+    return rec, keep
 
 
 def _ensemble_record(envs, risk):
@@ -626,6 +662,30 @@ class Plan:
         rec, keep = _basis_record(W, when, self.H)
         _capi.check(self.lib.mbd_plan_set_noise_basis(self.h, C.byref(rec)))
         del keep  # (the set call has copied the table)
+
+    def set_objective(self, row_weight=None, effort: float = 0.0, rate: float = 0.0, act_weight=None, prev0=None):
+        """Shape what the plan maximises (include/mbd_hip.h mbd_objective): a candidate's reward becomes
+        sum_h w[h] r[h] / sum(w) - (1 / H) sum_a q[a] (effort * sum_h u^2 + rate * sum_h (u[h] - u[h-1])^2) with ``row_weight`` w
+        [H] (None: the plain mean; ``mpc.discount_weights`` builds a discount with a terminal weight), ``act_weight`` q [Nu] (None:
+        ones) and u[-1] the action executed before the plan begins — ``prev0`` [Nu] (None: the first term is left out) for
+        ``run`` and the first tick of an episode, the last committed row afterwards.  Every call that samples reads it;
+        ``eval``, the final reward and an episode's reward log keep the env's own rewards."""
+        rec, keep = _objective_record(row_weight, effort, rate, act_weight, prev0, self.H, self.Nu)
+        _capi.check(self.lib.mbd_plan_set_objective(self.h, C.byref(rec)))
+        del keep  # (the set call has copied the tables)
+
+    def clear_objective(self):
+        _capi.check(self.lib.mbd_plan_set_objective(self.h, None))
+
+    def peek_objective(self):
+        """The last step's ``ret`` [shard_count] ([M, N] under an ensemble record) and ``cost`` [shard_count] (a plan with an
+        objective record)."""
+        M = len(self._ens_envs or ())
+        sh = self.cfg.shard_count
+        ret = np.zeros((M, sh) if M else sh, np.float32)
+        cost = np.zeros(sh, np.float32)
+        _capi.check(self.lib.mbd_plan_peek_objective(self.h, _capi.np_ptr(ret), _capi.np_ptr(cost)))
+        return ret, cost
 
     def peek_ensemble(self):
         """The last step's per-member rewards [M, N] and combined rewards [N] (a plan with an ensemble record)."""

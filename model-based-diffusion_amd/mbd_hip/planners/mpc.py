@@ -54,6 +54,16 @@ with every plant, ensemble and noise flag; the saved episode then carries the pr
 
     python -m mbd_hip.planners.mpc --env_name humanoidrun --warm_steps 20 --delay_ticks 1 --plant_mass 1.3
 
+Every plan maximises the unweighted mean of the env's per-step rewards.  An objective record (include/mbd_hip.h mbd_objective;
+DESIGN.md section 1 "N13 objective") shapes that: ``--discount G --terminal_weight W`` weigh horizon row h by G ** h and the last
+row W times that (``discount_weights``); ``--effort_cost L`` and ``--rate_cost L`` subtract the controller's own costs on a
+candidate's squared actions and on its squared step-to-step differences, the first difference taken against the last row the
+previous tick committed — what keeps a replanning sampler from chattering; ``--act_weight FILE.npy`` weighs the two costs per
+actuator.  With any of them the report gains ``action_rate``, the executed rows' mean squared step-to-step difference.  The
+episode's rewards stay the env's own.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --discount 0.98 --rate_cost 0.1
+
 A demo plan (``--enable_demo``) compares its 50 planned steps with the env's 50 demo rows; in an episode the demo has to move
 with the system.  ``--demo_clip env|FILE.npy`` (include/mbd_hip.h mbd_mpc_demo; DESIGN.md section 1 "N10 demo clock") sets the
 clip the episode follows — the env's own demo, or an array [n_track, L, 3] (car2d: [L, 2]) — and ``--demo_start c0`` the clip
@@ -136,6 +146,11 @@ class MpcArgs(Args):
     sigma_cold: float = 1.0  # path-integral methods: the sampling sigma tick 0 starts from (1.0: path_integral.py:131) ...
     sigma_warm: float = 1.0  # ... and every later tick,
     sigma_gain: float = 0.0  # or with G > 0 (cma-es only) clamp(G * the sigma the last tick ended with, sigma_warm, sigma_cold)
+    discount: float = 1.0  # gamma: horizon row h of a plan weighs gamma ** h in what the plan maximises (discount_weights) ...
+    terminal_weight: float = 1.0  # ... and the last row this many times that
+    effort_cost: float = 0.0  # lambda_u: the controller's own cost on sum_h u^2 of a candidate (mbd_objective) ...
+    rate_cost: float = 0.0  # ... lambda_du on sum_h (u_h - u_{h-1})^2, u_{-1} the last row committed before the plan begins
+    act_weight: str = ""  # FILE.npy: the two costs' weights per actuator [Nu]
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -265,6 +280,46 @@ def _basis_of(args: MpcArgs):
 
 def _basis_settings(args: MpcArgs) -> dict:
     return {f: getattr(args, f) for f in _BASIS_FIELDS}
+
+
+_OBJECTIVE_FIELDS = ("discount", "terminal_weight", "effort_cost", "rate_cost", "act_weight")
+
+
+def discount_weights(H: int, gamma: float, terminal: float = 1.0) -> np.ndarray:
+    """The row weights [H] of a discounted objective (include/mbd_hip.h mbd_objective.row_weight): w[h] = gamma ** h, the last row
+    multiplied by ``terminal`` (it stands for everything behind the horizon) — in float64, rounded once to float32."""
+    H = int(H)
+    if H < 1:
+        raise ValueError(f"Hsample={H}: must be >= 1")
+    if not (np.isfinite(gamma) and gamma >= 0):
+        raise ValueError(f"discount={gamma!r}: must be finite and >= 0")
+    if not (np.isfinite(terminal) and terminal >= 0):
+        raise ValueError(f"terminal_weight={terminal!r}: must be finite and >= 0")
+    w = np.float64(gamma) ** np.arange(H, dtype=np.float64)
+    w[-1] *= np.float64(terminal)
+    return np.ascontiguousarray(w.astype(np.float32))
+
+
+def action_rate(actions) -> float:
+    """The executed rows' mean squared step-to-step difference, mean over steps and actuators of (u_n - u_{n-1})^2 (float64)."""
+    a = np.asarray(actions, np.float64)
+    return float(np.mean(np.diff(a, axis=-2) ** 2)) if a.shape[-2] > 1 else 0.0
+
+
+def _has_objective(args: MpcArgs) -> bool:
+    """Whether any objective flag differs from its default (then, and only then, the plan gets a record)."""
+    return any(getattr(args, f) != MpcArgs.__dataclass_fields__[f].default for f in _OBJECTIVE_FIELDS)
+
+
+def _objective_of(args: MpcArgs) -> dict:
+    """``Plan.set_objective``'s arguments: the row weights only where a discount or a terminal weight is asked for."""
+    weighted = args.discount != 1.0 or args.terminal_weight != 1.0
+    return dict(row_weight=discount_weights(args.Hsample, args.discount, args.terminal_weight) if weighted else None,
+                effort=args.effort_cost, rate=args.rate_cost, act_weight=np.load(args.act_weight) if args.act_weight else None)
+
+
+def _objective_settings(args: MpcArgs) -> dict:
+    return {f: getattr(args, f) for f in _OBJECTIVE_FIELDS} if _has_objective(args) else {}
 
 
 def _has_delay(args: MpcArgs) -> bool:
@@ -409,6 +464,8 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
         plan.set_mpc_delay(args.delay_ticks)
     if _has_demo(args):
         plan.set_mpc_demo(*_demo_of(env, args))
+    if _has_objective(args):
+        plan.set_objective(**_objective_of(args))
     return env, plan, state_init, rng_exp
 
 
@@ -512,6 +569,8 @@ def _setup_batch(arg_list, device: int):
         sweep.set_mpc_delay(a0.delay_ticks)
     if _has_demo(a0):  # (one clip and one clock)
         sweep.set_mpc_demo(*_demo_of(env, a0))
+    if _has_objective(a0):  # (and one objective)
+        sweep.set_objective(**_objective_of(a0))
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -547,7 +606,8 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
         shape = _shape_settings(arg_list[0]) if _has_shape(arg_list[0]) else {}
         if _has_basis(arg_list[0]):
             shape = dict(shape, **_basis_settings(arg_list[0]))
-        shape = dict(shape, **_delay_settings(arg_list[0]), **_demo_settings(arg_list[0]), **_sigma_settings(arg_list[0]))
+        shape = dict(shape, **_delay_settings(arg_list[0]), **_demo_settings(arg_list[0]), **_sigma_settings(arg_list[0]),
+                     **_objective_settings(arg_list[0]))
         windows = {"demo_windows": ep["demo_windows"]} if "demo_windows" in ep else {}  # (one table: every episode's)
         return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, **windows, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
                               **_plant_settings(arg_list[k]), **shape) for k in range(len(arg_list))]
@@ -585,7 +645,7 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         shape = _shape_settings(args) if _has_shape(args) else {}
         if _has_basis(args):
             shape = dict(shape, **_basis_settings(args))
-        shape = dict(shape, **_delay_settings(args), **_demo_settings(args), **_sigma_settings(args))
+        shape = dict(shape, **_delay_settings(args), **_demo_settings(args), **_sigma_settings(args), **_objective_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -653,6 +713,8 @@ def _main(argv=None) -> dict:
         res.update(_basis_settings(args))
     res.update(_delay_settings(args))  # (without a record the line is what it always was)
     res.update(_sigma_settings(args))
+    if _has_objective(args):  # (the executed rows' mean squared step-to-step difference, from actions_out on the host)
+        res.update(_objective_settings(args), action_rate=action_rate(ep["actions"]))
     if _has_demo(args):
         res.update(_demo_settings(args), track_err_mean=float(ep["track_err"].mean()))
     if not args.not_render:
@@ -685,6 +747,8 @@ def _main_online(args: MpcArgs) -> dict:
         res.update(_plant_settings(args))
     res.update(_delay_settings(args))
     res.update(_sigma_settings(args))
+    if _has_objective(args):
+        res.update(_objective_settings(args), action_rate=action_rate(ep["actions"]))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -728,6 +792,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
             plan.set_mpc_delay(a0.delay_ticks)
         if _has_demo(a0):
             plan.set_mpc_demo(*_demo_of(env, a0))
+        if _has_objective(a0):
+            plan.set_objective(**_objective_of(a0))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -754,6 +820,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
         res.update(_basis_settings(a0))
     res.update(_delay_settings(a0))
     res.update(_sigma_settings(a0))
+    if _has_objective(a0):
+        res.update(_objective_settings(a0), action_rate=action_rate(ep["actions"]))
     if _has_demo(a0):
         res.update(_demo_settings(a0), track_err_mean=float(ep["track_err"].mean()))
     if not a0.not_render:
