@@ -18,6 +18,9 @@
  * replanned rows from chattering; the command the system is executing when the session opens goes in as prev0 — here zeros, the
  * actuators at rest; on a robot, its current command — and from then on the library carries the last committed row itself.
  *
+ * Every plan carries a weighting record (mbd_weighting) with rejection on: this is the example of driving a real system, and one
+ * diverged candidate must not poison the plan.
+ *
  * Prints one line per tick: "tick T reward R ms M flags F", then "mean_reward R ms_per_tick M". */
 #include <math.h>
 #include <stdio.h>
@@ -85,6 +88,14 @@ int main(int argc, char** argv) {
     obj.prev0 = command;
     obj.rows = H; obj.cols = Nu;
     CHECK(mbd_plan_set_objective(plan, &obj));
+  }
+  { /* a real system can leave the model's well-behaved region: a candidate whose rollout diverges (a NaN or infinite reward) is
+     * left out of every step's weights instead of turning the whole plan into NaN.  With nothing dropped the plan's bits are
+     * unchanged.  (ess_frac > 0 with a bracket would also choose every step's temperature by the effective sample size.) */
+    mbd_weighting wt;
+    memset(&wt, 0, sizeof(wt));
+    wt.reject_nonfinite = 1;
+    CHECK(mbd_plan_set_weighting(plan, &wt));
   }
   if (D > 0) { /* plans arrive D ticks late; the system starts committed to zeros */
     mbd_mpc_delay delay;

@@ -658,6 +658,65 @@ int mbd_plan_set_objective(mbd_plan* plan, const mbd_objective* rec);
  * before a step has run with one. */
 int mbd_plan_peek_objective(mbd_plan* plan, float* ret_out, float* cost_out);
 
+/* ---- weighting: how a step turns the candidates' rewards into weights (no counterpart in the reference, whose softmax runs at
+ * the configured temp_sample over all Nsample rewards, mbd_planner.py:110-127; DESIGN.md section 1 "N14 weighting") ---- */
+/* A weighting record is a setting of a plan (of a sweep) beside the objective, ensemble and noise records.  It does two things to
+ * the score of every diffusion step: candidates whose reward is not finite are left out — a diverged candidate no longer turns the
+ * whole plan's mean into NaN —, and the temperature of the softmax can be chosen per step so that the effective sample size
+ * ESS = (sum w)^2 / sum w^2 of the weights meets a target fraction of the candidates kept. */
+typedef struct mbd_weighting {
+  int32_t reject_nonfinite; /* 0 / 1: candidates whose reward is NaN or +-inf get weight +0 and leave the statistics */
+  float   ess_frac;         /* 0: keep the plan's temperature; in (0, 1]: choose it so that ESS ~= ess_frac * kept  */
+  float   temp_min, temp_max; /* the bracket when ess_frac > 0: finite, 0 < temp_min <= temp_max                    */
+  int32_t iters;            /* bisection steps, 1..32 (ess_frac > 0)                                                */
+  int32_t reserved[6];      /* must be 0 */
+} mbd_weighting;
+/* With a record in force the score of a step is — f32 throughout, every operation rounded; r [N] is the rewards buffer as the score
+ * receives it (behind the objective and ensemble records, whose NaN it then drops), T0 the plan's temp_sample (plan k's temperature
+ * in a sweep); sumB and maxB are the score's block reductions (thread t of 1024 takes i = t, t + 1024, ... ascending, a xor-
+ * butterfly over the 64 lanes, the 16 wavefront values combined in order); a dropped entry takes part as +0 in a sum and -inf in a
+ * max, positions never move:
+ *   keep[n] = !reject_nonfinite || isfinite(r[n]);   kept = count (integer)
+ *   mean = sumB(r) / float(kept);   sd = sqrt(sumB((r - mean)^2) / float(kept));   sd < 1e-4 -> 1   (every update method)
+ *          (the squared deviations accumulate as the score without a record accumulates them: acc = fma(d, d, acc))
+ *   z[n] = (r[n] - mean) / sd;   zmax = (maxB(r) - mean) / sd
+ *   E(T): e[n] = exp_((z[n] / T) - (zmax / T));  S1 = sumB(e);  S2 = sumB(e * e);  ess = (S1 * S1) / S2
+ *   ess_frac == 0:  T* = T0
+ *   else: target = ess_frac * float(kept)
+ *         if !(ess(temp_min) < target) T* = temp_min
+ *         else if !(ess(temp_max) > target) T* = temp_max
+ *         else lo, hi = temp_min, temp_max; iters times: mid = sqrt(lo * hi); ess(mid) < target ? lo = mid : hi = mid;   T* = hi
+ *   w[n] = e[n] / S1 at T*, dropped: +0;   rew_mean out = mean;   log: T*, ess(T*), kept
+ *   kept == 0: every weight +0 (the new mean is then all zeros, or what the literal score form makes of them), rew_mean NaN,
+ *              log T0, 0, 0
+ * Two consequences.  With ess_frac == 0, no reward dropped and sd >= 1e-4 the step has the bits of the step without a record: the
+ * three operations ((r - mean) / sd) / T and the maximum through the largest reward are the existing ones.  ESS lies in [1, kept],
+ * because the maximal entry has e = exp_(0) = 1, and nothing overflows — as long as z / T itself is finite: z is a standardised reward,
+ * at most sqrt(kept) in size, so any temp_min above 1e-30 is safe; the set call does not refuse a smaller one, under which zmax / T
+ * overflows, the maximal entry becomes inf - inf and the step's weights NaN.  Everything downstream is untouched and consumes these weights: the
+ * weighted mean, the score update, cma-es' spread and sigma, cem's selection — a dropped candidate's +0 sorts below every positive
+ * weight.
+ * Under a record a step gains at most one launch: the weigh kernel stands where the score kernel stands and the step takes the
+ * kernels that consume given weights (the ones MBD_NO_FUSED_SCORE=1 selects; sweeps: the batch weighted mean in its weights-given
+ * form).  No record, or a cleared one: every call keeps its launches and its bits.
+ * Every mode takes the record — all four update methods, lazy and materialised candidates, plans with an ensemble, objective,
+ * plant, delay, sigma, noise-shape or noise-basis record, sharded plans (every rank scores all N gathered rewards through
+ * mbd_plan_score_update and sets the same record), sweeps (one record for all plans), episodes and both kinds of session (read at
+ * open) — except a plan created with enable_demo: the demo blend re-standardises and applies the temperature twice, and what an
+ * ESS target should mean there is out of scope: MBD_ERR_UNSUPPORTED.
+ * The set call is synchronous (it waits for the device) and is to be called between diffusion steps; rec == NULL clears.  Refused
+ * with MBD_ERR_INVALID before any device access, the message naming the field: a NULL handle, non-zero reserved,
+ * reject_nonfinite outside {0, 1}, ess_frac outside [0, 1] or non-finite, and with ess_frac > 0 a bracket that is not finite with
+ * 0 < temp_min <= temp_max, or iters outside 1..32.  MBD_ERR_STATE while a session is open on the handle. */
+int mbd_plan_set_weighting(mbd_plan* plan, const mbd_weighting* rec);
+/* The log of the record's score steps (HOST; any of the three may be NULL; synchronises the device): the temperature used, the
+ * ESS at that temperature and the kept count of every score step of the last mbd_plan_run (Ndiffuse - 1 entries), the last
+ * mbd_plan_reverse_once or mbd_plan_score_update (1), or the last tick of an episode or session (warm_steps of a warm tick,
+ * Ndiffuse - 1 of a cold one), in the order the steps ran.  The log lives on the device and the weigh kernel writes it: nothing is
+ * read by the host inside a loop.  *count_out: the entries there are; at most `capacity` are copied.  MBD_ERR_STATE without a
+ * record. */
+int mbd_plan_peek_weighting(mbd_plan* plan, float* temp_out, float* ess_out, int32_t* kept_out, int capacity, int* count_out);
+
 /* ---- planning ahead of the plant: an episode whose plans take D ticks to arrive (the real-time iteration scheme; no
  * counterpart in the reference; DESIGN.md section 1 "N9 delay") ---- */
 /* The episode of mbd_plan_run_mpc plans from s_t and executes that plan's first rows from the same s_t: planning takes no time.
@@ -881,6 +940,12 @@ int mbd_sweep_set_objective(mbd_sweep* sweep, const mbd_objective* rec);
 /* plan k's ret_out [Nsample] and cost_out [Nsample] of the last step; as mbd_plan_peek_objective; k outside [0, n_plans) ->
  * MBD_ERR_INVALID */
 int mbd_sweep_peek_objective(mbd_sweep* sweep, int k, float* ret_out, float* cost_out);
+/* one weighting record (mbd_weighting, above) for all plans of the sweep, T0 being each plan's own temperature: plan k of
+ * mbd_sweep_run, episode k of mbd_sweep_run_mpc and of a sweep's session equal the single plan with that record and temps[k], bit
+ * for bit.  Refusals as mbd_plan_set_weighting's. */
+int mbd_sweep_set_weighting(mbd_sweep* sweep, const mbd_weighting* rec);
+/* plan k's log of the last run or the last tick; as mbd_plan_peek_weighting; k outside [0, n_plans) -> MBD_ERR_INVALID */
+int mbd_sweep_peek_weighting(mbd_sweep* sweep, int k, float* temp_out, float* ess_out, int32_t* kept_out, int capacity, int* count_out);
 /* one delay record (mbd_mpc_delay, above) for all episodes of the sweep: episode k of mbd_sweep_run_mpc is then
  * mbd_plan_run_mpc on a plan of its own with the same record, bit for bit, whatever the other episodes do.  The prediction is
  * ONE rollout launch over the n_plans episodes, one candidate each, and the n_plans * Nsample planning candidates start from

@@ -71,6 +71,14 @@ int mbd_debug_check_objective(const mbd_objective* rec, int Hsample, int action_
 int mbd_debug_objective_host(const float* rewss, const float* rews, int B, int N, int H, int Nu, const float* cand, int lazy,
                              float sigma, const float* ybar, const float* w, float wsum, const float* q, float effort, float rate,
                              const float* prev, float* rews_out, float* ret_out, float* cost_out);
+/* weigh_kernel's arithmetic on the HOST (include/mbd_hip.h mbd_weighting): the per-entry functions and the temperature selection
+ * the kernel calls (one text for host and device), with the block reductions restated as loops over the 1024 virtual threads, their
+ * 64-lane butterflies and the 16 wavefront values in order; no device touched.  HOST rews [N]; temp: T0; std_guard is accepted for
+ * symmetry with the score and ignored (under a record every update method has the guard); rec NULL: rejection off, ess_frac 0.
+ * weights_out [N]; rew_mean_out, temp_out, ess_out, kept_out: one value each; any may be NULL.  The record is checked as the set
+ * calls check it (MBD_ERR_INVALID naming the field). */
+int mbd_debug_weighting_host(const float* rews, int N, float temp, int std_guard, const mbd_weighting* rec, float* weights_out,
+                             float* rew_mean_out, float* temp_out, float* ess_out, int32_t* kept_out);
 #ifdef __cplusplus
 }
 #endif

@@ -438,6 +438,28 @@ struct ObjectiveRec {
   int peek(const mbd_env* env, int k, float* ret_out, float* cost_out, const char* what) const;
 };
 int check_objective(const mbd_objective* rec, int Hsample, int action_size, float* wsum_out);
+// The weighting record of a plan or a sweep (include/mbd_hip.h mbd_weighting) as the handle keeps it.  check_weighting: the refusals
+// the record alone decides, in the header's order, each naming the field, before any device access.  set: behind the handle's NULL,
+// session and enable_demo checks (nullptr clears); makes room for the log — three arrays [P][cap], cap = Ndiffuse - 1 entries per
+// plan — and, where the N rewards outgrow the default LDS window, raises weigh_kernel's.  begin(): a run, a phase call or a tick
+// starts its log; slot(): where the next score step's entry goes (plan 0's; weigh_kernel adds plan k's stride), count advanced.
+struct WeightingRec {
+  bool has = false;
+  WeighRec rec{};
+  int P = 1, cap = 0, count = 0;
+  DevBuf<float> d_temp, d_ess;
+  DevBuf<int> d_kept;
+  int set(const mbd_weighting* r, int device, int P_, int cap_, int N);
+  void begin() { count = 0; }
+  WeighLog slot() {
+    if (count >= cap) count = 0;  // (never: no loop scores more than Ndiffuse - 1 steps; the log stays inside its buffers regardless)
+    const int c = count++;
+    return WeighLog{d_temp.get() + c, d_ess.get() + c, d_kept.get() + c, (long long)cap};
+  }
+  int peek(const mbd_env* env, int k, float* temp_out, float* ess_out, int32_t* kept_out, int capacity, int* count_out,
+           const char* what) const;
+};
+int check_weighting(const mbd_weighting* rec);
 // One tick of a plant's disturbance chain, dk, d_t = split(dk): advances dk, fills slot k of sp with d_t and the record's
 // deviations — the kick's only in the ticks that end with one — and says whether tick t does
 bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k);

@@ -2,6 +2,7 @@
 // reverse-diffusion step split at its exchange point (mbd_plan_sample_rollout / mbd_plan_score_update; the step functions
 // behind them take the rollouts' start state as a parameter), and the loops over steps (mbd_plan_reverse_once, mbd_plan_run,
 // mbd_plan_eval, mbd_plan_peek; the receding-horizon loop mbd_plan_run_mpc).  mbd_planner.py:84-148,179-180.
+#define MBD_WEIGH_KERNEL 1  // this unit launches weigh_kernel (mbd_step_kernels.h)
 #include "mbd_internal.h"
 #include "../../include/mbd_hip_debug.h"
 
@@ -184,6 +185,8 @@ struct mbd_plan {
   int basis_knots = 0, basis_when = MBD_NOISE_ALWAYS;
   // the objective record (mbd_plan_set_objective) with its tables, the previous action and the last step's ret and cost
   ObjectiveRec obj;
+  // the weighting record (mbd_plan_set_weighting) with the device log of its score steps
+  WeightingRec wt;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_plan_mpc_open); it uses the episodes' buffers above — d_mpc_state for the
   // state handed in, d_mpc_pred for the one predicted state, d_mpc_queue — so a handle runs episodes or a session, not both
@@ -614,8 +617,14 @@ static int plan_score_update(mbd_plan* p, int i, const float* d_Ybar_i, const fl
   const int split_env = lever("MBD_WMEAN_SPLIT");
   const bool split = split_env >= 0 ? split_env != 0 : (size_t)N * sizeof(float) > 48 * 1024;
   const bool no_fused_score = env_flag("MBD_NO_FUSED_SCORE");
-  const bool fused_score = !split && c.update_method != 3 && (size_t)N * sizeof(float) <= 48 * 1024 && !no_fused_score;
-  if (!fused_score) {
+  // under a weighting record the weigh kernel stands where score_kernel stands and the step takes the kernels that consume given
+  // weights, the ones MBD_NO_FUSED_SCORE=1 selects
+  const bool fused_score = !split && c.update_method != 3 && (size_t)N * sizeof(float) <= 48 * 1024 && !no_fused_score && !p->wt.has;
+  if (p->wt.has) {
+    hipLaunchKernelGGL(weigh_kernel, dim3(1), dim3(kScoreThreads), lds_n, s, d_rews_all, N, c.temp_sample, p->wt.rec,
+                       p->d_weights.get(), d_rew_mean, p->d_lg.get(), p->wt.slot(), PiBatch{});
+    HIP_TRY(hipGetLastError());
+  } else if (!fused_score) {
     hipLaunchKernelGGL(score_kernel, dim3(1), dim3(kScoreThreads), lds_n, s, d_rews_all,
                        c.enable_demo ? d_logpd_all : nullptr, N, rew_xref, c.temp_sample,
                        c.update_method == 0 ? 1 : 0, p->d_weights, d_rew_mean, p->d_lg, PiBatch{});
@@ -676,6 +685,7 @@ extern "C" int mbd_plan_score_update(mbd_plan* p, int i, const uint32_t key_samp
                                      float* d_rew_mean, void* stream_) {
   (void)key_sample;  // the candidates (or their normals) of all N are already resident from phase 1 of this step
   if (p) NO_SESSION(p, "score_update");
+  if (p) p->wt.begin();
   return plan_score_update(p, i, d_Ybar_i, d_rews_all, d_logpd_all, d_Ybar_im1, d_rew_mean, stream_, p ? p->env->rew_xref : 0.0f);
 }
 
@@ -880,6 +890,7 @@ extern "C" int mbd_plan_reverse_once(mbd_plan* p, int i, uint32_t key_inout[2], 
   NO_SESSION(p, "reverse_once");
   hipStream_t s = (hipStream_t)stream_;
   // the update is not in place on the device (wmean reads Ybar_i while writing Ybar_{i-1})
+  p->wt.begin();
   MBD_TRY(reverse_once_impl(p, p->d_state0, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s, noise_always(p)));
   HIP_TRY(hipMemcpyAsync(d_Ybar, p->d_Ybar, sizeof(float) * p->HNu, hipMemcpyDeviceToDevice, s));
   return MBD_OK;
@@ -900,6 +911,7 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
   }
   HIP_TRY(hipMemsetAsync(cur, 0, sizeof(float) * HNu, s));
   HIP_TRY(hipStreamSynchronize(s));
+  p->wt.begin();
   auto t0 = std::chrono::steady_clock::now();
   for (int i = Nd - 1; i >= 1; --i) {  // reverse() (mbd_planner.py:138-148)
     float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // Ybars.append(Yi)
@@ -1540,6 +1552,164 @@ extern "C" int mbd_plan_peek_objective(mbd_plan* p, float* ret_out, float* cost_
   return p->obj.peek(p->env, 0, ret_out, cost_out, "plan");
 }
 
+// ---- the weighting record (include/mbd_hip.h mbd_weighting) --------------------------------------------------------------
+int check_weighting(const mbd_weighting* rec) {
+  for (int r = 0; r < 6; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "weighting: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (rec->reject_nonfinite != 0 && rec->reject_nonfinite != 1)
+    return fail(MBD_ERR_INVALID, "weighting: reject_nonfinite=%d: must be 0 or 1", rec->reject_nonfinite);
+  if (!std::isfinite(rec->ess_frac) || rec->ess_frac < 0.0f || rec->ess_frac > 1.0f)
+    return fail(MBD_ERR_INVALID, "weighting: ess_frac=%g: must lie in [0, 1]", (double)rec->ess_frac);
+  if (rec->ess_frac > 0.0f) {
+    if (!std::isfinite(rec->temp_min) || !(rec->temp_min > 0.0f))
+      return fail(MBD_ERR_INVALID, "weighting: temp_min=%g: must be finite and > 0", (double)rec->temp_min);
+    if (!std::isfinite(rec->temp_max) || !(rec->temp_max >= rec->temp_min))
+      return fail(MBD_ERR_INVALID, "weighting: temp_max=%g: must be finite and >= temp_min=%g", (double)rec->temp_max,
+                  (double)rec->temp_min);
+    if (rec->iters < 1 || rec->iters > 32) return fail(MBD_ERR_INVALID, "weighting: iters=%d: must lie in 1..32", rec->iters);
+  }
+  return MBD_OK;
+}
+static WeighRec weigh_rec_of(const mbd_weighting* rec) {
+  WeighRec R{};
+  if (rec) {
+    R.reject = rec->reject_nonfinite; R.ess_frac = rec->ess_frac; R.temp_min = rec->temp_min; R.temp_max = rec->temp_max;
+    R.iters = rec->iters;
+  }
+  return R;
+}
+
+// include/mbd_hip_debug.h: weigh_kernel on the host.  The reductions of the kernel's workgroup, restated: partial t of 1024 takes
+// the entries i = t, t + 1024, ... in ascending i, each wavefront's 64 partials go through the xor-butterfly — at every stage lane l
+// takes x[l] (+ or max) x[l ^ off], so every lane ends with the same value —, and the 16 wavefront values are combined in order.
+namespace {
+struct HostBlock {
+  float part[kScoreThreads];
+  template <class Op> float reduce(Op op) {
+    float wave[kScoreThreads / 64];
+    for (int w = 0; w < kScoreThreads / 64; ++w) {
+      float x[64], y[64];
+      for (int l = 0; l < 64; ++l) x[l] = part[w * 64 + l];
+      for (int off = 32; off >= 1; off >>= 1) {
+        for (int l = 0; l < 64; ++l) y[l] = op(x[l], x[l ^ off]);
+        for (int l = 0; l < 64; ++l) x[l] = y[l];
+      }
+      wave[w] = x[0];
+    }
+    float s = wave[0];
+    for (int w = 1; w < kScoreThreads / 64; ++w) s = op(s, wave[w]);
+    return s;
+  }
+  float sum() { return reduce([](float a, float b) { return a + b; }); }
+  float max() { return reduce([](float a, float b) { return fmax_(a, b); }); }
+  void fill(float v) { for (int t = 0; t < kScoreThreads; ++t) part[t] = v; }
+};
+}  // namespace
+extern "C" int mbd_debug_weighting_host(const float* rews, int N, float temp, int std_guard, const mbd_weighting* rec,
+                                        float* weights_out, float* rew_mean_out, float* temp_out, float* ess_out, int32_t* kept_out) {
+  (void)std_guard;
+  if (!rews || N < 1) return fail(MBD_ERR_INVALID, "weighting_host: rews=%p N=%d", (const void*)rews, N);
+  if (rec) MBD_TRY(check_weighting(rec));
+  const WeighRec R = weigh_rec_of(rec);
+  std::vector<float> e((size_t)N, 0.0f);
+  std::vector<char> keep((size_t)N);
+  HostBlock a, b;
+  int kept = 0;
+  a.fill(0.0f); b.fill(-__builtin_inff());
+  for (int i = 0; i < N; ++i) {
+    keep[i] = weigh_keep(rews[i], R.reject) ? 1 : 0;
+    if (!keep[i]) continue;
+    ++kept;
+    a.part[i % kScoreThreads] = a.part[i % kScoreThreads] + rews[i];
+    b.part[i % kScoreThreads] = fmax_(b.part[i % kScoreThreads], rews[i]);
+  }
+  const float sum = a.sum(), rmax = b.max();
+  if (kept == 0) {
+    if (weights_out) for (int i = 0; i < N; ++i) weights_out[i] = 0.0f;
+    if (rew_mean_out) *rew_mean_out = __builtin_nanf("");
+    if (temp_out) *temp_out = temp;
+    if (ess_out) *ess_out = 0.0f;
+    if (kept_out) *kept_out = 0;
+    return MBD_OK;
+  }
+  const float mean = sum / (float)kept;
+  a.fill(0.0f);
+  for (int i = 0; i < N; ++i)
+    if (keep[i]) a.part[i % kScoreThreads] = weigh_dev(a.part[i % kScoreThreads], rews[i], mean);
+  const float sd = weigh_sd(a.sum(), kept);
+  const float zmax = weigh_z(rmax, mean, sd);
+  float S1 = 0.0f;
+  auto pass = [&](float T) {
+    a.fill(0.0f); b.fill(0.0f);
+    for (int i = 0; i < N; ++i) {
+      e[i] = keep[i] ? weigh_e(weigh_z(rews[i], mean, sd), zmax, T) : 0.0f;
+      if (!keep[i]) continue;
+      a.part[i % kScoreThreads] = a.part[i % kScoreThreads] + e[i];
+      b.part[i % kScoreThreads] = b.part[i % kScoreThreads] + e[i] * e[i];
+    }
+    S1 = a.sum();
+    return weigh_ess(S1, b.sum());
+  };
+  const float Ts = weigh_select(R, temp, kept, pass);
+  const float ess = pass(Ts);
+  if (weights_out) for (int i = 0; i < N; ++i) weights_out[i] = keep[i] ? e[i] / S1 : 0.0f;
+  if (rew_mean_out) *rew_mean_out = mean;
+  if (temp_out) *temp_out = Ts;
+  if (ess_out) *ess_out = ess;
+  if (kept_out) *kept_out = kept;
+  return MBD_OK;
+}
+
+int WeightingRec::set(const mbd_weighting* r, int device, int P_, int cap_, int N) {
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still write the log)
+  has = false;
+  count = 0;
+  if (!r) return MBD_OK;
+  P = P_; cap = cap_;
+  HIP_TRY(d_temp.grow((size_t)P * cap));
+  HIP_TRY(d_ess.grow((size_t)P * cap));
+  HIP_TRY(d_kept.grow((size_t)P * cap));
+  // (the attribute belongs to THIS unit's copy of the static kernel, the one a plan launches.  A sweep launches mbd_sweep.hip's copy,
+  // which never needs it: mbd_sweep_create refuses plans whose N weights outgrow the default 48 KB window, so for a sweep the test
+  // below is always false)
+  if ((size_t)N * sizeof(float) > 48 * 1024 && N <= kLdsN)
+    HIP_TRY(hipFuncSetAttribute((const void*)weigh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
+  rec = weigh_rec_of(r);
+  has = true;
+  return MBD_OK;
+}
+
+int WeightingRec::peek(const mbd_env* env, int k, float* temp_out, float* ess_out, int32_t* kept_out, int capacity, int* count_out,
+                       const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_weighting: the %s has no weighting record", what);
+  if (k < 0 || k >= P) return fail(MBD_ERR_INVALID, "peek_weighting: plan k=%d outside [0,%d)", k, P);
+  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_weighting: capacity=%d", capacity);
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const int n = count < capacity ? count : capacity;
+  const size_t off = (size_t)k * cap;
+  if (n > 0 && temp_out) HIP_TRY(hipMemcpy(temp_out, d_temp.get() + off, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (n > 0 && ess_out) HIP_TRY(hipMemcpy(ess_out, d_ess.get() + off, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (n > 0 && kept_out) HIP_TRY(hipMemcpy(kept_out, d_kept.get() + off, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (count_out) *count_out = count;
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_weighting(mbd_plan* p, const mbd_weighting* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_weighting");
+  if (rec) MBD_TRY(check_weighting(rec));  // (before any device access)
+  if (rec && p->cfg.enable_demo)
+    return fail(MBD_ERR_UNSUPPORTED, "weighting record: enable_demo=1: the demo blend standardises twice, an ESS target is not defined there");
+  return p->wt.set(rec, p->env->device, 1, p->cfg.Ndiffuse - 1, p->cfg.Nsample);
+}
+
+extern "C" int mbd_plan_peek_weighting(mbd_plan* p, float* temp_out, float* ess_out, int32_t* kept_out, int capacity, int* count_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->wt.peek(p->env, 0, temp_out, ess_out, kept_out, capacity, count_out, "plan");
+}
+
 // ---- one tick's planning, shared by the batch episode (mbd_plan_run_mpc) and the session (mbd_plan_mpc_submit) ------------------
 // The tick's keys, host arithmetic: rng, k_t = split(rng) advances the episode's chain; r = k_t is where the tick's own chain
 // starts (mbd_plan_run's from it); after = split(split(rng')[1])[1] is the Y0s_rng of tick t+1's first step, whose normals are
@@ -1582,6 +1752,7 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
   // the noise shape and basis: a cold tick is mbd_plan_run's loop (MBD_NOISE_WARM_TICKS: without), every other tick samples under
   // them in either mode — the first normals of the next tick, prepared beside this tick's last rollout, included
   const NoiseSpec ns = tk.cold ? noise_always(p) : noise_warm(p);
+  p->wt.begin();  // (a weighting record's log holds the last tick's steps)
   const float* cur = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros of a cold tick, shift_E(M_{t-1}) otherwise
   for (int i = tk.cold ? Nd - 1 : tk.K; i >= 1; --i) {
     float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)

@@ -881,6 +881,54 @@ static __global__ __launch_bounds__(kScoreThreads) void score_kernel(const float
   if (threadIdx.x == 0) *rew_mean_out = rew_mean;
 }
 
+// ---- the weighting record (mbd_plan_set_weighting, include/mbd_hip.h mbd_weighting; DESIGN.md section 1 "N14 weighting"): the
+// candidates' rewards -> weights[N] with non-finite rewards left out and the temperature chosen per step by the effective sample
+// size; under a record it stands where score_kernel stands, and the step takes the kernels that consume given weights ----
+// The arithmetic of one entry and of the selection is the functions below, host and device text: the kernel's threads run them
+// between the block reductions, mbd_debug_weighting_host runs them on the CPU between restatements of those reductions over the
+// 1024 virtual threads.  f32, every operation rounded (the build's -ffp-contract=off); the one fused operation is the squared
+// deviation's accumulation, score_block's own, which the bits of a step without a record oblige.
+struct WeighRec {
+  int reject;  // drop NaN and +-inf rewards
+  float ess_frac, temp_min, temp_max;
+  int iters;
+};
+// where a step's log entry goes: plan 0's slot of each of the three logs, plan k's `stride` entries further
+struct WeighLog {
+  float* temp;
+  float* ess;
+  int* kept;
+  long long stride;
+};
+// decided on the bits (exponent all ones), not by a compare a fast-math flag could fold
+MBD_HD bool weigh_keep(float r, int reject) { return !reject || (__builtin_bit_cast(uint32_t, r) & 0x7f800000u) != 0x7f800000u; }
+MBD_HD float weigh_dev(float part, float r, float mean) {
+  const float d = r - mean;
+  return ffma(d, d, part);
+}
+MBD_HD float weigh_sd(float sumsq, int kept) {
+  const float sd = fsqrt(sumsq / (float)kept);
+  return sd < 1e-4f ? 1.0f : sd;  // (under a record every update method has the guard)
+}
+MBD_HD float weigh_z(float r, float mean, float sd) { return (r - mean) / sd; }
+// ((r - mean) / sd) / T and the maximum through the largest reward: score_block's three operations, so the maximal entry is exp_(0) = 1
+MBD_HD float weigh_e(float z, float zmax, float T) { return exp_(z / T - zmax / T); }
+MBD_HD float weigh_ess(float S1, float S2) { return (S1 * S1) / S2; }
+// T*: ess_at(T) is one pass over the kept entries (E(T) of the contract).  Both clamps and the loop compare with `!(a < b)` forms, so
+// a NaN ess ends at a clamp instead of walking the loop.
+template <class Ess>
+MBD_HD float weigh_select(const WeighRec& R, float T0, int kept, Ess&& ess_at) {
+  if (R.ess_frac == 0.0f) return T0;
+  const float target = R.ess_frac * (float)kept;
+  if (!(ess_at(R.temp_min) < target)) return R.temp_min;
+  if (!(ess_at(R.temp_max) > target)) return R.temp_max;
+  float lo = R.temp_min, hi = R.temp_max;
+  for (int k = 0; k < R.iters; ++k) {
+    const float mid = fsqrt(lo * hi);
+    if (ess_at(mid) < target) lo = mid; else hi = mid;
+  }
+  return hi;
+}
 // ---- A7-A8: weighted mean + score update (mbd_planner.py:128-133) ---------------------------------------
 // A workgroup owns kWmE = 16 consecutive outputs e of [H][Nu] and splits the candidates into 64 groups:
 // thread (g, j) runs a sequential fma over n = g, g+64, ... for output j (a wavefront reads four 64-byte row
@@ -976,7 +1024,9 @@ static __global__ __launch_bounds__(kWmE * kWmG) void wmean_kernel(const float* 
 // neighbour — when the neighbours drift apart in time and the line has left the L2 in between it is fetched twice (the sweep's
 // batch form: 2.0x its algorithmic bytes, PMC round 4); a 256-byte segment touches 3 lines for 2 lines' worth of data:
 // 1.5x at worst, whatever the L2 does.
-template <int ROUND, bool REGS, int V = 1>  // rows in flight per round of the chain, score_block's REGS (48, true: one plan; sweeps: 32, false)
+// GIVEN (sweeps under a weighting record): weights_out already holds the plan's N weights — weigh_kernel's — and rew_mean_out its
+// mean reward; the workgroups load them into wl[] in place of deriving them, and the chains below are the same text.
+template <int ROUND, bool REGS, int V = 1, bool GIVEN = false>  // rows in flight per round of the chain, score_block's REGS (48, true: one plan; sweeps: 32, false)
 __device__ __forceinline__ void score_wmean_body(
     const float* __restrict__ rews, const float* __restrict__ lp_demo, int N, float rew_xref, float temp, int std_guard,
     float* __restrict__ weights_out, float* __restrict__ rew_mean_out, const float* __restrict__ Y0s, int HNu,
@@ -1012,12 +1062,16 @@ __device__ __forceinline__ void score_wmean_body(
   // the step's mean reward may go to a pinned host slot the host is polling (per-step progress, mbd_planner.py:147):
   // a system-scope store leaves as soon as the first reduction has it — a plain one would sit in the cache until the
   // kernel ends — so the host turns around while the rest of the score and the weighted mean below run
-  const float den = score_block<REGS>(rews, lp_demo, N, rew_xref, temp, std_guard, wl, red_s, rew_mean,
-                                      writer ? rew_mean_out : nullptr);
-  for (int i = threadIdx.x; i < N; i += kScoreThreads) {
-    const float w = wl[i] / den;
-    wl[i] = w;
-    if (writer) weights_out[i] = w;
+  if constexpr (GIVEN) {
+    for (int i = threadIdx.x; i < N; i += kScoreThreads) wl[i] = weights_out[i];
+  } else {
+    const float den = score_block<REGS>(rews, lp_demo, N, rew_xref, temp, std_guard, wl, red_s, rew_mean,
+                                        writer ? rew_mean_out : nullptr);
+    for (int i = threadIdx.x; i < N; i += kScoreThreads) {
+      const float w = wl[i] / den;
+      wl[i] = w;
+      if (writer) weights_out[i] = w;
+    }
   }
   __syncthreads();
   float acc[V];
@@ -1140,7 +1194,7 @@ struct ScoreBatch {
 // each, ONE per CU of plan k's XCD — they start together and stay together, a row segment is 128 bytes: the 2.0x of V = 1
 // (plan k's 54 tiles, two to a CU, drifting apart behind XCD k's 4 MB L2 while 3.5 MB of normals stream through it) is gone:
 // sweep8 28.2 MB per launch for 28.0 MB algorithmic, 11.3 us instead of 15.5 (profiles/r05_score_ab.txt).
-template <int V>
+template <int V, bool GIVEN = false>
 static __global__ __launch_bounds__(kWmE * kWmG, V == 1 ? 8 : 4) void score_wmean_batch_kernel(
     const float* __restrict__ rews, const float* __restrict__ lp_demo, int N, float rew_xref, float temp, int std_guard,
     float* __restrict__ weights_out, float* __restrict__ rew_mean_out, const float* __restrict__ Y0s, int HNu,
@@ -1158,7 +1212,7 @@ static __global__ __launch_bounds__(kWmE * kWmG, V == 1 ? 8 : 4) void score_wmea
     k = c + 8 * (m / T);
     tile = m % T;
   }
-  score_wmean_body<32, false, V>(rews + k * sb.rews, lp_demo ? lp_demo + k * sb.lp : nullptr, N, rew_xref, sb.temps ? sb.temps[k] : temp,
+  score_wmean_body<32, false, V, GIVEN>(rews + k * sb.rews, lp_demo ? lp_demo + k * sb.lp : nullptr, N, rew_xref, sb.temps ? sb.temps[k] : temp,
                    std_guard, weights_out + k * sb.weights, rew_mean_out + k * sb.mean, Y0s + k * sb.cand, HNu,
                    Ybar_i + k * sb.ybar_in, alpha_i, alpha_bar_i, alpha_bar_im1, literal, Ybar_im1 + k * sb.ybar_out, lazy,
                    sigma, ybar_keep ? ybar_keep + k * sb.keep : nullptr, tile, tile == 0);
@@ -1384,5 +1438,126 @@ static __global__ __launch_bounds__(64) void cem_mean_kernel(const int* __restri
   mu_out[e] = acc / (float)K;
 }
 
+
+// ---- the weigh kernel of a weighting record (the arithmetic: weigh_keep ... weigh_select above).  Last in this header and compiled
+// only by the units that launch it (MBD_WEIGH_KERNEL: mbd_plan.hip, mbd_sweep.hip): a static kernel is emitted by every unit that
+// sees it, and one emitted in front of other kernels moves their addresses — the code objects of the units that do not launch it,
+// the rollouts' among them, stay what they were, and in the two that do every earlier kernel keeps its place ----
+#ifdef MBD_WEIGH_KERNEL
+// two sums in one pass over the barriers, each in block_sum's order (red: 2 x 16 entries)
+__device__ __forceinline__ void block_sum2(float& xa, float& xb, float* red) {
+  xa = wave_sum(xa);
+  xb = wave_sum(xb);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = xa;
+    red[kScoreThreads / 64 + (threadIdx.x >> 6)] = xb;
+  }
+  __syncthreads();
+  float a = red[0], b = red[kScoreThreads / 64];
+#pragma unroll
+  for (int w = 1; w < kScoreThreads / 64; ++w) {
+    a = a + red[w];
+    b = b + red[kScoreThreads / 64 + w];
+  }
+  xa = a;
+  xb = b;
+}
+// ONE 1024-thread workgroup per plan (blockIdx.y = plan, PiBatch's strides: a single plan launches one row and zero strides).
+// Thread t owns the entries i = t, t + 1024, ... and nothing else, in every pass: up to 8192 candidates they cross from memory
+// once and stay in registers (from the second reduction on as z), beyond that they are re-read; e[] of the last pass goes to lg —
+// LDS, or the plan's global scratch beyond the LDS window — and needs no barrier of its own.  The selection's branches are taken
+// on values every thread read from the same LDS words: uniform.  iters + 3 passes at most, each one exp_ per entry and one
+// two-value block reduction.  Plain vector loads and stores; the mean reward leaves through a system-scope store as soon as the
+// first reduction has it (the progress poll's slot, as in the fused score), the log entry through thread 0.
+static __global__ __launch_bounds__(kScoreThreads) void weigh_kernel(const float* __restrict__ rews, int N, float temp, WeighRec R,
+                                                              float* __restrict__ weights, float* __restrict__ rew_mean_out,
+                                                              float* __restrict__ lg_global, WeighLog log, PiBatch pb) {
+  const long long plan = blockIdx.y;
+  rews += plan * pb.rews; weights += plan * pb.weights; rew_mean_out += plan * pb.mean;
+  if (pb.temps) temp = pb.temps[plan];
+  extern __shared__ __attribute__((aligned(16))) float lg_lds[];
+  float* __restrict__ lg = lg_global ? lg_global : lg_lds;
+  __shared__ float red[2 * (kScoreThreads / 64)];
+  __shared__ int red_n[kScoreThreads / 64];
+  const int tid = threadIdx.x;
+  constexpr int RK = 8;
+  const bool in_regs = N <= RK * kScoreThreads;  // (uniform)
+  float r[RK];
+  unsigned km = 0;  // bit k: entry tid + 1024 k exists and is kept
+#pragma unroll
+  for (int k = 0; k < RK; ++k) {
+    const bool ok = in_regs && tid + k * kScoreThreads < N;
+    r[k] = ok ? rews[tid + k * kScoreThreads] : 0.0f;
+    km |= (ok && weigh_keep(r[k], R.reject)) ? 1u << k : 0u;
+  }
+  // f(i, x, keep) over this thread's entries in ascending i: x = the register's value, or rews[i] re-read
+  auto each = [&](auto&& f) {
+    if (in_regs) {
+#pragma unroll
+      for (int k = 0; k < RK; ++k)
+        if (tid + k * kScoreThreads < N) f(tid + k * kScoreThreads, r[k], (km >> k & 1u) != 0, k);
+    } else {
+      for (int i = tid; i < N; i += kScoreThreads) {
+        const float x = rews[i];
+        f(i, x, weigh_keep(x, R.reject), 0);
+      }
+    }
+  };
+  float part = 0.0f, rmax = -__builtin_inff();
+  int cnt = 0;
+  each([&](int, float x, bool keep, int) {
+    part = keep ? part + x : part;
+    rmax = keep ? fmax_(rmax, x) : rmax;
+    cnt += keep ? 1 : 0;
+  });
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+  if ((tid & 63) == 0) red_n[tid >> 6] = cnt;
+  block_sum_max(part, rmax, red);  // (its barriers cover red_n)
+  int kept = 0;
+#pragma unroll
+  for (int w = 0; w < kScoreThreads / 64; ++w) kept += red_n[w];
+  float* __restrict__ log_temp = log.temp + plan * log.stride;
+  float* __restrict__ log_ess = log.ess + plan * log.stride;
+  int* __restrict__ log_kept = log.kept + plan * log.stride;
+  if (kept == 0) {  // (uniform) nothing to weigh: every weight +0, the mean reward NaN
+    for (int i = tid; i < N; i += kScoreThreads) weights[i] = 0.0f;
+    if (tid == 0) {
+      __hip_atomic_store(rew_mean_out, __builtin_nanf(""), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      *log_temp = temp; *log_ess = 0.0f; *log_kept = 0;
+    }
+    return;
+  }
+  const float mean = part / (float)kept;
+  if (tid == 0) __hip_atomic_store(rew_mean_out, mean, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  part = 0.0f;
+  each([&](int, float x, bool keep, int) { part = keep ? weigh_dev(part, x, mean) : part; });
+  const float sd = weigh_sd(block_sum(part, red), kept);
+  const float zmax = weigh_z(rmax, mean, sd);
+  if (in_regs) {  // the registers hold z from here on
+#pragma unroll
+    for (int k = 0; k < RK; ++k) r[k] = weigh_z(r[k], mean, sd);
+  }
+  float S1 = 0.0f, S2 = 0.0f;
+  auto pass = [&](float T, bool store) {
+    float p1 = 0.0f, p2 = 0.0f;
+    each([&](int i, float x, bool keep, int) {
+      const float e = keep ? weigh_e(in_regs ? x : weigh_z(x, mean, sd), zmax, T) : 0.0f;
+      p1 = keep ? p1 + e : p1;
+      p2 = keep ? p2 + e * e : p2;
+      if (store) lg[i] = e;
+    });
+    block_sum2(p1, p2, red);
+    S1 = p1;
+    S2 = p2;
+    return weigh_ess(p1, p2);
+  };
+  const float Ts = weigh_select(R, temp, kept, [&](float T) { return pass(T, false); });
+  const float ess = pass(Ts, true);
+  each([&](int i, float, bool keep, int) { weights[i] = keep ? lg[i] / S1 : 0.0f; });
+  if (tid == 0) { *log_temp = Ts; *log_ess = ess; *log_kept = kept; }
+}
+#endif  // MBD_WEIGH_KERNEL
 
 }  // namespace mbd

@@ -1,6 +1,7 @@
 // mbd_sweep.hip — sweeps (include/mbd_hip.h): several plans of one env advanced in lockstep, one rollout launch over all
 // their candidates per step (mbd/scripts/run_mbd.py:17-64); MBD plans and the path-integral baselines.  The sweep handle, its
 // ring of noise buffers (sweep_step: another protocol than a plan's NoiseRing) and the batched receding-horizon loop.
+#define MBD_WEIGH_KERNEL 1  // this unit launches weigh_kernel (mbd_step_kernels.h)
 #include "mbd_internal.h"
 
 namespace {
@@ -12,14 +13,33 @@ int wmean_batch_v() {
   const int v = lever("MBD_WMEAN_V");
   return (v == 1 || v == 2 || v == 4) ? v : 2;
 }
+// given: under a weighting record — weigh_kernel has written every plan's weights and mean reward, the launch loads the weights
+// where it would derive them (score_wmean_body's GIVEN form; the same grid, tiles and plan-to-XCD mapping)
 template <typename... Args>
-void launch_score_wmean_batch(int V, int HNu, int P, size_t lds, hipStream_t s, Args... args) {
+void launch_score_wmean_batch(int V, bool given, int HNu, int P, size_t lds, hipStream_t s, Args... args) {
   using namespace mbd;
   const dim3 block(kWmE * kWmG);
   auto tiles = [&](int v) { return dim3((unsigned)((HNu + kWmE * v - 1) / (kWmE * v)), (unsigned)P); };
+  if (given) {
+    if (V == 1) hipLaunchKernelGGL((score_wmean_batch_kernel<1, true>), tiles(1), block, lds, s, args...);
+    else if (V == 2) hipLaunchKernelGGL((score_wmean_batch_kernel<2, true>), tiles(2), block, lds, s, args...);
+    else hipLaunchKernelGGL((score_wmean_batch_kernel<4, true>), tiles(4), block, lds, s, args...);
+    return;
+  }
   if (V == 1) hipLaunchKernelGGL(score_wmean_batch_kernel<1>, tiles(1), block, lds, s, args...);
   else if (V == 2) hipLaunchKernelGGL(score_wmean_batch_kernel<2>, tiles(2), block, lds, s, args...);
   else hipLaunchKernelGGL(score_wmean_batch_kernel<4>, tiles(4), block, lds, s, args...);
+}
+// the weigh kernel over the P plans of a step (blockIdx.y = plan), in front of the launch that consumes its weights
+int launch_weigh_batch(WeightingRec& wt, int P, int N, int Nd, const float* d_rews, float temp, const float* d_temps, float* d_weights,
+                       float* d_rew_mean, hipStream_t s) {
+  using namespace mbd;
+  PiBatch pb;
+  pb.rews = N; pb.weights = N; pb.mean = Nd - 1; pb.temps = d_temps;
+  hipLaunchKernelGGL(weigh_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), sizeof(float) * (size_t)N, s, d_rews, N, temp, wt.rec,
+                     d_weights, d_rew_mean, (float*)nullptr, wt.slot(), pb);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
 }
 }  // namespace
 
@@ -103,6 +123,8 @@ struct mbd_sweep {
   NoiseSpec noise_warm() const { return noise_spec(true); }
   // the objective record of all the sweep's plans (mbd_sweep_set_objective): a plan's, with every plan's previous action [P][Nu]
   ObjectiveRec obj;
+  // the weighting record of all the sweep's plans (mbd_sweep_set_weighting) with every plan's log [P][Ndiffuse - 1]
+  WeightingRec wt;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_sweep_mpc_open): it uses the batch's buffers above — slice 0 of d_mpc_states for
   // the states handed in, slice 0 of d_mpc_pred, d_mpc_queue, d_mpc_ybar — so a handle runs batches or a session, not both
@@ -264,9 +286,12 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
   pb.mu = mu_stride;
   if (c.update_method == 3) {  // cem_update (path_integral.py:48-52)
     const int K = N < 10 ? N : 10;
-    hipLaunchKernelGGL(score_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), sizeof(float) * (size_t)N, s, (const float*)w->d_rews,
-                       (const float*)nullptr, N, e->rew_xref, c.temp_sample, 0, w->d_weights, w->d_rewmeans + step,
-                       (float*)nullptr, pb);
+    if (w->wt.has)
+      MBD_TRY(launch_weigh_batch(w->wt, P, N, Nd, w->d_rews, c.temp_sample, w->d_temps, w->d_weights, w->d_rewmeans + step, s));
+    else
+      hipLaunchKernelGGL(score_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), sizeof(float) * (size_t)N, s, (const float*)w->d_rews,
+                         (const float*)nullptr, N, e->rew_xref, c.temp_sample, 0, w->d_weights, w->d_rewmeans + step,
+                         (float*)nullptr, pb);
     hipLaunchKernelGGL(cem_select_kernel, dim3(1, (unsigned)P), b64, sizeof(float) * (size_t)N, s, (const float*)w->d_weights, N, K,
                        w->d_idx, (float*)nullptr, pb);
     hipLaunchKernelGGL(cem_mean_kernel, dim3((HNu + 63) / 64, (unsigned)P), b64, 0, s, (const int*)w->d_idx, K,
@@ -275,7 +300,9 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
     ScoreBatch sb;
     sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)per_plan;
     sb.ybar_in = mu_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
-    launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
+    if (w->wt.has)
+      MBD_TRY(launch_weigh_batch(w->wt, P, N, Nd, w->d_rews, c.temp_sample, w->d_temps, w->d_weights, w->d_rewmeans + step, s));
+    launch_score_wmean_batch(wmean_batch_v(), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
                              c.temp_sample, 0, w->d_weights.get(), w->d_rewmeans + step, (const float*)w->d_Y0s, HNu, mu_in, 1.0f, 1.0f,
                              1.0f, 0, mu_out, 0, 0.0f, (float*)nullptr, sb);
     if (c.update_method == 2) {
@@ -301,6 +328,7 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
   }
   HIP_TRY(hipStreamSynchronize(s));
   auto t0 = std::chrono::steady_clock::now();
+  w->wt.begin();
   for (int i = Nd - 1, step = 0; i >= 1; --i, ++step) {
     SweepKeys sk;
     for (int k = 0; k < P; ++k) {  // rng, Y0s_rng = split(rng) (path_integral.py:114)
@@ -417,7 +445,9 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
   ScoreBatch sb;
   sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)N * HNu;
   sb.ybar_in = st.ybar_in_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
-  launch_score_wmean_batch(wmean_batch_v(), HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), c.enable_demo ? w->d_lp.get() : nullptr, N,
+  if (w->wt.has)
+    MBD_TRY(launch_weigh_batch(w->wt, P, N, Nd, w->d_rews, c.temp_sample, w->d_temps, w->d_weights, w->d_rewmeans + st.slot, s));
+  launch_score_wmean_batch(wmean_batch_v(), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), c.enable_demo ? w->d_lp.get() : nullptr, N,
                            st.rew_xref, c.temp_sample, 1, w->d_weights.get(), w->d_rewmeans + st.slot, w->d_eps[cur].get(), HNu, st.ybar_in,
                            w->alphas[i], w->alphas_bar[i], w->alphas_bar[i - 1], c.literal_score,
                            w->d_mu + (size_t)st.slot * HNu, 1, w->sigmas[i], (float*)nullptr, sb);
@@ -445,6 +475,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
   sweep_split_keys(w, rng, sk);
   sweep_noise(w, sk, 0, s, w->noise_always());  // step Nd-1
   HIP_TRY(hipGetLastError());
+  w->wt.begin();
   for (int i = Nd - 1, step = 0; i >= 1; --i, ++step) {
     if (i > 1) sweep_split_keys(w, rng, sk);
     SweepStep st;
@@ -509,6 +540,22 @@ extern "C" int mbd_sweep_set_objective(mbd_sweep* w, const mbd_objective* rec) {
 extern "C" int mbd_sweep_peek_objective(mbd_sweep* w, int k, float* ret_out, float* cost_out) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   return w->obj.peek(w->env, k, ret_out, cost_out, "sweep");
+}
+
+// one weighting record for all plans of the sweep (include/mbd_hip.h mbd_weighting), as mbd_plan_set_weighting
+extern "C" int mbd_sweep_set_weighting(mbd_sweep* w, const mbd_weighting* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  NO_SWEEP_SESSION(w, "set_weighting");
+  if (rec) MBD_TRY(check_weighting(rec));  // (before any device access)
+  if (rec && w->cfg.enable_demo)
+    return fail(MBD_ERR_UNSUPPORTED, "weighting record: enable_demo=1: the demo blend standardises twice, an ESS target is not defined there");
+  return w->wt.set(rec, w->env->device, w->P, w->cfg.Ndiffuse - 1, w->cfg.Nsample);
+}
+
+extern "C" int mbd_sweep_peek_weighting(mbd_sweep* w, int k, float* temp_out, float* ess_out, int32_t* kept_out, int capacity,
+                                        int* count_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  return w->wt.peek(w->env, k, temp_out, ess_out, kept_out, capacity, count_out, "sweep");
 }
 
 extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant* rec) {
@@ -678,6 +725,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   for (int t = 0, q = 0; t < T; ++t) {
     const float* states_t = w->d_mpc_states + (size_t)t * P * S;
     const int i_start = t == 0 ? Nd - 1 : K;
+    w->wt.begin();  // (a weighting record's log holds the last tick's steps)
     // with a delay record: every episode's committed rows, the prediction of where they leave it, and the plans from there
     const float* q_in = has_delay ? w->d_mpc_queue + (size_t)(t & 1) * P * Q : nullptr;
     float* q_out = has_delay ? w->d_mpc_queue + (size_t)((t + 1) & 1) * P * Q : nullptr;
@@ -949,6 +997,7 @@ extern "C" int mbd_sweep_mpc_submit(mbd_sweep* w, const float* states) {
   session_split_keys(w, r, active, sk);
   sweep_noise(w, sk, 0, s, ns);
   HIP_TRY(hipGetLastError());
+  w->wt.begin();
   for (int i = i_start, q = 0; i >= 1; --i, ++q) {
     if (i > 1) {
       for (int k = 0; k < P; ++k) active_next[k] = ss.cold[k] || i - 1 <= K;

@@ -106,6 +106,13 @@ class Objective(C.Structure):
                 ("effort", C.c_float), ("rate", C.c_float), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class Weighting(C.Structure):
+    """mbd_weighting (include/mbd_hip.h): whether candidates with a non-finite reward are left out of a step's weights, and the
+    effective-sample-size target, bracket and bisection steps its temperature is chosen by."""
+    _fields_ = [("reject_nonfinite", C.c_int32), ("ess_frac", C.c_float), ("temp_min", C.c_float), ("temp_max", C.c_float),
+                ("iters", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
 TICK_ROWS_NONFINITE, TICK_STATE_NONFINITE, TICK_COLD = 1, 2, 4
 
 
@@ -123,6 +130,7 @@ EXPORTS = [
     "mbd_plan_schedule", "mbd_plan_set_state0", "mbd_plan_sample_rollout", "mbd_plan_prefetch_noise", "mbd_plan_score_update",
     "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_set_mpc_delay", "mbd_plan_peek_mpc_predicted", "mbd_plan_set_mpc_demo", "mbd_plan_peek_mpc_track", "mbd_plan_set_mpc_sigma", "mbd_plan_peek_mpc_sigma",
     "mbd_plan_set_objective", "mbd_plan_peek_objective", "mbd_sweep_set_objective", "mbd_sweep_peek_objective",
+    "mbd_plan_set_weighting", "mbd_plan_peek_weighting", "mbd_sweep_set_weighting", "mbd_sweep_peek_weighting",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
@@ -205,6 +213,10 @@ def load() -> C.CDLL:
     lib.mbd_plan_peek_objective.argtypes = [_vp, _vp, _vp]
     lib.mbd_sweep_set_objective.argtypes = [_vp, C.POINTER(Objective)]
     lib.mbd_sweep_peek_objective.argtypes = [_vp, _i, _vp, _vp]
+    lib.mbd_plan_set_weighting.argtypes = [_vp, C.POINTER(Weighting)]
+    lib.mbd_plan_peek_weighting.argtypes = [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
+    lib.mbd_sweep_set_weighting.argtypes = [_vp, C.POINTER(Weighting)]
+    lib.mbd_sweep_peek_weighting.argtypes = [_vp, _i, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
     lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
     lib.mbd_plan_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(MpcTickInfo)]
@@ -375,6 +387,40 @@ def debug_objective_host(rewss, rews, cand, w=None, q=None, effort: float = 0.0,
                                        opt(w), float(wsum), np_ptr(q), float(effort), float(rate), opt(prev), np_ptr(out), np_ptr(ret),
                                        np_ptr(cost)))
     return out, ret, cost
+
+
+def weighting_record(reject_nonfinite=True, ess_frac: float = 0.0, temp_min=None, temp_max=None, iters: int = 12) -> "Weighting":
+    """The mbd_weighting of ``set_weighting``'s arguments (a bracket of None: zeros, which the library accepts with ess_frac == 0)."""
+    rec = Weighting()
+    rec.reject_nonfinite = int(reject_nonfinite)
+    rec.ess_frac = float(ess_frac)
+    rec.temp_min = 0.0 if temp_min is None else float(temp_min)
+    rec.temp_max = 0.0 if temp_max is None else float(temp_max)
+    rec.iters = int(iters)
+    return rec
+
+
+def debug_weighting_host(rews, temp: float, rec: "Weighting" = None, std_guard: int = 1):
+    """include/mbd_hip_debug.h: weigh_kernel's arithmetic run on the host (no device).  ``rews`` [N], ``temp`` T0, ``rec`` a
+    ``Weighting`` or None.  Returns (weights [N], rew_mean, T*, ess, kept)."""
+    lib = load()
+    lib.mbd_debug_weighting_host.argtypes = [_vp, _i, _f, _i, C.POINTER(Weighting), _vp, _vp, _vp, _vp, _vp]
+    rews = np.ascontiguousarray(rews, np.float32)
+    w = np.full(rews.shape[0], np.nan, np.float32)
+    mean, T, ess, kept = np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.float32), np.zeros(1, np.int32)
+    check(lib.mbd_debug_weighting_host(np_ptr(rews), rews.shape[0], float(temp), int(std_guard), None if rec is None else C.byref(rec),
+                                       np_ptr(w), np_ptr(mean), np_ptr(T), np_ptr(ess), np_ptr(kept)))
+    return w, mean[0], T[0], ess[0], int(kept[0])
+
+
+def peek_weighting(fn, handle, k, capacity: int) -> dict:
+    """mbd_plan_peek_weighting (k None) or mbd_sweep_peek_weighting: {'temp', 'ess', 'kept'}, one entry per score step."""
+    temp, ess, kept = np.zeros(capacity, np.float32), np.zeros(capacity, np.float32), np.zeros(capacity, np.int32)
+    n = C.c_int(0)
+    head = (handle,) if k is None else (handle, int(k))
+    check(fn(*head, np_ptr(temp), np_ptr(ess), np_ptr(kept), int(capacity), C.byref(n)))
+    m = min(n.value, capacity)
+    return {"temp": temp[:m], "ess": ess[:m], "kept": kept[:m]}
 
 
 def debug_math_ops() -> list:

@@ -212,6 +212,18 @@ class Sweep:
     def clear_objective(self):
         _capi.check(self.lib.mbd_sweep_set_objective(self.h, None))
 
+    def set_weighting(self, reject_nonfinite=True, ess_frac: float = 0.0, temp_min=None, temp_max=None, iters: int = 12):
+        """One weighting record for all plans of the sweep (``Plan.set_weighting``), each at its own temperature."""
+        rec = _capi.weighting_record(reject_nonfinite, ess_frac, temp_min, temp_max, iters)
+        _capi.check(self.lib.mbd_sweep_set_weighting(self.h, C.byref(rec)))
+
+    def clear_weighting(self):
+        _capi.check(self.lib.mbd_sweep_set_weighting(self.h, None))
+
+    def peek_weighting(self, k: int) -> dict:
+        """Plan k's ``temp``, ``ess`` and ``kept`` of every score step of the last run or tick (``Plan.peek_weighting``)."""
+        return _capi.peek_weighting(self.lib.mbd_sweep_peek_weighting, self.h, k, self.cfg.Ndiffuse - 1)
+
     def peek_objective(self, k: int):
         """Plan k's ``ret`` [N] and ``cost`` [N] of the last step (a sweep with an objective record)."""
         N = self.cfg.Nsample
@@ -676,6 +688,23 @@ class Plan:
 
     def clear_objective(self):
         _capi.check(self.lib.mbd_plan_set_objective(self.h, None))
+
+    def set_weighting(self, reject_nonfinite=True, ess_frac: float = 0.0, temp_min=None, temp_max=None, iters: int = 12):
+        """Weigh the candidates robustly (include/mbd_hip.h mbd_weighting): with ``reject_nonfinite`` a candidate whose reward is
+        NaN or infinite gets weight 0 and leaves the step's statistics, so one diverged rollout no longer turns the plan's mean
+        into NaN; with ``ess_frac`` in (0, 1] every step chooses its softmax temperature inside [``temp_min``, ``temp_max``] by
+        ``iters`` bisection steps so that the effective sample size of the weights is about ``ess_frac`` times the candidates
+        kept (0: the plan's ``temp_sample``).  Not for plans created with ``enable_demo``."""
+        rec = _capi.weighting_record(reject_nonfinite, ess_frac, temp_min, temp_max, iters)
+        _capi.check(self.lib.mbd_plan_set_weighting(self.h, C.byref(rec)))
+
+    def clear_weighting(self):
+        _capi.check(self.lib.mbd_plan_set_weighting(self.h, None))
+
+    def peek_weighting(self) -> dict:
+        """``temp``, ``ess`` and ``kept``, one entry per score step of the last ``run``, the last phase call or the last tick (a
+        plan with a weighting record)."""
+        return _capi.peek_weighting(self.lib.mbd_plan_peek_weighting, self.h, None, self.cfg.Ndiffuse - 1)
 
     def peek_objective(self):
         """The last step's ``ret`` [shard_count] ([M, N] under an ensemble record) and ``cost`` [shard_count] (a plan with an

@@ -64,6 +64,16 @@ episode's rewards stay the env's own.
 
     python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --discount 0.98 --rate_cost 0.1
 
+Every step weighs its candidates by a softmax of their standardised rewards at the env's ``temp_sample``, and one candidate whose
+reward is NaN or infinite makes every weight NaN.  A weighting record (include/mbd_hip.h mbd_weighting; DESIGN.md section 1 "N14
+weighting") changes both: ``--reject_nonfinite`` leaves such candidates out of the step, and ``--ess_frac F --temp_min A --temp_max
+B --ess_iters I`` lets every step choose its temperature inside [A, B] by I bisection steps so that the effective sample size of
+the weights is F times the candidates kept.  With either the report gains ``weighting_last_tick``: the temperature used, the ESS
+and the kept count of each diffusion step of the LAST tick, which is what the device keeps of an episode it runs on its own; with
+``--online``, where the script sees every tick, it gains ``weighting`` instead: one entry per tick, its last step's.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --reject_nonfinite --ess_frac 0.25
+
 A demo plan (``--enable_demo``) compares its 50 planned steps with the env's 50 demo rows; in an episode the demo has to move
 with the system.  ``--demo_clip env|FILE.npy`` (include/mbd_hip.h mbd_mpc_demo; DESIGN.md section 1 "N10 demo clock") sets the
 clip the episode follows — the env's own demo, or an array [n_track, L, 3] (car2d: [L, 2]) — and ``--demo_start c0`` the clip
@@ -151,6 +161,11 @@ class MpcArgs(Args):
     effort_cost: float = 0.0  # lambda_u: the controller's own cost on sum_h u^2 of a candidate (mbd_objective) ...
     rate_cost: float = 0.0  # ... lambda_du on sum_h (u_h - u_{h-1})^2, u_{-1} the last row committed before the plan begins
     act_weight: str = ""  # FILE.npy: the two costs' weights per actuator [Nu]
+    reject_nonfinite: bool = False  # candidates whose reward is NaN or infinite get weight 0 and leave the statistics (mbd_weighting)
+    ess_frac: float = 0.0  # F > 0: every step chooses its temperature so that the effective sample size is F times the candidates kept ...
+    temp_min: float = 0.01  # ... inside [temp_min, temp_max] ...
+    temp_max: float = 10.0
+    ess_iters: int = 12  # ... by this many bisection steps
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -322,6 +337,28 @@ def _objective_settings(args: MpcArgs) -> dict:
     return {f: getattr(args, f) for f in _OBJECTIVE_FIELDS} if _has_objective(args) else {}
 
 
+def _has_weighting(args: MpcArgs) -> bool:
+    """Whether the arguments ask for a weighting record at all (rejection, or an ESS target)."""
+    return bool(args.reject_nonfinite) or args.ess_frac != 0.0
+
+
+def _weighting_of(args: MpcArgs) -> dict:
+    """``Plan.set_weighting``'s arguments (the bracket only with a target)."""
+    ess = args.ess_frac != 0.0
+    return dict(reject_nonfinite=args.reject_nonfinite, ess_frac=args.ess_frac, temp_min=args.temp_min if ess else None,
+                temp_max=args.temp_max if ess else None, iters=args.ess_iters)
+
+
+def _weighting_settings(args: MpcArgs) -> dict:
+    return dict(reject_nonfinite=args.reject_nonfinite, ess_frac=args.ess_frac, temp_min=args.temp_min, temp_max=args.temp_max,
+                ess_iters=args.ess_iters) if _has_weighting(args) else {}
+
+
+def _weighting_log(log: dict) -> dict:
+    """A peeked log as JSON-ready lists."""
+    return dict(temp=[float(x) for x in log["temp"]], ess=[float(x) for x in log["ess"]], kept=[int(x) for x in log["kept"]])
+
+
 def _has_delay(args: MpcArgs) -> bool:
     """Whether the arguments ask for a delay record at all (the default: none)."""
     return args.delay_ticks != 0
@@ -466,6 +503,8 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
         plan.set_mpc_demo(*_demo_of(env, args))
     if _has_objective(args):
         plan.set_objective(**_objective_of(args))
+    if _has_weighting(args):
+        plan.set_weighting(**_weighting_of(args))
     return env, plan, state_init, rng_exp
 
 
@@ -484,10 +523,13 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
     pe = env if plant is None else plant
     T, E = args.n_ticks, args.exec_steps
     s = np.ascontiguousarray(state_init.pipeline_state, np.float32).reshape(-1)
-    actions, rewards, states, means, predicted, secs = [], [], [s], [], [], []
+    actions, rewards, states, means, predicted, secs, wlog = [], [], [s], [], [], [], []
     with plan.mpc_open(key, args.warm_steps, E, T) as session:
         for _ in range(T):
             out = session.tick(s)
+            if _has_weighting(args):  # (between ticks: the tick's last score step)
+                wl = plan.peek_weighting()
+                wlog.append((wl["temp"][-1], wl["ess"][-1], wl["kept"][-1]))
             rows = out["head"]  # (the rows to execute now: the plan's own first rows, or under a delay record the queue's head)
             rewss, fin = pe.rollout(State(s, None, np.float32(0), np.float32(0), {}), rows[None], want_final=True)
             s = fin[0].cpu().numpy().reshape(-1)
@@ -501,6 +543,9 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
               seconds=float(np.sum(secs)), tick_seconds=np.asarray(secs, np.float64))
     if plan._has_delay:
         ep["predicted"] = np.stack(predicted)
+    if wlog:  # per tick: the temperature, ESS and kept count of the tick's last step
+        ep["weighting"] = dict(temp=np.array([w[0] for w in wlog], np.float32), ess=np.array([w[1] for w in wlog], np.float32),
+                               kept=np.array([w[2] for w in wlog], np.int32))
     return ep
 
 
@@ -571,6 +616,8 @@ def _setup_batch(arg_list, device: int):
         sweep.set_mpc_demo(*_demo_of(env, a0))
     if _has_objective(a0):  # (and one objective)
         sweep.set_objective(**_objective_of(a0))
+    if _has_weighting(a0):  # (and one weighting record)
+        sweep.set_weighting(**_weighting_of(a0))
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -607,7 +654,7 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
         if _has_basis(arg_list[0]):
             shape = dict(shape, **_basis_settings(arg_list[0]))
         shape = dict(shape, **_delay_settings(arg_list[0]), **_demo_settings(arg_list[0]), **_sigma_settings(arg_list[0]),
-                     **_objective_settings(arg_list[0]))
+                     **_objective_settings(arg_list[0]), **_weighting_settings(arg_list[0]))
         windows = {"demo_windows": ep["demo_windows"]} if "demo_windows" in ep else {}  # (one table: every episode's)
         return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, **windows, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
                               **_plant_settings(arg_list[k]), **shape) for k in range(len(arg_list))]
@@ -635,6 +682,8 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
     env, plan, state_init, key = _setup(args, 0 if device is None else device)
     try:
         ep = plan.run_mpc(key, args.n_ticks, args.warm_steps, args.exec_steps)
+        if _has_weighting(args):  # (the device log holds the last tick's score steps: their temperature, ESS and kept count)
+            ep["weighting_last_tick"] = plan.peek_weighting()
     finally:
         plan.close()
     reward = float(ep["rewards"].mean())
@@ -645,7 +694,8 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         shape = _shape_settings(args) if _has_shape(args) else {}
         if _has_basis(args):
             shape = dict(shape, **_basis_settings(args))
-        shape = dict(shape, **_delay_settings(args), **_demo_settings(args), **_sigma_settings(args), **_objective_settings(args))
+        shape = dict(shape, **_delay_settings(args), **_demo_settings(args), **_sigma_settings(args), **_objective_settings(args),
+                     **_weighting_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -689,6 +739,7 @@ def _main(argv=None) -> dict:
         plan.run_mpc(key, T, K, E)  # warm-up
         _, _, _, open_secs = plan.run(key)
         ep = plan.run_mpc(key, T, K, E)
+        wlog = plan.peek_weighting() if _has_weighting(args) else None
         nominal = None
         if _has_plant(args):  # what the perturbation cost: the same episode without the record
             plan.clear_mpc_plant()
@@ -717,6 +768,8 @@ def _main(argv=None) -> dict:
         res.update(_objective_settings(args), action_rate=action_rate(ep["actions"]))
     if _has_demo(args):
         res.update(_demo_settings(args), track_err_mean=float(ep["track_err"].mean()))
+    if wlog is not None:  # (the last tick's score steps)
+        res.update(_weighting_settings(args), weighting_last_tick=_weighting_log(wlog))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -749,6 +802,8 @@ def _main_online(args: MpcArgs) -> dict:
     res.update(_sigma_settings(args))
     if _has_objective(args):
         res.update(_objective_settings(args), action_rate=action_rate(ep["actions"]))
+    if "weighting" in ep:  # (per tick)
+        res.update(_weighting_settings(args), weighting=_weighting_log(ep["weighting"]))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -794,6 +849,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
             plan.set_mpc_demo(*_demo_of(env, a0))
         if _has_objective(a0):
             plan.set_objective(**_objective_of(a0))
+        if _has_weighting(a0):
+            plan.set_weighting(**_weighting_of(a0))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -822,6 +879,7 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
     res.update(_sigma_settings(a0))
     if _has_objective(a0):
         res.update(_objective_settings(a0), action_rate=action_rate(ep["actions"]))
+    res.update(_weighting_settings(a0))
     if _has_demo(a0):
         res.update(_demo_settings(a0), track_err_mean=float(ep["track_err"].mean()))
     if not a0.not_render:
