@@ -30,8 +30,15 @@ def next_sigma(sigma_end, cold, warm, gain):
     return f(x)
 
 
-def plan_tick(oenv, s_plan, r, mu, sigma, n_it, N, H, temp, method, impl=1):
-    """n_it refinements (path_integral.py:113-126) from the state ``s_plan``.  Returns (r', mu, sigma: float32)."""
+def orc_update(orc, m, rews, Y0s, mu, sigma, temp):
+    """The update rule of a refinement: (mu, sigma) of Oracle.pi_update."""
+    mu, sigma, _, _ = orc.pi_update(m, rews, Y0s, mu, float(sigma), temp)  # :122-125
+    return mu, sigma
+
+
+def plan_tick(oenv, s_plan, r, mu, sigma, n_it, N, H, temp, method, impl=1, update=orc_update):
+    """n_it refinements (path_integral.py:113-126) from the state ``s_plan``.  Returns (r', mu, sigma: float32).  ``update``: a
+    stand-in for ``orc_update`` with its signature (a weighting record's: tests/weighting_checker.py)."""
     orc = oenv.orc
     m = METHODS[method] if isinstance(method, str) else int(method)
     for _ in range(n_it):
@@ -39,16 +46,17 @@ def plan_tick(oenv, s_plan, r, mu, sigma, n_it, N, H, temp, method, impl=1):
         r, ks = keys[0], keys[1]  # rng, Y0s_rng = split(rng)  (:114)
         Y0s = orc.sample(ks, impl, N, H, oenv.Nu, 0, N, float(sigma), mu)  # :115-119
         rews = op.mean_h(orc, np.ascontiguousarray(oenv.rollout(s_plan, Y0s)))  # :121
-        mu, sigma, _, _ = orc.pi_update(m, rews, Y0s, mu, float(sigma), temp)  # :122-125
+        mu, sigma = update(orc, m, rews, Y0s, mu, sigma, temp)
         sigma = np.float32(sigma)
     return r, mu, np.float32(sigma)
 
 
 def episode(oenv, state0, key, N, H, Nd, temp, T, K, E, method, sigma_cold=1.0, sigma_warm=1.0, gain=0.0, D=0, rows0=None,
-            plant=None, dkey=None, act_std=0.0, kick_std=0.0, kick_every=1, impl=1):
+            plant=None, dkey=None, act_std=0.0, kick_std=0.0, kick_every=1, impl=1, plan_tick=plan_tick):
     """A closed-loop episode of T ticks.  ``D`` > 0: the plans arrive D ticks late (mpc_delay_checker).  ``dkey`` not None: a
     plant record (mpc_plant_checker).  Returns dict(actions [T*E, Nu], rewards [T*E], states [T+1, S], means [T, H, Nu],
-    sigmas [T, 2] — the sigma each tick started from and ended with —, and with a delay predicted [T, S])."""
+    sigmas [T, 2] — the sigma each tick started from and ended with —, and with a delay predicted [T, S]).  ``plan_tick``: a stand-in
+    for this module's, with its signature."""
     orc = oenv.orc
     Nu = oenv.Nu
     has_plant = dkey is not None
@@ -99,8 +107,9 @@ class Session:
     from it and returns dict(mean, rows, sigma: (start, end)); ``reset_mean`` makes the next tick cold, sigma included;
     ``sigma`` is what the next tick starts from."""
 
-    def __init__(self, oenv, key, N, H, Nd, temp, K, E, method, sigma_cold=1.0, sigma_warm=1.0, gain=0.0, impl=1):
+    def __init__(self, oenv, key, N, H, Nd, temp, K, E, method, sigma_cold=1.0, sigma_warm=1.0, gain=0.0, impl=1, plan_tick=plan_tick):
         self.oenv, self.rng = oenv, np.asarray(key, np.uint32)
+        self.plan_tick = plan_tick
         self.cfg = (N, H, temp, method, impl)
         self.Nd, self.K, self.E = Nd, K, E
         self.rec = (sigma_cold, sigma_warm, gain)
@@ -116,7 +125,7 @@ class Session:
         self.rng, r = keys[0], keys[1]
         s = np.ascontiguousarray(state, np.float32).reshape(-1)
         start = np.float32(self.sigma)
-        _, M, end = plan_tick(self.oenv, s, r, self.mu, start, self.n_it, N, H, temp, method, impl)
+        _, M, end = self.plan_tick(self.oenv, s, r, self.mu, start, self.n_it, N, H, temp, method, impl)
         self.mu, self.n_it = shift(M, self.E), self.K
         self.sigma = next_sigma(end, *self.rec)
         return dict(mean=M, rows=M[: self.E].copy(), sigma=(start, np.float32(end)))

@@ -168,17 +168,18 @@ def pi_plan(orc, oenv, rec: Record, state0, key, N, H, Nd, temp, method, impl=1)
 
 
 def episode(oenv, rec: Record, state0, key, N, H, Nd, temp, T, K, E, D=0, rows0=None, plant=None, dkey=None, act_std=0.0,
-            method=None, sigma=(1.0, 1.0, 0.0), env=None, prev=None, reset_at=(), env_of_tick=None, impl=1, **session_kw):
+            kick_std=0.0, kick_every=1, method=None, sigma=(1.0, 1.0, 0.0), env=None, prev=None, reset_at=(), env_of_tick=None, impl=1, **session_kw):
     """A closed-loop episode of T ticks under the record.  The previous action: in the first tick the clipped last row of the
     committed queue (D > 0), else clip(prev0) or none; afterwards clip(M_{t-1}[E-1]) — the commanded row, whatever a plant adds.
     ``env`` / ``prev``: an env that already wraps ObjectiveEnvs (an ensemble) and the ``Prev`` they share.  ``method``: a
     path-integral update (mpc_pi_checker.Session, no delay) instead of the MBD session.  ``reset_at``: ticks in front of which the
     mean is reset (a session's reset_mean: prev stays).  ``env_of_tick(t, prev)``: the env tick t plans with (a demo record: the tick's
-    window wrapped in an ObjectiveEnv on the shared ``prev``; ``session_kw`` then carries a ``reverse_once`` with enable_demo).  Returns dict(actions, rewards, states, means, last)."""
+    window wrapped in an ObjectiveEnv on the shared ``prev``; ``session_kw`` then carries a ``reverse_once`` with enable_demo; a
+    weighting record: weighting_checker's ``reverse_once``, or its ``plan_tick`` for a path-integral session).  Returns dict(actions, rewards, states, means, last)."""
     import mpc_online_checker as online
     import mpc_pi_checker as pic
     from mpc_checker import execute
-    from mpc_plant_checker import disturbances, rows_of
+    from mpc_plant_checker import disturbances, kick, rows_of
     orc, Nu = oenv.orc, oenv.Nu
     if env_of_tick is not None:
         prev = Prev(rec.prev0)
@@ -189,7 +190,7 @@ def episode(oenv, rec: Record, state0, key, N, H, Nd, temp, T, K, E, D=0, rows0=
     if method is None:
         sess = online.Session(env, key, N, H, Nd, temp, K, E, D, rows0, impl=impl, **session_kw)
     else:
-        sess = pic.Session(env, key, N, H, Nd, temp, K, E, method, *sigma, impl=impl)
+        sess = pic.Session(env, key, N, H, Nd, temp, K, E, method, *sigma, impl=impl, **session_kw)
     prev.value = clip(sess.C.reshape(-1, Nu)[-1]) if D else clip(rec.prev0)
     plant = oenv if plant is None else plant
     dk = None if dkey is None else np.asarray(dkey, np.uint32)
@@ -208,6 +209,8 @@ def episode(oenv, rec: Record, state0, key, N, H, Nd, temp, T, K, E, D=0, rows0=
             rows = rows_of(rows, E, eps, act_std)
         rew, s = execute(plant, s, rows)
         s = np.asarray(s, f32).reshape(-1)
+        if dk is not None and kick_std > 0 and (t + 1) % kick_every == 0:  # (mpc_plant_checker.episode's kick)
+            s = kick(plant, s, (f32(kick_std) * eps[E * Nu:].astype(f32)).astype(f32))
         actions.append(rows)
         rewards.append(rew)
         states.append(s)

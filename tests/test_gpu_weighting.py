@@ -158,11 +158,11 @@ def test_whole_run_under_an_ess_target(gpu, orc):
         plan.close()
 
 
-@pytest.mark.parametrize("method", [0, 1])
+@pytest.mark.parametrize("method", [0, 1, 2, 3])
 @pytest.mark.parametrize("P", [3, 8])
 def test_sweeps_equal_their_plans_alone(gpu, method, P):
     """P plans with distinct temperatures and one record in one sweep: plan k's run and log are the single plan's with that
-    temperature and record, bit for bit (MBD and mppi; P = 8: the plan-to-XCD mapping)."""
+    temperature and record, bit for bit (MBD, mppi, cma-es and cem; P = 8: the plan-to-XCD mapping)."""
     from mbd_hip.planners.mbd_planner import Plan, Sweep
     name = "hopper"
     env, N, Nd = _env(name), 80, 4

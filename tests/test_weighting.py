@@ -179,3 +179,139 @@ def test_cli_flags_map_to_the_record():
     assert (rec.reject_nonfinite, rec.iters) == (0, 7)
     assert (np.float32(rec.ess_frac), np.float32(rec.temp_min), np.float32(rec.temp_max)) == (np.float32(0.3), np.float32(0.02), np.float32(5.0))
     assert mpc._weighting_settings(a) == dict(reject_nonfinite=False, ess_frac=0.3, temp_min=0.02, temp_max=5.0, ess_iters=7)
+
+
+# ---- the record together with the other records (tests/weighting_combined_inputs.py; tests/test_gpu_weighting_combined.py) ---------
+@pytest.mark.parametrize("N", [5, 64, 1025])
+@pytest.mark.parametrize("H,Nu", [(3, 2), (30, 3)], ids=["HNu6", "HNu90"])
+def test_pi_update_sigma_equals_the_c_checker(orc, N, H, Nu):
+    """``wc.pi_update`` — cma-es' sigma restated from given weights: the sequential fma per output, the 64 strided partials, the
+    wavefront's butterfly, the floor — against orc.pi_update where the two must coincide: nothing dropped, ess_frac = 0, spread >=
+    1e-4 (the path-integral score has no guard).  HNu = 6 leaves 58 partials at +0, HNu = 90 gives 26 of them two terms."""
+    Y0s, mu = pi.candidates(N, H=H, Nu=Nu)
+    n = 0
+    for shape in ("normal", "quantised", "two_values"):
+        if shape not in pi.shapes(N):
+            continue
+        rews = pi.rewards(shape, N)
+        if rews.astype(np.float64).std() < 2e-4:
+            continue
+        for sigma0 in (0.7, 1e-3):
+            res = wc.weigh(orc, rews, 0.5, wc.Record(reject_nonfinite=True))
+            assert res["kept"] == N and res["branch"] == "fixed"
+            for method in (1, 2, 3):
+                mu_r, sig_r, w_r, _ = orc.pi_update(method, rews, Y0s, mu, sigma0, 0.5)
+                out, sig = wc.pi_update(orc, method, res, Y0s, mu, sigma0)
+                same_bits(res["weights"], w_r, f"{shape} N={N}: weights")
+                same_bits(out, mu_r, f"{shape} N={N} method {method}: mean")
+                same_bits(sig, np.float32(sig_r), f"{shape} N={N} method {method}: sigma from {sigma0}")
+                if method != 2:
+                    assert sig == np.float32(sigma0)
+                elif sigma0 == 1e-3:  # (the spread of candidates within [-1, 1] is below 1: the floor holds the carry)
+                    assert sig == np.float32(1e-3)
+        n += 1
+    assert n >= 2
+
+
+def test_pi_update_sigma_floor_and_nan(orc):
+    """Every weight +0 (all dropped): the spread is +0 and sigma is the 1e-3 floor; a NaN weight keeps sigma NaN."""
+    Y0s, mu = pi.candidates(64, H=3, Nu=2)
+    res = wc.weigh(orc, np.full(64, np.nan, np.float32), 0.1, wc.Record(reject_nonfinite=True))
+    assert wc.pi_update(orc, 2, res, Y0s, mu, 0.7)[1].view(np.uint32) == np.float32(1e-3).view(np.uint32)
+    res = wc.weigh(orc, np.full(64, np.nan, np.float32), 0.1, wc.Record(reject_nonfinite=False))
+    assert np.isnan(wc.pi_update(orc, 2, res, Y0s, mu, 0.7)[1])
+
+
+@pytest.mark.parametrize("method", ["mppi", "cma-es", "cem"])
+def test_plan_tick_under_a_record_that_changes_nothing(method):
+    """``wc.plan_tick`` under rejection alone on healthy rollouts is mpc_pi_checker.plan_tick, and an episode over it the plain
+    episode, sigmas included; the defaults of ``plan_tick=`` / ``update=`` leave mpc_pi_checker's own results alone (the other
+    CPU tests of tests/test_mpc_pi.py run on them)."""
+    import mpc_pi_cases as cases
+    import mpc_pi_checker as pic
+    oe, o = cases.oenv("hopper"), cases._orc()
+    s0, key = cases.start("hopper")
+    N, H = 33, 4
+    mu = (np.random.default_rng(2).normal(size=(H, oe.Nu)) * 0.3).astype(np.float32)
+    a = pic.plan_tick(oe, s0, key, mu, np.float32(0.7), 2, N, H, 0.1, method)
+    log = []
+    b = wc.plan_tick(oe, s0, key, mu, np.float32(0.7), 2, N, H, 0.1, method, rec=wi.REJECT, log=log)
+    for x, y, what in zip(a, b, ("key", "mean", "sigma")):
+        same_bits(np.asarray(x), np.asarray(y), f"{method}: {what}")
+    assert [e[2] for e in log] == [N, N] and all(e[0] == np.float32(0.1) for e in log)
+    rec = (1.0, 0.5, 0.9 if method == "cma-es" else 0.0)
+    plain = pic.episode(oe, s0, key, N, H, 4, 0.1, 2, 2, 1, method, *rec)
+    under = pic.episode(oe, s0, key, N, H, 4, 0.1, 2, 2, 1, method, *rec, plan_tick=functools.partial(wc.plan_tick, rec=wi.REJECT))
+    for k in plain:
+        same_bits(under[k], plain[k], f"{method} episode: {k}")
+    sess = pic.Session(oe, key, N, H, 4, 0.1, 2, 1, method, *rec, plan_tick=functools.partial(wc.plan_tick, rec=wi.REJECT))
+    for t in range(2):
+        same_bits(sess.tick(plain["states"][t])["mean"], plain["means"][t], f"{method} session, tick {t}")
+
+
+# wc.episode of the commit before ``reverse_once`` took oracle.planner's signature — its own loop over mpc_checker.execute and
+# shift —, recorded from that code: hopper from mpc_pi_cases.start, N = 33, H = 4, Ndiffuse = 4, T = 3, K = 2, E = 1 under wi.ESS.
+# sha256 of the float32 arrays' bytes, and the log as (temp bits, ess bits, kept) per step per tick.
+_EPISODE_BEFORE = dict(
+    actions="d83204212266dd4243aaf7e33b61051384de2997056fa8da2fabb97453f4374c",
+    rewards="2c5ade4529a7e148f215ec96797ffa0692fce34692c388cc920d25052779c1de",
+    states="5af2c46d3c94e4d73c66bfd3fec9b8553074e7c4c58033c85545d235feca2c84",
+    means="df8586a100b7b958d5bc89f43fc5a6d5f53ee40804640c6f26a253b3d3e5a52c",
+    log=[[(1052168149, 1090781429, 33), (1054513261, 1090795796, 33), (1061922109, 1090781706, 33)],
+         [(1051849190, 1090784108, 33), (1057540026, 1090794013, 33)], [(1056390106, 1090783122, 33), (1061436012, 1090795477, 33)]])
+
+
+def test_episode_keeps_the_bits_it_had_before_it_became_a_composition():
+    """``wc.episode`` is now objective_checker.episode over ``wc.reverse_once``; its results are the recorded ones, bit for bit; so
+    is mpc_online_checker's session handed ``wc.reverse_once`` directly."""
+    import hashlib
+
+    import mpc_online_checker as online
+    import mpc_pi_cases as cases
+    oe = cases.oenv("hopper")
+    s0, key = cases.start("hopper")
+    ep = wc.episode(oe, s0, key, 33, 4, 4, 0.1, 3, 2, 1, wi.ESS)
+    for k in ("actions", "rewards", "states", "means"):
+        assert hashlib.sha256(np.ascontiguousarray(ep[k], np.float32).tobytes()).hexdigest() == _EPISODE_BEFORE[k], k
+    bits = [[(int(np.float32(t).view(np.uint32)), int(np.float32(e).view(np.uint32)), int(k)) for t, e, k in tick] for tick in ep["log"]]
+    assert bits == _EPISODE_BEFORE["log"]
+    got = online.session(oe, key, ep["states"][:3], 33, 4, 4, 0.1, 2, 1, reverse_once=functools.partial(wc.reverse_once, rec=wi.ESS))
+    same_bits(got["means"], ep["means"], "a session over wc.reverse_once")
+
+
+def test_combined_cases_reach_what_they_are_there_for(orc):
+    """Of the very cases tests/test_gpu_weighting_combined.py runs, in the checker: the real-divergence launches drop between 1 and
+    N - 1 candidates (one step under every method's sigma; every tick of the closed loop, whose means and states stay finite); behind
+    an objective and behind an ensemble the selection takes the loop and a clamp; an ensemble with a diverged member drops some
+    candidates and keeps some; the objective moves the temperatures; the cem case has three positive weights among twelve kept."""
+    import weighting_combined_inputs as wci
+    for method in (0, 1):  # (one sigma for MBD, one for the path-integral plans)
+        d = wci.divergence_step(orc, method)
+        kept = int(np.isfinite(d["rews"]).sum())
+        assert 0 < kept < wci.STEP["N"], (method, kept)
+        assert (d["Y0s"][:, :, 0] != 0).all()  # (no candidate is spared by a zero: the shape is not zero there)
+    ep = wci.divergence_episode(orc, wi.REJECT)
+    assert np.isfinite(ep["means"]).all() and np.isfinite(ep["states"]).all()
+    assert all(0 < e[2] < wci.LOOP["N"] for tick in ep["log"] for e in tick), ep["log"]
+    with_o, without = wci.objective_episode(orc, wi.ESS), wci.objective_episode(orc, wi.ESS, with_objective=False)
+    assert all(a[0] != b[0] for ta, tb in zip(with_o["log"], without["log"]) for a, b in zip(ta, tb))
+    seen = {wci.branch_of(e, wi.ESS) for tick in with_o["log"] for e in tick} | {wci.branch_of(e, wci.FULL) for e in wci.objective_run(orc, wci.FULL)["log"]}
+    assert {"loop", "max"} <= seen, seen
+    seen, drops = set(), []
+    for N, bad, risk, with_obj in wci.ENSEMBLES:
+        st = wci.ensemble_step(orc, N, bad, risk, wi.ESS, with_obj)
+        kept = st["log"][0][2]
+        assert kept == int(np.isfinite(st["det"]["rews"]).sum())
+        drops.append(N - kept)
+        seen.add(wci.branch_of(st["log"][0], wi.ESS))
+        assert 0 < kept < N, (N, bad, risk, kept)
+    for N, bad, risk, with_obj in (wci.ENSEMBLES[0], wci.ENSEMBLES[-1]):  # (the later steps of an episode keep more: the loop)
+        ep = wci.ensemble_episode(orc, N, bad, risk, wi.ESS, with_obj)
+        assert np.isfinite(ep["means"]).all() and all(0 < e[2] < N for tick in ep["log"] for e in tick)
+        seen |= {wci.branch_of(e, wi.ESS) for tick in ep["log"] for e in tick}
+    seen |= {wci.branch_of(e, wci.FULL) for e in wci.ensemble_step(orc, 33, 2, "min", wci.FULL)["log"]}
+    assert {"loop", "min", "max"} <= seen, seen
+    r, rec = wci.cem_ties()["few_positive"]
+    res = wc.weigh(orc, r, 0.1, rec)
+    assert res["kept"] == 12 and int((res["weights"] > 0).sum()) == 3 and res["branch"] == "min"
+    assert (res["weights"][[0, 1, 2, 4, 5, 6, 7, 8, 9]].view(np.uint32) == 0).all()  # kept, and +0 like the dropped ones

@@ -7,7 +7,9 @@ own — goes through the oracle's ``dot``: dot((d, 1, 0), (d, acc, 0)) = fma(d, 
 
 ``weigh`` is the contract; ``update`` is what the untouched downstream kernels make of given weights (the weighted mean in wsum64's
 order with the score form, cem's selection), restated so that a step, a run and an episode can be checked with ``weigh`` standing
-in the score's place; ``reverse_once`` / ``run`` / ``episode`` are oracle.planner's and mpc_checker's loops with that step."""
+in the score's place; ``reverse_once`` is oracle.planner's step with that (same signature, same return value: it stands wherever
+a checker takes a ``reverse_once``), ``run`` / ``episode`` the loops over it; ``pi_update`` / ``plan_tick`` are the path-integral
+plans' update (cma-es' sigma from the given weights included) and mpc_pi_checker's tick with it."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -196,18 +198,25 @@ def update(orc, method, w, Y0s, Ybar_i, sched=None, i=None, literal=True):
     return m.reshape(shape)
 
 
-def reverse_once(orc, env, state0, i, rng, Ybar_i, sched, N, H, T0, rec: Record, impl=1, log=None):
-    """oracle.planner.reverse_once with ``weigh`` in the score's place.  Returns (rng', Ybar_im1, rew_mean); ``log``: a list the
-    step's (temp, ess, kept) is appended to."""
+def reverse_once(orc, env, state0, i, rng, Ybar_i, sched, N, H, T0, impl=1, enable_demo=False, literal=True, timers=None, *,
+                 rec: Record = Record(reject_nonfinite=False), log=None):
+    """oracle.planner.reverse_once with ``weigh`` in the score's place, in its signature and with its return value — (rng',
+    Ybar_im1, rew_mean, details) — so that ``functools.partial(reverse_once, rec=..., log=...)`` stands wherever a checker takes a
+    ``reverse_once`` (mpc_online_checker.Session, objective_checker.episode).  ``env`` is seen through ``.rollout`` only: an
+    ObjectiveEnv, an EnsembleEnv, a plain OracleEnv.  ``log``: a list the step's (temp, ess, kept) is appended to."""
     from oracle import planner as op
+    if enable_demo:
+        raise ValueError("a weighting record is refused on demo plans")
     keys = orc.split(rng, 2, impl)
     rng, ks = keys[0], keys[1]
     Y0s = orc.sample(ks, impl, N, H, env.Nu, 0, N, float(sched[2][i]), Ybar_i)
-    rews = op.mean_h(orc, np.ascontiguousarray(env.rollout(state0, Y0s)))
+    rewss = env.rollout(state0, Y0s)
+    rews = op.mean_h(orc, np.ascontiguousarray(rewss))
     res = weigh(orc, rews, T0, rec)
     if log is not None:
         log.append((res["temp"], res["ess"], res["kept"]))
-    return rng, update(orc, 0, res["weights"], Y0s, Ybar_i, sched, i), res["rew_mean"]
+    out = update(orc, 0, res["weights"], Y0s, Ybar_i, sched, i, literal=literal)
+    return rng, out, res["rew_mean"], dict(Y0s=Y0s, rewss=rewss, rews=rews, weights=res["weights"], res=res)
 
 
 def run(orc, env, state0, key, N, H, Nd, T0, rec: Record, impl=1, beta0=1e-4, betaT=1e-2):
@@ -216,31 +225,88 @@ def run(orc, env, state0, key, N, H, Nd, T0, rec: Record, impl=1, beta0=1e-4, be
     r, Ybar = np.asarray(key, np.uint32), np.zeros((H, env.Nu), f32)
     mus, rms, log = [], [], []
     for i in range(Nd - 1, 0, -1):
-        r, Ybar, rm = reverse_once(orc, env, state0, i, r, Ybar, sched, N, H, T0, rec, impl, log)
+        r, Ybar, rm, _ = reverse_once(orc, env, state0, i, r, Ybar, sched, N, H, T0, impl, rec=rec, log=log)
         mus.append(Ybar)
         rms.append(rm)
     return dict(mu_0ts=np.stack(mus), rew_means=np.array(rms, f32), log=log)
 
 
-def episode(oenv, state0, key, N, H, Nd, T0, T, K, E, rec: Record, impl=1, beta0=1e-4, betaT=1e-2):
-    """mpc_checker.episode with ``weigh`` in the score's place; beside its results, ``log``: per tick the (temp, ess, kept) of the
-    tick's steps."""
-    import mpc_checker as mc
-    orc = oenv.orc
-    sched = orc.schedule(beta0, betaT, Nd)
-    rng = np.asarray(key, np.uint32)
-    s = np.ascontiguousarray(state0, f32).reshape(-1)
-    Ybar, i_start = np.zeros((H, oenv.Nu), f32), Nd - 1
-    actions, rewards, states, means, logs = [], [], [s], [], []
-    for _ in range(T):
-        keys = orc.split(rng, 2, impl)
-        rng, r = keys[0], keys[1]
-        log = []
-        for i in range(i_start, 0, -1):
-            r, Ybar, _ = reverse_once(orc, oenv, s, i, r, Ybar, sched, N, H, T0, rec, impl, log)
-        M = Ybar
-        rew, s = mc.execute(oenv, s, M[:E])
-        actions.append(M[:E]); rewards.append(rew); states.append(s); means.append(M); logs.append(log)
-        Ybar, i_start = mc.shift(M, E), K
-    return dict(actions=np.concatenate(actions), rewards=np.concatenate(rewards), states=np.stack(states), means=np.stack(means),
-                log=logs)
+def ticks_of(log, Nd, K, T):
+    """A flat episode log as one list per tick: Nd - 1 entries for the cold tick 0, K for every warm one."""
+    cuts = np.cumsum([0, Nd - 1] + [K] * (T - 1))
+    assert len(log) == cuts[-1], (len(log), cuts)
+    return [log[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+
+
+def episode(oenv, state0, key, N, H, Nd, T0, T, K, E, rec: Record, impl=1, beta0=1e-4, betaT=1e-2, **kw):
+    """objective_checker.episode (mpc_online_checker's session tick by tick, mpc_checker's executed rows; no objective record
+    unless ``kw`` brings an ``env`` that holds one) with ``reverse_once`` in the step's place; beside its results, ``log``: per
+    tick the (temp, ess, kept) of the tick's steps.  ``kw``: D, rows0, plant, dkey, act_std, env, prev, orec (an objective
+    record: objective_checker.Record)."""
+    import functools
+
+    import objective_checker as oc
+    log = []
+    orec = kw.pop("orec", None)
+    if orec is None:
+        orec = oc.Record()
+        kw.setdefault("env", oenv)
+        kw.setdefault("prev", oc.Prev())
+    out = oc.episode(oenv, orec, state0, key, N, H, Nd, T0, T, K, E, impl=impl, beta0=beta0, betaT=betaT,
+                     reverse_once=functools.partial(reverse_once, rec=rec, log=log), **kw)
+    out["log"] = ticks_of(log, Nd, K, T)
+    return out
+
+
+# ---- path-integral plans under a record ------------------------------------------------------------------------------------------
+def _wave_sum(part):
+    """One wavefront's xor-butterfly sum of 64 partials (lane 0's value)."""
+    x = np.asarray(part, f32).copy()
+    lanes = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        x = (x + x[lanes ^ off]).astype(f32)
+    return f32(x[0])
+
+
+def cma_sigma(orc, w, Y0s, mu, sigma):
+    """cma_spread_kernel and cma_sigma_kernel restated for given weights: s[e] = sqrt(acc), acc = fma(w[n], d * d, acc) over n
+    ascending from +0 with d = Y0s[n][e] - mu[e] and d * d rounded; part[t] = sum of s[i], i = t, t + 64, ...; the wavefront's
+    butterfly; / HNu, * sigma, and max(., 1e-3) as ``sig < 1e-3 ? 1e-3 : sig``, which keeps a NaN."""
+    Y = np.ascontiguousarray(Y0s, f32).reshape(np.shape(Y0s)[0], -1)
+    m = np.asarray(mu, f32).reshape(-1)
+    HNu = Y.shape[1]
+    with np.errstate(all="ignore"):
+        acc = np.zeros(HNu, f32)
+        for n in range(Y.shape[0]):
+            d = (Y[n] - m).astype(f32)
+            acc = _fma(orc, w[n], (d * d).astype(f32), acc)
+        s = np.sqrt(acc).astype(f32)
+        part = np.zeros(64, f32)
+        for i0 in range(0, HNu, 64):
+            seg = s[i0:i0 + 64]
+            part[:seg.shape[0]] = (part[:seg.shape[0]] + seg).astype(f32)
+        sig = f32(f32(_wave_sum(part) / f32(HNu)) * f32(sigma))
+        return f32(1e-3) if sig < f32(1e-3) else sig
+
+
+def pi_update(orc, method, res, Y0s, mu, sigma):
+    """What a path-integral plan makes of ``weigh``'s result ``res``: (the new mean — ``update`` —, sigma: cma-es' new one,
+    otherwise the one given)."""
+    out = update(orc, int(method), res["weights"], Y0s, mu)
+    if int(method) == 2:
+        return out, cma_sigma(orc, res["weights"], Y0s, mu, sigma)
+    return out, f32(sigma)
+
+
+def plan_tick(oenv, s_plan, r, mu, sigma, n_it, N, H, temp, method, impl=1, *, rec: Record = Record(reject_nonfinite=False), log=None):
+    """mpc_pi_checker.plan_tick with ``weigh`` and ``pi_update`` in orc.pi_update's place.  ``log``: a list every refinement's
+    (temp, ess, kept) is appended to."""
+    import mpc_pi_checker as pic
+
+    def upd(orc, m, rews, Y0s, mu_t, sig, T0):
+        res = weigh(orc, rews, T0, rec)
+        if log is not None:
+            log.append((res["temp"], res["ess"], res["kept"]))
+        return pi_update(orc, m, res, Y0s, mu_t, sig)
+
+    return pic.plan_tick(oenv, s_plan, r, mu, sigma, n_it, N, H, temp, method, impl, update=upd)
