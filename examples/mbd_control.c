@@ -2,7 +2,7 @@
  * session (mbd_plan_mpc_open) is opened once and advanced one tick per call from the state the caller's system is in.
  *
  *   gcc -O2 -I include examples/mbd_control.c -o mbd_control -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
- *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi]
+ *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi] [--pick]
  *                 env    N   H  Nd K ticks
  *
  * The "system" here is a second env the example owns, stepped with mbd_env_step — the env's rollout kernel at B = 1, H = 1 through
@@ -20,6 +20,12 @@
  *
  * Every plan carries a weighting record (mbd_weighting) with rejection on: this is the example of driving a real system, and one
  * diverged candidate must not poison the plan.
+ *
+ * --pick (with --mppi, in either order, behind everything else): a pick record (mbd_mpc_pick) with all three candidates — a tick then
+ * hands on the best of its new mean, the plan it was already committed to and the best candidate of its last step, as the planner's
+ * model values them, and its line gains "choice C value V": which one (0 mean, 1 incumbent, 2 best candidate) and the value of the
+ * plan handed on, a health signal for a loop around a real system.  (MBD_PICK_MEAN alone would report the value and change no row.)
+ * One more small rollout per tick; without the flag no record is set and nothing changes.
  *
  * Prints one line per tick: "tick T reward R ms M flags F", then "mean_reward R ms_per_tick M". */
 #include <math.h>
@@ -46,8 +52,11 @@ static int plant_step(mbd_env* plant, float* state, const float* action, float* 
 }
 
 int main(int argc, char** argv) {
-  const int mppi = argc > 1 && strcmp(argv[argc - 1], "--mppi") == 0;
-  if (mppi) argc -= 1;
+  int mppi = 0, pick = 0;
+  while (argc > 1 && (strcmp(argv[argc - 1], "--mppi") == 0 || strcmp(argv[argc - 1], "--pick") == 0)) { /* trailing flags */
+    if (strcmp(argv[argc - 1], "--mppi") == 0) mppi = 1; else pick = 1;
+    argc -= 1;
+  }
   float rate_cost = 0.0f;
   if (argc > 2 && strcmp(argv[argc - 2], "--rate_cost") == 0) {
     rate_cost = (float)atof(argv[argc - 1]);
@@ -97,6 +106,12 @@ int main(int argc, char** argv) {
     wt.reject_nonfinite = 1;
     CHECK(mbd_plan_set_weighting(plan, &wt));
   }
+  if (pick) { /* hand on the best of the mean, the incumbent and the best candidate; log the choice and the three values */
+    mbd_mpc_pick rec;
+    memset(&rec, 0, sizeof(rec));
+    rec.candidates = MBD_PICK_MEAN | MBD_PICK_PREV | MBD_PICK_BEST;
+    CHECK(mbd_plan_set_mpc_pick(plan, &rec));
+  }
   if (D > 0) { /* plans arrive D ticks late; the system starts committed to zeros */
     mbd_mpc_delay delay;
     memset(&delay, 0, sizeof(delay));
@@ -128,7 +143,14 @@ int main(int argc, char** argv) {
       if (!isfinite(head[k])) head[k] = 0.0f; /* hold */
     float reward = 0.0f;
     for (int j = 0; j < E; ++j) CHECK(plant_step(plant, state, head + (size_t)j * Nu, scratch, S, &reward));
-    printf("tick %d reward %.9g ms %.3f flags %d\n", info.tick, reward, 1e3 * info.seconds, info.flags);
+    printf("tick %d reward %.9g ms %.3f flags %d", info.tick, reward, 1e3 * info.seconds, info.flags);
+    if (pick) {
+      int32_t choice = 0;
+      float rets[3] = {0.0f, 0.0f, 0.0f};
+      CHECK(mbd_plan_peek_mpc_pick(plan, &choice, rets, NULL, 1, NULL)); /* (the most recent tick's entry) */
+      printf(" choice %d value %.9g", (int)choice, rets[choice]);
+    }
+    printf("\n");
     reward_sum += reward;
     seconds += info.seconds;
   }

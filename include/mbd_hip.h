@@ -717,6 +717,53 @@ int mbd_plan_set_weighting(mbd_plan* plan, const mbd_weighting* rec);
  * record. */
 int mbd_plan_peek_weighting(mbd_plan* plan, float* temp_out, float* ess_out, int32_t* kept_out, int capacity, int* count_out);
 
+/* ---- what a tick executes: its mean, the incumbent or the best candidate (predictive sampling's and guarded MPPI's rule; no
+ * counterpart in the reference; DESIGN.md section 1 "N15 pick") ---- */
+/* Every receding-horizon path hands on one thing, the tick's new mean M_t, which is never rolled out.  Two other plans are at hand
+ * when a tick ends: the incumbent — the plan the last tick committed to, shifted E rows: the Ybar the tick started from — and the
+ * best candidate of the tick's last step.  A pick record evaluates the three on the plan's env and hands on the best of those the
+ * record enables.  A setting of a plan (of a sweep), read by mbd_plan_run_mpc, mbd_sweep_run_mpc and both kinds of session (at open).
+ * The contract, f32 throughout.  With a record in force a tick adds, behind its last diffusion or refinement step and in front of
+ * the objective record's next previous action and of every boundary kernel:
+ *   inputs   r[N]: the rewards the last step's score read (with an objective record: the shaped returns); Y_i, sigma_i: that step's
+ *            mean and sigma; M_t: the tick's result; B_t: the Ybar the tick started from; s: the state the tick planned from (under
+ *            a delay record the predicted state).
+ *   n*       the lowest index among the maxima of the FINITE r[n] (NaN and +-inf never qualify, +0 and -0 tie); -1: none is finite.
+ *   slots    [3][H][Nu]: 0 = M_t; 1 = B_t, present except on a cold tick (tick 0; a session's tick after reset_mean); 2 = candidate
+ *            n*, present when n* >= 0, formed exactly as mbd_plan_peek forms it — clip(eps[n*] * sigma_i + Y_i) from the step's
+ *            normals with the product and the sum each rounded (a noise shape or basis is already in those normals), or row n* of
+ *            the materialised candidates (car2d, path-integral plans).  An absent slot holds M_t: the launches never change shape.
+ *   ret[3]   the plan's env's rollout of the three slots from s over H rows, ONE launch — on the planner's model, never the plant —
+ *            and under an objective record its launch over those rows with the tick's previous action.  Candidates are independent
+ *            in every launch form, so ret[2] == r[n*] bit for bit.
+ *   choice   c = -1; for k = 0, 1, 2: slot k enabled, present and isfinite(ret[k]), and (c < 0 or ret[k] > ret[c]) -> c = k; c < 0
+ *            at the end -> c = 0.  Ties keep the earlier slot; a non-finite return is never picked while a finite one is available.
+ *   output   P_t = slot c stands wherever M_t stood: the rows executed (or queued under a delay record), the shift into the next
+ *            tick's Ybar, means_out and a session's mean_out, the objective record's next previous action.
+ *   log      per tick and plan, on the device: choice, ret[3] (all three, whatever is enabled or present) and n*.
+ * A tick gains three launches (the gather of n* and the slots, the rollout, the choice), four with an objective record; in a sweep
+ * the rollout is one launch over the 3 n_plans slots.  Stream order on the handle's stream is the whole synchronisation; the extra
+ * rollout carries no progress word and no noise job, and a session's boundary kernel stays its tick's last kernel.
+ * Without a record nothing is launched and every bit is as it was.  candidates == MBD_PICK_MEAN: the episode is the episode without a
+ * record bit for bit, and the log carries the value of every executed plan.
+ * Composes with plant, delay, sigma, objective, weighting, noise-shape and noise-basis records, sweeps and sessions (under a
+ * weighting record a dropped candidate is not finite and is never n*).  rec == NULL clears.  Refused before any device access, the
+ * message naming the field: a NULL handle, candidates == 0 or with unknown bits, non-zero reserved -> MBD_ERR_INVALID; a plan created
+ * with enable_demo (its score is not the return) or carrying an ensemble record (its reward is a reduction over members) ->
+ * MBD_ERR_UNSUPPORTED, and so is mbd_plan_set_ensemble on a plan that carries a pick record; a session open on the handle ->
+ * MBD_ERR_STATE. */
+enum { MBD_PICK_MEAN = 1, MBD_PICK_PREV = 2, MBD_PICK_BEST = 4 };
+typedef struct mbd_mpc_pick {
+  int32_t candidates;  /* non-empty union of the bits above */
+  int32_t reserved[7]; /* 0 */
+} mbd_mpc_pick;
+int mbd_plan_set_mpc_pick(mbd_plan* plan, const mbd_mpc_pick* rec);
+/* The log of the last episode's or the session's ticks (HOST; any of the three may be NULL; synchronises the device): choice_out
+ * [capacity], rets_out [capacity][3], best_out [capacity].  *count_out: the ticks served so far; min(count, capacity) entries are
+ * copied — the most recent ones, oldest first, so a capacity of at least count gives the ticks from 0 on (the device keeps the last
+ * 65536 ticks of a longer session).  MBD_ERR_STATE without a record. */
+int mbd_plan_peek_mpc_pick(mbd_plan* plan, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity, int* count_out);
+
 /* ---- planning ahead of the plant: an episode whose plans take D ticks to arrive (the real-time iteration scheme; no
  * counterpart in the reference; DESIGN.md section 1 "N9 delay") ---- */
 /* The episode of mbd_plan_run_mpc plans from s_t and executes that plan's first rows from the same s_t: planning takes no time.
@@ -860,7 +907,7 @@ int mbd_plan_mpc_reset_mean(mbd_plan* plan);
 /* close: waits for a tick in flight and drops it.  NULL plan -> MBD_ERR_INVALID; no session open -> MBD_ERR_STATE.
  * mbd_plan_destroy closes an open session.  While a session is open, these calls on the same handle return MBD_ERR_STATE, the
  * message naming the session: mbd_plan_run, _run_mpc, _eval, _set_state0, _reverse_once, _sample_rollout, _score_update and
- * every mbd_plan_set_* record call (plant, ensemble, noise shape, noise basis, delay, demo, sigma, objective). */
+ * every mbd_plan_set_* record call (plant, ensemble, noise shape, noise basis, delay, demo, sigma, objective, weighting, pick). */
 int mbd_plan_mpc_close(mbd_plan* plan);
 
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
@@ -946,6 +993,14 @@ int mbd_sweep_peek_objective(mbd_sweep* sweep, int k, float* ret_out, float* cos
 int mbd_sweep_set_weighting(mbd_sweep* sweep, const mbd_weighting* rec);
 /* plan k's log of the last run or the last tick; as mbd_plan_peek_weighting; k outside [0, n_plans) -> MBD_ERR_INVALID */
 int mbd_sweep_peek_weighting(mbd_sweep* sweep, int k, float* temp_out, float* ess_out, int32_t* kept_out, int capacity, int* count_out);
+/* one pick record (mbd_mpc_pick, above) for all episodes of the sweep: episode k of mbd_sweep_run_mpc and of a sweep's session
+ * equals the single plan's with that record, bit for bit, logs included.  The gather and the choice are one launch each over the
+ * n_plans episodes (blockIdx.y = episode), the rollout one launch over the 3 n_plans slots from the episodes' own states.  Refusals
+ * as mbd_plan_set_mpc_pick's (sweeps take no ensemble). */
+int mbd_sweep_set_mpc_pick(mbd_sweep* sweep, const mbd_mpc_pick* rec);
+/* episode k's log; as mbd_plan_peek_mpc_pick; k outside [0, n_plans) -> MBD_ERR_INVALID */
+int mbd_sweep_peek_mpc_pick(mbd_sweep* sweep, int k, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity,
+                            int* count_out);
 /* one delay record (mbd_mpc_delay, above) for all episodes of the sweep: episode k of mbd_sweep_run_mpc is then
  * mbd_plan_run_mpc on a plan of its own with the same record, bit for bit, whatever the other episodes do.  The prediction is
  * ONE rollout launch over the n_plans episodes, one candidate each, and the n_plans * Nsample planning candidates start from

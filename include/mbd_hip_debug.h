@@ -79,6 +79,10 @@ int mbd_debug_objective_host(const float* rewss, const float* rews, int B, int N
  * calls check it (MBD_ERR_INVALID naming the field). */
 int mbd_debug_weighting_host(const float* rews, int N, float temp, int std_guard, const mbd_weighting* rec, float* weights_out,
                              float* rew_mean_out, float* temp_out, float* ess_out, int32_t* kept_out);
+/* the argmax of pick_gather_kernel alone (include/mbd_hip.h mbd_mpc_pick), on the DEVICE: HOST rews [P][N], one 1024-thread
+ * workgroup per row; best_out [P]: the lowest index among the maxima of the row's finite entries, -1 where none is finite.  NULL
+ * arguments, P outside [1, 65535] or N < 1 -> MBD_ERR_INVALID before any device access; no device -> MBD_ERR_NO_DEVICE. */
+int mbd_debug_pick_best(const float* rews, int P, int N, int32_t* best_out);
 #ifdef __cplusplus
 }
 #endif

@@ -427,6 +427,10 @@ struct ObjectiveRec {
   // [B][H] and d_rews [B] are the rollout's outputs, d_rews is rewritten in place; B, row0: ObjectiveArgs
   int launch(const float* d_rewss, float* d_rews, int B, int row0, const float* d_cand, bool lazy, float sigma,
              const float* d_ybar, long long ybar_stride, hipStream_t s);
+  // the same launch over B materialised plans [P][B][H][Nu] that are not a step's candidates (a pick record's slots): row b is plan
+  // b of d_plans, results into the caller's d_ret_keep / d_cost_keep [P][B]; what mbd_*_peek_objective shows stays the last step's
+  int launch_rows(const float* d_rewss, float* d_rews, int B, const float* d_plans, float* d_ret_keep, float* d_cost_keep, bool batch,
+                  hipStream_t s);
   // in front of an episode's or a session's first tick: d_queue_last — row D E - 1 of episode 0's committed queue [P][Q] on the
   // device, or nullptr: no delay record
   int episode_start(const float* d_queue_last, long long Q, hipStream_t s);
@@ -460,6 +464,42 @@ struct WeightingRec {
            const char* what) const;
 };
 int check_weighting(const mbd_weighting* rec);
+// The pick record of a plan or a sweep (include/mbd_hip.h mbd_mpc_pick) as the handle keeps it, with what the two handles do alike.
+// check_mpc_pick: the refusals the record alone decides, each naming the field, before any device access.  set: behind the handle's
+// NULL, session, enable_demo and ensemble checks (nullptr clears); makes room for P plans' slots [P][3][HNu], their returns and
+// per-step rewards.  start: in front of an episode's or a session's first tick — room for the log, a ring of min(n_ticks,
+// kPickLogCap) entries per plan, entry of tick j at j % cap — and no tick served.  tick: the three launches (four with an objective
+// record) behind a tick's last update kernel, on stream s (defined in mbd_plan.hip, which alone compiles the kernels); what it reads
+// is PickTick, and it leaves P_t where M_t lay.  peek: the most recent min(count, capacity, cap) ticks of plan k, oldest first.
+constexpr int kPickLogCap = 65536;
+struct PickTick {
+  const float* state;   // [P][S] where the tick planned from
+  int N;                // candidates per plan
+  const float* rews;    // [P][N] the rewards the last step's score read
+  const float* cand;    // [P][N][HNu] the last step's candidates, or their normals (lazy) ...
+  bool lazy;
+  float sigma;          // ... with that step's sigma_i and Ybar_i
+  const float* ybar_i;
+  long long ybar_i_stride;
+  float* M;             // the tick's result: P_t afterwards
+  long long M_stride;
+  const float* B;       // the Ybar the tick started from
+  long long B_stride;
+  unsigned cold;        // bit k: plan k's tick was cold
+};
+struct PickRec {
+  bool has = false;
+  int mask = 0, P = 1, HNu = 0, H = 0, cap = 0;
+  long long count = 0;  // ticks served since start
+  DevBuf<float> d_slots, d_rets, d_rewss, d_obj_ret, d_obj_cost, d_log_rets;
+  DevBuf<int> d_best, d_log_choice, d_log_best;
+  int set(const mbd_mpc_pick* rec, int device, int P_, int HNu_, int H_);
+  int start(long long n_ticks);
+  int tick(mbd_env* env, ObjectiveRec& obj, const PickTick& tk, hipStream_t s);
+  int peek(const mbd_env* env, int k, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity, int* count_out,
+           const char* what) const;
+};
+int check_mpc_pick(const mbd_mpc_pick* rec);
 // One tick of a plant's disturbance chain, dk, d_t = split(dk): advances dk, fills slot k of sp with d_t and the record's
 // deviations — the kick's only in the ticks that end with one — and says whether tick t does
 bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k);

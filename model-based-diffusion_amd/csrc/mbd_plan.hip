@@ -3,6 +3,7 @@
 // behind them take the rollouts' start state as a parameter), and the loops over steps (mbd_plan_reverse_once, mbd_plan_run,
 // mbd_plan_eval, mbd_plan_peek; the receding-horizon loop mbd_plan_run_mpc).  mbd_planner.py:84-148,179-180.
 #define MBD_WEIGH_KERNEL 1  // this unit launches weigh_kernel (mbd_step_kernels.h)
+#define MBD_PICK_KERNEL 1   // ... and, for plans and sweeps alike, the pick record's kernels
 #include "mbd_internal.h"
 #include "../../include/mbd_hip_debug.h"
 
@@ -187,6 +188,8 @@ struct mbd_plan {
   ObjectiveRec obj;
   // the weighting record (mbd_plan_set_weighting) with the device log of its score steps
   WeightingRec wt;
+  // the pick record (mbd_plan_set_mpc_pick) with its slots and the device log of its ticks
+  PickRec pick;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_plan_mpc_open); it uses the episodes' buffers above — d_mpc_state for the
   // state handed in, d_mpc_pred for the one predicted state, d_mpc_queue — so a handle runs episodes or a session, not both
@@ -1366,6 +1369,9 @@ extern "C" int mbd_plan_set_ensemble(mbd_plan* p, const mbd_ensemble* rec) {
     return MBD_OK;
   }
   MBD_TRY(check_ensemble(p, rec));
+  if (p->pick.has)
+    return fail(MBD_ERR_UNSUPPORTED, "ensemble: the plan carries a pick record (mbd_plan_set_mpc_pick): the pick compares returns, an "
+                                     "ensemble's reward is a reduction over members");
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the previous record's buffers)
   const size_t N = (size_t)p->cfg.Nsample, H = (size_t)p->cfg.Hsample, M = (size_t)rec->n_members;
@@ -1505,6 +1511,24 @@ int ObjectiveRec::launch(const float* d_rewss, float* d_rews, int B, int row0, c
   HIP_TRY(hipGetLastError());
   rows = B;
   stepped = true;
+  return MBD_OK;
+}
+
+int ObjectiveRec::launch_rows(const float* d_rewss, float* d_rews, int B, const float* d_plans, float* d_ret_keep, float* d_cost_keep,
+                              bool batch, hipStream_t s) {
+  ObjectiveArgs A;
+  A.rewss = d_rewss; A.rews = d_rews;
+  A.B = B; A.N = B; A.row0 = 0; A.H = H; A.Nu = Nu;
+  A.cand = d_plans; A.lazy = 0; A.sigma = 0.0f; A.ybar = nullptr;
+  A.w = has_w ? d_w.get() : nullptr; A.wsum = wsum;
+  A.q = d_q; A.effort = effort; A.rate = rate; A.costs = costs() ? 1 : 0;
+  A.prev = prev;
+  A.ret_keep = d_ret_keep; A.cost_keep = d_cost_keep;
+  if (!batch)
+    hipLaunchKernelGGL(objective_kernel, dim3(objective_blocks(B)), dim3(kObjThreads), 0, s, A);
+  else
+    hipLaunchKernelGGL(objective_batch_kernel, dim3(objective_blocks(B), (unsigned)P), dim3(kObjThreads), 0, s, A, 0ll);
+  HIP_TRY(hipGetLastError());
   return MBD_OK;
 }
 
@@ -1710,6 +1734,140 @@ extern "C" int mbd_plan_peek_weighting(mbd_plan* p, float* temp_out, float* ess_
   return p->wt.peek(p->env, 0, temp_out, ess_out, kept_out, capacity, count_out, "plan");
 }
 
+// ---- the pick record (include/mbd_hip.h mbd_mpc_pick) ------------------------------------------------------------------------
+int check_mpc_pick(const mbd_mpc_pick* rec) {
+  const int all = MBD_PICK_MEAN | MBD_PICK_PREV | MBD_PICK_BEST;
+  if (rec->candidates == 0) return fail(MBD_ERR_INVALID, "mpc pick: candidates=0: at least one of MEAN (1), PREV (2), BEST (4)");
+  if (rec->candidates & ~all) return fail(MBD_ERR_INVALID, "mpc pick: candidates=%d: unknown bits (MEAN 1, PREV 2, BEST 4)", rec->candidates);
+  for (int r = 0; r < 7; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "mpc pick: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  return MBD_OK;
+}
+
+int PickRec::set(const mbd_mpc_pick* rec, int device, int P_, int HNu_, int H_) {
+  if (!rec) {
+    has = false;
+    return MBD_OK;
+  }
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());
+  has = false;
+  P = P_; HNu = HNu_; H = H_;
+  HIP_TRY(d_slots.grow((size_t)P * 3 * HNu));
+  HIP_TRY(d_rets.grow((size_t)P * 3));
+  HIP_TRY(d_rewss.grow((size_t)P * 3 * H));
+  HIP_TRY(d_obj_ret.grow((size_t)P * 3));
+  HIP_TRY(d_obj_cost.grow((size_t)P * 3));
+  HIP_TRY(d_best.grow(P));
+  mask = rec->candidates;
+  cap = 0;
+  count = 0;
+  has = true;
+  return MBD_OK;
+}
+
+int PickRec::start(long long n_ticks) {
+  if (!has) return MBD_OK;
+  const int want = (int)(n_ticks < kPickLogCap ? (n_ticks < 1 ? 1 : n_ticks) : kPickLogCap);
+  HIP_TRY(d_log_choice.grow((size_t)P * want));
+  HIP_TRY(d_log_rets.grow((size_t)P * want * 3));
+  HIP_TRY(d_log_best.grow((size_t)P * want));
+  cap = want;
+  count = 0;
+  return MBD_OK;
+}
+
+// A tick's pick, on the tick's stream behind its last update kernel: pick_gather_kernel (n* and the three slots of every plan),
+// ONE rollout launch of the plan's env over the 3 P slots from the states the tick planned from — no progress word, no noise job,
+// like a delay record's prediction launch —, under an objective record its launch over those rows with the tick's previous action,
+// and pick_choose_kernel.  Stream order is the whole argument: the gather reads the last step's rewards, normals and Ybar_i behind
+// that step's weighted mean — the buffer of normals is next written two steps later, by a job that is ordered behind the NEXT
+// rollout launch of the handle or behind a mark on this stream, both behind this launch —, and the choose kernel writes P_t over
+// M_t in front of everything that reads it: the objective's next prev, the boundary kernels, the execution of the rows.
+int PickRec::tick(mbd_env* env, ObjectiveRec& obj, const PickTick& tk, hipStream_t s) {
+  if (!has) return MBD_OK;
+  if (cap < 1) return fail(MBD_ERR_STATE, "mpc pick: the record's log was not started");
+  const int S = env->state_size();
+  PickGather G;
+  G.rews = tk.rews; G.rews_stride = tk.N; G.N = tk.N; G.HNu = HNu;
+  G.cand = tk.cand; G.cand_stride = (long long)tk.N * HNu; G.lazy = tk.lazy ? 1 : 0; G.sigma = tk.sigma;
+  G.ybar_i = tk.ybar_i; G.ybar_i_stride = tk.ybar_i_stride;
+  G.M = tk.M; G.M_stride = tk.M_stride; G.B = tk.B; G.B_stride = tk.B_stride;
+  G.cold = tk.cold;
+  G.slots = d_slots; G.best = d_best;
+  hipLaunchKernelGGL(pick_gather_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), 0, s, G);
+  HIP_TRY(hipGetLastError());
+  const int sw[3] = {3, S, 0};  // (a sweep of three-candidate plans: plan k's slots start from plan k's state)
+  MBD_TRY(launch_rollout(env, tk.state, d_slots, 3 * P, H, d_rewss, d_rets, nullptr, nullptr, s, nullptr, P > 1 ? sw : nullptr));
+  if (obj.has) MBD_TRY(obj.launch_rows(d_rewss, d_rets, 3, d_slots, d_obj_ret, d_obj_cost, P > 1, s));
+  const long long at = count % cap;
+  PickChoose C;
+  C.rets = d_rets; C.slots = d_slots; C.best = d_best; C.HNu = HNu; C.mask = mask; C.cold = tk.cold;
+  C.out = tk.M; C.out_stride = tk.M_stride;
+  C.log_choice = d_log_choice.get() + at; C.log_rets = d_log_rets.get() + at * 3; C.log_best = d_log_best.get() + at;
+  C.log_stride = cap;
+  hipLaunchKernelGGL(pick_choose_kernel, dim3(1, (unsigned)P), dim3(256), 0, s, C);
+  HIP_TRY(hipGetLastError());
+  count += 1;
+  return MBD_OK;
+}
+
+int PickRec::peek(const mbd_env* env, int k, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity, int* count_out,
+                  const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_mpc_pick: the %s has no pick record", what);
+  if (k < 0 || k >= P) return fail(MBD_ERR_INVALID, "peek_mpc_pick: plan k=%d outside [0,%d)", k, P);
+  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_mpc_pick: capacity=%d", capacity);
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  long long n = count < capacity ? count : capacity;
+  if (n > cap) n = cap;
+  // tick count - n + j lies at its index modulo cap: one run of entries, or two where the ring wraps — at most two copies per log
+  for (long long j = 0; j < n;) {
+    const long long slot = (count - n + j) % cap;
+    const long long run = n - j < cap - slot ? n - j : cap - slot;
+    const size_t at = (size_t)k * cap + (size_t)slot;
+    if (choice_out) HIP_TRY(hipMemcpy(choice_out + j, d_log_choice.get() + at, sizeof(int32_t) * run, hipMemcpyDeviceToHost));
+    if (rets_out) HIP_TRY(hipMemcpy(rets_out + 3 * j, d_log_rets.get() + 3 * at, sizeof(float) * 3 * run, hipMemcpyDeviceToHost));
+    if (best_out) HIP_TRY(hipMemcpy(best_out + j, d_log_best.get() + at, sizeof(int32_t) * run, hipMemcpyDeviceToHost));
+    j += run;
+  }
+  if (count_out) *count_out = (int)(count < 0x7fffffff ? count : 0x7fffffff);
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_mpc_pick(mbd_plan* p, const mbd_mpc_pick* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_mpc_pick");
+  if (rec) MBD_TRY(check_mpc_pick(rec));  // (before any device access)
+  if (rec && p->cfg.enable_demo)
+    return fail(MBD_ERR_UNSUPPORTED, "mpc pick record: enable_demo=1: a demo plan's score is not the return the pick compares");
+  if (rec && p->has_ens)
+    return fail(MBD_ERR_UNSUPPORTED, "mpc pick record: the plan carries an ensemble record: its reward is a reduction over members");
+  return p->pick.set(rec, p->env->device, 1, p->HNu, p->cfg.Hsample);
+}
+
+extern "C" int mbd_plan_peek_mpc_pick(mbd_plan* p, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity, int* count_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->pick.peek(p->env, 0, choice_out, rets_out, best_out, capacity, count_out, "plan");
+}
+
+// include/mbd_hip_debug.h: the device argmax of pick_gather_kernel over P rows of N rewards
+extern "C" int mbd_debug_pick_best(const float* rews, int P, int N, int32_t* best_out) {
+  if (!rews || !best_out) return fail(MBD_ERR_INVALID, "pick_best: NULL argument");
+  if (P < 1 || P > 65535 || N < 1) return fail(MBD_ERR_INVALID, "pick_best: P=%d N=%d", P, N);
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  DevBuf<float> d_rews;
+  DevBuf<int> d_best;
+  HIP_TRY(d_rews.alloc((size_t)P * N));
+  HIP_TRY(d_best.alloc(P));
+  HIP_TRY(hipMemcpy(d_rews, rews, sizeof(float) * (size_t)P * N, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(pick_best_probe_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), 0, 0, (const float*)d_rews, N, d_best.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(best_out, d_best, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
 // ---- one tick's planning, shared by the batch episode (mbd_plan_run_mpc) and the session (mbd_plan_mpc_submit) ------------------
 // The tick's keys, host arithmetic: rng, k_t = split(rng) advances the episode's chain; r = k_t is where the tick's own chain
 // starts (mbd_plan_run's from it); after = split(split(rng')[1])[1] is the Y0s_rng of tick t+1's first step, whose normals are
@@ -1754,11 +1912,24 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
   const NoiseSpec ns = tk.cold ? noise_always(p) : noise_warm(p);
   p->wt.begin();  // (a weighting record's log holds the last tick's steps)
   const float* cur = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros of a cold tick, shift_E(M_{t-1}) otherwise
+  const float* last_in = cur;    // Ybar_i of the tick's last step
+  float* last_out = nullptr;
   for (int i = tk.cold ? Nd - 1 : tk.K; i >= 1; --i) {
     float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
     MBD_TRY(plan_keep_in_step(p));
     MBD_TRY(reverse_once_impl(p, plan_from, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, ns, tk.key_after, noise_warm(p), tk.d_xref));
-    cur = nxt;
+    last_in = cur;
+    cur = last_out = nxt;
+  }
+  // with a pick record: P_t over M_t where it lies, so that everything below and every boundary reads the picked plan
+  if (p->pick.has) {
+    PickTick pt{};
+    pt.state = plan_from; pt.N = p->cfg.Nsample; pt.rews = p->d_rews;
+    pt.cand = p->lazy ? p->ring.eps[p->ring.cur].get() : p->d_Y0s.get();
+    pt.lazy = p->lazy; pt.sigma = p->sigmas[1]; pt.ybar_i = last_in; pt.ybar_i_stride = 0;
+    pt.M = last_out; pt.M_stride = 0; pt.B = p->d_Ybar; pt.B_stride = 0;
+    pt.cold = tk.cold ? 1u : 0u;
+    MBD_TRY(p->pick.tick(p->env, p->obj, pt, s));
   }
   *mean = cur;
   // with an objective record, the next tick's previous action: clip(M_t[E-1]) — the commanded row, whatever a plant record adds to
@@ -1859,6 +2030,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     ObjectiveRec& o;
     ~ObjEpisode() { o.episode_end(); }
   } obj_episode{p->obj};
+  MBD_TRY(p->pick.start(T));  // (a pick record's log: one entry per tick)
   if (pi) {  // sigma = sigma_cold and the log's first entry, by the kernel that carries sigma across the boundaries
     MBD_TRY(p->sigma_rec.start(T, 1));
     p->sigma_rec.launch(p->d_sigma, 1, 0, true, s);
@@ -2014,6 +2186,7 @@ extern "C" int mbd_plan_mpc_open(mbd_plan* p, const mbd_mpc_config* mc, const ui
   }
   HIP_TRY(hipStreamSynchronize(s));
   if (p->demo.has) MBD_TRY(p->demo.session_start());
+  MBD_TRY(p->pick.start(mc->n_ticks));  // (a pick record's log: the session's ticks, the most recent kPickLogCap of them)
   // the objective record's previous action of the first tick, as mbd_plan_run_mpc forms it, and the session's slot until close —
   // behind everything else that can fail, and itself leaving the slot alone when it fails: a failed open leaves prev as it was
   MBD_TRY(p->obj.episode_start(p->delay.has ? p->d_mpc_queue + (Q - p->Nu) : nullptr, Q, s));

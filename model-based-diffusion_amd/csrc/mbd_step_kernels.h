@@ -1560,4 +1560,145 @@ static __global__ __launch_bounds__(kScoreThreads) void weigh_kernel(const float
 }
 #endif  // MBD_WEIGH_KERNEL
 
+// ---- the pick record (mbd_plan_set_mpc_pick, include/mbd_hip.h mbd_mpc_pick; DESIGN.md section 1 "N15 pick"): what a tick hands
+// on — its mean, the incumbent, or the best candidate of its last step.  Two kernels around one small rollout launch, behind the
+// tick's last update kernel.  Last in this header under their own guard, for weigh_kernel's reason (above): only the unit that
+// launches them (mbd_plan.hip, for plans and sweeps alike) emits them, directly behind weigh_kernel — the other units' code objects
+// stay what they were, and in that unit only the template instantiations the compiler emits at its end lie further along ----
+// finite on the bits (exponent not all ones), as weigh_keep decides it
+MBD_HD bool pick_finite(float r) { return (__builtin_bit_cast(uint32_t, r) & 0x7f800000u) != 0x7f800000u; }
+// whether the pair (v, i) goes in front of (bv, bi): i < 0 is "none"; the larger value, among equal values (+0 == -0) the lower index
+MBD_HD bool pick_before(float v, int i, float bv, int bi) { return i >= 0 && (bi < 0 || v > bv || (v == bv && i < bi)); }
+// the three plans of a tick that a choice is made among, per plan k (blockIdx.y; every pointer is plan 0's, plan k's lies its stride
+// further): slot 0 = M, slot 1 = B (cold bit k set: M), slot 2 = candidate n* (none: M)
+struct PickGather {
+  const float* rews;    // [N] the rewards the last step's score read
+  long long rews_stride;
+  int N, HNu;
+  const float* cand;    // [N][HNu] that step's candidates, or their normals (lazy)
+  long long cand_stride;
+  int lazy;
+  float sigma;          // lazy: sigma_i ...
+  const float* ybar_i;  // ... and Ybar_i [HNu] of that step
+  long long ybar_i_stride;
+  const float* M;       // [HNu] the tick's result
+  long long M_stride;
+  const float* B;       // [HNu] the Ybar the tick started from
+  long long B_stride;
+  unsigned cold;        // bit k: plan k's tick was cold — it has no incumbent
+  float* slots;         // [3][HNu], plan k's 3 HNu further
+  int* best;            // [1] n*, plan k's one further
+};
+#ifdef MBD_PICK_KERNEL
+// n* of one plan's rewards by the calling 1024-thread workgroup; every thread returns the same value.  Thread t walks
+// i = t, t + 1024, ... ascending and replaces on strictly greater only; the butterfly and the scan over the sixteen wavefronts'
+// pairs order by (value, lower index), which is a total order on pairs of distinct indices: whatever the combination order, the
+// winner is the lowest index among the maxima
+__device__ __forceinline__ int pick_argmax_block(const float* __restrict__ rews, int N, float* red_v, int* red_i) {
+  const int tid = threadIdx.x;
+  float bv = 0.0f;
+  int bi = -1;
+  for (int i = tid; i < N; i += kScoreThreads) {
+    const float x = rews[i];
+    const bool take = pick_finite(x) && (bi < 0 || x > bv);
+    bv = take ? x : bv;
+    bi = take ? i : bi;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float ov = __shfl_xor(bv, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    const bool take = pick_before(ov, oi, bv, bi);
+    bv = take ? ov : bv;
+    bi = take ? oi : bi;
+  }
+  if ((tid & 63) == 0) { red_v[tid >> 6] = bv; red_i[tid >> 6] = bi; }
+  __syncthreads();
+  bv = red_v[0];
+  bi = red_i[0];
+#pragma unroll
+  for (int w = 1; w < kScoreThreads / 64; ++w) {
+    const float ov = red_v[w];
+    const int oi = red_i[w];
+    const bool take = pick_before(ov, oi, bv, bi);
+    bv = take ? ov : bv;
+    bi = take ? oi : bi;
+  }
+  return bi;
+}
+// ONE 1024-thread workgroup per plan: n*, then the three slots — the candidate formed as mbd_plan_peek forms it (shift_kernel's
+// element: eps * sigma rounded, + Ybar_i rounded, clipped; a materialised plan's row as it stands).  n* is read by every thread from
+// the same LDS words (uniform) and never leaves the device.  Plain vector loads and stores.
+static __global__ __launch_bounds__(kScoreThreads) void pick_gather_kernel(PickGather A) {
+  const long long k = blockIdx.y;
+  __shared__ float red_v[kScoreThreads / 64];
+  __shared__ int red_i[kScoreThreads / 64];
+  const int best = pick_argmax_block(A.rews + k * A.rews_stride, A.N, red_v, red_i);
+  const float* __restrict__ M = A.M + k * A.M_stride;
+  const float* __restrict__ B = A.B + k * A.B_stride;
+  const float* __restrict__ yb = A.lazy ? A.ybar_i + k * A.ybar_i_stride : M;
+  const float* __restrict__ row = best >= 0 ? A.cand + k * A.cand_stride + (long long)best * A.HNu : M;
+  const bool lazy = A.lazy && best >= 0;
+  const bool has_prev = !((A.cold >> k) & 1u);
+  float* __restrict__ out = A.slots + k * 3 * A.HNu;
+  for (int e = threadIdx.x; e < A.HNu; e += kScoreThreads) {
+    const float m = M[e];
+    const float x = row[e];
+    out[e] = m;
+    out[A.HNu + e] = has_prev ? B[e] : m;
+    out[2 * A.HNu + e] = lazy ? fclip(x * A.sigma + yb[e], -1.0f, 1.0f) : x;
+  }
+  if (threadIdx.x == 0) A.best[k] = best;
+}
+// the argmax alone over P rows of N rewards (mbd_debug_pick_best)
+static __global__ __launch_bounds__(kScoreThreads) void pick_best_probe_kernel(const float* __restrict__ rews, int N, int* __restrict__ best) {
+  __shared__ float red_v[kScoreThreads / 64];
+  __shared__ int red_i[kScoreThreads / 64];
+  const int b = pick_argmax_block(rews + (long long)blockIdx.y * N, N, red_v, red_i);
+  if (threadIdx.x == 0) best[blockIdx.y] = b;
+}
+// ONE 256-thread workgroup per plan, behind the rollout (and the objective launch) of the three slots: the choice c — in slot order,
+// a slot that is enabled, present and of finite return takes over on strictly greater; none: 0 —, slot c over the tick's result
+// where it lies (every consumer of M_t downstream then reads P_t), and the tick's log entry through thread 0.  c is decided by
+// every thread from the same three loads: uniform.
+struct PickChoose {
+  const float* rets;   // [3], plan k's 3 further
+  const float* slots;  // [3][HNu]
+  const int* best;
+  int HNu, mask;
+  unsigned cold;
+  float* out;          // [HNu] the tick's result, plan k's out_stride further
+  long long out_stride;
+  int* log_choice;     // the tick's entry of plan 0's logs; plan k's log_stride entries further (rets: 3 floats per entry)
+  float* log_rets;
+  int* log_best;
+  long long log_stride;
+};
+static __global__ __launch_bounds__(256) void pick_choose_kernel(PickChoose A) {
+  const long long k = blockIdx.y;
+  const float* __restrict__ rets = A.rets + k * 3;
+  const int best = A.best[k];
+  const float r[3] = {rets[0], rets[1], rets[2]};
+  const bool present[3] = {true, !((A.cold >> k) & 1u), best >= 0};
+  int c = -1;
+  float rc = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const bool take = ((A.mask >> j) & 1) && present[j] && pick_finite(r[j]) && (c < 0 || r[j] > rc);
+    rc = take ? r[j] : rc;
+    c = take ? j : c;
+  }
+  if (c < 0) c = 0;
+  const float* __restrict__ src = A.slots + (k * 3 + c) * A.HNu;
+  float* __restrict__ out = A.out + k * A.out_stride;
+  for (int e = threadIdx.x; e < A.HNu; e += 256) out[e] = src[e];
+  if (threadIdx.x == 0) {
+    A.log_choice[k * A.log_stride] = c;
+    float* lr = A.log_rets + k * A.log_stride * 3;
+    lr[0] = r[0]; lr[1] = r[1]; lr[2] = r[2];
+    A.log_best[k * A.log_stride] = best;
+  }
+}
+#endif  // MBD_PICK_KERNEL
+
 }  // namespace mbd

@@ -125,6 +125,8 @@ struct mbd_sweep {
   ObjectiveRec obj;
   // the weighting record of all the sweep's plans (mbd_sweep_set_weighting) with every plan's log [P][Ndiffuse - 1]
   WeightingRec wt;
+  // the pick record of all the sweep's episodes (mbd_sweep_set_mpc_pick) with every episode's slots and log
+  PickRec pick;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_sweep_mpc_open): it uses the batch's buffers above — slice 0 of d_mpc_states for
   // the states handed in, slice 0 of d_mpc_pred, d_mpc_queue, d_mpc_ybar — so a handle runs batches or a session, not both
@@ -558,6 +560,43 @@ extern "C" int mbd_sweep_peek_weighting(mbd_sweep* w, int k, float* temp_out, fl
   return w->wt.peek(w->env, k, temp_out, ess_out, kept_out, capacity, count_out, "sweep");
 }
 
+// one pick record for all episodes of the sweep (include/mbd_hip.h mbd_mpc_pick), as mbd_plan_set_mpc_pick
+extern "C" int mbd_sweep_set_mpc_pick(mbd_sweep* w, const mbd_mpc_pick* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  NO_SWEEP_SESSION(w, "set_mpc_pick");
+  if (rec) MBD_TRY(check_mpc_pick(rec));  // (before any device access)
+  if (rec && w->cfg.enable_demo)
+    return fail(MBD_ERR_UNSUPPORTED, "mpc pick record: enable_demo=1: a demo plan's score is not the return the pick compares");
+  return w->pick.set(rec, w->env->device, w->P, w->HNu, w->cfg.Hsample);
+}
+
+extern "C" int mbd_sweep_peek_mpc_pick(mbd_sweep* w, int k, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity,
+                                       int* count_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  return w->pick.peek(w->env, k, choice_out, rets_out, best_out, capacity, count_out, "sweep");
+}
+
+namespace {
+// every episode's pick behind a tick's last step (PickRec::tick): the tick planned from plan_from [P][S] and started from ybar0
+// [P][HNu]; i_start: its first diffusion step; buf: the ring buffer its last step's normals lie in (MBD sweeps)
+int sweep_pick(mbd_sweep* w, const float* plan_from, const float* ybar0, int i_start, int buf, unsigned cold, hipStream_t s) {
+  if (!w->pick.has) return MBD_OK;
+  const int Nd = w->cfg.Ndiffuse, HNu = w->HNu;
+  const long long mu_stride = (long long)(Nd - 1) * HNu;
+  const bool lazy = w->cfg.update_method == 0;
+  PickTick pt{};
+  pt.state = plan_from; pt.N = w->cfg.Nsample; pt.rews = w->d_rews;
+  pt.cand = lazy ? w->d_eps[buf].get() : w->d_Y0s.get();
+  pt.lazy = lazy; pt.sigma = w->sigmas[1];
+  pt.ybar_i = i_start == 1 ? ybar0 : w->d_mu + (size_t)(Nd - 3) * HNu;  // (Ybar_1 of the last step: the tick's own start, or slot Nd-3)
+  pt.ybar_i_stride = i_start == 1 ? HNu : mu_stride;
+  pt.M = w->d_mu + (size_t)(Nd - 2) * HNu; pt.M_stride = mu_stride;
+  pt.B = ybar0; pt.B_stride = HNu;
+  pt.cold = cold;
+  return w->pick.tick(w->env, w->obj, pt, s);
+}
+}  // namespace
+
 extern "C" int mbd_sweep_set_mpc_plant(mbd_sweep* w, int k, const mbd_mpc_plant* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "episode k=%d outside [0,%d)", k, w->P);
@@ -698,6 +737,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     ObjectiveRec& o;
     ~ObjEpisode() { o.episode_end(); }
   } obj_episode{w->obj};
+  MBD_TRY(w->pick.start(T));  // (a pick record's logs: one entry per tick and episode)
   HIP_TRY(hipStreamSynchronize(s));
   progress_reset(w->h_progress);
   const auto t0 = std::chrono::steady_clock::now();
@@ -775,6 +815,9 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     // (with a delay record the rows executed are the queues' heads: into the tick's slice of their log, which the rollout
     // reads — unless plant records form the disturbed rows there themselves)
     float* rows_t = any_plant || has_delay ? w->d_mpc_actions + (size_t)t * P * EN : nullptr;
+    // (in front of all of it, with a pick record: every episode's P_t over its M_t where it lies)
+    MBD_TRY(sweep_pick(w, plan_from, t == 0 ? w->d_zero.get() : w->d_mpc_ybar.get(), i_start, pi ? 0 : (q + 2) % 3,
+                       t == 0 ? 0xffffffffu : 0u, s));
     // (in front of it, with an objective record: the next tick's previous actions, clip(M_{.,t}[E-1]), one launch)
     MBD_TRY(w->obj.tick_advance(w->d_mu + (size_t)(Nd - 2) * HNu + (size_t)(E - 1) * Nu, mu_stride, s));
     if (has_delay)
@@ -929,6 +972,7 @@ extern "C" int mbd_sweep_mpc_open(mbd_sweep* w, const mbd_mpc_config* mc, const 
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(w->aux));
   if (w->demo.has) MBD_TRY(w->demo.session_start());
+  MBD_TRY(w->pick.start(mc->n_ticks));
   // an objective record's previous actions of the first tick and the session's slot until close: behind everything else that can
   // fail (a failed open leaves prev as it was); the launch is stream-ordered in front of the first tick
   MBD_TRY(w->obj.episode_start(w->delay.has ? w->d_mpc_queue + (Q - w->Nu) : nullptr, Q, s));
@@ -1019,7 +1063,13 @@ extern "C" int mbd_sweep_mpc_submit(mbd_sweep* w, const float* states) {
     st.rew_xref = w->demo.has ? w->demo.rew_xref : e->rew_xref;
     MBD_TRY(sweep_step(w, st));
   }
-  // the next tick's previous actions (an objective record) in FRONT of the boundary, which stays the tick's last kernel
+  // a pick record's launches, then the next tick's previous actions (an objective record), in FRONT of the boundary, which stays
+  // the tick's last kernel
+  {
+    unsigned cold = 0;
+    for (int k = 0; k < P; ++k) cold |= ss.cold[k] ? 1u << k : 0u;
+    MBD_TRY(sweep_pick(w, plan_from, w->d_mpc_ybar.get(), i_start, (i_start - 1) % 3, cold, s));
+  }
   MBD_TRY(w->obj.tick_advance(w->d_mu + (size_t)(Nd - 2) * HNu + (size_t)(E - 1) * w->Nu, mu_stride, s));
   hipLaunchKernelGGL(mpc_session_boundary_batch_kernel, dim3(1, (unsigned)P), dim3(256), 0, s,
                      (const float*)(w->d_mu + (size_t)(Nd - 2) * HNu), mu_stride, HNu, EN, w->d_mpc_ybar.get(), q_in, q_out, Q,

@@ -113,6 +113,15 @@ class Weighting(C.Structure):
                 ("iters", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
+PICK_MEAN, PICK_PREV, PICK_BEST = 1, 2, 4
+
+
+class MpcPick(C.Structure):
+    """mbd_mpc_pick (include/mbd_hip.h): which of a tick's three plans — its mean, the incumbent, the best candidate of its last
+    step — the tick may hand on."""
+    _fields_ = [("candidates", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 TICK_ROWS_NONFINITE, TICK_STATE_NONFINITE, TICK_COLD = 1, 2, 4
 
 
@@ -131,6 +140,7 @@ EXPORTS = [
     "mbd_plan_set_sigma", "mbd_plan_get_sigma", "mbd_plan_reverse_once", "mbd_plan_run", "mbd_plan_run_mpc", "mbd_plan_set_mpc_plant", "mbd_plan_set_ensemble", "mbd_plan_peek_ensemble", "mbd_plan_set_noise_shape", "mbd_plan_set_noise_basis", "mbd_plan_set_mpc_delay", "mbd_plan_peek_mpc_predicted", "mbd_plan_set_mpc_demo", "mbd_plan_peek_mpc_track", "mbd_plan_set_mpc_sigma", "mbd_plan_peek_mpc_sigma",
     "mbd_plan_set_objective", "mbd_plan_peek_objective", "mbd_sweep_set_objective", "mbd_sweep_peek_objective",
     "mbd_plan_set_weighting", "mbd_plan_peek_weighting", "mbd_sweep_set_weighting", "mbd_sweep_peek_weighting",
+    "mbd_plan_set_mpc_pick", "mbd_plan_peek_mpc_pick", "mbd_sweep_set_mpc_pick", "mbd_sweep_peek_mpc_pick",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
@@ -217,6 +227,10 @@ def load() -> C.CDLL:
     lib.mbd_plan_peek_weighting.argtypes = [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_sweep_set_weighting.argtypes = [_vp, C.POINTER(Weighting)]
     lib.mbd_sweep_peek_weighting.argtypes = [_vp, _i, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
+    lib.mbd_plan_set_mpc_pick.argtypes = [_vp, C.POINTER(MpcPick)]
+    lib.mbd_plan_peek_mpc_pick.argtypes = [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
+    lib.mbd_sweep_set_mpc_pick.argtypes = [_vp, C.POINTER(MpcPick)]
+    lib.mbd_sweep_peek_mpc_pick.argtypes = [_vp, _i, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
     lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
     lib.mbd_plan_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(MpcTickInfo)]
@@ -421,6 +435,49 @@ def peek_weighting(fn, handle, k, capacity: int) -> dict:
     check(fn(*head, np_ptr(temp), np_ptr(ess), np_ptr(kept), int(capacity), C.byref(n)))
     m = min(n.value, capacity)
     return {"temp": temp[:m], "ess": ess[:m], "kept": kept[:m]}
+
+
+def pick_record(mean=True, prev=True, best=True) -> "MpcPick":
+    """The mbd_mpc_pick of ``set_mpc_pick``'s arguments (none enabled goes to the library, which names the field)."""
+    rec = MpcPick()
+    rec.candidates = (PICK_MEAN if mean else 0) | (PICK_PREV if prev else 0) | (PICK_BEST if best else 0)
+    return rec
+
+
+def peek_mpc_pick(fn, handle, k, capacity: int = None) -> dict:
+    """mbd_plan_peek_mpc_pick (k None) or mbd_sweep_peek_mpc_pick: {'choice' [n], 'rets' [n, 3], 'best' [n]}, one entry per tick —
+    every tick served so far, or the most recent ``capacity`` of them, oldest first."""
+    head = (handle,) if k is None else (handle, int(k))
+    n = C.c_int(0)
+    if capacity is None:
+        check(fn(*head, None, None, None, 0, C.byref(n)))
+        capacity = n.value
+    capacity = max(int(capacity), 0)
+    choice, rets, best = np.zeros(capacity, np.int32), np.zeros((capacity, 3), np.float32), np.zeros(capacity, np.int32)
+    check(fn(*head, np_ptr(choice), np_ptr(rets), np_ptr(best), capacity, C.byref(n)))
+    m = min(n.value, capacity)
+    return {"choice": choice[:m], "rets": rets[:m], "best": best[:m]}
+
+
+def has_mpc_pick(fn, handle, k) -> bool:
+    """Whether the handle carries a pick record: the peek call's own answer (MBD_ERR_STATE: none)."""
+    head = (handle,) if k is None else (handle, int(k))
+    rc = fn(*head, None, None, None, 0, None)
+    if rc == MBD_ERR_STATE:
+        return False
+    check(rc)
+    return True
+
+
+def debug_pick_best(rews) -> np.ndarray:
+    """include/mbd_hip_debug.h: the pick record's argmax on the GPU.  ``rews`` [P, N] (or [N]); returns best [P] (or an int)."""
+    lib = load()
+    lib.mbd_debug_pick_best.argtypes = [_vp, _i, _i, _vp]
+    r = np.ascontiguousarray(rews, np.float32)
+    r2 = r.reshape(1, -1) if r.ndim == 1 else r
+    best = np.full(r2.shape[0], -2, np.int32)
+    check(lib.mbd_debug_pick_best(np_ptr(r2), r2.shape[0], r2.shape[1], np_ptr(best)))
+    return int(best[0]) if r.ndim == 1 else best
 
 
 def debug_math_ops() -> list:

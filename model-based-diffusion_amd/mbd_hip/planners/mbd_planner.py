@@ -138,6 +138,8 @@ class Sweep:
             for e in range(P):
                 _capi.check(self.lib.mbd_sweep_peek_mpc_track(self.h, e, _capi.np_ptr(out["track_err"][e]),
                                                               _capi.np_ptr(out["demo_windows"]) if e == 0 else None))
+        if self.has_mpc_pick():  # (what every tick of every episode handed on, and the three plans' values)
+            out["pick"] = [self.peek_mpc_pick(e, T) for e in range(P)]
         return out
 
     def mpc_open(self, keys, warm_steps: int, exec_steps: int = 1, max_ticks: int = None):
@@ -223,6 +225,23 @@ class Sweep:
     def peek_weighting(self, k: int) -> dict:
         """Plan k's ``temp``, ``ess`` and ``kept`` of every score step of the last run or tick (``Plan.peek_weighting``)."""
         return _capi.peek_weighting(self.lib.mbd_sweep_peek_weighting, self.h, k, self.cfg.Ndiffuse - 1)
+
+    def set_mpc_pick(self, mean=True, prev=True, best=True):
+        """One pick record for all episodes of the sweep (``Plan.set_mpc_pick``): episode k of ``run_mpc`` and of a session is
+        then the single plan's with the same record, bit for bit; ``run_mpc`` also returns ``pick``, one dict per episode."""
+        rec = _capi.pick_record(mean, prev, best)
+        _capi.check(self.lib.mbd_sweep_set_mpc_pick(self.h, C.byref(rec)))
+
+    def clear_mpc_pick(self):
+        _capi.check(self.lib.mbd_sweep_set_mpc_pick(self.h, None))
+
+    def has_mpc_pick(self) -> bool:
+        """Whether the sweep carries a pick record: asked of the library, so a record set through the C ABI counts."""
+        return _capi.has_mpc_pick(self.lib.mbd_sweep_peek_mpc_pick, self.h, 0)
+
+    def peek_mpc_pick(self, k: int, capacity: int = None) -> dict:
+        """Episode k's ``choice`` [n], ``rets`` [n, 3] and ``best`` [n] of the ticks served so far (``Plan.peek_mpc_pick``)."""
+        return _capi.peek_mpc_pick(self.lib.mbd_sweep_peek_mpc_pick, self.h, k, capacity)
 
     def peek_objective(self, k: int):
         """Plan k's ``ret`` [N] and ``cost`` [N] of the last step (a sweep with an objective record)."""
@@ -405,6 +424,8 @@ class MpcSession:
         mc.n_ticks = 2 ** 31 - 1 if max_ticks is None else int(max_ticks)
         mc.warm_steps, mc.exec_steps = int(warm_steps), int(exec_steps)
         self._open = False
+        self._pick, self._pick_tick = None, -1  # (the last collected tick's pick entry, fetched when ``pick`` is first read)
+        self._ticks = 0
         _capi.check(self._fn("open")(plan.h, C.byref(mc), _capi.key_array(key) if self.P is None else _capi.np_ptr(k)))
         self._open = True
 
@@ -447,9 +468,29 @@ class MpcSession:
         info = (_capi.MpcTickInfo * (self.P or 1))()
         _capi.check(self._fn("collect")(p.h, _capi.np_ptr(rows), _capi.np_ptr(mean), _capi.np_ptr(head), _capi.np_ptr(pred), info))
         flags, rew = np.array([i.flags for i in info], np.int32), np.array([i.rew_mean for i in info], np.float32)
+        self._ticks += 1
         return dict(rows=rows, mean=mean, head=head, predicted=pred if p._has_delay else None,
                     flags=int(flags[0]) if self.P is None else flags, rew_mean=float(rew[0]) if self.P is None else rew,
                     seconds=info[0].seconds, tick=info[0].tick)
+
+    @property
+    def pick(self):
+        """With a pick record: what the last collected tick handed on — dict(choice, rets [3], best); a sweep's session: arrays [P],
+        [P, 3], [P].  None without a record or before the first collect.  Read from the device log when asked for (one peek per
+        tick at the most), so a loop that never looks pays nothing."""
+        p = self.plan
+        if self._ticks == 0 or not p.has_mpc_pick():
+            return None
+        if self._pick_tick != self._ticks:
+            if self.P is None:
+                last = p.peek_mpc_pick(1)
+                self._pick = dict(choice=int(last["choice"][0]), rets=last["rets"][0], best=int(last["best"][0]))
+            else:
+                last = [p.peek_mpc_pick(e, 1) for e in range(self.P)]
+                self._pick = dict(choice=np.array([x["choice"][0] for x in last], np.int32), rets=np.stack([x["rets"][0] for x in last]),
+                                  best=np.array([x["best"][0] for x in last], np.int32))
+            self._pick_tick = self._ticks
+        return self._pick
 
     def tick(self, state=None, q=None, qd=None) -> dict:
         """``submit`` then ``collect``."""
@@ -568,7 +609,30 @@ class Plan:
             out["track_err"] = np.zeros((T * E, Kt), np.float32)
             out["demo_windows"] = np.zeros((T, Kt, _capi.XREF_ROWS, Cc), np.float32)
             _capi.check(self.lib.mbd_plan_peek_mpc_track(self.h, _capi.np_ptr(out["track_err"]), _capi.np_ptr(out["demo_windows"])))
+        if self.has_mpc_pick():  # (what every tick handed on, and the three plans' values)
+            out["pick"] = self.peek_mpc_pick(T)
         return out
+
+    def set_mpc_pick(self, mean=True, prev=True, best=True):
+        """Choose what a tick hands on (include/mbd_hip.h mbd_mpc_pick): of its mean, the incumbent (the last tick's plan shifted)
+        and the best candidate of its last step — those enabled here — the one the plan's env values most.  The picked plan
+        stands wherever the mean stood: the rows executed, the next tick's warm start, ``means``.  ``run_mpc`` then also returns
+        ``pick`` = dict(choice [T], rets [T, 3], best [T]); a session has ``pick`` after each collect.  ``mean`` alone leaves the
+        episode's bits unchanged and logs the value of every executed plan."""
+        rec = _capi.pick_record(mean, prev, best)
+        _capi.check(self.lib.mbd_plan_set_mpc_pick(self.h, C.byref(rec)))
+
+    def clear_mpc_pick(self):
+        _capi.check(self.lib.mbd_plan_set_mpc_pick(self.h, None))
+
+    def has_mpc_pick(self) -> bool:
+        """Whether the plan carries a pick record: asked of the library, so a record set through the C ABI counts."""
+        return _capi.has_mpc_pick(self.lib.mbd_plan_peek_mpc_pick, self.h, None)
+
+    def peek_mpc_pick(self, capacity: int = None) -> dict:
+        """``choice`` [n], ``rets`` [n, 3] and ``best`` [n] of the ticks the last episode or the session has served (the most
+        recent ``capacity``, oldest first; None: all)."""
+        return _capi.peek_mpc_pick(self.lib.mbd_plan_peek_mpc_pick, self.h, None, capacity)
 
     def mpc_open(self, key, warm_steps: int, exec_steps: int = 1, max_ticks: int = None) -> MpcSession:
         """Open a session (include/mbd_hip.h mbd_plan_mpc_open): ``run_mpc``'s episode advanced one tick per call from a state

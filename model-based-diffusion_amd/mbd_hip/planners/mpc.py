@@ -74,6 +74,15 @@ and the kept count of each diffusion step of the LAST tick, which is what the de
 
     python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --reject_nonfinite --ess_frac 0.25
 
+Every tick hands on its new mean, which nobody has rolled out.  ``--pick mean,prev,best`` (any non-empty subset; include/mbd_hip.h
+mbd_mpc_pick; DESIGN.md section 1 "N15 pick") evaluates the mean, the incumbent — the last tick's plan, shifted — and the best
+candidate of the tick's last step on the planner's model and hands on the best of those named: the rows executed, the next tick's
+warm start and ``means`` are the picked plan's.  ``--pick mean`` leaves the episode's bits alone and logs the value of every executed
+plan.  The details gain ``pick`` = dict(choice, rets, best) per tick, the report ``pick_log``: the share of ticks per choice and the
+mean value of the picked plan and of the mean.  ``--online`` and ``--n_episodes`` honour it.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --pick mean,prev,best
+
 A demo plan (``--enable_demo``) compares its 50 planned steps with the env's 50 demo rows; in an episode the demo has to move
 with the system.  ``--demo_clip env|FILE.npy`` (include/mbd_hip.h mbd_mpc_demo; DESIGN.md section 1 "N10 demo clock") sets the
 clip the episode follows — the env's own demo, or an array [n_track, L, 3] (car2d: [L, 2]) — and ``--demo_start c0`` the clip
@@ -166,6 +175,7 @@ class MpcArgs(Args):
     temp_min: float = 0.01  # ... inside [temp_min, temp_max] ...
     temp_max: float = 10.0
     ess_iters: int = 12  # ... by this many bisection steps
+    pick: str = ""  # "mean,prev,best" or any non-empty subset: what a tick may hand on (mbd_mpc_pick); "": the mean, nothing evaluated
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -354,6 +364,37 @@ def _weighting_settings(args: MpcArgs) -> dict:
                 ess_iters=args.ess_iters) if _has_weighting(args) else {}
 
 
+_PICK_NAMES = ("mean", "prev", "best")
+
+
+def _has_pick(args: MpcArgs) -> bool:
+    return bool(args.pick)
+
+
+def _pick_of(args: MpcArgs) -> dict:
+    """``Plan.set_mpc_pick``'s arguments from ``pick``: a comma-separated non-empty subset of mean, prev, best."""
+    names = [n.strip() for n in args.pick.split(",") if n.strip()]
+    if not names or any(n not in _PICK_NAMES for n in names):
+        raise ValueError(f"pick={args.pick!r}: a comma-separated non-empty subset of {', '.join(_PICK_NAMES)}")
+    return {n: n in names for n in _PICK_NAMES}
+
+
+def _pick_settings(args: MpcArgs) -> dict:
+    return dict(pick=args.pick) if _has_pick(args) else {}
+
+
+def _pick_log(log) -> dict:
+    """A pick log (one episode's dict, or a batch's list of them) as JSON: the share of ticks per choice and the mean value of the
+    picked plan and of the mean."""
+    logs = log if isinstance(log, list) else [log]
+    choice = np.concatenate([np.asarray(l["choice"]) for l in logs])
+    rets = np.concatenate([np.asarray(l["rets"], np.float32).reshape(-1, 3) for l in logs])
+    picked = rets[np.arange(len(choice)), choice] if len(choice) else rets[:, 0]
+    with np.errstate(all="ignore"):
+        return dict(share={n: float(np.mean(choice == k)) for k, n in enumerate(_PICK_NAMES)},
+                    picked_value_mean=float(np.mean(picked)), mean_value_mean=float(np.mean(rets[:, 0])))
+
+
 def _weighting_log(log: dict) -> dict:
     """A peeked log as JSON-ready lists."""
     return dict(temp=[float(x) for x in log["temp"]], ess=[float(x) for x in log["ess"]], kept=[int(x) for x in log["kept"]])
@@ -505,6 +546,8 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
         plan.set_objective(**_objective_of(args))
     if _has_weighting(args):
         plan.set_weighting(**_weighting_of(args))
+    if _has_pick(args):
+        plan.set_mpc_pick(**_pick_of(args))
     return env, plan, state_init, rng_exp
 
 
@@ -523,13 +566,15 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
     pe = env if plant is None else plant
     T, E = args.n_ticks, args.exec_steps
     s = np.ascontiguousarray(state_init.pipeline_state, np.float32).reshape(-1)
-    actions, rewards, states, means, predicted, secs, wlog = [], [], [s], [], [], [], []
+    actions, rewards, states, means, predicted, secs, wlog, plog = [], [], [s], [], [], [], [], []
     with plan.mpc_open(key, args.warm_steps, E, T) as session:
         for _ in range(T):
             out = session.tick(s)
             if _has_weighting(args):  # (between ticks: the tick's last score step)
                 wl = plan.peek_weighting()
                 wlog.append((wl["temp"][-1], wl["ess"][-1], wl["kept"][-1]))
+            if session.pick is not None:  # (a pick record: what the tick handed on)
+                plog.append(session.pick)
             rows = out["head"]  # (the rows to execute now: the plan's own first rows, or under a delay record the queue's head)
             rewss, fin = pe.rollout(State(s, None, np.float32(0), np.float32(0), {}), rows[None], want_final=True)
             s = fin[0].cpu().numpy().reshape(-1)
@@ -546,6 +591,9 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
     if wlog:  # per tick: the temperature, ESS and kept count of the tick's last step
         ep["weighting"] = dict(temp=np.array([w[0] for w in wlog], np.float32), ess=np.array([w[1] for w in wlog], np.float32),
                                kept=np.array([w[2] for w in wlog], np.int32))
+    if plog:
+        ep["pick"] = dict(choice=np.array([x["choice"] for x in plog], np.int32), rets=np.stack([x["rets"] for x in plog]),
+                          best=np.array([x["best"] for x in plog], np.int32))
     return ep
 
 
@@ -618,6 +666,8 @@ def _setup_batch(arg_list, device: int):
         sweep.set_objective(**_objective_of(a0))
     if _has_weighting(a0):  # (and one weighting record)
         sweep.set_weighting(**_weighting_of(a0))
+    if _has_pick(a0):  # (and one pick record)
+        sweep.set_mpc_pick(**_pick_of(a0))
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -656,7 +706,8 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
         shape = dict(shape, **_delay_settings(arg_list[0]), **_demo_settings(arg_list[0]), **_sigma_settings(arg_list[0]),
                      **_objective_settings(arg_list[0]), **_weighting_settings(arg_list[0]))
         windows = {"demo_windows": ep["demo_windows"]} if "demo_windows" in ep else {}  # (one table: every episode's)
-        return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, **windows, seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
+        pick = (lambda k: {"pick": ep["pick"][k]}) if "pick" in ep else (lambda k: {})
+        return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, **windows, **pick(k), seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
                               **_plant_settings(arg_list[k]), **shape) for k in range(len(arg_list))]
     return rewards
 
@@ -770,6 +821,8 @@ def _main(argv=None) -> dict:
         res.update(_demo_settings(args), track_err_mean=float(ep["track_err"].mean()))
     if wlog is not None:  # (the last tick's score steps)
         res.update(_weighting_settings(args), weighting_last_tick=_weighting_log(wlog))
+    if "pick" in ep:
+        res.update(_pick_settings(args), pick_log=_pick_log(ep["pick"]))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -804,6 +857,8 @@ def _main_online(args: MpcArgs) -> dict:
         res.update(_objective_settings(args), action_rate=action_rate(ep["actions"]))
     if "weighting" in ep:  # (per tick)
         res.update(_weighting_settings(args), weighting=_weighting_log(ep["weighting"]))
+    if "pick" in ep:
+        res.update(_pick_settings(args), pick_log=_pick_log(ep["pick"]))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -851,6 +906,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
             plan.set_objective(**_objective_of(a0))
         if _has_weighting(a0):
             plan.set_weighting(**_weighting_of(a0))
+        if _has_pick(a0):
+            plan.set_mpc_pick(**_pick_of(a0))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -880,6 +937,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
     if _has_objective(a0):
         res.update(_objective_settings(a0), action_rate=action_rate(ep["actions"]))
     res.update(_weighting_settings(a0))
+    if "pick" in ep:
+        res.update(_pick_settings(a0), pick_log=_pick_log(ep["pick"]))
     if _has_demo(a0):
         res.update(_demo_settings(a0), track_err_mean=float(ep["track_err"].mean()))
     if not a0.not_render:
