@@ -2,7 +2,7 @@
  * session (mbd_plan_mpc_open) is opened once and advanced one tick per call from the state the caller's system is in.
  *
  *   gcc -O2 -I include examples/mbd_control.c -o mbd_control -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
- *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi] [--pick]
+ *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi] [--pick] [--value]
  *                 env    N   H  Nd K ticks
  *
  * The "system" here is a second env the example owns, stepped with mbd_env_step — the env's rollout kernel at B = 1, H = 1 through
@@ -26,6 +26,10 @@
  * model values them, and its line gains "choice C value V": which one (0 mean, 1 incumbent, 2 best candidate) and the value of the
  * plan handed on, a health signal for a loop around a real system.  (MBD_PICK_MEAN alone would report the value and change no row.)
  * One more small rollout per tick; without the flag no record is set and nothing changes.
+ *
+ * --value (among the trailing flags): a value record (mbd_value) — here the smallest net there is, a linear value on the height of
+ * link 0 at the end of every candidate's rollout, weighing like one further reward row; a real controller loads a fitted net
+ * (python -m mbd_hip.scripts.fit_value) into the same struct.  Rigid-body envs only (the state record's float 2 is link 0's z).
  *
  * Prints one line per tick: "tick T reward R ms M flags F", then "mean_reward R ms_per_tick M". */
 #include <math.h>
@@ -52,9 +56,12 @@ static int plant_step(mbd_env* plant, float* state, const float* action, float* 
 }
 
 int main(int argc, char** argv) {
-  int mppi = 0, pick = 0;
-  while (argc > 1 && (strcmp(argv[argc - 1], "--mppi") == 0 || strcmp(argv[argc - 1], "--pick") == 0)) { /* trailing flags */
-    if (strcmp(argv[argc - 1], "--mppi") == 0) mppi = 1; else pick = 1;
+  int mppi = 0, pick = 0, value = 0;
+  while (argc > 1 && (strcmp(argv[argc - 1], "--mppi") == 0 || strcmp(argv[argc - 1], "--pick") == 0 ||
+                      strcmp(argv[argc - 1], "--value") == 0)) { /* trailing flags */
+    if (strcmp(argv[argc - 1], "--mppi") == 0) mppi = 1;
+    else if (strcmp(argv[argc - 1], "--pick") == 0) pick = 1;
+    else value = 1;
     argc -= 1;
   }
   float rate_cost = 0.0f;
@@ -111,6 +118,22 @@ int main(int argc, char** argv) {
     memset(&rec, 0, sizeof(rec));
     rec.candidates = MBD_PICK_MEAN | MBD_PICK_PREV | MBD_PICK_BEST;
     CHECK(mbd_plan_set_mpc_pick(plan, &rec));
+  }
+  if (value) { /* V(s_H) = z of link 0: one layer of one output, weighing like one more of the H reward rows */
+    float* w = (float*)calloc((size_t)S, sizeof(float));
+    const float bias = 0.0f;
+    if (!w) {
+      fprintf(stderr, "out of memory\n");
+      return 1;
+    }
+    w[2] = 1.0f;
+    mbd_value val;
+    memset(&val, 0, sizeof(val));
+    val.W[0] = w; val.b[0] = &bias;
+    val.n_in = S; val.n_layers = 1; val.width[0] = 1;
+    val.act = MBD_VALUE_RELU; val.scale = 1.0f / (float)H;
+    CHECK(mbd_plan_set_value(plan, &val)); /* (copied: the tables may go) */
+    free(w);
   }
   if (D > 0) { /* plans arrive D ticks late; the system starts committed to zeros */
     mbd_mpc_delay delay;

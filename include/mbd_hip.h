@@ -764,6 +764,67 @@ int mbd_plan_set_mpc_pick(mbd_plan* plan, const mbd_mpc_pick* rec);
  * 65536 ticks of a longer session).  MBD_ERR_STATE without a record. */
 int mbd_plan_peek_mpc_pick(mbd_plan* plan, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity, int* count_out);
 
+/* ---- terminal value: what the state a candidate's rollout ends in is worth (MPPI with a value function, TD-MPC, value-guided
+ * predictive sampling; no counterpart in the reference, whose plans score their Hsample rows and nothing beyond; DESIGN.md
+ * section 1 "N16 value") ---- */
+/* A value record is a small fully connected net V over the env's state record, a setting of a plan (of a sweep) beside the
+ * objective, weighting and pick records.  With a record in force every rollout launch that scores candidates also writes their
+ * final states, and ONE launch behind it (behind the objective record's, where there is one) adds scale * V(s_H) to each row's
+ * reward; the score, the weights and every update rule are unchanged and consume those rewards.  All pointers HOST, copied by the
+ * set call. */
+#define MBD_VALUE_MAX_LAYERS 4
+#define MBD_VALUE_MAX_WIDTH 256
+enum { MBD_VALUE_RELU = 0, MBD_VALUE_TANH = 1 };
+enum { MBD_VALUE_REL_XY = 1 };
+typedef struct mbd_value {
+  const float* W[MBD_VALUE_MAX_LAYERS]; /* W[l-1] of layer l = 1..n_layers: [width[l-1]][width of layer l-1 (n_in for l = 1)],
+                                           row-major — torch's nn.Linear.weight.  All entries finite                          */
+  const float* b[MBD_VALUE_MAX_LAYERS]; /* [width[l-1]], finite                                                               */
+  const float* center;   /* [n_in] or NULL = zeros; finite                                                                    */
+  const float* in_scale; /* [n_in] or NULL = ones; finite; 0 masks an input                                                   */
+  int32_t n_in;          /* must equal the env's state_size (n_links * 13; car2d 3)                                           */
+  int32_t n_layers;      /* 1 .. MBD_VALUE_MAX_LAYERS; 1 is a linear value                                                    */
+  int32_t width[MBD_VALUE_MAX_LAYERS]; /* entries [0, n_layers): 1 .. MBD_VALUE_MAX_WIDTH, the last one 1                     */
+  int32_t act;           /* MBD_VALUE_RELU / MBD_VALUE_TANH: every hidden layer's; the last layer has none                    */
+  int32_t flags;         /* MBD_VALUE_REL_XY (rigid-body envs only): link 0's x and y are subtracted from every link's        */
+  float   scale;         /* finite: the weight of V in a candidate's reward (V is neither discounted nor divided by Hsample:
+                            that is this number)                                                                              */
+  int32_t reserved[5];   /* must be 0 */
+} mbd_value;
+/* The contract.  f32 throughout, every operation rounded; fma is the fused multiply-add, exp_ the library's exponential (the
+ * primitive the weighting record's score uses).  Row b of a launch, s [n_in] its rollout's final state, W_l = W[l-1], b_l = b[l-1],
+ * width_0 = n_in:
+ *   REL_XY:  x0 = s[0], y0 = s[1];  for every link l:  s[13 l] = s[13 l] - x0,  s[13 l + 1] = s[13 l + 1] - y0
+ *   x_0[j]  = (s[j] - center[j]) * in_scale[j]
+ *   layer l = 1 .. n_layers, output o:  a = b_l[o];  for k = 0 .. width_{l-1} - 1 ascending:  a = fma(W_l[o][k], x_{l-1}[k], a)
+ *   hidden: x_l[o] = act(a);   last: V = a
+ *   relu(a) = a if a > 0;  +0 if a <= 0;  a if a is NaN
+ *   tanh(a):  m = |a| if |a| < 44 else 44;  t = exp_((-2) * m);  y = (1 - t) / (1 + t);  a if a is NaN, else copysign(y, a)
+ *   rews[b] = rews[b] + (scale * V)                                       (a product, then a sum; no fma)
+ * rews[b] on the right is what the step would score without the record: the rollout's mean over Hsample, or what an objective
+ * record left there.  The order is fixed within one (row, output) chain only; rows never meet, so a candidate whose final state is
+ * not finite gets whatever this arithmetic gives — usually NaN, which a weighting record then drops — and leaves every other row's
+ * bits alone.
+ * Where the record applies: mbd_plan_sample_rollout (the rows of the local shard), mbd_plan_reverse_once, mbd_plan_run, episodes
+ * and sessions, MBD and path-integral plans, lazy and materialised candidates, demo plans (the blend reads the rewards the record
+ * leaves), sweeps (one net for all plans), and the three slots of a pick record, whose returns then include scale * V.  Unchanged,
+ * as under an objective record: the rewards an episode reports, rew_final, the executed rows' rollouts, a delay record's
+ * prediction.  Without a record no buffer is allocated, no final state is written and nothing is launched: every bit is as it was.
+ * The set call copies the net (the weights transposed, for the kernel's coalesced reads), is synchronous and is to be called
+ * between diffusion steps; rec == NULL clears.  Refused before any device access, the message naming the field.
+ * MBD_ERR_INVALID: a NULL handle; non-zero reserved; n_in != state_size; n_layers outside 1 .. MBD_VALUE_MAX_LAYERS; a width
+ * outside 1 .. MBD_VALUE_MAX_WIDTH; a last width other than 1; an unknown act; unknown flags; a NULL W or b of a layer in use; a
+ * non-finite weight, bias, center, in_scale or scale.  MBD_ERR_UNSUPPORTED: MBD_VALUE_REL_XY on car2d (it has no links).
+ * MBD_ERR_STATE: a plan that carries an ensemble record (an ensemble launch returns rewards only) — and mbd_plan_set_ensemble on a
+ * plan that carries a value record —; a session open on the handle. */
+int mbd_plan_set_value(mbd_plan* plan, const mbd_value* rec);
+/* the last step's V per row (HOST [shard_count]; synchronises the device).  MBD_ERR_STATE without a record, or before a step has
+ * run with one. */
+int mbd_plan_peek_value(mbd_plan* plan, float* v_out);
+/* V of states the caller gives: states HOST [B][state_size], v_out HOST [B], B >= 1 — the step's kernel on rows of the caller's (a
+ * check of an imported net).  Synchronous.  MBD_ERR_STATE without a record; MBD_ERR_INVALID: NULL arguments, B < 1. */
+int mbd_plan_eval_value(mbd_plan* plan, const float* states, int B, float* v_out);
+
 /* ---- planning ahead of the plant: an episode whose plans take D ticks to arrive (the real-time iteration scheme; no
  * counterpart in the reference; DESIGN.md section 1 "N9 delay") ---- */
 /* The episode of mbd_plan_run_mpc plans from s_t and executes that plan's first rows from the same s_t: planning takes no time.
@@ -907,7 +968,7 @@ int mbd_plan_mpc_reset_mean(mbd_plan* plan);
 /* close: waits for a tick in flight and drops it.  NULL plan -> MBD_ERR_INVALID; no session open -> MBD_ERR_STATE.
  * mbd_plan_destroy closes an open session.  While a session is open, these calls on the same handle return MBD_ERR_STATE, the
  * message naming the session: mbd_plan_run, _run_mpc, _eval, _set_state0, _reverse_once, _sample_rollout, _score_update and
- * every mbd_plan_set_* record call (plant, ensemble, noise shape, noise basis, delay, demo, sigma, objective, weighting, pick). */
+ * every mbd_plan_set_* record call (plant, ensemble, noise shape, noise basis, delay, demo, sigma, objective, weighting, pick, value). */
 int mbd_plan_mpc_close(mbd_plan* plan);
 
 /* what the last step worked on, copied to HOST buffers (inspection / parity tests; synchronises the device): the
@@ -998,6 +1059,10 @@ int mbd_sweep_peek_weighting(mbd_sweep* sweep, int k, float* temp_out, float* es
  * n_plans episodes (blockIdx.y = episode), the rollout one launch over the 3 n_plans slots from the episodes' own states.  Refusals
  * as mbd_plan_set_mpc_pick's (sweeps take no ensemble). */
 int mbd_sweep_set_mpc_pick(mbd_sweep* sweep, const mbd_mpc_pick* rec);
+/* one value record (mbd_value, above) for all plans of the sweep — one net: plan k of mbd_sweep_run, episode k of mbd_sweep_run_mpc
+ * and of a sweep's session is then the single plan's with the same record, bit for bit, whatever the other plans do.  One launch over
+ * the n_plans * Nsample rows per step.  Refusals as mbd_plan_set_value's (sweeps take no ensemble). */
+int mbd_sweep_set_value(mbd_sweep* sweep, const mbd_value* rec);
 /* episode k's log; as mbd_plan_peek_mpc_pick; k outside [0, n_plans) -> MBD_ERR_INVALID */
 int mbd_sweep_peek_mpc_pick(mbd_sweep* sweep, int k, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity,
                             int* count_out);

@@ -83,6 +83,14 @@ int mbd_debug_weighting_host(const float* rews, int N, float temp, int std_guard
  * workgroup per row; best_out [P]: the lowest index among the maxima of the row's finite entries, -1 where none is finite.  NULL
  * arguments, P outside [1, 65535] or N < 1 -> MBD_ERR_INVALID before any device access; no device -> MBD_ERR_NO_DEVICE. */
 int mbd_debug_pick_best(const float* rews, int P, int N, int32_t* best_out);
+/* The refusals a value record alone decides (include/mbd_hip.h mbd_value) for an env of that state_size; rigid_body != 0: the env
+ * has links (MBD_VALUE_REL_XY allowed).  The function both set calls run on their record, host arithmetic, no device. */
+int mbd_debug_check_value(const mbd_value* rec, int state_size, int rigid_body);
+/* value_kernel's arithmetic on the HOST: the functions the kernel calls (one text for host and device) over B rows in a loop, no
+ * device touched.  The record is checked as the set calls check it against state_size = rec->n_in.  HOST states [B][n_in], rews
+ * [B] or NULL; v_out [B]: V; rews_out [B] or NULL: rews + (scale * V). */
+int mbd_debug_value_host(const mbd_value* rec, int rigid_body, const float* states, const float* rews, int B, float* v_out,
+                         float* rews_out);
 #ifdef __cplusplus
 }
 #endif

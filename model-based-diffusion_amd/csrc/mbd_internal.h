@@ -442,6 +442,37 @@ struct ObjectiveRec {
   int peek(const mbd_env* env, int k, float* ret_out, float* cost_out, const char* what) const;
 };
 int check_objective(const mbd_objective* rec, int Hsample, int action_size, float* wsum_out);
+// The value record of a plan or a sweep (include/mbd_hip.h mbd_value) as the handle keeps it, with what the two handles do alike.
+// check_value: the refusals the record alone decides against the env's state_size and kind, in the header's order, each naming the
+// field — host arithmetic on the record's own tables, before any device access.  set: behind the handle's NULL, session and ensemble
+// checks and check_value (nullptr clears); copies the net onto the device, every layer transposed, and makes room for the final
+// states and the V of max_rows rows (a plan: its shard; a sweep: P N) and of the 3 P slots of a pick record.  final(): what a
+// rollout launch is handed as d_state_final — nullptr without a record, so that a launch without one is what it was.  launch: the
+// kernel over B rows of d_fin, d_rews rewritten in place, V into d_v_keep (defined in mbd_plan.hip, which alone compiles the kernel);
+// launch_step: the same over the step's own buffers, what peek shows.
+struct ValueRec {
+  bool has = false, stepped = false;
+  int S = 0, n_layers = 0, act = 0, rel = 0, rows = 0;
+  size_t max_rows = 0;
+  int width[4] = {0, 0, 0, 0};
+  float scale = 0.0f;
+  DevBuf<float> d_net;  // center [S] | in_scale [S] | per layer: Wt [K][width] | b [width]
+  size_t off_W[4] = {0, 0, 0, 0}, off_b[4] = {0, 0, 0, 0};
+  DevBuf<float> d_final, d_v, d_pick_final, d_pick_v, d_eval_in, d_eval_v;
+  int set(const mbd_value* rec, const mbd_env* env, size_t max_rows_, int P);
+  float* final() const { return has ? d_final.get() : nullptr; }
+  float* pick_final() const { return has ? d_pick_final.get() : nullptr; }
+  int launch(const float* d_fin, float* d_rews, int B, float* d_v_keep, hipStream_t s) const;
+  int launch_step(float* d_rews, int B, hipStream_t s) {
+    if (!has) return MBD_OK;
+    rows = B;
+    stepped = true;
+    return launch(d_final, d_rews, B, d_v, s);
+  }
+  int peek(const mbd_env* env, float* v_out, const char* what) const;
+  int eval(const mbd_env* env, const float* states, int B, float* v_out, const char* what);
+};
+int check_value(const mbd_value* rec, int state_size, bool rigid_body);
 // The weighting record of a plan or a sweep (include/mbd_hip.h mbd_weighting) as the handle keeps it.  check_weighting: the refusals
 // the record alone decides, in the header's order, each naming the field, before any device access.  set: behind the handle's NULL,
 // session and enable_demo checks (nullptr clears); makes room for the log — three arrays [P][cap], cap = Ndiffuse - 1 entries per
@@ -495,7 +526,7 @@ struct PickRec {
   DevBuf<int> d_best, d_log_choice, d_log_best;
   int set(const mbd_mpc_pick* rec, int device, int P_, int HNu_, int H_);
   int start(long long n_ticks);
-  int tick(mbd_env* env, ObjectiveRec& obj, const PickTick& tk, hipStream_t s);
+  int tick(mbd_env* env, ObjectiveRec& obj, const ValueRec& val, const PickTick& tk, hipStream_t s);
   int peek(const mbd_env* env, int k, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity, int* count_out,
            const char* what) const;
 };

@@ -4,6 +4,7 @@
 // mbd_plan_eval, mbd_plan_peek; the receding-horizon loop mbd_plan_run_mpc).  mbd_planner.py:84-148,179-180.
 #define MBD_WEIGH_KERNEL 1  // this unit launches weigh_kernel (mbd_step_kernels.h)
 #define MBD_PICK_KERNEL 1   // ... and, for plans and sweeps alike, the pick record's kernels
+#define MBD_VALUE_KERNEL 1  // ... and the value record's
 #include "mbd_internal.h"
 #include "../../include/mbd_hip_debug.h"
 
@@ -190,6 +191,8 @@ struct mbd_plan {
   WeightingRec wt;
   // the pick record (mbd_plan_set_mpc_pick) with its slots and the device log of its ticks
   PickRec pick;
+  // the value record (mbd_plan_set_value) with its net, the shard's final states and the last step's V
+  ValueRec val;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_plan_mpc_open); it uses the episodes' buffers above — d_mpc_state for the
   // state handed in, d_mpc_pred for the one predicted state, d_mpc_queue — so a handle runs episodes or a session, not both
@@ -573,7 +576,7 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
     p->ens_stepped = true;
   } else {
     MBD_TRY(launch_rollout(e, d_state0, d_cand + (size_t)c.shard_begin * HNu, c.shard_count, H, p->d_rewss, d_rews_local,
-                           (c.enable_demo && !fused_lp) ? p->d_xpos.get() : nullptr, nullptr, s, p->lazy ? &lz : nullptr,
+                           (c.enable_demo && !fused_lp) ? p->d_xpos.get() : nullptr, p->val.final(), s, p->lazy ? &lz : nullptr,
                            nullptr, fused_lp ? d_logpd_local : nullptr, nullptr, d_xref));
   }
   MBD_TRY(p->timing.end(s));
@@ -583,6 +586,9 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
   // mean is already marked as the buffer's last reader.
   if (p->obj.has && !p->has_ens)
     MBD_TRY(p->obj.launch(p->d_rewss, d_rews_local, c.shard_count, c.shard_begin, d_cand, p->lazy, p->sigmas[i], d_Ybar_i, -1, s));
+  // The value record: ONE launch behind the objective's adds scale * V of the shard's final states, which the rollout above wrote
+  // (never under an ensemble: the set calls refuse the pair)
+  MBD_TRY(p->val.launch_step(d_rews_local, c.shard_count, s));
   MBD_TRY(finish_noise_job(p, lz, marked));
   if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, p->d_xpos, c.shard_count, H, d_logpd_local, s, d_xref));
   return MBD_OK;
@@ -1372,6 +1378,8 @@ extern "C" int mbd_plan_set_ensemble(mbd_plan* p, const mbd_ensemble* rec) {
   if (p->pick.has)
     return fail(MBD_ERR_UNSUPPORTED, "ensemble: the plan carries a pick record (mbd_plan_set_mpc_pick): the pick compares returns, an "
                                      "ensemble's reward is a reduction over members");
+  if (p->val.has)
+    return fail(MBD_ERR_STATE, "ensemble: the plan carries a value record (mbd_plan_set_value): an ensemble launch returns rewards only");
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the previous record's buffers)
   const size_t N = (size_t)p->cfg.Nsample, H = (size_t)p->cfg.Hsample, M = (size_t)rec->n_members;
@@ -1574,6 +1582,189 @@ extern "C" int mbd_plan_set_objective(mbd_plan* p, const mbd_objective* rec) {
 extern "C" int mbd_plan_peek_objective(mbd_plan* p, float* ret_out, float* cost_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
   return p->obj.peek(p->env, 0, ret_out, cost_out, "plan");
+}
+
+// ---- the value record (include/mbd_hip.h mbd_value) ---------------------------------------------------------------------------
+int check_value(const mbd_value* rec, int state_size, bool rigid_body) {
+  for (int r = 0; r < 5; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "value: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (rec->n_in != state_size) return fail(MBD_ERR_INVALID, "value: n_in=%d, the env's state_size is %d", rec->n_in, state_size);
+  if (rec->n_layers < 1 || rec->n_layers > MBD_VALUE_MAX_LAYERS)
+    return fail(MBD_ERR_INVALID, "value: n_layers=%d: must lie in 1..%d", rec->n_layers, MBD_VALUE_MAX_LAYERS);
+  for (int l = 0; l < rec->n_layers; ++l)
+    if (rec->width[l] < 1 || rec->width[l] > MBD_VALUE_MAX_WIDTH)
+      return fail(MBD_ERR_INVALID, "value: width[%d]=%d: must lie in 1..%d", l, rec->width[l], MBD_VALUE_MAX_WIDTH);
+  if (rec->width[rec->n_layers - 1] != 1)
+    return fail(MBD_ERR_INVALID, "value: width[%d]=%d: the last layer's width must be 1", rec->n_layers - 1, rec->width[rec->n_layers - 1]);
+  if (rec->act != MBD_VALUE_RELU && rec->act != MBD_VALUE_TANH) return fail(MBD_ERR_INVALID, "value: act=%d: RELU (0) or TANH (1)", rec->act);
+  if (rec->flags & ~MBD_VALUE_REL_XY) return fail(MBD_ERR_INVALID, "value: flags=%d: unknown bits (REL_XY 1)", rec->flags);
+  if ((rec->flags & MBD_VALUE_REL_XY) && !rigid_body)
+    return fail(MBD_ERR_UNSUPPORTED, "value: flags: MBD_VALUE_REL_XY needs a rigid-body env (car2d has no links)");
+  if (!std::isfinite(rec->scale)) return fail(MBD_ERR_INVALID, "value: scale=%g: must be finite", (double)rec->scale);
+  if (state_size > kValueMaxWidth) return fail(MBD_ERR_INVALID, "value: n_in=%d: at most %d", rec->n_in, kValueMaxWidth);
+  for (int j = 0; rec->center && j < state_size; ++j)
+    if (!std::isfinite(rec->center[j])) return fail(MBD_ERR_INVALID, "value: center[%d]=%g: must be finite", j, (double)rec->center[j]);
+  for (int j = 0; rec->in_scale && j < state_size; ++j)
+    if (!std::isfinite(rec->in_scale[j])) return fail(MBD_ERR_INVALID, "value: in_scale[%d]=%g: must be finite", j, (double)rec->in_scale[j]);
+  int K = state_size;
+  for (int l = 0; l < rec->n_layers; ++l) {
+    const int W = rec->width[l];
+    if (!rec->W[l]) return fail(MBD_ERR_INVALID, "value: W[%d] is NULL", l);
+    if (!rec->b[l]) return fail(MBD_ERR_INVALID, "value: b[%d] is NULL", l);
+    for (size_t e = 0; e < (size_t)W * K; ++e)
+      if (!std::isfinite(rec->W[l][e]))
+        return fail(MBD_ERR_INVALID, "value: W[%d][%zu][%zu]=%g: must be finite", l, e / K, e % K, (double)rec->W[l][e]);
+    for (int o = 0; o < W; ++o)
+      if (!std::isfinite(rec->b[l][o])) return fail(MBD_ERR_INVALID, "value: b[%d][%d]=%g: must be finite", l, o, (double)rec->b[l][o]);
+    K = W;
+  }
+  return MBD_OK;
+}
+extern "C" int mbd_debug_check_value(const mbd_value* rec, int state_size, int rigid_body) {
+  if (!rec) return fail(MBD_ERR_INVALID, "value record is NULL");
+  if (state_size < 0) return fail(MBD_ERR_INVALID, "state_size=%d", state_size);
+  return check_value(rec, state_size, rigid_body != 0);
+}
+// include/mbd_hip_debug.h: value_kernel's functions on the host (one text for host and device), row by row — no device is touched
+extern "C" int mbd_debug_value_host(const mbd_value* rec, int rigid_body, const float* states, const float* rews, int B, float* v_out,
+                                    float* rews_out) {
+  if (!rec || !states || !v_out) return fail(MBD_ERR_INVALID, "NULL argument");
+  if (B < 1) return fail(MBD_ERR_INVALID, "value_host: B=%d", B);
+  if (rews_out && !rews) return fail(MBD_ERR_INVALID, "value_host: rews_out needs rews");
+  MBD_TRY(check_value(rec, rec->n_in, rigid_body != 0));
+  const int S = rec->n_in, rel = rec->flags & MBD_VALUE_REL_XY;
+  std::vector<float> center((size_t)S, 0.0f), in_scale((size_t)S, 1.0f), x(kValueMaxWidth), y(kValueMaxWidth);
+  if (rec->center) center.assign(rec->center, rec->center + S);
+  if (rec->in_scale) in_scale.assign(rec->in_scale, rec->in_scale + S);
+  for (int b = 0; b < B; ++b) {
+    for (int j = 0; j < S; ++j) x[j] = value_input(states + (size_t)b * S, j, rel, center.data(), in_scale.data());
+    int K = S;
+    float V = 0.0f;
+    for (int l = 0; l < rec->n_layers; ++l) {
+      const int W = rec->width[l];
+      for (int o = 0; o < W; ++o) {
+        float a = rec->b[l][o];
+        for (int k = 0; k < K; ++k) a = value_step(rec->W[l][(size_t)o * K + k], x[k], a);
+        y[o] = l + 1 < rec->n_layers ? value_act(a, rec->act) : a;
+      }
+      V = y[0];
+      x.swap(y);
+      K = W;
+    }
+    v_out[b] = V;
+    if (rews_out) rews_out[b] = value_add(rews[b], rec->scale, V);
+  }
+  return MBD_OK;
+}
+
+int ValueRec::set(const mbd_value* rec, const mbd_env* env, size_t max_rows_, int P) {
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the previous record's net)
+  has = false;
+  stepped = false;
+  if (!rec) return MBD_OK;
+  S = rec->n_in; n_layers = rec->n_layers; act = rec->act; rel = rec->flags & MBD_VALUE_REL_XY; scale = rec->scale;
+  max_rows = max_rows_;
+  std::vector<float> net((size_t)2 * S);
+  for (int j = 0; j < S; ++j) {
+    net[j] = rec->center ? rec->center[j] : 0.0f;
+    net[(size_t)S + j] = rec->in_scale ? rec->in_scale[j] : 1.0f;
+  }
+  int K = S;
+  for (int l = 0; l < n_layers; ++l) {
+    const int W = width[l] = rec->width[l];
+    off_W[l] = net.size();
+    net.resize(net.size() + (size_t)K * W);
+    for (int o = 0; o < W; ++o)  // transposed: Wt[k][o]
+      for (int k = 0; k < K; ++k) net[off_W[l] + (size_t)k * W + o] = rec->W[l][(size_t)o * K + k];
+    off_b[l] = net.size();
+    net.insert(net.end(), rec->b[l], rec->b[l] + W);
+    K = W;
+  }
+  HIP_TRY(d_net.alloc(net.size()));
+  HIP_TRY(hipMemcpy(d_net, net.data(), sizeof(float) * net.size(), hipMemcpyHostToDevice));
+  HIP_TRY(d_final.grow(max_rows * S));
+  HIP_TRY(d_v.grow(max_rows));
+  HIP_TRY(d_pick_final.grow((size_t)3 * P * S));
+  HIP_TRY(d_pick_v.grow((size_t)3 * P));
+  has = true;
+  return MBD_OK;
+}
+
+// The tile: how many rows a workgroup takes.  More rows reuse a weight more often, leave fewer workgroups and make each one's
+// chain of dependent loads longer.  Measured (docs/experiments.md section 26): 4 rows beat 8 and 16 at 1024 rows and at 4096, where
+// even 16 rows leave every CU a workgroup — the launch is bound by the latency of its weight loads, not by their volume — so 4 it
+// is.  The lever MBD_VALUE_TILE = 8 / 16 selects the other instantiations for tests and A/B runs (the bits do not depend on it: a
+// row's chains are its own whatever the tile).
+static int value_tile() {
+  const int forced = lever("MBD_VALUE_TILE");
+  return (forced == 8 || forced == 16) ? forced : 4;
+}
+
+int ValueRec::launch(const float* d_fin, float* d_rews, int B, float* d_v_keep, hipStream_t s) const {
+  if (!has) return MBD_OK;
+  ValueArgs A;
+  A.fin = d_fin; A.rews = d_rews; A.v_keep = d_v_keep;
+  A.B = B; A.S = S; A.n_layers = n_layers; A.act = act; A.rel = rel ? 1 : 0; A.scale = scale;
+  int widest = 64;  // threads: the widest hidden layer, in whole wavefronts (the staging loop and the last layer take any count >= 16)
+  for (int l = 0; l < kValueMaxLayers; ++l) {
+    A.width[l] = l < n_layers ? width[l] : 0;
+    A.Wt[l] = l < n_layers ? d_net.get() + off_W[l] : nullptr;
+    A.b[l] = l < n_layers ? d_net.get() + off_b[l] : nullptr;
+    if (l + 1 < n_layers && width[l] > widest) widest = width[l];
+  }
+  A.center = d_net.get();
+  A.in_scale = d_net.get() + S;
+  const dim3 block((unsigned)((widest + 63) / 64 * 64));
+  const int C = value_tile();
+  const dim3 grid((unsigned)((B + C - 1) / C));
+  if (C == 16) hipLaunchKernelGGL(value_kernel<16>, grid, block, 0, s, A);
+  else if (C == 8) hipLaunchKernelGGL(value_kernel<8>, grid, block, 0, s, A);
+  else hipLaunchKernelGGL(value_kernel<4>, grid, block, 0, s, A);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+
+int ValueRec::peek(const mbd_env* env, float* v_out, const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_value: the %s has no value record", what);
+  if (!stepped) return fail(MBD_ERR_STATE, "peek_value: no diffusion step with the record to show yet");
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (v_out) HIP_TRY(hipMemcpy(v_out, d_v.get(), sizeof(float) * rows, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
+int ValueRec::eval(const mbd_env* env, const float* states, int B, float* v_out, const char* what) {
+  if (!states || !v_out) return fail(MBD_ERR_INVALID, "eval_value: NULL argument");
+  if (B < 1) return fail(MBD_ERR_INVALID, "eval_value: B=%d", B);
+  if (!has) return fail(MBD_ERR_STATE, "eval_value: the %s has no value record", what);
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(d_eval_in.grow((size_t)B * S));
+  HIP_TRY(d_eval_v.grow(B));
+  HIP_TRY(hipMemcpy(d_eval_in, states, sizeof(float) * (size_t)B * S, hipMemcpyHostToDevice));
+  MBD_TRY(launch(d_eval_in, nullptr, B, d_eval_v, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(v_out, d_eval_v.get(), sizeof(float) * B, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_set_value(mbd_plan* p, const mbd_value* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  NO_SESSION(p, "set_value");
+  if (rec) MBD_TRY(check_value(rec, p->env->state_size(), p->env->kind == ENV_MODEL));  // (before any device access)
+  if (rec && p->has_ens)
+    return fail(MBD_ERR_STATE, "value record: the plan carries an ensemble record (an ensemble launch returns rewards only)");
+  return p->val.set(rec, p->env, (size_t)p->cfg.shard_count, 1);
+}
+
+extern "C" int mbd_plan_peek_value(mbd_plan* p, float* v_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->val.peek(p->env, v_out, "plan");
+}
+
+extern "C" int mbd_plan_eval_value(mbd_plan* p, const float* states, int B, float* v_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->val.eval(p->env, states, B, v_out, "plan");
 }
 
 // ---- the weighting record (include/mbd_hip.h mbd_weighting) --------------------------------------------------------------
@@ -1784,7 +1975,9 @@ int PickRec::start(long long n_ticks) {
 // that step's weighted mean — the buffer of normals is next written two steps later, by a job that is ordered behind the NEXT
 // rollout launch of the handle or behind a mark on this stream, both behind this launch —, and the choose kernel writes P_t over
 // M_t in front of everything that reads it: the objective's next prev, the boundary kernels, the execution of the rows.
-int PickRec::tick(mbd_env* env, ObjectiveRec& obj, const PickTick& tk, hipStream_t s) {
+// Under a value record the slots' rollout writes their final states and the value launch follows the objective's, as in a step: the
+// three returns are what the planner maximises.
+int PickRec::tick(mbd_env* env, ObjectiveRec& obj, const ValueRec& val, const PickTick& tk, hipStream_t s) {
   if (!has) return MBD_OK;
   if (cap < 1) return fail(MBD_ERR_STATE, "mpc pick: the record's log was not started");
   const int S = env->state_size();
@@ -1798,8 +1991,9 @@ int PickRec::tick(mbd_env* env, ObjectiveRec& obj, const PickTick& tk, hipStream
   hipLaunchKernelGGL(pick_gather_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), 0, s, G);
   HIP_TRY(hipGetLastError());
   const int sw[3] = {3, S, 0};  // (a sweep of three-candidate plans: plan k's slots start from plan k's state)
-  MBD_TRY(launch_rollout(env, tk.state, d_slots, 3 * P, H, d_rewss, d_rets, nullptr, nullptr, s, nullptr, P > 1 ? sw : nullptr));
+  MBD_TRY(launch_rollout(env, tk.state, d_slots, 3 * P, H, d_rewss, d_rets, nullptr, val.pick_final(), s, nullptr, P > 1 ? sw : nullptr));
   if (obj.has) MBD_TRY(obj.launch_rows(d_rewss, d_rets, 3, d_slots, d_obj_ret, d_obj_cost, P > 1, s));
+  MBD_TRY(val.launch(val.pick_final(), d_rets, 3 * P, val.d_pick_v, s));
   const long long at = count % cap;
   PickChoose C;
   C.rets = d_rets; C.slots = d_slots; C.best = d_best; C.HNu = HNu; C.mask = mask; C.cold = tk.cold;
@@ -1929,7 +2123,7 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
     pt.lazy = p->lazy; pt.sigma = p->sigmas[1]; pt.ybar_i = last_in; pt.ybar_i_stride = 0;
     pt.M = last_out; pt.M_stride = 0; pt.B = p->d_Ybar; pt.B_stride = 0;
     pt.cold = tk.cold ? 1u : 0u;
-    MBD_TRY(p->pick.tick(p->env, p->obj, pt, s));
+    MBD_TRY(p->pick.tick(p->env, p->obj, p->val, pt, s));
   }
   *mean = cur;
   // with an objective record, the next tick's previous action: clip(M_t[E-1]) — the commanded row, whatever a plant record adds to

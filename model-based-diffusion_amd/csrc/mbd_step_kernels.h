@@ -1701,4 +1701,105 @@ static __global__ __launch_bounds__(256) void pick_choose_kernel(PickChoose A) {
 }
 #endif  // MBD_PICK_KERNEL
 
+// ---- the terminal value (mbd_plan_set_value, include/mbd_hip.h mbd_value): behind a rollout launch (and the objective's), the
+// rows' final states -> rews[b] = rews[b] + (scale * V(s_H)).  Last in this header under its own guard, for weigh_kernel's reason:
+// only mbd_plan.hip, which launches it for plans and sweeps alike, emits it, behind the pick kernels ----
+// The arithmetic of one row is the functions below, host and device text: mbd_debug_value_host loops them on the CPU, where a test
+// without a device holds them to the checker.  f32, every operation rounded (the build's -ffp-contract=off; the fma is explicit).
+#ifdef MBD_VALUE_KERNEL
+constexpr int kValueMaxLayers = 4;
+constexpr int kValueMaxWidth = 256;
+// input j of a row whose final state is s: under REL_XY the x and y of every link (floats 0 and 1 of its 13) less link 0's
+MBD_HD float value_input(const float* __restrict__ s, int j, int rel, const float* __restrict__ center,
+                         const float* __restrict__ in_scale) {
+  float v = s[j];
+  const int c = j % MBD_LINK_STATE;
+  if (rel && c < 2) v = v - s[c];
+  return (v - center[j]) * in_scale[j];
+}
+MBD_HD float value_step(float w, float x, float a) { return ffma(w, x, a); }
+MBD_HD float value_relu(float a) { return a > 0.0f ? a : (a <= 0.0f ? 0.0f : a); }
+MBD_HD float value_tanh(float a) {
+  const float aa = fabs_(a);
+  const float m = aa < 44.0f ? aa : 44.0f;
+  const float t = exp_(-2.0f * m);
+  const float y = (1.0f - t) / (1.0f + t);
+  return a != a ? a : __builtin_copysignf(y, a);
+}
+MBD_HD float value_act(float a, int act) { return act == 1 ? value_tanh(a) : value_relu(a); }
+MBD_HD float value_add(float rew, float scale, float V) { return rew + scale * V; }
+
+// The net on the device: layer l's weights TRANSPOSED, Wt[l] [K_l][width_l] (K_l: the layer's inputs), so that the lanes of a
+// wavefront — output units — read one row k with consecutive addresses.
+struct ValueArgs {
+  const float* fin;   // [B][S] the rows' final states
+  float* rews;        // [B] in / out, or nullptr: V only (mbd_plan_eval_value)
+  float* v_keep;      // [B] V
+  int B, S, n_layers, act, rel;
+  int width[kValueMaxLayers];
+  const float* Wt[kValueMaxLayers];
+  const float* b[kValueMaxLayers];
+  const float* center;    // [S]
+  const float* in_scale;  // [S]
+  float scale;
+};
+// One workgroup takes a tile of C rows; its threads are output units.  The tile's activations lie in LDS as x[k][C]: in the loop
+// over k every lane reads the SAME C floats (a broadcast: no bank conflict, one ds_read_b128 per four rows) and one weight of its
+// own, and runs C independent fma chains in registers — the contract fixes the order within a (row, output) chain only, and each
+// chain here runs k ascending from its bias.  A weight is read once per workgroup and used C times.  The last layer has one output:
+// there the lanes are the tile's rows instead (lane c walks row c's chain; the weight is the uniform operand).  No MFMA: the matrix
+// unit sums a tile's products in an order of its own that no checker can restate in float32, and this contract is bit for bit.
+// Rows never meet: row c of the tile has its own accumulators and its own column of x; rows >= B stage zeros, compute and store
+// nothing.  Bounds: fin is read at rows < B only, x0 / x1 hold kValueMaxWidth x C floats and every width and S is <= kValueMaxWidth
+// (the set call), thread o writes x[o][.] only for o < width <= kValueMaxWidth.  Plain vector loads and stores.
+template <int C>
+static __global__ __launch_bounds__(kValueMaxWidth) void value_kernel(ValueArgs A) {
+  static_assert(MBD_MAX_LINKS * MBD_LINK_STATE <= kValueMaxWidth, "a state record fits the activation buffers");
+  __shared__ float xa[kValueMaxWidth * C];
+  __shared__ float xb[kValueMaxWidth * C];
+  const int tid = threadIdx.x;
+  const int row0 = blockIdx.x * C;
+  for (int e = tid; e < A.S * C; e += blockDim.x) {  // x_0, e = c S + j: consecutive threads read consecutive floats of a row
+    const int c = e / A.S, j = e - c * A.S;
+    const int b = row0 + c;
+    xa[j * C + c] = b < A.B ? value_input(A.fin + (size_t)b * A.S, j, A.rel, A.center, A.in_scale) : 0.0f;
+  }
+  __syncthreads();
+  float* xin = xa;
+  float* xout = xb;
+  int K = A.S;
+  for (int l = 0; l + 1 < A.n_layers; ++l) {  // the hidden layers
+    const int W = A.width[l];
+    if (tid < W) {
+      const float* __restrict__ w = A.Wt[l] + tid;
+      const float bias = A.b[l][tid];
+      float acc[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[c] = bias;
+#pragma unroll 8
+      for (int k = 0; k < K; ++k) {  // (the loads do not depend on the chains: unrolled, eight weights are in flight)
+        const float wv = w[(size_t)k * W];
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = value_step(wv, xin[k * C + c], acc[c]);
+      }
+#pragma unroll
+      for (int c = 0; c < C; ++c) xout[tid * C + c] = value_act(acc[c], A.act);
+    }
+    __syncthreads();
+    float* t = xin; xin = xout; xout = t;
+    K = W;
+  }
+  if (tid < C && row0 + tid < A.B) {  // the last layer: lane = row of the tile
+    const int l = A.n_layers - 1;
+    const float* __restrict__ w = A.Wt[l];
+    float a = A.b[l][0];
+#pragma unroll 8
+    for (int k = 0; k < K; ++k) a = value_step(w[k], xin[k * C + tid], a);
+    const int b = row0 + tid;
+    A.v_keep[b] = a;
+    if (A.rews) A.rews[b] = value_add(A.rews[b], A.scale, a);
+  }
+}
+#endif  // MBD_VALUE_KERNEL
+
 }  // namespace mbd

@@ -123,6 +123,8 @@ struct mbd_sweep {
   NoiseSpec noise_warm() const { return noise_spec(true); }
   // the objective record of all the sweep's plans (mbd_sweep_set_objective): a plan's, with every plan's previous action [P][Nu]
   ObjectiveRec obj;
+  // the value record of all the sweep's plans (mbd_sweep_set_value): one net, the P N rows' final states and the last step's V
+  ValueRec val;
   // the weighting record of all the sweep's plans (mbd_sweep_set_weighting) with every plan's log [P][Ndiffuse - 1]
   WeightingRec wt;
   // the pick record of all the sweep's episodes (mbd_sweep_set_mpc_pick) with every episode's slots and log
@@ -281,10 +283,12 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
   HIP_TRY(hipGetLastError());
   MBD_TRY(w->timing.begin(s));
   const int sw[3] = {N, S, 0};
-  MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, nullptr, s, nullptr, sw));
+  MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, w->val.final(), s, nullptr, sw));
   MBD_TRY(w->timing.end(s));
   // the objective record: one launch over the P N rows (blockIdx.y = plan) on the materialised candidates
   if (w->obj.has) MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_Y0s, false, 0.0f, nullptr, 0, s));
+  // the value record: one launch over the P N rows behind it (one net: the plans' rows are one batch)
+  MBD_TRY(w->val.launch_step(w->d_rews, P * N, s));
   pb.mu = mu_stride;
   if (c.update_method == 3) {  // cem_update (path_integral.py:48-52)
     const int K = N < 10 ? N : 10;
@@ -436,7 +440,7 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
   MBD_TRY(w->timing.begin(s));
   const bool fused_lp = c.enable_demo && rollout_choice(e, P * N, H, sw).fuses_logpd;  // (mbd_plan.hip: the log-densities out of the rollout)
   MBD_TRY(launch_rollout(e, st.state0, w->d_eps[cur], P * N, H, w->d_rewss, w->d_rews,
-                         (c.enable_demo && !fused_lp) ? w->d_xpos.get() : nullptr, nullptr, s, &lz, sw,
+                         (c.enable_demo && !fused_lp) ? w->d_xpos.get() : nullptr, w->val.final(), s, &lz, sw,
                          fused_lp ? w->d_lp.get() : nullptr, nullptr, st.xref));
   MBD_TRY(w->timing.end(s));
   if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, w->d_xpos, P * N, H, w->d_lp, s, st.xref));
@@ -444,6 +448,8 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
   // change: the launch reads eps[cur] on the steps' stream in front of the weighted mean, which is the buffer's last reader.
   if (w->obj.has)
     MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_eps[cur], true, w->sigmas[i], st.ybar_in, st.ybar_in_stride, s));
+  // the value record: one launch over the P N rows behind it (one net: the plans' rows are one batch)
+  MBD_TRY(w->val.launch_step(w->d_rews, P * N, s));
   ScoreBatch sb;
   sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)N * HNu;
   sb.ybar_in = st.ybar_in_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
@@ -544,6 +550,14 @@ extern "C" int mbd_sweep_peek_objective(mbd_sweep* w, int k, float* ret_out, flo
   return w->obj.peek(w->env, k, ret_out, cost_out, "sweep");
 }
 
+// one value record for all plans of the sweep (include/mbd_hip.h mbd_value), as mbd_plan_set_value
+extern "C" int mbd_sweep_set_value(mbd_sweep* w, const mbd_value* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  NO_SWEEP_SESSION(w, "set_value");
+  if (rec) MBD_TRY(check_value(rec, w->env->state_size(), w->env->kind == ENV_MODEL));  // (before any device access)
+  return w->val.set(rec, w->env, (size_t)w->P * w->cfg.Nsample, w->P);
+}
+
 // one weighting record for all plans of the sweep (include/mbd_hip.h mbd_weighting), as mbd_plan_set_weighting
 extern "C" int mbd_sweep_set_weighting(mbd_sweep* w, const mbd_weighting* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
@@ -593,7 +607,7 @@ int sweep_pick(mbd_sweep* w, const float* plan_from, const float* ybar0, int i_s
   pt.M = w->d_mu + (size_t)(Nd - 2) * HNu; pt.M_stride = mu_stride;
   pt.B = ybar0; pt.B_stride = HNu;
   pt.cold = cold;
-  return w->pick.tick(w->env, w->obj, pt, s);
+  return w->pick.tick(w->env, w->obj, w->val, pt, s);
 }
 }  // namespace
 

@@ -122,6 +122,20 @@ class MpcPick(C.Structure):
     _fields_ = [("candidates", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+VALUE_MAX_LAYERS, VALUE_MAX_WIDTH = 4, 256
+VALUE_RELU, VALUE_TANH = 0, 1
+VALUE_REL_XY = 1
+
+
+class Value(C.Structure):
+    """mbd_value (include/mbd_hip.h): a small fully connected net over the env's state record, whose output at a rollout's final
+    state is added, times ``scale``, to the candidate's reward."""
+    _fields_ = [("W", C.POINTER(C.c_float) * VALUE_MAX_LAYERS), ("b", C.POINTER(C.c_float) * VALUE_MAX_LAYERS),
+                ("center", C.POINTER(C.c_float)), ("in_scale", C.POINTER(C.c_float)), ("n_in", C.c_int32),
+                ("n_layers", C.c_int32), ("width", C.c_int32 * VALUE_MAX_LAYERS), ("act", C.c_int32), ("flags", C.c_int32),
+                ("scale", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
 TICK_ROWS_NONFINITE, TICK_STATE_NONFINITE, TICK_COLD = 1, 2, 4
 
 
@@ -141,6 +155,7 @@ EXPORTS = [
     "mbd_plan_set_objective", "mbd_plan_peek_objective", "mbd_sweep_set_objective", "mbd_sweep_peek_objective",
     "mbd_plan_set_weighting", "mbd_plan_peek_weighting", "mbd_sweep_set_weighting", "mbd_sweep_peek_weighting",
     "mbd_plan_set_mpc_pick", "mbd_plan_peek_mpc_pick", "mbd_sweep_set_mpc_pick", "mbd_sweep_peek_mpc_pick",
+    "mbd_plan_set_value", "mbd_plan_peek_value", "mbd_plan_eval_value", "mbd_sweep_set_value",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
@@ -231,6 +246,10 @@ def load() -> C.CDLL:
     lib.mbd_plan_peek_mpc_pick.argtypes = [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_sweep_set_mpc_pick.argtypes = [_vp, C.POINTER(MpcPick)]
     lib.mbd_sweep_peek_mpc_pick.argtypes = [_vp, _i, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
+    lib.mbd_plan_set_value.argtypes = [_vp, C.POINTER(Value)]
+    lib.mbd_plan_peek_value.argtypes = [_vp, _vp]
+    lib.mbd_plan_eval_value.argtypes = [_vp, _vp, _i, _vp]
+    lib.mbd_sweep_set_value.argtypes = [_vp, C.POINTER(Value)]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
     lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
     lib.mbd_plan_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(MpcTickInfo)]
@@ -276,7 +295,8 @@ def load() -> C.CDLL:
 
 LEVERS = ("MBD_NO_DPP", "MBD_NO_NFR_CONST", "MBD_NO_REWARD_CONST", "MBD_NO_PLANAR_FLAGS", "MBD_NO_FAST_SLIDES",
           "MBD_NO_FUSED_NOISE", "MBD_NO_LAZY", "MBD_NO_PREFETCH", "MBD_NO_AUX", "MBD_WMEAN_SPLIT", "MBD_NO_FUSED_SCORE",
-          "MBD_PK2", "MBD_WPB", "MBD_LDS_RESERVE", "MBD_NO_HELPERS", "MBD_ENS_SPLIT", "MBD_NO_UNIT_CONST")
+          "MBD_PK2", "MBD_WPB", "MBD_LDS_RESERVE", "MBD_NO_HELPERS", "MBD_ENS_SPLIT", "MBD_NO_UNIT_CONST",
+          "MBD_VALUE_TILE")
 
 
 def debug_set(name: str, value: int) -> None:
@@ -401,6 +421,31 @@ def debug_objective_host(rewss, rews, cand, w=None, q=None, effort: float = 0.0,
                                        opt(w), float(wsum), np_ptr(q), float(effort), float(rate), opt(prev), np_ptr(out), np_ptr(ret),
                                        np_ptr(cost)))
     return out, ret, cost
+
+
+def debug_check_value(rec: "Value", state_size: int, rigid_body: bool = True) -> int:
+    """include/mbd_hip_debug.h: the refusals a value record alone decides, for an env of that state_size and kind — no device
+    needed.  Returns the code (the message: ``load().mbd_last_error()``)."""
+    lib = load()
+    lib.mbd_debug_check_value.argtypes = [C.POINTER(Value), _i, _i]
+    return lib.mbd_debug_check_value(C.byref(rec), int(state_size), int(bool(rigid_body)))
+
+
+def debug_value_host(rec: "Value", states, rews=None, rigid_body: bool = True):
+    """include/mbd_hip_debug.h: value_kernel's arithmetic run on the host (no device).  ``states`` [B, n_in], ``rews`` [B] or None.
+    Returns V [B], or (V, rews + scale * V) when ``rews`` is given."""
+    lib = load()
+    lib.mbd_debug_value_host.argtypes = [C.POINTER(Value), _i, _vp, _vp, _i, _vp, _vp]
+    states = np.ascontiguousarray(states, np.float32)
+    B = states.shape[0]
+    v = np.full(B, np.nan, np.float32)
+    if rews is None:
+        check(lib.mbd_debug_value_host(C.byref(rec), int(bool(rigid_body)), np_ptr(states), None, B, np_ptr(v), None))
+        return v
+    rews = np.ascontiguousarray(rews, np.float32)
+    out = np.full(B, np.nan, np.float32)
+    check(lib.mbd_debug_value_host(C.byref(rec), int(bool(rigid_body)), np_ptr(states), np_ptr(rews), B, np_ptr(v), np_ptr(out)))
+    return v, out
 
 
 def weighting_record(reject_nonfinite=True, ess_frac: float = 0.0, temp_min=None, temp_max=None, iters: int = 12) -> "Weighting":

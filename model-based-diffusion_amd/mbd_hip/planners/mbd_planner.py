@@ -214,6 +214,15 @@ class Sweep:
     def clear_objective(self):
         _capi.check(self.lib.mbd_sweep_set_objective(self.h, None))
 
+    def set_value(self, net, scale: float = None):
+        """One value record for all plans of the sweep (``Plan.set_value``; one net): plan k of ``run``, episode k of ``run_mpc`` and
+        of a session is then the single plan's with the same record, bit for bit.  None clears."""
+        if net is None:
+            _capi.check(self.lib.mbd_sweep_set_value(self.h, None))
+            return
+        rec = net.record(scale)
+        _capi.check(self.lib.mbd_sweep_set_value(self.h, C.byref(rec)))  # (the set call has copied the net)
+
     def set_weighting(self, reject_nonfinite=True, ess_frac: float = 0.0, temp_min=None, temp_max=None, iters: int = 12):
         """One weighting record for all plans of the sweep (``Plan.set_weighting``), each at its own temperature."""
         rec = _capi.weighting_record(reject_nonfinite, ess_frac, temp_min, temp_max, iters)
@@ -752,6 +761,33 @@ class Plan:
 
     def clear_objective(self):
         _capi.check(self.lib.mbd_plan_set_objective(self.h, None))
+
+    def set_value(self, net, scale: float = None):
+        """Score every candidate's end state with a terminal value net (include/mbd_hip.h mbd_value): ``net`` is a
+        ``planners.value.ValueNet`` over the env's state record, and a candidate's reward becomes its reward without the record
+        plus ``scale`` * V(final state) (``scale`` None: the net's own; ``value.terminal_scale(weight, Hsample)`` weighs V like
+        ``weight`` further rows).  Every call that samples reads it; ``eval``, the final reward and an episode's reward log keep the
+        env's own rewards.  None clears."""
+        if net is None:
+            _capi.check(self.lib.mbd_plan_set_value(self.h, None))
+            return
+        rec = net.record(scale)
+        _capi.check(self.lib.mbd_plan_set_value(self.h, C.byref(rec)))  # (the set call has copied the net)
+
+    def peek_value(self):
+        """The last step's V [shard_count] (a plan with a value record)."""
+        v = np.zeros(self.cfg.shard_count, np.float32)
+        _capi.check(self.lib.mbd_plan_peek_value(self.h, _capi.np_ptr(v)))
+        return v
+
+    def eval_value(self, states):
+        """V [B] of ``states`` [B, state_size], by the kernel the steps run (a check of an imported net)."""
+        states = np.ascontiguousarray(states, np.float32)
+        if states.ndim != 2 or states.shape[1] != self.env._state_size:
+            raise ValueError(f"states {states.shape}: expected [B, {self.env._state_size}]")
+        v = np.full(states.shape[0], np.nan, np.float32)
+        _capi.check(self.lib.mbd_plan_eval_value(self.h, _capi.np_ptr(states), states.shape[0], _capi.np_ptr(v)))
+        return v
 
     def set_weighting(self, reject_nonfinite=True, ess_frac: float = 0.0, temp_min=None, temp_max=None, iters: int = 12):
         """Weigh the candidates robustly (include/mbd_hip.h mbd_weighting): with ``reject_nonfinite`` a candidate whose reward is

@@ -64,6 +64,14 @@ episode's rewards stay the env's own.
 
     python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --discount 0.98 --rate_cost 0.1
 
+A plan scores its Hsample rows and nothing beyond them.  A value record (include/mbd_hip.h mbd_value; DESIGN.md section 1 "N16
+value") adds what the state a candidate ends in is worth: ``--value FILE.npz`` loads a terminal value net over the state record
+(``planners.value.ValueNet.save``; ``python -m mbd_hip.scripts.fit_value`` fits one to logged episodes) and ``--value_scale X`` lets
+its V weigh like X further reward rows (the record's scale is X / Hsample).  With ``--value`` the report gains ``value`` and
+``value_scale``; the episode's rewards stay the env's own.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --Hsample 25 --value value.npz --value_scale 0.25
+
 Every step weighs its candidates by a softmax of their standardised rewards at the env's ``temp_sample``, and one candidate whose
 reward is NaN or infinite makes every weight NaN.  A weighting record (include/mbd_hip.h mbd_weighting; DESIGN.md section 1 "N14
 weighting") changes both: ``--reject_nonfinite`` leaves such candidates out of the step, and ``--ess_frac F --temp_min A --temp_max
@@ -176,6 +184,22 @@ class MpcArgs(Args):
     temp_max: float = 10.0
     ess_iters: int = 12  # ... by this many bisection steps
     pick: str = ""  # "mean,prev,best" or any non-empty subset: what a tick may hand on (mbd_mpc_pick); "": the mean, nothing evaluated
+    value: str = ""  # FILE.npz: a terminal value net (planners.value.ValueNet.save; scripts.fit_value) over the state record ...
+    value_scale: float = 1.0  # ... whose V at a candidate's final state weighs like this many further reward rows (scale = X / Hsample)
+
+
+def _has_value(args: MpcArgs) -> bool:
+    return bool(args.value)
+
+
+def _value_of(args: MpcArgs):
+    """``set_value``'s arguments: the net of ``--value`` and the record's scale."""
+    from .value import ValueNet, terminal_scale
+    return ValueNet.load(args.value), terminal_scale(args.value_scale, args.Hsample)
+
+
+def _value_settings(args: MpcArgs) -> dict:
+    return dict(value=args.value, value_scale=args.value_scale) if _has_value(args) else {}
 
 
 _PLANT_FIELDS = ("plant_mass", "plant_friction", "plant_gear", "act_noise_std", "kick_std", "kick_every", "disturb_seed")
@@ -548,6 +572,8 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
         plan.set_weighting(**_weighting_of(args))
     if _has_pick(args):
         plan.set_mpc_pick(**_pick_of(args))
+    if _has_value(args):
+        plan.set_value(*_value_of(args))
     return env, plan, state_init, rng_exp
 
 
@@ -668,6 +694,8 @@ def _setup_batch(arg_list, device: int):
         sweep.set_weighting(**_weighting_of(a0))
     if _has_pick(a0):  # (and one pick record)
         sweep.set_mpc_pick(**_pick_of(a0))
+    if _has_value(a0):  # (and one value net)
+        sweep.set_value(*_value_of(a0))
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -823,6 +851,7 @@ def _main(argv=None) -> dict:
         res.update(_weighting_settings(args), weighting_last_tick=_weighting_log(wlog))
     if "pick" in ep:
         res.update(_pick_settings(args), pick_log=_pick_log(ep["pick"]))
+    res.update(_value_settings(args))  # (without --value the line is what it always was)
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -859,6 +888,7 @@ def _main_online(args: MpcArgs) -> dict:
         res.update(_weighting_settings(args), weighting=_weighting_log(ep["weighting"]))
     if "pick" in ep:
         res.update(_pick_settings(args), pick_log=_pick_log(ep["pick"]))
+    res.update(_value_settings(args))  # (without --value the line is what it always was)
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -908,6 +938,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
             plan.set_weighting(**_weighting_of(a0))
         if _has_pick(a0):
             plan.set_mpc_pick(**_pick_of(a0))
+        if _has_value(a0):
+            plan.set_value(*_value_of(a0))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -939,6 +971,7 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
     res.update(_weighting_settings(a0))
     if "pick" in ep:
         res.update(_pick_settings(a0), pick_log=_pick_log(ep["pick"]))
+    res.update(_value_settings(a0))
     if _has_demo(a0):
         res.update(_demo_settings(a0), track_err_mean=float(ep["track_err"].mean()))
     if not a0.not_render:
