@@ -91,6 +91,19 @@ int mbd_debug_check_value(const mbd_value* rec, int state_size, int rigid_body);
  * [B] or NULL; v_out [B]: V; rews_out [B] or NULL: rews + (scale * V). */
 int mbd_debug_value_host(const mbd_value* rec, int rigid_body, const float* states, const float* rews, int B, float* v_out,
                          float* rews_out);
+/* The update step of a sweep on its own, on the DEVICE: what a lockstep step launches behind its rollout and its records' launches
+ * — under a weighting record the weigh kernel, then score + weighted mean over the P plans (MBD, mppi, cma-es: plus spread and sigma)
+ * or score, selection and mean of the best (cem) — with every plan's temperature, on uploaded arrays, for diffusion step i's schedule
+ * values and the env's rew_xref.  All arrays HOST.  cand [P][N][H Nu]: update_method 0 the step's normals z, a candidate being
+ * clip((z * sigma_i) + ybar, -1, 1) as the lazy plans form it, otherwise the candidates; ybar [P][H Nu]: Ybar_i, or the mean; rews
+ * [P][N]; lp [P][N]: exactly with enable_demo; sigma_in [P]: exactly for cma-es.  ybar_out [P][H Nu], weights_out [P][N],
+ * rew_mean_out [P], sigma_out [P] (cma-es), idx_out [P][min(N, 10)] (cem); any may be NULL.  What is read back is filled with quiet
+ * NaN (idx: -1) first.  Argument errors first (NULL sweep / cand / ybar / rews, lp or sigma_in missing or given where not taken, i
+ * outside [1, Ndiffuse - 1]), before any device access; then MBD_ERR_STATE while a session is open.  Launches no rollout; a
+ * weighting record's entry of the step is entry 0 of mbd_sweep_peek_weighting.  A run after it equals a fresh sweep's. */
+int mbd_debug_sweep_update(mbd_sweep* sweep, int i, const float* cand, const float* ybar, const float* rews, const float* lp,
+                           const float* sigma_in, float* ybar_out, float* weights_out, float* rew_mean_out, float* sigma_out,
+                           int32_t* idx_out);
 #ifdef __cplusplus
 }
 #endif

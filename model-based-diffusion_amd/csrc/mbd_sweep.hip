@@ -8,10 +8,15 @@ namespace {
 // outputs per thread of the sweeps' score + weighted mean launch (score_wmean_batch_kernel<V>): 2 — a workgroup owns 32 outputs,
 // 128 bytes of every candidate row, P x 27 workgroups for the humanoid.  Measured on sweep8 (profiles/r05_score_ab.txt; the
 // launch's algorithmic bytes are 28.0 MB): V = 1 15.5 us / 48.2 MB, V = 2 11.3 us / 28.2 MB, V = 4 22.0 us / 28.2 MB.
-// MBD_WMEAN_V = 1 / 2 / 4 forces it (A/B, tests; same bits whatever it is)
-int wmean_batch_v() {
+// MBD_WMEAN_V = 1 / 2 / 4 forces it (A/B, tests; same bits whatever it is) — where it fits: the launch asks for 4 N bytes of
+// dynamic LDS beside the kernel's own red[64][16 V + 1] and red_s[32] (the gfx950 code object's fixed group segment: 4480, 8576,
+// 16 768 bytes for V = 1, 2, 4; 128 fewer in the GIVEN form), and nothing raises the launch's 64 KiB limit.  V = 4 passes it
+// above N = 12 192 of the 12 288 candidates a sweep accepts: there the launch takes 2 (57 728 bytes at most).
+int wmean_batch_v(int N) {
   const int v = lever("MBD_WMEAN_V");
-  return (v == 1 || v == 2 || v == 4) ? v : 2;
+  if (v != 1 && v != 2 && v != 4) return 2;
+  const size_t fixed = sizeof(float) * (size_t)(mbd::kWmG * (mbd::kWmE * v + 1) + 2 * (mbd::kScoreThreads / 64));
+  return fixed + sizeof(float) * (size_t)N <= 64 * 1024 ? v : 2;
 }
 // given: under a weighting record — weigh_kernel has written every plan's weights and mean reward, the launch loads the weights
 // where it would derive them (score_wmean_body's GIVEN form; the same grid, tiles and plan-to-XCD mapping)
@@ -248,47 +253,19 @@ static int sweep_results(mbd_sweep* w, float* mu_0ts_out, float* rew_means_out, 
 // spread and sigma; cem: score, selection, mean of the K best.  Same kernels, same order, same bits as mbd_plan_run.
 // sweep_pi_step is that lockstep step, shared by mbd_sweep_run and the path-integral episodes of mbd_sweep_run_mpc.
 namespace {
-struct PiStep {
-  int slot;              // slot of every plan's d_mu / d_rewmeans the step writes
-  const float* state0;   // [P][S] start states of the rollouts
-  const float* mu_in;    // the mean of plan 0 the step samples around; plan k's is mu_stride floats further
-  long long mu_stride;
-  NoiseSpec ns;          // the noise shape and basis the step samples under
-};
-int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
+// the update rule's kernels of a lockstep step, behind the value record's launch: the step's, and mbd_debug_sweep_update's on
+// uploaded rewards.  step: slot of every plan's d_mu / d_rewmeans; mu_in: the mean of plan 0 the candidates were sampled around
+int sweep_pi_update(mbd_sweep* w, int step, const float* mu_in, long long mu_stride) {
   mbd_env* e = w->env;
   const mbd_plan_config& c = w->cfg;
-  const int P = w->P, N = c.Nsample, H = c.Hsample, Nd = c.Ndiffuse, HNu = w->HNu, S = e->state_size();
+  const int P = w->P, N = c.Nsample, Nd = c.Ndiffuse, HNu = w->HNu;
   hipStream_t s = w->stream;
   const uint64_t per_plan = (uint64_t)N * HNu;
-  const unsigned nblocks = noise_blocks(c.prng_impl, per_plan, 4096);
   const dim3 b64(64);
   PiBatch pb;
   pb.rews = N; pb.weights = N; pb.mean = Nd - 1; pb.cand = (long long)per_plan; pb.spread = HNu; pb.sigma = 1; pb.idx = 16;
   pb.out = (long long)(Nd - 1) * HNu; pb.temps = w->d_temps;
-  const int step = st.slot;
-  const float* mu_in = st.mu_in;
-  const long long mu_stride = st.mu_stride;
   float* mu_out = w->d_mu + (size_t)step * HNu;
-  const NoiseSpec& ns = st.ns;
-  if (ns.W) {  // under a noise basis: the knot kernel into the scratch z, then sample_batch_kernel's two roundings
-    hipLaunchKernelGGL(knot_noise_batch_kernel, dim3(knot_blocks(N, w->Nu, 1024), (unsigned)P), dim3(kKnotThreads), 0, s, sk,
-                       c.prng_impl, N, H, w->Nu, ns.knots, ns.W, ns.g, w->d_knot_z.get());
-    hipLaunchKernelGGL(shift_batch_kernel, dim3(noise_blocks(MBD_PRNG_PARTITIONABLE, per_plan, 4096), (unsigned)P), dim3(256), 0, s,
-                       (const float*)w->d_knot_z, N, HNu, (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s.get());
-  } else {
-    hipLaunchKernelGGL(sample_batch_kernel, dim3(nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
-                       (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s, ns.g);
-  }
-  HIP_TRY(hipGetLastError());
-  MBD_TRY(w->timing.begin(s));
-  const int sw[3] = {N, S, 0};
-  MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, w->val.final(), s, nullptr, sw));
-  MBD_TRY(w->timing.end(s));
-  // the objective record: one launch over the P N rows (blockIdx.y = plan) on the materialised candidates
-  if (w->obj.has) MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_Y0s, false, 0.0f, nullptr, 0, s));
-  // the value record: one launch over the P N rows behind it (one net: the plans' rows are one batch)
-  MBD_TRY(w->val.launch_step(w->d_rews, P * N, s));
   pb.mu = mu_stride;
   if (c.update_method == 3) {  // cem_update (path_integral.py:48-52)
     const int K = N < 10 ? N : 10;
@@ -308,7 +285,7 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
     sb.ybar_in = mu_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
     if (w->wt.has)
       MBD_TRY(launch_weigh_batch(w->wt, P, N, Nd, w->d_rews, c.temp_sample, w->d_temps, w->d_weights, w->d_rewmeans + step, s));
-    launch_score_wmean_batch(wmean_batch_v(), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
+    launch_score_wmean_batch(wmean_batch_v(N), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
                              c.temp_sample, 0, w->d_weights.get(), w->d_rewmeans + step, (const float*)w->d_Y0s, HNu, mu_in, 1.0f, 1.0f,
                              1.0f, 0, mu_out, 0, 0.0f, (float*)nullptr, sb);
     if (c.update_method == 2) {
@@ -319,6 +296,45 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
   }
   HIP_TRY(hipGetLastError());
   return MBD_OK;
+}
+
+struct PiStep {
+  int slot;              // slot of every plan's d_mu / d_rewmeans the step writes
+  const float* state0;   // [P][S] start states of the rollouts
+  const float* mu_in;    // the mean of plan 0 the step samples around; plan k's is mu_stride floats further
+  long long mu_stride;
+  NoiseSpec ns;          // the noise shape and basis the step samples under
+};
+int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
+  mbd_env* e = w->env;
+  const mbd_plan_config& c = w->cfg;
+  const int P = w->P, N = c.Nsample, H = c.Hsample, HNu = w->HNu, S = e->state_size();
+  hipStream_t s = w->stream;
+  const uint64_t per_plan = (uint64_t)N * HNu;
+  const unsigned nblocks = noise_blocks(c.prng_impl, per_plan, 4096);
+  const int step = st.slot;
+  const float* mu_in = st.mu_in;
+  const long long mu_stride = st.mu_stride;
+  const NoiseSpec& ns = st.ns;
+  if (ns.W) {  // under a noise basis: the knot kernel into the scratch z, then sample_batch_kernel's two roundings
+    hipLaunchKernelGGL(knot_noise_batch_kernel, dim3(knot_blocks(N, w->Nu, 1024), (unsigned)P), dim3(kKnotThreads), 0, s, sk,
+                       c.prng_impl, N, H, w->Nu, ns.knots, ns.W, ns.g, w->d_knot_z.get());
+    hipLaunchKernelGGL(shift_batch_kernel, dim3(noise_blocks(MBD_PRNG_PARTITIONABLE, per_plan, 4096), (unsigned)P), dim3(256), 0, s,
+                       (const float*)w->d_knot_z, N, HNu, (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s.get());
+  } else {
+    hipLaunchKernelGGL(sample_batch_kernel, dim3(nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
+                       (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s, ns.g);
+  }
+  HIP_TRY(hipGetLastError());
+  MBD_TRY(w->timing.begin(s));
+  const int sw[3] = {N, S, 0};
+  MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, w->val.final(), s, nullptr, sw));
+  MBD_TRY(w->timing.end(s));
+  // the objective record: one launch over the P N rows (blockIdx.y = plan) on the materialised candidates
+  if (w->obj.has) MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_Y0s, false, 0.0f, nullptr, 0, s));
+  // the value record: one launch over the P N rows behind it (one net: the plans' rows are one batch)
+  MBD_TRY(w->val.launch_step(w->d_rews, P * N, s));
+  return sweep_pi_update(w, step, mu_in, mu_stride);
 }
 }  // namespace
 
@@ -405,10 +421,30 @@ void sweep_split_keys(const mbd_sweep* w, std::vector<uint32_t>& rng, SweepKeys&
   }
 }
 
+// what a lockstep step launches behind the value record's launch — the weigh kernel under a weighting record, then the score +
+// weighted mean over the P plans —: the step's, and mbd_debug_sweep_update's on uploaded rewards.  i: diffusion step; slot: of
+// every plan's d_mu / d_rewmeans; eps: the step's normals [P][N][HNu]; ybar_in: Ybar_i of plan 0, plan k's ybar_in_stride further
+int sweep_update(mbd_sweep* w, int i, int slot, const float* eps, const float* ybar_in, long long ybar_in_stride, float rew_xref) {
+  const mbd_plan_config& c = w->cfg;
+  const int P = w->P, N = c.Nsample, Nd = c.Ndiffuse, HNu = w->HNu;
+  hipStream_t s = w->stream;
+  ScoreBatch sb;
+  sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)N * HNu;
+  sb.ybar_in = ybar_in_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
+  if (w->wt.has)
+    MBD_TRY(launch_weigh_batch(w->wt, P, N, Nd, w->d_rews, c.temp_sample, w->d_temps, w->d_weights, w->d_rewmeans + slot, s));
+  launch_score_wmean_batch(wmean_batch_v(N), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), c.enable_demo ? w->d_lp.get() : nullptr, N,
+                           rew_xref, c.temp_sample, 1, w->d_weights.get(), w->d_rewmeans + slot, eps, HNu, ybar_in,
+                           w->alphas[i], w->alphas_bar[i], w->alphas_bar[i - 1], c.literal_score,
+                           w->d_mu + (size_t)slot * HNu, 1, w->sigmas[i], (float*)nullptr, sb);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+
 int sweep_step(mbd_sweep* w, const SweepStep& st) {
   mbd_env* e = w->env;
   const mbd_plan_config& c = w->cfg;
-  const int P = w->P, N = c.Nsample, H = c.Hsample, Nd = c.Ndiffuse, HNu = w->HNu, S = e->state_size();
+  const int P = w->P, N = c.Nsample, H = c.Hsample, S = e->state_size();
   const int step = st.q, i = st.i;
   hipStream_t s = w->stream;
   const int cur = step % 3, nxt = (step + 1) % 3;
@@ -450,17 +486,7 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
     MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_eps[cur], true, w->sigmas[i], st.ybar_in, st.ybar_in_stride, s));
   // the value record: one launch over the P N rows behind it (one net: the plans' rows are one batch)
   MBD_TRY(w->val.launch_step(w->d_rews, P * N, s));
-  ScoreBatch sb;
-  sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = Nd - 1; sb.cand = (long long)N * HNu;
-  sb.ybar_in = st.ybar_in_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
-  if (w->wt.has)
-    MBD_TRY(launch_weigh_batch(w->wt, P, N, Nd, w->d_rews, c.temp_sample, w->d_temps, w->d_weights, w->d_rewmeans + st.slot, s));
-  launch_score_wmean_batch(wmean_batch_v(), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), c.enable_demo ? w->d_lp.get() : nullptr, N,
-                           st.rew_xref, c.temp_sample, 1, w->d_weights.get(), w->d_rewmeans + st.slot, w->d_eps[cur].get(), HNu, st.ybar_in,
-                           w->alphas[i], w->alphas_bar[i], w->alphas_bar[i - 1], c.literal_score,
-                           w->d_mu + (size_t)st.slot * HNu, 1, w->sigmas[i], (float*)nullptr, sb);
-  HIP_TRY(hipGetLastError());
-  return MBD_OK;
+  return sweep_update(w, i, st.slot, w->d_eps[cur].get(), st.ybar_in, st.ybar_in_stride, st.rew_xref);
 }
 }  // namespace
 
@@ -499,6 +525,58 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
   auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
   return sweep_results(w, mu_0ts_out, rew_means_out, rew_final_out);
+}
+
+// The update step of a sweep alone on uploaded arrays (include/mbd_hip_debug.h): sweep_update / sweep_pi_update — what a lockstep
+// step launches behind its value record's launch — with slot 0 of every plan, ring buffer 0 (MBD) or d_Y0s as the candidates and
+// d_final as the [P][HNu] buffer of the means.  No rollout, objective or value launch; d_zero is not written, and a run after it
+// generates its own normals, resets sigma and rewrites every slot, so it equals a fresh sweep's.
+extern "C" int mbd_debug_sweep_update(mbd_sweep* w, int i, const float* cand, const float* ybar, const float* rews, const float* lp,
+                                      const float* sigma_in, float* ybar_out, float* weights_out, float* rew_mean_out,
+                                      float* sigma_out, int32_t* idx_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "debug_sweep_update: sweep is NULL");
+  if (!cand) return fail(MBD_ERR_INVALID, "debug_sweep_update: cand is NULL");
+  if (!ybar) return fail(MBD_ERR_INVALID, "debug_sweep_update: ybar is NULL");
+  if (!rews) return fail(MBD_ERR_INVALID, "debug_sweep_update: rews is NULL");
+  const mbd_plan_config& c = w->cfg;
+  if (c.enable_demo && !lp) return fail(MBD_ERR_INVALID, "debug_sweep_update: lp is NULL on a sweep with enable_demo");
+  if (!c.enable_demo && lp) return fail(MBD_ERR_INVALID, "debug_sweep_update: lp given on a sweep without enable_demo");
+  if (c.update_method == 2 && !sigma_in) return fail(MBD_ERR_INVALID, "debug_sweep_update: sigma_in is NULL on a cma-es sweep");
+  if (c.update_method != 2 && sigma_in) return fail(MBD_ERR_INVALID, "debug_sweep_update: sigma_in given on a sweep that is not cma-es");
+  if (i < 1 || i > c.Ndiffuse - 1) return fail(MBD_ERR_INVALID, "debug_sweep_update: i=%d outside [1,%d]", i, c.Ndiffuse - 1);
+  NO_SWEEP_SESSION(w, "debug_sweep_update");
+  mbd_env* e = w->env;
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const int P = w->P, N = c.Nsample, Nd = c.Ndiffuse, HNu = w->HNu, K = N < 10 ? N : 10;
+  const bool pi = c.update_method != 0;
+  const size_t PN = (size_t)P * N, mu_pitch = sizeof(float) * (size_t)(Nd - 1) * HNu, row = sizeof(float) * HNu;
+  float* d_cand = pi ? w->d_Y0s.get() : w->d_eps[0].get();
+  HIP_TRY(hipMemcpy(d_cand, cand, sizeof(float) * PN * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(w->d_final, ybar, row * P, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(w->d_rews, rews, sizeof(float) * PN, hipMemcpyHostToDevice));
+  if (lp) HIP_TRY(hipMemcpy(w->d_lp, lp, sizeof(float) * PN, hipMemcpyHostToDevice));
+  if (sigma_in) HIP_TRY(hipMemcpy(w->d_sigma, sigma_in, sizeof(float) * P, hipMemcpyHostToDevice));
+  {  // a quiet NaN over what is read back: an output no kernel wrote is seen
+    const size_t PE = (size_t)P * HNu;
+    const std::vector<float> nan(PN > PE ? PN : PE, __builtin_nanf(""));
+    HIP_TRY(hipMemcpy(w->d_weights, nan.data(), sizeof(float) * PN, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy2D(w->d_mu, mu_pitch, nan.data(), row, row, P, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy2D(w->d_rewmeans, sizeof(float) * (Nd - 1), nan.data(), sizeof(float), sizeof(float), P, hipMemcpyHostToDevice));
+    if (c.update_method == 3) HIP_TRY(hipMemset(w->d_idx, 0xff, sizeof(int) * (size_t)P * 16));
+  }
+  w->wt.begin();  // (the step's entry of a weighting record's log is entry 0: mbd_sweep_peek_weighting)
+  if (pi) MBD_TRY(sweep_pi_update(w, 0, w->d_final, HNu));
+  else MBD_TRY(sweep_update(w, i, 0, d_cand, w->d_final, HNu, e->rew_xref));
+  HIP_TRY(hipStreamSynchronize(w->stream));
+  if (ybar_out) HIP_TRY(hipMemcpy2D(ybar_out, row, w->d_mu, mu_pitch, row, P, hipMemcpyDeviceToHost));
+  if (weights_out) HIP_TRY(hipMemcpy(weights_out, w->d_weights, sizeof(float) * PN, hipMemcpyDeviceToHost));
+  if (rew_mean_out)
+    HIP_TRY(hipMemcpy2D(rew_mean_out, sizeof(float), w->d_rewmeans, sizeof(float) * (Nd - 1), sizeof(float), P, hipMemcpyDeviceToHost));
+  if (sigma_out && c.update_method == 2) HIP_TRY(hipMemcpy(sigma_out, w->d_sigma, sizeof(float) * P, hipMemcpyDeviceToHost));
+  if (idx_out && c.update_method == 3)
+    HIP_TRY(hipMemcpy2D(idx_out, sizeof(int) * K, w->d_idx, sizeof(int) * 16, sizeof(int) * K, P, hipMemcpyDeviceToHost));
+  return MBD_OK;
 }
 
 // one noise shape for all plans of the sweep (include/mbd_hip.h mbd_noise_shape).  A sweep prepares nothing across run calls:

@@ -525,6 +525,33 @@ def debug_pick_best(rews) -> np.ndarray:
     return int(best[0]) if r.ndim == 1 else best
 
 
+SWEEP_UPDATE_ARGTYPES = [_vp, _i] + [_vp] * 10
+
+
+def debug_sweep_update(handle, i: int, cand, ybar, rews, lp=None, sigma_in=None, sigma: bool = False, idx: bool = False) -> dict:
+    """include/mbd_hip_debug.h: the update step of a sweep (``Sweep.h``) alone on uploaded arrays.  ``cand`` [P, N, H, Nu] (MBD
+    sweeps: the normals), ``ybar`` [P, H, Nu], ``rews`` [P, N], ``lp`` [P, N] (demo sweeps), ``sigma_in`` [P] (cma-es).  Returns
+    {'ybar' [P, H, Nu], 'weights' [P, N], 'rew_mean' [P]} and, asked for, 'sigma' [P] (cma-es) and 'idx' [P, min(N, 10)] (cem);
+    every output starts as NaN (idx: -2), so one the library did not write shows."""
+    lib = load()
+    lib.mbd_debug_sweep_update.argtypes = SWEEP_UPDATE_ARGTYPES
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    cand, ybar, rews, lp, sigma_in = f32(cand), f32(ybar), f32(rews), f32(lp), f32(sigma_in)
+    P, N = rews.shape
+    assert cand.size == P * N * (ybar.size // P) and ybar.shape[0] == P, (cand.shape, ybar.shape, rews.shape)
+    out = {"ybar": np.full(ybar.shape, np.nan, np.float32), "weights": np.full((P, N), np.nan, np.float32),
+           "rew_mean": np.full(P, np.nan, np.float32)}
+    if sigma:
+        out["sigma"] = np.full(P, np.nan, np.float32)
+    if idx:
+        out["idx"] = np.full((P, min(N, 10)), -2, np.int32)
+    opt = lambda a: None if a is None else np_ptr(a)
+    check(lib.mbd_debug_sweep_update(handle, int(i), np_ptr(cand), np_ptr(ybar), np_ptr(rews), opt(lp), opt(sigma_in),
+                                     np_ptr(out["ybar"]), np_ptr(out["weights"]), np_ptr(out["rew_mean"]), opt(out.get("sigma")),
+                                     opt(out.get("idx"))))
+    return out
+
+
 def debug_math_ops() -> list:
     """include/mbd_hip_debug.h: the names of the primitives mbd_debug_eval_math evaluates."""
     lib = load()
