@@ -825,6 +825,67 @@ int mbd_plan_peek_value(mbd_plan* plan, float* v_out);
  * check of an imported net).  Synchronous.  MBD_ERR_STATE without a record; MBD_ERR_INVALID: NULL arguments, B < 1. */
 int mbd_plan_eval_value(mbd_plan* plan, const float* states, int B, float* v_out);
 
+/* ---- adapt: the shape of the sampling noise learnt from the weighted spread of the candidates (the diagonal covariance of CEM,
+ * iCEM and CoVO-MPC; no counterpart in the reference, whose sigma_i is one scalar; DESIGN.md section 1 "N17 adapt") ---- */
+/* An adapt record is a setting of a plan beside the noise shape.  The plan keeps a device table a [Hsample][action_size], all ones
+ * at the start, and rewrites it behind every diffusion step from the weighted spread of that step's candidates; the samplers draw
+ * under G = a * g (one product per element), g being the caller's noise shape in force at that step, ones where none is.  The rule
+ * moves the SHAPE and leaves the scale alone: the sigma schedule, or a path-integral plan's carried sigma, still says how much noise
+ * a step has; the table says where it goes — it narrows the elements where selection narrowed the candidates more than on average
+ * and widens the others, within [a_min, a_max]. */
+typedef struct mbd_adapt {
+  float   rate;         /* 0 < rate <= 1: how far a step moves a towards its target                                    */
+  float   a_min, a_max; /* finite, 0 < a_min <= 1 <= a_max: the clamp of every entry                                   */
+  int32_t carry;        /* 0: a is all ones at the start of every tick; 1: at a tick boundary a is shifted exec_steps
+                           rows forward with the mean, the appended rows take 1                                        */
+  int32_t reserved[4];  /* must be 0 */
+} mbd_adapt;
+/* The update behind step i — f32 throughout, every operation rounded, the two fma explicit.  w [N]: the weights phase 2 of the step
+ * used (the score's, or the weigh kernel's under a weighting record); Ybar_i: the mean the step sampled around; sigma: what it
+ * sampled with (the schedule's sigma_i; the carried device scalar of an mppi plan); G: the table it sampled under.  For every
+ * element e = (h, a):
+ *   Y[n]   the candidate's value exactly as the weighted mean forms it: lazy plans clip((z[n][e] * sigma) + Ybar_i[e], -1, 1) from the
+ *          shaped normal z, materialised plans the stored value
+ *   d[n] = Y[n] - Ybar_i[e]
+ *   m1 = sum_n w[n] d[n],  m2 = sum_n w[n] (d[n] * d[n])   both in the weighted mean's order ("wsum64"): 64 groups, group k a
+ *          sequential chain acc = fma(w[n], x, acc) over n = k, k + 64, ... from +0 (x = d[n], or the rounded product d[n] * d[n]);
+ *          the 64 partials added in group order, starting from group 0's
+ *   var  = m2 - (m1 * m1);  var < 0 -> +0   (a NaN stays)
+ *   active[e] = G[e] > 0;   s[e] = sqrt(var) / (sigma * G[e])   for active e.  An element the caller's shape froze (G[e] == 0)
+ *          keeps its a[e] and takes no part below
+ *   S = sqrt((sum over active e, ascending, of s[e] * s[e], from +0) / float(n_active))
+ *   n_active == 0, or S not finite, or not S > 0: the step changes nothing and its log entry says skipped (all weight on one
+ *          candidate makes every var zero, for instance)
+ *   otherwise, for active e:  t = a[e] * (s[e] / S);   a'[e] = a[e] + (rate * (t - a[e])),  below a_min -> a_min, above a_max ->
+ *          a_max;   G'[e] = a'[e] * g[e]  (no shape in force: a'[e])
+ *   log: S as computed (NaN with no active element), skipped 0 / 1
+ * Consequences.  Before the first update, and with a_min == a_max == 1 throughout, a is all ones and G == g bit for bit (x * 1 is
+ * x): the plan has the bits of the plan without a record.  A frozen element stays frozen: G'[e] = a[e] * 0.
+ * When the table changes otherwise: a is all ones after the set call, at the start of mbd_plan_run, at the start of every cold tick
+ * of an episode or a session, and after mbd_plan_mpc_reset_mean; at the start of every other tick it follows `carry` (one small
+ * launch, which also forms G under the shape in force in that tick: a shape set MBD_NOISE_WARM_TICKS enters G from tick 1 on;
+ * behind an episode's last tick and at mbd_plan_mpc_close G is formed under the shape in force outside warm ticks again).
+ * Between phase calls (mbd_plan_sample_rollout / mbd_plan_score_update, mbd_plan_reverse_once) the table persists.
+ * A step's normals now depend on the previous step's result, so a plan with a record makes them in front of its rollout — the
+ * path plans with shares_device take — and prepares nothing ahead: mbd_plan_prefetch_noise is a no-op for it.  The update is two
+ * launches behind the step's update kernel on the step's stream; the tick's launch stands in front of the tick's first step.
+ * Without a record nothing is launched and nothing changes.
+ * Scope: MBD and mppi plans (update_method 0 and 1), rigid-body envs and car2d, lazy and materialised candidates, with or without
+ * noise-shape, noise-basis, objective, weighting, value, ensemble, plant, delay, sigma and pick records; mbd_plan_run, the unsharded
+ * phase calls, mbd_plan_run_mpc and sessions.  Sweeps have no such call.
+ * The set call is synchronous (it waits for the device), discards normals prepared ahead as mbd_plan_set_noise_shape does, and is to
+ * be called between diffusion steps; rec == NULL clears.  Refused before any device access, the message naming the field —
+ * MBD_ERR_INVALID: a NULL handle, rate outside (0, 1] or non-finite, a_min / a_max non-finite or not 0 < a_min <= 1 <= a_max, carry
+ * outside {0, 1}, non-zero reserved; MBD_ERR_UNSUPPORTED: update_method 2 or 3 (cma-es and cem adapt their own sigma), a plan
+ * created with enable_demo; MBD_ERR_STATE: a sharded plan, a session open on the handle. */
+int mbd_plan_set_adapt(mbd_plan* plan, const mbd_adapt* rec);
+/* The table and the log (HOST; any of the outputs may be NULL; synchronises the device): a_out [Hsample][action_size] the current
+ * table; ratio_out / skipped_out: S and the skipped flag of the steps since the last mbd_plan_run, mbd_plan_run_mpc or
+ * mbd_plan_mpc_open began (the phase calls append), in the order the steps ran — the most recent min(count, capacity, 65536) of
+ * them, oldest first.  The log lives on the device and the update's second kernel writes it.  *count_out: the steps there were.
+ * MBD_ERR_STATE without a record; MBD_ERR_INVALID: a NULL handle, capacity < 0. */
+int mbd_plan_peek_adapt(mbd_plan* plan, float* a_out, float* ratio_out, int32_t* skipped_out, int capacity, int* count_out);
+
 /* ---- planning ahead of the plant: an episode whose plans take D ticks to arrive (the real-time iteration scheme; no
  * counterpart in the reference; DESIGN.md section 1 "N9 delay") ---- */
 /* The episode of mbd_plan_run_mpc plans from s_t and executes that plan's first rows from the same s_t: planning takes no time.

@@ -104,6 +104,23 @@ int mbd_debug_value_host(const mbd_value* rec, int rigid_body, const float* stat
 int mbd_debug_sweep_update(mbd_sweep* sweep, int i, const float* cand, const float* ybar, const float* rews, const float* lp,
                            const float* sigma_in, float* ybar_out, float* weights_out, float* rew_mean_out, float* sigma_out,
                            int32_t* idx_out);
+/* The refusals an adapt record alone decides (include/mbd_hip.h mbd_adapt) for a plan of that update_method and enable_demo: the
+ * function the set call runs on its record, host arithmetic, no device. */
+int mbd_debug_check_adapt(const mbd_adapt* rec, int update_method, int enable_demo);
+/* An adapt record's update on the HOST: the per-element functions the two kernels call (one text for host and device) looped on the
+ * CPU, the chains over the 64 groups and every sum in the kernels' order; no device touched.  HOST w [N] the weights; cand [N][HNu]
+ * — values, or with lazy != 0 shaped normals formed as clip((z * sigma) + ybar[e], -1, 1) —; ybar [HNu] Ybar_i; a [HNu]; g [HNu] or
+ * NULL: no shape; G = a * g is formed first.  a_out, G_out [HNu], S_out, skipped_out: one value each; any may be NULL.  rate, a_min
+ * and a_max are checked as the set call checks them (MBD_ERR_INVALID naming the field); N * HNu <= 2^26. */
+int mbd_debug_adapt_host(const float* w, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy, const float* a,
+                         const float* g, float rate, float a_min, float a_max, float* a_out, float* G_out, float* S_out,
+                         int32_t* skipped_out);
+/* The same on the DEVICE, by the launches a step makes: the table kernel forms G = a * g from the uploaded arrays, then
+ * adapt_spread_kernel and adapt_finish_kernel.  sigma_on_device != 0: the kernels read sigma from a device scalar, as an mppi plan's
+ * do.  What is read back is filled with NaN (skipped: -1) first.  Argument errors first, then MBD_ERR_NO_DEVICE. */
+int mbd_debug_adapt_step(const float* w, const float* cand, int N, int HNu, const float* ybar, float sigma, int sigma_on_device,
+                         int lazy, const float* a, const float* g, float rate, float a_min, float a_max, float* a_out, float* G_out,
+                         float* S_out, int32_t* skipped_out);
 #ifdef __cplusplus
 }
 #endif

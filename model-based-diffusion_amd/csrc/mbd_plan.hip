@@ -5,6 +5,7 @@
 #define MBD_WEIGH_KERNEL 1  // this unit launches weigh_kernel (mbd_step_kernels.h)
 #define MBD_PICK_KERNEL 1   // ... and, for plans and sweeps alike, the pick record's kernels
 #define MBD_VALUE_KERNEL 1  // ... and the value record's
+#define MBD_ADAPT_KERNEL 1  // ... and the adapt record's (plans only)
 #include "mbd_internal.h"
 #include "../../include/mbd_hip_debug.h"
 
@@ -124,6 +125,22 @@ struct MpcSession {
   std::chrono::steady_clock::time_point t_submit{};
 };
 
+// The adapt record of a plan (include/mbd_hip.h mbd_adapt) as the handle keeps it: the rule, the table a and G = a * g [HNu] on the
+// device — G is what the samplers take as their shape while the record is in force (noise_spec) —, the scratch the update's two
+// kernels hand var and s through, and the device log, a ring of kAdaptLogCap entries (entry of step j at j % cap; count: steps
+// since the log began).  g_cur: the caller's shape G was last formed under (the plan's d_shape or nullptr), which the update's second
+// kernel forms G' under again.  All zero: no record (a zeroed stand-in handle has none).
+constexpr int kAdaptLogCap = 65536;
+struct AdaptRec {
+  bool has = false;
+  AdaptRule rule{};
+  int carry = 0;
+  long long count = 0;
+  const float* g_cur = nullptr;
+  DevBuf<float> d_a, d_G, d_buf, d_log_S;
+  DevBuf<int> d_log_skipped;
+};
+
 struct mbd_plan {
   mbd_env* env = nullptr;
   hipStream_t last_stream = nullptr;  // stream of the plan's previous phase call (plan_enter orders a change of stream)
@@ -193,6 +210,8 @@ struct mbd_plan {
   PickRec pick;
   // the value record (mbd_plan_set_value) with its net, the shard's final states and the last step's V
   ValueRec val;
+  // the adapt record (mbd_plan_set_adapt) with its table, the shape the samplers draw under and the device log of its steps
+  AdaptRec adapt;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_plan_mpc_open); it uses the episodes' buffers above — d_mpc_state for the
   // state handed in, d_mpc_pred for the one predicted state, d_mpc_queue — so a handle runs episodes or a session, not both
@@ -344,6 +363,9 @@ static const float* shape_warm(const mbd_plan* p) { return p->has_shape ? p->d_s
 static NoiseSpec noise_spec(const mbd_plan* p, bool warm_tick) {
   NoiseSpec ns;
   ns.g = warm_tick ? shape_warm(p) : shape_always(p);
+  // under an adapt record the samplers draw under G = a * g: the record's table stands where the caller's shape stood, in every
+  // step — the launches that rewrite it are handed the caller's shape in force (adapt_table)
+  if (p->adapt.has) ns.g = p->adapt.d_G.get();
   if (p->has_basis && (warm_tick || p->basis_when == MBD_NOISE_ALWAYS)) {
     ns.W = p->d_basis.get();
     ns.knots = p->basis_knots;
@@ -352,6 +374,44 @@ static NoiseSpec noise_spec(const mbd_plan* p, bool warm_tick) {
 }
 static NoiseSpec noise_always(const mbd_plan* p) { return noise_spec(p, false); }
 static NoiseSpec noise_warm(const mbd_plan* p) { return noise_spec(p, true); }
+
+// ---- the adapt record's launches (include/mbd_hip.h mbd_adapt; set, peek and the debug entries: below) -----------------------
+// The table at the start of a run or a tick, or under a new shape: shift < 0: a = ones, otherwise a shifted `shift` elements forward
+// (0: as it is); G = a * g under the caller's shape g now in force, which the updates that follow keep forming G under.  ONE launch.
+static int adapt_table(mbd_plan* p, int shift, const float* g, hipStream_t s) {
+  AdaptRec& A = p->adapt;
+  if (!A.has) return MBD_OK;
+  A.g_cur = g;
+  hipLaunchKernelGGL(adapt_table_kernel, dim3(1), dim3(kAdaptThreads), 0, s, A.d_a.get(), A.d_G.get(), g, p->HNu, shift);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+// the two launches of an update on caller-given arrays (a step's: adapt_update; mbd_debug_adapt_step): var into d_buf, then S, a', G'
+// and the log entry.  The weights are staged in LDS while they fit the default 48 KB window, read from memory beyond
+static int adapt_launch(const float* d_w, const float* d_cand, int N, int HNu, const float* d_ybar, int lazy, float sigma,
+                        const float* d_sigma, float* d_buf, float* d_a, const float* d_g, float* d_G, const AdaptRule& R,
+                        float* d_log_S, int* d_log_skipped, hipStream_t s) {
+  const dim3 grid((HNu + kWmE - 1) / kWmE), block(kWmE * kWmG);
+  if ((size_t)N * sizeof(float) <= 48 * 1024)
+    hipLaunchKernelGGL(adapt_spread_kernel<true>, grid, block, sizeof(float) * (size_t)N, s, d_w, d_cand, N, HNu, d_ybar, lazy, sigma,
+                       d_sigma, d_buf);
+  else
+    hipLaunchKernelGGL(adapt_spread_kernel<false>, grid, block, 0, s, d_w, d_cand, N, HNu, d_ybar, lazy, sigma, d_sigma, d_buf);
+  hipLaunchKernelGGL(adapt_finish_kernel, dim3(1), dim3(kAdaptThreads), 0, s, d_buf, HNu, sigma, d_sigma, d_a, d_g, d_G, R, d_log_S,
+                     d_log_skipped);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+// behind the update kernel of step i, on the step's stream: the step's weights, its candidates (or normals) and the Ybar_i and
+// sigma it sampled with — an mppi plan's from the carried device scalar, which its sampler read
+static int adapt_update(mbd_plan* p, int i, const float* d_Ybar_i, const float* d_cand, hipStream_t s) {
+  AdaptRec& A = p->adapt;
+  if (!A.has) return MBD_OK;
+  const int slot = (int)(A.count++ % kAdaptLogCap);
+  return adapt_launch(p->d_weights, d_cand, p->cfg.Nsample, p->HNu, d_Ybar_i, p->lazy ? 1 : 0, p->sigmas[i],
+                      p->cfg.update_method > 0 ? p->d_sigma.get() : nullptr, A.d_buf, A.d_a, A.g_cur, A.d_G, A.rule,
+                      A.d_log_S.get() + slot, A.d_log_skipped.get() + slot, s);
+}
 
 // z [N][HNu] of a step into `out`: noise_kernel, or under a basis knot_noise_kernel
 static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], float* out, const NoiseSpec& ns) {
@@ -375,7 +435,8 @@ static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], flo
 // rollout.  Under a basis the job is knot_noise_kernel's and always goes to the second stream: prepare_noise_job)
 static int declare_next_key(mbd_plan* p, const uint32_t key_next[2], const NoiseSpec& ns) {
   const bool off = env_flag("MBD_NO_PREFETCH");
-  if (off || !p->lazy) return MBD_OK;
+  // (under an adapt record a step's normals depend on the previous step's result: nothing is declared, every step makes its own)
+  if (off || !p->lazy || p->adapt.has) return MBD_OK;
   p->ring.hint_key[0] = key_next[0];
   p->ring.hint_key[1] = key_next[1];
   p->ring.hint_ns = ns;
@@ -407,7 +468,8 @@ static int plan_enter(mbd_plan* p, hipStream_t s) {
 // action fetch and inside the weighted mean.  The step's normals: ring.cur afterwards.
 static int obtain_normals(mbd_plan* p, const uint32_t key_sample[2], const NoiseSpec& ns, hipStream_t s) {
   NoiseRing& ring = p->ring;
-  int cur = ring.find(key_sample, ns);
+  // (under an adapt record the table behind ns.g changes from step to step: a buffer's tag says nothing, nothing is reused)
+  int cur = p->adapt.has ? -1 : ring.find(key_sample, ns);
   if (cur >= 0) {  // prepared behind the previous rollout
     MBD_TRY(ring.join(cur, s));
   } else {  // not prepared: generate now, into the buffer behind the previous step's (stream order protects it)
@@ -682,6 +744,10 @@ static int plan_score_update(mbd_plan* p, int i, const float* d_Ybar_i, const fl
     }
   }
   HIP_TRY(hipGetLastError());
+  // The adapt record: TWO launches behind the update kernel rewrite the table the next step samples under, from the weights, the
+  // candidates (eps[cur] of a lazy plan: read here in front of the ring's mark, so the weighted mean's argument covers them) and the
+  // Ybar_i the caller has not yet moved on from
+  MBD_TRY(adapt_update(p, i, d_Ybar_i, d_cand, s));
   if (p->lazy) {
     p->peek_ybar = p->d_ybar_keep;
     MBD_TRY(p->ring.mark_wmean(s, p->aux != nullptr));
@@ -744,11 +810,15 @@ extern "C" int mbd_plan_set_noise_shape(mbd_plan* p, const mbd_noise_shape* rec)
   // change: the ring forgets them and the declared key, so the next step generates its own under the new setting.
   p->ring.forget();
   p->has_shape = false;
-  if (!rec) return MBD_OK;
-  HIP_TRY(p->d_shape.grow(p->HNu));
-  HIP_TRY(hipMemcpy(p->d_shape, rec->scale, sizeof(float) * p->HNu, hipMemcpyHostToDevice));
-  p->shape_when = rec->when;
-  p->has_shape = true;
+  if (rec) {
+    HIP_TRY(p->d_shape.grow(p->HNu));
+    HIP_TRY(hipMemcpy(p->d_shape, rec->scale, sizeof(float) * p->HNu, hipMemcpyHostToDevice));
+    p->shape_when = rec->when;
+    p->has_shape = true;
+  }
+  // an adapt record's G = a * g is formed again under the shape now in force outside warm ticks (a run and a tick form their own)
+  MBD_TRY(adapt_table(p, 0, shape_always(p), p->stream));
+  if (p->adapt.has) HIP_TRY(hipStreamSynchronize(p->stream));
   return MBD_OK;
 }
 
@@ -854,7 +924,7 @@ extern "C" int mbd_debug_knot_noise_host(const uint32_t key[2], int impl, int N,
 // it needs it and the step's stream carries no event (NoiseRing: the ring of three buffers).
 static int plan_keep_in_step(mbd_plan* p) {
   NoiseRing& ring = p->ring;
-  if (!p->lazy || !ring.progress || ring.seq == 0 || p->cfg.shares_device != 0) return MBD_OK;
+  if (!p->lazy || !ring.progress || ring.seq == 0 || p->cfg.shares_device != 0 || p->adapt.has) return MBD_OK;
   // (a plan with a noise basis prepares its normals on the second stream whatever the launch could take)
   if (!p->has_basis && rollout_takes_noise(plan_rollout_choice(p), p->cfg.prng_impl, p->cfg.Nsample, p->HNu)) return MBD_OK;
   // (a stream slower than the limit: the loop stops keeping step and the step orders the two streams with an event instead —
@@ -919,6 +989,8 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
     HIP_TRY(hipMemcpy(p->d_sigma, &one, sizeof(float), hipMemcpyHostToDevice));
   }
   HIP_TRY(hipMemsetAsync(cur, 0, sizeof(float) * HNu, s));
+  MBD_TRY(adapt_table(p, -1, shape_always(p), s));  // (an adapt record: a = ones, and its log begins)
+  p->adapt.count = 0;
   HIP_TRY(hipStreamSynchronize(s));
   p->wt.begin();
   auto t0 = std::chrono::steady_clock::now();
@@ -2062,6 +2134,174 @@ extern "C" int mbd_debug_pick_best(const float* rews, int P, int N, int32_t* bes
   return MBD_OK;
 }
 
+// ---- the adapt record (include/mbd_hip.h mbd_adapt) ---------------------------------------------------------------------------
+// the refusals the record alone decides against the handle's update_method and enable_demo, in the header's order, each naming the
+// field — host arithmetic, before any device access
+static int check_adapt(const mbd_adapt* rec, int update_method, int enable_demo) {
+  if (!std::isfinite(rec->rate) || !(rec->rate > 0.0f) || rec->rate > 1.0f)
+    return fail(MBD_ERR_INVALID, "adapt record: rate=%g: must lie in (0, 1]", (double)rec->rate);
+  if (!std::isfinite(rec->a_min) || !(rec->a_min > 0.0f) || rec->a_min > 1.0f)
+    return fail(MBD_ERR_INVALID, "adapt record: a_min=%g: must be finite with 0 < a_min <= 1", (double)rec->a_min);
+  if (!std::isfinite(rec->a_max) || rec->a_max < 1.0f)
+    return fail(MBD_ERR_INVALID, "adapt record: a_max=%g: must be finite and >= 1", (double)rec->a_max);
+  if (rec->carry != 0 && rec->carry != 1) return fail(MBD_ERR_INVALID, "adapt record: carry=%d: 0 or 1", rec->carry);
+  for (int r = 0; r < 4; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "adapt record: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (update_method == 2 || update_method == 3)
+    return fail(MBD_ERR_UNSUPPORTED, "adapt record: update_method=%d: cma-es (2) and cem (3) adapt their own sigma", update_method);
+  if (enable_demo) return fail(MBD_ERR_UNSUPPORTED, "adapt record: enable_demo=1: demo plans take no adapt record");
+  return MBD_OK;
+}
+extern "C" int mbd_debug_check_adapt(const mbd_adapt* rec, int update_method, int enable_demo) {
+  if (!rec) return fail(MBD_ERR_INVALID, "adapt record is NULL");
+  return check_adapt(rec, update_method, enable_demo);
+}
+
+extern "C" int mbd_plan_set_adapt(mbd_plan* p, const mbd_adapt* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (rec) MBD_TRY(check_adapt(rec, p->cfg.update_method, p->cfg.enable_demo));  // (before any device access)
+  if (rec && p->cfg.shard_count != p->cfg.Nsample)
+    return fail(MBD_ERR_STATE, "adapt record: shard_count=%d of Nsample=%d: sharded plans take no adapt record", p->cfg.shard_count,
+                p->cfg.Nsample);
+  NO_SESSION(p, "set_adapt");
+  AdaptRec& A = p->adapt;
+  if (!rec && !A.has) return MBD_OK;  // (nothing to clear: no device is touched)
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read G or write the log)
+  // normals prepared ahead were made under another table: as mbd_plan_set_noise_shape, nothing prepared survives
+  p->ring.forget();
+  A.has = false;
+  A.count = 0;
+  if (!rec) return MBD_OK;
+  HIP_TRY(A.d_a.grow(p->HNu));
+  HIP_TRY(A.d_G.grow(p->HNu));
+  HIP_TRY(A.d_buf.grow(p->HNu));
+  HIP_TRY(A.d_log_S.grow(kAdaptLogCap));
+  HIP_TRY(A.d_log_skipped.grow(kAdaptLogCap));
+  A.rule = AdaptRule{rec->rate, rec->a_min, rec->a_max};
+  A.carry = rec->carry;
+  A.has = true;
+  MBD_TRY(adapt_table(p, -1, shape_always(p), p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_peek_adapt(mbd_plan* p, float* a_out, float* ratio_out, int32_t* skipped_out, int capacity, int* count_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  const AdaptRec& A = p->adapt;
+  if (!A.has) return fail(MBD_ERR_STATE, "peek_adapt: the plan has no adapt record");
+  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_adapt: capacity=%d", capacity);
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (a_out) HIP_TRY(hipMemcpy(a_out, A.d_a, sizeof(float) * p->HNu, hipMemcpyDeviceToHost));
+  long long n = A.count < kAdaptLogCap ? A.count : kAdaptLogCap;
+  if (n > capacity) n = capacity;
+  // the most recent n entries, oldest first: the ring may wrap between two of them — two pieces at the most
+  const size_t first = (size_t)((A.count - n) % kAdaptLogCap);
+  const size_t n0 = (size_t)n < kAdaptLogCap - first ? (size_t)n : kAdaptLogCap - first, n1 = (size_t)n - n0;
+  if (ratio_out && n0) HIP_TRY(hipMemcpy(ratio_out, A.d_log_S.get() + first, sizeof(float) * n0, hipMemcpyDeviceToHost));
+  if (ratio_out && n1) HIP_TRY(hipMemcpy(ratio_out + n0, A.d_log_S.get(), sizeof(float) * n1, hipMemcpyDeviceToHost));
+  if (skipped_out && n0) HIP_TRY(hipMemcpy(skipped_out, A.d_log_skipped.get() + first, sizeof(int32_t) * n0, hipMemcpyDeviceToHost));
+  if (skipped_out && n1) HIP_TRY(hipMemcpy(skipped_out + n0, A.d_log_skipped.get(), sizeof(int32_t) * n1, hipMemcpyDeviceToHost));
+  if (count_out) *count_out = (int)(A.count < 0x7fffffffll ? A.count : 0x7fffffffll);
+  return MBD_OK;
+}
+
+// include/mbd_hip_debug.h: the update on the HOST — the per-element functions the kernels call (one text for host and device), the
+// chains and the sums in the kernels' order, no device touched
+static int check_adapt_step_args(const char* what, const float* w, const float* cand, int N, int HNu, const float* ybar, const float* a,
+                                 float rate, float a_min, float a_max) {
+  if (!w || !cand || !ybar || !a) return fail(MBD_ERR_INVALID, "%s: NULL argument", what);
+  if (N < 1 || HNu < 1 || (uint64_t)N * (uint64_t)HNu > (1ull << 26)) return fail(MBD_ERR_INVALID, "%s: N=%d HNu=%d", what, N, HNu);
+  mbd_adapt rec{};
+  rec.rate = rate; rec.a_min = a_min; rec.a_max = a_max;
+  return check_adapt(&rec, 0, 0);
+}
+extern "C" int mbd_debug_adapt_host(const float* w, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy,
+                                    const float* a, const float* g, float rate, float a_min, float a_max, float* a_out, float* G_out,
+                                    float* S_out, int32_t* skipped_out) {
+  MBD_TRY(check_adapt_step_args("adapt_host", w, cand, N, HNu, ybar, a, rate, a_min, a_max));
+  const AdaptRule R{rate, a_min, a_max};
+  std::vector<float> G((size_t)HNu), s((size_t)HNu, 0.0f), an(a, a + HNu);
+  for (int e = 0; e < HNu; ++e) G[e] = adapt_G(a[e], g, e);
+  float acc = 0.0f;
+  int n_active = 0;
+  for (int e = 0; e < HNu; ++e) {
+    float m1[kWmG], m2[kWmG];
+    for (int k = 0; k < kWmG; ++k) {
+      m1[k] = m2[k] = 0.0f;
+      for (int n = k; n < N; n += kWmG)
+        adapt_chain(w[n], adapt_value(cand[(size_t)n * HNu + e], lazy, sigma, ybar[e]), ybar[e], m1[k], m2[k]);
+    }
+    float t1 = m1[0], t2 = m2[0];
+    for (int k = 1; k < kWmG; ++k) {
+      t1 = t1 + m1[k];
+      t2 = t2 + m2[k];
+    }
+    if (!(G[e] > 0.0f)) continue;
+    s[e] = adapt_s(adapt_var(t1, t2), sigma, G[e]);
+    acc = acc + s[e] * s[e];
+    ++n_active;
+  }
+  const float S = adapt_ratio(acc, n_active);
+  const bool skip = adapt_skip(S, n_active);
+  if (!skip)
+    for (int e = 0; e < HNu; ++e)
+      if (G[e] > 0.0f) {
+        an[e] = adapt_next(a[e], s[e], S, R);
+        G[e] = adapt_G(an[e], g, e);
+      }
+  if (a_out) memcpy(a_out, an.data(), sizeof(float) * HNu);
+  if (G_out) memcpy(G_out, G.data(), sizeof(float) * HNu);
+  if (S_out) *S_out = S;
+  if (skipped_out) *skipped_out = skip ? 1 : 0;
+  return MBD_OK;
+}
+// ... and on the DEVICE: the table kernel forms G = a * g from the uploaded arrays, then the update's two launches
+extern "C" int mbd_debug_adapt_step(const float* w, const float* cand, int N, int HNu, const float* ybar, float sigma,
+                                    int sigma_on_device, int lazy, const float* a, const float* g, float rate, float a_min, float a_max,
+                                    float* a_out, float* G_out, float* S_out, int32_t* skipped_out) {
+  MBD_TRY(check_adapt_step_args("adapt_step", w, cand, N, HNu, ybar, a, rate, a_min, a_max));
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  const size_t n = (size_t)N * HNu;
+  DevBuf<float> d_w, d_cand, d_ybar, d_a, d_g, d_G, d_buf, d_sigma, d_S;
+  DevBuf<int> d_skip;
+  HIP_TRY(d_w.alloc(N));
+  HIP_TRY(d_cand.alloc(n));
+  HIP_TRY(d_ybar.alloc(HNu));
+  HIP_TRY(d_a.alloc(HNu));
+  HIP_TRY(d_G.alloc(HNu));
+  HIP_TRY(d_buf.alloc(HNu));
+  HIP_TRY(d_sigma.alloc(1));
+  HIP_TRY(d_S.alloc(1));
+  HIP_TRY(d_skip.alloc(1));
+  if (g) {
+    HIP_TRY(d_g.alloc(HNu));
+    HIP_TRY(hipMemcpy(d_g, g, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy(d_w, w, sizeof(float) * N, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_cand, cand, sizeof(float) * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_ybar, ybar, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_a, a, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_sigma, &sigma, sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_G, 0xff, sizeof(float) * HNu));  // (what is read back and left unwritten reads back as NaN, or -1)
+  HIP_TRY(hipMemset(d_buf, 0xff, sizeof(float) * HNu));
+  HIP_TRY(hipMemset(d_S, 0xff, sizeof(float)));
+  HIP_TRY(hipMemset(d_skip, 0xff, sizeof(int)));
+  const float* dg = g ? d_g.get() : nullptr;
+  hipLaunchKernelGGL(adapt_table_kernel, dim3(1), dim3(kAdaptThreads), 0, nullptr, d_a.get(), d_G.get(), dg, HNu, 0);
+  HIP_TRY(hipGetLastError());
+  // (sigma from the device scalar: the host value handed to the kernels is then a NaN they must not use)
+  MBD_TRY(adapt_launch(d_w, d_cand, N, HNu, d_ybar, lazy ? 1 : 0, sigma_on_device ? __builtin_nanf("") : sigma,
+                       sigma_on_device ? d_sigma.get() : nullptr, d_buf, d_a, dg, d_G, AdaptRule{rate, a_min, a_max}, d_S, d_skip, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  if (a_out) HIP_TRY(hipMemcpy(a_out, d_a, sizeof(float) * HNu, hipMemcpyDeviceToHost));
+  if (G_out) HIP_TRY(hipMemcpy(G_out, d_G, sizeof(float) * HNu, hipMemcpyDeviceToHost));
+  if (S_out) HIP_TRY(hipMemcpy(S_out, d_S, sizeof(float), hipMemcpyDeviceToHost));
+  if (skipped_out) HIP_TRY(hipMemcpy(skipped_out, d_skip, sizeof(int32_t), hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
 // ---- one tick's planning, shared by the batch episode (mbd_plan_run_mpc) and the session (mbd_plan_mpc_submit) ------------------
 // The tick's keys, host arithmetic: rng, k_t = split(rng) advances the episode's chain; r = k_t is where the tick's own chain
 // starts (mbd_plan_run's from it); after = split(split(rng')[1])[1] is the Y0s_rng of tick t+1's first step, whose normals are
@@ -2104,6 +2344,10 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
   // the noise shape and basis: a cold tick is mbd_plan_run's loop (MBD_NOISE_WARM_TICKS: without), every other tick samples under
   // them in either mode — the first normals of the next tick, prepared beside this tick's last rollout, included
   const NoiseSpec ns = tk.cold ? noise_always(p) : noise_warm(p);
+  // with an adapt record, ONE launch in front of the tick's first sampler: a = ones in a cold tick and without carry, otherwise a
+  // shifted E rows forward with the mean; G under the caller's shape in force in this tick.  Stream order is the whole argument: it
+  // stands behind the previous tick's last update and in front of this tick's first sampler, which reads G
+  MBD_TRY(adapt_table(p, tk.cold || !p->adapt.carry ? -1 : tk.E * p->Nu, tk.cold ? shape_always(p) : shape_warm(p), s));
   p->wt.begin();  // (a weighting record's log holds the last tick's steps)
   const float* cur = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros of a cold tick, shift_E(M_{t-1}) otherwise
   const float* last_in = cur;    // Ybar_i of the tick's last step
@@ -2225,6 +2469,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     ~ObjEpisode() { o.episode_end(); }
   } obj_episode{p->obj};
   MBD_TRY(p->pick.start(T));  // (a pick record's log: one entry per tick)
+  p->adapt.count = 0;         // (an adapt record's log: the episode's steps)
   if (pi) {  // sigma = sigma_cold and the log's first entry, by the kernel that carries sigma across the boundaries
     MBD_TRY(p->sigma_rec.start(T, 1));
     p->sigma_rec.launch(p->d_sigma, 1, 0, true, s);
@@ -2286,6 +2531,9 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
     s_t = s_next;
   }
   if (has_demo) MBD_TRY(p->demo.finish(T, 1, E, s));
+  // an adapt record's G leaves the episode formed under the shape in force OUTSIDE warm ticks again (the table itself stays): the
+  // phase calls that may follow sample under it, as they would under the caller's shape without a record
+  MBD_TRY(adapt_table(p, 0, shape_always(p), s));
   HIP_TRY(hipStreamSynchronize(s));
   const auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
@@ -2386,6 +2634,7 @@ extern "C" int mbd_plan_mpc_open(mbd_plan* p, const mbd_mpc_config* mc, const ui
   MBD_TRY(p->obj.episode_start(p->delay.has ? p->d_mpc_queue + (Q - p->Nu) : nullptr, Q, s));
   // (nothing fails from here on: a refused or failed open leaves the last episode's logs readable)
   if (p->delay.has) p->delay.pred_ticks = 0;  // (mbd_plan_peek_mpc_predicted does not serve sessions)
+  p->adapt.count = 0;                         // (an adapt record's log: the session's steps)
   ss.mc = *mc;
   ss.rng[0] = key[0]; ss.rng[1] = key[1];
   ss.t = 0; ss.qbuf = 0; ss.flags = 0;
@@ -2488,6 +2737,10 @@ extern "C" int mbd_plan_mpc_reset_mean(mbd_plan* p) {
   if (!p->session.open) return fail(MBD_ERR_STATE, "mpc_reset_mean: no session is open on this plan");
   if (p->session.in_flight) return fail(MBD_ERR_STATE, "mpc_reset_mean: a tick is in flight (mbd_plan_mpc_collect first)");
   p->session.cold = true;  // (the next submit zeroes Ybar; the queue stays)
+  if (p->adapt.has) {      // (an adapt record's table is all ones again: written now as well, so that mbd_plan_peek_adapt says so)
+    HIP_TRY(hipSetDevice(p->env->device));
+    MBD_TRY(adapt_table(p, -1, shape_always(p), p->stream));
+  }
   if (p->cfg.update_method != 0) {  // (and starts from sigma_cold: written now as well, so that mbd_plan_get_sigma says so)
     HIP_TRY(hipSetDevice(p->env->device));
     p->sigma_rec.launch(p->d_sigma, 1, 0, true, p->stream);
@@ -2502,6 +2755,10 @@ extern "C" int mbd_plan_mpc_close(mbd_plan* p) {
   if (!ss.open) return fail(MBD_ERR_STATE, "mpc_close: no session is open on this plan");
   HIP_TRY(hipSetDevice(p->env->device));
   if (ss.in_flight) HIP_TRY(hipStreamSynchronize(p->stream));  // (its last kernel writes the mailbox)
+  if (p->adapt.has) {  // (as behind mbd_plan_run_mpc: G under the shape in force outside warm ticks, for the phase calls)
+    MBD_TRY(adapt_table(p, 0, shape_always(p), p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+  }
   ss.in_flight = false;
   ss.open = false;
   p->obj.episode_end();

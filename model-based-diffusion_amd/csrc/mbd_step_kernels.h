@@ -1802,4 +1802,175 @@ static __global__ __launch_bounds__(kValueMaxWidth) void value_kernel(ValueArgs 
 }
 #endif  // MBD_VALUE_KERNEL
 
+// ---- the adapt record (mbd_plan_set_adapt, include/mbd_hip.h mbd_adapt): behind a step's update kernel, the weighted spread of the
+// step's candidates per element -> the table a and G = a * g the next step samples under.  Last in this header under its own guard,
+// for weigh_kernel's reason: only mbd_plan.hip emits the kernels, behind the value kernel ----
+// The arithmetic of one element is the functions below, host and device text: mbd_debug_adapt_host loops them on the CPU, where a
+// test without a device holds them to the checker.  f32, every operation rounded (the build's -ffp-contract=off; the fma is explicit).
+struct AdaptRule {
+  float rate, a_min, a_max;
+};
+// the candidate's value as the weighted mean forms it (wmean_kernel's val)
+MBD_HD float adapt_value(float x, int lazy, float sigma, float yb) { return lazy ? fclip(x * sigma + yb, -1.0f, 1.0f) : x; }
+// one candidate's term of the two chains of an element
+MBD_HD void adapt_chain(float w, float y, float yb, float& m1, float& m2) {
+  const float d = y - yb;
+  m1 = ffma(w, d, m1);
+  m2 = ffma(w, d * d, m2);
+}
+MBD_HD float adapt_var(float m1, float m2) {
+  const float v = m2 - m1 * m1;
+  return v < 0.0f ? 0.0f : v;  // (a NaN stays)
+}
+MBD_HD float adapt_s(float var, float sigma, float G) { return fsqrt(var) / (sigma * G); }
+MBD_HD float adapt_ratio(float sumsq, int n_active) { return fsqrt(sumsq / (float)n_active); }
+MBD_HD bool adapt_skip(float S, int n_active) { return n_active == 0 || !(S > 0.0f) || !(S < __builtin_inff()); }
+MBD_HD float adapt_next(float a, float s, float S, const AdaptRule& R) {
+  const float t = a * (s / S);
+  const float v = a + R.rate * (t - a);
+  return v < R.a_min ? R.a_min : (v > R.a_max ? R.a_max : v);
+}
+MBD_HD float adapt_G(float a, const float* __restrict__ g, int e) { return g ? a * g[e] : a; }
+
+#ifdef MBD_ADAPT_KERNEL
+// The spread of every element: var[e] of the contract.  The weighted mean's decomposition (wmean_kernel): a workgroup owns kWmE = 16
+// consecutive outputs, in the XCD-aware tile order (xcd_tile: the tile next door shares half of every 128-byte line, so one XCD's
+// workgroups take consecutive tiles), and splits the candidates into 64 groups; thread (g, j) runs the TWO chains of output j over
+// n = g, g + 64, ... — a wavefront reads four 64-byte row segments per load instruction, 32 rows in flight per round while there are
+// that many, then 16, then the tail —, and the 64 partials of each sum are added in group order.  The candidate tensor is read once.
+// The weights: STAGE = true stages all N in LDS once per workgroup, shared by the tile's 16 outputs — while they fit the default
+// 48 KB window (N <= 12288); beyond it (STAGE = false) every thread reads its weights from memory — the 16 threads of a group the
+// same word, so a wavefront's load touches four distinct weights, and all workgroups the same N floats, which the L2 holds —: same
+// values, same chains, same bits, and no plan size is refused.
+// Bounds: rows n < N only (each round's guard), column e <= HNu - 1 (clamped; a clamped thread stores nothing), wl[i] for i < N.
+// No cross-lane sum, no MFMA: the order of every sum is the contract's.  Plain vector loads and stores.
+template <bool STAGE>
+static __global__ __launch_bounds__(kWmE * kWmG) void adapt_spread_kernel(const float* __restrict__ weights,
+                                                                   const float* __restrict__ cand, int N, int HNu,
+                                                                   const float* __restrict__ Ybar_i, int lazy, float sigma,
+                                                                   const float* __restrict__ sigma_dev,
+                                                                   float* __restrict__ var_out) {
+  extern __shared__ __attribute__((aligned(16))) float wl[];
+  __shared__ float red[2][kWmG][kWmE + 1];
+  const int j = threadIdx.x & (kWmE - 1), g = threadIdx.x / kWmE;
+  const int e_raw = xcd_tile(blockIdx.x, gridDim.x, 0) * kWmE + j;
+  const int e = e_raw < HNu ? e_raw : HNu - 1;
+  const float* __restrict__ col = cand + e;
+  if (sigma_dev) sigma = *sigma_dev;  // (a path-integral plan's carried sigma: what its sampler read)
+  const float yb = Ybar_i[e];
+  if (STAGE) {
+    for (int i = threadIdx.x; i < N; i += kWmE * kWmG) wl[i] = weights[i];
+    __syncthreads();
+  }
+  const float* __restrict__ w = STAGE ? wl : weights;
+  float m1 = 0.0f, m2 = 0.0f;
+  int n = g;
+  for (; n + 31 * kWmG < N; n += 32 * kWmG) {
+    float y[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) y[k] = col[(size_t)(n + k * kWmG) * HNu];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < 32; ++k) adapt_chain(w[n + k * kWmG], adapt_value(y[k], lazy, sigma, yb), yb, m1, m2);
+  }
+  for (; n + 15 * kWmG < N; n += 16 * kWmG) {
+    float y[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) y[k] = col[(size_t)(n + k * kWmG) * HNu];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) adapt_chain(w[n + k * kWmG], adapt_value(y[k], lazy, sigma, yb), yb, m1, m2);
+  }
+  for (; n < N; n += kWmG) adapt_chain(w[n], adapt_value(col[(size_t)n * HNu], lazy, sigma, yb), yb, m1, m2);
+  red[0][g][j] = m1;
+  red[1][g][j] = m2;
+  __syncthreads();
+  if (g != 0 || e_raw >= HNu) return;
+  float t1 = red[0][0][j], t2 = red[1][0][j];
+#pragma unroll 8
+  for (int k = 1; k < kWmG; ++k) {
+    t1 = t1 + red[0][k][j];
+    t2 = t2 + red[1][k][j];
+  }
+  var_out[e] = adapt_var(t1, t2);
+}
+// ONE workgroup: s[e] of the active elements in parallel (into buf, which arrives holding var), S by thread 0 in ascending e, then
+// the new a and G of the active elements in parallel, and the log entry.  Thread t owns the elements e = t, t + 256, ... in both
+// parallel passes, so a[e] and G[e] are read and written by one thread only.  The sum of S crosses to thread 0 through LDS, a chunk
+// of kAdaptChunk squares at a time: its chain then waits for LDS reads, which the compiler batches, not for a memory round trip per
+// element (850 dependent adds behind L2 loads took 83 us at humanoidrun, the whole rollout takes 504).  A frozen element's slot holds
+// +0: the accumulator is +0, positive or NaN, so adding +0 leaves its bits — the sum is the contract's sum over the active elements
+// in ascending e.  n_active is an integer count: an LDS atomic, whose order does not matter.  The trip counts are uniform.
+constexpr int kAdaptThreads = 256, kAdaptChunk = 2048;
+static __global__ __launch_bounds__(kAdaptThreads) void adapt_finish_kernel(float* __restrict__ buf, int HNu, float sigma,
+                                                                     const float* __restrict__ sigma_dev, float* __restrict__ a,
+                                                                     const float* __restrict__ g, float* __restrict__ G,
+                                                                     AdaptRule R, float* __restrict__ log_S,
+                                                                     int* __restrict__ log_skipped) {
+  __shared__ float q[kAdaptChunk];
+  __shared__ float sh_S;
+  __shared__ int sh_skip, sh_n;
+  if (sigma_dev) sigma = *sigma_dev;
+  if (threadIdx.x == 0) sh_n = 0;
+  int mine = 0;
+  float acc = 0.0f;  // (thread 0's)
+  for (int base = 0; base < HNu; base += kAdaptChunk) {
+    const int cnt = HNu - base < kAdaptChunk ? HNu - base : kAdaptChunk;
+    for (int k = threadIdx.x; k < cnt; k += kAdaptThreads) {
+      const int e = base + k;
+      const float Ge = G[e];
+      const bool active = Ge > 0.0f;
+      const float s = active ? adapt_s(buf[e], sigma, Ge) : 0.0f;
+      buf[e] = s;
+      q[k] = s * s;
+      mine += active ? 1 : 0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll 16
+      for (int k = 0; k < cnt; ++k) acc = acc + q[k];
+    }
+    __syncthreads();
+  }
+  atomicAdd(&sh_n, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int n_active = sh_n;
+    const float S = adapt_ratio(acc, n_active);
+    const bool skip = adapt_skip(S, n_active);
+    sh_S = S;
+    sh_skip = skip ? 1 : 0;
+    *log_S = S;
+    *log_skipped = skip ? 1 : 0;
+  }
+  __syncthreads();
+  if (sh_skip) return;
+  const float S = sh_S;
+  for (int e = threadIdx.x; e < HNu; e += kAdaptThreads) {
+    if (!(G[e] > 0.0f)) continue;
+    const float an = adapt_next(a[e], buf[e], S, R);
+    a[e] = an;
+    G[e] = adapt_G(an, g, e);
+  }
+}
+// The table at the start of a run or a tick, and whenever the shape in force changes: shift < 0: a = ones; otherwise a[e] =
+// a[e + shift], ones past the end (shift = 0: a as it is); then G = a * g under the shape g now in force (nullptr: none).  ONE
+// workgroup; the shift is in place, so a block of 256 elements is read, then — behind a barrier — written: a later block reads
+// only elements no earlier block wrote (its reads start at or behind its own first element).  The trip count is uniform.
+static __global__ __launch_bounds__(kAdaptThreads) void adapt_table_kernel(float* __restrict__ a, float* __restrict__ G,
+                                                                    const float* __restrict__ g, int HNu, int shift) {
+  for (int base = 0; base < HNu; base += kAdaptThreads) {
+    const int e = base + threadIdx.x;
+    float v = 1.0f;
+    if (e < HNu && shift >= 0 && e + shift < HNu) v = a[e + shift];
+    __syncthreads();
+    if (e < HNu) {
+      a[e] = v;
+      G[e] = adapt_G(v, g, e);
+    }
+    __syncthreads();
+  }
+}
+#endif  // MBD_ADAPT_KERNEL
+
 }  // namespace mbd

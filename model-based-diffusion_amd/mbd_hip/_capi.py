@@ -113,6 +113,12 @@ class Weighting(C.Structure):
                 ("iters", C.c_int32), ("reserved", C.c_int32 * 6)]
 
 
+class Adapt(C.Structure):
+    """mbd_adapt (include/mbd_hip.h): how fast the table that shapes a plan's sampling noise follows the weighted spread of its
+    candidates, the clamp of its entries, and whether it is carried across tick boundaries."""
+    _fields_ = [("rate", C.c_float), ("a_min", C.c_float), ("a_max", C.c_float), ("carry", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
 PICK_MEAN, PICK_PREV, PICK_BEST = 1, 2, 4
 
 
@@ -156,6 +162,7 @@ EXPORTS = [
     "mbd_plan_set_weighting", "mbd_plan_peek_weighting", "mbd_sweep_set_weighting", "mbd_sweep_peek_weighting",
     "mbd_plan_set_mpc_pick", "mbd_plan_peek_mpc_pick", "mbd_sweep_set_mpc_pick", "mbd_sweep_peek_mpc_pick",
     "mbd_plan_set_value", "mbd_plan_peek_value", "mbd_plan_eval_value", "mbd_sweep_set_value",
+    "mbd_plan_set_adapt", "mbd_plan_peek_adapt",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
@@ -250,6 +257,8 @@ def load() -> C.CDLL:
     lib.mbd_plan_peek_value.argtypes = [_vp, _vp]
     lib.mbd_plan_eval_value.argtypes = [_vp, _vp, _i, _vp]
     lib.mbd_sweep_set_value.argtypes = [_vp, C.POINTER(Value)]
+    lib.mbd_plan_set_adapt.argtypes = [_vp, C.POINTER(Adapt)]
+    lib.mbd_plan_peek_adapt.argtypes = [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
     lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
     lib.mbd_plan_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(MpcTickInfo)]
@@ -480,6 +489,67 @@ def peek_weighting(fn, handle, k, capacity: int) -> dict:
     check(fn(*head, np_ptr(temp), np_ptr(ess), np_ptr(kept), int(capacity), C.byref(n)))
     m = min(n.value, capacity)
     return {"temp": temp[:m], "ess": ess[:m], "kept": kept[:m]}
+
+
+def adapt_record(rate: float, a_min: float, a_max: float, carry=True) -> "Adapt":
+    """The mbd_adapt of ``Plan.set_adapt``'s arguments."""
+    rec = Adapt()
+    rec.rate, rec.a_min, rec.a_max, rec.carry = float(rate), float(a_min), float(a_max), int(carry)
+    return rec
+
+
+def debug_check_adapt(rec: "Adapt", update_method: int = 0, enable_demo: bool = False) -> int:
+    """include/mbd_hip_debug.h: the refusals an adapt record alone decides for a plan of that update_method and enable_demo; the
+    return code (the message: ``mbd_last_error``)."""
+    lib = load()
+    lib.mbd_debug_check_adapt.argtypes = [C.POINTER(Adapt), _i, _i]
+    return lib.mbd_debug_check_adapt(None if rec is None else C.byref(rec), int(update_method), int(bool(enable_demo)))
+
+
+def _debug_adapt(device: bool, w, cand, ybar, sigma, lazy, a, g, rate, a_min, a_max, sigma_on_device=False):
+    lib = load()
+    w = np.ascontiguousarray(w, np.float32)
+    cand = np.ascontiguousarray(cand, np.float32).reshape(w.shape[0], -1)
+    N, HNu = cand.shape
+    ybar = np.ascontiguousarray(ybar, np.float32).reshape(HNu)
+    a = np.ascontiguousarray(a, np.float32).reshape(HNu)
+    g = None if g is None else np.ascontiguousarray(g, np.float32).reshape(HNu)
+    a_out, G_out = np.full(HNu, np.nan, np.float32), np.full(HNu, np.nan, np.float32)
+    S, skipped = np.full(1, np.nan, np.float32), np.full(1, -1, np.int32)
+    gp = None if g is None else np_ptr(g)
+    tail = (np_ptr(a), gp, float(rate), float(a_min), float(a_max), np_ptr(a_out), np_ptr(G_out), np_ptr(S), np_ptr(skipped))
+    if device:
+        lib.mbd_debug_adapt_step.argtypes = [_vp, _vp, _i, _i, _vp, _f, _i, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]
+        check(lib.mbd_debug_adapt_step(np_ptr(w), np_ptr(cand), N, HNu, np_ptr(ybar), float(sigma), int(bool(sigma_on_device)),
+                                       int(bool(lazy)), *tail))
+    else:
+        lib.mbd_debug_adapt_host.argtypes = [_vp, _vp, _i, _i, _vp, _f, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp]
+        check(lib.mbd_debug_adapt_host(np_ptr(w), np_ptr(cand), N, HNu, np_ptr(ybar), float(sigma), int(bool(lazy)), *tail))
+    return a_out, G_out, S[0], int(skipped[0])
+
+
+def debug_adapt_host(w, cand, ybar, sigma, lazy, a, g, rate, a_min, a_max):
+    """include/mbd_hip_debug.h: an adapt record's update on the host (no device).  ``w`` [N], ``cand`` [N, HNu] (values, or with
+    ``lazy`` shaped normals), ``ybar`` [HNu], ``a`` [HNu], ``g`` [HNu] or None.  Returns (a' [HNu], G' [HNu], S, skipped)."""
+    return _debug_adapt(False, w, cand, ybar, sigma, lazy, a, g, rate, a_min, a_max)
+
+
+def debug_adapt_step(w, cand, ybar, sigma, lazy, a, g, rate, a_min, a_max, sigma_on_device=False):
+    """The same by the launches a step makes, on the device; ``sigma_on_device``: the kernels read sigma from a device scalar."""
+    return _debug_adapt(True, w, cand, ybar, sigma, lazy, a, g, rate, a_min, a_max, sigma_on_device)
+
+
+def peek_adapt(fn, handle, HNu: int, capacity: int = None) -> dict:
+    """mbd_plan_peek_adapt: {'a' [HNu], 'ratio' [n], 'skipped' [n], 'count'} — every step logged, or the most recent ``capacity``."""
+    n = C.c_int(0)
+    if capacity is None:
+        check(fn(handle, None, None, None, 0, C.byref(n)))
+        capacity = min(n.value, 65536)
+    a = np.zeros(HNu, np.float32)
+    ratio, skipped = np.zeros(max(capacity, 1), np.float32), np.zeros(max(capacity, 1), np.int32)
+    check(fn(handle, np_ptr(a), np_ptr(ratio), np_ptr(skipped), int(capacity), C.byref(n)))
+    m = min(n.value, capacity)
+    return {"a": a, "ratio": ratio[:m], "skipped": skipped[:m], "count": n.value}
 
 
 def pick_record(mean=True, prev=True, best=True) -> "MpcPick":

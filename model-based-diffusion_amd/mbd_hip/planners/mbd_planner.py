@@ -806,6 +806,25 @@ class Plan:
         plan with a weighting record)."""
         return _capi.peek_weighting(self.lib.mbd_plan_peek_weighting, self.h, None, self.cfg.Ndiffuse - 1)
 
+    def set_adapt(self, rate: float, a_min: float, a_max: float, carry=True):
+        """Shape the sampling noise from the weighted spread of the candidates (include/mbd_hip.h mbd_adapt): the plan keeps a table
+        ``a`` [H, Nu], all ones at the start, samples under ``a`` times the noise shape in force, and moves ``a`` behind every
+        diffusion step by ``rate`` towards where the spread of the step's weighted candidates says the noise should go, every
+        entry within [``a_min``, ``a_max``].  ``carry``: a tick boundary shifts the table with the mean (False: every tick starts
+        from ones).  MBD and mppi plans, unsharded, without ``enable_demo``."""
+        rec = _capi.adapt_record(rate, a_min, a_max, carry)
+        _capi.check(self.lib.mbd_plan_set_adapt(self.h, C.byref(rec)))
+
+    def clear_adapt(self):
+        _capi.check(self.lib.mbd_plan_set_adapt(self.h, None))
+
+    def peek_adapt(self, capacity: int = None) -> dict:
+        """``a`` [H, Nu], the table as it stands, and ``ratio`` / ``skipped``: S and the skipped flag of every step since the last
+        ``run``, episode or session began — or the most recent ``capacity`` of them (a plan with an adapt record)."""
+        out = _capi.peek_adapt(self.lib.mbd_plan_peek_adapt, self.h, self.H * self.Nu, capacity)
+        out["a"] = out["a"].reshape(self.H, self.Nu)
+        return out
+
     def peek_objective(self):
         """The last step's ``ret`` [shard_count] ([M, N] under an ensemble record) and ``cost`` [shard_count] (a plan with an
         objective record)."""

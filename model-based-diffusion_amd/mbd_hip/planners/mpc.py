@@ -91,6 +91,17 @@ mean value of the picked plan and of the mean.  ``--online`` and ``--n_episodes`
 
     python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --pick mean,prev,best
 
+The noise every step samples with has one shape: flat, or what ``--noise_shape`` / ``--tail_rows`` fix in advance.  An adapt record
+(include/mbd_hip.h mbd_adapt; DESIGN.md section 1 "N17 adapt") lets the plan learn it: ``--adapt_rate R`` (0 < R <= 1) keeps a table
+per horizon row and actuator, all ones at the start, which every diffusion step moves by R towards where the weighted spread of its
+candidates says the noise should go — narrower where selection narrowed them more than on average, wider elsewhere —, every entry
+within [``--adapt_min``, ``--adapt_max``]; the steps sample under the table times the noise shape in force.  ``--adapt_carry``
+shifts the table across a tick boundary with the mean (otherwise every tick starts from ones).  MBD and mppi plans, single
+episodes; ``--online`` honours it.  The details gain ``adapt`` = dict(a, ratio, skipped, count): the table behind the episode and
+the log of its steps; the report ``adapt_table_min`` / ``adapt_table_max`` and ``adapt_steps_skipped``.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --adapt_rate 0.3 --adapt_carry
+
 A demo plan (``--enable_demo``) compares its 50 planned steps with the env's 50 demo rows; in an episode the demo has to move
 with the system.  ``--demo_clip env|FILE.npy`` (include/mbd_hip.h mbd_mpc_demo; DESIGN.md section 1 "N10 demo clock") sets the
 clip the episode follows — the env's own demo, or an array [n_track, L, 3] (car2d: [L, 2]) — and ``--demo_start c0`` the clip
@@ -186,6 +197,10 @@ class MpcArgs(Args):
     pick: str = ""  # "mean,prev,best" or any non-empty subset: what a tick may hand on (mbd_mpc_pick); "": the mean, nothing evaluated
     value: str = ""  # FILE.npz: a terminal value net (planners.value.ValueNet.save; scripts.fit_value) over the state record ...
     value_scale: float = 1.0  # ... whose V at a candidate's final state weighs like this many further reward rows (scale = X / Hsample)
+    adapt_rate: float = 0.0  # R > 0: an adapt record (mbd_adapt) — every step moves the noise table by R towards its target ...
+    adapt_min: float = 0.25  # ... every entry within [adapt_min, adapt_max];
+    adapt_max: float = 4.0
+    adapt_carry: bool = False  # the table is shifted across a tick boundary with the mean (default: every tick starts from ones)
 
 
 def _has_value(args: MpcArgs) -> bool:
@@ -388,6 +403,27 @@ def _weighting_settings(args: MpcArgs) -> dict:
                 ess_iters=args.ess_iters) if _has_weighting(args) else {}
 
 
+def _has_adapt(args: MpcArgs) -> bool:
+    """Whether the arguments ask for an adapt record at all (a rate)."""
+    return args.adapt_rate != 0.0
+
+
+def _adapt_of(args: MpcArgs) -> dict:
+    """``Plan.set_adapt``'s arguments."""
+    return dict(rate=args.adapt_rate, a_min=args.adapt_min, a_max=args.adapt_max, carry=bool(args.adapt_carry))
+
+
+def _adapt_settings(args: MpcArgs) -> dict:
+    return dict(adapt_rate=args.adapt_rate, adapt_min=args.adapt_min, adapt_max=args.adapt_max,
+                adapt_carry=bool(args.adapt_carry)) if _has_adapt(args) else {}
+
+
+def _adapt_log(log: dict) -> dict:
+    """A peeked table and log as the report's three numbers."""
+    return dict(adapt_table_min=float(log["a"].min()), adapt_table_max=float(log["a"].max()),
+                adapt_steps_skipped=int(np.sum(log["skipped"])))
+
+
 _PICK_NAMES = ("mean", "prev", "best")
 
 
@@ -574,6 +610,8 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
         plan.set_mpc_pick(**_pick_of(args))
     if _has_value(args):
         plan.set_value(*_value_of(args))
+    if _has_adapt(args):
+        plan.set_adapt(**_adapt_of(args))
     return env, plan, state_init, rng_exp
 
 
@@ -610,6 +648,7 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
             means.append(out["mean"])
             predicted.append(out["predicted"])
             secs.append(out["seconds"])
+        adapt = plan.peek_adapt() if _has_adapt(args) else None  # (the table behind the last tick, the log of the session's steps)
     ep = dict(actions=np.concatenate(actions), rewards=np.concatenate(rewards), states=np.stack(states), means=np.stack(means),
               seconds=float(np.sum(secs)), tick_seconds=np.asarray(secs, np.float64))
     if plan._has_delay:
@@ -617,6 +656,8 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
     if wlog:  # per tick: the temperature, ESS and kept count of the tick's last step
         ep["weighting"] = dict(temp=np.array([w[0] for w in wlog], np.float32), ess=np.array([w[1] for w in wlog], np.float32),
                                kept=np.array([w[2] for w in wlog], np.int32))
+    if adapt is not None:
+        ep["adapt"] = adapt
     if plog:
         ep["pick"] = dict(choice=np.array([x["choice"] for x in plog], np.int32), rets=np.stack([x["rets"] for x in plog]),
                           best=np.array([x["best"] for x in plog], np.int32))
@@ -650,6 +691,9 @@ def _check_batch(arg_list) -> None:
     if not 1 <= len(arg_list) <= MAX_EPISODES:
         raise ValueError(f"{len(arg_list)} episodes: a batch holds 1 to {MAX_EPISODES}")
     for k, a in enumerate(arg_list):
+        if _has_adapt(a):
+            raise ValueError(f"episode {k} carries adapt_rate={a.adapt_rate!r}: sweeps take no adapt record (their samplers take one "
+                             "shape for all plans); run the episodes one by one (run_mpc)")
         if _has_ensemble(a):
             raise ValueError(f"episode {k} carries ensemble flags ({', '.join(f for f in _ENS_FIELDS if getattr(a, f) != MpcArgs.__dataclass_fields__[f].default)}): "
                              "batches of lockstep episodes take no ensemble; run the episodes one by one (run_mpc)")
@@ -763,6 +807,8 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         ep = plan.run_mpc(key, args.n_ticks, args.warm_steps, args.exec_steps)
         if _has_weighting(args):  # (the device log holds the last tick's score steps: their temperature, ESS and kept count)
             ep["weighting_last_tick"] = plan.peek_weighting()
+        if _has_adapt(args):  # (the table behind the last tick and the log of the episode's steps)
+            ep["adapt"] = plan.peek_adapt()
     finally:
         plan.close()
     reward = float(ep["rewards"].mean())
@@ -774,7 +820,7 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         if _has_basis(args):
             shape = dict(shape, **_basis_settings(args))
         shape = dict(shape, **_delay_settings(args), **_demo_settings(args), **_sigma_settings(args), **_objective_settings(args),
-                     **_weighting_settings(args))
+                     **_weighting_settings(args), **_adapt_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -819,6 +865,7 @@ def _main(argv=None) -> dict:
         _, _, _, open_secs = plan.run(key)
         ep = plan.run_mpc(key, T, K, E)
         wlog = plan.peek_weighting() if _has_weighting(args) else None
+        alog = plan.peek_adapt() if _has_adapt(args) else None
         nominal = None
         if _has_plant(args):  # what the perturbation cost: the same episode without the record
             plan.clear_mpc_plant()
@@ -852,6 +899,8 @@ def _main(argv=None) -> dict:
     if "pick" in ep:
         res.update(_pick_settings(args), pick_log=_pick_log(ep["pick"]))
     res.update(_value_settings(args))  # (without --value the line is what it always was)
+    if alog is not None:
+        res.update(_adapt_settings(args), **_adapt_log(alog))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -889,6 +938,8 @@ def _main_online(args: MpcArgs) -> dict:
     if "pick" in ep:
         res.update(_pick_settings(args), pick_log=_pick_log(ep["pick"]))
     res.update(_value_settings(args))  # (without --value the line is what it always was)
+    if "adapt" in ep:
+        res.update(_adapt_settings(args), **_adapt_log(ep["adapt"]))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
