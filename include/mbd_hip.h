@@ -226,7 +226,12 @@ int mbd_builtin_model(const char* env_name, mbd_model_t* model_out);
 int mbd_env_create_car2d(int device, const float* xref, mbd_env** out);
 /* rigid-body envs: humanoidrun / humanoidtrack / hopper / halfcheetah — the caller passes the
  * compiled model. xref = [n_track][50][3] float32 demo body positions or NULL. rew_xref as
- * humanoidtrack.py:44. */
+ * humanoidtrack.py:44.
+ * Tracked links (n_track, track_link): slot k of every rollout's positions [B][H][n_track][3], of xref and of the demo
+ * log-density is link track_link[k].  Refused with MBD_ERR_INVALID before any device is looked for, the message naming the
+ * field: n_track outside [0, MBD_MAX_TRACK]; a track_link[k], k < n_track, outside [0, n_links); one link in two slots (a link
+ * is tracked once); MBD_FLAG_PLANAR together with n_track > 0 — the planar kernels return no positions: compile such a
+ * model planar=False (mbd_hip/mjcf.py) to track its links.  Entries of track_link at or past n_track are not read. */
 int mbd_env_create_model(const char* env_name, int device, const mbd_model_t* model,
                          const float* xref, float rew_xref, mbd_env** out);
 int mbd_env_destroy(mbd_env* env);
@@ -260,7 +265,8 @@ int mbd_env_xref(const mbd_env* env, float* xref_out, int capacity, int* count_o
  *   d_xpos      : [B][H][K][3] tracked link positions after every control step (car2d: [B][H][3] = q) — the
  *                 d_xpos output of mbd_env_rollout
  *   d_logpd_out : [B]
- * H must be 50 (the demos have 50 rows). asynchronous on `stream`. */
+ * H must be 50 (the demos have 50 rows). asynchronous on `stream`.  A candidate with a NaN position gets a NaN (jnp.clip
+ * keeps a NaN distance); an infinite one a saturated term. */
 int mbd_env_xref_logpd(const mbd_env* env, const float* d_xpos, int B, int H, float* d_logpd_out, void* stream);
 /* _get_obs (humanoidrun.py:43-44, hopper.py:49-55, car2d.py:86; brax ant / half_cheetah) of ONE state:
  * kinematics.inverse on the host (the planner never reads observations, mbd_planner.py:71 — API parity only).

@@ -1892,7 +1892,7 @@ __device__ __forceinline__ void rollout_body(RolloutParams P) {
     if constexpr (RK == MBD_REW_HUMANOIDTRACK) {  // (every lane evaluates it; the tracked links' lanes are read at the end)
       const float ex = o1.x - xr.x, ey = o1.y - xr.y, ez = o1.z - xr.z;
       float d = fsqrt(ex * ex + ey * ey + ez * ez);
-      d = fclip(d, 0.0f, 0.5f);
+      d = fclip_nan(d, 0.0f, 0.5f);
       const float sd = d / 0.5f;
       lp_acc = lp_acc + sd * sd;
     }

@@ -47,6 +47,9 @@ MBD_HD float fclip(float v, float lo, float hi) {
   return v < lo ? lo : (v > hi ? hi : v);
 #endif
 }
+// the same clamp for a value that may be NaN (a distance from a diverged candidate's positions): the two selects themselves, which
+// leave a NaN a NaN as jnp.clip does — v_med3_f32 answers a NaN operand with the smallest of the other two
+MBD_HD float fclip_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 MBD_HD v3 mk3(float x, float y, float z) { return v3{x, y, z}; }
 MBD_HD float dot(v3 a, v3 b) { return ffma(a.x, b.x, ffma(a.y, b.y, a.z * b.z)); }

@@ -504,6 +504,8 @@ inline unsigned demo_blocks(long long items) {
 // the contract's order since round 6 (rounds 1-5: one chain over all K H terms), chosen so that the rollout kernels can
 // accumulate S_k on the tracked link's lane as the control steps go by (RolloutParams::lp) and produce the same bits
 // without this launch; the standalone entry (mbd_env_xref_logpd) and the instantiations that do not accumulate use this kernel.
+// The clamp is fclip_nan: a NaN distance (a diverged candidate's positions) stays a NaN, as the reference's jnp.clip leaves it,
+// here, in logpd_car2d_kernel and in the rollouts' accumulation alike (v_med3_f32 would turn it into a term of 0).
 constexpr int kLogpdThreads = 256, kLogpdMaxTerms = MBD_MAX_TRACK * 64;
 static __global__ __launch_bounds__(kLogpdThreads) void logpd_track_kernel(const float* __restrict__ xpos,
                                                                     const float* __restrict__ xref, int B, int H, int K,
@@ -517,7 +519,7 @@ static __global__ __launch_bounds__(kLogpdThreads) void logpd_track_kernel(const
     const float* c = xref + ((size_t)k * H + t) * 3;
     float ex = a[0] - c[0], ey = a[1] - c[1], ez = a[2] - c[2];
     float d = fsqrt(ex * ex + ey * ey + ez * ez);
-    d = fclip(d, 0.0f, 0.5f);
+    d = fclip_nan(d, 0.0f, 0.5f);
     float s = d / 0.5f;
     term[k * H + t] = s * s;
   }
@@ -545,7 +547,7 @@ static __global__ __launch_bounds__(64) void logpd_car2d_kernel(const float* __r
     const float* a = qs + ((size_t)b * H + t) * 3;
     float ex = a[0] - xref[2 * t], ey = a[1] - xref[2 * t + 1];
     float d = fsqrt(ex * ex + ey * ey);
-    d = fclip(d, 0.0f, 0.5f);
+    d = fclip_nan(d, 0.0f, 0.5f);
     float s = d / 0.5f;
     acc = acc + s * s;
   }

@@ -192,19 +192,32 @@ class Car2d(_EnvBase):
 class RigidBodyEnv(_EnvBase):
     """HumanoidRun / HumanoidTrack / Hopper / Halfcheetah (mbd/envs/*.py) behind the C ABI."""
 
-    def __init__(self, env_name: str, device: int = 0, model: Optional[Model] = None):
+    def __init__(self, env_name: str, device: int = 0, model: Optional[Model] = None, xref=None, rew_xref: float = 0.0):
+        """``xref`` [n_track][50][3], ``rew_xref``: the demonstration of a caller-compiled ``model`` with tracked links and its
+        reward level (mbd_env_create_model); without them only "humanoidtrack" carries one, its own."""
         self._lib = _capi.load()
         self.device = device
         self.env_name = env_name
         spec = specs.SPECS[env_name]
         h = C.c_void_p()
         if model is None:
+            if xref is not None:
+                raise ValueError("xref belongs to a caller-compiled model: pass model= with it")
             # by name, like mbd.envs.get_env: the compiled model and the demo live inside the library
             _capi.check(self._lib.mbd_env_create(env_name.encode(), device, C.byref(h)))
         else:  # a caller-compiled model (mbd_hip.mjcf.load): custom MJCF files, experiments
-            xref_ptr, rew_xref = None, 0.0
-            if env_name == "humanoidtrack":
+            xref_ptr = None
+            if xref is not None:
+                K = int(model.fields["n_track"])
+                xr = np.ascontiguousarray(xref, np.float32)
+                if xr.shape != (K, _capi.XREF_ROWS, 3):
+                    raise ValueError(f"xref has shape {xr.shape}, the model's n_track={K} wants ({K}, {_capi.XREF_ROWS}, 3)")
+                xref_ptr, rew_xref = _capi.np_ptr(xr), float(rew_xref)
+            elif env_name == "humanoidtrack":
                 xr = np.ascontiguousarray(np.load(os.path.join(_ASSETS, "compiled", "jog_xref.npy")), np.float32)
+                if xr.shape[0] != int(model.fields["n_track"]):  # (the library copies n_track tracks from the pointer)
+                    raise ValueError(f"humanoidtrack's own demonstration has {xr.shape[0]} tracks, the model's n_track="
+                                     f"{int(model.fields['n_track'])}: pass xref= for a retracked model")
                 xref_ptr, rew_xref = _capi.np_ptr(xr), 1.0  # humanoidtrack.py:44
             st = model.to_struct()
             _capi.check(self._lib.mbd_env_create_model(env_name.encode(), device, C.byref(st), xref_ptr, rew_xref,

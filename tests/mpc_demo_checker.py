@@ -148,11 +148,18 @@ SEED_RESET, SEED_KEY, SEED_DISTURB = 5, 6, 11
 REW_XREF = {"humanoidtrack": 1.0, "car2d": 0.75}  # the records' reward level (humanoidtrack.py:44; car2d: any finite value does)
 
 
-def oracle_env(orc, name):
-    """The OracleEnv of ``name`` with its demo, from the compiled assets — no device."""
+def oracle_env(orc, name, custom=None, rew_xref=None):
+    """The OracleEnv of ``name`` with its demo, from the compiled assets — no device.  ``custom``: (model, xref) of a
+    caller-compiled tracked model (a mbd_hip.model.Model and its demonstration [n_track, 50, 3]) under that env name, with
+    ``rew_xref`` as its reward level."""
     import os
 
     from conftest import ROOT, load_model
+    if custom is not None:
+        m, xref = custom
+        assert np.shape(xref) == (int(m.fields["n_track"]), ROWS, 3), np.shape(xref)
+        return op.OracleEnv(orc, name, m.to_struct(), xref=np.ascontiguousarray(xref, np.float32),
+                            rew_xref=float(REW_XREF.get(name, 0.0) if rew_xref is None else rew_xref), init_q=m.init_q)
     compiled = os.path.join(ROOT, "model-based-diffusion_amd", "assets", "compiled")
     if name == "car2d":
         return op.OracleEnv(orc, "car2d", xref=np.load(os.path.join(compiled, "car2d_xref.npy")).astype(np.float32),
