@@ -2,7 +2,7 @@
  * session (mbd_plan_mpc_open) is opened once and advanced one tick per call from the state the caller's system is in.
  *
  *   gcc -O2 -I include examples/mbd_control.c -o mbd_control -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
- *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi] [--pick] [--value]
+ *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi] [--pick] [--value] [--elites]
  *                 env    N   H  Nd K ticks
  *
  * The "system" here is a second env the example owns, stepped with mbd_env_step — the env's rollout kernel at B = 1, H = 1 through
@@ -31,6 +31,10 @@
  * link 0 at the end of every candidate's rollout, weighing like one further reward row; a real controller loads a fitted net
  * (python -m mbd_hip.scripts.fit_value) into the same struct.  Rigid-body envs only (the state record's float 2 is link 0's z).
  *
+ * --elites (among the trailing flags): an elite record (mbd_elites) — the four best candidates of every diffusion step are candidates
+ * of the next one, candidate 0 of every step is the step's mean itself, and a tick boundary shifts the elites with the mean; the
+ * tick's line gains "kept K top R": how many of the last step's elites had been injected, and the best return it saw.
+ *
  * Prints one line per tick: "tick T reward R ms M flags F", then "mean_reward R ms_per_tick M". */
 #include <math.h>
 #include <stdio.h>
@@ -56,11 +60,12 @@ static int plant_step(mbd_env* plant, float* state, const float* action, float* 
 }
 
 int main(int argc, char** argv) {
-  int mppi = 0, pick = 0, value = 0;
+  int mppi = 0, pick = 0, value = 0, elites = 0;
   while (argc > 1 && (strcmp(argv[argc - 1], "--mppi") == 0 || strcmp(argv[argc - 1], "--pick") == 0 ||
-                      strcmp(argv[argc - 1], "--value") == 0)) { /* trailing flags */
+                      strcmp(argv[argc - 1], "--value") == 0 || strcmp(argv[argc - 1], "--elites") == 0)) { /* trailing flags */
     if (strcmp(argv[argc - 1], "--mppi") == 0) mppi = 1;
     else if (strcmp(argv[argc - 1], "--pick") == 0) pick = 1;
+    else if (strcmp(argv[argc - 1], "--elites") == 0) elites = 1;
     else value = 1;
     argc -= 1;
   }
@@ -135,6 +140,12 @@ int main(int argc, char** argv) {
     CHECK(mbd_plan_set_value(plan, &val)); /* (copied: the tables may go) */
     free(w);
   }
+  if (elites) { /* keep what a step found: its four best candidates and its mean are candidates of the next step, across ticks too */
+    mbd_elites el;
+    memset(&el, 0, sizeof(el));
+    el.n_elites = 4; el.nominal = 1; el.carry = 1;
+    CHECK(mbd_plan_set_elites(plan, &el));
+  }
   if (D > 0) { /* plans arrive D ticks late; the system starts committed to zeros */
     mbd_mpc_delay delay;
     memset(&delay, 0, sizeof(delay));
@@ -172,6 +183,12 @@ int main(int argc, char** argv) {
       float rets[3] = {0.0f, 0.0f, 0.0f};
       CHECK(mbd_plan_peek_mpc_pick(plan, &choice, rets, NULL, 1, NULL)); /* (the most recent tick's entry) */
       printf(" choice %d value %.9g", (int)choice, rets[choice]);
+    }
+    if (elites) {
+      int32_t kept = 0;
+      float top = 0.0f;
+      CHECK(mbd_plan_peek_elites(plan, NULL, NULL, NULL, NULL, NULL, &kept, &top, 1, NULL)); /* (the most recent step's entry) */
+      printf(" kept %d top %.9g", (int)kept, top);
     }
     printf("\n");
     reward_sum += reward;

@@ -892,6 +892,74 @@ int mbd_plan_set_adapt(mbd_plan* plan, const mbd_adapt* rec);
  * MBD_ERR_STATE without a record; MBD_ERR_INVALID: a NULL handle, capacity < 0. */
 int mbd_plan_peek_adapt(mbd_plan* plan, float* a_out, float* ratio_out, int32_t* skipped_out, int capacity, int* count_out);
 
+/* ---- elites: a step's best candidates are candidates of the next step, and the step's mean may be one itself (the elite carry-over
+ * of iCEM and CEM-MPC; the noise-free nominal of MPPI implementations and of predictive sampling; no counterpart in the reference,
+ * whose every step draws N fresh candidates; DESIGN.md section 1 "N18 elites") ---- */
+/* An elite record is a setting of a plan beside the adapt record.  The plan keeps, on the device, the rows E [n_elites][HNu] of the
+ * best candidates its last diffusion step found, their returns R and indices src [n_elites], and one integer `count`, 0 <= count <=
+ * n_elites, the number present.  Every step first overwrites its first candidates with them (injection), and behind its update takes
+ * over its own best (selection).  No rollout kernel and no update kernel changes: an injected candidate is rolled out, scored and
+ * averaged like any other. */
+typedef struct mbd_elites {
+  int32_t n_elites;   /* 0..32: how many of a step's best candidates the next step takes over              */
+  int32_t nominal;    /* 0 / 1: candidate 0 of every step is the step's mean itself, clip(Ybar_i)          */
+  int32_t carry;      /* 0: a tick starts without elites; 1: at a tick boundary they are shifted with the mean */
+  int32_t reserved[5];  /* must be 0 */
+} mbd_elites;
+/* The contract — f32 throughout, every operation rounded.  slots = nominal + count.
+ * INJECTION, in phase 1 of step i, behind the launch that made the step's normals z [N][HNu] (lazy plans: the MBD update on a
+ * rigid-body env) or candidates Y0s [N][HNu] (materialised plans: car2d, mppi), in front of the rollout.  For every element e:
+ *   nominal set, candidate 0:        lazy z[0][e] = +0;                  materialised Y0s[0][e] = clip(Ybar_i[e], -1, 1)
+ *   elite j < count, candidate nominal + j:
+ *                                    materialised Y0s[nominal+j][e] = E[j][e]
+ *                                    lazy z[nominal+j][e] = g[e] == 0 ? +0 : (E[j][e] - Ybar_i[e]) / sigma_i   (the subtraction and
+ *                                    the division each rounded)
+ *   candidates from `slots` on keep every bit they were drawn with.
+ * g is the shape the step's sampler was handed — the caller's noise shape in force in that step, or an adapt record's G —; with no
+ * shape in force there is no test on g.  A frozen element therefore stays frozen.  What is rolled out and averaged for a lazy elite
+ * is what the consumers of z form, clip((z * sigma_i) + Ybar_i, -1, 1): NOT E[j] bit for bit — the division and the product do not
+ * undo each other exactly, and a frozen element takes Ybar_i's value.  The contract is the z above.  The rows are written behind a
+ * noise basis where one is in force: they need not lie in the basis' span.
+ * SELECTION, in phase 2 of step i, behind the step's update kernel (and an adapt record's launches), over r [N], the rewards the
+ * score read — behind an objective, a value and an ensemble record:
+ *   only finite entries (exponent bits not all ones) take part
+ *   order: descending value, equal values (+0 == -0) lower index first — a total order on distinct indices
+ *   count' = min(n_elites, number of finite entries);  src'[j] = the j-th entry in that order;  R'[j] = r[src'[j]]
+ *   E'[j] = candidate src'[j] as mbd_plan_peek forms it: lazy clip((z[e] * sigma_i) + Ybar_i[e], -1, 1) from the step's normals —
+ *           the injected rows included — and its Ybar_i; materialised the row as it stands
+ *   log entry of the step: count', kept = the number of j with src'[j] < slots (the slots the step injected), top = R'[0], or the
+ *           quiet NaN 0x7fc00000 when count' == 0
+ * The injected candidates take part like any other, so an elite that is still among the best stays.  There is no sum in it: the
+ * result is decided by an order and by gathers, whatever the algorithm.
+ * LIFE CYCLE.  count = 0: at the set call, at the start of mbd_plan_run, at a cold tick of an episode or a session, behind
+ * mbd_plan_mpc_reset_mean, and at the start of every other tick with carry == 0.  With carry == 1 the start of every other tick
+ * shifts every present elite exec_steps rows forward with zeros behind it — the mean's own shift —, count stays, and R is stale until
+ * the next selection rewrites it.  (One small launch in front of the tick's first sampler; behind an episode's last tick the elites
+ * stay as that tick's last step selected them.)  The phase calls (mbd_plan_sample_rollout / mbd_plan_score_update,
+ * mbd_plan_reverse_once) use the state as it stands.
+ * A step's candidates now depend on the previous step's result, so a plan with a record takes the adapt record's route through the
+ * noise ring: every step makes its normals in front of its rollout, nothing is prepared ahead or reused, and
+ * mbd_plan_prefetch_noise is a no-op for it.  A step gains two launches, a tick one more.  Without a record nothing is launched and
+ * every call keeps its bits.
+ * Scope: MBD and mppi plans (update_method 0 and 1), rigid-body envs and car2d, lazy and materialised candidates, with or without
+ * plant, delay, sigma, objective, weighting, value, ensemble, pick, adapt, noise-shape and noise-basis records (a pick record's best
+ * candidate may then be an elite); mbd_plan_run, the unsharded phase calls, mbd_plan_run_mpc and sessions.  Sweeps have no such call.
+ * The set call is synchronous (it waits for the device), discards normals prepared ahead, and is to be called between diffusion
+ * steps; rec == NULL clears.  Refused before any device access, the message naming the field — MBD_ERR_INVALID: a NULL handle,
+ * n_elites outside [0, 32], nominal or carry outside {0, 1}, n_elites + nominal == 0, n_elites + nominal >= Nsample, non-zero
+ * reserved; MBD_ERR_UNSUPPORTED: update_method 2 or 3 (cem keeps elites of its own kind, cma-es' spread would be biased by repeated
+ * rows), a plan created with enable_demo (its score is not the return); MBD_ERR_STATE: a sharded plan, a session open on the
+ * handle. */
+int mbd_plan_set_elites(mbd_plan* plan, const mbd_elites* rec);
+/* The elites and the log (HOST; any of the outputs may be NULL; synchronises the device): elites_out [n_elites][HNu], returns_out
+ * and src_out [n_elites] as they stand — only the first *count_out entries mean anything —; log_count / log_kept / log_top: the
+ * entries of the steps since the last mbd_plan_run, mbd_plan_run_mpc or mbd_plan_mpc_open began (the phase calls append), in the order
+ * the steps ran — the most recent min(steps, capacity, 65536) of them, oldest first.  The log lives on the device and the selection
+ * kernel writes it.  *n_log_out: the steps there were.  MBD_ERR_STATE without a record; MBD_ERR_INVALID: a NULL handle,
+ * capacity < 0. */
+int mbd_plan_peek_elites(mbd_plan* plan, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
+                         int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out);
+
 /* ---- planning ahead of the plant: an episode whose plans take D ticks to arrive (the real-time iteration scheme; no
  * counterpart in the reference; DESIGN.md section 1 "N9 delay") ---- */
 /* The episode of mbd_plan_run_mpc plans from s_t and executes that plan's first rows from the same s_t: planning takes no time.

@@ -121,6 +121,26 @@ int mbd_debug_adapt_host(const float* w, const float* cand, int N, int HNu, cons
 int mbd_debug_adapt_step(const float* w, const float* cand, int N, int HNu, const float* ybar, float sigma, int sigma_on_device,
                          int lazy, const float* a, const float* g, float rate, float a_min, float a_max, float* a_out, float* G_out,
                          float* S_out, int32_t* skipped_out);
+/* The refusals an elite record alone decides (include/mbd_hip.h mbd_elites) for a plan of that Nsample, update_method and
+ * enable_demo: the function the set call runs on its record, host arithmetic, no device. */
+int mbd_debug_check_elites(const mbd_elites* rec, int Nsample, int update_method, int enable_demo);
+/* One step of an elite record on the HOST: the injection of E_in [count_in][HNu] (and the nominal) into a copy of cand [N][HNu] —
+ * values, or with lazy != 0 normals —, then the selection over rews [N] from that copy; the per-element functions and the order the
+ * kernels use (one text for host and device), no device touched.  ybar [HNu] Ybar_i; g [HNu] or NULL: no shape.  cand_out [N][HNu]
+ * the candidates behind the injection; E_out [n_elites][HNu], R_out, src_out [n_elites]: rows and entries from count' on have all
+ * bits set; count_out, kept_out, top_out: the log entry.  Any output may be NULL.  n_elites, nominal and N are checked as the set
+ * call checks them; 0 <= count_in <= n_elites; N * HNu <= 2^26. */
+int mbd_debug_elites_host(const float* rews, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy,
+                          const float* g, int n_elites, int nominal, const float* E_in, int count_in, float* cand_out, float* E_out,
+                          float* R_out, int32_t* src_out, int32_t* count_out, int32_t* kept_out, float* top_out);
+/* The two launches alone on the DEVICE, on caller-given arrays: elite_inject_kernel over cand (count_in in a device word, as a
+ * plan's), and elite_select_kernel over rews and cand (count_in: the word it finds; what is read back is filled with all-ones bits
+ * first).  Argument errors first, then MBD_ERR_NO_DEVICE. */
+int mbd_debug_elites_inject(const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy, const float* g, int n_elites,
+                            int nominal, const float* E_in, int count_in, float* cand_out);
+int mbd_debug_elites_select(const float* rews, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy,
+                            int n_elites, int nominal, int count_in, float* E_out, float* R_out, int32_t* src_out, int32_t* count_out,
+                            int32_t* kept_out, float* top_out);
 #ifdef __cplusplus
 }
 #endif

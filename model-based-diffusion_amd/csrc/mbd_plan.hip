@@ -6,6 +6,7 @@
 #define MBD_PICK_KERNEL 1   // ... and, for plans and sweeps alike, the pick record's kernels
 #define MBD_VALUE_KERNEL 1  // ... and the value record's
 #define MBD_ADAPT_KERNEL 1  // ... and the adapt record's (plans only)
+#define MBD_ELITE_KERNEL 1  // ... and the elite record's (plans only)
 #include "mbd_internal.h"
 #include "../../include/mbd_hip_debug.h"
 
@@ -141,6 +142,19 @@ struct AdaptRec {
   DevBuf<int> d_log_skipped;
 };
 
+// The elite record of a plan (include/mbd_hip.h mbd_elites) as the handle keeps it: the record, the elites' rows E [n][HNu], their
+// returns R and source indices src [n], the device word `count`, and the device log, a ring of kEliteLogCap entries (entry of step j
+// at j % cap; steps: selections since the log began).  count never comes back to the host inside a loop: every kernel loads it.
+// All zero: no record (a zeroed stand-in handle has none).
+constexpr int kEliteLogCap = 65536;
+struct EliteRec {
+  bool has = false;
+  int n = 0, nominal = 0, carry = 0;
+  long long steps = 0;
+  DevBuf<float> d_E, d_R, d_log_top;
+  DevBuf<int> d_src, d_count, d_log_count, d_log_kept;
+};
+
 struct mbd_plan {
   mbd_env* env = nullptr;
   hipStream_t last_stream = nullptr;  // stream of the plan's previous phase call (plan_enter orders a change of stream)
@@ -212,6 +226,8 @@ struct mbd_plan {
   ValueRec val;
   // the adapt record (mbd_plan_set_adapt) with its table, the shape the samplers draw under and the device log of its steps
   AdaptRec adapt;
+  // the elite record (mbd_plan_set_elites) with the elites, their count on the device and the device log of its steps
+  EliteRec elite;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_plan_mpc_open); it uses the episodes' buffers above — d_mpc_state for the
   // state handed in, d_mpc_pred for the one predicted state, d_mpc_queue — so a handle runs episodes or a session, not both
@@ -375,6 +391,11 @@ static NoiseSpec noise_spec(const mbd_plan* p, bool warm_tick) {
 static NoiseSpec noise_always(const mbd_plan* p) { return noise_spec(p, false); }
 static NoiseSpec noise_warm(const mbd_plan* p) { return noise_spec(p, true); }
 
+// Whether a step's candidates depend on the previous step's result — an adapt record's table, an elite record's rows —, so that
+// nothing about them can be prepared ahead or reused: the noise ring declares nothing, reuses nothing, and the loops do not hold the
+// host back for a second stream that has no job.
+static bool follows_result(const mbd_plan* p) { return p->adapt.has || p->elite.has; }
+
 // ---- the adapt record's launches (include/mbd_hip.h mbd_adapt; set, peek and the debug entries: below) -----------------------
 // The table at the start of a run or a tick, or under a new shape: shift < 0: a = ones, otherwise a shifted `shift` elements forward
 // (0: as it is); G = a * g under the caller's shape g now in force, which the updates that follow keep forming G under.  ONE launch.
@@ -413,6 +434,49 @@ static int adapt_update(mbd_plan* p, int i, const float* d_Ybar_i, const float* 
                       A.d_log_S.get() + slot, A.d_log_skipped.get() + slot, s);
 }
 
+// ---- the elite record's launches (include/mbd_hip.h mbd_elites; set, peek and the debug entries: below) -----------------------
+// The elites at the start of a run or a tick: shift < 0: count = 0, otherwise the present rows shifted `shift` elements forward.
+// ONE launch, a workgroup per row.
+static int elite_table(mbd_plan* p, int shift, hipStream_t s) {
+  EliteRec& L = p->elite;
+  if (!L.has) return MBD_OK;
+  hipLaunchKernelGGL(elite_shift_kernel, dim3(L.n > 0 ? L.n : 1), dim3(kEliteThreads), 0, s, L.d_E.get(), L.d_count.get(), p->HNu, shift);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+// the injection on caller-given arrays (a step's: elite_inject; mbd_debug_elites_inject)
+static int elite_inject_launch(const EliteInject& A, hipStream_t s) {
+  const long long total = (long long)(A.nominal + A.n_elites) * A.HNu;
+  hipLaunchKernelGGL(elite_inject_kernel, dim3((unsigned)((total + kEliteThreads - 1) / kEliteThreads)), dim3(kEliteThreads), 0, s, A);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+// phase 1 of step i, behind the launch that made the step's normals (lazy: eps[cur]) or candidates (d_Y0s), in front of the rollout:
+// g is the shape the step's sampler was handed.  The buffer of a lazy plan no longer holds what its tag says: the ring forgets it.
+static int elite_inject(mbd_plan* p, int i, const float* d_Ybar_i, const float* g, hipStream_t s) {
+  EliteRec& L = p->elite;
+  if (!L.has) return MBD_OK;
+  EliteInject A{};
+  A.cand = p->lazy ? p->ring.eps[p->ring.cur].get() : p->d_Y0s.get();
+  A.HNu = p->HNu; A.ybar_i = d_Ybar_i; A.lazy = p->lazy ? 1 : 0; A.sigma = p->sigmas[i]; A.g = g;
+  A.n_elites = L.n; A.nominal = L.nominal; A.E = L.d_E; A.count = L.d_count;
+  if (p->lazy) p->ring.valid[p->ring.cur] = false;
+  return elite_inject_launch(A, s);
+}
+// phase 2 of step i, behind the step's update kernel (and an adapt record's launches): the selection over the rewards the score read
+static int elite_select(mbd_plan* p, int i, const float* d_Ybar_i, const float* d_cand, const float* d_rews_all, hipStream_t s) {
+  EliteRec& L = p->elite;
+  if (!L.has) return MBD_OK;
+  const int slot = (int)(L.steps++ % kEliteLogCap);
+  EliteSelect A{};
+  A.rews = d_rews_all; A.N = p->cfg.Nsample; A.HNu = p->HNu; A.cand = d_cand; A.lazy = p->lazy ? 1 : 0; A.sigma = p->sigmas[i];
+  A.ybar_i = d_Ybar_i; A.n_elites = L.n; A.nominal = L.nominal; A.E = L.d_E; A.R = L.d_R; A.src = L.d_src; A.count = L.d_count;
+  A.log_count = L.d_log_count.get() + slot; A.log_kept = L.d_log_kept.get() + slot; A.log_top = L.d_log_top.get() + slot;
+  hipLaunchKernelGGL(elite_select_kernel, dim3(1), dim3(kScoreThreads), 0, s, A);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+
 // z [N][HNu] of a step into `out`: noise_kernel, or under a basis knot_noise_kernel
 static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], float* out, const NoiseSpec& ns) {
   const mbd_plan_config& c = p->cfg;
@@ -435,8 +499,9 @@ static void launch_noise(mbd_plan* p, hipStream_t st, const uint32_t key[2], flo
 // rollout.  Under a basis the job is knot_noise_kernel's and always goes to the second stream: prepare_noise_job)
 static int declare_next_key(mbd_plan* p, const uint32_t key_next[2], const NoiseSpec& ns) {
   const bool off = env_flag("MBD_NO_PREFETCH");
-  // (under an adapt record a step's normals depend on the previous step's result: nothing is declared, every step makes its own)
-  if (off || !p->lazy || p->adapt.has) return MBD_OK;
+  // (under an adapt or an elite record a step's normals depend on the previous step's result: nothing is declared, every step makes
+  // its own)
+  if (off || !p->lazy || follows_result(p)) return MBD_OK;
   p->ring.hint_key[0] = key_next[0];
   p->ring.hint_key[1] = key_next[1];
   p->ring.hint_ns = ns;
@@ -468,8 +533,9 @@ static int plan_enter(mbd_plan* p, hipStream_t s) {
 // action fetch and inside the weighted mean.  The step's normals: ring.cur afterwards.
 static int obtain_normals(mbd_plan* p, const uint32_t key_sample[2], const NoiseSpec& ns, hipStream_t s) {
   NoiseRing& ring = p->ring;
-  // (under an adapt record the table behind ns.g changes from step to step: a buffer's tag says nothing, nothing is reused)
-  int cur = p->adapt.has ? -1 : ring.find(key_sample, ns);
+  // (under an adapt record the table behind ns.g changes from step to step, under an elite record rows of the buffer are rewritten
+  // behind the sampler: a buffer's tag says nothing, nothing is reused)
+  int cur = follows_result(p) ? -1 : ring.find(key_sample, ns);
   if (cur >= 0) {  // prepared behind the previous rollout
     MBD_TRY(ring.join(cur, s));
   } else {  // not prepared: generate now, into the buffer behind the previous step's (stream order protects it)
@@ -612,6 +678,9 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
   } else {
     MBD_TRY(sample_candidates(p, i, key_sample, d_Ybar_i, ns, s));
   }
+  // The elite record: ONE launch between the sampler and the rollout rewrites the first rows — the step's mean, the elites the
+  // previous step left
+  MBD_TRY(elite_inject(p, i, d_Ybar_i, ns.g, s));
   // A2/A3: rollout of the local shard
   MBD_TRY(p->timing.begin(s));
   const float* d_cand = p->lazy ? ring.eps[ring.cur] : p->d_Y0s;
@@ -748,6 +817,9 @@ static int plan_score_update(mbd_plan* p, int i, const float* d_Ybar_i, const fl
   // candidates (eps[cur] of a lazy plan: read here in front of the ring's mark, so the weighted mean's argument covers them) and the
   // Ybar_i the caller has not yet moved on from
   MBD_TRY(adapt_update(p, i, d_Ybar_i, d_cand, s));
+  // The elite record: ONE launch in the same place takes the step's best candidates over — from the rewards the score read, the
+  // candidates (eps[cur]: in front of the ring's mark as well) and Ybar_i
+  MBD_TRY(elite_select(p, i, d_Ybar_i, d_cand, d_rews_all, s));
   if (p->lazy) {
     p->peek_ybar = p->d_ybar_keep;
     MBD_TRY(p->ring.mark_wmean(s, p->aux != nullptr));
@@ -924,7 +996,7 @@ extern "C" int mbd_debug_knot_noise_host(const uint32_t key[2], int impl, int N,
 // it needs it and the step's stream carries no event (NoiseRing: the ring of three buffers).
 static int plan_keep_in_step(mbd_plan* p) {
   NoiseRing& ring = p->ring;
-  if (!p->lazy || !ring.progress || ring.seq == 0 || p->cfg.shares_device != 0 || p->adapt.has) return MBD_OK;
+  if (!p->lazy || !ring.progress || ring.seq == 0 || p->cfg.shares_device != 0 || follows_result(p)) return MBD_OK;
   // (a plan with a noise basis prepares its normals on the second stream whatever the launch could take)
   if (!p->has_basis && rollout_takes_noise(plan_rollout_choice(p), p->cfg.prng_impl, p->cfg.Nsample, p->HNu)) return MBD_OK;
   // (a stream slower than the limit: the loop stops keeping step and the step orders the two streams with an event instead —
@@ -991,6 +1063,8 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
   HIP_TRY(hipMemsetAsync(cur, 0, sizeof(float) * HNu, s));
   MBD_TRY(adapt_table(p, -1, shape_always(p), s));  // (an adapt record: a = ones, and its log begins)
   p->adapt.count = 0;
+  MBD_TRY(elite_table(p, -1, s));  // (an elite record: no elites, and its log begins)
+  p->elite.steps = 0;
   HIP_TRY(hipStreamSynchronize(s));
   p->wt.begin();
   auto t0 = std::chrono::steady_clock::now();
@@ -2302,6 +2376,234 @@ extern "C" int mbd_debug_adapt_step(const float* w, const float* cand, int N, in
   return MBD_OK;
 }
 
+// ---- the elite record (include/mbd_hip.h mbd_elites) --------------------------------------------------------------------------
+// the refusals the record alone decides against the handle's Nsample, update_method and enable_demo, in the header's order, each
+// naming the field — host arithmetic, before any device access
+static int check_elites(const mbd_elites* rec, int Nsample, int update_method, int enable_demo) {
+  if (rec->n_elites < 0 || rec->n_elites > kEliteMax)
+    return fail(MBD_ERR_INVALID, "elite record: n_elites=%d outside [0, %d]", rec->n_elites, kEliteMax);
+  if (rec->nominal != 0 && rec->nominal != 1) return fail(MBD_ERR_INVALID, "elite record: nominal=%d: 0 or 1", rec->nominal);
+  if (rec->carry != 0 && rec->carry != 1) return fail(MBD_ERR_INVALID, "elite record: carry=%d: 0 or 1", rec->carry);
+  if (rec->n_elites + rec->nominal == 0)
+    return fail(MBD_ERR_INVALID, "elite record: n_elites=0 with nominal=0: the record asks for nothing (NULL clears)");
+  if (rec->n_elites + rec->nominal >= Nsample)
+    return fail(MBD_ERR_INVALID, "elite record: n_elites=%d + nominal=%d must lie below Nsample=%d", rec->n_elites, rec->nominal, Nsample);
+  for (int r = 0; r < 5; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "elite record: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (update_method == 2 || update_method == 3)
+    return fail(MBD_ERR_UNSUPPORTED, "elite record: update_method=%d: cem (3) keeps elites of its own kind, cma-es' (2) spread would "
+                                     "be biased by repeated rows", update_method);
+  if (enable_demo) return fail(MBD_ERR_UNSUPPORTED, "elite record: enable_demo=1: a demo plan's score is not the return");
+  return MBD_OK;
+}
+extern "C" int mbd_debug_check_elites(const mbd_elites* rec, int Nsample, int update_method, int enable_demo) {
+  if (!rec) return fail(MBD_ERR_INVALID, "elite record is NULL");
+  return check_elites(rec, Nsample, update_method, enable_demo);
+}
+
+extern "C" int mbd_plan_set_elites(mbd_plan* p, const mbd_elites* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (rec) MBD_TRY(check_elites(rec, p->cfg.Nsample, p->cfg.update_method, p->cfg.enable_demo));  // (before any device access)
+  if (rec && p->cfg.shard_count != p->cfg.Nsample)
+    return fail(MBD_ERR_STATE, "elite record: shard_count=%d of Nsample=%d: sharded plans take no elite record", p->cfg.shard_count,
+                p->cfg.Nsample);
+  NO_SESSION(p, "set_elites");
+  EliteRec& L = p->elite;
+  if (!rec && !L.has) return MBD_OK;  // (nothing to clear: no device is touched)
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the elites or write the log)
+  // normals prepared ahead are not what the record's steps take, and a buffer the record rewrote is not what its tag said: as
+  // mbd_plan_set_noise_shape, nothing prepared survives — in either direction
+  p->ring.forget();
+  L.has = false;
+  L.steps = 0;
+  if (!rec) return MBD_OK;
+  const size_t n = rec->n_elites > 0 ? (size_t)rec->n_elites : 1;
+  HIP_TRY(L.d_E.grow(n * p->HNu));
+  HIP_TRY(L.d_R.grow(n));
+  HIP_TRY(L.d_src.grow(n));
+  HIP_TRY(L.d_count.grow(1));
+  HIP_TRY(L.d_log_count.grow(kEliteLogCap));
+  HIP_TRY(L.d_log_kept.grow(kEliteLogCap));
+  HIP_TRY(L.d_log_top.grow(kEliteLogCap));
+  L.n = rec->n_elites;
+  L.nominal = rec->nominal;
+  L.carry = rec->carry;
+  L.has = true;
+  MBD_TRY(elite_table(p, -1, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return MBD_OK;
+}
+
+// the most recent n entries of a device ring of kEliteLogCap entries that has seen `steps`, oldest first: two pieces at the most
+template <typename T>
+static int elite_log_read(const T* d_ring, long long steps, long long n, T* out) {
+  if (!out || n <= 0) return MBD_OK;
+  const size_t first = (size_t)((steps - n) % kEliteLogCap);
+  const size_t n0 = (size_t)n < kEliteLogCap - first ? (size_t)n : kEliteLogCap - first, n1 = (size_t)n - n0;
+  HIP_TRY(hipMemcpy(out, d_ring + first, sizeof(T) * n0, hipMemcpyDeviceToHost));
+  if (n1) HIP_TRY(hipMemcpy(out + n0, d_ring, sizeof(T) * n1, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+extern "C" int mbd_plan_peek_elites(mbd_plan* p, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
+                                    int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  const EliteRec& L = p->elite;
+  if (!L.has) return fail(MBD_ERR_STATE, "peek_elites: the plan has no elite record");
+  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_elites: capacity=%d", capacity);
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (elites_out && L.n) HIP_TRY(hipMemcpy(elites_out, L.d_E, sizeof(float) * (size_t)L.n * p->HNu, hipMemcpyDeviceToHost));
+  if (returns_out && L.n) HIP_TRY(hipMemcpy(returns_out, L.d_R, sizeof(float) * L.n, hipMemcpyDeviceToHost));
+  if (src_out && L.n) HIP_TRY(hipMemcpy(src_out, L.d_src, sizeof(int32_t) * L.n, hipMemcpyDeviceToHost));
+  if (count_out) HIP_TRY(hipMemcpy(count_out, L.d_count, sizeof(int32_t), hipMemcpyDeviceToHost));
+  long long n = L.steps < kEliteLogCap ? L.steps : kEliteLogCap;
+  if (n > capacity) n = capacity;
+  MBD_TRY(elite_log_read<int>(L.d_log_count, L.steps, n, log_count));
+  MBD_TRY(elite_log_read<int>(L.d_log_kept, L.steps, n, log_kept));
+  MBD_TRY(elite_log_read<float>(L.d_log_top, L.steps, n, log_top));
+  if (n_log_out) *n_log_out = (int)(L.steps < 0x7fffffffll ? L.steps : 0x7fffffffll);
+  return MBD_OK;
+}
+
+// include/mbd_hip_debug.h: one step of the record on the HOST — the injection, then the selection — from the functions the kernels
+// call (one text for host and device); no device touched
+static int check_elites_args(const char* what, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy, int n_elites,
+                             int nominal, const float* E_in, int count_in) {
+  if (!cand || !ybar) return fail(MBD_ERR_INVALID, "%s: NULL argument", what);
+  if (N < 1 || HNu < 1 || (uint64_t)N * (uint64_t)HNu > (1ull << 26)) return fail(MBD_ERR_INVALID, "%s: N=%d HNu=%d", what, N, HNu);
+  if (n_elites < 0 || n_elites > kEliteMax) return fail(MBD_ERR_INVALID, "%s: n_elites=%d outside [0, %d]", what, n_elites, kEliteMax);
+  if (nominal != 0 && nominal != 1) return fail(MBD_ERR_INVALID, "%s: nominal=%d: 0 or 1", what, nominal);
+  if (n_elites + nominal >= N) return fail(MBD_ERR_INVALID, "%s: n_elites=%d + nominal=%d must lie below N=%d", what, n_elites, nominal, N);
+  if (count_in < 0 || count_in > n_elites) return fail(MBD_ERR_INVALID, "%s: count=%d outside [0, n_elites=%d]", what, count_in, n_elites);
+  if (count_in > 0 && !E_in) return fail(MBD_ERR_INVALID, "%s: count=%d without elites", what, count_in);
+  if (lazy && !(sigma > 0.0f)) return fail(MBD_ERR_INVALID, "%s: sigma=%g: a lazy plan's sigma is > 0", what, (double)sigma);
+  return MBD_OK;
+}
+static void elites_inject_host(float* cand, int HNu, const float* ybar, float sigma, int lazy, const float* g, int nominal,
+                               const float* E_in, int count_in) {
+  for (int slot = 0; slot < nominal + count_in; ++slot)
+    for (int e = 0; e < HNu; ++e) {
+      float v;
+      if (slot < nominal) {
+        v = elite_nominal(ybar[e], lazy);
+      } else {
+        const float Ej = E_in[(size_t)(slot - nominal) * HNu + e];
+        v = lazy ? elite_z(Ej, ybar[e], sigma, g, e) : Ej;
+      }
+      cand[(size_t)slot * HNu + e] = v;
+    }
+}
+extern "C" int mbd_debug_elites_host(const float* rews, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy,
+                                     const float* g, int n_elites, int nominal, const float* E_in, int count_in, float* cand_out,
+                                     float* E_out, float* R_out, int32_t* src_out, int32_t* count_out, int32_t* kept_out,
+                                     float* top_out) {
+  MBD_TRY(check_elites_args("elites_host", cand, N, HNu, ybar, sigma, lazy, n_elites, nominal, E_in, count_in));
+  if (!rews) return fail(MBD_ERR_INVALID, "elites_host: NULL argument");
+  std::vector<float> c(cand, cand + (size_t)N * HNu);
+  elites_inject_host(c.data(), HNu, ybar, sigma, lazy, g, nominal, E_in, count_in);
+  int src[kEliteMax];
+  float R[kEliteMax];
+  const int cnt = elite_select_host(rews, N, n_elites, src, R);
+  int kept = 0;
+  for (int j = 0; j < cnt; ++j) kept += src[j] < nominal + count_in ? 1 : 0;
+  if (cand_out) memcpy(cand_out, c.data(), sizeof(float) * c.size());
+  // (rows and entries from count' on are left as the device entry leaves them: all bits set)
+  if (E_out) memset(E_out, 0xff, sizeof(float) * (size_t)n_elites * HNu);
+  if (R_out) memset(R_out, 0xff, sizeof(float) * n_elites);
+  if (src_out) memset(src_out, 0xff, sizeof(int32_t) * n_elites);
+  for (int j = 0; j < cnt; ++j) {
+    if (E_out)
+      for (int e = 0; e < HNu; ++e) E_out[(size_t)j * HNu + e] = elite_value(c[(size_t)src[j] * HNu + e], lazy, sigma, ybar[e]);
+    if (R_out) R_out[j] = R[j];
+    if (src_out) src_out[j] = src[j];
+  }
+  if (count_out) *count_out = cnt;
+  if (kept_out) *kept_out = kept;
+  if (top_out) *top_out = cnt > 0 ? R[0] : __builtin_bit_cast(float, 0x7fc00000u);
+  return MBD_OK;
+}
+// ... and the two launches alone on the DEVICE, on caller-given arrays.  What is read back is filled with all-ones bits first.
+extern "C" int mbd_debug_elites_inject(const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy, const float* g,
+                                       int n_elites, int nominal, const float* E_in, int count_in, float* cand_out) {
+  MBD_TRY(check_elites_args("elites_inject", cand, N, HNu, ybar, sigma, lazy, n_elites, nominal, E_in, count_in));
+  if (!cand_out) return fail(MBD_ERR_INVALID, "elites_inject: NULL argument");
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  const size_t n = (size_t)N * HNu, ne = (size_t)(n_elites > 0 ? n_elites : 1) * HNu;
+  DevBuf<float> d_cand, d_ybar, d_g, d_E;
+  DevBuf<int> d_count;
+  HIP_TRY(d_cand.alloc(n));
+  HIP_TRY(d_ybar.alloc(HNu));
+  HIP_TRY(d_E.alloc(ne));
+  HIP_TRY(d_count.alloc(1));
+  if (g) {
+    HIP_TRY(d_g.alloc(HNu));
+    HIP_TRY(hipMemcpy(d_g, g, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy(d_cand, cand, sizeof(float) * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_ybar, ybar, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_E, 0xff, sizeof(float) * ne));
+  if (count_in > 0) HIP_TRY(hipMemcpy(d_E, E_in, sizeof(float) * (size_t)count_in * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_count, &count_in, sizeof(int), hipMemcpyHostToDevice));
+  EliteInject A{};
+  A.cand = d_cand; A.HNu = HNu; A.ybar_i = d_ybar; A.lazy = lazy ? 1 : 0; A.sigma = sigma; A.g = g ? d_g.get() : nullptr;
+  A.n_elites = n_elites; A.nominal = nominal; A.E = d_E; A.count = d_count;
+  MBD_TRY(elite_inject_launch(A, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(cand_out, d_cand, sizeof(float) * n, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+extern "C" int mbd_debug_elites_select(const float* rews, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy,
+                                       int n_elites, int nominal, int count_in, float* E_out, float* R_out, int32_t* src_out,
+                                       int32_t* count_out, int32_t* kept_out, float* top_out) {
+  MBD_TRY(check_elites_args("elites_select", cand, N, HNu, ybar, sigma, lazy, n_elites, nominal, nullptr, 0));
+  if (!rews) return fail(MBD_ERR_INVALID, "elites_select: NULL argument");
+  if (count_in < 0 || count_in > n_elites) return fail(MBD_ERR_INVALID, "elites_select: count=%d outside [0, n_elites=%d]", count_in, n_elites);
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  const size_t n = (size_t)N * HNu, k = (size_t)(n_elites > 0 ? n_elites : 1);
+  DevBuf<float> d_rews, d_cand, d_ybar, d_E, d_R, d_top;
+  DevBuf<int> d_src, d_count, d_lc, d_lk;
+  HIP_TRY(d_rews.alloc(N));
+  HIP_TRY(d_cand.alloc(n));
+  HIP_TRY(d_ybar.alloc(HNu));
+  HIP_TRY(d_E.alloc(k * HNu));
+  HIP_TRY(d_R.alloc(k));
+  HIP_TRY(d_src.alloc(k));
+  HIP_TRY(d_count.alloc(1));
+  HIP_TRY(d_lc.alloc(1));
+  HIP_TRY(d_lk.alloc(1));
+  HIP_TRY(d_top.alloc(1));
+  HIP_TRY(hipMemcpy(d_rews, rews, sizeof(float) * N, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_cand, cand, sizeof(float) * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_ybar, ybar, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_count, &count_in, sizeof(int), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(d_E, 0xff, sizeof(float) * k * HNu));
+  HIP_TRY(hipMemset(d_R, 0xff, sizeof(float) * k));
+  HIP_TRY(hipMemset(d_src, 0xff, sizeof(int) * k));
+  HIP_TRY(hipMemset(d_lc, 0xff, sizeof(int)));
+  HIP_TRY(hipMemset(d_lk, 0xff, sizeof(int)));
+  HIP_TRY(hipMemset(d_top, 0xff, sizeof(float)));
+  EliteSelect A{};
+  A.rews = d_rews; A.N = N; A.HNu = HNu; A.cand = d_cand; A.lazy = lazy ? 1 : 0; A.sigma = sigma; A.ybar_i = d_ybar;
+  A.n_elites = n_elites; A.nominal = nominal; A.E = d_E; A.R = d_R; A.src = d_src; A.count = d_count;
+  A.log_count = d_lc; A.log_kept = d_lk; A.log_top = d_top;
+  hipLaunchKernelGGL(elite_select_kernel, dim3(1), dim3(kScoreThreads), 0, nullptr, A);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  if (E_out && n_elites) HIP_TRY(hipMemcpy(E_out, d_E, sizeof(float) * (size_t)n_elites * HNu, hipMemcpyDeviceToHost));
+  if (R_out && n_elites) HIP_TRY(hipMemcpy(R_out, d_R, sizeof(float) * n_elites, hipMemcpyDeviceToHost));
+  if (src_out && n_elites) HIP_TRY(hipMemcpy(src_out, d_src, sizeof(int32_t) * n_elites, hipMemcpyDeviceToHost));
+  // (count' as the plan's word holds it; the log entry's copy must agree with it: the caller gets the log's, the word is checked)
+  int cnt_word = -1, cnt_log = -1;
+  HIP_TRY(hipMemcpy(&cnt_word, d_count, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&cnt_log, d_lc, sizeof(int), hipMemcpyDeviceToHost));
+  if (cnt_word != cnt_log) return fail(MBD_ERR_STATE, "elites_select: count word %d, log entry %d", cnt_word, cnt_log);
+  if (count_out) *count_out = cnt_word;
+  if (kept_out) HIP_TRY(hipMemcpy(kept_out, d_lk, sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (top_out) HIP_TRY(hipMemcpy(top_out, d_top, sizeof(float), hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
 // ---- one tick's planning, shared by the batch episode (mbd_plan_run_mpc) and the session (mbd_plan_mpc_submit) ------------------
 // The tick's keys, host arithmetic: rng, k_t = split(rng) advances the episode's chain; r = k_t is where the tick's own chain
 // starts (mbd_plan_run's from it); after = split(split(rng')[1])[1] is the Y0s_rng of tick t+1's first step, whose normals are
@@ -2348,6 +2650,9 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
   // shifted E rows forward with the mean; G under the caller's shape in force in this tick.  Stream order is the whole argument: it
   // stands behind the previous tick's last update and in front of this tick's first sampler, which reads G
   MBD_TRY(adapt_table(p, tk.cold || !p->adapt.carry ? -1 : tk.E * p->Nu, tk.cold ? shape_always(p) : shape_warm(p), s));
+  // with an elite record, ONE launch in the same place: no elites in a cold tick and without carry, otherwise the present ones
+  // shifted E rows forward with the mean
+  MBD_TRY(elite_table(p, tk.cold || !p->elite.carry ? -1 : tk.E * p->Nu, s));
   p->wt.begin();  // (a weighting record's log holds the last tick's steps)
   const float* cur = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros of a cold tick, shift_E(M_{t-1}) otherwise
   const float* last_in = cur;    // Ybar_i of the tick's last step
@@ -2470,6 +2775,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   } obj_episode{p->obj};
   MBD_TRY(p->pick.start(T));  // (a pick record's log: one entry per tick)
   p->adapt.count = 0;         // (an adapt record's log: the episode's steps)
+  p->elite.steps = 0;         // (an elite record's log likewise)
   if (pi) {  // sigma = sigma_cold and the log's first entry, by the kernel that carries sigma across the boundaries
     MBD_TRY(p->sigma_rec.start(T, 1));
     p->sigma_rec.launch(p->d_sigma, 1, 0, true, s);
@@ -2635,6 +2941,7 @@ extern "C" int mbd_plan_mpc_open(mbd_plan* p, const mbd_mpc_config* mc, const ui
   // (nothing fails from here on: a refused or failed open leaves the last episode's logs readable)
   if (p->delay.has) p->delay.pred_ticks = 0;  // (mbd_plan_peek_mpc_predicted does not serve sessions)
   p->adapt.count = 0;                         // (an adapt record's log: the session's steps)
+  p->elite.steps = 0;                         // (an elite record's log likewise)
   ss.mc = *mc;
   ss.rng[0] = key[0]; ss.rng[1] = key[1];
   ss.t = 0; ss.qbuf = 0; ss.flags = 0;
@@ -2740,6 +3047,10 @@ extern "C" int mbd_plan_mpc_reset_mean(mbd_plan* p) {
   if (p->adapt.has) {      // (an adapt record's table is all ones again: written now as well, so that mbd_plan_peek_adapt says so)
     HIP_TRY(hipSetDevice(p->env->device));
     MBD_TRY(adapt_table(p, -1, shape_always(p), p->stream));
+  }
+  if (p->elite.has) {  // (an elite record's elites are gone: written now as well, so that mbd_plan_peek_elites says so)
+    HIP_TRY(hipSetDevice(p->env->device));
+    MBD_TRY(elite_table(p, -1, p->stream));
   }
   if (p->cfg.update_method != 0) {  // (and starts from sigma_cold: written now as well, so that mbd_plan_get_sigma says so)
     HIP_TRY(hipSetDevice(p->env->device));

@@ -1975,4 +1975,205 @@ static __global__ __launch_bounds__(kAdaptThreads) void adapt_table_kernel(float
 }
 #endif  // MBD_ADAPT_KERNEL
 
+// ---- the elite record (mbd_plan_set_elites, include/mbd_hip.h mbd_elites; DESIGN.md section 1 "N18 elites"): a step's best
+// candidates are candidates of the next step, and the step's mean itself may be candidate 0.  Injection behind the step's sampler,
+// selection behind its update kernel, a shift at a tick boundary.  Last in this header under its own guard, for weigh_kernel's
+// reason: only mbd_plan.hip emits the kernels, behind the adapt kernels ----
+// The arithmetic of one element and the order are the functions below, host and device text: mbd_debug_elites_host loops them on
+// the CPU.  f32, every operation rounded.
+constexpr int kEliteMax = 32;
+// the normal that stands for an elite's element in a lazy plan: under a shape, a frozen element stays frozen
+MBD_HD float elite_z(float Ej, float yb, float sigma, const float* __restrict__ g, int e) {
+  return (g && g[e] == 0.0f) ? 0.0f : (Ej - yb) / sigma;
+}
+// the nominal's element: the normal +0 of a lazy plan, the clipped mean of a materialised one
+MBD_HD float elite_nominal(float yb, int lazy) { return lazy ? 0.0f : fclip(yb, -1.0f, 1.0f); }
+// a candidate's element as mbd_plan_peek forms it (pick_gather_kernel's)
+MBD_HD float elite_value(float x, int lazy, float sigma, float yb) { return lazy ? fclip(x * sigma + yb, -1.0f, 1.0f) : x; }
+// whether entry (x, i) can still be taken once (pv, pi) has been (pi < 0: nothing yet): finite, and strictly behind it in
+// pick_before's order
+MBD_HD bool elite_open(float x, int i, float pv, int pi) { return pick_finite(x) && (pi < 0 || pick_before(pv, pi, x, i)); }
+// the selection on the host: k rounds, each the first open entry in the order.  Returns count'
+static inline int elite_select_host(const float* r, int N, int k, int* src, float* R) {
+  float pv = 0.0f;
+  int pi = -1, cnt = 0;
+  for (int j = 0; j < k; ++j) {
+    float bv = 0.0f;
+    int bi = -1;
+    for (int i = 0; i < N; ++i)
+      if (elite_open(r[i], i, pv, pi) && pick_before(r[i], i, bv, bi)) {
+        bv = r[i];
+        bi = i;
+      }
+    if (bi < 0) break;
+    src[cnt] = bi;
+    R[cnt] = bv;
+    ++cnt;
+    pv = bv;
+    pi = bi;
+  }
+  return cnt;
+}
+struct EliteSelect {
+  const float* rews;    // [N] the rewards the step's score read
+  int N, HNu;
+  const float* cand;    // [N][HNu] the step's candidates, or their normals (lazy)
+  int lazy;
+  float sigma;          // lazy: sigma_i ...
+  const float* ybar_i;  // ... and Ybar_i [HNu] of the step
+  int n_elites, nominal;
+  float* E;             // [n_elites][HNu]
+  float* R;             // [n_elites]
+  int* src;             // [n_elites]
+  int* count;           // [1]: read (the step's slots), then rewritten
+  int* log_count;       // the step's log entry
+  int* log_kept;
+  float* log_top;
+};
+struct EliteInject {
+  float* cand;          // [N][HNu] the step's candidates, or their normals (lazy): rows 0 .. slots - 1 are rewritten
+  int HNu;
+  const float* ybar_i;  // [HNu]
+  int lazy;
+  float sigma;
+  const float* g;       // [HNu] the shape the step's sampler was handed, or nullptr
+  int n_elites, nominal;
+  const float* E;
+  const int* count;
+};
+#ifdef MBD_ELITE_KERNEL
+constexpr int kEliteRegs = 8, kEliteThreads = 256;
+// ONE 1024-thread workgroup: the n_elites best finite rewards in pick_before's order, then E', R', src', count' and the log entry.
+// Thread t owns the entries t, t + 1024, ...: the first kEliteRegs of them (8192 candidates) stay in registers, those beyond are
+// read again in every round.  Round j: every thread offers its best entry that is still open behind winner j - 1 (ascending i,
+// replaced on pick_before only), the wavefront's butterfly and the scan over the sixteen wavefronts' offers combine them as
+// pick_argmax_block does — a total order on distinct indices, so the combination order does not matter.  Every thread reads the
+// round's winner from the same LDS words: the loop's exit and the gather's rows are uniform.  The offers' LDS words alternate
+// between two sets, so a round costs ONE barrier: a thread that writes set b in round j + 2 has passed round j + 1's barrier, which
+// every thread reaches behind its reads of round j.
+// k rounds, not one sort of the sixteen wavefronts' top-k lists: a round is eight selects per thread, twelve cross-lane moves and
+// one barrier with sixteen broadcast LDS reads behind it, all on one dependent chain; the merge would keep 32 offers per lane live
+// or spill them.  Measured at N = 1024, HNu = 850 (docs/experiments.md section 28): 5.6 us at k = 1, 14.3 at k = 4, 95 at k = 32 —
+// 2.9 us per elite, the round and the row's gather together, each gather a dependent load and store.  Fine at the few elites
+// sampling MPC uses; at k = 32 it is a sixth of a humanoid step, and batching the gathers' loads is the first thing to try.
+// Bounds: rews[i] for i < N; cand rows win_i[j] < N; E rows j < count' <= n_elites.  Plain vector loads and stores.
+static __global__ __launch_bounds__(kScoreThreads) void elite_select_kernel(EliteSelect A) {
+  __shared__ float red_v[2][kScoreThreads / 64];
+  __shared__ int red_i[2][kScoreThreads / 64];
+  __shared__ float win_v[kEliteMax];
+  __shared__ int win_i[kEliteMax];
+  const int tid = threadIdx.x;
+  float rv[kEliteRegs];
+#pragma unroll
+  for (int q = 0; q < kEliteRegs; ++q) {
+    const int i = tid + q * kScoreThreads;
+    rv[q] = i < A.N ? A.rews[i] : __builtin_nanf("");  // (a NaN is never open)
+  }
+  float pv = 0.0f;
+  int pi = -1, cnt = 0;
+  for (int j = 0; j < A.n_elites; ++j) {
+    float bv = 0.0f;
+    int bi = -1;
+#pragma unroll
+    for (int q = 0; q < kEliteRegs; ++q) {
+      const int i = tid + q * kScoreThreads;
+      const bool take = elite_open(rv[q], i, pv, pi) && pick_before(rv[q], i, bv, bi);
+      bv = take ? rv[q] : bv;
+      bi = take ? i : bi;
+    }
+    for (int i = tid + kEliteRegs * kScoreThreads; i < A.N; i += kScoreThreads) {
+      const float x = A.rews[i];
+      const bool take = elite_open(x, i, pv, pi) && pick_before(x, i, bv, bi);
+      bv = take ? x : bv;
+      bi = take ? i : bi;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const float ov = __shfl_xor(bv, off, 64);
+      const int oi = __shfl_xor(bi, off, 64);
+      const bool take = pick_before(ov, oi, bv, bi);
+      bv = take ? ov : bv;
+      bi = take ? oi : bi;
+    }
+    const int b = j & 1;
+    if ((tid & 63) == 0) { red_v[b][tid >> 6] = bv; red_i[b][tid >> 6] = bi; }
+    __syncthreads();
+    bv = red_v[b][0];
+    bi = red_i[b][0];
+#pragma unroll
+    for (int w = 1; w < kScoreThreads / 64; ++w) {
+      const float ov = red_v[b][w];
+      const int oi = red_i[b][w];
+      const bool take = pick_before(ov, oi, bv, bi);
+      bv = take ? ov : bv;
+      bi = take ? oi : bi;
+    }
+    if (bi < 0) break;  // (no open entry is left: uniform)
+    if (tid == 0) { win_v[j] = bv; win_i[j] = bi; }
+    pv = bv;
+    pi = bi;
+    cnt = j + 1;
+  }
+  __syncthreads();
+  for (int j = 0; j < cnt; ++j) {
+    const float* __restrict__ row = A.cand + (size_t)win_i[j] * A.HNu;
+    float* __restrict__ out = A.E + (size_t)j * A.HNu;
+    for (int e = tid; e < A.HNu; e += kScoreThreads) out[e] = elite_value(row[e], A.lazy, A.sigma, A.ybar_i[e]);
+  }
+  if (tid == 0) {
+    const int slots = A.nominal + *A.count;
+    int kept = 0;
+    for (int j = 0; j < cnt; ++j) {
+      A.R[j] = win_v[j];
+      A.src[j] = win_i[j];
+      kept += win_i[j] < slots ? 1 : 0;
+    }
+    *A.count = cnt;
+    *A.log_count = cnt;
+    *A.log_kept = kept;
+    *A.log_top = cnt > 0 ? win_v[0] : __builtin_bit_cast(float, 0x7fc00000u);
+  }
+}
+// Behind the launch that made the step's normals (or candidates), in front of its rollout: rows 0 .. nominal + count - 1.  The grid
+// covers (nominal + n_elites) HNu elements; every thread loads count and a thread of an absent slot writes nothing.  Bounds: the
+// loaded count is held to [0, n_elites], and the set call refuses nominal + n_elites >= Nsample, so a written row lies below N.
+static __global__ __launch_bounds__(kEliteThreads) void elite_inject_kernel(EliteInject A) {
+  const int idx = blockIdx.x * kEliteThreads + threadIdx.x;
+  const int slot = idx / A.HNu, e = idx - slot * A.HNu;
+  int cnt = *A.count;
+  cnt = cnt < 0 ? 0 : (cnt > A.n_elites ? A.n_elites : cnt);
+  if (slot >= A.nominal + cnt) return;
+  const float yb = A.ybar_i[e];
+  float v;
+  if (slot < A.nominal) {
+    v = elite_nominal(yb, A.lazy);
+  } else {
+    const float Ej = A.E[(size_t)(slot - A.nominal) * A.HNu + e];
+    v = A.lazy ? elite_z(Ej, yb, A.sigma, A.g, e) : Ej;
+  }
+  A.cand[(size_t)slot * A.HNu + e] = v;
+}
+// The elites at the start of a run or a tick: shift < 0: count = 0; otherwise every present elite's row shifted `shift` elements
+// forward with zeros behind it (the mean's own shift), count as it is.  Workgroup j owns row j; the shift is in place, so a block of
+// 256 elements is read, then — behind a barrier — written: a later block reads only elements no earlier block wrote.  A workgroup
+// leaves as a whole (count is one word), so the barriers' trip count is uniform.
+static __global__ __launch_bounds__(kEliteThreads) void elite_shift_kernel(float* __restrict__ E, int* __restrict__ count, int HNu,
+                                                                    int shift) {
+  if (shift < 0) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count = 0;
+    return;
+  }
+  if ((int)blockIdx.x >= *count) return;
+  float* __restrict__ row = E + (size_t)blockIdx.x * HNu;
+  for (int base = 0; base < HNu; base += kEliteThreads) {
+    const int e = base + threadIdx.x;
+    float v = 0.0f;
+    if (e < HNu && e + shift < HNu) v = row[e + shift];
+    __syncthreads();
+    if (e < HNu) row[e] = v;
+    __syncthreads();
+  }
+}
+#endif  // MBD_ELITE_KERNEL
+
 }  // namespace mbd

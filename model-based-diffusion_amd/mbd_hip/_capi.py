@@ -119,6 +119,13 @@ class Adapt(C.Structure):
     _fields_ = [("rate", C.c_float), ("a_min", C.c_float), ("a_max", C.c_float), ("carry", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class Elites(C.Structure):
+    """mbd_elites (include/mbd_hip.h): how many of a step's best candidates the next step takes over, whether candidate 0 of every
+    step is the step's mean itself, and whether the elites are carried across tick boundaries."""
+    _fields_ = [("n_elites", C.c_int32), ("nominal", C.c_int32), ("carry", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+ELITES_MAX = 32
 PICK_MEAN, PICK_PREV, PICK_BEST = 1, 2, 4
 
 
@@ -162,7 +169,7 @@ EXPORTS = [
     "mbd_plan_set_weighting", "mbd_plan_peek_weighting", "mbd_sweep_set_weighting", "mbd_sweep_peek_weighting",
     "mbd_plan_set_mpc_pick", "mbd_plan_peek_mpc_pick", "mbd_sweep_set_mpc_pick", "mbd_sweep_peek_mpc_pick",
     "mbd_plan_set_value", "mbd_plan_peek_value", "mbd_plan_eval_value", "mbd_sweep_set_value",
-    "mbd_plan_set_adapt", "mbd_plan_peek_adapt",
+    "mbd_plan_set_adapt", "mbd_plan_peek_adapt", "mbd_plan_set_elites", "mbd_plan_peek_elites",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
@@ -258,6 +265,8 @@ def load() -> C.CDLL:
     lib.mbd_plan_eval_value.argtypes = [_vp, _vp, _i, _vp]
     lib.mbd_sweep_set_value.argtypes = [_vp, C.POINTER(Value)]
     lib.mbd_plan_set_adapt.argtypes = [_vp, C.POINTER(Adapt)]
+    lib.mbd_plan_set_elites.argtypes = [_vp, C.POINTER(Elites)]
+    lib.mbd_plan_peek_elites.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_plan_peek_adapt.argtypes = [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
     lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
@@ -550,6 +559,104 @@ def peek_adapt(fn, handle, HNu: int, capacity: int = None) -> dict:
     check(fn(handle, np_ptr(a), np_ptr(ratio), np_ptr(skipped), int(capacity), C.byref(n)))
     m = min(n.value, capacity)
     return {"a": a, "ratio": ratio[:m], "skipped": skipped[:m], "count": n.value}
+
+
+def elites_record(n_elites: int, nominal=False, carry=False) -> "Elites":
+    """The mbd_elites of ``Plan.set_elites``'s arguments."""
+    rec = Elites()
+    rec.n_elites, rec.nominal, rec.carry = int(n_elites), int(nominal), int(carry)
+    return rec
+
+
+def debug_check_elites(rec: "Elites", Nsample: int, update_method: int = 0, enable_demo: bool = False) -> int:
+    """include/mbd_hip_debug.h: the refusals an elite record alone decides for a plan of that Nsample, update_method and
+    enable_demo; the return code (the message: ``mbd_last_error``)."""
+    lib = load()
+    lib.mbd_debug_check_elites.argtypes = [C.POINTER(Elites), _i, _i, _i]
+    return lib.mbd_debug_check_elites(None if rec is None else C.byref(rec), int(Nsample), int(update_method), int(bool(enable_demo)))
+
+
+def _elites_arrays(cand, ybar, g, n_elites, E_in):
+    cand = np.ascontiguousarray(cand, np.float32)
+    cand = cand.reshape(cand.shape[0], -1)
+    N, HNu = cand.shape
+    ybar = np.ascontiguousarray(ybar, np.float32).reshape(HNu)
+    g = None if g is None else np.ascontiguousarray(g, np.float32).reshape(HNu)
+    E_in = np.zeros((0, HNu), np.float32) if E_in is None else np.ascontiguousarray(E_in, np.float32).reshape(-1, HNu)
+    return cand, N, HNu, ybar, g, E_in
+
+
+def _elites_outputs(n_elites, HNu):
+    k = max(int(n_elites), 1)
+    return (np.zeros((k, HNu), np.float32), np.zeros(k, np.float32), np.zeros(k, np.int32), np.full(1, -1, np.int32),
+            np.full(1, -1, np.int32), np.zeros(1, np.float32))
+
+
+def _elites_result(n_elites, outs, cand_out=None):
+    E, R, src, count, kept, top = outs
+    res = dict(E=E[:n_elites], R=R[:n_elites], src=src[:n_elites], count=int(count[0]), kept=int(kept[0]), top=top[0])
+    if cand_out is not None:
+        res["cand"] = cand_out
+    return res
+
+
+def debug_elites_host(rews, cand, ybar, sigma, lazy, g, n_elites, nominal, E_in=None):
+    """include/mbd_hip_debug.h: one step of an elite record on the host (no device) — the injection of ``E_in`` [count, HNu] (and the
+    nominal) into a copy of ``cand`` [N, HNu] (values, or with ``lazy`` normals), then the selection over ``rews`` [N].  Returns
+    dict(cand [N, HNu] behind the injection, E [n_elites, HNu], R, src [n_elites] — all bits set from ``count`` on —, count, kept,
+    top)."""
+    lib = load()
+    cand, N, HNu, ybar, g, E_in = _elites_arrays(cand, ybar, g, n_elites, E_in)
+    rews = np.ascontiguousarray(rews, np.float32).reshape(N)
+    outs = _elites_outputs(n_elites, HNu)
+    cand_out = np.zeros_like(cand)
+    lib.mbd_debug_elites_host.argtypes = [_vp, _vp, _i, _i, _vp, _f, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+    check(lib.mbd_debug_elites_host(np_ptr(rews), np_ptr(cand), N, HNu, np_ptr(ybar), float(sigma), int(bool(lazy)),
+                                    None if g is None else np_ptr(g), int(n_elites), int(nominal),
+                                    np_ptr(E_in) if E_in.shape[0] else None, int(E_in.shape[0]), np_ptr(cand_out),
+                                    *[np_ptr(o) for o in outs]))
+    return _elites_result(int(n_elites), outs, cand_out)
+
+
+def debug_elites_inject(cand, ybar, sigma, lazy, g, n_elites, nominal, E_in=None):
+    """elite_inject_kernel alone on the device over ``cand`` [N, HNu]: the candidates behind the injection."""
+    lib = load()
+    cand, N, HNu, ybar, g, E_in = _elites_arrays(cand, ybar, g, n_elites, E_in)
+    cand_out = np.zeros_like(cand)
+    lib.mbd_debug_elites_inject.argtypes = [_vp, _i, _i, _vp, _f, _i, _vp, _i, _i, _vp, _i, _vp]
+    check(lib.mbd_debug_elites_inject(np_ptr(cand), N, HNu, np_ptr(ybar), float(sigma), int(bool(lazy)),
+                                      None if g is None else np_ptr(g), int(n_elites), int(nominal),
+                                      np_ptr(E_in) if E_in.shape[0] else None, int(E_in.shape[0]), np_ptr(cand_out)))
+    return cand_out
+
+
+def debug_elites_select(rews, cand, ybar, sigma, lazy, n_elites, nominal, count_in=0):
+    """elite_select_kernel alone on the device over ``rews`` [N] and ``cand`` [N, HNu]; ``count_in``: the count word it finds.
+    Returns ``debug_elites_host``'s dict without ``cand``."""
+    lib = load()
+    cand, N, HNu, ybar, _, _ = _elites_arrays(cand, ybar, None, n_elites, None)
+    rews = np.ascontiguousarray(rews, np.float32).reshape(N)
+    outs = _elites_outputs(n_elites, HNu)
+    lib.mbd_debug_elites_select.argtypes = [_vp, _vp, _i, _i, _vp, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]
+    check(lib.mbd_debug_elites_select(np_ptr(rews), np_ptr(cand), N, HNu, np_ptr(ybar), float(sigma), int(bool(lazy)), int(n_elites),
+                                      int(nominal), int(count_in), *[np_ptr(o) for o in outs]))
+    return _elites_result(int(n_elites), outs)
+
+
+def peek_elites(fn, handle, n_elites: int, HNu: int, capacity: int = None) -> dict:
+    """mbd_plan_peek_elites: {'E' [count, HNu], 'R' [count], 'src' [count], 'count', 'log_count' / 'log_kept' / 'log_top' [n],
+    'steps'} — every step logged, or the most recent ``capacity``."""
+    n = C.c_int(0)
+    if capacity is None:
+        check(fn(handle, None, None, None, None, None, None, None, 0, C.byref(n)))
+        capacity = min(n.value, 65536)
+    k, cap = max(int(n_elites), 1), max(int(capacity), 1)
+    E, R, src, count = np.zeros((k, HNu), np.float32), np.zeros(k, np.float32), np.zeros(k, np.int32), np.zeros(1, np.int32)
+    lc, lk, lt = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.float32)
+    check(fn(handle, np_ptr(E), np_ptr(R), np_ptr(src), np_ptr(count), np_ptr(lc), np_ptr(lk), np_ptr(lt), int(capacity), C.byref(n)))
+    m, c = min(n.value, int(capacity)), int(count[0])
+    return {"E": E[:c], "R": R[:c], "src": src[:c], "count": c, "log_count": lc[:m], "log_kept": lk[:m], "log_top": lt[:m],
+            "steps": n.value}
 
 
 def pick_record(mean=True, prev=True, best=True) -> "MpcPick":

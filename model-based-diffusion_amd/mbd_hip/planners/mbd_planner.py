@@ -825,6 +825,33 @@ class Plan:
         out["a"] = out["a"].reshape(self.H, self.Nu)
         return out
 
+    def set_elites(self, n_elites: int, nominal=False, carry=False):
+        """Carry a step's best candidates into the next step (include/mbd_hip.h mbd_elites): the ``n_elites`` best candidates of
+        every diffusion step (0 to 32, by the rewards its score read) overwrite the next step's first candidates; ``nominal``:
+        candidate 0 of every step is the step's mean itself, noise-free; ``carry``: a tick boundary shifts the elites with the mean
+        (False: every tick starts without elites).  MBD and mppi plans, unsharded, without ``enable_demo``."""
+        rec = _capi.elites_record(n_elites, nominal, carry)
+        _capi.check(self.lib.mbd_plan_set_elites(self.h, C.byref(rec)))
+        self._elites = int(n_elites)
+
+    def clear_elites(self):
+        _capi.check(self.lib.mbd_plan_set_elites(self.h, None))
+        self._elites = None
+
+    @property
+    def has_elites(self) -> bool:
+        return getattr(self, "_elites", None) is not None
+
+    def peek_elites(self, capacity: int = None) -> dict:
+        """``E`` [count, H, Nu], ``R`` and ``src`` [count]: the elites as they stand; ``log_count`` / ``log_kept`` / ``log_top``: per
+        step since the last ``run``, episode or session began — or the most recent ``capacity`` of them — how many elites the step
+        selected, how many of them were candidates it had injected, and the best return (a plan with an elite record)."""
+        if not self.has_elites:
+            _capi.check(self.lib.mbd_plan_peek_elites(self.h, None, None, None, None, None, None, None, 0, None))
+        out = _capi.peek_elites(self.lib.mbd_plan_peek_elites, self.h, self._elites or 0, self.H * self.Nu, capacity)
+        out["E"] = out["E"].reshape(-1, self.H, self.Nu)
+        return out
+
     def peek_objective(self):
         """The last step's ``ret`` [shard_count] ([M, N] under an ensemble record) and ``cost`` [shard_count] (a plan with an
         objective record)."""

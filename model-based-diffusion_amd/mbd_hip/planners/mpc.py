@@ -102,6 +102,16 @@ the log of its steps; the report ``adapt_table_min`` / ``adapt_table_max`` and `
 
     python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --adapt_rate 0.3 --adapt_carry
 
+Every step draws its candidates afresh and keeps only their weighted mean.  An elite record (include/mbd_hip.h mbd_elites; DESIGN.md
+section 1 "N18 elites") carries candidates over: ``--elites K`` (0 to 32) makes the K best candidates of every diffusion step
+candidates of the next one, ``--elite_nominal`` makes candidate 0 of every step the step's mean itself, noise-free, and
+``--elite_carry`` shifts the elites across a tick boundary with the mean (otherwise every tick starts without elites).  MBD and mppi
+plans, single episodes; ``--online`` honours it.  The details gain ``elite_log`` = dict(E, R, src, count, log_count, log_kept,
+log_top, steps): the elites behind the episode and the log of its steps; the report ``elites_kept`` and ``elites_top``, per tick the number of
+selected candidates that had been injected (summed over the tick's steps) and the best return of the tick's last step.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --elites 4 --elite_nominal --elite_carry
+
 A demo plan (``--enable_demo``) compares its 50 planned steps with the env's 50 demo rows; in an episode the demo has to move
 with the system.  ``--demo_clip env|FILE.npy`` (include/mbd_hip.h mbd_mpc_demo; DESIGN.md section 1 "N10 demo clock") sets the
 clip the episode follows — the env's own demo, or an array [n_track, L, 3] (car2d: [L, 2]) — and ``--demo_start c0`` the clip
@@ -201,6 +211,9 @@ class MpcArgs(Args):
     adapt_min: float = 0.25  # ... every entry within [adapt_min, adapt_max];
     adapt_max: float = 4.0
     adapt_carry: bool = False  # the table is shifted across a tick boundary with the mean (default: every tick starts from ones)
+    elites: int = 0  # K > 0: an elite record (mbd_elites) — the K best candidates of a step are candidates of the next one ...
+    elite_nominal: bool = False  # ... candidate 0 of every step is the step's mean itself (with --elites 0: the record is this alone)
+    elite_carry: bool = False  # ... and a tick boundary shifts the elites with the mean (default: every tick starts without elites)
 
 
 def _has_value(args: MpcArgs) -> bool:
@@ -424,6 +437,29 @@ def _adapt_log(log: dict) -> dict:
                 adapt_steps_skipped=int(np.sum(log["skipped"])))
 
 
+def _has_elites(args: MpcArgs) -> bool:
+    """Whether the arguments ask for an elite record at all (elites, or the nominal)."""
+    return args.elites != 0 or bool(args.elite_nominal)
+
+
+def _elites_of(args: MpcArgs) -> dict:
+    """``Plan.set_elites``'s arguments."""
+    return dict(n_elites=args.elites, nominal=bool(args.elite_nominal), carry=bool(args.elite_carry))
+
+
+def _elites_settings(args: MpcArgs) -> dict:
+    return dict(elites=args.elites, elite_nominal=bool(args.elite_nominal), elite_carry=bool(args.elite_carry)) if _has_elites(args) else {}
+
+
+def _elites_log(log: dict, Nd: int, K: int) -> dict:
+    """A peeked step log as the report's two lists, one entry per tick: tick 0 ran Nd - 1 steps, every other tick K."""
+    n = len(log["log_kept"])
+    cuts = [0] + [min(c, n) for c in range(Nd - 1, n + K, K)] if n else [0]
+    kept = [int(np.sum(log["log_kept"][a:b])) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+    top = [float(log["log_top"][b - 1]) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
+    return dict(elites_kept=kept, elites_top=top)
+
+
 _PICK_NAMES = ("mean", "prev", "best")
 
 
@@ -612,6 +648,8 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
         plan.set_value(*_value_of(args))
     if _has_adapt(args):
         plan.set_adapt(**_adapt_of(args))
+    if _has_elites(args):
+        plan.set_elites(**_elites_of(args))
     return env, plan, state_init, rng_exp
 
 
@@ -649,6 +687,7 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
             predicted.append(out["predicted"])
             secs.append(out["seconds"])
         adapt = plan.peek_adapt() if _has_adapt(args) else None  # (the table behind the last tick, the log of the session's steps)
+        elites = plan.peek_elites() if _has_elites(args) else None
     ep = dict(actions=np.concatenate(actions), rewards=np.concatenate(rewards), states=np.stack(states), means=np.stack(means),
               seconds=float(np.sum(secs)), tick_seconds=np.asarray(secs, np.float64))
     if plan._has_delay:
@@ -658,6 +697,8 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
                                kept=np.array([w[2] for w in wlog], np.int32))
     if adapt is not None:
         ep["adapt"] = adapt
+    if elites is not None:
+        ep["elite_log"] = elites
     if plog:
         ep["pick"] = dict(choice=np.array([x["choice"] for x in plog], np.int32), rets=np.stack([x["rets"] for x in plog]),
                           best=np.array([x["best"] for x in plog], np.int32))
@@ -691,6 +732,9 @@ def _check_batch(arg_list) -> None:
     if not 1 <= len(arg_list) <= MAX_EPISODES:
         raise ValueError(f"{len(arg_list)} episodes: a batch holds 1 to {MAX_EPISODES}")
     for k, a in enumerate(arg_list):
+        if _has_elites(a):
+            raise ValueError(f"episode {k} carries elites={a.elites!r} / elite_nominal={a.elite_nominal!r}: sweeps take no elite "
+                             "record; run the episodes one by one (run_mpc)")
         if _has_adapt(a):
             raise ValueError(f"episode {k} carries adapt_rate={a.adapt_rate!r}: sweeps take no adapt record (their samplers take one "
                              "shape for all plans); run the episodes one by one (run_mpc)")
@@ -809,6 +853,8 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
             ep["weighting_last_tick"] = plan.peek_weighting()
         if _has_adapt(args):  # (the table behind the last tick and the log of the episode's steps)
             ep["adapt"] = plan.peek_adapt()
+        if _has_elites(args):  # (the elites behind the last tick and the log of the episode's steps)
+            ep["elite_log"] = plan.peek_elites()
     finally:
         plan.close()
     reward = float(ep["rewards"].mean())
@@ -820,7 +866,7 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         if _has_basis(args):
             shape = dict(shape, **_basis_settings(args))
         shape = dict(shape, **_delay_settings(args), **_demo_settings(args), **_sigma_settings(args), **_objective_settings(args),
-                     **_weighting_settings(args), **_adapt_settings(args))
+                     **_weighting_settings(args), **_adapt_settings(args), **_elites_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -866,6 +912,7 @@ def _main(argv=None) -> dict:
         ep = plan.run_mpc(key, T, K, E)
         wlog = plan.peek_weighting() if _has_weighting(args) else None
         alog = plan.peek_adapt() if _has_adapt(args) else None
+        elog = plan.peek_elites() if _has_elites(args) else None
         nominal = None
         if _has_plant(args):  # what the perturbation cost: the same episode without the record
             plan.clear_mpc_plant()
@@ -901,6 +948,8 @@ def _main(argv=None) -> dict:
     res.update(_value_settings(args))  # (without --value the line is what it always was)
     if alog is not None:
         res.update(_adapt_settings(args), **_adapt_log(alog))
+    if elog is not None:
+        res.update(_elites_settings(args), **_elites_log(elog, args.Ndiffuse, K))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -940,6 +989,8 @@ def _main_online(args: MpcArgs) -> dict:
     res.update(_value_settings(args))  # (without --value the line is what it always was)
     if "adapt" in ep:
         res.update(_adapt_settings(args), **_adapt_log(ep["adapt"]))
+    if "elite_log" in ep:
+        res.update(_elites_settings(args), **_elites_log(ep["elite_log"], args.Ndiffuse, args.warm_steps))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
