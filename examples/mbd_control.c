@@ -2,7 +2,7 @@
  * session (mbd_plan_mpc_open) is opened once and advanced one tick per call from the state the caller's system is in.
  *
  *   gcc -O2 -I include examples/mbd_control.c -o mbd_control -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
- *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi] [--pick] [--value] [--elites]
+ *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi] [--pick] [--value] [--elites] [--togo]
  *                 env    N   H  Nd K ticks
  *
  * The "system" here is a second env the example owns, stepped with mbd_env_step — the env's rollout kernel at B = 1, H = 1 through
@@ -35,6 +35,10 @@
  * of the next one, candidate 0 of every step is the step's mean itself, and a tick boundary shifts the elites with the mean; the
  * tick's line gains "kept K top R": how many of the last step's elites had been injected, and the best return it saw.
  *
+ * --togo (among the trailing flags): a to-go record (mbd_togo) — the horizon's rows in groups of five, each group updated under
+ * weights from the candidates' mean reward from the group's first row onwards, no group starting with fewer than five rows ahead;
+ * not beside --rate_cost or --value (the library refuses the pair).  The tick's line gains "groups G".
+ *
  * Prints one line per tick: "tick T reward R ms M flags F", then "mean_reward R ms_per_tick M". */
 #include <math.h>
 #include <stdio.h>
@@ -60,12 +64,14 @@ static int plant_step(mbd_env* plant, float* state, const float* action, float* 
 }
 
 int main(int argc, char** argv) {
-  int mppi = 0, pick = 0, value = 0, elites = 0;
+  int mppi = 0, pick = 0, value = 0, elites = 0, togo = 0;
   while (argc > 1 && (strcmp(argv[argc - 1], "--mppi") == 0 || strcmp(argv[argc - 1], "--pick") == 0 ||
-                      strcmp(argv[argc - 1], "--value") == 0 || strcmp(argv[argc - 1], "--elites") == 0)) { /* trailing flags */
+                      strcmp(argv[argc - 1], "--value") == 0 || strcmp(argv[argc - 1], "--elites") == 0 ||
+                      strcmp(argv[argc - 1], "--togo") == 0)) { /* trailing flags */
     if (strcmp(argv[argc - 1], "--mppi") == 0) mppi = 1;
     else if (strcmp(argv[argc - 1], "--pick") == 0) pick = 1;
     else if (strcmp(argv[argc - 1], "--elites") == 0) elites = 1;
+    else if (strcmp(argv[argc - 1], "--togo") == 0) togo = 1;
     else value = 1;
     argc -= 1;
   }
@@ -146,6 +152,12 @@ int main(int argc, char** argv) {
     el.n_elites = 4; el.nominal = 1; el.carry = 1;
     CHECK(mbd_plan_set_elites(plan, &el));
   }
+  if (togo) { /* weigh a row by the return still ahead of it: groups of five rows, the last one at least five long */
+    mbd_togo tg;
+    memset(&tg, 0, sizeof(tg));
+    tg.block = 5; tg.min_tail = H < 5 ? H : 5;
+    CHECK(mbd_plan_set_togo(plan, &tg));
+  }
   if (D > 0) { /* plans arrive D ticks late; the system starts committed to zeros */
     mbd_mpc_delay delay;
     memset(&delay, 0, sizeof(delay));
@@ -189,6 +201,11 @@ int main(int argc, char** argv) {
       float top = 0.0f;
       CHECK(mbd_plan_peek_elites(plan, NULL, NULL, NULL, NULL, NULL, &kept, &top, 1, NULL)); /* (the most recent step's entry) */
       printf(" kept %d top %.9g", (int)kept, top);
+    }
+    if (togo) {
+      int32_t groups = 0;
+      CHECK(mbd_plan_peek_togo(plan, NULL, NULL, NULL, &groups));
+      printf(" groups %d", (int)groups);
     }
     printf("\n");
     reward_sum += reward;

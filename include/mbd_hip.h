@@ -960,6 +960,50 @@ int mbd_plan_set_elites(mbd_plan* plan, const mbd_elites* rec);
 int mbd_plan_peek_elites(mbd_plan* plan, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
                          int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out);
 
+/* ---- to-go: a horizon row is weighed by the return still ahead of it (the to-go return of PI^2, Theodorou, Buchli and Schaal 2010;
+ * MPPI is PI^2 with this switched off; no counterpart in the reference, whose one weight per candidate multiplies all its rows;
+ * DESIGN.md section 1 "N19 to-go") ---- */
+/* A to-go record is a setting of a plan beside the adapt and elite records.  The horizon's rows fall into G groups of `block` rows,
+ * and the rows of group j are what the step's ordinary update would give if the candidates' rewards were R_j, their mean reward from
+ * the group's first row onwards.  No rollout kernel, sampler or launch choice changes: the rollouts already store rewss [N][H]. */
+typedef struct mbd_togo {
+  int32_t block;     /* >= 1: rows per group                                                            */
+  int32_t min_tail;  /* 1..Hsample: a group starts only where at least this many rows are still ahead   */
+  int32_t reserved[2];  /* must be 0 */
+} mbd_togo;
+/* The contract — f32 throughout, every operation rounded, no contraction.  H = Hsample, N = Nsample.
+ * GROUPS.  The starts are s_0 = 0 and s_j = j * block for every j >= 1 with s_j < H and H - s_j >= min_tail; G is their number.
+ * Group j owns rows [s_j, s_{j+1}), the last group [s_{G-1}, H).  block >= H or min_tail == H gives G = 1.
+ * RETURNS.  R_0[n] = rews[n], the very array the step's score reads.  For the other groups one descending pass per candidate:
+ *   acc = +0;  for t = H-1 down to s_1:  acc = acc + rewss[n][t];  whenever t is a start s_j (j >= 1):  R_j[n] = acc / float(H - s_j)
+ * with rewss the rewards of the step's rollout.  Nothing is skipped: a NaN in step t reaches exactly the groups with s_j <= t, and
+ * group 0 through rews.
+ * UPDATE.  For every group j and every element e = (h, a) with h in group j, Ybar_{i-1}[e] is element e of the step's ordinary
+ * update computed from R_j in place of rews: the score's standardisation and softmax with temp_sample and the std guard of MBD (none
+ * for mppi), the wsum64 chain of the weighted mean over candidate values formed as today — clip((z * sigma_i) + Ybar_i, -1, 1) for
+ * lazy plans, the stored value for materialised ones —, and the literal or identity score update.
+ * UNCHANGED.  Everything else the update stores keeps its meaning and its bits: the step's mean reward is rews' mean in the score's
+ * order, the weights mbd_plan_peek returns are group 0's, and the rows of group 0 are the rows of the plan without a record for the
+ * same inputs.  G = 1 is no record, bit for bit.  Elite selection and a pick record keep reading rews.
+ * A step's candidates do not depend on the previous result beyond what the mean already does: the noise prefetch stays.  With a
+ * record a step launches two kernels (the returns, then score and weighted mean per group) where it launches one; without a record
+ * every call keeps its launches and its bits.
+ * Scope: MBD and mppi plans (update_method 0 and 1), rigid-body envs and car2d, lazy and materialised candidates; mbd_plan_run, the
+ * unsharded phase calls, mbd_plan_reverse_once, mbd_plan_run_mpc and sessions; beside plant, delay, sigma, noise-shape, noise-basis,
+ * pick and elite records.  Sweeps have no such call.
+ * The set call is synchronous (it waits for the device) and is to be called between diffusion steps; rec == NULL clears.  Refused
+ * before any device access, the message naming the field or the record — MBD_ERR_INVALID: a NULL handle, block < 1, min_tail outside
+ * [1, Hsample], non-zero reserved; MBD_ERR_UNSUPPORTED: update_method 2 or 3, a plan created with enable_demo, Nsample > 12288 (the
+ * weights must fit LDS), a plan holding an objective, value, weighting, adapt or ensemble record (their per-row meaning is not
+ * defined here; their set calls refuse a plan holding a to-go record in turn); MBD_ERR_STATE: a sharded plan, a session open on the
+ * handle. */
+int mbd_plan_set_togo(mbd_plan* plan, const mbd_togo* rec);
+/* The last step's values (HOST; any output may be NULL; synchronises the device): starts_out [G] the groups' first rows, R_out and
+ * W_out [G][Nsample] the groups' returns and weights (row 0: rews and the plan's weights), *n_groups_out = G.  The caller's arrays
+ * hold G <= Hsample rows.  Before the record's first step R and W are all-ones bits (NaN).  MBD_ERR_STATE without a record;
+ * MBD_ERR_INVALID: a NULL handle. */
+int mbd_plan_peek_togo(mbd_plan* plan, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out);
+
 /* ---- planning ahead of the plant: an episode whose plans take D ticks to arrive (the real-time iteration scheme; no
  * counterpart in the reference; DESIGN.md section 1 "N9 delay") ---- */
 /* The episode of mbd_plan_run_mpc plans from s_t and executes that plan's first rows from the same s_t: planning takes no time.

@@ -141,6 +141,23 @@ int mbd_debug_elites_inject(const float* cand, int N, int HNu, const float* ybar
 int mbd_debug_elites_select(const float* rews, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy,
                             int n_elites, int nominal, int count_in, float* E_out, float* R_out, int32_t* src_out, int32_t* count_out,
                             int32_t* kept_out, float* top_out);
+/* The refusals a to-go record alone decides (include/mbd_hip.h mbd_togo) for a plan of that Hsample, Nsample, update_method and
+ * enable_demo: the function the set call runs on its record, host arithmetic, no device. */
+int mbd_debug_check_togo(const mbd_togo* rec, int Hsample, int Nsample, int update_method, int enable_demo);
+/* A to-go record's group layout and returns on the HOST: the functions the returns kernel calls (one text for host and device)
+ * looped over the candidates on the CPU; no device touched.  HOST rews [N], rewss [N][H]; starts_out [G] (room for H entries),
+ * R_out [G][N] (room for H rows; row 0 = rews), *n_groups_out = G; any output may be NULL, and rews / rewss may be NULL when R_out
+ * is.  block and min_tail are checked as the set call checks them; N * H <= 2^26. */
+int mbd_debug_togo_host(const float* rews, const float* rewss, int N, int H, int block, int min_tail, int32_t* starts_out,
+                        float* R_out, int32_t* n_groups_out);
+/* The step's two launches alone on the DEVICE, on caller-given arrays: togo_returns_kernel, then togo_update_kernel.  HOST cand
+ * [N][H * Nu] — values, or with lazy != 0 normals formed as clip((z * sigma) + ybar[e], -1, 1) —, ybar [H * Nu] Ybar_i, rews [N],
+ * rewss [N][H]; std_guard != 0: MBD's guard of the standard deviation (0: mppi); literal as mbd_plan_config's literal_score.
+ * ybar_out [H * Nu] Ybar_{i-1}, R_out and W_out [G][N], rew_mean_out: one value; any may be NULL.  What is read back is filled with
+ * quiet NaN first.  Argument errors first (NULL inputs, sizes, block, min_tail, N > 12288), then MBD_ERR_NO_DEVICE. */
+int mbd_debug_togo_step(const float* cand, const float* ybar, const float* rews, const float* rewss, int N, int H, int Nu, int block,
+                        int min_tail, int lazy, float sigma, float temp, int std_guard, float alpha_i, float alpha_bar_i,
+                        float alpha_bar_im1, int literal, float* ybar_out, float* R_out, float* W_out, float* rew_mean_out);
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@
 #define MBD_VALUE_KERNEL 1  // ... and the value record's
 #define MBD_ADAPT_KERNEL 1  // ... and the adapt record's (plans only)
 #define MBD_ELITE_KERNEL 1  // ... and the elite record's (plans only)
+#define MBD_TOGO_KERNEL 1   // ... and the to-go record's (plans only)
 #include "mbd_internal.h"
 #include "../../include/mbd_hip_debug.h"
 
@@ -155,6 +156,17 @@ struct EliteRec {
   DevBuf<int> d_src, d_count, d_log_count, d_log_kept;
 };
 
+// The to-go record of a plan (include/mbd_hip.h mbd_togo) as the handle keeps it: the record, the layout it gives at the plan's
+// Hsample — G groups, group j's first row starts[j] = j block —, and the last step's returns and weights R, W [G][N] (row 0 of W is
+// never written: group 0's weights are the plan's d_weights).  All zero: no record (a zeroed stand-in handle has none).
+struct TogoRec {
+  bool has = false;
+  int block = 0, min_tail = 0, G = 0;
+  bool stepped = false;  // a step of the record has run: d_weights are group 0's
+  std::vector<int32_t> starts;
+  DevBuf<float> d_R, d_W;
+};
+
 struct mbd_plan {
   mbd_env* env = nullptr;
   hipStream_t last_stream = nullptr;  // stream of the plan's previous phase call (plan_enter orders a change of stream)
@@ -228,6 +240,8 @@ struct mbd_plan {
   AdaptRec adapt;
   // the elite record (mbd_plan_set_elites) with the elites, their count on the device and the device log of its steps
   EliteRec elite;
+  // the to-go record (mbd_plan_set_togo) with the groups' returns and weights of the last step
+  TogoRec togo;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_plan_mpc_open); it uses the episodes' buffers above — d_mpc_state for the
   // state handed in, d_mpc_pred for the one predicted state, d_mpc_queue — so a handle runs episodes or a session, not both
@@ -473,6 +487,29 @@ static int elite_select(mbd_plan* p, int i, const float* d_Ybar_i, const float* 
   A.ybar_i = d_Ybar_i; A.n_elites = L.n; A.nominal = L.nominal; A.E = L.d_E; A.R = L.d_R; A.src = L.d_src; A.count = L.d_count;
   A.log_count = L.d_log_count.get() + slot; A.log_kept = L.d_log_kept.get() + slot; A.log_top = L.d_log_top.get() + slot;
   hipLaunchKernelGGL(elite_select_kernel, dim3(1), dim3(kScoreThreads), 0, s, A);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+
+// ---- the to-go record's launches (include/mbd_hip.h mbd_togo; set, peek and the debug entries: below) ------------------------
+// the layout a record gives at horizon H
+static void togo_layout(TogoRec& L, int block, int min_tail, int H) {
+  L.block = block; L.min_tail = min_tail;
+  L.G = togo_groups(H, block, min_tail);
+  L.starts.resize(L.G);
+  for (int j = 0; j < L.G; ++j) L.starts[j] = togo_start(j, block);
+}
+// A step's two launches on caller-given arrays (a plan's step: plan_score_update; mbd_debug_togo_step): A carries everything but
+// the layout and the record's buffers.  Groups 0 .. G - 2 hold block Nu elements in tpg tiles each, the last group the rest.
+static int togo_launch(TogoRec& L, const float* d_rewss, TogoUpdate A, hipStream_t s) {
+  const TogoReturns Rt{A.rews, d_rewss, L.d_R.get(), A.N, A.H, L.block, L.G};
+  hipLaunchKernelGGL(togo_returns_kernel, dim3((A.N + kTogoThreads - 1) / kTogoThreads), dim3(kTogoThreads), 0, s, Rt);
+  HIP_TRY(hipGetLastError());
+  const long long last = (long long)(A.H - togo_start(L.G - 1, L.block)) * A.Nu;
+  A.R = L.d_R; A.W = L.d_W; A.G = L.G; A.block = L.block;
+  A.tpg = L.G > 1 ? (int)(((long long)L.block * A.Nu + kWmE - 1) / kWmE) : 1;
+  A.T = (L.G - 1) * A.tpg + (int)((last + kWmE - 1) / kWmE);
+  hipLaunchKernelGGL(togo_update_kernel, dim3(A.T), dim3(kWmE * kWmG), sizeof(float) * (size_t)A.N, s, A);
   HIP_TRY(hipGetLastError());
   return MBD_OK;
 }
@@ -780,7 +817,17 @@ static int plan_score_update(mbd_plan* p, int i, const float* d_Ybar_i, const fl
     hipLaunchKernelGGL(cem_mean_kernel, ge, b64, 0, s, p->d_idx, K, p->d_Y0s, HNu, d_Ybar_im1, PiBatch{});
   } else {  // MBD (:128-133), mppi (:33-36), cma-es (:39-45)
     const int lit = c.update_method == 0 ? c.literal_score : 0;
-    if (fused_score) {
+    if (p->togo.has) {
+      // The to-go record: TWO launches stand where the fused launch stands — the groups' returns from the rewards per step the
+      // step's rollout left in d_rewss, then score and weighted mean per group (mbd_step_kernels.h togo_update_kernel)
+      TogoUpdate A{};
+      A.rews = d_rews_all; A.weights = p->d_weights; A.rew_mean = d_rew_mean; A.cand = d_cand; A.ybar_i = d_Ybar_i;
+      A.ybar_im1 = d_Ybar_im1; A.ybar_keep = p->d_ybar_keep; A.N = N; A.H = c.Hsample; A.Nu = p->Nu; A.temp = c.temp_sample;
+      A.std_guard = c.update_method == 0 ? 1 : 0; A.alpha_i = p->alphas[i]; A.alpha_bar_i = p->alphas_bar[i];
+      A.alpha_bar_im1 = p->alphas_bar[i - 1]; A.literal = lit; A.lazy = lazy; A.sigma = sigma_i;
+      MBD_TRY(togo_launch(p->togo, p->d_rewss, A, s));
+      p->togo.stepped = true;
+    } else if (fused_score) {
       // XCD pinning (mbd_step_kernels.h pinned_tile): the T tiles on the fewest XCDs X in {1, 2, 4, 8} that give every tile
       // a CU of its own (32 per XCD) and keep an XCD's share of the candidates' rows within its 4 MB L2; the launch is
       // 8 ceil(T / X) workgroups long, those of the other XCDs leave at once.  MBD_WMEAN_XCDS = 1 / 2 / 4 / 8 forces X.
@@ -1520,6 +1567,9 @@ extern "C" int mbd_plan_set_ensemble(mbd_plan* p, const mbd_ensemble* rec) {
     p->ens_rec = mbd_ensemble{};
     return MBD_OK;
   }
+  if (p->togo.has)  // (before check_ensemble, which may read the members' reference from the device)
+    return fail(MBD_ERR_UNSUPPORTED, "ensemble: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
+                                     "row is not defined");
   MBD_TRY(check_ensemble(p, rec));
   if (p->pick.has)
     return fail(MBD_ERR_UNSUPPORTED, "ensemble: the plan carries a pick record (mbd_plan_set_mpc_pick): the pick compares returns, an "
@@ -1722,6 +1772,9 @@ extern "C" int mbd_plan_set_objective(mbd_plan* p, const mbd_objective* rec) {
   NO_SESSION(p, "set_objective");
   float wsum = 0.0f;
   if (rec) MBD_TRY(check_objective(rec, p->cfg.Hsample, p->Nu, &wsum));  // (before any device access)
+  if (rec && p->togo.has)
+    return fail(MBD_ERR_UNSUPPORTED, "objective record: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
+                                     "row is not defined");
   return p->obj.set(rec, wsum, p->env->device, 1, p->cfg.Nsample, p->cfg.Hsample, p->Nu, (size_t)MBD_MAX_ENSEMBLE * p->cfg.Nsample);
 }
 
@@ -1900,6 +1953,9 @@ extern "C" int mbd_plan_set_value(mbd_plan* p, const mbd_value* rec) {
   if (rec) MBD_TRY(check_value(rec, p->env->state_size(), p->env->kind == ENV_MODEL));  // (before any device access)
   if (rec && p->has_ens)
     return fail(MBD_ERR_STATE, "value record: the plan carries an ensemble record (an ensemble launch returns rewards only)");
+  if (rec && p->togo.has)
+    return fail(MBD_ERR_UNSUPPORTED, "value record: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
+                                     "row is not defined");
   return p->val.set(rec, p->env, (size_t)p->cfg.shard_count, 1);
 }
 
@@ -2063,6 +2119,9 @@ extern "C" int mbd_plan_set_weighting(mbd_plan* p, const mbd_weighting* rec) {
   if (rec) MBD_TRY(check_weighting(rec));  // (before any device access)
   if (rec && p->cfg.enable_demo)
     return fail(MBD_ERR_UNSUPPORTED, "weighting record: enable_demo=1: the demo blend standardises twice, an ESS target is not defined there");
+  if (rec && p->togo.has)
+    return fail(MBD_ERR_UNSUPPORTED, "weighting record: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
+                                     "row is not defined");
   return p->wt.set(rec, p->env->device, 1, p->cfg.Ndiffuse - 1, p->cfg.Nsample);
 }
 
@@ -2238,6 +2297,9 @@ extern "C" int mbd_plan_set_adapt(mbd_plan* p, const mbd_adapt* rec) {
     return fail(MBD_ERR_STATE, "adapt record: shard_count=%d of Nsample=%d: sharded plans take no adapt record", p->cfg.shard_count,
                 p->cfg.Nsample);
   NO_SESSION(p, "set_adapt");
+  if (rec && p->togo.has)
+    return fail(MBD_ERR_UNSUPPORTED, "adapt record: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
+                                     "row is not defined");
   AdaptRec& A = p->adapt;
   if (!rec && !A.has) return MBD_OK;  // (nothing to clear: no device is touched)
   HIP_TRY(hipSetDevice(p->env->device));
@@ -2601,6 +2663,148 @@ extern "C" int mbd_debug_elites_select(const float* rews, const float* cand, int
   if (count_out) *count_out = cnt_word;
   if (kept_out) HIP_TRY(hipMemcpy(kept_out, d_lk, sizeof(int32_t), hipMemcpyDeviceToHost));
   if (top_out) HIP_TRY(hipMemcpy(top_out, d_top, sizeof(float), hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
+// ---- the to-go record (include/mbd_hip.h mbd_togo) ---------------------------------------------------------------------------
+// the refusals the record alone decides against the handle's Hsample, Nsample, update_method and enable_demo, in the header's order,
+// each naming the field — host arithmetic, before any device access
+constexpr int kTogoMaxN = 12288;  // the N weights of a group in the default 48 KB LDS window
+static int check_togo(const mbd_togo* rec, int Hsample, int Nsample, int update_method, int enable_demo) {
+  if (rec->block < 1) return fail(MBD_ERR_INVALID, "to-go record: block=%d: at least 1", rec->block);
+  if (rec->min_tail < 1 || rec->min_tail > Hsample)
+    return fail(MBD_ERR_INVALID, "to-go record: min_tail=%d outside [1, Hsample=%d]", rec->min_tail, Hsample);
+  for (int r = 0; r < 2; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "to-go record: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  if (update_method == 2 || update_method == 3)
+    return fail(MBD_ERR_UNSUPPORTED, "to-go record: update_method=%d: cma-es (2) and cem (3) have no per-row form here", update_method);
+  if (enable_demo) return fail(MBD_ERR_UNSUPPORTED, "to-go record: enable_demo=1: a demo plan's score is not the return");
+  if (Nsample > kTogoMaxN)
+    return fail(MBD_ERR_UNSUPPORTED, "to-go record: Nsample=%d above %d: a group's weights must fit LDS", Nsample, kTogoMaxN);
+  return MBD_OK;
+}
+extern "C" int mbd_debug_check_togo(const mbd_togo* rec, int Hsample, int Nsample, int update_method, int enable_demo) {
+  if (!rec) return fail(MBD_ERR_INVALID, "to-go record is NULL");
+  return check_togo(rec, Hsample, Nsample, update_method, enable_demo);
+}
+
+extern "C" int mbd_plan_set_togo(mbd_plan* p, const mbd_togo* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (rec) {  // (before any device access)
+    MBD_TRY(check_togo(rec, p->cfg.Hsample, p->cfg.Nsample, p->cfg.update_method, p->cfg.enable_demo));
+    const char* other = p->obj.has ? "an objective" : p->val.has ? "a value" : p->wt.has ? "a weighting" : p->adapt.has ? "an adapt"
+                        : p->has_ens ? "an ensemble" : nullptr;
+    if (other)
+      return fail(MBD_ERR_UNSUPPORTED, "to-go record: the plan carries %s record: what that record means per horizon row is not defined",
+                  other);
+    if (p->cfg.shard_count != p->cfg.Nsample)
+      return fail(MBD_ERR_STATE, "to-go record: shard_count=%d of Nsample=%d: sharded plans take no to-go record", p->cfg.shard_count,
+                  p->cfg.Nsample);
+  }
+  NO_SESSION(p, "set_togo");
+  TogoRec& L = p->togo;
+  if (!rec && !L.has) return MBD_OK;  // (nothing to clear: no device is touched)
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still write R and W)
+  L.has = false;
+  if (!rec) return MBD_OK;
+  togo_layout(L, rec->block, rec->min_tail, p->cfg.Hsample);
+  const size_t n = (size_t)L.G * p->cfg.Nsample;
+  HIP_TRY(L.d_R.grow(n));
+  HIP_TRY(L.d_W.grow(n));
+  HIP_TRY(hipMemset(L.d_R, 0xff, sizeof(float) * n));  // (no step yet: mbd_plan_peek_togo says so)
+  HIP_TRY(hipMemset(L.d_W, 0xff, sizeof(float) * n));
+  HIP_TRY(hipDeviceSynchronize());
+  L.stepped = false;
+  L.has = true;
+  return MBD_OK;
+}
+
+extern "C" int mbd_plan_peek_togo(mbd_plan* p, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  const TogoRec& L = p->togo;
+  if (!L.has) return fail(MBD_ERR_STATE, "peek_togo: the plan has no to-go record");
+  HIP_TRY(hipSetDevice(p->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t N = (size_t)p->cfg.Nsample;
+  if (starts_out) memcpy(starts_out, L.starts.data(), sizeof(int32_t) * L.G);
+  if (R_out) HIP_TRY(hipMemcpy(R_out, L.d_R, sizeof(float) * L.G * N, hipMemcpyDeviceToHost));
+  if (W_out) {
+    HIP_TRY(hipMemcpy(W_out, L.d_W, sizeof(float) * L.G * N, hipMemcpyDeviceToHost));
+    // (group 0's weights are the plan's own, once a step of the record has written them)
+    if (L.stepped) HIP_TRY(hipMemcpy(W_out, p->d_weights, sizeof(float) * N, hipMemcpyDeviceToHost));
+  }
+  if (n_groups_out) *n_groups_out = L.G;
+  return MBD_OK;
+}
+
+// include/mbd_hip_debug.h: the layout and the returns on the HOST, from the functions the returns kernel calls; no device touched
+static int check_togo_args(const char* what, int N, int H, int block, int min_tail) {
+  if (N < 1 || H < 1 || (uint64_t)N * (uint64_t)H > (1ull << 26)) return fail(MBD_ERR_INVALID, "%s: N=%d H=%d", what, N, H);
+  if (block < 1) return fail(MBD_ERR_INVALID, "%s: block=%d: at least 1", what, block);
+  if (min_tail < 1 || min_tail > H) return fail(MBD_ERR_INVALID, "%s: min_tail=%d outside [1, H=%d]", what, min_tail, H);
+  return MBD_OK;
+}
+extern "C" int mbd_debug_togo_host(const float* rews, const float* rewss, int N, int H, int block, int min_tail, int32_t* starts_out,
+                                   float* R_out, int32_t* n_groups_out) {
+  MBD_TRY(check_togo_args("togo_host", N, H, block, min_tail));
+  if (R_out && (!rews || !rewss)) return fail(MBD_ERR_INVALID, "togo_host: NULL argument");
+  const int G = togo_groups(H, block, min_tail);
+  if (starts_out)
+    for (int j = 0; j < G; ++j) starts_out[j] = togo_start(j, block);
+  if (n_groups_out) *n_groups_out = G;
+  if (!R_out) return MBD_OK;
+  for (int n = 0; n < N; ++n) {
+    R_out[n] = rews[n];
+    togo_chain(rewss + (size_t)n * H, H, block, G, [&](int j, float v) { R_out[(size_t)j * N + n] = v; });
+  }
+  return MBD_OK;
+}
+// ... and the step's two launches alone on the DEVICE, on caller-given arrays.  What is read back is filled with quiet NaN first.
+extern "C" int mbd_debug_togo_step(const float* cand, const float* ybar, const float* rews, const float* rewss, int N, int H, int Nu,
+                                   int block, int min_tail, int lazy, float sigma, float temp, int std_guard, float alpha_i,
+                                   float alpha_bar_i, float alpha_bar_im1, int literal, float* ybar_out, float* R_out, float* W_out,
+                                   float* rew_mean_out) {
+  if (!cand || !ybar || !rews || !rewss) return fail(MBD_ERR_INVALID, "togo_step: NULL argument");
+  MBD_TRY(check_togo_args("togo_step", N, H, block, min_tail));
+  if (Nu < 1 || (uint64_t)N * (uint64_t)H * (uint64_t)Nu > (1ull << 26)) return fail(MBD_ERR_INVALID, "togo_step: N=%d H=%d Nu=%d", N, H, Nu);
+  if (N > kTogoMaxN) return fail(MBD_ERR_INVALID, "togo_step: N=%d above %d", N, kTogoMaxN);
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  const size_t HNu = (size_t)H * Nu, n = (size_t)N * HNu;
+  TogoRec L;
+  togo_layout(L, block, min_tail, H);
+  const size_t gn = (size_t)L.G * N;
+  DevBuf<float> d_cand, d_ybar, d_rews, d_rewss, d_out, d_keep, d_w, d_mean;
+  HIP_TRY(d_cand.alloc(n));
+  HIP_TRY(d_ybar.alloc(HNu));
+  HIP_TRY(d_rews.alloc(N));
+  HIP_TRY(d_rewss.alloc((size_t)N * H));
+  HIP_TRY(d_out.alloc(HNu));
+  HIP_TRY(d_keep.alloc(HNu));
+  HIP_TRY(d_w.alloc(N));
+  HIP_TRY(d_mean.alloc(1));
+  HIP_TRY(L.d_R.alloc(gn));
+  HIP_TRY(L.d_W.alloc(gn));
+  HIP_TRY(hipMemcpy(d_cand, cand, sizeof(float) * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_ybar, ybar, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_rews, rews, sizeof(float) * N, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_rewss, rewss, sizeof(float) * (size_t)N * H, hipMemcpyHostToDevice));
+  for (auto [ptr, cnt] : {std::pair<float*, size_t>{d_out.get(), HNu}, {d_keep.get(), HNu}, {d_w.get(), (size_t)N}, {d_mean.get(), 1},
+                          {L.d_R.get(), gn}, {L.d_W.get(), gn}})
+    HIP_TRY(hipMemset(ptr, 0xff, sizeof(float) * cnt));
+  TogoUpdate A{};
+  A.rews = d_rews; A.weights = d_w; A.rew_mean = d_mean; A.cand = d_cand; A.ybar_i = d_ybar; A.ybar_im1 = d_out; A.ybar_keep = d_keep;
+  A.N = N; A.H = H; A.Nu = Nu; A.temp = temp; A.std_guard = std_guard ? 1 : 0; A.alpha_i = alpha_i; A.alpha_bar_i = alpha_bar_i;
+  A.alpha_bar_im1 = alpha_bar_im1; A.literal = literal ? 1 : 0; A.lazy = lazy ? 1 : 0; A.sigma = sigma;
+  MBD_TRY(togo_launch(L, d_rewss, A, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  if (ybar_out) HIP_TRY(hipMemcpy(ybar_out, d_out, sizeof(float) * HNu, hipMemcpyDeviceToHost));
+  if (R_out) HIP_TRY(hipMemcpy(R_out, L.d_R, sizeof(float) * gn, hipMemcpyDeviceToHost));
+  if (W_out) {
+    HIP_TRY(hipMemcpy(W_out, L.d_W, sizeof(float) * gn, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(W_out, d_w, sizeof(float) * N, hipMemcpyDeviceToHost));
+  }
+  if (rew_mean_out) HIP_TRY(hipMemcpy(rew_mean_out, d_mean, sizeof(float), hipMemcpyDeviceToHost));
   return MBD_OK;
 }
 

@@ -1028,12 +1028,16 @@ static __global__ __launch_bounds__(kWmE * kWmG) void wmean_kernel(const float* 
 // 1.5x at worst, whatever the L2 does.
 // GIVEN (sweeps under a weighting record): weights_out already holds the plan's N weights — weigh_kernel's — and rew_mean_out its
 // mean reward; the workgroups load them into wl[] in place of deriving them, and the chains below are the same text.
-template <int ROUND, bool REGS, int V = 1, bool GIVEN = false>  // rows in flight per round of the chain, score_block's REGS (48, true: one plan; sweeps: 32, false)
+// SPAN (the to-go record's kernel, togo_update_kernel): the workgroup owns the outputs [e_base, e_base + 16 V) below e_lim <= HNu, a
+// tile of one group's element range, in place of tile `tile` of the whole [0, HNu) — what rews, weights_out and writer mean is then
+// per group.  Everything else is this text; without SPAN the two arguments are not read.
+template <int ROUND, bool REGS, int V = 1, bool GIVEN = false, bool SPAN = false>  // rows in flight per round of the chain, score_block's REGS (48, true: one plan; sweeps: 32, false)
 __device__ __forceinline__ void score_wmean_body(
     const float* __restrict__ rews, const float* __restrict__ lp_demo, int N, float rew_xref, float temp, int std_guard,
     float* __restrict__ weights_out, float* __restrict__ rew_mean_out, const float* __restrict__ Y0s, int HNu,
     const float* __restrict__ Ybar_i, float alpha_i, float alpha_bar_i, float alpha_bar_im1, int literal,
-    float* __restrict__ Ybar_im1, int lazy, float sigma, float* __restrict__ ybar_keep, int tile, bool writer) {
+    float* __restrict__ Ybar_im1, int lazy, float sigma, float* __restrict__ ybar_keep, int tile, bool writer, int e_base = 0,
+    int e_lim = 0) {
   // tile: which 16 outputs this workgroup owns (XCD-aware, xcd_tile / the batch kernel); writer: the one workgroup of the
   // plan that stores the weights and the mean reward (every workgroup derives the same values)
   static_assert(kWmE * kWmG == kScoreThreads, "score_block runs on the weighted mean's workgroup");
@@ -1041,12 +1045,13 @@ __device__ __forceinline__ void score_wmean_body(
   __shared__ float red_s[2 * (kScoreThreads / 64)];
   __shared__ float red[kWmG][kWmE * V + 1];
   const int j = threadIdx.x & (kWmE - 1), g = threadIdx.x / kWmE;
-  const int e0 = tile * (kWmE * V) + j * V;  // this thread's first output
+  int e0;  // this thread's first output
+  if constexpr (SPAN) e0 = e_base + j * V; else e0 = tile * (kWmE * V) + j * V;
   int e[V];
   float yb[V];
 #pragma unroll
   for (int v = 0; v < V; ++v) {
-    e[v] = e0 + v < HNu ? e0 + v : HNu - 1;
+    if constexpr (SPAN) e[v] = e0 + v < e_lim ? e0 + v : e_lim - 1; else e[v] = e0 + v < HNu ? e0 + v : HNu - 1;
     yb[v] = lazy ? Ybar_i[e[v]] : 0.0f;
   }
   auto val = [&](float x, int v) { return lazy ? fclip(x * sigma + yb[v], -1.0f, 1.0f) : x; };
@@ -1133,8 +1138,10 @@ __device__ __forceinline__ void score_wmean_body(
   __syncthreads();
   // the 16 V outputs of the tile, one per thread of the first 16 V threads: the 64 partials of an output in group order
   if ((int)threadIdx.x >= kWmE * V) return;
-  const int jo = threadIdx.x, eo = tile * (kWmE * V) + jo;
-  if (eo >= HNu) return;
+  const int jo = threadIdx.x;
+  int eo;
+  if constexpr (SPAN) eo = e_base + jo; else eo = tile * (kWmE * V) + jo;
+  if (eo >= (SPAN ? e_lim : HNu)) return;
   if (ybar_keep) ybar_keep[eo] = Ybar_i[eo];
   float tot = red[0][jo];
 #pragma unroll 8
@@ -2175,5 +2182,116 @@ static __global__ __launch_bounds__(kEliteThreads) void elite_shift_kernel(float
   }
 }
 #endif  // MBD_ELITE_KERNEL
+
+// ---- the to-go record (mbd_plan_set_togo, include/mbd_hip.h mbd_togo; DESIGN.md section 1 "N19 to-go"): the horizon's rows in G
+// groups, group j's rows updated under weights derived from R_j, the candidates' mean reward from row s_j onwards.  Under a record
+// the two kernels below stand where the fused score + weighted-mean launch stands. ----
+// The layout and the arithmetic of the returns are the functions below, host and device text (mbd_debug_togo_host loops them on the
+// CPU).  f32, every operation rounded.
+// The starts are s_j = j block for every j >= 1 with H - j block >= min_tail (min_tail >= 1: then j block < H as well), a condition
+// that holds for j = 1 .. (H - min_tail) / block and for no j beyond: G = 1 + (H - min_tail) / block, and s_j = j block for all j < G.
+MBD_HD int togo_groups(int H, int block, int min_tail) { return 1 + (H - min_tail) / block; }
+MBD_HD int togo_start(int j, int block) { return j * block; }
+MBD_HD int togo_end(int j, int G, int H, int block) { return j + 1 < G ? (j + 1) * block : H; }
+MBD_HD float togo_add(float acc, float r) { return acc + r; }
+MBD_HD float togo_ret(float acc, int H, int s) { return acc / (float)(H - s); }
+// One candidate's descending pass: acc = +0, acc += row[t] for t = H - 1 down to s_1 = block, and store(j, R_j) whenever t = s_j.
+// Nothing is skipped: a NaN of step t is in acc for every t' <= t.  The loads of sixteen steps leave together, their adds follow in
+// the contract's order.  Bounds: t runs over [block, H - 1] with block >= 1, j over [1, G - 1]; G = 1 runs no iteration.
+template <class Store>
+MBD_HD void togo_chain(const float* __restrict__ row, int H, int block, int G, Store&& store) {
+  if (G < 2) return;
+  float acc = 0.0f;
+  int j = G - 1, s = togo_start(j, block);
+  int t = H - 1;
+  for (; t - 15 >= block; t -= 16) {
+    float y[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) y[k] = row[t - k];
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      acc = togo_add(acc, y[k]);
+      if (t - k == s) {
+        store(j, togo_ret(acc, H, s));
+        --j;
+        s -= block;
+      }
+    }
+  }
+  for (; t >= block; --t) {
+    acc = togo_add(acc, row[t]);
+    if (t == s) {
+      store(j, togo_ret(acc, H, s));
+      --j;
+      s -= block;
+    }
+  }
+}
+
+#ifdef MBD_TOGO_KERNEL
+// R [G][N] from rewss [N][H]: row 0 is a copy of rews, the array the step's score reads (for the peek call: the update kernel reads
+// group 0's returns from rews itself); rows 1 .. G - 1 are togo_chain's.  A lane owns a candidate and reads its row of rewss with
+// direct strided loads — sixteen in flight — since the whole of rewss is N H floats (200 KB at the flagship size) and sits in L2 behind
+// the rollout that wrote it; workgroups of one wavefront spread the candidates over the CUs.  Bounds: n < N guards every access; a
+// load is rewss[n H + t] with t in [block, H - 1], a store R[j N + n] with j in [0, G - 1].
+constexpr int kTogoThreads = 64;
+struct TogoReturns {
+  const float* rews;   // [N]
+  const float* rewss;  // [N][H]
+  float* R;            // [G][N]
+  int N, H, block, G;
+};
+static __global__ __launch_bounds__(kTogoThreads) void togo_returns_kernel(TogoReturns A) {
+  const int n = blockIdx.x * kTogoThreads + threadIdx.x;
+  if (n >= A.N) return;
+  float* __restrict__ R = A.R;
+  R[n] = A.rews[n];
+  togo_chain(A.rewss + (size_t)n * A.H, A.H, A.block, A.G, [&](int j, float v) { R[(size_t)j * A.N + n] = v; });
+}
+
+// Score and weighted mean per group in ONE launch: score_wmean_kernel's workgroup (kWmE x kWmG = 1024 threads) and text
+// (score_wmean_body: score_block into the LDS weights, the prefetch, the rounds of 48 rows, the tail, the 64 partials in order, the
+// final formula), over tiles that never straddle a group.  Groups 0 .. G - 2 hold block Nu elements each, tpg = ceil(block Nu / 16)
+// tiles; the last group holds (H - s_{G-1}) Nu elements in the remaining T - (G - 1) tpg tiles; tile x of the XCD-aware order
+// (xcd_tile: neighbouring tiles, which share candidate lines, meet in one L2) is tile t = x - j tpg of group j = min(x / tpg, G - 1).
+// A group's last tile may be partial: the span holds its outputs below e_lim = s_{j+1} Nu.  Group j's workgroups derive W_j from
+// R_j (group 0: from rews itself); its first workgroup stores W_j — group 0's into the plan's weights, with the mean reward and its
+// early system-scope copy, as the fused kernel's workgroup 0 does — and every workgroup stores ybar_keep for its own elements.
+// Bounds: the launch has exactly T workgroups and xcd_tile is a bijection on [0, T); t < the group's tile count, so
+// e_base = s_j Nu + 16 t < e_lim <= H Nu: the span clamps its loads to e_lim - 1 and stores below e_lim only.  R and W rows j < G.
+// LDS: N floats of weights (N <= 12288: the set call) beside the span's two reduction arrays.
+struct TogoUpdate {
+  const float* rews;  // [N]: R_0
+  const float* R;     // [G][N]: rows 1 .. G - 1 are read
+  float* W;           // [G][N]: rows 1 .. G - 1 are written
+  float* weights;     // [N]: W_0
+  float* rew_mean;
+  const float* cand;  // [N][H Nu]
+  const float* ybar_i;
+  float* ybar_im1;
+  float* ybar_keep;
+  int N, H, Nu, G, block, tpg, T;
+  float temp;
+  int std_guard;
+  float alpha_i, alpha_bar_i, alpha_bar_im1;
+  int literal, lazy;
+  float sigma;
+};
+static __global__ __launch_bounds__(kWmE * kWmG) void togo_update_kernel(TogoUpdate A) {
+  const int x = xcd_tile(blockIdx.x, A.T, 0);
+  int j = x / A.tpg;
+  j = j < A.G - 1 ? j : A.G - 1;
+  const int t = x - j * A.tpg;
+  const int e_base = togo_start(j, A.block) * A.Nu + t * kWmE, e_lim = togo_end(j, A.G, A.H, A.block) * A.Nu;
+  const size_t row = (size_t)j * A.N;
+  score_wmean_body<48, true, 1, false, true>(j ? A.R + row : A.rews, nullptr, A.N, 0.0f, A.temp, A.std_guard, j ? A.W + row : A.weights,
+                                             j ? nullptr : A.rew_mean, A.cand, A.H * A.Nu, A.ybar_i, A.alpha_i, A.alpha_bar_i,
+                                             A.alpha_bar_im1, A.literal, A.ybar_im1, A.lazy, A.sigma, A.ybar_keep, 0, t == 0, e_base,
+                                             e_lim);
+}
+#endif  // MBD_TOGO_KERNEL
 
 }  // namespace mbd

@@ -125,7 +125,14 @@ class Elites(C.Structure):
     _fields_ = [("n_elites", C.c_int32), ("nominal", C.c_int32), ("carry", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class Togo(C.Structure):
+    """mbd_togo (include/mbd_hip.h): the horizon's rows in groups of ``block``, a group starting only where at least ``min_tail``
+    rows are still ahead; group j's rows are updated under weights from the return from its first row onwards."""
+    _fields_ = [("block", C.c_int32), ("min_tail", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 ELITES_MAX = 32
+TOGO_MAX_N = 12288
 PICK_MEAN, PICK_PREV, PICK_BEST = 1, 2, 4
 
 
@@ -170,6 +177,7 @@ EXPORTS = [
     "mbd_plan_set_mpc_pick", "mbd_plan_peek_mpc_pick", "mbd_sweep_set_mpc_pick", "mbd_sweep_peek_mpc_pick",
     "mbd_plan_set_value", "mbd_plan_peek_value", "mbd_plan_eval_value", "mbd_sweep_set_value",
     "mbd_plan_set_adapt", "mbd_plan_peek_adapt", "mbd_plan_set_elites", "mbd_plan_peek_elites",
+    "mbd_plan_set_togo", "mbd_plan_peek_togo",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
@@ -266,6 +274,8 @@ def load() -> C.CDLL:
     lib.mbd_sweep_set_value.argtypes = [_vp, C.POINTER(Value)]
     lib.mbd_plan_set_adapt.argtypes = [_vp, C.POINTER(Adapt)]
     lib.mbd_plan_set_elites.argtypes = [_vp, C.POINTER(Elites)]
+    lib.mbd_plan_set_togo.argtypes = [_vp, C.POINTER(Togo)]
+    lib.mbd_plan_peek_togo.argtypes = [_vp, _vp, _vp, _vp, _vp]
     lib.mbd_plan_peek_elites.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_plan_peek_adapt.argtypes = [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
@@ -657,6 +667,74 @@ def peek_elites(fn, handle, n_elites: int, HNu: int, capacity: int = None) -> di
     m, c = min(n.value, int(capacity)), int(count[0])
     return {"E": E[:c], "R": R[:c], "src": src[:c], "count": c, "log_count": lc[:m], "log_kept": lk[:m], "log_top": lt[:m],
             "steps": n.value}
+
+
+def togo_record(block: int = 1, min_tail: int = 1) -> "Togo":
+    """The mbd_togo of ``Plan.set_togo``'s arguments."""
+    rec = Togo()
+    rec.block, rec.min_tail = int(block), int(min_tail)
+    return rec
+
+
+def debug_check_togo(rec: "Togo", Hsample: int, Nsample: int, update_method: int = 0, enable_demo: bool = False) -> int:
+    """include/mbd_hip_debug.h: the refusals a to-go record alone decides for a plan of that Hsample, Nsample, update_method and
+    enable_demo; the return code (the message: ``mbd_last_error``)."""
+    lib = load()
+    lib.mbd_debug_check_togo.argtypes = [C.POINTER(Togo), _i, _i, _i, _i]
+    return lib.mbd_debug_check_togo(None if rec is None else C.byref(rec), int(Hsample), int(Nsample), int(update_method),
+                                    int(bool(enable_demo)))
+
+
+def debug_togo_host(rews, rewss, block: int, min_tail: int) -> dict:
+    """include/mbd_hip_debug.h: a to-go record's group layout and returns on the host (no device) from ``rews`` [N] and ``rewss``
+    [N, H].  Returns dict(starts [G], R [G, N])."""
+    lib = load()
+    rewss = np.ascontiguousarray(rewss, np.float32)
+    N, H = rewss.shape
+    rews = np.ascontiguousarray(rews, np.float32).reshape(N)
+    starts, R, G = np.full(H, -1, np.int32), np.zeros((H, N), np.float32), C.c_int32(0)
+    lib.mbd_debug_togo_host.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(C.c_int32)]
+    check(lib.mbd_debug_togo_host(np_ptr(rews), np_ptr(rewss), N, H, int(block), int(min_tail), np_ptr(starts), np_ptr(R), C.byref(G)))
+    return dict(starts=starts[:G.value].copy(), R=R.reshape(-1)[:G.value * N].reshape(G.value, N).copy())
+
+
+def debug_togo_layout(H: int, block: int, min_tail: int) -> np.ndarray:
+    """The group starts alone (``mbd_debug_togo_host`` without rewards; no device)."""
+    lib = load()
+    starts, G = np.full(max(int(H), 1), -1, np.int32), C.c_int32(0)
+    lib.mbd_debug_togo_host.argtypes = [_vp, _vp, _i, _i, _i, _i, _vp, _vp, C.POINTER(C.c_int32)]
+    check(lib.mbd_debug_togo_host(None, None, 1, int(H), int(block), int(min_tail), np_ptr(starts), None, C.byref(G)))
+    return starts[:G.value].copy()
+
+
+def debug_togo_step(cand, ybar, rews, rewss, Nu: int, block: int, min_tail: int, lazy, sigma: float, temp: float, std_guard,
+                    alpha_i: float, alpha_bar_i: float, alpha_bar_im1: float, literal, n_groups: int) -> dict:
+    """include/mbd_hip_debug.h: the step's two launches alone on the device over ``cand`` [N, H * Nu] (values, or with ``lazy``
+    normals), ``ybar`` [H * Nu], ``rews`` [N] and ``rewss`` [N, H]; ``n_groups``: the layout's G (``debug_togo_layout``).  Returns
+    dict(ybar [H, Nu], R, W [G, N], rew_mean)."""
+    lib = load()
+    rewss = np.ascontiguousarray(rewss, np.float32)
+    N, H = rewss.shape
+    cand = np.ascontiguousarray(cand, np.float32).reshape(N, H * int(Nu))
+    ybar = np.ascontiguousarray(ybar, np.float32).reshape(H * int(Nu))
+    rews = np.ascontiguousarray(rews, np.float32).reshape(N)
+    G = int(n_groups)
+    out, R, W, mean = np.zeros((H, int(Nu)), np.float32), np.zeros((G, N), np.float32), np.zeros((G, N), np.float32), np.zeros(1, np.float32)
+    lib.mbd_debug_togo_step.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp]
+    check(lib.mbd_debug_togo_step(np_ptr(cand), np_ptr(ybar), np_ptr(rews), np_ptr(rewss), N, H, int(Nu), int(block), int(min_tail),
+                                  int(bool(lazy)), float(sigma), float(temp), int(bool(std_guard)), float(alpha_i), float(alpha_bar_i),
+                                  float(alpha_bar_im1), int(bool(literal)), np_ptr(out), np_ptr(R), np_ptr(W), np_ptr(mean)))
+    return dict(ybar=out, R=R, W=W, rew_mean=mean[0])
+
+
+def peek_togo(fn, handle, H: int, N: int) -> dict:
+    """mbd_plan_peek_togo: {'starts' [G], 'R' [G, N], 'W' [G, N]} of the last step."""
+    G = C.c_int32(0)
+    check(fn(handle, None, None, None, C.byref(G)))
+    g = G.value
+    starts, R, W = np.zeros(g, np.int32), np.zeros((g, N), np.float32), np.zeros((g, N), np.float32)
+    check(fn(handle, np_ptr(starts), np_ptr(R), np_ptr(W), C.byref(G)))
+    return {"starts": starts, "R": R, "W": W}
 
 
 def pick_record(mean=True, prev=True, best=True) -> "MpcPick":

@@ -852,6 +852,30 @@ class Plan:
         out["E"] = out["E"].reshape(-1, self.H, self.Nu)
         return out
 
+    def set_togo(self, block: int = 1, min_tail: int = 1):
+        """Weigh each horizon row by the return still ahead of it (include/mbd_hip.h mbd_togo): the rows fall into groups of
+        ``block``, a group starting only where at least ``min_tail`` rows are still ahead, and group j's rows are the step's update
+        under weights from the candidates' mean reward from the group's first row onwards.  MBD and mppi plans, unsharded, without
+        ``enable_demo``, at most 12288 candidates, and without an objective, value, weighting, adapt or ensemble record."""
+        rec = _capi.togo_record(block, min_tail)
+        _capi.check(self.lib.mbd_plan_set_togo(self.h, C.byref(rec)))
+        self._togo = (int(block), int(min_tail))
+
+    def clear_togo(self):
+        _capi.check(self.lib.mbd_plan_set_togo(self.h, None))
+        self._togo = None
+
+    @property
+    def has_togo(self) -> bool:
+        return getattr(self, "_togo", None) is not None
+
+    def peek_togo(self) -> dict:
+        """``starts`` [G] the groups' first rows, ``R`` and ``W`` [G, Nsample] the groups' returns and weights of the last step (a
+        plan with a to-go record); row 0 is the rewards the score read and the weights ``peek`` returns."""
+        if not self.has_togo:
+            _capi.check(self.lib.mbd_plan_peek_togo(self.h, None, None, None, None))
+        return _capi.peek_togo(self.lib.mbd_plan_peek_togo, self.h, self.H, self.cfg.Nsample)
+
     def peek_objective(self):
         """The last step's ``ret`` [shard_count] ([M, N] under an ensemble record) and ``cost`` [shard_count] (a plan with an
         objective record)."""

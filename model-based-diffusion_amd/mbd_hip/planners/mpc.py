@@ -112,6 +112,16 @@ selected candidates that had been injected (summed over the tick's steps) and th
 
     python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --elites 4 --elite_nominal --elite_carry
 
+Every update weighs a candidate once: its whole return multiplies all its horizon rows, so the noise it drew in a late row is
+credited with rewards of earlier rows it cannot have caused.  A to-go record (include/mbd_hip.h mbd_togo; DESIGN.md section 1 "N19
+to-go") weighs a row by the return still ahead of it, the to-go return of PI^2: ``--togo_block B`` groups the rows B at a time and
+updates each group under weights from the candidates' mean reward from the group's first row onwards; ``--togo_min_tail M`` starts a
+group only where at least M rows are still ahead (the last group takes the rest).  There is no record unless ``--togo_block`` is
+given.  MBD and mppi plans, single episodes; ``--online`` honours it; not beside the objective, value, weighting, adapt or ensemble
+flags.  The report gains ``togo_groups``, the groups' first rows.
+
+    python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --togo_block 5 --togo_min_tail 10
+
 A demo plan (``--enable_demo``) compares its 50 planned steps with the env's 50 demo rows; in an episode the demo has to move
 with the system.  ``--demo_clip env|FILE.npy`` (include/mbd_hip.h mbd_mpc_demo; DESIGN.md section 1 "N10 demo clock") sets the
 clip the episode follows — the env's own demo, or an array [n_track, L, 3] (car2d: [L, 2]) — and ``--demo_start c0`` the clip
@@ -214,6 +224,8 @@ class MpcArgs(Args):
     elites: int = 0  # K > 0: an elite record (mbd_elites) — the K best candidates of a step are candidates of the next one ...
     elite_nominal: bool = False  # ... candidate 0 of every step is the step's mean itself (with --elites 0: the record is this alone)
     elite_carry: bool = False  # ... and a tick boundary shifts the elites with the mean (default: every tick starts without elites)
+    togo_block: int = 0  # B > 0: a to-go record (mbd_togo) — the horizon's rows in groups of B, each under weights from the return ahead ...
+    togo_min_tail: int = 1  # ... a group starting only where at least this many rows are still ahead
 
 
 def _has_value(args: MpcArgs) -> bool:
@@ -460,6 +472,31 @@ def _elites_log(log: dict, Nd: int, K: int) -> dict:
     return dict(elites_kept=kept, elites_top=top)
 
 
+def _has_togo(args: MpcArgs) -> bool:
+    """Whether the arguments ask for a to-go record at all (a block)."""
+    return args.togo_block != 0
+
+
+def _togo_of(args: MpcArgs) -> dict:
+    """``Plan.set_togo``'s arguments."""
+    return dict(block=args.togo_block, min_tail=args.togo_min_tail)
+
+
+def _togo_settings(args: MpcArgs) -> dict:
+    return dict(togo_block=args.togo_block, togo_min_tail=args.togo_min_tail) if _has_togo(args) else {}
+
+
+def _check_togo(args: MpcArgs) -> None:
+    """What a to-go record refuses, decided from the arguments alone: the records whose per-row meaning is not defined."""
+    if not _has_togo(args):
+        return
+    for name, has in (("objective", _has_objective), ("value", _has_value), ("weighting", _has_weighting), ("adapt", _has_adapt),
+                      ("ensemble", _has_ensemble)):
+        if has(args):
+            raise ValueError(f"togo_block={args.togo_block!r} beside the {name} flags: a plan takes a to-go record or {name} record, "
+                             "not both (what that record means per horizon row is not defined)")
+
+
 _PICK_NAMES = ("mean", "prev", "best")
 
 
@@ -618,6 +655,7 @@ def _reset_and_key(env, seed: int):
 
 def _setup(args: MpcArgs, device: int, online: bool = False):
     """``online``: no plant record is set — the caller executes the rows (``run_mpc_online``)."""
+    _check_togo(args)
     apply_recommended(args)
     env = get_env(args.env_name, device=device)
     state_init, rng_exp = _reset_and_key(env, args.seed)
@@ -650,6 +688,8 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
         plan.set_adapt(**_adapt_of(args))
     if _has_elites(args):
         plan.set_elites(**_elites_of(args))
+    if _has_togo(args):
+        plan.set_togo(**_togo_of(args))
     return env, plan, state_init, rng_exp
 
 
@@ -688,6 +728,7 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
             secs.append(out["seconds"])
         adapt = plan.peek_adapt() if _has_adapt(args) else None  # (the table behind the last tick, the log of the session's steps)
         elites = plan.peek_elites() if _has_elites(args) else None
+        togo = plan.peek_togo() if _has_togo(args) else None
     ep = dict(actions=np.concatenate(actions), rewards=np.concatenate(rewards), states=np.stack(states), means=np.stack(means),
               seconds=float(np.sum(secs)), tick_seconds=np.asarray(secs, np.float64))
     if plan._has_delay:
@@ -699,6 +740,8 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
         ep["adapt"] = adapt
     if elites is not None:
         ep["elite_log"] = elites
+    if togo is not None:
+        ep["togo"] = togo
     if plog:
         ep["pick"] = dict(choice=np.array([x["choice"] for x in plog], np.int32), rets=np.stack([x["rets"] for x in plog]),
                           best=np.array([x["best"] for x in plog], np.int32))
@@ -732,6 +775,9 @@ def _check_batch(arg_list) -> None:
     if not 1 <= len(arg_list) <= MAX_EPISODES:
         raise ValueError(f"{len(arg_list)} episodes: a batch holds 1 to {MAX_EPISODES}")
     for k, a in enumerate(arg_list):
+        if _has_togo(a):
+            raise ValueError(f"episode {k} carries togo_block={a.togo_block!r}: sweeps take no to-go record; run the episodes one by "
+                             "one (run_mpc)")
         if _has_elites(a):
             raise ValueError(f"episode {k} carries elites={a.elites!r} / elite_nominal={a.elite_nominal!r}: sweeps take no elite "
                              "record; run the episodes one by one (run_mpc)")
@@ -855,6 +901,8 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
             ep["adapt"] = plan.peek_adapt()
         if _has_elites(args):  # (the elites behind the last tick and the log of the episode's steps)
             ep["elite_log"] = plan.peek_elites()
+        if _has_togo(args):  # (the layout, and the last step's returns and weights per group)
+            ep["togo"] = plan.peek_togo()
     finally:
         plan.close()
     reward = float(ep["rewards"].mean())
@@ -866,7 +914,7 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         if _has_basis(args):
             shape = dict(shape, **_basis_settings(args))
         shape = dict(shape, **_delay_settings(args), **_demo_settings(args), **_sigma_settings(args), **_objective_settings(args),
-                     **_weighting_settings(args), **_adapt_settings(args), **_elites_settings(args))
+                     **_weighting_settings(args), **_adapt_settings(args), **_elites_settings(args), **_togo_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -913,6 +961,7 @@ def _main(argv=None) -> dict:
         wlog = plan.peek_weighting() if _has_weighting(args) else None
         alog = plan.peek_adapt() if _has_adapt(args) else None
         elog = plan.peek_elites() if _has_elites(args) else None
+        tlog = plan.peek_togo() if _has_togo(args) else None
         nominal = None
         if _has_plant(args):  # what the perturbation cost: the same episode without the record
             plan.clear_mpc_plant()
@@ -950,6 +999,8 @@ def _main(argv=None) -> dict:
         res.update(_adapt_settings(args), **_adapt_log(alog))
     if elog is not None:
         res.update(_elites_settings(args), **_elites_log(elog, args.Ndiffuse, K))
+    if tlog is not None:
+        res.update(_togo_settings(args), togo_groups=[int(x) for x in tlog["starts"]])
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -991,6 +1042,8 @@ def _main_online(args: MpcArgs) -> dict:
         res.update(_adapt_settings(args), **_adapt_log(ep["adapt"]))
     if "elite_log" in ep:
         res.update(_elites_settings(args), **_elites_log(ep["elite_log"], args.Ndiffuse, args.warm_steps))
+    if "togo" in ep:
+        res.update(_togo_settings(args), togo_groups=[int(x) for x in ep["togo"]["starts"]])
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
