@@ -146,21 +146,16 @@ extern "C" int mbd_debug_eval_math(const char* op, long long n, const float* in,
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
   if (n == 0) return MBD_OK;
   const int k_in = kMathOps[id].k_in, k_out = kMathOps[id].k_out;
-  const size_t bin = sizeof(float) * (size_t)n * k_in, bout = sizeof(float) * (size_t)n * k_out;
-  float *d_in = nullptr, *d_out = nullptr;
-  hipError_t e = hipMalloc(&d_in, bin);
-  if (e == hipSuccess) e = hipMalloc(&d_out, bout);
-  if (e == hipSuccess) e = hipMemcpy(d_in, in, bin, hipMemcpyHostToDevice);
+  DevBuf<float> d_in, d_out;
+  hipError_t e = d_in.upload(in, (size_t)n * k_in);
+  if (e == hipSuccess) e = d_out.alloc((size_t)n * k_out);
   if (e == hipSuccess) {
     const int block = 256;
-    hipLaunchKernelGGL(eval_math_kernel, dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, 0, id, n, k_in,
-                       k_out, d_in, d_out);
+    hipLaunchKernelGGL(eval_math_kernel, dim3((unsigned)((n + block - 1) / block)), dim3(block), 0, 0, id, n, k_in, k_out, d_in.get(),
+                       d_out.get());
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpy(out, d_out, bout, hipMemcpyDeviceToHost);
-  const hipError_t e_free = d_in ? hipFree(d_in) : hipSuccess;
-  if (d_out) (void)hipFree(d_out);
-  if (e == hipSuccess) e = e_free;
+  if (e == hipSuccess) e = d_out.download(out, (size_t)n * k_out);  // (a copy on the null stream: behind the kernel)
   if (e != hipSuccess) return fail(MBD_ERR_HIP, "eval_math(%s): %s", op, hipGetErrorString(e));
   return MBD_OK;
 }

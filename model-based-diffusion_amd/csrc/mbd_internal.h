@@ -1,8 +1,11 @@
 // mbd_internal.h — what the translation units of libmbd_hip.so's host side share (NOT part of the boundary: the C ABI is
 // include/mbd_hip.h): the owners of runtime resources, the env handle, error reporting, the test levers, what plans and
-// sweeps do alike, and the functions one unit defines for the others.  (A handle only its own unit uses is defined there.)
+// sweeps do alike, and the functions one unit defines for the others.  (A handle only its own unit uses is defined there: the
+// adapt, elite and to-go records of a plan, in the other records' form, are mbd_plan.hip's.)
 // Units: mbd_env.hip (library, levers, envs, the rollout launch), mbd_plan.hip (plans: one reverse-diffusion step and the
-// loops over it), mbd_sweep.hip (sweeps: several plans per launch), mbd_exchange.hip (the in-library exchange).
+// loops over it, every record's members), mbd_sweep.hip (sweeps: several plans per launch), mbd_exchange.hip (the in-library
+// exchange), mbd_debug_math.hip (mbd_math.h over arrays); mbd_pk2.hip, mbd_planar.hip and mbd_hot3d.hip hold rollout
+// instantiations only.  mbd_ring.h: the ring logs' arithmetic, which includes nothing and is tested on the host alone.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,6 +28,7 @@
 #include "../../include/mbd_hip.h"
 #include "mbd_kernels.h"
 #include "mbd_launch.h"
+#include "mbd_ring.h"
 #include "mbd_step_kernels.h"
 
 using namespace mbd;
@@ -93,6 +97,21 @@ class DevBuf {  // n elements of device memory; converts to T*, so kernel argume
     return e;
   }
   hipError_t grow(size_t n) { return n <= n_ ? hipSuccess : alloc(n); }  // at least n elements; the contents do not survive
+  // The three moves of an entry that runs a kernel on host arrays (the mbd_debug_* entries, the peeks).  None synchronises: that
+  // stays with the caller.  (Inlined, so that the library's symbol list does not grow.)  upload: n elements holding host[0 .. n)
+  __forceinline__ hipError_t upload(const T* host, size_t n) {
+    const hipError_t e = alloc(n);
+    return e != hipSuccess ? e : hipMemcpy(p_, host, sizeof(T) * n, hipMemcpyHostToDevice);
+  }
+  // n elements with every bit set: what a kernel leaves unwritten reads back as NaN, or -1
+  __forceinline__ hipError_t alloc_poisoned(size_t n) {
+    const hipError_t e = alloc(n);
+    return e != hipSuccess ? e : hipMemset(p_, 0xff, sizeof(T) * n);
+  }
+  // the first n elements into host[0 .. n); nothing for a NULL host (an output the caller did not ask for) or n == 0
+  __forceinline__ hipError_t download(T* host, size_t n) const {
+    return host && n ? hipMemcpy(host, p_, sizeof(T) * n, hipMemcpyDeviceToHost) : hipSuccess;
+  }
   operator T*() const { return p_; }
   T* get() const { return p_; }  // (where no conversion happens by itself: a deduced parameter, an operand of ?:)
 
@@ -170,6 +189,23 @@ class PinnedBuf {  // n floats of pinned host memory mapped into the device's ad
   float* h_ = nullptr;
   float* d_ = nullptr;
 };
+
+// ---- the device ring logs (mbd_ring.h has the arithmetic) -------------------------------------------------------------
+// A record's log of its ticks or steps on the device: entry j at j % cap, `count` entries ever written (host bookkeeping: the
+// kernels are handed the slot).  kLogCap: the most a log holds per plan.  ring_slot: where the next entry goes, count advanced.
+// ring_read: the most recent min(n, count, cap) entries of ONE ring — d_ring [cap][width], a plan's own (the caller adds plan
+// k's cap width elements) — into host out, oldest first, by at most two copies; nothing for a NULL out.
+constexpr int kLogCap = 65536;
+static inline long long ring_slot(long long& count, long long cap) { return count++ % cap; }
+template <typename T>
+static int ring_read(const T* d_ring, int width, long long count, long long cap, long long n, T* out) {
+  const RingRuns r = ring_recent(count, cap, n);
+  for (int i = 0; out && i < 2; ++i) {
+    if (r.len[i]) HIP_TRY(hipMemcpy(out, d_ring + r.first[i] * width, sizeof(T) * r.len[i] * width, hipMemcpyDeviceToHost));
+    out += r.len[i] * width;
+  }
+  return MBD_OK;
+}
 
 struct mbd_env : EnvShape {  // (the shape: derive_shape, at creation; car2d keeps the defaults)
   int kind = ENV_MODEL;
@@ -499,10 +535,9 @@ int check_weighting(const mbd_weighting* rec);
 // check_mpc_pick: the refusals the record alone decides, each naming the field, before any device access.  set: behind the handle's
 // NULL, session, enable_demo and ensemble checks (nullptr clears); makes room for P plans' slots [P][3][HNu], their returns and
 // per-step rewards.  start: in front of an episode's or a session's first tick — room for the log, a ring of min(n_ticks,
-// kPickLogCap) entries per plan, entry of tick j at j % cap — and no tick served.  tick: the three launches (four with an objective
+// kLogCap) entries per plan, entry of tick j at j % cap — and no tick served.  tick: the three launches (four with an objective
 // record) behind a tick's last update kernel, on stream s (defined in mbd_plan.hip, which alone compiles the kernels); what it reads
 // is PickTick, and it leaves P_t where M_t lay.  peek: the most recent min(count, capacity, cap) ticks of plan k, oldest first.
-constexpr int kPickLogCap = 65536;
 struct PickTick {
   const float* state;   // [P][S] where the tick planned from
   int N;                // candidates per plan

@@ -127,12 +127,26 @@ struct MpcSession {
   std::chrono::steady_clock::time_point t_submit{};
 };
 
-// The adapt record of a plan (include/mbd_hip.h mbd_adapt) as the handle keeps it: the rule, the table a and G = a * g [HNu] on the
-// device — G is what the samplers take as their shape while the record is in force (noise_spec) —, the scratch the update's two
-// kernels hand var and s through, and the device log, a ring of kAdaptLogCap entries (entry of step j at j % cap; count: steps
-// since the log began).  g_cur: the caller's shape G was last formed under (the plan's d_shape or nullptr), which the update's second
-// kernel forms G' under again.  All zero: no record (a zeroed stand-in handle has none).
-constexpr int kAdaptLogCap = 65536;
+// A step's candidates as the launches behind its sampler are handed them (an adapt record's update, an elite record's injection
+// and selection): cand [N][HNu], or their normals (lazy) with the sigma_i and Ybar_i the step sampled with — an mppi plan's sigma
+// from the carried device scalar, which its sampler read (d_sigma, nullptr: the host value).
+struct StepCand {
+  const float* cand;
+  int N, HNu, lazy;
+  float sigma;
+  const float* d_sigma;
+  const float* ybar_i;
+};
+
+// The plan-only records, in the form of mbd_internal.h's: set behind the handle's refusals (nullptr clears), the launches a step or
+// a tick makes — each returns at once without a record, and the mbd_debug_* entries run the same members on a scratch record —, and
+// peek.  All zero: no record (a zeroed stand-in handle has none).  MBD_HIDDEN: a member function no other unit calls stays out of
+// the library's symbol list.
+#define MBD_HIDDEN __attribute__((visibility("hidden")))
+// The adapt record (include/mbd_hip.h mbd_adapt): the rule, the table a and G = a * g [HNu] on the device — G is what the samplers
+// take as their shape while the record is in force (noise_spec) —, the scratch the update's two kernels hand var and s through, and
+// the device log, a ring of kLogCap entries (count: steps since the log began).  g_cur: the caller's shape G was last formed under
+// (the plan's d_shape or nullptr), which the update's second kernel forms G' under again.
 struct AdaptRec {
   bool has = false;
   AdaptRule rule{};
@@ -141,31 +155,63 @@ struct AdaptRec {
   const float* g_cur = nullptr;
   DevBuf<float> d_a, d_G, d_buf, d_log_S;
   DevBuf<int> d_log_skipped;
+  // g: the caller's shape in force outside warm ticks; the table is all ones afterwards (one launch on s, waited for)
+  MBD_HIDDEN int set(const mbd_adapt* rec, int HNu, const float* g, const mbd_env* env, hipStream_t s);
+  // The table at the start of a run or a tick, or under a new shape: shift < 0: a = ones, otherwise a shifted `shift` elements
+  // forward (0: as it is); G = a * g under the caller's shape g now in force, which the updates that follow keep forming G under.
+  // ONE launch.
+  MBD_HIDDEN int table(int shift, const float* g, int HNu, hipStream_t s);
+  // behind a step's update kernel, on the step's stream, from the step's weights d_w [N]: var into d_buf, then S, a', G' and the
+  // log entry.  TWO launches; the weights are staged in LDS while they fit the default 48 KB window, read from memory beyond
+  MBD_HIDDEN int update(const float* d_w, const StepCand& c, hipStream_t s);
+  // HOST a_out [HNu] and the most recent min(count, capacity, kLogCap) log entries, oldest first
+  MBD_HIDDEN int peek(const mbd_env* env, int HNu, float* a_out, float* ratio_out, int32_t* skipped_out, int capacity, int* count_out) const;
 };
 
-// The elite record of a plan (include/mbd_hip.h mbd_elites) as the handle keeps it: the record, the elites' rows E [n][HNu], their
-// returns R and source indices src [n], the device word `count`, and the device log, a ring of kEliteLogCap entries (entry of step j
-// at j % cap; steps: selections since the log began).  count never comes back to the host inside a loop: every kernel loads it.
-// All zero: no record (a zeroed stand-in handle has none).
-constexpr int kEliteLogCap = 65536;
+// The elite record (include/mbd_hip.h mbd_elites): the record, the elites' rows E [n][HNu], their returns R and source indices src
+// [n], the device word `count`, and the device log, a ring of kLogCap entries (steps: selections since the log began).  count never
+// comes back to the host inside a loop: every kernel loads it.
 struct EliteRec {
   bool has = false;
   int n = 0, nominal = 0, carry = 0;
   long long steps = 0;
   DevBuf<float> d_E, d_R, d_log_top;
   DevBuf<int> d_src, d_count, d_log_count, d_log_kept;
+  // no elites afterwards (one launch on s, waited for)
+  MBD_HIDDEN int set(const mbd_elites* rec, int HNu, const mbd_env* env, hipStream_t s);
+  // The elites at the start of a run or a tick: shift < 0: count = 0, otherwise the present rows shifted `shift` elements forward.
+  // ONE launch, a workgroup per row.
+  MBD_HIDDEN int table(int shift, int HNu, hipStream_t s);
+  // phase 1 of a step, behind the launch that made the step's normals or candidates, in front of the rollout: c.cand's first rows
+  // are rewritten; g is the shape the step's sampler was handed.  ONE launch.
+  MBD_HIDDEN int inject(const StepCand& c, const float* g, hipStream_t s);
+  // phase 2 of a step, behind the step's update kernel (and an adapt record's launches): the selection over the rewards the score
+  // read, and the log entry.  ONE launch.
+  MBD_HIDDEN int select(const float* d_rews, const StepCand& c, hipStream_t s);
+  // HOST the elites, their count and the most recent min(steps, capacity, kLogCap) log entries, oldest first
+  MBD_HIDDEN int peek(const mbd_env* env, int HNu, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
+                      int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out) const;
 };
 
-// The to-go record of a plan (include/mbd_hip.h mbd_togo) as the handle keeps it: the record, the layout it gives at the plan's
-// Hsample — G groups, group j's first row starts[j] = j block —, and the last step's returns and weights R, W [G][N] (row 0 of W is
-// never written: group 0's weights are the plan's d_weights).  All zero: no record (a zeroed stand-in handle has none).
+// The to-go record (include/mbd_hip.h mbd_togo): the record, the layout it gives at the plan's Hsample — G groups, group j's first
+// row starts[j] = j block —, and the last step's returns and weights R, W [G][N] (row 0 of W is never written: group 0's weights are
+// the plan's d_weights).
 struct TogoRec {
   bool has = false;
   int block = 0, min_tail = 0, G = 0;
   bool stepped = false;  // a step of the record has run: d_weights are group 0's
   std::vector<int32_t> starts;
   DevBuf<float> d_R, d_W;
+  MBD_HIDDEN int set(const mbd_togo* rec, int H, int N, const mbd_env* env);
+  // the layout a record gives at horizon H
+  MBD_HIDDEN void layout(int block_, int min_tail_, int H);
+  // A step's two launches, where the fused score and weighted mean stand without a record: A carries everything but the layout and
+  // the record's buffers.  Groups 0 .. G - 2 hold block Nu elements in tpg tiles each, the last group the rest.
+  MBD_HIDDEN int launch(const float* d_rewss, TogoUpdate A, hipStream_t s);
+  // HOST starts [G], R and W [G][N]; d_weights: the plan's own [N], group 0's once a step of the record has written them
+  MBD_HIDDEN int peek(const mbd_env* env, int N, const float* d_weights, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out) const;
 };
+#undef MBD_HIDDEN
 
 struct mbd_plan {
   mbd_env* env = nullptr;
@@ -254,6 +300,16 @@ struct mbd_plan {
 // the refusal of a call that would disturb an open session (include/mbd_hip.h mbd_plan_mpc_close)
 #define NO_SESSION(p, what) \
   if ((p)->session.open) return fail(MBD_ERR_STATE, what ": a session is open on this plan (mbd_plan_mpc_close first)")
+// the refusal of a record beside a to-go record (who: how the refused record's messages begin), and of a plan-only record on a
+// sharded plan (kind: "adapt", "elite", "to-go")
+static int refuse_beside_togo(const char* who) {
+  return fail(MBD_ERR_UNSUPPORTED, "%s: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon row is not "
+                                   "defined", who);
+}
+static int refuse_sharded(const mbd_plan_config& c, const char* kind) {
+  return fail(MBD_ERR_STATE, "%s record: shard_count=%d of Nsample=%d: sharded plans take no %s record", kind, c.shard_count, c.Nsample,
+              kind);
+}
 
 // ==================================================================================================
 // planner
@@ -325,11 +381,10 @@ extern "C" int mbd_plan_create(mbd_env* env, const mbd_plan_config* cfg, mbd_pla
     HIP_TRY(p->d_ybar_keep.alloc(p->HNu));
   }
   if (cfg->update_method > 0) {
-    HIP_TRY(p->d_sigma.alloc(1));
+    const float one = 1.0f;  // path_integral.py:131
+    HIP_TRY(p->d_sigma.upload(&one, 1));
     HIP_TRY(p->d_spread.alloc(p->HNu));
     HIP_TRY(p->d_idx.alloc(16));
-    const float one = 1.0f;  // path_integral.py:131
-    HIP_TRY(hipMemcpy(p->d_sigma, &one, sizeof(float), hipMemcpyHostToDevice));
   }
   *out = guard.release();
   return MBD_OK;
@@ -394,7 +449,7 @@ static NoiseSpec noise_spec(const mbd_plan* p, bool warm_tick) {
   NoiseSpec ns;
   ns.g = warm_tick ? shape_warm(p) : shape_always(p);
   // under an adapt record the samplers draw under G = a * g: the record's table stands where the caller's shape stood, in every
-  // step — the launches that rewrite it are handed the caller's shape in force (adapt_table)
+  // step — the launches that rewrite it are handed the caller's shape in force (AdaptRec::table)
   if (p->adapt.has) ns.g = p->adapt.d_G.get();
   if (p->has_basis && (warm_tick || p->basis_when == MBD_NOISE_ALWAYS)) {
     ns.W = p->d_basis.get();
@@ -410,105 +465,78 @@ static NoiseSpec noise_warm(const mbd_plan* p) { return noise_spec(p, true); }
 // host back for a second stream that has no job.
 static bool follows_result(const mbd_plan* p) { return p->adapt.has || p->elite.has; }
 
-// ---- the adapt record's launches (include/mbd_hip.h mbd_adapt; set, peek and the debug entries: below) -----------------------
-// The table at the start of a run or a tick, or under a new shape: shift < 0: a = ones, otherwise a shifted `shift` elements forward
-// (0: as it is); G = a * g under the caller's shape g now in force, which the updates that follow keep forming G under.  ONE launch.
-static int adapt_table(mbd_plan* p, int shift, const float* g, hipStream_t s) {
-  AdaptRec& A = p->adapt;
-  if (!A.has) return MBD_OK;
-  A.g_cur = g;
-  hipLaunchKernelGGL(adapt_table_kernel, dim3(1), dim3(kAdaptThreads), 0, s, A.d_a.get(), A.d_G.get(), g, p->HNu, shift);
+// ---- the launches of the adapt, elite and to-go records (what a step and a tick run; set, peek and the debug entries, which run
+// the same members on a scratch record: below, record by record) ------------------------------------------------------------------
+int AdaptRec::table(int shift, const float* g, int HNu, hipStream_t s) {
+  if (!has) return MBD_OK;
+  g_cur = g;
+  hipLaunchKernelGGL(adapt_table_kernel, dim3(1), dim3(kAdaptThreads), 0, s, d_a.get(), d_G.get(), g, HNu, shift);
   HIP_TRY(hipGetLastError());
   return MBD_OK;
-}
-// the two launches of an update on caller-given arrays (a step's: adapt_update; mbd_debug_adapt_step): var into d_buf, then S, a', G'
-// and the log entry.  The weights are staged in LDS while they fit the default 48 KB window, read from memory beyond
-static int adapt_launch(const float* d_w, const float* d_cand, int N, int HNu, const float* d_ybar, int lazy, float sigma,
-                        const float* d_sigma, float* d_buf, float* d_a, const float* d_g, float* d_G, const AdaptRule& R,
-                        float* d_log_S, int* d_log_skipped, hipStream_t s) {
-  const dim3 grid((HNu + kWmE - 1) / kWmE), block(kWmE * kWmG);
-  if ((size_t)N * sizeof(float) <= 48 * 1024)
-    hipLaunchKernelGGL(adapt_spread_kernel<true>, grid, block, sizeof(float) * (size_t)N, s, d_w, d_cand, N, HNu, d_ybar, lazy, sigma,
-                       d_sigma, d_buf);
-  else
-    hipLaunchKernelGGL(adapt_spread_kernel<false>, grid, block, 0, s, d_w, d_cand, N, HNu, d_ybar, lazy, sigma, d_sigma, d_buf);
-  hipLaunchKernelGGL(adapt_finish_kernel, dim3(1), dim3(kAdaptThreads), 0, s, d_buf, HNu, sigma, d_sigma, d_a, d_g, d_G, R, d_log_S,
-                     d_log_skipped);
-  HIP_TRY(hipGetLastError());
-  return MBD_OK;
-}
-// behind the update kernel of step i, on the step's stream: the step's weights, its candidates (or normals) and the Ybar_i and
-// sigma it sampled with — an mppi plan's from the carried device scalar, which its sampler read
-static int adapt_update(mbd_plan* p, int i, const float* d_Ybar_i, const float* d_cand, hipStream_t s) {
-  AdaptRec& A = p->adapt;
-  if (!A.has) return MBD_OK;
-  const int slot = (int)(A.count++ % kAdaptLogCap);
-  return adapt_launch(p->d_weights, d_cand, p->cfg.Nsample, p->HNu, d_Ybar_i, p->lazy ? 1 : 0, p->sigmas[i],
-                      p->cfg.update_method > 0 ? p->d_sigma.get() : nullptr, A.d_buf, A.d_a, A.g_cur, A.d_G, A.rule,
-                      A.d_log_S.get() + slot, A.d_log_skipped.get() + slot, s);
 }
 
-// ---- the elite record's launches (include/mbd_hip.h mbd_elites; set, peek and the debug entries: below) -----------------------
-// The elites at the start of a run or a tick: shift < 0: count = 0, otherwise the present rows shifted `shift` elements forward.
-// ONE launch, a workgroup per row.
-static int elite_table(mbd_plan* p, int shift, hipStream_t s) {
-  EliteRec& L = p->elite;
-  if (!L.has) return MBD_OK;
-  hipLaunchKernelGGL(elite_shift_kernel, dim3(L.n > 0 ? L.n : 1), dim3(kEliteThreads), 0, s, L.d_E.get(), L.d_count.get(), p->HNu, shift);
+int AdaptRec::update(const float* d_w, const StepCand& c, hipStream_t s) {
+  if (!has) return MBD_OK;
+  const long long slot = ring_slot(count, kLogCap);
+  const dim3 grid((c.HNu + kWmE - 1) / kWmE), block(kWmE * kWmG);
+  if ((size_t)c.N * sizeof(float) <= 48 * 1024)
+    hipLaunchKernelGGL(adapt_spread_kernel<true>, grid, block, sizeof(float) * (size_t)c.N, s, d_w, c.cand, c.N, c.HNu, c.ybar_i, c.lazy,
+                       c.sigma, c.d_sigma, d_buf.get());
+  else
+    hipLaunchKernelGGL(adapt_spread_kernel<false>, grid, block, 0, s, d_w, c.cand, c.N, c.HNu, c.ybar_i, c.lazy, c.sigma, c.d_sigma,
+                       d_buf.get());
+  hipLaunchKernelGGL(adapt_finish_kernel, dim3(1), dim3(kAdaptThreads), 0, s, d_buf.get(), c.HNu, c.sigma, c.d_sigma, d_a.get(), g_cur,
+                     d_G.get(), rule, d_log_S.get() + slot, d_log_skipped.get() + slot);
   HIP_TRY(hipGetLastError());
   return MBD_OK;
 }
-// the injection on caller-given arrays (a step's: elite_inject; mbd_debug_elites_inject)
-static int elite_inject_launch(const EliteInject& A, hipStream_t s) {
-  const long long total = (long long)(A.nominal + A.n_elites) * A.HNu;
+
+int EliteRec::table(int shift, int HNu, hipStream_t s) {
+  if (!has) return MBD_OK;
+  hipLaunchKernelGGL(elite_shift_kernel, dim3(n > 0 ? n : 1), dim3(kEliteThreads), 0, s, d_E.get(), d_count.get(), HNu, shift);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+
+int EliteRec::inject(const StepCand& c, const float* g, hipStream_t s) {
+  if (!has) return MBD_OK;
+  EliteInject A{};
+  A.cand = const_cast<float*>(c.cand);  // (the one launch that writes a step's candidates behind their sampler)
+  A.HNu = c.HNu; A.ybar_i = c.ybar_i; A.lazy = c.lazy; A.sigma = c.sigma; A.g = g;
+  A.n_elites = n; A.nominal = nominal; A.E = d_E; A.count = d_count;
+  const long long total = (long long)(nominal + n) * c.HNu;
   hipLaunchKernelGGL(elite_inject_kernel, dim3((unsigned)((total + kEliteThreads - 1) / kEliteThreads)), dim3(kEliteThreads), 0, s, A);
   HIP_TRY(hipGetLastError());
   return MBD_OK;
 }
-// phase 1 of step i, behind the launch that made the step's normals (lazy: eps[cur]) or candidates (d_Y0s), in front of the rollout:
-// g is the shape the step's sampler was handed.  The buffer of a lazy plan no longer holds what its tag says: the ring forgets it.
-static int elite_inject(mbd_plan* p, int i, const float* d_Ybar_i, const float* g, hipStream_t s) {
-  EliteRec& L = p->elite;
-  if (!L.has) return MBD_OK;
-  EliteInject A{};
-  A.cand = p->lazy ? p->ring.eps[p->ring.cur].get() : p->d_Y0s.get();
-  A.HNu = p->HNu; A.ybar_i = d_Ybar_i; A.lazy = p->lazy ? 1 : 0; A.sigma = p->sigmas[i]; A.g = g;
-  A.n_elites = L.n; A.nominal = L.nominal; A.E = L.d_E; A.count = L.d_count;
-  if (p->lazy) p->ring.valid[p->ring.cur] = false;
-  return elite_inject_launch(A, s);
-}
-// phase 2 of step i, behind the step's update kernel (and an adapt record's launches): the selection over the rewards the score read
-static int elite_select(mbd_plan* p, int i, const float* d_Ybar_i, const float* d_cand, const float* d_rews_all, hipStream_t s) {
-  EliteRec& L = p->elite;
-  if (!L.has) return MBD_OK;
-  const int slot = (int)(L.steps++ % kEliteLogCap);
+
+int EliteRec::select(const float* d_rews, const StepCand& c, hipStream_t s) {
+  if (!has) return MBD_OK;
+  const long long slot = ring_slot(steps, kLogCap);
   EliteSelect A{};
-  A.rews = d_rews_all; A.N = p->cfg.Nsample; A.HNu = p->HNu; A.cand = d_cand; A.lazy = p->lazy ? 1 : 0; A.sigma = p->sigmas[i];
-  A.ybar_i = d_Ybar_i; A.n_elites = L.n; A.nominal = L.nominal; A.E = L.d_E; A.R = L.d_R; A.src = L.d_src; A.count = L.d_count;
-  A.log_count = L.d_log_count.get() + slot; A.log_kept = L.d_log_kept.get() + slot; A.log_top = L.d_log_top.get() + slot;
+  A.rews = d_rews; A.N = c.N; A.HNu = c.HNu; A.cand = c.cand; A.lazy = c.lazy; A.sigma = c.sigma; A.ybar_i = c.ybar_i;
+  A.n_elites = n; A.nominal = nominal; A.E = d_E; A.R = d_R; A.src = d_src; A.count = d_count;
+  A.log_count = d_log_count.get() + slot; A.log_kept = d_log_kept.get() + slot; A.log_top = d_log_top.get() + slot;
   hipLaunchKernelGGL(elite_select_kernel, dim3(1), dim3(kScoreThreads), 0, s, A);
   HIP_TRY(hipGetLastError());
   return MBD_OK;
 }
 
-// ---- the to-go record's launches (include/mbd_hip.h mbd_togo; set, peek and the debug entries: below) ------------------------
-// the layout a record gives at horizon H
-static void togo_layout(TogoRec& L, int block, int min_tail, int H) {
-  L.block = block; L.min_tail = min_tail;
-  L.G = togo_groups(H, block, min_tail);
-  L.starts.resize(L.G);
-  for (int j = 0; j < L.G; ++j) L.starts[j] = togo_start(j, block);
+void TogoRec::layout(int block_, int min_tail_, int H) {
+  block = block_; min_tail = min_tail_;
+  G = togo_groups(H, block, min_tail);
+  starts.resize(G);
+  for (int j = 0; j < G; ++j) starts[j] = togo_start(j, block);
 }
-// A step's two launches on caller-given arrays (a plan's step: plan_score_update; mbd_debug_togo_step): A carries everything but
-// the layout and the record's buffers.  Groups 0 .. G - 2 hold block Nu elements in tpg tiles each, the last group the rest.
-static int togo_launch(TogoRec& L, const float* d_rewss, TogoUpdate A, hipStream_t s) {
-  const TogoReturns Rt{A.rews, d_rewss, L.d_R.get(), A.N, A.H, L.block, L.G};
+
+int TogoRec::launch(const float* d_rewss, TogoUpdate A, hipStream_t s) {
+  const TogoReturns Rt{A.rews, d_rewss, d_R.get(), A.N, A.H, block, G};
   hipLaunchKernelGGL(togo_returns_kernel, dim3((A.N + kTogoThreads - 1) / kTogoThreads), dim3(kTogoThreads), 0, s, Rt);
   HIP_TRY(hipGetLastError());
-  const long long last = (long long)(A.H - togo_start(L.G - 1, L.block)) * A.Nu;
-  A.R = L.d_R; A.W = L.d_W; A.G = L.G; A.block = L.block;
-  A.tpg = L.G > 1 ? (int)(((long long)L.block * A.Nu + kWmE - 1) / kWmE) : 1;
-  A.T = (L.G - 1) * A.tpg + (int)((last + kWmE - 1) / kWmE);
+  const long long last = (long long)(A.H - togo_start(G - 1, block)) * A.Nu;
+  A.R = d_R; A.W = d_W; A.G = G; A.block = block;
+  A.tpg = G > 1 ? (int)(((long long)block * A.Nu + kWmE - 1) / kWmE) : 1;
+  A.T = (G - 1) * A.tpg + (int)((last + kWmE - 1) / kWmE);
   hipLaunchKernelGGL(togo_update_kernel, dim3(A.T), dim3(kWmE * kWmG), sizeof(float) * (size_t)A.N, s, A);
   HIP_TRY(hipGetLastError());
   return MBD_OK;
@@ -716,11 +744,15 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
     MBD_TRY(sample_candidates(p, i, key_sample, d_Ybar_i, ns, s));
   }
   // The elite record: ONE launch between the sampler and the rollout rewrites the first rows — the step's mean, the elites the
-  // previous step left
-  MBD_TRY(elite_inject(p, i, d_Ybar_i, ns.g, s));
+  // previous step left; ns.g is the shape the step's sampler was handed.  The buffer of a lazy plan no longer holds what its tag
+  // says: the ring forgets it.
+  const float* d_cand = p->lazy ? ring.eps[ring.cur] : p->d_Y0s;
+  if (p->elite.has) {
+    if (p->lazy) ring.valid[ring.cur] = false;
+    MBD_TRY(p->elite.inject(StepCand{d_cand, N, HNu, p->lazy ? 1 : 0, p->sigmas[i], nullptr, d_Ybar_i}, ns.g, s));
+  }
   // A2/A3: rollout of the local shard
   MBD_TRY(p->timing.begin(s));
-  const float* d_cand = p->lazy ? ring.eps[ring.cur] : p->d_Y0s;
   if (p->lazy) {
     lz.progress = ring.progress;
     lz.progress_val = ++ring.seq;
@@ -825,7 +857,7 @@ static int plan_score_update(mbd_plan* p, int i, const float* d_Ybar_i, const fl
       A.ybar_im1 = d_Ybar_im1; A.ybar_keep = p->d_ybar_keep; A.N = N; A.H = c.Hsample; A.Nu = p->Nu; A.temp = c.temp_sample;
       A.std_guard = c.update_method == 0 ? 1 : 0; A.alpha_i = p->alphas[i]; A.alpha_bar_i = p->alphas_bar[i];
       A.alpha_bar_im1 = p->alphas_bar[i - 1]; A.literal = lit; A.lazy = lazy; A.sigma = sigma_i;
-      MBD_TRY(togo_launch(p->togo, p->d_rewss, A, s));
+      MBD_TRY(p->togo.launch(p->d_rewss, A, s));
       p->togo.stepped = true;
     } else if (fused_score) {
       // XCD pinning (mbd_step_kernels.h pinned_tile): the T tiles on the fewest XCDs X in {1, 2, 4, 8} that give every tile
@@ -862,11 +894,12 @@ static int plan_score_update(mbd_plan* p, int i, const float* d_Ybar_i, const fl
   HIP_TRY(hipGetLastError());
   // The adapt record: TWO launches behind the update kernel rewrite the table the next step samples under, from the weights, the
   // candidates (eps[cur] of a lazy plan: read here in front of the ring's mark, so the weighted mean's argument covers them) and the
-  // Ybar_i the caller has not yet moved on from
-  MBD_TRY(adapt_update(p, i, d_Ybar_i, d_cand, s));
+  // Ybar_i the caller has not yet moved on from — with the sigma the step sampled with, an mppi plan's from the carried device scalar
+  const StepCand sc{d_cand, N, HNu, lazy, sigma_i, c.update_method > 0 ? p->d_sigma.get() : nullptr, d_Ybar_i};
+  if (p->adapt.has) MBD_TRY(p->adapt.update(p->d_weights, sc, s));
   // The elite record: ONE launch in the same place takes the step's best candidates over — from the rewards the score read, the
   // candidates (eps[cur]: in front of the ring's mark as well) and Ybar_i
-  MBD_TRY(elite_select(p, i, d_Ybar_i, d_cand, d_rews_all, s));
+  if (p->elite.has) MBD_TRY(p->elite.select(d_rews_all, sc, s));
   if (p->lazy) {
     p->peek_ybar = p->d_ybar_keep;
     MBD_TRY(p->ring.mark_wmean(s, p->aux != nullptr));
@@ -896,7 +929,7 @@ extern "C" int mbd_plan_get_sigma(mbd_plan* p, float* sigma_out) {
   if (!p->d_sigma) return fail(MBD_ERR_STATE, "not a path-integral plan (update_method == 0)");
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(sigma_out, p->d_sigma, sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(p->d_sigma.download(sigma_out, 1));
   return MBD_OK;
 }
 
@@ -936,7 +969,7 @@ extern "C" int mbd_plan_set_noise_shape(mbd_plan* p, const mbd_noise_shape* rec)
     p->has_shape = true;
   }
   // an adapt record's G = a * g is formed again under the shape now in force outside warm ticks (a run and a tick form their own)
-  MBD_TRY(adapt_table(p, 0, shape_always(p), p->stream));
+  MBD_TRY(p->adapt.table(0, shape_always(p), p->HNu, p->stream));
   if (p->adapt.has) HIP_TRY(hipStreamSynchronize(p->stream));
   return MBD_OK;
 }
@@ -951,15 +984,13 @@ extern "C" int mbd_debug_noise_shaped(const uint32_t key[2], int impl, int N, in
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
   const size_t n = (size_t)N * HNu;
   DevBuf<float> d_g, d_z;
-  HIP_TRY(d_g.alloc(HNu));
-  HIP_TRY(d_z.alloc(n));
-  HIP_TRY(hipMemcpy(d_g, g, sizeof(float) * HNu, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_z, 0xff, sizeof(float) * n));  // (an element left unwritten reads back as NaN)
+  HIP_TRY(d_g.upload(g, HNu));
+  HIP_TRY(d_z.alloc_poisoned(n));  // (an element left unwritten reads back as NaN)
   hipLaunchKernelGGL(noise_shaped_probe_kernel, dim3((unsigned)blocks), dim3(256), 0, nullptr, key[0], key[1], impl, N, HNu, d_z.get(),
                      (const float*)d_g, wide);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(z_out, d_z, sizeof(float) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(d_z.download(z_out, n));
   return MBD_OK;
 }
 
@@ -1008,19 +1039,14 @@ extern "C" int mbd_debug_knot_noise(const uint32_t key[2], int impl, int N, int 
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
   const size_t HNu = (size_t)H * Nu, n = (size_t)N * HNu;
   DevBuf<float> d_W, d_g, d_z;
-  HIP_TRY(d_W.alloc((size_t)H * n_knots));
-  HIP_TRY(d_z.alloc(n));
-  HIP_TRY(hipMemcpy(d_W, W, sizeof(float) * (size_t)H * n_knots, hipMemcpyHostToDevice));
-  if (g) {
-    HIP_TRY(d_g.alloc(HNu));
-    HIP_TRY(hipMemcpy(d_g, g, sizeof(float) * HNu, hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMemset(d_z, 0xff, sizeof(float) * n));  // (an element left unwritten reads back as NaN)
+  HIP_TRY(d_W.upload(W, (size_t)H * n_knots));
+  if (g) HIP_TRY(d_g.upload(g, HNu));  // (without: d_g stays nullptr)
+  HIP_TRY(d_z.alloc_poisoned(n));      // (an element left unwritten reads back as NaN)
   hipLaunchKernelGGL(knot_noise_kernel, dim3((unsigned)blocks), dim3(kKnotThreads), 0, nullptr, key[0], key[1], impl, N, H, Nu, n_knots,
-                     (const float*)d_W, g ? (const float*)d_g : (const float*)nullptr, d_z.get());
+                     (const float*)d_W, (const float*)d_g, d_z.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(z_out, d_z, sizeof(float) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(d_z.download(z_out, n));
   return MBD_OK;
 }
 
@@ -1108,9 +1134,9 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
     HIP_TRY(hipMemcpy(p->d_sigma, &one, sizeof(float), hipMemcpyHostToDevice));
   }
   HIP_TRY(hipMemsetAsync(cur, 0, sizeof(float) * HNu, s));
-  MBD_TRY(adapt_table(p, -1, shape_always(p), s));  // (an adapt record: a = ones, and its log begins)
+  MBD_TRY(p->adapt.table(-1, shape_always(p), HNu, s));  // (an adapt record: a = ones, and its log begins)
   p->adapt.count = 0;
-  MBD_TRY(elite_table(p, -1, s));  // (an elite record: no elites, and its log begins)
+  MBD_TRY(p->elite.table(-1, HNu, s));  // (an elite record: no elites, and its log begins)
   p->elite.steps = 0;
   HIP_TRY(hipStreamSynchronize(s));
   p->wt.begin();
@@ -1124,12 +1150,12 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
   HIP_TRY(hipStreamSynchronize(s));
   auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
-  if (mu_0ts_out) HIP_TRY(hipMemcpy(mu_0ts_out, p->d_mu, sizeof(float) * (size_t)(Nd - 1) * HNu, hipMemcpyDeviceToHost));
-  if (rew_means_out) HIP_TRY(hipMemcpy(rew_means_out, p->d_rewmeans, sizeof(float) * (size_t)(Nd - 1), hipMemcpyDeviceToHost));
+  HIP_TRY(p->d_mu.download(mu_0ts_out, (size_t)(Nd - 1) * HNu));
+  HIP_TRY(p->d_rewmeans.download(rew_means_out, (size_t)(Nd - 1)));
   if (rew_final_out) {  // rollout_us(state_init, Yi[-1]).mean()  (mbd_planner.py:179-180)
     MBD_TRY(launch_rollout(p->env, p->d_state0, cur, 1, p->cfg.Hsample, nullptr, p->d_scratch, nullptr, nullptr, s));
     HIP_TRY(hipStreamSynchronize(s));
-    HIP_TRY(hipMemcpy(rew_final_out, p->d_scratch, sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(p->d_scratch.download(rew_final_out, 1));
   }
   return MBD_OK;
 }
@@ -1354,9 +1380,7 @@ extern "C" int mbd_plan_peek_mpc_predicted(mbd_plan* p, float* predicted_out) {
   if (p->delay.pred_ticks < 1) return fail(MBD_ERR_STATE, "peek_mpc_predicted: no episode has run with the record yet");
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipDeviceSynchronize());
-  if (predicted_out)
-    HIP_TRY(hipMemcpy(predicted_out, p->d_mpc_pred, sizeof(float) * (size_t)p->delay.pred_ticks * p->env->state_size(),
-                      hipMemcpyDeviceToHost));
+  HIP_TRY(p->d_mpc_pred.download(predicted_out, (size_t)p->delay.pred_ticks * p->env->state_size()));
   return MBD_OK;
 }
 
@@ -1453,8 +1477,7 @@ int DemoRec::peek(int device, int k, float* err_out, float* windows_out, const c
     HIP_TRY(hipMemcpy(tmp.data(), d_err, sizeof(float) * tmp.size(), hipMemcpyDeviceToHost));
     for (size_t t = 0; t < T; ++t) memcpy(err_out + t * EK, tmp.data() + (t * P + (size_t)k) * EK, sizeof(float) * EK);
   }
-  if (windows_out)
-    HIP_TRY(hipMemcpy(windows_out, d_windows, sizeof(float) * T * K * kXrefRows * C, hipMemcpyDeviceToHost));
+  HIP_TRY(d_windows.download(windows_out, T * K * kXrefRows * C));
   return MBD_OK;
 }
 
@@ -1567,9 +1590,7 @@ extern "C" int mbd_plan_set_ensemble(mbd_plan* p, const mbd_ensemble* rec) {
     p->ens_rec = mbd_ensemble{};
     return MBD_OK;
   }
-  if (p->togo.has)  // (before check_ensemble, which may read the members' reference from the device)
-    return fail(MBD_ERR_UNSUPPORTED, "ensemble: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
-                                     "row is not defined");
+  if (p->togo.has) return refuse_beside_togo("ensemble");  // (before check_ensemble, which may read the members' reference from the device)
   MBD_TRY(check_ensemble(p, rec));
   if (p->pick.has)
     return fail(MBD_ERR_UNSUPPORTED, "ensemble: the plan carries a pick record (mbd_plan_set_mpc_pick): the pick compares returns, an "
@@ -1599,8 +1620,8 @@ extern "C" int mbd_plan_peek_ensemble(mbd_plan* p, float* rews_members_out, floa
   HIP_TRY(hipSetDevice(p->env->device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t N = (size_t)p->cfg.Nsample, M = (size_t)p->ens_rec.n_members;
-  if (rews_members_out) HIP_TRY(hipMemcpy(rews_members_out, p->d_ens_rews, sizeof(float) * M * N, hipMemcpyDeviceToHost));
-  if (rews_out) HIP_TRY(hipMemcpy(rews_out, p->d_ens_comb, sizeof(float) * N, hipMemcpyDeviceToHost));
+  HIP_TRY(p->d_ens_rews.download(rews_members_out, M * N));
+  HIP_TRY(p->d_ens_comb.download(rews_out, N));
   return MBD_OK;
 }
 
@@ -1772,9 +1793,7 @@ extern "C" int mbd_plan_set_objective(mbd_plan* p, const mbd_objective* rec) {
   NO_SESSION(p, "set_objective");
   float wsum = 0.0f;
   if (rec) MBD_TRY(check_objective(rec, p->cfg.Hsample, p->Nu, &wsum));  // (before any device access)
-  if (rec && p->togo.has)
-    return fail(MBD_ERR_UNSUPPORTED, "objective record: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
-                                     "row is not defined");
+  if (rec && p->togo.has) return refuse_beside_togo("objective record");
   return p->obj.set(rec, wsum, p->env->device, 1, p->cfg.Nsample, p->cfg.Hsample, p->Nu, (size_t)MBD_MAX_ENSEMBLE * p->cfg.Nsample);
 }
 
@@ -1880,8 +1899,7 @@ int ValueRec::set(const mbd_value* rec, const mbd_env* env, size_t max_rows_, in
     net.insert(net.end(), rec->b[l], rec->b[l] + W);
     K = W;
   }
-  HIP_TRY(d_net.alloc(net.size()));
-  HIP_TRY(hipMemcpy(d_net, net.data(), sizeof(float) * net.size(), hipMemcpyHostToDevice));
+  HIP_TRY(d_net.upload(net.data(), net.size()));
   HIP_TRY(d_final.grow(max_rows * S));
   HIP_TRY(d_v.grow(max_rows));
   HIP_TRY(d_pick_final.grow((size_t)3 * P * S));
@@ -1929,7 +1947,7 @@ int ValueRec::peek(const mbd_env* env, float* v_out, const char* what) const {
   if (!stepped) return fail(MBD_ERR_STATE, "peek_value: no diffusion step with the record to show yet");
   HIP_TRY(hipSetDevice(env->device));
   HIP_TRY(hipDeviceSynchronize());
-  if (v_out) HIP_TRY(hipMemcpy(v_out, d_v.get(), sizeof(float) * rows, hipMemcpyDeviceToHost));
+  HIP_TRY(d_v.download(v_out, rows));
   return MBD_OK;
 }
 
@@ -1943,7 +1961,7 @@ int ValueRec::eval(const mbd_env* env, const float* states, int B, float* v_out,
   HIP_TRY(hipMemcpy(d_eval_in, states, sizeof(float) * (size_t)B * S, hipMemcpyHostToDevice));
   MBD_TRY(launch(d_eval_in, nullptr, B, d_eval_v, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(v_out, d_eval_v.get(), sizeof(float) * B, hipMemcpyDeviceToHost));
+  HIP_TRY(d_eval_v.download(v_out, B));
   return MBD_OK;
 }
 
@@ -1953,9 +1971,7 @@ extern "C" int mbd_plan_set_value(mbd_plan* p, const mbd_value* rec) {
   if (rec) MBD_TRY(check_value(rec, p->env->state_size(), p->env->kind == ENV_MODEL));  // (before any device access)
   if (rec && p->has_ens)
     return fail(MBD_ERR_STATE, "value record: the plan carries an ensemble record (an ensemble launch returns rewards only)");
-  if (rec && p->togo.has)
-    return fail(MBD_ERR_UNSUPPORTED, "value record: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
-                                     "row is not defined");
+  if (rec && p->togo.has) return refuse_beside_togo("value record");
   return p->val.set(rec, p->env, (size_t)p->cfg.shard_count, 1);
 }
 
@@ -2119,9 +2135,7 @@ extern "C" int mbd_plan_set_weighting(mbd_plan* p, const mbd_weighting* rec) {
   if (rec) MBD_TRY(check_weighting(rec));  // (before any device access)
   if (rec && p->cfg.enable_demo)
     return fail(MBD_ERR_UNSUPPORTED, "weighting record: enable_demo=1: the demo blend standardises twice, an ESS target is not defined there");
-  if (rec && p->togo.has)
-    return fail(MBD_ERR_UNSUPPORTED, "weighting record: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
-                                     "row is not defined");
+  if (rec && p->togo.has) return refuse_beside_togo("weighting record");
   return p->wt.set(rec, p->env->device, 1, p->cfg.Ndiffuse - 1, p->cfg.Nsample);
 }
 
@@ -2164,7 +2178,7 @@ int PickRec::set(const mbd_mpc_pick* rec, int device, int P_, int HNu_, int H_) 
 
 int PickRec::start(long long n_ticks) {
   if (!has) return MBD_OK;
-  const int want = (int)(n_ticks < kPickLogCap ? (n_ticks < 1 ? 1 : n_ticks) : kPickLogCap);
+  const int want = (int)(n_ticks < kLogCap ? (n_ticks < 1 ? 1 : n_ticks) : kLogCap);
   HIP_TRY(d_log_choice.grow((size_t)P * want));
   HIP_TRY(d_log_rets.grow((size_t)P * want * 3));
   HIP_TRY(d_log_best.grow((size_t)P * want));
@@ -2199,7 +2213,7 @@ int PickRec::tick(mbd_env* env, ObjectiveRec& obj, const ValueRec& val, const Pi
   MBD_TRY(launch_rollout(env, tk.state, d_slots, 3 * P, H, d_rewss, d_rets, nullptr, val.pick_final(), s, nullptr, P > 1 ? sw : nullptr));
   if (obj.has) MBD_TRY(obj.launch_rows(d_rewss, d_rets, 3, d_slots, d_obj_ret, d_obj_cost, P > 1, s));
   MBD_TRY(val.launch(val.pick_final(), d_rets, 3 * P, val.d_pick_v, s));
-  const long long at = count % cap;
+  const long long at = count % cap;  // (ring_slot's slot; count advances behind the launch check)
   PickChoose C;
   C.rets = d_rets; C.slots = d_slots; C.best = d_best; C.HNu = HNu; C.mask = mask; C.cold = tk.cold;
   C.out = tk.M; C.out_stride = tk.M_stride;
@@ -2218,18 +2232,10 @@ int PickRec::peek(const mbd_env* env, int k, int32_t* choice_out, float* rets_ou
   if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_mpc_pick: capacity=%d", capacity);
   HIP_TRY(hipSetDevice(env->device));
   HIP_TRY(hipDeviceSynchronize());
-  long long n = count < capacity ? count : capacity;
-  if (n > cap) n = cap;
-  // tick count - n + j lies at its index modulo cap: one run of entries, or two where the ring wraps — at most two copies per log
-  for (long long j = 0; j < n;) {
-    const long long slot = (count - n + j) % cap;
-    const long long run = n - j < cap - slot ? n - j : cap - slot;
-    const size_t at = (size_t)k * cap + (size_t)slot;
-    if (choice_out) HIP_TRY(hipMemcpy(choice_out + j, d_log_choice.get() + at, sizeof(int32_t) * run, hipMemcpyDeviceToHost));
-    if (rets_out) HIP_TRY(hipMemcpy(rets_out + 3 * j, d_log_rets.get() + 3 * at, sizeof(float) * 3 * run, hipMemcpyDeviceToHost));
-    if (best_out) HIP_TRY(hipMemcpy(best_out + j, d_log_best.get() + at, sizeof(int32_t) * run, hipMemcpyDeviceToHost));
-    j += run;
-  }
+  const size_t at = (size_t)k * cap;  // (plan k's rings)
+  MBD_TRY(ring_read(d_log_choice.get() + at, 1, count, cap, capacity, choice_out));
+  MBD_TRY(ring_read(d_log_rets.get() + 3 * at, 3, count, cap, capacity, rets_out));
+  MBD_TRY(ring_read(d_log_best.get() + at, 1, count, cap, capacity, best_out));
   if (count_out) *count_out = (int)(count < 0x7fffffff ? count : 0x7fffffff);
   return MBD_OK;
 }
@@ -2257,13 +2263,12 @@ extern "C" int mbd_debug_pick_best(const float* rews, int P, int N, int32_t* bes
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
   DevBuf<float> d_rews;
   DevBuf<int> d_best;
-  HIP_TRY(d_rews.alloc((size_t)P * N));
+  HIP_TRY(d_rews.upload(rews, (size_t)P * N));
   HIP_TRY(d_best.alloc(P));
-  HIP_TRY(hipMemcpy(d_rews, rews, sizeof(float) * (size_t)P * N, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(pick_best_probe_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), 0, 0, (const float*)d_rews, N, d_best.get());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(best_out, d_best, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
+  HIP_TRY(d_best.download(best_out, P));
   return MBD_OK;
 }
 
@@ -2290,57 +2295,52 @@ extern "C" int mbd_debug_check_adapt(const mbd_adapt* rec, int update_method, in
   return check_adapt(rec, update_method, enable_demo);
 }
 
+int AdaptRec::set(const mbd_adapt* rec, int HNu, const float* g, const mbd_env* env, hipStream_t s) {
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read G or write the log)
+  has = false;
+  count = 0;
+  if (!rec) return MBD_OK;
+  HIP_TRY(d_a.grow(HNu));
+  HIP_TRY(d_G.grow(HNu));
+  HIP_TRY(d_buf.grow(HNu));
+  HIP_TRY(d_log_S.grow(kLogCap));
+  HIP_TRY(d_log_skipped.grow(kLogCap));
+  rule = AdaptRule{rec->rate, rec->a_min, rec->a_max};
+  carry = rec->carry;
+  has = true;
+  MBD_TRY(table(-1, g, HNu, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return MBD_OK;
+}
+
+int AdaptRec::peek(const mbd_env* env, int HNu, float* a_out, float* ratio_out, int32_t* skipped_out, int capacity, int* count_out) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_adapt: the plan has no adapt record");
+  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_adapt: capacity=%d", capacity);
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(d_a.download(a_out, HNu));
+  MBD_TRY(ring_read(d_log_S.get(), 1, count, kLogCap, capacity, ratio_out));
+  MBD_TRY(ring_read(d_log_skipped.get(), 1, count, kLogCap, capacity, skipped_out));
+  if (count_out) *count_out = (int)(count < 0x7fffffffll ? count : 0x7fffffffll);
+  return MBD_OK;
+}
+
 extern "C" int mbd_plan_set_adapt(mbd_plan* p, const mbd_adapt* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
   if (rec) MBD_TRY(check_adapt(rec, p->cfg.update_method, p->cfg.enable_demo));  // (before any device access)
-  if (rec && p->cfg.shard_count != p->cfg.Nsample)
-    return fail(MBD_ERR_STATE, "adapt record: shard_count=%d of Nsample=%d: sharded plans take no adapt record", p->cfg.shard_count,
-                p->cfg.Nsample);
+  if (rec && p->cfg.shard_count != p->cfg.Nsample) return refuse_sharded(p->cfg, "adapt");
   NO_SESSION(p, "set_adapt");
-  if (rec && p->togo.has)
-    return fail(MBD_ERR_UNSUPPORTED, "adapt record: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon "
-                                     "row is not defined");
-  AdaptRec& A = p->adapt;
-  if (!rec && !A.has) return MBD_OK;  // (nothing to clear: no device is touched)
-  HIP_TRY(hipSetDevice(p->env->device));
-  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read G or write the log)
+  if (rec && p->togo.has) return refuse_beside_togo("adapt record");
+  if (!rec && !p->adapt.has) return MBD_OK;  // (nothing to clear: no device is touched)
   // normals prepared ahead were made under another table: as mbd_plan_set_noise_shape, nothing prepared survives
   p->ring.forget();
-  A.has = false;
-  A.count = 0;
-  if (!rec) return MBD_OK;
-  HIP_TRY(A.d_a.grow(p->HNu));
-  HIP_TRY(A.d_G.grow(p->HNu));
-  HIP_TRY(A.d_buf.grow(p->HNu));
-  HIP_TRY(A.d_log_S.grow(kAdaptLogCap));
-  HIP_TRY(A.d_log_skipped.grow(kAdaptLogCap));
-  A.rule = AdaptRule{rec->rate, rec->a_min, rec->a_max};
-  A.carry = rec->carry;
-  A.has = true;
-  MBD_TRY(adapt_table(p, -1, shape_always(p), p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return MBD_OK;
+  return p->adapt.set(rec, p->HNu, shape_always(p), p->env, p->stream);
 }
 
 extern "C" int mbd_plan_peek_adapt(mbd_plan* p, float* a_out, float* ratio_out, int32_t* skipped_out, int capacity, int* count_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
-  const AdaptRec& A = p->adapt;
-  if (!A.has) return fail(MBD_ERR_STATE, "peek_adapt: the plan has no adapt record");
-  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_adapt: capacity=%d", capacity);
-  HIP_TRY(hipSetDevice(p->env->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (a_out) HIP_TRY(hipMemcpy(a_out, A.d_a, sizeof(float) * p->HNu, hipMemcpyDeviceToHost));
-  long long n = A.count < kAdaptLogCap ? A.count : kAdaptLogCap;
-  if (n > capacity) n = capacity;
-  // the most recent n entries, oldest first: the ring may wrap between two of them — two pieces at the most
-  const size_t first = (size_t)((A.count - n) % kAdaptLogCap);
-  const size_t n0 = (size_t)n < kAdaptLogCap - first ? (size_t)n : kAdaptLogCap - first, n1 = (size_t)n - n0;
-  if (ratio_out && n0) HIP_TRY(hipMemcpy(ratio_out, A.d_log_S.get() + first, sizeof(float) * n0, hipMemcpyDeviceToHost));
-  if (ratio_out && n1) HIP_TRY(hipMemcpy(ratio_out + n0, A.d_log_S.get(), sizeof(float) * n1, hipMemcpyDeviceToHost));
-  if (skipped_out && n0) HIP_TRY(hipMemcpy(skipped_out, A.d_log_skipped.get() + first, sizeof(int32_t) * n0, hipMemcpyDeviceToHost));
-  if (skipped_out && n1) HIP_TRY(hipMemcpy(skipped_out + n0, A.d_log_skipped.get(), sizeof(int32_t) * n1, hipMemcpyDeviceToHost));
-  if (count_out) *count_out = (int)(A.count < 0x7fffffffll ? A.count : 0x7fffffffll);
-  return MBD_OK;
+  return p->adapt.peek(p->env, p->HNu, a_out, ratio_out, skipped_out, capacity, count_out);
 }
 
 // include/mbd_hip_debug.h: the update on the HOST — the per-element functions the kernels call (one text for host and device), the
@@ -2393,48 +2393,36 @@ extern "C" int mbd_debug_adapt_host(const float* w, const float* cand, int N, in
   if (skipped_out) *skipped_out = skip ? 1 : 0;
   return MBD_OK;
 }
-// ... and on the DEVICE: the table kernel forms G = a * g from the uploaded arrays, then the update's two launches
+// ... and on the DEVICE, by a scratch record's own launches: its table launch forms G = a * g from the uploaded arrays, then the
+// update's two.  The log is one entry long (count = 0: slot 0); what is read back and left unwritten reads back as NaN, or -1.
 extern "C" int mbd_debug_adapt_step(const float* w, const float* cand, int N, int HNu, const float* ybar, float sigma,
                                     int sigma_on_device, int lazy, const float* a, const float* g, float rate, float a_min, float a_max,
                                     float* a_out, float* G_out, float* S_out, int32_t* skipped_out) {
   MBD_TRY(check_adapt_step_args("adapt_step", w, cand, N, HNu, ybar, a, rate, a_min, a_max));
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
-  const size_t n = (size_t)N * HNu;
-  DevBuf<float> d_w, d_cand, d_ybar, d_a, d_g, d_G, d_buf, d_sigma, d_S;
-  DevBuf<int> d_skip;
-  HIP_TRY(d_w.alloc(N));
-  HIP_TRY(d_cand.alloc(n));
-  HIP_TRY(d_ybar.alloc(HNu));
-  HIP_TRY(d_a.alloc(HNu));
-  HIP_TRY(d_G.alloc(HNu));
-  HIP_TRY(d_buf.alloc(HNu));
-  HIP_TRY(d_sigma.alloc(1));
-  HIP_TRY(d_S.alloc(1));
-  HIP_TRY(d_skip.alloc(1));
-  if (g) {
-    HIP_TRY(d_g.alloc(HNu));
-    HIP_TRY(hipMemcpy(d_g, g, sizeof(float) * HNu, hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMemcpy(d_w, w, sizeof(float) * N, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_cand, cand, sizeof(float) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_ybar, ybar, sizeof(float) * HNu, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_a, a, sizeof(float) * HNu, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_sigma, &sigma, sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_G, 0xff, sizeof(float) * HNu));  // (what is read back and left unwritten reads back as NaN, or -1)
-  HIP_TRY(hipMemset(d_buf, 0xff, sizeof(float) * HNu));
-  HIP_TRY(hipMemset(d_S, 0xff, sizeof(float)));
-  HIP_TRY(hipMemset(d_skip, 0xff, sizeof(int)));
-  const float* dg = g ? d_g.get() : nullptr;
-  hipLaunchKernelGGL(adapt_table_kernel, dim3(1), dim3(kAdaptThreads), 0, nullptr, d_a.get(), d_G.get(), dg, HNu, 0);
-  HIP_TRY(hipGetLastError());
+  DevBuf<float> d_w, d_cand, d_ybar, d_g, d_sigma;
+  AdaptRec A;
+  HIP_TRY(d_w.upload(w, N));
+  HIP_TRY(d_cand.upload(cand, (size_t)N * HNu));
+  HIP_TRY(d_ybar.upload(ybar, HNu));
+  if (g) HIP_TRY(d_g.upload(g, HNu));  // (without: d_g stays nullptr)
+  HIP_TRY(d_sigma.upload(&sigma, 1));
+  HIP_TRY(A.d_a.upload(a, HNu));
+  HIP_TRY(A.d_G.alloc_poisoned(HNu));
+  HIP_TRY(A.d_buf.alloc_poisoned(HNu));
+  HIP_TRY(A.d_log_S.alloc_poisoned(1));
+  HIP_TRY(A.d_log_skipped.alloc_poisoned(1));
+  A.rule = AdaptRule{rate, a_min, a_max};
+  A.has = true;
+  MBD_TRY(A.table(0, d_g, HNu, nullptr));
   // (sigma from the device scalar: the host value handed to the kernels is then a NaN they must not use)
-  MBD_TRY(adapt_launch(d_w, d_cand, N, HNu, d_ybar, lazy ? 1 : 0, sigma_on_device ? __builtin_nanf("") : sigma,
-                       sigma_on_device ? d_sigma.get() : nullptr, d_buf, d_a, dg, d_G, AdaptRule{rate, a_min, a_max}, d_S, d_skip, nullptr));
+  MBD_TRY(A.update(d_w, StepCand{d_cand, N, HNu, lazy ? 1 : 0, sigma_on_device ? __builtin_nanf("") : sigma,
+                                 sigma_on_device ? d_sigma.get() : nullptr, d_ybar}, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  if (a_out) HIP_TRY(hipMemcpy(a_out, d_a, sizeof(float) * HNu, hipMemcpyDeviceToHost));
-  if (G_out) HIP_TRY(hipMemcpy(G_out, d_G, sizeof(float) * HNu, hipMemcpyDeviceToHost));
-  if (S_out) HIP_TRY(hipMemcpy(S_out, d_S, sizeof(float), hipMemcpyDeviceToHost));
-  if (skipped_out) HIP_TRY(hipMemcpy(skipped_out, d_skip, sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(A.d_a.download(a_out, HNu));
+  HIP_TRY(A.d_G.download(G_out, HNu));
+  HIP_TRY(A.d_log_S.download(S_out, 1));
+  HIP_TRY(A.d_log_skipped.download(skipped_out, 1));
   return MBD_OK;
 }
 
@@ -2463,69 +2451,61 @@ extern "C" int mbd_debug_check_elites(const mbd_elites* rec, int Nsample, int up
   return check_elites(rec, Nsample, update_method, enable_demo);
 }
 
-extern "C" int mbd_plan_set_elites(mbd_plan* p, const mbd_elites* rec) {
-  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
-  if (rec) MBD_TRY(check_elites(rec, p->cfg.Nsample, p->cfg.update_method, p->cfg.enable_demo));  // (before any device access)
-  if (rec && p->cfg.shard_count != p->cfg.Nsample)
-    return fail(MBD_ERR_STATE, "elite record: shard_count=%d of Nsample=%d: sharded plans take no elite record", p->cfg.shard_count,
-                p->cfg.Nsample);
-  NO_SESSION(p, "set_elites");
-  EliteRec& L = p->elite;
-  if (!rec && !L.has) return MBD_OK;  // (nothing to clear: no device is touched)
-  HIP_TRY(hipSetDevice(p->env->device));
+int EliteRec::set(const mbd_elites* rec, int HNu, const mbd_env* env, hipStream_t s) {
+  HIP_TRY(hipSetDevice(env->device));
   HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the elites or write the log)
-  // normals prepared ahead are not what the record's steps take, and a buffer the record rewrote is not what its tag said: as
-  // mbd_plan_set_noise_shape, nothing prepared survives — in either direction
-  p->ring.forget();
-  L.has = false;
-  L.steps = 0;
+  has = false;
+  steps = 0;
   if (!rec) return MBD_OK;
-  const size_t n = rec->n_elites > 0 ? (size_t)rec->n_elites : 1;
-  HIP_TRY(L.d_E.grow(n * p->HNu));
-  HIP_TRY(L.d_R.grow(n));
-  HIP_TRY(L.d_src.grow(n));
-  HIP_TRY(L.d_count.grow(1));
-  HIP_TRY(L.d_log_count.grow(kEliteLogCap));
-  HIP_TRY(L.d_log_kept.grow(kEliteLogCap));
-  HIP_TRY(L.d_log_top.grow(kEliteLogCap));
-  L.n = rec->n_elites;
-  L.nominal = rec->nominal;
-  L.carry = rec->carry;
-  L.has = true;
-  MBD_TRY(elite_table(p, -1, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t rows = rec->n_elites > 0 ? (size_t)rec->n_elites : 1;
+  HIP_TRY(d_E.grow(rows * HNu));
+  HIP_TRY(d_R.grow(rows));
+  HIP_TRY(d_src.grow(rows));
+  HIP_TRY(d_count.grow(1));
+  HIP_TRY(d_log_count.grow(kLogCap));
+  HIP_TRY(d_log_kept.grow(kLogCap));
+  HIP_TRY(d_log_top.grow(kLogCap));
+  n = rec->n_elites; nominal = rec->nominal; carry = rec->carry;
+  has = true;
+  MBD_TRY(table(-1, HNu, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return MBD_OK;
 }
 
-// the most recent n entries of a device ring of kEliteLogCap entries that has seen `steps`, oldest first: two pieces at the most
-template <typename T>
-static int elite_log_read(const T* d_ring, long long steps, long long n, T* out) {
-  if (!out || n <= 0) return MBD_OK;
-  const size_t first = (size_t)((steps - n) % kEliteLogCap);
-  const size_t n0 = (size_t)n < kEliteLogCap - first ? (size_t)n : kEliteLogCap - first, n1 = (size_t)n - n0;
-  HIP_TRY(hipMemcpy(out, d_ring + first, sizeof(T) * n0, hipMemcpyDeviceToHost));
-  if (n1) HIP_TRY(hipMemcpy(out + n0, d_ring, sizeof(T) * n1, hipMemcpyDeviceToHost));
+int EliteRec::peek(const mbd_env* env, int HNu, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
+                   int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_elites: the plan has no elite record");
+  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_elites: capacity=%d", capacity);
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(d_E.download(elites_out, (size_t)n * HNu));
+  HIP_TRY(d_R.download(returns_out, n));
+  HIP_TRY(d_src.download(src_out, n));
+  HIP_TRY(d_count.download(count_out, 1));
+  MBD_TRY(ring_read(d_log_count.get(), 1, steps, kLogCap, capacity, log_count));
+  MBD_TRY(ring_read(d_log_kept.get(), 1, steps, kLogCap, capacity, log_kept));
+  MBD_TRY(ring_read(d_log_top.get(), 1, steps, kLogCap, capacity, log_top));
+  if (n_log_out) *n_log_out = (int)(steps < 0x7fffffffll ? steps : 0x7fffffffll);
   return MBD_OK;
 }
+
+extern "C" int mbd_plan_set_elites(mbd_plan* p, const mbd_elites* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (rec) MBD_TRY(check_elites(rec, p->cfg.Nsample, p->cfg.update_method, p->cfg.enable_demo));  // (before any device access)
+  if (rec && p->cfg.shard_count != p->cfg.Nsample) return refuse_sharded(p->cfg, "elite");
+  NO_SESSION(p, "set_elites");
+  if (!rec && !p->elite.has) return MBD_OK;  // (nothing to clear: no device is touched)
+  // normals prepared ahead are not what the record's steps take, and a buffer the record rewrote is not what its tag said: as
+  // mbd_plan_set_noise_shape, nothing prepared survives — in either direction
+  p->ring.forget();
+  return p->elite.set(rec, p->HNu, p->env, p->stream);
+}
+
 extern "C" int mbd_plan_peek_elites(mbd_plan* p, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
                                     int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
-  const EliteRec& L = p->elite;
-  if (!L.has) return fail(MBD_ERR_STATE, "peek_elites: the plan has no elite record");
-  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_elites: capacity=%d", capacity);
-  HIP_TRY(hipSetDevice(p->env->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (elites_out && L.n) HIP_TRY(hipMemcpy(elites_out, L.d_E, sizeof(float) * (size_t)L.n * p->HNu, hipMemcpyDeviceToHost));
-  if (returns_out && L.n) HIP_TRY(hipMemcpy(returns_out, L.d_R, sizeof(float) * L.n, hipMemcpyDeviceToHost));
-  if (src_out && L.n) HIP_TRY(hipMemcpy(src_out, L.d_src, sizeof(int32_t) * L.n, hipMemcpyDeviceToHost));
-  if (count_out) HIP_TRY(hipMemcpy(count_out, L.d_count, sizeof(int32_t), hipMemcpyDeviceToHost));
-  long long n = L.steps < kEliteLogCap ? L.steps : kEliteLogCap;
-  if (n > capacity) n = capacity;
-  MBD_TRY(elite_log_read<int>(L.d_log_count, L.steps, n, log_count));
-  MBD_TRY(elite_log_read<int>(L.d_log_kept, L.steps, n, log_kept));
-  MBD_TRY(elite_log_read<float>(L.d_log_top, L.steps, n, log_top));
-  if (n_log_out) *n_log_out = (int)(L.steps < 0x7fffffffll ? L.steps : 0x7fffffffll);
-  return MBD_OK;
+  return p->elite.peek(p->env, p->HNu, elites_out, returns_out, src_out, count_out, log_count, log_kept, log_top, capacity,
+                       n_log_out);
 }
 
 // include/mbd_hip_debug.h: one step of the record on the HOST — the injection, then the selection — from the functions the kernels
@@ -2585,34 +2565,26 @@ extern "C" int mbd_debug_elites_host(const float* rews, const float* cand, int N
   if (top_out) *top_out = cnt > 0 ? R[0] : __builtin_bit_cast(float, 0x7fc00000u);
   return MBD_OK;
 }
-// ... and the two launches alone on the DEVICE, on caller-given arrays.  What is read back is filled with all-ones bits first.
+// ... and the two launches alone on the DEVICE, on caller-given arrays, by a scratch record's own members.  What is read back is
+// filled with all-ones bits first; the log is one entry long (steps = 0: slot 0).
 extern "C" int mbd_debug_elites_inject(const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy, const float* g,
                                        int n_elites, int nominal, const float* E_in, int count_in, float* cand_out) {
   MBD_TRY(check_elites_args("elites_inject", cand, N, HNu, ybar, sigma, lazy, n_elites, nominal, E_in, count_in));
   if (!cand_out) return fail(MBD_ERR_INVALID, "elites_inject: NULL argument");
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
-  const size_t n = (size_t)N * HNu, ne = (size_t)(n_elites > 0 ? n_elites : 1) * HNu;
-  DevBuf<float> d_cand, d_ybar, d_g, d_E;
-  DevBuf<int> d_count;
-  HIP_TRY(d_cand.alloc(n));
-  HIP_TRY(d_ybar.alloc(HNu));
-  HIP_TRY(d_E.alloc(ne));
-  HIP_TRY(d_count.alloc(1));
-  if (g) {
-    HIP_TRY(d_g.alloc(HNu));
-    HIP_TRY(hipMemcpy(d_g, g, sizeof(float) * HNu, hipMemcpyHostToDevice));
-  }
-  HIP_TRY(hipMemcpy(d_cand, cand, sizeof(float) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_ybar, ybar, sizeof(float) * HNu, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_E, 0xff, sizeof(float) * ne));
-  if (count_in > 0) HIP_TRY(hipMemcpy(d_E, E_in, sizeof(float) * (size_t)count_in * HNu, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_count, &count_in, sizeof(int), hipMemcpyHostToDevice));
-  EliteInject A{};
-  A.cand = d_cand; A.HNu = HNu; A.ybar_i = d_ybar; A.lazy = lazy ? 1 : 0; A.sigma = sigma; A.g = g ? d_g.get() : nullptr;
-  A.n_elites = n_elites; A.nominal = nominal; A.E = d_E; A.count = d_count;
-  MBD_TRY(elite_inject_launch(A, nullptr));
+  const size_t n = (size_t)N * HNu;
+  DevBuf<float> d_cand, d_ybar, d_g;
+  EliteRec L;
+  L.n = n_elites; L.nominal = nominal; L.has = true;
+  HIP_TRY(d_cand.upload(cand, n));
+  HIP_TRY(d_ybar.upload(ybar, HNu));
+  if (g) HIP_TRY(d_g.upload(g, HNu));  // (without: d_g stays nullptr)
+  HIP_TRY(L.d_E.alloc_poisoned((size_t)(n_elites > 0 ? n_elites : 1) * HNu));
+  if (count_in > 0) HIP_TRY(hipMemcpy(L.d_E, E_in, sizeof(float) * (size_t)count_in * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(L.d_count.upload(&count_in, 1));
+  MBD_TRY(L.inject(StepCand{d_cand, N, HNu, lazy ? 1 : 0, sigma, nullptr, d_ybar}, d_g, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(cand_out, d_cand, sizeof(float) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(d_cand.download(cand_out, n));
   return MBD_OK;
 }
 extern "C" int mbd_debug_elites_select(const float* rews, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy,
@@ -2622,47 +2594,33 @@ extern "C" int mbd_debug_elites_select(const float* rews, const float* cand, int
   if (!rews) return fail(MBD_ERR_INVALID, "elites_select: NULL argument");
   if (count_in < 0 || count_in > n_elites) return fail(MBD_ERR_INVALID, "elites_select: count=%d outside [0, n_elites=%d]", count_in, n_elites);
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
-  const size_t n = (size_t)N * HNu, k = (size_t)(n_elites > 0 ? n_elites : 1);
-  DevBuf<float> d_rews, d_cand, d_ybar, d_E, d_R, d_top;
-  DevBuf<int> d_src, d_count, d_lc, d_lk;
-  HIP_TRY(d_rews.alloc(N));
-  HIP_TRY(d_cand.alloc(n));
-  HIP_TRY(d_ybar.alloc(HNu));
-  HIP_TRY(d_E.alloc(k * HNu));
-  HIP_TRY(d_R.alloc(k));
-  HIP_TRY(d_src.alloc(k));
-  HIP_TRY(d_count.alloc(1));
-  HIP_TRY(d_lc.alloc(1));
-  HIP_TRY(d_lk.alloc(1));
-  HIP_TRY(d_top.alloc(1));
-  HIP_TRY(hipMemcpy(d_rews, rews, sizeof(float) * N, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_cand, cand, sizeof(float) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_ybar, ybar, sizeof(float) * HNu, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_count, &count_in, sizeof(int), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(d_E, 0xff, sizeof(float) * k * HNu));
-  HIP_TRY(hipMemset(d_R, 0xff, sizeof(float) * k));
-  HIP_TRY(hipMemset(d_src, 0xff, sizeof(int) * k));
-  HIP_TRY(hipMemset(d_lc, 0xff, sizeof(int)));
-  HIP_TRY(hipMemset(d_lk, 0xff, sizeof(int)));
-  HIP_TRY(hipMemset(d_top, 0xff, sizeof(float)));
-  EliteSelect A{};
-  A.rews = d_rews; A.N = N; A.HNu = HNu; A.cand = d_cand; A.lazy = lazy ? 1 : 0; A.sigma = sigma; A.ybar_i = d_ybar;
-  A.n_elites = n_elites; A.nominal = nominal; A.E = d_E; A.R = d_R; A.src = d_src; A.count = d_count;
-  A.log_count = d_lc; A.log_kept = d_lk; A.log_top = d_top;
-  hipLaunchKernelGGL(elite_select_kernel, dim3(1), dim3(kScoreThreads), 0, nullptr, A);
-  HIP_TRY(hipGetLastError());
+  const size_t k = (size_t)(n_elites > 0 ? n_elites : 1);
+  DevBuf<float> d_rews, d_cand, d_ybar;
+  EliteRec L;
+  L.n = n_elites; L.nominal = nominal; L.has = true;
+  HIP_TRY(d_rews.upload(rews, N));
+  HIP_TRY(d_cand.upload(cand, (size_t)N * HNu));
+  HIP_TRY(d_ybar.upload(ybar, HNu));
+  HIP_TRY(L.d_count.upload(&count_in, 1));
+  HIP_TRY(L.d_E.alloc_poisoned(k * HNu));
+  HIP_TRY(L.d_R.alloc_poisoned(k));
+  HIP_TRY(L.d_src.alloc_poisoned(k));
+  HIP_TRY(L.d_log_count.alloc_poisoned(1));
+  HIP_TRY(L.d_log_kept.alloc_poisoned(1));
+  HIP_TRY(L.d_log_top.alloc_poisoned(1));
+  MBD_TRY(L.select(d_rews, StepCand{d_cand, N, HNu, lazy ? 1 : 0, sigma, nullptr, d_ybar}, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  if (E_out && n_elites) HIP_TRY(hipMemcpy(E_out, d_E, sizeof(float) * (size_t)n_elites * HNu, hipMemcpyDeviceToHost));
-  if (R_out && n_elites) HIP_TRY(hipMemcpy(R_out, d_R, sizeof(float) * n_elites, hipMemcpyDeviceToHost));
-  if (src_out && n_elites) HIP_TRY(hipMemcpy(src_out, d_src, sizeof(int32_t) * n_elites, hipMemcpyDeviceToHost));
+  HIP_TRY(L.d_E.download(E_out, (size_t)n_elites * HNu));
+  HIP_TRY(L.d_R.download(R_out, n_elites));
+  HIP_TRY(L.d_src.download(src_out, n_elites));
   // (count' as the plan's word holds it; the log entry's copy must agree with it: the caller gets the log's, the word is checked)
   int cnt_word = -1, cnt_log = -1;
-  HIP_TRY(hipMemcpy(&cnt_word, d_count, sizeof(int), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&cnt_log, d_lc, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(L.d_count.download(&cnt_word, 1));
+  HIP_TRY(L.d_log_count.download(&cnt_log, 1));
   if (cnt_word != cnt_log) return fail(MBD_ERR_STATE, "elites_select: count word %d, log entry %d", cnt_word, cnt_log);
   if (count_out) *count_out = cnt_word;
-  if (kept_out) HIP_TRY(hipMemcpy(kept_out, d_lk, sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (top_out) HIP_TRY(hipMemcpy(top_out, d_top, sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(L.d_log_kept.download(kept_out, 1));
+  HIP_TRY(L.d_log_top.download(top_out, 1));
   return MBD_OK;
 }
 
@@ -2688,6 +2646,37 @@ extern "C" int mbd_debug_check_togo(const mbd_togo* rec, int Hsample, int Nsampl
   return check_togo(rec, Hsample, Nsample, update_method, enable_demo);
 }
 
+int TogoRec::set(const mbd_togo* rec, int H, int N, const mbd_env* env) {
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still write R and W)
+  has = false;
+  if (!rec) return MBD_OK;
+  layout(rec->block, rec->min_tail, H);
+  const size_t n = (size_t)G * N;
+  HIP_TRY(d_R.grow(n));
+  HIP_TRY(d_W.grow(n));
+  HIP_TRY(hipMemset(d_R, 0xff, sizeof(float) * n));  // (no step yet: mbd_plan_peek_togo says so)
+  HIP_TRY(hipMemset(d_W, 0xff, sizeof(float) * n));
+  HIP_TRY(hipDeviceSynchronize());
+  stepped = false;
+  has = true;
+  return MBD_OK;
+}
+
+int TogoRec::peek(const mbd_env* env, int N, const float* d_weights, int32_t* starts_out, float* R_out, float* W_out,
+                  int32_t* n_groups_out) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_togo: the plan has no to-go record");
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (starts_out) memcpy(starts_out, starts.data(), sizeof(int32_t) * G);
+  HIP_TRY(d_R.download(R_out, (size_t)G * N));
+  HIP_TRY(d_W.download(W_out, (size_t)G * N));
+  // (group 0's weights are the plan's own, once a step of the record has written them)
+  if (W_out && stepped) HIP_TRY(hipMemcpy(W_out, d_weights, sizeof(float) * N, hipMemcpyDeviceToHost));
+  if (n_groups_out) *n_groups_out = G;
+  return MBD_OK;
+}
+
 extern "C" int mbd_plan_set_togo(mbd_plan* p, const mbd_togo* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
   if (rec) {  // (before any device access)
@@ -2697,45 +2686,16 @@ extern "C" int mbd_plan_set_togo(mbd_plan* p, const mbd_togo* rec) {
     if (other)
       return fail(MBD_ERR_UNSUPPORTED, "to-go record: the plan carries %s record: what that record means per horizon row is not defined",
                   other);
-    if (p->cfg.shard_count != p->cfg.Nsample)
-      return fail(MBD_ERR_STATE, "to-go record: shard_count=%d of Nsample=%d: sharded plans take no to-go record", p->cfg.shard_count,
-                  p->cfg.Nsample);
+    if (p->cfg.shard_count != p->cfg.Nsample) return refuse_sharded(p->cfg, "to-go");
   }
   NO_SESSION(p, "set_togo");
-  TogoRec& L = p->togo;
-  if (!rec && !L.has) return MBD_OK;  // (nothing to clear: no device is touched)
-  HIP_TRY(hipSetDevice(p->env->device));
-  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still write R and W)
-  L.has = false;
-  if (!rec) return MBD_OK;
-  togo_layout(L, rec->block, rec->min_tail, p->cfg.Hsample);
-  const size_t n = (size_t)L.G * p->cfg.Nsample;
-  HIP_TRY(L.d_R.grow(n));
-  HIP_TRY(L.d_W.grow(n));
-  HIP_TRY(hipMemset(L.d_R, 0xff, sizeof(float) * n));  // (no step yet: mbd_plan_peek_togo says so)
-  HIP_TRY(hipMemset(L.d_W, 0xff, sizeof(float) * n));
-  HIP_TRY(hipDeviceSynchronize());
-  L.stepped = false;
-  L.has = true;
-  return MBD_OK;
+  if (!rec && !p->togo.has) return MBD_OK;  // (nothing to clear: no device is touched)
+  return p->togo.set(rec, p->cfg.Hsample, p->cfg.Nsample, p->env);
 }
 
 extern "C" int mbd_plan_peek_togo(mbd_plan* p, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
-  const TogoRec& L = p->togo;
-  if (!L.has) return fail(MBD_ERR_STATE, "peek_togo: the plan has no to-go record");
-  HIP_TRY(hipSetDevice(p->env->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t N = (size_t)p->cfg.Nsample;
-  if (starts_out) memcpy(starts_out, L.starts.data(), sizeof(int32_t) * L.G);
-  if (R_out) HIP_TRY(hipMemcpy(R_out, L.d_R, sizeof(float) * L.G * N, hipMemcpyDeviceToHost));
-  if (W_out) {
-    HIP_TRY(hipMemcpy(W_out, L.d_W, sizeof(float) * L.G * N, hipMemcpyDeviceToHost));
-    // (group 0's weights are the plan's own, once a step of the record has written them)
-    if (L.stepped) HIP_TRY(hipMemcpy(W_out, p->d_weights, sizeof(float) * N, hipMemcpyDeviceToHost));
-  }
-  if (n_groups_out) *n_groups_out = L.G;
-  return MBD_OK;
+  return p->togo.peek(p->env, p->cfg.Nsample, p->d_weights, starts_out, R_out, W_out, n_groups_out);
 }
 
 // include/mbd_hip_debug.h: the layout and the returns on the HOST, from the functions the returns kernel calls; no device touched
@@ -2760,7 +2720,8 @@ extern "C" int mbd_debug_togo_host(const float* rews, const float* rewss, int N,
   }
   return MBD_OK;
 }
-// ... and the step's two launches alone on the DEVICE, on caller-given arrays.  What is read back is filled with quiet NaN first.
+// ... and the step's two launches alone on the DEVICE, on caller-given arrays, by a scratch record's own launch.  What is read back
+// is filled with all-ones bits (quiet NaN) first.
 extern "C" int mbd_debug_togo_step(const float* cand, const float* ybar, const float* rews, const float* rewss, int N, int H, int Nu,
                                    int block, int min_tail, int lazy, float sigma, float temp, int std_guard, float alpha_i,
                                    float alpha_bar_i, float alpha_bar_im1, int literal, float* ybar_out, float* R_out, float* W_out,
@@ -2770,41 +2731,32 @@ extern "C" int mbd_debug_togo_step(const float* cand, const float* ybar, const f
   if (Nu < 1 || (uint64_t)N * (uint64_t)H * (uint64_t)Nu > (1ull << 26)) return fail(MBD_ERR_INVALID, "togo_step: N=%d H=%d Nu=%d", N, H, Nu);
   if (N > kTogoMaxN) return fail(MBD_ERR_INVALID, "togo_step: N=%d above %d", N, kTogoMaxN);
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
-  const size_t HNu = (size_t)H * Nu, n = (size_t)N * HNu;
+  const size_t HNu = (size_t)H * Nu;
   TogoRec L;
-  togo_layout(L, block, min_tail, H);
+  L.layout(block, min_tail, H);
   const size_t gn = (size_t)L.G * N;
   DevBuf<float> d_cand, d_ybar, d_rews, d_rewss, d_out, d_keep, d_w, d_mean;
-  HIP_TRY(d_cand.alloc(n));
-  HIP_TRY(d_ybar.alloc(HNu));
-  HIP_TRY(d_rews.alloc(N));
-  HIP_TRY(d_rewss.alloc((size_t)N * H));
-  HIP_TRY(d_out.alloc(HNu));
-  HIP_TRY(d_keep.alloc(HNu));
-  HIP_TRY(d_w.alloc(N));
-  HIP_TRY(d_mean.alloc(1));
-  HIP_TRY(L.d_R.alloc(gn));
-  HIP_TRY(L.d_W.alloc(gn));
-  HIP_TRY(hipMemcpy(d_cand, cand, sizeof(float) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_ybar, ybar, sizeof(float) * HNu, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_rews, rews, sizeof(float) * N, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(d_rewss, rewss, sizeof(float) * (size_t)N * H, hipMemcpyHostToDevice));
-  for (auto [ptr, cnt] : {std::pair<float*, size_t>{d_out.get(), HNu}, {d_keep.get(), HNu}, {d_w.get(), (size_t)N}, {d_mean.get(), 1},
-                          {L.d_R.get(), gn}, {L.d_W.get(), gn}})
-    HIP_TRY(hipMemset(ptr, 0xff, sizeof(float) * cnt));
+  HIP_TRY(d_cand.upload(cand, (size_t)N * HNu));
+  HIP_TRY(d_ybar.upload(ybar, HNu));
+  HIP_TRY(d_rews.upload(rews, N));
+  HIP_TRY(d_rewss.upload(rewss, (size_t)N * H));
+  HIP_TRY(d_out.alloc_poisoned(HNu));
+  HIP_TRY(d_keep.alloc_poisoned(HNu));
+  HIP_TRY(d_w.alloc_poisoned(N));
+  HIP_TRY(d_mean.alloc_poisoned(1));
+  HIP_TRY(L.d_R.alloc_poisoned(gn));
+  HIP_TRY(L.d_W.alloc_poisoned(gn));
   TogoUpdate A{};
   A.rews = d_rews; A.weights = d_w; A.rew_mean = d_mean; A.cand = d_cand; A.ybar_i = d_ybar; A.ybar_im1 = d_out; A.ybar_keep = d_keep;
   A.N = N; A.H = H; A.Nu = Nu; A.temp = temp; A.std_guard = std_guard ? 1 : 0; A.alpha_i = alpha_i; A.alpha_bar_i = alpha_bar_i;
   A.alpha_bar_im1 = alpha_bar_im1; A.literal = literal ? 1 : 0; A.lazy = lazy ? 1 : 0; A.sigma = sigma;
-  MBD_TRY(togo_launch(L, d_rewss, A, nullptr));
+  MBD_TRY(L.launch(d_rewss, A, nullptr));
   HIP_TRY(hipDeviceSynchronize());
-  if (ybar_out) HIP_TRY(hipMemcpy(ybar_out, d_out, sizeof(float) * HNu, hipMemcpyDeviceToHost));
-  if (R_out) HIP_TRY(hipMemcpy(R_out, L.d_R, sizeof(float) * gn, hipMemcpyDeviceToHost));
-  if (W_out) {
-    HIP_TRY(hipMemcpy(W_out, L.d_W, sizeof(float) * gn, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(W_out, d_w, sizeof(float) * N, hipMemcpyDeviceToHost));
-  }
-  if (rew_mean_out) HIP_TRY(hipMemcpy(rew_mean_out, d_mean, sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(d_out.download(ybar_out, HNu));
+  HIP_TRY(L.d_R.download(R_out, gn));
+  HIP_TRY(L.d_W.download(W_out, gn));
+  HIP_TRY(d_w.download(W_out, N));  // (group 0's weights)
+  HIP_TRY(d_mean.download(rew_mean_out, 1));
   return MBD_OK;
 }
 
@@ -2853,10 +2805,10 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
   // with an adapt record, ONE launch in front of the tick's first sampler: a = ones in a cold tick and without carry, otherwise a
   // shifted E rows forward with the mean; G under the caller's shape in force in this tick.  Stream order is the whole argument: it
   // stands behind the previous tick's last update and in front of this tick's first sampler, which reads G
-  MBD_TRY(adapt_table(p, tk.cold || !p->adapt.carry ? -1 : tk.E * p->Nu, tk.cold ? shape_always(p) : shape_warm(p), s));
+  MBD_TRY(p->adapt.table(tk.cold || !p->adapt.carry ? -1 : tk.E * p->Nu, tk.cold ? shape_always(p) : shape_warm(p), HNu, s));
   // with an elite record, ONE launch in the same place: no elites in a cold tick and without carry, otherwise the present ones
   // shifted E rows forward with the mean
-  MBD_TRY(elite_table(p, tk.cold || !p->elite.carry ? -1 : tk.E * p->Nu, s));
+  MBD_TRY(p->elite.table(tk.cold || !p->elite.carry ? -1 : tk.E * p->Nu, HNu, s));
   p->wt.begin();  // (a weighting record's log holds the last tick's steps)
   const float* cur = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros of a cold tick, shift_E(M_{t-1}) otherwise
   const float* last_in = cur;    // Ybar_i of the tick's last step
@@ -3043,21 +2995,21 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   if (has_demo) MBD_TRY(p->demo.finish(T, 1, E, s));
   // an adapt record's G leaves the episode formed under the shape in force OUTSIDE warm ticks again (the table itself stays): the
   // phase calls that may follow sample under it, as they would under the caller's shape without a record
-  MBD_TRY(adapt_table(p, 0, shape_always(p), s));
+  MBD_TRY(p->adapt.table(0, shape_always(p), HNu, s));
   HIP_TRY(hipStreamSynchronize(s));
   const auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
-  if (rewards_out) HIP_TRY(hipMemcpy(rewards_out, p->d_mpc_rewards, sizeof(float) * (size_t)T * E, hipMemcpyDeviceToHost));
-  if (states_out) HIP_TRY(hipMemcpy(states_out, p->d_mpc_states, sizeof(float) * ((size_t)T + 1) * S, hipMemcpyDeviceToHost));
+  HIP_TRY(p->d_mpc_rewards.download(rewards_out, (size_t)T * E));
+  HIP_TRY(p->d_mpc_states.download(states_out, ((size_t)T + 1) * S));
   if (has_delay) p->delay.pred_ticks = T;
   if (pi) { p->sigma_rec.ticks = T; p->sigma_rec.episodes = 1; }
   if (has_plant || has_delay) {  // (the executed rows carry the action noise, or are the committed queue's: their own log)
-    if (actions_out) HIP_TRY(hipMemcpy(actions_out, p->d_mpc_actions, sizeof(float) * (size_t)T * EN, hipMemcpyDeviceToHost));
-    if (means_out) HIP_TRY(hipMemcpy(means_out, p->d_mpc_means, sizeof(float) * (size_t)T * HNu, hipMemcpyDeviceToHost));
+    HIP_TRY(p->d_mpc_actions.download(actions_out, (size_t)T * EN));
+    HIP_TRY(p->d_mpc_means.download(means_out, (size_t)T * HNu));
   } else if (means_out || actions_out) {  // (the executed rows are M_t[0:E]: taken from the one copy of the means)
     std::vector<float> tmp(means_out ? 0 : (size_t)T * HNu);
     float* m = means_out ? means_out : tmp.data();
-    HIP_TRY(hipMemcpy(m, p->d_mpc_means, sizeof(float) * (size_t)T * HNu, hipMemcpyDeviceToHost));
+    HIP_TRY(p->d_mpc_means.download(m, (size_t)T * HNu));
     if (actions_out)
       for (int t = 0; t < T; ++t) memcpy(actions_out + (size_t)t * E * Nu, m + (size_t)t * HNu, sizeof(float) * (size_t)E * Nu);
   }
@@ -3138,7 +3090,7 @@ extern "C" int mbd_plan_mpc_open(mbd_plan* p, const mbd_mpc_config* mc, const ui
   }
   HIP_TRY(hipStreamSynchronize(s));
   if (p->demo.has) MBD_TRY(p->demo.session_start());
-  MBD_TRY(p->pick.start(mc->n_ticks));  // (a pick record's log: the session's ticks, the most recent kPickLogCap of them)
+  MBD_TRY(p->pick.start(mc->n_ticks));  // (a pick record's log: the session's ticks, the most recent kLogCap of them)
   // the objective record's previous action of the first tick, as mbd_plan_run_mpc forms it, and the session's slot until close —
   // behind everything else that can fail, and itself leaving the slot alone when it fails: a failed open leaves prev as it was
   MBD_TRY(p->obj.episode_start(p->delay.has ? p->d_mpc_queue + (Q - p->Nu) : nullptr, Q, s));
@@ -3250,11 +3202,11 @@ extern "C" int mbd_plan_mpc_reset_mean(mbd_plan* p) {
   p->session.cold = true;  // (the next submit zeroes Ybar; the queue stays)
   if (p->adapt.has) {      // (an adapt record's table is all ones again: written now as well, so that mbd_plan_peek_adapt says so)
     HIP_TRY(hipSetDevice(p->env->device));
-    MBD_TRY(adapt_table(p, -1, shape_always(p), p->stream));
+    MBD_TRY(p->adapt.table(-1, shape_always(p), p->HNu, p->stream));
   }
   if (p->elite.has) {  // (an elite record's elites are gone: written now as well, so that mbd_plan_peek_elites says so)
     HIP_TRY(hipSetDevice(p->env->device));
-    MBD_TRY(elite_table(p, -1, p->stream));
+    MBD_TRY(p->elite.table(-1, p->HNu, p->stream));
   }
   if (p->cfg.update_method != 0) {  // (and starts from sigma_cold: written now as well, so that mbd_plan_get_sigma says so)
     HIP_TRY(hipSetDevice(p->env->device));
@@ -3271,7 +3223,7 @@ extern "C" int mbd_plan_mpc_close(mbd_plan* p) {
   HIP_TRY(hipSetDevice(p->env->device));
   if (ss.in_flight) HIP_TRY(hipStreamSynchronize(p->stream));  // (its last kernel writes the mailbox)
   if (p->adapt.has) {  // (as behind mbd_plan_run_mpc: G under the shape in force outside warm ticks, for the phase calls)
-    MBD_TRY(adapt_table(p, 0, shape_always(p), p->stream));
+    MBD_TRY(p->adapt.table(0, shape_always(p), p->HNu, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
   }
   ss.in_flight = false;
@@ -3290,7 +3242,7 @@ extern "C" int mbd_plan_eval(mbd_plan* p, const float* Y, float* rew_final_out) 
   MBD_TRY(launch_rollout(p->env, p->d_state0, p->d_Ybar + p->HNu, 1, p->cfg.Hsample, nullptr, p->d_scratch, nullptr, nullptr,
                          p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
-  HIP_TRY(hipMemcpy(rew_final_out, p->d_scratch, sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(p->d_scratch.download(rew_final_out, 1));
   return MBD_OK;
 }
 
@@ -3308,11 +3260,11 @@ extern "C" int mbd_plan_peek(mbd_plan* p, float* Y0s_out, float* rewss_out, floa
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(p->stream));
   }
-  if (Y0s_out) HIP_TRY(hipMemcpy(Y0s_out, p->d_Y0s, sizeof(float) * (size_t)c.Nsample * p->HNu, hipMemcpyDeviceToHost));
+  HIP_TRY(p->d_Y0s.download(Y0s_out, (size_t)c.Nsample * p->HNu));
   // (with an ensemble record that has stepped: member 0's rows of the launch over all members)
   const float* rewss = p->has_ens && p->ens_stepped ? p->d_ens_rewss : p->d_rewss;
   if (rewss_out) HIP_TRY(hipMemcpy(rewss_out, rewss, sizeof(float) * (size_t)c.shard_count * c.Hsample, hipMemcpyDeviceToHost));
-  if (weights_out) HIP_TRY(hipMemcpy(weights_out, p->d_weights, sizeof(float) * (size_t)c.Nsample, hipMemcpyDeviceToHost));
+  HIP_TRY(p->d_weights.download(weights_out, (size_t)c.Nsample));
   return MBD_OK;
 }
 

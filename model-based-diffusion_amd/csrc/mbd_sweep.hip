@@ -193,8 +193,7 @@ extern "C" int mbd_sweep_create(mbd_env* env, const mbd_plan_config* cfg, int n_
   HIP_TRY(hipMemset(w->d_zero, 0, sizeof(float) * (size_t)P * w->HNu));
   HIP_TRY(w->d_mu.alloc((size_t)P * (Nd - 1) * w->HNu));
   HIP_TRY(w->d_rewmeans.alloc((size_t)P * (Nd - 1)));
-  HIP_TRY(w->d_temps.alloc(P));
-  HIP_TRY(hipMemcpy(w->d_temps, w->temps.data(), sizeof(float) * P, hipMemcpyHostToDevice));
+  HIP_TRY(w->d_temps.upload(w->temps.data(), P));
   HIP_TRY(w->d_final.alloc((size_t)P * w->HNu));
   HIP_TRY(w->d_final_rew.alloc(P));
   *out = guard.release();
@@ -235,15 +234,15 @@ static int sweep_results(mbd_sweep* w, float* mu_0ts_out, float* rew_means_out, 
   const int P = w->P, Nd = w->cfg.Ndiffuse, HNu = w->HNu;
   hipStream_t s = w->stream;
   const size_t mu_n = (size_t)P * (Nd - 1) * HNu;
-  if (mu_0ts_out) HIP_TRY(hipMemcpy(mu_0ts_out, w->d_mu, sizeof(float) * mu_n, hipMemcpyDeviceToHost));
-  if (rew_means_out) HIP_TRY(hipMemcpy(rew_means_out, w->d_rewmeans, sizeof(float) * (size_t)P * (Nd - 1), hipMemcpyDeviceToHost));
+  HIP_TRY(w->d_mu.download(mu_0ts_out, mu_n));
+  HIP_TRY(w->d_rewmeans.download(rew_means_out, (size_t)P * (Nd - 1)));
   if (!rew_final_out) return MBD_OK;
   HIP_TRY(hipMemcpy2DAsync(w->d_final, sizeof(float) * HNu, w->d_mu + (size_t)(Nd - 2) * HNu,
                            sizeof(float) * (size_t)(Nd - 1) * HNu, sizeof(float) * HNu, P, hipMemcpyDeviceToDevice, s));
   const int sw[3] = {1, w->env->state_size(), 0};
   MBD_TRY(launch_rollout(w->env, w->d_state0, w->d_final, P, w->cfg.Hsample, nullptr, w->d_final_rew, nullptr, nullptr, s, nullptr, sw));
   HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(hipMemcpy(rew_final_out, w->d_final_rew, sizeof(float) * P, hipMemcpyDeviceToHost));
+  HIP_TRY(w->d_final_rew.download(rew_final_out, P));
   return MBD_OK;
 }
 
@@ -377,7 +376,7 @@ extern "C" int mbd_sweep_get_sigmas(mbd_sweep* w, float* sigmas_out) {
   if (!w->d_sigma) return fail(MBD_ERR_STATE, "not a path-integral sweep (update_method == 0)");
   HIP_TRY(hipSetDevice(w->env->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(sigmas_out, w->d_sigma, sizeof(float) * w->P, hipMemcpyDeviceToHost));
+  HIP_TRY(w->d_sigma.download(sigmas_out, w->P));
   return MBD_OK;
 }
 
@@ -570,10 +569,10 @@ extern "C" int mbd_debug_sweep_update(mbd_sweep* w, int i, const float* cand, co
   else MBD_TRY(sweep_update(w, i, 0, d_cand, w->d_final, HNu, e->rew_xref));
   HIP_TRY(hipStreamSynchronize(w->stream));
   if (ybar_out) HIP_TRY(hipMemcpy2D(ybar_out, row, w->d_mu, mu_pitch, row, P, hipMemcpyDeviceToHost));
-  if (weights_out) HIP_TRY(hipMemcpy(weights_out, w->d_weights, sizeof(float) * PN, hipMemcpyDeviceToHost));
+  HIP_TRY(w->d_weights.download(weights_out, PN));
   if (rew_mean_out)
     HIP_TRY(hipMemcpy2D(rew_mean_out, sizeof(float), w->d_rewmeans, sizeof(float) * (Nd - 1), sizeof(float), P, hipMemcpyDeviceToHost));
-  if (sigma_out && c.update_method == 2) HIP_TRY(hipMemcpy(sigma_out, w->d_sigma, sizeof(float) * P, hipMemcpyDeviceToHost));
+  if (c.update_method == 2) HIP_TRY(w->d_sigma.download(sigma_out, P));
   if (idx_out && c.update_method == 3)
     HIP_TRY(hipMemcpy2D(idx_out, sizeof(int) * K, w->d_idx, sizeof(int) * 16, sizeof(int) * K, P, hipMemcpyDeviceToHost));
   return MBD_OK;
