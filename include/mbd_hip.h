@@ -878,7 +878,8 @@ typedef struct mbd_adapt {
  * Without a record nothing is launched and nothing changes.
  * Scope: MBD and mppi plans (update_method 0 and 1), rigid-body envs and car2d, lazy and materialised candidates, with or without
  * noise-shape, noise-basis, objective, weighting, value, ensemble, plant, delay, sigma and pick records; mbd_plan_run, the unsharded
- * phase calls, mbd_plan_run_mpc and sessions.  Sweeps have no such call.
+ * phase calls, mbd_plan_run_mpc and sessions.  Sweeps take elite and to-go records (mbd_sweep_set_elites, mbd_sweep_set_togo), not yet
+ * this one: their samplers are handed one shape for all plans.
  * The set call is synchronous (it waits for the device), discards normals prepared ahead as mbd_plan_set_noise_shape does, and is to
  * be called between diffusion steps; rec == NULL clears.  Refused before any device access, the message naming the field —
  * MBD_ERR_INVALID: a NULL handle, rate outside (0, 1] or non-finite, a_min / a_max non-finite or not 0 < a_min <= 1 <= a_max, carry
@@ -943,7 +944,7 @@ typedef struct mbd_elites {
  * every call keeps its bits.
  * Scope: MBD and mppi plans (update_method 0 and 1), rigid-body envs and car2d, lazy and materialised candidates, with or without
  * plant, delay, sigma, objective, weighting, value, ensemble, pick, adapt, noise-shape and noise-basis records (a pick record's best
- * candidate may then be an elite); mbd_plan_run, the unsharded phase calls, mbd_plan_run_mpc and sessions.  Sweeps have no such call.
+ * candidate may then be an elite); mbd_plan_run, the unsharded phase calls, mbd_plan_run_mpc and sessions.  Sweeps: mbd_sweep_set_elites.
  * The set call is synchronous (it waits for the device), discards normals prepared ahead, and is to be called between diffusion
  * steps; rec == NULL clears.  Refused before any device access, the message naming the field — MBD_ERR_INVALID: a NULL handle,
  * n_elites outside [0, 32], nominal or carry outside {0, 1}, n_elites + nominal == 0, n_elites + nominal >= Nsample, non-zero
@@ -990,7 +991,7 @@ typedef struct mbd_togo {
  * every call keeps its launches and its bits.
  * Scope: MBD and mppi plans (update_method 0 and 1), rigid-body envs and car2d, lazy and materialised candidates; mbd_plan_run, the
  * unsharded phase calls, mbd_plan_reverse_once, mbd_plan_run_mpc and sessions; beside plant, delay, sigma, noise-shape, noise-basis,
- * pick and elite records.  Sweeps have no such call.
+ * pick and elite records.  Sweeps: mbd_sweep_set_togo.
  * The set call is synchronous (it waits for the device) and is to be called between diffusion steps; rec == NULL clears.  Refused
  * before any device access, the message naming the field or the record — MBD_ERR_INVALID: a NULL handle, block < 1, min_tail outside
  * [1, Hsample], non-zero reserved; MBD_ERR_UNSUPPORTED: update_method 2 or 3, a plan created with enable_demo, Nsample > 12288 (the
@@ -1233,6 +1234,30 @@ int mbd_sweep_peek_objective(mbd_sweep* sweep, int k, float* ret_out, float* cos
 int mbd_sweep_set_weighting(mbd_sweep* sweep, const mbd_weighting* rec);
 /* plan k's log of the last run or the last tick; as mbd_plan_peek_weighting; k outside [0, n_plans) -> MBD_ERR_INVALID */
 int mbd_sweep_peek_weighting(mbd_sweep* sweep, int k, float* temp_out, float* ess_out, int32_t* kept_out, int capacity, int* count_out);
+/* one elite record (mbd_elites, above) for all plans of the sweep; NULL clears.  The contract is mbd_elites' per plan: plan k of
+ * mbd_sweep_run, episode k of mbd_sweep_run_mpc and of a sweep's session equal the single plan with that record and temps[k], bit for
+ * bit — plan k's, with its own E, R, src, count and log; what the other plans do or are fed makes no difference.  A step gains two
+ * launches over the n_plans plans (blockIdx.y = plan), a tick one more; the counts stay on the device.  In a session's tick after
+ * mbd_sweep_mpc_reset_mean(k) the episodes that idle through the steps above warm_steps take no part in the record's launches, and
+ * mbd_sweep_mpc_reset_mean(k) empties episode k's elites.  Beside the sweep's plant, delay, sigma, pick, noise-shape, noise-basis,
+ * objective, value, weighting and to-go records.  Refused before any device access, the message naming the field: the field checks
+ * are mbd_plan_set_elites' on the sweep's config (MBD_ERR_UNSUPPORTED: update_method 2 or 3, enable_demo; MBD_ERR_INVALID: the
+ * rest, n_elites + nominal >= Nsample among them, and a NULL handle); then MBD_ERR_STATE while a session is open. */
+int mbd_sweep_set_elites(mbd_sweep* sweep, const mbd_elites* rec);
+/* plan k's elites, count and log, as mbd_plan_peek_elites: the log holds the steps since the last mbd_sweep_run, mbd_sweep_run_mpc
+ * or mbd_sweep_mpc_open began.  MBD_ERR_INVALID: a NULL handle, k outside [0, n_plans), capacity < 0; MBD_ERR_STATE without a record. */
+int mbd_sweep_peek_elites(mbd_sweep* sweep, int k, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
+                          int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out);
+/* one to-go record (mbd_togo, above) for all plans of the sweep; NULL clears.  The contract is mbd_togo's per plan — plan k's, with
+ * its own R_j and W_j under temps[k] — and the guarantee mbd_sweep_set_elites gives.  A step launches the record's two kernels over
+ * the n_plans plans where it launches the batch score and weighted mean.  Beside the sweep's plant, delay, sigma, pick, noise-shape,
+ * noise-basis and elite records.  Refused before any device access, the message naming the field or the record: the field checks are
+ * mbd_plan_set_togo's on the sweep's config; MBD_ERR_UNSUPPORTED beside the sweep's objective, value or weighting record — whose set
+ * calls in turn refuse a sweep that carries a to-go record —; then MBD_ERR_STATE while a session is open. */
+int mbd_sweep_set_togo(mbd_sweep* sweep, const mbd_togo* rec);
+/* plan k's values of the last step, as mbd_plan_peek_togo.  MBD_ERR_INVALID: a NULL handle, k outside [0, n_plans); MBD_ERR_STATE
+ * without a record. */
+int mbd_sweep_peek_togo(mbd_sweep* sweep, int k, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out);
 /* one pick record (mbd_mpc_pick, above) for all episodes of the sweep: episode k of mbd_sweep_run_mpc and of a sweep's session
  * equals the single plan's with that record, bit for bit, logs included.  The gather and the choice are one launch each over the
  * n_plans episodes (blockIdx.y = episode), the rollout one launch over the 3 n_plans slots from the episodes' own states.  Refusals

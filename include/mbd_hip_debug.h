@@ -158,6 +158,24 @@ int mbd_debug_togo_host(const float* rews, const float* rewss, int N, int H, int
 int mbd_debug_togo_step(const float* cand, const float* ybar, const float* rews, const float* rewss, int N, int H, int Nu, int block,
                         int min_tail, int lazy, float sigma, float temp, int std_guard, float alpha_i, float alpha_bar_i,
                         float alpha_bar_im1, int literal, float* ybar_out, float* R_out, float* W_out, float* rew_mean_out);
+/* An elite record's two batch launches alone on the DEVICE for P plans at once, on caller-given HOST arrays, keeping no sweep state:
+ * elite_inject_batch_kernel, then elite_select_batch_kernel.  mask: bit k set = plan k takes part; a plan left out is neither read
+ * nor written.  rews [P][N], cand [P][N][HNu] (values, or with lazy != 0 normals), ybar [P][HNu], g [HNu] or NULL, E_in
+ * [P][max(n_elites, 1)][HNu] (plan k's first count_in[k] rows are read; the rest is replaced by all-ones bits), count_in [P].
+ * cand_out [P][N][HNu] the candidates behind the injection; E_out, R_out, src_out [P][max(n_elites, 1)] rows; count_out, kept_out,
+ * top_out [P]; any output may be NULL.  What no kernel wrote reads back with all bits set (count_out: count_in).  Argument errors
+ * first (as mbd_debug_elites_inject's, P outside [1, 32]), then MBD_ERR_NO_DEVICE. */
+int mbd_debug_sweep_elites_step(int P, uint32_t mask, const float* rews, const float* cand, int N, int HNu, const float* ybar, float sigma,
+                                int lazy, const float* g, int n_elites, int nominal, const float* E_in, const int32_t* count_in,
+                                float* cand_out, float* E_out, float* R_out, int32_t* src_out, int32_t* count_out, int32_t* kept_out,
+                                float* top_out);
+/* A to-go record's two batch launches alone on the DEVICE for P plans at once: togo_returns_batch_kernel, then
+ * togo_update_batch_kernel under temps [P].  As mbd_debug_togo_step with a leading [P] on every array: cand [P][N][H * Nu], ybar
+ * [P][H * Nu], rews [P][N], rewss [P][N][H]; ybar_out [P][H * Nu], R_out and W_out [P][G][N], rew_mean_out [P]. */
+int mbd_debug_sweep_togo_step(int P, const float* temps, const float* cand, const float* ybar, const float* rews, const float* rewss,
+                              int N, int H, int Nu, int block, int min_tail, int lazy, float sigma, int std_guard, float alpha_i,
+                              float alpha_bar_i, float alpha_bar_im1, int literal, float* ybar_out, float* R_out, float* W_out,
+                              float* rew_mean_out);
 #ifdef __cplusplus
 }
 #endif

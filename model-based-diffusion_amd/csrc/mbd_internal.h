@@ -531,6 +531,8 @@ struct WeightingRec {
            const char* what) const;
 };
 int check_weighting(const mbd_weighting* rec);
+// the refusal of a record beside a to-go record (mbd_plan.hip; who: how the refused record's messages begin, handle: "plan" / "sweep")
+int refuse_beside_togo(const char* who, const char* handle = "plan");
 // The pick record of a plan or a sweep (include/mbd_hip.h mbd_mpc_pick) as the handle keeps it, with what the two handles do alike.
 // check_mpc_pick: the refusals the record alone decides, each naming the field, before any device access.  set: behind the handle's
 // NULL, session, enable_demo and ensemble checks (nullptr clears); makes room for P plans' slots [P][3][HNu], their returns and

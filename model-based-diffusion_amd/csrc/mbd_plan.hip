@@ -302,9 +302,9 @@ struct mbd_plan {
   if ((p)->session.open) return fail(MBD_ERR_STATE, what ": a session is open on this plan (mbd_plan_mpc_close first)")
 // the refusal of a record beside a to-go record (who: how the refused record's messages begin), and of a plan-only record on a
 // sharded plan (kind: "adapt", "elite", "to-go")
-static int refuse_beside_togo(const char* who) {
-  return fail(MBD_ERR_UNSUPPORTED, "%s: the plan carries a to-go record (mbd_plan_set_togo): what the record means per horizon row is not "
-                                   "defined", who);
+int refuse_beside_togo(const char* who, const char* handle) {  // (mbd_internal.h: the sweeps' set calls refuse with the same text)
+  return fail(MBD_ERR_UNSUPPORTED, "%s: the %s carries a to-go record (mbd_%s_set_togo): what the record means per horizon row is not "
+                                   "defined", who, handle, handle);
 }
 static int refuse_sharded(const mbd_plan_config& c, const char* kind) {
   return fail(MBD_ERR_STATE, "%s record: shard_count=%d of Nsample=%d: sharded plans take no %s record", kind, c.shard_count, c.Nsample,

@@ -2064,7 +2064,7 @@ constexpr int kEliteRegs = 8, kEliteThreads = 256;
 // 2.9 us per elite, the round and the row's gather together, each gather a dependent load and store.  Fine at the few elites
 // sampling MPC uses; at k = 32 it is a sixth of a humanoid step, and batching the gathers' loads is the first thing to try.
 // Bounds: rews[i] for i < N; cand rows win_i[j] < N; E rows j < count' <= n_elites.  Plain vector loads and stores.
-static __global__ __launch_bounds__(kScoreThreads) void elite_select_kernel(EliteSelect A) {
+__device__ __forceinline__ void elite_select_body(const EliteSelect& A) {
   __shared__ float red_v[2][kScoreThreads / 64];
   __shared__ int red_i[2][kScoreThreads / 64];
   __shared__ float win_v[kEliteMax];
@@ -2141,10 +2141,11 @@ static __global__ __launch_bounds__(kScoreThreads) void elite_select_kernel(Elit
     *A.log_top = cnt > 0 ? win_v[0] : __builtin_bit_cast(float, 0x7fc00000u);
   }
 }
+static __global__ __launch_bounds__(kScoreThreads) void elite_select_kernel(EliteSelect A) { elite_select_body(A); }
 // Behind the launch that made the step's normals (or candidates), in front of its rollout: rows 0 .. nominal + count - 1.  The grid
 // covers (nominal + n_elites) HNu elements; every thread loads count and a thread of an absent slot writes nothing.  Bounds: the
 // loaded count is held to [0, n_elites], and the set call refuses nominal + n_elites >= Nsample, so a written row lies below N.
-static __global__ __launch_bounds__(kEliteThreads) void elite_inject_kernel(EliteInject A) {
+__device__ __forceinline__ void elite_inject_body(const EliteInject& A) {
   const int idx = blockIdx.x * kEliteThreads + threadIdx.x;
   const int slot = idx / A.HNu, e = idx - slot * A.HNu;
   int cnt = *A.count;
@@ -2160,12 +2161,12 @@ static __global__ __launch_bounds__(kEliteThreads) void elite_inject_kernel(Elit
   }
   A.cand[(size_t)slot * A.HNu + e] = v;
 }
+static __global__ __launch_bounds__(kEliteThreads) void elite_inject_kernel(EliteInject A) { elite_inject_body(A); }
 // The elites at the start of a run or a tick: shift < 0: count = 0; otherwise every present elite's row shifted `shift` elements
 // forward with zeros behind it (the mean's own shift), count as it is.  Workgroup j owns row j; the shift is in place, so a block of
 // 256 elements is read, then — behind a barrier — written: a later block reads only elements no earlier block wrote.  A workgroup
 // leaves as a whole (count is one word), so the barriers' trip count is uniform.
-static __global__ __launch_bounds__(kEliteThreads) void elite_shift_kernel(float* __restrict__ E, int* __restrict__ count, int HNu,
-                                                                    int shift) {
+__device__ __forceinline__ void elite_shift_body(float* __restrict__ E, int* __restrict__ count, int HNu, int shift) {
   if (shift < 0) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *count = 0;
     return;
@@ -2181,6 +2182,49 @@ static __global__ __launch_bounds__(kEliteThreads) void elite_shift_kernel(float
     __syncthreads();
   }
 }
+static __global__ __launch_bounds__(kEliteThreads) void elite_shift_kernel(float* __restrict__ E, int* __restrict__ count, int HNu,
+                                                                    int shift) {
+  elite_shift_body(E, count, HNu, shift);
+}
+
+// SWEEPS (mbd_sweep_set_elites): the three launches for P plans of one env at once — blockIdx.y is the plan, whose candidates, Ybar_i,
+// rewards and elite state (E, R, src, count, the log's slot) sit at fixed strides, in elements, from plan 0's.  The bodies are the
+// single-plan kernels': same text, same order, same bits; only the indexing is new.  MBD_SWEEP_KERNEL: the unit that launches them
+// (mbd_sweep.hip) alone emits them.  mask: bit k set = plan k takes part; the
+// workgroups of a plan that does not return before they read or write anything (a session's mixed tick: the episodes that idle).
+// Bounds: gridDim.y = P <= 32 = the mask's width; every stride is the size of one plan's array, so plan k's accesses are the
+// single-plan kernel's inside slice k.
+#ifdef MBD_SWEEP_KERNEL
+struct EliteBatch {
+  long long cand, ybar, rews;  // [P][N][HNu], Ybar_i of plan k (0: one for all), [P][N]
+  long long E, R, log;         // rows HNu, rows (R and src), the log's capacity per plan; count: one word per plan
+  unsigned mask;
+};
+static __global__ __launch_bounds__(kEliteThreads) void elite_inject_batch_kernel(EliteInject A, EliteBatch B) {
+  const long long k = blockIdx.y;
+  if (!((B.mask >> k) & 1u)) return;
+  A.cand += k * B.cand; A.ybar_i += k * B.ybar; A.E += k * B.E; A.count += k;
+  elite_inject_body(A);
+}
+// one int per plan: a shift (-1 empties, E Nu shifts with the mean, 0 leaves), or the slot of the plan's log its entry goes to
+struct EliteShifts {
+  int s[32];
+};
+static __global__ __launch_bounds__(kScoreThreads) void elite_select_batch_kernel(EliteSelect A, EliteBatch B, EliteShifts slot) {
+  const long long k = blockIdx.y;
+  if (!((B.mask >> k) & 1u)) return;  // (uniform: the whole workgroup, in front of every barrier)
+  A.rews += k * B.rews; A.cand += k * B.cand; A.ybar_i += k * B.ybar; A.E += k * B.E; A.R += k * B.R; A.src += k * B.R; A.count += k;
+  const long long entry = k * B.log + slot.s[k];  // (slot.s[k] in [0, B.log): the host's ring_slot)
+  A.log_count += entry; A.log_kept += entry; A.log_top += entry;
+  elite_select_body(A);
+}
+static __global__ __launch_bounds__(kEliteThreads) void elite_shift_batch_kernel(float* __restrict__ E, int* __restrict__ count, int HNu,
+                                                                          EliteShifts sh, EliteBatch B) {
+  const long long k = blockIdx.y;
+  if (!((B.mask >> k) & 1u)) return;
+  elite_shift_body(E + k * B.E, count + k, HNu, sh.s[k]);
+}
+#endif  // MBD_SWEEP_KERNEL
 #endif  // MBD_ELITE_KERNEL
 
 // ---- the to-go record (mbd_plan_set_togo, include/mbd_hip.h mbd_togo; DESIGN.md section 1 "N19 to-go"): the horizon's rows in G
@@ -2292,6 +2336,47 @@ static __global__ __launch_bounds__(kWmE * kWmG) void togo_update_kernel(TogoUpd
                                              A.alpha_bar_im1, A.literal, A.ybar_im1, A.lazy, A.sigma, A.ybar_keep, 0, t == 0, e_base,
                                              e_lim);
 }
+
+#ifdef MBD_SWEEP_KERNEL
+// SWEEPS (mbd_sweep_set_togo): the two launches for P plans at once.  rewss is [P N][H] contiguous and rews [P N], so a lane of the
+// returns kernel still owns one candidate b = k N + n of the P N; it writes R [P][G][N], row 0 of every plan a copy of its rews.
+// Bounds: b < P N guards every access; a load is rewss[b H + t] with t in [block, H - 1], a store R[(k G + j) N + n], j in [0, G - 1].
+static __global__ __launch_bounds__(kTogoThreads) void togo_returns_batch_kernel(TogoReturns A, int P) {
+  const long long b = (long long)blockIdx.x * kTogoThreads + threadIdx.x;
+  if (b >= (long long)P * A.N) return;
+  const int k = (int)(b / A.N), n = (int)(b - (long long)k * A.N);
+  float* __restrict__ R = A.R + (size_t)k * A.G * A.N;
+  R[n] = A.rews[b];
+  togo_chain(A.rewss + (size_t)b * A.H, A.H, A.block, A.G, [&](int j, float v) { R[(size_t)j * A.N + n] = v; });
+}
+// The update: togo_update_kernel's tiles (the same closed form from tile x to group and tile of the group, never straddling a group)
+// with score_wmean_batch_kernel's plan and tile order, strides and per-plan temperatures — gridDim.x = T tiles, blockIdx.y the plan;
+// a multiple of 8 plans puts plan k's tiles on XCD k mod 8, otherwise each plan's row of workgroups takes the XCD-aware tile order.
+// The chains are score_wmean_body's SPAN form with the sweeps' rounds (32 rows in flight, rewards re-read: same bits).  R and W are
+// [P][G][N]; group 0's first workgroup stores plan k's weights and mean reward where the batch score kernel stores them.
+// Bounds: as togo_update_kernel per plan; (k, x) is a bijection on [0, P) x [0, T).  LDS: N floats beside the span's arrays.
+// One workgroup per CU (87 registers, none spilled; held to the 64 of two workgroups per CU the span's clamped indices spill 20 bytes).
+static __global__ __launch_bounds__(kWmE * kWmG, 4) void togo_update_batch_kernel(TogoUpdate A, ScoreBatch sb) {
+  const int T = gridDim.x, P = gridDim.y;
+  long long k = blockIdx.y;
+  int x = xcd_tile(blockIdx.x, T, blockIdx.y * T);
+  if ((P & 7) == 0) {
+    const int lin = blockIdx.y * T + blockIdx.x, c = lin & 7, m = lin >> 3;
+    k = c + 8 * (m / T);
+    x = m % T;
+  }
+  int j = x / A.tpg;
+  j = j < A.G - 1 ? j : A.G - 1;
+  const int t = x - j * A.tpg;
+  const int e_base = togo_start(j, A.block) * A.Nu + t * kWmE, e_lim = togo_end(j, A.G, A.H, A.block) * A.Nu;
+  const size_t row = ((size_t)k * A.G + j) * A.N;
+  score_wmean_body<32, false, 1, false, true>(j ? A.R + row : A.rews + k * sb.rews, nullptr, A.N, 0.0f, sb.temps ? sb.temps[k] : A.temp,
+                                              A.std_guard, j ? A.W + row : A.weights + k * sb.weights,
+                                              j ? nullptr : A.rew_mean + k * sb.mean, A.cand + k * sb.cand, A.H * A.Nu,
+                                              A.ybar_i + k * sb.ybar_in, A.alpha_i, A.alpha_bar_i, A.alpha_bar_im1, A.literal,
+                                              A.ybar_im1 + k * sb.ybar_out, A.lazy, A.sigma, nullptr, 0, t == 0, e_base, e_lim);
+}
+#endif  // MBD_SWEEP_KERNEL
 #endif  // MBD_TOGO_KERNEL
 
 }  // namespace mbd

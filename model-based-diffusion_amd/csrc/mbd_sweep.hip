@@ -2,9 +2,112 @@
 // their candidates per step (mbd/scripts/run_mbd.py:17-64); MBD plans and the path-integral baselines.  The sweep handle, its
 // ring of noise buffers (sweep_step: another protocol than a plan's NoiseRing) and the batched receding-horizon loop.
 #define MBD_WEIGH_KERNEL 1  // this unit launches weigh_kernel (mbd_step_kernels.h)
+#define MBD_ELITE_KERNEL 1  // ... and the elite and to-go records' batch kernels
+#define MBD_TOGO_KERNEL 1
+#define MBD_SWEEP_KERNEL 1  // (their forms over P plans: this unit's alone)
 #include "mbd_internal.h"
+#include "../../include/mbd_hip_debug.h"
 
 namespace {
+// The elite record of all the sweep's plans (mbd_sweep_set_elites), a plan's EliteRec per plan: E [P][rows][HNu], R and src
+// [P][rows] (rows = max(n, 1)), count [P] on the device — never read back inside a loop — and the three logs [P][kLogCap].  steps is
+// host bookkeeping PER PLAN: in a session's mixed tick the episodes that idle make no selection, and their logs stay a single
+// session's.  Every launch takes the mask of the plans that take part (bit k: plan k).
+struct SweepEliteRec {
+  bool has = false;
+  int n = 0, nominal = 0, carry = 0, rows = 1;
+  int log_cap = kLogCap;  // entries of a plan's log (the debug entry's scratch record: 1)
+  long long steps[MBD_SWEEP_MAX_PLANS] = {};
+  DevBuf<float> d_E, d_R, d_log_top;
+  DevBuf<int> d_src, d_count, d_log_count, d_log_kept;
+  void restart() { for (long long& c : steps) c = 0; }
+  EliteBatch batch(long long cand, long long ybar, long long rews, int HNu, unsigned mask) const {
+    EliteBatch B{};
+    B.cand = cand; B.ybar = ybar; B.rews = rews; B.E = (long long)rows * HNu; B.R = rows; B.log = log_cap; B.mask = mask;
+    return B;
+  }
+  int alloc(int P, int HNu) {
+    HIP_TRY(d_E.grow((size_t)P * rows * HNu));
+    HIP_TRY(d_R.grow((size_t)P * rows));
+    HIP_TRY(d_src.grow((size_t)P * rows));
+    HIP_TRY(d_count.grow(P));
+    return MBD_OK;
+  }
+  // the plans' elites at the start of a run or a tick: shift[k] < 0 empties plan k's, otherwise its rows move shift[k] elements forward
+  int table(int P, int HNu, const EliteShifts& sh, unsigned mask, hipStream_t s) {
+    if (!has) return MBD_OK;
+    hipLaunchKernelGGL(elite_shift_batch_kernel, dim3((unsigned)rows, (unsigned)P), dim3(kEliteThreads), 0, s, d_E.get(), d_count.get(), HNu,
+                       sh, batch(0, 0, 0, HNu, mask));
+    HIP_TRY(hipGetLastError());
+    return MBD_OK;
+  }
+  int table_all(int P, int HNu, int shift, hipStream_t s) {
+    EliteShifts sh;
+    for (int& v : sh.s) v = shift;
+    return table(P, HNu, sh, 0xffffffffu, s);
+  }
+  // behind the launch that made the step's normals or candidates, in front of the rollout (EliteRec::inject per plan)
+  int inject(int P, float* cand, long long cand_stride, int HNu, int lazy, float sigma, const float* ybar, long long ybar_stride,
+             const float* g, unsigned mask, hipStream_t s) {
+    if (!has) return MBD_OK;
+    EliteInject A{};
+    A.cand = cand; A.HNu = HNu; A.ybar_i = ybar; A.lazy = lazy; A.sigma = sigma; A.g = g;
+    A.n_elites = n; A.nominal = nominal; A.E = d_E; A.count = d_count;
+    const long long total = (long long)(nominal + n) * HNu;
+    hipLaunchKernelGGL(elite_inject_batch_kernel, dim3((unsigned)((total + kEliteThreads - 1) / kEliteThreads), (unsigned)P),
+                       dim3(kEliteThreads), 0, s, A, batch(cand_stride, ybar_stride, 0, HNu, mask));
+    HIP_TRY(hipGetLastError());
+    return MBD_OK;
+  }
+  // behind the step's update kernel (EliteRec::select per plan); the plans of the mask gain a log entry, each at its own ring's slot
+  int select(int P, const float* rews, int N, const float* cand, long long cand_stride, int HNu, int lazy, float sigma,
+             const float* ybar, long long ybar_stride, unsigned mask, hipStream_t s) {
+    if (!has) return MBD_OK;
+    EliteSelect A{};
+    A.rews = rews; A.N = N; A.HNu = HNu; A.cand = cand; A.lazy = lazy; A.sigma = sigma; A.ybar_i = ybar;
+    A.n_elites = n; A.nominal = nominal; A.E = d_E; A.R = d_R; A.src = d_src; A.count = d_count;
+    A.log_count = d_log_count; A.log_kept = d_log_kept; A.log_top = d_log_top;
+    EliteBatch B = batch(cand_stride, ybar_stride, N, HNu, mask);
+    EliteShifts slots;  // (plan k's entry lies at slot[k] of its own ring)
+    for (int k = 0; k < MBD_SWEEP_MAX_PLANS; ++k) slots.s[k] = 0;
+    for (int k = 0; k < P; ++k)
+      if ((mask >> k) & 1u) slots.s[k] = (int)ring_slot(steps[k], log_cap);
+    hipLaunchKernelGGL(elite_select_batch_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), 0, s, A, B, slots);
+    HIP_TRY(hipGetLastError());
+    return MBD_OK;
+  }
+};
+
+// The to-go record of all the sweep's plans (mbd_sweep_set_togo), a plan's TogoRec per plan: one layout, R and W [P][G][N] (row 0 of
+// a plan's W is never written: group 0's weights are the plan's slice of d_weights).
+struct SweepTogoRec {
+  bool has = false, stepped = false;
+  int block = 0, min_tail = 0, G = 0;
+  std::vector<int32_t> starts;
+  DevBuf<float> d_R, d_W;
+  void layout(int block_, int min_tail_, int H) {
+    block = block_; min_tail = min_tail_;
+    G = togo_groups(H, block, min_tail);
+    starts.resize(G);
+    for (int j = 0; j < G; ++j) starts[j] = togo_start(j, block);
+  }
+  // the step's two launches where the batch score + weighted mean stands: A and sb carry everything but the layout and R, W
+  int launch(int P, const float* d_rewss, TogoUpdate A, const ScoreBatch& sb, hipStream_t s) {
+    const TogoReturns Rt{A.rews, d_rewss, d_R.get(), A.N, A.H, block, G};
+    const long long PN = (long long)P * A.N;
+    hipLaunchKernelGGL(togo_returns_batch_kernel, dim3((unsigned)((PN + kTogoThreads - 1) / kTogoThreads)), dim3(kTogoThreads), 0, s, Rt, P);
+    HIP_TRY(hipGetLastError());
+    const long long last = (long long)(A.H - togo_start(G - 1, block)) * A.Nu;
+    A.R = d_R; A.W = d_W; A.G = G; A.block = block;
+    A.tpg = G > 1 ? (int)(((long long)block * A.Nu + kWmE - 1) / kWmE) : 1;
+    A.T = (G - 1) * A.tpg + (int)((last + kWmE - 1) / kWmE);
+    hipLaunchKernelGGL(togo_update_batch_kernel, dim3((unsigned)A.T, (unsigned)P), dim3(kWmE * kWmG), sizeof(float) * (size_t)A.N, s, A, sb);
+    HIP_TRY(hipGetLastError());
+    stepped = true;
+    return MBD_OK;
+  }
+};
+
 // outputs per thread of the sweeps' score + weighted mean launch (score_wmean_batch_kernel<V>): 2 — a workgroup owns 32 outputs,
 // 128 bytes of every candidate row, P x 27 workgroups for the humanoid.  Measured on sweep8 (profiles/r05_score_ab.txt; the
 // launch's algorithmic bytes are 28.0 MB): V = 1 15.5 us / 48.2 MB, V = 2 11.3 us / 28.2 MB, V = 4 22.0 us / 28.2 MB.
@@ -70,8 +173,9 @@ struct mbd_sweep {
   std::vector<float> temps, alphas, alphas_bar, sigmas;
   Stream stream, aux;
   // The normals of a step live in a ring of THREE buffers, so that the stream of the steps carries no event at all: the
-  // buffer step k+1's normals go into was last read by step k-2's weighted mean, which has finished once the rollout of
-  // step k-1 has STARTED — the host learns that from the progress word the rollout launches store into (pinned memory),
+  // buffer step k+1's normals go into was last read by step k-2's weighted mean — with an elite record by step k-2's selection,
+  // the launch behind it on the same stream; the record's injection into a buffer is on that stream too, behind the wait for
+  // ev_ready and in front of every reader —, which has finished once the rollout of step k-1 has STARTED — the host learns that from the progress word the rollout launches store into (pinned memory),
   // and the loop stays that close behind the device.  (Two buffers + events: a record behind every weighted mean and a
   // wait in front of every rollout idled the queue 17 us per step, profiles/r03_ring_ab.txt.)
   Event ev_ready[3];  // eps[b] holds the normals of its step (recorded on aux)
@@ -134,6 +238,9 @@ struct mbd_sweep {
   WeightingRec wt;
   // the pick record of all the sweep's episodes (mbd_sweep_set_mpc_pick) with every episode's slots and log
   PickRec pick;
+  // the elite record of all the sweep's plans (mbd_sweep_set_elites) and the to-go record (mbd_sweep_set_togo)
+  SweepEliteRec elite;
+  SweepTogoRec togo;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_sweep_mpc_open): it uses the batch's buffers above — slice 0 of d_mpc_states for
   // the states handed in, slice 0 of d_mpc_pred, d_mpc_queue, d_mpc_ybar — so a handle runs batches or a session, not both
@@ -254,7 +361,8 @@ static int sweep_results(mbd_sweep* w, float* mu_0ts_out, float* rew_means_out, 
 namespace {
 // the update rule's kernels of a lockstep step, behind the value record's launch: the step's, and mbd_debug_sweep_update's on
 // uploaded rewards.  step: slot of every plan's d_mu / d_rewmeans; mu_in: the mean of plan 0 the candidates were sampled around
-int sweep_pi_update(mbd_sweep* w, int step, const float* mu_in, long long mu_stride) {
+// recs: the step's (an elite and a to-go record's launches run; mask: the plans that take part in the selection), not the debug entry's
+int sweep_pi_update(mbd_sweep* w, int step, const float* mu_in, long long mu_stride, bool recs = false, unsigned mask = 0xffffffffu) {
   mbd_env* e = w->env;
   const mbd_plan_config& c = w->cfg;
   const int P = w->P, N = c.Nsample, Nd = c.Ndiffuse, HNu = w->HNu;
@@ -284,9 +392,17 @@ int sweep_pi_update(mbd_sweep* w, int step, const float* mu_in, long long mu_str
     sb.ybar_in = mu_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
     if (w->wt.has)
       MBD_TRY(launch_weigh_batch(w->wt, P, N, Nd, w->d_rews, c.temp_sample, w->d_temps, w->d_weights, w->d_rewmeans + step, s));
-    launch_score_wmean_batch(wmean_batch_v(N), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
-                             c.temp_sample, 0, w->d_weights.get(), w->d_rewmeans + step, (const float*)w->d_Y0s, HNu, mu_in, 1.0f, 1.0f,
-                             1.0f, 0, mu_out, 0, 0.0f, (float*)nullptr, sb);
+    if (recs && w->togo.has) {  // the to-go record's two launches in the fused launch's place (an mppi plan's TogoUpdate per plan)
+      TogoUpdate A{};
+      A.rews = w->d_rews; A.weights = w->d_weights; A.rew_mean = w->d_rewmeans + step; A.cand = w->d_Y0s; A.ybar_i = mu_in;
+      A.ybar_im1 = mu_out; A.N = N; A.H = c.Hsample; A.Nu = w->Nu; A.temp = c.temp_sample; A.std_guard = 0;
+      A.alpha_i = 1.0f; A.alpha_bar_i = 1.0f; A.alpha_bar_im1 = 1.0f; A.literal = 0; A.lazy = 0; A.sigma = 0.0f;
+      MBD_TRY(w->togo.launch(P, w->d_rewss, A, sb, s));
+    } else {
+      launch_score_wmean_batch(wmean_batch_v(N), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
+                               c.temp_sample, 0, w->d_weights.get(), w->d_rewmeans + step, (const float*)w->d_Y0s, HNu, mu_in, 1.0f, 1.0f,
+                               1.0f, 0, mu_out, 0, 0.0f, (float*)nullptr, sb);
+    }
     if (c.update_method == 2) {
       hipLaunchKernelGGL(cma_spread_kernel, dim3((HNu + 63) / 64, (unsigned)P), b64, 0, s, (const float*)w->d_weights,
                          (const float*)w->d_Y0s, N, HNu, mu_in, w->d_spread, pb);
@@ -294,6 +410,8 @@ int sweep_pi_update(mbd_sweep* w, int step, const float* mu_in, long long mu_str
     }
   }
   HIP_TRY(hipGetLastError());
+  // the elite record: the selection behind the update, over the rewards the score read and the materialised candidates
+  if (recs) MBD_TRY(w->elite.select(P, w->d_rews, N, w->d_Y0s, (long long)per_plan, HNu, 0, 0.0f, mu_in, mu_stride, mask, s));
   return MBD_OK;
 }
 
@@ -325,6 +443,8 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
                        (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s, ns.g);
   }
   HIP_TRY(hipGetLastError());
+  // the elite record: ONE launch between the sampler and the rollout rewrites every plan's first rows
+  MBD_TRY(w->elite.inject(P, w->d_Y0s, (long long)per_plan, HNu, 0, 0.0f, mu_in, mu_stride, ns.g, 0xffffffffu, s));
   MBD_TRY(w->timing.begin(s));
   const int sw[3] = {N, S, 0};
   MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, w->val.final(), s, nullptr, sw));
@@ -333,7 +453,7 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
   if (w->obj.has) MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_Y0s, false, 0.0f, nullptr, 0, s));
   // the value record: one launch over the P N rows behind it (one net: the plans' rows are one batch)
   MBD_TRY(w->val.launch_step(w->d_rews, P * N, s));
-  return sweep_pi_update(w, step, mu_in, mu_stride);
+  return sweep_pi_update(w, step, mu_in, mu_stride, true);
 }
 }  // namespace
 
@@ -347,6 +467,8 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
     std::vector<float> ones((size_t)P, 1.0f);  // sigma = 1.0 (path_integral.py:131)
     HIP_TRY(hipMemcpy(w->d_sigma, ones.data(), sizeof(float) * P, hipMemcpyHostToDevice));
   }
+  MBD_TRY(w->elite.table_all(P, HNu, -1, s));  // (an elite record: no plan has elites, and the logs begin)
+  w->elite.restart();
   HIP_TRY(hipStreamSynchronize(s));
   auto t0 = std::chrono::steady_clock::now();
   w->wt.begin();
@@ -393,6 +515,8 @@ struct SweepStep {
   NoiseSpec next_ns;           // the noise shape and basis that following step samples under
   const float* xref = nullptr; // the demo table of the step: a tick's window of a batch with a demo record, nullptr: the env's ...
   float rew_xref = 0.0f;       // ... and the demo's reward level in the blend: the record's, or the env's
+  const float* g = nullptr;    // the noise shape THIS step's sampler was handed (an elite record's injection keeps frozen elements)
+  unsigned mask = 0xffffffffu; // the plans an elite record's launches take part for (a session's mixed tick: not the idling ones)
 };
 
 // the normals of a step depend on its keys only: they are generated on the second stream while the previous step's
@@ -423,7 +547,9 @@ void sweep_split_keys(const mbd_sweep* w, std::vector<uint32_t>& rng, SweepKeys&
 // what a lockstep step launches behind the value record's launch — the weigh kernel under a weighting record, then the score +
 // weighted mean over the P plans —: the step's, and mbd_debug_sweep_update's on uploaded rewards.  i: diffusion step; slot: of
 // every plan's d_mu / d_rewmeans; eps: the step's normals [P][N][HNu]; ybar_in: Ybar_i of plan 0, plan k's ybar_in_stride further
-int sweep_update(mbd_sweep* w, int i, int slot, const float* eps, const float* ybar_in, long long ybar_in_stride, float rew_xref) {
+// recs: the step's (an elite and a to-go record's launches run; mask: the plans that take part in the selection), not the debug entry's
+int sweep_update(mbd_sweep* w, int i, int slot, const float* eps, const float* ybar_in, long long ybar_in_stride, float rew_xref,
+                 bool recs = false, unsigned mask = 0xffffffffu) {
   const mbd_plan_config& c = w->cfg;
   const int P = w->P, N = c.Nsample, Nd = c.Ndiffuse, HNu = w->HNu;
   hipStream_t s = w->stream;
@@ -432,11 +558,23 @@ int sweep_update(mbd_sweep* w, int i, int slot, const float* eps, const float* y
   sb.ybar_in = ybar_in_stride; sb.ybar_out = (long long)(Nd - 1) * HNu; sb.keep = 0; sb.temps = w->d_temps;
   if (w->wt.has)
     MBD_TRY(launch_weigh_batch(w->wt, P, N, Nd, w->d_rews, c.temp_sample, w->d_temps, w->d_weights, w->d_rewmeans + slot, s));
-  launch_score_wmean_batch(wmean_batch_v(N), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), c.enable_demo ? w->d_lp.get() : nullptr, N,
-                           rew_xref, c.temp_sample, 1, w->d_weights.get(), w->d_rewmeans + slot, eps, HNu, ybar_in,
-                           w->alphas[i], w->alphas_bar[i], w->alphas_bar[i - 1], c.literal_score,
-                           w->d_mu + (size_t)slot * HNu, 1, w->sigmas[i], (float*)nullptr, sb);
+  if (recs && w->togo.has) {  // the to-go record's two launches in the fused launch's place (a plan's TogoUpdate per plan)
+    TogoUpdate A{};
+    A.rews = w->d_rews; A.weights = w->d_weights; A.rew_mean = w->d_rewmeans + slot; A.cand = eps; A.ybar_i = ybar_in;
+    A.ybar_im1 = w->d_mu + (size_t)slot * HNu; A.N = N; A.H = c.Hsample; A.Nu = w->Nu; A.temp = c.temp_sample; A.std_guard = 1;
+    A.alpha_i = w->alphas[i]; A.alpha_bar_i = w->alphas_bar[i]; A.alpha_bar_im1 = w->alphas_bar[i - 1]; A.literal = c.literal_score;
+    A.lazy = 1; A.sigma = w->sigmas[i];
+    MBD_TRY(w->togo.launch(P, w->d_rewss, A, sb, s));
+  } else {
+    launch_score_wmean_batch(wmean_batch_v(N), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), c.enable_demo ? w->d_lp.get() : nullptr, N,
+                             rew_xref, c.temp_sample, 1, w->d_weights.get(), w->d_rewmeans + slot, eps, HNu, ybar_in,
+                             w->alphas[i], w->alphas_bar[i], w->alphas_bar[i - 1], c.literal_score,
+                             w->d_mu + (size_t)slot * HNu, 1, w->sigmas[i], (float*)nullptr, sb);
+  }
   HIP_TRY(hipGetLastError());
+  // the elite record: the selection behind the update, over the rewards the score read and the step's normals — on the steps' stream,
+  // so it is now eps[cur]'s last reader (see mbd_sweep)
+  if (recs) MBD_TRY(w->elite.select(P, w->d_rews, N, eps, (long long)N * HNu, HNu, 1, w->sigmas[i], ybar_in, ybar_in_stride, mask, s));
   return MBD_OK;
 }
 
@@ -466,6 +604,9 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(w->ev_ready[nxt], w->aux));
   }
+  // the elite record: ONE launch on the steps' stream, behind the wait for eps[cur] and in front of the rollout, rewrites every
+  // plan's first rows of normals
+  MBD_TRY(w->elite.inject(P, w->d_eps[cur], (long long)N * w->HNu, w->HNu, 1, w->sigmas[i], st.ybar_in, st.ybar_in_stride, st.g, st.mask, s));
   LazyArgs lz;
   lz.ybar = st.ybar_in;
   lz.sigma = w->sigmas[i];
@@ -485,7 +626,7 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
     MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_eps[cur], true, w->sigmas[i], st.ybar_in, st.ybar_in_stride, s));
   // the value record: one launch over the P N rows behind it (one net: the plans' rows are one batch)
   MBD_TRY(w->val.launch_step(w->d_rews, P * N, s));
-  return sweep_update(w, i, st.slot, w->d_eps[cur].get(), st.ybar_in, st.ybar_in_stride, st.rew_xref);
+  return sweep_update(w, i, st.slot, w->d_eps[cur].get(), st.ybar_in, st.ybar_in_stride, st.rew_xref, true, st.mask);
 }
 }  // namespace
 
@@ -500,6 +641,8 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
   hipStream_t s = w->stream;
   if (c.update_method != 0) return sweep_run_path_integral(w, keys, mu_0ts_out, rew_means_out, rew_final_out, loop_seconds_out);
   std::vector<uint32_t> rng(keys, keys + 2 * (size_t)P);
+  MBD_TRY(w->elite.table_all(P, HNu, -1, s));  // (an elite record: no plan has elites, and the logs begin)
+  w->elite.restart();
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(w->aux));
   progress_reset(w->h_progress);
@@ -518,6 +661,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
     st.next_keys = i > 1 ? &sk : nullptr;
     st.next_ns = w->noise_always();
     st.rew_xref = e->rew_xref;
+    st.g = w->shape_always();
     MBD_TRY(sweep_step(w, st));
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -619,6 +763,7 @@ extern "C" int mbd_sweep_set_objective(mbd_sweep* w, const mbd_objective* rec) {
   NO_SWEEP_SESSION(w, "set_objective");
   float wsum = 0.0f;
   if (rec) MBD_TRY(check_objective(rec, w->cfg.Hsample, w->Nu, &wsum));  // (before any device access)
+  if (rec && w->togo.has) return refuse_beside_togo("objective record", "sweep");
   return w->obj.set(rec, wsum, w->env->device, w->P, w->cfg.Nsample, w->cfg.Hsample, w->Nu, (size_t)w->cfg.Nsample);
 }
 
@@ -632,6 +777,7 @@ extern "C" int mbd_sweep_set_value(mbd_sweep* w, const mbd_value* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   NO_SWEEP_SESSION(w, "set_value");
   if (rec) MBD_TRY(check_value(rec, w->env->state_size(), w->env->kind == ENV_MODEL));  // (before any device access)
+  if (rec && w->togo.has) return refuse_beside_togo("value record", "sweep");
   return w->val.set(rec, w->env, (size_t)w->P * w->cfg.Nsample, w->P);
 }
 
@@ -642,6 +788,7 @@ extern "C" int mbd_sweep_set_weighting(mbd_sweep* w, const mbd_weighting* rec) {
   if (rec) MBD_TRY(check_weighting(rec));  // (before any device access)
   if (rec && w->cfg.enable_demo)
     return fail(MBD_ERR_UNSUPPORTED, "weighting record: enable_demo=1: the demo blend standardises twice, an ESS target is not defined there");
+  if (rec && w->togo.has) return refuse_beside_togo("weighting record", "sweep");
   return w->wt.set(rec, w->env->device, w->P, w->cfg.Ndiffuse - 1, w->cfg.Nsample);
 }
 
@@ -649,6 +796,209 @@ extern "C" int mbd_sweep_peek_weighting(mbd_sweep* w, int k, float* temp_out, fl
                                         int* count_out) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   return w->wt.peek(w->env, k, temp_out, ess_out, kept_out, capacity, count_out, "sweep");
+}
+
+// one elite record for all plans of the sweep (include/mbd_hip.h mbd_elites), as mbd_plan_set_elites: the field checks are the
+// plan's, on the sweep's config; no plan has elites afterwards
+extern "C" int mbd_sweep_set_elites(mbd_sweep* w, const mbd_elites* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (rec) MBD_TRY(mbd_debug_check_elites(rec, w->cfg.Nsample, w->cfg.update_method, w->cfg.enable_demo));  // (before any device access)
+  NO_SWEEP_SESSION(w, "set_elites");
+  SweepEliteRec& L = w->elite;
+  if (!rec && !L.has) return MBD_OK;  // (nothing to clear: no device is touched)
+  HIP_TRY(hipSetDevice(w->env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the elites or write the logs)
+  L.has = false;
+  L.restart();
+  if (!rec) return MBD_OK;
+  L.n = rec->n_elites; L.nominal = rec->nominal; L.carry = rec->carry;
+  L.rows = L.n > 0 ? L.n : 1;
+  MBD_TRY(L.alloc(w->P, w->HNu));
+  HIP_TRY(L.d_log_count.grow((size_t)w->P * kLogCap));
+  HIP_TRY(L.d_log_kept.grow((size_t)w->P * kLogCap));
+  HIP_TRY(L.d_log_top.grow((size_t)w->P * kLogCap));
+  L.has = true;
+  MBD_TRY(L.table_all(w->P, w->HNu, -1, w->stream));
+  HIP_TRY(hipStreamSynchronize(w->stream));
+  return MBD_OK;
+}
+
+extern "C" int mbd_sweep_peek_elites(mbd_sweep* w, int k, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
+                                     int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "peek_elites: plan k=%d outside [0,%d)", k, w->P);
+  const SweepEliteRec& L = w->elite;
+  if (!L.has) return fail(MBD_ERR_STATE, "peek_elites: the sweep has no elite record");
+  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_elites: capacity=%d", capacity);
+  HIP_TRY(hipSetDevice(w->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t row = (size_t)k * L.rows, log = (size_t)k * kLogCap;
+  const long long steps = L.steps[k];
+  if (elites_out) HIP_TRY(hipMemcpy(elites_out, L.d_E + row * w->HNu, sizeof(float) * (size_t)L.n * w->HNu, hipMemcpyDeviceToHost));
+  if (returns_out) HIP_TRY(hipMemcpy(returns_out, L.d_R + row, sizeof(float) * L.n, hipMemcpyDeviceToHost));
+  if (src_out) HIP_TRY(hipMemcpy(src_out, L.d_src + row, sizeof(int32_t) * L.n, hipMemcpyDeviceToHost));
+  if (count_out) HIP_TRY(hipMemcpy(count_out, L.d_count + k, sizeof(int32_t), hipMemcpyDeviceToHost));
+  MBD_TRY(ring_read(L.d_log_count.get() + log, 1, steps, kLogCap, capacity, log_count));
+  MBD_TRY(ring_read(L.d_log_kept.get() + log, 1, steps, kLogCap, capacity, log_kept));
+  MBD_TRY(ring_read(L.d_log_top.get() + log, 1, steps, kLogCap, capacity, log_top));
+  if (n_log_out) *n_log_out = (int)(steps < 0x7fffffffll ? steps : 0x7fffffffll);
+  return MBD_OK;
+}
+
+// one to-go record for all plans of the sweep (include/mbd_hip.h mbd_togo), as mbd_plan_set_togo
+extern "C" int mbd_sweep_set_togo(mbd_sweep* w, const mbd_togo* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (rec) {  // (before any device access)
+    MBD_TRY(mbd_debug_check_togo(rec, w->cfg.Hsample, w->cfg.Nsample, w->cfg.update_method, w->cfg.enable_demo));
+    const char* other = w->obj.has ? "an objective" : w->val.has ? "a value" : w->wt.has ? "a weighting" : nullptr;
+    if (other)
+      return fail(MBD_ERR_UNSUPPORTED, "to-go record: the sweep carries %s record: what that record means per horizon row is not defined",
+                  other);
+  }
+  NO_SWEEP_SESSION(w, "set_togo");
+  SweepTogoRec& L = w->togo;
+  if (!rec && !L.has) return MBD_OK;  // (nothing to clear: no device is touched)
+  HIP_TRY(hipSetDevice(w->env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still write R and W)
+  L.has = false;
+  if (!rec) return MBD_OK;
+  L.layout(rec->block, rec->min_tail, w->cfg.Hsample);
+  const size_t n = (size_t)w->P * L.G * w->cfg.Nsample;
+  HIP_TRY(L.d_R.grow(n));
+  HIP_TRY(L.d_W.grow(n));
+  HIP_TRY(hipMemset(L.d_R, 0xff, sizeof(float) * n));  // (no step yet: mbd_sweep_peek_togo says so)
+  HIP_TRY(hipMemset(L.d_W, 0xff, sizeof(float) * n));
+  HIP_TRY(hipDeviceSynchronize());
+  L.stepped = false;
+  L.has = true;
+  return MBD_OK;
+}
+
+extern "C" int mbd_sweep_peek_togo(mbd_sweep* w, int k, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "peek_togo: plan k=%d outside [0,%d)", k, w->P);
+  const SweepTogoRec& L = w->togo;
+  if (!L.has) return fail(MBD_ERR_STATE, "peek_togo: the sweep has no to-go record");
+  HIP_TRY(hipSetDevice(w->env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t N = (size_t)w->cfg.Nsample, gn = (size_t)L.G * N;
+  if (starts_out) memcpy(starts_out, L.starts.data(), sizeof(int32_t) * L.G);
+  if (R_out) HIP_TRY(hipMemcpy(R_out, L.d_R + (size_t)k * gn, sizeof(float) * gn, hipMemcpyDeviceToHost));
+  if (W_out) HIP_TRY(hipMemcpy(W_out, L.d_W + (size_t)k * gn, sizeof(float) * gn, hipMemcpyDeviceToHost));
+  // (group 0's weights are the plan's own slice of d_weights, once a step of the record has written them)
+  if (W_out && L.stepped) HIP_TRY(hipMemcpy(W_out, w->d_weights + (size_t)k * N, sizeof(float) * N, hipMemcpyDeviceToHost));
+  if (n_groups_out) *n_groups_out = L.G;
+  return MBD_OK;
+}
+
+// include/mbd_hip_debug.h: an elite record's two batch launches alone on caller-given arrays for P plans — the injection, then the
+// selection — by a scratch record's own members; no sweep.  What is read back is filled with all-ones bits first.
+extern "C" int mbd_debug_sweep_elites_step(int P, uint32_t mask, const float* rews, const float* cand, int N, int HNu, const float* ybar,
+                                           float sigma, int lazy, const float* g, int n_elites, int nominal, const float* E_in,
+                                           const int32_t* count_in, float* cand_out, float* E_out, float* R_out, int32_t* src_out,
+                                           int32_t* count_out, int32_t* kept_out, float* top_out) {
+  if (!rews || !cand || !ybar || !count_in) return fail(MBD_ERR_INVALID, "sweep_elites_step: NULL argument");
+  if (P < 1 || P > MBD_SWEEP_MAX_PLANS) return fail(MBD_ERR_INVALID, "sweep_elites_step: P=%d outside [1,%d]", P, MBD_SWEEP_MAX_PLANS);
+  if (N < 1 || HNu < 1 || (uint64_t)P * (uint64_t)N * (uint64_t)HNu > (1ull << 27))
+    return fail(MBD_ERR_INVALID, "sweep_elites_step: P=%d N=%d HNu=%d", P, N, HNu);
+  if (n_elites < 0 || n_elites > kEliteMax) return fail(MBD_ERR_INVALID, "sweep_elites_step: n_elites=%d outside [0, %d]", n_elites, kEliteMax);
+  if (nominal != 0 && nominal != 1) return fail(MBD_ERR_INVALID, "sweep_elites_step: nominal=%d: 0 or 1", nominal);
+  if (n_elites + nominal >= N) return fail(MBD_ERR_INVALID, "sweep_elites_step: n_elites=%d + nominal=%d must lie below N=%d", n_elites, nominal, N);
+  for (int k = 0; k < P; ++k) {
+    if (count_in[k] < 0 || count_in[k] > n_elites)
+      return fail(MBD_ERR_INVALID, "sweep_elites_step: count[%d]=%d outside [0, n_elites=%d]", k, count_in[k], n_elites);
+    if (count_in[k] > 0 && !E_in) return fail(MBD_ERR_INVALID, "sweep_elites_step: count[%d]=%d without elites", k, count_in[k]);
+  }
+  if (lazy && !(sigma > 0.0f)) return fail(MBD_ERR_INVALID, "sweep_elites_step: sigma=%g: a lazy plan's sigma is > 0", (double)sigma);
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  const size_t PN = (size_t)P * N, per_plan = (size_t)N * HNu;
+  DevBuf<float> d_rews, d_cand, d_ybar, d_g;
+  SweepEliteRec L;
+  L.n = n_elites; L.nominal = nominal; L.rows = n_elites > 0 ? n_elites : 1; L.has = true;
+  const size_t PR = (size_t)P * L.rows;
+  HIP_TRY(d_rews.upload(rews, PN));
+  HIP_TRY(d_cand.upload(cand, PN * HNu));
+  HIP_TRY(d_ybar.upload(ybar, (size_t)P * HNu));
+  if (g) HIP_TRY(d_g.upload(g, HNu));
+  HIP_TRY(L.d_E.alloc_poisoned(PR * HNu));
+  if (E_in && n_elites > 0) HIP_TRY(hipMemcpy(L.d_E, E_in, sizeof(float) * PR * HNu, hipMemcpyHostToDevice));
+  HIP_TRY(L.d_R.alloc_poisoned(PR));
+  HIP_TRY(L.d_src.alloc_poisoned(PR));
+  HIP_TRY(L.d_count.upload(count_in, P));
+  L.log_cap = 1;  // (the log of the scratch record is one entry long per plan)
+  HIP_TRY(L.d_log_count.alloc_poisoned(P));
+  HIP_TRY(L.d_log_kept.alloc_poisoned(P));
+  HIP_TRY(L.d_log_top.alloc_poisoned(P));
+  if (E_in && n_elites > 0) {  // (E' of a masked-out plan must read back as it went in: poison what the caller did not give)
+    for (int k = 0; k < P; ++k)
+      if (count_in[k] < L.rows)
+        HIP_TRY(hipMemset(L.d_E + ((size_t)k * L.rows + count_in[k]) * HNu, 0xff, sizeof(float) * (size_t)(L.rows - count_in[k]) * HNu));
+  }
+  MBD_TRY(L.inject(P, d_cand, (long long)per_plan, HNu, lazy ? 1 : 0, sigma, d_ybar, HNu, d_g, mask, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(d_cand.download(cand_out, PN * HNu));
+  MBD_TRY(L.select(P, d_rews, N, d_cand, (long long)per_plan, HNu, lazy ? 1 : 0, sigma, d_ybar, HNu, mask, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(L.d_E.download(E_out, PR * HNu));
+  HIP_TRY(L.d_R.download(R_out, PR));
+  HIP_TRY(L.d_src.download(src_out, PR));
+  HIP_TRY(L.d_count.download(count_out, P));
+  HIP_TRY(L.d_log_kept.download(kept_out, P));
+  HIP_TRY(L.d_log_top.download(top_out, P));
+  std::vector<int32_t> cnt_word(P), cnt_log(P);  // (count' as the word holds it must agree with the log entry's copy)
+  HIP_TRY(L.d_count.download(cnt_word.data(), P));
+  HIP_TRY(L.d_log_count.download(cnt_log.data(), P));
+  for (int k = 0; k < P; ++k)
+    if (((mask >> k) & 1u) && cnt_word[k] != cnt_log[k])
+      return fail(MBD_ERR_STATE, "sweep_elites_step: plan %d: count word %d, log entry %d", k, cnt_word[k], cnt_log[k]);
+  return MBD_OK;
+}
+
+// include/mbd_hip_debug.h: a to-go record's two batch launches alone on caller-given arrays for P plans, by a scratch record's own
+// launch; no sweep.  What is read back is filled with all-ones bits (quiet NaN) first.
+extern "C" int mbd_debug_sweep_togo_step(int P, const float* temps, const float* cand, const float* ybar, const float* rews,
+                                         const float* rewss, int N, int H, int Nu, int block, int min_tail, int lazy, float sigma,
+                                         int std_guard, float alpha_i, float alpha_bar_i, float alpha_bar_im1, int literal,
+                                         float* ybar_out, float* R_out, float* W_out, float* rew_mean_out) {
+  if (!temps || !cand || !ybar || !rews || !rewss) return fail(MBD_ERR_INVALID, "sweep_togo_step: NULL argument");
+  if (P < 1 || P > MBD_SWEEP_MAX_PLANS) return fail(MBD_ERR_INVALID, "sweep_togo_step: P=%d outside [1,%d]", P, MBD_SWEEP_MAX_PLANS);
+  if (N < 1 || H < 1 || Nu < 1 || (uint64_t)P * (uint64_t)N * (uint64_t)H * (uint64_t)Nu > (1ull << 27))
+    return fail(MBD_ERR_INVALID, "sweep_togo_step: P=%d N=%d H=%d Nu=%d", P, N, H, Nu);
+  if (block < 1) return fail(MBD_ERR_INVALID, "sweep_togo_step: block=%d: at least 1", block);
+  if (min_tail < 1 || min_tail > H) return fail(MBD_ERR_INVALID, "sweep_togo_step: min_tail=%d outside [1, H=%d]", min_tail, H);
+  if (N > 12288) return fail(MBD_ERR_INVALID, "sweep_togo_step: N=%d above 12288", N);
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  const size_t HNu = (size_t)H * Nu, PN = (size_t)P * N;
+  SweepTogoRec L;
+  L.layout(block, min_tail, H);
+  const size_t gn = (size_t)P * L.G * N;
+  DevBuf<float> d_temps, d_cand, d_ybar, d_rews, d_rewss, d_out, d_w, d_mean;
+  HIP_TRY(d_temps.upload(temps, P));
+  HIP_TRY(d_cand.upload(cand, PN * HNu));
+  HIP_TRY(d_ybar.upload(ybar, (size_t)P * HNu));
+  HIP_TRY(d_rews.upload(rews, PN));
+  HIP_TRY(d_rewss.upload(rewss, PN * H));
+  HIP_TRY(d_out.alloc_poisoned((size_t)P * HNu));
+  HIP_TRY(d_w.alloc_poisoned(PN));
+  HIP_TRY(d_mean.alloc_poisoned(P));
+  HIP_TRY(L.d_R.alloc_poisoned(gn));
+  HIP_TRY(L.d_W.alloc_poisoned(gn));
+  TogoUpdate A{};
+  A.rews = d_rews; A.weights = d_w; A.rew_mean = d_mean; A.cand = d_cand; A.ybar_i = d_ybar; A.ybar_im1 = d_out;
+  A.N = N; A.H = H; A.Nu = Nu; A.temp = 0.0f; A.std_guard = std_guard ? 1 : 0; A.alpha_i = alpha_i; A.alpha_bar_i = alpha_bar_i;
+  A.alpha_bar_im1 = alpha_bar_im1; A.literal = literal ? 1 : 0; A.lazy = lazy ? 1 : 0; A.sigma = sigma;
+  ScoreBatch sb;
+  sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = 1; sb.cand = (long long)N * (long long)HNu; sb.ybar_in = (long long)HNu;
+  sb.ybar_out = (long long)HNu; sb.keep = 0; sb.temps = d_temps;
+  MBD_TRY(L.launch(P, d_rewss, A, sb, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(d_out.download(ybar_out, (size_t)P * HNu));
+  HIP_TRY(L.d_R.download(R_out, gn));
+  HIP_TRY(L.d_W.download(W_out, gn));
+  if (W_out)  // (group 0's weights: every plan's row 0)
+    HIP_TRY(hipMemcpy2D(W_out, sizeof(float) * (size_t)L.G * N, d_w, sizeof(float) * N, sizeof(float) * N, P, hipMemcpyDeviceToHost));
+  HIP_TRY(d_mean.download(rew_mean_out, P));
+  return MBD_OK;
 }
 
 // one pick record for all episodes of the sweep (include/mbd_hip.h mbd_mpc_pick), as mbd_plan_set_mpc_pick
@@ -829,6 +1179,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     ~ObjEpisode() { o.episode_end(); }
   } obj_episode{w->obj};
   MBD_TRY(w->pick.start(T));  // (a pick record's logs: one entry per tick and episode)
+  w->elite.restart();         // (an elite record's logs: the episodes' steps)
   HIP_TRY(hipStreamSynchronize(s));
   progress_reset(w->h_progress);
   const auto t0 = std::chrono::steady_clock::now();
@@ -857,6 +1208,9 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     const float* states_t = w->d_mpc_states + (size_t)t * P * S;
     const int i_start = t == 0 ? Nd - 1 : K;
     w->wt.begin();  // (a weighting record's log holds the last tick's steps)
+    // with an elite record, ONE launch in front of the tick's first sampler: no elites in tick 0 and without carry, otherwise every
+    // episode's shifted E rows forward with its mean
+    MBD_TRY(w->elite.table_all(P, HNu, t == 0 || !w->elite.carry ? -1 : EN, s));
     // with a delay record: every episode's committed rows, the prediction of where they leave it, and the plans from there
     const float* q_in = has_delay ? w->d_mpc_queue + (size_t)(t & 1) * P * Q : nullptr;
     float* q_out = has_delay ? w->d_mpc_queue + (size_t)((t + 1) & 1) * P * Q : nullptr;
@@ -900,6 +1254,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       st.next_ns = (t == 0 && i > 1) ? w->noise_always() : w->noise_warm();
       st.xref = has_demo ? w->demo.window(t) : nullptr;
       st.rew_xref = has_demo ? w->demo.rew_xref : e->rew_xref;
+      st.g = t == 0 ? w->shape_always() : w->shape_warm();
       MBD_TRY(sweep_step(w, st));
     }
     // the boundary: the logs of M_{.,t}, its first E rows and Ybar of tick t+1; then the rows executed from s_{.,t}
@@ -1069,6 +1424,7 @@ extern "C" int mbd_sweep_mpc_open(mbd_sweep* w, const mbd_mpc_config* mc, const 
   MBD_TRY(w->obj.episode_start(w->delay.has ? w->d_mpc_queue + (Q - w->Nu) : nullptr, Q, s));
   // (nothing fails from here on: the bookkeeping of the previous batch's logs goes last)
   if (w->delay.has) w->delay.pred_ticks = 0;  // (mbd_sweep_peek_mpc_predicted does not serve sessions)
+  w->elite.restart();                         // (an elite record's logs: the session's steps)
   ss.mc = *mc;
   ss.rng.assign(keys, keys + 2 * (size_t)P);
   for (int k = 0; k < MBD_SWEEP_MAX_PLANS; ++k) { ss.cold[k] = true; ss.flags[k] = 0; }
@@ -1125,6 +1481,11 @@ extern "C" int mbd_sweep_mpc_submit(mbd_sweep* w, const float* states) {
     plan_from = w->d_mpc_pred;
   }
   progress_reset(w->h_progress);  // (both streams are idle: see above)
+  {  // with an elite record: a cold episode's elites go, the others' shift with their means (or go as well, without carry)
+    EliteShifts sh;
+    for (int k = 0; k < MBD_SWEEP_MAX_PLANS; ++k) sh.s[k] = ss.cold[k] || !w->elite.carry ? -1 : EN;
+    MBD_TRY(w->elite.table(P, HNu, sh, 0xffffffffu, s));
+  }
   const int i_start = any_cold ? Nd - 1 : K;
   const long long mu_stride = (long long)(Nd - 1) * HNu;
   bool active[MBD_SWEEP_MAX_PLANS], active_next[MBD_SWEEP_MAX_PLANS];
@@ -1152,6 +1513,9 @@ extern "C" int mbd_sweep_mpc_submit(mbd_sweep* w, const float* states) {
     st.next_ns = ns;
     st.xref = w->demo.has ? w->demo.window(0) : nullptr;
     st.rew_xref = w->demo.has ? w->demo.rew_xref : e->rew_xref;
+    st.g = ns.g;
+    st.mask = 0;  // (an elite record's launches leave out the episodes that idle through this step)
+    for (int k = 0; k < P; ++k) st.mask |= (ss.cold[k] || i <= K) ? 1u << k : 0u;
     MBD_TRY(sweep_step(w, st));
   }
   // a pick record's launches, then the next tick's previous actions (an objective record), in FRONT of the boundary, which stays
@@ -1217,6 +1581,12 @@ extern "C" int mbd_sweep_mpc_reset_mean(mbd_sweep* w, int k) {
   if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "mpc_reset_mean: episode k=%d outside [0,%d)", k, w->P);
   if (w->session.in_flight) return fail(MBD_ERR_STATE, "mpc_reset_mean: a tick is in flight (mbd_sweep_mpc_collect first)");
   w->session.cold[k] = true;  // (the next submit zeroes its Ybar; its queue stays)
+  if (w->elite.has) {  // (an elite record's elites of episode k are gone: written now as well, so that mbd_sweep_peek_elites says so)
+    HIP_TRY(hipSetDevice(w->env->device));
+    EliteShifts sh;
+    for (int& v : sh.s) v = -1;
+    MBD_TRY(w->elite.table(w->P, w->HNu, sh, 1u << k, w->stream));
+  }
   return MBD_OK;
 }
 

@@ -178,6 +178,7 @@ EXPORTS = [
     "mbd_plan_set_value", "mbd_plan_peek_value", "mbd_plan_eval_value", "mbd_sweep_set_value",
     "mbd_plan_set_adapt", "mbd_plan_peek_adapt", "mbd_plan_set_elites", "mbd_plan_peek_elites",
     "mbd_plan_set_togo", "mbd_plan_peek_togo",
+    "mbd_sweep_set_elites", "mbd_sweep_peek_elites", "mbd_sweep_set_togo", "mbd_sweep_peek_togo",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
     "mbd_plan_enable_timing",
@@ -277,6 +278,10 @@ def load() -> C.CDLL:
     lib.mbd_plan_set_togo.argtypes = [_vp, C.POINTER(Togo)]
     lib.mbd_plan_peek_togo.argtypes = [_vp, _vp, _vp, _vp, _vp]
     lib.mbd_plan_peek_elites.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
+    lib.mbd_sweep_set_elites.argtypes = [_vp, C.POINTER(Elites)]
+    lib.mbd_sweep_peek_elites.argtypes = [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
+    lib.mbd_sweep_set_togo.argtypes = [_vp, C.POINTER(Togo)]
+    lib.mbd_sweep_peek_togo.argtypes = [_vp, _i, _vp, _vp, _vp, _vp]
     lib.mbd_plan_peek_adapt.argtypes = [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
     lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
@@ -651,6 +656,56 @@ def debug_elites_select(rews, cand, ybar, sigma, lazy, n_elites, nominal, count_
     check(lib.mbd_debug_elites_select(np_ptr(rews), np_ptr(cand), N, HNu, np_ptr(ybar), float(sigma), int(bool(lazy)), int(n_elites),
                                       int(nominal), int(count_in), *[np_ptr(o) for o in outs]))
     return _elites_result(int(n_elites), outs)
+
+
+def debug_sweep_elites_step(rews, cand, ybar, sigma, lazy, g, n_elites, nominal, E_in, count_in, mask=0xffffffff) -> dict:
+    """include/mbd_hip_debug.h: an elite record's two batch launches alone on the device for P plans — ``rews`` [P, N], ``cand``
+    [P, N, HNu], ``ybar`` [P, HNu], ``E_in`` [P, max(n_elites, 1), HNu], ``count_in`` [P]; ``mask``: the plans that take part.
+    Returns dict(cand, E [P, max(n_elites, 1), HNu], R, src [P, max(n_elites, 1)], count, kept, top [P]): what no kernel wrote has
+    all bits set (``count``: ``count_in``)."""
+    lib = load()
+    cand = np.ascontiguousarray(cand, np.float32)
+    P, N = cand.shape[:2]
+    cand = cand.reshape(P, N, -1)
+    HNu, k = cand.shape[2], max(int(n_elites), 1)
+    rews = np.ascontiguousarray(rews, np.float32).reshape(P, N)
+    ybar = np.ascontiguousarray(ybar, np.float32).reshape(P, HNu)
+    g = None if g is None else np.ascontiguousarray(g, np.float32).reshape(HNu)
+    E_in = np.ascontiguousarray(E_in, np.float32).reshape(P, k, HNu)
+    count_in = np.ascontiguousarray(count_in, np.int32).reshape(P)
+    cand_out, E, R, src = np.zeros_like(cand), np.zeros((P, k, HNu), np.float32), np.zeros((P, k), np.float32), np.zeros((P, k), np.int32)
+    count, kept, top = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.float32)
+    lib.mbd_debug_sweep_elites_step.argtypes = [_i, C.c_uint32, _vp, _vp, _i, _i, _vp, _f, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _vp, _vp]
+    check(lib.mbd_debug_sweep_elites_step(P, int(mask) & 0xffffffff, np_ptr(rews), np_ptr(cand), N, HNu, np_ptr(ybar), float(sigma),
+                                          int(bool(lazy)), None if g is None else np_ptr(g), int(n_elites), int(nominal), np_ptr(E_in),
+                                          np_ptr(count_in), np_ptr(cand_out), np_ptr(E), np_ptr(R), np_ptr(src), np_ptr(count),
+                                          np_ptr(kept), np_ptr(top)))
+    return dict(cand=cand_out, E=E, R=R, src=src, count=count, kept=kept, top=top)
+
+
+def debug_sweep_togo_step(temps, cand, ybar, rews, rewss, Nu: int, block: int, min_tail: int, lazy, sigma: float, std_guard,
+                          alpha_i: float, alpha_bar_i: float, alpha_bar_im1: float, literal, n_groups: int) -> dict:
+    """include/mbd_hip_debug.h: a to-go record's two batch launches alone on the device for P plans under ``temps`` [P] — ``cand``
+    [P, N, H * Nu], ``ybar`` [P, H * Nu], ``rews`` [P, N], ``rewss`` [P, N, H].  Returns dict(ybar [P, H, Nu], R, W [P, G, N],
+    rew_mean [P])."""
+    lib = load()
+    rewss = np.ascontiguousarray(rewss, np.float32)
+    P, N, H = rewss.shape
+    temps = np.ascontiguousarray(temps, np.float32).reshape(P)
+    cand = np.ascontiguousarray(cand, np.float32).reshape(P, N, H * int(Nu))
+    ybar = np.ascontiguousarray(ybar, np.float32).reshape(P, H * int(Nu))
+    rews = np.ascontiguousarray(rews, np.float32).reshape(P, N)
+    G = int(n_groups)
+    out, R, W = np.zeros((P, H, int(Nu)), np.float32), np.zeros((P, G, N), np.float32), np.zeros((P, G, N), np.float32)
+    mean = np.zeros(P, np.float32)
+    lib.mbd_debug_sweep_togo_step.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _i, _vp, _vp,
+                                              _vp, _vp]
+    check(lib.mbd_debug_sweep_togo_step(P, np_ptr(temps), np_ptr(cand), np_ptr(ybar), np_ptr(rews), np_ptr(rewss), N, H, int(Nu),
+                                        int(block), int(min_tail), int(bool(lazy)), float(sigma), int(bool(std_guard)), float(alpha_i),
+                                        float(alpha_bar_i), float(alpha_bar_im1), int(bool(literal)), np_ptr(out), np_ptr(R), np_ptr(W),
+                                        np_ptr(mean)))
+    return dict(ybar=out, R=R, W=W, rew_mean=mean)
 
 
 def peek_elites(fn, handle, n_elites: int, HNu: int, capacity: int = None) -> dict:

@@ -235,6 +235,52 @@ class Sweep:
         """Plan k's ``temp``, ``ess`` and ``kept`` of every score step of the last run or tick (``Plan.peek_weighting``)."""
         return _capi.peek_weighting(self.lib.mbd_sweep_peek_weighting, self.h, k, self.cfg.Ndiffuse - 1)
 
+    def set_elites(self, n_elites: int, nominal=False, carry=False):
+        """One elite record for all plans of the sweep (``Plan.set_elites``): plan k of ``run``, episode k of ``run_mpc`` and of a
+        session is then the single plan's with the same record, bit for bit, with its own elites, count and log."""
+        rec = _capi.elites_record(n_elites, nominal, carry)
+        _capi.check(self.lib.mbd_sweep_set_elites(self.h, C.byref(rec)))
+        self._elites = int(n_elites)
+
+    def clear_elites(self):
+        _capi.check(self.lib.mbd_sweep_set_elites(self.h, None))
+        self._elites = None
+
+    @property
+    def has_elites(self) -> bool:
+        return getattr(self, "_elites", None) is not None
+
+    def peek_elites(self, k: int, capacity: int = None) -> dict:
+        """Plan k's ``E`` [count, H, Nu], ``R``, ``src``, ``count`` and log (``Plan.peek_elites``)."""
+        fn = lambda h, *a: self.lib.mbd_sweep_peek_elites(h, int(k), *a)  # noqa: E731
+        if not self.has_elites:
+            _capi.check(fn(self.h, None, None, None, None, None, None, None, 0, None))
+        out = _capi.peek_elites(fn, self.h, self._elites or 0, self.H * self.Nu, capacity)
+        out["E"] = out["E"].reshape(-1, self.H, self.Nu)
+        return out
+
+    def set_togo(self, block: int = 1, min_tail: int = 1):
+        """One to-go record for all plans of the sweep (``Plan.set_togo``), each plan under its own temperature, with the same
+        guarantee.  Not beside an objective, value or weighting record."""
+        rec = _capi.togo_record(block, min_tail)
+        _capi.check(self.lib.mbd_sweep_set_togo(self.h, C.byref(rec)))
+        self._togo = (int(block), int(min_tail))
+
+    def clear_togo(self):
+        _capi.check(self.lib.mbd_sweep_set_togo(self.h, None))
+        self._togo = None
+
+    @property
+    def has_togo(self) -> bool:
+        return getattr(self, "_togo", None) is not None
+
+    def peek_togo(self, k: int) -> dict:
+        """Plan k's ``starts`` [G], ``R`` and ``W`` [G, Nsample] of the last step (``Plan.peek_togo``)."""
+        fn = lambda h, *a: self.lib.mbd_sweep_peek_togo(h, int(k), *a)  # noqa: E731
+        if not self.has_togo:
+            _capi.check(fn(self.h, None, None, None, None))
+        return _capi.peek_togo(fn, self.h, self.H, self.cfg.Nsample)
+
     def set_mpc_pick(self, mean=True, prev=True, best=True):
         """One pick record for all episodes of the sweep (``Plan.set_mpc_pick``): episode k of ``run_mpc`` and of a session is
         then the single plan's with the same record, bit for bit; ``run_mpc`` also returns ``pick``, one dict per episode."""

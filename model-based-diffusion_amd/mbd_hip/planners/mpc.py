@@ -106,7 +106,8 @@ Every step draws its candidates afresh and keeps only their weighted mean.  An e
 section 1 "N18 elites") carries candidates over: ``--elites K`` (0 to 32) makes the K best candidates of every diffusion step
 candidates of the next one, ``--elite_nominal`` makes candidate 0 of every step the step's mean itself, noise-free, and
 ``--elite_carry`` shifts the elites across a tick boundary with the mean (otherwise every tick starts without elites).  MBD and mppi
-plans, single episodes; ``--online`` honours it.  The details gain ``elite_log`` = dict(E, R, src, count, log_count, log_kept,
+plans; ``--online`` and ``--n_episodes`` honour it (one record for the batch; every episode has its own elites and log, and the
+report's two fields then hold one list per episode).  The details gain ``elite_log`` = dict(E, R, src, count, log_count, log_kept,
 log_top, steps): the elites behind the episode and the log of its steps; the report ``elites_kept`` and ``elites_top``, per tick the number of
 selected candidates that had been injected (summed over the tick's steps) and the best return of the tick's last step.
 
@@ -117,7 +118,7 @@ credited with rewards of earlier rows it cannot have caused.  A to-go record (in
 to-go") weighs a row by the return still ahead of it, the to-go return of PI^2: ``--togo_block B`` groups the rows B at a time and
 updates each group under weights from the candidates' mean reward from the group's first row onwards; ``--togo_min_tail M`` starts a
 group only where at least M rows are still ahead (the last group takes the rest).  There is no record unless ``--togo_block`` is
-given.  MBD and mppi plans, single episodes; ``--online`` honours it; not beside the objective, value, weighting, adapt or ensemble
+given.  MBD and mppi plans; ``--online`` and ``--n_episodes`` honour it (one record for the batch); not beside the objective, value, weighting, adapt or ensemble
 flags.  The report gains ``togo_groups``, the groups' first rows.
 
     python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --togo_block 5 --togo_min_tail 10
@@ -768,7 +769,8 @@ def run_mpc_online(args: MpcArgs, device: int = None, return_details: bool = Fal
 def _check_batch(arg_list) -> None:
     """What a batch of lockstep episodes takes (the rule of scripts.run_mbd._batchable): up to 32 episodes of one rigid-body
     env with one set of sizes, schedule, (T, K, E) and delay_ticks; seeds, temperatures and the plant settings may differ.
-    Decided from the arguments alone."""
+    Decided from the arguments alone.  The episodes' OWN arguments: an elite or to-go record is the batch's, one for all episodes,
+    and ``_check_batch_records`` takes those flags off the episodes before it asks this function."""
     from dataclasses import asdict
 
     from ..scripts.run_mbd import _resolved
@@ -776,11 +778,11 @@ def _check_batch(arg_list) -> None:
         raise ValueError(f"{len(arg_list)} episodes: a batch holds 1 to {MAX_EPISODES}")
     for k, a in enumerate(arg_list):
         if _has_togo(a):
-            raise ValueError(f"episode {k} carries togo_block={a.togo_block!r}: sweeps take no to-go record; run the episodes one by "
-                             "one (run_mpc)")
+            raise ValueError(f"episode {k} carries togo_block={a.togo_block!r} of its own: a sweep takes one to-go record for all its "
+                             "episodes (_check_batch_records)")
         if _has_elites(a):
-            raise ValueError(f"episode {k} carries elites={a.elites!r} / elite_nominal={a.elite_nominal!r}: sweeps take no elite "
-                             "record; run the episodes one by one (run_mpc)")
+            raise ValueError(f"episode {k} carries elites={a.elites!r} / elite_nominal={a.elite_nominal!r} of its own: a sweep takes "
+                             "one elite record for all its episodes (_check_batch_records)")
         if _has_adapt(a):
             raise ValueError(f"episode {k} carries adapt_rate={a.adapt_rate!r}: sweeps take no adapt record (their samplers take one "
                              "shape for all plans); run the episodes one by one (run_mpc)")
@@ -804,6 +806,25 @@ def _check_batch(arg_list) -> None:
         raise ValueError("enable_demo: demos are time-indexed, an episode has no clock for them: give it one with demo_clip")
     if _has_demo(arg_list[0]) and not ds[0]["enable_demo"]:
         raise ValueError(f"demo_clip={arg_list[0].demo_clip!r} without enable_demo: the plans do not use demos")
+
+
+_BATCH_RECORD_FIELDS = ("elites", "elite_nominal", "elite_carry", "togo_block", "togo_min_tail")
+
+
+def _check_batch_records(arg_list) -> None:
+    """``_check_batch`` for a batch that may carry an elite and a to-go record (mbd_sweep_set_elites, mbd_sweep_set_togo): the five
+    flags are the batch's — equal in every episode, else ValueError naming the field —, ``_check_togo``'s refusals hold, and the
+    episodes without those flags are what ``_check_batch`` takes.  An adapt record stays refused there."""
+    from dataclasses import replace
+    arg_list = list(arg_list)
+    for k, a in enumerate(arg_list):
+        _check_togo(a)
+        for f in _BATCH_RECORD_FIELDS:
+            if getattr(a, f) != getattr(arg_list[0], f):
+                raise ValueError(f"{f} differs between episodes 0 and {k} ({getattr(arg_list[0], f)!r}, {getattr(a, f)!r}): a sweep takes "
+                                 "one elite and one to-go record for all its episodes")
+    none = {f: MpcArgs.__dataclass_fields__[f].default for f in _BATCH_RECORD_FIELDS}
+    _check_batch([replace(a, **none) for a in arg_list])
 
 
 def _setup_batch(arg_list, device: int):
@@ -830,6 +851,10 @@ def _setup_batch(arg_list, device: int):
         sweep.set_mpc_pick(**_pick_of(a0))
     if _has_value(a0):  # (and one value net)
         sweep.set_value(*_value_of(a0))
+    if _has_elites(a0):  # (and one elite record: every episode has its own elites)
+        sweep.set_elites(**_elites_of(a0))
+    if _has_togo(a0):  # (and one to-go record)
+        sweep.set_togo(**_togo_of(a0))
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -852,10 +877,11 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
     Unless the first episode says ``not_render``: results/<env>/mpc_episode.npz, its arrays with a leading episode axis when
     there is more than one episode."""
     arg_list = list(arg_list)
-    _check_batch(arg_list)
+    _check_batch_records(arg_list)
     env, sweep, states, keys = _setup_batch(arg_list, 0 if device is None else device)
     try:
         ep = sweep.run_mpc(keys, arg_list[0].n_ticks, arg_list[0].warm_steps, arg_list[0].exec_steps)
+        _peek_batch_records(sweep, arg_list[0], ep)
     finally:
         sweep.close()
     rewards = [float(r.mean()) for r in ep["rewards"]]
@@ -866,12 +892,21 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
         if _has_basis(arg_list[0]):
             shape = dict(shape, **_basis_settings(arg_list[0]))
         shape = dict(shape, **_delay_settings(arg_list[0]), **_demo_settings(arg_list[0]), **_sigma_settings(arg_list[0]),
-                     **_objective_settings(arg_list[0]), **_weighting_settings(arg_list[0]))
+                     **_objective_settings(arg_list[0]), **_weighting_settings(arg_list[0]), **_elites_settings(arg_list[0]),
+                     **_togo_settings(arg_list[0]))
         windows = {"demo_windows": ep["demo_windows"]} if "demo_windows" in ep else {}  # (one table: every episode's)
-        pick = (lambda k: {"pick": ep["pick"][k]}) if "pick" in ep else (lambda k: {})
+        pick = (lambda k: {f: ep[f][k] for f in ("pick", "elite_log", "togo") if f in ep})
         return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, **windows, **pick(k), seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
                               **_plant_settings(arg_list[k]), **shape) for k in range(len(arg_list))]
     return rewards
+
+
+def _peek_batch_records(sweep, a0: MpcArgs, ep: dict) -> None:
+    """Every episode's elites and step log, and its last step's returns and weights per group, as ``run_mpc`` reports them."""
+    if _has_elites(a0):
+        ep["elite_log"] = [sweep.peek_elites(k) for k in range(sweep.P)]
+    if _has_togo(a0):
+        ep["togo"] = [sweep.peek_togo(k) for k in range(sweep.P)]
 
 
 def _logs(ep: dict) -> tuple:
@@ -941,7 +976,7 @@ def _main(argv=None) -> dict:
         if n_episodes != 1 and _has_sigma(args):  # (the library's own refusal: sessions of path-integral sweeps)
             from dataclasses import replace
             arg_list = [replace(args, seed=args.seed + k) for k in range(n_episodes)]
-            _check_batch(arg_list)
+            _check_batch_records(arg_list)
             _, sweep, _, keys = _setup_batch(arg_list, 0)
             try:
                 sweep.mpc_open(keys, args.warm_steps, args.exec_steps, args.n_ticks).close()
@@ -1059,7 +1094,7 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
     from dataclasses import replace
 
     arg_list = [replace(args, seed=args.seed + k) for k in range(P)]
-    _check_batch(arg_list)
+    _check_batch_records(arg_list)
     with contextlib.redirect_stdout(sys.stderr):  # (stdout carries the JSON line only)
         env, sweep, states, keys = _setup_batch(arg_list, 0)
         a0 = arg_list[0]
@@ -1067,6 +1102,7 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
         sweep.run_mpc(keys, T, K, E)  # warm-up
         _, _, _, open_secs = sweep.run(keys, outputs=False)
         ep = sweep.run_mpc(keys, T, K, E)
+        _peek_batch_records(sweep, a0, ep)
         nominal = None
         if _has_plant(a0):  # what the perturbation cost: the same batch without the records
             for k in range(P):
@@ -1095,6 +1131,10 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
             plan.set_mpc_pick(**_pick_of(a0))
         if _has_value(a0):
             plan.set_value(*_value_of(a0))
+        if _has_elites(a0):
+            plan.set_elites(**_elites_of(a0))
+        if _has_togo(a0):
+            plan.set_togo(**_togo_of(a0))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -1127,6 +1167,11 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
     if "pick" in ep:
         res.update(_pick_settings(a0), pick_log=_pick_log(ep["pick"]))
     res.update(_value_settings(a0))
+    if "elite_log" in ep:  # (per episode)
+        logs = [_elites_log(lg, Nd, K) for lg in ep["elite_log"]]
+        res.update(_elites_settings(a0), elites_kept=[lg["elites_kept"] for lg in logs], elites_top=[lg["elites_top"] for lg in logs])
+    if "togo" in ep:  # (one layout for the batch)
+        res.update(_togo_settings(a0), togo_groups=[int(x) for x in ep["togo"][0]["starts"]])
     if _has_demo(a0):
         res.update(_demo_settings(a0), track_err_mean=float(ep["track_err"].mean()))
     if not a0.not_render:
