@@ -2,7 +2,7 @@
  * session (mbd_plan_mpc_open) is opened once and advanced one tick per call from the state the caller's system is in.
  *
  *   gcc -O2 -I include examples/mbd_control.c -o mbd_control -L model-based-diffusion_amd/lib -lmbd_hip -Wl,-rpath,$PWD/model-based-diffusion_amd/lib -lm
- *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi] [--pick] [--value] [--elites] [--togo]
+ *   ./mbd_control hopper 256 20 10 3 20 [delay_ticks] [--rate_cost L] [--mppi] [--pick] [--value] [--elites] [--togo] [--zones]
  *                 env    N   H  Nd K ticks
  *
  * The "system" here is a second env the example owns, stepped with mbd_env_step — the env's rollout kernel at B = 1, H = 1 through
@@ -39,6 +39,12 @@
  * weights from the candidates' mean reward from the group's first row onwards, no group starting with fewer than five rows ahead;
  * not beside --rate_cost or --value (the library refuses the pair).  The tick's line gains "groups G".
  *
+ * --zones (among the trailing flags): a zone record (mbd_zones) on the env's model retracked to its root link — a keep-out pillar one
+ * metre ahead of the start and a goal on the ground plane that this program moves with the system before every tick
+ * (mbd_plan_update_zones: host state only, allowed while the session is open); rigid-body envs that are not planar (humanoidrun, ant;
+ * not beside --pick or --togo).  The tick's line gains "pen P clear C": the mean penalty of the last step's candidates and the
+ * smallest keep-out clearance among them.
+ *
  * Prints one line per tick: "tick T reward R ms M flags F", then "mean_reward R ms_per_tick M". */
 #include <math.h>
 #include <stdio.h>
@@ -64,14 +70,15 @@ static int plant_step(mbd_env* plant, float* state, const float* action, float* 
 }
 
 int main(int argc, char** argv) {
-  int mppi = 0, pick = 0, value = 0, elites = 0, togo = 0;
+  int mppi = 0, pick = 0, value = 0, elites = 0, togo = 0, zones = 0;
   while (argc > 1 && (strcmp(argv[argc - 1], "--mppi") == 0 || strcmp(argv[argc - 1], "--pick") == 0 ||
                       strcmp(argv[argc - 1], "--value") == 0 || strcmp(argv[argc - 1], "--elites") == 0 ||
-                      strcmp(argv[argc - 1], "--togo") == 0)) { /* trailing flags */
+                      strcmp(argv[argc - 1], "--togo") == 0 || strcmp(argv[argc - 1], "--zones") == 0)) { /* trailing flags */
     if (strcmp(argv[argc - 1], "--mppi") == 0) mppi = 1;
     else if (strcmp(argv[argc - 1], "--pick") == 0) pick = 1;
     else if (strcmp(argv[argc - 1], "--elites") == 0) elites = 1;
     else if (strcmp(argv[argc - 1], "--togo") == 0) togo = 1;
+    else if (strcmp(argv[argc - 1], "--zones") == 0) zones = 1;
     else value = 1;
     argc -= 1;
   }
@@ -85,7 +92,15 @@ int main(int argc, char** argv) {
   const int K = argc > 5 ? atoi(argv[5]) : 3, T = argc > 6 ? atoi(argv[6]) : 20, D = argc > 7 ? atoi(argv[7]) : 0;
   const int impl = MBD_PRNG_PARTITIONABLE, E = 1;
   mbd_env *env = NULL, *plant = NULL;
-  CHECK(mbd_env_create(env_name, 0, &env));   /* the planner's model */
+  if (zones) { /* the planner's model, tracking its root link: the rollouts then return that link's world positions */
+    static mbd_model_t model;
+    CHECK(mbd_builtin_model(env_name, &model));
+    model.n_track = 1;
+    model.track_link[0] = 0;
+    CHECK(mbd_env_create_model(env_name, 0, &model, NULL, 0.0f, &env));
+  } else {
+    CHECK(mbd_env_create(env_name, 0, &env)); /* the planner's model */
+  }
   CHECK(mbd_env_create(env_name, 0, &plant)); /* the system: here a second env, owned by this program */
   int Nu = 0, Nx = 0, S = 0;
   CHECK(mbd_env_info(env, &Nu, &Nx, &S, NULL, NULL, NULL));
@@ -158,6 +173,20 @@ int main(int argc, char** argv) {
     tg.block = 5; tg.min_tail = H < 5 ? H : 5;
     CHECK(mbd_plan_set_togo(plan, &tg));
   }
+  mbd_zones zn;
+  memset(&zn, 0, sizeof(zn));
+  float* zone_pen = zones ? (float*)malloc(sizeof(float) * (size_t)N) : NULL;
+  float* zone_clr = zones ? (float*)malloc(sizeof(float) * (size_t)N) : NULL;
+  if (zones) { /* a pillar to keep out of and a goal on the ground plane, both for track slot 0 (the root link) */
+    zn.n_zones = 2;
+    zn.zone[0].kind = MBD_ZONE_KEEP_OUT; zn.zone[0].links = 1u;
+    zn.zone[0].center[0] = 1.0f; zn.zone[0].scale[0] = 1.0f; zn.zone[0].scale[1] = 1.0f; /* (1, 1, 0): a vertical cylinder */
+    zn.zone[0].radius = 0.3f; zn.zone[0].margin = 0.3f; zn.zone[0].weight = 5.0f;
+    zn.zone[1].kind = MBD_ZONE_GOAL; zn.zone[1].links = 1u;
+    zn.zone[1].center[0] = 2.0f; zn.zone[1].scale[0] = 1.0f; zn.zone[1].scale[1] = 1.0f;
+    zn.zone[1].radius = 0.2f; zn.zone[1].margin = 4.0f; zn.zone[1].weight = 1.0f;
+    CHECK(mbd_plan_set_zones(plan, &zn));
+  }
   if (D > 0) { /* plans arrive D ticks late; the system starts committed to zeros */
     mbd_mpc_delay delay;
     memset(&delay, 0, sizeof(delay));
@@ -180,6 +209,11 @@ int main(int argc, char** argv) {
   double reward_sum = 0.0, seconds = 0.0;
   for (int t = 0; t < T; ++t) {
     mbd_mpc_tick_info info;
+    if (zones) { /* the goal stays two metres ahead of the system, half a metre to its left: moved between two ticks */
+      zn.zone[1].center[0] = state[0] + 2.0f;
+      zn.zone[1].center[1] = state[1] + 0.5f;
+      CHECK(mbd_plan_update_zones(plan, &zn));
+    }
     CHECK(mbd_plan_mpc_tick(plan, state, rows, NULL, head, NULL, &info));
     /* never forward non-finite rows.  The flag speaks of `rows`, the NEW plan: plan afresh from the next state.  What goes to the
      * actuators is `head` — without a delay record the same rows; with one, the queue's head, which rows flagged D ticks ago have
@@ -207,12 +241,24 @@ int main(int argc, char** argv) {
       CHECK(mbd_plan_peek_togo(plan, NULL, NULL, NULL, &groups));
       printf(" groups %d", (int)groups);
     }
+    if (zones) {
+      double pen = 0.0;
+      float clr = INFINITY;
+      CHECK(mbd_plan_peek_zones(plan, zone_pen, zone_clr));
+      for (int n = 0; n < N; ++n) {
+        pen += zone_pen[n];
+        if (!(zone_clr[n] >= clr)) clr = zone_clr[n];
+      }
+      printf(" pen %.6g clear %.6g", pen / N, clr);
+    }
     printf("\n");
     reward_sum += reward;
     seconds += info.seconds;
   }
   printf("mean_reward %.9g ms_per_tick %.3f\n", reward_sum / T, 1e3 * seconds / T);
   CHECK(mbd_plan_mpc_close(plan));
+  free(zone_clr);
+  free(zone_pen);
   free(head);
   free(command);
   free(rows);

@@ -1005,6 +1005,54 @@ int mbd_plan_set_togo(mbd_plan* plan, const mbd_togo* rec);
  * MBD_ERR_INVALID: a NULL handle. */
 int mbd_plan_peek_togo(mbd_plan* plan, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out);
 
+/* ---- zones: keep-out regions and goals for the env's tracked links (the obstacle and goal costs a sampling MPC is usually given; no
+ * counterpart in the reference, whose plans maximise the env's reward alone; DESIGN.md section 1 "N20 zones") ---- */
+/* A zone record is a setting of a plan beside the objective and value records.  The planning rollouts already write the tracked
+ * links' world positions when they are handed a buffer; under a record they are handed one, and ONE launch between the rollout and
+ * the score subtracts a penalty from each candidate's reward.  No rollout kernel, sampler, update kernel or launch choice changes;
+ * without a record every call keeps its launches and its bits. */
+#define MBD_MAX_ZONES 16
+enum { MBD_ZONE_KEEP_OUT = 0, MBD_ZONE_GOAL = 1 };
+typedef struct { int32_t kind; uint32_t links; float center[3]; float scale[3]; float radius, margin, weight; int32_t reserved; } mbd_zone;
+typedef struct { int32_t n_zones; int32_t reserved[3]; mbd_zone zone[MBD_MAX_ZONES]; } mbd_zones;
+/* links: a bit mask over the env's track slots — bit k is slot k, which is link track_link[k].  scale multiplies the three coordinate
+ * differences before the distance is taken: (1,1,1) a sphere, (1,1,0) a vertical cylinder or a point goal on the ground plane,
+ * (1,0,0) a slab.
+ * The contract — f32 throughout, every operation rounded, no contraction.  H = Hsample; x the positions [B][H][n_track][3] of the
+ * launch's rollout.
+ * PENALTY of row b.  For step t, slot k ascending, zone z ascending, where bit k of zone z's links is set:
+ *   e_i = (x_i - c_i) * s_i;  q = (e_0 e_0 + e_1 e_1) + e_2 e_2;  d = sqrt(q)
+ *   keep-out: u = ((r + m) - d) / m        goal: u = (d - r) / m
+ *   v = u < 0 ? 0 : (u > 1 ? 1 : u)  (a NaN stays a NaN);  term = w * (v * v)
+ * s_t starts at +0 and adds the terms with k outer and z inner; pen starts at +0 and adds s_t in ascending t, then one division by
+ * float(H); rews[b] = rews[b] - pen.  Nothing is skipped; a slot/zone pair outside the mask contributes no operation at all.
+ * CLEARANCE.  clr_t is the minimum of d - r over the step's keep-out terms, +inf where there are none; clr the minimum of clr_t over
+ * t.  A NaN wins and is stored as the canonical quiet NaN 0x7fc00000, so the order of the minimum cannot show.
+ * WHERE.  The launch runs behind the objective's and in front of the value's: elite selection, weighting, adapt and every update
+ * rule read the rews it wrote; rewss is not touched.  All four update methods, lazy and materialised candidates; mbd_plan_run, the
+ * phase calls, mbd_plan_reverse_once, mbd_plan_run_mpc and sessions.
+ * The set call is synchronous and is to be called between diffusion steps; rec == NULL clears.  Refused before any device access,
+ * the message naming the field or the record — MBD_ERR_INVALID: a NULL handle; n_zones outside [1, MBD_MAX_ZONES]; a kind other
+ * than 0 or 1; links zero or with a bit at or above n_track; a non-finite center; a scale entry non-finite or negative, or all three
+ * zero; radius non-finite or negative; margin non-finite or not positive; weight non-finite or negative; non-zero reserved.
+ * MBD_ERR_UNSUPPORTED: car2d; an env whose model tracks no link (compile planar models planar=False with track_names); a plan created
+ * with enable_demo; a plan holding an ensemble, to-go or pick record — their set calls refuse a plan holding a zone record in turn.
+ * MBD_ERR_STATE: a sharded plan; a session open on the handle.  At the run call of an episode, MBD_ERR_INVALID: a plant env whose
+ * tracked links differ from the plan's (the demo record's rule). */
+int mbd_plan_set_zones(mbd_plan* plan, const mbd_zones* rec);
+/* Replaces the table of a plan that already holds a record: how a caller moves a goal or an obstacle between ticks.  Host state only
+ * (the table travels as kernel arguments), so it is allowed while a session is open.  The record's own refusals as above;
+ * MBD_ERR_STATE: a plan without a record, a session's tick in flight (collect it first). */
+int mbd_plan_update_zones(mbd_plan* plan, const mbd_zones* rec);
+/* the last step's pen and clr per candidate (HOST [Nsample] each, either may be NULL; synchronises the device).  MBD_ERR_STATE
+ * without a record, or before a step has run with one. */
+int mbd_plan_peek_zones(mbd_plan* plan, float* pen_out, float* clear_out);
+/* An episode of mbd_plan_run_mpc under a record also logs, for every executed control step, s_t of the contract (its penalty before
+ * the division by H) and clr_t, taken from the positions the executed rows' rollout wrote: HOST pen_out, clear_out [T * exec_steps],
+ * either may be NULL.  The logged rewards stay the env's.  MBD_ERR_STATE without a record, or before an episode has run with one
+ * (a session logs nothing executed: the caller owns the system). */
+int mbd_plan_peek_mpc_zones(mbd_plan* plan, float* pen_out, float* clear_out);
+
 /* ---- planning ahead of the plant: an episode whose plans take D ticks to arrive (the real-time iteration scheme; no
  * counterpart in the reference; DESIGN.md section 1 "N9 delay") ---- */
 /* The episode of mbd_plan_run_mpc plans from s_t and executes that plan's first rows from the same s_t: planning takes no time.
@@ -1267,6 +1315,18 @@ int mbd_sweep_set_mpc_pick(mbd_sweep* sweep, const mbd_mpc_pick* rec);
  * and of a sweep's session is then the single plan's with the same record, bit for bit, whatever the other plans do.  One launch over
  * the n_plans * Nsample rows per step.  Refusals as mbd_plan_set_value's (sweeps take no ensemble). */
 int mbd_sweep_set_value(mbd_sweep* sweep, const mbd_value* rec);
+/* one zone record (mbd_zones, above) for all plans of the sweep — one table: plan k of mbd_sweep_run, episode k of mbd_sweep_run_mpc
+ * and of a sweep's session is then the single plan's with the same record, bit for bit.  One launch over the n_plans * Nsample rows
+ * per step, behind the objective's.  Refusals as mbd_plan_set_zones' on the sweep's config (sweeps take no ensemble and are never
+ * sharded); MBD_ERR_UNSUPPORTED beside the sweep's to-go or pick record, whose set calls refuse a sweep with a zone record in turn. */
+int mbd_sweep_set_zones(mbd_sweep* sweep, const mbd_zones* rec);
+/* as mbd_plan_update_zones: the table of a sweep that already holds a record, allowed while a session is open but not while a tick
+ * is in flight */
+int mbd_sweep_update_zones(mbd_sweep* sweep, const mbd_zones* rec);
+/* plan k's pen and clr of the last step, as mbd_plan_peek_zones; k outside [0, n_plans) -> MBD_ERR_INVALID */
+int mbd_sweep_peek_zones(mbd_sweep* sweep, int k, float* pen_out, float* clear_out);
+/* episode k's log of the last mbd_sweep_run_mpc, as mbd_plan_peek_mpc_zones; k outside [0, n_plans) -> MBD_ERR_INVALID */
+int mbd_sweep_peek_mpc_zones(mbd_sweep* sweep, int k, float* pen_out, float* clear_out);
 /* episode k's log; as mbd_plan_peek_mpc_pick; k outside [0, n_plans) -> MBD_ERR_INVALID */
 int mbd_sweep_peek_mpc_pick(mbd_sweep* sweep, int k, int32_t* choice_out, float* rets_out, int32_t* best_out, int capacity,
                             int* count_out);

@@ -158,6 +158,19 @@ int mbd_debug_togo_host(const float* rews, const float* rewss, int N, int H, int
 int mbd_debug_togo_step(const float* cand, const float* ybar, const float* rews, const float* rewss, int N, int H, int Nu, int block,
                         int min_tail, int lazy, float sigma, float temp, int std_guard, float alpha_i, float alpha_bar_i,
                         float alpha_bar_im1, int literal, float* ybar_out, float* R_out, float* W_out, float* rew_mean_out);
+/* The refusals a zone record alone decides (include/mbd_hip.h mbd_zones) for an env of that n_track: the function the set call runs on
+ * its record, host arithmetic, no device. */
+int mbd_debug_check_zones(const mbd_zones* rec, int n_track);
+/* A zone record's launch on the HOST: the functions the kernel calls (one text for host and device) looped over B rows of H steps
+ * and K tracks on the CPU in the kernel's order; no device touched.  HOST xpos [B][H][K][3], rews [B] (may be NULL when rews_out is).
+ * rews_out, pen_out, clr_out [B], step_pen_out, step_clr_out [B][H]; any output may be NULL.  The record is checked as the set call
+ * checks it against n_track = K; 1 <= K <= MBD_MAX_TRACK, B * H * K <= 2^26. */
+int mbd_debug_zones_host(const mbd_zones* rec, const float* xpos, const float* rews, int B, int H, int K, float* rews_out,
+                         float* pen_out, float* clr_out, float* step_pen_out, float* step_clr_out);
+/* zones_kernel alone on the DEVICE, on the same arguments.  What is read back is filled with all-ones bits first.  Argument errors
+ * first, then MBD_ERR_NO_DEVICE. */
+int mbd_debug_zones_step(const mbd_zones* rec, const float* xpos, const float* rews, int B, int H, int K, float* rews_out,
+                         float* pen_out, float* clr_out, float* step_pen_out, float* step_clr_out);
 /* An elite record's two batch launches alone on the DEVICE for P plans at once, on caller-given HOST arrays, keeping no sweep state:
  * elite_inject_batch_kernel, then elite_select_batch_kernel.  mask: bit k set = plan k takes part; a plan left out is neither read
  * nor written.  rews [P][N], cand [P][N][HNu] (values, or with lazy != 0 normals), ybar [P][HNu], g [HNu] or NULL, E_in

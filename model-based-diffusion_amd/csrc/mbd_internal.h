@@ -509,6 +509,46 @@ struct ValueRec {
   int eval(const mbd_env* env, const float* states, int B, float* v_out, const char* what);
 };
 int check_value(const mbd_value* rec, int state_size, bool rigid_body);
+// The zone record of a plan or a sweep (include/mbd_hip.h mbd_zones) as the handle keeps it, with what the two handles do alike.
+// check_zones: the refusals the record alone decides against the env's n_track, in the header's order, each naming the field — host
+// arithmetic, before any device access.  set: behind the handle's NULL, session, env, demo, shard and record checks and check_zones
+// (nullptr clears); makes room for the positions, pen and clr of max_rows rows of H steps and K tracks.  update: the table alone —
+// host state, since the table travels as kernel arguments.  xpos(): what a planning rollout is handed as d_xpos — nullptr without
+// a record, so that a launch without one is what it was.  launch: the kernel over B rows of d_x (defined in mbd_plan.hip, which alone
+// compiles it); launch_step: the same over the step's own buffers, what peek shows.  An episode logs its executed steps: start makes
+// room for the positions [T P E][K][3] and the log [T P E] twice, log runs the kernel over one tick's executed rows of all P episodes.
+struct ZoneRec {
+  bool has = false, stepped = false;
+  mbd_zones tab{};
+  int K = 0, H = 0, rows = 0;
+  int ticks = 0, exec = 0, episodes = 0;
+  DevBuf<float> d_x, d_pen, d_clr, d_xlog, d_log_pen, d_log_clr;
+  int set(const mbd_zones* rec, const mbd_env* env, size_t max_rows, int H_);
+  int update(const mbd_zones* rec, const mbd_env* env, const char* what);
+  float* xpos() const { return has ? d_x.get() : nullptr; }
+  int launch(const float* d_xp, float* d_rews, int B, int H_, float* d_pen_keep, float* d_clr_keep, float* d_step_pen,
+             float* d_step_clr, hipStream_t s) const;
+  int launch_step(float* d_rews, int B, hipStream_t s) {
+    if (!has) return MBD_OK;
+    rows = B;
+    stepped = true;
+    return launch(d_x, d_rews, B, H, d_pen, d_clr, nullptr, nullptr, s);
+  }
+  // the plant env of an episode with the record: the positions it writes must be the tracked links' of the planning env
+  int check_plant(const mbd_env* env, const mbd_env* plant) const;
+  int start(int T, int P, int E);
+  float* xlog(int t, int P, int E, int k = 0) const { return has ? d_xlog.get() + ((size_t)t * P + k) * E * K * 3 : nullptr; }
+  // behind the rollout of tick t's executed rows: s_t and clr_t of the P E steps into the log, ONE launch
+  int log(int t, int P, int E, hipStream_t s) const;
+  int peek(const mbd_env* env, int k, int N, float* pen_out, float* clr_out, const char* what) const;
+  // HOST pen_out, clr_out [T E] of episode k of the last run
+  int peek_mpc(const mbd_env* env, int k, float* pen_out, float* clr_out, const char* what) const;
+};
+int check_zones(const mbd_zones* rec, int n_track);
+// the refusals of a zone record the handle's env and config decide, behind check_zones (handle: "plan" / "sweep"); and the refusal of
+// a record beside a zone record (mbd_plan.hip; who: how the refused record's messages begin)
+int check_zones_handle(const mbd_env* env, const mbd_plan_config& c, const char* handle);
+int refuse_beside_zones(const char* who, const char* handle = "plan");
 // The weighting record of a plan or a sweep (include/mbd_hip.h mbd_weighting) as the handle keeps it.  check_weighting: the refusals
 // the record alone decides, in the header's order, each naming the field, before any device access.  set: behind the handle's NULL,
 // session and enable_demo checks (nullptr clears); makes room for the log — three arrays [P][cap], cap = Ndiffuse - 1 entries per

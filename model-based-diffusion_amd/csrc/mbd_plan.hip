@@ -8,6 +8,7 @@
 #define MBD_ADAPT_KERNEL 1  // ... and the adapt record's (plans only)
 #define MBD_ELITE_KERNEL 1  // ... and the elite record's (plans only)
 #define MBD_TOGO_KERNEL 1   // ... and the to-go record's (plans only)
+#define MBD_ZONE_KERNEL 1   // ... and, for plans and sweeps alike, the zone record's
 #include "mbd_internal.h"
 #include "../../include/mbd_hip_debug.h"
 
@@ -282,6 +283,8 @@ struct mbd_plan {
   PickRec pick;
   // the value record (mbd_plan_set_value) with its net, the shard's final states and the last step's V
   ValueRec val;
+  // the zone record (mbd_plan_set_zones) with its table, the step's tracked positions and the last step's pen and clr
+  ZoneRec zone;
   // the adapt record (mbd_plan_set_adapt) with its table, the shape the samplers draw under and the device log of its steps
   AdaptRec adapt;
   // the elite record (mbd_plan_set_elites) with the elites, their count on the device and the device log of its steps
@@ -776,8 +779,8 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
     p->ens_stepped = true;
   } else {
     MBD_TRY(launch_rollout(e, d_state0, d_cand + (size_t)c.shard_begin * HNu, c.shard_count, H, p->d_rewss, d_rews_local,
-                           (c.enable_demo && !fused_lp) ? p->d_xpos.get() : nullptr, p->val.final(), s, p->lazy ? &lz : nullptr,
-                           nullptr, fused_lp ? d_logpd_local : nullptr, nullptr, d_xref));
+                           (c.enable_demo && !fused_lp) ? p->d_xpos.get() : p->zone.xpos(), p->val.final(), s,
+                           p->lazy ? &lz : nullptr, nullptr, fused_lp ? d_logpd_local : nullptr, nullptr, d_xref));
   }
   MBD_TRY(p->timing.end(s));
   // The objective record: ONE launch between the rollout and the score rewrites the shard's rewards in place (a path-integral plan
@@ -786,7 +789,10 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
   // mean is already marked as the buffer's last reader.
   if (p->obj.has && !p->has_ens)
     MBD_TRY(p->obj.launch(p->d_rewss, d_rews_local, c.shard_count, c.shard_begin, d_cand, p->lazy, p->sigmas[i], d_Ybar_i, -1, s));
-  // The value record: ONE launch behind the objective's adds scale * V of the shard's final states, which the rollout above wrote
+  // The zone record: ONE launch behind the objective's subtracts the penalty of the tracked positions the rollout above wrote
+  // (never under an ensemble, a demo or a shard: the set calls refuse them)
+  MBD_TRY(p->zone.launch_step(d_rews_local, c.shard_count, s));
+  // The value record: ONE launch behind the zones' adds scale * V of the shard's final states, which the rollout above wrote
   // (never under an ensemble: the set calls refuse the pair)
   MBD_TRY(p->val.launch_step(d_rews_local, c.shard_count, s));
   MBD_TRY(finish_noise_job(p, lz, marked));
@@ -1590,6 +1596,7 @@ extern "C" int mbd_plan_set_ensemble(mbd_plan* p, const mbd_ensemble* rec) {
     p->ens_rec = mbd_ensemble{};
     return MBD_OK;
   }
+  if (p->zone.has) return refuse_beside_zones("ensemble");
   if (p->togo.has) return refuse_beside_togo("ensemble");  // (before check_ensemble, which may read the members' reference from the device)
   MBD_TRY(check_ensemble(p, rec));
   if (p->pick.has)
@@ -1985,6 +1992,229 @@ extern "C" int mbd_plan_eval_value(mbd_plan* p, const float* states, int B, floa
   return p->val.eval(p->env, states, B, v_out, "plan");
 }
 
+// ---- the zone record (include/mbd_hip.h mbd_zones) ----------------------------------------------------------------------------
+int check_zones(const mbd_zones* rec, int n_track) {
+  if (rec->n_zones < 1 || rec->n_zones > MBD_MAX_ZONES)
+    return fail(MBD_ERR_INVALID, "zones: n_zones=%d: must lie in 1..%d", rec->n_zones, MBD_MAX_ZONES);
+  for (int r = 0; r < 3; ++r)
+    if (rec->reserved[r] != 0) return fail(MBD_ERR_INVALID, "zones: reserved[%d]=%d: must be 0", r, rec->reserved[r]);
+  for (int z = 0; z < rec->n_zones; ++z) {
+    const mbd_zone& zn = rec->zone[z];
+    if (zn.kind != MBD_ZONE_KEEP_OUT && zn.kind != MBD_ZONE_GOAL)
+      return fail(MBD_ERR_INVALID, "zones: zone[%d].kind=%d: KEEP_OUT (0) or GOAL (1)", z, zn.kind);
+    if (zn.links == 0u) return fail(MBD_ERR_INVALID, "zones: zone[%d].links=0: at least one track slot", z);
+    if (n_track < 32 && (zn.links >> n_track) != 0u)
+      return fail(MBD_ERR_INVALID, "zones: zone[%d].links=0x%x: a bit at or above the env's n_track=%d", z, zn.links, n_track);
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(zn.center[i]))
+        return fail(MBD_ERR_INVALID, "zones: zone[%d].center[%d]=%g: must be finite", z, i, (double)zn.center[i]);
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(zn.scale[i]) || zn.scale[i] < 0.0f)
+        return fail(MBD_ERR_INVALID, "zones: zone[%d].scale[%d]=%g: must be finite and >= 0", z, i, (double)zn.scale[i]);
+    if (zn.scale[0] == 0.0f && zn.scale[1] == 0.0f && zn.scale[2] == 0.0f)
+      return fail(MBD_ERR_INVALID, "zones: zone[%d].scale: all three entries are 0", z);
+    if (!std::isfinite(zn.radius) || zn.radius < 0.0f)
+      return fail(MBD_ERR_INVALID, "zones: zone[%d].radius=%g: must be finite and >= 0", z, (double)zn.radius);
+    if (!std::isfinite(zn.margin) || !(zn.margin > 0.0f))
+      return fail(MBD_ERR_INVALID, "zones: zone[%d].margin=%g: must be finite and > 0", z, (double)zn.margin);
+    if (!std::isfinite(zn.weight) || zn.weight < 0.0f)
+      return fail(MBD_ERR_INVALID, "zones: zone[%d].weight=%g: must be finite and >= 0", z, (double)zn.weight);
+    if (zn.reserved != 0) return fail(MBD_ERR_INVALID, "zones: zone[%d].reserved=%d: must be 0", z, zn.reserved);
+  }
+  return MBD_OK;
+}
+extern "C" int mbd_debug_check_zones(const mbd_zones* rec, int n_track) {
+  if (!rec) return fail(MBD_ERR_INVALID, "zone record is NULL");
+  if (n_track < 0 || n_track > MBD_MAX_TRACK) return fail(MBD_ERR_INVALID, "check_zones: n_track=%d outside [0, %d]", n_track, MBD_MAX_TRACK);
+  return check_zones(rec, n_track);
+}
+static int check_zones_args(const char* what, const mbd_zones* rec, const float* xpos, int B, int H, int K) {
+  if (!rec || !xpos) return fail(MBD_ERR_INVALID, "%s: NULL argument", what);
+  if (B < 1 || H < 1 || K < 1 || K > MBD_MAX_TRACK || (long long)B * H * K > (1ll << 26))
+    return fail(MBD_ERR_INVALID, "%s: B=%d H=%d K=%d (K <= %d, B H K <= 2^26)", what, B, H, K, MBD_MAX_TRACK);
+  return check_zones(rec, K);
+}
+// include/mbd_hip_debug.h: zones_kernel's functions on the host (one text for host and device), row by row in the kernel's order —
+// no device is touched
+extern "C" int mbd_debug_zones_host(const mbd_zones* rec, const float* xpos, const float* rews, int B, int H, int K, float* rews_out,
+                                    float* pen_out, float* clr_out, float* step_pen_out, float* step_clr_out) {
+  MBD_TRY(check_zones_args("zones_host", rec, xpos, B, H, K));
+  if (rews_out && !rews) return fail(MBD_ERR_INVALID, "zones_host: rews_out needs rews");
+  for (int b = 0; b < B; ++b) {
+    float pen = 0.0f, clr = __builtin_inff();
+    for (int t = 0; t < H; ++t) {
+      const size_t at = (size_t)b * H + t;
+      float s_t, c_t;
+      zone_step(xpos + at * K * 3, K, *rec, s_t, c_t);
+      if (step_pen_out) step_pen_out[at] = s_t;
+      if (step_clr_out) step_clr_out[at] = zone_canon(c_t);
+      pen = pen + s_t;
+      clr = zone_min(clr, c_t);
+    }
+    pen = pen / (float)H;
+    if (pen_out) pen_out[b] = pen;
+    if (clr_out) clr_out[b] = zone_canon(clr);
+    if (rews_out) rews_out[b] = rews[b] - pen;
+  }
+  return MBD_OK;
+}
+
+int ZoneRec::launch(const float* d_xp, float* d_rews, int B, int H_, float* d_pen_keep, float* d_clr_keep, float* d_step_pen,
+                    float* d_step_clr, hipStream_t s) const {
+  ZoneArgs A;
+  A.xpos = d_xp; A.rews = d_rews; A.pen_keep = d_pen_keep; A.clr_keep = d_clr_keep; A.step_pen = d_step_pen; A.step_clr = d_step_clr;
+  A.B = B; A.H = H_; A.K = K;
+  A.Z = tab;
+  hipLaunchKernelGGL(zones_kernel, dim3((unsigned)((B + kZoneRows - 1) / kZoneRows)), dim3(64 * kZoneRows), 0, s, A);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+// include/mbd_hip_debug.h: the kernel alone on the same arguments; what is read back is filled with all-ones bits first
+extern "C" int mbd_debug_zones_step(const mbd_zones* rec, const float* xpos, const float* rews, int B, int H, int K, float* rews_out,
+                                    float* pen_out, float* clr_out, float* step_pen_out, float* step_clr_out) {
+  MBD_TRY(check_zones_args("zones_step", rec, xpos, B, H, K));
+  if (rews_out && !rews) return fail(MBD_ERR_INVALID, "zones_step: rews_out needs rews");
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "zones_step: no gfx950 device visible (there is no CPU fallback)");
+  ZoneRec zr;
+  zr.tab = *rec;
+  zr.K = K;
+  DevBuf<float> d_x, d_rews, d_pen, d_clr, d_sp, d_sc;
+  const size_t BH = (size_t)B * H;
+  HIP_TRY(d_x.upload(xpos, BH * K * 3));
+  if (rews) HIP_TRY(d_rews.upload(rews, B));
+  HIP_TRY(d_pen.alloc_poisoned(B));
+  HIP_TRY(d_clr.alloc_poisoned(B));
+  HIP_TRY(d_sp.alloc_poisoned(BH));
+  HIP_TRY(d_sc.alloc_poisoned(BH));
+  MBD_TRY(zr.launch(d_x, rews ? d_rews.get() : nullptr, B, H, d_pen, d_clr, d_sp, d_sc, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  if (rews) HIP_TRY(d_rews.download(rews_out, B));
+  HIP_TRY(d_pen.download(pen_out, B));
+  HIP_TRY(d_clr.download(clr_out, B));
+  HIP_TRY(d_sp.download(step_pen_out, BH));
+  HIP_TRY(d_sc.download(step_clr_out, BH));
+  return MBD_OK;
+}
+
+int ZoneRec::set(const mbd_zones* rec, const mbd_env* env, size_t max_rows, int H_) {
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still write the previous record's buffers)
+  has = false;
+  stepped = false;
+  ticks = exec = episodes = 0;
+  if (!rec) return MBD_OK;
+  K = env->model.n_track;
+  H = H_;
+  HIP_TRY(d_x.grow(max_rows * H * K * 3));
+  HIP_TRY(d_pen.grow(max_rows));
+  HIP_TRY(d_clr.grow(max_rows));
+  tab = *rec;
+  has = true;
+  return MBD_OK;
+}
+
+int ZoneRec::update(const mbd_zones* rec, const mbd_env* env, const char* what) {
+  if (!rec) return fail(MBD_ERR_INVALID, "update_zones: zone record is NULL");
+  if (!has) return fail(MBD_ERR_STATE, "update_zones: the %s has no zone record (mbd_%s_set_zones first)", what, what);
+  MBD_TRY(check_zones(rec, env->model.n_track));
+  tab = *rec;  // (launches already enqueued carry the table they were launched with)
+  return MBD_OK;
+}
+
+int ZoneRec::check_plant(const mbd_env* env, const mbd_env* plant) const {
+  if (!has || plant == env) return MBD_OK;
+  if (plant->model.n_track != env->model.n_track)
+    return fail(MBD_ERR_INVALID, "zone record: the plant's n_track=%d, the planning env's is %d", plant->model.n_track, env->model.n_track);
+  for (int k = 0; k < env->model.n_track; ++k)
+    if (plant->model.track_link[k] != env->model.track_link[k])
+      return fail(MBD_ERR_INVALID, "zone record: the plant's track_link[%d]=%d, the planning env's is %d", k,
+                  plant->model.track_link[k], env->model.track_link[k]);
+  return MBD_OK;
+}
+
+int ZoneRec::start(int T, int P, int E) {
+  ticks = exec = episodes = 0;
+  if (!has) return MBD_OK;
+  const size_t steps = (size_t)T * P * E;
+  HIP_TRY(d_xlog.grow(steps * K * 3));
+  HIP_TRY(d_log_pen.grow(steps));
+  HIP_TRY(d_log_clr.grow(steps));
+  return MBD_OK;
+}
+
+int ZoneRec::log(int t, int P, int E, hipStream_t s) const {
+  if (!has) return MBD_OK;
+  const size_t at = (size_t)t * P * E;
+  return launch(xlog(t, P, E), nullptr, P, E, nullptr, nullptr, d_log_pen.get() + at, d_log_clr.get() + at, s);
+}
+
+int ZoneRec::peek(const mbd_env* env, int k, int N, float* pen_out, float* clr_out, const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_zones: the %s has no zone record", what);
+  if (!stepped) return fail(MBD_ERR_STATE, "peek_zones: no diffusion step with the record to show yet");
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (pen_out) HIP_TRY(hipMemcpy(pen_out, d_pen.get() + (size_t)k * N, sizeof(float) * N, hipMemcpyDeviceToHost));
+  if (clr_out) HIP_TRY(hipMemcpy(clr_out, d_clr.get() + (size_t)k * N, sizeof(float) * N, hipMemcpyDeviceToHost));
+  return MBD_OK;
+}
+
+int ZoneRec::peek_mpc(const mbd_env* env, int k, float* pen_out, float* clr_out, const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_mpc_zones: the %s has no zone record", what);
+  if (!ticks) return fail(MBD_ERR_STATE, "peek_mpc_zones: no episode has run with the record yet");
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  for (int t = 0; t < ticks; ++t) {  // the log is tick-major [T][P][E]
+    const size_t at = ((size_t)t * episodes + k) * exec;
+    if (pen_out) HIP_TRY(hipMemcpy(pen_out + (size_t)t * exec, d_log_pen.get() + at, sizeof(float) * exec, hipMemcpyDeviceToHost));
+    if (clr_out) HIP_TRY(hipMemcpy(clr_out + (size_t)t * exec, d_log_clr.get() + at, sizeof(float) * exec, hipMemcpyDeviceToHost));
+  }
+  return MBD_OK;
+}
+
+// the refusals of a zone record a handle's env and config decide (plans and sweeps alike), behind check_zones
+int check_zones_handle(const mbd_env* env, const mbd_plan_config& c, const char* handle) {
+  if (env && env->kind == ENV_CAR2D) return fail(MBD_ERR_UNSUPPORTED, "zone record: car2d has no tracked links");
+  if (!env || env->model.n_track < 1)
+    return fail(MBD_ERR_UNSUPPORTED, "zone record: the env's model tracks no link (n_track=0): compile planar models planar=False with "
+                                     "track_names");
+  if (c.enable_demo) return fail(MBD_ERR_UNSUPPORTED, "zone record: the %s was created with enable_demo: demo plans are out of scope", handle);
+  return MBD_OK;
+}
+int refuse_beside_zones(const char* who, const char* handle) {
+  return fail(MBD_ERR_UNSUPPORTED, "%s: the %s carries a zone record (mbd_%s_set_zones): the pair is out of scope", who, handle, handle);
+}
+
+extern "C" int mbd_plan_set_zones(mbd_plan* p, const mbd_zones* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (rec) {  // (before any device access)
+    const int n_track = p->env && p->env->kind == ENV_MODEL ? p->env->model.n_track : 0;
+    MBD_TRY(check_zones(rec, n_track > 0 ? n_track : 32));  // (an env without tracks: the other fields first, then its own refusal)
+    MBD_TRY(check_zones_handle(p->env, p->cfg, "plan"));
+    if (p->has_ens) return fail(MBD_ERR_UNSUPPORTED, "zone record: the plan carries an ensemble record (an ensemble launch returns rewards only)");
+    if (p->togo.has) return refuse_beside_togo("zone record");
+    if (p->pick.has) return fail(MBD_ERR_UNSUPPORTED, "zone record: the plan carries a pick record (its slots' rollouts write no positions)");
+    if (p->cfg.shard_count != p->cfg.Nsample) return refuse_sharded(p->cfg, "zone");
+  }
+  NO_SESSION(p, "set_zones");
+  return p->zone.set(rec, p->env, (size_t)p->cfg.shard_count, p->cfg.Hsample);
+}
+
+extern "C" int mbd_plan_update_zones(mbd_plan* p, const mbd_zones* rec) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  if (p->session.in_flight) return fail(MBD_ERR_STATE, "update_zones: a tick is in flight (mbd_plan_mpc_collect first)");
+  return p->zone.update(rec, p->env, "plan");
+}
+
+extern "C" int mbd_plan_peek_zones(mbd_plan* p, float* pen_out, float* clear_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->zone.peek(p->env, 0, p->zone.rows, pen_out, clear_out, "plan");
+}
+
+extern "C" int mbd_plan_peek_mpc_zones(mbd_plan* p, float* pen_out, float* clear_out) {
+  if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
+  return p->zone.peek_mpc(p->env, 0, pen_out, clear_out, "plan");
+}
+
 // ---- the weighting record (include/mbd_hip.h mbd_weighting) --------------------------------------------------------------
 int check_weighting(const mbd_weighting* rec) {
   for (int r = 0; r < 6; ++r)
@@ -2248,6 +2478,7 @@ extern "C" int mbd_plan_set_mpc_pick(mbd_plan* p, const mbd_mpc_pick* rec) {
     return fail(MBD_ERR_UNSUPPORTED, "mpc pick record: enable_demo=1: a demo plan's score is not the return the pick compares");
   if (rec && p->has_ens)
     return fail(MBD_ERR_UNSUPPORTED, "mpc pick record: the plan carries an ensemble record: its reward is a reduction over members");
+  if (rec && p->zone.has) return refuse_beside_zones("mpc pick record");
   return p->pick.set(rec, p->env->device, 1, p->HNu, p->cfg.Hsample);
 }
 
@@ -2686,6 +2917,7 @@ extern "C" int mbd_plan_set_togo(mbd_plan* p, const mbd_togo* rec) {
     if (other)
       return fail(MBD_ERR_UNSUPPORTED, "to-go record: the plan carries %s record: what that record means per horizon row is not defined",
                   other);
+    if (p->zone.has) return refuse_beside_zones("to-go record");
     if (p->cfg.shard_count != p->cfg.Nsample) return refuse_sharded(p->cfg, "to-go");
   }
   NO_SESSION(p, "set_togo");
@@ -2911,6 +3143,9 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   // with a demo record (only a demo plan carries one): the table of the ticks' windows, one launch, and the position log
   const bool has_demo = p->demo.has;
   MBD_TRY(p->demo.check_plant(e, pe));
+  // with a zone record: the same rule for the plant, and room for the log of the executed steps
+  MBD_TRY(p->zone.check_plant(e, pe));
+  MBD_TRY(p->zone.start(T, 1, E));
   const int planar = e->kind == ENV_MODEL && (e->model.flags & MBD_FLAG_PLANAR) ? 1 : 0;
   uint32_t dk[2] = {pr.key[0], pr.key[1]};  // the disturbance key chain: dk, d_t = split(dk) per tick
   const float* s_t = p->d_state0;  // where tick t's rollouts start: s_0 in the plan's own buffer, then the ping-pong buffers
@@ -2972,8 +3207,11 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
       rows = exec_rows;
     }
     // (with a demo record the launch also writes the tracked positions of its E steps into their log: same rewards, same state)
-    MBD_TRY(launch_rollout(pe, s_t, rows, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr, has_demo ? p->demo.xlog(t, 1, E) : nullptr,
-                           s_next, s));
+    // (and with a zone record — never beside a demo record, which only demo plans carry)
+    MBD_TRY(launch_rollout(pe, s_t, rows, 1, E, p->d_mpc_rewards + (size_t)t * E, nullptr,
+                           has_demo ? p->demo.xlog(t, 1, E) : p->zone.xlog(t, 1, E), s_next, s));
+    // with a zone record: s_t and clr_t of the E executed steps into the episode's log, ONE launch over that single row
+    MBD_TRY(p->zone.log(t, 1, E, s));
     float* const exec_log = has_plant ? nullptr : p->d_mpc_actions + (size_t)t * EN;  // (a plant's rows kernel has logged them)
     if (has_delay && kick_now)
       hipLaunchKernelGGL(mpc_boundary_delay_kick_kernel, dim3(1), dim3(256), 0, s, cur, HNu, EN, s_next, S,
@@ -3002,6 +3240,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   HIP_TRY(p->d_mpc_rewards.download(rewards_out, (size_t)T * E));
   HIP_TRY(p->d_mpc_states.download(states_out, ((size_t)T + 1) * S));
   if (has_delay) p->delay.pred_ticks = T;
+  if (p->zone.has) { p->zone.ticks = T; p->zone.exec = E; p->zone.episodes = 1; }
   if (pi) { p->sigma_rec.ticks = T; p->sigma_rec.episodes = 1; }
   if (has_plant || has_delay) {  // (the executed rows carry the action noise, or are the committed queue's: their own log)
     HIP_TRY(p->d_mpc_actions.download(actions_out, (size_t)T * EN));

@@ -2379,4 +2379,94 @@ static __global__ __launch_bounds__(kWmE * kWmG, 4) void togo_update_batch_kerne
 #endif  // MBD_SWEEP_KERNEL
 #endif  // MBD_TOGO_KERNEL
 
+// ---- the zone record (mbd_plan_set_zones, include/mbd_hip.h mbd_zones; DESIGN.md section 1 "N20 zones"): behind a rollout launch
+// that wrote the tracked links' positions (and behind the objective's launch), rews[b] = rews[b] - pen[b].  Last in this header under
+// its own guard, for weigh_kernel's reason: only mbd_plan.hip, which launches it for plans and sweeps alike, emits it ----
+// The arithmetic of one term and one step is the functions below, host and device text: mbd_debug_zones_host loops them on the CPU,
+// where a test without a device holds them to the checker.  f32, every operation rounded (the build's -ffp-contract=off).
+MBD_HD float zone_dist(const float* __restrict__ x, const mbd_zone& z) {
+  const float e0 = (x[0] - z.center[0]) * z.scale[0];
+  const float e1 = (x[1] - z.center[1]) * z.scale[1];
+  const float e2 = (x[2] - z.center[2]) * z.scale[2];
+  return fsqrt((e0 * e0 + e1 * e1) + e2 * e2);
+}
+MBD_HD float zone_u(int kind, float d, float r, float m) { return kind == MBD_ZONE_GOAL ? (d - r) / m : ((r + m) - d) / m; }
+MBD_HD float zone_term(float w, float u) {
+  const float v = fclip_nan(u, 0.0f, 1.0f);
+  return w * (v * v);
+}
+// the minimum in which a NaN wins whichever side it stands on; zone_canon: the one NaN that is stored
+MBD_HD float zone_min(float a, float b) { return a != a ? a : (b != b ? b : (b < a ? b : a)); }
+MBD_HD float zone_canon(float v) { return v != v ? __builtin_bit_cast(float, 0x7fc00000u) : v; }
+// One step: x [K][3] the tracked positions; s_t and clr_t of the contract, slot k outer and zone z inner.  The table's values do not
+// depend on the lane: on the device they are scalar operands from the kernel's argument segment.
+MBD_HD void zone_step(const float* __restrict__ x, int K, const mbd_zones& Z, float& s_t, float& clr_t) {
+  float s = 0.0f, c = __builtin_inff();
+  for (int k = 0; k < K; ++k) {
+    const float xk[3] = {x[3 * k], x[3 * k + 1], x[3 * k + 2]};
+    for (int z = 0; z < Z.n_zones; ++z) {
+      const mbd_zone& zn = Z.zone[z];
+      if (!((zn.links >> k) & 1u)) continue;
+      const float d = zone_dist(xk, zn);
+      s = s + zone_term(zn.weight, zone_u(zn.kind, d, zn.radius, zn.margin));
+      if (zn.kind == MBD_ZONE_KEEP_OUT) c = zone_min(c, d - zn.radius);
+    }
+  }
+  s_t = s;
+  clr_t = c;
+}
+
+#ifdef MBD_ZONE_KERNEL
+// One wavefront per row, kZoneRows rows per workgroup.  A lane owns steps t = lane, lane + 64, ...: it reads its K 3 contiguous
+// floats, forms s_t and clr_t and leaves s_t in LDS; lane 0 of the row then runs the contract's ascending chain over the 64 steps of
+// the pass (the loads of the chain do not depend on it).  The minimum crosses lanes (zone_min is order-free: a NaN wins on either
+// side, and the stored NaN is canonical); no sum does.  The table is a kernel argument: nothing of it lives in device memory.
+// Bounds: a row b >= B loads and stores nothing (it still meets the barriers: H does not depend on the row); a step t >= H
+// likewise; a load is xpos[((b H + t) K + k) 3 + i] with b < B, t < H, k < K; the stores are rews / pen_keep / clr_keep [b] and
+// step_pen / step_clr [b H + t].  LDS: kZoneRows x 64 floats.  Plain vector loads and stores.
+constexpr int kZoneRows = 4;
+struct ZoneArgs {
+  const float* xpos;  // [B][H][K][3]
+  float* rews;        // [B] in / out, or nullptr: the outputs below only
+  float* pen_keep;    // [B] pen, or nullptr
+  float* clr_keep;    // [B] clr, or nullptr
+  float* step_pen;    // [B][H] s_t, or nullptr (planning launches)
+  float* step_clr;    // [B][H] clr_t, or nullptr
+  int B, H, K;
+  mbd_zones Z;
+};
+static __global__ __launch_bounds__(64 * kZoneRows) void zones_kernel(ZoneArgs A) {
+  __shared__ float sh[kZoneRows][64];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long b = (long long)blockIdx.x * kZoneRows + wave;
+  const bool live = b < A.B;
+  float pen = 0.0f, clr = __builtin_inff();
+  for (int t0 = 0; t0 < A.H; t0 += 64) {
+    const int t = t0 + lane;
+    float s_t = 0.0f, c_t = __builtin_inff();
+    if (live && t < A.H) {
+      const size_t at = (size_t)b * A.H + t;
+      zone_step(A.xpos + at * A.K * 3, A.K, A.Z, s_t, c_t);
+      if (A.step_pen) A.step_pen[at] = s_t;
+      if (A.step_clr) A.step_clr[at] = zone_canon(c_t);
+      clr = zone_min(clr, c_t);
+    }
+    sh[wave][lane] = s_t;
+    __syncthreads();
+    if (live && lane == 0) {
+      const int n = A.H - t0 < 64 ? A.H - t0 : 64;
+      for (int j = 0; j < n; ++j) pen = pen + sh[wave][j];
+    }
+    __syncthreads();
+  }
+  for (int off = 32; off; off >>= 1) clr = zone_min(clr, __shfl_xor(clr, off, 64));
+  if (live && lane == 0) {
+    pen = pen / (float)A.H;
+    if (A.pen_keep) A.pen_keep[b] = pen;
+    if (A.clr_keep) A.clr_keep[b] = zone_canon(clr);
+    if (A.rews) A.rews[b] = A.rews[b] - pen;
+  }
+}
+#endif  // MBD_ZONE_KERNEL
+
 }  // namespace mbd

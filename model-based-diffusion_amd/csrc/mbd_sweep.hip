@@ -236,6 +236,8 @@ struct mbd_sweep {
   ValueRec val;
   // the weighting record of all the sweep's plans (mbd_sweep_set_weighting) with every plan's log [P][Ndiffuse - 1]
   WeightingRec wt;
+  // the zone record of all the sweep's plans (mbd_sweep_set_zones): one table, the P N rows' tracked positions, pen and clr
+  ZoneRec zone;
   // the pick record of all the sweep's episodes (mbd_sweep_set_mpc_pick) with every episode's slots and log
   PickRec pick;
   // the elite record of all the sweep's plans (mbd_sweep_set_elites) and the to-go record (mbd_sweep_set_togo)
@@ -447,10 +449,12 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
   MBD_TRY(w->elite.inject(P, w->d_Y0s, (long long)per_plan, HNu, 0, 0.0f, mu_in, mu_stride, ns.g, 0xffffffffu, s));
   MBD_TRY(w->timing.begin(s));
   const int sw[3] = {N, S, 0};
-  MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, nullptr, w->val.final(), s, nullptr, sw));
+  MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, w->zone.xpos(), w->val.final(), s, nullptr, sw));
   MBD_TRY(w->timing.end(s));
   // the objective record: one launch over the P N rows (blockIdx.y = plan) on the materialised candidates
   if (w->obj.has) MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_Y0s, false, 0.0f, nullptr, 0, s));
+  // the zone record: one launch over the P N rows behind it (one table: the plans' rows are one batch)
+  MBD_TRY(w->zone.launch_step(w->d_rews, P * N, s));
   // the value record: one launch over the P N rows behind it (one net: the plans' rows are one batch)
   MBD_TRY(w->val.launch_step(w->d_rews, P * N, s));
   return sweep_pi_update(w, step, mu_in, mu_stride, true);
@@ -616,7 +620,7 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
   MBD_TRY(w->timing.begin(s));
   const bool fused_lp = c.enable_demo && rollout_choice(e, P * N, H, sw).fuses_logpd;  // (mbd_plan.hip: the log-densities out of the rollout)
   MBD_TRY(launch_rollout(e, st.state0, w->d_eps[cur], P * N, H, w->d_rewss, w->d_rews,
-                         (c.enable_demo && !fused_lp) ? w->d_xpos.get() : nullptr, w->val.final(), s, &lz, sw,
+                         (c.enable_demo && !fused_lp) ? w->d_xpos.get() : w->zone.xpos(), w->val.final(), s, &lz, sw,
                          fused_lp ? w->d_lp.get() : nullptr, nullptr, st.xref));
   MBD_TRY(w->timing.end(s));
   if (c.enable_demo && !fused_lp) MBD_TRY(launch_logpd(e, w->d_xpos, P * N, H, w->d_lp, s, st.xref));
@@ -624,6 +628,8 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
   // change: the launch reads eps[cur] on the steps' stream in front of the weighted mean, which is the buffer's last reader.
   if (w->obj.has)
     MBD_TRY(w->obj.launch(w->d_rewss, w->d_rews, N, 0, w->d_eps[cur], true, w->sigmas[i], st.ybar_in, st.ybar_in_stride, s));
+  // the zone record: one launch over the P N rows behind it (one table: the plans' rows are one batch)
+  MBD_TRY(w->zone.launch_step(w->d_rews, P * N, s));
   // the value record: one launch over the P N rows behind it (one net: the plans' rows are one batch)
   MBD_TRY(w->val.launch_step(w->d_rews, P * N, s));
   return sweep_update(w, i, st.slot, w->d_eps[cur].get(), st.ybar_in, st.ybar_in_stride, st.rew_xref, true, st.mask);
@@ -781,6 +787,38 @@ extern "C" int mbd_sweep_set_value(mbd_sweep* w, const mbd_value* rec) {
   return w->val.set(rec, w->env, (size_t)w->P * w->cfg.Nsample, w->P);
 }
 
+// one zone record for all plans of the sweep (include/mbd_hip.h mbd_zones), as mbd_plan_set_zones
+extern "C" int mbd_sweep_set_zones(mbd_sweep* w, const mbd_zones* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (rec) {  // (before any device access)
+    const int n_track = w->env ? w->env->model.n_track : 0;
+    MBD_TRY(check_zones(rec, n_track > 0 ? n_track : 32));
+    MBD_TRY(check_zones_handle(w->env, w->cfg, "sweep"));
+    if (w->togo.has) return refuse_beside_togo("zone record", "sweep");
+    if (w->pick.has) return fail(MBD_ERR_UNSUPPORTED, "zone record: the sweep carries a pick record (its slots' rollouts write no positions)");
+  }
+  NO_SWEEP_SESSION(w, "set_zones");
+  return w->zone.set(rec, w->env, (size_t)w->P * w->cfg.Nsample, w->cfg.Hsample);
+}
+
+extern "C" int mbd_sweep_update_zones(mbd_sweep* w, const mbd_zones* rec) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (w->session.in_flight) return fail(MBD_ERR_STATE, "update_zones: a tick is in flight (mbd_sweep_mpc_collect first)");
+  return w->zone.update(rec, w->env, "sweep");
+}
+
+extern "C" int mbd_sweep_peek_zones(mbd_sweep* w, int k, float* pen_out, float* clear_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "peek_zones: plan k=%d outside [0,%d)", k, w->P);
+  return w->zone.peek(w->env, k, w->cfg.Nsample, pen_out, clear_out, "sweep");
+}
+
+extern "C" int mbd_sweep_peek_mpc_zones(mbd_sweep* w, int k, float* pen_out, float* clear_out) {
+  if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
+  if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "peek_mpc_zones: episode k=%d outside [0,%d)", k, w->P);
+  return w->zone.peek_mpc(w->env, k, pen_out, clear_out, "sweep");
+}
+
 // one weighting record for all plans of the sweep (include/mbd_hip.h mbd_weighting), as mbd_plan_set_weighting
 extern "C" int mbd_sweep_set_weighting(mbd_sweep* w, const mbd_weighting* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
@@ -854,6 +892,7 @@ extern "C" int mbd_sweep_set_togo(mbd_sweep* w, const mbd_togo* rec) {
     if (other)
       return fail(MBD_ERR_UNSUPPORTED, "to-go record: the sweep carries %s record: what that record means per horizon row is not defined",
                   other);
+    if (w->zone.has) return refuse_beside_zones("to-go record", "sweep");
   }
   NO_SWEEP_SESSION(w, "set_togo");
   SweepTogoRec& L = w->togo;
@@ -1008,6 +1047,7 @@ extern "C" int mbd_sweep_set_mpc_pick(mbd_sweep* w, const mbd_mpc_pick* rec) {
   if (rec) MBD_TRY(check_mpc_pick(rec));  // (before any device access)
   if (rec && w->cfg.enable_demo)
     return fail(MBD_ERR_UNSUPPORTED, "mpc pick record: enable_demo=1: a demo plan's score is not the return the pick compares");
+  if (rec && w->zone.has) return refuse_beside_zones("mpc pick record", "sweep");
   return w->pick.set(rec, w->env->device, w->P, w->HNu, w->cfg.Hsample);
 }
 
@@ -1159,6 +1199,10 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
   const bool has_demo = w->demo.has;
   for (int k = 0; k < P; ++k)
     if (w->has_plant[k] && w->plant_rec[k].plant) MBD_TRY(w->demo.check_plant(e, w->plant_rec[k].plant));
+  // with a zone record likewise, and room for the log of the executed steps
+  for (int k = 0; k < P; ++k)
+    if (w->has_plant[k] && w->plant_rec[k].plant) MBD_TRY(w->zone.check_plant(e, w->plant_rec[k].plant));
+  MBD_TRY(w->zone.start(T, P, E));
   const int planar = (e->model.flags & MBD_FLAG_PLANAR) ? 1 : 0;
   // the disturbance key chains: dk, d_t = split(dk) per tick and episode
   std::vector<uint32_t> dk(2 * (size_t)P, 0u);
@@ -1278,7 +1322,10 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     if (!any_plant) {
       // (with a demo record the launch also writes the tracked positions of every episode's E steps into their log)
       MBD_TRY(launch_rollout(e, states_t, has_delay ? rows_t : w->d_mpc_rows.get(), P, E, w->d_mpc_rewards + (size_t)t * P * E, nullptr,
-                             has_demo ? w->demo.xlog(t, P, E) : nullptr, w->d_mpc_states + (size_t)(t + 1) * P * S, s, nullptr, exec_sw));
+                             has_demo ? w->demo.xlog(t, P, E) : w->zone.xlog(t, P, E), w->d_mpc_states + (size_t)(t + 1) * P * S, s,
+                             nullptr, exec_sw));
+      // (with a zone record: s_t and clr_t of every episode's E executed steps into the log, one launch over the P rows)
+      MBD_TRY(w->zone.log(t, P, E, s));
       continue;
     }
     SweepPlant sp{};
@@ -1297,10 +1344,11 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       int k1 = k0 + 1;
       while (k1 < P && plant_of(k1) == plant_of(k0)) ++k1;
       MBD_TRY(launch_rollout(plant_of(k0), states_t + (size_t)k0 * S, rows_t + (size_t)k0 * EN, k1 - k0, E,
-                             rewards_t + (size_t)k0 * E, nullptr, has_demo ? w->demo.xlog(t, P, E, k0) : nullptr,
+                             rewards_t + (size_t)k0 * E, nullptr, has_demo ? w->demo.xlog(t, P, E, k0) : w->zone.xlog(t, P, E, k0),
                              states_t1 + (size_t)k0 * S, s, nullptr, exec_sw));
       k0 = k1;
     }
+    MBD_TRY(w->zone.log(t, P, E, s));
     if (any_kick) {
       hipLaunchKernelGGL(mpc_kick_batch_kernel, dim3(1, (unsigned)P), dim3(64), 0, s, sp, states_t1, S,
                          (const float*)w->d_plant_kick, planar);
@@ -1332,6 +1380,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     episode_major(states_out, T + 1, S, S);
   }
   if (has_delay) w->delay.pred_ticks = T;
+  if (w->zone.has) { w->zone.ticks = T; w->zone.exec = E; w->zone.episodes = P; }
   if (pi) { w->sigma_rec.ticks = T; w->sigma_rec.episodes = P; }
   if ((any_plant || has_delay) && actions_out) {  // (the executed rows carry the action noise, or are the queues': their own log)
     HIP_TRY(fetch(w->d_mpc_actions, (size_t)T * P * EN));

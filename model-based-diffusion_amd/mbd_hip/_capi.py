@@ -131,6 +131,23 @@ class Togo(C.Structure):
     _fields_ = [("block", C.c_int32), ("min_tail", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+MAX_ZONES = 16
+ZONE_KEEP_OUT, ZONE_GOAL = 0, 1
+
+
+class Zone(C.Structure):
+    """mbd_zone (include/mbd_hip.h): a keep-out region or a goal for the track slots of ``links`` — the distance is taken over
+    the coordinate differences from ``center`` times ``scale``; a keep-out zone costs inside ``radius + margin``, a goal outside
+    ``radius``."""
+    _fields_ = [("kind", C.c_int32), ("links", C.c_uint32), ("center", C.c_float * 3), ("scale", C.c_float * 3),
+                ("radius", C.c_float), ("margin", C.c_float), ("weight", C.c_float), ("reserved", C.c_int32)]
+
+
+class Zones(C.Structure):
+    """mbd_zones (include/mbd_hip.h): the table of a zone record."""
+    _fields_ = [("n_zones", C.c_int32), ("reserved", C.c_int32 * 3), ("zone", Zone * MAX_ZONES)]
+
+
 ELITES_MAX = 32
 TOGO_MAX_N = 12288
 PICK_MEAN, PICK_PREV, PICK_BEST = 1, 2, 4
@@ -178,6 +195,8 @@ EXPORTS = [
     "mbd_plan_set_value", "mbd_plan_peek_value", "mbd_plan_eval_value", "mbd_sweep_set_value",
     "mbd_plan_set_adapt", "mbd_plan_peek_adapt", "mbd_plan_set_elites", "mbd_plan_peek_elites",
     "mbd_plan_set_togo", "mbd_plan_peek_togo",
+    "mbd_plan_set_zones", "mbd_plan_update_zones", "mbd_plan_peek_zones", "mbd_plan_peek_mpc_zones",
+    "mbd_sweep_set_zones", "mbd_sweep_update_zones", "mbd_sweep_peek_zones", "mbd_sweep_peek_mpc_zones",
     "mbd_sweep_set_elites", "mbd_sweep_peek_elites", "mbd_sweep_set_togo", "mbd_sweep_peek_togo",
     "mbd_plan_mpc_open", "mbd_plan_mpc_submit", "mbd_plan_mpc_collect", "mbd_plan_mpc_tick", "mbd_plan_mpc_reset_mean",
     "mbd_plan_mpc_close", "mbd_plan_eval", "mbd_plan_peek", "mbd_plan_kernel_time",
@@ -283,6 +302,14 @@ def load() -> C.CDLL:
     lib.mbd_sweep_set_togo.argtypes = [_vp, C.POINTER(Togo)]
     lib.mbd_sweep_peek_togo.argtypes = [_vp, _i, _vp, _vp, _vp, _vp]
     lib.mbd_plan_peek_adapt.argtypes = [_vp, _vp, _vp, _vp, _i, C.POINTER(C.c_int)]
+    lib.mbd_plan_set_zones.argtypes = [_vp, C.POINTER(Zones)]
+    lib.mbd_plan_update_zones.argtypes = [_vp, C.POINTER(Zones)]
+    lib.mbd_plan_peek_zones.argtypes = [_vp, _vp, _vp]
+    lib.mbd_plan_peek_mpc_zones.argtypes = [_vp, _vp, _vp]
+    lib.mbd_sweep_set_zones.argtypes = [_vp, C.POINTER(Zones)]
+    lib.mbd_sweep_update_zones.argtypes = [_vp, C.POINTER(Zones)]
+    lib.mbd_sweep_peek_zones.argtypes = [_vp, _i, _vp, _vp]
+    lib.mbd_sweep_peek_mpc_zones.argtypes = [_vp, _i, _vp, _vp]
     lib.mbd_plan_mpc_open.argtypes = [_vp, C.POINTER(MpcConfig), _u32p]
     lib.mbd_plan_mpc_submit.argtypes = [_vp, _vp]
     lib.mbd_plan_mpc_collect.argtypes = [_vp, _vp, _vp, _vp, _vp, C.POINTER(MpcTickInfo)]
@@ -722,6 +749,98 @@ def peek_elites(fn, handle, n_elites: int, HNu: int, capacity: int = None) -> di
     m, c = min(n.value, int(capacity)), int(count[0])
     return {"E": E[:c], "R": R[:c], "src": src[:c], "count": c, "log_count": lc[:m], "log_kept": lk[:m], "log_top": lt[:m],
             "steps": n.value}
+
+
+_ZONE_KINDS = {"out": ZONE_KEEP_OUT, "keep_out": ZONE_KEEP_OUT, "goal": ZONE_GOAL, ZONE_KEEP_OUT: ZONE_KEEP_OUT, ZONE_GOAL: ZONE_GOAL}
+
+
+def zone_entry(kind, center, radius: float, margin: float, weight: float = 1.0, links=None, axes: str = "xyz") -> dict:
+    """One entry of a zone record as a plain dict: ``kind`` "out" / "goal" (or the C constants), ``center`` [3], ``links`` None
+    (every track slot), a bit mask, or a list of track slots or link names (names are resolved against the env by
+    ``zones_record``); ``axes``: which coordinate differences count — "xyz" a sphere, "xy" a vertical cylinder, "x" a slab."""
+    if kind not in _ZONE_KINDS:
+        raise ValueError(f"zone: kind={kind!r}: 'out' or 'goal'")
+    if not axes or any(a not in "xyz" for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError(f"zone: axes={axes!r}: a subset of 'xyz'")
+    c = [float(v) for v in np.asarray(center, np.float64).reshape(-1)]
+    if len(c) != 3:
+        raise ValueError(f"zone: center has {len(c)} entries, expected 3")
+    return dict(kind=_ZONE_KINDS[kind], center=c, scale=[1.0 if a in axes else 0.0 for a in "xyz"], radius=float(radius),
+                margin=float(margin), weight=float(weight), links=links)
+
+
+def zones_record(zones, n_track: int, track_names=None) -> "Zones":
+    """The mbd_zones of ``Plan.set_zones``'s argument: a list of ``zone_entry`` dicts (a dict may carry ``scale`` [3] of its own).
+    ``track_names``: the link names of the env's track slots, for entries whose ``links`` name links."""
+    zones = list(zones)
+    if not 1 <= len(zones) <= MAX_ZONES:
+        raise ValueError(f"zones: {len(zones)} entries: must lie in 1..{MAX_ZONES}")
+    rec = Zones()
+    rec.n_zones = len(zones)
+    for z, e in enumerate(zones):
+        links = e.get("links")
+        if links is None:
+            mask = (1 << int(n_track)) - 1
+        elif isinstance(links, (int, np.integer)):
+            mask = int(links)
+        else:
+            mask = 0
+            for l in links:
+                if isinstance(l, str):
+                    if track_names is None or l not in track_names:
+                        raise ValueError(f"zones: zone[{z}].links: {l!r} is not a tracked link ({list(track_names or ())})")
+                    l = list(track_names).index(l)
+                if not 0 <= int(l) < 32:
+                    raise ValueError(f"zones: zone[{z}].links: slot {l} outside [0, 32)")
+                mask |= 1 << int(l)
+        zn = rec.zone[z]
+        zn.kind, zn.links = int(e["kind"]), mask & 0xffffffff
+        for i in range(3):
+            zn.center[i], zn.scale[i] = float(e["center"][i]), float(e["scale"][i])
+        zn.radius, zn.margin, zn.weight = float(e["radius"]), float(e["margin"]), float(e["weight"])
+    return rec
+
+
+def debug_check_zones(rec: "Zones", n_track: int) -> int:
+    """include/mbd_hip_debug.h: the refusals a zone record alone decides for an env of that n_track; the return code (the message:
+    ``mbd_last_error``)."""
+    lib = load()
+    lib.mbd_debug_check_zones.argtypes = [C.POINTER(Zones), _i]
+    return lib.mbd_debug_check_zones(None if rec is None else C.byref(rec), int(n_track))
+
+
+def _debug_zones(fn, rec, xpos, rews):
+    xpos = np.ascontiguousarray(xpos, np.float32)
+    B, H, K = xpos.shape[:3]
+    rews = None if rews is None else np.ascontiguousarray(rews, np.float32)
+    out = dict(rews=np.full(B, np.nan, np.float32), pen=np.full(B, np.nan, np.float32), clr=np.full(B, np.nan, np.float32),
+               step_pen=np.full((B, H), np.nan, np.float32), step_clr=np.full((B, H), np.nan, np.float32))
+    fn.argtypes = [C.POINTER(Zones), _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]
+    check(fn(C.byref(rec), np_ptr(xpos), None if rews is None else np_ptr(rews), B, H, K,
+             None if rews is None else np_ptr(out["rews"]), np_ptr(out["pen"]), np_ptr(out["clr"]), np_ptr(out["step_pen"]),
+             np_ptr(out["step_clr"])))
+    if rews is None:
+        del out["rews"]
+    return out
+
+
+def debug_zones_host(rec: "Zones", xpos, rews=None) -> dict:
+    """include/mbd_hip_debug.h: a zone record's launch on the host (no device) over ``xpos`` [B, H, K, 3] and ``rews`` [B].
+    Returns dict(rews, pen, clr [B], step_pen, step_clr [B, H])."""
+    return _debug_zones(load().mbd_debug_zones_host, rec, xpos, rews)
+
+
+def debug_zones_step(rec: "Zones", xpos, rews=None) -> dict:
+    """include/mbd_hip_debug.h: zones_kernel alone on the device, on the same arguments as ``debug_zones_host``."""
+    return _debug_zones(load().mbd_debug_zones_step, rec, xpos, rews)
+
+
+def peek_zones(fn, handle, k, N: int) -> dict:
+    """mbd_*_peek_zones: {'pen' [N], 'clr' [N]} of the last step (``k`` None: a plan)."""
+    pen, clr = np.zeros(N, np.float32), np.zeros(N, np.float32)
+    args = (handle,) if k is None else (handle, int(k))
+    check(fn(*args, np_ptr(pen), np_ptr(clr)))
+    return dict(pen=pen, clr=clr)
 
 
 def togo_record(block: int = 1, min_tail: int = 1) -> "Togo":

@@ -118,6 +118,37 @@ class Model:
                 setattr(m, extra, getattr(self, extra))
         return m
 
+    def tracked(self, links) -> "Model":
+        """A copy of the model that tracks ``links`` — link names or positions in the model, in that order, at most MAX_TRACK, none
+        twice; everything else is shared with this model.  The tracked links' world positions are what a rollout returns as
+        ``xpos``, a demonstration is followed by and a zone record (``Plan.set_zones``) measures.  A planar model is refused: the
+        planar kernels return no positions — compile it ``planar=False`` with ``track_names``."""
+        if int(self.fields.get("flags", 0)) & FLAG_PLANAR:
+            raise ValueError(f"tracked: {self.env_name or 'the model'} is planar: the planar kernels return no positions; compile "
+                             "the model planar=False with track_names")
+        idx = []
+        for l in links:
+            if isinstance(l, str):
+                if l not in self.link_names:
+                    raise ValueError(f"tracked: no link named {l!r} (the model's links: {self.link_names})")
+                l = self.link_names.index(l)
+            l = int(l)
+            if not 0 <= l < self.n_links:
+                raise ValueError(f"tracked: link {l} outside [0, {self.n_links})")
+            if l in idx:
+                raise ValueError(f"tracked: link {l} given twice")
+            idx.append(l)
+        if len(idx) > MAX_TRACK:
+            raise ValueError(f"tracked: {len(idx)} links, at most {MAX_TRACK}")
+        f = dict(self.fields)
+        f["n_track"] = len(idx)
+        f["track_link"] = np.asarray(idx, np.int32)
+        m = Model(f, self.link_names, self.actuator_names, self.env_name)
+        for extra in ("masses", "inertias"):
+            if hasattr(self, extra):
+                setattr(m, extra, getattr(self, extra))
+        return m
+
     def scaled(self, mass: float = 1.0, friction: float = 1.0, gear: float = 1.0) -> "Model":
         """A copy of the model with every link ``mass`` times as heavy (``inv_mass`` and ``inv_inertia`` divided by it), the
         contact ``friction`` and the actuators' ``act_gear`` multiplied — float32 arithmetic; everything else is shared with

@@ -140,6 +140,11 @@ class Sweep:
                                                               _capi.np_ptr(out["demo_windows"]) if e == 0 else None))
         if self.has_mpc_pick():  # (what every tick of every episode handed on, and the three plans' values)
             out["pick"] = [self.peek_mpc_pick(e, T) for e in range(P)]
+        if self.has_zones:  # (every episode's penalties and keep-out clearances of its executed control steps)
+            out["zone_pen"], out["zone_clear"] = np.zeros((P, T * E), np.float32), np.zeros((P, T * E), np.float32)
+            for e in range(P):
+                _capi.check(self.lib.mbd_sweep_peek_mpc_zones(self.h, e, _capi.np_ptr(out["zone_pen"][e]),
+                                                              _capi.np_ptr(out["zone_clear"][e])))
         return out
 
     def mpc_open(self, keys, warm_steps: int, exec_steps: int = 1, max_ticks: int = None):
@@ -280,6 +285,35 @@ class Sweep:
         if not self.has_togo:
             _capi.check(fn(self.h, None, None, None, None))
         return _capi.peek_togo(fn, self.h, self.H, self.cfg.Nsample)
+
+    def set_zones(self, zones):
+        """One zone record for all plans of the sweep (``Plan.set_zones``): plan k of ``run``, episode k of ``run_mpc`` and of a
+        session equals the single plan with that record, bit for bit."""
+        zones = list(zones)
+        rec = _zones_record(self.env, zones)
+        _capi.check(self.lib.mbd_sweep_set_zones(self.h, C.byref(rec)))
+        self._zones = len(zones)
+
+    def clear_zones(self):
+        _capi.check(self.lib.mbd_sweep_set_zones(self.h, None))
+        self._zones = None
+
+    @property
+    def has_zones(self) -> bool:
+        return getattr(self, "_zones", None) is not None
+
+    def update_zones(self, zones):
+        """Replace the table of the sweep's zone record (``Plan.update_zones``)."""
+        zones = list(zones)
+        rec = _zones_record(self.env, zones)
+        _capi.check(self.lib.mbd_sweep_update_zones(self.h, C.byref(rec)))
+        self._zones = len(zones)
+
+    def peek_zones(self, k: int) -> dict:
+        """Plan ``k``'s ``pen`` and ``clr`` [Nsample] of the last step (``Plan.peek_zones``)."""
+        if not self.has_zones:
+            _capi.check(self.lib.mbd_sweep_peek_zones(self.h, int(k), None, None))
+        return _capi.peek_zones(self.lib.mbd_sweep_peek_zones, self.h, int(k), self.cfg.Nsample)
 
     def set_mpc_pick(self, mean=True, prev=True, best=True):
         """One pick record for all episodes of the sweep (``Plan.set_mpc_pick``): episode k of ``run_mpc`` and of a session is
@@ -436,6 +470,16 @@ def _objective_record(row_weight, effort, rate, act_weight, prev0, H, Nu):
     return rec, keep
 
 
+def _zones_record(env, zones):
+    """The mbd_zones of a list of ``mpc.zone`` entries against ``env``'s track slots (link names resolve to slots)."""
+    sys_ = getattr(env, "sys", None)
+    K = int(sys_.fields["n_track"]) if sys_ is not None else 0
+    names = None
+    if sys_ is not None and sys_.link_names:
+        names = [sys_.link_names[int(l)] for l in np.asarray(sys_.fields["track_link"])[:K]]
+    return _capi.zones_record(zones, K, names)
+
+
 def _ensemble_record(envs, risk):
     """The mbd_ensemble of ``set_ensemble``'s arguments (an entry None: the plan's own env)."""
     envs = list(envs)
@@ -552,6 +596,11 @@ class MpcSession:
         self.submit(state, q, qd)
         return self.collect()
 
+    def update_zones(self, zones) -> None:
+        """Replace the table of the handle's zone record between two ticks (``Plan.update_zones``): the next tick plans under it.
+        Refused while a tick is in flight."""
+        self.plan.update_zones(zones)
+
     def reset_mean(self, k: int = None) -> None:
         """The next tick is a cold one (Ybar = 0, Ndiffuse-1 steps, flagged TICK_COLD): what a controller does after rows it
         could not use.  The delay queue stays.  A sweep's session: episode ``k``'s (None: every episode's)."""
@@ -666,6 +715,9 @@ class Plan:
             _capi.check(self.lib.mbd_plan_peek_mpc_track(self.h, _capi.np_ptr(out["track_err"]), _capi.np_ptr(out["demo_windows"])))
         if self.has_mpc_pick():  # (what every tick handed on, and the three plans' values)
             out["pick"] = self.peek_mpc_pick(T)
+        if self.has_zones:  # (the penalty and the keep-out clearance of every executed control step)
+            out["zone_pen"], out["zone_clear"] = np.zeros(T * E, np.float32), np.zeros(T * E, np.float32)
+            _capi.check(self.lib.mbd_plan_peek_mpc_zones(self.h, _capi.np_ptr(out["zone_pen"]), _capi.np_ptr(out["zone_clear"])))
         return out
 
     def set_mpc_pick(self, mean=True, prev=True, best=True):
@@ -921,6 +973,42 @@ class Plan:
         if not self.has_togo:
             _capi.check(self.lib.mbd_plan_peek_togo(self.h, None, None, None, None))
         return _capi.peek_togo(self.lib.mbd_plan_peek_togo, self.h, self.H, self.cfg.Nsample)
+
+    def set_zones(self, zones):
+        """Keep-out regions and goals for the env's tracked links (include/mbd_hip.h mbd_zones): ``zones`` is a list of
+        ``mpc.zone`` entries.  Every step subtracts from each candidate's reward the mean over the horizon of the entries'
+        penalties at the tracked positions its rollout passed through.  The env must track links (``get_env(name, track=...)``);
+        unsharded plans without ``enable_demo`` and without an ensemble, to-go or pick record.  ``run_mpc`` then also returns
+        ``zone_pen`` and ``zone_clear`` [T*E]: the penalty and the keep-out clearance of every executed control step."""
+        zones = list(zones)
+        rec = _zones_record(self.env, zones)
+        _capi.check(self.lib.mbd_plan_set_zones(self.h, C.byref(rec)))
+        self._zones = len(zones)
+        self._zone_entries = zones
+
+    def clear_zones(self):
+        _capi.check(self.lib.mbd_plan_set_zones(self.h, None))
+        self._zones = None
+
+    @property
+    def has_zones(self) -> bool:
+        return getattr(self, "_zones", None) is not None
+
+    def update_zones(self, zones):
+        """Replace the table of the plan's zone record — move a goal or an obstacle.  Allowed between the ticks of an open
+        session (``MpcSession.update_zones``); the next step plans under the new table."""
+        zones = list(zones)
+        rec = _zones_record(self.env, zones)
+        _capi.check(self.lib.mbd_plan_update_zones(self.h, C.byref(rec)))
+        self._zones = len(zones)
+        self._zone_entries = zones
+
+    def peek_zones(self) -> dict:
+        """``pen`` and ``clr`` [Nsample] of the last step (a plan with a zone record): each candidate's penalty and its smallest
+        distance to a keep-out surface (negative: inside; +inf without keep-out entries)."""
+        if not self.has_zones:
+            _capi.check(self.lib.mbd_plan_peek_zones(self.h, None, None))
+        return _capi.peek_zones(self.lib.mbd_plan_peek_zones, self.h, None, self.cfg.shard_count)
 
     def peek_objective(self):
         """The last step's ``ret`` [shard_count] ([M, N] under an ensemble record) and ``cost`` [shard_count] (a plan with an

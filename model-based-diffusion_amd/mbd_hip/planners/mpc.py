@@ -123,6 +123,19 @@ flags.  The report gains ``togo_groups``, the groups' first rows.
 
     python -m mbd_hip.planners.mpc --env_name hopper --warm_steps 20 --togo_block 5 --togo_min_tail 10
 
+None of the above says where the body may go.  A zone record (include/mbd_hip.h mbd_zones; DESIGN.md section 1 "N20 zones") does:
+``--zone_links torso,left_shin`` retracks the built-in model (``get_env(name, track=...)``) so that the rollouts return those links'
+world positions, and ``--zones`` lists keep-out regions and goals for them, ';' between entries, each
+``kind:cx,cy,cz:radius:margin[:weight[:axes[:links]]]`` — kind ``out`` (a cost inside radius + margin, rising to ``weight`` at the
+surface) or ``goal`` (a cost outside radius, rising to ``weight`` at radius + margin); axes a subset of ``xyz`` (``xy``: a vertical
+cylinder, or a point goal on the ground plane); links a comma list of the tracked links the entry applies to (default: all).  Every
+step subtracts the horizon mean of the penalties from each candidate's reward.  ``--online`` and ``--n_episodes`` honour the flags
+(one record for the batch).  The report gains ``zone_pen_mean``, ``zone_clear_min`` and ``zone_hits`` — the executed control steps'
+mean penalty, smallest keep-out clearance and the number of them inside a keep-out region; the saved episode ``zone_pen`` and
+``zone_clear``.  The logged rewards stay the env's.
+
+    python -m mbd_hip.planners.mpc --env_name humanoidrun --zone_links torso --zones "out:2,0,1:0.3:0.3:5;goal:6,0,1.2:0.2:6:1:xy"
+
 A demo plan (``--enable_demo``) compares its 50 planned steps with the env's 50 demo rows; in an episode the demo has to move
 with the system.  ``--demo_clip env|FILE.npy`` (include/mbd_hip.h mbd_mpc_demo; DESIGN.md section 1 "N10 demo clock") sets the
 clip the episode follows — the env's own demo, or an array [n_track, L, 3] (car2d: [L, 2]) — and ``--demo_start c0`` the clip
@@ -227,6 +240,73 @@ class MpcArgs(Args):
     elite_carry: bool = False  # ... and a tick boundary shifts the elites with the mean (default: every tick starts without elites)
     togo_block: int = 0  # B > 0: a to-go record (mbd_togo) — the horizon's rows in groups of B, each under weights from the return ahead ...
     togo_min_tail: int = 1  # ... a group starting only where at least this many rows are still ahead
+    zones: str = ""  # "kind:cx,cy,cz:radius:margin[:weight[:axes[:links]]];...": a zone record (mbd_zones) for the tracked links ...
+    zone_links: str = ""  # ... comma list of link names or positions the built-in model is retracked to (get_env's track)
+
+
+def zone(kind, center, radius: float, margin: float, weight: float = 1.0, links=None, axes: str = "xyz") -> dict:
+    """One entry of a zone record (``Plan.set_zones``, include/mbd_hip.h mbd_zone): ``kind`` "out" — a keep-out region: a
+    tracked link nearer than ``radius + margin`` to ``center`` costs ``weight * clip((radius + margin - d) / margin, 0, 1) ** 2``
+    per step — or "goal": ``weight * clip((d - radius) / margin, 0, 1) ** 2``.  ``axes`` says which coordinate differences the
+    distance d is taken over ("xyz" a sphere, "xy" a vertical cylinder or a point goal on the ground plane, "x" a slab);
+    ``links`` which tracked links the entry applies to — None: all, else a list of track slots or link names, or a bit mask."""
+    return _capi.zone_entry(kind, center, radius, margin, weight, links, axes)
+
+
+def parse_zones(text: str) -> list:
+    """The entries of ``--zones``: ';' between entries, each ``kind:cx,cy,cz:radius:margin[:weight[:axes[:links]]]``."""
+    out = []
+    for k, item in enumerate(x for x in text.split(";") if x.strip()):
+        f = [x.strip() for x in item.split(":")]
+        if not 4 <= len(f) <= 7:
+            raise ValueError(f"zones: entry {k} {item!r}: kind:cx,cy,cz:radius:margin[:weight[:axes[:links]]]")
+        try:
+            center = [float(x) for x in f[1].split(",")]
+            radius, margin = float(f[2]), float(f[3])
+            weight = float(f[4]) if len(f) > 4 and f[4] else 1.0
+        except ValueError:
+            raise ValueError(f"zones: entry {k} {item!r}: center, radius, margin and weight are numbers") from None
+        axes = f[5] if len(f) > 5 and f[5] else "xyz"
+        links = None
+        if len(f) > 6 and f[6]:
+            links = [int(x) if x.lstrip("-").isdigit() else x for x in (y.strip() for y in f[6].split(","))]
+        out.append(zone(f[0], center, radius, margin, weight, links, axes))
+    if not out:
+        raise ValueError(f"zones={text!r}: no entry")
+    return out
+
+
+def _has_zones(args: MpcArgs) -> bool:
+    return bool(args.zones)
+
+
+def _track_of(args: MpcArgs) -> tuple:
+    """``get_env``'s track: the links of ``--zone_links`` (positions as ints)."""
+    return tuple(int(x) if x.lstrip("-").isdigit() else x for x in (y.strip() for y in args.zone_links.split(",")) if x)
+
+
+def _get_env(args: MpcArgs, device: int):
+    """The env of the arguments: the built-in one, retracked where ``--zone_links`` says so (without the flag: today's call)."""
+    track = _track_of(args)
+    return get_env(args.env_name, device=device, track=track) if track else get_env(args.env_name, device=device)
+
+
+def _zones_settings(args: MpcArgs) -> dict:
+    return dict(zones=args.zones, zone_links=args.zone_links) if _has_zones(args) else {}
+
+
+def zones_report(ep: dict) -> dict:
+    """``zone_pen_mean``, ``zone_clear_min`` and ``zone_hits`` (the executed steps with negative clearance) of an episode's
+    ``zone_pen`` / ``zone_clear`` logs, any leading episode axes included."""
+    pen, clr = np.asarray(ep["zone_pen"], np.float64), np.asarray(ep["zone_clear"], np.float64)
+    return dict(zone_pen_mean=float(pen.mean()), zone_clear_min=float(clr.min()), zone_hits=int((clr < 0).sum()))
+
+
+def _online_zone_log(plan, xpos) -> tuple:
+    """(s_t, clr_t) of executed steps from their tracked positions [E, K, 3]: the library's host text of the zone launch."""
+    from .mbd_planner import _zones_record
+    out = _capi.debug_zones_host(_zones_record(plan.env, plan._zone_entries), np.asarray(xpos, np.float32)[None])
+    return out["step_pen"][0], out["step_clr"][0]
 
 
 def _has_value(args: MpcArgs) -> bool:
@@ -658,7 +738,7 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
     """``online``: no plant record is set — the caller executes the rows (``run_mpc_online``)."""
     _check_togo(args)
     apply_recommended(args)
-    env = get_env(args.env_name, device=device)
+    env = _get_env(args, device)
     state_init, rng_exp = _reset_and_key(env, args.seed)
     plan = Plan(env, args, update_method=_method(args))
     plan.set_state0(state_init)
@@ -691,6 +771,8 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
         plan.set_elites(**_elites_of(args))
     if _has_togo(args):
         plan.set_togo(**_togo_of(args))
+    if _has_zones(args):
+        plan.set_zones(parse_zones(args.zones))
     return env, plan, state_init, rng_exp
 
 
@@ -709,7 +791,7 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
     pe = env if plant is None else plant
     T, E = args.n_ticks, args.exec_steps
     s = np.ascontiguousarray(state_init.pipeline_state, np.float32).reshape(-1)
-    actions, rewards, states, means, predicted, secs, wlog, plog = [], [], [s], [], [], [], [], []
+    actions, rewards, states, means, predicted, secs, wlog, plog, zlog = [], [], [s], [], [], [], [], [], []
     with plan.mpc_open(key, args.warm_steps, E, T) as session:
         for _ in range(T):
             out = session.tick(s)
@@ -719,7 +801,11 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
             if session.pick is not None:  # (a pick record: what the tick handed on)
                 plog.append(session.pick)
             rows = out["head"]  # (the rows to execute now: the plan's own first rows, or under a delay record the queue's head)
-            rewss, fin = pe.rollout(State(s, None, np.float32(0), np.float32(0), {}), rows[None], want_final=True)
+            if _has_zones(args):  # (the executed steps' tracked positions: their penalties and clearances, on the host)
+                rewss, xp, fin = pe.rollout(State(s, None, np.float32(0), np.float32(0), {}), rows[None], want_xpos=True, want_final=True)
+                zlog.append(_online_zone_log(plan, xp[0].cpu().numpy()))
+            else:
+                rewss, fin = pe.rollout(State(s, None, np.float32(0), np.float32(0), {}), rows[None], want_final=True)
             s = fin[0].cpu().numpy().reshape(-1)
             actions.append(rows)
             rewards.append(rewss[0].cpu().numpy())
@@ -743,6 +829,8 @@ def _online_episode(env, plant, plan, state_init, key, args: MpcArgs) -> dict:
         ep["elite_log"] = elites
     if togo is not None:
         ep["togo"] = togo
+    if zlog:
+        ep["zone_pen"], ep["zone_clear"] = np.concatenate([z[0] for z in zlog]), np.concatenate([z[1] for z in zlog])
     if plog:
         ep["pick"] = dict(choice=np.array([x["choice"] for x in plog], np.int32), rets=np.stack([x["rets"] for x in plog]),
                           best=np.array([x["best"] for x in plog], np.int32))
@@ -831,7 +919,7 @@ def _setup_batch(arg_list, device: int):
     for a in arg_list:
         apply_recommended(a)
     a0 = arg_list[0]
-    env = get_env(a0.env_name, device=device)
+    env = _get_env(a0, device)
     sweep = Sweep(env, a0, len(arg_list), temps=[a.temp_sample for a in arg_list], update_method=_method(a0))
     if _has_sigma(a0):  # (one record for all episodes: _check_batch has held the four fields equal)
         sweep.set_mpc_sigma(*_sigma_of(a0))
@@ -855,6 +943,8 @@ def _setup_batch(arg_list, device: int):
         sweep.set_elites(**_elites_of(a0))
     if _has_togo(a0):  # (and one to-go record)
         sweep.set_togo(**_togo_of(a0))
+    if _has_zones(a0):  # (and one zone record: _check_batch has held the two fields equal)
+        sweep.set_zones(parse_zones(a0.zones))
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -893,7 +983,7 @@ def run_mpc_batch(arg_list, device: int = None, return_details: bool = False):
             shape = dict(shape, **_basis_settings(arg_list[0]))
         shape = dict(shape, **_delay_settings(arg_list[0]), **_demo_settings(arg_list[0]), **_sigma_settings(arg_list[0]),
                      **_objective_settings(arg_list[0]), **_weighting_settings(arg_list[0]), **_elites_settings(arg_list[0]),
-                     **_togo_settings(arg_list[0]))
+                     **_togo_settings(arg_list[0]), **_zones_settings(arg_list[0]))
         windows = {"demo_windows": ep["demo_windows"]} if "demo_windows" in ep else {}  # (one table: every episode's)
         pick = (lambda k: {f: ep[f][k] for f in ("pick", "elite_log", "togo") if f in ep})
         return rewards, [dict({f: ep[f][k] for f in _logs(ep)}, **windows, **pick(k), seconds=ep["seconds"], state_init=states[k], key=keys[k], dt=env.dt,
@@ -912,7 +1002,7 @@ def _peek_batch_records(sweep, a0: MpcArgs, ep: dict) -> None:
 def _logs(ep: dict) -> tuple:
     """The episode's logs: the four every episode has, the predicted states of one with a delay record, the distances from
     the clip of one with a demo record, the ticks' sigmas of a path-integral one."""
-    return _LOGS + tuple(k for k in ("predicted", "track_err", "sigmas") if k in ep)
+    return _LOGS + tuple(k for k in ("predicted", "track_err", "sigmas", "zone_pen", "zone_clear") if k in ep)
 
 
 def _save(args: MpcArgs, ep: dict) -> None:
@@ -949,7 +1039,8 @@ def run_mpc(args: MpcArgs, device: int = None, return_details: bool = False):
         if _has_basis(args):
             shape = dict(shape, **_basis_settings(args))
         shape = dict(shape, **_delay_settings(args), **_demo_settings(args), **_sigma_settings(args), **_objective_settings(args),
-                     **_weighting_settings(args), **_adapt_settings(args), **_elites_settings(args), **_togo_settings(args))
+                     **_weighting_settings(args), **_adapt_settings(args), **_elites_settings(args), **_togo_settings(args),
+                     **_zones_settings(args))
         return reward, dict(ep, state_init=state_init, key=key, dt=env.dt, **_plant_settings(args), **ens, **shape)
     return reward
 
@@ -1036,6 +1127,8 @@ def _main(argv=None) -> dict:
         res.update(_elites_settings(args), **_elites_log(elog, args.Ndiffuse, K))
     if tlog is not None:
         res.update(_togo_settings(args), togo_groups=[int(x) for x in tlog["starts"]])
+    if "zone_pen" in ep:  # (the executed control steps' penalties and keep-out clearances)
+        res.update(_zones_settings(args), **zones_report(ep))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -1079,6 +1172,8 @@ def _main_online(args: MpcArgs) -> dict:
         res.update(_elites_settings(args), **_elites_log(ep["elite_log"], args.Ndiffuse, args.warm_steps))
     if "togo" in ep:
         res.update(_togo_settings(args), togo_groups=[int(x) for x in ep["togo"]["starts"]])
+    if "zone_pen" in ep:
+        res.update(_zones_settings(args), **zones_report(ep))
     if not args.not_render:
         _save(args, ep)
     print(json.dumps(res), flush=True)
@@ -1135,6 +1230,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
             plan.set_elites(**_elites_of(a0))
         if _has_togo(a0):
             plan.set_togo(**_togo_of(a0))
+        if _has_zones(a0):
+            plan.set_zones(parse_zones(a0.zones))
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
@@ -1174,6 +1271,8 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
         res.update(_togo_settings(a0), togo_groups=[int(x) for x in ep["togo"][0]["starts"]])
     if _has_demo(a0):
         res.update(_demo_settings(a0), track_err_mean=float(ep["track_err"].mean()))
+    if "zone_pen" in ep:  # (over all episodes)
+        res.update(_zones_settings(a0), **zones_report(ep))
     if not a0.not_render:
         _save(a0, ep)
     print(json.dumps(res), flush=True)
