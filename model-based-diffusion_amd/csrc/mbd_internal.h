@@ -1,7 +1,9 @@
 // mbd_internal.h — what the translation units of libmbd_hip.so's host side share (NOT part of the boundary: the C ABI is
 // include/mbd_hip.h): the owners of runtime resources, the env handle, error reporting, the test levers, what plans and
-// sweeps do alike, and the functions one unit defines for the others.  (A handle only its own unit uses is defined there: the
-// adapt, elite and to-go records of a plan, in the other records' form, are mbd_plan.hip's.)
+// sweeps do alike — every record both handles take, once: the struct, its check_*, set and peek; the launches of a record whose
+// single and batch kernels live in different units (elites, to-go) are free functions of each unit over the shared struct — and
+// the functions one unit defines for the others.  (A handle only its own unit uses is defined there: the adapt record of a plan,
+// in the other records' form, is mbd_plan.hip's.)
 // Units: mbd_env.hip (library, levers, envs, the rollout launch), mbd_plan.hip (plans: one reverse-diffusion step and the
 // loops over it, every record's members), mbd_sweep.hip (sweeps: several plans per launch), mbd_exchange.hip (the in-library
 // exchange), mbd_debug_math.hip (mbd_math.h over arrays); mbd_pk2.hip, mbd_planar.hip and mbd_hot3d.hip hold rollout
@@ -32,6 +34,9 @@
 #include "mbd_step_kernels.h"
 
 using namespace mbd;
+
+// a function or member that crosses units but not the library's boundary: it stays out of the library's symbol list
+#define MBD_HIDDEN __attribute__((visibility("hidden")))
 
 // error reporting (mbd_env.hip): sets the thread-local message of mbd_last_error() and returns `code`
 int fail(int code, const char* fmt, ...);
@@ -401,6 +406,32 @@ int check_mpc_sigma(const mbd_mpc_sigma* rec, int update_method);
 int check_noise_shape(const mbd_noise_shape* rec, int Hsample, int action_size);
 // the refusals of a noise-basis record (include/mbd_hip.h mbd_noise_basis) of a handle with Hsample rows, likewise
 int check_noise_basis(const mbd_noise_basis* rec, int Hsample);
+// The noise shape and the noise basis of a plan or a sweep (mbd_*_set_noise_shape, mbd_*_set_noise_basis) as the handle keeps them:
+// the tables g [HNu] and W [Hsample][knots] on the device and when each is in force; d_knot_z: the scratch z knot_noise_kernel fills
+// in front of shift_kernel where candidates are materialised (the caller says how many elements).  The samplers take the tables as
+// pointers, nullptr for a flat step.  shape_always: every step outside the warm ticks of an episode (the phase calls, a run, tick 0);
+// shape_warm: the steps of the ticks t >= 1, where either mode is in force; spec: with the basis beside it, each under its own
+// `when` — the caller's tables only (a plan's adapt record stands its own table in: mbd_plan.hip noise_spec).  set_shape, set_basis:
+// behind the handle's NULL and session checks and check_noise_*, (nullptr clears) — they wait for the device, since a step in flight,
+// or normals being prepared ahead, may still read the previous table.
+struct NoiseRec {
+  bool has_shape = false, has_basis = false;
+  int shape_when = MBD_NOISE_ALWAYS, basis_when = MBD_NOISE_ALWAYS, knots = 0;
+  DevBuf<float> d_shape, d_basis, d_knot_z;
+  const float* shape_always() const { return has_shape && shape_when == MBD_NOISE_ALWAYS ? d_shape.get() : nullptr; }
+  const float* shape_warm() const { return has_shape ? d_shape.get() : nullptr; }
+  NoiseSpec spec(bool warm_tick) const {
+    NoiseSpec ns;
+    ns.g = warm_tick ? shape_warm() : shape_always();
+    if (has_basis && (warm_tick || basis_when == MBD_NOISE_ALWAYS)) {
+      ns.W = d_basis.get();
+      ns.knots = knots;
+    }
+    return ns;
+  }
+  MBD_HIDDEN int set_shape(const mbd_noise_shape* rec, int HNu, int device);
+  MBD_HIDDEN int set_basis(const mbd_noise_basis* rec, int Hsample, size_t knot_z_elems, int device);
+};
 // The delay record of a plan or a sweep (include/mbd_hip.h mbd_mpc_delay) as the handle keeps it — rows0 copied to the host, it
 // goes to the device when an episode starts — with what the two handles do alike: the refusals the record alone decides, in the
 // header's order, each naming the field (check_mpc_delay: host arithmetic, before any device access), the set call behind
@@ -573,6 +604,56 @@ struct WeightingRec {
 int check_weighting(const mbd_weighting* rec);
 // the refusal of a record beside a to-go record (mbd_plan.hip; who: how the refused record's messages begin, handle: "plan" / "sweep")
 int refuse_beside_togo(const char* who, const char* handle = "plan");
+// The elite record of a plan or of all the plans of a sweep (include/mbd_hip.h mbd_elites) as the handle keeps it, with what the two
+// handles do alike.  The state of P plans (a plan: P = 1): the elites' rows E [P][rows][HNu], their returns R and source indices src
+// [P][rows] (rows = max(n, 1)), the device words count [P], and the three device logs [P][log_cap], rings of log_cap entries (a
+// scratch record of the mbd_debug_* entries: 1).  count never comes back to the host inside a loop: every kernel loads it.  steps:
+// plan k's selections since its log began — host bookkeeping PER PLAN: in a sweep session's mixed tick the episodes that idle make no
+// selection, and their logs stay a single session's.  check_elites: the refusals the record alone decides against the handle's
+// Nsample, update_method and enable_demo, in the header's order, each naming the field — host arithmetic, before any device access.
+// set: behind the handle's refusals (nullptr clears); waits for the device, makes room, and leaves the launch that empties the
+// elites to the caller.  The launches a step or a tick makes are each unit's own, over this struct: the single and the batch
+// kernels live in different units (mbd_plan.hip elite_table / elite_inject / elite_select; mbd_sweep.hip likewise, with mask and strides).
+struct EliteRec {
+  bool has = false;
+  int n = 0, nominal = 0, carry = 0, rows = 1, P = 1;
+  int log_cap = kLogCap;
+  long long steps[MBD_SWEEP_MAX_PLANS] = {};
+  DevBuf<float> d_E, d_R, d_log_top;
+  DevBuf<int> d_src, d_count, d_log_count, d_log_kept;
+  void restart() { for (long long& c : steps) c = 0; }  // (the logs begin)
+  void layout(int n_elites, int nominal_, int carry_, int P_) {
+    n = n_elites; nominal = nominal_; carry = carry_; P = P_;
+    rows = n > 0 ? n : 1;
+  }
+  MBD_HIDDEN int set(const mbd_elites* rec, int P_, int HNu, int device);
+  // the scratch record of the mbd_debug_* entries: every buffer with all bits set, logs one entry long, count_in [P_] in the count
+  // words and plan k's first count_in[k] rows from E_in [P_][rows][HNu] (NULL: none)
+  MBD_HIDDEN int scratch(int n_elites, int nominal_, int P_, int HNu, const float* E_in, const int32_t* count_in);
+  // HOST plan k's elites, their count and the most recent min(steps, capacity, log_cap) log entries, oldest first
+  MBD_HIDDEN int peek(const mbd_env* env, int k, int HNu, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
+                      int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out, const char* what) const;
+};
+MBD_HIDDEN int check_elites(const mbd_elites* rec, int Nsample, int update_method, int enable_demo);
+// The to-go record of a plan or of all the plans of a sweep (include/mbd_hip.h mbd_togo) as the handle keeps it: the record, the
+// layout it gives at the handle's Hsample — G groups, group j's first row starts[j] = j block —, and the last step's returns and
+// weights R, W [P][G][N] (row 0 of a plan's W is never written: group 0's weights are the plan's d_weights).  check_togo: the refusals
+// the record alone decides against the handle's Hsample, Nsample, update_method and enable_demo, likewise.  set: behind the handle's
+// refusals (nullptr clears); R and W read as all-ones bits until a step has run.  The step's two launches are each unit's own
+// (togo_launch), and set stepped.
+struct TogoRec {
+  bool has = false;
+  int block = 0, min_tail = 0, G = 0;
+  bool stepped = false;  // a step of the record has run: d_weights are group 0's
+  std::vector<int32_t> starts;
+  DevBuf<float> d_R, d_W;
+  MBD_HIDDEN void layout(int block_, int min_tail_, int H);  // the layout a record gives at horizon H
+  MBD_HIDDEN int set(const mbd_togo* rec, int P, int H, int N, int device);
+  // HOST starts [G], plan k's R and W [G][N]; d_weights: the handle's own [P][N], group 0's once a step of the record has written them
+  MBD_HIDDEN int peek(const mbd_env* env, int k, int N, const float* d_weights, int32_t* starts_out, float* R_out, float* W_out,
+                      int32_t* n_groups_out, const char* what) const;
+};
+MBD_HIDDEN int check_togo(const mbd_togo* rec, int Hsample, int Nsample, int update_method, int enable_demo);
 // The pick record of a plan or a sweep (include/mbd_hip.h mbd_mpc_pick) as the handle keeps it, with what the two handles do alike.
 // check_mpc_pick: the refusals the record alone decides, each naming the field, before any device access.  set: behind the handle's
 // NULL, session, enable_demo and ensemble checks (nullptr clears); makes room for P plans' slots [P][3][HNu], their returns and

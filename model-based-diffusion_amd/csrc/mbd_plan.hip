@@ -139,11 +139,9 @@ struct StepCand {
   const float* ybar_i;
 };
 
-// The plan-only records, in the form of mbd_internal.h's: set behind the handle's refusals (nullptr clears), the launches a step or
+// The plan-only record, in the form of mbd_internal.h's: set behind the handle's refusals (nullptr clears), the launches a step or
 // a tick makes — each returns at once without a record, and the mbd_debug_* entries run the same members on a scratch record —, and
-// peek.  All zero: no record (a zeroed stand-in handle has none).  MBD_HIDDEN: a member function no other unit calls stays out of
-// the library's symbol list.
-#define MBD_HIDDEN __attribute__((visibility("hidden")))
+// peek.  All zero: no record (a zeroed stand-in handle has none).
 // The adapt record (include/mbd_hip.h mbd_adapt): the rule, the table a and G = a * g [HNu] on the device — G is what the samplers
 // take as their shape while the record is in force (noise_spec) —, the scratch the update's two kernels hand var and s through, and
 // the device log, a ring of kLogCap entries (count: steps since the log began).  g_cur: the caller's shape G was last formed under
@@ -168,51 +166,6 @@ struct AdaptRec {
   // HOST a_out [HNu] and the most recent min(count, capacity, kLogCap) log entries, oldest first
   MBD_HIDDEN int peek(const mbd_env* env, int HNu, float* a_out, float* ratio_out, int32_t* skipped_out, int capacity, int* count_out) const;
 };
-
-// The elite record (include/mbd_hip.h mbd_elites): the record, the elites' rows E [n][HNu], their returns R and source indices src
-// [n], the device word `count`, and the device log, a ring of kLogCap entries (steps: selections since the log began).  count never
-// comes back to the host inside a loop: every kernel loads it.
-struct EliteRec {
-  bool has = false;
-  int n = 0, nominal = 0, carry = 0;
-  long long steps = 0;
-  DevBuf<float> d_E, d_R, d_log_top;
-  DevBuf<int> d_src, d_count, d_log_count, d_log_kept;
-  // no elites afterwards (one launch on s, waited for)
-  MBD_HIDDEN int set(const mbd_elites* rec, int HNu, const mbd_env* env, hipStream_t s);
-  // The elites at the start of a run or a tick: shift < 0: count = 0, otherwise the present rows shifted `shift` elements forward.
-  // ONE launch, a workgroup per row.
-  MBD_HIDDEN int table(int shift, int HNu, hipStream_t s);
-  // phase 1 of a step, behind the launch that made the step's normals or candidates, in front of the rollout: c.cand's first rows
-  // are rewritten; g is the shape the step's sampler was handed.  ONE launch.
-  MBD_HIDDEN int inject(const StepCand& c, const float* g, hipStream_t s);
-  // phase 2 of a step, behind the step's update kernel (and an adapt record's launches): the selection over the rewards the score
-  // read, and the log entry.  ONE launch.
-  MBD_HIDDEN int select(const float* d_rews, const StepCand& c, hipStream_t s);
-  // HOST the elites, their count and the most recent min(steps, capacity, kLogCap) log entries, oldest first
-  MBD_HIDDEN int peek(const mbd_env* env, int HNu, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
-                      int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out) const;
-};
-
-// The to-go record (include/mbd_hip.h mbd_togo): the record, the layout it gives at the plan's Hsample — G groups, group j's first
-// row starts[j] = j block —, and the last step's returns and weights R, W [G][N] (row 0 of W is never written: group 0's weights are
-// the plan's d_weights).
-struct TogoRec {
-  bool has = false;
-  int block = 0, min_tail = 0, G = 0;
-  bool stepped = false;  // a step of the record has run: d_weights are group 0's
-  std::vector<int32_t> starts;
-  DevBuf<float> d_R, d_W;
-  MBD_HIDDEN int set(const mbd_togo* rec, int H, int N, const mbd_env* env);
-  // the layout a record gives at horizon H
-  MBD_HIDDEN void layout(int block_, int min_tail_, int H);
-  // A step's two launches, where the fused score and weighted mean stand without a record: A carries everything but the layout and
-  // the record's buffers.  Groups 0 .. G - 2 hold block Nu elements in tpg tiles each, the last group the rest.
-  MBD_HIDDEN int launch(const float* d_rewss, TogoUpdate A, hipStream_t s);
-  // HOST starts [G], R and W [G][N]; d_weights: the plan's own [N], group 0's once a step of the record has written them
-  MBD_HIDDEN int peek(const mbd_env* env, int N, const float* d_weights, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out) const;
-};
-#undef MBD_HIDDEN
 
 struct mbd_plan {
   mbd_env* env = nullptr;
@@ -265,16 +218,9 @@ struct mbd_plan {
   mbd_ensemble ens_rec{};
   bool has_ens = false, ens_stepped = false;
   DevBuf<float> d_ens_rews, d_ens_rewss, d_ens_comb;
-  // the noise shape (mbd_plan_set_noise_shape): the table g [HNu] on the device and when it is in force.  The samplers take
-  // it as a pointer, nullptr for a flat step (shape_always / shape_warm below decide per loop)
-  DevBuf<float> d_shape;
-  bool has_shape = false;
-  int shape_when = MBD_NOISE_ALWAYS;
-  // the noise basis (mbd_plan_set_noise_basis): the table W [Hsample][basis_knots] on the device and when it is in force; and,
-  // for materialised plans, the scratch z [N][HNu] knot_noise_kernel fills in front of shift_kernel
-  DevBuf<float> d_basis, d_knot_z;
-  bool has_basis = false;
-  int basis_knots = 0, basis_when = MBD_NOISE_ALWAYS;
+  // the noise shape (mbd_plan_set_noise_shape) and the noise basis (mbd_plan_set_noise_basis) with their tables; d_knot_z [N][HNu]
+  // for materialised plans only
+  NoiseRec noise;
   // the objective record (mbd_plan_set_objective) with its tables, the previous action and the last step's ret and cost
   ObjectiveRec obj;
   // the weighting record (mbd_plan_set_weighting) with the device log of its score steps
@@ -440,28 +386,14 @@ static int ensure_aux(mbd_plan* p) {
   return MBD_OK;
 }
 
-// The noise shape of the plan's steps (include/mbd_hip.h mbd_noise_shape), as the pointer the samplers take — nullptr: flat.
-// shape_always: every step outside the warm ticks of an episode (the phase calls, mbd_plan_run, tick 0); shape_warm: the
-// steps of the ticks t >= 1 of mbd_plan_run_mpc, where either mode is in force.
-static const float* shape_always(const mbd_plan* p) {
-  return p->has_shape && p->shape_when == MBD_NOISE_ALWAYS ? p->d_shape.get() : nullptr;
-}
-static const float* shape_warm(const mbd_plan* p) { return p->has_shape ? p->d_shape.get() : nullptr; }
-// ... and with the noise basis (mbd_noise_basis) beside it, each under its own `when`: what a step's normals are made under
+// What a step's normals are made under (warm_tick: a step of the ticks t >= 1 of mbd_plan_run_mpc): the plan's noise record's, and
+// under an adapt record the samplers draw under G = a * g: the record's table stands where the caller's shape stood, in every
+// step — the launches that rewrite it are handed the caller's shape in force (AdaptRec::table)
 static NoiseSpec noise_spec(const mbd_plan* p, bool warm_tick) {
-  NoiseSpec ns;
-  ns.g = warm_tick ? shape_warm(p) : shape_always(p);
-  // under an adapt record the samplers draw under G = a * g: the record's table stands where the caller's shape stood, in every
-  // step — the launches that rewrite it are handed the caller's shape in force (AdaptRec::table)
+  NoiseSpec ns = p->noise.spec(warm_tick);
   if (p->adapt.has) ns.g = p->adapt.d_G.get();
-  if (p->has_basis && (warm_tick || p->basis_when == MBD_NOISE_ALWAYS)) {
-    ns.W = p->d_basis.get();
-    ns.knots = p->basis_knots;
-  }
   return ns;
 }
-static NoiseSpec noise_always(const mbd_plan* p) { return noise_spec(p, false); }
-static NoiseSpec noise_warm(const mbd_plan* p) { return noise_spec(p, true); }
 
 // Whether a step's candidates depend on the previous step's result — an adapt record's table, an elite record's rows —, so that
 // nothing about them can be prepared ahead or reused: the noise ring declares nothing, reuses nothing, and the loops do not hold the
@@ -494,32 +426,38 @@ int AdaptRec::update(const float* d_w, const StepCand& c, hipStream_t s) {
   return MBD_OK;
 }
 
-int EliteRec::table(int shift, int HNu, hipStream_t s) {
-  if (!has) return MBD_OK;
-  hipLaunchKernelGGL(elite_shift_kernel, dim3(n > 0 ? n : 1), dim3(kEliteThreads), 0, s, d_E.get(), d_count.get(), HNu, shift);
+// The elite record's launches for a plan (mbd_internal.h EliteRec, P = 1).  elite_table: the elites at the start of a run or a tick —
+// shift < 0: count = 0, otherwise the present rows shifted `shift` elements forward.  ONE launch, a workgroup per row.
+static int elite_table(EliteRec& L, int shift, int HNu, hipStream_t s) {
+  if (!L.has) return MBD_OK;
+  hipLaunchKernelGGL(elite_shift_kernel, dim3(L.rows), dim3(kEliteThreads), 0, s, L.d_E.get(), L.d_count.get(), HNu, shift);
   HIP_TRY(hipGetLastError());
   return MBD_OK;
 }
 
-int EliteRec::inject(const StepCand& c, const float* g, hipStream_t s) {
-  if (!has) return MBD_OK;
+// phase 1 of a step, behind the launch that made the step's normals or candidates, in front of the rollout: c.cand's first rows
+// are rewritten; g is the shape the step's sampler was handed.  ONE launch.
+static int elite_inject(EliteRec& L, const StepCand& c, const float* g, hipStream_t s) {
+  if (!L.has) return MBD_OK;
   EliteInject A{};
   A.cand = const_cast<float*>(c.cand);  // (the one launch that writes a step's candidates behind their sampler)
   A.HNu = c.HNu; A.ybar_i = c.ybar_i; A.lazy = c.lazy; A.sigma = c.sigma; A.g = g;
-  A.n_elites = n; A.nominal = nominal; A.E = d_E; A.count = d_count;
-  const long long total = (long long)(nominal + n) * c.HNu;
+  A.n_elites = L.n; A.nominal = L.nominal; A.E = L.d_E; A.count = L.d_count;
+  const long long total = (long long)(L.nominal + L.n) * c.HNu;
   hipLaunchKernelGGL(elite_inject_kernel, dim3((unsigned)((total + kEliteThreads - 1) / kEliteThreads)), dim3(kEliteThreads), 0, s, A);
   HIP_TRY(hipGetLastError());
   return MBD_OK;
 }
 
-int EliteRec::select(const float* d_rews, const StepCand& c, hipStream_t s) {
-  if (!has) return MBD_OK;
-  const long long slot = ring_slot(steps, kLogCap);
+// phase 2 of a step, behind the step's update kernel (and an adapt record's launches): the selection over the rewards the score
+// read, and the log entry.  ONE launch.
+static int elite_select(EliteRec& L, const float* d_rews, const StepCand& c, hipStream_t s) {
+  if (!L.has) return MBD_OK;
+  const long long slot = ring_slot(L.steps[0], L.log_cap);
   EliteSelect A{};
   A.rews = d_rews; A.N = c.N; A.HNu = c.HNu; A.cand = c.cand; A.lazy = c.lazy; A.sigma = c.sigma; A.ybar_i = c.ybar_i;
-  A.n_elites = n; A.nominal = nominal; A.E = d_E; A.R = d_R; A.src = d_src; A.count = d_count;
-  A.log_count = d_log_count.get() + slot; A.log_kept = d_log_kept.get() + slot; A.log_top = d_log_top.get() + slot;
+  A.n_elites = L.n; A.nominal = L.nominal; A.E = L.d_E; A.R = L.d_R; A.src = L.d_src; A.count = L.d_count;
+  A.log_count = L.d_log_count.get() + slot; A.log_kept = L.d_log_kept.get() + slot; A.log_top = L.d_log_top.get() + slot;
   hipLaunchKernelGGL(elite_select_kernel, dim3(1), dim3(kScoreThreads), 0, s, A);
   HIP_TRY(hipGetLastError());
   return MBD_OK;
@@ -532,16 +470,20 @@ void TogoRec::layout(int block_, int min_tail_, int H) {
   for (int j = 0; j < G; ++j) starts[j] = togo_start(j, block);
 }
 
-int TogoRec::launch(const float* d_rewss, TogoUpdate A, hipStream_t s) {
-  const TogoReturns Rt{A.rews, d_rewss, d_R.get(), A.N, A.H, block, G};
+// A step's two launches of a plan's to-go record, where the fused score and weighted mean stand without a record: A carries everything
+// but the layout and the record's buffers.  Groups 0 .. G - 2 hold block Nu elements in tpg tiles each, the last group the rest.
+static int togo_launch(TogoRec& L, const float* d_rewss, TogoUpdate A, hipStream_t s) {
+  const int block = L.block, G = L.G;
+  const TogoReturns Rt{A.rews, d_rewss, L.d_R.get(), A.N, A.H, block, G};
   hipLaunchKernelGGL(togo_returns_kernel, dim3((A.N + kTogoThreads - 1) / kTogoThreads), dim3(kTogoThreads), 0, s, Rt);
   HIP_TRY(hipGetLastError());
   const long long last = (long long)(A.H - togo_start(G - 1, block)) * A.Nu;
-  A.R = d_R; A.W = d_W; A.G = G; A.block = block;
+  A.R = L.d_R; A.W = L.d_W; A.G = G; A.block = block;
   A.tpg = G > 1 ? (int)(((long long)block * A.Nu + kWmE - 1) / kWmE) : 1;
   A.T = (G - 1) * A.tpg + (int)((last + kWmE - 1) / kWmE);
   hipLaunchKernelGGL(togo_update_kernel, dim3(A.T), dim3(kWmE * kWmG), sizeof(float) * (size_t)A.N, s, A);
   HIP_TRY(hipGetLastError());
+  L.stepped = true;
   return MBD_OK;
 }
 
@@ -579,7 +521,7 @@ static int declare_next_key(mbd_plan* p, const uint32_t key_next[2], const Noise
 extern "C" int mbd_plan_prefetch_noise(mbd_plan* p, const uint32_t key_next[2], void* stream_) {
   (void)stream_;
   if (!p || !key_next) return fail(MBD_ERR_INVALID, "NULL argument");
-  return declare_next_key(p, key_next, noise_always(p));
+  return declare_next_key(p, key_next, noise_spec(p, false));
 }
 
 // A plan's phases depend on each other through its buffers (the normals one step's launch prepares are read by the
@@ -628,8 +570,8 @@ static int sample_candidates(mbd_plan* p, int i, const uint32_t key_sample[2], c
   const uint64_t total = (uint64_t)N * HNu;
   const float* g = ns.g;
   if (ns.W) {
-    launch_noise(p, s, key_sample, p->d_knot_z, ns);
-    hipLaunchKernelGGL(shift_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)p->d_knot_z, HNu, 0ull,
+    launch_noise(p, s, key_sample, p->noise.d_knot_z, ns);
+    hipLaunchKernelGGL(shift_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)p->noise.d_knot_z, HNu, 0ull,
                        (unsigned long long)total, p->sigmas[i],
                        c.update_method > 0 ? (const float*)p->d_sigma : (const float*)nullptr, d_Ybar_i, p->d_Y0s.get());
     HIP_TRY(hipGetLastError());
@@ -752,7 +694,7 @@ static int plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sample[2],
   const float* d_cand = p->lazy ? ring.eps[ring.cur] : p->d_Y0s;
   if (p->elite.has) {
     if (p->lazy) ring.valid[ring.cur] = false;
-    MBD_TRY(p->elite.inject(StepCand{d_cand, N, HNu, p->lazy ? 1 : 0, p->sigmas[i], nullptr, d_Ybar_i}, ns.g, s));
+    MBD_TRY(elite_inject(p->elite, StepCand{d_cand, N, HNu, p->lazy ? 1 : 0, p->sigmas[i], nullptr, d_Ybar_i}, ns.g, s));
   }
   // A2/A3: rollout of the local shard
   MBD_TRY(p->timing.begin(s));
@@ -804,7 +746,7 @@ extern "C" int mbd_plan_sample_rollout(mbd_plan* p, int i, const uint32_t key_sa
                                        float* d_rews_local, float* d_logpd_local, void* stream_) {
   if (p) NO_SESSION(p, "sample_rollout");
   return plan_sample_rollout(p, i, key_sample, d_Ybar_i, d_rews_local, d_logpd_local, (hipStream_t)stream_,
-                             p ? p->d_state0.get() : nullptr, p ? noise_always(p) : NoiseSpec{});
+                             p ? p->d_state0.get() : nullptr, p ? noise_spec(p, false) : NoiseSpec{});
 }
 
 // phase 2 of a step; rew_xref: the demo's reward level in the blend — the env's (mbd_plan_score_update), or an episode's
@@ -863,8 +805,7 @@ static int plan_score_update(mbd_plan* p, int i, const float* d_Ybar_i, const fl
       A.ybar_im1 = d_Ybar_im1; A.ybar_keep = p->d_ybar_keep; A.N = N; A.H = c.Hsample; A.Nu = p->Nu; A.temp = c.temp_sample;
       A.std_guard = c.update_method == 0 ? 1 : 0; A.alpha_i = p->alphas[i]; A.alpha_bar_i = p->alphas_bar[i];
       A.alpha_bar_im1 = p->alphas_bar[i - 1]; A.literal = lit; A.lazy = lazy; A.sigma = sigma_i;
-      MBD_TRY(p->togo.launch(p->d_rewss, A, s));
-      p->togo.stepped = true;
+      MBD_TRY(togo_launch(p->togo, p->d_rewss, A, s));
     } else if (fused_score) {
       // XCD pinning (mbd_step_kernels.h pinned_tile): the T tiles on the fewest XCDs X in {1, 2, 4, 8} that give every tile
       // a CU of its own (32 per XCD) and keep an XCD's share of the candidates' rows within its 4 MB L2; the launch is
@@ -905,7 +846,7 @@ static int plan_score_update(mbd_plan* p, int i, const float* d_Ybar_i, const fl
   if (p->adapt.has) MBD_TRY(p->adapt.update(p->d_weights, sc, s));
   // The elite record: ONE launch in the same place takes the step's best candidates over — from the rewards the score read, the
   // candidates (eps[cur]: in front of the ring's mark as well) and Ybar_i
-  if (p->elite.has) MBD_TRY(p->elite.select(d_rews_all, sc, s));
+  if (p->elite.has) MBD_TRY(elite_select(p->elite, d_rews_all, sc, s));
   if (p->lazy) {
     p->peek_ybar = p->d_ybar_keep;
     MBD_TRY(p->ring.mark_wmean(s, p->aux != nullptr));
@@ -958,24 +899,28 @@ int check_noise_shape(const mbd_noise_shape* rec, int Hsample, int action_size) 
   return MBD_OK;
 }
 
+int NoiseRec::set_shape(const mbd_noise_shape* rec, int HNu, int device) {
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight, or normals being prepared ahead, may still read the previous table)
+  has_shape = false;
+  if (!rec) return MBD_OK;
+  HIP_TRY(d_shape.grow(HNu));
+  HIP_TRY(hipMemcpy(d_shape, rec->scale, sizeof(float) * HNu, hipMemcpyHostToDevice));
+  shape_when = rec->when;
+  has_shape = true;
+  return MBD_OK;
+}
+
 extern "C" int mbd_plan_set_noise_shape(mbd_plan* p, const mbd_noise_shape* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
   NO_SESSION(p, "set_noise_shape");
   if (rec) MBD_TRY(check_noise_shape(rec, p->cfg.Hsample, p->Nu));
-  HIP_TRY(hipSetDevice(p->env->device));
-  HIP_TRY(hipDeviceSynchronize());  // (a step in flight, or normals being prepared ahead, may still read the previous table)
   // Normals prepared ahead were scaled under the previous setting, and the table behind the pointer that tags them is about to
   // change: the ring forgets them and the declared key, so the next step generates its own under the new setting.
   p->ring.forget();
-  p->has_shape = false;
-  if (rec) {
-    HIP_TRY(p->d_shape.grow(p->HNu));
-    HIP_TRY(hipMemcpy(p->d_shape, rec->scale, sizeof(float) * p->HNu, hipMemcpyHostToDevice));
-    p->shape_when = rec->when;
-    p->has_shape = true;
-  }
+  MBD_TRY(p->noise.set_shape(rec, p->HNu, p->env->device));
   // an adapt record's G = a * g is formed again under the shape now in force outside warm ticks (a run and a tick form their own)
-  MBD_TRY(p->adapt.table(0, shape_always(p), p->HNu, p->stream));
+  MBD_TRY(p->adapt.table(0, p->noise.shape_always(), p->HNu, p->stream));
   if (p->adapt.has) HIP_TRY(hipStreamSynchronize(p->stream));
   return MBD_OK;
 }
@@ -1015,24 +960,27 @@ int check_noise_basis(const mbd_noise_basis* rec, int Hsample) {
   return MBD_OK;
 }
 
+int NoiseRec::set_basis(const mbd_noise_basis* rec, int Hsample, size_t knot_z_elems, int device) {
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());  // (as set_shape)
+  has_basis = false;
+  if (!rec) return MBD_OK;
+  HIP_TRY(d_basis.grow((size_t)Hsample * MBD_MAX_KNOTS));
+  HIP_TRY(d_knot_z.grow(knot_z_elems));
+  HIP_TRY(hipMemcpy(d_basis, rec->basis, sizeof(float) * (size_t)Hsample * (size_t)rec->n_knots, hipMemcpyHostToDevice));
+  knots = rec->n_knots;
+  basis_when = rec->when;
+  has_basis = true;
+  return MBD_OK;
+}
+
 extern "C" int mbd_plan_set_noise_basis(mbd_plan* p, const mbd_noise_basis* rec) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
   NO_SESSION(p, "set_noise_basis");
   if (rec) MBD_TRY(check_noise_basis(rec, p->cfg.Hsample));
-  HIP_TRY(hipSetDevice(p->env->device));
-  HIP_TRY(hipDeviceSynchronize());  // (a step in flight, or normals being prepared ahead, may still read the previous table)
-  // as mbd_plan_set_noise_shape: nothing prepared under the previous setting survives
-  p->ring.forget();
-  p->has_basis = false;
-  if (!rec) return MBD_OK;
-  const size_t n = (size_t)p->cfg.Hsample * (size_t)rec->n_knots;
-  HIP_TRY(p->d_basis.grow((size_t)p->cfg.Hsample * MBD_MAX_KNOTS));
-  if (!p->lazy) HIP_TRY(p->d_knot_z.grow((size_t)p->cfg.Nsample * p->HNu));
-  HIP_TRY(hipMemcpy(p->d_basis, rec->basis, sizeof(float) * n, hipMemcpyHostToDevice));
-  p->basis_knots = rec->n_knots;
-  p->basis_when = rec->when;
-  p->has_basis = true;
-  return MBD_OK;
+  p->ring.forget();  // (as mbd_plan_set_noise_shape: nothing prepared under the previous setting survives)
+  // (materialised plans alone run knot_noise_kernel into the scratch z [N][HNu])
+  return p->noise.set_basis(rec, p->cfg.Hsample, p->lazy ? 0 : (size_t)p->cfg.Nsample * p->HNu, p->env->device);
 }
 
 // include/mbd_hip_debug.h: knot_noise_kernel alone, on `blocks` workgroups of kKnotThreads threads
@@ -1077,7 +1025,7 @@ static int plan_keep_in_step(mbd_plan* p) {
   NoiseRing& ring = p->ring;
   if (!p->lazy || !ring.progress || ring.seq == 0 || p->cfg.shares_device != 0 || follows_result(p)) return MBD_OK;
   // (a plan with a noise basis prepares its normals on the second stream whatever the launch could take)
-  if (!p->has_basis && rollout_takes_noise(plan_rollout_choice(p), p->cfg.prng_impl, p->cfg.Nsample, p->HNu)) return MBD_OK;
+  if (!p->noise.has_basis && rollout_takes_noise(plan_rollout_choice(p), p->cfg.prng_impl, p->cfg.Nsample, p->HNu)) return MBD_OK;
   // (a stream slower than the limit: the loop stops keeping step and the step orders the two streams with an event instead —
   // NoiseRing::mark_last_reader's own bounded wait, then a mark on the step's stream for the aux stream)
   ring.kept_in_step = progress_wait(ring.progress, ring.seq, kInStepWaitMs, 20);
@@ -1121,7 +1069,7 @@ extern "C" int mbd_plan_reverse_once(mbd_plan* p, int i, uint32_t key_inout[2], 
   hipStream_t s = (hipStream_t)stream_;
   // the update is not in place on the device (wmean reads Ybar_i while writing Ybar_{i-1})
   p->wt.begin();
-  MBD_TRY(reverse_once_impl(p, p->d_state0, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s, noise_always(p)));
+  MBD_TRY(reverse_once_impl(p, p->d_state0, i, key_inout, d_Ybar, p->d_Ybar, d_rew_mean, s, noise_spec(p, false)));
   HIP_TRY(hipMemcpyAsync(d_Ybar, p->d_Ybar, sizeof(float) * p->HNu, hipMemcpyDeviceToDevice, s));
   return MBD_OK;
 }
@@ -1140,17 +1088,17 @@ extern "C" int mbd_plan_run(mbd_plan* p, const uint32_t key[2], float* mu_0ts_ou
     HIP_TRY(hipMemcpy(p->d_sigma, &one, sizeof(float), hipMemcpyHostToDevice));
   }
   HIP_TRY(hipMemsetAsync(cur, 0, sizeof(float) * HNu, s));
-  MBD_TRY(p->adapt.table(-1, shape_always(p), HNu, s));  // (an adapt record: a = ones, and its log begins)
+  MBD_TRY(p->adapt.table(-1, p->noise.shape_always(), HNu, s));  // (an adapt record: a = ones, and its log begins)
   p->adapt.count = 0;
-  MBD_TRY(p->elite.table(-1, HNu, s));  // (an elite record: no elites, and its log begins)
-  p->elite.steps = 0;
+  MBD_TRY(elite_table(p->elite, -1, HNu, s));  // (an elite record: no elites, and its log begins)
+  p->elite.restart();
   HIP_TRY(hipStreamSynchronize(s));
   p->wt.begin();
   auto t0 = std::chrono::steady_clock::now();
   for (int i = Nd - 1; i >= 1; --i) {  // reverse() (mbd_planner.py:138-148)
     float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // Ybars.append(Yi)
     MBD_TRY(plan_keep_in_step(p));
-    MBD_TRY(reverse_once_impl(p, p->d_state0, i, rng, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, noise_always(p)));
+    MBD_TRY(reverse_once_impl(p, p->d_state0, i, rng, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, noise_spec(p, false)));
     cur = nxt;
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -2566,7 +2514,7 @@ extern "C" int mbd_plan_set_adapt(mbd_plan* p, const mbd_adapt* rec) {
   if (!rec && !p->adapt.has) return MBD_OK;  // (nothing to clear: no device is touched)
   // normals prepared ahead were made under another table: as mbd_plan_set_noise_shape, nothing prepared survives
   p->ring.forget();
-  return p->adapt.set(rec, p->HNu, shape_always(p), p->env, p->stream);
+  return p->adapt.set(rec, p->HNu, p->noise.shape_always(), p->env, p->stream);
 }
 
 extern "C" int mbd_plan_peek_adapt(mbd_plan* p, float* a_out, float* ratio_out, int32_t* skipped_out, int capacity, int* count_out) {
@@ -2660,7 +2608,7 @@ extern "C" int mbd_debug_adapt_step(const float* w, const float* cand, int N, in
 // ---- the elite record (include/mbd_hip.h mbd_elites) --------------------------------------------------------------------------
 // the refusals the record alone decides against the handle's Nsample, update_method and enable_demo, in the header's order, each
 // naming the field — host arithmetic, before any device access
-static int check_elites(const mbd_elites* rec, int Nsample, int update_method, int enable_demo) {
+int check_elites(const mbd_elites* rec, int Nsample, int update_method, int enable_demo) {
   if (rec->n_elites < 0 || rec->n_elites > kEliteMax)
     return fail(MBD_ERR_INVALID, "elite record: n_elites=%d outside [0, %d]", rec->n_elites, kEliteMax);
   if (rec->nominal != 0 && rec->nominal != 1) return fail(MBD_ERR_INVALID, "elite record: nominal=%d: 0 or 1", rec->nominal);
@@ -2682,41 +2630,60 @@ extern "C" int mbd_debug_check_elites(const mbd_elites* rec, int Nsample, int up
   return check_elites(rec, Nsample, update_method, enable_demo);
 }
 
-int EliteRec::set(const mbd_elites* rec, int HNu, const mbd_env* env, hipStream_t s) {
-  HIP_TRY(hipSetDevice(env->device));
-  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the elites or write the log)
+int EliteRec::set(const mbd_elites* rec, int P_, int HNu, int device) {
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the elites or write the logs)
   has = false;
-  steps = 0;
+  restart();
   if (!rec) return MBD_OK;
-  const size_t rows = rec->n_elites > 0 ? (size_t)rec->n_elites : 1;
-  HIP_TRY(d_E.grow(rows * HNu));
-  HIP_TRY(d_R.grow(rows));
-  HIP_TRY(d_src.grow(rows));
-  HIP_TRY(d_count.grow(1));
-  HIP_TRY(d_log_count.grow(kLogCap));
-  HIP_TRY(d_log_kept.grow(kLogCap));
-  HIP_TRY(d_log_top.grow(kLogCap));
-  n = rec->n_elites; nominal = rec->nominal; carry = rec->carry;
+  layout(rec->n_elites, rec->nominal, rec->carry, P_);
+  const size_t PR = (size_t)P * rows;
+  HIP_TRY(d_E.grow(PR * HNu));
+  HIP_TRY(d_R.grow(PR));
+  HIP_TRY(d_src.grow(PR));
+  HIP_TRY(d_count.grow(P));
+  HIP_TRY(d_log_count.grow((size_t)P * log_cap));
+  HIP_TRY(d_log_kept.grow((size_t)P * log_cap));
+  HIP_TRY(d_log_top.grow((size_t)P * log_cap));
   has = true;
-  MBD_TRY(table(-1, HNu, s));
-  HIP_TRY(hipStreamSynchronize(s));
   return MBD_OK;
 }
 
-int EliteRec::peek(const mbd_env* env, int HNu, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
-                   int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out) const {
-  if (!has) return fail(MBD_ERR_STATE, "peek_elites: the plan has no elite record");
+int EliteRec::scratch(int n_elites, int nominal_, int P_, int HNu, const float* E_in, const int32_t* count_in) {
+  layout(n_elites, nominal_, 0, P_);
+  log_cap = 1;
+  has = true;
+  const size_t PR = (size_t)P * rows;
+  HIP_TRY(d_E.alloc_poisoned(PR * HNu));
+  HIP_TRY(d_R.alloc_poisoned(PR));
+  HIP_TRY(d_src.alloc_poisoned(PR));
+  HIP_TRY(d_count.upload(count_in, P));
+  HIP_TRY(d_log_count.alloc_poisoned(P));
+  HIP_TRY(d_log_kept.alloc_poisoned(P));
+  HIP_TRY(d_log_top.alloc_poisoned(P));
+  // (the rows from count_in[k] on stay poisoned: E' of a plan no launch writes reads back as it went in)
+  for (int k = 0; E_in && k < P; ++k) {
+    const size_t at = (size_t)k * rows * HNu;
+    if (count_in[k] > 0) HIP_TRY(hipMemcpy(d_E + at, E_in + at, sizeof(float) * (size_t)count_in[k] * HNu, hipMemcpyHostToDevice));
+  }
+  return MBD_OK;
+}
+
+int EliteRec::peek(const mbd_env* env, int k, int HNu, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
+                   int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out, const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_elites: the %s has no elite record", what);
   if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_elites: capacity=%d", capacity);
   HIP_TRY(hipSetDevice(env->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(d_E.download(elites_out, (size_t)n * HNu));
-  HIP_TRY(d_R.download(returns_out, n));
-  HIP_TRY(d_src.download(src_out, n));
-  HIP_TRY(d_count.download(count_out, 1));
-  MBD_TRY(ring_read(d_log_count.get(), 1, steps, kLogCap, capacity, log_count));
-  MBD_TRY(ring_read(d_log_kept.get(), 1, steps, kLogCap, capacity, log_kept));
-  MBD_TRY(ring_read(d_log_top.get(), 1, steps, kLogCap, capacity, log_top));
-  if (n_log_out) *n_log_out = (int)(steps < 0x7fffffffll ? steps : 0x7fffffffll);
+  const size_t row = (size_t)k * rows, log = (size_t)k * log_cap;
+  if (elites_out && n) HIP_TRY(hipMemcpy(elites_out, d_E + row * HNu, sizeof(float) * (size_t)n * HNu, hipMemcpyDeviceToHost));
+  if (returns_out && n) HIP_TRY(hipMemcpy(returns_out, d_R + row, sizeof(float) * n, hipMemcpyDeviceToHost));
+  if (src_out && n) HIP_TRY(hipMemcpy(src_out, d_src + row, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  if (count_out) HIP_TRY(hipMemcpy(count_out, d_count + k, sizeof(int32_t), hipMemcpyDeviceToHost));
+  MBD_TRY(ring_read(d_log_count.get() + log, 1, steps[k], log_cap, capacity, log_count));
+  MBD_TRY(ring_read(d_log_kept.get() + log, 1, steps[k], log_cap, capacity, log_kept));
+  MBD_TRY(ring_read(d_log_top.get() + log, 1, steps[k], log_cap, capacity, log_top));
+  if (n_log_out) *n_log_out = (int)(steps[k] < 0x7fffffffll ? steps[k] : 0x7fffffffll);
   return MBD_OK;
 }
 
@@ -2729,14 +2696,17 @@ extern "C" int mbd_plan_set_elites(mbd_plan* p, const mbd_elites* rec) {
   // normals prepared ahead are not what the record's steps take, and a buffer the record rewrote is not what its tag said: as
   // mbd_plan_set_noise_shape, nothing prepared survives — in either direction
   p->ring.forget();
-  return p->elite.set(rec, p->HNu, p->env, p->stream);
+  MBD_TRY(p->elite.set(rec, 1, p->HNu, p->env->device));
+  MBD_TRY(elite_table(p->elite, -1, p->HNu, p->stream));  // (no elites afterwards: one launch, waited for)
+  if (p->elite.has) HIP_TRY(hipStreamSynchronize(p->stream));
+  return MBD_OK;
 }
 
 extern "C" int mbd_plan_peek_elites(mbd_plan* p, float* elites_out, float* returns_out, int32_t* src_out, int32_t* count_out,
                                     int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
-  return p->elite.peek(p->env, p->HNu, elites_out, returns_out, src_out, count_out, log_count, log_kept, log_top, capacity,
-                       n_log_out);
+  return p->elite.peek(p->env, 0, p->HNu, elites_out, returns_out, src_out, count_out, log_count, log_kept, log_top, capacity,
+                       n_log_out, "plan");
 }
 
 // include/mbd_hip_debug.h: one step of the record on the HOST — the injection, then the selection — from the functions the kernels
@@ -2806,14 +2776,11 @@ extern "C" int mbd_debug_elites_inject(const float* cand, int N, int HNu, const 
   const size_t n = (size_t)N * HNu;
   DevBuf<float> d_cand, d_ybar, d_g;
   EliteRec L;
-  L.n = n_elites; L.nominal = nominal; L.has = true;
   HIP_TRY(d_cand.upload(cand, n));
   HIP_TRY(d_ybar.upload(ybar, HNu));
   if (g) HIP_TRY(d_g.upload(g, HNu));  // (without: d_g stays nullptr)
-  HIP_TRY(L.d_E.alloc_poisoned((size_t)(n_elites > 0 ? n_elites : 1) * HNu));
-  if (count_in > 0) HIP_TRY(hipMemcpy(L.d_E, E_in, sizeof(float) * (size_t)count_in * HNu, hipMemcpyHostToDevice));
-  HIP_TRY(L.d_count.upload(&count_in, 1));
-  MBD_TRY(L.inject(StepCand{d_cand, N, HNu, lazy ? 1 : 0, sigma, nullptr, d_ybar}, d_g, nullptr));
+  MBD_TRY(L.scratch(n_elites, nominal, 1, HNu, E_in, &count_in));
+  MBD_TRY(elite_inject(L, StepCand{d_cand, N, HNu, lazy ? 1 : 0, sigma, nullptr, d_ybar}, d_g, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(d_cand.download(cand_out, n));
   return MBD_OK;
@@ -2825,21 +2792,13 @@ extern "C" int mbd_debug_elites_select(const float* rews, const float* cand, int
   if (!rews) return fail(MBD_ERR_INVALID, "elites_select: NULL argument");
   if (count_in < 0 || count_in > n_elites) return fail(MBD_ERR_INVALID, "elites_select: count=%d outside [0, n_elites=%d]", count_in, n_elites);
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
-  const size_t k = (size_t)(n_elites > 0 ? n_elites : 1);
   DevBuf<float> d_rews, d_cand, d_ybar;
   EliteRec L;
-  L.n = n_elites; L.nominal = nominal; L.has = true;
   HIP_TRY(d_rews.upload(rews, N));
   HIP_TRY(d_cand.upload(cand, (size_t)N * HNu));
   HIP_TRY(d_ybar.upload(ybar, HNu));
-  HIP_TRY(L.d_count.upload(&count_in, 1));
-  HIP_TRY(L.d_E.alloc_poisoned(k * HNu));
-  HIP_TRY(L.d_R.alloc_poisoned(k));
-  HIP_TRY(L.d_src.alloc_poisoned(k));
-  HIP_TRY(L.d_log_count.alloc_poisoned(1));
-  HIP_TRY(L.d_log_kept.alloc_poisoned(1));
-  HIP_TRY(L.d_log_top.alloc_poisoned(1));
-  MBD_TRY(L.select(d_rews, StepCand{d_cand, N, HNu, lazy ? 1 : 0, sigma, nullptr, d_ybar}, nullptr));
+  MBD_TRY(L.scratch(n_elites, nominal, 1, HNu, nullptr, &count_in));
+  MBD_TRY(elite_select(L, d_rews, StepCand{d_cand, N, HNu, lazy ? 1 : 0, sigma, nullptr, d_ybar}, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(L.d_E.download(E_out, (size_t)n_elites * HNu));
   HIP_TRY(L.d_R.download(R_out, n_elites));
@@ -2859,7 +2818,7 @@ extern "C" int mbd_debug_elites_select(const float* rews, const float* cand, int
 // the refusals the record alone decides against the handle's Hsample, Nsample, update_method and enable_demo, in the header's order,
 // each naming the field — host arithmetic, before any device access
 constexpr int kTogoMaxN = 12288;  // the N weights of a group in the default 48 KB LDS window
-static int check_togo(const mbd_togo* rec, int Hsample, int Nsample, int update_method, int enable_demo) {
+int check_togo(const mbd_togo* rec, int Hsample, int Nsample, int update_method, int enable_demo) {
   if (rec->block < 1) return fail(MBD_ERR_INVALID, "to-go record: block=%d: at least 1", rec->block);
   if (rec->min_tail < 1 || rec->min_tail > Hsample)
     return fail(MBD_ERR_INVALID, "to-go record: min_tail=%d outside [1, Hsample=%d]", rec->min_tail, Hsample);
@@ -2877,16 +2836,16 @@ extern "C" int mbd_debug_check_togo(const mbd_togo* rec, int Hsample, int Nsampl
   return check_togo(rec, Hsample, Nsample, update_method, enable_demo);
 }
 
-int TogoRec::set(const mbd_togo* rec, int H, int N, const mbd_env* env) {
-  HIP_TRY(hipSetDevice(env->device));
+int TogoRec::set(const mbd_togo* rec, int P, int H, int N, int device) {
+  HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still write R and W)
   has = false;
   if (!rec) return MBD_OK;
   layout(rec->block, rec->min_tail, H);
-  const size_t n = (size_t)G * N;
+  const size_t n = (size_t)P * G * N;
   HIP_TRY(d_R.grow(n));
   HIP_TRY(d_W.grow(n));
-  HIP_TRY(hipMemset(d_R, 0xff, sizeof(float) * n));  // (no step yet: mbd_plan_peek_togo says so)
+  HIP_TRY(hipMemset(d_R, 0xff, sizeof(float) * n));  // (no step yet: mbd_*_peek_togo says so)
   HIP_TRY(hipMemset(d_W, 0xff, sizeof(float) * n));
   HIP_TRY(hipDeviceSynchronize());
   stepped = false;
@@ -2894,16 +2853,17 @@ int TogoRec::set(const mbd_togo* rec, int H, int N, const mbd_env* env) {
   return MBD_OK;
 }
 
-int TogoRec::peek(const mbd_env* env, int N, const float* d_weights, int32_t* starts_out, float* R_out, float* W_out,
-                  int32_t* n_groups_out) const {
-  if (!has) return fail(MBD_ERR_STATE, "peek_togo: the plan has no to-go record");
+int TogoRec::peek(const mbd_env* env, int k, int N, const float* d_weights, int32_t* starts_out, float* R_out, float* W_out,
+                  int32_t* n_groups_out, const char* what) const {
+  if (!has) return fail(MBD_ERR_STATE, "peek_togo: the %s has no to-go record", what);
   HIP_TRY(hipSetDevice(env->device));
   HIP_TRY(hipDeviceSynchronize());
+  const size_t gn = (size_t)G * N;
   if (starts_out) memcpy(starts_out, starts.data(), sizeof(int32_t) * G);
-  HIP_TRY(d_R.download(R_out, (size_t)G * N));
-  HIP_TRY(d_W.download(W_out, (size_t)G * N));
-  // (group 0's weights are the plan's own, once a step of the record has written them)
-  if (W_out && stepped) HIP_TRY(hipMemcpy(W_out, d_weights, sizeof(float) * N, hipMemcpyDeviceToHost));
+  if (R_out) HIP_TRY(hipMemcpy(R_out, d_R + (size_t)k * gn, sizeof(float) * gn, hipMemcpyDeviceToHost));
+  if (W_out) HIP_TRY(hipMemcpy(W_out, d_W + (size_t)k * gn, sizeof(float) * gn, hipMemcpyDeviceToHost));
+  // (group 0's weights are the plan's own slice of d_weights, once a step of the record has written them)
+  if (W_out && stepped) HIP_TRY(hipMemcpy(W_out, d_weights + (size_t)k * N, sizeof(float) * N, hipMemcpyDeviceToHost));
   if (n_groups_out) *n_groups_out = G;
   return MBD_OK;
 }
@@ -2922,12 +2882,12 @@ extern "C" int mbd_plan_set_togo(mbd_plan* p, const mbd_togo* rec) {
   }
   NO_SESSION(p, "set_togo");
   if (!rec && !p->togo.has) return MBD_OK;  // (nothing to clear: no device is touched)
-  return p->togo.set(rec, p->cfg.Hsample, p->cfg.Nsample, p->env);
+  return p->togo.set(rec, 1, p->cfg.Hsample, p->cfg.Nsample, p->env->device);
 }
 
 extern "C" int mbd_plan_peek_togo(mbd_plan* p, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out) {
   if (!p) return fail(MBD_ERR_INVALID, "plan is NULL");
-  return p->togo.peek(p->env, p->cfg.Nsample, p->d_weights, starts_out, R_out, W_out, n_groups_out);
+  return p->togo.peek(p->env, 0, p->cfg.Nsample, p->d_weights, starts_out, R_out, W_out, n_groups_out, "plan");
 }
 
 // include/mbd_hip_debug.h: the layout and the returns on the HOST, from the functions the returns kernel calls; no device touched
@@ -2982,7 +2942,7 @@ extern "C" int mbd_debug_togo_step(const float* cand, const float* ybar, const f
   A.rews = d_rews; A.weights = d_w; A.rew_mean = d_mean; A.cand = d_cand; A.ybar_i = d_ybar; A.ybar_im1 = d_out; A.ybar_keep = d_keep;
   A.N = N; A.H = H; A.Nu = Nu; A.temp = temp; A.std_guard = std_guard ? 1 : 0; A.alpha_i = alpha_i; A.alpha_bar_i = alpha_bar_i;
   A.alpha_bar_im1 = alpha_bar_im1; A.literal = literal ? 1 : 0; A.lazy = lazy ? 1 : 0; A.sigma = sigma;
-  MBD_TRY(L.launch(d_rewss, A, nullptr));
+  MBD_TRY(togo_launch(L, d_rewss, A, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(d_out.download(ybar_out, HNu));
   HIP_TRY(L.d_R.download(R_out, gn));
@@ -3033,14 +2993,14 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
   }
   // the noise shape and basis: a cold tick is mbd_plan_run's loop (MBD_NOISE_WARM_TICKS: without), every other tick samples under
   // them in either mode — the first normals of the next tick, prepared beside this tick's last rollout, included
-  const NoiseSpec ns = tk.cold ? noise_always(p) : noise_warm(p);
+  const NoiseSpec ns = noise_spec(p, !tk.cold);
   // with an adapt record, ONE launch in front of the tick's first sampler: a = ones in a cold tick and without carry, otherwise a
   // shifted E rows forward with the mean; G under the caller's shape in force in this tick.  Stream order is the whole argument: it
   // stands behind the previous tick's last update and in front of this tick's first sampler, which reads G
-  MBD_TRY(p->adapt.table(tk.cold || !p->adapt.carry ? -1 : tk.E * p->Nu, tk.cold ? shape_always(p) : shape_warm(p), HNu, s));
+  MBD_TRY(p->adapt.table(tk.cold || !p->adapt.carry ? -1 : tk.E * p->Nu, tk.cold ? p->noise.shape_always() : p->noise.shape_warm(), HNu, s));
   // with an elite record, ONE launch in the same place: no elites in a cold tick and without carry, otherwise the present ones
   // shifted E rows forward with the mean
-  MBD_TRY(p->elite.table(tk.cold || !p->elite.carry ? -1 : tk.E * p->Nu, HNu, s));
+  MBD_TRY(elite_table(p->elite, tk.cold || !p->elite.carry ? -1 : tk.E * p->Nu, HNu, s));
   p->wt.begin();  // (a weighting record's log holds the last tick's steps)
   const float* cur = p->d_Ybar;  // Ybar at a tick's first step: YN = zeros of a cold tick, shift_E(M_{t-1}) otherwise
   const float* last_in = cur;    // Ybar_i of the tick's last step
@@ -3048,7 +3008,7 @@ static int mpc_plan_tick(mbd_plan* p, const MpcTick& tk, uint32_t r[2], hipStrea
   for (int i = tk.cold ? Nd - 1 : tk.K; i >= 1; --i) {
     float* nxt = p->d_mu + (size_t)(Nd - 1 - i) * HNu;  // (K <= Nd-1: a warm tick's steps use the last K slots)
     MBD_TRY(plan_keep_in_step(p));
-    MBD_TRY(reverse_once_impl(p, plan_from, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, ns, tk.key_after, noise_warm(p), tk.d_xref));
+    MBD_TRY(reverse_once_impl(p, plan_from, i, r, cur, nxt, p->d_rewmeans + (Nd - 1 - i), s, ns, tk.key_after, noise_spec(p, true), tk.d_xref));
     last_in = cur;
     cur = last_out = nxt;
   }
@@ -3166,7 +3126,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   } obj_episode{p->obj};
   MBD_TRY(p->pick.start(T));  // (a pick record's log: one entry per tick)
   p->adapt.count = 0;         // (an adapt record's log: the episode's steps)
-  p->elite.steps = 0;         // (an elite record's log likewise)
+  p->elite.restart();         // (an elite record's log likewise)
   if (pi) {  // sigma = sigma_cold and the log's first entry, by the kernel that carries sigma across the boundaries
     MBD_TRY(p->sigma_rec.start(T, 1));
     p->sigma_rec.launch(p->d_sigma, 1, 0, true, s);
@@ -3233,7 +3193,7 @@ extern "C" int mbd_plan_run_mpc(mbd_plan* p, const mbd_mpc_config* mc, const uin
   if (has_demo) MBD_TRY(p->demo.finish(T, 1, E, s));
   // an adapt record's G leaves the episode formed under the shape in force OUTSIDE warm ticks again (the table itself stays): the
   // phase calls that may follow sample under it, as they would under the caller's shape without a record
-  MBD_TRY(p->adapt.table(0, shape_always(p), HNu, s));
+  MBD_TRY(p->adapt.table(0, p->noise.shape_always(), HNu, s));
   HIP_TRY(hipStreamSynchronize(s));
   const auto t1 = std::chrono::steady_clock::now();
   if (loop_seconds_out) *loop_seconds_out = std::chrono::duration<double>(t1 - t0).count();
@@ -3336,7 +3296,7 @@ extern "C" int mbd_plan_mpc_open(mbd_plan* p, const mbd_mpc_config* mc, const ui
   // (nothing fails from here on: a refused or failed open leaves the last episode's logs readable)
   if (p->delay.has) p->delay.pred_ticks = 0;  // (mbd_plan_peek_mpc_predicted does not serve sessions)
   p->adapt.count = 0;                         // (an adapt record's log: the session's steps)
-  p->elite.steps = 0;                         // (an elite record's log likewise)
+  p->elite.restart();                         // (an elite record's log likewise)
   ss.mc = *mc;
   ss.rng[0] = key[0]; ss.rng[1] = key[1];
   ss.t = 0; ss.qbuf = 0; ss.flags = 0;
@@ -3441,11 +3401,11 @@ extern "C" int mbd_plan_mpc_reset_mean(mbd_plan* p) {
   p->session.cold = true;  // (the next submit zeroes Ybar; the queue stays)
   if (p->adapt.has) {      // (an adapt record's table is all ones again: written now as well, so that mbd_plan_peek_adapt says so)
     HIP_TRY(hipSetDevice(p->env->device));
-    MBD_TRY(p->adapt.table(-1, shape_always(p), p->HNu, p->stream));
+    MBD_TRY(p->adapt.table(-1, p->noise.shape_always(), p->HNu, p->stream));
   }
   if (p->elite.has) {  // (an elite record's elites are gone: written now as well, so that mbd_plan_peek_elites says so)
     HIP_TRY(hipSetDevice(p->env->device));
-    MBD_TRY(p->elite.table(-1, p->HNu, p->stream));
+    MBD_TRY(elite_table(p->elite, -1, p->HNu, p->stream));
   }
   if (p->cfg.update_method != 0) {  // (and starts from sigma_cold: written now as well, so that mbd_plan_get_sigma says so)
     HIP_TRY(hipSetDevice(p->env->device));
@@ -3462,7 +3422,7 @@ extern "C" int mbd_plan_mpc_close(mbd_plan* p) {
   HIP_TRY(hipSetDevice(p->env->device));
   if (ss.in_flight) HIP_TRY(hipStreamSynchronize(p->stream));  // (its last kernel writes the mailbox)
   if (p->adapt.has) {  // (as behind mbd_plan_run_mpc: G under the shape in force outside warm ticks, for the phase calls)
-    MBD_TRY(p->adapt.table(0, shape_always(p), p->HNu, p->stream));
+    MBD_TRY(p->adapt.table(0, p->noise.shape_always(), p->HNu, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
   }
   ss.in_flight = false;

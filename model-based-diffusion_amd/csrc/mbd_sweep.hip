@@ -9,104 +9,74 @@
 #include "../../include/mbd_hip_debug.h"
 
 namespace {
-// The elite record of all the sweep's plans (mbd_sweep_set_elites), a plan's EliteRec per plan: E [P][rows][HNu], R and src
-// [P][rows] (rows = max(n, 1)), count [P] on the device — never read back inside a loop — and the three logs [P][kLogCap].  steps is
-// host bookkeeping PER PLAN: in a session's mixed tick the episodes that idle make no selection, and their logs stay a single
-// session's.  Every launch takes the mask of the plans that take part (bit k: plan k).
-struct SweepEliteRec {
-  bool has = false;
-  int n = 0, nominal = 0, carry = 0, rows = 1;
-  int log_cap = kLogCap;  // entries of a plan's log (the debug entry's scratch record: 1)
-  long long steps[MBD_SWEEP_MAX_PLANS] = {};
-  DevBuf<float> d_E, d_R, d_log_top;
-  DevBuf<int> d_src, d_count, d_log_count, d_log_kept;
-  void restart() { for (long long& c : steps) c = 0; }
-  EliteBatch batch(long long cand, long long ybar, long long rews, int HNu, unsigned mask) const {
-    EliteBatch B{};
-    B.cand = cand; B.ybar = ybar; B.rews = rews; B.E = (long long)rows * HNu; B.R = rows; B.log = log_cap; B.mask = mask;
-    return B;
-  }
-  int alloc(int P, int HNu) {
-    HIP_TRY(d_E.grow((size_t)P * rows * HNu));
-    HIP_TRY(d_R.grow((size_t)P * rows));
-    HIP_TRY(d_src.grow((size_t)P * rows));
-    HIP_TRY(d_count.grow(P));
-    return MBD_OK;
-  }
-  // the plans' elites at the start of a run or a tick: shift[k] < 0 empties plan k's, otherwise its rows move shift[k] elements forward
-  int table(int P, int HNu, const EliteShifts& sh, unsigned mask, hipStream_t s) {
-    if (!has) return MBD_OK;
-    hipLaunchKernelGGL(elite_shift_batch_kernel, dim3((unsigned)rows, (unsigned)P), dim3(kEliteThreads), 0, s, d_E.get(), d_count.get(), HNu,
-                       sh, batch(0, 0, 0, HNu, mask));
-    HIP_TRY(hipGetLastError());
-    return MBD_OK;
-  }
-  int table_all(int P, int HNu, int shift, hipStream_t s) {
-    EliteShifts sh;
-    for (int& v : sh.s) v = shift;
-    return table(P, HNu, sh, 0xffffffffu, s);
-  }
-  // behind the launch that made the step's normals or candidates, in front of the rollout (EliteRec::inject per plan)
-  int inject(int P, float* cand, long long cand_stride, int HNu, int lazy, float sigma, const float* ybar, long long ybar_stride,
-             const float* g, unsigned mask, hipStream_t s) {
-    if (!has) return MBD_OK;
-    EliteInject A{};
-    A.cand = cand; A.HNu = HNu; A.ybar_i = ybar; A.lazy = lazy; A.sigma = sigma; A.g = g;
-    A.n_elites = n; A.nominal = nominal; A.E = d_E; A.count = d_count;
-    const long long total = (long long)(nominal + n) * HNu;
-    hipLaunchKernelGGL(elite_inject_batch_kernel, dim3((unsigned)((total + kEliteThreads - 1) / kEliteThreads), (unsigned)P),
-                       dim3(kEliteThreads), 0, s, A, batch(cand_stride, ybar_stride, 0, HNu, mask));
-    HIP_TRY(hipGetLastError());
-    return MBD_OK;
-  }
-  // behind the step's update kernel (EliteRec::select per plan); the plans of the mask gain a log entry, each at its own ring's slot
-  int select(int P, const float* rews, int N, const float* cand, long long cand_stride, int HNu, int lazy, float sigma,
-             const float* ybar, long long ybar_stride, unsigned mask, hipStream_t s) {
-    if (!has) return MBD_OK;
-    EliteSelect A{};
-    A.rews = rews; A.N = N; A.HNu = HNu; A.cand = cand; A.lazy = lazy; A.sigma = sigma; A.ybar_i = ybar;
-    A.n_elites = n; A.nominal = nominal; A.E = d_E; A.R = d_R; A.src = d_src; A.count = d_count;
-    A.log_count = d_log_count; A.log_kept = d_log_kept; A.log_top = d_log_top;
-    EliteBatch B = batch(cand_stride, ybar_stride, N, HNu, mask);
-    EliteShifts slots;  // (plan k's entry lies at slot[k] of its own ring)
-    for (int k = 0; k < MBD_SWEEP_MAX_PLANS; ++k) slots.s[k] = 0;
-    for (int k = 0; k < P; ++k)
-      if ((mask >> k) & 1u) slots.s[k] = (int)ring_slot(steps[k], log_cap);
-    hipLaunchKernelGGL(elite_select_batch_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), 0, s, A, B, slots);
-    HIP_TRY(hipGetLastError());
-    return MBD_OK;
-  }
-};
+// The elite record's launches for the P plans of a sweep (mbd_internal.h EliteRec): the batch kernels, which take the plans' strides
+// (EliteBatch) and the mask of the plans that take part (bit k: plan k).
+EliteBatch elite_batch(const EliteRec& L, long long cand, long long ybar, long long rews, int HNu, unsigned mask) {
+  EliteBatch B{};
+  B.cand = cand; B.ybar = ybar; B.rews = rews; B.E = (long long)L.rows * HNu; B.R = L.rows; B.log = L.log_cap; B.mask = mask;
+  return B;
+}
+// the plans' elites at the start of a run or a tick: shift[k] < 0 empties plan k's, otherwise its rows move shift[k] elements forward
+int elite_table(EliteRec& L, int P, int HNu, const EliteShifts& sh, unsigned mask, hipStream_t s) {
+  if (!L.has) return MBD_OK;
+  hipLaunchKernelGGL(elite_shift_batch_kernel, dim3((unsigned)L.rows, (unsigned)P), dim3(kEliteThreads), 0, s, L.d_E.get(), L.d_count.get(), HNu,
+                     sh, elite_batch(L, 0, 0, 0, HNu, mask));
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+int elite_table_all(EliteRec& L, int P, int HNu, int shift, hipStream_t s) {
+  EliteShifts sh;
+  for (int& v : sh.s) v = shift;
+  return elite_table(L, P, HNu, sh, 0xffffffffu, s);
+}
+// behind the launch that made the step's normals or candidates, in front of the rollout (a plan's elite_inject per plan)
+int elite_inject(EliteRec& L, int P, float* cand, long long cand_stride, int HNu, int lazy, float sigma, const float* ybar,
+                 long long ybar_stride, const float* g, unsigned mask, hipStream_t s) {
+  if (!L.has) return MBD_OK;
+  EliteInject A{};
+  A.cand = cand; A.HNu = HNu; A.ybar_i = ybar; A.lazy = lazy; A.sigma = sigma; A.g = g;
+  A.n_elites = L.n; A.nominal = L.nominal; A.E = L.d_E; A.count = L.d_count;
+  const long long total = (long long)(L.nominal + L.n) * HNu;
+  hipLaunchKernelGGL(elite_inject_batch_kernel, dim3((unsigned)((total + kEliteThreads - 1) / kEliteThreads), (unsigned)P),
+                     dim3(kEliteThreads), 0, s, A, elite_batch(L, cand_stride, ybar_stride, 0, HNu, mask));
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
+// behind the step's update kernel (a plan's elite_select per plan); the plans of the mask gain a log entry, each at its own ring's slot
+int elite_select(EliteRec& L, int P, const float* rews, int N, const float* cand, long long cand_stride, int HNu, int lazy, float sigma,
+                 const float* ybar, long long ybar_stride, unsigned mask, hipStream_t s) {
+  if (!L.has) return MBD_OK;
+  EliteSelect A{};
+  A.rews = rews; A.N = N; A.HNu = HNu; A.cand = cand; A.lazy = lazy; A.sigma = sigma; A.ybar_i = ybar;
+  A.n_elites = L.n; A.nominal = L.nominal; A.E = L.d_E; A.R = L.d_R; A.src = L.d_src; A.count = L.d_count;
+  A.log_count = L.d_log_count; A.log_kept = L.d_log_kept; A.log_top = L.d_log_top;
+  EliteBatch B = elite_batch(L, cand_stride, ybar_stride, N, HNu, mask);
+  EliteShifts slots;  // (plan k's entry lies at slot[k] of its own ring)
+  for (int k = 0; k < MBD_SWEEP_MAX_PLANS; ++k) slots.s[k] = 0;
+  for (int k = 0; k < P; ++k)
+    if ((mask >> k) & 1u) slots.s[k] = (int)ring_slot(L.steps[k], L.log_cap);
+  hipLaunchKernelGGL(elite_select_batch_kernel, dim3(1, (unsigned)P), dim3(kScoreThreads), 0, s, A, B, slots);
+  HIP_TRY(hipGetLastError());
+  return MBD_OK;
+}
 
-// The to-go record of all the sweep's plans (mbd_sweep_set_togo), a plan's TogoRec per plan: one layout, R and W [P][G][N] (row 0 of
-// a plan's W is never written: group 0's weights are the plan's slice of d_weights).
-struct SweepTogoRec {
-  bool has = false, stepped = false;
-  int block = 0, min_tail = 0, G = 0;
-  std::vector<int32_t> starts;
-  DevBuf<float> d_R, d_W;
-  void layout(int block_, int min_tail_, int H) {
-    block = block_; min_tail = min_tail_;
-    G = togo_groups(H, block, min_tail);
-    starts.resize(G);
-    for (int j = 0; j < G; ++j) starts[j] = togo_start(j, block);
-  }
-  // the step's two launches where the batch score + weighted mean stands: A and sb carry everything but the layout and R, W
-  int launch(int P, const float* d_rewss, TogoUpdate A, const ScoreBatch& sb, hipStream_t s) {
-    const TogoReturns Rt{A.rews, d_rewss, d_R.get(), A.N, A.H, block, G};
-    const long long PN = (long long)P * A.N;
-    hipLaunchKernelGGL(togo_returns_batch_kernel, dim3((unsigned)((PN + kTogoThreads - 1) / kTogoThreads)), dim3(kTogoThreads), 0, s, Rt, P);
-    HIP_TRY(hipGetLastError());
-    const long long last = (long long)(A.H - togo_start(G - 1, block)) * A.Nu;
-    A.R = d_R; A.W = d_W; A.G = G; A.block = block;
-    A.tpg = G > 1 ? (int)(((long long)block * A.Nu + kWmE - 1) / kWmE) : 1;
-    A.T = (G - 1) * A.tpg + (int)((last + kWmE - 1) / kWmE);
-    hipLaunchKernelGGL(togo_update_batch_kernel, dim3((unsigned)A.T, (unsigned)P), dim3(kWmE * kWmG), sizeof(float) * (size_t)A.N, s, A, sb);
-    HIP_TRY(hipGetLastError());
-    stepped = true;
-    return MBD_OK;
-  }
-};
+// The to-go record's two launches for the P plans of a sweep (mbd_internal.h TogoRec), where the batch score + weighted mean stands:
+// A and sb carry everything but the layout and R, W
+int togo_launch(TogoRec& L, int P, const float* d_rewss, TogoUpdate A, const ScoreBatch& sb, hipStream_t s) {
+  const int block = L.block, G = L.G;
+  const TogoReturns Rt{A.rews, d_rewss, L.d_R.get(), A.N, A.H, block, G};
+  const long long PN = (long long)P * A.N;
+  hipLaunchKernelGGL(togo_returns_batch_kernel, dim3((unsigned)((PN + kTogoThreads - 1) / kTogoThreads)), dim3(kTogoThreads), 0, s, Rt, P);
+  HIP_TRY(hipGetLastError());
+  const long long last = (long long)(A.H - togo_start(G - 1, block)) * A.Nu;
+  A.R = L.d_R; A.W = L.d_W; A.G = G; A.block = block;
+  A.tpg = G > 1 ? (int)(((long long)block * A.Nu + kWmE - 1) / kWmE) : 1;
+  A.T = (G - 1) * A.tpg + (int)((last + kWmE - 1) / kWmE);
+  hipLaunchKernelGGL(togo_update_batch_kernel, dim3((unsigned)A.T, (unsigned)P), dim3(kWmE * kWmG), sizeof(float) * (size_t)A.N, s, A, sb);
+  HIP_TRY(hipGetLastError());
+  L.stepped = true;
+  return MBD_OK;
+}
 
 // outputs per thread of the sweeps' score + weighted mean launch (score_wmean_batch_kernel<V>): 2 — a workgroup owns 32 outputs,
 // 128 bytes of every candidate row, P x 27 workgroups for the humanoid.  Measured on sweep8 (profiles/r05_score_ab.txt; the
@@ -208,28 +178,9 @@ struct mbd_sweep {
   DemoRec demo;
   // the sigma record of all episodes of a path-integral sweep (mbd_sweep_set_mpc_sigma) with the log of the last batch's sigmas
   SigmaRec sigma_rec;
-  // the noise shape of all the sweep's plans (mbd_sweep_set_noise_shape): a plan's, with the same two accessors
-  DevBuf<float> d_shape;
-  bool has_shape = false;
-  int shape_when = MBD_NOISE_ALWAYS;
-  const float* shape_always() const { return has_shape && shape_when == MBD_NOISE_ALWAYS ? d_shape.get() : nullptr; }
-  const float* shape_warm() const { return has_shape ? d_shape.get() : nullptr; }
-  // the noise basis of all the sweep's plans (mbd_sweep_set_noise_basis), likewise; d_knot_z [P][N][HNu]: the scratch of a
-  // path-integral sweep's knot_noise_batch_kernel in front of shift_batch_kernel
-  DevBuf<float> d_basis, d_knot_z;
-  bool has_basis = false;
-  int basis_knots = 0, basis_when = MBD_NOISE_ALWAYS;
-  NoiseSpec noise_spec(bool warm_tick) const {
-    NoiseSpec ns;
-    ns.g = warm_tick ? shape_warm() : shape_always();
-    if (has_basis && (warm_tick || basis_when == MBD_NOISE_ALWAYS)) {
-      ns.W = d_basis.get();
-      ns.knots = basis_knots;
-    }
-    return ns;
-  }
-  NoiseSpec noise_always() const { return noise_spec(false); }
-  NoiseSpec noise_warm() const { return noise_spec(true); }
+  // the noise shape and the noise basis of all the sweep's plans (mbd_sweep_set_noise_shape, mbd_sweep_set_noise_basis): a plan's;
+  // d_knot_z [P][N][HNu]: the scratch of a path-integral sweep's knot_noise_batch_kernel in front of shift_batch_kernel
+  NoiseRec noise;
   // the objective record of all the sweep's plans (mbd_sweep_set_objective): a plan's, with every plan's previous action [P][Nu]
   ObjectiveRec obj;
   // the value record of all the sweep's plans (mbd_sweep_set_value): one net, the P N rows' final states and the last step's V
@@ -241,8 +192,8 @@ struct mbd_sweep {
   // the pick record of all the sweep's episodes (mbd_sweep_set_mpc_pick) with every episode's slots and log
   PickRec pick;
   // the elite record of all the sweep's plans (mbd_sweep_set_elites) and the to-go record (mbd_sweep_set_togo)
-  SweepEliteRec elite;
-  SweepTogoRec togo;
+  EliteRec elite;
+  TogoRec togo;
   TimingPool timing;
   // the session a caller drives tick by tick (mbd_sweep_mpc_open): it uses the batch's buffers above — slice 0 of d_mpc_states for
   // the states handed in, slice 0 of d_mpc_pred, d_mpc_queue, d_mpc_ybar — so a handle runs batches or a session, not both
@@ -399,7 +350,7 @@ int sweep_pi_update(mbd_sweep* w, int step, const float* mu_in, long long mu_str
       A.rews = w->d_rews; A.weights = w->d_weights; A.rew_mean = w->d_rewmeans + step; A.cand = w->d_Y0s; A.ybar_i = mu_in;
       A.ybar_im1 = mu_out; A.N = N; A.H = c.Hsample; A.Nu = w->Nu; A.temp = c.temp_sample; A.std_guard = 0;
       A.alpha_i = 1.0f; A.alpha_bar_i = 1.0f; A.alpha_bar_im1 = 1.0f; A.literal = 0; A.lazy = 0; A.sigma = 0.0f;
-      MBD_TRY(w->togo.launch(P, w->d_rewss, A, sb, s));
+      MBD_TRY(togo_launch(w->togo, P, w->d_rewss, A, sb, s));
     } else {
       launch_score_wmean_batch(wmean_batch_v(N), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), (const float*)nullptr, N, e->rew_xref,
                                c.temp_sample, 0, w->d_weights.get(), w->d_rewmeans + step, (const float*)w->d_Y0s, HNu, mu_in, 1.0f, 1.0f,
@@ -413,7 +364,7 @@ int sweep_pi_update(mbd_sweep* w, int step, const float* mu_in, long long mu_str
   }
   HIP_TRY(hipGetLastError());
   // the elite record: the selection behind the update, over the rewards the score read and the materialised candidates
-  if (recs) MBD_TRY(w->elite.select(P, w->d_rews, N, w->d_Y0s, (long long)per_plan, HNu, 0, 0.0f, mu_in, mu_stride, mask, s));
+  if (recs) MBD_TRY(elite_select(w->elite, P, w->d_rews, N, w->d_Y0s, (long long)per_plan, HNu, 0, 0.0f, mu_in, mu_stride, mask, s));
   return MBD_OK;
 }
 
@@ -437,16 +388,16 @@ int sweep_pi_step(mbd_sweep* w, const PiStep& st, const SweepKeys& sk) {
   const NoiseSpec& ns = st.ns;
   if (ns.W) {  // under a noise basis: the knot kernel into the scratch z, then sample_batch_kernel's two roundings
     hipLaunchKernelGGL(knot_noise_batch_kernel, dim3(knot_blocks(N, w->Nu, 1024), (unsigned)P), dim3(kKnotThreads), 0, s, sk,
-                       c.prng_impl, N, H, w->Nu, ns.knots, ns.W, ns.g, w->d_knot_z.get());
+                       c.prng_impl, N, H, w->Nu, ns.knots, ns.W, ns.g, w->noise.d_knot_z.get());
     hipLaunchKernelGGL(shift_batch_kernel, dim3(noise_blocks(MBD_PRNG_PARTITIONABLE, per_plan, 4096), (unsigned)P), dim3(256), 0, s,
-                       (const float*)w->d_knot_z, N, HNu, (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s.get());
+                       (const float*)w->noise.d_knot_z, N, HNu, (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s.get());
   } else {
     hipLaunchKernelGGL(sample_batch_kernel, dim3(nblocks, (unsigned)P), dim3(256), 0, s, sk, c.prng_impl, N, HNu,
                        (const float*)w->d_sigma, mu_in, mu_stride, w->d_Y0s, ns.g);
   }
   HIP_TRY(hipGetLastError());
   // the elite record: ONE launch between the sampler and the rollout rewrites every plan's first rows
-  MBD_TRY(w->elite.inject(P, w->d_Y0s, (long long)per_plan, HNu, 0, 0.0f, mu_in, mu_stride, ns.g, 0xffffffffu, s));
+  MBD_TRY(elite_inject(w->elite, P, w->d_Y0s, (long long)per_plan, HNu, 0, 0.0f, mu_in, mu_stride, ns.g, 0xffffffffu, s));
   MBD_TRY(w->timing.begin(s));
   const int sw[3] = {N, S, 0};
   MBD_TRY(launch_rollout(e, st.state0, w->d_Y0s, P * N, H, w->d_rewss, w->d_rews, w->zone.xpos(), w->val.final(), s, nullptr, sw));
@@ -471,7 +422,7 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
     std::vector<float> ones((size_t)P, 1.0f);  // sigma = 1.0 (path_integral.py:131)
     HIP_TRY(hipMemcpy(w->d_sigma, ones.data(), sizeof(float) * P, hipMemcpyHostToDevice));
   }
-  MBD_TRY(w->elite.table_all(P, HNu, -1, s));  // (an elite record: no plan has elites, and the logs begin)
+  MBD_TRY(elite_table_all(w->elite, P, HNu, -1, s));  // (an elite record: no plan has elites, and the logs begin)
   w->elite.restart();
   HIP_TRY(hipStreamSynchronize(s));
   auto t0 = std::chrono::steady_clock::now();
@@ -488,7 +439,7 @@ static int sweep_run_path_integral(mbd_sweep* w, const uint32_t* keys, float* mu
     st.slot = step; st.state0 = w->d_state0;
     st.mu_in = step == 0 ? w->d_zero.get() : w->d_mu + (size_t)(step - 1) * HNu;
     st.mu_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
-    st.ns = w->noise_always();
+    st.ns = w->noise.spec(false);
     MBD_TRY(sweep_pi_step(w, st, sk));
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -568,7 +519,7 @@ int sweep_update(mbd_sweep* w, int i, int slot, const float* eps, const float* y
     A.ybar_im1 = w->d_mu + (size_t)slot * HNu; A.N = N; A.H = c.Hsample; A.Nu = w->Nu; A.temp = c.temp_sample; A.std_guard = 1;
     A.alpha_i = w->alphas[i]; A.alpha_bar_i = w->alphas_bar[i]; A.alpha_bar_im1 = w->alphas_bar[i - 1]; A.literal = c.literal_score;
     A.lazy = 1; A.sigma = w->sigmas[i];
-    MBD_TRY(w->togo.launch(P, w->d_rewss, A, sb, s));
+    MBD_TRY(togo_launch(w->togo, P, w->d_rewss, A, sb, s));
   } else {
     launch_score_wmean_batch(wmean_batch_v(N), w->wt.has, HNu, P, sizeof(float) * (size_t)N, s, w->d_rews.get(), c.enable_demo ? w->d_lp.get() : nullptr, N,
                              rew_xref, c.temp_sample, 1, w->d_weights.get(), w->d_rewmeans + slot, eps, HNu, ybar_in,
@@ -578,7 +529,7 @@ int sweep_update(mbd_sweep* w, int i, int slot, const float* eps, const float* y
   HIP_TRY(hipGetLastError());
   // the elite record: the selection behind the update, over the rewards the score read and the step's normals — on the steps' stream,
   // so it is now eps[cur]'s last reader (see mbd_sweep)
-  if (recs) MBD_TRY(w->elite.select(P, w->d_rews, N, eps, (long long)N * HNu, HNu, 1, w->sigmas[i], ybar_in, ybar_in_stride, mask, s));
+  if (recs) MBD_TRY(elite_select(w->elite, P, w->d_rews, N, eps, (long long)N * HNu, HNu, 1, w->sigmas[i], ybar_in, ybar_in_stride, mask, s));
   return MBD_OK;
 }
 
@@ -610,7 +561,7 @@ int sweep_step(mbd_sweep* w, const SweepStep& st) {
   }
   // the elite record: ONE launch on the steps' stream, behind the wait for eps[cur] and in front of the rollout, rewrites every
   // plan's first rows of normals
-  MBD_TRY(w->elite.inject(P, w->d_eps[cur], (long long)N * w->HNu, w->HNu, 1, w->sigmas[i], st.ybar_in, st.ybar_in_stride, st.g, st.mask, s));
+  MBD_TRY(elite_inject(w->elite, P, w->d_eps[cur], (long long)N * w->HNu, w->HNu, 1, w->sigmas[i], st.ybar_in, st.ybar_in_stride, st.g, st.mask, s));
   LazyArgs lz;
   lz.ybar = st.ybar_in;
   lz.sigma = w->sigmas[i];
@@ -647,7 +598,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
   hipStream_t s = w->stream;
   if (c.update_method != 0) return sweep_run_path_integral(w, keys, mu_0ts_out, rew_means_out, rew_final_out, loop_seconds_out);
   std::vector<uint32_t> rng(keys, keys + 2 * (size_t)P);
-  MBD_TRY(w->elite.table_all(P, HNu, -1, s));  // (an elite record: no plan has elites, and the logs begin)
+  MBD_TRY(elite_table_all(w->elite, P, HNu, -1, s));  // (an elite record: no plan has elites, and the logs begin)
   w->elite.restart();
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipStreamSynchronize(w->aux));
@@ -655,7 +606,7 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
   auto t0 = std::chrono::steady_clock::now();
   SweepKeys sk;
   sweep_split_keys(w, rng, sk);
-  sweep_noise(w, sk, 0, s, w->noise_always());  // step Nd-1
+  sweep_noise(w, sk, 0, s, w->noise.spec(false));  // step Nd-1
   HIP_TRY(hipGetLastError());
   w->wt.begin();
   for (int i = Nd - 1, step = 0; i >= 1; --i, ++step) {
@@ -665,9 +616,9 @@ extern "C" int mbd_sweep_run(mbd_sweep* w, const uint32_t* keys, float* mu_0ts_o
     st.ybar_in = step == 0 ? w->d_zero : w->d_mu + (size_t)(step - 1) * HNu;
     st.ybar_in_stride = step == 0 ? HNu : (long long)(Nd - 1) * HNu;
     st.next_keys = i > 1 ? &sk : nullptr;
-    st.next_ns = w->noise_always();
+    st.next_ns = w->noise.spec(false);
     st.rew_xref = e->rew_xref;
-    st.g = w->shape_always();
+    st.g = w->noise.shape_always();
     MBD_TRY(sweep_step(w, st));
   }
   HIP_TRY(hipStreamSynchronize(s));
@@ -734,15 +685,7 @@ extern "C" int mbd_sweep_set_noise_shape(mbd_sweep* w, const mbd_noise_shape* re
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   NO_SWEEP_SESSION(w, "set_noise_shape");
   if (rec) MBD_TRY(check_noise_shape(rec, w->cfg.Hsample, w->Nu));
-  HIP_TRY(hipSetDevice(w->env->device));
-  HIP_TRY(hipDeviceSynchronize());
-  w->has_shape = false;
-  if (!rec) return MBD_OK;
-  HIP_TRY(w->d_shape.grow(w->HNu));
-  HIP_TRY(hipMemcpy(w->d_shape, rec->scale, sizeof(float) * w->HNu, hipMemcpyHostToDevice));
-  w->shape_when = rec->when;
-  w->has_shape = true;
-  return MBD_OK;
+  return w->noise.set_shape(rec, w->HNu, w->env->device);
 }
 
 // one noise basis for all plans of the sweep (include/mbd_hip.h mbd_noise_basis), as mbd_sweep_set_noise_shape
@@ -750,17 +693,8 @@ extern "C" int mbd_sweep_set_noise_basis(mbd_sweep* w, const mbd_noise_basis* re
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   NO_SWEEP_SESSION(w, "set_noise_basis");
   if (rec) MBD_TRY(check_noise_basis(rec, w->cfg.Hsample));
-  HIP_TRY(hipSetDevice(w->env->device));
-  HIP_TRY(hipDeviceSynchronize());
-  w->has_basis = false;
-  if (!rec) return MBD_OK;
-  HIP_TRY(w->d_basis.grow((size_t)w->cfg.Hsample * MBD_MAX_KNOTS));
-  if (w->cfg.update_method != 0) HIP_TRY(w->d_knot_z.grow((size_t)w->P * w->cfg.Nsample * w->HNu));
-  HIP_TRY(hipMemcpy(w->d_basis, rec->basis, sizeof(float) * (size_t)w->cfg.Hsample * rec->n_knots, hipMemcpyHostToDevice));
-  w->basis_knots = rec->n_knots;
-  w->basis_when = rec->when;
-  w->has_basis = true;
-  return MBD_OK;
+  // (path-integral sweeps alone run knot_noise_batch_kernel into the scratch z)
+  return w->noise.set_basis(rec, w->cfg.Hsample, w->cfg.update_method != 0 ? (size_t)w->P * w->cfg.Nsample * w->HNu : 0, w->env->device);
 }
 
 // one objective record for all plans of the sweep (include/mbd_hip.h mbd_objective), as mbd_plan_set_objective
@@ -840,24 +774,12 @@ extern "C" int mbd_sweep_peek_weighting(mbd_sweep* w, int k, float* temp_out, fl
 // plan's, on the sweep's config; no plan has elites afterwards
 extern "C" int mbd_sweep_set_elites(mbd_sweep* w, const mbd_elites* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
-  if (rec) MBD_TRY(mbd_debug_check_elites(rec, w->cfg.Nsample, w->cfg.update_method, w->cfg.enable_demo));  // (before any device access)
+  if (rec) MBD_TRY(check_elites(rec, w->cfg.Nsample, w->cfg.update_method, w->cfg.enable_demo));  // (before any device access)
   NO_SWEEP_SESSION(w, "set_elites");
-  SweepEliteRec& L = w->elite;
-  if (!rec && !L.has) return MBD_OK;  // (nothing to clear: no device is touched)
-  HIP_TRY(hipSetDevice(w->env->device));
-  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still read the elites or write the logs)
-  L.has = false;
-  L.restart();
-  if (!rec) return MBD_OK;
-  L.n = rec->n_elites; L.nominal = rec->nominal; L.carry = rec->carry;
-  L.rows = L.n > 0 ? L.n : 1;
-  MBD_TRY(L.alloc(w->P, w->HNu));
-  HIP_TRY(L.d_log_count.grow((size_t)w->P * kLogCap));
-  HIP_TRY(L.d_log_kept.grow((size_t)w->P * kLogCap));
-  HIP_TRY(L.d_log_top.grow((size_t)w->P * kLogCap));
-  L.has = true;
-  MBD_TRY(L.table_all(w->P, w->HNu, -1, w->stream));
-  HIP_TRY(hipStreamSynchronize(w->stream));
+  if (!rec && !w->elite.has) return MBD_OK;  // (nothing to clear: no device is touched)
+  MBD_TRY(w->elite.set(rec, w->P, w->HNu, w->env->device));
+  MBD_TRY(elite_table_all(w->elite, w->P, w->HNu, -1, w->stream));  // (no plan has elites afterwards: one launch, waited for)
+  if (w->elite.has) HIP_TRY(hipStreamSynchronize(w->stream));
   return MBD_OK;
 }
 
@@ -865,29 +787,15 @@ extern "C" int mbd_sweep_peek_elites(mbd_sweep* w, int k, float* elites_out, flo
                                      int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "peek_elites: plan k=%d outside [0,%d)", k, w->P);
-  const SweepEliteRec& L = w->elite;
-  if (!L.has) return fail(MBD_ERR_STATE, "peek_elites: the sweep has no elite record");
-  if (capacity < 0) return fail(MBD_ERR_INVALID, "peek_elites: capacity=%d", capacity);
-  HIP_TRY(hipSetDevice(w->env->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t row = (size_t)k * L.rows, log = (size_t)k * kLogCap;
-  const long long steps = L.steps[k];
-  if (elites_out) HIP_TRY(hipMemcpy(elites_out, L.d_E + row * w->HNu, sizeof(float) * (size_t)L.n * w->HNu, hipMemcpyDeviceToHost));
-  if (returns_out) HIP_TRY(hipMemcpy(returns_out, L.d_R + row, sizeof(float) * L.n, hipMemcpyDeviceToHost));
-  if (src_out) HIP_TRY(hipMemcpy(src_out, L.d_src + row, sizeof(int32_t) * L.n, hipMemcpyDeviceToHost));
-  if (count_out) HIP_TRY(hipMemcpy(count_out, L.d_count + k, sizeof(int32_t), hipMemcpyDeviceToHost));
-  MBD_TRY(ring_read(L.d_log_count.get() + log, 1, steps, kLogCap, capacity, log_count));
-  MBD_TRY(ring_read(L.d_log_kept.get() + log, 1, steps, kLogCap, capacity, log_kept));
-  MBD_TRY(ring_read(L.d_log_top.get() + log, 1, steps, kLogCap, capacity, log_top));
-  if (n_log_out) *n_log_out = (int)(steps < 0x7fffffffll ? steps : 0x7fffffffll);
-  return MBD_OK;
+  return w->elite.peek(w->env, k, w->HNu, elites_out, returns_out, src_out, count_out, log_count, log_kept, log_top, capacity, n_log_out,
+                       "sweep");
 }
 
 // one to-go record for all plans of the sweep (include/mbd_hip.h mbd_togo), as mbd_plan_set_togo
 extern "C" int mbd_sweep_set_togo(mbd_sweep* w, const mbd_togo* rec) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   if (rec) {  // (before any device access)
-    MBD_TRY(mbd_debug_check_togo(rec, w->cfg.Hsample, w->cfg.Nsample, w->cfg.update_method, w->cfg.enable_demo));
+    MBD_TRY(check_togo(rec, w->cfg.Hsample, w->cfg.Nsample, w->cfg.update_method, w->cfg.enable_demo));
     const char* other = w->obj.has ? "an objective" : w->val.has ? "a value" : w->wt.has ? "a weighting" : nullptr;
     if (other)
       return fail(MBD_ERR_UNSUPPORTED, "to-go record: the sweep carries %s record: what that record means per horizon row is not defined",
@@ -895,39 +803,14 @@ extern "C" int mbd_sweep_set_togo(mbd_sweep* w, const mbd_togo* rec) {
     if (w->zone.has) return refuse_beside_zones("to-go record", "sweep");
   }
   NO_SWEEP_SESSION(w, "set_togo");
-  SweepTogoRec& L = w->togo;
-  if (!rec && !L.has) return MBD_OK;  // (nothing to clear: no device is touched)
-  HIP_TRY(hipSetDevice(w->env->device));
-  HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still write R and W)
-  L.has = false;
-  if (!rec) return MBD_OK;
-  L.layout(rec->block, rec->min_tail, w->cfg.Hsample);
-  const size_t n = (size_t)w->P * L.G * w->cfg.Nsample;
-  HIP_TRY(L.d_R.grow(n));
-  HIP_TRY(L.d_W.grow(n));
-  HIP_TRY(hipMemset(L.d_R, 0xff, sizeof(float) * n));  // (no step yet: mbd_sweep_peek_togo says so)
-  HIP_TRY(hipMemset(L.d_W, 0xff, sizeof(float) * n));
-  HIP_TRY(hipDeviceSynchronize());
-  L.stepped = false;
-  L.has = true;
-  return MBD_OK;
+  if (!rec && !w->togo.has) return MBD_OK;  // (nothing to clear: no device is touched)
+  return w->togo.set(rec, w->P, w->cfg.Hsample, w->cfg.Nsample, w->env->device);
 }
 
 extern "C" int mbd_sweep_peek_togo(mbd_sweep* w, int k, int32_t* starts_out, float* R_out, float* W_out, int32_t* n_groups_out) {
   if (!w) return fail(MBD_ERR_INVALID, "sweep is NULL");
   if (k < 0 || k >= w->P) return fail(MBD_ERR_INVALID, "peek_togo: plan k=%d outside [0,%d)", k, w->P);
-  const SweepTogoRec& L = w->togo;
-  if (!L.has) return fail(MBD_ERR_STATE, "peek_togo: the sweep has no to-go record");
-  HIP_TRY(hipSetDevice(w->env->device));
-  HIP_TRY(hipDeviceSynchronize());
-  const size_t N = (size_t)w->cfg.Nsample, gn = (size_t)L.G * N;
-  if (starts_out) memcpy(starts_out, L.starts.data(), sizeof(int32_t) * L.G);
-  if (R_out) HIP_TRY(hipMemcpy(R_out, L.d_R + (size_t)k * gn, sizeof(float) * gn, hipMemcpyDeviceToHost));
-  if (W_out) HIP_TRY(hipMemcpy(W_out, L.d_W + (size_t)k * gn, sizeof(float) * gn, hipMemcpyDeviceToHost));
-  // (group 0's weights are the plan's own slice of d_weights, once a step of the record has written them)
-  if (W_out && L.stepped) HIP_TRY(hipMemcpy(W_out, w->d_weights + (size_t)k * N, sizeof(float) * N, hipMemcpyDeviceToHost));
-  if (n_groups_out) *n_groups_out = L.G;
-  return MBD_OK;
+  return w->togo.peek(w->env, k, w->cfg.Nsample, w->d_weights, starts_out, R_out, W_out, n_groups_out, "sweep");
 }
 
 // include/mbd_hip_debug.h: an elite record's two batch launches alone on caller-given arrays for P plans — the injection, then the
@@ -952,31 +835,17 @@ extern "C" int mbd_debug_sweep_elites_step(int P, uint32_t mask, const float* re
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
   const size_t PN = (size_t)P * N, per_plan = (size_t)N * HNu;
   DevBuf<float> d_rews, d_cand, d_ybar, d_g;
-  SweepEliteRec L;
-  L.n = n_elites; L.nominal = nominal; L.rows = n_elites > 0 ? n_elites : 1; L.has = true;
-  const size_t PR = (size_t)P * L.rows;
+  EliteRec L;
   HIP_TRY(d_rews.upload(rews, PN));
   HIP_TRY(d_cand.upload(cand, PN * HNu));
   HIP_TRY(d_ybar.upload(ybar, (size_t)P * HNu));
   if (g) HIP_TRY(d_g.upload(g, HNu));
-  HIP_TRY(L.d_E.alloc_poisoned(PR * HNu));
-  if (E_in && n_elites > 0) HIP_TRY(hipMemcpy(L.d_E, E_in, sizeof(float) * PR * HNu, hipMemcpyHostToDevice));
-  HIP_TRY(L.d_R.alloc_poisoned(PR));
-  HIP_TRY(L.d_src.alloc_poisoned(PR));
-  HIP_TRY(L.d_count.upload(count_in, P));
-  L.log_cap = 1;  // (the log of the scratch record is one entry long per plan)
-  HIP_TRY(L.d_log_count.alloc_poisoned(P));
-  HIP_TRY(L.d_log_kept.alloc_poisoned(P));
-  HIP_TRY(L.d_log_top.alloc_poisoned(P));
-  if (E_in && n_elites > 0) {  // (E' of a masked-out plan must read back as it went in: poison what the caller did not give)
-    for (int k = 0; k < P; ++k)
-      if (count_in[k] < L.rows)
-        HIP_TRY(hipMemset(L.d_E + ((size_t)k * L.rows + count_in[k]) * HNu, 0xff, sizeof(float) * (size_t)(L.rows - count_in[k]) * HNu));
-  }
-  MBD_TRY(L.inject(P, d_cand, (long long)per_plan, HNu, lazy ? 1 : 0, sigma, d_ybar, HNu, d_g, mask, nullptr));
+  MBD_TRY(L.scratch(n_elites, nominal, P, HNu, E_in, count_in));
+  const size_t PR = (size_t)P * L.rows;
+  MBD_TRY(elite_inject(L, P, d_cand, (long long)per_plan, HNu, lazy ? 1 : 0, sigma, d_ybar, HNu, d_g, mask, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(d_cand.download(cand_out, PN * HNu));
-  MBD_TRY(L.select(P, d_rews, N, d_cand, (long long)per_plan, HNu, lazy ? 1 : 0, sigma, d_ybar, HNu, mask, nullptr));
+  MBD_TRY(elite_select(L, P, d_rews, N, d_cand, (long long)per_plan, HNu, lazy ? 1 : 0, sigma, d_ybar, HNu, mask, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(L.d_E.download(E_out, PR * HNu));
   HIP_TRY(L.d_R.download(R_out, PR));
@@ -1008,7 +877,7 @@ extern "C" int mbd_debug_sweep_togo_step(int P, const float* temps, const float*
   if (N > 12288) return fail(MBD_ERR_INVALID, "sweep_togo_step: N=%d above 12288", N);
   if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
   const size_t HNu = (size_t)H * Nu, PN = (size_t)P * N;
-  SweepTogoRec L;
+  TogoRec L;
   L.layout(block, min_tail, H);
   const size_t gn = (size_t)P * L.G * N;
   DevBuf<float> d_temps, d_cand, d_ybar, d_rews, d_rewss, d_out, d_w, d_mean;
@@ -1029,7 +898,7 @@ extern "C" int mbd_debug_sweep_togo_step(int P, const float* temps, const float*
   ScoreBatch sb;
   sb.rews = N; sb.lp = N; sb.weights = N; sb.mean = 1; sb.cand = (long long)N * (long long)HNu; sb.ybar_in = (long long)HNu;
   sb.ybar_out = (long long)HNu; sb.keep = 0; sb.temps = d_temps;
-  MBD_TRY(L.launch(P, d_rewss, A, sb, nullptr));
+  MBD_TRY(togo_launch(L, P, d_rewss, A, sb, nullptr));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(d_out.download(ybar_out, (size_t)P * HNu));
   HIP_TRY(L.d_R.download(R_out, gn));
@@ -1243,7 +1112,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     w->sigma_rec.launch(w->d_sigma, P, 0, true, s);
   } else {
     first_keys_of_tick();
-    sweep_noise(w, sk, 0, s, w->noise_always());  // tick 0, step Nd-1
+    sweep_noise(w, sk, 0, s, w->noise.spec(false));  // tick 0, step Nd-1
   }
   HIP_TRY(hipGetLastError());
   const long long mu_stride = (long long)(Nd - 1) * HNu;
@@ -1254,7 +1123,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
     w->wt.begin();  // (a weighting record's log holds the last tick's steps)
     // with an elite record, ONE launch in front of the tick's first sampler: no elites in tick 0 and without carry, otherwise every
     // episode's shifted E rows forward with its mean
-    MBD_TRY(w->elite.table_all(P, HNu, t == 0 || !w->elite.carry ? -1 : EN, s));
+    MBD_TRY(elite_table_all(w->elite, P, HNu, t == 0 || !w->elite.carry ? -1 : EN, s));
     // with a delay record: every episode's committed rows, the prediction of where they leave it, and the plans from there
     const float* q_in = has_delay ? w->d_mpc_queue + (size_t)(t & 1) * P * Q : nullptr;
     float* q_out = has_delay ? w->d_mpc_queue + (size_t)((t + 1) & 1) * P * Q : nullptr;
@@ -1277,7 +1146,7 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
         st.state0 = plan_from;
         st.mu_in = i == i_start ? (t == 0 ? w->d_zero.get() : w->d_mpc_ybar.get()) : w->d_mu + (size_t)(st.slot - 1) * HNu;
         st.mu_stride = i == i_start ? HNu : mu_stride;
-        st.ns = t == 0 ? w->noise_always() : w->noise_warm();
+        st.ns = w->noise.spec(t != 0);
         MBD_TRY(sweep_pi_step(w, st, sk));
       }
       w->sigma_rec.launch(w->d_sigma, P, t, false, s);
@@ -1295,10 +1164,10 @@ extern "C" int mbd_sweep_run_mpc(mbd_sweep* w, const mbd_mpc_config* mc, const u
       st.next_keys = follows ? &sk : nullptr;
       // (the noise shape and basis of the following step: this tick's, or — behind a tick's last step — a warm tick's,
       // mbd_plan_run_mpc)
-      st.next_ns = (t == 0 && i > 1) ? w->noise_always() : w->noise_warm();
+      st.next_ns = w->noise.spec(!(t == 0 && i > 1));
       st.xref = has_demo ? w->demo.window(t) : nullptr;
       st.rew_xref = has_demo ? w->demo.rew_xref : e->rew_xref;
-      st.g = t == 0 ? w->shape_always() : w->shape_warm();
+      st.g = t == 0 ? w->noise.shape_always() : w->noise.shape_warm();
       MBD_TRY(sweep_step(w, st));
     }
     // the boundary: the logs of M_{.,t}, its first E rows and Ybar of tick t+1; then the rows executed from s_{.,t}
@@ -1497,8 +1366,8 @@ extern "C" int mbd_sweep_mpc_submit(mbd_sweep* w, const float* states) {
   const int D = w->delay.D, Q = D * EN;
   bool any_cold = false, all_cold = true;
   for (int k = 0; k < P; ++k) { any_cold = any_cold || ss.cold[k]; all_cold = all_cold && ss.cold[k]; }
-  const NoiseSpec ns = all_cold ? w->noise_always() : w->noise_warm();
-  if (any_cold && !all_cold && !(w->noise_always() == w->noise_warm()))
+  const NoiseSpec ns = w->noise.spec(!all_cold);
+  if (any_cold && !all_cold && !(w->noise.spec(false) == w->noise.spec(true)))
     return fail(MBD_ERR_UNSUPPORTED, "mpc_submit: some episodes' ticks are cold and some are not, under a noise shape or basis in force "
                                      "in the warm ticks only: one launch samples under one; reset every episode's mean, or none's");
   HIP_TRY(hipSetDevice(e->device));
@@ -1533,7 +1402,7 @@ extern "C" int mbd_sweep_mpc_submit(mbd_sweep* w, const float* states) {
   {  // with an elite record: a cold episode's elites go, the others' shift with their means (or go as well, without carry)
     EliteShifts sh;
     for (int k = 0; k < MBD_SWEEP_MAX_PLANS; ++k) sh.s[k] = ss.cold[k] || !w->elite.carry ? -1 : EN;
-    MBD_TRY(w->elite.table(P, HNu, sh, 0xffffffffu, s));
+    MBD_TRY(elite_table(w->elite, P, HNu, sh, 0xffffffffu, s));
   }
   const int i_start = any_cold ? Nd - 1 : K;
   const long long mu_stride = (long long)(Nd - 1) * HNu;
@@ -1634,7 +1503,7 @@ extern "C" int mbd_sweep_mpc_reset_mean(mbd_sweep* w, int k) {
     HIP_TRY(hipSetDevice(w->env->device));
     EliteShifts sh;
     for (int& v : sh.s) v = -1;
-    MBD_TRY(w->elite.table(w->P, w->HNu, sh, 1u << k, w->stream));
+    MBD_TRY(elite_table(w->elite, w->P, w->HNu, sh, 1u << k, w->stream));
   }
   return MBD_OK;
 }

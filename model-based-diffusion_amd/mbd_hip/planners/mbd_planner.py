@@ -55,12 +55,207 @@ def apply_recommended(args: Args) -> None:
         print(f"override temp_sample to {args.temp_sample}")
 
 
-class Sweep:
+class _Records:
+    """The records a ``Plan`` and a ``Sweep`` both take, written once: ``_prefix`` is the C prefix of the handle's entries
+    ("mbd_plan_" / "mbd_sweep_"), ``self.h`` the handle.  A sweep's record is one record for all its plans."""
+
+    _prefix = None
+
+    def _c(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def _set(self, name, rec):
+        _capi.check(self._c("set_" + name)(self.h, None if rec is None else C.byref(rec)))
+
+    def set_mpc_pick(self, mean=True, prev=True, best=True):
+        """Choose what a tick hands on (include/mbd_hip.h mbd_mpc_pick): of its mean, the incumbent (the last tick's plan shifted)
+        and the best candidate of its last step — those enabled here — the one the plan's env values most.  The picked plan
+        stands wherever the mean stood: the rows executed, the next tick's warm start, ``means``.  ``run_mpc`` then also returns
+        ``pick`` = dict(choice [T], rets [T, 3], best [T]) (a sweep: one dict per episode); a session has ``pick`` after each
+        collect.  ``mean`` alone leaves the episode's bits unchanged and logs the value of every executed plan."""
+        self._set("mpc_pick", _capi.pick_record(mean, prev, best))
+
+    def clear_mpc_pick(self):
+        self._set("mpc_pick", None)
+
+    def has_mpc_pick(self) -> bool:
+        """Whether the handle carries a pick record: asked of the library, so a record set through the C ABI counts."""
+        return _capi.has_mpc_pick(self._c("peek_mpc_pick"), self.h, self._pick_k)
+
+    def set_mpc_demo(self, clip, start_row: int = 0, rew_xref: float = None):
+        """Follow a demonstration on the episode's clock (include/mbd_hip.h mbd_mpc_demo; demo plans only): tick t of
+        ``run_mpc`` plans under the 50 rows of ``clip`` [n_track, L, 3] (car2d: [L, 2]) from row
+        ``start_row + (t + delay_ticks) * exec_steps`` on, rows past the clip's end holding its last row, with ``rew_xref``
+        (None: the env's) as the demo's reward level.  ``run_mpc`` then also returns ``track_err`` [T*E, K] — the distance of
+        every executed control step's tracked positions from its clip row — and ``demo_windows`` [T, K, 50, 3] (car2d: 2; a
+        sweep: one clip and one clock, ``track_err`` [P, T*E, K]).  ``run`` ignores it."""
+        rec, keep = _demo_record(self.env, clip, start_row, rew_xref)
+        self._set("mpc_demo", rec)
+        self._demo_shape = (keep.shape[0], keep.shape[2])
+        del keep  # (the set call has copied the clip)
+
+    def clear_mpc_demo(self):
+        self._set("mpc_demo", None)
+        self._demo_shape = None
+
+    def set_mpc_delay(self, ticks: int, rows0=None):
+        """Plan ahead of the plant (include/mbd_hip.h mbd_mpc_delay): a plan made in tick t of ``run_mpc`` is first executed in
+        tick t + ``ticks`` (1..8).  Meanwhile the system executes the rows it is already committed to — ``rows0``
+        [ticks * exec_steps, Nu] when the episode starts, None: zeros — and every tick plans from the state the plan's env
+        predicts those rows will reach.  ``run_mpc`` then also returns ``predicted`` [T, state_size] (a sweep:
+        [P, T, state_size]), and ``means[t]``'s row 0 belongs to control step (t + ticks) * exec_steps.  ``run`` ignores it."""
+        rec, keep = _delay_record(ticks, rows0, self.Nu)
+        self._set("mpc_delay", rec)
+        self._has_delay = True
+        del keep  # (the set call has copied the rows)
+
+    def clear_mpc_delay(self):
+        self._set("mpc_delay", None)
+        self._has_delay = False
+
+    def set_mpc_sigma(self, cold: float = 1.0, warm: float = 1.0, gain: float = 0.0):
+        """Run a path-integral plan (``update_method`` 1 / 2 / 3: mppi, cma-es, cem) as a receding-horizon controller
+        (include/mbd_hip.h mbd_mpc_sigma): ``run_mpc`` and ``mpc_open`` then accept the plan; a cold tick (tick 0; a session's
+        tick after ``reset_mean``) starts from sigma ``cold``, every other tick from ``warm`` — or, with ``gain`` > 0 (cma-es
+        only, ``warm`` <= ``cold``), from clamp(gain * the sigma the last tick ended with, warm, cold).  ``run_mpc`` then also
+        returns ``sigmas`` [T, 2] (a sweep: [P, T, 2]): what every tick started from and ended with.  ``run`` ignores it.
+        Sessions of path-integral sweeps stay refused."""
+        self._set("mpc_sigma", _sigma_record(cold, warm, gain))
+        self._has_sigma = True
+
+    def clear_mpc_sigma(self):
+        self._set("mpc_sigma", None)
+        self._has_sigma = False
+
+    def set_noise_shape(self, scale, when: str = "always"):
+        """Shape the sampling noise per horizon row and actuator (include/mbd_hip.h mbd_noise_shape): ``scale`` [H, Nu] (or
+        anything that broadcasts to it) of finite values >= 0; a candidate is clip((eps * scale) * sigma_i + Ybar_i).
+        ``when``: "always" — every diffusion step of every call that samples — or "warm": only the ticks t >= 1 of
+        ``run_mpc`` (``mpc.tail_shape`` gives the rows a warm tick has just appended the noise a cold plan starts with).  All
+        ones is no shape, bit for bit; zeros freeze their elements at clip(Ybar_i)."""
+        rec, keep = _noise_record(scale, when, self.H, self.Nu)
+        self._set("noise_shape", rec)
+        del keep  # (the set call has copied the table)
+
+    def clear_noise_shape(self):
+        self._set("noise_shape", None)
+
+    def set_noise_basis(self, W, when: str = "always"):
+        """Correlate the sampling noise along the horizon (include/mbd_hip.h mbd_noise_basis): ``W`` [H, n_knots] of finite
+        values, n_knots <= 16; a step then draws normal(key, (N, n_knots, Nu)) and a candidate is
+        clip(((sum_k W[h, k] eps[n, k, a]) * shape) * sigma_i + Ybar_i) (``mpc.knot_basis`` builds interpolation and hold
+        tables).  ``when`` as ``set_noise_shape``'s, independently of the shape's.  None clears."""
+        rec, keep = (None, None) if W is None else _basis_record(W, when, self.H)
+        self._set("noise_basis", rec)
+        del keep  # (the set call has copied the table)
+
+    def set_objective(self, row_weight=None, effort: float = 0.0, rate: float = 0.0, act_weight=None, prev0=None):
+        """Shape what the plan maximises (include/mbd_hip.h mbd_objective): a candidate's reward becomes
+        sum_h w[h] r[h] / sum(w) - (1 / H) sum_a q[a] (effort * sum_h u^2 + rate * sum_h (u[h] - u[h-1])^2) with ``row_weight`` w
+        [H] (None: the plain mean; ``mpc.discount_weights`` builds a discount with a terminal weight), ``act_weight`` q [Nu] (None:
+        ones) and u[-1] the action executed before the plan begins — ``prev0`` [Nu] (None: the first term is left out; a sweep:
+        every plan's) for ``run`` and the first tick of an episode, the last committed row afterwards.  Every call that samples
+        reads it; ``eval``, the final reward and an episode's reward log keep the env's own rewards."""
+        rec, keep = _objective_record(row_weight, effort, rate, act_weight, prev0, self.H, self.Nu)
+        self._set("objective", rec)
+        del keep  # (the set call has copied the tables)
+
+    def clear_objective(self):
+        self._set("objective", None)
+
+    def set_value(self, net, scale: float = None):
+        """Score every candidate's end state with a terminal value net (include/mbd_hip.h mbd_value): ``net`` is a
+        ``planners.value.ValueNet`` over the env's state record, and a candidate's reward becomes its reward without the record
+        plus ``scale`` * V(final state) (``scale`` None: the net's own; ``value.terminal_scale(weight, Hsample)`` weighs V like
+        ``weight`` further rows).  Every call that samples reads it; ``eval``, the final reward and an episode's reward log keep the
+        env's own rewards.  None clears."""
+        self._set("value", None if net is None else net.record(scale))  # (the set call has copied the net)
+
+    def set_weighting(self, reject_nonfinite=True, ess_frac: float = 0.0, temp_min=None, temp_max=None, iters: int = 12):
+        """Weigh the candidates robustly (include/mbd_hip.h mbd_weighting): with ``reject_nonfinite`` a candidate whose reward is
+        NaN or infinite gets weight 0 and leaves the step's statistics, so one diverged rollout no longer turns the plan's mean
+        into NaN; with ``ess_frac`` in (0, 1] every step chooses its softmax temperature inside [``temp_min``, ``temp_max``] by
+        ``iters`` bisection steps so that the effective sample size of the weights is about ``ess_frac`` times the candidates
+        kept (0: the plan's ``temp_sample``; a sweep: each plan at its own temperature).  Not for plans created with
+        ``enable_demo``."""
+        self._set("weighting", _capi.weighting_record(reject_nonfinite, ess_frac, temp_min, temp_max, iters))
+
+    def clear_weighting(self):
+        self._set("weighting", None)
+
+    def set_elites(self, n_elites: int, nominal=False, carry=False):
+        """Carry a step's best candidates into the next step (include/mbd_hip.h mbd_elites): the ``n_elites`` best candidates of
+        every diffusion step (0 to 32, by the rewards its score read) overwrite the next step's first candidates; ``nominal``:
+        candidate 0 of every step is the step's mean itself, noise-free; ``carry``: a tick boundary shifts the elites with the mean
+        (False: every tick starts without elites).  MBD and mppi plans, unsharded, without ``enable_demo``.  A sweep's plans each
+        have their own elites, count and log."""
+        self._set("elites", _capi.elites_record(n_elites, nominal, carry))
+        self._elites = int(n_elites)
+
+    def clear_elites(self):
+        self._set("elites", None)
+        self._elites = None
+
+    @property
+    def has_elites(self) -> bool:
+        return getattr(self, "_elites", None) is not None
+
+    def set_togo(self, block: int = 1, min_tail: int = 1):
+        """Weigh each horizon row by the return still ahead of it (include/mbd_hip.h mbd_togo): the rows fall into groups of
+        ``block``, a group starting only where at least ``min_tail`` rows are still ahead, and group j's rows are the step's update
+        under weights from the candidates' mean reward from the group's first row onwards (a sweep: each plan under its own
+        temperature).  MBD and mppi plans, unsharded, without ``enable_demo``, at most 12288 candidates, and without an objective,
+        value, weighting, adapt or ensemble record."""
+        self._set("togo", _capi.togo_record(block, min_tail))
+        self._togo = (int(block), int(min_tail))
+
+    def clear_togo(self):
+        self._set("togo", None)
+        self._togo = None
+
+    @property
+    def has_togo(self) -> bool:
+        return getattr(self, "_togo", None) is not None
+
+    def _put_zones(self, call, zones):
+        zones = list(zones)
+        _capi.check(self._c(call)(self.h, C.byref(_zones_record(self.env, zones))))
+        self._zones = len(zones)
+        self._zone_entries = zones
+
+    def set_zones(self, zones):
+        """Keep-out regions and goals for the env's tracked links (include/mbd_hip.h mbd_zones): ``zones`` is a list of
+        ``mpc.zone`` entries.  Every step subtracts from each candidate's reward the mean over the horizon of the entries'
+        penalties at the tracked positions its rollout passed through.  The env must track links (``get_env(name, track=...)``);
+        unsharded plans without ``enable_demo`` and without an ensemble, to-go or pick record.  ``run_mpc`` then also returns
+        ``zone_pen`` and ``zone_clear`` [T*E] (a sweep: [P, T*E]): the penalty and the keep-out clearance of every executed
+        control step."""
+        self._put_zones("set_zones", zones)
+
+    def clear_zones(self):
+        self._set("zones", None)
+        self._zones = None
+
+    @property
+    def has_zones(self) -> bool:
+        return getattr(self, "_zones", None) is not None
+
+    def update_zones(self, zones):
+        """Replace the table of the handle's zone record — move a goal or an obstacle.  Allowed between the ticks of an open
+        session (``MpcSession.update_zones``); the next step plans under the new table."""
+        self._put_zones("update_zones", zones)
+
+
+class Sweep(_Records):
     """Owner of an ``mbd_sweep`` handle: several plans of one env (same sizes and schedule; seeds, start states and
     temperatures may differ) advanced in lockstep — ONE rollout launch over all their candidates and ONE score launch per
     diffusion step (mbd/scripts/run_mbd.py:17-64).  Every plan's result is bit-identical to ``Plan.run`` on its own.
     ``update_method``: 0 MBD plans; 1 / 2 / 3 the path-integral baselines mppi / cma-es / cem (``args`` is then a
-    path_integral.Args: Nrefine plays Ndiffuse)."""
+    path_integral.Args: Nrefine plays Ndiffuse).  A record set on the sweep is one record for all its plans, and the guarantee
+    holds under every one of them: plan k of ``run``, episode k of ``run_mpc`` and of a session, is the single plan's with the
+    same record, bit for bit."""
+
+    _prefix, _pick_k = "mbd_sweep_", 0
 
     def __init__(self, env, args, n_plans: int, temps=None, literal_score: bool = True, update_method: int = 0):
         self.lib = _capi.load()
@@ -153,31 +348,6 @@ class Sweep:
         episodes' states [P, state_size]; ``reset_mean(k)`` makes episode k's next tick a cold one."""
         return MpcSession(self, keys, warm_steps, exec_steps, max_ticks)
 
-    def set_mpc_demo(self, clip, start_row: int = 0, rew_xref: float = None):
-        """One demo record for all episodes of the sweep (``Plan.set_mpc_demo``) — one clip and one clock: episode k of
-        ``run_mpc`` is then ``Plan.run_mpc`` with the same record, bit for bit; ``run_mpc`` also returns ``track_err``
-        [P, T*E, K] and ``demo_windows`` [T, K, 50, 3]."""
-        rec, keep = _demo_record(self.env, clip, start_row, rew_xref)
-        _capi.check(self.lib.mbd_sweep_set_mpc_demo(self.h, C.byref(rec)))
-        self._demo_shape = (keep.shape[0], keep.shape[2])
-        del keep  # (the set call has copied the clip)
-
-    def clear_mpc_demo(self):
-        _capi.check(self.lib.mbd_sweep_set_mpc_demo(self.h, None))
-        self._demo_shape = None
-
-    def set_mpc_sigma(self, cold: float = 1.0, warm: float = 1.0, gain: float = 0.0):
-        """One sigma record for all episodes of a path-integral sweep (``Plan.set_mpc_sigma``): episode k of ``run_mpc`` is then
-        ``Plan.run_mpc`` on a path-integral plan with the same record, bit for bit; ``run_mpc`` also returns ``sigmas``
-        [P, T, 2].  Sessions of path-integral sweeps stay refused."""
-        rec = _sigma_record(cold, warm, gain)
-        _capi.check(self.lib.mbd_sweep_set_mpc_sigma(self.h, C.byref(rec)))
-        self._has_sigma = True
-
-    def clear_mpc_sigma(self):
-        _capi.check(self.lib.mbd_sweep_set_mpc_sigma(self.h, None))
-        self._has_sigma = False
-
     def set_mpc_plant(self, k: int, env=None, key=None, act_std: float = 0.0, kick_std: float = 0.0, kick_every: int = 1):
         """The plant of episode ``k`` (``Plan.set_mpc_plant``): episode k of ``run_mpc`` is then ``Plan.run_mpc`` with that
         record, bit for bit.  Episodes may carry different plants, keys and stds, or none; consecutive episodes that share
@@ -190,70 +360,9 @@ class Sweep:
         _capi.check(self.lib.mbd_sweep_set_mpc_plant(self.h, int(k), None))
         self._plant_envs.pop(int(k), None)
 
-    def set_noise_shape(self, scale, when: str = "always"):
-        """One noise shape for all plans of the sweep (``Plan.set_noise_shape``): plan k of ``run``, episode k of ``run_mpc``,
-        is then the single plan's with the same shape, bit for bit."""
-        rec, keep = _noise_record(scale, when, self.H, self.Nu)
-        _capi.check(self.lib.mbd_sweep_set_noise_shape(self.h, C.byref(rec)))
-        del keep  # (the set call has copied the table)
-
-    def clear_noise_shape(self):
-        _capi.check(self.lib.mbd_sweep_set_noise_shape(self.h, None))
-
-    def set_noise_basis(self, W, when: str = "always"):
-        """One noise basis for all plans of the sweep (``Plan.set_noise_basis``), with the same guarantee; None clears."""
-        if W is None:
-            _capi.check(self.lib.mbd_sweep_set_noise_basis(self.h, None))
-            return
-        rec, keep = _basis_record(W, when, self.H)
-        _capi.check(self.lib.mbd_sweep_set_noise_basis(self.h, C.byref(rec)))
-        del keep  # (the set call has copied the table)
-
-    def set_objective(self, row_weight=None, effort: float = 0.0, rate: float = 0.0, act_weight=None, prev0=None):
-        """One objective record for all plans of the sweep (``Plan.set_objective``; ``prev0`` is every plan's): plan k of ``run``,
-        episode k of ``run_mpc`` and of a session is then the single plan's with the same record, bit for bit."""
-        rec, keep = _objective_record(row_weight, effort, rate, act_weight, prev0, self.H, self.Nu)
-        _capi.check(self.lib.mbd_sweep_set_objective(self.h, C.byref(rec)))
-        del keep  # (the set call has copied the tables)
-
-    def clear_objective(self):
-        _capi.check(self.lib.mbd_sweep_set_objective(self.h, None))
-
-    def set_value(self, net, scale: float = None):
-        """One value record for all plans of the sweep (``Plan.set_value``; one net): plan k of ``run``, episode k of ``run_mpc`` and
-        of a session is then the single plan's with the same record, bit for bit.  None clears."""
-        if net is None:
-            _capi.check(self.lib.mbd_sweep_set_value(self.h, None))
-            return
-        rec = net.record(scale)
-        _capi.check(self.lib.mbd_sweep_set_value(self.h, C.byref(rec)))  # (the set call has copied the net)
-
-    def set_weighting(self, reject_nonfinite=True, ess_frac: float = 0.0, temp_min=None, temp_max=None, iters: int = 12):
-        """One weighting record for all plans of the sweep (``Plan.set_weighting``), each at its own temperature."""
-        rec = _capi.weighting_record(reject_nonfinite, ess_frac, temp_min, temp_max, iters)
-        _capi.check(self.lib.mbd_sweep_set_weighting(self.h, C.byref(rec)))
-
-    def clear_weighting(self):
-        _capi.check(self.lib.mbd_sweep_set_weighting(self.h, None))
-
     def peek_weighting(self, k: int) -> dict:
         """Plan k's ``temp``, ``ess`` and ``kept`` of every score step of the last run or tick (``Plan.peek_weighting``)."""
         return _capi.peek_weighting(self.lib.mbd_sweep_peek_weighting, self.h, k, self.cfg.Ndiffuse - 1)
-
-    def set_elites(self, n_elites: int, nominal=False, carry=False):
-        """One elite record for all plans of the sweep (``Plan.set_elites``): plan k of ``run``, episode k of ``run_mpc`` and of a
-        session is then the single plan's with the same record, bit for bit, with its own elites, count and log."""
-        rec = _capi.elites_record(n_elites, nominal, carry)
-        _capi.check(self.lib.mbd_sweep_set_elites(self.h, C.byref(rec)))
-        self._elites = int(n_elites)
-
-    def clear_elites(self):
-        _capi.check(self.lib.mbd_sweep_set_elites(self.h, None))
-        self._elites = None
-
-    @property
-    def has_elites(self) -> bool:
-        return getattr(self, "_elites", None) is not None
 
     def peek_elites(self, k: int, capacity: int = None) -> dict:
         """Plan k's ``E`` [count, H, Nu], ``R``, ``src``, ``count`` and log (``Plan.peek_elites``)."""
@@ -264,21 +373,6 @@ class Sweep:
         out["E"] = out["E"].reshape(-1, self.H, self.Nu)
         return out
 
-    def set_togo(self, block: int = 1, min_tail: int = 1):
-        """One to-go record for all plans of the sweep (``Plan.set_togo``), each plan under its own temperature, with the same
-        guarantee.  Not beside an objective, value or weighting record."""
-        rec = _capi.togo_record(block, min_tail)
-        _capi.check(self.lib.mbd_sweep_set_togo(self.h, C.byref(rec)))
-        self._togo = (int(block), int(min_tail))
-
-    def clear_togo(self):
-        _capi.check(self.lib.mbd_sweep_set_togo(self.h, None))
-        self._togo = None
-
-    @property
-    def has_togo(self) -> bool:
-        return getattr(self, "_togo", None) is not None
-
     def peek_togo(self, k: int) -> dict:
         """Plan k's ``starts`` [G], ``R`` and ``W`` [G, Nsample] of the last step (``Plan.peek_togo``)."""
         fn = lambda h, *a: self.lib.mbd_sweep_peek_togo(h, int(k), *a)  # noqa: E731
@@ -286,47 +380,11 @@ class Sweep:
             _capi.check(fn(self.h, None, None, None, None))
         return _capi.peek_togo(fn, self.h, self.H, self.cfg.Nsample)
 
-    def set_zones(self, zones):
-        """One zone record for all plans of the sweep (``Plan.set_zones``): plan k of ``run``, episode k of ``run_mpc`` and of a
-        session equals the single plan with that record, bit for bit."""
-        zones = list(zones)
-        rec = _zones_record(self.env, zones)
-        _capi.check(self.lib.mbd_sweep_set_zones(self.h, C.byref(rec)))
-        self._zones = len(zones)
-
-    def clear_zones(self):
-        _capi.check(self.lib.mbd_sweep_set_zones(self.h, None))
-        self._zones = None
-
-    @property
-    def has_zones(self) -> bool:
-        return getattr(self, "_zones", None) is not None
-
-    def update_zones(self, zones):
-        """Replace the table of the sweep's zone record (``Plan.update_zones``)."""
-        zones = list(zones)
-        rec = _zones_record(self.env, zones)
-        _capi.check(self.lib.mbd_sweep_update_zones(self.h, C.byref(rec)))
-        self._zones = len(zones)
-
     def peek_zones(self, k: int) -> dict:
         """Plan ``k``'s ``pen`` and ``clr`` [Nsample] of the last step (``Plan.peek_zones``)."""
         if not self.has_zones:
             _capi.check(self.lib.mbd_sweep_peek_zones(self.h, int(k), None, None))
         return _capi.peek_zones(self.lib.mbd_sweep_peek_zones, self.h, int(k), self.cfg.Nsample)
-
-    def set_mpc_pick(self, mean=True, prev=True, best=True):
-        """One pick record for all episodes of the sweep (``Plan.set_mpc_pick``): episode k of ``run_mpc`` and of a session is
-        then the single plan's with the same record, bit for bit; ``run_mpc`` also returns ``pick``, one dict per episode."""
-        rec = _capi.pick_record(mean, prev, best)
-        _capi.check(self.lib.mbd_sweep_set_mpc_pick(self.h, C.byref(rec)))
-
-    def clear_mpc_pick(self):
-        _capi.check(self.lib.mbd_sweep_set_mpc_pick(self.h, None))
-
-    def has_mpc_pick(self) -> bool:
-        """Whether the sweep carries a pick record: asked of the library, so a record set through the C ABI counts."""
-        return _capi.has_mpc_pick(self.lib.mbd_sweep_peek_mpc_pick, self.h, 0)
 
     def peek_mpc_pick(self, k: int, capacity: int = None) -> dict:
         """Episode k's ``choice`` [n], ``rets`` [n, 3] and ``best`` [n] of the ticks served so far (``Plan.peek_mpc_pick``)."""
@@ -338,18 +396,6 @@ class Sweep:
         ret, cost = np.zeros(N, np.float32), np.zeros(N, np.float32)
         _capi.check(self.lib.mbd_sweep_peek_objective(self.h, int(k), _capi.np_ptr(ret), _capi.np_ptr(cost)))
         return ret, cost
-
-    def set_mpc_delay(self, ticks: int, rows0=None):
-        """One delay record for all episodes of the sweep (``Plan.set_mpc_delay``): episode k of ``run_mpc`` is then
-        ``Plan.run_mpc`` with the same record, bit for bit; ``run_mpc`` also returns ``predicted`` [P, T, state_size]."""
-        rec, keep = _delay_record(ticks, rows0, self.Nu)
-        _capi.check(self.lib.mbd_sweep_set_mpc_delay(self.h, C.byref(rec)))
-        self._has_delay = True
-        del keep  # (the set call has copied the rows)
-
-    def clear_mpc_delay(self):
-        _capi.check(self.lib.mbd_sweep_set_mpc_delay(self.h, None))
-        self._has_delay = False
 
     def get_sigmas(self):
         """path-integral sweeps: every plan's carried sigma after the last run (path_integral.py:113,131)."""
@@ -630,8 +676,10 @@ class MpcSession:
             pass
 
 
-class Plan:
+class Plan(_Records):
     """Thin owner of an ``mbd_plan`` handle."""
+
+    _prefix, _pick_k = "mbd_plan_", None
 
     def __init__(self, env, args, shard_begin: int = 0, shard_count: int = None, literal_score: bool = True,
                  update_method: int = 0, shares_device: bool = False):
@@ -720,22 +768,6 @@ class Plan:
             _capi.check(self.lib.mbd_plan_peek_mpc_zones(self.h, _capi.np_ptr(out["zone_pen"]), _capi.np_ptr(out["zone_clear"])))
         return out
 
-    def set_mpc_pick(self, mean=True, prev=True, best=True):
-        """Choose what a tick hands on (include/mbd_hip.h mbd_mpc_pick): of its mean, the incumbent (the last tick's plan shifted)
-        and the best candidate of its last step — those enabled here — the one the plan's env values most.  The picked plan
-        stands wherever the mean stood: the rows executed, the next tick's warm start, ``means``.  ``run_mpc`` then also returns
-        ``pick`` = dict(choice [T], rets [T, 3], best [T]); a session has ``pick`` after each collect.  ``mean`` alone leaves the
-        episode's bits unchanged and logs the value of every executed plan."""
-        rec = _capi.pick_record(mean, prev, best)
-        _capi.check(self.lib.mbd_plan_set_mpc_pick(self.h, C.byref(rec)))
-
-    def clear_mpc_pick(self):
-        _capi.check(self.lib.mbd_plan_set_mpc_pick(self.h, None))
-
-    def has_mpc_pick(self) -> bool:
-        """Whether the plan carries a pick record: asked of the library, so a record set through the C ABI counts."""
-        return _capi.has_mpc_pick(self.lib.mbd_plan_peek_mpc_pick, self.h, None)
-
     def peek_mpc_pick(self, capacity: int = None) -> dict:
         """``choice`` [n], ``rets`` [n, 3] and ``best`` [n] of the ticks the last episode or the session has served (the most
         recent ``capacity``, oldest first; None: all)."""
@@ -747,51 +779,6 @@ class Plan:
         delay and demo records are read now; a plant record is refused (the caller is the plant).  ``max_ticks`` None: no limit.
         Until the session is closed the plan's other calls are refused."""
         return MpcSession(self, key, warm_steps, exec_steps, max_ticks)
-
-    def set_mpc_demo(self, clip, start_row: int = 0, rew_xref: float = None):
-        """Follow a demonstration on the episode's clock (include/mbd_hip.h mbd_mpc_demo; demo plans only): tick t of
-        ``run_mpc`` plans under the 50 rows of ``clip`` [n_track, L, 3] (car2d: [L, 2]) from row
-        ``start_row + (t + delay_ticks) * exec_steps`` on, rows past the clip's end holding its last row, with ``rew_xref``
-        (None: the env's) as the demo's reward level.  ``run_mpc`` then also returns ``track_err`` [T*E, K] — the distance of
-        every executed control step's tracked positions from its clip row — and ``demo_windows`` [T, K, 50, 3] (car2d: 2).
-        ``run`` ignores it."""
-        rec, keep = _demo_record(self.env, clip, start_row, rew_xref)
-        _capi.check(self.lib.mbd_plan_set_mpc_demo(self.h, C.byref(rec)))
-        self._demo_shape = (keep.shape[0], keep.shape[2])
-        del keep  # (the set call has copied the clip)
-
-    def clear_mpc_demo(self):
-        _capi.check(self.lib.mbd_plan_set_mpc_demo(self.h, None))
-        self._demo_shape = None
-
-    def set_mpc_delay(self, ticks: int, rows0=None):
-        """Plan ahead of the plant (include/mbd_hip.h mbd_mpc_delay): a plan made in tick t of ``run_mpc`` is first executed in
-        tick t + ``ticks`` (1..8).  Meanwhile the system executes the rows it is already committed to — ``rows0``
-        [ticks * exec_steps, Nu] when the episode starts, None: zeros — and every tick plans from the state the plan's env
-        predicts those rows will reach.  ``run_mpc`` then also returns ``predicted`` [T, state_size], and ``means[t]``'s row 0
-        belongs to control step (t + ticks) * exec_steps.  ``run`` ignores it."""
-        rec, keep = _delay_record(ticks, rows0, self.Nu)
-        _capi.check(self.lib.mbd_plan_set_mpc_delay(self.h, C.byref(rec)))
-        self._has_delay = True
-        del keep  # (the set call has copied the rows)
-
-    def clear_mpc_delay(self):
-        _capi.check(self.lib.mbd_plan_set_mpc_delay(self.h, None))
-        self._has_delay = False
-
-    def set_mpc_sigma(self, cold: float = 1.0, warm: float = 1.0, gain: float = 0.0):
-        """Run a path-integral plan (``update_method`` 1 / 2 / 3: mppi, cma-es, cem) as a receding-horizon controller
-        (include/mbd_hip.h mbd_mpc_sigma): ``run_mpc`` and ``mpc_open`` then accept the plan; a cold tick (tick 0; a session's
-        tick after ``reset_mean``) starts from sigma ``cold``, every other tick from ``warm`` — or, with ``gain`` > 0 (cma-es
-        only, ``warm`` <= ``cold``), from clamp(gain * the sigma the last tick ended with, warm, cold).  ``run_mpc`` then also
-        returns ``sigmas`` [T, 2]: what every tick started from and ended with.  ``run`` ignores it."""
-        rec = _sigma_record(cold, warm, gain)
-        _capi.check(self.lib.mbd_plan_set_mpc_sigma(self.h, C.byref(rec)))
-        self._has_sigma = True
-
-    def clear_mpc_sigma(self):
-        _capi.check(self.lib.mbd_plan_set_mpc_sigma(self.h, None))
-        self._has_sigma = False
 
     def set_mpc_plant(self, env=None, key=None, act_std: float = 0.0, kick_std: float = 0.0, kick_every: int = 1):
         """The plant of the plan's episodes (include/mbd_hip.h mbd_mpc_plant): ``run_mpc`` then executes the rows on ``env``
@@ -821,57 +808,6 @@ class Plan:
         _capi.check(self.lib.mbd_plan_set_ensemble(self.h, None))
         self._ens_envs = None
 
-    def set_noise_shape(self, scale, when: str = "always"):
-        """Shape the sampling noise per horizon row and actuator (include/mbd_hip.h mbd_noise_shape): ``scale`` [H, Nu] (or
-        anything that broadcasts to it) of finite values >= 0; a candidate is clip((eps * scale) * sigma_i + Ybar_i).
-        ``when``: "always" — every diffusion step of every call that samples — or "warm": only the ticks t >= 1 of
-        ``run_mpc`` (``mpc.tail_shape`` gives the rows a warm tick has just appended the noise a cold plan starts with).  All
-        ones is no shape, bit for bit; zeros freeze their elements at clip(Ybar_i)."""
-        rec, keep = _noise_record(scale, when, self.H, self.Nu)
-        _capi.check(self.lib.mbd_plan_set_noise_shape(self.h, C.byref(rec)))
-        del keep  # (the set call has copied the table)
-
-    def clear_noise_shape(self):
-        _capi.check(self.lib.mbd_plan_set_noise_shape(self.h, None))
-
-    def set_noise_basis(self, W, when: str = "always"):
-        """Correlate the sampling noise along the horizon (include/mbd_hip.h mbd_noise_basis): ``W`` [H, n_knots] of finite
-        values, n_knots <= 16; a step then draws normal(key, (N, n_knots, Nu)) and a candidate is
-        clip(((sum_k W[h, k] eps[n, k, a]) * shape) * sigma_i + Ybar_i) (``mpc.knot_basis`` builds interpolation and hold
-        tables).  ``when`` as ``set_noise_shape``'s, independently of the shape's.  None clears."""
-        if W is None:
-            _capi.check(self.lib.mbd_plan_set_noise_basis(self.h, None))
-            return
-        rec, keep = _basis_record(W, when, self.H)
-        _capi.check(self.lib.mbd_plan_set_noise_basis(self.h, C.byref(rec)))
-        del keep  # (the set call has copied the table)
-
-    def set_objective(self, row_weight=None, effort: float = 0.0, rate: float = 0.0, act_weight=None, prev0=None):
-        """Shape what the plan maximises (include/mbd_hip.h mbd_objective): a candidate's reward becomes
-        sum_h w[h] r[h] / sum(w) - (1 / H) sum_a q[a] (effort * sum_h u^2 + rate * sum_h (u[h] - u[h-1])^2) with ``row_weight`` w
-        [H] (None: the plain mean; ``mpc.discount_weights`` builds a discount with a terminal weight), ``act_weight`` q [Nu] (None:
-        ones) and u[-1] the action executed before the plan begins — ``prev0`` [Nu] (None: the first term is left out) for
-        ``run`` and the first tick of an episode, the last committed row afterwards.  Every call that samples reads it;
-        ``eval``, the final reward and an episode's reward log keep the env's own rewards."""
-        rec, keep = _objective_record(row_weight, effort, rate, act_weight, prev0, self.H, self.Nu)
-        _capi.check(self.lib.mbd_plan_set_objective(self.h, C.byref(rec)))
-        del keep  # (the set call has copied the tables)
-
-    def clear_objective(self):
-        _capi.check(self.lib.mbd_plan_set_objective(self.h, None))
-
-    def set_value(self, net, scale: float = None):
-        """Score every candidate's end state with a terminal value net (include/mbd_hip.h mbd_value): ``net`` is a
-        ``planners.value.ValueNet`` over the env's state record, and a candidate's reward becomes its reward without the record
-        plus ``scale`` * V(final state) (``scale`` None: the net's own; ``value.terminal_scale(weight, Hsample)`` weighs V like
-        ``weight`` further rows).  Every call that samples reads it; ``eval``, the final reward and an episode's reward log keep the
-        env's own rewards.  None clears."""
-        if net is None:
-            _capi.check(self.lib.mbd_plan_set_value(self.h, None))
-            return
-        rec = net.record(scale)
-        _capi.check(self.lib.mbd_plan_set_value(self.h, C.byref(rec)))  # (the set call has copied the net)
-
     def peek_value(self):
         """The last step's V [shard_count] (a plan with a value record)."""
         v = np.zeros(self.cfg.shard_count, np.float32)
@@ -886,18 +822,6 @@ class Plan:
         v = np.full(states.shape[0], np.nan, np.float32)
         _capi.check(self.lib.mbd_plan_eval_value(self.h, _capi.np_ptr(states), states.shape[0], _capi.np_ptr(v)))
         return v
-
-    def set_weighting(self, reject_nonfinite=True, ess_frac: float = 0.0, temp_min=None, temp_max=None, iters: int = 12):
-        """Weigh the candidates robustly (include/mbd_hip.h mbd_weighting): with ``reject_nonfinite`` a candidate whose reward is
-        NaN or infinite gets weight 0 and leaves the step's statistics, so one diverged rollout no longer turns the plan's mean
-        into NaN; with ``ess_frac`` in (0, 1] every step chooses its softmax temperature inside [``temp_min``, ``temp_max``] by
-        ``iters`` bisection steps so that the effective sample size of the weights is about ``ess_frac`` times the candidates
-        kept (0: the plan's ``temp_sample``).  Not for plans created with ``enable_demo``."""
-        rec = _capi.weighting_record(reject_nonfinite, ess_frac, temp_min, temp_max, iters)
-        _capi.check(self.lib.mbd_plan_set_weighting(self.h, C.byref(rec)))
-
-    def clear_weighting(self):
-        _capi.check(self.lib.mbd_plan_set_weighting(self.h, None))
 
     def peek_weighting(self) -> dict:
         """``temp``, ``ess`` and ``kept``, one entry per score step of the last ``run``, the last phase call or the last tick (a
@@ -923,23 +847,6 @@ class Plan:
         out["a"] = out["a"].reshape(self.H, self.Nu)
         return out
 
-    def set_elites(self, n_elites: int, nominal=False, carry=False):
-        """Carry a step's best candidates into the next step (include/mbd_hip.h mbd_elites): the ``n_elites`` best candidates of
-        every diffusion step (0 to 32, by the rewards its score read) overwrite the next step's first candidates; ``nominal``:
-        candidate 0 of every step is the step's mean itself, noise-free; ``carry``: a tick boundary shifts the elites with the mean
-        (False: every tick starts without elites).  MBD and mppi plans, unsharded, without ``enable_demo``."""
-        rec = _capi.elites_record(n_elites, nominal, carry)
-        _capi.check(self.lib.mbd_plan_set_elites(self.h, C.byref(rec)))
-        self._elites = int(n_elites)
-
-    def clear_elites(self):
-        _capi.check(self.lib.mbd_plan_set_elites(self.h, None))
-        self._elites = None
-
-    @property
-    def has_elites(self) -> bool:
-        return getattr(self, "_elites", None) is not None
-
     def peek_elites(self, capacity: int = None) -> dict:
         """``E`` [count, H, Nu], ``R`` and ``src`` [count]: the elites as they stand; ``log_count`` / ``log_kept`` / ``log_top``: per
         step since the last ``run``, episode or session began — or the most recent ``capacity`` of them — how many elites the step
@@ -950,58 +857,12 @@ class Plan:
         out["E"] = out["E"].reshape(-1, self.H, self.Nu)
         return out
 
-    def set_togo(self, block: int = 1, min_tail: int = 1):
-        """Weigh each horizon row by the return still ahead of it (include/mbd_hip.h mbd_togo): the rows fall into groups of
-        ``block``, a group starting only where at least ``min_tail`` rows are still ahead, and group j's rows are the step's update
-        under weights from the candidates' mean reward from the group's first row onwards.  MBD and mppi plans, unsharded, without
-        ``enable_demo``, at most 12288 candidates, and without an objective, value, weighting, adapt or ensemble record."""
-        rec = _capi.togo_record(block, min_tail)
-        _capi.check(self.lib.mbd_plan_set_togo(self.h, C.byref(rec)))
-        self._togo = (int(block), int(min_tail))
-
-    def clear_togo(self):
-        _capi.check(self.lib.mbd_plan_set_togo(self.h, None))
-        self._togo = None
-
-    @property
-    def has_togo(self) -> bool:
-        return getattr(self, "_togo", None) is not None
-
     def peek_togo(self) -> dict:
         """``starts`` [G] the groups' first rows, ``R`` and ``W`` [G, Nsample] the groups' returns and weights of the last step (a
         plan with a to-go record); row 0 is the rewards the score read and the weights ``peek`` returns."""
         if not self.has_togo:
             _capi.check(self.lib.mbd_plan_peek_togo(self.h, None, None, None, None))
         return _capi.peek_togo(self.lib.mbd_plan_peek_togo, self.h, self.H, self.cfg.Nsample)
-
-    def set_zones(self, zones):
-        """Keep-out regions and goals for the env's tracked links (include/mbd_hip.h mbd_zones): ``zones`` is a list of
-        ``mpc.zone`` entries.  Every step subtracts from each candidate's reward the mean over the horizon of the entries'
-        penalties at the tracked positions its rollout passed through.  The env must track links (``get_env(name, track=...)``);
-        unsharded plans without ``enable_demo`` and without an ensemble, to-go or pick record.  ``run_mpc`` then also returns
-        ``zone_pen`` and ``zone_clear`` [T*E]: the penalty and the keep-out clearance of every executed control step."""
-        zones = list(zones)
-        rec = _zones_record(self.env, zones)
-        _capi.check(self.lib.mbd_plan_set_zones(self.h, C.byref(rec)))
-        self._zones = len(zones)
-        self._zone_entries = zones
-
-    def clear_zones(self):
-        _capi.check(self.lib.mbd_plan_set_zones(self.h, None))
-        self._zones = None
-
-    @property
-    def has_zones(self) -> bool:
-        return getattr(self, "_zones", None) is not None
-
-    def update_zones(self, zones):
-        """Replace the table of the plan's zone record — move a goal or an obstacle.  Allowed between the ticks of an open
-        session (``MpcSession.update_zones``); the next step plans under the new table."""
-        zones = list(zones)
-        rec = _zones_record(self.env, zones)
-        _capi.check(self.lib.mbd_plan_update_zones(self.h, C.byref(rec)))
-        self._zones = len(zones)
-        self._zone_entries = zones
 
     def peek_zones(self) -> dict:
         """``pen`` and ``clr`` [Nsample] of the last step (a plan with a zone record): each candidate's penalty and its smallest

@@ -734,6 +734,40 @@ def _reset_and_key(env, seed: int):
     return state_init, rng_exp
 
 
+def _set_records(handle, env, args: MpcArgs, after_sigma=None, after_value=None) -> None:
+    """The records a ``Plan`` and a ``Sweep`` both take, in the one order of their set calls (a sweep: one record for all episodes —
+    ``_check_batch`` has held the fields equal).  ``after_sigma`` / ``after_value``: where a plan's set calls of what only a plan
+    takes stand in that order — the plant and the ensemble record; the adapt record."""
+    if _has_sigma(args):
+        handle.set_mpc_sigma(*_sigma_of(args))
+    if after_sigma:
+        after_sigma()
+    if _has_shape(args):
+        handle.set_noise_shape(*_shape_of(args, env.action_size))
+    if _has_basis(args):
+        handle.set_noise_basis(*_basis_of(args))
+    if _has_delay(args):
+        handle.set_mpc_delay(args.delay_ticks)
+    if _has_demo(args):
+        handle.set_mpc_demo(*_demo_of(env, args))
+    if _has_objective(args):
+        handle.set_objective(**_objective_of(args))
+    if _has_weighting(args):
+        handle.set_weighting(**_weighting_of(args))
+    if _has_pick(args):
+        handle.set_mpc_pick(**_pick_of(args))
+    if _has_value(args):
+        handle.set_value(*_value_of(args))
+    if after_value:
+        after_value()
+    if _has_elites(args):  # (a sweep: every episode has its own elites)
+        handle.set_elites(**_elites_of(args))
+    if _has_togo(args):
+        handle.set_togo(**_togo_of(args))
+    if _has_zones(args):
+        handle.set_zones(parse_zones(args.zones))
+
+
 def _setup(args: MpcArgs, device: int, online: bool = False):
     """``online``: no plant record is set — the caller executes the rows (``run_mpc_online``)."""
     _check_togo(args)
@@ -742,37 +776,19 @@ def _setup(args: MpcArgs, device: int, online: bool = False):
     state_init, rng_exp = _reset_and_key(env, args.seed)
     plan = Plan(env, args, update_method=_method(args))
     plan.set_state0(state_init)
-    if _has_sigma(args):
-        plan.set_mpc_sigma(*_sigma_of(args))
     cache = {}
-    if _has_plant(args) and not online:
-        plan.set_mpc_plant(**_record_kwargs(env, args, device, cache))
-    if _has_ensemble(args):
-        plan.set_ensemble(_ensemble_envs(env, args, device, cache), args.ens_risk)
-    if _has_shape(args):
-        plan.set_noise_shape(*_shape_of(args, env.action_size))
-    if _has_basis(args):
-        plan.set_noise_basis(*_basis_of(args))
-    if _has_delay(args):
-        plan.set_mpc_delay(args.delay_ticks)
-    if _has_demo(args):
-        plan.set_mpc_demo(*_demo_of(env, args))
-    if _has_objective(args):
-        plan.set_objective(**_objective_of(args))
-    if _has_weighting(args):
-        plan.set_weighting(**_weighting_of(args))
-    if _has_pick(args):
-        plan.set_mpc_pick(**_pick_of(args))
-    if _has_value(args):
-        plan.set_value(*_value_of(args))
-    if _has_adapt(args):
-        plan.set_adapt(**_adapt_of(args))
-    if _has_elites(args):
-        plan.set_elites(**_elites_of(args))
-    if _has_togo(args):
-        plan.set_togo(**_togo_of(args))
-    if _has_zones(args):
-        plan.set_zones(parse_zones(args.zones))
+
+    def plant_and_ensemble():
+        if _has_plant(args) and not online:
+            plan.set_mpc_plant(**_record_kwargs(env, args, device, cache))
+        if _has_ensemble(args):
+            plan.set_ensemble(_ensemble_envs(env, args, device, cache), args.ens_risk)
+
+    def adapt():
+        if _has_adapt(args):
+            plan.set_adapt(**_adapt_of(args))
+
+    _set_records(plan, env, args, plant_and_ensemble, adapt)
     return env, plan, state_init, rng_exp
 
 
@@ -921,30 +937,7 @@ def _setup_batch(arg_list, device: int):
     a0 = arg_list[0]
     env = _get_env(a0, device)
     sweep = Sweep(env, a0, len(arg_list), temps=[a.temp_sample for a in arg_list], update_method=_method(a0))
-    if _has_sigma(a0):  # (one record for all episodes: _check_batch has held the four fields equal)
-        sweep.set_mpc_sigma(*_sigma_of(a0))
-    if _has_shape(a0):  # (one shape for all episodes: _check_batch has held the three fields equal)
-        sweep.set_noise_shape(*_shape_of(a0, env.action_size))
-    if _has_basis(a0):  # (and one basis)
-        sweep.set_noise_basis(*_basis_of(a0))
-    if _has_delay(a0):  # (and one delay)
-        sweep.set_mpc_delay(a0.delay_ticks)
-    if _has_demo(a0):  # (one clip and one clock)
-        sweep.set_mpc_demo(*_demo_of(env, a0))
-    if _has_objective(a0):  # (and one objective)
-        sweep.set_objective(**_objective_of(a0))
-    if _has_weighting(a0):  # (and one weighting record)
-        sweep.set_weighting(**_weighting_of(a0))
-    if _has_pick(a0):  # (and one pick record)
-        sweep.set_mpc_pick(**_pick_of(a0))
-    if _has_value(a0):  # (and one value net)
-        sweep.set_value(*_value_of(a0))
-    if _has_elites(a0):  # (and one elite record: every episode has its own elites)
-        sweep.set_elites(**_elites_of(a0))
-    if _has_togo(a0):  # (and one to-go record)
-        sweep.set_togo(**_togo_of(a0))
-    if _has_zones(a0):  # (and one zone record: _check_batch has held the two fields equal)
-        sweep.set_zones(parse_zones(a0.zones))
+    _set_records(sweep, env, a0)
     states, keys, plants = [], [], {}
     for k, a in enumerate(arg_list):
         state_init, rng_exp = _reset_and_key(env, a.seed)
@@ -1206,32 +1199,12 @@ def _main_batch(args: MpcArgs, P: int) -> dict:
         sweep.close()
         plan = Plan(env, a0, update_method=_method(a0))
         plan.set_state0(states[0])
-        if _has_sigma(a0):
-            plan.set_mpc_sigma(*_sigma_of(a0))
-        if _has_plant(a0):
-            plan.set_mpc_plant(**_record_kwargs(env, a0, 0))
-        if _has_shape(a0):
-            plan.set_noise_shape(*_shape_of(a0, env.action_size))
-        if _has_basis(a0):
-            plan.set_noise_basis(*_basis_of(a0))
-        if _has_delay(a0):
-            plan.set_mpc_delay(a0.delay_ticks)
-        if _has_demo(a0):
-            plan.set_mpc_demo(*_demo_of(env, a0))
-        if _has_objective(a0):
-            plan.set_objective(**_objective_of(a0))
-        if _has_weighting(a0):
-            plan.set_weighting(**_weighting_of(a0))
-        if _has_pick(a0):
-            plan.set_mpc_pick(**_pick_of(a0))
-        if _has_value(a0):
-            plan.set_value(*_value_of(a0))
-        if _has_elites(a0):
-            plan.set_elites(**_elites_of(a0))
-        if _has_togo(a0):
-            plan.set_togo(**_togo_of(a0))
-        if _has_zones(a0):
-            plan.set_zones(parse_zones(a0.zones))
+
+        def plant():
+            if _has_plant(a0):
+                plan.set_mpc_plant(**_record_kwargs(env, a0, 0))
+
+        _set_records(plan, env, a0, plant)
         plan.run_mpc(keys[0], T, K, E)  # warm-up
         _, _, _, open_secs_1 = plan.run(keys[0])
         seq = plan.run_mpc(keys[0], T, K, E)
