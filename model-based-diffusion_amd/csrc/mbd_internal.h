@@ -8,6 +8,9 @@
 // loops over it, every record's members), mbd_sweep.hip (sweeps: several plans per launch), mbd_exchange.hip (the in-library
 // exchange), mbd_debug_math.hip (mbd_math.h over arrays); mbd_pk2.hip, mbd_planar.hip and mbd_hot3d.hip hold rollout
 // instantiations only.  mbd_ring.h: the ring logs' arithmetic, which includes nothing and is tested on the host alone.
+// No step kernel is visible from here: a static kernel is emitted by every unit that sees it, so a unit that launches step kernels
+// includes their header itself (mbd_env.hip: mbd_env_kernels.h; mbd_plan.hip, mbd_sweep.hip: mbd_step_kernels.h), and this header
+// takes the three argument structs its records keep by value from mbd_step_args.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -31,7 +34,7 @@
 #include "mbd_kernels.h"
 #include "mbd_launch.h"
 #include "mbd_ring.h"
-#include "mbd_step_kernels.h"
+#include "mbd_step_args.h"
 
 using namespace mbd;
 
@@ -583,7 +586,7 @@ int refuse_beside_zones(const char* who, const char* handle = "plan");
 // The weighting record of a plan or a sweep (include/mbd_hip.h mbd_weighting) as the handle keeps it.  check_weighting: the refusals
 // the record alone decides, in the header's order, each naming the field, before any device access.  set: behind the handle's NULL,
 // session and enable_demo checks (nullptr clears); makes room for the log — three arrays [P][cap], cap = Ndiffuse - 1 entries per
-// plan — and, where the N rewards outgrow the default LDS window, raises weigh_kernel's.  begin(): a run, a phase call or a tick
+// plan (weigh_kernel's LDS window is the launching unit's to raise: mbd_plan_set_weighting).  begin(): a run, a phase call or a tick
 // starts its log; slot(): where the next score step's entry goes (plan 0's; weigh_kernel adds plan k's stride), count advanced.
 struct WeightingRec {
   bool has = false;

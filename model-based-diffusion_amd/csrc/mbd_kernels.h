@@ -2,8 +2,10 @@
 // mbd/planners/mbd_planner.py:109 — jax.vmap(rollout_us) of the positional rigid-body step (utils.py:14-20; A2/A3 of
 // SURVEY.md §8) — and what every rollout unit shares: RolloutParams, the DPP exchange, the noise generator that rides in
 // spare workgroups, the per-lane constant records.  The other kernels of a step (sampling, score, weighted mean, sweeps'
-// batched forms, path-integral updates, car2d) are in mbd_step_kernels.h; the two-candidates-per-lane and planar rollouts
-// in mbd_pk2.h / mbd_planar.h.
+// batched forms, path-integral updates) are in mbd_step_kernels.h, car2d, the demo log-densities and the gather of the
+// per-lane records in mbd_env_kernels.h; the two-candidates-per-lane and planar rollouts in mbd_pk2.h / mbd_planar.h.
+// (MBD_SHARED_ONLY, which mbd_pk2.hip, mbd_planar.hip and mbd_hot3d.hip still define, kept that gather kernel out of those
+// units while it lived here; nothing reads the macro any more.)
 //
 // Layout of the rollout kernel (the one that matters): ONE LINK PER LANE.  A candidate occupies LPS
 // consecutive lanes of a wavefront (LPS = 16 for the 11-link humanoid, 8 for the 7-link cheetah, 4 for
@@ -750,171 +752,6 @@ struct LaneRec3 {
   // owner (the lane itself otherwise); is_owner / is_helper.
   int help_src_rel, help_from_rel[2], is_owner, is_helper;
 };
-#ifndef MBD_SHARED_ONLY  // (translation units that only want the shared pieces: mbd_pk2.hip)
-// lps lanes; dpp: the lane <-> link table of a DPP layout is in force (else lane = link); axi: axisymmetric inertia
-// instantiation (the tensors are remapped to (a, a, c, u)).  The code of the former kernel prologue, unchanged.
-static __global__ void lane_setup3_kernel(const mbd_model_t* __restrict__ M, const signed char* __restrict__ lane_tab, int LPS,
-                                   int dpp, int axi, LaneRec3* __restrict__ out, int helpers = 0) {
-  const int l_lane = threadIdx.x;
-  if (l_lane >= LPS) return;
-  const bool DPP = dpp != 0;
-  LaneRec3 R;
-  const int L = M->n_links, Nu = M->n_act, K = M->n_track;
-  const int l_link = DPP ? (int)lane_tab[l_lane] : l_lane;  // the link this lane holds
-  const bool link_ok = l_link >= 0 && l_link < L;
-  const int l = link_ok ? l_link : 0;
-  auto lane_of = [&](int link) { return DPP ? (int)lane_tab[16 + link] : link; };  // (relative to the group's first lane)
-  const int lane = l_lane;
-  const int parent = M->parent[l];
-  const int nr = M->n_rot[l];
-  const bool is_joint = link_ok && nr >= 0;
-  const int ns = M->n_slide[l];  // (kernels without slide joints ignore everything slide-related)
-  const bool world_parent = parent < 0;
-  R.l = l; R.link_ok = link_ok; R.root_lane = link_ok && l == 0; R.parent = parent; R.nr = nr; R.is_joint = is_joint;
-  R.ns = ns; R.world_parent = world_parent; R.nr_eff = is_joint ? nr : -1;
-  R.plane_rel = parent >= 0 ? lane_of(parent) : lane;
-  Inert<false> ic, ip;
-  ic.inv_mass = M->inv_mass[l];
-  ip.inv_mass = world_parent ? 0.0f : M->inv_mass[parent >= 0 ? parent : 0];
-  for (int k = 0; k < 6; ++k) {
-    ic.ib[k] = M->inv_inertia[l][k];
-    ip.ib[k] = world_parent ? 0.0f : M->inv_inertia[parent >= 0 ? parent : 0][k];
-  }
-  if (axi) { axi_remap<false>(ic); axi_remap<false>(ip); }
-  R.ic_inv_mass = ic.inv_mass; R.ip_inv_mass = ip.inv_mass;
-  for (int k = 0; k < 6; ++k) { R.ic_ib[k] = ic.ib[k]; R.ip_ib[k] = ip.ib[k]; }
-  for (int k = 0; k < 3; ++k) { R.ap_pos[k] = M->ap_pos[l][k]; R.ac_pos[k] = M->ac_pos[l][k]; }
-  for (int k = 0; k < 4; ++k) { R.ap_rot[k] = M->ap_rot[l][k]; R.ac_rot[k] = M->ac_rot[l][k]; }
-  const q4 ap_rot = q4{M->ap_rot[l][0], M->ap_rot[l][1], M->ap_rot[l][2], M->ap_rot[l][3]};
-  // non-joint lanes (free root, padding) are masked through their scalars: every contribution they
-  // compute is then an exact zero
-  R.ang_damp = is_joint ? M->ang_damp[l] : 0.0f; R.vel_damp = is_joint ? M->vel_damp[l] : 0.0f;
-  const int zero_lane = M->n_rot[0] < 0 ? lane_of(0) : (L < LPS ? L : -1);  // a lane contributing zeros
-  R.need_child_mask = !(M->n_rot[0] < 0) && !(L < LPS);
-  R.lane_of1_rel = lane_of(1);
-  v3 saxis[3];
-  int act_rot[3], act_sl[3];
-  float gear_rot[3], gear_sl[3], alo_rot[3], ahi_rot[3], alo_sl[3], ahi_sl[3];
-  for (int k = 0; k < 3; ++k) {
-    R.lim_lo[k] = M->rot_lo[l][k]; R.lim_hi[k] = M->rot_hi[l][k];
-    R.stiff[k] = M->rot_stiff[l][k]; R.damp[k] = M->rot_damp[l][k];
-    saxis[k] = mk3(M->slide_axis[l][k][0], M->slide_axis[l][k][1], M->slide_axis[l][k][2]);
-    R.sl_lo[k] = M->slide_lo[l][k]; R.sl_hi[k] = M->slide_hi[l][k]; R.sl_damp[k] = M->slide_damp[l][k];
-    act_rot[k] = -1; act_sl[k] = -1;
-    gear_rot[k] = gear_sl[k] = 0.0f; alo_rot[k] = alo_sl[k] = 0.0f; ahi_rot[k] = ahi_sl[k] = 0.0f;
-  }
-  for (int a = 0; a < Nu; ++a) {
-    if (M->act_link[a] != l || !link_ok) continue;
-    const int s = M->act_slot[a];
-    for (int k = 0; k < 3; ++k) {
-      if (s == k) { act_rot[k] = a; gear_rot[k] = M->act_gear[a]; alo_rot[k] = M->act_lo[a]; ahi_rot[k] = M->act_hi[a]; }
-      if (s == 3 + k) { act_sl[k] = a; gear_sl[k] = M->act_gear[a]; alo_sl[k] = M->act_lo[a]; ahi_sl[k] = M->act_hi[a]; }
-    }
-  }
-  // Slide slots a joint does not have are masked in the CONSTANTS, once: a zero axis makes the slot's velocity,
-  // force, projection and limit terms exact zeros (everything it multiplies is finite).  Hinge slots are NOT
-  // masked that way: the Euler angles of a slot the joint lacks are meaningless and can overflow near the gimbal
-  // singularity, so they are discarded by selects (0 * inf would be NaN).
-  for (int k = 0; k < 3; ++k) {
-    const bool has_sl = is_joint && k < ns;
-    saxis[k] = sel3(has_sl, saxis[k], mk3(0.0f, 0.0f, 0.0f));
-    gear_sl[k] = has_sl ? gear_sl[k] : 0.0f;
-    const v3 sw = rot(saxis[k], ap_rot);  // SLIDEW: the slide axes in the world frame, once
-    R.saxis[k][0] = saxis[k].x; R.saxis[k][1] = saxis[k].y; R.saxis[k][2] = saxis[k].z;
-    R.saxis_w[k][0] = sw.x; R.saxis_w[k][1] = sw.y; R.saxis_w[k][2] = sw.z;
-    R.act_rot[k] = act_rot[k]; R.act_sl[k] = act_sl[k];
-    R.gear_rot[k] = gear_rot[k]; R.gear_sl[k] = gear_sl[k];
-    R.alo_rot[k] = alo_rot[k]; R.ahi_rot[k] = ahi_rot[k]; R.alo_sl[k] = alo_sl[k]; R.ahi_sl[k] = ahi_sl[k];
-  }
-  int child_lane[4] = {-1, -1, -1, -1};
-  {
-    int nc = 0;
-    for (int c = l + 1; c < L; ++c)
-      if (M->parent[c] == l && link_ok) {
-        if (nc < 4) child_lane[nc] = lane_of(c);
-        ++nc;
-      }
-  }
-  for (int c = 0; c < 4; ++c) {
-    R.child_lane_rel[c] = child_lane[c];
-    R.child_src_rel[c] = child_lane[c] >= 0 ? child_lane[c] : (zero_lane >= 0 ? zero_lane : lane);
-  }
-  // DPP layout: 0/1 masks — rm[s]: this link has an s-th child (it sits at lane - Ds); pm[s]: this link is the
-  // s-th child of its parent (which sits at lane + Ds)
-  int myslot = -1;
-  if (DPP && link_ok && parent >= 0) {
-    myslot = 0;
-    for (int c = 0; c < l; ++c) myslot += M->parent[c] == parent ? 1 : 0;
-  }
-  for (int k = 0; k < 4; ++k) {
-    R.rm[k] = (DPP && child_lane[k] >= 0) ? 1.0f : 0.0f;
-    R.pm[k] = (DPP && myslot == k) ? 1.0f : 0.0f;
-  }
-  {
-    int nc = 0;
-    for (int j = 0; j < 5; ++j) { R.col_has[j] = 0; R.col_rad[j] = 0.0f; R.col_pos[j][0] = R.col_pos[j][1] = R.col_pos[j][2] = 0.0f; }
-    for (int k = 0; k < M->n_col; ++k)
-      if (M->col_link[k] == l && link_ok) {
-        if (nc < 5) {
-          R.col_has[nc] = 1; R.col_rad[nc] = M->col_radius[k];
-          R.col_pos[nc][0] = M->col_pos[k][0]; R.col_pos[nc][1] = M->col_pos[k][1]; R.col_pos[nc][2] = M->col_pos[k][2];
-        }
-        ++nc;
-      }
-  }
-  R.help_src_rel = lane; R.help_from_rel[0] = R.help_from_rel[1] = lane; R.is_owner = 0; R.is_helper = 0;
-  if (helpers && DPP) {
-    // the one link with more than two colliders, its first two idle lanes (the host checked that all of this exists)
-    int owner = -1;
-    for (int c = 0; c < L && owner < 0; ++c) {
-      int n = 0;
-      for (int k = 0; k < M->n_col; ++k) n += M->col_link[k] == c ? 1 : 0;
-      if (n > 2) owner = c;
-    }
-    int idle[2] = {-1, -1}, ni = 0;
-    for (int q = 0; q < LPS && ni < 2; ++q)
-      if ((int)lane_tab[q] < 0) idle[ni++] = q;
-    if (owner >= 0 && ni == 2) {
-      const int owner_lane = lane_of(owner);
-      const int which = lane == idle[0] ? 0 : (lane == idle[1] ? 1 : -1);
-      if (link_ok && l == owner) {
-        R.is_owner = 1; R.help_from_rel[0] = idle[0]; R.help_from_rel[1] = idle[1];
-        for (int j = 2; j < 5; ++j) R.col_has[j] = 0;  // (stage (4) of the owner runs slots 0, 1; the rest come from the helpers)
-      } else if (which >= 0) {
-        R.is_helper = 1; R.help_src_rel = owner_lane;
-        int nc = 0;
-        for (int k = 0; k < M->n_col; ++k)
-          if (M->col_link[k] == owner) {
-            const int slot = nc - 2 - 2 * which;  // helper 0: colliders 2, 3; helper 1: collider 4 (and 5)
-            if (slot >= 0 && slot < 2) {
-              R.col_has[slot] = 1; R.col_rad[slot] = M->col_radius[k];
-              R.col_pos[slot][0] = M->col_pos[k][0]; R.col_pos[slot][1] = M->col_pos[k][1]; R.col_pos[slot][2] = M->col_pos[k][2];
-            }
-            ++nc;
-          }
-        R.ic_inv_mass = M->inv_mass[owner];
-        for (int k = 0; k < 6; ++k) R.ic_ib[k] = M->inv_inertia[owner][k];
-      }
-    }
-  }
-  int track_k = -1;
-  for (int k = 0; k < K; ++k)
-    if (M->track_link[k] == l && link_ok) track_k = k;
-  R.track_k = track_k;
-  for (int k = 0; k < 3; ++k) R.com[k] = M->com[l][k];
-  R.js_pos = is_joint ? M->joint_scale_pos : 0.0f; R.js_ang = is_joint ? M->joint_scale_ang : 0.0f;
-  R.invm_sum = ip.inv_mass + ic.inv_mass;
-  // isotropic models: the shares of an angular correction, (-ib_p, ib_c)/(ib_p + ib_c) * joint_scale_ang
-  // (zero on non-joint lanes through js_ang)
-  {
-    const float ibs = ip.ib[0] + ic.ib[0];
-    R.kang2[0] = -((ip.ib[0] / ibs) * R.js_ang); R.kang2[1] = (ic.ib[0] / ibs) * R.js_ang;
-  }
-  out[l_lane] = R;
-}
-
-#endif  // MBD_SHARED_ONLY
-
 // LPS   lanes per candidate (power of two >= n_links)
 // ISO   model-wide isotropic inverse inertia (spring_inertia_scale = 1 models: the humanoid)
 // SLIDES any slide dof in the model (planar roots of hopper / halfcheetah)

@@ -10,6 +10,7 @@
 #define MBD_TOGO_KERNEL 1   // ... and the to-go record's (plans only)
 #define MBD_ZONE_KERNEL 1   // ... and, for plans and sweeps alike, the zone record's
 #include "mbd_internal.h"
+#include "mbd_step_kernels.h"
 #include "../../include/mbd_hip_debug.h"
 
 // LAZY plans (the MBD update on a rigid-body env): the candidates are never materialised.  eps[b] holds the normals
@@ -2271,7 +2272,10 @@ extern "C" int mbd_debug_weighting_host(const float* rews, int N, float temp, in
   return MBD_OK;
 }
 
+// (N is no longer read — the launching unit raises weigh_kernel's LDS window, mbd_plan_set_weighting — and stays in the signature:
+// the member is one of the library's symbols, and the symbol list does not change)
 int WeightingRec::set(const mbd_weighting* r, int device, int P_, int cap_, int N) {
+  (void)N;
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipDeviceSynchronize());  // (a step in flight may still write the log)
   has = false;
@@ -2281,11 +2285,6 @@ int WeightingRec::set(const mbd_weighting* r, int device, int P_, int cap_, int 
   HIP_TRY(d_temp.grow((size_t)P * cap));
   HIP_TRY(d_ess.grow((size_t)P * cap));
   HIP_TRY(d_kept.grow((size_t)P * cap));
-  // (the attribute belongs to THIS unit's copy of the static kernel, the one a plan launches.  A sweep launches mbd_sweep.hip's copy,
-  // which never needs it: mbd_sweep_create refuses plans whose N weights outgrow the default 48 KB window, so for a sweep the test
-  // below is always false)
-  if ((size_t)N * sizeof(float) > 48 * 1024 && N <= kLdsN)
-    HIP_TRY(hipFuncSetAttribute((const void*)weigh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
   rec = weigh_rec_of(r);
   has = true;
   return MBD_OK;
@@ -2314,6 +2313,11 @@ extern "C" int mbd_plan_set_weighting(mbd_plan* p, const mbd_weighting* rec) {
   if (rec && p->cfg.enable_demo)
     return fail(MBD_ERR_UNSUPPORTED, "weighting record: enable_demo=1: the demo blend standardises twice, an ESS target is not defined there");
   if (rec && p->togo.has) return refuse_beside_togo("weighting record");
+  // weigh_kernel's logp0 window, as mbd_plan_create raises score_kernel's (a sweep never needs it: mbd_sweep_create refuses N > 12288)
+  if (rec && (size_t)p->cfg.Nsample * sizeof(float) > 48 * 1024 && p->cfg.Nsample <= kLdsN) {
+    HIP_TRY(hipSetDevice(p->env->device));
+    HIP_TRY(hipFuncSetAttribute((const void*)weigh_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024));
+  }
   return p->wt.set(rec, p->env->device, 1, p->cfg.Ndiffuse - 1, p->cfg.Nsample);
 }
 

@@ -1,81 +1,14 @@
 // mbd_step_kernels.h — the kernels of a diffusion step around the rollout (mbd_planner.py:103-135): sampling / noise,
-// demo log-densities, score (standardise, demo blend, softmax), weighted mean + score update, their batched forms for sweeps,
-// the path-integral update rules, and the car2d rollout.  Non-template and `static`: each host unit (mbd_env / mbd_plan /
-// mbd_sweep .hip) compiles the ones it launches.  The rollout kernels and what they share live in mbd_kernels.h.
+// score (standardise, demo blend, softmax), weighted mean + score update, their batched forms for sweeps, the records' kernels,
+// the path-integral update rules.  Non-template and `static`, so every unit that sees them emits them: only mbd_plan.hip and
+// mbd_sweep.hip include this header (mbd_env.hip's own kernels are in mbd_env_kernels.h).  The rollout kernels and what they
+// share live in mbd_kernels.h.
 #pragma once
 
 #include "mbd_kernels.h"
+#include "mbd_step_args.h"
 
 namespace mbd {
-
-// ---- car2d (mbd/envs/car2d.py): one candidate per lane -------------------------------------------------
-struct Car2dParams {
-  const float* q0;  // [3]
-  const float* us;  // [B][H][2]
-  float* rewss;     // [B][H] or nullptr
-  float* rews;      // [B] or nullptr
-  float* qs;        // [B][H][3] or nullptr
-  float* q_final;   // [B][3] or nullptr
-  int B, H;
-};
-
-__device__ __forceinline__ void car_dyn(const float x[3], float u0, float u1, float dx[3]) {
-  float sn, cs;
-  sincos_(x[2], &sn, &cs);
-  dx[0] = u1 * sn * 3.0f;
-  dx[1] = u1 * cs * 3.0f;
-  dx[2] = u0 * 3.14159274101257324f / 3.0f * 2.0f;
-}
-__device__ __forceinline__ float car_reward(const float q[3]) {
-  float dx = q[0] - 0.5f, dy = q[1] - 0.0f;
-  // (sqrt_floor is the correctly rounded square root from 1e-30 up — exhaustive, probe_short — and its floor of 1e-15
-  // below that leaves the reward at exactly 1, like the true root)
-  float d = sqrt_floor(dx * dx + dy * dy);
-  d = fclip(d, 0.0f, 0.2f);
-  float t = d / 0.2f;
-  return 1.0f - t * t;
-}
-
-static __global__ __launch_bounds__(64) void car2d_rollout_kernel(Car2dParams P) {
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= P.B) return;
-  // obstacle centres (car2d.py:48-63): python float64 products cast to f32
-  const float cx[11] = {(float)(0.3 * -3), (float)(0.3 * -2), (float)(0.3 * -1), 0.0f, 0.0f, 0.0f, 0.0f,
-                        (float)(0.3 * -3), (float)(0.3 * -2), (float)(0.3 * -1), 0.0f};
-  const float cy[11] = {(float)(0.3 * 2), (float)(0.3 * 2), (float)(0.3 * 2), (float)(0.3 * 2),
-                        (float)(0.3 * 1), 0.0f, (float)(0.3 * -1), (float)(0.3 * -2), (float)(0.3 * -2),
-                        (float)(0.3 * -2), (float)(0.3 * -2)};
-  const float dt = (float)0.1, dt2 = (float)(0.1 / 2), dt6 = (float)(0.1 / 6);
-  float q[3] = {P.q0[0], P.q0[1], P.q0[2]};
-  float sum = 0.0f;
-  for (int t = 0; t < P.H; ++t) {
-    const float* u = P.us + ((size_t)b * P.H + t) * 2;
-    float a0 = fclip(u[0], -1.0f, 1.0f), a1 = fclip(u[1], -1.0f, 1.0f);
-    float k1[3], k2[3], k3[3], k4[3], x[3], qn[3];
-    car_dyn(q, a0, a1, k1);
-    for (int i = 0; i < 3; ++i) x[i] = q[i] + dt2 * k1[i];
-    car_dyn(x, a0, a1, k2);
-    for (int i = 0; i < 3; ++i) x[i] = q[i] + dt2 * k2[i];
-    car_dyn(x, a0, a1, k3);
-    for (int i = 0; i < 3; ++i) x[i] = q[i] + dt * k3[i];
-    car_dyn(x, a0, a1, k4);
-    for (int i = 0; i < 3; ++i) qn[i] = q[i] + dt6 * (k1[i] + 2.0f * k2[i] + 2.0f * k3[i] + k4[i]);
-    bool collide = false;
-    for (int i = 0; i < 11; ++i) {
-      float dx = qn[0] - cx[i], dy = qn[1] - cy[i];
-      // sqrtf(x) < 0.3f  <=>  x < 0x1.70a3d8p-4 (0.09000000357627869): the correctly rounded square root is monotonic and
-      // that is the smallest float32 whose root rounds to >= 0.3f (tests/test_spec_math.py checks the window around it)
-      collide = collide || (dx * dx + dy * dy < 0.09000000357627869f);
-    }
-    for (int i = 0; i < 3; ++i) q[i] = collide ? q[i] : qn[i];
-    float rew = car_reward(q);
-    sum = sum + rew;
-    if (P.rewss) P.rewss[(size_t)b * P.H + t] = rew;
-    if (P.qs) { float* o = P.qs + ((size_t)b * P.H + t) * 3; o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; }
-  }
-  if (P.rews) P.rews[b] = sum / (float)P.H;
-  if (P.q_final) { P.q_final[b * 3] = q[0]; P.q_final[b * 3 + 1] = q[1]; P.q_final[b * 3 + 2] = q[2]; }
-}
 
 // ---- A1: sampling (mbd_planner.py:103-106) -------------------------------------------------------------
 // Y0s[e] for the flat elements [e_begin, e_begin + e_count) of the global [N][HNu] tensor (a rank's own rows
@@ -497,63 +430,6 @@ inline unsigned demo_blocks(long long items) {
   return (unsigned)(b < 1 ? 1 : (b < 1024 ? b : 1024));
 }
 
-// ---- A5: demo log-densities ------------------------------------------------------------------------------
-// HumanoidTrack.eval_xref_logpd (humanoidtrack.py:98-106): xpos [B][H][K][3], xref [K][H][3].  One workgroup per
-// candidate: its K*H terms ((clip(|x - xref|, 0, .5) / .5)^2, the candidate's 3 K H floats are contiguous) are formed in
-// parallel and parked in LDS; thread k then adds link k's H terms in t order (S_k), thread 0 the K sums in link order —
-// the contract's order since round 6 (rounds 1-5: one chain over all K H terms), chosen so that the rollout kernels can
-// accumulate S_k on the tracked link's lane as the control steps go by (RolloutParams::lp) and produce the same bits
-// without this launch; the standalone entry (mbd_env_xref_logpd) and the instantiations that do not accumulate use this kernel.
-// The clamp is fclip_nan: a NaN distance (a diverged candidate's positions) stays a NaN, as the reference's jnp.clip leaves it,
-// here, in logpd_car2d_kernel and in the rollouts' accumulation alike (v_med3_f32 would turn it into a term of 0).
-constexpr int kLogpdThreads = 256, kLogpdMaxTerms = MBD_MAX_TRACK * 64;
-static __global__ __launch_bounds__(kLogpdThreads) void logpd_track_kernel(const float* __restrict__ xpos,
-                                                                    const float* __restrict__ xref, int B, int H, int K,
-                                                                    float* __restrict__ lp) {
-  __shared__ float term[kLogpdMaxTerms];
-  const int b = blockIdx.x;
-  const int n = K * H;
-  for (int i = threadIdx.x; i < n; i += kLogpdThreads) {
-    const int t = i / K, k = i - t * K;  // (xpos order: t outer, k inner)
-    const float* a = xpos + ((size_t)b * n + i) * 3;
-    const float* c = xref + ((size_t)k * H + t) * 3;
-    float ex = a[0] - c[0], ey = a[1] - c[1], ez = a[2] - c[2];
-    float d = fsqrt(ex * ex + ey * ey + ez * ez);
-    d = fclip_nan(d, 0.0f, 0.5f);
-    float s = d / 0.5f;
-    term[k * H + t] = s * s;
-  }
-  __shared__ float part[MBD_MAX_TRACK];
-  __syncthreads();
-  if ((int)threadIdx.x < K) {
-    float a = 0.0f;
-    for (int t = 0; t < H; ++t) a = a + term[threadIdx.x * H + t];
-    part[threadIdx.x] = a;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  float acc = part[0];
-  for (int k = 1; k < K; ++k) acc = acc + part[k];
-  lp[b] = 0.0f - acc / (float)n;
-}
-// Car2d.eval_xref_logpd (car2d.py:95-102): qs [B][H][3], xref [H][2]
-static __global__ __launch_bounds__(64) void logpd_car2d_kernel(const float* __restrict__ qs,
-                                                         const float* __restrict__ xref, int B, int H,
-                                                         float* __restrict__ lp) {
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  float acc = 0.0f;
-  for (int t = 0; t < H; ++t) {
-    const float* a = qs + ((size_t)b * H + t) * 3;
-    float ex = a[0] - xref[2 * t], ey = a[1] - xref[2 * t + 1];
-    float d = fsqrt(ex * ex + ey * ey);
-    d = fclip_nan(d, 0.0f, 0.5f);
-    float s = d / 0.5f;
-    acc = acc + s * s;
-  }
-  lp[b] = 0.0f - acc / (float)H;
-}
-
 // ---- A4-A6: standardise, demo blend, softmax -> weights[N] (mbd_planner.py:110-127) -------------------
 // The canonical one-wavefront reduction of the numerical contract: lane j accumulates the elements
 // i = j, j+64, ... in increasing i, then a xor-butterfly over the 64 lanes.
@@ -890,18 +766,6 @@ static __global__ __launch_bounds__(kScoreThreads) void score_kernel(const float
 // between the block reductions, mbd_debug_weighting_host runs them on the CPU between restatements of those reductions over the
 // 1024 virtual threads.  f32, every operation rounded (the build's -ffp-contract=off); the one fused operation is the squared
 // deviation's accumulation, score_block's own, which the bits of a step without a record oblige.
-struct WeighRec {
-  int reject;  // drop NaN and +-inf rewards
-  float ess_frac, temp_min, temp_max;
-  int iters;
-};
-// where a step's log entry goes: plan 0's slot of each of the three logs, plan k's `stride` entries further
-struct WeighLog {
-  float* temp;
-  float* ess;
-  int* kept;
-  long long stride;
-};
 // decided on the bits (exponent all ones), not by a compare a fast-math flag could fold
 MBD_HD bool weigh_keep(float r, int reject) { return !reject || (__builtin_bit_cast(uint32_t, r) & 0x7f800000u) != 0x7f800000u; }
 MBD_HD float weigh_dev(float part, float r, float mean) {
@@ -1247,14 +1111,6 @@ static __global__ __launch_bounds__(kKnotThreads) void knot_noise_batch_kernel(S
 }
 
 // ---- the plant of a receding-horizon episode (include/mbd_hip.h mbd_mpc_plant): disturbances drawn and applied on the device ----
-// What a tick's disturbance launches need of every episode (blockIdx.y = episode; a single plan is episode 0), passed like
-// SweepKeys: d_t of the disturbance key chain, the action-noise std, and the kick std — which the host sets to 0 in the
-// ticks that carry no kick, so that it doubles as the kick kernels' mask.  has[k] == 0: the episode has no record.
-struct SweepPlant {
-  uint32_t k[32][2];
-  float act_std[32], kick_std[32];
-  unsigned char has[32];
-};
 // One workgroup per episode, behind the tick's last weighted mean: eps = normal(d_t, (EN + 3,)) by noise_fill (the counters
 // and layouts of every other normal of the library: bit-exact to the checker's; never shaped — a noise shape is the
 // planner's exploration, the disturbances are the world's), then the executed rows
@@ -1446,7 +1302,6 @@ static __global__ __launch_bounds__(64) void cem_mean_kernel(const int* __restri
   for (int k = 0; k < K; ++k) acc = acc + Y0s[(size_t)idx[k] * HNu + e];
   mu_out[e] = acc / (float)K;
 }
-
 
 // ---- the weigh kernel of a weighting record (the arithmetic: weigh_keep ... weigh_select above).  Last in this header and compiled
 // only by the units that launch it (MBD_WEIGH_KERNEL: mbd_plan.hip, mbd_sweep.hip): a static kernel is emitted by every unit that

@@ -6,6 +6,7 @@
 #define MBD_TOGO_KERNEL 1
 #define MBD_SWEEP_KERNEL 1  // (their forms over P plans: this unit's alone)
 #include "mbd_internal.h"
+#include "mbd_step_kernels.h"
 #include "../../include/mbd_hip_debug.h"
 
 namespace {
