@@ -189,6 +189,15 @@ int mbd_debug_sweep_togo_step(int P, const float* temps, const float* cand, cons
                               int N, int H, int Nu, int block, int min_tail, int lazy, float sigma, int std_guard, float alpha_i,
                               float alpha_bar_i, float alpha_bar_im1, int literal, float* ybar_out, float* R_out, float* W_out,
                               float* rew_mean_out);
+/* The reader of the device ring logs alone on the DEVICE (a pick record's ticks, an adapt and an elite record's steps): HOST ring
+ * [cap][width] is uploaded as a log that has seen `count` entries, entry j at slot j % cap, and the function every peek calls reads
+ * the most recent min(n, count, cap) of them into HOST out [min(n, count, cap)][width], oldest first — the two copies, the advance
+ * of out between them and the scaling by width, wrapped or not.  out is filled with all-ones bits first (give it room for one
+ * element where nothing is read).  The _i32 entry is the instantiation the integer logs use.  NULL arguments, width outside
+ * [1, 16], cap outside [1, 65536], count < 0 or n < 0 -> MBD_ERR_INVALID before any device access; no device ->
+ * MBD_ERR_NO_DEVICE. */
+int mbd_debug_ring_read(const float* ring, int width, long long cap, long long count, long long n, float* out);
+int mbd_debug_ring_read_i32(const int32_t* ring, int width, long long cap, long long count, long long n, int32_t* out);
 #ifdef __cplusplus
 }
 #endif

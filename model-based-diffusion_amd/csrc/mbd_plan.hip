@@ -2455,6 +2455,28 @@ extern "C" int mbd_debug_pick_best(const float* rews, int P, int N, int32_t* bes
   return MBD_OK;
 }
 
+// include/mbd_hip_debug.h: ring_read on the device over a caller-given ring, both instantiations the logs use
+template <typename T>
+static int debug_ring_read(const T* ring, int width, long long cap, long long count, long long n, T* out) {
+  if (!ring || !out) return fail(MBD_ERR_INVALID, "ring_read: NULL argument");
+  if (width < 1 || width > 16 || cap < 1 || cap > kLogCap || count < 0 || n < 0)
+    return fail(MBD_ERR_INVALID, "ring_read: width=%d cap=%lld count=%lld n=%lld", width, cap, count, n);
+  if (device_count_quiet() < 1) return fail(MBD_ERR_NO_DEVICE, "no HIP device: this library has no CPU fallback");
+  DevBuf<T> d_ring;
+  HIP_TRY(d_ring.upload(ring, (size_t)cap * width));
+  const long long m = std::min(std::min(n, count), cap);
+  memset(out, 0xff, sizeof(T) * (size_t)m * width);
+  return ring_read<T>(d_ring.get(), width, count, cap, n, out);
+}
+
+extern "C" int mbd_debug_ring_read(const float* ring, int width, long long cap, long long count, long long n, float* out) {
+  return debug_ring_read<float>(ring, width, cap, count, n, out);
+}
+
+extern "C" int mbd_debug_ring_read_i32(const int32_t* ring, int width, long long cap, long long count, long long n, int32_t* out) {
+  return debug_ring_read<int32_t>(ring, width, cap, count, n, out);
+}
+
 // ---- the adapt record (include/mbd_hip.h mbd_adapt) ---------------------------------------------------------------------------
 // the refusals the record alone decides against the handle's update_method and enable_demo, in the header's order, each naming the
 // field — host arithmetic, before any device access

@@ -954,6 +954,26 @@ def debug_pick_best(rews) -> np.ndarray:
     return int(best[0]) if r.ndim == 1 else best
 
 
+RING_READ_ARGTYPES = [_vp, _i, C.c_longlong, C.c_longlong, C.c_longlong, _vp]
+
+
+def debug_ring_read(ring, count: int, n: int) -> np.ndarray:
+    """include/mbd_hip_debug.h: the device logs' reader alone on the GPU.  ``ring`` [cap, width] float32 or int32 (the dtype chooses
+    the instantiation), a log that has seen ``count`` entries; returns the most recent min(n, count, cap) of them [m, width],
+    oldest first.  What the reader did not write keeps all bits set."""
+    lib = load()
+    ring = np.ascontiguousarray(ring)
+    if ring.dtype not in (np.float32, np.int32) or ring.ndim != 2:
+        raise ValueError(f"ring of dtype {ring.dtype} and shape {ring.shape}: [cap, width] float32 or int32")
+    fn = lib.mbd_debug_ring_read if ring.dtype == np.float32 else lib.mbd_debug_ring_read_i32
+    fn.argtypes = RING_READ_ARGTYPES
+    cap, width = ring.shape
+    m = max(min(int(n), int(count), cap), 0)
+    out = np.zeros((max(m, 1), width), ring.dtype)  # (room for one element where nothing is read: the entry refuses NULL)
+    check(fn(np_ptr(ring), width, cap, int(count), int(n), np_ptr(out)))
+    return out[:m]
+
+
 SWEEP_UPDATE_ARGTYPES = [_vp, _i] + [_vp] * 10
 
 
