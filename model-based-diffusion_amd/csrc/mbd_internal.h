@@ -1,16 +1,17 @@
 // mbd_internal.h — what the translation units of libmbd_hip.so's host side share (NOT part of the boundary: the C ABI is
 // include/mbd_hip.h): the owners of runtime resources, the env handle, error reporting, the test levers, what plans and
-// sweeps do alike — every record both handles take, once: the struct, its check_*, set and peek; the launches of a record whose
-// single and batch kernels live in different units (elites, to-go) are free functions of each unit over the shared struct — and
-// the functions one unit defines for the others.  (A handle only its own unit uses is defined there: the adapt record of a plan,
-// in the other records' form, is mbd_plan.hip's.)
-// Units: mbd_env.hip (library, levers, envs, the rollout launch), mbd_plan.hip (plans: one reverse-diffusion step and the
-// loops over it, every record's members), mbd_sweep.hip (sweeps: several plans per launch), mbd_exchange.hip (the in-library
-// exchange), mbd_debug_math.hip (mbd_math.h over arrays); mbd_pk2.hip, mbd_planar.hip and mbd_hot3d.hip hold rollout
+// sweeps do alike — every record, once: the struct, its check_*, set and peek (the adapt record too, which only plans hold); the
+// launches of a record whose single and batch kernels are step kernels (elites, to-go) are free functions of each handle unit over
+// the shared struct — and the functions one unit defines for the others.
+// Units: mbd_env.hip (library, levers, envs, the rollout launch), mbd_records.hip (every record's members, the check_* family and
+// the refusals plans and sweeps share, the mbd_debug_* entries that launch record kernels or none), mbd_plan.hip (plans: one
+// reverse-diffusion step and the loops over it), mbd_sweep.hip (sweeps: several plans per launch), mbd_exchange.hip (the
+// in-library exchange), mbd_debug_math.hip (mbd_math.h over arrays); mbd_pk2.hip, mbd_planar.hip and mbd_hot3d.hip hold rollout
 // instantiations only.  mbd_ring.h: the ring logs' arithmetic, which includes nothing and is tested on the host alone.
-// No step kernel is visible from here: a static kernel is emitted by every unit that sees it, so a unit that launches step kernels
-// includes their header itself (mbd_env.hip: mbd_env_kernels.h; mbd_plan.hip, mbd_sweep.hip: mbd_step_kernels.h), and this header
-// takes the three argument structs its records keep by value from mbd_step_args.h.
+// No kernel is visible from here: a static kernel is emitted by every unit that sees it, so a unit that launches kernels includes
+// their header itself (mbd_env.hip: mbd_env_kernels.h; mbd_records.hip: mbd_record_kernels.h; mbd_plan.hip, mbd_sweep.hip:
+// mbd_step_kernels.h).  This header takes the argument structs its records keep by value from mbd_step_args.h, and the constants
+// and host-and-device functions the kernel headers and the host code share from mbd_step_device.h, which defines no kernel.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,6 +36,7 @@
 #include "mbd_launch.h"
 #include "mbd_ring.h"
 #include "mbd_step_args.h"
+#include "mbd_step_device.h"
 
 using namespace mbd;
 
@@ -369,7 +371,7 @@ int launch_rollout(mbd_env* env, const float* d_state0, const float* d_us, int B
 // whether the device is a whole 8-XCD part (the premise of the XCD-pinned launch forms)
 bool device_has_eight_xcds(const mbd_env* env);
 int launch_logpd(const mbd_env* e, const float* d_xpos, int B, int H, float* d_out, hipStream_t s, const float* d_xref = nullptr);
-// ---- defined in mbd_plan.hip -----------------------------------------------------------------------------------------
+// ---- defined in mbd_records.hip (plant_tick_draw, at the end: mbd_plan.hip) ------------------------------------------
 // noise schedule (mbd_planner.py:84-87)
 void host_schedule(float beta0, float betaT, int Nd, std::vector<float>& alphas, std::vector<float>& alphas_bar,
                    std::vector<float>& sigmas);
@@ -518,7 +520,7 @@ int check_objective(const mbd_objective* rec, int Hsample, int action_size, floa
 // checks and check_value (nullptr clears); copies the net onto the device, every layer transposed, and makes room for the final
 // states and the V of max_rows rows (a plan: its shard; a sweep: P N) and of the 3 P slots of a pick record.  final(): what a
 // rollout launch is handed as d_state_final — nullptr without a record, so that a launch without one is what it was.  launch: the
-// kernel over B rows of d_fin, d_rews rewritten in place, V into d_v_keep (defined in mbd_plan.hip, which alone compiles the kernel);
+// kernel over B rows of d_fin, d_rews rewritten in place, V into d_v_keep;
 // launch_step: the same over the step's own buffers, what peek shows.
 struct ValueRec {
   bool has = false, stepped = false;
@@ -548,8 +550,8 @@ int check_value(const mbd_value* rec, int state_size, bool rigid_body);
 // arithmetic, before any device access.  set: behind the handle's NULL, session, env, demo, shard and record checks and check_zones
 // (nullptr clears); makes room for the positions, pen and clr of max_rows rows of H steps and K tracks.  update: the table alone —
 // host state, since the table travels as kernel arguments.  xpos(): what a planning rollout is handed as d_xpos — nullptr without
-// a record, so that a launch without one is what it was.  launch: the kernel over B rows of d_x (defined in mbd_plan.hip, which alone
-// compiles it); launch_step: the same over the step's own buffers, what peek shows.  An episode logs its executed steps: start makes
+// a record, so that a launch without one is what it was.  launch: the kernel over B rows of d_x; launch_step: the same over the
+// step's own buffers, what peek shows.  An episode logs its executed steps: start makes
 // room for the positions [T P E][K][3] and the log [T P E] twice, log runs the kernel over one tick's executed rows of all P episodes.
 struct ZoneRec {
   bool has = false, stepped = false;
@@ -580,7 +582,7 @@ struct ZoneRec {
 };
 int check_zones(const mbd_zones* rec, int n_track);
 // the refusals of a zone record the handle's env and config decide, behind check_zones (handle: "plan" / "sweep"); and the refusal of
-// a record beside a zone record (mbd_plan.hip; who: how the refused record's messages begin)
+// a record beside a zone record (who: how the refused record's messages begin)
 int check_zones_handle(const mbd_env* env, const mbd_plan_config& c, const char* handle);
 int refuse_beside_zones(const char* who, const char* handle = "plan");
 // The weighting record of a plan or a sweep (include/mbd_hip.h mbd_weighting) as the handle keeps it.  check_weighting: the refusals
@@ -605,7 +607,7 @@ struct WeightingRec {
            const char* what) const;
 };
 int check_weighting(const mbd_weighting* rec);
-// the refusal of a record beside a to-go record (mbd_plan.hip; who: how the refused record's messages begin, handle: "plan" / "sweep")
+// the refusal of a record beside a to-go record (who: how the refused record's messages begin, handle: "plan" / "sweep")
 int refuse_beside_togo(const char* who, const char* handle = "plan");
 // The elite record of a plan or of all the plans of a sweep (include/mbd_hip.h mbd_elites) as the handle keeps it, with what the two
 // handles do alike.  The state of P plans (a plan: P = 1): the elites' rows E [P][rows][HNu], their returns R and source indices src
@@ -638,6 +640,19 @@ struct EliteRec {
                       int32_t* log_count, int32_t* log_kept, float* log_top, int capacity, int* n_log_out, const char* what) const;
 };
 MBD_HIDDEN int check_elites(const mbd_elites* rec, int Nsample, int update_method, int enable_demo);
+// the refusals the mbd_debug_elites_* entries share (mbd_records.hip: the host entry; mbd_plan.hip: the two that launch step kernels)
+MBD_HIDDEN inline int check_elites_args(const char* what, const float* cand, int N, int HNu, const float* ybar, float sigma, int lazy, int n_elites,
+                             int nominal, const float* E_in, int count_in) {
+  if (!cand || !ybar) return fail(MBD_ERR_INVALID, "%s: NULL argument", what);
+  if (N < 1 || HNu < 1 || (uint64_t)N * (uint64_t)HNu > (1ull << 26)) return fail(MBD_ERR_INVALID, "%s: N=%d HNu=%d", what, N, HNu);
+  if (n_elites < 0 || n_elites > kEliteMax) return fail(MBD_ERR_INVALID, "%s: n_elites=%d outside [0, %d]", what, n_elites, kEliteMax);
+  if (nominal != 0 && nominal != 1) return fail(MBD_ERR_INVALID, "%s: nominal=%d: 0 or 1", what, nominal);
+  if (n_elites + nominal >= N) return fail(MBD_ERR_INVALID, "%s: n_elites=%d + nominal=%d must lie below N=%d", what, n_elites, nominal, N);
+  if (count_in < 0 || count_in > n_elites) return fail(MBD_ERR_INVALID, "%s: count=%d outside [0, n_elites=%d]", what, count_in, n_elites);
+  if (count_in > 0 && !E_in) return fail(MBD_ERR_INVALID, "%s: count=%d without elites", what, count_in);
+  if (lazy && !(sigma > 0.0f)) return fail(MBD_ERR_INVALID, "%s: sigma=%g: a lazy plan's sigma is > 0", what, (double)sigma);
+  return MBD_OK;
+}
 // The to-go record of a plan or of all the plans of a sweep (include/mbd_hip.h mbd_togo) as the handle keeps it: the record, the
 // layout it gives at the handle's Hsample — G groups, group j's first row starts[j] = j block —, and the last step's returns and
 // weights R, W [P][G][N] (row 0 of a plan's W is never written: group 0's weights are the plan's d_weights).  check_togo: the refusals
@@ -656,13 +671,16 @@ struct TogoRec {
   MBD_HIDDEN int peek(const mbd_env* env, int k, int N, const float* d_weights, int32_t* starts_out, float* R_out, float* W_out,
                       int32_t* n_groups_out, const char* what) const;
 };
+constexpr int kTogoMaxN = 12288;  // the N weights of a group in the default 48 KB LDS window
 MBD_HIDDEN int check_togo(const mbd_togo* rec, int Hsample, int Nsample, int update_method, int enable_demo);
+// the refusals mbd_debug_togo_host (mbd_records.hip) and mbd_debug_togo_step (mbd_plan.hip: it launches step kernels) share
+MBD_HIDDEN int check_togo_args(const char* what, int N, int H, int block, int min_tail);
 // The pick record of a plan or a sweep (include/mbd_hip.h mbd_mpc_pick) as the handle keeps it, with what the two handles do alike.
 // check_mpc_pick: the refusals the record alone decides, each naming the field, before any device access.  set: behind the handle's
 // NULL, session, enable_demo and ensemble checks (nullptr clears); makes room for P plans' slots [P][3][HNu], their returns and
 // per-step rewards.  start: in front of an episode's or a session's first tick — room for the log, a ring of min(n_ticks,
 // kLogCap) entries per plan, entry of tick j at j % cap — and no tick served.  tick: the three launches (four with an objective
-// record) behind a tick's last update kernel, on stream s (defined in mbd_plan.hip, which alone compiles the kernels); what it reads
+// record) behind a tick's last update kernel, on stream s; what it reads
 // is PickTick, and it leaves P_t where M_t lay.  peek: the most recent min(count, capacity, cap) ticks of plan k, oldest first.
 struct PickTick {
   const float* state;   // [P][S] where the tick planned from
@@ -692,6 +710,46 @@ struct PickRec {
            const char* what) const;
 };
 int check_mpc_pick(const mbd_mpc_pick* rec);
+// A step's candidates as the launches behind its sampler are handed them (an adapt record's update, an elite record's injection
+// and selection): cand [N][HNu], or their normals (lazy) with the sigma_i and Ybar_i the step sampled with — an mppi plan's sigma
+// from the carried device scalar, which its sampler read (d_sigma, nullptr: the host value).
+struct StepCand {
+  const float* cand;
+  int N, HNu, lazy;
+  float sigma;
+  const float* d_sigma;
+  const float* ybar_i;
+};
+// The plan-only record, in the form of the others: set behind the handle's refusals (nullptr clears), the launches a step or
+// a tick makes — each returns at once without a record, and the mbd_debug_* entries run the same members on a scratch record —, and
+// peek.  All zero: no record (a zeroed stand-in handle has none).
+// The adapt record (include/mbd_hip.h mbd_adapt): the rule, the table a and G = a * g [HNu] on the device — G is what the samplers
+// take as their shape while the record is in force (noise_spec) —, the scratch the update's two kernels hand var and s through, and
+// the device log, a ring of kLogCap entries (count: steps since the log began).  g_cur: the caller's shape G was last formed under
+// (the plan's d_shape or nullptr), which the update's second kernel forms G' under again.
+struct AdaptRec {
+  bool has = false;
+  AdaptRule rule{};
+  int carry = 0;
+  long long count = 0;
+  const float* g_cur = nullptr;
+  DevBuf<float> d_a, d_G, d_buf, d_log_S;
+  DevBuf<int> d_log_skipped;
+  // g: the caller's shape in force outside warm ticks; the table is all ones afterwards (one launch on s, waited for)
+  MBD_HIDDEN int set(const mbd_adapt* rec, int HNu, const float* g, const mbd_env* env, hipStream_t s);
+  // The table at the start of a run or a tick, or under a new shape: shift < 0: a = ones, otherwise a shifted `shift` elements
+  // forward (0: as it is); G = a * g under the caller's shape g now in force, which the updates that follow keep forming G under.
+  // ONE launch.
+  MBD_HIDDEN int table(int shift, const float* g, int HNu, hipStream_t s);
+  // behind a step's update kernel, on the step's stream, from the step's weights d_w [N]: var into d_buf, then S, a', G' and the
+  // log entry.  TWO launches; the weights are staged in LDS while they fit the default 48 KB window, read from memory beyond
+  MBD_HIDDEN int update(const float* d_w, const StepCand& c, hipStream_t s);
+  // HOST a_out [HNu] and the most recent min(count, capacity, kLogCap) log entries, oldest first
+  MBD_HIDDEN int peek(const mbd_env* env, int HNu, float* a_out, float* ratio_out, int32_t* skipped_out, int capacity, int* count_out) const;
+};
+// the refusals the record alone decides against the handle's update_method and enable_demo, in the header's order, each naming the
+// field — host arithmetic, before any device access
+MBD_HIDDEN int check_adapt(const mbd_adapt* rec, int update_method, int enable_demo);
 // One tick of a plant's disturbance chain, dk, d_t = split(dk): advances dk, fills slot k of sp with d_t and the record's
 // deviations — the kick's only in the ticks that end with one — and says whether tick t does
 bool plant_tick_draw(const mbd_mpc_plant& pr, int prng_impl, int t, uint32_t dk[2], SweepPlant& sp, int k);
